@@ -8,13 +8,18 @@ bucket reduction -> one Jacobian point; with N GPUs the global MSM has N * 2^20 
 point-chunk, and each step ends with the all-gather of N 96-byte partials (RCCL over xGMI) and a
 local point-sum.  value = points processed by all ranks / max-over-ranks wall time.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel (bucket accumulation) against the
-HBM roofline with its algorithmic bytes (96 B per (base, scalar) pair) over its average
-duration measured with HIP events on the library's stream.  `cpu_baseline` times the plain-C CPU
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times exactly K steps once and prints
+it; --dump-outputs DIR writes the point the last timed step computed (DIR/msm_result.npy).  The
+inputs are seeded, so two builds given the same arguments can be compared output for output.
+--full adds everything else: five timed regions (the median reported), stage times, the sub-records
+for other sizes, configurations and prove_step, and the checks against the CPU restatement.
+`roofline` prices the dominant kernel (bucket accumulation) against the HBM roofline with its
+algorithmic bytes (96 B per (base, scalar) pair) over its average duration measured
+with HIP events on the library's stream.  `cpu_baseline` times the plain-C CPU
 restatement (oracle/pasta_ref.c, kind "port") on this box's host cores on the same inputs and checks
 the GPU result against it bit-for-bit (only this leg touches oracle/).
 """
@@ -72,7 +77,10 @@ def flat_summary(line, failures=()):
         if k_.startswith("strong_2_") and isinstance(v_, dict):
             s["msm_sharded_" + k_[7:] + "_gpoints_per_s"] = _r(v_.get("value"))
     s["cpu_msm_gpoints_per_s"] = _r((line.get("cpu_baseline") or {}).get("value"), 6)
-    s["parity"] = "bit-exact vs oracle/ in this run: %s; unpinned vs nova-snark" % (not failures)
+    if line.get("cpu_baseline") or line.get("self_check") or failures:
+        s["parity"] = "bit-exact vs oracle/ in this run: %s; unpinned vs nova-snark" % (not failures)
+    else:
+        s["parity"] = "not checked in this run (bench.py --full checks it)"
     return s
 
 
@@ -163,9 +171,17 @@ def contract_line(full):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100, help="timed MSM steps (100 x 1.3 ms: a region long enough for +-1 %)")
+    ap.add_argument("--steps", type=int, default=100, help="timed MSM steps (100 x 1.3 ms: a region long enough for +-1 %%)")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--regions", type=int, default=5, help="the timed region of `steps` steps is run this many times; the median region is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg besides the headline: stage times and roofline, box fingerprints, the strong-scaling and replica "
+                         "sub-records, msm_sizes, prove_step, the CPU baselines and the parity checks.  Without it a run sets up, warms "
+                         "up, times `steps` steps once and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/msm_result.npy: the MSM's point as canonical "
+                         "affine x and y (not Montgomery), little-endian 32-bit limbs as float64, shape (2, 8); the identity is all zeros")
+    ap.add_argument("--regions", type=int, default=0, help="the timed region of `steps` steps is run this many times; the median region is "
+                    "reported (0 = one region, five with --full)")
     ap.add_argument("--no-sizes", action="store_true", help="skip the msm_sizes leg (2^20, 2^22, 2^24 one at a time; variable-base 2^20)")
     ap.add_argument("--settle", type=int, default=40, help="untimed MSM steps during set-up, before the warm-up steps (clock ramp, workspaces)")
     ap.add_argument("--log2n", type=int, default=20, help="points per GPU (2^k)")
@@ -182,22 +198,22 @@ def parse():
                     help="take the N > 1 code path (process group, all-gather on the step's stream) with a world of one")
     ap.add_argument("--strong-log2n", type=int, default=24,
                     help="BASELINE config 4: one MSM of 2^k points TOTAL, sharded over the ranks (strong scaling), as a sub-record; "
-                         "runs for N > 1 (and for N = 1 with --rehearse-collective or --strong); 0 = skip")
-    ap.add_argument("--strong", action="store_true", help="run the strong-scaling sub-record on one GPU too")
+                         "runs with --full for N > 1 (and for N = 1 with --rehearse-collective or --strong); 0 = skip")
+    ap.add_argument("--strong", action="store_true", help="with --full, run the strong-scaling sub-record on one GPU too")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-prove", action="store_true", help="skip the prove_step leg (BASELINE config 3)")
     ap.add_argument("--prove-log2t", type=int, default=16, help="MinRoot iterations per prove_step (2^k)")
     ap.add_argument("--prove-chains", type=int, default=2,
                     help="also report the aggregate rate of this many independent chains proven concurrently (1 = skip)")
     ap.add_argument("--prove-steps", type=int, default=52, help="1 base case + 1 warm-up fold + timed steady-state folds (50: a timed repeat opens with an empty "
-                    "lookahead and closes with a drain -- about 0.5 ms whatever its length, 2.4 % of 24 steps, 1.2 % of 50; tools/gpu_prove_modes.py: 100 steps)")
+                    "lookahead and closes with a drain -- about 0.5 ms whatever its length, 2.4 %% of 24 steps, 1.2 %% of 50; tools/gpu_prove_modes.py: 100 steps)")
     ap.add_argument("--prove-repeats", type=int, default=7, help="the steady state is timed this many times (a fresh proof each): 7 x 24 = 168 timed steps; the median repeat is reported (a host stall of a few ms -- other tenants of the node -- lands in one or two)")
     ap.add_argument("--digit-budget-gib", type=int, default=20,
                     help="HBM the prove_step leg lets the digit tables of a parameter set take (vdf_nova_tuning.digit_budget_bytes).  The "
                          "default is the LIBRARY's default, 20 GiB (10-bit tables, 19 GB at t = 2^16): the headline is what a host gets "
-                         "without asking.  40 GiB buys the 11-bit tables (35 GB) for ~1 % (r4: 1,130-1,145 against 1,123 prove_step/s), 72 GiB "
+                         "without asking.  40 GiB buys the 11-bit tables (35 GB) for ~1 %% (r4: 1,130-1,145 against 1,123 prove_step/s), 72 GiB "
                          "the 12-bit ones (65 GB) for nothing more; with another value the library's default is measured beside it as "
-                         "prove_step.library_default_budget (a leg that follows the main one in the same process runs ~10 % below its own "
+                         "prove_step.library_default_budget (a leg that follows the main one in the same process runs ~10 %% below its own "
                          "process's rate: DESIGN.md 4.3.4)")
     ap.add_argument("--no-bound-form", action="store_true", help="skip the bound-form sub-record of the prove_step leg")
     ap.add_argument("--no-reference-cases", action="store_true", help="skip the reference's own bench cases (benches/nova.rs:62-66)")
@@ -519,6 +535,17 @@ def _jac_to_affine_ints(raw, bm):
     R = 1 << 256
     X, Y, Z = (int.from_bytes(raw[32 * k:32 * k + 32], "little") * pow(R, -1, bm) % bm for k in range(3))
     return None if Z == 0 else (X * pow(Z, -2, bm) % bm, Y * pow(Z, -3, bm) % bm)
+
+
+def dump_outputs(out_dir, result, curve):
+    """--dump-outputs: the point one MSM step hands its caller (12 words, Jacobian, Montgomery) in the canonical affine form, so
+    that two builds compare equal exactly when they computed the same group element.  32-bit limbs are exact in float64."""
+    import vdf_amd
+    bm = _P if curve == vdf_amd.CURVE_PALLAS else _Q
+    pt = _jac_to_affine_ints(result.cpu().numpy().view("<u8").tobytes(), bm) or (0, 0)
+    limbs = [[(v >> (32 * k)) & 0xFFFFFFFF for k in range(8)] for v in pt]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "msm_result.npy"), np.array(limbs, dtype=np.float64))
 
 
 def strong_scaling_leg(ctx, curve, log2n, rank, world, steps, dist, always_gather):
@@ -1216,40 +1243,45 @@ def main():
     gc.collect()
     gc.disable()                            # (the harness's collector stays out of the timed regions -- and out of the gap between the
                                             # settle steps and them: a collection is ~50 ms of idle device; see prove_step_leg)
-    fp_msm = [box_fingerprint(ctx, "before the settle steps of the MSM leg")]
+    fp_msm = [box_fingerprint(ctx, "before the settle steps of the MSM leg")] if args.full else None
     for i in range(args.settle):
         step(i)
     fence()
     for i in range(max(args.warmup, depth)):
         step(i)
     fence()
-    for c in ctxs:
-        c.set_timing(True)
-        c.msm_timing()                    # clear
-    # The contract's timed region -- EXACTLY `steps` steps between two fences -- is run `regions` times back to back and the
-    # MEDIAN region is reported (at the driver's --steps 20 one region is 25 ms: a single one cannot be read finer than
-    # +-3 %); ms_per_step x steps is the duration of that one region.
+    if args.full:                         # stage times for stage_ms and the roofline: HIP events around each MSM's stages
+        for c in ctxs:
+            c.set_timing(True)
+            c.msm_timing()                # clear
+    # The contract's timed region -- EXACTLY `steps` steps between two fences.  With --full it is run `regions` times back to
+    # back and the MEDIAN region is reported (at the driver's --steps 20 one region is 25 ms: a single one cannot be read finer
+    # than +-3 %); ms_per_step x steps is the duration of that one region.
     region_s = []
-    for _ in range(max(1, args.regions)):
+    for _ in range(max(1, args.regions or (5 if args.full else 1))):
         t0 = time.perf_counter()
         for i in range(args.steps):
             step(i)
         fence()
         region_s.append(time.perf_counter() - t0)
     gc.enable()
-    fp_msm.append(box_fingerprint(ctx, "after the MSM regions"))
     elapsed = median(region_s)
-    sort_ms = acc_ms = tail_ms = total_ms = 0.0
-    calls = 0
-    for c in ctxs:
-        a_, b_, c_, d_, n_ = c.msm_timing()
-        sort_ms += a_; acc_ms += b_; tail_ms += c_; total_ms += d_; calls += n_
-        c.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        # the last timed step ran on context (steps - 1) % depth; every rank holds the same summed point
+        dump_outputs(args.dump_outputs, results[(args.steps - 1) % depth], curve)
+    if args.full:
+        fp_msm.append(box_fingerprint(ctx, "after the MSM regions"))
+        sort_ms = acc_ms = tail_ms = total_ms = 0.0
+        calls = 0
+        for c in ctxs:
+            a_, b_, c_, d_, n_ = c.msm_timing()
+            sort_ms += a_; acc_ms += b_; tail_ms += c_; total_ms += d_; calls += n_
+            c.set_timing(False)
     # One more short pass, one step at a time on context 0 (not part of `value`): with steps in flight a kernel's
     # HIP-event (and rocprof) duration includes the time its workgroups queue behind the other stream's, so the
     # isolated duration of the dominant kernel is measured separately for the issue-rate figure.
     iso = None
-    if depth > 1:
+    if depth > 1 and args.full:
         ctx.set_timing(True)
         ctx.msm_timing()
         for _ in range(5):
@@ -1264,7 +1296,7 @@ def main():
         region_s = [float(x) for x in t.tolist()]
         elapsed = median(region_s)
     strong = None
-    if args.strong_log2n and (world > 1 or args.rehearse_collective or args.strong):
+    if args.full and args.strong_log2n and (world > 1 or args.rehearse_collective or args.strong):
         for c in ctxs:
             c.set_async(True)
         strong = strong_scaling_leg(ctx, curve, args.strong_log2n, rank, world, max(3, args.steps // 4), dist,
@@ -1272,7 +1304,7 @@ def main():
     # prove_step across GPUs: one chain does not shard (each step needs the previous challenge), so N GPUs prove N
     # independent chains -- replicas, no collective on the data path; only the rates are combined here
     replicas = None
-    if (world > 1 or args.rehearse_collective) and not args.no_prove:
+    if args.full and (world > 1 or args.rehearse_collective) and not args.no_prove:
         ctx.set_async(False)
         for k in range(1, depth):                 # the MSM legs are done: the prover needs the hardware queues (three per chain)
             shs[k] = None
@@ -1299,35 +1331,7 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = (n * world) / (elapsed / args.steps) / 1e9
-        acc_avg_ms = acc_ms / max(calls, 1)
-        acc_iso_ms = iso["accumulate"] if iso else acc_avg_ms
-        alg_bytes = 96.0 * n
-        # roofline.achieved prices the kernel's own duration: the launch alone on the device (isolated).  With steps in
-        # flight a launch's HIP-event duration also contains the time its workgroups queue behind the other step's; that
-        # figure is kept beside it (overlapped_*), never used for frac.
-        achieved = alg_bytes / (acc_iso_ms * 1e-3) / 1e9
-        achieved_overlapped = alg_bytes / (acc_avg_ms * 1e-3) / 1e9
         window = shs[0].bases.window or args.window or 16
-        windows_eff = (255 + window - 1) // window                    # entries per point: scalars are below 2^255, zero digits are rare
-        ctx_num_simds = 4 * torch.cuda.get_device_properties(local_rank).multi_processor_count
-        # measured inputs of the two derived figures come from profiles/ (tracked, with their provenance), not from literals
-        def latest(prefix):
-            import glob
-            c = sorted(glob.glob(os.path.join(ROOT, "profiles", prefix + "_r*.json")))
-            try:
-                return (json.load(open(c[-1])), os.path.basename(c[-1])) if c else (None, None)
-            except Exception:
-                return None, None
-        tj, tfile = latest("traffic")
-        traffic = tj.get("k_accumulate_hbm_bytes_per_launch") if tj else None
-        vm, vfile = latest("valu_model")
-        valu = None
-        if vm:
-            per_add, cyc, ghz = vm["valu_per_bucket_addition"], vm["cycles_per_valu_wave_instruction_per_simd"], vm["sustained_shader_clock_ghz"]
-            issue = lambda ms: (per_add * n * windows_eff / 64.0) / (ctx_num_simds * ms * 1e-3 * ghz * 1e9 / cyc)
-            valu = {"valu_issue_frac": issue(acc_iso_ms), "of_timed_region_accumulate_only": issue(elapsed / args.steps * 1e3),
-                    "valu_per_bucket_addition": per_add, "cycles_per_valu_wave_instruction_per_simd": cyc,
-                    "sustained_shader_clock_ghz": ghz, "source": "profiles/" + vfile, "produced_at_commit": vm.get("produced_at_commit"), "provenance": vm.get("provenance")}
         line = {
             "metric": "MSM GPoints/s at 2^20 (Pallas, Pedersen-commitment MSM of Nova prove_step); prove_step/s in `prove_step`",
             "value": value, "unit": "GPoints/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1339,41 +1343,73 @@ def main():
                        "workload_detail": f"{'seeded try-and-increment' if args.bases == 'tai' else '[k_i]G'} generators (seed 7), scalars from torch Philox "
                                           f"(seed 1234+rank), bucket sets {args.sets}, {depth} independent steps in flight on {depth} streams",
                        "points_per_gpu": n, "window_bits": window, "bucket_sets": args.sets, "steps_in_flight": depth},
-            # the two ways to run the same MSM, side by side: `value` is the pipelined throughput
-            "single_msm": {"latency_ms": iso["pipeline"] if iso else total_ms / max(calls, 1),
-                           "value": n / ((iso["pipeline"] if iso else total_ms / max(calls, 1)) * 1e-3) / 1e9, "unit": "GPoints/s",
-                           "what": "one MSM at a time on an idle device (stream-synchronised between calls)"},
-            "pipelined": {"ms_per_msm": ms_per_step, "value": value, "unit": "GPoints/s", "steps_in_flight": depth},
             "timed_regions": {"regions": len(region_s), "steps_per_region": args.steps, "reported": "median region",
                               "ms_per_step_by_region": [round(x / args.steps * 1e3, 4) for x in region_s]},
-            "stage_ms": {"sort": sort_ms / max(calls, 1), "accumulate": acc_avg_ms, "tail": tail_ms / max(calls, 1),
-                         "pipeline": total_ms / max(calls, 1)},
-            "stage_ms_one_step_at_a_time": iso,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
-                         "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": ("profiles/" + tfile) if tfile else None,
-                         "traffic_produced_at_commit": (tj or {}).get("produced_at_commit"),
-                         "kernel": "k_accumulate", "algorithmic_bytes_per_launch": alg_bytes,
-                         "avg_launch_ms": acc_iso_ms, "launch_timing": "HIP events on the launching stream, one step at a time",
-                         "overlapped_avg_launch_ms": acc_avg_ms, "overlapped_achieved": achieved_overlapped,
-                         "valu": valu,
-                         "note": "k_accumulate is integer-VALU-issue bound, neither HBM nor MFMA: frac is the contract's HBM "
-                                 "figure from the isolated launch.  overlapped_* is the HIP-event duration inside the timed region, "
-                                 "where a launch also waits for the other in-flight step's workgroups to retire (it can exceed "
-                                 "ms_per_step and is not kernel time).  valu.* is the bound that holds (DESIGN.md 4.1, 4.2)"},
         }
+        if args.full:
+            acc_avg_ms = acc_ms / max(calls, 1)
+            acc_iso_ms = iso["accumulate"] if iso else acc_avg_ms
+            alg_bytes = 96.0 * n
+            # roofline.achieved prices the kernel's own duration: the launch alone on the device (isolated).  With steps in
+            # flight a launch's HIP-event duration also contains the time its workgroups queue behind the other step's; that
+            # figure is kept beside it (overlapped_*), never used for frac.
+            achieved = alg_bytes / (acc_iso_ms * 1e-3) / 1e9
+            achieved_overlapped = alg_bytes / (acc_avg_ms * 1e-3) / 1e9
+            windows_eff = (255 + window - 1) // window                    # entries per point: scalars are below 2^255, zero digits are rare
+            ctx_num_simds = 4 * torch.cuda.get_device_properties(local_rank).multi_processor_count
+            # measured inputs of the two derived figures come from profiles/ (tracked, with their provenance), not from literals
+            def latest(prefix):
+                import glob
+                c = sorted(glob.glob(os.path.join(ROOT, "profiles", prefix + "_r*.json")))
+                try:
+                    return (json.load(open(c[-1])), os.path.basename(c[-1])) if c else (None, None)
+                except Exception:
+                    return None, None
+            tj, tfile = latest("traffic")
+            traffic = tj.get("k_accumulate_hbm_bytes_per_launch") if tj else None
+            vm, vfile = latest("valu_model")
+            valu = None
+            if vm:
+                per_add, cyc, ghz = vm["valu_per_bucket_addition"], vm["cycles_per_valu_wave_instruction_per_simd"], vm["sustained_shader_clock_ghz"]
+                issue = lambda ms: (per_add * n * windows_eff / 64.0) / (ctx_num_simds * ms * 1e-3 * ghz * 1e9 / cyc)
+                valu = {"valu_issue_frac": issue(acc_iso_ms), "of_timed_region_accumulate_only": issue(elapsed / args.steps * 1e3),
+                        "valu_per_bucket_addition": per_add, "cycles_per_valu_wave_instruction_per_simd": cyc,
+                        "sustained_shader_clock_ghz": ghz, "source": "profiles/" + vfile, "produced_at_commit": vm.get("produced_at_commit"), "provenance": vm.get("provenance")}
+            line.update({
+                # the two ways to run the same MSM, side by side: `value` is the pipelined throughput
+                "single_msm": {"latency_ms": iso["pipeline"] if iso else total_ms / max(calls, 1),
+                               "value": n / ((iso["pipeline"] if iso else total_ms / max(calls, 1)) * 1e-3) / 1e9, "unit": "GPoints/s",
+                               "what": "one MSM at a time on an idle device (stream-synchronised between calls)"},
+                "pipelined": {"ms_per_msm": ms_per_step, "value": value, "unit": "GPoints/s", "steps_in_flight": depth},
+                "stage_ms": {"sort": sort_ms / max(calls, 1), "accumulate": acc_avg_ms, "tail": tail_ms / max(calls, 1),
+                             "pipeline": total_ms / max(calls, 1)},
+                "stage_ms_one_step_at_a_time": iso,
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
+                             "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": ("profiles/" + tfile) if tfile else None,
+                             "traffic_produced_at_commit": (tj or {}).get("produced_at_commit"),
+                             "kernel": "k_accumulate", "algorithmic_bytes_per_launch": alg_bytes,
+                             "avg_launch_ms": acc_iso_ms, "launch_timing": "HIP events on the launching stream, one step at a time",
+                             "overlapped_avg_launch_ms": acc_avg_ms, "overlapped_achieved": achieved_overlapped,
+                             "valu": valu,
+                             "note": "k_accumulate is integer-VALU-issue bound, neither HBM nor MFMA: frac is the contract's HBM "
+                                     "figure from the isolated launch.  overlapped_* is the HIP-event duration inside the timed region, "
+                                     "where a launch also waits for the other in-flight step's workgroups to retire (it can exceed "
+                                     "ms_per_step and is not kernel time).  valu.* is the bound that holds (DESIGN.md 4.1, 4.2)"},
+            })
         if strong is not None:
             line["strong_2_%d" % args.strong_log2n] = strong
         if replicas is not None:
             line["prove_step_replicas"] = replicas
-        line["box"] = {"host": host_fingerprint(), "device": fp_msm}
-        if world == 1 and not args.no_sizes and not args.rehearse_collective:
+        if args.full:
+            line["box"] = {"host": host_fingerprint(), "device": fp_msm}
+        if args.full and world == 1 and not args.no_sizes and not args.rehearse_collective:
             for c in ctxs:
                 c.sync()
             line["box"]["hbm"] = hbm_fingerprint(ctx)
             line["msm_sizes"] = msm_sizes_leg(ctx, curve)
             for c in ctxs:
                 c.set_async(True)
-        if world == 1 and not args.no_prove and not args.rehearse_collective:
+        if args.full and world == 1 and not args.no_prove and not args.rehearse_collective:
             ctx.set_async(False)
             for c in ctxs[1:]:                    # the MSM leg's other queues are done: a prover needs the hardware queues (three per chain)
                 c.close()
@@ -1433,7 +1469,7 @@ def main():
                 # drop in the gather rate or a jump in the allocation time is this process's own fragmentation of the pool
                 line["box"]["hbm_after_prove_legs"] = hbm_fingerprint(ctx)
         failures = []
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             ctx.set_async(False)
             line["cpu_baseline"] = cpu_baseline_leg(ctx, sh.bases, sc, n, curve, result.cpu().numpy().view("<u8"))
             if not line["cpu_baseline"]["parity_bit_exact"]:
@@ -1444,7 +1480,7 @@ def main():
                 if not line["prove_step"]["cpu_baseline"]["parity_bit_exact"]:
                     failures.append("prove_step: a GPU result differs from the C restatement at t = 2^%d" % args.prove_log2t)
                 line["prove_step"]["cpu_baseline_config1"] = cpu_prove_baseline_leg()
-        elif world == 1:
+        elif args.full and world == 1:
             # without the CPU leg the result is still checked: the same scalars against generators with known discrete
             # logarithms, sum s_i [k_i] G = [sum s_i k_i] G (host big integers only; no oracle code involved)
             line["self_check"] = msm_dlog_self_check(ctx, curve, sc, min(n, 1 << 16))

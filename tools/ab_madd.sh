@@ -10,7 +10,7 @@ AB=$R/vdf_amd/csrc/build/ab/libvdf_hip.so
 for round in $(seq 1 ${1:-2}); do
   for which in ab shipped; do
     if [ $which = ab ]; then export VDF_HIP_LIB=$AB; else unset VDF_HIP_LIB; fi
-    m=$(timeout -k 10 200 python3 $R/bench.py --no-prove --no-cpu --no-sizes --steps 100 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('msm %.4f GPoints/s  %.4f ms/step  acc alone %.4f ms' % (d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms']))")
+    m=$(timeout -k 10 200 python3 $R/bench.py --full --no-prove --no-cpu --no-sizes --steps 100 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('msm %.4f GPoints/s  %.4f ms/step  acc alone %.4f ms' % (d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms']))")
     p=$(timeout -k 10 300 python3 $R/tools/gpu_prove_time.py 16 100 ref 2>&1 | grep "steady state")
     echo "== round $round [$which] $m | prove: $p"
   done

@@ -2,7 +2,7 @@
 """profiles/valu_model_rNN.json from raw measurements (all taken on the MI355X box by tools/profile_round.sh):
   op_rates.txt    tools/ubench/op_rates: cycles per wave-instruction per SIMD, by instruction, from kernel wall time
   clock_probe.txt tools/ubench/clock_probe: sustained shader clock under a multiply-bound kernel
-  <pmc dir>       rocprofv3 --pmc SQ_INSTS_VALU over `bench.py --depth 1 --no-prove --no-cpu` (k_accumulate launches)
+  <pmc dir>       rocprofv3 --pmc SQ_INSTS_VALU over `bench.py --full --depth 1 --no-prove --no-cpu` (k_accumulate launches)
 usage: make_valu_model.py <op_rates.txt> <clock_probe.txt> <pmc dir> <entries per launch> <out.json>"""
 import csv, glob, json, re, sys
 
@@ -20,7 +20,7 @@ for f in glob.glob(pmc_dir + "/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         if "k_accumulate" in r["Kernel_Name"] and r["Counter_Name"] == "SQ_INSTS_VALU":
             vals.append(float(r["Counter_Value"]))
-# the run also holds a small self-check MSM (bench.py --no-cpu): keep the launches of the timed workload only
+# the run also holds a small self-check MSM (bench.py --full --no-cpu): keep the launches of the timed workload only
 vals = [v for v in vals if v >= 0.8 * max(vals)]
 per_launch = sum(vals) / len(vals)
 res = {"produced_at_commit": commit, "round": tag, "valu_per_bucket_addition": per_launch * 64.0 / entries,         # SQ_INSTS_VALU counts wave-instructions

@@ -19,7 +19,7 @@ fetch_dir, write_dir, out = sys.argv[1:4]
 substr = sys.argv[4] if len(sys.argv) > 4 else "k_accumulate"
 fs = per_kernel(fetch_dir, "FETCH_SIZE", substr)
 ws = per_kernel(write_dir, "WRITE_SIZE", substr)
-# the run also holds a small self-check MSM (bench.py --no-cpu): keep the launches of the timed workload only
+# the run also holds a small self-check MSM (bench.py --full --no-cpu): keep the launches of the timed workload only
 fs = [v for v in fs if v >= 0.8 * max(fs)]
 ws = [v for v in ws if v >= 0.8 * max(ws)]
 res = {"produced_at_commit": sys.argv[6] if len(sys.argv) > 6 else "unknown", "kernel": substr, "launches": len(fs),
