@@ -397,6 +397,22 @@ int  vdf_pair_table(vdf_ctx* ctx, int field, const vdf_fe* lo, const vdf_fe* hi,
  * inner-product argument that stopped at a vector of 2^log_m elements instead of halving down to one. */
 int  vdf_pair_table_pattern(vdf_ctx* ctx, int field, const vdf_fe* lo, const vdf_fe* hi, int k, const vdf_fe* pattern, int log_m,
                             vdf_fe* out);
+/* One opening of an inner-product argument as its verifier's final check sees it: a weight, the k round factors
+ * (lo = x^-1, hi = x of round j) and the final vector of 2^log_m elements; every element host memory, Montgomery form;
+ * k + log_m <= 24, log_m <= 4. */
+typedef struct vdf_ipa_opening {
+  vdf_fe weight;
+  int k, log_m;
+  const vdf_fe* lo;
+  const vdf_fe* hi;
+  const vdf_fe* pattern;
+} vdf_ipa_opening;
+/* out[i] = sum over the openings q with i < 2^(k_q + log_m_q) of
+ *            weight_q * pattern_q[i mod 2^log_m_q] * prod_j (bit (k_q-1-j) of (i >> log_m_q) ? hi_q[j] : lo_q[j]),   i < n,
+ * zero past every opening: the generator coefficients of a random linear combination of many openings' checks (one MSM over
+ * the generators for all of them); count = 1 with weight 1 is vdf_pair_table_pattern.  The openings' factors travel to the
+ * device in one copy per call; out (device, n elements) is ready for vdf_msm(..., is_mont = 1). */
+int  vdf_ipa_coefficients(vdf_ctx* ctx, int field, const vdf_ipa_opening* ops, int count, size_t n, vdf_fe* out);
 /* v[t][i] <- c_lo[t] * v[t][i] + c_hi[t] * v[t][i + n/2], i < n/2, for t < k <= 8 vectors of length n (power of two)
  * in one launch: a sum-check binding (1 - r, r); the argument's folds (x, x^-1) / (x^-1, x). */
 int  vdf_fold_halves(vdf_ctx* ctx, int field, int k, vdf_fe* const v[], const vdf_fe c_lo[], const vdf_fe c_hi[], size_t n);

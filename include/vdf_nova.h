@@ -320,6 +320,15 @@ int  vdf_nova_compress(const vdf_proof* proof, vdf_pp* pp, vdf_snark** out);
  * folds itself), the carried zi_primary equals zi and zi_secondary == [0]. */
 int  vdf_nova_verify_compressed(const vdf_snark* snark, vdf_pp* pp, size_t num_steps, const vdf_fe z0[3], const vdf_fe zi[3],
                                 int* ok);
+/* Many compressed proofs under one parameter set: ok[q] = what vdf_nova_verify_compressed returns for entry q (up to a
+ * soundness error of about 2^-128), *all_ok = 1 iff every entry verifies; z0, zi: count x arity elements.  Each proof's
+ * exact checks and transcript replay run on their own; the group checks of all its inner-product openings are combined,
+ * with independent 128-bit weights drawn from a transcript of the whole batch, into one MSM over each side's generators
+ * and one over the small points.  When a combined check fails, every remaining entry is verified on its own.  A null
+ * proof or one made under other parameters fails the call with VDF_ERR_BAD_ARG (vdf_nova_last_error names the entry);
+ * count = 0 gives *all_ok = 1. */
+int  vdf_nova_verify_compressed_batch(vdf_pp* pp, size_t count, const vdf_snark* const snarks[], const size_t num_steps[],
+                                      const vdf_fe* z0, const vdf_fe* zi, int ok[], int* all_ok);
 void vdf_nova_snark_free(vdf_snark* snark);
 /* Flat canonical encoding of the two arguments, primary then secondary (little-endian, non-Montgomery, 64-byte points;
  * layout in the implementation and in oracle/wire.py): size, export, and import -- which replaces the arguments of

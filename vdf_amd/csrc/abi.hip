@@ -674,6 +674,9 @@ void vdf_ctx_destroy(vdf_ctx* ctx) {
   if (ctx->small_pool) (void)hipFree(ctx->small_pool);
   if (ctx->h_out) (void)hipHostFree(ctx->h_out);
   if (ctx->reduce_scratch) (void)hipFree(ctx->reduce_scratch);
+  if (ctx->ipa_host) (void)hipHostFree(ctx->ipa_host);
+  if (ctx->ipa_dev) (void)hipFree(ctx->ipa_dev);
+  if (ctx->ipa_copied) (void)hipEventDestroy(ctx->ipa_copied);
   if (ctx->direct_arrived) (void)hipFree(ctx->direct_arrived);
   if (ctx->glv_scalars) (void)hipFree(ctx->glv_scalars);
   if (ctx->glv_pts) (void)hipFree(ctx->glv_pts);
@@ -1684,16 +1687,61 @@ int vdf_pair_table(vdf_ctx* ctx, int field, const vdf_fe* lo, const vdf_fe* hi, 
   });
 }
 
+// the openings' factors: packed into the context's pinned block, one copy to its device block, then the kernel (a call
+// waits only for the previous call's copy before it repacks)
+static Status ipa_coefficients(vdf_ctx* ctx, int field, const vdf_ipa_opening* ops, int count, size_t n, void* out) {
+  if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
+  if (count < 0 || count > (1 << 16)) return Status{VDF_ERR_BAD_ARG, "0..65536 openings"};
+  if (count && !ops) return Status{VDF_ERR_BAD_ARG, "null openings"};
+  if (n > ((size_t)1 << 32)) return Status{VDF_ERR_BAD_LENGTH, "at most 2^32 entries"};
+  for (int q = 0; q < count; ++q) {
+    const vdf_ipa_opening& o = ops[q];
+    if (o.k < 0 || o.log_m < 0 || o.log_m > 4 || o.k + o.log_m > 24)
+      return Status{VDF_ERR_BAD_LENGTH, "0..24 variables in all, pattern of 1..16 (opening " + std::to_string(q) + ")"};
+    if (o.k && (!o.lo || !o.hi || ptr_is_device(o.lo) || ptr_is_device(o.hi))) return Status{VDF_ERR_BAD_ARG, kHostScalar};
+    if (!o.pattern || ptr_is_device(o.pattern)) return Status{VDF_ERR_BAD_ARG, kHostScalar};
+  }
+  if (n && !ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, kDevVec};
+  if (n == 0) return Status{};
+  const size_t bytes = vdf::snark_ipa_block_bytes(count);
+  if (bytes > ctx->ipa_cap) {
+    const size_t cap = std::max(bytes, vdf::snark_ipa_block_bytes(64));
+    VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));              // an earlier launch may still read the device block
+    if (ctx->ipa_host) { (void)hipHostFree(ctx->ipa_host); ctx->ipa_host = nullptr; }
+    if (ctx->ipa_dev) { (void)hipFree(ctx->ipa_dev); ctx->ipa_dev = nullptr; }
+    ctx->ipa_cap = 0;
+    VDF_TRY_HIP(hipHostMalloc(&ctx->ipa_host, cap, hipHostMallocDefault));
+    VDF_TRY_HIP(hipMalloc(&ctx->ipa_dev, cap));
+    ctx->ipa_cap = cap;
+  } else if (ctx->ipa_copied) {
+    VDF_TRY_HIP(hipEventSynchronize(ctx->ipa_copied));
+  }
+  if (!ctx->ipa_copied) VDF_TRY_HIP(hipEventCreateWithFlags(&ctx->ipa_copied, hipEventDisableTiming));
+  if (bytes) {
+    vdf::snark_ipa_pack(ops, count, ctx->ipa_host);
+    VDF_TRY_HIP(hipMemcpyAsync(ctx->ipa_dev, ctx->ipa_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    VDF_TRY_HIP(hipEventRecord(ctx->ipa_copied, ctx->stream));
+  }
+  VDF_TRY(vdf::snark_ipa_coefficients(field, ctx->ipa_dev, count, n, out, ctx->stream));
+  if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  return Status{};
+}
+
+int vdf_ipa_coefficients(vdf_ctx* ctx, int field, const vdf_ipa_opening* ops, int count, size_t n, vdf_fe* out) {
+  return guarded(ctx, [&]() -> Status { return ipa_coefficients(ctx, field, ops, count, n, out); });
+}
+
+// one opening of weight 1
 int vdf_pair_table_pattern(vdf_ctx* ctx, int field, const vdf_fe* lo, const vdf_fe* hi, int k, const vdf_fe* pattern, int log_m,
                            vdf_fe* out) {
   return guarded(ctx, [&]() -> Status {
     if (k < 0 || log_m < 0 || log_m > 4 || k + log_m > 24) return Status{VDF_ERR_BAD_LENGTH, "0..24 variables in all, pattern of 1..16"};
-    if (k && (!lo || !hi || ptr_is_device(lo) || ptr_is_device(hi))) return Status{VDF_ERR_BAD_ARG, kHostScalar};
-    if (!pattern || ptr_is_device(pattern)) return Status{VDF_ERR_BAD_ARG, kHostScalar};
+    if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
     if (!ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, kDevVec};
-    VDF_TRY(vdf::snark_pair_table_pattern(field, lo, hi, k, pattern, log_m, out, ctx->stream));
-    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
-    return Status{};
+    vdf_ipa_opening op{};
+    vdf::snark_field_one(field, &op.weight);
+    op.k = k; op.log_m = log_m; op.lo = lo; op.hi = hi; op.pattern = pattern;
+    return ipa_coefficients(ctx, field, &op, 1, (size_t)1 << (k + log_m), out);
   });
 }
 

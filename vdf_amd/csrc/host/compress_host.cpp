@@ -367,17 +367,29 @@ struct IpaCheck {
   // state
   size_t k = 0, m = 0, idx = 0;
   int log_m = 0;
-  Pt Qp, acc;
   Fe bfin;
-  std::vector<Fe> xs, xis;
 };
 
-// The transcript order of ipa_prove_many; then, per opening, two device MSMs: sum_j x_j^2 L_j + x_j^-2 R_j (2k
-// multiplications by full-size scalars: on the host they were the whole cost of verification, 0.25 ms each) and the
-// folded generators against the sent vector.
-int ipa_verify_many(const Side& sd, Transcript& tr, IpaCheck* jobs, int njobs, void* d_s, bool* ok) {
-  const Side* pp = &sd;
-  vdf_ctx* ctx = sd.ctx;
+// What is left of an opening's check once the transcript is replayed: with Q' = c gen_u (c the 128-bit challenge) and ab the
+// sent vector against b's fold,
+//   P + c (v - ab) gen_u + sum_j (x_j^2 L_j + x_j^-2 R_j) == MSM(G, coefficients)
+// where the coefficients are vdf_ipa_coefficients' table of the rounds (lo = x^-1, hi = x) over the sent vector a.  Linear in
+// the group: checks of many openings combine with random weights into one equation (vdf_nova_verify_compressed_batch).
+struct IpaDeferred {
+  size_t n = 0;
+  int k = 0, log_m = 0;
+  std::vector<Fe> xs, xis;         // the round challenges and their inverses
+  std::vector<Aff> lr_pts;         // L_0, R_0, L_1, R_1, ...
+  std::vector<Fe> lr_sc;           // x_0^2, x_0^-2, ...
+  std::vector<Fe> a;               // the sent vector (2^log_m elements)
+  Aff P;
+  Fe v, ab;
+  uint64_t q_raw[4];
+};
+
+// The transcript order of ipa_prove_many, up to the last check of each opening (sizes, challenges, b's fold, ab).  *ok =
+// false for a proof that fails a size check or draws a zero challenge.
+int ipa_replay(const Side& sd, Transcript& tr, IpaCheck* jobs, int njobs, IpaDeferred* out, bool* ok) {
   const Field& F = *sd.F;
   const Field& Fb = *sd.Fb;
   *ok = false;
@@ -395,18 +407,19 @@ int ipa_verify_many(const Side& sd, Transcript& tr, IpaCheck* jobs, int njobs, v
   }
   for (int q = 0; q < njobs; ++q) {
     IpaCheck& c = jobs[q];
+    IpaDeferred& d = out[q];
     tr.absorb_pt(c.label, &c.P, 1, Fb);
     tr.absorb_fe(c.label, &c.v, 1, F);
-    tr.challenge(c.label, F, raw);
-    c.Qp = pt_mul(pt_from_aff(pp->gen_u, Fb), raw, 128, Fb);
-    c.acc = pt_add(pt_from_aff(c.P, Fb), pt_mul_fe(c.Qp, c.v, F, Fb), Fb);
+    tr.challenge(c.label, F, d.q_raw);
     c.bfin = one(F);
-    c.xs.resize(c.k); c.xis.resize(c.k);
+    d.n = c.n; d.k = (int)c.k; d.log_m = c.log_m; d.P = c.P; d.v = c.v; d.a = c.proof->a;
+    d.xs.resize(c.k); d.xis.resize(c.k);
   }
   for (;;) {
     bool any = false;
     for (int q = 0; q < njobs; ++q) {
       IpaCheck& c = jobs[q];
+      IpaDeferred& d = out[q];
       if (c.idx >= c.k) continue;
       any = true;
       const size_t j = c.idx++;
@@ -417,53 +430,66 @@ int ipa_verify_many(const Side& sd, Transcript& tr, IpaCheck* jobs, int njobs, v
       const Fe xi = inverse(x, F);
       const Fe& r = (*c.rb)[j];
       c.bfin = mul(c.bfin, add(mul(sub(one(F), r, F), xi, F), mul(r, x, F), F), F);
-      c.xs[j] = x; c.xis[j] = xi;
+      d.xs[j] = x; d.xis[j] = xi;
     }
     if (!any) break;
   }
-  bool all = true;
   for (int q = 0; q < njobs; ++q) {
     IpaCheck& c = jobs[q];
-    const size_t k = c.k, m = c.m;
-    if (k) {
-      std::vector<Aff> lr_pts(2 * k);
-      std::vector<Fe> lr_sc(2 * k);
-      for (size_t j = 0; j < k; ++j) {
-        lr_pts[2 * j] = c.proof->L[j]; lr_sc[2 * j] = sqr(c.xs[j], F);
-        lr_pts[2 * j + 1] = c.proof->R[j]; lr_sc[2 * j + 1] = sqr(c.xis[j], F);
-      }
-      vdf_bases* lrb = nullptr;
-      HIPCALL(ctx, vdf_bases_upload(ctx, sd.curve, (const vdf_affine*)lr_pts.data(), 2 * k, &lrb));
-      vdf_jac jlr;
-      const int rc = vdf_msm(ctx, lrb, 0, (const vdf_fe*)lr_sc.data(), 2 * k, 1, &jlr);
-      const std::string err = rc == VDF_OK ? "" : vdf_last_error(ctx);
-      vdf_bases_free(lrb);
-      if (rc != VDF_OK) return fail(rc, "vdf_msm (L, R): " + err);
-      HIPCALL(ctx, vdf_ctx_sync(ctx));
-      c.acc = pt_add(c.acc, pt_from_aff(jac_to_aff(jlr, Fb), Fb), Fb);
+    IpaDeferred& d = out[q];
+    d.lr_pts.resize(2 * c.k); d.lr_sc.resize(2 * c.k);
+    for (size_t j = 0; j < c.k; ++j) {
+      d.lr_pts[2 * j] = c.proof->L[j]; d.lr_sc[2 * j] = sqr(d.xs[j], F);
+      d.lr_pts[2 * j + 1] = c.proof->R[j]; d.lr_sc[2 * j + 1] = sqr(d.xis[j], F);
     }
-    // coefficients of the original generators in sum_i a_i G'_i, G'_i the folded generators: the table of the performed
-    // rounds over the top index bits times the sent vector over the low ones; b folded in closed form: bfin (the
-    // rounds) times eq over the remaining variables
-    HIPCALL(ctx, vdf_pair_table_pattern(ctx, sd.field, (const vdf_fe*)c.xis.data(), (const vdf_fe*)c.xs.data(), (int)k,
-                                        (const vdf_fe*)c.proof->a.data(), c.log_m, (vdf_fe*)d_s));
-    vdf_jac jg;
-    HIPCALL(ctx, vdf_msm(ctx, pp->gens, 0, (const vdf_fe*)d_s, c.n, 1, &jg));
-    HIPCALL(ctx, vdf_ctx_sync(ctx));
+    // b folded in closed form: bfin (the rounds) times eq over the remaining variables
     Fe ab = zero();
-    for (size_t i = 0; i < m; ++i) {
+    for (size_t i = 0; i < c.m; ++i) {
       Fe bi = c.bfin;
       for (int j = 0; j < c.log_m; ++j) {
-        const Fe& r = (*c.rb)[k + j];
+        const Fe& r = (*c.rb)[c.k + j];
         bi = mul(bi, ((i >> (c.log_m - 1 - j)) & 1) ? r : sub(one(F), r, F), F);
       }
       ab = add(ab, mul(c.proof->a[i], bi, F), F);
     }
-    const Pt rhs = pt_add(pt_from_aff(jac_to_aff(jg, Fb), Fb), pt_mul_fe(c.Qp, ab, F, Fb), Fb);
-    const Aff a1 = pt_to_aff(c.acc, Fb), a2 = pt_to_aff(rhs, Fb);
-    all = all && memcmp(&a1, &a2, sizeof(Aff)) == 0;
+    d.ab = ab;
   }
-  *ok = all;
+  *ok = true;
+  return VDF_OK;
+}
+
+// One opening's check on its own: two device MSMs, sum_j x_j^2 L_j + x_j^-2 R_j (2k multiplications by full-size scalars: on
+// the host they were the whole cost of verification, 0.25 ms each) and the folded generators against the sent vector.
+// d_s: n device elements of scratch.
+int ipa_check_one(const Side& sd, const IpaDeferred& d, void* d_s, bool* ok) {
+  const Side* pp = &sd;
+  vdf_ctx* ctx = sd.ctx;
+  const Field& F = *sd.F;
+  const Field& Fb = *sd.Fb;
+  *ok = false;
+  const Pt Qp = pt_mul(pt_from_aff(pp->gen_u, Fb), d.q_raw, 128, Fb);
+  Pt acc = pt_add(pt_from_aff(d.P, Fb), pt_mul_fe(Qp, d.v, F, Fb), Fb);
+  if (d.k) {
+    vdf_bases* lrb = nullptr;
+    HIPCALL(ctx, vdf_bases_upload(ctx, sd.curve, (const vdf_affine*)d.lr_pts.data(), 2 * d.k, &lrb));
+    vdf_jac jlr;
+    const int rc = vdf_msm(ctx, lrb, 0, (const vdf_fe*)d.lr_sc.data(), 2 * d.k, 1, &jlr);
+    const std::string err = rc == VDF_OK ? "" : vdf_last_error(ctx);
+    vdf_bases_free(lrb);
+    if (rc != VDF_OK) return fail(rc, "vdf_msm (L, R): " + err);
+    HIPCALL(ctx, vdf_ctx_sync(ctx));
+    acc = pt_add(acc, pt_from_aff(jac_to_aff(jlr, Fb), Fb), Fb);
+  }
+  // coefficients of the original generators in sum_i a_i G'_i, G'_i the folded generators: the table of the performed
+  // rounds over the top index bits times the sent vector over the low ones
+  HIPCALL(ctx, vdf_pair_table_pattern(ctx, sd.field, (const vdf_fe*)d.xis.data(), (const vdf_fe*)d.xs.data(), d.k,
+                                      (const vdf_fe*)d.a.data(), d.log_m, (vdf_fe*)d_s));
+  vdf_jac jg;
+  HIPCALL(ctx, vdf_msm(ctx, pp->gens, 0, (const vdf_fe*)d_s, d.n, 1, &jg));
+  HIPCALL(ctx, vdf_ctx_sync(ctx));
+  const Pt rhs = pt_add(pt_from_aff(jac_to_aff(jg, Fb), Fb), pt_mul_fe(Qp, d.ab, F, Fb), Fb);
+  const Aff a1 = pt_to_aff(acc, Fb), a2 = pt_to_aff(rhs, Fb);
+  *ok = memcmp(&a1, &a2, sizeof(Aff)) == 0;
   return VDF_OK;
 }
 
@@ -619,7 +645,10 @@ int spartan_prove(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, con
   return ipa_prove_many(sd, tr, jobs, 2, h_lr);
 }
 
-int spartan_verify(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, const Fe* X, const Spartan& pf, bool* ok) {
+// The verifier's transcript replay of one side's argument: sizes, both sum-checks, M(r_y) on the device, the openings up to
+// their deferred group checks (out[0]: W, out[1]: E).  *ok = false when an exact check fails.
+int spartan_replay(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, const Fe* X, const Spartan& pf, IpaDeferred out[2],
+                   bool* ok) {
   const Side* pp = &sd;
   vdf_ctx* ctx = sd.ctx;
   const Field& F = *sd.F;
@@ -658,12 +687,11 @@ int spartan_verify(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, co
   }
   // M(r_y) on the device: eq(r_x, .) -> transposed product -> dot with eq(r_y, .)
   DevBufs bufs(ctx, sd.arena);
-  { int rc = bufs.reserve(L.M + pp->ncols + 2 * L.Z + L.NW); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
-  void *d_eq_rx, *d_cols, *d_mvec, *d_eq_ry, *d_s;
+  { int rc = bufs.reserve(L.M + pp->ncols + 2 * L.Z); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+  void *d_eq_rx, *d_cols, *d_mvec, *d_eq_ry;
   { int rc = bufs.zeros(L.M, &d_eq_rx); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
   { int rc = bufs.zeros(pp->ncols, &d_cols); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
   for (void** p : {&d_mvec, &d_eq_ry}) { int rc = bufs.zeros(L.Z, p); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
-  { int rc = bufs.zeros(L.NW, &d_s); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
   { int rc = eq_table_dev(sd, rx, d_eq_rx); if (rc != VDF_OK) return rc; }
   { int rc = m_vector_dev(sd, L, d_eq_rx, rho, d_cols, d_mvec); if (rc != VDF_OK) return rc; }
   { int rc = eq_table_dev(sd, ry, d_eq_ry); if (rc != VDF_OK) return rc; }
@@ -687,7 +715,7 @@ int spartan_verify(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, co
   IpaCheck checks[2];
   checks[0].label = "ipaW"; checks[0].n = L.NW; checks[0].rb = &rest; checks[0].v = pf.w_eval; checks[0].P = cW; checks[0].proof = &pf.ipaW;
   checks[1].label = "ipaE"; checks[1].n = L.M; checks[1].rb = &rx; checks[1].v = e; checks[1].P = cE; checks[1].proof = &pf.ipaE;
-  return ipa_verify_many(sd, tr, checks, 2, d_s, ok);
+  return ipa_replay(sd, tr, checks, 2, out, ok);
 }
 
 }  // namespace
@@ -826,6 +854,112 @@ int vdf_nova_compress(const vdf_proof* p, vdf_pp* pp, vdf_snark** out) {
 
 void vdf_nova_snark_free(vdf_snark* s) { delete s; }
 
+}  // extern "C"
+
+namespace {
+
+// The exact checks of one compressed proof (src/nova/proof.rs:383): the two output hashes, the carried z_i, the last fold of
+// the instances, then each side's transcript replay; its four openings' group checks are left in d[side][W / E].  *ok =
+// false when an exact check fails.  The caller has checked the parameters and made the context asynchronous.
+int verify_replay(const vdf_snark* s, vdf_pp* pp, size_t num_steps, const vdf_fe* z0, const vdf_fe* zi, IpaDeferred d[2][2], bool* ok) {
+  *ok = false;
+  if (num_steps == 0) return VDF_OK;
+  const Side& S1 = pp->s[PRIMARY];
+  const Side& S2 = pp->s[SECONDARY];
+  const Field& F1 = *S1.F;
+  const Field& F2 = *S2.F;
+  if (s->zi1.size() != pp->arity) return VDF_OK;
+  const std::vector<Fe> z0p((const Fe*)z0, (const Fe*)z0 + pp->arity), z0s(1, zero()), zi1 = s->zi1, zi2(s->zi2, s->zi2 + 1);
+  uint64_t hv[4];
+  hash_state(S1.field, pp->params[PRIMARY], from_u64(num_steps, F1), z0p, zi1, to_relaxed(s->r_U2, F2), hv, pp->ro);
+  if (int_to_fe(hv, F2) != s->l_u2.X[0]) return VDF_OK;
+  hash_state(S2.field, pp->params[SECONDARY], from_u64(num_steps, F2), z0s, zi2, to_relaxed(s->r_U1, F1), hv, pp->ro);
+  if (int_to_fe(hv, F2) != s->l_u2.X[1]) return VDF_OK;
+  if (memcmp(s->zi1.data(), zi, 32 * pp->arity) != 0 || !s->zi2[0].is_zero()) return VDF_OK;       // src/nova/proof.rs:386
+  uint64_t r[4];
+  fold_challenge(pp, s->r_U2, s->l_u2, s->T2, r);
+  const Inst f2 = fold_instance(S2, s->r_U2, s->l_u2, s->T2, r);
+  bool good = false;
+  int rc = spartan_replay(S1, s->r_U1.comm_W, s->r_U1.comm_E, s->r_U1.u, s->r_U1.X, s->sp[0], d[0], &good);
+  if (rc != VDF_OK || !good) return rc;
+  rc = spartan_replay(S2, f2.comm_W, f2.comm_E, f2.u, f2.X, s->sp[1], d[1], &good);
+  if (rc != VDF_OK || !good) return rc;
+  *ok = true;
+  return VDF_OK;
+}
+
+// one compressed proof, every check at once (the single verifier)
+int verify_one(const vdf_snark* s, vdf_pp* pp, size_t num_steps, const vdf_fe* z0, const vdf_fe* zi, bool* ok) {
+  *ok = false;
+  IpaDeferred d[2][2];
+  bool good = false;
+  { int rc = verify_replay(s, pp, num_steps, z0, zi, d, &good); if (rc != VDF_OK || !good) return rc; }
+  for (int side = 0; side < 2; ++side) {
+    const Side& sd = pp->s[side];
+    DevBufs bufs(sd.ctx, sd.arena);
+    const size_t n = std::max(d[side][0].n, d[side][1].n);
+    void* d_s;
+    { int rc = bufs.reserve(n); if (rc != VDF_OK) return fail(rc, vdf_last_error(sd.ctx)); }
+    { int rc = bufs.zeros(n, &d_s); if (rc != VDF_OK) return fail(rc, vdf_last_error(sd.ctx)); }
+    for (int q = 0; q < 2; ++q) {
+      int rc = ipa_check_one(sd, d[side][q], d_s, &good);
+      if (rc != VDF_OK || !good) return rc;
+    }
+  }
+  *ok = true;
+  return VDF_OK;
+}
+
+// The deferred checks of many openings of one side as one equation: with independent weights w_o,
+//   MSM(G, sum_o w_o coefficients_o) == sum_o w_o (P_o + sum_j x_j^2 L_j + x_j^-2 R_j) + (sum_o w_o c_o (v_o - ab_o)) gen_u
+// -- one coefficient launch and one MSM over the generators, one MSM over the uploaded small points (gen_u once).
+int check_combined(const Side& sd, const std::vector<const IpaDeferred*>& ds, const std::vector<Fe>& w, bool* ok) {
+  vdf_ctx* ctx = sd.ctx;
+  const Field& F = *sd.F;
+  const Field& Fb = *sd.Fb;
+  *ok = false;
+  const size_t cnt = ds.size();
+  size_t n = 0, npts = 1;
+  for (const IpaDeferred* d : ds) { n = std::max(n, d->n); npts += 1 + d->lr_pts.size(); }
+  std::vector<vdf_ipa_opening> ops(cnt);
+  std::vector<Aff> pts;
+  std::vector<Fe> sc;
+  pts.reserve(npts); sc.reserve(npts);
+  Fe u_sc = zero();
+  for (size_t o = 0; o < cnt; ++o) {
+    const IpaDeferred& d = *ds[o];
+    vdf_ipa_opening& op = ops[o];
+    memcpy(&op.weight, &w[o], 32);
+    op.k = d.k; op.log_m = d.log_m;
+    op.lo = (const vdf_fe*)d.xis.data(); op.hi = (const vdf_fe*)d.xs.data(); op.pattern = (const vdf_fe*)d.a.data();
+    pts.push_back(d.P); sc.push_back(w[o]);
+    for (size_t j = 0; j < d.lr_pts.size(); ++j) { pts.push_back(d.lr_pts[j]); sc.push_back(mul(w[o], d.lr_sc[j], F)); }
+    u_sc = add(u_sc, mul(w[o], mul(int_to_fe(d.q_raw, F), sub(d.v, d.ab, F), F), F), F);
+  }
+  pts.push_back(sd.gen_u); sc.push_back(u_sc);
+  DevBufs bufs(ctx, sd.arena);
+  void* d_c;
+  { int rc = bufs.reserve(n); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+  { int rc = bufs.zeros(n, &d_c); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+  HIPCALL(ctx, vdf_ipa_coefficients(ctx, sd.field, ops.data(), (int)cnt, n, (vdf_fe*)d_c));
+  vdf_jac jg, jp;
+  HIPCALL(ctx, vdf_msm(ctx, sd.gens, 0, (const vdf_fe*)d_c, n, 1, &jg));
+  vdf_bases* pb = nullptr;
+  HIPCALL(ctx, vdf_bases_upload(ctx, sd.curve, (const vdf_affine*)pts.data(), pts.size(), &pb));
+  const int rc = vdf_msm(ctx, pb, 0, (const vdf_fe*)sc.data(), pts.size(), 1, &jp);
+  const std::string err = rc == VDF_OK ? "" : vdf_last_error(ctx);
+  vdf_bases_free(pb);
+  if (rc != VDF_OK) return fail(rc, "vdf_msm (small points): " + err);
+  HIPCALL(ctx, vdf_ctx_sync(ctx));
+  const Aff a1 = jac_to_aff(jg, Fb), a2 = jac_to_aff(jp, Fb);
+  *ok = memcmp(&a1, &a2, sizeof(Aff)) == 0;
+  return VDF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 // verification of the compressed proof (src/nova/proof.rs:383): the two output hashes, the last fold of the instances,
 // then one argument per side
 int vdf_nova_verify_compressed(const vdf_snark* s, vdf_pp* pp, size_t num_steps, const vdf_fe z0[3], const vdf_fe zi[3], int* ok) {
@@ -834,20 +968,6 @@ int vdf_nova_verify_compressed(const vdf_snark* s, vdf_pp* pp, size_t num_steps,
     *ok = 0;
     if (s->t != pp->t || memcmp(s->digest, pp->digest, 32) != 0) return fail(VDF_ERR_BAD_ARG, "proof was made under other public parameters");
     if (num_steps == 0) return VDF_OK;
-    const Side& S1 = pp->s[PRIMARY];
-    const Side& S2 = pp->s[SECONDARY];
-    const Field& F1 = *S1.F;
-    const Field& F2 = *S2.F;
-    if (s->zi1.size() != pp->arity) return VDF_OK;
-    const std::vector<Fe> z0p((const Fe*)z0, (const Fe*)z0 + pp->arity), z0s(1, zero()), zi1 = s->zi1, zi2(s->zi2, s->zi2 + 1);
-    uint64_t hv[4];
-    hash_state(S1.field, pp->params[PRIMARY], from_u64(num_steps, F1), z0p, zi1, to_relaxed(s->r_U2, F2), hv, pp->ro);
-    if (int_to_fe(hv, F2) != s->l_u2.X[0]) return VDF_OK;
-    hash_state(S2.field, pp->params[SECONDARY], from_u64(num_steps, F2), z0s, zi2, to_relaxed(s->r_U1, F1), hv, pp->ro);
-    if (int_to_fe(hv, F2) != s->l_u2.X[1]) return VDF_OK;
-    uint64_t r[4];
-    fold_challenge(pp, s->r_U2, s->l_u2, s->T2, r);
-    const Inst f2 = fold_instance(S2, s->r_U2, s->l_u2, s->T2, r);
     vdf_ctx* ctx = pp->ctx;
     int was_async = 0;
     HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
@@ -855,13 +975,95 @@ int vdf_nova_verify_compressed(const vdf_snark* s, vdf_pp* pp, size_t num_steps,
     HIPCALL(ctx, vdf_ctx_set_async(ctx, 1));
     struct Restore { vdf_ctx* c; int a; ~Restore() { vdf_ctx_sync(c); vdf_ctx_set_async(c, a); } } restore{ctx, was_async};
     bool good = false;
-    int rc = spartan_verify(S1, s->r_U1.comm_W, s->r_U1.comm_E, s->r_U1.u, s->r_U1.X, s->sp[0], &good);
+    int rc = verify_one(s, pp, num_steps, z0, zi, &good);
     if (rc != VDF_OK) return rc;
-    if (!good) return VDF_OK;
-    rc = spartan_verify(S2, f2.comm_W, f2.comm_E, f2.u, f2.X, s->sp[1], &good);
-    if (rc != VDF_OK) return rc;
-    if (!good) return VDF_OK;
-    *ok = (memcmp(s->zi1.data(), zi, 32 * pp->arity) == 0 && s->zi2[0].is_zero()) ? 1 : 0;       // src/nova/proof.rs:386
+    *ok = good ? 1 : 0;
+    return VDF_OK;
+  });
+}
+
+// Many compressed proofs under one parameter set: every proof's exact checks and transcript replay, then its openings' group
+// checks combined per side with 128-bit weights drawn from a transcript of the whole batch -- the weights depend on every
+// proof, statement and step count, so errors in two proofs cannot be made to cancel.  When a combined check fails, the
+// single verifier decides each remaining entry.
+int vdf_nova_verify_compressed_batch(vdf_pp* pp, size_t count, const vdf_snark* const snarks[], const size_t num_steps[],
+                                     const vdf_fe* z0, const vdf_fe* zi, int ok[], int* all_ok) {
+  return nova_guard([&]() -> int {
+    if (!pp || !all_ok) return fail(VDF_ERR_BAD_ARG, "null argument");
+    *all_ok = 0;
+    if (count == 0) { *all_ok = 1; return VDF_OK; }
+    if (!snarks || !num_steps || !z0 || !zi || !ok) return fail(VDF_ERR_BAD_ARG, "null argument");
+    for (size_t q = 0; q < count; ++q) ok[q] = 0;
+    for (size_t q = 0; q < count; ++q) {
+      const vdf_snark* s = snarks[q];
+      if (!s) return fail(VDF_ERR_BAD_ARG, "entry " + std::to_string(q) + ": null proof");
+      if (s->t != pp->t || memcmp(s->digest, pp->digest, 32) != 0)
+        return fail(VDF_ERR_BAD_ARG, "entry " + std::to_string(q) + ": proof was made under other public parameters");
+    }
+    const size_t ar = pp->arity;
+    // the weights' transcript: the parameters, then every entry in full
+    Transcript tw("verify-batch");
+    tw.absorb("pp", pp->digest, 32);
+    { const uint64_t c = count; tw.absorb("count", &c, 8); }
+    std::vector<uint8_t> buf;
+    for (size_t q = 0; q < count; ++q) {
+      buf.resize(vdf_nova_snark_serialized_size(snarks[q]));
+      { int rc = vdf_nova_snark_serialize(snarks[q], buf.data(), buf.size()); if (rc != VDF_OK) return rc; }
+      tw.absorb("proof", buf.data(), buf.size());
+      const uint64_t st = num_steps[q];
+      tw.absorb("steps", &st, 8);
+      tw.absorb("z0", z0 + q * ar, 32 * ar);
+      tw.absorb("zi", zi + q * ar, 32 * ar);
+    }
+    vdf_ctx* ctx = pp->ctx;
+    int was_async = 0;
+    HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
+    HIPCALL(ctx, vdf_ctx_sync(ctx));
+    HIPCALL(ctx, vdf_ctx_set_async(ctx, 1));
+    struct Restore { vdf_ctx* c; int a; ~Restore() { vdf_ctx_sync(c); vdf_ctx_set_async(c, a); } } restore{ctx, was_async};
+    // exact checks and replays; an entry that fails one leaves the batch
+    std::vector<std::array<std::array<IpaDeferred, 2>, 2>> d(count);
+    std::vector<size_t> live;
+    for (size_t q = 0; q < count; ++q) {
+      IpaDeferred dq[2][2];
+      bool good = false;
+      int rc = verify_replay(snarks[q], pp, num_steps[q], z0 + q * ar, zi + q * ar, dq, &good);
+      if (rc != VDF_OK) return rc;
+      if (!good) continue;
+      for (int side = 0; side < 2; ++side)
+        for (int o = 0; o < 2; ++o) d[q][side][o] = std::move(dq[side][o]);
+      live.push_back(q);
+    }
+    // one weight per opening: entry by entry, side by side, W then E (drawn for every entry, so that the weights of an
+    // entry do not depend on which others failed)
+    std::vector<std::array<std::array<Fe, 2>, 2>> w(count);
+    uint64_t raw[4];
+    for (size_t q = 0; q < count; ++q)
+      for (int side = 0; side < 2; ++side)
+        for (int o = 0; o < 2; ++o) w[q][side][o] = tw.challenge("weight", *pp->s[side].F, raw);
+    bool combined = true;
+    if (!live.empty())
+      for (int side = 0; side < 2 && combined; ++side) {
+        std::vector<const IpaDeferred*> ds;
+        std::vector<Fe> ws;
+        for (size_t q : live)
+          for (int o = 0; o < 2; ++o) { ds.push_back(&d[q][side][o]); ws.push_back(w[q][side][o]); }
+        int rc = check_combined(pp->s[side], ds, ws, &combined);
+        if (rc != VDF_OK) return rc;
+      }
+    if (combined) {
+      for (size_t q : live) ok[q] = 1;
+    } else {
+      for (size_t q : live) {                                         // attribution: each remaining entry on its own
+        bool good = false;
+        int rc = verify_one(snarks[q], pp, num_steps[q], z0 + q * ar, zi + q * ar, &good);
+        if (rc != VDF_OK) return rc;
+        ok[q] = good ? 1 : 0;
+      }
+    }
+    int all = 1;
+    for (size_t q = 0; q < count; ++q) all &= ok[q];
+    *all_ok = all;
     return VDF_OK;
   });
 }

@@ -87,6 +87,10 @@ struct vdf_ctx {
   hipEvent_t side_go[4] = {nullptr, nullptr, nullptr, nullptr}, side_done[4] = {nullptr, nullptr, nullptr, nullptr};
   bool job_open = false;
   void* reduce_scratch = nullptr;    // per-workgroup partial sums of vdf_reduce
+  void* ipa_host = nullptr;          // vdf_ipa_coefficients: the openings' factors packed in pinned memory ...
+  void* ipa_dev = nullptr;           // ... and their device copy, ipa_cap bytes each (grown on demand)
+  size_t ipa_cap = 0;
+  hipEvent_t ipa_copied = nullptr;   // the last copy out of ipa_host has been made
   int acc_fill = 0;                  // accumulate workgroups per CU this context's MSMs fill (vdf_ctx_set_accumulate_fill; 0 = process-wide)
   int light_prio = 3;                // wave priority of this context's sort / bucket-reduction kernels (vdf_ctx_set_light_priority)
   hipEvent_t acc_gate = nullptr;     // one-shot: the next bucket-method MSM's accumulation waits for this event (vdf_ctx_gate_accumulate)
@@ -277,8 +281,12 @@ Status vec_clock_probe(int iters, int workgroups, unsigned long long* d_out3, hi
 // ---- snark.hip -------------------------------------------------------------------------
 // vdf_fe* arguments are HOST pointers whose values travel as kernel arguments; void* are device vectors
 Status snark_pair_table(int field, const vdf_fe* lo, const vdf_fe* hi, int k, void* out, hipStream_t s);
-Status snark_pair_table_pattern(int field, const vdf_fe* lo, const vdf_fe* hi, int k, const vdf_fe* pattern, int log_m, void* out,
-                                hipStream_t s);
+// the inner-product argument's coefficients (vdf_ipa_coefficients): the openings packed into a block of
+// snark_ipa_block_bytes(count) bytes, which the kernel reads from device memory
+size_t snark_ipa_block_bytes(int count);
+void snark_ipa_pack(const vdf_ipa_opening* ops, int count, void* block);
+void snark_field_one(int field, vdf_fe* out);             // 1 in Montgomery form
+Status snark_ipa_coefficients(int field, const void* block, int count, size_t n, void* out, hipStream_t s);
 Status snark_fold_halves(int field, int k, void* const v[], const vdf_fe c_lo[], const vdf_fe c_hi[], size_t n, hipStream_t s);
 size_t snark_reduce_scratch_bytes();
 Status snark_reduce(int field, int kind, const void* const tables[], const vdf_fe* u, size_t n, void* scratch, void* out,

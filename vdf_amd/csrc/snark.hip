@@ -6,8 +6,9 @@
 // Everything here is a streaming pass or a reduction over vectors of field elements: HBM-bound, no MFMA.
 // Multilinear tables are MSB-first (index i = sum x_j 2^(k-j)): binding a variable folds the upper half of a table
 // onto its lower half, so every pass reads two coalesced halves.
-//   k_eq_table        out[i] = prod_j (bit_j(i) ? hi_j : lo_j)   (eq(r, .) with lo = 1 - r, hi = r; the inner-
-//                     product argument's generator coefficients with lo = x^-1, hi = x)
+//   k_eq_table        out[i] = prod_j (bit_j(i) ? hi_j : lo_j)   (eq(r, .) with lo = 1 - r, hi = r)
+//   k_ipa_coefficients  out[i] = sum_q w_q pattern_q[low bits of i] prod_j (bit_j ? hi_qj : lo_qj): the inner-product
+//                     argument's generator coefficients (lo = x^-1, hi = x) of one opening, or a weighted sum over many
 //   k_fold_halves     v[i] <- c_lo v[i] + c_hi v[i + h] for up to 8 vectors (sum-check binding: c = (1 - r, r);
 //                     inner-product argument: (x, x^-1) / (x^-1, x))
 //   k_reduce / k_reduce_final   sums over i < h of a per-kind term (dot product, the two sum-check round
@@ -68,35 +69,106 @@ Status snark_pair_table(int field, const vdf_fe* lo, const vdf_fe* hi, int k, vo
   return Status{};
 }
 
-// out[i] = (pair table over the top k bits of i) * pattern[low log_m bits of i]: the coefficient of generator i in the
-// verifier's check of an inner-product argument that stopped at a vector of 2^log_m elements
-struct PatternArgs { FeArg p[16]; int log_m; };
-template <class P>
-__global__ __launch_bounds__(256) void k_eq_table_pattern(PairArgs a, PatternArgs pat, size_t n, char* __restrict__ out) {
-  __builtin_amdgcn_s_setprio(3);
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const size_t hi_idx = i >> pat.log_m;
-  Fe<P> acc = arg_fe<P>(pat.p[i & (((size_t)1 << pat.log_m) - 1)]);
-  for (int j = 0; j < a.k; ++j) {
-    const bool bit = (hi_idx >> (a.k - 1 - j)) & 1;
-    acc = fe_mul(acc, arg_fe<P>(bit ? a.hi[j] : a.lo[j]));
+// ---- the inner-product argument's generator coefficients, for many openings at once ------------------------------
+// out[i] = sum over openings q with i < 2^(k_q + log_m_q) of
+//            w_q * pattern_q[i mod 2^log_m_q] * prod_j (bit (k_q-1-j) of (i >> log_m_q) ? hi_q[j] : lo_q[j])
+// -- the coefficient of generator i in a weighted sum of verifier checks of arguments that stopped at a vector of 2^log_m
+// elements (one opening with w = 1: the single check, vdf_pair_table_pattern).  The factors live in a device block
+// (IpaOpDev per opening) read at wave-uniform addresses.  Wave v owns the 512 entries [512 v, 512 v + 512), its lane l
+// the eight entries 512 v + l + 64 e, e < 8: the index bits that vary within a thread are 6..8, so per opening a thread
+// forms the product over every other bit once (the weight and the pattern element folded in) and expands bits 8, 7, 6 as
+// a three-level product tree -- 14 products for 8 entries, plus k/8 for the prefix, instead of k per entry; the stores of
+// one instruction are 64 consecutive entries.
+struct IpaOpDev { FeArg w, lo[24], hi[24], pat[16]; int k, log_m, pad[6]; };
+static constexpr int IPA_RUN = 8;                              // entries per thread (index bits 6..8)
+
+size_t snark_ipa_block_bytes(int count) { return (size_t)(count > 0 ? count : 0) * sizeof(IpaOpDev); }
+
+void snark_ipa_pack(const vdf_ipa_opening* ops, int count, void* block) {
+  IpaOpDev* d = reinterpret_cast<IpaOpDev*>(block);
+  for (int q = 0; q < count; ++q) {
+    IpaOpDev o{};
+    const vdf_ipa_opening& s = ops[q];
+    o.k = s.k; o.log_m = s.log_m;
+    o.w = to_arg(&s.weight);
+    for (int j = 0; j < s.k; ++j) { o.lo[j] = to_arg(&s.lo[j]); o.hi[j] = to_arg(&s.hi[j]); }
+    for (int j = 0; j < (1 << s.log_m); ++j) o.pat[j] = to_arg(&s.pattern[j]);
+    std::memcpy(&d[q], &o, sizeof(o));
   }
-  fe_store<P>(out + i * 32, acc);
 }
 
-Status snark_pair_table_pattern(int field, const vdf_fe* lo, const vdf_fe* hi, int k, const vdf_fe* pattern, int log_m, void* out,
-                                hipStream_t s) {
-  if (k < 0 || log_m < 0 || log_m > 4 || k + log_m > 24) return Status{VDF_ERR_BAD_LENGTH, "at most 24 variables, pattern of at most 16"};
-  PairArgs a{};
-  a.k = k;
-  for (int j = 0; j < k; ++j) { a.lo[j] = to_arg(&lo[j]); a.hi[j] = to_arg(&hi[j]); }
-  PatternArgs pa{};
-  pa.log_m = log_m;
-  for (int j = 0; j < (1 << log_m); ++j) pa.p[j] = to_arg(&pattern[j]);
-  const size_t n = (size_t)1 << (k + log_m);
-  KTimer kt(s, "k_eq_table_pattern", 32.0 * n);
-  SNARK_DISPATCH(field, k_eq_table_pattern, grid_for(n), dim3(256), 0, s, a, pa, n, reinterpret_cast<char*>(out));
+void snark_field_one(int field, vdf_fe* out) {
+  if (field == VDF_FIELD_FP) { const Fe<FpParams> one = fe_one<FpParams>(); std::memcpy(out, one.v, 32); }
+  else { const Fe<FqParams> one = fe_one<FqParams>(); std::memcpy(out, one.v, 32); }
+}
+
+template <class P>
+__device__ __forceinline__ Fe<P> pick(const IpaOpDev& o, int j, bool bit) {
+  const Fe<P> lo = arg_fe<P>(o.lo[j]), hi = arg_fe<P>(o.hi[j]);      // both uniform loads, a per-lane select
+  return bit ? hi : lo;
+}
+
+template <class P>
+__global__ __launch_bounds__(256) void k_ipa_coefficients(const IpaOpDev* __restrict__ ops, int count, size_t n, char* __restrict__ out) {
+  __builtin_amdgcn_s_setprio(3);
+  const unsigned lane = threadIdx.x & 63;
+  const size_t base = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 * IPA_RUN);      // wave-uniform
+  if (base >= n) return;
+  const size_t i0 = base + lane;
+  Fe<P> acc[IPA_RUN];
+#pragma unroll
+  for (int e = 0; e < IPA_RUN; ++e) acc[e] = fe_zero<P>();
+  for (int q = 0; q < count; ++q) {
+    const IpaOpDev& o = ops[q];
+    const int k = o.k, log_m = o.log_m, K = k + log_m;          // round variable j is index bit K-1-j
+    if (base >> K) continue;                                    // every entry of this wave is past the opening
+    const Fe<P> pw = fe_mul(arg_fe<P>(o.w), fe_load<P>(&o.pat[lane & ((1u << log_m) - 1)]));
+    if (K >= 9) {                                               // bits 6..8 are round bits: the whole run is inside the opening
+      Fe<P> pre = pw;
+      for (int j = 0; j < k; ++j) {
+        const int b = K - 1 - j;
+        if (b >= 6 && b < 9) continue;
+        pre = fe_mul(pre, pick<P>(o, j, (i0 >> b) & 1));
+      }
+      const int j8 = K - 9, j7 = K - 8, j6 = K - 7;
+#pragma unroll
+      for (int b8 = 0; b8 < 2; ++b8) {
+        const Fe<P> s8 = fe_mul(pre, pick<P>(o, j8, b8));
+#pragma unroll
+        for (int b7 = 0; b7 < 2; ++b7) {
+          const Fe<P> s7 = fe_mul(s8, pick<P>(o, j7, b7));
+#pragma unroll
+          for (int b6 = 0; b6 < 2; ++b6) {
+            const int e = 4 * b8 + 2 * b7 + b6;
+            acc[e] = fe_add(acc[e], fe_mul(s7, pick<P>(o, j6, b6)));
+          }
+        }
+      }
+    } else {                                                    // an opening of fewer than 512 entries (base = 0): entry by entry
+#pragma unroll
+      for (int e = 0; e < IPA_RUN; ++e) {
+        const size_t i = i0 + 64 * e;
+        if (i >> K) continue;
+        Fe<P> v = pw;
+        for (int j = 0; j < k; ++j) v = fe_mul(v, pick<P>(o, j, (i >> (K - 1 - j)) & 1));
+        acc[e] = fe_add(acc[e], v);
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < IPA_RUN; ++e) {
+    const size_t i = i0 + 64 * e;
+    if (i < n) fe_store<P>(out + i * 32, acc[e]);
+  }
+}
+
+Status snark_ipa_coefficients(int field, const void* block, int count, size_t n, void* out, hipStream_t s) {
+  if (n == 0) return Status{};
+  const size_t waves = (n + 64 * IPA_RUN - 1) / (64 * IPA_RUN);
+  const dim3 grid((unsigned)((waves + 3) / 4));
+  KTimer kt(s, "k_ipa_coefficients", 32.0 * n);                // one element written per index; the factors are a few KiB
+  SNARK_DISPATCH(field, k_ipa_coefficients, grid, dim3(256), 0, s, reinterpret_cast<const IpaOpDev*>(block), count, n,
+                 reinterpret_cast<char*>(out));
   return Status{};
 }
 

@@ -41,6 +41,12 @@ def tuning_set(**fields) -> HipTuning:
     return t
 
 
+class IpaOpening(C.Structure):
+    """vdf_ipa_opening (include/vdf_hip.h): one opening of an inner-product argument for vdf_ipa_coefficients."""
+    _fields_ = [("weight", C.c_uint64 * 4), ("k", C.c_int), ("log_m", C.c_int), ("lo", C.c_void_p), ("hi", C.c_void_p),
+                ("pattern", C.c_void_p)]
+
+
 class VdfError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"vdf_hip error {code}: {msg}")
@@ -464,6 +470,19 @@ class Context:
 
     def pair_table_pattern(self, field, lo, hi, k, pattern, log_m, out) -> None:
         self._check(lib.vdf_pair_table_pattern(self.handle, field, _ptr(lo), _ptr(hi), k, _ptr(pattern), log_m, _ptr(out)))
+
+    def ipa_coefficients(self, field, openings, n, out) -> None:
+        """out[i] = sum over the openings of weight * pattern[i mod 2^log_m] * prod_j (bit ? hi[j] : lo[j]) (vdf_hip.h);
+        openings: [(weight, lo, hi, pattern)] with Montgomery host arrays of 1, k, k and 2^log_m elements."""
+        ops = (IpaOpening * len(openings))()
+        keep = []
+        for o, (w, lo, hi, pat) in zip(ops, openings):
+            lo, hi, pat = (np.ascontiguousarray(x, dtype="<u8").reshape(-1, 4) for x in (lo, hi, pat))
+            keep += [lo, hi, pat]
+            o.weight = (C.c_uint64 * 4)(*np.ascontiguousarray(w, dtype="<u8").reshape(4).tolist())
+            o.k, o.log_m = lo.shape[0], max(pat.shape[0] - 1, 0).bit_length()
+            o.lo, o.hi, o.pattern = (x.ctypes.data if x.shape[0] else None for x in (lo, hi, pat))
+        self._check(lib.vdf_ipa_coefficients(self.handle, field, ops, len(openings), n, _ptr(out)))
 
     def fold_halves(self, field, vectors, c_lo, c_hi, n) -> None:
         k = len(vectors)

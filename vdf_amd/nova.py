@@ -73,6 +73,7 @@ for _name, _res, _args in [
     ("vdf_nova_synthesis_stats", _i, [C.POINTER(_u64), C.POINTER(_u64)]),
     ("vdf_nova_compress", _i, [_vp, _vp, C.POINTER(_vp)]),
     ("vdf_nova_verify_compressed", _i, [_vp, _vp, _sz, C.POINTER(_Fe * 3), C.POINTER(_Fe * 3), C.POINTER(_i)]),
+    ("vdf_nova_verify_compressed_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_sz), _vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
     ("vdf_nova_snark_free", None, [_vp]),
     ("vdf_nova_snark_size", _sz, [_vp]),
     ("vdf_nova_snark_bytes", _i, [_vp, _vp, _sz]),
@@ -656,3 +657,21 @@ class CompressedNovaVDFProof:     # NovaVDFProof::Compressed, src/nova/proof.rs:
             self.free()
         except Exception:
             pass
+
+
+def verify_compressed_batch(pp: NovaVDFPublicParams, items: Sequence[tuple]) -> list:
+    """Verifies many compressed proofs at once (vdf_nova_verify_compressed_batch): items = [(snark, num_steps, z0, zi), ...];
+    returns one bool per item, each what snark.verify(pp, num_steps, z0, zi) returns."""
+    n = len(items)
+    arity = getattr(pp, "arity", 3)
+    snarks = (_vp * max(n, 1))(*[it[0].handle for it in items])
+    steps = (_sz * max(n, 1))(*[int(it[1]) for it in items])
+    for it in items:
+        if len(it[2]) != arity or len(it[3]) != arity:
+            raise ValueError(f"z0 and zi need {arity} elements each")
+    z0 = _zn([v for it in items for v in it[2]] or [bytes(32)])
+    zi = _zn([v for it in items for v in it[3]] or [bytes(32)])
+    ok = (_i * max(n, 1))()
+    all_ok = C.c_int(0)
+    _check(nova_lib.vdf_nova_verify_compressed_batch(pp.handle, n, snarks, steps, z0, zi, ok, C.byref(all_ok)))
+    return [bool(ok[q]) for q in range(n)]
