@@ -426,6 +426,20 @@ enum { VDF_REDUCE_DOT = 0, VDF_REDUCE_QUADRATIC_ROUND = 1, VDF_REDUCE_R1CS_ROUND
 int  vdf_reduce(vdf_ctx* ctx, int field, int kind, const vdf_fe* const tables[], const vdf_fe* u, size_t n, vdf_fe* out);
 /* out[y] = sum_x eq[x] (A + rho B + rho^2 C)[x, y] for the num_cols columns of the shape (eq: num_cons elements). */
 int  vdf_spmv3_t(vdf_ctx* ctx, const vdf_shape* shape, const vdf_fe* eq, const vdf_fe* rho, vdf_fe* out);
+/* The same passes for many instances of one length at once (the lockstep rounds of vdf_nova_compress_batch); the
+ * instances' pointers and factors travel to the device in one copy per call.  Field sums are exact, so every result equals
+ * that of the single call bit for bit.
+ * vdf_reduce_batch: `count` (<= 512) reductions of one kind over tables of length n; tables = count x (5 for kind 2, else
+ * 2) device pointers, instance by instance; u = count host elements for kind 2 (else ignored, may be NULL); out = count x
+ * nout elements (host, pinned or device), nout = 1, 2, 3, 2 for kinds 0..3.  Two launches in all. */
+int  vdf_reduce_batch(vdf_ctx* ctx, int field, int kind, size_t count, const vdf_fe* const tables[], const vdf_fe* u, size_t n,
+                      vdf_fe* out);
+/* vdf_fold_halves for up to 320 vectors of one length n, each with its own c_lo[t], c_hi[t] (host); one launch. */
+int  vdf_fold_halves_batch(vdf_ctx* ctx, int field, int k, vdf_fe* const v[], const vdf_fe c_lo[], const vdf_fe c_hi[], size_t n);
+/* vdf_spmv3_t for `count` instances (eq[q], rho[q] -> out[q]) over one shape: the column structure is read once per
+ * launch of up to four instances. */
+int  vdf_spmv3_t_batch(vdf_ctx* ctx, const vdf_shape* shape, size_t count, const vdf_fe* const eq[], const vdf_fe rho[],
+                       vdf_fe* const out[]);
 /* One round of the inner-product argument without materialising folded generators: with n_j the current length of
  * a, s[t] the coefficient of original generator t in its folded generator, h = n_j / 2 and r = t mod n_j,
  *   sL[t] = r >= h ? s[t] a[r - h] : 0,   sR[t] = r < h ? s[t] a[r + h] : 0,   t < n,

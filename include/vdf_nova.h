@@ -315,6 +315,16 @@ int  vdf_nova_synthesis_stats(uint64_t* queued, uint64_t* misses);
  * extra generator of the openings is generator number num_gens of the same family.  Self-consistent, bit-exact against
  * the oracle, not interchangeable with nova-snark (unpinned).  Every pass over a vector runs on the GPU. */
 int  vdf_nova_compress(const vdf_proof* proof, vdf_pp* pp, vdf_snark** out);
+/* vdf_nova_compress for many proofs under one parameter set: out[q] serialises to exactly what
+ * vdf_nova_compress(proofs[q], pp) gives, and is freed on its own with vdf_nova_snark_free.  Groups of up to 8 distinct
+ * proofs (fewer when the free device memory does not hold their scratch) move through both sides' arguments in lockstep:
+ * every sum-check round is one reduction and one fold for the whole group, the M-vectors one transposed product, and the
+ * rounds of the openings are spread over the set's compression queues, one proof's MSM sort and host turn under another's
+ * bucket accumulation.  Each proof keeps its own transcript.  A proof named more than once is compressed once; every slot
+ * that names it gets its own copy.  The proofs are left as vdf_nova_compress leaves them.  A null pp or out: VDF_ERR_BAD_ARG;
+ * a null proof, one made under other parameters (VDF_ERR_BAD_ARG) or one with no steps (VDF_ERR_BAD_LENGTH) fails the whole
+ * call before any device work, every out[q] NULL and vdf_nova_last_error naming the entry; count = 0 does nothing. */
+int  vdf_nova_compress_batch(vdf_pp* pp, size_t count, const vdf_proof* const proofs[], vdf_snark* out[]);
 /* NovaVDFProof::verify for the Compressed variant (:383): *ok = 1 iff the two output hashes match the carried
  * instances for num_steps steps from z0, both arguments verify (the secondary one for the instance the verifier
  * folds itself), the carried zi_primary equals zi and zi_secondary == [0]. */

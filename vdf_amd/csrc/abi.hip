@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <thread>
+#include <functional>
 #include <map>
 #include <array>
 #include <new>
@@ -1687,23 +1688,10 @@ int vdf_pair_table(vdf_ctx* ctx, int field, const vdf_fe* lo, const vdf_fe* hi, 
   });
 }
 
-// the openings' factors: packed into the context's pinned block, one copy to its device block, then the kernel (a call
-// waits only for the previous call's copy before it repacks)
-static Status ipa_coefficients(vdf_ctx* ctx, int field, const vdf_ipa_opening* ops, int count, size_t n, void* out) {
-  if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
-  if (count < 0 || count > (1 << 16)) return Status{VDF_ERR_BAD_ARG, "0..65536 openings"};
-  if (count && !ops) return Status{VDF_ERR_BAD_ARG, "null openings"};
-  if (n > ((size_t)1 << 32)) return Status{VDF_ERR_BAD_LENGTH, "at most 2^32 entries"};
-  for (int q = 0; q < count; ++q) {
-    const vdf_ipa_opening& o = ops[q];
-    if (o.k < 0 || o.log_m < 0 || o.log_m > 4 || o.k + o.log_m > 24)
-      return Status{VDF_ERR_BAD_LENGTH, "0..24 variables in all, pattern of 1..16 (opening " + std::to_string(q) + ")"};
-    if (o.k && (!o.lo || !o.hi || ptr_is_device(o.lo) || ptr_is_device(o.hi))) return Status{VDF_ERR_BAD_ARG, kHostScalar};
-    if (!o.pattern || ptr_is_device(o.pattern)) return Status{VDF_ERR_BAD_ARG, kHostScalar};
-  }
-  if (n && !ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, kDevVec};
-  if (n == 0) return Status{};
-  const size_t bytes = vdf::snark_ipa_block_bytes(count);
+// a call's argument block (the openings' factors of vdf_ipa_coefficients, the instances of the batched passes): packed into
+// the context's pinned block, one copy to its device block, then the kernel (a call waits only for the previous call's copy
+// before it repacks); the block is the device copy
+static Status arg_block(vdf_ctx* ctx, size_t bytes, const std::function<void(void*)>& pack, const void** block) {
   if (bytes > ctx->ipa_cap) {
     const size_t cap = std::max(bytes, vdf::snark_ipa_block_bytes(64));
     VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));              // an earlier launch may still read the device block
@@ -1718,11 +1706,31 @@ static Status ipa_coefficients(vdf_ctx* ctx, int field, const vdf_ipa_opening* o
   }
   if (!ctx->ipa_copied) VDF_TRY_HIP(hipEventCreateWithFlags(&ctx->ipa_copied, hipEventDisableTiming));
   if (bytes) {
-    vdf::snark_ipa_pack(ops, count, ctx->ipa_host);
+    pack(ctx->ipa_host);
     VDF_TRY_HIP(hipMemcpyAsync(ctx->ipa_dev, ctx->ipa_host, bytes, hipMemcpyHostToDevice, ctx->stream));
     VDF_TRY_HIP(hipEventRecord(ctx->ipa_copied, ctx->stream));
   }
-  VDF_TRY(vdf::snark_ipa_coefficients(field, ctx->ipa_dev, count, n, out, ctx->stream));
+  *block = ctx->ipa_dev;
+  return Status{};
+}
+
+static Status ipa_coefficients(vdf_ctx* ctx, int field, const vdf_ipa_opening* ops, int count, size_t n, void* out) {
+  if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
+  if (count < 0 || count > (1 << 16)) return Status{VDF_ERR_BAD_ARG, "0..65536 openings"};
+  if (count && !ops) return Status{VDF_ERR_BAD_ARG, "null openings"};
+  if (n > ((size_t)1 << 32)) return Status{VDF_ERR_BAD_LENGTH, "at most 2^32 entries"};
+  for (int q = 0; q < count; ++q) {
+    const vdf_ipa_opening& o = ops[q];
+    if (o.k < 0 || o.log_m < 0 || o.log_m > 4 || o.k + o.log_m > 24)
+      return Status{VDF_ERR_BAD_LENGTH, "0..24 variables in all, pattern of 1..16 (opening " + std::to_string(q) + ")"};
+    if (o.k && (!o.lo || !o.hi || ptr_is_device(o.lo) || ptr_is_device(o.hi))) return Status{VDF_ERR_BAD_ARG, kHostScalar};
+    if (!o.pattern || ptr_is_device(o.pattern)) return Status{VDF_ERR_BAD_ARG, kHostScalar};
+  }
+  if (n && !ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, kDevVec};
+  if (n == 0) return Status{};
+  const void* block = nullptr;
+  VDF_TRY(arg_block(ctx, vdf::snark_ipa_block_bytes(count), [&](void* h) { vdf::snark_ipa_pack(ops, count, h); }, &block));
+  VDF_TRY(vdf::snark_ipa_coefficients(field, block, count, n, out, ctx->stream));
   if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
   return Status{};
 }
@@ -1787,6 +1795,78 @@ int vdf_spmv3_t(vdf_ctx* ctx, const vdf_shape* shape, const vdf_fe* eq, const vd
     vdf::KTimer kt(ctx->stream, "k_spmvt(+heavy cols)", nnz3 * (4 + 4 + 32) + (double)shape->num_cols * (4 + 32));
     VDF_TRY(vdf::snark_spmvt(shape->field, shape->d_t_colptr, shape->d_t_row, shape->d_t_cm, shape->d_t_heavy, shape->t_nheavy,
                              shape->t_nbig, shape->d_dict, eq, rho, shape->num_cols, out, ctx->reduce_scratch, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
+// ---- the same passes for many instances of one length (the lockstep rounds of vdf_nova_compress_batch) -------------
+int vdf_reduce_batch(vdf_ctx* ctx, int field, int kind, size_t count, const vdf_fe* const tables[], const vdf_fe* u, size_t n,
+                     vdf_fe* out) {
+  return guarded(ctx, [&]() -> Status {
+    if (kind < 0 || kind > 3) return Status{VDF_ERR_BAD_ARG, "unknown reduction"};
+    if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
+    if (count > (size_t)vdf::SNARK_REDUCE_BATCH_MAX) return Status{VDF_ERR_BAD_ARG, "0..512 instances"};
+    if (count == 0) return Status{};
+    if (!tables || !out) return Status{VDF_ERR_BAD_ARG, "null argument"};
+    if (kind == 2 && (!u || ptr_is_device(u))) return Status{VDF_ERR_BAD_ARG, kHostScalar};
+    if (kind != 0 && (n < 2 || (n & (n - 1)))) return Status{VDF_ERR_BAD_LENGTH, "length must be a power of two >= 2"};
+    const int ntab = kind == 2 ? 5 : 2, nout = kind == 0 ? 1 : kind == 2 ? 3 : 2;
+    for (size_t i = 0; i < count * ntab; ++i)
+      if (n && !ptr_is_device(tables[i])) return Status{VDF_ERR_BAD_ARG, kDevVec};
+    if (!ctx->reduce_scratch) VDF_TRY_HIP(hipMalloc(&ctx->reduce_scratch, vdf::snark_reduce_scratch_bytes()));
+    const void* block = nullptr;
+    VDF_TRY(arg_block(ctx, count * vdf::snark_reduce_item_bytes(),
+                      [&](void* h) { vdf::snark_reduce_pack(kind, (int)count, reinterpret_cast<const void* const*>(tables), kind == 2 ? u : nullptr, h); },
+                      &block));
+    Staging st(ctx);
+    void* d_out = nullptr;
+    VDF_TRY(st.out(out, count * nout * sizeof(vdf_fe), &d_out));
+    VDF_TRY(vdf::snark_reduce_batch(field, kind, block, (int)count, n, ctx->reduce_scratch, d_out, ctx->stream));
+    return st.finish();
+  });
+}
+
+int vdf_fold_halves_batch(vdf_ctx* ctx, int field, int k, vdf_fe* const v[], const vdf_fe c_lo[], const vdf_fe c_hi[], size_t n) {
+  return guarded(ctx, [&]() -> Status {
+    if (k < 0 || k > vdf::SNARK_FOLD_BATCH_MAX) return Status{VDF_ERR_BAD_ARG, "k must be 0..320"};
+    if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
+    if (k == 0) return Status{};
+    if (n < 2 || (n & (n - 1))) return Status{VDF_ERR_BAD_LENGTH, "length must be a power of two >= 2"};
+    if (!v || !c_lo || !c_hi || ptr_is_device(c_lo) || ptr_is_device(c_hi)) return Status{VDF_ERR_BAD_ARG, kHostScalar};
+    for (int i = 0; i < k; ++i) if (!ptr_is_device(v[i])) return Status{VDF_ERR_BAD_ARG, kDevVec};
+    const void* block = nullptr;
+    VDF_TRY(arg_block(ctx, (size_t)k * vdf::snark_fold_item_bytes(),
+                      [&](void* h) { vdf::snark_fold_pack(k, reinterpret_cast<void* const*>(v), c_lo, c_hi, h); }, &block));
+    VDF_TRY(vdf::snark_fold_halves_batch(field, block, k, n, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
+int vdf_spmv3_t_batch(vdf_ctx* ctx, const vdf_shape* shape, size_t count, const vdf_fe* const eq[], const vdf_fe rho[],
+                      vdf_fe* const out[]) {
+  return guarded(ctx, [&]() -> Status {
+    if (!shape || !shape->ctx || shape->ctx->device != ctx->device) return Status{VDF_ERR_BAD_ARG, "bad shape handle"};
+    if (count > 4096) return Status{VDF_ERR_BAD_ARG, "0..4096 instances"};
+    if (count == 0) return Status{};
+    if (!eq || !out || !rho || ptr_is_device(rho)) return Status{VDF_ERR_BAD_ARG, kHostScalar};
+    for (size_t q = 0; q < count; ++q) if (!ptr_is_device(eq[q]) || !ptr_is_device(out[q])) return Status{VDF_ERR_BAD_ARG, kDevVec};
+    if (!ctx->reduce_scratch) VDF_TRY_HIP(hipMalloc(&ctx->reduce_scratch, vdf::snark_reduce_scratch_bytes()));
+    const void* block = nullptr;
+    VDF_TRY(arg_block(ctx, count * vdf::snark_spmvt_item_bytes(),
+                      [&](void* h) {
+                        vdf::snark_spmvt_pack((int)count, reinterpret_cast<const void* const*>(eq), rho,
+                                              reinterpret_cast<void* const*>(out), h);
+                      },
+                      &block));
+    // as vdf_spmv3_t's, with the column structure read once per launch of up to SPMVT_BATCH instances
+    const double nnz3 = (double)(shape->nnz[0] + shape->nnz[1] + shape->nnz[2]);
+    const double launches = (double)((count + vdf::SPMVT_BATCH - 1) / vdf::SPMVT_BATCH);
+    vdf::KTimer kt(ctx->stream, "k_spmvt_batch(+heavy cols)",
+                   launches * (nnz3 * 8 + (double)shape->num_cols * 4) + (double)count * (nnz3 * 32 + (double)shape->num_cols * 32));
+    VDF_TRY(vdf::snark_spmvt_batch(shape->field, shape->d_t_colptr, shape->d_t_row, shape->d_t_cm, shape->d_t_heavy, shape->t_nheavy,
+                                   shape->t_nbig, shape->d_dict, block, (int)count, shape->num_cols, ctx->reduce_scratch, ctx->stream));
     if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
     return Status{};
   });

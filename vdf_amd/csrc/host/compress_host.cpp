@@ -1,5 +1,6 @@
 // libvdf_nova.so, part 3: NovaVDFProof::compress and verification of the compressed proof: one Spartan-style argument
 // per side of the curve cycle (SS1 / SS2 of src/nova/proof.rs:32-33), after the last secondary instance is folded.
+#include <algorithm>
 #include <thread>
 #include "nova_internal.hpp"
 
@@ -215,130 +216,98 @@ struct IpaJob {
                                    // read after the round's one synchronisation (behind the MSM), not after one of their own
 };
 
-// The same two openings, same transcript, on TWO queues half a round apart.  A round's batched MSM is sort (0.26 ms at
-// 2^19 + 2^18 generators), bucket accumulation (0.91), fix-up and bucket reduction (0.26): only the middle one fills the
-// device, and in lockstep the device idles through the other two and through the host's turn, 15 times.  Here opening W
-// runs on the side's queue and opening E on a second one, E's accumulation gated behind W's whole MSM
-// (vdf_ctx_gate_accumulate): E's sort runs under W's accumulation, E's accumulation under W's host turn and W's next sort,
-// E's reduction under W's next accumulation.  The transcript sees what it saw before -- round by round W's L, R and
-// challenge, then E's -- because only LAUNCHES move: W's next round is enqueued as soon as W's challenge is drawn, before
-// E's points of this round are read.  The bytes of the proof do not change (tests/test_gpu_compress.py compares them with
-// the oracle's lockstep prover).
-constexpr int IPA_MARK = 8;                  // (a library slot, vdf_hip.h: 0..3 on the caller's context are the caller's; prove_step holds 4..7)
-static int ipa_prove_two_queues(const Side& sd, Transcript& tr, IpaJob* jobs, vdf_jac* h_lr) {
-  const Side* pp = &sd;
-  vdf_ctx* cq[2] = {sd.ctx, sd.ctx_b};
-  const Field& F = *sd.F;
-  const Field& Fb = *sd.Fb;
-  uint64_t raw[4];
-  // whatever way this function is left, nothing of it is still on either queue: the caller frees the pinned result slots
-  struct Drain { vdf_ctx* a; vdf_ctx* b; ~Drain() { (void)vdf_ctx_sync(a); (void)vdf_ctx_sync(b); } } drain{cq[0], cq[1]};
-  HIPCALL(cq[1], vdf_ctx_set_async(cq[1], 1));
-  HIPCALL(cq[1], vdf_ctx_wait(cq[1], cq[0]));                          // the E opening's vectors were made on the first queue
-  bool w_marked = false;
-  auto enqueue = [&](int q) -> int {                                   // this round's L and R of opening q, on its queue
-    IpaJob& jb = jobs[q];
-    vdf_ctx* ctx = cq[q];
-    const vdf_fe* ab[2] = {(const vdf_fe*)jb.d_a, (const vdf_fe*)jb.d_b};
-    HIPCALL(ctx, vdf_reduce(ctx, sd.field, VDF_REDUCE_IPA_CROSS, ab, nullptr, jb.nj, (vdf_fe*)jb.cross));        // pinned: no wait here
-    HIPCALL(ctx, vdf_ipa_scalars(ctx, sd.field, (const vdf_fe*)jb.d_a, (const vdf_fe*)jb.d_s, jb.n, jb.nj, (vdf_fe*)jb.d_sL,
-                                 (vdf_fe*)jb.d_sR));
-    if (q == 1 && w_marked) HIPCALL(ctx, vdf_ctx_gate_accumulate(ctx, cq[0], IPA_MARK));
-    const size_t off[2] = {0, 0}, len[2] = {jb.n, jb.n};
-    const vdf_fe* sc[2] = {(const vdf_fe*)jb.d_sL, (const vdf_fe*)jb.d_sR};
-    HIPCALL(ctx, vdf_msm_batch(ctx, pp->gens, 2, off, sc, len, 1, h_lr + 2 * q));
-    if (q == 0) { HIPCALL(ctx, vdf_ctx_mark(ctx, IPA_MARK)); w_marked = true; }
-    return VDF_OK;
-  };
-  auto finish = [&](int q) -> int {                                    // the round's points, challenge and fold of opening q
-    IpaJob& jb = jobs[q];
-    vdf_ctx* ctx = cq[q];
-    HIPCALL(ctx, vdf_ctx_sync(ctx));
-    Aff l0, r0;
-    jac_to_aff2(h_lr[2 * q], h_lr[2 * q + 1], Fb, &l0, &r0);
-    const Aff Lp = pt_to_aff(pt_add(pt_from_aff(l0, Fb), jb.Qtab->mul(jb.cross[0], F), Fb), Fb);
-    const Aff Rp = pt_to_aff(pt_add(pt_from_aff(r0, Fb), jb.Qtab->mul(jb.cross[1], F), Fb), Fb);
-    const Aff lr[2] = {Lp, Rp};
-    tr.absorb_pt(jb.label, lr, 2, Fb);
-    const Fe x = tr.challenge(jb.label, F, raw);
-    const Fe xi = inverse(x, F);
-    vdf_fe* vecs[2] = {(vdf_fe*)jb.d_a, (vdf_fe*)jb.d_b};
-    const Fe c_lo[2] = {x, xi}, c_hi[2] = {xi, x};
-    HIPCALL(ctx, vdf_fold_halves(ctx, sd.field, 2, vecs, (const vdf_fe*)c_lo, (const vdf_fe*)c_hi, jb.nj));
-    HIPCALL(ctx, vdf_scale_pattern(ctx, sd.field, (vdf_fe*)jb.d_s, jb.n, jb.nj, (const vdf_fe*)&xi, (const vdf_fe*)&x));
-    jb.out->L.push_back(Lp); jb.out->R.push_back(Rp);
-    jb.nj >>= 1;
-    return VDF_OK;
-  };
-  for (int q = 0; q < 2; ++q)
-    if (jobs[q].nj > IPA_STOP) { int rc = enqueue(q); if (rc != VDF_OK) return rc; }
-  for (int q = 0; q < 2; ++q) jobs[q].make_q(pp->gen_u, Fb);             // under the first round's MSMs
-  for (;;) {
-    const bool active[2] = {jobs[0].nj > IPA_STOP, jobs[1].nj > IPA_STOP};       // in THIS round (the lockstep loop's `act`)
-    if (!active[0] && !active[1]) break;
-    w_marked = false;
-    for (int q = 0; q < 2; ++q) {
-      if (!active[q]) continue;
-      { int rc = finish(q); if (rc != VDF_OK) return rc; }
-      if (jobs[q].nj > IPA_STOP) { int rc = enqueue(q); if (rc != VDF_OK) return rc; }
-    }
-  }
-  for (int q = 0; q < 2; ++q) {
-    HIPCALL(cq[q], vdf_ctx_sync(cq[q]));
-    jobs[q].out->a.resize(jobs[q].nj);
-    HIPCALL(cq[q], vdf_dev_memcpy(cq[q], jobs[q].out->a.data(), jobs[q].d_a, jobs[q].nj * 32));
-  }
-  return VDF_OK;
-}
+// The rounds of many openings.  A UNIT is one or two openings of one transcript whose L and R go into ONE batched MSM per
+// round (two or four groups: one sort, one accumulate grid, one bucket reduction) on the unit's queue; a unit's round ends
+// with one wait (for its MSM's mark), then job by job its points are absorbed, its challenge drawn and its vectors folded,
+// and its next round is enqueued at once -- before the next unit's points of this round are read.  Only launches move
+// between units: every transcript sees what the test oracle's lockstep prover (ipa_prove_many) gives it -- round by round
+// W's L, R and challenge, then E's -- so the bytes of a proof do not depend on how its openings are grouped.
+//   * one proof, two queues: W and E are units of their own, half a round apart.  A round's batched MSM is sort (0.26 ms at
+//     2^19 + 2^18 generators), bucket accumulation (0.91), fix-up and bucket reduction (0.26): only the middle one fills
+//     the device, and in lockstep the device idles through the other two and through the host's turn, 15 times.  E's
+//     accumulation is gated behind W's whole MSM (vdf_ctx_gate_accumulate): E's sort runs under W's accumulation, E's
+//     accumulation under W's host turn and W's next sort, E's reduction under W's next accumulation.
+//   * one proof, one queue: a single unit of both openings (the oracle's lockstep, one four-group MSM per round).
+//   * K proofs (vdf_nova_compress_batch): a unit per proof, round robin over the side's queues, each unit's accumulation
+//     gated behind the MSM of the unit enqueued just before it on another queue: one proof's sort, tail and host turn
+//     run under another's accumulation.
+constexpr int IPA_MARK = 8;                  // (library slots, vdf_hip.h: 0..3 on the caller's context are the caller's; prove_step holds 4..7)
+constexpr int IPA_UNITS_PER_QUEUE = VDF_MARK_SLOTS - IPA_MARK;
+struct IpaUnit {
+  Transcript* tr;
+  IpaJob* jobs[2];
+  int njobs;
+  vdf_ctx* ctx;                    // its queue
+  int slot;                        // its mark slot on that queue
+  vdf_jac* h_lr;                   // 2 * njobs pinned result points
+};
 
-// Several inner-product arguments in lockstep (the test oracle's ipa_prove_many): statements and values are absorbed job
-// by job; then every round ALL still-active jobs put their L and R into ONE batched MSM (up to four groups: one sort, one
-// accumulate grid, one bucket reduction) before any challenge of the round is drawn, and job by job absorb them, draw
-// their challenge and fold.  h_lr: 2 * jobs pinned result slots.
-int ipa_prove_many(const Side& sd, Transcript& tr, IpaJob* jobs, int njobs, vdf_jac* h_lr) {
+int ipa_prove_units(const Side& sd, IpaUnit* units, int nunits) {
   const Side* pp = &sd;
-  vdf_ctx* ctx = sd.ctx;
   const Field& F = *sd.F;
   const Field& Fb = *sd.Fb;
   uint64_t raw[4];
-  if (njobs < 1 || njobs > 2) return fail(VDF_ERR_BAD_ARG, "one or two openings at a time (four MSMs per batch)");
-  for (int q = 0; q < njobs; ++q) {
-    IpaJob& jb = jobs[q];
-    tr.absorb_pt(jb.label, &jb.P, 1, Fb);
-    tr.absorb_fe(jb.label, &jb.v, 1, F);
-    tr.challenge(jb.label, F, jb.q_raw);
-    jb.nj = jb.n;
-    jb.out->L.clear(); jb.out->R.clear();
-  }
-  if (njobs == 2 && sd.ctx_b) return ipa_prove_two_queues(sd, tr, jobs, h_lr);
-  for (int q = 0; q < njobs; ++q) jobs[q].make_q(pp->gen_u, Fb);
-  for (;;) {
-    IpaJob* act[2];
-    int na = 0;
-    for (int q = 0; q < njobs; ++q) if (jobs[q].nj > IPA_STOP) act[na++] = &jobs[q];
-    if (!na) break;
+  std::vector<vdf_ctx*> queues;
+  for (int u = 0; u < nunits; ++u)
+    if (std::find(queues.begin(), queues.end(), units[u].ctx) == queues.end()) queues.push_back(units[u].ctx);
+  // whatever way this function is left, nothing of it is still on any queue: the caller frees the pinned result slots
+  struct Drain { std::vector<vdf_ctx*>& q; ~Drain() { for (vdf_ctx* c : q) (void)vdf_ctx_sync(c); } } drain{queues};
+  for (vdf_ctx* c : queues)
+    if (c != sd.ctx) {
+      HIPCALL(c, vdf_ctx_set_async(c, 1));
+      HIPCALL(c, vdf_ctx_wait(c, sd.ctx));                            // the openings' vectors were made on the side's queue
+    }
+  for (int u = 0; u < nunits; ++u)
+    for (int j = 0; j < units[u].njobs; ++j) {
+      IpaJob& jb = *units[u].jobs[j];
+      Transcript& tr = *units[u].tr;
+      tr.absorb_pt(jb.label, &jb.P, 1, Fb);
+      tr.absorb_fe(jb.label, &jb.v, 1, F);
+      tr.challenge(jb.label, F, jb.q_raw);
+      jb.nj = jb.n;
+      jb.out->L.clear(); jb.out->R.clear();
+    }
+  auto active = [&](int u) { for (int j = 0; j < units[u].njobs; ++j) if (units[u].jobs[j]->nj > IPA_STOP) return true; return false; };
+  int last = -1;                                                       // the unit enqueued last in this round
+  auto enqueue = [&](int u) -> int {                                   // this round's L and R of the unit's active openings
+    IpaUnit& un = units[u];
+    vdf_ctx* ctx = un.ctx;
     size_t off[4] = {0, 0, 0, 0}, len[4];
     const vdf_fe* sc[4];
-    for (int q = 0; q < na; ++q) {
-      IpaJob& jb = *act[q];
+    int na = 0;
+    for (int j = 0; j < un.njobs; ++j) {
+      IpaJob& jb = *un.jobs[j];
+      if (jb.nj <= IPA_STOP) continue;
       const vdf_fe* ab[2] = {(const vdf_fe*)jb.d_a, (const vdf_fe*)jb.d_b};
       HIPCALL(ctx, vdf_reduce(ctx, sd.field, VDF_REDUCE_IPA_CROSS, ab, nullptr, jb.nj, (vdf_fe*)jb.cross));      // pinned: no wait here
       HIPCALL(ctx, vdf_ipa_scalars(ctx, sd.field, (const vdf_fe*)jb.d_a, (const vdf_fe*)jb.d_s, jb.n, jb.nj, (vdf_fe*)jb.d_sL,
                                    (vdf_fe*)jb.d_sR));
-      sc[2 * q] = (const vdf_fe*)jb.d_sL; sc[2 * q + 1] = (const vdf_fe*)jb.d_sR;
-      len[2 * q] = len[2 * q + 1] = jb.n;
+      sc[2 * na] = (const vdf_fe*)jb.d_sL; sc[2 * na + 1] = (const vdf_fe*)jb.d_sR;
+      len[2 * na] = len[2 * na + 1] = jb.n;
+      ++na;
     }
-    HIPCALL(ctx, vdf_msm_batch(ctx, pp->gens, 2 * na, off, sc, len, 1, h_lr));
-    HIPCALL(ctx, vdf_ctx_sync(ctx));
-    for (int q = 0; q < na; ++q) {
-      IpaJob& jb = *act[q];
+    if (last >= 0 && units[last].ctx != ctx) HIPCALL(ctx, vdf_ctx_gate_accumulate(ctx, units[last].ctx, units[last].slot));
+    HIPCALL(ctx, vdf_msm_batch(ctx, pp->gens, 2 * na, off, sc, len, 1, un.h_lr));
+    HIPCALL(ctx, vdf_ctx_mark(ctx, un.slot));
+    last = u;
+    return VDF_OK;
+  };
+  auto finish = [&](int u) -> int {                                    // the round's points, challenges and folds of the unit
+    IpaUnit& un = units[u];
+    vdf_ctx* ctx = un.ctx;
+    HIPCALL(ctx, vdf_ctx_sync_mark(ctx, un.slot));
+    int a = 0;
+    for (int j = 0; j < un.njobs; ++j) {
+      IpaJob& jb = *un.jobs[j];
+      if (jb.nj <= IPA_STOP) continue;
       Aff l0, r0;
-      jac_to_aff2(h_lr[2 * q], h_lr[2 * q + 1], Fb, &l0, &r0);
+      jac_to_aff2(un.h_lr[2 * a], un.h_lr[2 * a + 1], Fb, &l0, &r0);
+      ++a;
       const Aff Lp = pt_to_aff(pt_add(pt_from_aff(l0, Fb), jb.Qtab->mul(jb.cross[0], F), Fb), Fb);
       const Aff Rp = pt_to_aff(pt_add(pt_from_aff(r0, Fb), jb.Qtab->mul(jb.cross[1], F), Fb), Fb);
       const Aff lr[2] = {Lp, Rp};
-      tr.absorb_pt(jb.label, lr, 2, Fb);
-      const Fe x = tr.challenge(jb.label, F, raw);
+      un.tr->absorb_pt(jb.label, lr, 2, Fb);
+      const Fe x = un.tr->challenge(jb.label, F, raw);
       const Fe xi = inverse(x, F);
       vdf_fe* vecs[2] = {(vdf_fe*)jb.d_a, (vdf_fe*)jb.d_b};
       const Fe c_lo[2] = {x, xi}, c_hi[2] = {xi, x};
@@ -347,12 +316,31 @@ int ipa_prove_many(const Side& sd, Transcript& tr, IpaJob* jobs, int njobs, vdf_
       jb.out->L.push_back(Lp); jb.out->R.push_back(Rp);
       jb.nj >>= 1;
     }
+    return VDF_OK;
+  };
+  for (int u = 0; u < nunits; ++u)
+    if (active(u)) { int rc = enqueue(u); if (rc != VDF_OK) return rc; }
+  for (int u = 0; u < nunits; ++u)                                     // Q and its table: under the first round's MSMs
+    for (int j = 0; j < units[u].njobs; ++j) units[u].jobs[j]->make_q(pp->gen_u, Fb);
+  for (;;) {
+    std::vector<char> act(nunits);                                     // active in THIS round
+    bool any = false;
+    for (int u = 0; u < nunits; ++u) any |= (act[u] = active(u));
+    if (!any) break;
+    last = -1;
+    for (int u = 0; u < nunits; ++u) {
+      if (!act[u]) continue;
+      { int rc = finish(u); if (rc != VDF_OK) return rc; }
+      if (active(u)) { int rc = enqueue(u); if (rc != VDF_OK) return rc; }
+    }
   }
-  HIPCALL(ctx, vdf_ctx_sync(ctx));
-  for (int q = 0; q < njobs; ++q) {
-    jobs[q].out->a.resize(jobs[q].nj);
-    HIPCALL(ctx, vdf_dev_memcpy(ctx, jobs[q].out->a.data(), jobs[q].d_a, jobs[q].nj * 32));
-  }
+  for (vdf_ctx* c : queues) HIPCALL(c, vdf_ctx_sync(c));
+  for (int u = 0; u < nunits; ++u)
+    for (int j = 0; j < units[u].njobs; ++j) {
+      IpaJob& jb = *units[u].jobs[j];
+      jb.out->a.resize(jb.nj);
+      HIPCALL(sd.ctx, vdf_dev_memcpy(sd.ctx, jb.out->a.data(), jb.d_a, jb.nj * 32));
+    }
   return VDF_OK;
 }
 
@@ -387,7 +375,7 @@ struct IpaDeferred {
   uint64_t q_raw[4];
 };
 
-// The transcript order of ipa_prove_many, up to the last check of each opening (sizes, challenges, b's fold, ab).  *ok =
+// The transcript order of ipa_prove_units, up to the last check of each opening (sizes, challenges, b's fold, ab).  *ok =
 // false for a proof that fails a size check or draws a zero challenge.
 int ipa_replay(const Side& sd, Transcript& tr, IpaCheck* jobs, int njobs, IpaDeferred* out, bool* ok) {
   const Field& F = *sd.F;
@@ -496,8 +484,35 @@ int ipa_check_one(const Side& sd, const IpaDeferred& d, void* d_s, bool* ok) {
 // tables of this many entries and fewer finish their sum-check on the host (a power of two; at least 2)
 constexpr size_t SUMCHECK_HOST_TAIL = 512;
 
-int spartan_prove(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, const Fe* X, const void* d_z, const void* d_E,
-                  Spartan* out) {
+// The passes of K proofs' rounds: one launch for all of them (vdf_*_batch), or the single call for one proof (the launches
+// of vdf_nova_compress stay what they were)
+int reduce_k(const Side& sd, int kind, size_t K, const vdf_fe* const* tabs, const Fe* u, size_t n, Fe* out) {
+  vdf_ctx* ctx = sd.ctx;
+  if (K == 1) HIPCALL(ctx, vdf_reduce(ctx, sd.field, kind, tabs, (const vdf_fe*)u, n, (vdf_fe*)out));
+  else HIPCALL(ctx, vdf_reduce_batch(ctx, sd.field, kind, K, tabs, (const vdf_fe*)u, n, (vdf_fe*)out));
+  return VDF_OK;
+}
+int fold_k(const Side& sd, int k, vdf_fe* const* vecs, const Fe* c_lo, const Fe* c_hi, size_t n) {
+  vdf_ctx* ctx = sd.ctx;
+  if (k <= 8) HIPCALL(ctx, vdf_fold_halves(ctx, sd.field, k, vecs, (const vdf_fe*)c_lo, (const vdf_fe*)c_hi, n));
+  else HIPCALL(ctx, vdf_fold_halves_batch(ctx, sd.field, k, vecs, (const vdf_fe*)c_lo, (const vdf_fe*)c_hi, n));
+  return VDF_OK;
+}
+
+// the statement and witness of one side's argument
+struct ProveIn { Aff cW, cE; Fe u; const Fe* X; const void* d_z; const void* d_E; Spartan* out; };
+
+// the scratch vectors of one proof's argument, in elements
+size_t spartan_scratch_elems(const Side& sd) {
+  const Layout L = layout_of(sd);
+  return 5 * L.M + 2 * L.Z + 4 * L.NW + sd.ncols;
+}
+
+// K arguments on one side in lockstep: every round of every sum-check is one reduction and one fold for all K proofs, the
+// M-vectors one transposed product, the openings' rounds ipa_prove_units.  Each proof keeps its own transcript, in the order
+// of the single prover (spartan.py prove): only launches are shared, so every proof's bytes are those it has alone.
+// arena: the block the scratch comes from (K x spartan_scratch_elems), or none.
+int spartan_prove_many(const Side& sd, size_t K, const ProveIn* in, Arena* arena) {
   const Side* pp = &sd;
   vdf_ctx* ctx = sd.ctx;
   const Field& F = *sd.F;
@@ -505,145 +520,218 @@ int spartan_prove(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, con
   if (L.l1 > 24 || L.s > 24) return fail(VDF_ERR_BAD_LENGTH, "shape too large for the compression SNARK (2^24 entries)");
   if (L.NW > pp->num_gens) return fail(VDF_ERR_BAD_LENGTH, "not enough generators");
   const size_t nv = pp->num_vars, nc = pp->num_cons;
-  DevBufs bufs(ctx, sd.arena);
-  { int rc = bufs.reserve(5 * L.M + 2 * L.Z + 4 * L.NW + pp->ncols); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
-  void *d_eq, *d_az, *d_bz, *d_cz, *d_e, *d_cols, *d_mvec, *d_zpad, *d_w, *d_s, *d_sL, *d_sR;
-  for (void** p : {&d_eq, &d_az, &d_bz, &d_cz, &d_e}) { int rc = bufs.zeros(L.M, p); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
-  for (void** p : {&d_mvec, &d_zpad}) { int rc = bufs.zeros(L.Z, p); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
-  for (void** p : {&d_w, &d_s, &d_sL, &d_sR}) { int rc = bufs.zeros(L.NW, p); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
-  { int rc = bufs.zeros(pp->ncols, &d_cols); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
-  vdf_jac* h_lr = nullptr;                        // pinned: four result points of a round's batched MSM, then 2 x 2 cross terms
-  HIPCALL(ctx, vdf_host_alloc(ctx, 4 * sizeof(vdf_jac) + 4 * sizeof(Fe), (void**)&h_lr));
-  struct HostFree { vdf_ctx* c; void* p; ~HostFree() { vdf_host_free(c, p); } } hf{ctx, h_lr};
-  Fe* h_cross = reinterpret_cast<Fe*>(h_lr + 4);
+  struct Bufs { void *eq, *az, *bz, *cz, *e, *cols, *mvec, *zpad, *w, *s, *sL, *sR; };
+  std::vector<Bufs> b(K);
+  DevBufs bufs(ctx, arena);
+  { int rc = bufs.reserve(K * spartan_scratch_elems(sd)); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+  for (size_t q = 0; q < K; ++q) {
+    Bufs& x = b[q];
+    for (void** p : {&x.eq, &x.az, &x.bz, &x.cz, &x.e}) { int rc = bufs.zeros(L.M, p); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+    for (void** p : {&x.mvec, &x.zpad}) { int rc = bufs.zeros(L.Z, p); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+    for (void** p : {&x.w, &x.s, &x.sL, &x.sR}) { int rc = bufs.zeros(L.NW, p); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+    { int rc = bufs.zeros(pp->ncols, &x.cols); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+  }
+  // pinned: per proof four result points of a round's batched MSM, then 2 x 2 cross terms
+  const size_t per_pinned = 4 * sizeof(vdf_jac) + 4 * sizeof(Fe);
+  char* h_pin = nullptr;
+  HIPCALL(ctx, vdf_host_alloc(ctx, K * per_pinned, (void**)&h_pin));
+  struct HostFree { vdf_ctx* c; void* p; ~HostFree() { vdf_host_free(c, p); } } hf{ctx, h_pin};
 
-  Transcript tr("compress");
-  instance_bytes(tr, sd, cW, cE, u, X);
-  HIPCALL(ctx, vdf_spmv3(ctx, pp->shape, (const vdf_fe*)d_z, (vdf_fe*)d_az, (vdf_fe*)d_bz, (vdf_fe*)d_cz));
-  HIPCALL(ctx, vdf_dev_memcpy(ctx, d_e, d_E, nc * 32));
+  std::vector<Transcript> tr(K, Transcript("compress"));
+  std::vector<std::vector<Fe>> rx(K), ry(K);
   uint64_t raw[4];
-  std::vector<Fe> tau(L.s);
-  for (int j = 0; j < L.s; ++j) tau[j] = tr.challenge("tau", F, raw);
-  { int rc = eq_table_dev(sd, tau, d_eq); if (rc != VDF_OK) return rc; }
+  for (size_t q = 0; q < K; ++q) {
+    const ProveIn& p = in[q];
+    instance_bytes(tr[q], sd, p.cW, p.cE, p.u, p.X);
+    HIPCALL(ctx, vdf_spmv3(ctx, pp->shape, (const vdf_fe*)p.d_z, (vdf_fe*)b[q].az, (vdf_fe*)b[q].bz, (vdf_fe*)b[q].cz));
+    HIPCALL(ctx, vdf_dev_memcpy(ctx, b[q].e, p.d_E, nc * 32));
+    std::vector<Fe> tau(L.s);
+    for (int j = 0; j < L.s; ++j) tau[j] = tr[q].challenge("tau", F, raw);
+    { int rc = eq_table_dev(sd, tau, b[q].eq); if (rc != VDF_OK) return rc; }
+    p.out->outer.clear();
+    p.out->inner.clear();
+  }
   // ---- outer sum-check -----------------------------------------------------------------------------------
-  std::vector<Fe> rx;
-  out->outer.clear();
   {
-    const vdf_fe* tabs[5] = {(const vdf_fe*)d_eq, (const vdf_fe*)d_az, (const vdf_fe*)d_bz, (const vdf_fe*)d_cz, (const vdf_fe*)d_e};
-    vdf_fe* vecs[5] = {(vdf_fe*)d_eq, (vdf_fe*)d_az, (vdf_fe*)d_bz, (vdf_fe*)d_cz, (vdf_fe*)d_e};
+    std::vector<const vdf_fe*> tabs(5 * K);
+    std::vector<vdf_fe*> vecs(5 * K);
+    std::vector<Fe> us(K), c_lo(5 * K), c_hi(5 * K);
+    for (size_t q = 0; q < K; ++q) {
+      void* t[5] = {b[q].eq, b[q].az, b[q].bz, b[q].cz, b[q].e};
+      for (int k = 0; k < 5; ++k) { tabs[5 * q + k] = (const vdf_fe*)t[k]; vecs[5 * q + k] = (vdf_fe*)t[k]; }
+      us[q] = in[q].u;
+    }
+    std::vector<std::array<Fe, 3>> ev(K);
     size_t n = L.M;
     for (; n > SUMCHECK_HOST_TAIL; n >>= 1) {
-      std::array<Fe, 3> ev;
-      HIPCALL(ctx, vdf_reduce(ctx, sd.field, VDF_REDUCE_R1CS_ROUND, tabs, (const vdf_fe*)&u, n, (vdf_fe*)ev.data()));
-      tr.absorb_fe("outer", ev.data(), 3, F);
-      const Fe r = tr.challenge("outer", F, raw);
-      const Fe omr = sub(one(F), r, F);
-      const Fe c_lo[5] = {omr, omr, omr, omr, omr}, c_hi[5] = {r, r, r, r, r};
-      HIPCALL(ctx, vdf_fold_halves(ctx, sd.field, 5, vecs, (const vdf_fe*)c_lo, (const vdf_fe*)c_hi, n));
-      out->outer.push_back(ev);
-      rx.push_back(r);
+      { int rc = reduce_k(sd, VDF_REDUCE_R1CS_ROUND, K, tabs.data(), us.data(), n, ev[0].data()); if (rc != VDF_OK) return rc; }
+      for (size_t q = 0; q < K; ++q) {
+        tr[q].absorb_fe("outer", ev[q].data(), 3, F);
+        const Fe r = tr[q].challenge("outer", F, raw);
+        const Fe omr = sub(one(F), r, F);
+        for (int k = 0; k < 5; ++k) { c_lo[5 * q + k] = omr; c_hi[5 * q + k] = r; }
+        in[q].out->outer.push_back(ev[q]);
+        rx[q].push_back(r);
+      }
+      { int rc = fold_k(sd, (int)(5 * K), vecs.data(), c_lo.data(), c_hi.data(), n); if (rc != VDF_OK) return rc; }
     }
     // The last rounds on the HOST: a round over a table of a few hundred entries is two launches, a synchronisation and the
     // transcript -- ~0.25 ms of latency for microseconds of arithmetic -- nine times per sum-check.  The tables come down once
     // (5 x 512 elements) and the same sums, the same challenges and the same folds follow in host arithmetic (exact: the
     // values are the kernels', snark.hip reduce_term<2> / k_fold_halves).
-    std::vector<Fe> hv[5];
     HIPCALL(ctx, vdf_ctx_sync(ctx));
-    for (int k = 0; k < 5; ++k) { hv[k].resize(n); HIPCALL(ctx, vdf_dev_memcpy(ctx, hv[k].data(), vecs[k], n * 32)); }
-    for (; n > 1; n >>= 1) {
-      const size_t h = n / 2;
-      std::array<Fe, 3> ev = {zero(), zero(), zero()};
-      for (size_t i = 0; i < h; ++i) {
-        Fe lo[5], d[5], v[5];
-        for (int k = 0; k < 5; ++k) { lo[k] = hv[k][i]; d[k] = sub(hv[k][h + i], lo[k], F); }
-        auto term = [&](const Fe* w) { return mul(w[0], sub(sub(mul(w[1], w[2], F), mul(u, w[3], F), F), w[4], F), F); };
-        ev[0] = add(ev[0], term(lo), F);
-        for (int k = 0; k < 5; ++k) v[k] = add(lo[k], add(d[k], d[k], F), F);
-        ev[1] = add(ev[1], term(v), F);
-        for (int k = 0; k < 5; ++k) v[k] = add(v[k], d[k], F);
-        ev[2] = add(ev[2], term(v), F);
+    for (size_t q = 0; q < K; ++q) {
+      const Fe u = in[q].u;
+      std::vector<Fe> hv[5];
+      for (int k = 0; k < 5; ++k) { hv[k].resize(n); HIPCALL(ctx, vdf_dev_memcpy(ctx, hv[k].data(), vecs[5 * q + k], n * 32)); }
+      for (size_t m = n; m > 1; m >>= 1) {
+        const size_t h = m / 2;
+        std::array<Fe, 3> e = {zero(), zero(), zero()};
+        for (size_t i = 0; i < h; ++i) {
+          Fe lo[5], d[5], v[5];
+          for (int k = 0; k < 5; ++k) { lo[k] = hv[k][i]; d[k] = sub(hv[k][h + i], lo[k], F); }
+          auto term = [&](const Fe* w) { return mul(w[0], sub(sub(mul(w[1], w[2], F), mul(u, w[3], F), F), w[4], F), F); };
+          e[0] = add(e[0], term(lo), F);
+          for (int k = 0; k < 5; ++k) v[k] = add(lo[k], add(d[k], d[k], F), F);
+          e[1] = add(e[1], term(v), F);
+          for (int k = 0; k < 5; ++k) v[k] = add(v[k], d[k], F);
+          e[2] = add(e[2], term(v), F);
+        }
+        tr[q].absorb_fe("outer", e.data(), 3, F);
+        const Fe r = tr[q].challenge("outer", F, raw);
+        const Fe omr = sub(one(F), r, F);
+        for (int k = 0; k < 5; ++k)
+          for (size_t i = 0; i < h; ++i) hv[k][i] = add(mul(omr, hv[k][i], F), mul(r, hv[k][h + i], F), F);
+        in[q].out->outer.push_back(e);
+        rx[q].push_back(r);
       }
-      tr.absorb_fe("outer", ev.data(), 3, F);
-      const Fe r = tr.challenge("outer", F, raw);
-      const Fe omr = sub(one(F), r, F);
-      for (int k = 0; k < 5; ++k)
-        for (size_t i = 0; i < h; ++i) hv[k][i] = add(mul(omr, hv[k][i], F), mul(r, hv[k][h + i], F), F);
-      out->outer.push_back(ev);
-      rx.push_back(r);
+      Spartan* o = in[q].out;
+      o->claims[0] = hv[1][0]; o->claims[1] = hv[2][0]; o->claims[2] = hv[3][0]; o->claims[3] = hv[4][0];
     }
-    out->claims[0] = hv[1][0]; out->claims[1] = hv[2][0]; out->claims[2] = hv[3][0]; out->claims[3] = hv[4][0];
   }
-  tr.absorb_fe("claims", out->claims, 4, F);
-  const Fe rho = tr.challenge("rho", F, raw);
+  std::vector<Fe> rho(K);
+  for (size_t q = 0; q < K; ++q) {
+    tr[q].absorb_fe("claims", in[q].out->claims, 4, F);
+    rho[q] = tr[q].challenge("rho", F, raw);
+  }
   // ---- inner sum-check -----------------------------------------------------------------------------------
-  void* d_eq_rx = d_az;                                       // the outer tables are spent: reuse one as eq(r_x, .)
-  { int rc = eq_table_dev(sd, rx, d_eq_rx); if (rc != VDF_OK) return rc; }
-  { int rc = m_vector_dev(sd, L, d_eq_rx, rho, d_cols, d_mvec); if (rc != VDF_OK) return rc; }
-  HIPCALL(ctx, vdf_dev_memcpy(ctx, d_zpad, d_z, nv * 32));
-  HIPCALL(ctx, vdf_dev_memcpy(ctx, (char*)d_zpad + L.NW * 32, (const char*)d_z + nv * 32, (1 + NUM_IO) * 32));
-  HIPCALL(ctx, vdf_dev_memcpy(ctx, d_w, d_z, nv * 32));
-  std::vector<Fe> ry;
-  out->inner.clear();
+  // the outer tables are spent: az holds eq(r_x, .)
+  for (size_t q = 0; q < K; ++q) { int rc = eq_table_dev(sd, rx[q], b[q].az); if (rc != VDF_OK) return rc; }
+  if (K == 1) {
+    int rc = m_vector_dev(sd, L, b[0].az, rho[0], b[0].cols, b[0].mvec);
+    if (rc != VDF_OK) return rc;
+  } else {
+    std::vector<const vdf_fe*> eqs(K);
+    std::vector<vdf_fe*> cols(K);
+    for (size_t q = 0; q < K; ++q) { eqs[q] = (const vdf_fe*)b[q].az; cols[q] = (vdf_fe*)b[q].cols; }
+    HIPCALL(ctx, vdf_spmv3_t_batch(ctx, pp->shape, K, eqs.data(), (const vdf_fe*)rho.data(), cols.data()));
+    for (size_t q = 0; q < K; ++q) {                           // M(y) in the padded layout (m_vector_dev)
+      HIPCALL(ctx, vdf_dev_memset(ctx, b[q].mvec, 0, L.Z * 32));
+      HIPCALL(ctx, vdf_dev_memcpy(ctx, b[q].mvec, b[q].cols, nv * 32));
+      HIPCALL(ctx, vdf_dev_memcpy(ctx, (char*)b[q].mvec + L.NW * 32, (const char*)b[q].cols + nv * 32, (1 + NUM_IO) * 32));
+    }
+  }
+  for (size_t q = 0; q < K; ++q) {
+    HIPCALL(ctx, vdf_dev_memcpy(ctx, b[q].zpad, in[q].d_z, nv * 32));
+    HIPCALL(ctx, vdf_dev_memcpy(ctx, (char*)b[q].zpad + L.NW * 32, (const char*)in[q].d_z + nv * 32, (1 + NUM_IO) * 32));
+    HIPCALL(ctx, vdf_dev_memcpy(ctx, b[q].w, in[q].d_z, nv * 32));
+  }
   {
-    const vdf_fe* tabs[2] = {(const vdf_fe*)d_mvec, (const vdf_fe*)d_zpad};
-    vdf_fe* vecs[2] = {(vdf_fe*)d_mvec, (vdf_fe*)d_zpad};
+    std::vector<const vdf_fe*> tabs(2 * K);
+    std::vector<vdf_fe*> vecs(2 * K);
+    std::vector<Fe> c_lo(2 * K), c_hi(2 * K);
+    for (size_t q = 0; q < K; ++q) {
+      tabs[2 * q] = (const vdf_fe*)b[q].mvec; tabs[2 * q + 1] = (const vdf_fe*)b[q].zpad;
+      vecs[2 * q] = (vdf_fe*)b[q].mvec; vecs[2 * q + 1] = (vdf_fe*)b[q].zpad;
+    }
+    std::vector<std::array<Fe, 2>> ev(K);
     size_t n = L.Z;
     for (; n > SUMCHECK_HOST_TAIL; n >>= 1) {
-      std::array<Fe, 2> ev;
-      HIPCALL(ctx, vdf_reduce(ctx, sd.field, VDF_REDUCE_QUADRATIC_ROUND, tabs, nullptr, n, (vdf_fe*)ev.data()));
-      tr.absorb_fe("inner", ev.data(), 2, F);
-      const Fe r = tr.challenge("inner", F, raw);
-      const Fe omr = sub(one(F), r, F);
-      const Fe c_lo[2] = {omr, omr}, c_hi[2] = {r, r};
-      HIPCALL(ctx, vdf_fold_halves(ctx, sd.field, 2, vecs, (const vdf_fe*)c_lo, (const vdf_fe*)c_hi, n));
-      out->inner.push_back(ev);
-      ry.push_back(r);
-    }
-    std::vector<Fe> hv[2];                                      // the last rounds on the host (as in the outer sum-check)
-    HIPCALL(ctx, vdf_ctx_sync(ctx));
-    for (int k = 0; k < 2; ++k) { hv[k].resize(n); HIPCALL(ctx, vdf_dev_memcpy(ctx, hv[k].data(), vecs[k], n * 32)); }
-    for (; n > 1; n >>= 1) {
-      const size_t h = n / 2;
-      std::array<Fe, 2> ev = {zero(), zero()};
-      for (size_t i = 0; i < h; ++i) {
-        const Fe p0 = hv[0][i], p1 = hv[0][h + i], q0 = hv[1][i], q1 = hv[1][h + i];
-        ev[0] = add(ev[0], mul(p0, q0, F), F);
-        ev[1] = add(ev[1], mul(sub(add(p1, p1, F), p0, F), sub(add(q1, q1, F), q0, F), F), F);
+      { int rc = reduce_k(sd, VDF_REDUCE_QUADRATIC_ROUND, K, tabs.data(), nullptr, n, ev[0].data()); if (rc != VDF_OK) return rc; }
+      for (size_t q = 0; q < K; ++q) {
+        tr[q].absorb_fe("inner", ev[q].data(), 2, F);
+        const Fe r = tr[q].challenge("inner", F, raw);
+        const Fe omr = sub(one(F), r, F);
+        c_lo[2 * q] = c_lo[2 * q + 1] = omr; c_hi[2 * q] = c_hi[2 * q + 1] = r;
+        in[q].out->inner.push_back(ev[q]);
+        ry[q].push_back(r);
       }
-      tr.absorb_fe("inner", ev.data(), 2, F);
-      const Fe r = tr.challenge("inner", F, raw);
-      const Fe omr = sub(one(F), r, F);
-      for (int k = 0; k < 2; ++k)
-        for (size_t i = 0; i < h; ++i) hv[k][i] = add(mul(omr, hv[k][i], F), mul(r, hv[k][h + i], F), F);
-      out->inner.push_back(ev);
-      ry.push_back(r);
+      { int rc = fold_k(sd, (int)(2 * K), vecs.data(), c_lo.data(), c_hi.data(), n); if (rc != VDF_OK) return rc; }
+    }
+    HIPCALL(ctx, vdf_ctx_sync(ctx));                            // the last rounds on the host (as in the outer sum-check)
+    for (size_t q = 0; q < K; ++q) {
+      std::vector<Fe> hv[2];
+      for (int k = 0; k < 2; ++k) { hv[k].resize(n); HIPCALL(ctx, vdf_dev_memcpy(ctx, hv[k].data(), vecs[2 * q + k], n * 32)); }
+      for (size_t m = n; m > 1; m >>= 1) {
+        const size_t h = m / 2;
+        std::array<Fe, 2> e = {zero(), zero()};
+        for (size_t i = 0; i < h; ++i) {
+          const Fe p0 = hv[0][i], p1 = hv[0][h + i], q0 = hv[1][i], q1 = hv[1][h + i];
+          e[0] = add(e[0], mul(p0, q0, F), F);
+          e[1] = add(e[1], mul(sub(add(p1, p1, F), p0, F), sub(add(q1, q1, F), q0, F), F), F);
+        }
+        tr[q].absorb_fe("inner", e.data(), 2, F);
+        const Fe r = tr[q].challenge("inner", F, raw);
+        const Fe omr = sub(one(F), r, F);
+        for (int k = 0; k < 2; ++k)
+          for (size_t i = 0; i < h; ++i) hv[k][i] = add(mul(omr, hv[k][i], F), mul(r, hv[k][h + i], F), F);
+        in[q].out->inner.push_back(e);
+        ry[q].push_back(r);
+      }
     }
   }
   // ---- openings ----------------------------------------------------------------------------------------------
-  void* d_eq_ry = d_mvec;                                     // spent: reuse for eq(r_y[1:], .) (NW entries)
-  { std::vector<Fe> rest(ry.begin() + 1, ry.end()); int rc = eq_table_dev(sd, rest, d_eq_ry); if (rc != VDF_OK) return rc; }
-  {
-    const vdf_fe* tabs[2] = {(const vdf_fe*)d_w, (const vdf_fe*)d_eq_ry};
-    HIPCALL(ctx, vdf_reduce(ctx, sd.field, VDF_REDUCE_DOT, tabs, nullptr, L.NW, (vdf_fe*)&out->w_eval));
+  // mvec is spent: reuse it for eq(r_y[1:], .) (NW entries)
+  for (size_t q = 0; q < K; ++q) {
+    std::vector<Fe> rest(ry[q].begin() + 1, ry[q].end());
+    int rc = eq_table_dev(sd, rest, b[q].mvec);
+    if (rc != VDF_OK) return rc;
   }
-  tr.absorb_fe("weval", &out->w_eval, 1, F);
-  // the two openings advance in lockstep (one four-group MSM per round).  W: a = W padded, b = eq(r_y[1:], .);
-  // E: a = E padded to M (fresh copy: d_e was folded by the sum-check), b = eq(r_x, .).  Each needs its own coefficient
-  // and scalar vectors: the E opening's live in buffers the sum-checks are done with.
+  {
+    std::vector<const vdf_fe*> tabs(2 * K);
+    for (size_t q = 0; q < K; ++q) { tabs[2 * q] = (const vdf_fe*)b[q].w; tabs[2 * q + 1] = (const vdf_fe*)b[q].mvec; }
+    std::vector<Fe> we(K);
+    { int rc = reduce_k(sd, VDF_REDUCE_DOT, K, tabs.data(), nullptr, L.NW, we.data()); if (rc != VDF_OK) return rc; }
+    for (size_t q = 0; q < K; ++q) {
+      in[q].out->w_eval = we[q];
+      tr[q].absorb_fe("weval", &in[q].out->w_eval, 1, F);
+    }
+  }
+  // the two openings of a proof: W: a = W padded, b = eq(r_y[1:], .); E: a = E padded to M (fresh copy: e was folded by the
+  // sum-check), b = eq(r_x, .).  Each needs its own coefficient and scalar vectors: the E opening's live in buffers the
+  // sum-checks are done with (eq, bz, cz: M entries each; az holds eq(r_x, .)).
   std::vector<Fe> ones_lo(24, one(F));
-  HIPCALL(ctx, vdf_pair_table(ctx, sd.field, (const vdf_fe*)ones_lo.data(), (const vdf_fe*)ones_lo.data(), L.l1 - 1, (vdf_fe*)d_s));
-  HIPCALL(ctx, vdf_dev_memset(ctx, d_e, 0, L.M * 32));
-  HIPCALL(ctx, vdf_dev_memcpy(ctx, d_e, d_E, nc * 32));
-  void *d_sE = d_eq, *d_sLE = d_bz, *d_sRE = d_cz;            // M entries each, spent by the outer sum-check (d_az holds eq(r_x, .))
-  HIPCALL(ctx, vdf_pair_table(ctx, sd.field, (const vdf_fe*)ones_lo.data(), (const vdf_fe*)ones_lo.data(), L.s, (vdf_fe*)d_sE));
-  IpaJob jobs[2];
-  jobs[0].label = "ipaW"; jobs[0].n = L.NW; jobs[0].d_a = d_w; jobs[0].d_b = d_eq_ry; jobs[0].d_s = d_s; jobs[0].d_sL = d_sL;
-  jobs[0].d_sR = d_sR; jobs[0].v = out->w_eval; jobs[0].P = cW; jobs[0].out = &out->ipaW;
-  jobs[1].label = "ipaE"; jobs[1].n = L.M; jobs[1].d_a = d_e; jobs[1].d_b = d_eq_rx; jobs[1].d_s = d_sE; jobs[1].d_sL = d_sLE;
-  jobs[1].d_sR = d_sRE; jobs[1].v = out->claims[3]; jobs[1].P = cE; jobs[1].out = &out->ipaE;
-  jobs[0].cross = h_cross; jobs[1].cross = h_cross + 2;
-  return ipa_prove_many(sd, tr, jobs, 2, h_lr);
+  std::vector<IpaJob> jobs(2 * K);
+  for (size_t q = 0; q < K; ++q) {
+    Bufs& x = b[q];
+    HIPCALL(ctx, vdf_pair_table(ctx, sd.field, (const vdf_fe*)ones_lo.data(), (const vdf_fe*)ones_lo.data(), L.l1 - 1, (vdf_fe*)x.s));
+    HIPCALL(ctx, vdf_dev_memset(ctx, x.e, 0, L.M * 32));
+    HIPCALL(ctx, vdf_dev_memcpy(ctx, x.e, in[q].d_E, nc * 32));
+    HIPCALL(ctx, vdf_pair_table(ctx, sd.field, (const vdf_fe*)ones_lo.data(), (const vdf_fe*)ones_lo.data(), L.s, (vdf_fe*)x.eq));
+    Fe* h_cross = reinterpret_cast<Fe*>(h_pin + q * per_pinned + 4 * sizeof(vdf_jac));
+    IpaJob& w = jobs[2 * q];
+    IpaJob& e = jobs[2 * q + 1];
+    w.label = "ipaW"; w.n = L.NW; w.d_a = x.w; w.d_b = x.mvec; w.d_s = x.s; w.d_sL = x.sL; w.d_sR = x.sR;
+    w.v = in[q].out->w_eval; w.P = in[q].cW; w.out = &in[q].out->ipaW; w.cross = h_cross;
+    e.label = "ipaE"; e.n = L.M; e.d_a = x.e; e.d_b = x.az; e.d_s = x.eq; e.d_sL = x.bz; e.d_sR = x.cz;
+    e.v = in[q].out->claims[3]; e.P = in[q].cE; e.out = &in[q].out->ipaE; e.cross = h_cross + 2;
+  }
+  std::vector<IpaUnit> units;
+  vdf_jac* h_lr0 = reinterpret_cast<vdf_jac*>(h_pin);
+  if (K == 1 && sd.ctx_b) {                                   // one proof, two queues: each opening a unit of its own
+    units.push_back({&tr[0], {&jobs[0], nullptr}, 1, ctx, IPA_MARK, h_lr0});
+    units.push_back({&tr[0], {&jobs[1], nullptr}, 1, sd.ctx_b, IPA_MARK, h_lr0 + 2});
+  } else {                                                    // a unit per proof, round robin over the side's queues
+    vdf_ctx* qs[2] = {ctx, sd.ctx_b};
+    const size_t nq = sd.ctx_b ? 2 : 1;
+    if ((K + nq - 1) / nq > (size_t)IPA_UNITS_PER_QUEUE) return fail(VDF_ERR_BAD_ARG, "too many proofs in one lockstep group");
+    for (size_t q = 0; q < K; ++q)
+      units.push_back({&tr[q], {&jobs[2 * q], &jobs[2 * q + 1]}, 2, qs[q % nq], IPA_MARK + (int)(q / nq),
+                       reinterpret_cast<vdf_jac*>(h_pin + q * per_pinned)});
+  }
+  return ipa_prove_units(sd, units.data(), (int)units.size());
 }
+
 
 // The verifier's transcript replay of one side's argument: sizes, both sum-checks, M(r_y) on the device, the openings up to
 // their deferred group checks (out[0]: W, out[1]: E).  *ok = false when an exact check fails.
@@ -768,6 +856,93 @@ void spartan_resize(Spartan& p, const Layout& L) {
 // without the primary z_i (32 bytes per element of the step circuit's arity)
 constexpr size_t STATEMENT_WIRE_FIXED = 5 * 32 * 2 + 3 * 32 + 32 + 32;
 inline size_t statement_wire(size_t arity) { return STATEMENT_WIRE_FIXED + 32 * arity; }
+
+// vdf_nova_compress_batch: proofs per lockstep group, and the HBM left free beside the groups' scratch
+constexpr size_t COMPRESS_LOCKSTEP = 8;
+constexpr size_t COMPRESS_HBM_RESERVE = (size_t)2 << 30;
+}  // namespace
+
+namespace {
+// The statement of a compressed proof, and the last secondary instance folded into the running one (NIFS, as a prove_step
+// would) into scratch d_fz / d_fE: the proof keeps its instances; its secondary cross-term buffers (d_abc2, d_T) are
+// overwritten.  *f2: the folded instance.
+int compress_prelude(const vdf_proof* p, vdf_pp* pp, vdf_snark* s, void* d_fz, void* d_fE, Inst* f2) {
+  vdf_ctx* ctx = pp->ctx;
+  const Side& S2 = pp->s[SECONDARY];
+  s->t = pp->t;
+  memcpy(s->digest, pp->digest, 32);
+  s->r_U1 = p->r[PRIMARY].inst; s->r_U2 = p->r[SECONDARY].inst; s->l_u2 = p->l2;
+  s->zi1 = p->zi[PRIMARY];
+  s->zi2[0] = p->zi[SECONDARY][0];
+  vdf_proof* q = const_cast<vdf_proof*>(p);
+  SideState& s2 = q->r[SECONDARY];
+  HIPCALL(ctx, vdf_nifs_cross_term(ctx, S2.shape, (const vdf_fe*)p->d_l2z, (const vdf_fe*)s2.d_abc[0], (const vdf_fe*)s2.d_abc[1],
+                                   (const vdf_fe*)s2.d_abc[2], (const vdf_fe*)&s2.inst.u, (vdf_fe*)s2.d_abc2[0], (vdf_fe*)s2.d_abc2[1],
+                                   (vdf_fe*)s2.d_abc2[2], (vdf_fe*)s2.d_T));
+  vdf_jac jt;
+  HIPCALL(ctx, vdf_msm(ctx, S2.gens, 0, (const vdf_fe*)s2.d_T, S2.num_cons, 1, &jt));
+  s->T2 = jac_to_aff(jt, *S2.Fb);
+  uint64_t r[4];
+  fold_challenge(pp, s->r_U2, s->l_u2, s->T2, r);
+  *f2 = fold_instance(S2, s->r_U2, s->l_u2, s->T2, r);
+  const Fe rf = int_to_fe(r, *S2.F);
+  HIPCALL(ctx, vdf_axpy(ctx, S2.field, (const vdf_fe*)s2.d_z, (const vdf_fe*)&rf, (const vdf_fe*)p->d_l2z, S2.ncols, (vdf_fe*)d_fz));
+  HIPCALL(ctx, vdf_axpy(ctx, S2.field, (const vdf_fe*)s2.d_E, (const vdf_fe*)&rf, (const vdf_fe*)s2.d_T, S2.num_cons, (vdf_fe*)d_fE));
+  return VDF_OK;
+}
+
+// the queues of the two sides' arguments (created on first use; the caller holds pp->aux_mu)
+int compress_queues(vdf_pp* pp) {
+  vdf_ctx* ctx = pp->ctx;
+  if (!pp->aux_ctx) {
+    const int dev = vdf_ctx_device(ctx);
+    if (vdf_ctx_create_pooled(&dev, 1, VDF_QUEUE_SIDE, &pp->aux_ctx) != VDF_OK) return fail(VDF_ERR_DEVICE, std::string("compress: second context: ") + vdf_last_error(nullptr));
+  }
+  if (!pp->aux_ctx2 && pp->tune.compress_queues) {
+    const int dev = vdf_ctx_device(ctx);
+    if (vdf_ctx_create_pooled(&dev, 1, VDF_QUEUE_SIDE, &pp->aux_ctx2) != VDF_OK) return fail(VDF_ERR_DEVICE, std::string("compress: third context: ") + vdf_last_error(nullptr));
+  }
+  return VDF_OK;
+}
+
+// Both sides' arguments of K proofs: the two are independent (a transcript each), so the secondary side's runs on a second
+// queue of the device, driven by a second host thread, beside the primary's -- its small latency-bound MSMs and its host
+// work (transcript, point arithmetic between rounds) disappear under the primary side's 2^19-generator MSMs.
+// (nova-snark's CompressedSNARK::prove runs the two provers in parallel as well.)  in1 / in2: K statements per side;
+// arena1 / arena2: the sides' scratch blocks.
+int prove_both_sides(vdf_pp* pp, size_t K, const ProveIn* in1, const ProveIn* in2, Arena* arena1, Arena* arena2) {
+  vdf_ctx* ctx = pp->ctx;
+  { int rc = compress_queues(pp); if (rc != VDF_OK) return rc; }
+  vdf_ctx* cb = pp->aux_ctx;
+  HIPCALL(cb, vdf_ctx_set_async(cb, 1));
+  HIPCALL(cb, vdf_ctx_wait(cb, ctx));                                // the folded secondary witnesses were made on the first queue
+  Side S2b = pp->s[SECONDARY];
+  S2b.ctx = cb;
+  int rc2 = VDF_OK;
+  std::string err2;
+  std::thread side2([&] {
+    try { rc2 = spartan_prove_many(S2b, K, in2, arena2); }
+    catch (const std::exception& ex) { rc2 = VDF_ERR_DEVICE; err2 = ex.what(); }
+    if (rc2 != VDF_OK && err2.empty()) err2 = vdf_nova_last_error();  // (the message is per thread: carried over by hand)
+    (void)vdf_ctx_sync(cb);
+  });
+  int rc = VDF_OK;
+  Side S1b = pp->s[PRIMARY];
+  S1b.ctx_b = pp->tune.compress_queues ? pp->aux_ctx2 : nullptr;   // the primary side's second queue
+  try { rc = spartan_prove_many(S1b, K, in1, arena1); }
+  catch (...) { side2.join(); throw; }
+  side2.join();
+  if (rc != VDF_OK) return rc;
+  if (rc2 != VDF_OK) return fail(rc2, "compress, secondary side: " + err2);
+  return VDF_OK;
+}
+
+// the arena of a lockstep group: freed with it (the parameter set keeps only the single prover's blocks)
+struct OwnedArena : Arena {
+  vdf_ctx* ctx;
+  explicit OwnedArena(vdf_ctx* c) : ctx(c) {}
+  ~OwnedArena() { if (p) vdf_dev_free(ctx, p); }
+};
 }  // namespace
 
 extern "C" {
@@ -780,7 +955,6 @@ int vdf_nova_compress(const vdf_proof* p, vdf_pp* pp, vdf_snark** out) {
     if (p->i == 0) return fail(VDF_ERR_BAD_LENGTH, "nothing to compress");
     { int rc = finalize_l2(p); if (rc != VDF_OK) return rc; }
     vdf_ctx* ctx = pp->ctx;
-    const Side& S1 = pp->s[PRIMARY];
     const Side& S2 = pp->s[SECONDARY];
     int was_async = 0;
     HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
@@ -788,66 +962,95 @@ int vdf_nova_compress(const vdf_proof* p, vdf_pp* pp, vdf_snark** out) {
     HIPCALL(ctx, vdf_ctx_set_async(ctx, 1));
     struct Restore { vdf_ctx* c; int a; ~Restore() { vdf_ctx_sync(c); vdf_ctx_set_async(c, a); } } restore{ctx, was_async};
     std::unique_ptr<vdf_snark> s(new vdf_snark());
-    s->t = pp->t;
-    memcpy(s->digest, pp->digest, 32);
-    s->r_U1 = p->r[PRIMARY].inst; s->r_U2 = p->r[SECONDARY].inst; s->l_u2 = p->l2;
-    s->zi1 = p->zi[PRIMARY];
-    s->zi2[0] = p->zi[SECONDARY][0];
-    // the last secondary instance is folded into the running one (NIFS, as a prove_step would): into scratch, the proof is
-    // left as it is
-    vdf_proof* q = const_cast<vdf_proof*>(p);
-    SideState& s2 = q->r[SECONDARY];
     DevBufs bufs(ctx);
     void *d_fz, *d_fE;
     { int rc = bufs.zeros(S2.ncols, &d_fz); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
     { int rc = bufs.zeros(S2.num_cons, &d_fE); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
-    HIPCALL(ctx, vdf_nifs_cross_term(ctx, S2.shape, (const vdf_fe*)p->d_l2z, (const vdf_fe*)s2.d_abc[0], (const vdf_fe*)s2.d_abc[1],
-                                     (const vdf_fe*)s2.d_abc[2], (const vdf_fe*)&s2.inst.u, (vdf_fe*)s2.d_abc2[0], (vdf_fe*)s2.d_abc2[1],
-                                     (vdf_fe*)s2.d_abc2[2], (vdf_fe*)s2.d_T));
-    vdf_jac jt;
-    HIPCALL(ctx, vdf_msm(ctx, S2.gens, 0, (const vdf_fe*)s2.d_T, S2.num_cons, 1, &jt));
-    s->T2 = jac_to_aff(jt, *S2.Fb);
-    uint64_t r[4];
-    fold_challenge(pp, s->r_U2, s->l_u2, s->T2, r);
-    const Inst f2 = fold_instance(S2, s->r_U2, s->l_u2, s->T2, r);
-    const Fe rf = int_to_fe(r, *S2.F);
-    HIPCALL(ctx, vdf_axpy(ctx, S2.field, (const vdf_fe*)s2.d_z, (const vdf_fe*)&rf, (const vdf_fe*)p->d_l2z, S2.ncols, (vdf_fe*)d_fz));
-    HIPCALL(ctx, vdf_axpy(ctx, S2.field, (const vdf_fe*)s2.d_E, (const vdf_fe*)&rf, (const vdf_fe*)s2.d_T, S2.num_cons, (vdf_fe*)d_fE));
-    // The two arguments are independent (a transcript each): the secondary side's runs on a second queue of the device, driven
-    // by a second host thread, beside the primary's -- its small latency-bound MSMs and its host work (transcript, point
-    // arithmetic between rounds) disappear under the primary side's 2^19-generator MSMs.  (nova-snark's CompressedSNARK::prove
-    // runs the two provers in parallel as well.)
+    Inst f2;
+    { int rc = compress_prelude(p, pp, s.get(), d_fz, d_fE, &f2); if (rc != VDF_OK) return rc; }
     std::lock_guard<std::mutex> aux_lock(pp->aux_mu);
-    if (!pp->aux_ctx) {
-      const int dev = vdf_ctx_device(ctx);
-      if (vdf_ctx_create_pooled(&dev, 1, VDF_QUEUE_SIDE, &pp->aux_ctx) != VDF_OK) return fail(VDF_ERR_DEVICE, std::string("compress: second context: ") + vdf_last_error(nullptr));
-    }
-    if (!pp->aux_ctx2 && pp->tune.compress_queues) {
-      const int dev = vdf_ctx_device(ctx);
-      if (vdf_ctx_create_pooled(&dev, 1, VDF_QUEUE_SIDE, &pp->aux_ctx2) != VDF_OK) return fail(VDF_ERR_DEVICE, std::string("compress: third context: ") + vdf_last_error(nullptr));
-    }
-    vdf_ctx* cb = pp->aux_ctx;
-    HIPCALL(cb, vdf_ctx_set_async(cb, 1));
-    HIPCALL(cb, vdf_ctx_wait(cb, ctx));                                // the folded secondary witness was made on the first queue
-    Side S2b = S2;
-    S2b.ctx = cb;
-    int rc2 = VDF_OK;
-    std::string err2;
-    std::thread side2([&] {
-      try { rc2 = spartan_prove(S2b, f2.comm_W, f2.comm_E, f2.u, f2.X, d_fz, d_fE, &s->sp[1]); }
-      catch (const std::exception& ex) { rc2 = VDF_ERR_DEVICE; err2 = ex.what(); }
-      if (rc2 != VDF_OK && err2.empty()) err2 = vdf_nova_last_error();  // (the message is per thread: carried over by hand)
-      (void)vdf_ctx_sync(cb);
-    });
-    int rc = VDF_OK;
-    Side S1b = S1;
-    S1b.ctx_b = pp->tune.compress_queues ? pp->aux_ctx2 : nullptr;   // the primary side's second opening on a queue of its own
-    try { rc = spartan_prove(S1b, s->r_U1.comm_W, s->r_U1.comm_E, s->r_U1.u, s->r_U1.X, p->r[PRIMARY].d_z, p->r[PRIMARY].d_E, &s->sp[0]); }
-    catch (...) { side2.join(); throw; }
-    side2.join();
-    if (rc != VDF_OK) return rc;
-    if (rc2 != VDF_OK) return fail(rc2, "compress, secondary side: " + err2);
+    const ProveIn in1{s->r_U1.comm_W, s->r_U1.comm_E, s->r_U1.u, s->r_U1.X, p->r[PRIMARY].d_z, p->r[PRIMARY].d_E, &s->sp[0]};
+    const ProveIn in2{f2.comm_W, f2.comm_E, f2.u, f2.X, d_fz, d_fE, &s->sp[1]};
+    { int rc = prove_both_sides(pp, 1, &in1, &in2, &pp->arena[PRIMARY], &pp->arena[SECONDARY]); if (rc != VDF_OK) return rc; }
     *out = s.release();
+    return VDF_OK;
+  });
+}
+
+// Many proofs under one parameter set: groups of up to COMPRESS_LOCKSTEP distinct proofs move through both sides'
+// arguments in lockstep (spartan_prove_many); a proof named more than once is compressed once and copied.
+int vdf_nova_compress_batch(vdf_pp* pp, size_t count, const vdf_proof* const proofs[], vdf_snark* out[]) {
+  return nova_guard([&]() -> int {
+    if (!pp || !out) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (count == 0) return VDF_OK;
+    for (size_t q = 0; q < count; ++q) out[q] = nullptr;
+    if (!proofs) return fail(VDF_ERR_BAD_ARG, "null argument");
+    for (size_t q = 0; q < count; ++q) {
+      const vdf_proof* p = proofs[q];
+      if (!p) return fail(VDF_ERR_BAD_ARG, "entry " + std::to_string(q) + ": null proof");
+      if (p->pp != pp) return fail(VDF_ERR_BAD_ARG, "entry " + std::to_string(q) + ": proof was made under other public parameters");
+      if (p->i == 0) return fail(VDF_ERR_BAD_LENGTH, "entry " + std::to_string(q) + ": nothing to compress");
+    }
+    // distinct proofs in order of first appearance; slot q is a copy of the snark of uniq[which[q]]
+    std::vector<const vdf_proof*> uniq;
+    std::vector<size_t> which(count);
+    for (size_t q = 0; q < count; ++q) {
+      size_t k = 0;
+      while (k < uniq.size() && uniq[k] != proofs[q]) ++k;
+      if (k == uniq.size()) uniq.push_back(proofs[q]);
+      which[q] = k;
+    }
+    for (const vdf_proof* p : uniq) { int rc = finalize_l2(p); if (rc != VDF_OK) return rc; }
+    vdf_ctx* ctx = pp->ctx;
+    const Side& S1 = pp->s[PRIMARY];
+    const Side& S2 = pp->s[SECONDARY];
+    int was_async = 0;
+    HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
+    HIPCALL(ctx, vdf_ctx_sync(ctx));
+    HIPCALL(ctx, vdf_ctx_set_async(ctx, 1));
+    struct Restore { vdf_ctx* c; int a; ~Restore() { vdf_ctx_sync(c); vdf_ctx_set_async(c, a); } } restore{ctx, was_async};
+    // lockstep width: at most COMPRESS_LOCKSTEP proofs, fewer when the free HBM (less a reserve) does not hold their scratch
+    const size_t per_proof = 32 * (spartan_scratch_elems(S1) + spartan_scratch_elems(S2) + S2.ncols + S2.num_cons);
+    size_t width = COMPRESS_LOCKSTEP;
+    {
+      size_t free_b = 0, total_b = 0;
+      HIPCALL(ctx, vdf_dev_mem_info(ctx, &free_b, &total_b));
+      const size_t avail = free_b > COMPRESS_HBM_RESERVE ? free_b - COMPRESS_HBM_RESERVE : 0;
+      width = std::max<size_t>(1, std::min(width, avail / per_proof));
+    }
+    std::vector<std::unique_ptr<vdf_snark>> snarks(uniq.size());
+    std::lock_guard<std::mutex> aux_lock(pp->aux_mu);
+    for (size_t g0 = 0; g0 < uniq.size(); g0 += width) {
+      const size_t K = std::min(width, uniq.size() - g0);
+      DevBufs bufs(ctx);
+      std::vector<void*> d_fz(K), d_fE(K);
+      std::vector<Inst> f2(K);
+      std::vector<ProveIn> in1(K), in2(K);
+      for (size_t q = 0; q < K; ++q) {
+        const vdf_proof* p = uniq[g0 + q];
+        snarks[g0 + q].reset(new vdf_snark());
+        vdf_snark* s = snarks[g0 + q].get();
+        { int rc = bufs.zeros(S2.ncols, &d_fz[q]); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+        { int rc = bufs.zeros(S2.num_cons, &d_fE[q]); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+        { int rc = compress_prelude(p, pp, s, d_fz[q], d_fE[q], &f2[q]); if (rc != VDF_OK) return rc; }
+        in1[q] = {s->r_U1.comm_W, s->r_U1.comm_E, s->r_U1.u, s->r_U1.X, p->r[PRIMARY].d_z, p->r[PRIMARY].d_E, &s->sp[0]};
+        in2[q] = {f2[q].comm_W, f2[q].comm_E, f2[q].u, f2[q].X, d_fz[q], d_fE[q], &s->sp[1]};
+      }
+      OwnedArena a1(ctx), a2(pp->aux_ctx ? pp->aux_ctx : ctx);
+      if (K == 1) {                                                    // a group of one is the single prover's call
+        int rc = prove_both_sides(pp, 1, in1.data(), in2.data(), &pp->arena[PRIMARY], &pp->arena[SECONDARY]);
+        if (rc != VDF_OK) return rc;
+      } else {
+        { int rc = compress_queues(pp); if (rc != VDF_OK) return rc; }
+        a2.ctx = pp->aux_ctx;
+        int rc = prove_both_sides(pp, K, in1.data(), in2.data(), &a1, &a2);
+        if (rc != VDF_OK) return rc;
+      }
+    }
+    for (size_t q = 0; q < count; ++q) {
+      const vdf_snark& s = *snarks[which[q]];
+      out[q] = new vdf_snark(s);
+    }
     return VDF_OK;
   });
 }

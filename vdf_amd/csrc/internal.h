@@ -296,5 +296,21 @@ Status snark_spmvt(int field, const uint32_t* colptr, const uint32_t* rows, cons
                    hipStream_t s);
 Status snark_ipa_scalars(int field, const void* a, const void* sv, size_t n, size_t nj, void* sL, void* sR, hipStream_t s);
 Status snark_scale_pattern(int field, void* sv, size_t n, size_t nj, const vdf_fe* x_lo, const vdf_fe* x_hi, hipStream_t s);
+// many instances at once: pointers and factors packed (snark_*_pack, snark_*_item_bytes() each) into a block the kernels read
+// from device memory
+constexpr int SNARK_FOLD_BATCH_MAX = 320;                 // vectors of one vdf_fold_halves_batch
+constexpr int SNARK_REDUCE_BATCH_MAX = 512;               // instances of one vdf_reduce_batch (their partials fill the reduction scratch)
+constexpr int SPMVT_BATCH = 4;                            // instances per launch of k_spmvt_batch (one accumulator each per lane)
+size_t snark_reduce_item_bytes();
+size_t snark_fold_item_bytes();
+size_t snark_spmvt_item_bytes();
+void snark_reduce_pack(int kind, int count, const void* const tables[], const vdf_fe* u, void* block);
+void snark_fold_pack(int k, void* const v[], const vdf_fe c_lo[], const vdf_fe c_hi[], void* block);
+void snark_spmvt_pack(int count, const void* const eq[], const vdf_fe rho[], void* const out[], void* block);
+Status snark_reduce_batch(int field, int kind, const void* block, int count, size_t n, void* scratch, void* out, hipStream_t s);
+Status snark_fold_halves_batch(int field, const void* block, int k, size_t n, hipStream_t s);
+Status snark_spmvt_batch(int field, const uint32_t* colptr, const uint32_t* rows, const uint32_t* cm, const uint32_t* heavy,
+                         size_t nheavy, size_t nbig, const void* dict, const void* block, int count, size_t ncols, void* scratch,
+                         hipStream_t s);
 
 }  // namespace vdf

@@ -18,6 +18,8 @@
 //                     order; a thread per column, a workgroup per heavy column (the constant column has ~t entries)
 //   k_ipa_scalars     the two scalar vectors whose MSMs over the ORIGINAL generators are a round's L and R
 //   k_scale_pattern   s[t] *= ((t mod n_j) >= n_j / 2) ? x : x^-1
+//   k_reduce_batch / k_fold_halves_batch / k_spmvt_batch   the same passes for many instances of one length at once (the
+//                     lockstep rounds of several proofs: one launch with K times the rows, not K launches)
 #include <cstring>
 #include "internal.h"
 #include "fe.cuh"
@@ -476,6 +478,279 @@ Status snark_scale_pattern(int field, void* sv, size_t n, size_t nj, const vdf_f
   if (n == 0 || (n & (n - 1)) || nj < 2 || (nj & (nj - 1)) || nj > n) return Status{VDF_ERR_BAD_LENGTH, "lengths must be powers of two, 2 <= n_j <= n"};
   KTimer kt(s, "k_scale_pattern", 64.0 * n);
   SNARK_DISPATCH(field, k_scale_pattern, grid_for(n), dim3(256), 0, s, reinterpret_cast<char*>(sv), n, nj, to_arg(x_lo), to_arg(x_hi));
+  return Status{};
+}
+
+// ---- the same passes for many instances at once (vdf_reduce_batch, vdf_fold_halves_batch, vdf_spmv3_t_batch) ----------
+// The instances' pointers and factors live in a device block (the context's argument block, one copy per call) read at
+// wave-uniform addresses; an instance is blockIdx.y of the grid, so a round of K proofs is one launch of K times the rows.
+struct ReduceItemDev { const char* t[5]; FeArg u; };
+struct FoldItemDev { char* v; FeArg c_lo, c_hi; };
+struct SpmvtItemDev { const char* eq; char* out; FeArg rho; };
+
+size_t snark_reduce_item_bytes() { return sizeof(ReduceItemDev); }
+size_t snark_fold_item_bytes() { return sizeof(FoldItemDev); }
+size_t snark_spmvt_item_bytes() { return sizeof(SpmvtItemDev); }
+
+void snark_reduce_pack(int kind, int count, const void* const tables[], const vdf_fe* u, void* block) {
+  const int ntab = kind == 2 ? 5 : 2;
+  ReduceItemDev* d = reinterpret_cast<ReduceItemDev*>(block);
+  for (int q = 0; q < count; ++q) {
+    ReduceItemDev it{};
+    for (int k = 0; k < ntab; ++k) it.t[k] = reinterpret_cast<const char*>(tables[(size_t)q * ntab + k]);
+    if (u) it.u = to_arg(&u[q]);
+    std::memcpy(&d[q], &it, sizeof(it));
+  }
+}
+
+void snark_fold_pack(int k, void* const v[], const vdf_fe c_lo[], const vdf_fe c_hi[], void* block) {
+  FoldItemDev* d = reinterpret_cast<FoldItemDev*>(block);
+  for (int t = 0; t < k; ++t) {
+    FoldItemDev it{};
+    it.v = reinterpret_cast<char*>(v[t]); it.c_lo = to_arg(&c_lo[t]); it.c_hi = to_arg(&c_hi[t]);
+    std::memcpy(&d[t], &it, sizeof(it));
+  }
+}
+
+void snark_spmvt_pack(int count, const void* const eq[], const vdf_fe rho[], void* const out[], void* block) {
+  SpmvtItemDev* d = reinterpret_cast<SpmvtItemDev*>(block);
+  for (int q = 0; q < count; ++q) {
+    SpmvtItemDev it{};
+    it.eq = reinterpret_cast<const char*>(eq[q]); it.out = reinterpret_cast<char*>(out[q]); it.rho = to_arg(&rho[q]);
+    std::memcpy(&d[q], &it, sizeof(it));
+  }
+}
+
+template <class P, int KIND>
+__global__ __launch_bounds__(256) void k_reduce_batch(const ReduceItemDev* __restrict__ items, size_t n, char* __restrict__ partials) {
+  __builtin_amdgcn_s_setprio(3);
+  __shared__ __align__(16) char lds[256 * 3 * 32];
+  constexpr int NOUT = ReduceOuts<KIND>::N;
+  const ReduceItemDev& it = items[blockIdx.y];
+  ReduceArgs a;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) a.t[k] = it.t[k];
+  a.u = it.u;
+  a.n = n;
+  const size_t h = KIND == 0 ? n : n / 2;
+  Fe<P> acc[3] = {fe_zero<P>(), fe_zero<P>(), fe_zero<P>()};
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < h; i += (size_t)gridDim.x * 256) reduce_term<P, KIND>(a, i, h, acc);
+  block_tree<P, NOUT>(acc, lds);
+  const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+  if (threadIdx.x < NOUT) fe_store<P>(partials + (slot * NOUT + threadIdx.x) * 32, fe_load<P>(lds + (size_t)threadIdx.x * 256 * 32));
+}
+
+// one workgroup per instance over that instance's nblocks partials
+template <class P, int NOUT>
+__global__ __launch_bounds__(256) void k_reduce_final_batch(const char* __restrict__ partials, int nblocks, char* __restrict__ out) {
+  __builtin_amdgcn_s_setprio(3);
+  __shared__ __align__(16) char lds[256 * 3 * 32];
+  const char* p = partials + (size_t)blockIdx.x * nblocks * NOUT * 32;
+  Fe<P> acc[3] = {fe_zero<P>(), fe_zero<P>(), fe_zero<P>()};
+  for (int b = threadIdx.x; b < nblocks; b += 256)
+    for (int k = 0; k < NOUT; ++k) acc[k] = fe_add(acc[k], fe_load<P>(p + ((size_t)b * NOUT + k) * 32));
+  block_tree<P, NOUT>(acc, lds);
+  if (threadIdx.x < NOUT)
+    fe_store<P>(out + ((size_t)blockIdx.x * NOUT + threadIdx.x) * 32, fe_load<P>(lds + (size_t)threadIdx.x * 256 * 32));
+}
+
+template <class P, int KIND>
+static Status reduce_batch_launch(const void* block, int count, size_t n, void* scratch, void* out, hipStream_t s) {
+  constexpr int NOUT = ReduceOuts<KIND>::N;
+  const size_t h = KIND == 0 ? n : n / 2;
+  // the grid spans instances x rows: REDUCE_BLOCKS workgroups shared among the instances (at least one each), so the
+  // partials of a call fit the context's reduction scratch for count <= REDUCE_BLOCKS
+  int per = REDUCE_BLOCKS / count;
+  if (per < 1) per = 1;
+  int need = (int)((h + 255) / 256);
+  if (need < 1) need = 1;
+  if (per > need) per = need;
+  hipLaunchKernelGGL((k_reduce_batch<P, KIND>), dim3((unsigned)per, (unsigned)count), dim3(256), 0, s,
+                     reinterpret_cast<const ReduceItemDev*>(block), n, reinterpret_cast<char*>(scratch));
+  hipLaunchKernelGGL((k_reduce_final_batch<P, NOUT>), dim3((unsigned)count), dim3(256), 0, s, reinterpret_cast<const char*>(scratch), per,
+                     reinterpret_cast<char*>(out));
+  VDF_TRY_HIP(hipGetLastError());
+  return Status{};
+}
+
+Status snark_reduce_batch(int field, int kind, const void* block, int count, size_t n, void* scratch, void* out, hipStream_t s) {
+  if (kind < 0 || kind > 3) return Status{VDF_ERR_BAD_ARG, "unknown reduction"};
+  static_assert(SNARK_REDUCE_BATCH_MAX <= REDUCE_BLOCKS, "the partials of a batch fill the reduction scratch");
+  if (count < 0 || count > SNARK_REDUCE_BATCH_MAX) return Status{VDF_ERR_BAD_ARG, "0..512 instances"};
+  if (kind != 0 && (n < 2 || (n & (n - 1)))) return Status{VDF_ERR_BAD_LENGTH, "length must be a power of two >= 2"};
+  if (count == 0) return Status{};
+  KTimer kt(s, "k_reduce_batch", 32.0 * n * (kind == 2 ? 5 : 2) * count);
+#define RB(P, K) reduce_batch_launch<P, K>(block, count, n, scratch, out, s)
+  if (field == VDF_FIELD_FP) return kind == 0 ? RB(FpParams, 0) : kind == 1 ? RB(FpParams, 1) : kind == 2 ? RB(FpParams, 2) : RB(FpParams, 3);
+  if (field == VDF_FIELD_FQ) return kind == 0 ? RB(FqParams, 0) : kind == 1 ? RB(FqParams, 1) : kind == 2 ? RB(FqParams, 2) : RB(FqParams, 3);
+#undef RB
+  return Status{VDF_ERR_BAD_ARG, "unknown field"};
+}
+
+template <class P>
+__global__ __launch_bounds__(256) void k_fold_halves_batch(const FoldItemDev* __restrict__ items, size_t h) {
+  __builtin_amdgcn_s_setprio(3);
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= h) return;
+  const FoldItemDev& it = items[blockIdx.y];
+  char* v = it.v;
+  const Fe<P> lo = fe_load<P>(v + i * 32), hi = fe_load<P>(v + (h + i) * 32);
+  fe_store<P>(v + i * 32, fe_add(fe_mul(arg_fe<P>(it.c_lo), lo), fe_mul(arg_fe<P>(it.c_hi), hi)));
+}
+
+Status snark_fold_halves_batch(int field, const void* block, int k, size_t n, hipStream_t s) {
+  if (k <= 0) return Status{};
+  if (k > SNARK_FOLD_BATCH_MAX) return Status{VDF_ERR_BAD_ARG, "at most 320 vectors"};
+  if (n < 2 || (n & (n - 1))) return Status{VDF_ERR_BAD_LENGTH, "length must be a power of two >= 2"};
+  const size_t h = n / 2;
+  KTimer kt(s, "k_fold_halves_batch", 96.0 * h * k);
+  SNARK_DISPATCH(field, k_fold_halves_batch, dim3((unsigned)((h + 255) / 256), (unsigned)k), dim3(256), 0, s,
+                 reinterpret_cast<const FoldItemDev*>(block), h);
+  return Status{};
+}
+
+// M-vectors of up to SPMVT_BATCH instances in one pass over the column structure: a column's pointers, rows and coefficient
+// indices are read once, each lane carries one accumulator per instance (and the instance's rho, rho^2)
+template <class P, int CB>
+__device__ __forceinline__ void spmvt_entry_batch(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ cm,
+                                                  const char* __restrict__ dict, const SpmvtItemDev* __restrict__ items, int cnt,
+                                                  const Fe<P> (&pw)[CB][2], uint32_t k, Fe<P> (&acc)[CB]) {
+  const uint32_t c = cm[k], ci = c & 0x3FFFFFFFu, mat = c >> 30;
+  const size_t row = rows[k];
+  Fe<P> coef = fe_zero<P>();
+  if (ci > 1) coef = fe_load<P>(dict + (size_t)ci * 32);
+#pragma unroll
+  for (int q = 0; q < CB; ++q) {
+    if (q >= cnt) break;
+    Fe<P> v = fe_load<P>(items[q].eq + row * 32);
+    if (ci == 1) v = fe_neg(v);
+    else if (ci > 1) v = fe_mul(v, coef);
+    if (mat) v = fe_mul(v, pw[q][mat - 1]);
+    acc[q] = fe_add(acc[q], v);
+  }
+}
+
+template <class P, int CB>
+__device__ __forceinline__ void spmvt_powers(const SpmvtItemDev* __restrict__ items, int cnt, Fe<P> (&pw)[CB][2]) {
+#pragma unroll
+  for (int q = 0; q < CB; ++q) {
+    pw[q][0] = q < cnt ? arg_fe<P>(items[q].rho) : fe_zero<P>();
+    pw[q][1] = fe_mul(pw[q][0], pw[q][0]);
+  }
+}
+
+template <class P, int CB>
+__global__ __launch_bounds__(256) void k_spmvt_batch(const uint32_t* __restrict__ colptr, const uint32_t* __restrict__ rows,
+                                                     const uint32_t* __restrict__ cm, const char* __restrict__ dict,
+                                                     const SpmvtItemDev* __restrict__ items, int cnt, size_t ncols) {
+  __builtin_amdgcn_s_setprio(3);
+  const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= ncols) return;
+  const uint32_t lo = colptr[c], hi = colptr[c + 1];
+  if (hi - lo > SPMVT_HEAVY) return;                            // the heavy kernels write this column
+  Fe<P> pw[CB][2], acc[CB];
+  spmvt_powers<P, CB>(items, cnt, pw);
+#pragma unroll
+  for (int q = 0; q < CB; ++q) acc[q] = fe_zero<P>();
+  for (uint32_t k = lo; k < hi; ++k) spmvt_entry_batch<P, CB>(rows, cm, dict, items, cnt, pw, k, acc);
+#pragma unroll
+  for (int q = 0; q < CB; ++q)
+    if (q < cnt) fe_store<P>(items[q].out + c * 32, acc[q]);
+}
+
+// heavy columns: a workgroup per column (part = 1) or SPMVT_PARTS workgroups per column, each over a contiguous chunk,
+// into partials [column][part][instance] that k_spmvt_heavy_sum_batch adds
+template <class P, int CB>
+__global__ __launch_bounds__(256) void k_spmvt_heavy_batch(const uint32_t* __restrict__ heavy, const uint32_t* __restrict__ colptr,
+                                                           const uint32_t* __restrict__ rows, const uint32_t* __restrict__ cm,
+                                                           const char* __restrict__ dict, const SpmvtItemDev* __restrict__ items,
+                                                           int cnt, uint32_t parts, char* __restrict__ partials) {
+  __builtin_amdgcn_s_setprio(3);
+  __shared__ __align__(16) char lds[256 * 32];
+  const uint32_t item = blockIdx.x / parts, part = blockIdx.x % parts;
+  const uint32_t c = heavy[item];
+  const uint32_t lo = colptr[c], hi = colptr[c + 1];
+  const uint32_t chunk = (hi - lo + parts - 1) / parts;
+  const uint32_t k0 = lo + part * chunk, k1 = (k0 + chunk < hi) ? k0 + chunk : hi;
+  Fe<P> pw[CB][2], acc[CB];
+  spmvt_powers<P, CB>(items, cnt, pw);
+#pragma unroll
+  for (int q = 0; q < CB; ++q) acc[q] = fe_zero<P>();
+  for (uint32_t k = k0 + threadIdx.x; k < k1; k += 256) spmvt_entry_batch<P, CB>(rows, cm, dict, items, cnt, pw, k, acc);
+  for (int q = 0; q < cnt; ++q) {                               // one instance at a time through the LDS tree
+    Fe<P> one_acc[3] = {acc[0], fe_zero<P>(), fe_zero<P>()};
+#pragma unroll
+    for (int j = 0; j < CB; ++j) if (j == q) one_acc[0] = acc[j];
+    block_tree<P, 1>(one_acc, lds);
+    if (threadIdx.x == 0) {
+      if (parts == 1) fe_store<P>(items[q].out + (size_t)c * 32, fe_load<P>(lds));
+      else fe_store<P>(partials + ((size_t)blockIdx.x * CB + q) * 32, fe_load<P>(lds));
+    }
+    __syncthreads();
+  }
+}
+
+template <class P, int CB>
+__global__ __launch_bounds__(64) void k_spmvt_heavy_sum_batch(const uint32_t* __restrict__ heavy, const char* __restrict__ partials,
+                                                              const SpmvtItemDev* __restrict__ items) {
+  __builtin_amdgcn_s_setprio(3);
+  __shared__ __align__(16) char lds[64 * 32];
+  const int q = blockIdx.y;
+  fe_store<P>(lds + (size_t)threadIdx.x * 32, fe_load<P>(partials + (((size_t)blockIdx.x * SPMVT_PARTS + threadIdx.x) * CB + q) * 32));
+  __syncthreads();
+  for (int stride = 32; stride >= 1; stride >>= 1) {
+    if ((int)threadIdx.x < stride) {
+      char* p = lds + (size_t)threadIdx.x * 32;
+      fe_store<P>(p, fe_add(fe_load<P>(p), fe_load<P>(p + (size_t)stride * 32)));
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) fe_store<P>(items[q].out + (size_t)heavy[blockIdx.x] * 32, fe_load<P>(lds));
+}
+
+template <class P, int CB>
+static Status spmvt_batch_launch(const uint32_t* colptr, const uint32_t* rows, const uint32_t* cm, const uint32_t* heavy,
+                                 size_t nheavy, size_t nbig, const char* dict, const SpmvtItemDev* items, int cnt, size_t ncols,
+                                 void* scratch, hipStream_t s) {
+  hipLaunchKernelGGL((k_spmvt_batch<P, CB>), grid_for(ncols), dim3(256), 0, s, colptr, rows, cm, dict, items, cnt, ncols);
+  if (nheavy) {
+    // as snark_spmvt: the longest columns shared by SPMVT_PARTS workgroups each, as far as the scratch holds their partials
+    size_t shared = nbig < nheavy ? nbig : nheavy;
+    const size_t room = snark_reduce_scratch_bytes() / ((size_t)SPMVT_PARTS * CB * 32);
+    if (shared > room) shared = room;
+    char* part = reinterpret_cast<char*>(scratch);
+    if (shared) {
+      hipLaunchKernelGGL((k_spmvt_heavy_batch<P, CB>), dim3((unsigned)(shared * SPMVT_PARTS)), dim3(256), 0, s, heavy, colptr, rows,
+                         cm, dict, items, cnt, SPMVT_PARTS, part);
+      hipLaunchKernelGGL((k_spmvt_heavy_sum_batch<P, CB>), dim3((unsigned)shared, (unsigned)cnt), dim3(64), 0, s, heavy,
+                         reinterpret_cast<const char*>(part), items);
+    }
+    if (nheavy > shared)
+      hipLaunchKernelGGL((k_spmvt_heavy_batch<P, CB>), dim3((unsigned)(nheavy - shared)), dim3(256), 0, s, heavy + shared, colptr,
+                         rows, cm, dict, items, cnt, 1u, part);
+  }
+  VDF_TRY_HIP(hipGetLastError());
+  return Status{};
+}
+
+// block: count SpmvtItemDev; launches of up to SPMVT_BATCH instances each, one after the other on the stream (the heavy
+// columns' partials reuse the scratch)
+Status snark_spmvt_batch(int field, const uint32_t* colptr, const uint32_t* rows, const uint32_t* cm, const uint32_t* heavy,
+                         size_t nheavy, size_t nbig, const void* dict, const void* block, int count, size_t ncols, void* scratch,
+                         hipStream_t s) {
+  if (ncols == 0 || count <= 0) return Status{};
+  if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
+  const SpmvtItemDev* items = reinterpret_cast<const SpmvtItemDev*>(block);
+  const char* d = reinterpret_cast<const char*>(dict);
+  for (int q0 = 0; q0 < count; q0 += SPMVT_BATCH) {
+    const int cnt = count - q0 < SPMVT_BATCH ? count - q0 : SPMVT_BATCH;
+    const SpmvtItemDev* it = items + q0;
+#define SB(P, CB) spmvt_batch_launch<P, CB>(colptr, rows, cm, heavy, nheavy, nbig, d, it, cnt, ncols, scratch, s)
+    Status st = field == VDF_FIELD_FP ? (cnt == 1 ? SB(FpParams, 1) : cnt == 2 ? SB(FpParams, 2) : SB(FpParams, SPMVT_BATCH))
+                                      : (cnt == 1 ? SB(FqParams, 1) : cnt == 2 ? SB(FqParams, 2) : SB(FqParams, SPMVT_BATCH));
+#undef SB
+    if (st.code != VDF_OK) return st;
+  }
   return Status{};
 }
 

@@ -499,6 +499,34 @@ class Context:
     def spmv3_t(self, shape: Shape, eq, rho, out) -> None:
         self._check(lib.vdf_spmv3_t(self.handle, shape.handle, _ptr(eq), _ptr(rho), _ptr(out)))
 
+    def reduce_batch(self, field, kind, tables, n, u=None):
+        """vdf_reduce_batch: tables = one list of device vectors per instance (as reduce takes them), u = the instances'
+        host elements for kind 2 (count x 4 limbs); returns (count, nout, 4) limbs."""
+        count = len(tables)
+        nout = 1 if kind == 0 else 3 if kind == 2 else 2
+        out = np.zeros((count, nout, 4), dtype="<u8")
+        flat = [_ptr(x) for ts in tables for x in ts]
+        t = (C.c_void_p * max(len(flat), 1))(*flat)
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype="<u8").reshape(-1, 4)
+        self._check(lib.vdf_reduce_batch(self.handle, field, kind, count, t, _ptr(u), n, _ptr(out)))
+        return out
+
+    def fold_halves_batch(self, field, vectors, c_lo, c_hi, n) -> None:
+        """vdf_fold_halves_batch: up to 320 vectors of length n, c_lo / c_hi one host element each."""
+        k = len(vectors)
+        v = (C.c_void_p * max(k, 1))(*[_ptr(x) for x in vectors])
+        c_lo, c_hi = (np.ascontiguousarray(x, dtype="<u8").reshape(-1, 4) for x in (c_lo, c_hi))
+        self._check(lib.vdf_fold_halves_batch(self.handle, field, k, v, _ptr(c_lo), _ptr(c_hi), n))
+
+    def spmv3_t_batch(self, shape: Shape, eqs, rhos, outs) -> None:
+        """vdf_spmv3_t_batch: outs[q] = spmv3_t(eqs[q], rhos[q]) in one pass over the shape's columns."""
+        count = len(eqs)
+        e = (C.c_void_p * max(count, 1))(*[_ptr(x) for x in eqs])
+        o = (C.c_void_p * max(count, 1))(*[_ptr(x) for x in outs])
+        r = np.ascontiguousarray(rhos, dtype="<u8").reshape(-1, 4)
+        self._check(lib.vdf_spmv3_t_batch(self.handle, shape.handle, count, e, _ptr(r), o))
+
     def ipa_scalars(self, field, a, s, n, nj, sL, sR) -> None:
         self._check(lib.vdf_ipa_scalars(self.handle, field, _ptr(a), _ptr(s), n, nj, _ptr(sL), _ptr(sR)))
 

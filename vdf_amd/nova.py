@@ -72,6 +72,7 @@ for _name, _res, _args in [
     ("vdf_cs_value", _i, [_vp, C.c_uint32, _vp]),
     ("vdf_nova_synthesis_stats", _i, [C.POINTER(_u64), C.POINTER(_u64)]),
     ("vdf_nova_compress", _i, [_vp, _vp, C.POINTER(_vp)]),
+    ("vdf_nova_compress_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_vp)]),
     ("vdf_nova_verify_compressed", _i, [_vp, _vp, _sz, C.POINTER(_Fe * 3), C.POINTER(_Fe * 3), C.POINTER(_i)]),
     ("vdf_nova_verify_compressed_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_sz), _vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
     ("vdf_nova_snark_free", None, [_vp]),
@@ -657,6 +658,18 @@ class CompressedNovaVDFProof:     # NovaVDFProof::Compressed, src/nova/proof.rs:
             self.free()
         except Exception:
             pass
+
+
+def compress_batch(pp: NovaVDFPublicParams, proofs: Sequence["NovaVDFProof"]) -> list:
+    """Compresses many proofs under one parameter set (vdf_nova_compress_batch): one CompressedNovaVDFProof per entry, each
+    serialising to what proof.compress(pp) gives; a proof named twice gets two independent copies."""
+    n = len(proofs)
+    if n == 0:
+        return []
+    hs = (_vp * n)(*[None if p is None else p.handle for p in proofs])
+    out = (_vp * n)()
+    _check(nova_lib.vdf_nova_compress_batch(pp.handle, n, hs, out))
+    return [CompressedNovaVDFProof(out[q], pp) for q in range(n)]
 
 
 def verify_compressed_batch(pp: NovaVDFPublicParams, items: Sequence[tuple]) -> list:
