@@ -440,6 +440,17 @@ int  vdf_fold_halves_batch(vdf_ctx* ctx, int field, int k, vdf_fe* const v[], co
  * launch of up to four instances. */
 int  vdf_spmv3_t_batch(vdf_ctx* ctx, const vdf_shape* shape, size_t count, const vdf_fe* const eq[], const vdf_fe rho[],
                        vdf_fe* const out[]);
+/* Random linear combinations of many instances (vdf_nova_verify_batch), one pass each.
+ * out[i] = sum_j w[j] * v[j][i] for i < n_out, v[j][i] = 0 for i >= n[j] (n[j] <= n_out); w[j] canonical integers below 2^128
+ * (limbs 2 and 3 zero, else VDF_ERR_BAD_ARG); v, out device memory (out may be one of the v[j]); count 1..64.  v Montgomery
+ * gives out Montgomery, ready for vdf_msm(..., is_mont = 1). */
+int  vdf_lincomb_u128(vdf_ctx* ctx, int field, int count, const vdf_fe* const v[], const size_t n[], const vdf_fe w[],
+                      size_t n_out, vdf_fe* out);
+/* out[r] = sum_q rho[q] * ((A z_q)[r] * (B z_q)[r] - u[q] * (C z_q)[r] - E_q[r]) for every row r of `shape`; E[q] == NULL is
+ * the zero vector (E == NULL: all are); u Montgomery (host), rho canonical below 2^128 (host; limbs 2 and 3 zero, else
+ * VDF_ERR_BAD_ARG); z, E, out device memory; count 1..64.  The rows are read once for all instances. */
+int  vdf_relaxed_residual_batch(vdf_ctx* ctx, const vdf_shape* shape, int count, const vdf_fe* const z[], const vdf_fe* const E[],
+                                const vdf_fe u[], const vdf_fe rho[], vdf_fe* out);
 /* One round of the inner-product argument without materialising folded generators: with n_j the current length of
  * a, s[t] the coefficient of original generator t in its folded generator, h = n_j / 2 and r = t mod n_j,
  *   sL[t] = r >= h ? s[t] a[r - h] : 0,   sR[t] = r < h ? s[t] a[r + h] : 0,   t < n,

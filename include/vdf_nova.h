@@ -339,6 +339,17 @@ int  vdf_nova_verify_compressed(const vdf_snark* snark, vdf_pp* pp, size_t num_s
  * count = 0 gives *all_ok = 1. */
 int  vdf_nova_verify_compressed_batch(vdf_pp* pp, size_t count, const vdf_snark* const snarks[], const size_t num_steps[],
                                       const vdf_fe* z0, const vdf_fe* zi, int ok[], int* all_ok);
+/* Many running proofs under one parameter set: ok[q] = what vdf_nova_verify_custom returns for entry q (up to a soundness
+ * error of about 2^-128), *all_ok = 1 iff every entry verifies; z0, zi: count x arity elements.  Each entry's exact checks
+ * (step count, z0, output hashes, the last secondary instance's u and comm_E, zi, every instance's z tail) run on their own;
+ * then per side all live entries' commitments are opened in one MSM over the generators (and one over the commitments), and
+ * their R1CS residuals are summed in one pass over the shape and tested for zero.  The weights are 128 bits each from the
+ * operating system, fresh for every call.  When a combined check fails, every live entry is verified on its own.  The proofs
+ * are left as they were: a chain verified between two steps goes on to the same bytes.  A null pp, all_ok or array:
+ * VDF_ERR_BAD_ARG; a null proof or one made under other parameters fails the call with VDF_ERR_BAD_ARG, a half-folded one
+ * with VDF_ERR_DEVICE, before any device work and with vdf_nova_last_error naming the entry; count = 0 gives *all_ok = 1. */
+int  vdf_nova_verify_batch(vdf_pp* pp, size_t count, const vdf_proof* const proofs[], const size_t num_steps[], const vdf_fe* z0,
+                           const vdf_fe* zi, int ok[], int* all_ok);
 void vdf_nova_snark_free(vdf_snark* snark);
 /* Flat canonical encoding of the two arguments, primary then secondary (little-endian, non-Montgomery, 64-byte points;
  * layout in the implementation and in oracle/wire.py): size, export, and import -- which replaces the arguments of

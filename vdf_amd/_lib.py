@@ -99,6 +99,8 @@ PROTOTYPES = {
     "vdf_reduce_batch": (_i, [_vp, _i, _i, _sz, C.POINTER(_vp), _vp, _sz, _vp]),
     "vdf_fold_halves_batch": (_i, [_vp, _i, _i, C.POINTER(_vp), _vp, _vp, _sz]),
     "vdf_spmv3_t_batch": (_i, [_vp, _vp, _sz, C.POINTER(_vp), _vp, C.POINTER(_vp)]),
+    "vdf_lincomb_u128": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, _vp]),
+    "vdf_relaxed_residual_batch": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp]),
     "vdf_ipa_scalars": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _vp]),
     "vdf_scale_pattern": (_i, [_vp, _i, _vp, _sz, _sz, _vp, _vp]),
     "vdf_fe_mul": (_i, [_vp, _i, _vp, _vp, _sz, _vp]),

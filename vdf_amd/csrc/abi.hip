@@ -1872,6 +1872,61 @@ int vdf_spmv3_t_batch(vdf_ctx* ctx, const vdf_shape* shape, size_t count, const 
   });
 }
 
+// ---- random linear combinations of many instances (vdf_nova_verify_batch) -------------------------------------------
+static bool below_2_128(const vdf_fe& w) { return (w.l[2] | w.l[3]) == 0; }
+
+int vdf_lincomb_u128(vdf_ctx* ctx, int field, int count, const vdf_fe* const v[], const size_t n[], const vdf_fe w[],
+                     size_t n_out, vdf_fe* out) {
+  return guarded(ctx, [&]() -> Status {
+    if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
+    if (count < 1 || count > vdf::LINCOMB_MAX) return Status{VDF_ERR_BAD_ARG, "count must be 1..64"};
+    if (!v || !n || !w || ptr_is_device(w) || ptr_is_device(n)) return Status{VDF_ERR_BAD_ARG, kHostScalar};
+    const void* dv[vdf::LINCOMB_MAX];
+    for (int j = 0; j < count; ++j) {
+      if (!below_2_128(w[j])) return Status{VDF_ERR_BAD_ARG, "weight " + std::to_string(j) + " is not below 2^128"};
+      if (n[j] > n_out) return Status{VDF_ERR_BAD_LENGTH, "vector " + std::to_string(j) + " is longer than the output"};
+      if (n[j] && !ptr_is_device(v[j])) return Status{VDF_ERR_BAD_ARG, kDevVec};
+      dv[j] = v[j];
+    }
+    if (n_out && !ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, kDevVec};
+    VDF_TRY(vdf::vec_lincomb_u128(field, count, dv, n, w, n_out, out, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
+int vdf_relaxed_residual_batch(vdf_ctx* ctx, const vdf_shape* shape, int count, const vdf_fe* const z[], const vdf_fe* const E[],
+                               const vdf_fe u[], const vdf_fe rho[], vdf_fe* out) {
+  return guarded(ctx, [&]() -> Status {
+    // the shape is read-only device data: any context of its device may run over it
+    if (!shape || !shape->ctx || shape->ctx->device != ctx->device) return Status{VDF_ERR_BAD_ARG, "bad shape handle"};
+    if (count < 1 || count > vdf::RESIDUAL_BATCH_MAX) return Status{VDF_ERR_BAD_ARG, "count must be 1..64"};
+    if (!z || !u || !rho || ptr_is_device(u) || ptr_is_device(rho)) return Status{VDF_ERR_BAD_ARG, kHostScalar};
+    for (int q = 0; q < count; ++q) {
+      if (!below_2_128(rho[q])) return Status{VDF_ERR_BAD_ARG, "weight " + std::to_string(q) + " is not below 2^128"};
+      if (!ptr_is_device(z[q]) || (E && E[q] && !ptr_is_device(E[q]))) return Status{VDF_ERR_BAD_ARG, kDevVec};
+    }
+    if (!ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, kDevVec};
+    const void* block = nullptr;
+    VDF_TRY(arg_block(ctx, (size_t)count * vdf::residual_item_bytes(),
+                      [&](void* h) {
+                        vdf::residual_pack(count, reinterpret_cast<const void* const*>(z), reinterpret_cast<const void* const*>(E), u,
+                                           rho, h);
+                      },
+                      &block));
+    // algorithmic bytes: the structure once (row pointers, columns and coefficient indices), per instance the gathered z values,
+    // E and nothing else; the result once
+    const double nnz3 = (double)(shape->nnz[0] + shape->nnz[1] + shape->nnz[2]);
+    size_t with_e = 0;
+    for (int q = 0; q < count; ++q) with_e += E && E[q] ? 1 : 0;
+    const double bytes = (double)shape->num_cons * (3 * 4 + 32) + nnz3 * 8 + (double)count * nnz3 * 32 + (double)with_e * shape->num_cons * 32;
+    VDF_TRY(vdf::vec_relaxed_residual_batch(shape->field, shape->d_rowptr, shape->d_col, shape->d_coef, shape->d_dict, block, count,
+                                            shape->num_cons, shape->d_long_rowlist, shape->n_long_rowlist, out, bytes, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
 int vdf_ipa_scalars(vdf_ctx* ctx, int field, const vdf_fe* a, const vdf_fe* s, size_t n, size_t nj, vdf_fe* sL, vdf_fe* sR) {
   return guarded(ctx, [&]() -> Status {
     if (!all_device({a, s, sL, sR})) return Status{VDF_ERR_BAD_ARG, kDevVec};

@@ -1147,12 +1147,7 @@ int check_combined(const Side& sd, const std::vector<const IpaDeferred*>& ds, co
   HIPCALL(ctx, vdf_ipa_coefficients(ctx, sd.field, ops.data(), (int)cnt, n, (vdf_fe*)d_c));
   vdf_jac jg, jp;
   HIPCALL(ctx, vdf_msm(ctx, sd.gens, 0, (const vdf_fe*)d_c, n, 1, &jg));
-  vdf_bases* pb = nullptr;
-  HIPCALL(ctx, vdf_bases_upload(ctx, sd.curve, (const vdf_affine*)pts.data(), pts.size(), &pb));
-  const int rc = vdf_msm(ctx, pb, 0, (const vdf_fe*)sc.data(), pts.size(), 1, &jp);
-  const std::string err = rc == VDF_OK ? "" : vdf_last_error(ctx);
-  vdf_bases_free(pb);
-  if (rc != VDF_OK) return fail(rc, "vdf_msm (small points): " + err);
+  { int rc = msm_points(sd, pts, sc, &jp); if (rc != VDF_OK) return rc; }
   HIPCALL(ctx, vdf_ctx_sync(ctx));
   const Aff a1 = jac_to_aff(jg, Fb), a2 = jac_to_aff(jp, Fb);
   *ok = memcmp(&a1, &a2, sizeof(Aff)) == 0;
@@ -1160,6 +1155,23 @@ int check_combined(const Side& sd, const std::vector<const IpaDeferred*>& ds, co
 }
 
 }  // namespace
+
+namespace vdfnova {
+
+// sum_j sc[j] pts[j] over a few host points (Montgomery scalars) on the side's context: one upload, one MSM.  *out (host) is
+// ready after vdf_ctx_sync.
+int msm_points(const Side& sd, const std::vector<Aff>& pts, const std::vector<Fe>& sc, vdf_jac* out) {
+  vdf_ctx* ctx = sd.ctx;
+  vdf_bases* pb = nullptr;
+  HIPCALL(ctx, vdf_bases_upload(ctx, sd.curve, (const vdf_affine*)pts.data(), pts.size(), &pb));
+  const int rc = vdf_msm(ctx, pb, 0, (const vdf_fe*)sc.data(), pts.size(), 1, out);
+  const std::string err = rc == VDF_OK ? "" : vdf_last_error(ctx);
+  vdf_bases_free(pb);
+  if (rc != VDF_OK) return fail(rc, "vdf_msm (small points): " + err);
+  return VDF_OK;
+}
+
+}  // namespace vdfnova
 
 extern "C" {
 

@@ -1,6 +1,9 @@
 // libvdf_nova.so, part 2: the reference's Nova proof surface (src/nova/proof.rs:232-392) on top of the kernel ABI
 // (include/vdf_hip.h): public parameters, circuits, prove_step / prove_recursively, verify.  Protocol
 // "vdf-nova-ivc-v1", specified by oracle/nova.py; see include/vdf_nova.h.
+#include <sys/random.h>
+#include <algorithm>
+#include <cerrno>
 #include "nova_internal.hpp"
 
 using namespace vdfnova;
@@ -296,6 +299,95 @@ int check_sat(const Side& sd, const Inst& in, const void* d_z, const void* d_E, 
   HIPCALL(ctx, vdf_vec_is_zero(ctx, (const vdf_fe*)d_T, sd.num_cons, &zero));
   *ok = zero != 0;
   return VDF_OK;
+}
+
+int check_openings_combined(const Side& sd, const std::vector<OpeningTerm>& terms, void* d_scratch, bool* ok) {
+  vdf_ctx* ctx = sd.ctx;
+  *ok = false;
+  size_t n = 0;
+  for (const OpeningTerm& t : terms) n = std::max(n, t.n);
+  if (n == 0) { *ok = true; return VDF_OK; }
+  // sum_j w_j v_j, 64 vectors per launch: every later launch carries the sum so far as its first vector, weight 1
+  const vdf_fe w_one = {{1, 0, 0, 0}};
+  std::vector<const vdf_fe*> v;
+  std::vector<size_t> len;
+  std::vector<vdf_fe> w;
+  for (size_t at = 0; at < terms.size();) {
+    v.clear(); len.clear(); w.clear();
+    if (at) { v.push_back((const vdf_fe*)d_scratch); len.push_back(n); w.push_back(w_one); }
+    for (; at < terms.size() && v.size() < 64; ++at) {
+      v.push_back((const vdf_fe*)terms[at].d_v);
+      len.push_back(terms[at].n);
+      vdf_fe x;
+      memcpy(&x, &terms[at].w, 32);
+      w.push_back(x);
+    }
+    HIPCALL(ctx, vdf_lincomb_u128(ctx, sd.field, (int)v.size(), v.data(), len.data(), w.data(), n, (vdf_fe*)d_scratch));
+  }
+  vdf_jac jg, jp;
+  HIPCALL(ctx, vdf_msm(ctx, sd.gens, 0, (const vdf_fe*)d_scratch, n, 1, &jg));
+  // sum_j w_j C_j over the commitments (the identity adds nothing and is left out)
+  std::vector<Aff> pts;
+  std::vector<Fe> sc;
+  for (const OpeningTerm& t : terms)
+    if (!t.comm.is_id()) { pts.push_back(t.comm); sc.push_back(to_mont(t.w, *sd.F)); }
+  if (!pts.empty()) { int rc = msm_points(sd, pts, sc, &jp); if (rc != VDF_OK) return rc; }
+  HIPCALL(ctx, vdf_ctx_sync(ctx));
+  const Aff a1 = jac_to_aff(jg, *sd.Fb);
+  Aff a2;
+  memset(&a2, 0, sizeof(a2));
+  if (!pts.empty()) a2 = jac_to_aff(jp, *sd.Fb);
+  *ok = memcmp(&a1, &a2, sizeof(Aff)) == 0;
+  return VDF_OK;
+}
+
+int check_residuals_combined(const Side& sd, const std::vector<ResidualTerm>& terms, void* d_scratch, bool* ok) {
+  vdf_ctx* ctx = sd.ctx;
+  *ok = true;
+  for (size_t at = 0; at < terms.size() && *ok; at += 64) {
+    const int cnt = (int)std::min<size_t>(64, terms.size() - at);
+    std::vector<const vdf_fe*> z(cnt), E(cnt);
+    std::vector<vdf_fe> u(cnt), w(cnt);
+    for (int j = 0; j < cnt; ++j) {
+      const ResidualTerm& t = terms[at + j];
+      z[j] = (const vdf_fe*)t.d_z;
+      E[j] = (const vdf_fe*)t.d_E;
+      memcpy(&u[j], &t.u, 32);
+      memcpy(&w[j], &t.w, 32);
+    }
+    HIPCALL(ctx, vdf_relaxed_residual_batch(ctx, sd.shape, cnt, z.data(), E.data(), u.data(), w.data(), (vdf_fe*)d_scratch));
+    int zero = 0;
+    HIPCALL(ctx, vdf_vec_is_zero(ctx, (const vdf_fe*)d_scratch, sd.num_cons, &zero));
+    *ok = zero != 0;
+  }
+  return VDF_OK;
+}
+
+// The checks of a running proof that need no device work but the commitment to the last secondary witness (finalize_l2):
+// the step count, z0, then the two output hashes the last secondary instance carries (RecursiveSNARK::verify's prelude).
+// *ok = false when one fails.
+int running_prelude(const vdf_proof* p, vdf_pp* pp, size_t num_steps, const vdf_fe* z0, bool* ok) {
+  *ok = false;
+  if (num_steps == 0 || p->i != num_steps) return VDF_OK;                  // NovaError::ProofVerifyError
+  if (memcmp(p->z0[PRIMARY].data(), z0, 32 * pp->arity) != 0) return VDF_OK;   // not the chain this proof was started for
+  { int rc = finalize_l2(p); if (rc != VDF_OK) return rc; }
+  const Side& S1 = pp->s[PRIMARY];
+  const Side& S2 = pp->s[SECONDARY];
+  const Field& F1 = *S1.F;
+  const Field& F2 = *S2.F;
+  const std::vector<Fe> z0p((const Fe*)z0, (const Fe*)z0 + pp->arity), z0s(1, zero());
+  uint64_t hv[4];
+  hash_state(S1.field, pp->params[PRIMARY], from_u64(num_steps, F1), z0p, p->zi[PRIMARY], to_relaxed(p->r[SECONDARY].inst, F2), hv, pp->ro);
+  if (int_to_fe(hv, F2) != p->l2.X[0]) return VDF_OK;
+  hash_state(S2.field, pp->params[SECONDARY], from_u64(num_steps, F2), z0s, p->zi[SECONDARY], to_relaxed(p->r[PRIMARY].inst, F1), hv, pp->ro);
+  if (int_to_fe(hv, F2) != p->l2.X[1]) return VDF_OK;
+  *ok = true;
+  return VDF_OK;
+}
+
+// Ok(zi_primary == zi && zi_secondary == [0]), src/nova/proof.rs:386
+bool running_outputs(const vdf_proof* p, const vdf_pp* pp, const vdf_fe* zi) {
+  return memcmp(p->zi[PRIMARY].data(), zi, 32 * pp->arity) == 0 && p->zi[SECONDARY][0].is_zero();
 }
 
 }  // namespace vdfnova
@@ -1726,20 +1818,11 @@ int vdf_nova_verify_custom(const vdf_proof* p, vdf_pp* pp, size_t num_steps, con
     if (!p || !pp || !z0 || !zi || !ok) return fail(VDF_ERR_BAD_ARG, "null argument");
     *ok = 0;
     if (p->pp != pp) return fail(VDF_ERR_BAD_ARG, "proof was made under other public parameters");
-    if (num_steps == 0 || p->i != num_steps) return VDF_OK;                  // NovaError::ProofVerifyError
-    if (memcmp(p->z0[PRIMARY].data(), z0, 32 * pp->arity) != 0) return VDF_OK;   // not the chain this proof was started for
-    { int rc = finalize_l2(p); if (rc != VDF_OK) return rc; }
-    const Side& S1 = pp->s[PRIMARY];
+    // (1) the step count, z0 and the two output hashes the last secondary instance carries
+    bool good = false;
+    { int rc = running_prelude(p, pp, num_steps, z0, &good); if (rc != VDF_OK || !good) return rc; }
     const Side& S2 = pp->s[SECONDARY];
-    const Field& F1 = *S1.F;
     const Field& F2 = *S2.F;
-    // (1) the two output hashes the last secondary instance carries
-    const std::vector<Fe> z0p((const Fe*)z0, (const Fe*)z0 + pp->arity), z0s(1, zero());
-    uint64_t hv[4];
-    hash_state(S1.field, pp->params[PRIMARY], from_u64(num_steps, F1), z0p, p->zi[PRIMARY], to_relaxed(p->r[SECONDARY].inst, F2), hv, pp->ro);
-    if (int_to_fe(hv, F2) != p->l2.X[0]) return VDF_OK;
-    hash_state(S2.field, pp->params[SECONDARY], from_u64(num_steps, F2), z0s, p->zi[SECONDARY], to_relaxed(p->r[PRIMARY].inst, F1), hv, pp->ro);
-    if (int_to_fe(hv, F2) != p->l2.X[1]) return VDF_OK;
     // (2) three satisfiability claims
     vdf_ctx* ctx = pp->ctx;
     HIPCALL(ctx, vdf_ctx_sync(ctx));
@@ -1747,7 +1830,6 @@ int vdf_nova_verify_custom(const vdf_proof* p, vdf_pp* pp, size_t num_steps, con
     q->nifs2 = vdf_proof::NIFS2_NONE;          // ... which hold the next step's cross terms: that step makes them again
     if (q->ctx3) HIPCALL(q->ctx3, vdf_ctx_sync(q->ctx3));
     q->tahead_valid = false;
-    bool good = false;
     for (int s = 0; s < 2; ++s) {
       int rc = check_sat(pp->s[s], p->r[s].inst, p->r[s].d_z, p->r[s].d_E, q->r[s].d_abc2, q->r[s].d_T, &good);
       if (rc != VDF_OK) return rc;
@@ -1759,8 +1841,176 @@ int vdf_nova_verify_custom(const vdf_proof* p, vdf_pp* pp, size_t num_steps, con
       if (rc != VDF_OK) return rc;
       if (!good) return VDF_OK;
     }
-    // Ok(zi_primary == zi && zi_secondary == [0]), src/nova/proof.rs:386
-    *ok = (memcmp(p->zi[PRIMARY].data(), zi, 32 * pp->arity) == 0 && p->zi[SECONDARY][0].is_zero()) ? 1 : 0;
+    *ok = running_outputs(p, pp, zi) ? 1 : 0;
+    return VDF_OK;
+  });
+}
+
+}  // extern "C"
+
+namespace {
+
+// `count` weights below 2^128, 16 bytes each from the operating system (getrandom(2)), as plain integers
+int draw_weights(size_t count, std::vector<Fe>* out) {
+  std::vector<uint8_t> buf(count * 16);
+  size_t got = 0;
+  while (got < buf.size()) {
+    const ssize_t r = getrandom(buf.data() + got, buf.size() - got, 0);
+    if (r < 0) {
+      if (errno == EINTR) continue;
+      return fail(VDF_ERR_DEVICE, std::string("getrandom: ") + strerror(errno));
+    }
+    got += (size_t)r;
+  }
+  out->assign(count, zero());
+  for (size_t k = 0; k < count; ++k) memcpy((*out)[k].l, &buf[16 * k], 16);
+  return VDF_OK;
+}
+
+// a side's scratch for one batch call, in the parameter set's block for that side (grown on demand, kept)
+int side_scratch(const Side& sd, size_t elems, void** out) {
+  Arena* a = sd.arena;
+  const size_t bytes = elems * 32;
+  if (a->cap < bytes) {
+    if (a->p) { HIPCALL(sd.ctx, vdf_ctx_sync(sd.ctx)); vdf_dev_free(sd.ctx, a->p); a->p = nullptr; a->cap = 0; }
+    HIPCALL(sd.ctx, vdf_dev_alloc(sd.ctx, bytes, &a->p));
+    a->cap = bytes;
+  }
+  *out = a->p;
+  return VDF_OK;
+}
+
+// z = (W, u, X) of each instance must carry the instance's own u and X: the tails gathered on the device, one copy to the host
+int tails_match(const Side& sd, const std::vector<const void*>& d_z, const std::vector<const Inst*>& in, void* d_tails, std::vector<bool>* ok) {
+  vdf_ctx* ctx = sd.ctx;
+  const size_t tl = (1 + NUM_IO) * 32;
+  for (size_t j = 0; j < d_z.size(); ++j)
+    HIPCALL(ctx, vdf_dev_memcpy(ctx, (char*)d_tails + j * tl, (const char*)d_z[j] + sd.num_vars * 32, tl));
+  std::vector<Fe> h(d_z.size() * (1 + NUM_IO));
+  HIPCALL(ctx, vdf_dev_memcpy(ctx, h.data(), d_tails, d_z.size() * tl));
+  ok->assign(d_z.size(), false);
+  for (size_t j = 0; j < d_z.size(); ++j) {
+    const Fe* t = &h[j * (1 + NUM_IO)];
+    (*ok)[j] = t[0] == in[j]->u && memcmp(&t[1], in[j]->X, 32 * NUM_IO) == 0;
+  }
+  return VDF_OK;
+}
+
+// The device checks of the live entries, combined per side: *ok = true iff every combined check passes.  The scratch is the
+// parameter set's, never a proof's, so that every proof can go on proving as if it had not been verified.
+int verify_batch_device(vdf_pp* pp, const std::vector<const vdf_proof*>& ps, bool* ok) {
+  *ok = false;
+  const size_t K = ps.size();
+  // WHY THE WEIGHTS ARE DRAWN HERE AND NOT FROM A TRANSCRIPT: a running proof's witnesses are tens of MB that no transcript
+  // absorbs, so weights derived from the instances alone are fixed before the witnesses are -- and cancelling errors then get
+  // through (W1 + d in one proof and W2 - (a1 / a2) d in another pass the combined opening check).  So every weight is 128
+  // fresh bits from the operating system, per call: with the others fixed, sum_q w_q e_q = 0 holds for at most one value of a
+  // w_q whose e_q != 0, so each combined check lets a bad entry through with probability at most 2^-128.
+  // Per entry: primary a, b, rho; secondary a, b, c, rho (running), rho (last secondary instance).
+  std::vector<Fe> w;
+  { int rc = draw_weights(8 * K, &w); if (rc != VDF_OK) return rc; }
+  const size_t TL = 1 + NUM_IO;
+  for (int side = 0; side < 2; ++side) {
+    const Side& sd = pp->s[side];
+    const size_t n_open = std::max(sd.num_vars, sd.num_cons), ninst = side == PRIMARY ? K : 2 * K;
+    void* base = nullptr;
+    { int rc = side_scratch(sd, n_open + sd.num_cons + ninst * TL, &base); if (rc != VDF_OK) return rc; }
+    void* d_open = base;
+    void* d_res = (char*)base + n_open * 32;
+    void* d_tails = (char*)d_res + sd.num_cons * 32;
+    std::vector<const void*> zs;
+    std::vector<const Inst*> ins;
+    std::vector<OpeningTerm> open;
+    std::vector<ResidualTerm> res;
+    for (size_t q = 0; q < K; ++q) {
+      const vdf_proof* p = ps[q];
+      const SideState& st = p->r[side];
+      const Fe* wq = &w[8 * q + (side == PRIMARY ? 0 : 3)];
+      zs.push_back(st.d_z); ins.push_back(&st.inst);
+      open.push_back(OpeningTerm{st.d_z, sd.num_vars, st.inst.comm_W, wq[0]});
+      open.push_back(OpeningTerm{st.d_E, sd.num_cons, st.inst.comm_E, wq[1]});
+      res.push_back(ResidualTerm{st.d_z, st.d_E, st.inst.u, side == PRIMARY ? wq[2] : wq[3]});
+      if (side == SECONDARY) {
+        zs.push_back(p->d_l2z); ins.push_back(&p->l2);
+        open.push_back(OpeningTerm{p->d_l2z, sd.num_vars, p->l2.comm_W, wq[2]});
+        res.push_back(ResidualTerm{p->d_l2z, nullptr, p->l2.u, wq[4]});
+      }
+    }
+    std::vector<bool> tail_ok;
+    { int rc = tails_match(sd, zs, ins, d_tails, &tail_ok); if (rc != VDF_OK) return rc; }
+    for (bool b : tail_ok) if (!b) return VDF_OK;
+    bool good = false;
+    { int rc = check_openings_combined(sd, open, d_open, &good); if (rc != VDF_OK || !good) return rc; }
+    { int rc = check_residuals_combined(sd, res, d_res, &good); if (rc != VDF_OK || !good) return rc; }
+  }
+  *ok = true;
+  return VDF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Many running proofs under one parameter set: each entry's exact checks on its own (as vdf_nova_verify_custom makes them),
+// then per side one combined opening check and one combined residual check for all live entries, with weights the verifier
+// draws itself.  When a combined check fails, the single verifier decides each live entry.
+int vdf_nova_verify_batch(vdf_pp* pp, size_t count, const vdf_proof* const proofs[], const size_t num_steps[], const vdf_fe* z0,
+                          const vdf_fe* zi, int ok[], int* all_ok) {
+  return nova_guard([&]() -> int {
+    if (!pp || !all_ok) return fail(VDF_ERR_BAD_ARG, "null argument");
+    *all_ok = 0;
+    if (count == 0) { *all_ok = 1; return VDF_OK; }
+    if (!proofs || !num_steps || !z0 || !zi || !ok) return fail(VDF_ERR_BAD_ARG, "null argument");
+    for (size_t q = 0; q < count; ++q) ok[q] = 0;
+    for (size_t q = 0; q < count; ++q) {
+      if (!proofs[q]) return fail(VDF_ERR_BAD_ARG, "entry " + std::to_string(q) + ": null proof");
+      if (proofs[q]->pp != pp) return fail(VDF_ERR_BAD_ARG, "entry " + std::to_string(q) + ": proof was made under other public parameters");
+    }
+    for (size_t q = 0; q < count; ++q)
+      if (proofs[q]->poisoned)
+        return fail(VDF_ERR_DEVICE, "entry " + std::to_string(q) + ": this proof's running instance is half folded (an earlier prove_step failed on the device)");
+    const size_t ar = pp->arity;
+    const Field& F2 = *pp->s[SECONDARY].F;
+    // the exact checks; an entry that fails one leaves the batch
+    std::vector<size_t> live;
+    for (size_t q = 0; q < count; ++q) {
+      const vdf_proof* p = proofs[q];
+      bool good = false;
+      const int rc = running_prelude(p, pp, num_steps[q], z0 + q * ar, &good);
+      if (rc != VDF_OK) return fail(rc, "entry " + std::to_string(q) + ": " + vdf_nova_last_error());
+      if (!good || p->l2.u != one(F2) || !p->l2.comm_E.is_id() || !running_outputs(p, pp, zi + q * ar)) continue;
+      live.push_back(q);
+    }
+    bool combined = true;
+    if (!live.empty()) {
+      vdf_ctx* ctx = pp->ctx;
+      // every queue that may still write a live proof's running instances: the parameters' context, and each proof's early-rows
+      // context (it folds rows under fold_on_rows)
+      HIPCALL(ctx, vdf_ctx_sync(ctx));
+      for (size_t q : live)
+        if (proofs[q]->ctx3) HIPCALL(proofs[q]->ctx3, vdf_ctx_sync(proofs[q]->ctx3));
+      int was_async = 0;
+      HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
+      HIPCALL(ctx, vdf_ctx_set_async(ctx, 1));
+      struct Restore { vdf_ctx* c; int a; ~Restore() { vdf_ctx_sync(c); vdf_ctx_set_async(c, a); } } restore{ctx, was_async};
+      std::vector<const vdf_proof*> ps;
+      for (size_t q : live) ps.push_back(proofs[q]);
+      int rc = verify_batch_device(pp, ps, &combined);
+      if (rc != VDF_OK) return rc;
+    }
+    if (combined) {
+      for (size_t q : live) ok[q] = 1;
+    } else {
+      for (size_t q : live) {                                         // attribution: each live entry on its own
+        int good = 0;
+        int rc = vdf_nova_verify_custom(proofs[q], pp, num_steps[q], z0 + q * ar, zi + q * ar, &good);
+        if (rc != VDF_OK) return rc;
+        ok[q] = good;
+      }
+    }
+    int all = 1;
+    for (size_t q = 0; q < count; ++q) all &= ok[q];
+    *all_ok = all;
     return VDF_OK;
   });
 }

@@ -77,6 +77,19 @@ struct Inst { Aff comm_W, comm_E; Fe u; Fe X[NUM_IO]; };
 RelaxedInst to_relaxed(const Inst& in, const Field& own);
 // relaxed satisfiability of (inst, z = [W | u | X], E) on `sd`: commitments open and A z o B z = u C z + E
 int check_sat(const Side& sd, const Inst& in, const void* d_z, const void* d_E, void* d_scratch_abc[3], void* d_scratch_T, bool* ok);
+// sum_j sc[j] pts[j] over a few host points, Montgomery scalars (compress_host.cpp): enqueued on sd.ctx, *out ready after a sync
+int msm_points(const Side& sd, const std::vector<Aff>& pts, const std::vector<Fe>& sc, vdf_jac* out);
+// Deferred satisfiability checks of many instances of one side, combined with 128-bit weights the caller draws (nova_host.cpp,
+// vdf_nova_verify_batch).  Opening: a vector committed to under the side's generators, its commitment and its weight (a plain
+// integer below 2^128).  Residual: z = [W | u | X], E (null: zero), u, and its weight.
+struct OpeningTerm { const void* d_v; size_t n; Aff comm; Fe w; };
+struct ResidualTerm { const void* d_z; const void* d_E; Fe u; Fe w; };
+// MSM(G, sum_j w_j v_j) == sum_j w_j C_j: vdf_lincomb_u128 in groups of 64 into d_scratch (max n elements), one MSM over the
+// generators, one over the commitments
+int check_openings_combined(const Side& sd, const std::vector<OpeningTerm>& terms, void* d_scratch, bool* ok);
+// sum_j w_j (A z_j o B z_j - u_j C z_j - E_j) == 0: vdf_relaxed_residual_batch in groups of 64 into d_scratch (num_cons
+// elements), each group tested for zero
+int check_residuals_combined(const Side& sd, const std::vector<ResidualTerm>& terms, void* d_scratch, bool* ok);
 
 }  // namespace vdfnova
 

@@ -271,6 +271,18 @@ Status vec_nifs_cross_minroot_fold(int field, int per, uint64_t t, size_t seg_be
                                    void* az2, void* bz2, void* cz2, void* T, hipStream_t s);
 Status vec_fold_many(int field, const vdf_fe* r, int k, void* const acc[], const void* const add[], const size_t n[],
                      hipStream_t s);
+// random linear combinations of many instances (vdf_lincomb_u128, vdf_relaxed_residual_batch): w and rho plain integers below
+// 2^128, u Montgomery, all on the host; the residual's instances packed (residual_pack, residual_item_bytes() each) into a block
+// the kernel reads from device memory
+constexpr int LINCOMB_MAX = 64;                          // vectors of one vdf_lincomb_u128
+constexpr int RESIDUAL_BATCH_MAX = 64;                   // instances of one vdf_relaxed_residual_batch
+Status vec_lincomb_u128(int field, int count, const void* const v[], const size_t n[], const vdf_fe w[], size_t n_out, void* out,
+                        hipStream_t s);
+size_t residual_item_bytes();
+void residual_pack(int count, const void* const z[], const void* const E[], const vdf_fe u[], const vdf_fe rho[], void* block);
+Status vec_relaxed_residual_batch(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3], const uint32_t* const coef[3],
+                                  const void* dict, const void* block, int count, size_t rows, const uint32_t* long_rowlist,
+                                  size_t n_long_rows, void* out, double alg_bytes, hipStream_t s);
 Status vec_mul(int field, const void* a, const void* b, size_t n, void* out, hipStream_t s);
 Status vec_any_nonzero(const void* v, size_t n, uint32_t* d_flag, hipStream_t s);     // *d_flag = 1 iff some element is non-zero
 Status vec_to_mont(int field, const void* a, size_t n, void* out, hipStream_t s);

@@ -886,6 +886,172 @@ Status vec_fold_many(int field, const vdf_fe* r, int k, void* const acc[], const
   return Status{};
 }
 
+// ---- random linear combinations of many instances (vdf_nova_verify_batch) -------------------------------------------
+// out[i] = sum_j w[j] v[j][i], v[j][i] = 0 for i >= n[j]; w[j] a plain integer below 2^128 (fe_mul_u128, as k_fold_many_u128).
+// One pass: every lane reads its element of each vector once and writes its output once, the sum in registers.  `out` may
+// be one of the vectors (a lane reads all of its inputs before it stores).
+struct LincombArgs { const char* v[LINCOMB_MAX]; uint64_t n[LINCOMB_MAX]; uint32_t w[LINCOMB_MAX][4]; int count; };
+template <class P>
+__global__ __launch_bounds__(256) void k_lincomb_u128(LincombArgs a, size_t n_out, char* out) {
+  __builtin_amdgcn_s_setprio(3);     // light kernel: do not starve behind a co-running k_accumulate
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_out) return;
+  Fe<P> acc = fe_zero<P>();
+  // four vectors' loads in flight before their products
+  for (int j = 0; j < a.count; j += 4) {
+    Fe<P> x[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = j + k < a.count && i < a.n[j + k] ? fe_load<P>(a.v[j + k] + i * 32) : fe_zero<P>();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (j + k >= a.count) break;
+      const uint32_t r[4] = {a.w[j + k][0], a.w[j + k][1], a.w[j + k][2], a.w[j + k][3]};
+      acc = fe_add(acc, fe_mul_u128<P>(x[k], r));
+    }
+  }
+  fe_store<P>(out + i * 32, acc);
+}
+
+// out[r] = sum_q rho_q ((A z_q)[r] (B z_q)[r] - u_q (C z_q)[r] - E_q[r]): the relaxed R1CS residuals of many instances of one
+// shape, randomly combined, in one pass over the rows.  The instances are an argument block in device memory (uniform loads).
+// The first `long_wgs` workgroups give each row that has a matrix of more than VDF_LONG_ROW entries one wavefront (as
+// k_spmv_long: lanes stride over the entries, then a butterfly sum); the rest take one short row per lane, with the row's
+// first entries (column, coefficient index, dictionary value) loaded once in k_nifs_cross's three waves and the instances
+// looped over inside the lane.
+struct ResidualItem { const char* z; const char* E; uint32_t u[8]; uint32_t rho[4]; };
+static_assert(sizeof(ResidualItem) == 64, "argument block layout");
+template <class P>
+__device__ __forceinline__ Fe<P> residual_term(const Fe<P>& a, const Fe<P>& b, const Fe<P>& c, const ResidualItem& it, size_t r) {
+  Fe<P> u;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) u.v[k] = it.u[k];
+  Fe<P> t = fe_sub(fe_mul(a, b), fe_mul(u, c));
+  if (it.E) t = fe_sub(t, fe_load<P>(it.E + r * 32));
+  const uint32_t rho[4] = {it.rho[0], it.rho[1], it.rho[2], it.rho[3]};
+  return fe_mul_u128<P>(t, rho);
+}
+template <class P>
+__global__ __launch_bounds__(256) void k_relaxed_residual_batch(Csr3 m, const char* __restrict__ dict, const ResidualItem* __restrict__ items,
+                                                                int count, size_t rows, const uint32_t* __restrict__ long_rowlist,
+                                                                size_t n_long, uint32_t long_wgs, char* __restrict__ out) {
+  __builtin_amdgcn_s_setprio(3);     // light kernel: do not starve behind a co-running k_accumulate
+  if (blockIdx.x < long_wgs) {
+    const size_t w = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= n_long) return;                                        // whole wavefronts leave together
+    const uint32_t lane = threadIdx.x & 63, r = long_rowlist[w];
+    uint32_t lo[3], hi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { lo[k] = m.rowptr[k][r]; hi[k] = m.rowptr[k][r + 1]; }
+    Fe<P> acc = fe_zero<P>();
+    for (int q = 0; q < count; ++q) {
+      const ResidualItem& it = items[q];
+      Fe<P> s[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        s[k] = fe_zero<P>();
+        for (uint32_t e = lo[k] + lane; e < hi[k]; e += 64)
+          s[k] = fe_add(s[k], spmv_term<P>(fe_load<P>(it.z + (size_t)m.col[k][e] * 32), m.coef[k][e], dict));
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+          Fe<P> o;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) o.v[i] = __shfl_xor(s[k].v[i], off, 64);
+          s[k] = fe_add(s[k], o);
+        }
+      }
+      if (lane == 0) acc = fe_add(acc, residual_term<P>(s[0], s[1], s[2], it, r));
+    }
+    if (lane == 0) fe_store<P>(out + (size_t)r * 32, acc);
+    return;
+  }
+  const size_t r = (size_t)(blockIdx.x - long_wgs) * 256 + threadIdx.x;
+  if (r >= rows) return;
+  uint32_t lo[3], hi[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { lo[k] = m.rowptr[k][r]; hi[k] = m.rowptr[k][r + 1]; }
+  if (hi[0] - lo[0] > VDF_LONG_ROW || hi[1] - lo[1] > VDF_LONG_ROW || hi[2] - lo[2] > VDF_LONG_ROW) return;   // a wavefront's row
+  constexpr int PRE[3] = {2, 2, 4};
+  uint32_t cc[3][4], kk[3][4];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int j = 0; j < PRE[k]; ++j) {
+      const uint32_t e = lo[k] + j < hi[k] ? lo[k] + j : lo[k];       // (arrays are nnz + 1 long: lo is always readable)
+      cc[k][j] = lo[k] + j < hi[k] ? m.col[k][e] : 0u;
+      kk[k][j] = lo[k] + j < hi[k] ? m.coef[k][e] : 0u;
+    }
+  Fe<P> dv[3][4];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int j = 0; j < PRE[k]; ++j) dv[k][j] = kk[k][j] > 1 ? fe_load<P>(dict + (size_t)kk[k][j] * 32) : fe_zero<P>();
+  Fe<P> acc = fe_zero<P>();
+  for (int q = 0; q < count; ++q) {
+    const ResidualItem& it = items[q];
+    Fe<P> v[3][4];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int j = 0; j < PRE[k]; ++j) v[k][j] = fe_load<P>(it.z + (size_t)cc[k][j] * 32);
+    Fe<P> s[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      s[k] = fe_zero<P>();
+#pragma unroll
+      for (int j = 0; j < PRE[k]; ++j) {
+        if (lo[k] + j >= hi[k]) break;
+        const uint32_t ci = kk[k][j];
+        s[k] = ci == 0 ? fe_add(s[k], v[k][j]) : ci == 1 ? fe_sub(s[k], v[k][j]) : fe_add(s[k], fe_mul(v[k][j], dv[k][j]));
+      }
+      for (uint32_t e = lo[k] + PRE[k]; e < hi[k]; ++e)
+        s[k] = fe_add(s[k], spmv_term<P>(fe_load<P>(it.z + (size_t)m.col[k][e] * 32), m.coef[k][e], dict));
+    }
+    acc = fe_add(acc, residual_term<P>(s[0], s[1], s[2], it, r));
+  }
+  fe_store<P>(out + r * 32, acc);
+}
+
+Status vec_lincomb_u128(int field, int count, const void* const v[], const size_t n[], const vdf_fe w[], size_t n_out, void* out,
+                        hipStream_t s) {
+  if (n_out == 0) return Status{};
+  if (count < 1 || count > LINCOMB_MAX) return Status{VDF_ERR_BAD_ARG, "1..64 vectors"};
+  if ((n_out + 255) / 256 >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "combination too long"};
+  LincombArgs a{};
+  a.count = count;
+  double elems = (double)n_out;
+  for (int j = 0; j < count; ++j) {
+    a.v[j] = C(v[j]); a.n[j] = n[j];
+    memcpy(a.w[j], w[j].l, 16);
+    elems += (double)n[j];
+  }
+  KTimer kt(s, "k_lincomb_u128", 32.0 * elems);
+  FIELD_DISPATCH(field, k_lincomb_u128, grid_for(n_out), dim3(256), 0, s, a, n_out, M(out));
+  return Status{};
+}
+
+Status vec_relaxed_residual_batch(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3], const uint32_t* const coef[3],
+                                  const void* dict, const void* block, int count, size_t rows, const uint32_t* long_rowlist,
+                                  size_t n_long_rows, void* out, double alg_bytes, hipStream_t s) {
+  if (rows == 0 || count == 0) return Status{};
+  Csr3 m;
+  for (int k = 0; k < 3; ++k) { m.rowptr[k] = rowptr[k]; m.col[k] = col[k]; m.coef[k] = coef[k]; }
+  const uint32_t long_wgs = long_rowlist ? (uint32_t)((n_long_rows + 3) / 4) : 0u;
+  KTimer kt(s, "k_relaxed_residual_batch", alg_bytes);
+  FIELD_DISPATCH(field, k_relaxed_residual_batch, dim3((unsigned)((rows + 255) / 256) + long_wgs), dim3(256), 0, s, m, C(dict),
+                 reinterpret_cast<const ResidualItem*>(block), count, rows, long_rowlist, n_long_rows, long_wgs, M(out));
+  return Status{};
+}
+void residual_pack(int count, const void* const z[], const void* const E[], const vdf_fe u[], const vdf_fe rho[], void* block) {
+  ResidualItem* it = reinterpret_cast<ResidualItem*>(block);
+  for (int q = 0; q < count; ++q) {
+    it[q].z = C(z[q]);
+    it[q].E = E ? C(E[q]) : nullptr;
+    memcpy(it[q].u, u[q].l, 32);
+    memcpy(it[q].rho, rho[q].l, 16);
+  }
+}
+size_t residual_item_bytes() { return sizeof(ResidualItem); }
+
 // flag |= 1 when any of the n 32-byte elements is not all-zero (a residual vector checked where it lies)
 __global__ __launch_bounds__(256) void k_any_nonzero(const uint4* __restrict__ v, size_t n16, uint32_t* __restrict__ flag) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

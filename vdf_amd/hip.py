@@ -527,6 +527,25 @@ class Context:
         r = np.ascontiguousarray(rhos, dtype="<u8").reshape(-1, 4)
         self._check(lib.vdf_spmv3_t_batch(self.handle, shape.handle, count, e, _ptr(r), o))
 
+    def lincomb_u128(self, field, vectors, lengths, weights, n_out, out) -> None:
+        """vdf_lincomb_u128: out[i] = sum_j weights[j] * vectors[j][i] (zero past lengths[j]); weights: plain integers below
+        2^128 as a (count, 4) uint64 host array."""
+        count = len(vectors)
+        v = (C.c_void_p * max(count, 1))(*[_ptr(x) for x in vectors])
+        ln = (C.c_size_t * max(count, 1))(*[int(x) for x in lengths])
+        w = np.ascontiguousarray(weights, dtype="<u8").reshape(-1, 4)
+        self._check(lib.vdf_lincomb_u128(self.handle, field, count, v, ln, _ptr(w), n_out, _ptr(out)))
+
+    def relaxed_residual_batch(self, shape: Shape, zs, Es, us, rhos, out) -> None:
+        """vdf_relaxed_residual_batch: out[r] = sum_q rhos[q] ((A z_q)[r] (B z_q)[r] - us[q] (C z_q)[r] - Es[q][r]); an E of None
+        is zero; us Montgomery, rhos plain integers below 2^128, both (count, 4) uint64 host arrays."""
+        count = len(zs)
+        z = (C.c_void_p * max(count, 1))(*[_ptr(x) for x in zs])
+        e = (C.c_void_p * max(count, 1))(*[None if x is None else _ptr(x) for x in Es])
+        u = np.ascontiguousarray(us, dtype="<u8").reshape(-1, 4)
+        r = np.ascontiguousarray(rhos, dtype="<u8").reshape(-1, 4)
+        self._check(lib.vdf_relaxed_residual_batch(self.handle, shape.handle, count, z, e, _ptr(u), _ptr(r), _ptr(out)))
+
     def ipa_scalars(self, field, a, s, n, nj, sL, sR) -> None:
         self._check(lib.vdf_ipa_scalars(self.handle, field, _ptr(a), _ptr(s), n, nj, _ptr(sL), _ptr(sR)))
 

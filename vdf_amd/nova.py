@@ -75,6 +75,7 @@ for _name, _res, _args in [
     ("vdf_nova_compress_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_vp)]),
     ("vdf_nova_verify_compressed", _i, [_vp, _vp, _sz, C.POINTER(_Fe * 3), C.POINTER(_Fe * 3), C.POINTER(_i)]),
     ("vdf_nova_verify_compressed_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_sz), _vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    ("vdf_nova_verify_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_sz), _vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
     ("vdf_nova_snark_free", None, [_vp]),
     ("vdf_nova_snark_size", _sz, [_vp]),
     ("vdf_nova_snark_bytes", _i, [_vp, _vp, _sz]),
@@ -687,4 +688,22 @@ def verify_compressed_batch(pp: NovaVDFPublicParams, items: Sequence[tuple]) -> 
     ok = (_i * max(n, 1))()
     all_ok = C.c_int(0)
     _check(nova_lib.vdf_nova_verify_compressed_batch(pp.handle, n, snarks, steps, z0, zi, ok, C.byref(all_ok)))
+    return [bool(ok[q]) for q in range(n)]
+
+
+def verify_batch(pp: NovaVDFPublicParams, items: Sequence[tuple]) -> list:
+    """Verifies many running proofs at once (vdf_nova_verify_batch): items = [(proof, num_steps, z0, zi), ...]; returns one
+    bool per item, each what proof.verify(pp, num_steps, z0, zi) returns.  The proofs go on proving as if unverified."""
+    n = len(items)
+    arity = getattr(pp, "arity", 3)
+    proofs = (_vp * max(n, 1))(*[None if it[0] is None else it[0].handle for it in items])
+    steps = (_sz * max(n, 1))(*[int(it[1]) for it in items])
+    for it in items:
+        if len(it[2]) != arity or len(it[3]) != arity:
+            raise ValueError(f"z0 and zi need {arity} elements each")
+    z0 = _zn([v for it in items for v in it[2]] or [bytes(32)])
+    zi = _zn([v for it in items for v in it[3]] or [bytes(32)])
+    ok = (_i * max(n, 1))()
+    all_ok = C.c_int(0)
+    _check(nova_lib.vdf_nova_verify_batch(pp.handle, n, proofs, steps, z0, zi, ok, C.byref(all_ok)))
     return [bool(ok[q]) for q in range(n)]
