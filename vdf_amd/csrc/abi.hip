@@ -59,7 +59,7 @@ struct Staging {
   Status temp(size_t bytes, void** t) {
     const size_t need = (bytes + 255) / 256 * 256;
     if (need <= 1024 && ctx->small_pool && small_used + need <= vdf_ctx::SMALL_POOL_BYTES) {
-      *t = reinterpret_cast<char*>(ctx->small_pool) + small_used;
+      *t = vdf::bytes_of(ctx->small_pool) + small_used;
       small_used += need;
       return Status{};
     }
@@ -224,8 +224,6 @@ Status ensure_ws(vdf_ctx* ctx, size_t bytes) {
 constexpr size_t DIRECT_MAX_SCALARS = (size_t)1 << 17;
 bool direct_enabled() { return vdf::tuning().msm_direct != 0; }       // (tuning: 0 = bucket method only)
 
-size_t field_of_curve_scalar(int curve) { return curve == VDF_CURVE_PALLAS ? VDF_FIELD_FQ : VDF_FIELD_FP; }
-
 constexpr size_t GLV_MIN_POINTS = 1u << 12;      // below this the split's launches cost what the shorter chain saves
 #ifndef VDF_GLV_MAX_LOG2
 #define VDF_GLV_MAX_LOG2 21          /* (an A/B build may move it: make ab AB_FLAGS=-DVDF_GLV_MAX_LOG2=23) */
@@ -304,7 +302,7 @@ Status msm_core(vdf_ctx* ctx, const vdf_bases* bases, int groups, const size_t* 
       return Status{VDF_ERR_BAD_ARG, "a batch this wide does not fit the sort under this table's window and bucket sets: fewer MSMs per call"};
     plan = vdf::msm_make_plan(groups, n, offset, bases->tbl_c, bases->tbl_sets, bases->tbl_tables, ctx->num_cus, ctx->acc_fill);
     plan.tstride = (uint32_t)bases->n;
-    pts = reinterpret_cast<const char*>(bases->d_table);
+    pts = vdf::cbytes_of(bases->d_table);
   } else if (groups == 1 && offset[0] == 0 && n[0] == bases->n && n[0] >= GLV_MIN_POINTS && n[0] <= GLV_MAX_POINTS && ctx->msm_window == 0 &&
              vdf::tuning().glv) {
     // No table, the whole generator set: the endomorphism (msm.hip k_glv_*).  2n points [P | phi(P)] kept with the generators
@@ -358,14 +356,14 @@ Status msm_core(vdf_ctx* ctx, const vdf_bases* bases, int groups, const size_t* 
     const int c = ca >= 15 ? 16 : 13;
     plan = vdf::msm_make_plan(1, n2, off2, c, 0, 0, ctx->num_cus, ctx->acc_fill, 132);
     plan.tstride = 0;
-    pts = reinterpret_cast<const char*>(pts2);
+    pts = vdf::cbytes_of(pts2);
     ntot = n2[0];
   } else {
     int c = ctx->msm_window ? ctx->msm_window : vdf::msm_auto_window(nmax);
     while (c > 4 && !vdf::msm_plan_feasible(groups, c, 0)) --c;     // a table-less window is a tuning knob: lowered to what fits
     plan = vdf::msm_make_plan(groups, n, offset, c, 0, 0, ctx->num_cus, ctx->acc_fill);
     plan.tstride = 0;
-    pts = reinterpret_cast<const char*>(bases->d_pts);
+    pts = vdf::cbytes_of(bases->d_pts);
   }
   if ((size_t)plan.tstride * plan.tables + bases->n >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "table index exceeds 31 bits"};
   if ((uint64_t)ntot * plan.windows >= 0xFFF00000ull) return Status{VDF_ERR_BAD_LENGTH, "n * windows exceeds 32-bit entry positions"};
@@ -690,7 +688,6 @@ void vdf_ctx_destroy(vdf_ctx* ctx) {
     if (ctx->side_done[g]) (void)hipEventDestroy(ctx->side_done[g]);
     if (ctx->side[g]) { (void)hipStreamSynchronize(ctx->side[g]); (void)hipStreamDestroy(ctx->side[g]); }
   }
-  if (ctx->own_stream && ctx->stream) { (void)hipStreamDestroy(ctx->stream); pool_count_owned(ctx->device, -1); }
   if (ctx->pool_slot >= 0) pool_release(ctx->device, ctx->pool_slot);
   if (ctx->family) { std::lock_guard<std::mutex> lock(g_pool_mu); ctx->family->used[ctx->family_idx] = false; }
   ctx->family.reset();                               // the family's streams go with its last member
@@ -705,11 +702,9 @@ int vdf_ctx_set_stream(vdf_ctx* ctx, void* hip_stream) {
       if (ctx->foreign_stream) return Status{VDF_ERR_BAD_ARG, "this context has no stream of its own to return to"};
       return Status{};
     }
-    if (ctx->own_stream && ctx->stream) { (void)hipStreamDestroy(ctx->stream); pool_count_owned(ctx->device, -1); }
     if (ctx->pool_slot >= 0) { pool_release(ctx->device, ctx->pool_slot); ctx->pool_slot = -1; }
     // (a family member keeps its place: vdf_ctx_set_stream(ctx, NULL) returns to it; its neighbours are not handed out meanwhile)
     ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);
-    ctx->own_stream = false;
     ctx->foreign_stream = true;
     return Status{};
   });
@@ -758,7 +753,7 @@ int vdf_bases_upload(vdf_ctx* ctx, int curve, const vdf_affine* bases, size_t n,
   return guarded(ctx, [&]() -> Status {
     if (!out) return Status{VDF_ERR_BAD_ARG, "null out"};
     *out = nullptr;
-    if (curve != VDF_CURVE_PALLAS && curve != VDF_CURVE_VESTA) return Status{VDF_ERR_BAD_ARG, "unknown curve"};
+    VDF_TRY(vdf::check_curve(curve));
     if (n && !bases) return Status{VDF_ERR_BAD_ARG, "null bases"};
     vdf_bases* b = new vdf_bases();
     b->ctx = ctx; b->curve = curve; b->n = n;
@@ -805,7 +800,7 @@ int vdf_bases_generate_family(vdf_ctx* ctx, int curve, int family, uint64_t seed
   return guarded(ctx, [&]() -> Status {
     if (!out) return Status{VDF_ERR_BAD_ARG, "null out"};
     *out = nullptr;
-    if (curve != VDF_CURVE_PALLAS && curve != VDF_CURVE_VESTA) return Status{VDF_ERR_BAD_ARG, "unknown curve"};
+    VDF_TRY(vdf::check_curve(curve));
     if (n >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "too many bases"};
     vdf_bases* b = new vdf_bases();
     b->ctx = ctx; b->curve = curve; b->n = n;
@@ -825,7 +820,7 @@ int vdf_bases_generate_label(vdf_ctx* ctx, int curve, const uint8_t* label, size
   return guarded(ctx, [&]() -> Status {
     if (!out) return Status{VDF_ERR_BAD_ARG, "null out"};
     *out = nullptr;
-    if (curve != VDF_CURVE_PALLAS && curve != VDF_CURVE_VESTA) return Status{VDF_ERR_BAD_ARG, "unknown curve"};
+    VDF_TRY(vdf::check_curve(curve));
     if (n >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "too many bases"};
     if (label_len > 64 || (label_len && !label)) return Status{VDF_ERR_BAD_LENGTH, "label of at most 64 bytes"};
     vdf_bases* b = new vdf_bases();
@@ -923,7 +918,7 @@ int vdf_bases_download(vdf_ctx* ctx, const vdf_bases* bases, size_t offset, size
     if (!bases || bases->ctx != ctx || (n && !out)) return Status{VDF_ERR_BAD_ARG, "bad arguments"};
     if (offset > bases->n || n > bases->n - offset) return Status{VDF_ERR_BAD_LENGTH, "range exceeds the generator table"};
     if (n == 0) return Status{};
-    VDF_TRY_HIP(hipMemcpyAsync(out, reinterpret_cast<const char*>(bases->d_pts) + offset * 64, n * 64, hipMemcpyDefault, ctx->stream));
+    VDF_TRY_HIP(hipMemcpyAsync(out, vdf::cbytes_of(bases->d_pts) + offset * 64, n * 64, hipMemcpyDefault, ctx->stream));
     VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
     return Status{};
   });
@@ -981,7 +976,7 @@ int vdf_msm_job_begin(vdf_ctx* ctx, const vdf_bases* bases, int k, const size_t 
       return Status{VDF_ERR_BAD_ARG, "MSM jobs need a fixed-base table with one bucket set (vdf_bases_precompute(c, 1))"};
     std::unique_ptr<vdf_msm_job> job(new vdf_msm_job());
     job->ctx = ctx; job->bases = bases; job->k = k; job->is_mont = is_mont;
-    job->pts = reinterpret_cast<const char*>(bases->d_table);
+    job->pts = vdf::cbytes_of(bases->d_table);
     size_t off = 0;
     for (int g = 0; g < k; ++g) {
       if (offset[g] > bases->n || n[g] > bases->n - offset[g]) return Status{VDF_ERR_BAD_LENGTH, "offset + n exceeds the generator table"};
@@ -1019,7 +1014,7 @@ int vdf_msm_job_push(vdf_msm_job* job, int g, const vdf_fe* scalars) {
     VDF_TRY_HIP(hipEventRecord(ctx->side_go[g], ctx->stream));
     VDF_TRY_HIP(hipStreamWaitEvent(ctx->side[g], ctx->side_go[g], 0));
     const void* sc[vdf::MSM_MAX_GROUPS] = {scalars, nullptr, nullptr, nullptr};
-    char* ws = reinterpret_cast<char*>(ctx->ws);
+    char* ws = vdf::bytes_of(ctx->ws);
     char* buckets = ws + job->tail_off + (size_t)g * job->plan[g].nbk * 128;
     VDF_TRY(vdf::msm_run(job->bases->curve, job->plan[g], job->pts, sc, job->is_mont != 0, ws + job->ws_off[g], nullptr,
                          ctx->side[g], nullptr, buckets));
@@ -1040,7 +1035,7 @@ int vdf_msm_job_finish(vdf_msm_job* job, vdf_jac out[]) {
     VDF_TRY(st.out(out, job->k * sizeof(vdf_jac), &d_out));
     for (int g = 0; g < job->k; ++g) VDF_TRY_HIP(hipStreamWaitEvent(ctx->stream, ctx->side_done[g], 0));
     VDF_TRY(vdf::msm_tail(job->bases->curve, job->plan[0].c, 1, job->k, job->plan[0].nbk,
-                          reinterpret_cast<char*>(ctx->ws) + job->tail_off, d_out, ctx->stream));
+                          vdf::bytes_of(ctx->ws) + job->tail_off, d_out, ctx->stream));
     return st.finish();
   });
   // the job ends here whatever happened; an abandoned pipeline must not outlive the workspace it writes
@@ -1218,10 +1213,9 @@ int vdf_shape_create(vdf_ctx* ctx, int field, size_t num_cons, size_t num_cols, 
   return guarded(ctx, [&]() -> Status {
     if (!out || !rows || !cols || !vals || !nnz) return Status{VDF_ERR_BAD_ARG, "null argument"};
     *out = nullptr;
-    if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
-    if (num_cons >= (1ull << 31) || num_cols >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "shape too large"};
     std::array<uint32_t, 8> one, minus_one;
-    if (field == VDF_FIELD_FP) build_dict_consts<FpParams>(one, minus_one); else build_dict_consts<FqParams>(one, minus_one);
+    VDF_TRY(vdf::with_field(field, [&](auto f) { build_dict_consts<vdf::tag_t<decltype(f)>>(one, minus_one); return Status{}; }));
+    if (num_cons >= (1ull << 31) || num_cols >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "shape too large"};
     std::map<std::array<uint32_t, 8>, uint32_t> dict_idx;
     std::vector<std::array<uint32_t, 8>> dict;
     dict.push_back(one); dict_idx[one] = 0;
@@ -1715,7 +1709,7 @@ static Status arg_block(vdf_ctx* ctx, size_t bytes, const std::function<void(voi
 }
 
 static Status ipa_coefficients(vdf_ctx* ctx, int field, const vdf_ipa_opening* ops, int count, size_t n, void* out) {
-  if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
+  VDF_TRY(vdf::check_field(field));
   if (count < 0 || count > (1 << 16)) return Status{VDF_ERR_BAD_ARG, "0..65536 openings"};
   if (count && !ops) return Status{VDF_ERR_BAD_ARG, "null openings"};
   if (n > ((size_t)1 << 32)) return Status{VDF_ERR_BAD_LENGTH, "at most 2^32 entries"};
@@ -1744,10 +1738,9 @@ int vdf_pair_table_pattern(vdf_ctx* ctx, int field, const vdf_fe* lo, const vdf_
                            vdf_fe* out) {
   return guarded(ctx, [&]() -> Status {
     if (k < 0 || log_m < 0 || log_m > 4 || k + log_m > 24) return Status{VDF_ERR_BAD_LENGTH, "0..24 variables in all, pattern of 1..16"};
-    if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
-    if (!ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, kDevVec};
     vdf_ipa_opening op{};
-    vdf::snark_field_one(field, &op.weight);
+    VDF_TRY(vdf::snark_field_one(field, &op.weight));
+    if (!ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, kDevVec};
     op.k = k; op.log_m = log_m; op.lo = lo; op.hi = hi; op.pattern = pattern;
     return ipa_coefficients(ctx, field, &op, 1, (size_t)1 << (k + log_m), out);
   });
@@ -1805,7 +1798,7 @@ int vdf_reduce_batch(vdf_ctx* ctx, int field, int kind, size_t count, const vdf_
                      vdf_fe* out) {
   return guarded(ctx, [&]() -> Status {
     if (kind < 0 || kind > 3) return Status{VDF_ERR_BAD_ARG, "unknown reduction"};
-    if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
+    VDF_TRY(vdf::check_field(field));
     if (count > (size_t)vdf::SNARK_REDUCE_BATCH_MAX) return Status{VDF_ERR_BAD_ARG, "0..512 instances"};
     if (count == 0) return Status{};
     if (!tables || !out) return Status{VDF_ERR_BAD_ARG, "null argument"};
@@ -1830,7 +1823,7 @@ int vdf_reduce_batch(vdf_ctx* ctx, int field, int kind, size_t count, const vdf_
 int vdf_fold_halves_batch(vdf_ctx* ctx, int field, int k, vdf_fe* const v[], const vdf_fe c_lo[], const vdf_fe c_hi[], size_t n) {
   return guarded(ctx, [&]() -> Status {
     if (k < 0 || k > vdf::SNARK_FOLD_BATCH_MAX) return Status{VDF_ERR_BAD_ARG, "k must be 0..320"};
-    if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
+    VDF_TRY(vdf::check_field(field));
     if (k == 0) return Status{};
     if (n < 2 || (n & (n - 1))) return Status{VDF_ERR_BAD_LENGTH, "length must be a power of two >= 2"};
     if (!v || !c_lo || !c_hi || ptr_is_device(c_lo) || ptr_is_device(c_hi)) return Status{VDF_ERR_BAD_ARG, kHostScalar};
@@ -1878,7 +1871,7 @@ static bool below_2_128(const vdf_fe& w) { return (w.l[2] | w.l[3]) == 0; }
 int vdf_lincomb_u128(vdf_ctx* ctx, int field, int count, const vdf_fe* const v[], const size_t n[], const vdf_fe w[],
                      size_t n_out, vdf_fe* out) {
   return guarded(ctx, [&]() -> Status {
-    if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
+    VDF_TRY(vdf::check_field(field));
     if (count < 1 || count > vdf::LINCOMB_MAX) return Status{VDF_ERR_BAD_ARG, "count must be 1..64"};
     if (!v || !n || !w || ptr_is_device(w) || ptr_is_device(n)) return Status{VDF_ERR_BAD_ARG, kHostScalar};
     const void* dv[vdf::LINCOMB_MAX];

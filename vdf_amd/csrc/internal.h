@@ -5,8 +5,10 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/vdf_hip.h"
+#include "pasta_constants.h"
 
 namespace vdf {
 // Per-launch timing for the roofline report (vdf_ctx_set_kernel_timing): a launch site constructs a KTimer around its
@@ -54,7 +56,6 @@ struct vdf_queue_family {
 struct vdf_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  bool own_stream = false;
   int pool_slot = -1;                // >= 0: the stream belongs to the device's pool of hardware queues (vdf_ctx_create_pooled)
   std::shared_ptr<vdf_queue_family> family;   // the stream is family->s[family_idx] (vdf_ctx_create: 0; vdf_ctx_create_pooled_near: 1, 2)
   int family_idx = -1;
@@ -178,6 +179,66 @@ inline Status hip_status(hipError_t e, const char* what) {
     if (!s__.ok()) return s__;        \
   } while (0)
 
+// ---- run-time field / curve -> template argument -----------------------------------------
+// Every kernel is a template over the field (FpParams / FqParams, pasta_constants.h); this is the one way a launcher gets
+// from an `int field` or `int curve` to that argument.  The body is a generic lambda over tags:
+//   return with_field(field, [&](auto f) { hipLaunchKernelGGL((k_axpy<tag_t<decltype(f)>>), ...); });
+// A body that returns void is a plain launch and is followed by the hipGetLastError() check here; a body that returns a
+// Status (a launcher that is itself a template, or one with several checked steps) has its Status passed on.
+template <class P> struct FieldTag { using type = P; };
+template <class Tag> using tag_t = typename Tag::type;
+constexpr int field_id(FieldTag<FpParams>) { return VDF_FIELD_FP; }
+constexpr int field_id(FieldTag<FqParams>) { return VDF_FIELD_FQ; }
+
+template <class F, class... Tags> Status dispatch_body(F&& f, Tags... tags) {
+  if constexpr (std::is_void<decltype(f(tags...))>::value) {
+    f(tags...);
+    VDF_TRY_HIP(hipGetLastError());
+    return Status{};
+  } else {
+    return f(tags...);
+  }
+}
+
+template <class F> Status with_field(int field, F&& f) {
+  if (field == VDF_FIELD_FP) return dispatch_body(f, FieldTag<FpParams>{});
+  if (field == VDF_FIELD_FQ) return dispatch_body(f, FieldTag<FqParams>{});
+  return Status{VDF_ERR_BAD_ARG, "unknown field"};
+}
+// f(base, scalar): the field of a curve's coordinates and the field of its scalars.  THE table of the Pasta cycle, stated
+// here and nowhere else: Pallas = (Fp coordinates, Fq scalars), Vesta = (Fq coordinates, Fp scalars).
+template <class F> Status with_curve(int curve, F&& f) {
+  if (curve == VDF_CURVE_PALLAS) return dispatch_body(f, FieldTag<FpParams>{}, FieldTag<FqParams>{});
+  if (curve == VDF_CURVE_VESTA) return dispatch_body(f, FieldTag<FqParams>{}, FieldTag<FpParams>{});
+  return Status{VDF_ERR_BAD_ARG, "unknown curve"};
+}
+// the checks alone, for an entry point that allocates, uploads or caches something before its first launch
+inline Status check_field(int field) { return with_field(field, [](auto) { return Status{}; }); }
+inline Status check_curve(int curve) { return with_curve(curve, [](auto, auto) { return Status{}; }); }
+// VDF_FIELD_* of a curve's scalars (-1: unknown curve)
+inline int field_of_curve_scalar(int curve) {
+  int field = -1;
+  (void)with_curve(curve, [&](auto, auto scalar) { field = field_id(scalar); return Status{}; });
+  return field;
+}
+// A small compile-time integer (a reduction kind, variables per round, lanes per row, a batch width) from its run-time
+// value: f(std::integral_constant<int, V>{}) for the V of the list that equals v, under the same void / Status rule; a value
+// outside the list is VDF_ERR_BAD_ARG with the site's own message.  Only the listed values are instantiated, in the order of
+// the list (the kernels of a code object lie in the order of their instantiation).
+template <int... Vs, class F> Status with_int(int v, const char* otherwise, F&& f) {
+  Status st{VDF_ERR_BAD_ARG, otherwise};
+  (void)(... || (v == Vs && ((st = dispatch_body(f, std::integral_constant<int, Vs>{})), true)));
+  return st;
+}
+template <class F> Status with_bool(bool v, F&& f) {
+  return v ? dispatch_body(f, std::true_type{}) : dispatch_body(f, std::false_type{});
+}
+
+// device vectors travel through the ABI as void*; the kernels take bytes
+inline const char* cbytes_of(const void* p) { return static_cast<const char*>(p); }
+inline char* bytes_of(void* p) { return static_cast<char*>(p); }
+inline dim3 grid_for(size_t n) { return dim3((unsigned)((n + 255) / 256)); }     // one lane per element, workgroups of 256
+
 // ---- msm.hip --------------------------------------------------------------------------
 constexpr int MSM_MAX_GROUPS = 4;
 // A plan covers a BATCH of 1..4 independent MSMs ("groups") over the same generator table: each group has its
@@ -297,7 +358,7 @@ Status snark_pair_table(int field, const vdf_fe* lo, const vdf_fe* hi, int k, vo
 // snark_ipa_block_bytes(count) bytes, which the kernel reads from device memory
 size_t snark_ipa_block_bytes(int count);
 void snark_ipa_pack(const vdf_ipa_opening* ops, int count, void* block);
-void snark_field_one(int field, vdf_fe* out);             // 1 in Montgomery form
+Status snark_field_one(int field, vdf_fe* out);           // 1 in Montgomery form
 Status snark_ipa_coefficients(int field, const void* block, int count, size_t n, void* out, hipStream_t s);
 Status snark_fold_halves(int field, int k, void* const v[], const vdf_fe c_lo[], const vdf_fe c_hi[], size_t n, hipStream_t s);
 size_t snark_reduce_scratch_bytes();

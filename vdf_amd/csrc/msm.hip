@@ -1479,21 +1479,16 @@ __global__ __launch_bounds__(256) void k_glv_split(const uint32_t* __restrict__ 
   for (int l = 0; l < 8; ++l) { out[(size_t)i * 8 + l] = k1[l]; out[((size_t)n + i) * 8 + l] = k2[l]; }
 }
 Status glv_points(int curve, const void* d_pts, size_t n, void* d_out, hipStream_t stream) {
-  const dim3 grid((unsigned)((n + 255) / 256));
-  if (curve == VDF_CURVE_PALLAS) hipLaunchKernelGGL((k_glv_points<FpParams>), grid, dim3(256), 0, stream, reinterpret_cast<const char*>(d_pts), (uint32_t)n, reinterpret_cast<char*>(d_out));
-  else if (curve == VDF_CURVE_VESTA) hipLaunchKernelGGL((k_glv_points<FqParams>), grid, dim3(256), 0, stream, reinterpret_cast<const char*>(d_pts), (uint32_t)n, reinterpret_cast<char*>(d_out));
-  else return Status{VDF_ERR_BAD_ARG, "unknown curve"};
-  VDF_TRY_HIP(hipGetLastError());
-  return Status{};
+  return with_curve(curve, [&](auto base, auto) {
+    hipLaunchKernelGGL((k_glv_points<tag_t<decltype(base)>>), grid_for(n), dim3(256), 0, stream, cbytes_of(d_pts), (uint32_t)n, bytes_of(d_out));
+  });
 }
 Status glv_split(int curve, const void* d_scalars, size_t n, bool is_mont, void* d_out, hipStream_t stream) {
-  const dim3 grid((unsigned)((n + 255) / 256));
   KTimer kt(stream, "k_glv_split", 96.0 * n);
-  if (curve == VDF_CURVE_PALLAS) hipLaunchKernelGGL((k_glv_split<FqParams>), grid, dim3(256), 0, stream, reinterpret_cast<const uint32_t*>(d_scalars), (uint32_t)n, is_mont ? 1 : 0, reinterpret_cast<uint32_t*>(d_out));
-  else if (curve == VDF_CURVE_VESTA) hipLaunchKernelGGL((k_glv_split<FpParams>), grid, dim3(256), 0, stream, reinterpret_cast<const uint32_t*>(d_scalars), (uint32_t)n, is_mont ? 1 : 0, reinterpret_cast<uint32_t*>(d_out));
-  else return Status{VDF_ERR_BAD_ARG, "unknown curve"};
-  VDF_TRY_HIP(hipGetLastError());
-  return Status{};
+  return with_curve(curve, [&](auto, auto scalar) {
+    hipLaunchKernelGGL((k_glv_split<tag_t<decltype(scalar)>>), grid_for(n), dim3(256), 0, stream, reinterpret_cast<const uint32_t*>(d_scalars), (uint32_t)n,
+                       is_mont ? 1 : 0, reinterpret_cast<uint32_t*>(d_out));
+  });
 }
 
 // table[j][i] = 2^(shift*j) * P_i
@@ -1526,7 +1521,7 @@ static Status msm_tail_t(int c, int sets, int groups, uint32_t nbk, const char* 
     char* parts = partials + g.sums_bytes;
     hipLaunchKernelGGL((k_red_sums<P>), dim3(gsets * g.wgs_per_set), dim3(256), 0, st, bucket_acc, nbk, g.Lb, g.Q, g.wgs_per_set, sums, prio);
     hipLaunchKernelGGL((k_red_weights<P>), dim3(gsets * (g.bA + g.bB)), dim3(256), 0, st, sums, nbk, g.Lb, g.bA, g.bB, parts, prio);
-    char* direct = sets == 1 ? reinterpret_cast<char*>(d_out) : nullptr;
+    char* direct = sets == 1 ? bytes_of(d_out) : nullptr;
     hipLaunchKernelGGL((k_red_combine<P>), dim3(gsets), dim3(256), 0, st, parts, g.Lb, g.bA, g.bB, wsum, direct, prio);
     if (direct) {
       VDF_TRY_HIP(hipGetLastError());
@@ -1538,7 +1533,7 @@ static Status msm_tail_t(int c, int sets, int groups, uint32_t nbk, const char* 
                        bucket_acc, nbk, rg.seg, rg.threads_per_set, rg.blocks_per_set, partials, prio);
     hipLaunchKernelGGL((k_reduce2<P>), dim3(gsets), dim3(256), 0, st, partials, rg.blocks_per_set, wsum, prio);
   }
-  hipLaunchKernelGGL((k_final<P>), dim3(groups), dim3(64), 0, st, wsum, sets, c, reinterpret_cast<char*>(d_out), prio);
+  hipLaunchKernelGGL((k_final<P>), dim3(groups), dim3(64), 0, st, wsum, sets, c, bytes_of(d_out), prio);
   VDF_TRY_HIP(hipGetLastError());
   return Status{};
 }
@@ -1549,7 +1544,7 @@ template <class P, class SP>
 static Status msm_run_t(const MsmPlan& p, const void* d_points, const void* const* d_scalars, bool is_mont, void* ws,
                         void* d_out, hipStream_t st, hipEvent_t* ev, char* ext_bucket_acc, hipEvent_t acc_gate, int prio) {
   const WsLayout w = ws_layout(p);
-  char* base = reinterpret_cast<char*>(ws);
+  char* base = bytes_of(ws);
   uint32_t* countsA = reinterpret_cast<uint32_t*>(base + w.countsA);
   uint32_t* pcount = reinterpret_cast<uint32_t*>(base + w.pcount);
   uint32_t* pstart = reinterpret_cast<uint32_t*>(base + w.pstart);
@@ -1611,7 +1606,7 @@ static Status msm_run_t(const MsmPlan& p, const void* d_points, const void* cons
   // one CU and one onto another when other queues hold slots (a CU with three takes 1.5 x as long: the launch's tail)
   const unsigned acc_lds = (unsigned)(tuning().accumulate_lds >= 0 && tuning().accumulate_lds <= 65536 ? tuning().accumulate_lds : 0);
   hipLaunchKernelGGL((k_accumulate<P>), dim3((p.nthreads + 255) / 256), dim3(256), acc_lds, st, sorted, bstart, nkeys,
-                     reinterpret_cast<const uint32_t*>(base + w.tstart), reinterpret_cast<const char*>(d_points), bucket_acc, heads, p.slots, p.Lfixed, p.nthreads);
+                     reinterpret_cast<const uint32_t*>(base + w.tstart), cbytes_of(d_points), bucket_acc, heads, p.slots, p.Lfixed, p.nthreads);
   }
   if (ev) VDF_TRY_HIP(hipEventRecord(ev[2], st));
   const FixupTune tune = fixup_tune();
@@ -1632,14 +1627,11 @@ static Status msm_run_t(const MsmPlan& p, const void* d_points, const void* cons
 
 Status msm_run(int curve, const MsmPlan& plan, const void* d_points, const void* const* d_scalars, bool is_mont, void* ws,
                void* d_out, hipStream_t stream, hipEvent_t* ev, void* ext_bucket_acc, hipEvent_t acc_gate, int prio) {
-  // Pallas: coordinates in Fp, scalars in Fq.  Vesta: coordinates in Fq, scalars in Fp.
-  char* ext = reinterpret_cast<char*>(ext_bucket_acc);
+  char* ext = bytes_of(ext_bucket_acc);
   prio = std::min(prio, (int)tuning().light_priority);     // the process-wide ceiling holds on EVERY path that gets here (jobs too)
-  if (curve == VDF_CURVE_PALLAS)
-    return msm_run_t<FpParams, FqParams>(plan, d_points, d_scalars, is_mont, ws, d_out, stream, ev, ext, acc_gate, prio);
-  if (curve == VDF_CURVE_VESTA)
-    return msm_run_t<FqParams, FpParams>(plan, d_points, d_scalars, is_mont, ws, d_out, stream, ev, ext, acc_gate, prio);
-  return Status{VDF_ERR_BAD_ARG, "unknown curve"};
+  return with_curve(curve, [&](auto base, auto scalar) {
+    return msm_run_t<tag_t<decltype(base)>, tag_t<decltype(scalar)>>(plan, d_points, d_scalars, is_mont, ws, d_out, stream, ev, ext, acc_gate, prio);
+  });
 }
 
 // Stand-alone bucket reduction over `groups` x `sets` bucket sets laid out back to back (a job's shared array).
@@ -1656,12 +1648,12 @@ size_t msm_tail_ws_bytes(int groups, int sets, uint32_t nbk) {
 Status msm_tail(int curve, int c, int sets, int groups, uint32_t nbk, void* tail_ws, void* d_out, hipStream_t stream, int prio) {
   const size_t gsets = (size_t)groups * sets;
   prio = std::min(prio, (int)tuning().light_priority);
-  char* bucket_acc = reinterpret_cast<char*>(tail_ws);
+  char* bucket_acc = bytes_of(tail_ws);
   char* partials = bucket_acc + align_up(gsets * nbk * 128, 256);
   char* wsum = partials + tail_scratch_bytes(gsets, nbk);
-  if (curve == VDF_CURVE_PALLAS) return msm_tail_t<FpParams>(c, sets, groups, nbk, bucket_acc, partials, wsum, d_out, stream, prio);
-  if (curve == VDF_CURVE_VESTA) return msm_tail_t<FqParams>(c, sets, groups, nbk, bucket_acc, partials, wsum, d_out, stream, prio);
-  return Status{VDF_ERR_BAD_ARG, "unknown curve"};
+  return with_curve(curve, [&](auto base, auto) {
+    return msm_tail_t<tag_t<decltype(base)>>(c, sets, groups, nbk, bucket_acc, partials, wsum, d_out, stream, prio);
+  });
 }
 
 // sum of n Jacobian points: one wavefront = 16 quads striding over the inputs, butterfly reduce
@@ -1688,44 +1680,22 @@ __global__ __launch_bounds__(64) void k_point_sum(const char* __restrict__ pts, 
 
 Status point_sum(int curve, const void* d_jac, size_t n, void* d_out, hipStream_t stream) {
   const int prio = std::min(3, (int)tuning().light_priority);
-  if (curve == VDF_CURVE_PALLAS)
-    hipLaunchKernelGGL((k_point_sum<FpParams>), dim3(1), dim3(64), 0, stream, reinterpret_cast<const char*>(d_jac),
-                       (uint32_t)n, reinterpret_cast<char*>(d_out), prio);
-  else if (curve == VDF_CURVE_VESTA)
-    hipLaunchKernelGGL((k_point_sum<FqParams>), dim3(1), dim3(64), 0, stream, reinterpret_cast<const char*>(d_jac),
-                       (uint32_t)n, reinterpret_cast<char*>(d_out), prio);
-  else
-    return Status{VDF_ERR_BAD_ARG, "unknown curve"};
-  VDF_TRY_HIP(hipGetLastError());
-  return Status{};
+  return with_curve(curve, [&](auto base, auto) {
+    hipLaunchKernelGGL((k_point_sum<tag_t<decltype(base)>>), dim3(1), dim3(64), 0, stream, cbytes_of(d_jac), (uint32_t)n, bytes_of(d_out), prio);
+  });
 }
 
 Status bases_generate(int curve, int family, uint64_t seed, size_t start, size_t n, void* d_pts, hipStream_t stream) {
   if (n == 0) return Status{};
-  dim3 grid((unsigned)((n + 255) / 256));
-  if (family == VDF_GENS_TRY_AND_INCREMENT) {
-    if (curve == VDF_CURVE_PALLAS)
-      hipLaunchKernelGGL((k_bases_generate_tai<FpParams>), grid, dim3(256), 0, stream, seed, (uint64_t)start, (uint32_t)n,
-                         reinterpret_cast<char*>(d_pts));
-    else if (curve == VDF_CURVE_VESTA)
-      hipLaunchKernelGGL((k_bases_generate_tai<FqParams>), grid, dim3(256), 0, stream, seed, (uint64_t)start, (uint32_t)n,
-                         reinterpret_cast<char*>(d_pts));
-    else
-      return Status{VDF_ERR_BAD_ARG, "unknown curve"};
-    VDF_TRY_HIP(hipGetLastError());
-    return Status{};
-  }
+  if (family == VDF_GENS_TRY_AND_INCREMENT)
+    return with_curve(curve, [&](auto base, auto) {
+      hipLaunchKernelGGL((k_bases_generate_tai<tag_t<decltype(base)>>), grid_for(n), dim3(256), 0, stream, seed, (uint64_t)start, (uint32_t)n,
+                         bytes_of(d_pts));
+    });
   if (family != VDF_GENS_KNOWN_DLOG) return Status{VDF_ERR_BAD_ARG, "unknown generator family"};
-  if (curve == VDF_CURVE_PALLAS)
-    hipLaunchKernelGGL((k_bases_generate<FpParams>), grid, dim3(256), 0, stream, seed, (uint64_t)start, (uint32_t)n,
-                       reinterpret_cast<char*>(d_pts));
-  else if (curve == VDF_CURVE_VESTA)
-    hipLaunchKernelGGL((k_bases_generate<FqParams>), grid, dim3(256), 0, stream, seed, (uint64_t)start, (uint32_t)n,
-                       reinterpret_cast<char*>(d_pts));
-  else
-    return Status{VDF_ERR_BAD_ARG, "unknown curve"};
-  VDF_TRY_HIP(hipGetLastError());
-  return Status{};
+  return with_curve(curve, [&](auto base, auto) {
+    hipLaunchKernelGGL((k_bases_generate<tag_t<decltype(base)>>), grid_for(n), dim3(256), 0, stream, seed, (uint64_t)start, (uint32_t)n, bytes_of(d_pts));
+  });
 }
 
 Status bases_generate_label(int curve, const uint8_t* label, size_t len, size_t start, size_t n, void* d_pts, hipStream_t stream) {
@@ -1735,47 +1705,27 @@ Status bases_generate_label(int curve, const uint8_t* label, size_t len, size_t 
   std::memset(&gl, 0, sizeof(gl));
   if (len) std::memcpy(gl.bytes, label, len);
   gl.len = (uint32_t)len;
-  dim3 grid((unsigned)((n + 255) / 256));
-  if (curve == VDF_CURVE_PALLAS)
-    hipLaunchKernelGGL((k_bases_generate_label<FpParams>), grid, dim3(256), 0, stream, gl, (uint32_t)curve, (uint64_t)start, (uint32_t)n,
-                       reinterpret_cast<char*>(d_pts));
-  else if (curve == VDF_CURVE_VESTA)
-    hipLaunchKernelGGL((k_bases_generate_label<FqParams>), grid, dim3(256), 0, stream, gl, (uint32_t)curve, (uint64_t)start, (uint32_t)n,
-                       reinterpret_cast<char*>(d_pts));
-  else
-    return Status{VDF_ERR_BAD_ARG, "unknown curve"};
-  VDF_TRY_HIP(hipGetLastError());
-  return Status{};
+  return with_curve(curve, [&](auto base, auto) {
+    hipLaunchKernelGGL((k_bases_generate_label<tag_t<decltype(base)>>), grid_for(n), dim3(256), 0, stream, gl, (uint32_t)curve, (uint64_t)start, (uint32_t)n,
+                       bytes_of(d_pts));
+  });
 }
 
 Status bases_validate(int curve, const void* d_pts, size_t n, uint32_t* d_flags, hipStream_t stream) {
   if (n == 0) return Status{};
-  dim3 grid((unsigned)((n + 255) / 256));
-  if (curve == VDF_CURVE_PALLAS)
-    hipLaunchKernelGGL((k_validate_points<FpParams>), grid, dim3(256), 0, stream, reinterpret_cast<const char*>(d_pts), (uint32_t)n, d_flags);
-  else if (curve == VDF_CURVE_VESTA)
-    hipLaunchKernelGGL((k_validate_points<FqParams>), grid, dim3(256), 0, stream, reinterpret_cast<const char*>(d_pts), (uint32_t)n, d_flags);
-  else
-    return Status{VDF_ERR_BAD_ARG, "unknown curve"};
-  VDF_TRY_HIP(hipGetLastError());
-  return Status{};
+  return with_curve(curve, [&](auto base, auto) {
+    hipLaunchKernelGGL((k_validate_points<tag_t<decltype(base)>>), grid_for(n), dim3(256), 0, stream, cbytes_of(d_pts), (uint32_t)n, d_flags);
+  });
 }
 
 Status bases_precompute(int curve, const void* d_pts, size_t n, int c, int sets, int tables, void* d_table,
                         hipStream_t stream) {
   if (n == 0) return Status{};
-  dim3 grid((unsigned)((n + 255) / 256));
   const int shift = c * sets;
-  if (curve == VDF_CURVE_PALLAS)
-    hipLaunchKernelGGL((k_precompute<FpParams>), grid, dim3(256), 0, stream, reinterpret_cast<const char*>(d_pts),
-                       (uint32_t)n, shift, tables, reinterpret_cast<char*>(d_table));
-  else if (curve == VDF_CURVE_VESTA)
-    hipLaunchKernelGGL((k_precompute<FqParams>), grid, dim3(256), 0, stream, reinterpret_cast<const char*>(d_pts),
-                       (uint32_t)n, shift, tables, reinterpret_cast<char*>(d_table));
-  else
-    return Status{VDF_ERR_BAD_ARG, "unknown curve"};
-  VDF_TRY_HIP(hipGetLastError());
-  return Status{};
+  return with_curve(curve, [&](auto base, auto) {
+    hipLaunchKernelGGL((k_precompute<tag_t<decltype(base)>>), grid_for(n), dim3(256), 0, stream, cbytes_of(d_pts), (uint32_t)n, shift, tables,
+                       bytes_of(d_table));
+  });
 }
 
 }  // namespace vdf

@@ -93,31 +93,28 @@ Status digits_build(int curve, const void* d_pts, size_t first, size_t nslots, s
   if (nslots == 0) return Status{};
   const int W = direct_windows(c);
   const uint32_t M = 1u << (c - 1);
-  char* D = reinterpret_cast<char*>(d_digits) + ((slot0 * W) << (c - 1)) * 64;
-  const char* pts = reinterpret_cast<const char*>(d_pts) + first * 64;
+  char* D = bytes_of(d_digits) + ((slot0 * W) << (c - 1)) * 64;
+  const char* pts = cbytes_of(d_pts) + first * 64;
   // the fill keeps M/2 prefix products per thread: chunks of (slot, window) pairs under 256 MiB of scratch
   const size_t per_thread = (size_t)(M / 2) * 32;
   size_t chunk = ((size_t)256 << 20) / per_thread;
   if (chunk > nslots * W) chunk = nslots * W;
   if (chunk < 256) chunk = 256;
-  void* scratch = nullptr;
-  VDF_TRY_HIP(hipMalloc(&scratch, chunk * per_thread));
-  const dim3 gb((unsigned)((nslots + 255) / 256));
-  if (curve == VDF_CURVE_PALLAS) hipLaunchKernelGGL((k_digit_base<FpParams>), gb, dim3(256), 0, stream, pts, (uint32_t)nslots, c, W, D);
-  else hipLaunchKernelGGL((k_digit_base<FqParams>), gb, dim3(256), 0, stream, pts, (uint32_t)nslots, c, W, D);
-  for (size_t p0 = 0; p0 < nslots * W; p0 += chunk) {
-    const size_t np = (p0 + chunk <= nslots * W) ? chunk : nslots * W - p0;
-    const dim3 g((unsigned)((np + 255) / 256));
-    if (curve == VDF_CURVE_PALLAS)
-      hipLaunchKernelGGL((k_digit_fill<FpParams>), g, dim3(256), 0, stream, D, (uint32_t)p0, (uint32_t)np, c, reinterpret_cast<char*>(scratch));
-    else
-      hipLaunchKernelGGL((k_digit_fill<FqParams>), g, dim3(256), 0, stream, D, (uint32_t)p0, (uint32_t)np, c, reinterpret_cast<char*>(scratch));
-  }
-  hipError_t e = hipStreamSynchronize(stream);
-  (void)hipFree(scratch);
-  VDF_TRY_HIP(e);
-  VDF_TRY_HIP(hipGetLastError());
-  return Status{};
+  return with_curve(curve, [&](auto base, auto) -> Status {
+    using P = tag_t<decltype(base)>;
+    void* scratch = nullptr;
+    VDF_TRY_HIP(hipMalloc(&scratch, chunk * per_thread));
+    hipLaunchKernelGGL((k_digit_base<P>), grid_for(nslots), dim3(256), 0, stream, pts, (uint32_t)nslots, c, W, D);
+    for (size_t p0 = 0; p0 < nslots * W; p0 += chunk) {
+      const size_t np = (p0 + chunk <= nslots * W) ? chunk : nslots * W - p0;
+      hipLaunchKernelGGL((k_digit_fill<P>), grid_for(np), dim3(256), 0, stream, D, (uint32_t)p0, (uint32_t)np, c, bytes_of(scratch));
+    }
+    hipError_t e = hipStreamSynchronize(stream);
+    (void)hipFree(scratch);
+    VDF_TRY_HIP(e);
+    VDF_TRY_HIP(hipGetLastError());
+    return Status{};
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -350,14 +347,12 @@ static Status direct_run_t(int groups, const size_t* n, const size_t* slot0, con
   for (int g = 0; g < groups; ++g) empty_group |= geo.waves[g] == 0;
   if (waves) {
     KTimer kt(st, "k_direct_sum", 96.0 * nsum);         // a commitment's algorithmic bytes: 96 B per (base, scalar) pair
-    hipLaunchKernelGGL((k_direct_sum<P, SP>), dim3(waves / 4), dim3(256), 0, st, a, is_mont ? 1 : 0, c, W,
-                       reinterpret_cast<const char*>(d_digits), reinterpret_cast<char*>(ws), arrived, reinterpret_cast<char*>(d_out),
-                       tuning().direct_priority, fused);
+    hipLaunchKernelGGL((k_direct_sum<P, SP>), dim3(waves / 4), dim3(256), 0, st, a, is_mont ? 1 : 0, c, W, cbytes_of(d_digits), bytes_of(ws), arrived,
+                       bytes_of(d_out), tuning().direct_priority, fused);
   }
   if (empty_group || !fused) {     // a group without scalars has no workgroup to write its identity: the second launch does
     KTimer kt(st, "k_direct_final", 0.0);
-    hipLaunchKernelGGL((k_direct_final<P>), dim3(groups), dim3(256), 0, st, a, reinterpret_cast<const char*>(ws),
-                       reinterpret_cast<char*>(d_out));
+    hipLaunchKernelGGL((k_direct_final<P>), dim3(groups), dim3(256), 0, st, a, cbytes_of(ws), bytes_of(d_out));
   }
   VDF_TRY_HIP(hipGetLastError());
   return Status{};
@@ -365,11 +360,10 @@ static Status direct_run_t(int groups, const size_t* n, const size_t* slot0, con
 
 Status msm_direct_run(int curve, int groups, const size_t* n, const size_t* slot0, const void* const* d_scalars, bool is_mont,
                       int c, int num_cus, const void* d_digits, void* ws, void* d_out, uint32_t* arrived, hipStream_t stream) {
-  if (curve == VDF_CURVE_PALLAS)
-    return direct_run_t<FpParams, FqParams>(groups, n, slot0, d_scalars, is_mont, c, num_cus, d_digits, ws, d_out, arrived, stream);
-  if (curve == VDF_CURVE_VESTA)
-    return direct_run_t<FqParams, FpParams>(groups, n, slot0, d_scalars, is_mont, c, num_cus, d_digits, ws, d_out, arrived, stream);
-  return Status{VDF_ERR_BAD_ARG, "unknown curve"};
+  return with_curve(curve, [&](auto base, auto scalar) {
+    return direct_run_t<tag_t<decltype(base)>, tag_t<decltype(scalar)>>(groups, n, slot0, d_scalars, is_mont, c, num_cus, d_digits, ws, d_out, arrived,
+                                                                       stream);
+  });
 }
 
 }  // namespace vdf

@@ -34,15 +34,6 @@ template <class P> __device__ __forceinline__ Fe<P> arg_fe(const FeArg& a) {
   return r;
 }
 static FeArg to_arg(const vdf_fe* p) { FeArg v; std::memcpy(v.v, p, 32); return v; }
-static inline dim3 grid_for(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
-#define SNARK_DISPATCH(field, KERNEL, ...)                                                       \
-  do {                                                                                           \
-    if ((field) == VDF_FIELD_FP) hipLaunchKernelGGL((KERNEL<FpParams>), __VA_ARGS__);            \
-    else if ((field) == VDF_FIELD_FQ) hipLaunchKernelGGL((KERNEL<FqParams>), __VA_ARGS__);       \
-    else return Status{VDF_ERR_BAD_ARG, "unknown field"};                                        \
-    VDF_TRY_HIP(hipGetLastError());                                                              \
-  } while (0)
 
 // ---- tensor-product tables ---------------------------------------------------------------------------
 struct PairArgs { FeArg lo[24], hi[24]; int k; };
@@ -67,8 +58,9 @@ Status snark_pair_table(int field, const vdf_fe* lo, const vdf_fe* hi, int k, vo
   for (int j = 0; j < k; ++j) { a.lo[j] = to_arg(&lo[j]); a.hi[j] = to_arg(&hi[j]); }
   const size_t n = (size_t)1 << k;
   KTimer kt(s, "k_eq_table", 32.0 * n);                          // one element written per index; the factors are kernel arguments
-  SNARK_DISPATCH(field, k_eq_table, grid_for(n), dim3(256), 0, s, a, n, reinterpret_cast<char*>(out));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_eq_table<tag_t<decltype(f)>>), grid_for(n), dim3(256), 0, s, a, n, bytes_of(out));
+  });
 }
 
 // ---- the inner-product argument's generator coefficients, for many openings at once ------------------------------
@@ -99,9 +91,12 @@ void snark_ipa_pack(const vdf_ipa_opening* ops, int count, void* block) {
   }
 }
 
-void snark_field_one(int field, vdf_fe* out) {
-  if (field == VDF_FIELD_FP) { const Fe<FpParams> one = fe_one<FpParams>(); std::memcpy(out, one.v, 32); }
-  else { const Fe<FqParams> one = fe_one<FqParams>(); std::memcpy(out, one.v, 32); }
+Status snark_field_one(int field, vdf_fe* out) {
+  return with_field(field, [&](auto f) {
+    const auto one = fe_one<tag_t<decltype(f)>>();
+    std::memcpy(out, one.v, 32);
+    return Status{};
+  });
 }
 
 template <class P>
@@ -169,9 +164,9 @@ Status snark_ipa_coefficients(int field, const void* block, int count, size_t n,
   const size_t waves = (n + 64 * IPA_RUN - 1) / (64 * IPA_RUN);
   const dim3 grid((unsigned)((waves + 3) / 4));
   KTimer kt(s, "k_ipa_coefficients", 32.0 * n);                // one element written per index; the factors are a few KiB
-  SNARK_DISPATCH(field, k_ipa_coefficients, grid, dim3(256), 0, s, reinterpret_cast<const IpaOpDev*>(block), count, n,
-                 reinterpret_cast<char*>(out));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_ipa_coefficients<tag_t<decltype(f)>>), grid, dim3(256), 0, s, reinterpret_cast<const IpaOpDev*>(block), count, n, bytes_of(out));
+  });
 }
 
 // ---- folding the two halves of up to 8 vectors ----------------------------------------------------------
@@ -194,12 +189,13 @@ Status snark_fold_halves(int field, int k, void* const v[], const vdf_fe c_lo[],
   if (n < 2 || (n & (n - 1))) return Status{VDF_ERR_BAD_LENGTH, "length must be a power of two >= 2"};
   FoldHalvesArgs a{};
   a.k = k;
-  for (int t = 0; t < k; ++t) { a.v[t] = reinterpret_cast<char*>(v[t]); a.c_lo[t] = to_arg(&c_lo[t]); a.c_hi[t] = to_arg(&c_hi[t]); }
+  for (int t = 0; t < k; ++t) { a.v[t] = bytes_of(v[t]); a.c_lo[t] = to_arg(&c_lo[t]); a.c_hi[t] = to_arg(&c_hi[t]); }
   const size_t h = n / 2;
   dim3 grid((unsigned)((h + 255) / 256), (unsigned)k);
   KTimer kt(s, "k_fold_halves", 96.0 * h * k);                   // two halves read, the lower one written, per vector
-  SNARK_DISPATCH(field, k_fold_halves, grid, dim3(256), 0, s, a, h);
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_fold_halves<tag_t<decltype(f)>>), grid, dim3(256), 0, s, a, h);
+  });
 }
 
 // ---- reductions ------------------------------------------------------------------------------------------
@@ -291,32 +287,30 @@ static Status reduce_launch(const ReduceArgs& a, void* scratch, void* out, hipSt
   int blocks = (int)((h + 255) / 256);
   if (blocks > REDUCE_BLOCKS) blocks = REDUCE_BLOCKS;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((k_reduce<P, KIND>), dim3(blocks), dim3(256), 0, s, a, reinterpret_cast<char*>(scratch));
-  hipLaunchKernelGGL((k_reduce_final<P, NOUT>), dim3(1), dim3(256), 0, s, reinterpret_cast<const char*>(scratch), blocks,
-                     reinterpret_cast<char*>(out));
+  hipLaunchKernelGGL((k_reduce<P, KIND>), dim3(blocks), dim3(256), 0, s, a, bytes_of(scratch));
+  hipLaunchKernelGGL((k_reduce_final<P, NOUT>), dim3(1), dim3(256), 0, s, cbytes_of(scratch), blocks, bytes_of(out));
   VDF_TRY_HIP(hipGetLastError());
   return Status{};
 }
 
+static constexpr const char* BAD_KIND = "unknown reduction";
 size_t snark_reduce_scratch_bytes() { return (size_t)REDUCE_BLOCKS * 3 * 32; }
 
 Status snark_reduce(int field, int kind, const void* const tables[], const vdf_fe* u, size_t n, void* scratch, void* out,
                     hipStream_t s) {
-  if (kind < 0 || kind > 3) return Status{VDF_ERR_BAD_ARG, "unknown reduction"};
+  if (kind < 0 || kind > 3) return Status{VDF_ERR_BAD_ARG, BAD_KIND};
   if (kind != 0 && (n < 2 || (n & (n - 1)))) return Status{VDF_ERR_BAD_LENGTH, "length must be a power of two >= 2"};
   ReduceArgs a{};
   const int ntab = kind == 2 ? 5 : 2;
-  for (int k = 0; k < ntab; ++k) a.t[k] = reinterpret_cast<const char*>(tables[k]);
+  for (int k = 0; k < ntab; ++k) a.t[k] = cbytes_of(tables[k]);
   if (u) a.u = to_arg(u);
   a.n = n;
   // bytes read: kind 0 two vectors of n; kind 1 / 3 two vectors of n (both halves); kind 2 five tables of n
   KTimer kt(s, kind == 0 ? "k_reduce(dot)" : kind == 1 ? "k_reduce(quad round)" : kind == 2 ? "k_reduce(cubic round)" : "k_reduce(ipa cross)",
             32.0 * n * ntab);
-#define RL(P, K) reduce_launch<P, K>(a, scratch, out, s)
-  if (field == VDF_FIELD_FP) return kind == 0 ? RL(FpParams, 0) : kind == 1 ? RL(FpParams, 1) : kind == 2 ? RL(FpParams, 2) : RL(FpParams, 3);
-  if (field == VDF_FIELD_FQ) return kind == 0 ? RL(FqParams, 0) : kind == 1 ? RL(FqParams, 1) : kind == 2 ? RL(FqParams, 2) : RL(FqParams, 3);
-#undef RL
-  return Status{VDF_ERR_BAD_ARG, "unknown field"};
+  return with_field(field, [&](auto f) {
+    return with_int<0, 1, 2, 3>(kind, BAD_KIND, [&](auto k) { return reduce_launch<tag_t<decltype(f)>, k.value>(a, scratch, out, s); });
+  });
 }
 
 // ---- transposed sparse product -----------------------------------------------------------------------------
@@ -412,8 +406,10 @@ Status snark_spmvt(int field, const uint32_t* colptr, const uint32_t* rows, cons
                    void* scratch, hipStream_t s) {
   if (ncols == 0) return Status{};
   const FeArg r = to_arg(rho);
-  SNARK_DISPATCH(field, k_spmvt, grid_for(ncols), dim3(256), 0, s, colptr, rows, cm, reinterpret_cast<const char*>(dict),
-                 reinterpret_cast<const char*>(eq), r, ncols, reinterpret_cast<char*>(out));
+  VDF_TRY(with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_spmvt<tag_t<decltype(f)>>), grid_for(ncols), dim3(256), 0, s, colptr, rows, cm, cbytes_of(dict), cbytes_of(eq), r, ncols,
+                       bytes_of(out));
+  }));
   if (!nheavy) return Status{};
   // the list is sorted longest first: the first `nbig` columns (thousands of entries) are shared by SPMVT_PARTS workgroups
   // each, as far as the scratch reaches; the others get one workgroup each
@@ -424,14 +420,19 @@ Status snark_spmvt(int field, const uint32_t* colptr, const uint32_t* rows, cons
     if (shared > room) shared = room;
   }
   if (shared) {
-    SNARK_DISPATCH(field, k_spmvt_heavy_part, dim3((unsigned)(shared * SPMVT_PARTS)), dim3(256), 0, s, heavy, colptr, rows, cm,
-                   reinterpret_cast<const char*>(dict), reinterpret_cast<const char*>(eq), r, reinterpret_cast<char*>(scratch));
-    SNARK_DISPATCH(field, k_spmvt_heavy_sum, dim3((unsigned)shared), dim3(64), 0, s, heavy, reinterpret_cast<const char*>(scratch),
-                   reinterpret_cast<char*>(out));
+    VDF_TRY(with_field(field, [&](auto f) {
+      hipLaunchKernelGGL((k_spmvt_heavy_part<tag_t<decltype(f)>>), dim3((unsigned)(shared * SPMVT_PARTS)), dim3(256), 0, s, heavy, colptr, rows, cm,
+                         cbytes_of(dict), cbytes_of(eq), r, bytes_of(scratch));
+    }));
+    VDF_TRY(with_field(field, [&](auto f) {
+      hipLaunchKernelGGL((k_spmvt_heavy_sum<tag_t<decltype(f)>>), dim3((unsigned)shared), dim3(64), 0, s, heavy, cbytes_of(scratch), bytes_of(out));
+    }));
   }
   if (nheavy > shared)
-    SNARK_DISPATCH(field, k_spmvt_heavy, dim3((unsigned)(nheavy - shared)), dim3(256), 0, s, heavy + shared, colptr, rows, cm,
-                   reinterpret_cast<const char*>(dict), reinterpret_cast<const char*>(eq), r, reinterpret_cast<char*>(out));
+    return with_field(field, [&](auto f) {
+      hipLaunchKernelGGL((k_spmvt_heavy<tag_t<decltype(f)>>), dim3((unsigned)(nheavy - shared)), dim3(256), 0, s, heavy + shared, colptr, rows, cm,
+                         cbytes_of(dict), cbytes_of(eq), r, bytes_of(out));
+    });
   return Status{};
 }
 
@@ -469,16 +470,17 @@ __global__ __launch_bounds__(256) void k_scale_pattern(char* __restrict__ sv, si
 Status snark_ipa_scalars(int field, const void* a, const void* sv, size_t n, size_t nj, void* sL, void* sR, hipStream_t s) {
   if (n == 0 || (n & (n - 1)) || nj < 2 || (nj & (nj - 1)) || nj > n) return Status{VDF_ERR_BAD_LENGTH, "lengths must be powers of two, 2 <= n_j <= n"};
   KTimer kt(s, "k_ipa_scalars", 96.0 * n + 32.0 * nj);           // s read, sL and sR written, a read once
-  SNARK_DISPATCH(field, k_ipa_scalars, grid_for(n), dim3(256), 0, s, reinterpret_cast<const char*>(a),
-                 reinterpret_cast<const char*>(sv), n, nj, reinterpret_cast<char*>(sL), reinterpret_cast<char*>(sR));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_ipa_scalars<tag_t<decltype(f)>>), grid_for(n), dim3(256), 0, s, cbytes_of(a), cbytes_of(sv), n, nj, bytes_of(sL), bytes_of(sR));
+  });
 }
 
 Status snark_scale_pattern(int field, void* sv, size_t n, size_t nj, const vdf_fe* x_lo, const vdf_fe* x_hi, hipStream_t s) {
   if (n == 0 || (n & (n - 1)) || nj < 2 || (nj & (nj - 1)) || nj > n) return Status{VDF_ERR_BAD_LENGTH, "lengths must be powers of two, 2 <= n_j <= n"};
   KTimer kt(s, "k_scale_pattern", 64.0 * n);
-  SNARK_DISPATCH(field, k_scale_pattern, grid_for(n), dim3(256), 0, s, reinterpret_cast<char*>(sv), n, nj, to_arg(x_lo), to_arg(x_hi));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_scale_pattern<tag_t<decltype(f)>>), grid_for(n), dim3(256), 0, s, bytes_of(sv), n, nj, to_arg(x_lo), to_arg(x_hi));
+  });
 }
 
 // ---- the same passes for many instances at once (vdf_reduce_batch, vdf_fold_halves_batch, vdf_spmv3_t_batch) ----------
@@ -497,7 +499,7 @@ void snark_reduce_pack(int kind, int count, const void* const tables[], const vd
   ReduceItemDev* d = reinterpret_cast<ReduceItemDev*>(block);
   for (int q = 0; q < count; ++q) {
     ReduceItemDev it{};
-    for (int k = 0; k < ntab; ++k) it.t[k] = reinterpret_cast<const char*>(tables[(size_t)q * ntab + k]);
+    for (int k = 0; k < ntab; ++k) it.t[k] = cbytes_of(tables[(size_t)q * ntab + k]);
     if (u) it.u = to_arg(&u[q]);
     std::memcpy(&d[q], &it, sizeof(it));
   }
@@ -507,7 +509,7 @@ void snark_fold_pack(int k, void* const v[], const vdf_fe c_lo[], const vdf_fe c
   FoldItemDev* d = reinterpret_cast<FoldItemDev*>(block);
   for (int t = 0; t < k; ++t) {
     FoldItemDev it{};
-    it.v = reinterpret_cast<char*>(v[t]); it.c_lo = to_arg(&c_lo[t]); it.c_hi = to_arg(&c_hi[t]);
+    it.v = bytes_of(v[t]); it.c_lo = to_arg(&c_lo[t]); it.c_hi = to_arg(&c_hi[t]);
     std::memcpy(&d[t], &it, sizeof(it));
   }
 }
@@ -516,7 +518,7 @@ void snark_spmvt_pack(int count, const void* const eq[], const vdf_fe rho[], voi
   SpmvtItemDev* d = reinterpret_cast<SpmvtItemDev*>(block);
   for (int q = 0; q < count; ++q) {
     SpmvtItemDev it{};
-    it.eq = reinterpret_cast<const char*>(eq[q]); it.out = reinterpret_cast<char*>(out[q]); it.rho = to_arg(&rho[q]);
+    it.eq = cbytes_of(eq[q]); it.out = bytes_of(out[q]); it.rho = to_arg(&rho[q]);
     std::memcpy(&d[q], &it, sizeof(it));
   }
 }
@@ -565,26 +567,25 @@ static Status reduce_batch_launch(const void* block, int count, size_t n, void* 
   int need = (int)((h + 255) / 256);
   if (need < 1) need = 1;
   if (per > need) per = need;
-  hipLaunchKernelGGL((k_reduce_batch<P, KIND>), dim3((unsigned)per, (unsigned)count), dim3(256), 0, s,
-                     reinterpret_cast<const ReduceItemDev*>(block), n, reinterpret_cast<char*>(scratch));
-  hipLaunchKernelGGL((k_reduce_final_batch<P, NOUT>), dim3((unsigned)count), dim3(256), 0, s, reinterpret_cast<const char*>(scratch), per,
-                     reinterpret_cast<char*>(out));
+  hipLaunchKernelGGL((k_reduce_batch<P, KIND>), dim3((unsigned)per, (unsigned)count), dim3(256), 0, s, reinterpret_cast<const ReduceItemDev*>(block), n,
+                     bytes_of(scratch));
+  hipLaunchKernelGGL((k_reduce_final_batch<P, NOUT>), dim3((unsigned)count), dim3(256), 0, s, cbytes_of(scratch), per, bytes_of(out));
   VDF_TRY_HIP(hipGetLastError());
   return Status{};
 }
 
 Status snark_reduce_batch(int field, int kind, const void* block, int count, size_t n, void* scratch, void* out, hipStream_t s) {
-  if (kind < 0 || kind > 3) return Status{VDF_ERR_BAD_ARG, "unknown reduction"};
+  if (kind < 0 || kind > 3) return Status{VDF_ERR_BAD_ARG, BAD_KIND};
   static_assert(SNARK_REDUCE_BATCH_MAX <= REDUCE_BLOCKS, "the partials of a batch fill the reduction scratch");
   if (count < 0 || count > SNARK_REDUCE_BATCH_MAX) return Status{VDF_ERR_BAD_ARG, "0..512 instances"};
   if (kind != 0 && (n < 2 || (n & (n - 1)))) return Status{VDF_ERR_BAD_LENGTH, "length must be a power of two >= 2"};
   if (count == 0) return Status{};
   KTimer kt(s, "k_reduce_batch", 32.0 * n * (kind == 2 ? 5 : 2) * count);
-#define RB(P, K) reduce_batch_launch<P, K>(block, count, n, scratch, out, s)
-  if (field == VDF_FIELD_FP) return kind == 0 ? RB(FpParams, 0) : kind == 1 ? RB(FpParams, 1) : kind == 2 ? RB(FpParams, 2) : RB(FpParams, 3);
-  if (field == VDF_FIELD_FQ) return kind == 0 ? RB(FqParams, 0) : kind == 1 ? RB(FqParams, 1) : kind == 2 ? RB(FqParams, 2) : RB(FqParams, 3);
-#undef RB
-  return Status{VDF_ERR_BAD_ARG, "unknown field"};
+  return with_field(field, [&](auto f) {
+    return with_int<0, 1, 2, 3>(kind, BAD_KIND, [&](auto k) {
+      return reduce_batch_launch<tag_t<decltype(f)>, k.value>(block, count, n, scratch, out, s);
+    });
+  });
 }
 
 template <class P>
@@ -604,9 +605,10 @@ Status snark_fold_halves_batch(int field, const void* block, int k, size_t n, hi
   if (n < 2 || (n & (n - 1))) return Status{VDF_ERR_BAD_LENGTH, "length must be a power of two >= 2"};
   const size_t h = n / 2;
   KTimer kt(s, "k_fold_halves_batch", 96.0 * h * k);
-  SNARK_DISPATCH(field, k_fold_halves_batch, dim3((unsigned)((h + 255) / 256), (unsigned)k), dim3(256), 0, s,
-                 reinterpret_cast<const FoldItemDev*>(block), h);
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_fold_halves_batch<tag_t<decltype(f)>>), dim3((unsigned)((h + 255) / 256), (unsigned)k), dim3(256), 0, s,
+                       reinterpret_cast<const FoldItemDev*>(block), h);
+  });
 }
 
 // M-vectors of up to SPMVT_BATCH instances in one pass over the column structure: a column's pointers, rows and coefficient
@@ -718,12 +720,11 @@ static Status spmvt_batch_launch(const uint32_t* colptr, const uint32_t* rows, c
     size_t shared = nbig < nheavy ? nbig : nheavy;
     const size_t room = snark_reduce_scratch_bytes() / ((size_t)SPMVT_PARTS * CB * 32);
     if (shared > room) shared = room;
-    char* part = reinterpret_cast<char*>(scratch);
+    char* part = bytes_of(scratch);
     if (shared) {
       hipLaunchKernelGGL((k_spmvt_heavy_batch<P, CB>), dim3((unsigned)(shared * SPMVT_PARTS)), dim3(256), 0, s, heavy, colptr, rows,
                          cm, dict, items, cnt, SPMVT_PARTS, part);
-      hipLaunchKernelGGL((k_spmvt_heavy_sum_batch<P, CB>), dim3((unsigned)shared, (unsigned)cnt), dim3(64), 0, s, heavy,
-                         reinterpret_cast<const char*>(part), items);
+      hipLaunchKernelGGL((k_spmvt_heavy_sum_batch<P, CB>), dim3((unsigned)shared, (unsigned)cnt), dim3(64), 0, s, heavy, cbytes_of(part), items);
     }
     if (nheavy > shared)
       hipLaunchKernelGGL((k_spmvt_heavy_batch<P, CB>), dim3((unsigned)(nheavy - shared)), dim3(256), 0, s, heavy + shared, colptr,
@@ -739,19 +740,18 @@ Status snark_spmvt_batch(int field, const uint32_t* colptr, const uint32_t* rows
                          size_t nheavy, size_t nbig, const void* dict, const void* block, int count, size_t ncols, void* scratch,
                          hipStream_t s) {
   if (ncols == 0 || count <= 0) return Status{};
-  if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
   const SpmvtItemDev* items = reinterpret_cast<const SpmvtItemDev*>(block);
-  const char* d = reinterpret_cast<const char*>(dict);
-  for (int q0 = 0; q0 < count; q0 += SPMVT_BATCH) {
-    const int cnt = count - q0 < SPMVT_BATCH ? count - q0 : SPMVT_BATCH;
-    const SpmvtItemDev* it = items + q0;
-#define SB(P, CB) spmvt_batch_launch<P, CB>(colptr, rows, cm, heavy, nheavy, nbig, d, it, cnt, ncols, scratch, s)
-    Status st = field == VDF_FIELD_FP ? (cnt == 1 ? SB(FpParams, 1) : cnt == 2 ? SB(FpParams, 2) : SB(FpParams, SPMVT_BATCH))
-                                      : (cnt == 1 ? SB(FqParams, 1) : cnt == 2 ? SB(FqParams, 2) : SB(FqParams, SPMVT_BATCH));
-#undef SB
-    if (st.code != VDF_OK) return st;
-  }
-  return Status{};
+  return with_field(field, [&](auto f) {
+    for (int q0 = 0; q0 < count; q0 += SPMVT_BATCH) {
+      const int cnt = count - q0 < SPMVT_BATCH ? count - q0 : SPMVT_BATCH;
+      // the kernel's width: 1, 2, or SPMVT_BATCH accumulators per lane (3 instances run in the widest)
+      VDF_TRY((with_int<1, 2, SPMVT_BATCH>(cnt <= 2 ? cnt : SPMVT_BATCH, "batch width", [&](auto cb) {
+        return spmvt_batch_launch<tag_t<decltype(f)>, cb.value>(colptr, rows, cm, heavy, nheavy, nbig, cbytes_of(dict), items + q0, cnt, ncols,
+                                                               scratch, s);
+      })));
+    }
+    return Status{};
+  });
 }
 
 }  // namespace vdf

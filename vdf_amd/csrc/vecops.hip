@@ -13,7 +13,6 @@
 
 namespace vdf {
 
-static inline dim3 grid_for(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 template <class P>
 __global__ __launch_bounds__(256) void k_axpy(const char* __restrict__ a, const char* __restrict__ r,
@@ -679,37 +678,29 @@ __global__ __launch_bounds__(256) void k_clock_probe(int iters, unsigned long lo
   if (y.v[0] == 0x12345678u && y.v[5] == 0x9abcdef0u) out[2] = y.v[1];          // keeps the chain alive
 }
 
-#define FIELD_DISPATCH(field, KERNEL, ...)                                                       \
-  do {                                                                                           \
-    if ((field) == VDF_FIELD_FP) hipLaunchKernelGGL((KERNEL<FpParams>), __VA_ARGS__);            \
-    else if ((field) == VDF_FIELD_FQ) hipLaunchKernelGGL((KERNEL<FqParams>), __VA_ARGS__);       \
-    else return Status{VDF_ERR_BAD_ARG, "unknown field"};                                        \
-    VDF_TRY_HIP(hipGetLastError());                                                              \
-  } while (0)
-
-#define C(p) reinterpret_cast<const char*>(p)
-#define M(p) reinterpret_cast<char*>(p)
-
 Status vec_axpy(int field, const void* a, const void* r, const void* b, size_t n, void* out, hipStream_t s) {
   if (n == 0) return Status{};
   KTimer kt(s, "k_axpy", 96.0 * n);
-  FIELD_DISPATCH(field, k_axpy, grid_for(n), dim3(256), 0, s, C(a), C(r), C(b), n, M(out));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_axpy<tag_t<decltype(f)>>), grid_for(n), dim3(256), 0, s, cbytes_of(a), cbytes_of(r), cbytes_of(b), n, bytes_of(out));
+  });
 }
 
 Status vec_cross_term(int field, const void* az1, const void* bz1, const void* cz1, const void* az2, const void* bz2,
                       const void* cz2, const void* u1, size_t n, void* T, hipStream_t s) {
   if (n == 0) return Status{};
   KTimer kt(s, "k_cross_term", 224.0 * n);
-  FIELD_DISPATCH(field, k_cross_term, grid_for(n), dim3(256), 0, s, C(az1), C(bz1), C(cz1), C(az2), C(bz2), C(cz2),
-                 C(u1), n, M(T));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_cross_term<tag_t<decltype(f)>>), grid_for(n), dim3(256), 0, s, cbytes_of(az1), cbytes_of(bz1), cbytes_of(cz1), cbytes_of(az2),
+                       cbytes_of(bz2), cbytes_of(cz2), cbytes_of(u1), n, bytes_of(T));
+  });
 }
 
 Status vec_minroot_witness(int field, const void* trace_xy, const void* i0, uint64_t t, void* W, hipStream_t s) {
   KTimer kt(s, "k_minroot_witness", 192.0 * t);
-  FIELD_DISPATCH(field, k_minroot_witness, grid_for(t + 1), dim3(256), 0, s, C(trace_xy), C(i0), t, M(W));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_minroot_witness<tag_t<decltype(f)>>), grid_for(t + 1), dim3(256), 0, s, cbytes_of(trace_xy), cbytes_of(i0), t, bytes_of(W));
+  });
 }
 
 Status vec_spmv_long(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3], const uint32_t* const coef[3],
@@ -718,16 +709,18 @@ Status vec_spmv_long(int field, const uint32_t* const rowptr[3], const uint32_t*
   Csr3 m;
   for (int k = 0; k < 3; ++k) { m.rowptr[k] = rowptr[k]; m.col[k] = col[k]; m.coef[k] = coef[k]; }
   KTimer kt(s, "k_spmv_long", 0.0);                    // priced with the cross term that reads its results
-  FIELD_DISPATCH(field, k_spmv_long, dim3((unsigned)((n_long + 3) / 4)), dim3(256), 0, s, m, C(dict), C(z), long_rows, n_long,
-                 M(out[0]), M(out[1]), M(out[2]));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_spmv_long<tag_t<decltype(f)>>), dim3((unsigned)((n_long + 3) / 4)), dim3(256), 0, s, m, cbytes_of(dict), cbytes_of(z), long_rows,
+                       n_long, bytes_of(out[0]), bytes_of(out[1]), bytes_of(out[2]));
+  });
 }
 
 Status vec_spmv(int field, const uint32_t* rowptr, const uint32_t* col, const uint32_t* coef, const void* dict,
                 const void* z, size_t rows, void* out, hipStream_t s) {
   if (rows == 0) return Status{};
-  FIELD_DISPATCH(field, k_spmv, grid_for(rows), dim3(256), 0, s, rowptr, col, coef, C(dict), C(z), rows, M(out));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_spmv<tag_t<decltype(f)>>), grid_for(rows), dim3(256), 0, s, rowptr, col, coef, cbytes_of(dict), cbytes_of(z), rows, bytes_of(out));
+  });
 }
 
 static FeVal to_val(const vdf_fe* p) { FeVal v; std::memcpy(v.v, p, 32); return v; }
@@ -739,16 +732,18 @@ Status vec_step_z(int field, const void* trace_xy, uint64_t t, const vdf_fe z_in
   k.i0 = to_val(i0);
   k.u = to_val(u);
   for (int i = 0; i < 6; ++i) k.X[i] = to_val(&X[i]);
-  FIELD_DISPATCH(field, k_step_z, grid_for(t + 1), dim3(256), 0, s, C(trace_xy), k, t, M(z), M(packed));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_step_z<tag_t<decltype(f)>>), grid_for(t + 1), dim3(256), 0, s, cbytes_of(trace_xy), k, t, bytes_of(z), bytes_of(packed));
+  });
 }
 
 Status vec_step_segment(int field, const void* trace_xy, uint64_t t, const vdf_fe* i0, int per, void* out, void* packed,
                         const vdf_fe* i_in, hipStream_t s) {
   KTimer kt(s, "k_step_segment", (64.0 + 32.0 * per) * t);    // trace (x, y) read + `per` variables written per round
-  FIELD_DISPATCH(field, k_step_segment, grid_for(t + 1), dim3(256), 0, s, C(trace_xy), to_val(i0), t, per, M(out), M(packed),
-                 to_val(i_in ? i_in : i0));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_step_segment<tag_t<decltype(f)>>), grid_for(t + 1), dim3(256), 0, s, cbytes_of(trace_xy), to_val(i0), t, per, bytes_of(out),
+                       bytes_of(packed), to_val(i_in ? i_in : i0));
+  });
 }
 
 // lanes per row: 8 for the ~10^4 rows a step waits for (latency), 4 for long runs of short rows (the MinRoot rounds: all
@@ -774,52 +769,44 @@ Status vec_nifs_cross(int field, const uint32_t* const rowptr[3], const uint32_t
     KTimer kt(s, "k_nifs_cross_f", alg_bytes);
     const uint32_t long_wgs = (uint32_t)((n_long_rows + 3) / 4);
     const dim3 grid((unsigned)((rows + 31) / 32) + long_wgs);
-    FIELD_DISPATCH(field, k_nifs_cross_f, grid, dim3(256), 0, s, m, C(dict), C(z2), C(az1), C(bz1), C(cz1), to_val(u1), rows,
-                   skip_begin, skip_len, long_rowlist, n_long_rows, long_wgs, M(az2), M(bz2), M(cz2), M(T));
-    return Status{};
+    return with_field(field, [&](auto f) {
+      hipLaunchKernelGGL((k_nifs_cross_f<tag_t<decltype(f)>>), grid, dim3(256), 0, s, m, cbytes_of(dict), cbytes_of(z2), cbytes_of(az1), cbytes_of(bz1),
+                         cbytes_of(cz1), to_val(u1), rows, skip_begin, skip_len, long_rowlist, n_long_rows, long_wgs, bytes_of(az2), bytes_of(bz2),
+                         bytes_of(cz2), bytes_of(T));
+    });
   }
   KTimer kt(s, lpr == 1 ? "k_nifs_cross" : (lpr == 4 ? "k_nifs_cross_w4" : "k_nifs_cross_w8"), alg_bytes);
-  if (lpr == 1) {
-    FIELD_DISPATCH(field, k_nifs_cross, grid_for(rows), dim3(256), 0, s, m, C(dict), C(z2), C(az1), C(bz1), C(cz1),
-                   to_val(u1), rows, skip_begin, skip_len, M(az2), M(bz2), M(cz2), M(T));
-  } else if (lpr == 4) {
-    const dim3 grid((unsigned)((rows + 63) / 64));
-    if (field == VDF_FIELD_FP) hipLaunchKernelGGL((k_nifs_cross_w<FpParams, 4>), grid, dim3(256), 0, s, m, C(dict), C(z2), C(az1), C(bz1), C(cz1),
-                                                  to_val(u1), rows, skip_begin, skip_len, M(az2), M(bz2), M(cz2), M(T));
-    else if (field == VDF_FIELD_FQ) hipLaunchKernelGGL((k_nifs_cross_w<FqParams, 4>), grid, dim3(256), 0, s, m, C(dict), C(z2), C(az1), C(bz1), C(cz1),
-                                                       to_val(u1), rows, skip_begin, skip_len, M(az2), M(bz2), M(cz2), M(T));
-    else return Status{VDF_ERR_BAD_ARG, "unknown field"};
-    VDF_TRY_HIP(hipGetLastError());
-  } else {
-    const dim3 grid((unsigned)((rows + 31) / 32));
-    if (field == VDF_FIELD_FP) hipLaunchKernelGGL((k_nifs_cross_w<FpParams, 8>), grid, dim3(256), 0, s, m, C(dict), C(z2), C(az1), C(bz1), C(cz1),
-                                                  to_val(u1), rows, skip_begin, skip_len, M(az2), M(bz2), M(cz2), M(T));
-    else if (field == VDF_FIELD_FQ) hipLaunchKernelGGL((k_nifs_cross_w<FqParams, 8>), grid, dim3(256), 0, s, m, C(dict), C(z2), C(az1), C(bz1), C(cz1),
-                                                       to_val(u1), rows, skip_begin, skip_len, M(az2), M(bz2), M(cz2), M(T));
-    else return Status{VDF_ERR_BAD_ARG, "unknown field"};
-    VDF_TRY_HIP(hipGetLastError());
-  }
-  return Status{};
+  if (lpr == 1)
+    return with_field(field, [&](auto f) {
+      hipLaunchKernelGGL((k_nifs_cross<tag_t<decltype(f)>>), grid_for(rows), dim3(256), 0, s, m, cbytes_of(dict), cbytes_of(z2), cbytes_of(az1),
+                         cbytes_of(bz1), cbytes_of(cz1), to_val(u1), rows, skip_begin, skip_len, bytes_of(az2), bytes_of(bz2), bytes_of(cz2), bytes_of(T));
+    });
+  const dim3 grid((unsigned)((rows + 256 / lpr - 1) / (256 / lpr)));       // 64 rows of 4 lanes or 32 rows of 8 per workgroup
+  return with_int<4, 8>(lpr, "lanes per row", [&](auto lanes) {
+    return with_field(field, [&](auto f) {
+      hipLaunchKernelGGL((k_nifs_cross_w<tag_t<decltype(f)>, lanes.value>), grid, dim3(256), 0, s, m, cbytes_of(dict), cbytes_of(z2), cbytes_of(az1),
+                         cbytes_of(bz1), cbytes_of(cz1), to_val(u1), rows, skip_begin, skip_len, bytes_of(az2), bytes_of(bz2), bytes_of(cz2), bytes_of(T));
+    });
+  });
 }
 
+static constexpr const char* BAD_PER = "variables per round must be 3 or 4";
 Status vec_nifs_cross_minroot(int field, int per, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
                               const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, void* az2, void* bz2, void* cz2,
                               void* T, hipStream_t s) {
-  if (per != 3 && per != 4) return Status{VDF_ERR_BAD_ARG, "variables per round must be 3 or 4"};
+  if (per != 3 && per != 4) return Status{VDF_ERR_BAD_ARG, BAD_PER};
   if (t == 0 || seg_begin < 3) return Status{VDF_ERR_BAD_ARG, "bad segment"};
   const size_t rows = 3 * (size_t)t + 1;
   // algorithmic bytes: 3 running + 3 fresh + T elements per row, and the round's variables once (SURVEY 8d counts 224 B per
   // row for the cross term alone and the sparse products apart; here the products are the witness copies themselves)
   KTimer kt(s, "k_nifs_cross_minroot", (double)rows * 7 * 32 + (double)per * t * 32);
   const dim3 grid = grid_for(rows);
-#define LAUNCH_MR(PP, PERV) hipLaunchKernelGGL((k_nifs_cross_minroot<PP, PERV>), grid, dim3(256), 0, s, C(z2), seg_begin, one_col, t, row0, \
-                                               C(az1), C(bz1), C(cz1), to_val(u1), M(az2), M(bz2), M(cz2), M(T))
-  if (field == VDF_FIELD_FP) { if (per == 4) LAUNCH_MR(FpParams, 4); else LAUNCH_MR(FpParams, 3); }
-  else if (field == VDF_FIELD_FQ) { if (per == 4) LAUNCH_MR(FqParams, 4); else LAUNCH_MR(FqParams, 3); }
-  else return Status{VDF_ERR_BAD_ARG, "unknown field"};
-#undef LAUNCH_MR
-  VDF_TRY_HIP(hipGetLastError());
-  return Status{};
+  return with_field(field, [&](auto f) {
+    return with_int<4, 3>(per, BAD_PER, [&](auto perv) {
+      hipLaunchKernelGGL((k_nifs_cross_minroot<tag_t<decltype(f)>, perv.value>), grid, dim3(256), 0, s, cbytes_of(z2), seg_begin, one_col, t, row0,
+                         cbytes_of(az1), cbytes_of(bz1), cbytes_of(cz1), to_val(u1), bytes_of(az2), bytes_of(bz2), bytes_of(cz2), bytes_of(T));
+    });
+  });
 }
 
 // r: Montgomery form (host); sent as a plain integer when it is below 2^128 and tuning().fold_u128 allows (as vec_fold_many does)
@@ -830,26 +817,26 @@ template <class P> static bool plain_if_u128(const vdf_fe* r, FeVal& out) {
 Status vec_nifs_cross_minroot_fold(int field, int per, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
                                    const vdf_fe* r, void* az1, void* bz1, void* cz1, void* e1, const void* tprev, const vdf_fe* u1,
                                    void* az2, void* bz2, void* cz2, void* T, hipStream_t s) {
-  if (per != 3 && per != 4) return Status{VDF_ERR_BAD_ARG, "variables per round must be 3 or 4"};
+  if (per != 3 && per != 4) return Status{VDF_ERR_BAD_ARG, BAD_PER};
   if (t == 0 || seg_begin < 3) return Status{VDF_ERR_BAD_ARG, "bad segment"};
-  if (field != VDF_FIELD_FP && field != VDF_FIELD_FQ) return Status{VDF_ERR_BAD_ARG, "unknown field"};
   const size_t rows = 3 * (size_t)t + 1;
   // algorithmic bytes: the row of 3 running vectors read and written, 3 previous fresh read, 3 fresh + T written (E and the
   // previous T: read, read, written), and the round's variables once
   KTimer kt(s, "k_nifs_cross_minroot_fold", (double)rows * (13 + (e1 ? 3 : 0)) * 32 + (double)per * t * 32);
   const dim3 grid = grid_for(rows);
-  FeVal plain{};
-  const bool small = tuning().fold_u128 && (field == VDF_FIELD_FP ? plain_if_u128<FpParams>(r, plain) : plain_if_u128<FqParams>(r, plain));
-  const FeVal rv = small ? plain : to_val(r);
-#define LAUNCH_MRF(PP, PERV, U) hipLaunchKernelGGL((k_nifs_cross_minroot_fold<PP, PERV, U>), grid, dim3(256), 0, s, C(z2), seg_begin, one_col, t, row0, rv, \
-                                                  M(az1), M(bz1), M(cz1), M(e1), C(tprev), to_val(u1), M(az2), M(bz2), M(cz2), M(T))
-#define LAUNCH_MRF2(PP, PERV) do { if (small) LAUNCH_MRF(PP, PERV, true); else LAUNCH_MRF(PP, PERV, false); } while (0)
-  if (field == VDF_FIELD_FP) { if (per == 4) LAUNCH_MRF2(FpParams, 4); else LAUNCH_MRF2(FpParams, 3); }
-  else { if (per == 4) LAUNCH_MRF2(FqParams, 4); else LAUNCH_MRF2(FqParams, 3); }
-#undef LAUNCH_MRF2
-#undef LAUNCH_MRF
-  VDF_TRY_HIP(hipGetLastError());
-  return Status{};
+  return with_field(field, [&](auto f) {
+    using P = tag_t<decltype(f)>;
+    FeVal plain{};
+    const bool small = tuning().fold_u128 && plain_if_u128<P>(r, plain);
+    const FeVal rv = small ? plain : to_val(r);
+    return with_int<4, 3>(per, BAD_PER, [&](auto perv) {
+      return with_bool(small, [&](auto u128) {
+        hipLaunchKernelGGL((k_nifs_cross_minroot_fold<P, perv.value, u128.value>), grid, dim3(256), 0, s, cbytes_of(z2), seg_begin, one_col, t, row0, rv,
+                           bytes_of(az1), bytes_of(bz1), bytes_of(cz1), bytes_of(e1), cbytes_of(tprev), to_val(u1), bytes_of(az2), bytes_of(bz2),
+                           bytes_of(cz2), bytes_of(T));
+      });
+    });
+  });
 }
 
 Status vec_fold_many(int field, const vdf_fe* r, int k, void* const acc[], const void* const add[], const size_t n[],
@@ -860,7 +847,7 @@ Status vec_fold_many(int field, const vdf_fe* r, int k, void* const acc[], const
   a.k = k;
   uint64_t blocks = 0;
   for (int i = 0; i < k; ++i) {
-    a.acc[i] = M(acc[i]); a.add[i] = C(add[i]); a.n[i] = n[i];
+    a.acc[i] = bytes_of(acc[i]); a.add[i] = cbytes_of(add[i]); a.n[i] = n[i];
     blocks += (n[i] + 255) / 256;
     if (blocks >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "fold too large"};
     a.blk_end[i] = (uint32_t)blocks;
@@ -870,20 +857,16 @@ Status vec_fold_many(int field, const vdf_fe* r, int k, void* const acc[], const
   for (int i = 0; i < k; ++i) elems += (double)n[i];
   KTimer kt(s, "k_fold_many", 96.0 * elems);
   // a challenge below 2^128 (every NIFS fold): its plain value travels instead, and the product needs no Montgomery reduction
-  if (tuning().fold_u128) {
-    FeVal plain{};
-    bool small = false;
-    if (field == VDF_FIELD_FP) { Fe<FpParams> t; memcpy(t.v, r, 32); t = fe_from_mont(t); memcpy(plain.v, t.v, 32); }
-    else if (field == VDF_FIELD_FQ) { Fe<FqParams> t; memcpy(t.v, r, 32); t = fe_from_mont(t); memcpy(plain.v, t.v, 32); }
-    else return Status{VDF_ERR_BAD_ARG, "unknown field"};
-    small = (plain.v[4] | plain.v[5] | plain.v[6] | plain.v[7]) == 0;
-    if (small) {
-      FIELD_DISPATCH(field, k_fold_many_u128, dim3((unsigned)blocks), dim3(256), 0, s, a, plain);
-      return Status{};
-    }
-  }
-  FIELD_DISPATCH(field, k_fold_many, dim3((unsigned)blocks), dim3(256), 0, s, a, to_val(r));
-  return Status{};
+  FeVal plain{};
+  bool small = false;
+  if (tuning().fold_u128) VDF_TRY(with_field(field, [&](auto f) { small = plain_if_u128<tag_t<decltype(f)>>(r, plain); return Status{}; }));
+  if (small)
+    return with_field(field, [&](auto f) {
+      hipLaunchKernelGGL((k_fold_many_u128<tag_t<decltype(f)>>), dim3((unsigned)blocks), dim3(256), 0, s, a, plain);
+    });
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_fold_many<tag_t<decltype(f)>>), dim3((unsigned)blocks), dim3(256), 0, s, a, to_val(r));
+  });
 }
 
 // ---- random linear combinations of many instances (vdf_nova_verify_batch) -------------------------------------------
@@ -1020,13 +1003,14 @@ Status vec_lincomb_u128(int field, int count, const void* const v[], const size_
   a.count = count;
   double elems = (double)n_out;
   for (int j = 0; j < count; ++j) {
-    a.v[j] = C(v[j]); a.n[j] = n[j];
+    a.v[j] = cbytes_of(v[j]); a.n[j] = n[j];
     memcpy(a.w[j], w[j].l, 16);
     elems += (double)n[j];
   }
   KTimer kt(s, "k_lincomb_u128", 32.0 * elems);
-  FIELD_DISPATCH(field, k_lincomb_u128, grid_for(n_out), dim3(256), 0, s, a, n_out, M(out));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_lincomb_u128<tag_t<decltype(f)>>), grid_for(n_out), dim3(256), 0, s, a, n_out, bytes_of(out));
+  });
 }
 
 Status vec_relaxed_residual_batch(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3], const uint32_t* const coef[3],
@@ -1037,15 +1021,16 @@ Status vec_relaxed_residual_batch(int field, const uint32_t* const rowptr[3], co
   for (int k = 0; k < 3; ++k) { m.rowptr[k] = rowptr[k]; m.col[k] = col[k]; m.coef[k] = coef[k]; }
   const uint32_t long_wgs = long_rowlist ? (uint32_t)((n_long_rows + 3) / 4) : 0u;
   KTimer kt(s, "k_relaxed_residual_batch", alg_bytes);
-  FIELD_DISPATCH(field, k_relaxed_residual_batch, dim3((unsigned)((rows + 255) / 256) + long_wgs), dim3(256), 0, s, m, C(dict),
-                 reinterpret_cast<const ResidualItem*>(block), count, rows, long_rowlist, n_long_rows, long_wgs, M(out));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_relaxed_residual_batch<tag_t<decltype(f)>>), dim3((unsigned)((rows + 255) / 256) + long_wgs), dim3(256), 0, s, m, cbytes_of(dict),
+                       reinterpret_cast<const ResidualItem*>(block), count, rows, long_rowlist, n_long_rows, long_wgs, bytes_of(out));
+  });
 }
 void residual_pack(int count, const void* const z[], const void* const E[], const vdf_fe u[], const vdf_fe rho[], void* block) {
   ResidualItem* it = reinterpret_cast<ResidualItem*>(block);
   for (int q = 0; q < count; ++q) {
-    it[q].z = C(z[q]);
-    it[q].E = E ? C(E[q]) : nullptr;
+    it[q].z = cbytes_of(z[q]);
+    it[q].E = E ? cbytes_of(E[q]) : nullptr;
     memcpy(it[q].u, u[q].l, 32);
     memcpy(it[q].rho, rho[q].l, 16);
   }
@@ -1072,32 +1057,30 @@ Status vec_any_nonzero(const void* v, size_t n, uint32_t* d_flag, hipStream_t s)
 
 Status vec_mul(int field, const void* a, const void* b, size_t n, void* out, hipStream_t s) {
   if (n == 0) return Status{};
-  FIELD_DISPATCH(field, k_mul, grid_for(n), dim3(256), 0, s, C(a), C(b), n, M(out));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_mul<tag_t<decltype(f)>>), grid_for(n), dim3(256), 0, s, cbytes_of(a), cbytes_of(b), n, bytes_of(out));
+  });
 }
 
 Status vec_to_mont(int field, const void* a, size_t n, void* out, hipStream_t s) {
   if (n == 0) return Status{};
-  if (field == VDF_FIELD_FP) hipLaunchKernelGGL((k_mont<FpParams, 1>), grid_for(n), dim3(256), 0, s, C(a), n, M(out));
-  else if (field == VDF_FIELD_FQ) hipLaunchKernelGGL((k_mont<FqParams, 1>), grid_for(n), dim3(256), 0, s, C(a), n, M(out));
-  else return Status{VDF_ERR_BAD_ARG, "unknown field"};
-  VDF_TRY_HIP(hipGetLastError());
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_mont<tag_t<decltype(f)>, 1>), grid_for(n), dim3(256), 0, s, cbytes_of(a), n, bytes_of(out));
+  });
 }
 
 Status vec_from_mont(int field, const void* a, size_t n, void* out, hipStream_t s) {
   if (n == 0) return Status{};
-  if (field == VDF_FIELD_FP) hipLaunchKernelGGL((k_mont<FpParams, 0>), grid_for(n), dim3(256), 0, s, C(a), n, M(out));
-  else if (field == VDF_FIELD_FQ) hipLaunchKernelGGL((k_mont<FqParams, 0>), grid_for(n), dim3(256), 0, s, C(a), n, M(out));
-  else return Status{VDF_ERR_BAD_ARG, "unknown field"};
-  VDF_TRY_HIP(hipGetLastError());
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_mont<tag_t<decltype(f)>, 0>), grid_for(n), dim3(256), 0, s, cbytes_of(a), n, bytes_of(out));
+  });
 }
 
 Status vec_mul_chain(int field, const void* a, size_t n, int iters, void* out, hipStream_t s) {
   if (n == 0) return Status{};
-  FIELD_DISPATCH(field, k_mul_chain, grid_for(n), dim3(256), 0, s, C(a), n, iters, M(out));
-  return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_mul_chain<tag_t<decltype(f)>>), grid_for(n), dim3(256), 0, s, cbytes_of(a), n, iters, bytes_of(out));
+  });
 }
 
 Status vec_clock_probe(int iters, int workgroups, unsigned long long* d_out3, hipStream_t s) {
