@@ -40,6 +40,7 @@ extern "C" {
 typedef struct { uint64_t l[4]; } vdf_fe;            /* pasta_curves Fp / Fq, repr-c */
 typedef struct { vdf_fe x, y; } vdf_affine;          /* pallas::Affine / vesta::Affine */
 typedef struct { vdf_fe x, y, z; } vdf_jac;          /* pallas::Point / vesta::Point */
+typedef struct { vdf_fe x, y, i; } vdf_state;        /* src/minroot.rs:267-272: State<T> { x, y, i }, three Montgomery elements */
 
 typedef struct vdf_ctx vdf_ctx;
 typedef struct vdf_bases vdf_bases;
@@ -274,6 +275,32 @@ int  vdf_axpy(vdf_ctx* ctx, int field, const vdf_fe* a, const vdf_fe* r, const v
  * `input`); i0 = the `i` of trace_xy[0].  Round-parallel. */
 int  vdf_minroot_witness(vdf_ctx* ctx, int field, const vdf_fe* trace_xy, const vdf_fe* i0, uint64_t t,
                          vdf_fe* W_segment);
+
+/* ---- MinRoot inverse walks: a step's forward trace rebuilt from the state it ends in ------------------------
+ * The inverse round (src/minroot.rs:338-344) (x, y, i) -> (y - (i - 1), x^5 - (y - (i - 1)), i - 1) is three products where
+ * the forward round is ~285, and lands exactly on the state the forward round started from.  One lane per walk.
+ *
+ * n independent walks of `rounds` inverse rounds (at most 2^22 per call).  states: n states in DEVICE memory, read as where
+ * each walk stands and overwritten with where it stands afterwards (so a long walk may be cut into several calls).
+ * trace_xy (device, or NULL for no trace): walk w writes (x, y) of the state it stands on BEFORE round r to
+ *   trace_xy[2 * ((w / group) * group_stride + (w % group) * walk_stride + top - r)],   r = 0 .. rounds - 1
+ * (elements of 32 bytes; walk_stride, group_stride and top in states; group = 0: all walks are one group and group_stride is
+ * ignored), so a walk cut into calls passes top, top - rounds, ...; top >= rounds - 1.  The state a walk lands on is NOT
+ * written (it is the next call's first, or the caller's to compare and store).  With walk_stride = top = rounds the walks of
+ * one step's checkpoint intervals tile entries 1 .. t of that step's trace, each entry written once; group = walks per step
+ * and group_stride = t + 1 then lay the steps of a window out trace after trace, in one launch.  The caller sizes trace_xy.
+ * Exact: byte-identical to the host's rounds (vdf_nova.h vdf_minroot_inverse_round). */
+int  vdf_minroot_inverse_walk(vdf_ctx* ctx, int field, vdf_state* states, size_t n, uint64_t rounds, vdf_fe* trace_xy,
+                              size_t walk_stride, size_t top, size_t group, size_t group_stride);
+/* ok[w] = 1 iff `rounds` inverse rounds from results[w] land on originals[w] (x, y and i): the reference's check
+ * (src/minroot.rs:369-371), n at a time; rounds = 0 compares the states as they are.  results / originals / ok: host or device
+ * (device inputs are left as they were).  Walks longer than 2^22 rounds are cut into launches by the call. */
+int  vdf_minroot_check_batch(vdf_ctx* ctx, int field, const vdf_state* results, const vdf_state* originals, size_t n,
+                             uint64_t rounds, int* ok);
+/* trace_xy[2 * k * trace_stride] = (x, y) of states[k * state_stride], k < n (device memory; strides in states): entry 0 of
+ * the traces of a window of steps from their input states. */
+int  vdf_minroot_trace_heads(vdf_ctx* ctx, const vdf_state* states, size_t n, size_t state_stride, vdf_fe* trace_xy,
+                             size_t trace_stride);
 
 /* ---- fused step operations (one kernel launch each) --------------------------------------- */
 /* The three entry points below do what a sequence of the calls above does, in a single launch and with

@@ -44,8 +44,7 @@ extern "C" {
 enum { VDF_MODE_LTR_SEQUENTIAL = 0, VDF_MODE_LTR_ADDCHAIN_SEQUENTIAL = 1, VDF_MODE_RTL_SEQUENTIAL = 2,
        VDF_MODE_RTL_ADDCHAIN_SEQUENTIAL = 3 };
 
-/* src/minroot.rs:267-272: State<T> { x, y, i } as three Montgomery field elements */
-typedef struct { vdf_fe x, y, i; } vdf_state;
+/* State<T> { x, y, i } (src/minroot.rs:267-272) is vdf_state of vdf_hip.h: the device's inverse walks take it too */
 
 /* ---- MinRoot evaluator (trait MinRootVDF, src/minroot.rs:287-374); field = VDF_FIELD_FQ is
  * PallasVDF (:40-197), VDF_FIELD_FP is VestaVDF (:201-262, ignores the mode, :203-205) -------- */
@@ -56,6 +55,10 @@ int vdf_minroot_inverse_round(int field, const vdf_state* s, vdf_state* out);   
 /* eval / simple_eval (:348-359).  trace_xy (optional, 2*(t+1) elements) receives (x, y) of every
  * state 0..t -- the reference discards it (:352-359); the witness kernel consumes it. */
 int vdf_minroot_eval(int field, int mode, const vdf_state* s, uint64_t t, vdf_state* out, vdf_fe* trace_xy);
+/* simple_eval that keeps every `every`-th state instead of all or none: out_states[k] = the state after k * every rounds,
+ * k = 0 .. rounds_total / every (the first and the last included).  `every` must divide rounds_total (VDF_ERR_BAD_ARG; 0 too).
+ * The producer side of vdf_nova_circuits_from_checkpoints.  Pure, any thread. */
+int vdf_minroot_eval_checkpoints(int field, int mode, const vdf_state* s, uint64_t rounds_total, uint64_t every, vdf_state* out_states);
 int vdf_minroot_inverse_eval(int field, const vdf_state* s, uint64_t t, vdf_state* out);   /* :363-365 */
 int vdf_minroot_check(int field, const vdf_state* result, uint64_t t, const vdf_state* original); /* :369-371; 1 = ok */
 int vdf_minroot_element(int field, uint64_t n, vdf_fe* out);                           /* V::element, :60, :207 */
@@ -194,8 +197,39 @@ int  vdf_nova_shape_stencil(uint64_t t, int circuit_kind, uint64_t* early_begin,
 int  vdf_nova_eval_and_make_circuits(int mode, uint64_t num_iters_per_step, size_t num_steps,
                                      const vdf_state* initial_state, vdf_fe z0_primary[3], vdf_circuits** out);
 /* Moves every circuit's forward trace into HBM (outside the timed region: the trace is an input of
- * proving, produced by the untimed forward evaluation). */
+ * proving, produced by the untimed forward evaluation).  On checkpoint circuits: vdf_nova_circuits_materialize of all of
+ * them with wait = 1, so that eval -> upload -> prove works with either kind. */
 int  vdf_nova_circuits_upload(vdf_ctx* ctx, vdf_circuits* c);
+/* The circuits of a chain evaluated ELSEWHERE.  states: the chain's states every `every` rounds in forward order,
+ * num_steps * (t / every) + 1 of them, states[0] the initial state; `every` divides t (every = t: one state per step
+ * boundary, exactly what the reference's circuits hold, :57-66).  Host only; holds the states and NO trace (96 bytes per
+ * checkpoint instead of 64 (t + 1) per step).  Checked here: states[k].i == states[0].i + k * every (VDF_ERR_BAD_ARG,
+ * vdf_nova_last_error names k).  Returned reversed like eval_and_make_circuits (:294); z0_primary = the final state. */
+int  vdf_nova_circuits_from_checkpoints(uint64_t t, uint64_t every, size_t num_steps, const vdf_state* states,
+                                        vdf_fe z0_primary[3], vdf_circuits** out);
+/* Build the device-resident traces of circuits [first, first + count) (indices as prove_step's k) by inverse walks
+ * (vdf_hip.h vdf_minroot_inverse_walk), one per checkpoint interval, on a side queue of `ctx`'s device; entry 0 of a step's
+ * trace is its input state.  Steps that have a trace already are left alone (a second call is a no-op).  Every walk's landing
+ * state is compared ON THE DEVICE with the checkpoint before it; bad (optional, count ints) gets 1 for a step with a walk that
+ * missed, else 0.  Returns VDF_ERR_BAD_ARG (vdf_nova_last_error names the first such step) if any missed -- such a step is left
+ * without a trace -- and VDF_ERR_OOM, nothing built, if the traces do not fit.  The traces of one call are ONE device
+ * allocation, returned to the device when the last of them is released.
+ * wait = 0 enqueues the first slice of the walks and returns (bad is not written); each prove_step over these circuits then
+ * enqueues the share of the remaining rounds that finishes them by the step that needs them -- launches of a bounded number of
+ * rounds (1,024; environment VDF_NOVA_WALK_LAUNCH) so that a queue shared with a prover is never held for long -- and the next
+ * materialize / release / prove_step that needs the result enqueues what is left and waits for it; a walk that missed is
+ * reported by that call.  On circuits that carry host traces: VDF_ERR_BAD_ARG (they have vdf_nova_circuits_upload). */
+int  vdf_nova_circuits_materialize(vdf_ctx* ctx, vdf_circuits* c, size_t first, size_t count, int wait, int* bad);
+/* frees those traces (steps without one are skipped: releasing a range never materialised is a no-op); not while a
+ * prove_step over the circuits is running.  prove_step's guarantee -- nothing in flight reads the circuits' memory when it
+ * returns -- makes a release between two steps safe. */
+int  vdf_nova_circuits_release(vdf_circuits* c, size_t first, size_t count);
+/* how many circuits have a device trace now, and the device memory the traces hold: resident x (t + 1) x 64 bytes, plus the
+ * traces already released out of an allocation that others still use.  Pending walks are not waited for.  Outputs may be NULL. */
+int  vdf_nova_circuits_memory(const vdf_circuits* c, size_t* resident_steps, uint64_t* device_bytes);
+/* the device trace of circuit k, 2 (t + 1) elements, NULL when it has none (pending walks over it are finished first): for
+ * tests and tools */
+int  vdf_nova_circuit_trace(const vdf_circuits* c, size_t k, const void** d_trace);
 size_t vdf_nova_circuits_len(const vdf_circuits* c);
 /* result / input of circuit k (k = 0 is proved first): InverseMinRootCircuit.result / .input */
 int  vdf_nova_circuit_states(const vdf_circuits* c, size_t k, vdf_state* result, vdf_state* input);
@@ -205,11 +239,20 @@ void vdf_nova_circuits_free(vdf_circuits* c);
  * per circuit.  Returns VDF_ERR_* (the reference asserts success, :353). */
 int  vdf_nova_prove_recursively(vdf_pp* pp, const vdf_circuits* circuits, uint64_t num_iters_per_step,
                                 const vdf_fe z0[3], vdf_proof** out);
+/* The same with the window chosen.  Over checkpoint circuits whose traces are not all resident, prove_recursively builds them
+ * in windows of window_steps circuits: window 0 up front, then while window w is proved window w + 1 is walked on the side
+ * queue and window w - 1 released -- never more than two windows of traces in HBM, whatever the chain's length.
+ * window_steps = 0: as many steps as fit 1 GiB, at least 2 (255 at t = 2^16) -- what the plain call uses.  Circuits that carry
+ * traces, or whose traces the caller has made resident, are proved exactly as before and nothing of theirs is released. */
+int  vdf_nova_prove_recursively_windowed(vdf_pp* pp, const vdf_circuits* circuits, uint64_t num_iters_per_step,
+                                         const vdf_fe z0[3], size_t window_steps, vdf_proof** out);
 /* One RecursiveSNARK::prove_step (:342-349): *proof == NULL starts a new proof (the `None` case).  z0_secondary is
  * [0] (:310, :389-391).  What a step computes that does not depend on the chain -- the MinRoot rounds of circuit k and
  * their share of the commitment -- is enqueued one call early, for circuit k + 1 of the same `circuits`, on a second
  * context the proof owns; a call for any other step finds no such work waiting and does it then.  The results are
- * those of a prover without lookahead, and no call returns while anything in flight still reads the circuits' memory. */
+ * those of a prover without lookahead, and no call returns while anything in flight still reads the circuits' memory.
+ * Over checkpoint circuits the traces of circuit k AND of circuit k + 1 (when there is one) must be resident
+ * (vdf_nova_circuits_materialize): VDF_ERR_BAD_ARG "trace of circuit k not materialised" otherwise, nothing done. */
 int  vdf_nova_prove_step(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* circuits, size_t k, const vdf_fe z0[3]);
 /* NovaVDFProof::verify(pp, num_steps, z0, zi), :370-387: *ok = 1 iff the proof is valid for num_steps steps from z0
  * (two output hashes, three satisfiability claims), the verified zi_primary equals zi, and zi_secondary == [0]

@@ -84,6 +84,9 @@ PROTOTYPES = {
     "vdf_minroot_step_z_packed": (_i, [_vp, _i, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdf_minroot_step_segment": (_i, [_vp, _i, _vp, _u64, _vp, _i, _vp]),
     "vdf_minroot_step_segment_packed": (_i, [_vp, _i, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "vdf_minroot_inverse_walk": (_i, [_vp, _i, _vp, _sz, _u64, _vp, _sz, _sz, _sz, _sz]),
+    "vdf_minroot_check_batch": (_i, [_vp, _i, _vp, _vp, _sz, _u64, _vp]),
+    "vdf_minroot_trace_heads": (_i, [_vp, _vp, _sz, _sz, _vp, _sz]),
     "vdf_vec_is_zero": (_i, [_vp, _vp, _sz, C.POINTER(C.c_int)]),
     "vdf_nifs_cross_term": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdf_nifs_cross_term_rows": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

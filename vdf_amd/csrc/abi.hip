@@ -1984,6 +1984,60 @@ int vdf_fe_mul_chain(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, int ite
   });
 }
 
+// ---- MinRoot inverse walks (minroot.hip) --------------------------------------------------------
+int vdf_minroot_inverse_walk(vdf_ctx* ctx, int field, vdf_state* states, size_t n, uint64_t rounds, vdf_fe* trace_xy,
+                             size_t walk_stride, size_t top, size_t group, size_t group_stride) {
+  return guarded(ctx, [&]() -> Status {
+    VDF_TRY(vdf::check_field(field));
+    if (n == 0) return Status{};
+    if (!ptr_is_device(states)) return Status{VDF_ERR_BAD_ARG, "states must be in device memory"};
+    if (trace_xy && !ptr_is_device(trace_xy)) return Status{VDF_ERR_BAD_ARG, "trace_xy must be in device memory (or NULL)"};
+    VDF_TRY(vdf::minroot_inverse_walk(field, states, n, rounds, trace_xy, walk_stride, top, group, group_stride, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
+int vdf_minroot_check_batch(vdf_ctx* ctx, int field, const vdf_state* results, const vdf_state* originals, size_t n,
+                            uint64_t rounds, int* ok) {
+  return guarded(ctx, [&]() -> Status {
+    VDF_TRY(vdf::check_field(field));
+    if (n == 0) return Status{};
+    Staging st(ctx);
+    const void *dres, *dorig; void* dok;
+    const bool res_dev = ptr_is_device(results);
+    VDF_TRY(st.in(results, n * sizeof(vdf_state), &dres));
+    VDF_TRY(st.in(originals, n * sizeof(vdf_state), &dorig));
+    VDF_TRY(st.out(ok, n * sizeof(int), &dok));
+    if (rounds) {
+      void* walk = const_cast<void*>(dres);               // a staged copy is the call's own; a caller's device buffer is copied first
+      if (res_dev) {
+        VDF_TRY(st.temp(n * sizeof(vdf_state), &walk));
+        VDF_TRY_HIP(hipMemcpyAsync(walk, dres, n * sizeof(vdf_state), hipMemcpyDeviceToDevice, ctx->stream));
+      }
+      for (uint64_t done = 0; done < rounds;) {
+        const uint64_t now = std::min<uint64_t>(rounds - done, vdf::MINROOT_WALK_MAX_ROUNDS);
+        VDF_TRY(vdf::minroot_inverse_walk(field, walk, n, now, nullptr, 0, 0, 0, 0, ctx->stream));
+        done += now;
+      }
+      dres = walk;
+    }
+    VDF_TRY(vdf::minroot_states_match(dres, dorig, n, (int*)dok, ctx->stream));
+    return st.finish();
+  });
+}
+
+int vdf_minroot_trace_heads(vdf_ctx* ctx, const vdf_state* states, size_t n, size_t state_stride, vdf_fe* trace_xy,
+                            size_t trace_stride) {
+  return guarded(ctx, [&]() -> Status {
+    if (n == 0) return Status{};
+    if (!ptr_is_device(states) || !ptr_is_device(trace_xy)) return Status{VDF_ERR_BAD_ARG, "states and trace_xy must be in device memory"};
+    VDF_TRY(vdf::minroot_trace_heads(states, n, state_stride, trace_xy, trace_stride, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
 int vdf_ctx_clock_probe(vdf_ctx* ctx, int iters, double* shader_mhz, double* kernel_ms) {
   return guarded(ctx, [&]() -> Status {
     if (iters < 1 || iters > (1 << 22)) return Status{VDF_ERR_BAD_ARG, "iters out of range"};

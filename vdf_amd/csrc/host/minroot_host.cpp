@@ -163,6 +163,18 @@ int vdf_minroot_eval(int f, int mode, const vdf_state* s, uint64_t t, vdf_state*
   store_state(out, acc);
   return VDF_OK;
 }
+// simple_eval (:352-359) that keeps every `every`-th state: the producer side of vdf_nova_circuits_from_checkpoints
+int vdf_minroot_eval_checkpoints(int f, int mode, const vdf_state* s, uint64_t rounds_total, uint64_t every, vdf_state* out_states) {
+  if (!valid_field(f) || !valid_mode(mode) || !s || !out_states) return fail(VDF_ERR_BAD_ARG, "bad argument");
+  if (every == 0 || rounds_total % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide rounds_total");
+  St acc = load_state(s);
+  store_state(&out_states[0], acc);
+  for (uint64_t k = 0; k < rounds_total / every; ++k) {
+    eval_rounds(f, mode, &acc, every, nullptr);
+    store_state(&out_states[k + 1], acc);
+  }
+  return VDF_OK;
+}
 int vdf_minroot_inverse_eval(int f, const vdf_state* s, uint64_t t, vdf_state* out) {
   if (!valid_field(f) || !s || !out) return fail(VDF_ERR_BAD_ARG, "bad argument");
   St acc = load_state(s);

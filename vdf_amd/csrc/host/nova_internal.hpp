@@ -128,14 +128,54 @@ struct vdf_pp {
   unsigned digit_tables_skipped = 0;       // bit s: side s asked for a digit table and went without (no room, refused window)
 };
 
+// device memory of the traces one vdf_nova_circuits_materialize built: freed when the last circuit that points into it lets go
+struct TraceBlock {
+  vdf_ctx* ctx = nullptr;
+  void* d = nullptr;
+  uint64_t bytes = 0;
+  ~TraceBlock() { if (d) vdf_dev_free(ctx, d); }
+};
 struct Circuit {            // InverseMinRootCircuit<G1>, src/nova/proof.rs:57-66, + the forward trace
   uint64_t inverse_exponent = 5;
   vdfnova::St result, input;
   uint64_t t = 0;
   std::vector<Fe> trace_xy;  // (x, y) of states 0..t: trace[0] = input, trace[t] = result
-  void* d_trace = nullptr;   // the same trace in HBM (vdf_nova_circuits_upload)
+  void* d_trace = nullptr;   // the same trace in HBM (vdf_nova_circuits_upload, vdf_nova_circuits_materialize)
+  // a circuit made from checkpoints (vdf_nova_circuits_from_checkpoints) holds no host trace: the step's states every `every`
+  // rounds in forward order, cp[0] = input .. cp[t / every] = result; its d_trace lies inside `block`
+  uint64_t every = 0;
+  std::vector<vdfnova::St> cp;
+  std::shared_ptr<TraceBlock> block;
 };
-struct vdf_circuits { std::vector<Circuit> v; vdf_ctx* ctx = nullptr; };
+// Traces being rebuilt by inverse walks on the circuits' side queue (vdf_nova_circuits_materialize): one walk per checkpoint
+// interval of every step in `steps`, all in one launch per slice of rounds; `done` rounds of `every` are enqueued so far.
+struct WalkJob {
+  std::vector<size_t> steps;               // circuit indices, ascending
+  std::shared_ptr<TraceBlock> block;       // steps.size() traces of t + 1 entries
+  void* d_walk = nullptr;                  // where each walk stands
+  void* d_expect = nullptr;                // the checkpoint each walk must land on
+  int* h_ok = nullptr;                     // pinned: 1 per walk that landed on it
+  size_t walks = 0, per_step = 0;
+  uint64_t every = 0, done = 0;
+  bool matched = false;                    // the comparison has been enqueued
+};
+struct vdf_circuits {
+  std::vector<Circuit> v;
+  vdf_ctx* ctx = nullptr;
+  bool checkpoints = false;                // made by vdf_nova_circuits_from_checkpoints
+  // the walks run on a side queue of the device (made by the first materialize); a job enqueued with wait = 0 is finished by
+  // the next call that needs its result -- prove_step takes the circuits const, hence mutable
+  mutable vdf_ctx* side = nullptr;
+  mutable std::unique_ptr<WalkJob> job;
+  // the walks' buffers (where each stands, where it must land, the verdicts: pinned) are kept from one job to the next, and the
+  // windowed prove_recursively keeps the allocation of the window it releases for the window after next: a device free is a
+  // synchronisation of the whole device, and two per window showed in the prover's rate
+  mutable void* d_walk = nullptr;
+  mutable void* d_expect = nullptr;
+  mutable int* h_ok = nullptr;
+  mutable size_t scratch_walks = 0;
+  std::shared_ptr<TraceBlock> spare;
+};
 
 // NovaVDFProof::Recursive = nova-snark RecursiveSNARK: running instance + witness on both sides, the last secondary
 // instance unfolded, the step counter and both z_i.  Constant size in the number of steps.
@@ -199,6 +239,10 @@ int alloc_proof_buffers(vdf_proof* p);
 int finalize_l2(const vdf_proof* p);      // commits to the last secondary witness if that is still pending
 std::unique_ptr<StepCircuit> make_primary_circuit(const vdf_pp* pp, const Circuit* c, bool device_rounds);
 std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c);
+// checkpoint circuits (nova_host.cpp): finish the pending walks if they cover circuit k and say whether its trace is there;
+// enqueue the share of the pending walks that keeps them ahead of a prover about to prove circuit k
+int circuits_need(const vdf_circuits* c, size_t k);
+int circuits_pump(const vdf_circuits* c, size_t k);
 
 // ---- wire formats (wire_host.cpp; layout in include/vdf_nova.h) --------------------------------------------
 constexpr char WIRE_MAGIC_SNARK[9] = "VDFSNK03";      // compressed proof

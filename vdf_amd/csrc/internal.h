@@ -351,6 +351,15 @@ Status vec_from_mont(int field, const void* a, size_t n, void* out, hipStream_t 
 Status vec_mul_chain(int field, const void* a, size_t n, int iters, void* out, hipStream_t s);
 Status vec_clock_probe(int iters, int workgroups, unsigned long long* d_out3, hipStream_t s);   // d_out3 zeroed by the caller
 
+// ---- minroot.hip -----------------------------------------------------------------------
+// n walks of `rounds` inverse rounds in place over `states` (device, 96 B each); trace (device or null): walk w writes the
+// (x, y) it stands on before round r to entry (w / group) * group_stride + (w % group) * walk_stride + top - r (group == 0: one group)
+constexpr uint64_t MINROOT_WALK_MAX_ROUNDS = 1ull << 22;
+Status minroot_inverse_walk(int field, void* states, size_t n, uint64_t rounds, void* trace, size_t walk_stride, size_t top,
+                            size_t group, size_t group_stride, hipStream_t s);
+Status minroot_states_match(const void* a, const void* b, size_t n, int* ok, hipStream_t s);      // ok[w] = (a[w] == b[w]), 96 B each
+Status minroot_trace_heads(const void* states, size_t n, size_t state_stride, void* trace, size_t trace_stride, hipStream_t s);
+
 // ---- snark.hip -------------------------------------------------------------------------
 // vdf_fe* arguments are HOST pointers whose values travel as kernel arguments; void* are device vectors
 Status snark_pair_table(int field, const vdf_fe* lo, const vdf_fe* hi, int k, void* out, hipStream_t s);

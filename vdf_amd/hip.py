@@ -415,6 +415,19 @@ class Context:
         """The reference's allocation (4 variables per round) and the 3t + 4 scalars of its commitment without new_x."""
         self._check(lib.vdf_minroot_step_segment_packed(self.handle, field, _ptr(trace_xy), t, _ptr(i0), _ptr(i_in), _ptr(out), _ptr(packed)))
 
+    def minroot_inverse_walk(self, field, states, n, rounds, trace_xy=None, walk_stride=0, top=0, group=0, group_stride=0) -> None:
+        """n inverse walks of `rounds` rounds in place over `states` (device, 96 B each); trace_xy (device or None): walk w writes
+        the (x, y) it stands on before round r to entry (w // group) * group_stride + (w % group) * walk_stride + top - r."""
+        self._check(lib.vdf_minroot_inverse_walk(self.handle, field, _ptr(states), n, rounds, _ptr(trace_xy), walk_stride, top,
+                                                 group, group_stride))
+
+    def minroot_check_batch(self, field, results, originals, n, rounds, ok) -> None:
+        """ok[w] = 1 iff `rounds` inverse rounds from results[w] land on originals[w]; host or device buffers, ok int32."""
+        self._check(lib.vdf_minroot_check_batch(self.handle, field, _ptr(results), _ptr(originals), n, rounds, _ptr(ok)))
+
+    def minroot_trace_heads(self, states, n, state_stride, trace_xy, trace_stride) -> None:
+        self._check(lib.vdf_minroot_trace_heads(self.handle, _ptr(states), n, state_stride, _ptr(trace_xy), trace_stride))
+
     def gate_accumulate(self, other: "Context", slot: int) -> None:
         """The next bucket-method MSM on this context accumulates only after `other`'s mark `slot` (vdf_ctx_gate_accumulate)."""
         self._check(lib.vdf_ctx_gate_accumulate(self.handle, other.handle, slot))

@@ -45,6 +45,7 @@ for _name, _args in {
     "vdf_minroot_round": [_i, _i, C.POINTER(_State), C.POINTER(_State)],
     "vdf_minroot_inverse_round": [_i, C.POINTER(_State), C.POINTER(_State)],
     "vdf_minroot_eval": [_i, _i, C.POINTER(_State), _u64, C.POINTER(_State), _vp],
+    "vdf_minroot_eval_checkpoints": [_i, _i, C.POINTER(_State), _u64, _u64, _vp],
     "vdf_minroot_inverse_eval": [_i, C.POINTER(_State), _u64, C.POINTER(_State)],
     "vdf_minroot_check": [_i, C.POINTER(_State), _u64, C.POINTER(_State)],
     "vdf_minroot_element": [_i, _u64, C.POINTER(_Fe)],
@@ -156,6 +157,19 @@ class MinRootVDF:                 # trait MinRootVDF<G>, src/minroot.rs:287-374
 
     simple_eval = eval
 
+    def eval_checkpoints(self, x: State, t_total: int, every: int) -> List[State]:
+        """simple_eval that keeps the state after every `every` rounds, the first and the last included (what an evaluator
+        hands to a prover: InverseMinRootCircuit.from_checkpoints).  ValueError unless `every` divides t_total."""
+        if every <= 0 or t_total % every:
+            n = 1
+        else:
+            n = t_total // every + 1
+        out = (_State * n)()
+        rc = nova_lib.vdf_minroot_eval_checkpoints(self.FIELD, int(self.eval_mode), C.byref(x._c()), t_total, every, out)
+        if rc != 0:
+            raise ValueError("vdf_minroot_eval_checkpoints: %s" % nova_lib.vdf_nova_last_error().decode())
+        return [State._from_c(s) for s in out]
+
     @classmethod
     def inverse_eval(cls, x: State, t: int) -> State:   # :363-365
         out = _State()
@@ -165,6 +179,22 @@ class MinRootVDF:                 # trait MinRootVDF<G>, src/minroot.rs:287-374
     @classmethod
     def check(cls, result: State, t: int, original: State) -> bool:   # :369-371
         return bool(nova_lib.vdf_minroot_check(cls.FIELD, C.byref(result._c()), t, C.byref(original._c())))
+
+    @classmethod
+    def check_batch(cls, ctx, results, t: int, originals) -> List[bool]:
+        """The reference's check (:369-371) for many (result, original) pairs at once, on the GPU of `ctx`
+        (vdf_amd.hip.Context): one inverse walk per pair."""
+        import numpy as np
+        n = len(results)
+        if len(originals) != n:
+            raise ValueError("as many originals as results")
+        if n == 0:
+            return []
+        res = np.frombuffer(b"".join(s.x + s.y + s.i for s in results), dtype="<u8").copy()
+        org = np.frombuffer(b"".join(s.x + s.y + s.i for s in originals), dtype="<u8").copy()
+        ok = np.zeros(n, dtype=np.int32)
+        ctx.minroot_check_batch(cls.FIELD, res, org, n, t, ok)
+        return [bool(v) for v in ok]
 
 
 class PallasVDF(MinRootVDF):      # src/minroot.rs:38-197: modulus of Fq (scalar field of Pallas)

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import weakref
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -37,6 +37,12 @@ for _name, _res, _args in [
     ("vdf_nova_pp_stencil", _i, [_vp]),
     ("vdf_nova_shape_stencil", _i, [_u64, _i, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     ("vdf_nova_eval_and_make_circuits", _i, [_i, _u64, _sz, C.POINTER(_State), C.POINTER(_Fe * 3), C.POINTER(_vp)]),
+    ("vdf_nova_circuits_from_checkpoints", _i, [_u64, _u64, _sz, _vp, C.POINTER(_Fe * 3), C.POINTER(_vp)]),
+    ("vdf_nova_circuits_materialize", _i, [_vp, _vp, _sz, _sz, _i, _vp]),
+    ("vdf_nova_circuits_release", _i, [_vp, _sz, _sz]),
+    ("vdf_nova_circuits_memory", _i, [_vp, C.POINTER(_sz), C.POINTER(_u64)]),
+    ("vdf_nova_circuit_trace", _i, [_vp, _sz, C.POINTER(_vp)]),
+    ("vdf_nova_prove_recursively_windowed", _i, [_vp, _vp, _u64, C.POINTER(_Fe * 3), _sz, C.POINTER(_vp)]),
     ("vdf_nova_circuits_len", _sz, [_vp]),
     ("vdf_nova_circuits_upload", _i, [_vp, _vp]),
     ("vdf_nova_circuit_states", _i, [_vp, _sz, C.POINTER(_State), C.POINTER(_State)]),
@@ -453,6 +459,34 @@ class Circuits:
         self._ctx = ctx          # keep the context alive until the traces are freed ...
         ctx._children.add(self)  # ... and let it free them first if it is closed earlier
 
+    def materialize(self, ctx: Context, first: int = 0, count: Optional[int] = None, wait: bool = True) -> List[int]:
+        """Checkpoint circuits: build the device traces of circuits [first, first + count) by inverse walks on the GPU.  Returns
+        the flags per step (1 = a walk missed its checkpoint; all 0 with wait=False); raises VdfError when any missed."""
+        count = len(self) - first if count is None else count
+        bad = (C.c_int * max(count, 1))()
+        self._ctx = ctx
+        ctx._children.add(self)
+        rc = nova_lib.vdf_nova_circuits_materialize(ctx.handle, self.handle, first, count, 1 if wait else 0, bad)
+        self.last_bad = list(bad)[:count]
+        _check(rc)
+        return self.last_bad
+
+    def release(self, first: int = 0, count: Optional[int] = None) -> None:
+        count = len(self) - first if count is None else count
+        _check(nova_lib.vdf_nova_circuits_release(self.handle, first, count))
+
+    def memory(self) -> Tuple[int, int]:
+        """(circuits with a device trace, bytes of device memory their traces hold)"""
+        n, b = C.c_size_t(0), C.c_uint64(0)
+        _check(nova_lib.vdf_nova_circuits_memory(self.handle, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def trace_ptr(self, k: int) -> Optional[int]:
+        """device address of circuit k's trace (2 (t + 1) elements), None without one"""
+        p = C.c_void_p()
+        _check(nova_lib.vdf_nova_circuit_trace(self.handle, k, C.byref(p)))
+        return p.value
+
     def states(self, k: int) -> Tuple[State, State]:
         """(result, input) of circuit k: InverseMinRootCircuit.result / .input (:63-64)."""
         r, i = _State(), _State()
@@ -486,6 +520,20 @@ class InverseMinRootCircuit:      # src/nova/proof.rs:57-66, :239-299
                                                         C.byref(initial_state._c()), C.byref(z0), C.byref(h)))
         return [bytes(z0[k]) for k in range(3)], Circuits(h.value, num_iters_per_step)
 
+    @staticmethod
+    def from_checkpoints(t: int, every: int, num_steps: int, states: Sequence[State]) -> Tuple[List[bytes], Circuits]:
+        """The circuits of a chain evaluated elsewhere, from its states every `every` rounds in forward order
+        (num_steps * (t // every) + 1 of them, e.g. MinRootVDF.eval_checkpoints): no trace is held; Circuits.materialize, or
+        prove_recursively by itself, rebuilds the traces on the GPU window by window."""
+        if every > 0 and t % every == 0 and num_steps > 0 and len(states) != num_steps * (t // every) + 1:
+            raise ValueError("num_steps * (t // every) + 1 states expected")
+        raw = b"".join(s.x + s.y + s.i for s in states)
+        buf = (C.c_char * max(len(raw), 1)).from_buffer_copy(raw or b"\0")
+        z0 = (_Fe * 3)()
+        h = C.c_void_p()
+        _check(nova_lib.vdf_nova_circuits_from_checkpoints(t, every, num_steps, buf, C.byref(z0), C.byref(h)))
+        return [bytes(z0[k]) for k in range(3)], Circuits(h.value, t)
+
 
 class NovaVDFProof:               # enum NovaVDFProof { Recursive, Compressed }, :51-55
     def __init__(self, handle: int, pp: NovaVDFPublicParams):
@@ -495,9 +543,14 @@ class NovaVDFProof:               # enum NovaVDFProof { Recursive, Compressed },
 
     @staticmethod
     def prove_recursively(pp: NovaVDFPublicParams, circuits: Circuits, num_iters_per_step: int,
-                          z0: Sequence[bytes]) -> "NovaVDFProof":                       # :302-358
+                          z0: Sequence[bytes], window_steps: Optional[int] = None) -> "NovaVDFProof":   # :302-358
+        """window_steps: over checkpoint circuits, how many steps' traces one window of inverse walks rebuilds (None: 1 GiB's worth)."""
         h = C.c_void_p()
-        _check(nova_lib.vdf_nova_prove_recursively(pp.handle, circuits.handle, num_iters_per_step, C.byref(_z(z0)), C.byref(h)))
+        if window_steps is None:
+            _check(nova_lib.vdf_nova_prove_recursively(pp.handle, circuits.handle, num_iters_per_step, C.byref(_z(z0)), C.byref(h)))
+        else:
+            _check(nova_lib.vdf_nova_prove_recursively_windowed(pp.handle, circuits.handle, num_iters_per_step, C.byref(_z(z0)),
+                                                                window_steps, C.byref(h)))
         return NovaVDFProof(h.value, pp)
 
     @staticmethod
