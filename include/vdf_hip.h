@@ -340,6 +340,11 @@ int  vdf_minroot_step_segment(vdf_ctx* ctx, int field, const vdf_fe* trace_xy, u
  * -- the same group element from 3t + 4 instead of 4t + 1 terms (libvdf_nova.so commits the reference's circuit this way). */
 int  vdf_minroot_step_segment_packed(vdf_ctx* ctx, int field, const vdf_fe* trace_xy, uint64_t t, const vdf_fe* i0, const vdf_fe* i_in,
                                      vdf_fe* out, vdf_fe* packed);
+/* The variables of the FORWARD MinRoot step circuit (vdf_nova.h VDF_CIRCUIT_MINROOT_FORWARD), which proves a step in the
+ * direction it was evaluated: per round j the fifth root x_(j+1) = trace_xy[j + 1].x, its square and its fourth power, then
+ * final_i = i_end (the step's last round counter; host memory).  out has 3t + 1 elements; trace_xy as everywhere
+ * (trace_xy[k] = (x_k, y_k), k = 0..t, device memory). */
+int  vdf_minroot_forward_segment(vdf_ctx* ctx, int field, const vdf_fe* trace_xy, uint64_t t, const vdf_fe* i_end, vdf_fe* out);
 /* vdf_spmv3(shape, z2) followed by vdf_cross_term(Az1, Bz1, Cz1, Az2, Bz2, Cz2, u1): writes Az2, Bz2, Cz2
  * (num_cons each) and T.  u1: host memory.  (nova-snark NIFS::prove -> commit_T, K4 + K5.) */
 int  vdf_nifs_cross_term(vdf_ctx* ctx, const vdf_shape* shape, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,
@@ -367,6 +372,16 @@ int  vdf_nifs_cross_term_rows(vdf_ctx* ctx, const vdf_shape* shape, size_t row_b
 int  vdf_nifs_cross_term_minroot(vdf_ctx* ctx, int field, int vars_per_round, uint64_t t, size_t seg_begin, size_t one_col, size_t row_begin,
                                  const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2,
                                  vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T);
+/* The stencil of the FORWARD step circuit, rows [row_begin, row_begin + 3t + 1), with x' = x_(j+1), tmp1, tmp2 of round j at
+ * seg_begin + 3j .. + 2, final_i at seg_begin + 3t and z_in = (x_0, y_0, i) in the three variables before seg_begin:
+ *   row 3j      x' * x' = tmp1;    row 3j + 1   tmp1 * tmp1 = tmp2;
+ *   row 3j + 2  tmp2 * x' = x_j + y_j   (j = 0: z_in.x + z_in.y; j >= 1: x_j + x_(j-1) + i + (j - 1) * one);
+ *   row 3t      final_i * one = i + t * one.
+ * Operands and guarantees as vdf_nifs_cross_term_minroot (exact for any z2; the caller answers for the rows being this
+ * stencil).  libvdf_nova.so reports this stencil as code 5 (vdf_nova_pp_stencil). */
+int  vdf_nifs_cross_term_minroot_forward(vdf_ctx* ctx, int field, uint64_t t, size_t seg_begin, size_t one_col, size_t row_begin,
+                                         const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1, const vdf_fe* u1,
+                                         vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T);
 /* The same rows with the PREVIOUS fold of those rows applied on the way.  A prover that keeps A z, B z, C z of the running
  * instance folds them after every step (X1 <- X1 + r X2); for the stencil rows the fresh vectors X2 of the previous step are
  * exactly what this call is about to overwrite in Az2 / Bz2 / Cz2.  So, per row: Az1 += r Az2, Bz1 += r Bz2, Cz1 += r Cz2

@@ -29,7 +29,7 @@
  * point where they share its second queue; nothing else is.  The library has threads of its own: up to a few sets of three
  * detached synthesis helpers, made when a prover first wants them and parked between calls (they never touch a handle
  * outside the call that handed them work), and one thread per vdf_nova_compress for the secondary side's argument, joined
- * before the call returns.
+ * before the call returns; vdf_nova_eval_and_prove runs the forward evaluation on a thread of its own, joined before it returns.
  */
 #ifndef VDF_NOVA_H
 #define VDF_NOVA_H
@@ -77,8 +77,17 @@ typedef struct vdf_snark vdf_snark;       /* NovaVDFProof::Compressed, :54 */
  * work-in-progress reference that a drop-in reproduces.  BOUND: the sound variant, offered as an option -- new_x carried
  * as the linear combination y - i + 1 instead of a variable, 3 variables and the same 3 constraints per round.
  * The witness of the reference's circuit is committed WITHOUT a term per new_x: new_x_j is an affine image of new_y_(j-1),
- * so its share folds into derived generators (vdf_hip.h vdf_minroot_step_segment_packed) -- same commitment, 3t + 4 terms. */
-enum { VDF_CIRCUIT_MINROOT_BOUND = 0, VDF_CIRCUIT_MINROOT_REFERENCE = 1, VDF_CIRCUIT_CUSTOM = 2 /* vdf_step_circuit, below */ };
+ * so its share folds into derived generators (vdf_hip.h vdf_minroot_step_segment_packed) -- same commitment, 3t + 4 terms.
+ * FORWARD: the step in the direction of evaluation (src/minroot.rs:329-335), arity 3, z_in = (x_0, y_0, i_in): per round the
+ * fifth root x_(j+1) is allocated (the hint comes from the forward trace), tmp1 = x_(j+1)^2, tmp2 = tmp1^2 and
+ * tmp2 * x_(j+1) = x_j + y_j is enforced; y_(j+1) = x_j + i_in + j is a linear combination; then final_i = i_in + t.
+ * 3 variables and 3 constraints per round, the size of BOUND.  Sound by construction: the fifth root is the only free variable
+ * of a round and x -> x^5 is a bijection on Fq.  A proof of this kind states z0 = the chain's INITIAL state and zi = its final
+ * state, and its steps are proved in the order they are evaluated (vdf_nova_circuits_forward_begin, vdf_nova_eval_and_prove);
+ * verify, compress, the batch calls and both wire formats work on it unchanged.  packed_commit does not apply; fold_fused
+ * falls back to the unfused fold. */
+enum { VDF_CIRCUIT_MINROOT_BOUND = 0, VDF_CIRCUIT_MINROOT_REFERENCE = 1, VDF_CIRCUIT_CUSTOM = 2 /* vdf_step_circuit, below */,
+       VDF_CIRCUIT_MINROOT_FORWARD = 3 };
 enum { VDF_SIDE_PRIMARY = 0, VDF_SIDE_SECONDARY = 1 };
 
 /* public_params(num_iters_per_step), :232-237: both augmented circuits synthesised once for their R1CS shapes,
@@ -184,10 +193,13 @@ int  vdf_nova_pp_segment(const vdf_pp* pp, uint64_t* begin, uint64_t* len);
 int  vdf_nova_pp_early_rows(const vdf_pp* pp, uint64_t* begin, uint64_t* len);
 /* 4 / 3: the early rows are the built-in MinRoot stencil (the reference's rounds / the bound form), verified against the
  * shape's triples when the parameters were made -- their cross term runs without the sparse matrices
- * (vdf_hip.h vdf_nifs_cross_term_minroot); 0: they run through the generic sparse kernel (a custom circuit, or no early rows) */
+ * (vdf_hip.h vdf_nifs_cross_term_minroot); 5 (VDF_STENCIL_FORWARD): the forward circuit's stencil
+ * (vdf_nifs_cross_term_minroot_forward) -- a CODE, not a count of variables per round (that circuit has 3; 3 and 4 were
+ * taken); 0: they run through the generic sparse kernel (a custom circuit, or no early rows) */
+enum { VDF_STENCIL_FORWARD = 5 };
 int  vdf_nova_pp_stencil(const vdf_pp* pp);
 /* The same answer without a device (host only): builds the shape of the built-in step circuit at t, finds the early rows
- * and compares them with the stencil; returns 4 / 3 / 0 (negative: an error code).  Outputs may be NULL. */
+ * and compares them with the stencil; returns 5 / 4 / 3 / 0 (negative: an error code).  Outputs may be NULL. */
 int  vdf_nova_shape_stencil(uint64_t t, int circuit_kind, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin);
 
 /* InverseMinRootCircuit::eval_and_make_circuits, :262-299: num_steps forward evaluations of
@@ -230,6 +242,28 @@ int  vdf_nova_circuits_memory(const vdf_circuits* c, size_t* resident_steps, uin
 /* the device trace of circuit k, 2 (t + 1) elements, NULL when it has none (pending walks over it are finished first): for
  * tests and tools */
 int  vdf_nova_circuit_trace(const vdf_circuits* c, size_t k, const void** d_trace);
+/* host memory the circuits hold in traces and checkpoints (bytes) */
+int  vdf_nova_circuits_host_bytes(const vdf_circuits* c, uint64_t* bytes);
+
+/* ---- forward chains: circuits that GROW (for parameters of VDF_CIRCUIT_MINROOT_FORWARD) -------------------------------
+ * An empty chain of steps of t rounds that starts at initial_state; z0_primary = that state.  Steps are appended in the
+ * order of evaluation and circuit k is the k-th one pushed, so a prover may run while the chain is still being evaluated.
+ * There is NO lock: a push or a release must not overlap a vdf_nova_prove_step over the same circuits (between two steps
+ * both are safe).  prove_step's lookahead stops at the end of the vector: the last step pushed so far runs without it.
+ * prove_step with forward parameters over other circuits, or the other way round, is VDF_ERR_BAD_ARG.
+ * vdf_nova_prove_recursively[_windowed] over a complete forward chain work as over any other circuits. */
+int  vdf_nova_circuits_forward_begin(uint64_t t, const vdf_state* initial_state, vdf_fe z0_primary[3], vdf_circuits** out);
+/* Appends one step from its host trace, 2 (t + 1) elements as vdf_minroot_eval writes them.  Entry 0 must be (x, y) of the
+ * chain's current end (VDF_ERR_BAD_ARG otherwise, nothing appended); the step's result is entry t with i advanced by t.  The
+ * trace is copied and reaches the device through the proof's staging buffer when the step (or its lookahead) runs. */
+int  vdf_nova_circuits_push_trace(vdf_circuits* c, const vdf_fe* trace_xy);
+/* Appends one step from its t / every + 1 states every `every` rounds (states[0] = the chain's current end, compared whole;
+ * .i checked as vdf_nova_circuits_from_checkpoints checks it; `every` divides t and is the same for every such step of a
+ * chain).  The step holds no trace until vdf_nova_circuits_materialize rebuilds it by inverse walks, each checked against
+ * the checkpoint before it: the entry for an evaluator elsewhere that sends 96-byte states instead of 64 (t + 1) bytes a step.
+ * vdf_nova_circuits_release on a forward chain also drops the host trace of a step pushed by vdf_nova_circuits_push_trace:
+ * a long stream holds a bounded number of steps. */
+int  vdf_nova_circuits_push_checkpoints(vdf_circuits* c, uint64_t every, const vdf_state* states);
 size_t vdf_nova_circuits_len(const vdf_circuits* c);
 /* result / input of circuit k (k = 0 is proved first): InverseMinRootCircuit.result / .input */
 int  vdf_nova_circuit_states(const vdf_circuits* c, size_t k, vdf_state* result, vdf_state* input);
@@ -254,6 +288,15 @@ int  vdf_nova_prove_recursively_windowed(vdf_pp* pp, const vdf_circuits* circuit
  * Over checkpoint circuits the traces of circuit k AND of circuit k + 1 (when there is one) must be resident
  * (vdf_nova_circuits_materialize): VDF_ERR_BAD_ARG "trace of circuit k not materialised" otherwise, nothing done. */
 int  vdf_nova_prove_step(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* circuits, size_t k, const vdf_fe z0[3]);
+/* Evaluate a chain and prove it WHILE it is evaluated (forward parameters only).  A thread of this call runs
+ * vdf_minroot_eval step by step from initial_state (num_steps steps of pp's t rounds) and hands each finished trace over
+ * through a queue of at most 4; the calling thread pushes, proves and releases.  *out: the running proof of
+ * z0 = initial_state, zi = *final_state (optional output), ready for verify / compress.  stats (optional): eval_ms = the
+ * evaluator's time to its last round; after_eval_ms = from that moment to the return (the last step and the last secondary
+ * commitment); max_backlog = the most steps evaluated and not yet proved at the start of a step (1: the prover kept up). */
+typedef struct vdf_nova_stream_stats { double eval_ms, after_eval_ms; uint64_t max_backlog, steps; } vdf_nova_stream_stats;
+int  vdf_nova_eval_and_prove(vdf_pp* pp, int mode, const vdf_state* initial_state, size_t num_steps, vdf_state* final_state,
+                             vdf_proof** out, vdf_nova_stream_stats* stats);
 /* NovaVDFProof::verify(pp, num_steps, z0, zi), :370-387: *ok = 1 iff the proof is valid for num_steps steps from z0
  * (two output hashes, three satisfiability claims), the verified zi_primary equals zi, and zi_secondary == [0]
  * (the Ok(bool) of :386). */

@@ -4,6 +4,9 @@
 #include <sys/random.h>
 #include <algorithm>
 #include <cerrno>
+#include <condition_variable>
+#include <deque>
+#include <thread>
 #include "nova_internal.hpp"
 
 using namespace vdfnova;
@@ -21,6 +24,19 @@ RelaxedInst to_relaxed(const Inst& in, const Field& own) {
 }
 
 std::unique_ptr<StepCircuit> make_primary_circuit(const vdf_pp* pp, const Circuit* c, bool device_rounds) {
+  if (pp->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD) {
+    std::unique_ptr<ForwardMinRootCircuit> m(new ForwardMinRootCircuit());
+    m->t = pp->t;
+    m->device_rounds = device_rounds;
+    m->blank = c == nullptr;
+    if (c) {
+      m->result = MinRootState{c->result.x, c->result.y, c->result.i};
+      m->input = MinRootState{c->input.x, c->input.y, c->input.i};
+    } else {
+      m->result = m->input = MinRootState{zero(), zero(), zero()};
+    }
+    return std::unique_ptr<StepCircuit>(m.release());
+  }
   std::unique_ptr<InverseMinRootCircuit> m(new InverseMinRootCircuit());
   m->t = pp->t;
   m->bound = pp->circuit_kind == VDF_CIRCUIT_MINROOT_BOUND;
@@ -107,6 +123,13 @@ int vdf_cs_value(const vdf_cs* c, vdf_num a, vdf_fe* out) {
 }  // extern "C"
 
 namespace {
+
+// the step circuits this library writes itself (everything but VDF_CIRCUIT_CUSTOM)
+bool builtin_circuit(int kind) {
+  return kind == VDF_CIRCUIT_MINROOT_BOUND || kind == VDF_CIRCUIT_MINROOT_REFERENCE || kind == VDF_CIRCUIT_MINROOT_FORWARD;
+}
+// variables per round of a built-in circuit
+int vars_per_round(int kind) { return kind == VDF_CIRCUIT_MINROOT_REFERENCE ? 4 : 3; }
 
 AugInputs blank_inputs(size_t arity) {
   AugInputs in;
@@ -470,7 +493,7 @@ int vdf_nova_shape_export(uint64_t t, int circuit_kind, int side, uint64_t nnz[3
                           vdf_fe* const vals[3]) {
   return nova_guard([&]() -> int {
     if (t == 0 || t > (1ull << 24) || !nnz || (side != PRIMARY && side != SECONDARY)) return fail(VDF_ERR_BAD_ARG, "bad argument");
-    if (circuit_kind != VDF_CIRCUIT_MINROOT_BOUND && circuit_kind != VDF_CIRCUIT_MINROOT_REFERENCE) return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
+    if (!builtin_circuit(circuit_kind)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
     HostShape sh[2];
     build_shapes(t, circuit_kind, sh);
     const HostShape& h = sh[side];
@@ -637,7 +660,7 @@ static int public_params_impl(vdf_ctx* ctx, uint64_t t, int circuit_kind, const 
 int vdf_nova_public_params_tuned(vdf_ctx* ctx, uint64_t t, int circuit_kind, int gens_family, const vdf_nova_tuning* tuning, vdf_pp** out) {
   return nova_guard([&]() -> int {
     if (!ctx || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
-    if (circuit_kind != VDF_CIRCUIT_MINROOT_BOUND && circuit_kind != VDF_CIRCUIT_MINROOT_REFERENCE)
+    if (!builtin_circuit(circuit_kind))
       return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
     if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
     return public_params_impl(ctx, t, circuit_kind, nullptr, gens_family, tuning ? *tuning : default_tuning(), out);
@@ -650,7 +673,7 @@ int vdf_nova_public_params_ro(vdf_ctx* ctx, uint64_t t, int circuit_kind, int ge
     const RoInstance* ro = ro_from_abi(rop, &bad);
     if (bad) return fail(VDF_ERR_BAD_ARG, "unsupported RO parameter block (vdf_nova.h: alpha 5, 128 / 250 bits, family 1 widths 2..25)");
     if (!ctx || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
-    if (circuit_kind != VDF_CIRCUIT_MINROOT_BOUND && circuit_kind != VDF_CIRCUIT_MINROOT_REFERENCE)
+    if (!builtin_circuit(circuit_kind))
       return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
     if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
     return public_params_impl(ctx, t, circuit_kind, nullptr, gens_family, tuning ? *tuning : default_tuning(), out, ro);
@@ -775,6 +798,57 @@ static bool minroot_stencil_matches(const HostShape& h, const Field& F, uint64_t
   return true;
 }
 
+// The same question for the FORWARD circuit and vdf_nifs_cross_term_minroot_forward (include/vdf_hip.h): round j holds
+// x_(j+1), tmp1, tmp2 at S + 3j .., final_i at S + 3t, z_in in the three variables before S.
+static bool forward_stencil_matches(const HostShape& h, const Field& F, uint64_t t, size_t S, size_t row0) {
+  const size_t nrows = 3 * (size_t)t + 1, one_col = h.num_vars;
+  if (S < 3 || row0 + nrows > h.num_cons || S + 3 * (size_t)t + 1 > h.num_vars) return false;
+  typedef std::vector<std::pair<uint32_t, Fe>> Row;
+  const Fe p1 = one(F);
+  for (int k = 0; k < 3; ++k) {
+    std::vector<Row> got(nrows);
+    const Coo& m = h.m[k];
+    for (size_t e = 0; e < m.rows.size(); ++e)
+      if (m.rows[e] >= row0 && m.rows[e] < row0 + nrows) got[m.rows[e] - row0].push_back({m.cols[e], vdfhost::canon(m.vals[e], F)});
+    for (size_t i = 0; i < nrows; ++i) {
+      Row want;
+      if (i == nrows - 1) {
+        if (k == 0) want = {{(uint32_t)(S + 3 * (size_t)t), p1}};
+        else if (k == 1) want = {{(uint32_t)one_col, p1}};
+        else want = {{(uint32_t)(S - 1), p1}, {(uint32_t)one_col, from_u64(t, F)}};
+      } else {
+        const size_t j = i / 3, role = i - 3 * j, rd = S + 3 * j;
+        const uint32_t nx = (uint32_t)rd, t1 = nx + 1, t2 = nx + 2;
+        if (role == 0) want = k < 2 ? Row{{nx, p1}} : Row{{t1, p1}};
+        else if (role == 1) want = k < 2 ? Row{{t1, p1}} : Row{{t2, p1}};
+        else if (k == 0) want = {{t2, p1}};
+        else if (k == 1) want = {{nx, p1}};
+        else if (j == 0) want = {{(uint32_t)(S - 3), p1}, {(uint32_t)(S - 2), p1}};
+        else {
+          want = {{(uint32_t)(rd - 3), p1}, {(uint32_t)(j > 1 ? rd - 6 : S - 3), p1}, {(uint32_t)(S - 1), p1}};
+          if (j > 1) want.push_back({(uint32_t)one_col, from_u64(j - 1, F)});
+        }
+      }
+      Row& g = got[i];
+      if (g.size() != want.size()) return false;
+      auto by_col = [](const std::pair<uint32_t, Fe>& a, const std::pair<uint32_t, Fe>& b) { return a.first < b.first; };
+      std::sort(g.begin(), g.end(), by_col);
+      std::sort(want.begin(), want.end(), by_col);
+      for (size_t e = 0; e < g.size(); ++e)
+        if (g[e].first != want[e].first || g[e].second != vdfhost::canon(want[e].second, F)) return false;
+    }
+  }
+  return true;
+}
+// the stencil code of a built-in circuit whose early rows are [row0, row0 + 3t + 1): 3 / 4 = the inverse forms (variables
+// per round), 5 = the forward circuit; 0 = no match
+static int builtin_stencil(const HostShape& h, int circuit_kind, uint64_t t, size_t S, size_t row0) {
+  const Field& F = field(side_field(PRIMARY));
+  if (circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD) return forward_stencil_matches(h, F, t, S, row0) ? VDF_STENCIL_FORWARD : 0;
+  const int per = vars_per_round(circuit_kind);
+  return minroot_stencil_matches(h, F, t, per, S, row0) ? per : 0;
+}
+
 static int public_params_impl(vdf_ctx* ctx, uint64_t t, int circuit_kind, const vdf_step_circuit* custom, int gens_family,
                               const vdf_nova_tuning& tune, vdf_pp** out, const RoInstance* ro) {
   if (gens_family != VDF_GENS_TRY_AND_INCREMENT && gens_family != VDF_GENS_KNOWN_DLOG && gens_family != VDF_GENS_LABEL_SHAKE)
@@ -816,10 +890,8 @@ static int public_params_impl(vdf_ctx* ctx, uint64_t t, int circuit_kind, const 
     pp->ahead_mode = tune.early_rows == 1 ? 1 : 2;
     // the built-in circuits' early rows are a fixed stencil over the rounds' variables: compared with the shape triple by triple
     // once, here; from then on their cross term reads no sparse matrix (tuning.stencil = 0: the generic kernel, for A/B runs)
-    const int per = circuit_kind == VDF_CIRCUIT_MINROOT_BOUND ? 3 : 4;
-    if (!custom && pp->ahead_rows == 3 * t + 1 && tune.stencil &&
-        minroot_stencil_matches(h, field(side_field(PRIMARY)), t, per, pp->seg_begin, pp->ahead_row))
-      pp->stencil_per = per;
+    if (!custom && pp->ahead_rows == 3 * t + 1 && tune.stencil)
+      pp->stencil_per = builtin_stencil(h, circuit_kind, t, pp->seg_begin, pp->ahead_row);
   }
   ms[0] = now_ms() - mark; mark = now_ms();
   for (int s = 0; s < 2; ++s) {
@@ -990,7 +1062,7 @@ int vdf_nova_pp_stencil(const vdf_pp* pp) { return pp ? pp->stencil_per : 0; }
 // host only (no device): what vdf_nova_public_params would find for the built-in step circuit `circuit_kind` at `t`
 int vdf_nova_shape_stencil(uint64_t t, int circuit_kind, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
   return nova_guard([&]() -> int {
-    if (t == 0 || t > (1ull << 24) || (circuit_kind != VDF_CIRCUIT_MINROOT_BOUND && circuit_kind != VDF_CIRCUIT_MINROOT_REFERENCE))
+    if (t == 0 || t > (1ull << 24) || (!builtin_circuit(circuit_kind)))
       return -fail(VDF_ERR_BAD_ARG, "bad argument");
     HostShape sh[2];
     if (build_shapes(t, circuit_kind, sh) != VDF_OK) return -VDF_ERR_DEVICE;
@@ -1002,8 +1074,7 @@ int vdf_nova_shape_stencil(uint64_t t, int circuit_kind, uint64_t* early_begin, 
     if (early_begin) *early_begin = b;
     if (early_len) *early_len = n;
     if (seg_begin) *seg_begin = sb;
-    const int per = circuit_kind == VDF_CIRCUIT_MINROOT_BOUND ? 3 : 4;
-    return (n == 3 * t + 1 && minroot_stencil_matches(h, field(side_field(PRIMARY)), t, per, sb, b)) ? per : 0;
+    return n == 3 * t + 1 ? builtin_stencil(h, circuit_kind, t, sb, b) : 0;
   });
 }
 
@@ -1064,6 +1135,71 @@ int vdf_nova_circuits_from_checkpoints(uint64_t t, uint64_t every, size_t num_st
     }
     memcpy(z0_primary, &states[total - 1], 96);                        // z0 = final state, :278-281
     *out = cs.release();
+    return VDF_OK;
+  });
+}
+
+
+// ---- forward chains: circuits in the order of evaluation, appended to while the chain grows -------------------------
+int vdf_nova_circuits_forward_begin(uint64_t t, const vdf_state* initial_state, vdf_fe z0_primary[3], vdf_circuits** out) {
+  return nova_guard([&]() -> int {
+    if (!initial_state || !z0_primary || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    std::unique_ptr<vdf_circuits> cs(new vdf_circuits());
+    cs->forward = true;
+    cs->forward_t = t;
+    cs->end = load_state(initial_state);
+    memcpy(z0_primary, initial_state, 96);                             // z0 = the chain's initial state
+    *out = cs.release();
+    return VDF_OK;
+  });
+}
+int vdf_nova_circuits_push_trace(vdf_circuits* c, const vdf_fe* trace_xy) {
+  return nova_guard([&]() -> int {
+    if (!c || !trace_xy) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_forward_begin)");
+    const uint64_t t = c->forward_t;
+    if (memcmp(&trace_xy[0], &c->end.x, 32) != 0 || memcmp(&trace_xy[1], &c->end.y, 32) != 0)
+      return fail(VDF_ERR_BAD_ARG, "the trace does not start at the chain's current end");
+    Circuit cc;
+    cc.t = t;
+    cc.input = c->end;
+    memcpy(&cc.result.x, &trace_xy[2 * t], 32);
+    memcpy(&cc.result.y, &trace_xy[2 * t + 1], 32);
+    cc.result.i = add(c->end.i, from_u64(t, field(VDF_FIELD_FQ)), field(VDF_FIELD_FQ));
+    cc.trace_xy.assign((const Fe*)trace_xy, (const Fe*)trace_xy + 2 * (t + 1));
+    c->end = cc.result;
+    c->v.push_back(std::move(cc));
+    return VDF_OK;
+  });
+}
+int vdf_nova_circuits_push_checkpoints(vdf_circuits* c, uint64_t every, const vdf_state* states) {
+  return nova_guard([&]() -> int {
+    if (!c || !states) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_forward_begin)");
+    const uint64_t t = c->forward_t;
+    if (every == 0 || t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
+    if (!c->v.empty() && c->checkpoints)
+      for (const Circuit& k : c->v) if (k.every && k.every != every) return fail(VDF_ERR_BAD_ARG, "`every` differs from the chain's earlier checkpoint steps");
+    if (memcmp(&states[0], &c->end, 96) != 0) return fail(VDF_ERR_BAD_ARG, "states[0] is not the chain's current end");
+    const size_t per = (size_t)(t / every);
+    const Field& F = field(VDF_FIELD_FQ);
+    const Fe step = from_u64(every, F);
+    Fe want = c->end.i;
+    for (size_t k = 1; k <= per; ++k) {
+      want = add(want, step, F);
+      if (memcmp(&states[k].i, &want, 32) != 0)
+        return fail(VDF_ERR_BAD_ARG, "checkpoint " + std::to_string(k) + ": i is not states[0].i + " + std::to_string(k) + " * every");
+    }
+    Circuit cc;
+    cc.t = t;
+    cc.every = every;
+    cc.cp.resize(per + 1);
+    for (size_t m = 0; m <= per; ++m) cc.cp[m] = load_state(&states[m]);
+    cc.input = cc.cp.front();
+    cc.result = cc.cp.back();
+    c->end = cc.result;
+    c->checkpoints = true;
+    c->v.push_back(std::move(cc));
     return VDF_OK;
   });
 }
@@ -1196,7 +1332,8 @@ int vdf_nova_circuits_materialize(vdf_ctx* ctx, vdf_circuits* c, size_t first, s
     if (c->ctx && vdf_ctx_device(c->ctx) != vdf_ctx_device(ctx)) return fail(VDF_ERR_BAD_ARG, "the circuits' traces live on another device");
     c->ctx = ctx;
     std::unique_ptr<WalkJob> j(new WalkJob());
-    for (size_t k = first; k < first + count; ++k) if (!c->v[k].d_trace) j->steps.push_back(k);
+    // (a forward chain may mix steps pushed as traces with steps pushed as checkpoints: only the latter are walked)
+    for (size_t k = first; k < first + count; ++k) if (!c->v[k].d_trace && !c->v[k].cp.empty()) j->steps.push_back(k);
     if (j->steps.empty()) return pending;
     if (!c->side) {
       const int dev = vdf_ctx_device(ctx);
@@ -1263,6 +1400,8 @@ int vdf_nova_circuits_release(vdf_circuits* c, size_t first, size_t count) {
     if (c->job)
       for (size_t k : c->job->steps) if (k >= first && k - first < count) { pending = job_resolve(c, nullptr, 0, 0); break; }
     release_range(c, first, count, false);
+    // a forward chain is a stream: a step that has been proved lets go of its pushed host trace too
+    if (c->forward) for (size_t k = first; k < first + count; ++k) std::vector<Fe>().swap(c->v[k].trace_xy);
     return pending;
   });
 }
@@ -1408,6 +1547,7 @@ struct StepRun {
   const Field& F2;
   const size_t seg_b, seg_n, seg_e;    // the primary witness's run of round variables
   const int per;
+  const bool forward;                  // the forward step circuit: rounds by vdf_minroot_forward_segment, stencil code 5
   const bool t_ahead;                  // this step has early rows
   const size_t ta_b, ta_n, ta_e;
   const int t_parts;                   // (tuning.early_row_parts = 2 or 3: the early rows as an MSM job of that many parts (vdf_msm_job_*): a later part's
@@ -1437,7 +1577,7 @@ struct StepRun {
   StepRun(vdf_pp* pp_, vdf_proof* p_, const vdf_circuits* circuits_, size_t k_, const vdf_step_circuit* custom_, const Circuit& c_, bool first_)
       : pp(pp_), p(p_), circuits(circuits_), k(k_), custom(custom_), c(c_), first(first_), arity(pp_->arity), ctx(pp_->ctx), ct(p_->ctx3),
         S1(pp_->s[PRIMARY]), S2(pp_->s[SECONDARY]), F1(*pp_->s[PRIMARY].F), F2(*pp_->s[SECONDARY].F), seg_b(pp_->seg_begin), seg_n(pp_->seg_len),
-        seg_e(pp_->seg_begin + pp_->seg_len), per(pp_->circuit_kind == VDF_CIRCUIT_MINROOT_BOUND ? 3 : 4),
+        seg_e(pp_->seg_begin + pp_->seg_len), per(vars_per_round(pp_->circuit_kind)), forward(pp_->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD),
         t_ahead(!first_ && !custom_ && pp_->ahead_rows != 0), ta_b(pp_->ahead_row), ta_n(pp_->ahead_rows), ta_e(pp_->ahead_row + pp_->ahead_rows),
         t_parts(pp_->tune.early_row_parts), fold_on_rows(pp_->tune.fold_on_rows != 0), hb(&p_->h_pts[R]), early1(nullptr, aug_early_free),
         early2(nullptr, aug_early_free) {
@@ -1460,7 +1600,8 @@ struct StepRun {
     }
     char* seg = (char*)p->d_z2s[s] + seg_b * 32;
     void* packed = pp->seg_gens ? p->d_packed[j % D] : nullptr;
-    if (packed) HIPCALL(q, vdf_minroot_step_segment_packed(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.input.i,
+    if (forward) HIPCALL(q, vdf_minroot_forward_segment(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.result.i, (vdf_fe*)seg));
+    else if (packed) HIPCALL(q, vdf_minroot_step_segment_packed(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.input.i,
                                                             (const vdf_fe*)&cc.result.i, (vdf_fe*)seg, (vdf_fe*)packed));
     else HIPCALL(q, vdf_minroot_step_segment(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.input.i, per, (vdf_fe*)seg));
     HIPCALL(q, vdf_ctx_mark(q, MARK_Z));
@@ -1522,7 +1663,10 @@ struct StepRun {
   // lives in d_z2 (this step's, or -- launched on the way out -- the next one's).
   // fold_r (fused mode, stencil_fold_ok()): the challenge of the fold that has NOT been applied to the early rows of the running
   // A z, B z, C z and E yet -- the stencil applies it on the way (vdf_nifs_cross_term_minroot_fold) and MARK_FOLD is set behind it
-  bool stencil_fold_ok() const { return pp->tune.fold_fused != 0 && pp->stencil_per != 0 && (t_parts == 1 || ta_n < 4096); }
+  // (no fused kernel exists for the forward stencil: that kind keeps the unfused fold)
+  bool stencil_fold_ok() const {
+    return pp->tune.fold_fused != 0 && pp->stencil_per != 0 && pp->stencil_per != VDF_STENCIL_FORWARD && (t_parts == 1 || ta_n < 4096);
+  }
   int early_rows_launch(void* d_z2, vdf_ctx* cq, bool zin_in_place, const Fe* fold_r = nullptr) {
     SideState& s1 = p->r[PRIMARY];
     HIPCALL(ct, vdf_ctx_wait_mark(ct, cq, MARK_Z));                 // the rounds are in place (written a step ago, normally)
@@ -1539,6 +1683,12 @@ struct StepRun {
                                                      (vdf_fe*)s1.d_E, (const vdf_fe*)s1.d_T, (const vdf_fe*)&s1.inst.u, (vdf_fe*)s1.d_abc2[0],
                                                      (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
         HIPCALL(ct, vdf_ctx_mark(ct, MARK_FOLD));                    // the running instance is whole again from here on
+        return VDF_OK;
+      }
+      if (pp->stencil_per == VDF_STENCIL_FORWARD && b == ta_b && n == ta_n) {
+        HIPCALL(ct, vdf_nifs_cross_term_minroot_forward(ct, S1.field, pp->t, seg_b, S1.num_vars, b, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0],
+                                                        (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2], (const vdf_fe*)&s1.inst.u,
+                                                        (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
         return VDF_OK;
       }
       if (pp->stencil_per && b == ta_b && n == ta_n) {               // the MinRoot stencil: streams only (vdf_hip.h)
@@ -1912,6 +2062,9 @@ static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* ci
   if (!custom && k >= circuits->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
   const Circuit& c = custom ? no_circuit : circuits->v[k];
   if (!custom && c.t != pp->t) return fail(VDF_ERR_BAD_LENGTH, "circuit t differs from the public parameters");
+  if (!custom && circuits->forward != (pp->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD))
+    return fail(VDF_ERR_BAD_ARG, circuits->forward ? "forward circuits need parameters of VDF_CIRCUIT_MINROOT_FORWARD"
+                                                   : "forward parameters need circuits made by vdf_nova_circuits_forward_begin");
   if (!custom && circuits->checkpoints) {        // this step reads the trace of circuit k, and enqueues the rounds of circuit k + 1
     int rc = circuits_need(circuits, k);
     if (rc == VDF_OK && k + 1 < circuits->v.size() && circuits->v[k + 1].t == pp->t) rc = circuits_need(circuits, k + 1);
@@ -1938,8 +2091,10 @@ static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* ci
     return fail(VDF_ERR_BAD_ARG, "z0 differs from the one this proof was started with");
   }
   // StepCircuit::output's debug assertion: z_i must be the circuit's result (src/nova/proof.rs:147-149)
-  if (!custom && memcmp(p->zi[PRIMARY].data(), &c.result, 96) != 0)
-    return fail(VDF_ERR_BAD_ARG, "z_i does not match the circuit's result state");
+  // (the forward circuit starts from the step's input state and hands on its result)
+  if (!custom && memcmp(p->zi[PRIMARY].data(), pp->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD ? &c.input : &c.result, 96) != 0)
+    return fail(VDF_ERR_BAD_ARG, pp->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD ? "z_i does not match the circuit's input state"
+                                                                               : "z_i does not match the circuit's result state");
   const double t0 = now_ms();
   int was_async = 0;
   HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
@@ -1976,7 +2131,7 @@ int vdf_nova_prove_recursively_windowed(vdf_pp* pp, const vdf_circuits* circuits
     bool windowed = false;
     if (cs->checkpoints) {
       if (cs->job) { int rc = circuits_need(cs, cs->job->steps[0]); if (rc != VDF_OK) { *out = nullptr; return rc; } }
-      for (const Circuit& c : cs->v) windowed |= !c.d_trace;
+      for (const Circuit& c : cs->v) windowed |= !c.d_trace && !c.cp.empty();
     }
     const size_t W = !windowed ? n : window_steps ? std::max<size_t>(window_steps, 2)
                                                   : std::max<size_t>(2, (size_t)(((uint64_t)1 << 30) / ((pp->t + 1) * 64)));
@@ -1985,7 +2140,7 @@ int vdf_nova_prove_recursively_windowed(vdf_pp* pp, const vdf_circuits* circuits
       const size_t b = w * W;
       if (!windowed || b >= n) return VDF_OK;
       const size_t cnt = std::min(W, n - b);
-      for (size_t k = b; k < b + cnt; ++k) mine[k] = !cs->v[k].d_trace;
+      for (size_t k = b; k < b + cnt; ++k) mine[k] = !cs->v[k].d_trace && !cs->v[k].cp.empty();
       return vdf_nova_circuits_materialize(pp->ctx, cs, b, cnt, wait, nullptr);
     };
     auto drop = [&](size_t w) {
@@ -2014,6 +2169,95 @@ int vdf_nova_prove_recursively_windowed(vdf_pp* pp, const vdf_circuits* circuits
 int vdf_nova_prove_recursively(vdf_pp* pp, const vdf_circuits* circuits, uint64_t num_iters_per_step, const vdf_fe z0[3],
                                vdf_proof** out) {
   return vdf_nova_prove_recursively_windowed(pp, circuits, num_iters_per_step, z0, 0, out);
+}
+
+// Evaluate and prove at once: a thread of this call evaluates the chain step by step and hands every finished trace over
+// through a queue of at most EVAL_QUEUE entries; the calling thread pushes, proves and releases.  The prover is two orders of
+// magnitude faster than the evaluator, so the proof is complete one step and the last commitment after the last round.
+int vdf_nova_eval_and_prove(vdf_pp* pp, int mode, const vdf_state* initial_state, size_t num_steps, vdf_state* final_state,
+                            vdf_proof** out, vdf_nova_stream_stats* stats) {
+  return nova_guard([&]() -> int {
+    if (!pp || !initial_state || !out || !valid_mode(mode)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    if (num_steps == 0) return fail(VDF_ERR_BAD_ARG, "num_steps must be > 0");
+    if (pp->circuit_kind != VDF_CIRCUIT_MINROOT_FORWARD) return fail(VDF_ERR_BAD_ARG, "these parameters are not for VDF_CIRCUIT_MINROOT_FORWARD");
+    *out = nullptr;
+    constexpr size_t EVAL_QUEUE = 4;
+    const uint64_t t = pp->t;
+    struct Shared {
+      std::mutex mu;
+      std::condition_variable cv;
+      std::deque<std::vector<Fe>> traces;
+      bool stop = false;
+      double eval_end = 0, eval_ms = 0;
+    } sh;
+    const St init = load_state(initial_state);
+    std::thread evaluator;
+    struct Join {                                  // whatever way this call ends, the evaluator is told and waited for
+      Shared& sh; std::thread& th;
+      ~Join() { { std::lock_guard<std::mutex> lk(sh.mu); sh.stop = true; } sh.cv.notify_all(); if (th.joinable()) th.join(); }
+    } join{sh, evaluator};
+    evaluator = std::thread([&sh, init, t, num_steps, mode]() {
+      St state = init;
+      const double t_begin = now_ms();
+      for (size_t k = 0; k < num_steps; ++k) {
+        std::vector<Fe> trace(2 * (t + 1));
+        vdf_state in, res;
+        store_state(&in, state);
+        vdf_minroot_eval(VDF_FIELD_FQ, mode, &in, t, &res, (vdf_fe*)trace.data());
+        state = load_state(&res);
+        std::unique_lock<std::mutex> lk(sh.mu);
+        if (k + 1 == num_steps) { sh.eval_end = now_ms(); sh.eval_ms = sh.eval_end - t_begin; }   // the chain's output exists from here
+        sh.cv.wait(lk, [&] { return sh.traces.size() < EVAL_QUEUE || sh.stop; });
+        if (sh.stop) return;
+        sh.traces.push_back(std::move(trace));
+        sh.cv.notify_all();
+      }
+    });
+    vdf_circuits* cs = nullptr;
+    vdf_fe z0[3];
+    vdf_proof* p = nullptr;
+    int rc = vdf_nova_circuits_forward_begin(t, initial_state, z0, &cs);
+    size_t pushed = 0, max_backlog = 0;
+    for (size_t k = 0; rc == VDF_OK && k < num_steps; ++k) {
+      // everything the evaluator has finished goes into the chain (the step after this one then rides in this step's lookahead)
+      std::vector<std::vector<Fe>> got;
+      {
+        std::unique_lock<std::mutex> lk(sh.mu);
+        sh.cv.wait(lk, [&] { return !sh.traces.empty() || pushed > k; });
+        while (!sh.traces.empty()) { got.push_back(std::move(sh.traces.front())); sh.traces.pop_front(); }
+        sh.cv.notify_all();
+      }
+      for (size_t g = 0; rc == VDF_OK && g < got.size(); ++g) {
+        rc = vdf_nova_circuits_push_trace(cs, (const vdf_fe*)got[g].data());
+        if (rc == VDF_OK) ++pushed;
+      }
+      got.clear();
+      max_backlog = std::max(max_backlog, pushed - k);
+      if (rc == VDF_OK) rc = vdf_nova_prove_step(pp, &p, cs, k, z0);
+      if (rc == VDF_OK) rc = vdf_nova_circuits_release(cs, k, 1);
+    }
+    if (rc == VDF_OK) rc = finalize_l2(p);
+    const double t_done = now_ms();
+    if (rc == VDF_OK && final_state) store_state(final_state, cs->end);
+    if (cs) vdf_nova_circuits_free(cs);
+    if (rc != VDF_OK) { if (p) vdf_nova_proof_free(p); return rc; }
+    if (stats) {
+      stats->eval_ms = sh.eval_ms;
+      stats->after_eval_ms = t_done - sh.eval_end;
+      stats->max_backlog = max_backlog;
+      stats->steps = num_steps;
+    }
+    *out = p;
+    return VDF_OK;
+  });
+}
+
+int vdf_nova_circuits_host_bytes(const vdf_circuits* c, uint64_t* bytes) {
+  if (!c || !bytes) return fail(VDF_ERR_BAD_ARG, "null argument");
+  uint64_t n = 0;
+  for (const Circuit& k : c->v) n += k.trace_xy.size() * 32 + k.cp.size() * 96;
+  *bytes = n;
+  return VDF_OK;
 }
 
 void vdf_nova_proof_free(vdf_proof* p) {

@@ -108,7 +108,8 @@ struct vdf_pp {
   // constraints of the primary shape that read nothing of a fresh witness but that segment (and the constant): their
   // share of a step's cross term and of its commitment is made ahead of the rest, [ahead_row, ahead_row + ahead_rows)
   size_t ahead_row = 0, ahead_rows = 0;
-  int stencil_per = 0;           // 3 / 4: the early rows are the built-in MinRoot stencil with that many variables per round, checked against
+  int stencil_per = 0;           // 5 (VDF_STENCIL_FORWARD): the forward circuit's stencil (vdf_nifs_cross_term_minroot_forward);
+                                 // 3 / 4: the early rows are the built-in MinRoot stencil with that many variables per round, checked against
                                  // the shape at public_params -- their cross term needs no sparse matrix (vdf_nifs_cross_term_minroot); 0: generic rows
   int ahead_mode = 2;            // when they run: 2 = from the start of the step, beside the secondary side's NIFS; 1 = after it (tuning)
   size_t arity = 3;                        // of the primary step circuit (z0, zi)
@@ -162,7 +163,12 @@ struct WalkJob {
 struct vdf_circuits {
   std::vector<Circuit> v;
   vdf_ctx* ctx = nullptr;
-  bool checkpoints = false;                // made by vdf_nova_circuits_from_checkpoints
+  bool checkpoints = false;                // made by vdf_nova_circuits_from_checkpoints (or grown by vdf_nova_circuits_push_checkpoints)
+  // a forward chain (vdf_nova_circuits_forward_begin): circuits in the order of evaluation, appended to while the chain grows;
+  // `end` is the state the next pushed step must start from
+  bool forward = false;
+  uint64_t forward_t = 0;
+  vdfnova::St end;
   // the walks run on a side queue of the device (made by the first materialize); a job enqueued with wait = 0 is finished by
   // the next call that needs its result -- prove_step takes the circuits const, hence mutable
   mutable vdf_ctx* side = nullptr;

@@ -1,6 +1,7 @@
 // Constraint system, random oracle and gadgets of the Nova layer.  Specification: oracle/nova.py, oracle/poseidon.py
 // (see r1cs.hpp).  Host code only: O(10^4) sequential field operations per step, no kernel work.
 #include "r1cs.hpp"
+#include "../../../include/vdf_nova.h"
 
 #include <cstdio>
 #include <condition_variable>
@@ -1053,6 +1054,41 @@ std::vector<Num> InverseMinRootCircuit::synthesize(CS& cs, const std::vector<Num
 void InverseMinRootCircuit::output(const Fe* z, Fe* out) const {
   (void)z;
   out[0] = input.x; out[1] = input.y; out[2] = input.i;
+}
+
+std::vector<Num> ForwardMinRootCircuit::synthesize(CS& cs, const std::vector<Num>& z) const {
+  const Field& F = cs.F;
+  Num x = z[0], y = z[1];
+  const Num& i_in = z[2];
+  if (!cs.shape && device_rounds) {
+    // the rounds are left to the GPU (vdf_minroot_forward_segment fills them from the forward trace): the outputs are the
+    // stored state after the step
+    cs.skip(3 * t + 1, 3 * t + 1);
+    std::vector<Num> out(3);
+    out[0].v = result.x; out[1].v = result.y; out[2].v = result.i;
+    return out;
+  }
+  for (uint64_t j = 0; j < t; ++j) {
+    Fe root = vdfhost::zero();
+    if (!cs.shape) {                                                              // the hint: one host fifth root per round
+      const Fe sum = vdfhost::add(x.v, y.v, F);
+      vdf_minroot_forward_step(cs.field_id, VDF_MODE_LTR_ADDCHAIN_SEQUENTIAL, (const vdf_fe*)&sum, (vdf_fe*)&root);
+    }
+    const Num nx = cs.alloc(root);
+    const Num tmp1 = cs.mul(nx, nx);
+    const Num tmp2 = cs.mul(tmp1, tmp1);
+    cs.enforce(tmp2, nx, cs.add(x, y));
+    y = cs.add(cs.add(x, i_in), cs.constant_u64(j));
+    x = nx;
+  }
+  const Num tn = cs.constant_u64(t);
+  const Num final_i = cs.alloc(vdfhost::add(i_in.v, tn.v, F));
+  cs.enforce(final_i, cs.constant(one(F)), cs.add(i_in, tn));
+  return {x, y, final_i};
+}
+void ForwardMinRootCircuit::output(const Fe* z, Fe* out) const {
+  (void)z;
+  out[0] = result.x; out[1] = result.y; out[2] = result.i;
 }
 
 // =============================================================================================================

@@ -157,6 +157,15 @@ class MinRootVDF:                 # trait MinRootVDF<G>, src/minroot.rs:287-374
 
     simple_eval = eval
 
+    def eval_with_trace(self, x: State, t: int):
+        """(the state after t rounds, the forward trace: (x, y) of states 0..t as a (2 (t + 1), 4) uint64 array) -- the trace the
+        device kernels consume and ForwardCircuits.push_trace takes."""
+        import numpy as np
+        out = _State()
+        trace = np.zeros((2 * (t + 1), 4), dtype="<u8")
+        assert nova_lib.vdf_minroot_eval(self.FIELD, int(self.eval_mode), C.byref(x._c()), t, C.byref(out), trace.ctypes.data) == 0
+        return State._from_c(out), trace
+
     def eval_checkpoints(self, x: State, t_total: int, every: int) -> List[State]:
         """simple_eval that keeps the state after every `every` rounds, the first and the last included (what an evaluator
         hands to a prover: InverseMinRootCircuit.from_checkpoints).  ValueError unless `every` divides t_total."""

@@ -42,6 +42,11 @@ for _name, _res, _args in [
     ("vdf_nova_circuits_release", _i, [_vp, _sz, _sz]),
     ("vdf_nova_circuits_memory", _i, [_vp, C.POINTER(_sz), C.POINTER(_u64)]),
     ("vdf_nova_circuit_trace", _i, [_vp, _sz, C.POINTER(_vp)]),
+    ("vdf_nova_circuits_host_bytes", _i, [_vp, C.POINTER(_u64)]),
+    ("vdf_nova_circuits_forward_begin", _i, [_u64, C.POINTER(_State), C.POINTER(_Fe * 3), C.POINTER(_vp)]),
+    ("vdf_nova_circuits_push_trace", _i, [_vp, _vp]),
+    ("vdf_nova_circuits_push_checkpoints", _i, [_vp, _u64, _vp]),
+    ("vdf_nova_eval_and_prove", _i, [_vp, _i, C.POINTER(_State), _sz, C.POINTER(_State), C.POINTER(_vp), _vp]),
     ("vdf_nova_prove_recursively_windowed", _i, [_vp, _vp, _u64, C.POINTER(_Fe * 3), _sz, C.POINTER(_vp)]),
     ("vdf_nova_circuits_len", _sz, [_vp]),
     ("vdf_nova_circuits_upload", _i, [_vp, _vp]),
@@ -101,6 +106,8 @@ for _name, _res, _args in [
     getattr(nova_lib, _name).restype = _res
 
 CIRCUIT_MINROOT_BOUND, CIRCUIT_MINROOT_REFERENCE = 0, 1
+CIRCUIT_MINROOT_FORWARD = 3       # the step in the direction of evaluation (include/vdf_nova.h)
+STENCIL_FORWARD = 5               # vdf_nova_pp_stencil's code for the forward circuit's stencil
 SIDE_PRIMARY, SIDE_SECONDARY = 0, 1
 INST_RUNNING_PRIMARY, INST_RUNNING_SECONDARY, INST_FRESH_SECONDARY, INST_FRESH_PRIMARY_LAST = 0, 1, 2, 3
 GENS_KNOWN_DLOG, GENS_TRY_AND_INCREMENT, GENS_LABEL_SHAKE = 0, 1, 2
@@ -373,7 +380,8 @@ class NovaVDFPublicParams:        # src/nova/proof.rs:38-43
         return b.value, n.value
 
     def stencil(self) -> int:
-        """4 / 3: the early rows run as the MinRoot stencil (reference / bound rounds), 0: through the sparse kernel."""
+        """4 / 3: the early rows run as the MinRoot stencil (reference / bound rounds), 5: as the forward circuit's stencil,
+        0: through the sparse kernel."""
         return int(nova_lib.vdf_nova_pp_stencil(self.handle))
 
     def ro(self) -> dict:
@@ -481,6 +489,12 @@ class Circuits:
         _check(nova_lib.vdf_nova_circuits_memory(self.handle, C.byref(n), C.byref(b)))
         return n.value, b.value
 
+    def host_bytes(self) -> int:
+        """bytes of host memory held in traces and checkpoints"""
+        b = C.c_uint64(0)
+        _check(nova_lib.vdf_nova_circuits_host_bytes(self.handle, C.byref(b)))
+        return b.value
+
     def trace_ptr(self, k: int) -> Optional[int]:
         """device address of circuit k's trace (2 (t + 1) elements), None without one"""
         p = C.c_void_p()
@@ -535,6 +549,41 @@ class InverseMinRootCircuit:      # src/nova/proof.rs:57-66, :239-299
         return [bytes(z0[k]) for k in range(3)], Circuits(h.value, t)
 
 
+class ForwardCircuits(Circuits):
+    """A chain of forward step circuits (CIRCUIT_MINROOT_FORWARD) that grows while the chain is evaluated: circuit k is the
+    k-th step pushed.  Push and release between prove_steps, never during one (include/vdf_nova.h)."""
+
+    @staticmethod
+    def begin(t: int, initial_state: State) -> Tuple[List[bytes], "ForwardCircuits"]:
+        """(z0 = the initial state, an empty chain)"""
+        z0 = (_Fe * 3)()
+        h = C.c_void_p()
+        _check(nova_lib.vdf_nova_circuits_forward_begin(t, C.byref(initial_state._c()), C.byref(z0), C.byref(h)))
+        return [bytes(z0[k]) for k in range(3)], ForwardCircuits(h.value, t)
+
+    def push_trace(self, trace_xy: np.ndarray) -> None:
+        """Appends a step from its host trace, (x, y) of states 0..t as MinRootVDF.eval_with_trace returns it."""
+        tr = np.ascontiguousarray(trace_xy, dtype="<u8").reshape(-1, 4)
+        if tr.shape[0] != 2 * (self.t + 1):
+            raise ValueError("2 (t + 1) elements expected")
+        _check(nova_lib.vdf_nova_circuits_push_trace(self.handle, tr.ctypes.data))
+
+    def push_checkpoints(self, every: int, states: Sequence[State]) -> None:
+        """Appends a step from its t // every + 1 states every `every` rounds; materialize rebuilds its trace on the GPU."""
+        if every > 0 and self.t % every == 0 and len(states) != self.t // every + 1:
+            raise ValueError("t // every + 1 states expected")
+        raw = b"".join(s.x + s.y + s.i for s in states)
+        buf = (C.c_char * max(len(raw), 1)).from_buffer_copy(raw or b"\0")
+        _check(nova_lib.vdf_nova_circuits_push_checkpoints(self.handle, every, buf))
+
+
+class StreamStats(C.Structure):   # vdf_nova_stream_stats
+    _fields_ = [("eval_ms", C.c_double), ("after_eval_ms", C.c_double), ("max_backlog", C.c_uint64), ("steps", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class NovaVDFProof:               # enum NovaVDFProof { Recursive, Compressed }, :51-55
     def __init__(self, handle: int, pp: NovaVDFPublicParams):
         self.handle, self.pp = handle, pp
@@ -552,6 +601,16 @@ class NovaVDFProof:               # enum NovaVDFProof { Recursive, Compressed },
             _check(nova_lib.vdf_nova_prove_recursively_windowed(pp.handle, circuits.handle, num_iters_per_step, C.byref(_z(z0)),
                                                                 window_steps, C.byref(h)))
         return NovaVDFProof(h.value, pp)
+
+    @staticmethod
+    def eval_and_prove(pp: NovaVDFPublicParams, v: MinRootVDF, initial_state: State, num_steps: int) -> Tuple["NovaVDFProof", State, dict]:
+        """Evaluates num_steps steps from initial_state on a library thread and proves every step as it arrives (forward
+        parameters): (the running proof of z0 = initial, zi = final; the final state; vdf_nova_stream_stats as a dict)."""
+        h = C.c_void_p()
+        fin, st = _State(), StreamStats()
+        _check(nova_lib.vdf_nova_eval_and_prove(pp.handle, int(v.eval_mode), C.byref(initial_state._c()), num_steps, C.byref(fin),
+                                                C.byref(h), C.addressof(st)))
+        return NovaVDFProof(h.value, pp), State._from_c(fin), st.as_dict()
 
     @staticmethod
     def prove_step(pp: NovaVDFPublicParams, proof: "NovaVDFProof | None", circuits: Circuits, k: int,
