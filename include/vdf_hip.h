@@ -302,6 +302,35 @@ int  vdf_minroot_check_batch(vdf_ctx* ctx, int field, const vdf_state* results, 
 int  vdf_minroot_trace_heads(vdf_ctx* ctx, const vdf_state* states, size_t n, size_t state_stride, vdf_fe* trace_xy,
                              size_t trace_stride);
 
+/* ---- MinRoot forward walks: many chains evaluated at once ---------------------------------------------------------------
+ * The forward round (src/minroot.rs:329-335) (x, y, i) -> ((x + y)^e, x + i, i + 1) is 253 squarings and 30 products (Fp: 29) that
+ * each wait for the one before.  A chain is sequential; chains are independent: one lane per chain.  This is a THROUGHPUT feature for
+ * many chains (beacon lanes, sequential-work farms, test and benchmark corpora), NOT a faster VDF: a single chain on a lane is
+ * far slower than vdf_minroot_eval on a host core (README.md has the measured ratio).
+ *
+ * n independent walks of `rounds` forward rounds, at most VDF_MINROOT_FORWARD_MAX_ROUNDS per call (VDF_ERR_BAD_ARG above it: a
+ * round takes tens of microseconds and a launch must not hold a queue for seconds).  states: n states in DEVICE memory, read as
+ * where each walk stands and overwritten with where it stands afterwards, so a long walk is cut into calls.  `base` = the rounds
+ * the walks have behind them; with g = base + r + 1 the count after round r (r = 0 .. rounds - 1), walk w writes
+ *   trace_xy[2 * (w * walk_stride + g)] = (x, y) after the round              (device, or NULL; walk_stride in entries of 64 B),
+ *   checkpoints[w * cp_stride + g / every] = the state, when `every` divides g  (device, or NULL; cp_stride in states)
+ * -- the ascending counterpart of vdf_minroot_inverse_walk's layout.  Entry 0 / checkpoint 0 (the state a walk starts from) is
+ * the caller's to write.  The caller sizes both arrays.  The trace (64 B per round and chain) serves short walks and tests;
+ * checkpoints are the interface to the prover (vdf_nova.h vdf_nova_circuits_push_checkpoints / _from_checkpoints, which rebuild
+ * a step's trace by inverse walks at ~2 % of the evaluation's cost).  n = 0 or rounds = 0 do nothing.
+ * Exact: states, checkpoints and trace entries are byte for byte what vdf_minroot_round gives (vdf_nova.h), in any mode. */
+#define VDF_MINROOT_FORWARD_MAX_ROUNDS 2048
+int  vdf_minroot_forward_walk(vdf_ctx* ctx, int field, vdf_state* states, size_t n, uint64_t rounds, vdf_state* checkpoints,
+                              uint64_t every, size_t cp_stride, vdf_fe* trace_xy, size_t walk_stride, uint64_t base);
+/* vdf_minroot_eval_checkpoints (vdf_nova.h) for n chains at once: rounds_total forward rounds from initial[w], cut into launches
+ * of launch_rounds (0 = 1,024; at most VDF_MINROOT_FORWARD_MAX_ROUNDS) enqueued on the context's stream.  every = 0:
+ * out_states[w] = the final state of chain w (n states).  every > 0 (it must divide rounds_total, VDF_ERR_BAD_ARG otherwise):
+ * out_states[w * (rounds_total / every + 1) + k] = chain w after k * every rounds, k = 0 (the initial state) .. rounds_total /
+ * every -- per chain exactly the array vdf_minroot_eval_checkpoints writes, and what vdf_nova_circuits_push_checkpoints /
+ * _from_checkpoints take.  initial / out_states: host or device (a device `initial` is left as it was; they may not overlap). */
+int  vdf_minroot_eval_batch(vdf_ctx* ctx, int field, const vdf_state* initial, size_t n, uint64_t rounds_total, uint64_t every,
+                            uint64_t launch_rounds, vdf_state* out_states);
+
 /* ---- fused step operations (one kernel launch each) --------------------------------------- */
 /* The three entry points below do what a sequence of the calls above does, in a single launch and with
  * every single-field-element operand read from HOST memory and passed as a kernel argument: no staging

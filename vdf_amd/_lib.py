@@ -19,6 +19,7 @@ VDF_OK, VDF_ERR_BAD_ARG, VDF_ERR_BAD_LENGTH, VDF_ERR_NONCANONICAL, VDF_ERR_DEVIC
 CURVE_PALLAS, CURVE_VESTA = 0, 1
 FIELD_FP, FIELD_FQ = 0, 1
 GENS_KNOWN_DLOG, GENS_TRY_AND_INCREMENT = 0, 1
+MINROOT_FORWARD_MAX_ROUNDS = 2048          # VDF_MINROOT_FORWARD_MAX_ROUNDS
 
 # every symbol include/vdf_hip.h declares: (name, restype, argtypes)
 _vp, _sz, _i, _u64 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint64
@@ -88,6 +89,8 @@ PROTOTYPES = {
     "vdf_minroot_inverse_walk": (_i, [_vp, _i, _vp, _sz, _u64, _vp, _sz, _sz, _sz, _sz]),
     "vdf_minroot_check_batch": (_i, [_vp, _i, _vp, _vp, _sz, _u64, _vp]),
     "vdf_minroot_trace_heads": (_i, [_vp, _vp, _sz, _sz, _vp, _sz]),
+    "vdf_minroot_forward_walk": (_i, [_vp, _i, _vp, _sz, _u64, _vp, _u64, _sz, _vp, _sz, _u64]),
+    "vdf_minroot_eval_batch": (_i, [_vp, _i, _vp, _sz, _u64, _u64, _u64, _vp]),
     "vdf_vec_is_zero": (_i, [_vp, _vp, _sz, C.POINTER(C.c_int)]),
     "vdf_nifs_cross_term": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdf_nifs_cross_term_rows": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -2056,6 +2056,54 @@ int vdf_minroot_check_batch(vdf_ctx* ctx, int field, const vdf_state* results, c
   });
 }
 
+// ---- MinRoot forward walks (minroot.hip) --------------------------------------------------------
+int vdf_minroot_forward_walk(vdf_ctx* ctx, int field, vdf_state* states, size_t n, uint64_t rounds, vdf_state* checkpoints,
+                             uint64_t every, size_t cp_stride, vdf_fe* trace_xy, size_t walk_stride, uint64_t base) {
+  return guarded(ctx, [&]() -> Status {
+    VDF_TRY(vdf::check_field(field));
+    if (rounds > VDF_MINROOT_FORWARD_MAX_ROUNDS) return Status{VDF_ERR_BAD_ARG, "more than VDF_MINROOT_FORWARD_MAX_ROUNDS rounds in one call: cut the walk"};
+    if (n > ((size_t)1 << 31)) return Status{VDF_ERR_BAD_LENGTH, "more than 2^31 walks"};
+    if (n == 0 || rounds == 0) return Status{};
+    if (!ptr_is_device(states)) return Status{VDF_ERR_BAD_ARG, "states must be in device memory"};
+    if (checkpoints && !ptr_is_device(checkpoints)) return Status{VDF_ERR_BAD_ARG, "checkpoints must be in device memory (or NULL)"};
+    if (trace_xy && !ptr_is_device(trace_xy)) return Status{VDF_ERR_BAD_ARG, "trace_xy must be in device memory (or NULL)"};
+    VDF_TRY(vdf::minroot_forward_walk(field, states, n, rounds, checkpoints, every, cp_stride, trace_xy, walk_stride, base, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
+int vdf_minroot_eval_batch(vdf_ctx* ctx, int field, const vdf_state* initial, size_t n, uint64_t rounds_total, uint64_t every,
+                           uint64_t launch_rounds, vdf_state* out_states) {
+  return guarded(ctx, [&]() -> Status {
+    VDF_TRY(vdf::check_field(field));
+    if (every && rounds_total % every != 0) return Status{VDF_ERR_BAD_ARG, "`every` must divide rounds_total"};
+    if (launch_rounds == 0) launch_rounds = 1024;
+    if (launch_rounds > VDF_MINROOT_FORWARD_MAX_ROUNDS) return Status{VDF_ERR_BAD_ARG, "launch_rounds above VDF_MINROOT_FORWARD_MAX_ROUNDS"};
+    if (n > ((size_t)1 << 31)) return Status{VDF_ERR_BAD_LENGTH, "more than 2^31 chains"};
+    if (n == 0) return Status{};
+    const size_t per = every ? (size_t)(rounds_total / every) + 1 : 1;           // states per chain in out_states
+    if (per > SIZE_MAX / sizeof(vdf_state) / n) return Status{VDF_ERR_BAD_LENGTH, "out_states would not fit the address space"};
+    Staging st(ctx);
+    const void* dinit; void* dout;
+    VDF_TRY(st.in(initial, n * sizeof(vdf_state), &dinit));
+    VDF_TRY(st.out(out_states, n * per * sizeof(vdf_state), &dout));
+    void* walk = dout;                                         // every = 0: the walks run in the output itself
+    if (every) {
+      VDF_TRY(st.temp(n * sizeof(vdf_state), &walk));
+      VDF_TRY_HIP(hipMemcpy2DAsync(dout, per * sizeof(vdf_state), dinit, sizeof(vdf_state), sizeof(vdf_state), n, hipMemcpyDeviceToDevice,
+                                   ctx->stream));              // checkpoint 0 of every chain
+    }
+    VDF_TRY_HIP(hipMemcpyAsync(walk, dinit, n * sizeof(vdf_state), hipMemcpyDeviceToDevice, ctx->stream));
+    for (uint64_t done = 0; done < rounds_total;) {
+      const uint64_t now = std::min<uint64_t>(rounds_total - done, launch_rounds);
+      VDF_TRY(vdf::minroot_forward_walk(field, walk, n, now, every ? dout : nullptr, every, per, nullptr, 0, done, ctx->stream));
+      done += now;
+    }
+    return st.finish();
+  });
+}
+
 int vdf_minroot_trace_heads(vdf_ctx* ctx, const vdf_state* states, size_t n, size_t state_stride, vdf_fe* trace_xy,
                             size_t trace_stride) {
   return guarded(ctx, [&]() -> Status {

@@ -1,6 +1,7 @@
 // libvdf_nova.so, part 1: the reference's `minroot` module (src/minroot.rs) -- the forward (slow) and inverse
 // (fast) MinRoot rounds, the four forward-step chains, eval / check -- on the host, where the reference keeps them.
 #include "nova_internal.hpp"
+#include "../minroot_chain.h"
 
 using namespace vdfnova;
 
@@ -9,36 +10,32 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // MinRoot (src/minroot.rs)
 // ---------------------------------------------------------------------------------------------
-const uint64_t FP_RESCUE_INVALPHA[4] = {0xe0f0f3f0cccccccdull, 0x4e9ee0c9a10a60e2ull, 0x3333333333333333ull,
-                                        0x3333333333333333ull};   // src/minroot.rs:273-278
-const uint64_t FQ_RESCUE_INVALPHA[4] = {0xd69f2280cccccccdull, 0x4e9ee0c9a143ba4aull, 0x3333333333333333ull,
-                                        0x3333333333333333ull};   // src/minroot.rs:280-285
+// the two exponents and the two addition chains: minroot_chain.h, shared with the device's forward walk (minroot.hip)
+using vdf::FP_RESCUE_INVALPHA;
+using vdf::FQ_RESCUE_INVALPHA;
 
 // The chains run in the lazy domain [0, 2m) and canonicalise once, at the end (host_math.hpp).
 inline Fe lmul(const Fe& a, const Fe& b, const Field& F) { return mul<true>(a, b, F); }
 inline Fe lsqr(const Fe& a, const Field& F) { return sqr<true>(a, F); }
 
-struct Chain {   // the closures of src/minroot.rs:89-92 / :224-227
-  const Field& F;
-  Fe sq(Fe x, int n) const { for (int i = 0; i < n; ++i) x = lsqr(x, F); return x; }
-  Fe sqr_mul(const Fe& x, int n, const Fe& y) const { return lmul(y, sq(x, n), F); }
-};
-
-// PallasVDF::forward_step_ltr_addition_chain, src/minroot.rs:88-127
-Fe fwd_ltr_addchain_fq(const Fe& x) {
-  const Field& F = field_fq();
-  Chain c{F};
-  Fe q1 = x, q10 = c.sq(q1, 1), q11 = lmul(q10, q1, F), q101 = lmul(q10, q11, F), q110 = c.sq(q11, 1);
-  Fe q111 = lmul(q110, q1, F), q1001 = lmul(q111, q10, F), q1111 = lmul(q1001, q110, F);
-  Fe qr2 = c.sqr_mul(q110, 3, q11), qr4 = c.sqr_mul(qr2, 8, qr2), qr8 = c.sqr_mul(qr4, 16, qr4);
-  Fe qr16 = c.sqr_mul(qr8, 32, qr8), qr32 = c.sqr_mul(qr16, 64, qr16);
-  Fe v = c.sqr_mul(qr32, 5, q1001);
-  struct { int n; const Fe* y; } steps[] = {{8, &q111}, {4, &q1}, {2, &qr4}, {7, &q11}, {6, &q1001}, {3, &q101},
-      {7, &q101}, {7, &q111}, {4, &q111}, {5, &q1001}, {5, &q101}, {3, &q11}, {4, &q101}, {3, &q101}, {6, &q1111},
-      {4, &q1001}, {6, &q101}, {37, &qr8}, {2, &q1}};
-  for (auto& s : steps) v = c.sqr_mul(v, s.n, *s.y);
+// One chain of minroot_chain.h: v = slot[src]; v = v^(2^squarings); v = v * slot[mul]; slot[dst] = v, step by step (the closures of
+// src/minroot.rs:89-92 / :224-227 are a step with both a squaring run and a product)
+Fe run_chain(const vdf::MinrootChainProgram& prog, const Fe& x, const Field& F) {
+  Fe slot[vdf::MR_SLOTS];
+  slot[vdf::MR_S1] = x;
+  Fe v = x;
+  for (uint32_t k = 0; k < prog.len; ++k) {
+    const vdf::MinrootChainStep& s = prog.step[k];
+    if (s.src != vdf::MR_ACC) v = slot[s.src];
+    for (int i = 0; i < s.squarings; ++i) v = lsqr(v, F);
+    if (s.mul != vdf::MR_NONE) v = lmul(slot[s.mul], v, F);
+    if (s.dst != vdf::MR_NONE) slot[s.dst] = v;
+  }
   return canon(v, F);
 }
+
+// PallasVDF::forward_step_ltr_addition_chain, src/minroot.rs:88-127
+Fe fwd_ltr_addchain_fq(const Fe& x) { return run_chain(vdf::MINROOT_CHAIN_FQ, x, field_fq()); }
 // PallasVDF::forward_step_rtl_sequential, src/minroot.rs:130-151
 Fe fwd_rtl_fq(const Fe& x) {
   const Field& F = field_fq();
@@ -68,20 +65,7 @@ Fe fwd_rtl_addchain_fq(const Fe& x) {
   return canon(acc, F);
 }
 // VestaVDF::forward_step, src/minroot.rs:223-261
-Fe fwd_addchain_fp(const Fe& x) {
-  const Field& F = field_fp();
-  Chain c{F};
-  Fe p1 = x, p10 = c.sq(p1, 1), p11 = lmul(p10, p1, F), p101 = lmul(p10, p11, F), p110 = c.sq(p11, 1);
-  Fe p111 = lmul(p110, p1, F), p1001 = lmul(p111, p10, F), p1111 = lmul(p1001, p110, F);
-  Fe pr2 = c.sqr_mul(p110, 3, p11), pr4 = c.sqr_mul(pr2, 8, pr2), pr8 = c.sqr_mul(pr4, 16, pr4);
-  Fe pr16 = c.sqr_mul(pr8, 32, pr8), pr32 = c.sqr_mul(pr16, 64, pr16);
-  Fe v = c.sqr_mul(pr32, 5, p1001);
-  struct { int n; const Fe* y; } steps[] = {{8, &p111}, {4, &p1}, {2, &pr4}, {7, &p11}, {6, &p1001}, {3, &p101},
-      {5, &p1}, {7, &p101}, {4, &p11}, {8, &p111}, {4, &p1}, {4, &p111}, {9, &p1111}, {8, &p1111}, {6, &p1111},
-      {2, &p11}, {34, &pr8}, {2, &p1}};
-  for (auto& s : steps) v = c.sqr_mul(v, s.n, *s.y);
-  return canon(v, F);
-}
+Fe fwd_addchain_fp(const Fe& x) { return run_chain(vdf::MINROOT_CHAIN_FP, x, field_fp()); }
 
 // dispatch of src/minroot.rs:77-84; VestaVDF ignores the mode (:203-205)
 Fe forward_step(int field_id, int mode, const Fe& x) {

@@ -361,6 +361,11 @@ Status vec_clock_probe(int iters, int workgroups, unsigned long long* d_out3, hi
 constexpr uint64_t MINROOT_WALK_MAX_ROUNDS = 1ull << 22;
 Status minroot_inverse_walk(int field, void* states, size_t n, uint64_t rounds, void* trace, size_t walk_stride, size_t top,
                             size_t group, size_t group_stride, hipStream_t s);
+// n walks of `rounds` FORWARD rounds (at most VDF_MINROOT_FORWARD_MAX_ROUNDS) in place over `states`; `base` = the rounds a walk has behind
+// it: after round r walk w writes (x, y) to trace entry w * walk_stride + base + r + 1 (trace: device or null) and, when `every`
+// divides g = base + r + 1, its state to checkpoints[w * cp_stride + g / every] (checkpoints: device or null)
+Status minroot_forward_walk(int field, void* states, size_t n, uint64_t rounds, void* checkpoints, uint64_t every, size_t cp_stride,
+                            void* trace, size_t walk_stride, uint64_t base, hipStream_t s);
 Status minroot_states_match(const void* a, const void* b, size_t n, int* ok, hipStream_t s);      // ok[w] = (a[w] == b[w]), 96 B each
 Status minroot_trace_heads(const void* states, size_t n, size_t state_stride, void* trace, size_t trace_stride, hipStream_t s);
 

@@ -432,6 +432,19 @@ class Context:
     def minroot_trace_heads(self, states, n, state_stride, trace_xy, trace_stride) -> None:
         self._check(lib.vdf_minroot_trace_heads(self.handle, _ptr(states), n, state_stride, _ptr(trace_xy), trace_stride))
 
+    def minroot_forward_walk(self, field, states, n, rounds, checkpoints=None, every=0, cp_stride=0, trace_xy=None, walk_stride=0,
+                             base=0) -> None:
+        """n forward walks of `rounds` rounds (at most _lib.MINROOT_FORWARD_MAX_ROUNDS) in place over `states` (device, 96 B each).
+        With g = base + r + 1 after round r, walk w writes (x, y) to trace entry w * walk_stride + g and, when `every` divides g,
+        its state to checkpoints[w * cp_stride + g // every] (device or None).  Many chains at once: throughput, not latency."""
+        self._check(lib.vdf_minroot_forward_walk(self.handle, field, _ptr(states), n, rounds, _ptr(checkpoints), every, cp_stride,
+                                                 _ptr(trace_xy), walk_stride, base))
+
+    def minroot_eval_batch(self, field, initial, n, rounds_total, out_states, every=0, launch_rounds=0) -> None:
+        """vdf_minroot_eval_checkpoints for n chains: out_states[w] = the final state (every = 0), or the rounds_total // every + 1
+        states of chain w every `every` rounds, the initial one included; host or device buffers."""
+        self._check(lib.vdf_minroot_eval_batch(self.handle, field, _ptr(initial), n, rounds_total, every, launch_rounds, _ptr(out_states)))
+
     def gate_accumulate(self, other: "Context", slot: int) -> None:
         """The next bucket-method MSM on this context accumulates only after `other`'s mark `slot` (vdf_ctx_gate_accumulate)."""
         self._check(lib.vdf_ctx_gate_accumulate(self.handle, other.handle, slot))

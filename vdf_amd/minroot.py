@@ -205,6 +205,25 @@ class MinRootVDF:                 # trait MinRootVDF<G>, src/minroot.rs:287-374
         ctx.minroot_check_batch(cls.FIELD, res, org, n, t, ok)
         return [bool(v) for v in ok]
 
+    @classmethod
+    def eval_batch(cls, ctx, states, t: int, every: int = 0):
+        """eval (:348-359) for many initial states at once, on the GPU of `ctx` (vdf_amd.hip.Context): one lane per chain.
+        every = 0: [the state of chain w after t rounds]; every > 0 (it must divide t): per chain what eval_checkpoints returns,
+        [[the t // every + 1 states of chain w]].  For MANY chains -- a lone chain is far slower here than eval on the host."""
+        import numpy as np
+        n = len(states)
+        if every < 0 or (every and t % every):
+            raise ValueError("`every` must divide t")
+        if n == 0:
+            return []
+        per = t // every + 1 if every else 1
+        init = np.frombuffer(b"".join(s.x + s.y + s.i for s in states), dtype="<u8").copy()
+        out = np.zeros(n * per * 12, dtype="<u8")
+        ctx.minroot_eval_batch(cls.FIELD, init, n, t, out, every=every)
+        raw = out.tobytes()
+        flat = [State(raw[96 * k:96 * k + 32], raw[96 * k + 32:96 * k + 64], raw[96 * k + 64:96 * k + 96]) for k in range(n * per)]
+        return flat if not every else [flat[w * per:(w + 1) * per] for w in range(n)]
+
 
 class PallasVDF(MinRootVDF):      # src/minroot.rs:38-197: modulus of Fq (scalar field of Pallas)
     FIELD = FIELD_FQ
