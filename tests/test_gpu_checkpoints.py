@@ -10,48 +10,16 @@ import numpy as np
 import pytest
 
 from oracle import pasta as o
+from util import dev, dev_read, host, host_trace, mont_states, states_array
 from vdf_amd._lib import lib
 from vdf_amd.hip import VdfError
-from vdf_amd.minroot import EvalMode, PallasVDF, State, VestaVDF, FIELD_FP, FIELD_FQ, _State, nova_lib
+from vdf_amd.minroot import EvalMode, PallasVDF, State, VestaVDF, FIELD_FP, FIELD_FQ, nova_lib
 from vdf_amd.nova import (CIRCUIT_MINROOT_BOUND, CIRCUIT_MINROOT_REFERENCE, InverseMinRootCircuit, NovaVDFProof, public_params)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAST = EvalMode.LTRAddChainSequential
 FILL = 0xA5
-
-
-def dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.int64)).cuda()
-
-
-def host(tensor):
-    return tensor.cpu().numpy().view("<u8")
-
-
-def dev_read(ctx, ptr, nbytes):
-    out = np.zeros(nbytes // 8, dtype="<u8")
-    assert lib.vdf_dev_memcpy(ctx.handle, out.ctypes.data, ptr, nbytes) == 0
-    return out
-
-
-def states_array(states):
-    """[State] -> uint64[n, 12]"""
-    return np.frombuffer(b"".join(s.x + s.y + s.i for s in states), dtype="<u8").reshape(-1, 12).copy()
-
-
-def mont_states(rows, m):
-    """[(x, y, i) ints] -> uint64[n, 12] Montgomery"""
-    return np.frombuffer(b"".join(int(o.to_mont(v, m)).to_bytes(32, "little") for r in rows for v in r), dtype="<u8").reshape(-1, 12).copy()
-
-
-def host_trace(vdf, s0, t):
-    """(result, uint64[t + 1, 8]) of vdf_minroot_eval with its trace"""
-    buf = np.zeros((t + 1, 8), dtype="<u8")
-    out = _State()
-    assert nova_lib.vdf_minroot_eval(vdf.FIELD, int(vdf.eval_mode), C.byref(s0._c()), t, C.byref(out), buf.ctypes.data) == 0
-    return State._from_c(out), buf
 
 
 # ---- the kernel against the oracle -------------------------------------------------------------------------------
@@ -377,6 +345,35 @@ def test_misuse(ctx):
     with pytest.raises(VdfError):
         full.materialize(ctx)
     proof.free(); full.free(); cc.free(); pp.free()
+
+
+def test_uploaded_traces_stay_through_release(ctx):
+    """Circuits that carry host traces: upload gives every circuit a device trace of its own, release lets go of walked traces
+    only and so leaves these where they are, and free takes them with the handle.  Every comparison is exact."""
+    t, n = 4, 2
+    per = (t + 1) * 64
+    vdf = PallasVDF.new()
+    initial = chain(t, n, seed=13)
+    traces, s = [], initial
+    for _ in range(n):
+        s, tr = host_trace(vdf, s, t)
+        traces.append(tr)
+    _z0, circuits = InverseMinRootCircuit.eval_and_make_circuits(vdf, t, n, initial)
+    circuits.upload(ctx)
+    assert circuits.memory() == (2, 2 * 5 * 64)
+    ptrs = [circuits.trace_ptr(k) for k in range(n)]
+    assert all(ptrs) and ptrs[0] != ptrs[1]
+    circuits.release(0, 2)
+    assert circuits.memory() == (2, 2 * 5 * 64) and [circuits.trace_ptr(k) for k in range(n)] == ptrs
+    for k in range(n):                                                 # circuit k is forward step n - 1 - k
+        assert np.array_equal(dev_read(ctx, ptrs[k], per).reshape(t + 1, 8), traces[n - 1 - k])
+    circuits.upload(ctx)
+    assert circuits.memory() == (2, 2 * 5 * 64) and [circuits.trace_ptr(k) for k in range(n)] == ptrs
+    circuits.free()
+    _z0, again = InverseMinRootCircuit.eval_and_make_circuits(vdf, t, n, initial)
+    again.upload(ctx)
+    assert again.memory() == (2, 2 * 5 * 64)
+    again.free()
 
 
 def test_a_window_that_cannot_fit(ctx):

@@ -16,7 +16,7 @@ import vdf_amd
 from oracle import nova as nv, pasta as o
 from forward_spec import ForwardMinRootCircuit, chain, oracle_pp
 from test_gpu_nova import aff_ints, check_instance, _canon
-from util import limbs, mont, unmont, rand_limbs
+from util import dev, host, limbs, mont, unmont, rand_limbs
 from vdf_amd._lib import lib
 from vdf_amd.hip import VdfError
 from vdf_amd.minroot import EvalMode, PallasVDF, State, FIELD_FQ
@@ -29,15 +29,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAST = EvalMode.LTRAddChainSequential
 FILL = np.uint64(0xA5A5A5A5A5A5A5A5)
-
-
-def dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.int64)).cuda()
-
-
-def host(tensor):
-    return tensor.cpu().numpy().view("<u8")
 
 
 def zvec(s):

@@ -14,6 +14,7 @@ import pytest
 
 import vdf_amd
 from oracle import pasta as o
+from util import dev, host
 from vdf_amd import _lib
 from vdf_amd._lib import lib
 from vdf_amd.hip import VdfError
@@ -26,15 +27,6 @@ FAST = EvalMode.LTRAddChainSequential
 FILL = np.uint64(0xA5A5A5A5A5A5A5A5)
 CAP = _lib.MINROOT_FORWARD_MAX_ROUNDS
 POOL = ThreadPoolExecutor(max_workers=16)                  # the host evaluator releases the GIL (ctypes)
-
-
-def dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.int64)).cuda()
-
-
-def host(tensor):
-    return tensor.cpu().numpy().view("<u8")
 
 
 def vdf_of(field):

@@ -51,3 +51,41 @@ def rand_limbs(rng, n, top_mask=0x3FFFFFFFFFFFFFFF):
 
 def hexes(lst):
     return [int(h, 16) for h in lst]
+
+
+# ---- device buffers and MinRoot states (the GPU tests; torch and the libraries are imported where they are used) ------------
+
+def dev(x):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(x).view(np.int64)).cuda()
+
+
+def host(tensor):
+    return tensor.cpu().numpy().view("<u8")
+
+
+def dev_read(ctx, ptr, nbytes):
+    from vdf_amd._lib import lib
+    out = np.zeros(nbytes // 8, dtype="<u8")
+    assert lib.vdf_dev_memcpy(ctx.handle, out.ctypes.data, ptr, nbytes) == 0
+    return out
+
+
+def states_array(states):
+    """[State] -> uint64[n, 12]"""
+    return np.frombuffer(b"".join(s.x + s.y + s.i for s in states), dtype="<u8").reshape(-1, 12).copy()
+
+
+def mont_states(rows, m):
+    """[(x, y, i) ints] -> uint64[n, 12] Montgomery"""
+    return np.frombuffer(b"".join(int(o.to_mont(v, m)).to_bytes(32, "little") for r in rows for v in r), dtype="<u8").reshape(-1, 12).copy()
+
+
+def host_trace(vdf, s0, t):
+    """(result, uint64[t + 1, 8]) of vdf_minroot_eval with its trace"""
+    import ctypes as C
+    from vdf_amd.minroot import State, _State, nova_lib
+    buf = np.zeros((t + 1, 8), dtype="<u8")
+    out = _State()
+    assert nova_lib.vdf_minroot_eval(vdf.FIELD, int(vdf.eval_mode), C.byref(s0._c()), t, C.byref(out), buf.ctypes.data) == 0
+    return State._from_c(out), buf

@@ -1,0 +1,380 @@
+// libvdf_nova.so, part 2b: the circuits handle of the Nova surface (vdf_circuits; src/nova/proof.rs:57-66, :268-294) -- the steps
+// of a chain as prove_step reads them, made from an evaluation, from a chain's checkpoints or pushed while the chain grows, and
+// the device traces behind them: copied from the host, or rebuilt from checkpoints by inverse walks on a side queue.
+#include "nova_internal.hpp"
+
+using namespace vdfnova;
+
+namespace {
+// states[1 .. n] count on from states[0], whose i is `from`, in steps of `every`
+int check_counters(const vdf_state* states, size_t n, Fe from, uint64_t every) {
+  const Field& F = field(VDF_FIELD_FQ);
+  const Fe step = from_u64(every, F);
+  for (size_t k = 1; k <= n; ++k) {
+    from = add(from, step, F);
+    if (memcmp(&states[k].i, &from, 32) != 0)
+      return fail(VDF_ERR_BAD_ARG, "checkpoint " + std::to_string(k) + ": i is not states[0].i + " + std::to_string(k) + " * every");
+  }
+  return VDF_OK;
+}
+// the step whose states every `every` rounds are states[0 .. per]
+Circuit checkpoint_circuit(uint64_t t, uint64_t every, const vdf_state* states, size_t per) {
+  Circuit c;
+  c.t = t; c.every = every;
+  c.cp.resize(per + 1);
+  for (size_t m = 0; m <= per; ++m) c.cp[m] = load_state(&states[m]);
+  c.input = c.cp.front(); c.result = c.cp.back();
+  return c;
+}
+// ---- checkpoint circuits: traces by inverse walks ----------------------------------------------------------------
+// rounds per launch of the walks: a launch of 1,024 rounds holds a queue for about a millisecond
+uint64_t walk_launch_rounds() {
+  static const uint64_t v = [] {
+    const char* e = getenv("VDF_NOVA_WALK_LAUNCH");
+    const long n = e && *e ? atol(e) : 0;
+    return (uint64_t)(n >= 1 && n <= (1 << 22) ? n : 1024);
+  }();
+  return v;
+}
+// the one cast (WalkState, nova_internal.hpp): walks resolved, begun or parked under a const handle write d_trace and block of v[k]
+vdf_circuits* written(const vdf_circuits* c) { return const_cast<vdf_circuits*>(c); }
+void scratch_free(WalkState& w) {
+  if (w.d_walk) vdf_dev_free(w.side, w.d_walk);
+  if (w.d_expect) vdf_dev_free(w.side, w.d_expect);
+  if (w.h_ok) vdf_host_free(w.side, w.h_ok);
+  w.d_walk = w.d_expect = nullptr; w.h_ok = nullptr;
+  w.scratch_walks = 0;
+}
+int scratch_ensure(WalkState& w, size_t walks) {
+  if (w.scratch_walks >= walks) return VDF_OK;
+  scratch_free(w);
+  vdf_ctx* q = w.side;
+  if (vdf_dev_alloc(q, walks * 96, &w.d_walk) != VDF_OK || vdf_dev_alloc(q, walks * 96, &w.d_expect) != VDF_OK ||
+      vdf_host_alloc(q, walks * sizeof(int), (void**)&w.h_ok) != VDF_OK) {
+    const int rc = fail(VDF_ERR_OOM, std::string("walk buffers: ") + vdf_last_error(q));
+    scratch_free(w);
+    return rc;
+  }
+  w.scratch_walks = walks;
+  return VDF_OK;
+}
+// circuits [first, first + count) let go of their walked traces (one copied from the host stays); park: an allocation left to nobody becomes the spare
+void release_range(const vdf_circuits* c, size_t first, size_t count, bool park) {
+  for (size_t k = first; k < first + count; ++k) {
+    Circuit& cc = written(c)->v[k];
+    if (!cc.block || cc.cp.empty()) continue;
+    cc.d_trace = nullptr;
+    if (park && cc.block.use_count() == 1) c->walk.spare = std::move(cc.block);
+    cc.block.reset();
+  }
+}
+// enqueue up to `rounds` more rounds of the pending walks, in launches of the bounded length
+int job_enqueue(const vdf_circuits* c, uint64_t rounds) {
+  const WalkState& w = c->walk;
+  WalkJob* j = w.job.get();
+  const uint64_t t = c->v[j->steps[0]].t;
+  while (rounds && j->done < j->every) {
+    const uint64_t now = std::min(std::min(rounds, j->every - j->done), walk_launch_rounds());
+    HIPCALL(w.side, vdf_minroot_inverse_walk(w.side, VDF_FIELD_FQ, (vdf_state*)w.d_walk, j->walks, now, (vdf_fe*)j->block->d, (size_t)j->every,
+                                             (size_t)(j->every - j->done), j->per_step, (size_t)(t + 1)));
+    j->done += now;
+    rounds -= now;
+  }
+  return VDF_OK;
+}
+// finish the pending walks: the rest of their rounds, the comparison on the device, and the verdict per step
+int job_resolve(const vdf_circuits* c, int* bad, size_t bad_first, size_t bad_count) {
+  WalkState& w = c->walk;
+  WalkJob* j = w.job.get();
+  if (!j) return VDF_OK;
+  auto lose = [&](size_t k) { Circuit& cc = written(c)->v[k]; cc.d_trace = nullptr; cc.block.reset(); };   // left without a trace
+  int rc = job_enqueue(c, j->every);
+  if (rc == VDF_OK && !j->matched) {
+    rc = vdf_minroot_check_batch(w.side, VDF_FIELD_FQ, (const vdf_state*)w.d_walk, (const vdf_state*)w.d_expect, j->walks, 0, w.h_ok);
+    if (rc != VDF_OK) fail(rc, std::string("vdf_minroot_check_batch: ") + vdf_last_error(w.side));
+    j->matched = true;
+  }
+  if (rc == VDF_OK && (rc = vdf_ctx_sync(w.side)) != VDF_OK) fail(rc, std::string("vdf_ctx_sync: ") + vdf_last_error(w.side));
+  if (rc != VDF_OK) {                                                   // a device failure: none of these traces can be trusted
+    vdf_ctx_sync(w.side);
+    for (size_t k : j->steps) lose(k);
+    w.job.reset();
+    return rc;
+  }
+  size_t first_bad = (size_t)-1;
+  for (size_t li = 0; li < j->steps.size(); ++li) {
+    bool ok = true;
+    for (size_t m = 0; m < j->per_step; ++m) ok &= w.h_ok[li * j->per_step + m] == 1;
+    if (ok) continue;
+    const size_t k = j->steps[li];
+    lose(k);
+    if (first_bad == (size_t)-1) first_bad = k;
+    if (bad && k >= bad_first && k - bad_first < bad_count) bad[k - bad_first] = 1;
+  }
+  w.job.reset();                                                        // (its buffers stay: scratch_free)
+  if (first_bad != (size_t)-1)
+    return fail(VDF_ERR_BAD_ARG, "circuit " + std::to_string(first_bad) + ": an inverse walk did not land on the checkpoint before it");
+  return VDF_OK;
+}
+}  // namespace
+
+namespace vdfnova {
+int circuits_need(const vdf_circuits* c, size_t k) {
+  if (c->walk.job_covers(k)) { int rc = job_resolve(c, nullptr, 0, 0); if (rc != VDF_OK) return rc; }
+  const Circuit& cc = c->v[k];
+  if (!cc.d_trace && cc.trace_xy.empty()) return fail(VDF_ERR_BAD_ARG, "trace of circuit " + std::to_string(k) + " not materialised");
+  return VDF_OK;
+}
+// Called by prove_step(k), which needs circuits k and k + 1: the pending walks are wanted by prove_step(steps[0] - 1), so the
+// calls from here to there share the remaining rounds evenly.
+int circuits_pump(const vdf_circuits* c, size_t k) {
+  WalkJob* j = c->walk.job.get();
+  if (!j || j->done >= j->every) return VDF_OK;
+  const size_t wanted_at = j->steps[0] ? j->steps[0] - 1 : 0;
+  const uint64_t calls = wanted_at > k ? wanted_at - k : 1, left = j->every - j->done;
+  return job_enqueue(c, (left + calls - 1) / calls);
+}
+int circuits_settle(const vdf_circuits* c) { return job_resolve(c, nullptr, 0, 0); }
+void circuits_park(const vdf_circuits* c, size_t k) { release_range(c, k, 1, true); }
+void circuits_drop_spare(const vdf_circuits* c) { c->walk.spare.reset(); }
+int circuits_materialize(vdf_ctx* ctx, const vdf_circuits* c, size_t first, size_t count, int wait, int* bad) {
+  return vdf_nova_circuits_materialize(ctx, written(c), first, count, wait, bad);
+}
+}  // namespace vdfnova
+
+extern "C" {
+int vdf_nova_eval_and_make_circuits(int mode, uint64_t t, size_t num_steps, const vdf_state* initial_state,
+                                    vdf_fe z0_primary[3], vdf_circuits** out) {
+  return nova_guard([&]() -> int {
+    if (!valid_mode(mode) || !initial_state || !z0_primary || !out || t == 0) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    if (num_steps == 0) return fail(VDF_ERR_BAD_ARG, "num_steps must be > 0 (assert!, src/nova/proof.rs:268)");
+    vdf_circuits* cs = new vdf_circuits();
+    St state = load_state(initial_state);
+    for (size_t s = 0; s < num_steps; ++s) {                          // :274-279
+      Circuit c;
+      c.t = t;
+      c.input = state;                                                 // previous_state, :285-291
+      c.trace_xy.resize(2 * (t + 1));
+      eval_step(mode, t, &state, c.trace_xy.data());
+      c.result = state;
+      cs->v.push_back(std::move(c));
+    }
+    memcpy(z0_primary, &state, 96);                                    // z0 = final state, :278-281
+    std::reverse(cs->v.begin(), cs->v.end());                          // circuits.reverse(), :294
+    *out = cs;
+    return VDF_OK;
+  });
+}
+int vdf_nova_circuits_from_checkpoints(uint64_t t, uint64_t every, size_t num_steps, const vdf_state* states,
+                                       vdf_fe z0_primary[3], vdf_circuits** out) {
+  return nova_guard([&]() -> int {
+    if (!states || !z0_primary || !out || t == 0) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    if (num_steps == 0) return fail(VDF_ERR_BAD_ARG, "num_steps must be > 0 (assert!, src/nova/proof.rs:268)");
+    if (every == 0 || t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
+    const size_t per = (size_t)(t / every), total = num_steps * per + 1;
+    { int rc = check_counters(states, total - 1, load_state(&states[0]).i, every); if (rc != VDF_OK) return rc; }
+    std::unique_ptr<vdf_circuits> cs(new vdf_circuits());
+    cs->checkpoints = true;
+    cs->v.resize(num_steps);
+    for (size_t s = 0; s < num_steps; ++s) cs->v[num_steps - 1 - s] = checkpoint_circuit(t, every, states + s * per, per);   // circuits.reverse(), :294
+    memcpy(z0_primary, &states[total - 1], 96);                        // z0 = final state, :278-281
+    *out = cs.release();
+    return VDF_OK;
+  });
+}
+
+// ---- forward chains: circuits in the order of evaluation, appended to while the chain grows -------------------------
+int vdf_nova_circuits_forward_begin(uint64_t t, const vdf_state* initial_state, vdf_fe z0_primary[3], vdf_circuits** out) {
+  return nova_guard([&]() -> int {
+    if (!initial_state || !z0_primary || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    std::unique_ptr<vdf_circuits> cs(new vdf_circuits());
+    cs->forward = true;
+    cs->forward_t = t;
+    cs->end = load_state(initial_state);
+    memcpy(z0_primary, initial_state, 96);                             // z0 = the chain's initial state
+    *out = cs.release();
+    return VDF_OK;
+  });
+}
+int vdf_nova_circuits_push_trace(vdf_circuits* c, const vdf_fe* trace_xy) {
+  return nova_guard([&]() -> int {
+    if (!c || !trace_xy) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_forward_begin)");
+    const uint64_t t = c->forward_t;
+    if (memcmp(&trace_xy[0], &c->end.x, 32) != 0 || memcmp(&trace_xy[1], &c->end.y, 32) != 0)
+      return fail(VDF_ERR_BAD_ARG, "the trace does not start at the chain's current end");
+    Circuit cc;
+    cc.t = t;
+    cc.input = c->end;
+    memcpy(&cc.result.x, &trace_xy[2 * t], 32);
+    memcpy(&cc.result.y, &trace_xy[2 * t + 1], 32);
+    cc.result.i = add(c->end.i, from_u64(t, field(VDF_FIELD_FQ)), field(VDF_FIELD_FQ));
+    cc.trace_xy.assign((const Fe*)trace_xy, (const Fe*)trace_xy + 2 * (t + 1));
+    c->end = cc.result;
+    c->v.push_back(std::move(cc));
+    return VDF_OK;
+  });
+}
+int vdf_nova_circuits_push_checkpoints(vdf_circuits* c, uint64_t every, const vdf_state* states) {
+  return nova_guard([&]() -> int {
+    if (!c || !states) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_forward_begin)");
+    const uint64_t t = c->forward_t;
+    if (every == 0 || t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
+    if (!c->v.empty() && c->checkpoints)
+      for (const Circuit& k : c->v) if (k.every && k.every != every) return fail(VDF_ERR_BAD_ARG, "`every` differs from the chain's earlier checkpoint steps");
+    if (memcmp(&states[0], &c->end, 96) != 0) return fail(VDF_ERR_BAD_ARG, "states[0] is not the chain's current end");
+    const size_t per = (size_t)(t / every);
+    { int rc = check_counters(states, per, c->end.i, every); if (rc != VDF_OK) return rc; }
+    c->v.push_back(checkpoint_circuit(t, every, states, per));
+    c->end = c->v.back().result;
+    c->checkpoints = true;
+    return VDF_OK;
+  });
+}
+// ---- traces on the device ---------------------------------------------------------------------------------------
+int vdf_nova_circuits_materialize(vdf_ctx* ctx, vdf_circuits* c, size_t first, size_t count, int wait, int* bad) {
+  return nova_guard([&]() -> int {
+    if (!ctx || !c) return fail(VDF_ERR_BAD_ARG, "null argument");
+    WalkState& w = c->walk;
+    if (!c->checkpoints) return fail(VDF_ERR_BAD_ARG, "these circuits carry their traces: vdf_nova_circuits_upload");
+    if (first > c->v.size() || count > c->v.size() - first) return fail(VDF_ERR_BAD_LENGTH, "circuit range out of bounds");
+    if (bad) for (size_t k = 0; k < count; ++k) bad[k] = 0;
+    const int pending = job_resolve(c, bad, first, count);             // one job at a time; its verdict is this call's too
+    if (pending != VDF_OK && pending != VDF_ERR_BAD_ARG) return pending;
+    if (c->ctx && vdf_ctx_device(c->ctx) != vdf_ctx_device(ctx)) return fail(VDF_ERR_BAD_ARG, "the circuits' traces live on another device");
+    c->ctx = ctx;
+    std::unique_ptr<WalkJob> j(new WalkJob());
+    // (a forward chain may mix steps pushed as traces with steps pushed as checkpoints: only the latter are walked)
+    for (size_t k = first; k < first + count; ++k) if (needs_walk(c->v[k])) j->steps.push_back(k);
+    if (j->steps.empty()) return pending;
+    if (!w.side) {
+      const int dev = vdf_ctx_device(ctx);
+      if (vdf_ctx_create_pooled(&dev, 1, VDF_QUEUE_SIDE, &w.side) != VDF_OK)
+        return fail(VDF_ERR_DEVICE, std::string("walk context: ") + vdf_last_error(nullptr));
+      HIPCALL(w.side, vdf_ctx_set_async(w.side, 1));
+    }
+    vdf_ctx* q = w.side;
+    const Circuit& c0 = c->v[j->steps[0]];
+    const uint64_t t = c0.t, trace_bytes = (t + 1) * 64;
+    j->every = c0.every;
+    j->per_step = (size_t)(t / c0.every);
+    j->walks = j->steps.size() * j->per_step;
+    if (j->steps.size() > (~(uint64_t)0 >> 1) / trace_bytes) return fail(VDF_ERR_OOM, "the traces do not fit");
+    // the windowed prove_recursively's spare allocation, when it is exactly this size; anything else is asked of the device
+    if (w.spare && w.spare.use_count() == 1 && w.spare->ctx == ctx && w.spare->bytes == j->steps.size() * trace_bytes) j->block = std::move(w.spare);
+    w.spare.reset();
+    if (!j->block) {
+      j->block = std::shared_ptr<TraceBlock>(new TraceBlock{ctx, j->steps.size() * trace_bytes});
+      size_t free_bytes = 0;                       // asked first: an allocation beyond the free memory may be granted and fail later
+      HIPCALL(ctx, vdf_dev_mem_info(ctx, &free_bytes, nullptr));
+      if (j->block->bytes + j->walks * (2 * 96) > free_bytes)
+        return fail(VDF_ERR_OOM, "the traces of " + std::to_string(j->steps.size()) + " circuits (" + std::to_string(j->block->bytes) +
+                                     " bytes) do not fit the device's free memory (" + std::to_string(free_bytes) + " bytes)");
+      if (vdf_dev_alloc(ctx, j->block->bytes, &j->block->d) != VDF_OK) {
+        j->block->d = nullptr;
+        return fail(VDF_ERR_OOM, "the traces of " + std::to_string(j->steps.size()) + " circuits do not fit: " + vdf_last_error(ctx));
+      }
+    }
+    { int rc = scratch_ensure(w, j->walks); if (rc != VDF_OK) return rc; }
+    w.job = std::move(j);
+    WalkJob* job = w.job.get();
+    {
+      std::vector<St> from(job->walks), to(job->walks);
+      for (size_t li = 0; li < job->steps.size(); ++li) {
+        const Circuit& k = c->v[job->steps[li]];
+        for (size_t m = 0; m < job->per_step; ++m) { from[li * job->per_step + m] = k.cp[m + 1]; to[li * job->per_step + m] = k.cp[m]; }
+      }
+      memset(w.h_ok, 0, job->walks * sizeof(int));
+      int rc = vdf_dev_memcpy(q, w.d_walk, from.data(), job->walks * 96);
+      if (rc == VDF_OK) rc = vdf_dev_memcpy(q, w.d_expect, to.data(), job->walks * 96);
+      if (rc == VDF_OK) rc = vdf_minroot_trace_heads(q, (const vdf_state*)w.d_expect, job->steps.size(), job->per_step, (vdf_fe*)job->block->d, (size_t)(t + 1));
+      if (rc != VDF_OK) { rc = fail(rc, std::string("walk set-up: ") + vdf_last_error(q)); w.job.reset(); return rc; }
+    }
+    for (size_t li = 0; li < job->steps.size(); ++li) {                 // resident from now on; a walk that misses takes it away again
+      Circuit& k = c->v[job->steps[li]];
+      k.d_trace = (char*)job->block->d + li * trace_bytes;
+      k.block = job->block;
+    }
+    if (!wait) { int rc = job_enqueue(c, walk_launch_rounds()); return rc != VDF_OK ? rc : pending; }
+    const int rc = job_resolve(c, bad, first, count);
+    return rc != VDF_OK ? rc : pending;
+  });
+}
+int vdf_nova_circuits_release(vdf_circuits* c, size_t first, size_t count) {
+  return nova_guard([&]() -> int {
+    if (!c) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (first > c->v.size() || count > c->v.size() - first) return fail(VDF_ERR_BAD_LENGTH, "circuit range out of bounds");
+    const int pending = c->walk.job_covers(first, count) ? job_resolve(c, nullptr, 0, 0) : VDF_OK;
+    release_range(c, first, count, false);
+    // a forward chain is a stream: a step that has been proved lets go of its pushed host trace too
+    if (c->forward) for (size_t k = first; k < first + count; ++k) std::vector<Fe>().swap(c->v[k].trace_xy);
+    return pending;
+  });
+}
+int vdf_nova_circuits_memory(const vdf_circuits* c, size_t* resident_steps, uint64_t* device_bytes) {
+  if (!c) return fail(VDF_ERR_BAD_ARG, "null argument");
+  size_t n = 0;
+  uint64_t bytes = 0;
+  std::vector<const TraceBlock*> seen;
+  for (const Circuit& k : c->v) {
+    if (!k.d_trace) continue;
+    ++n;
+    if (std::find(seen.begin(), seen.end(), k.block.get()) != seen.end()) continue;   // a block counts once
+    seen.push_back(k.block.get());
+    bytes += k.block->bytes;
+  }
+  if (resident_steps) *resident_steps = n;
+  if (device_bytes) *device_bytes = bytes;
+  return VDF_OK;
+}
+int vdf_nova_circuit_trace(const vdf_circuits* c, size_t k, const void** d_trace) {
+  return nova_guard([&]() -> int {
+    if (!c || !d_trace) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (k >= c->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
+    *d_trace = nullptr;
+    if (c->walk.job_covers(k)) { int rc = job_resolve(c, nullptr, 0, 0); if (rc != VDF_OK && rc != VDF_ERR_BAD_ARG) return rc; }
+    *d_trace = c->v[k].d_trace;
+    return VDF_OK;
+  });
+}
+int vdf_nova_circuits_upload(vdf_ctx* ctx, vdf_circuits* c) {
+  if (ctx && c && c->checkpoints) return vdf_nova_circuits_materialize(ctx, c, 0, c->v.size(), 1, nullptr);
+  return nova_guard([&]() -> int {
+    if (!ctx || !c) return fail(VDF_ERR_BAD_ARG, "null argument");
+    c->ctx = ctx;
+    for (auto& k : c->v) {                          // a block per circuit
+      if (k.d_trace) continue;
+      std::shared_ptr<TraceBlock> b(new TraceBlock{ctx, k.trace_xy.size() * 32});
+      HIPCALL(ctx, vdf_dev_alloc(ctx, b->bytes, &b->d));
+      k.d_trace = b->d; k.block = std::move(b);
+      HIPCALL(ctx, vdf_dev_memcpy(ctx, k.d_trace, k.trace_xy.data(), k.trace_xy.size() * 32));
+    }
+    return VDF_OK;
+  });
+}
+size_t vdf_nova_circuits_len(const vdf_circuits* c) { return c ? c->v.size() : 0; }
+int vdf_nova_circuit_states(const vdf_circuits* c, size_t k, vdf_state* result, vdf_state* input) {
+  if (!c || k >= c->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
+  if (result) store_state(result, c->v[k].result);
+  if (input) store_state(input, c->v[k].input);
+  return VDF_OK;
+}
+int vdf_nova_circuits_host_bytes(const vdf_circuits* c, uint64_t* bytes) {
+  if (!c || !bytes) return fail(VDF_ERR_BAD_ARG, "null argument");
+  uint64_t n = 0;
+  for (const Circuit& k : c->v) n += k.trace_xy.size() * 32 + k.cp.size() * 96;
+  *bytes = n;
+  return VDF_OK;
+}
+void vdf_nova_circuits_free(vdf_circuits* c) {
+  if (!c) return;
+  WalkState& w = c->walk;
+  if (w.job) { vdf_ctx_sync(w.side); w.job.reset(); }
+  w.spare.reset();
+  if (w.side) scratch_free(w);
+  c->v.clear();                                   // every trace's allocation goes with the last circuit that points into it
+  if (w.side) vdf_ctx_destroy(w.side);
+  delete c;
+}
+}  // extern "C"

@@ -1,8 +1,7 @@
 // libvdf_nova.so, part 2: the reference's Nova proof surface (src/nova/proof.rs:232-392) on top of the kernel ABI
-// (include/vdf_hip.h): public parameters, circuits, prove_step / prove_recursively, verify.  Protocol
-// "vdf-nova-ivc-v1", specified by oracle/nova.py; see include/vdf_nova.h.
+// (include/vdf_hip.h): public parameters, prove_step / prove_recursively, verify; the circuits they prove are
+// circuits_host.cpp's.  Protocol "vdf-nova-ivc-v1", specified by oracle/nova.py; see include/vdf_nova.h.
 #include <sys/random.h>
-#include <algorithm>
 #include <cerrno>
 #include <condition_variable>
 #include <deque>
@@ -1078,391 +1077,6 @@ int vdf_nova_shape_stencil(uint64_t t, int circuit_kind, uint64_t* early_begin, 
   });
 }
 
-// ---- circuits ----------------------------------------------------------------------------------------
-int vdf_nova_eval_and_make_circuits(int mode, uint64_t t, size_t num_steps, const vdf_state* initial_state,
-                                    vdf_fe z0_primary[3], vdf_circuits** out) {
-  return nova_guard([&]() -> int {
-    if (!valid_mode(mode) || !initial_state || !z0_primary || !out || t == 0) return fail(VDF_ERR_BAD_ARG, "bad argument");
-    if (num_steps == 0) return fail(VDF_ERR_BAD_ARG, "num_steps must be > 0 (assert!, src/nova/proof.rs:268)");
-    vdf_circuits* cs = new vdf_circuits();
-    St state = load_state(initial_state);
-    for (size_t s = 0; s < num_steps; ++s) {                          // :274-279
-      Circuit c;
-      c.t = t;
-      c.input = state;                                                 // previous_state, :285-291
-      c.trace_xy.resize(2 * (t + 1));
-      vdf_state res;
-      vdf_state in;
-      store_state(&in, state);
-      vdf_minroot_eval(VDF_FIELD_FQ, mode, &in, t, &res, (vdf_fe*)c.trace_xy.data());
-      c.result = load_state(&res);
-      state = c.result;
-      cs->v.push_back(std::move(c));
-    }
-    memcpy(z0_primary, &state, 96);                                    // z0 = final state, :278-281
-    std::vector<Circuit> rev(cs->v.rbegin(), cs->v.rend());            // circuits.reverse(), :294
-    cs->v.swap(rev);
-    *out = cs;
-    return VDF_OK;
-  });
-}
-int vdf_nova_circuits_from_checkpoints(uint64_t t, uint64_t every, size_t num_steps, const vdf_state* states,
-                                       vdf_fe z0_primary[3], vdf_circuits** out) {
-  return nova_guard([&]() -> int {
-    if (!states || !z0_primary || !out || t == 0) return fail(VDF_ERR_BAD_ARG, "bad argument");
-    if (num_steps == 0) return fail(VDF_ERR_BAD_ARG, "num_steps must be > 0 (assert!, src/nova/proof.rs:268)");
-    if (every == 0 || t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
-    const size_t per = (size_t)(t / every), total = num_steps * per + 1;
-    const Field& F = field(VDF_FIELD_FQ);
-    const Fe step = from_u64(every, F);
-    Fe want = load_state(&states[0]).i;
-    for (size_t k = 1; k < total; ++k) {
-      want = add(want, step, F);
-      if (memcmp(&states[k].i, &want, 32) != 0)
-        return fail(VDF_ERR_BAD_ARG, "checkpoint " + std::to_string(k) + ": i is not states[0].i + " + std::to_string(k) + " * every");
-    }
-    std::unique_ptr<vdf_circuits> cs(new vdf_circuits());
-    cs->checkpoints = true;
-    cs->v.resize(num_steps);
-    for (size_t s = 0; s < num_steps; ++s) {
-      Circuit& c = cs->v[num_steps - 1 - s];                           // circuits.reverse(), :294
-      c.t = t;
-      c.every = every;
-      c.cp.resize(per + 1);
-      for (size_t m = 0; m <= per; ++m) c.cp[m] = load_state(&states[s * per + m]);
-      c.input = c.cp.front();
-      c.result = c.cp.back();
-    }
-    memcpy(z0_primary, &states[total - 1], 96);                        // z0 = final state, :278-281
-    *out = cs.release();
-    return VDF_OK;
-  });
-}
-
-
-// ---- forward chains: circuits in the order of evaluation, appended to while the chain grows -------------------------
-int vdf_nova_circuits_forward_begin(uint64_t t, const vdf_state* initial_state, vdf_fe z0_primary[3], vdf_circuits** out) {
-  return nova_guard([&]() -> int {
-    if (!initial_state || !z0_primary || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
-    std::unique_ptr<vdf_circuits> cs(new vdf_circuits());
-    cs->forward = true;
-    cs->forward_t = t;
-    cs->end = load_state(initial_state);
-    memcpy(z0_primary, initial_state, 96);                             // z0 = the chain's initial state
-    *out = cs.release();
-    return VDF_OK;
-  });
-}
-int vdf_nova_circuits_push_trace(vdf_circuits* c, const vdf_fe* trace_xy) {
-  return nova_guard([&]() -> int {
-    if (!c || !trace_xy) return fail(VDF_ERR_BAD_ARG, "null argument");
-    if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_forward_begin)");
-    const uint64_t t = c->forward_t;
-    if (memcmp(&trace_xy[0], &c->end.x, 32) != 0 || memcmp(&trace_xy[1], &c->end.y, 32) != 0)
-      return fail(VDF_ERR_BAD_ARG, "the trace does not start at the chain's current end");
-    Circuit cc;
-    cc.t = t;
-    cc.input = c->end;
-    memcpy(&cc.result.x, &trace_xy[2 * t], 32);
-    memcpy(&cc.result.y, &trace_xy[2 * t + 1], 32);
-    cc.result.i = add(c->end.i, from_u64(t, field(VDF_FIELD_FQ)), field(VDF_FIELD_FQ));
-    cc.trace_xy.assign((const Fe*)trace_xy, (const Fe*)trace_xy + 2 * (t + 1));
-    c->end = cc.result;
-    c->v.push_back(std::move(cc));
-    return VDF_OK;
-  });
-}
-int vdf_nova_circuits_push_checkpoints(vdf_circuits* c, uint64_t every, const vdf_state* states) {
-  return nova_guard([&]() -> int {
-    if (!c || !states) return fail(VDF_ERR_BAD_ARG, "null argument");
-    if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_forward_begin)");
-    const uint64_t t = c->forward_t;
-    if (every == 0 || t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
-    if (!c->v.empty() && c->checkpoints)
-      for (const Circuit& k : c->v) if (k.every && k.every != every) return fail(VDF_ERR_BAD_ARG, "`every` differs from the chain's earlier checkpoint steps");
-    if (memcmp(&states[0], &c->end, 96) != 0) return fail(VDF_ERR_BAD_ARG, "states[0] is not the chain's current end");
-    const size_t per = (size_t)(t / every);
-    const Field& F = field(VDF_FIELD_FQ);
-    const Fe step = from_u64(every, F);
-    Fe want = c->end.i;
-    for (size_t k = 1; k <= per; ++k) {
-      want = add(want, step, F);
-      if (memcmp(&states[k].i, &want, 32) != 0)
-        return fail(VDF_ERR_BAD_ARG, "checkpoint " + std::to_string(k) + ": i is not states[0].i + " + std::to_string(k) + " * every");
-    }
-    Circuit cc;
-    cc.t = t;
-    cc.every = every;
-    cc.cp.resize(per + 1);
-    for (size_t m = 0; m <= per; ++m) cc.cp[m] = load_state(&states[m]);
-    cc.input = cc.cp.front();
-    cc.result = cc.cp.back();
-    c->end = cc.result;
-    c->checkpoints = true;
-    c->v.push_back(std::move(cc));
-    return VDF_OK;
-  });
-}
-
-}  // extern "C"
-// ---- checkpoint circuits: traces by inverse walks ----------------------------------------------------------------
-namespace {
-// rounds per launch of the walks: a launch of 1,024 rounds holds a queue for about a millisecond
-uint64_t walk_launch_rounds() {
-  static const uint64_t v = [] {
-    const char* e = getenv("VDF_NOVA_WALK_LAUNCH");
-    const long n = e && *e ? atol(e) : 0;
-    return (uint64_t)(n >= 1 && n <= (1 << 22) ? n : 1024);
-  }();
-  return v;
-}
-void job_drop(const vdf_circuits* c) {
-  c->job.reset();                                  // (its buffers are the circuits': scratch_free)
-}
-void scratch_free(const vdf_circuits* c) {
-  if (c->d_walk) vdf_dev_free(c->side, c->d_walk);
-  if (c->d_expect) vdf_dev_free(c->side, c->d_expect);
-  if (c->h_ok) vdf_host_free(c->side, c->h_ok);
-  c->d_walk = c->d_expect = nullptr;
-  c->h_ok = nullptr;
-  c->scratch_walks = 0;
-}
-int scratch_ensure(const vdf_circuits* c, size_t walks) {
-  if (c->scratch_walks >= walks) return VDF_OK;
-  scratch_free(c);
-  vdf_ctx* q = c->side;
-  if (vdf_dev_alloc(q, walks * 96, &c->d_walk) != VDF_OK || vdf_dev_alloc(q, walks * 96, &c->d_expect) != VDF_OK ||
-      vdf_host_alloc(q, walks * sizeof(int), (void**)&c->h_ok) != VDF_OK) {
-    const int rc = fail(VDF_ERR_OOM, std::string("walk buffers: ") + vdf_last_error(q));
-    scratch_free(c);
-    return rc;
-  }
-  c->scratch_walks = walks;
-  return VDF_OK;
-}
-// circuits [first, first + count) let go of their traces; park: an allocation nobody points into any more is kept as the spare
-void release_range(vdf_circuits* c, size_t first, size_t count, bool park) {
-  for (size_t k = first; k < first + count; ++k) {
-    Circuit& cc = c->v[k];
-    if (!cc.block) continue;                                            // no trace, or one vdf_nova_circuits_upload owns
-    cc.d_trace = nullptr;
-    if (park && cc.block.use_count() == 1) c->spare = std::move(cc.block);
-    cc.block.reset();
-  }
-}
-// enqueue up to `rounds` more rounds of the pending walks, in launches of the bounded length
-int job_enqueue(const vdf_circuits* c, uint64_t rounds) {
-  WalkJob* j = c->job.get();
-  const uint64_t t = c->v[j->steps[0]].t;
-  while (rounds && j->done < j->every) {
-    const uint64_t now = std::min(std::min(rounds, j->every - j->done), walk_launch_rounds());
-    HIPCALL(c->side, vdf_minroot_inverse_walk(c->side, VDF_FIELD_FQ, (vdf_state*)j->d_walk, j->walks, now, (vdf_fe*)j->block->d, (size_t)j->every,
-                                              (size_t)(j->every - j->done), j->per_step, (size_t)(t + 1)));
-    j->done += now;
-    rounds -= now;
-  }
-  return VDF_OK;
-}
-// finish the pending walks: the rest of their rounds, the comparison on the device, and the verdict per step
-int job_resolve(const vdf_circuits* cc, int* bad, size_t bad_first, size_t bad_count) {
-  vdf_circuits* c = const_cast<vdf_circuits*>(cc);
-  WalkJob* j = c->job.get();
-  if (!j) return VDF_OK;
-  int rc = job_enqueue(c, j->every);
-  if (rc == VDF_OK && !j->matched) {
-    rc = vdf_minroot_check_batch(c->side, VDF_FIELD_FQ, (const vdf_state*)j->d_walk, (const vdf_state*)j->d_expect, j->walks, 0, j->h_ok);
-    if (rc != VDF_OK) fail(rc, std::string("vdf_minroot_check_batch: ") + vdf_last_error(c->side));
-    j->matched = true;
-  }
-  if (rc == VDF_OK && (rc = vdf_ctx_sync(c->side)) != VDF_OK) fail(rc, std::string("vdf_ctx_sync: ") + vdf_last_error(c->side));
-  if (rc != VDF_OK) {                                                   // a device failure: none of these traces can be trusted
-    vdf_ctx_sync(c->side);
-    for (size_t k : j->steps) { c->v[k].d_trace = nullptr; c->v[k].block.reset(); }
-    job_drop(c);
-    return rc;
-  }
-  size_t first_bad = (size_t)-1;
-  for (size_t li = 0; li < j->steps.size(); ++li) {
-    bool ok = true;
-    for (size_t m = 0; m < j->per_step; ++m) ok &= j->h_ok[li * j->per_step + m] == 1;
-    if (ok) continue;
-    const size_t k = j->steps[li];
-    c->v[k].d_trace = nullptr;                                          // left without a trace
-    c->v[k].block.reset();
-    if (first_bad == (size_t)-1) first_bad = k;
-    if (bad && k >= bad_first && k - bad_first < bad_count) bad[k - bad_first] = 1;
-  }
-  job_drop(c);
-  if (first_bad != (size_t)-1)
-    return fail(VDF_ERR_BAD_ARG, "circuit " + std::to_string(first_bad) + ": an inverse walk did not land on the checkpoint before it");
-  return VDF_OK;
-}
-}  // namespace
-
-namespace vdfnova {
-int circuits_need(const vdf_circuits* c, size_t k) {
-  if (c->job) {
-    const std::vector<size_t>& st = c->job->steps;
-    if (std::binary_search(st.begin(), st.end(), k)) { int rc = job_resolve(c, nullptr, 0, 0); if (rc != VDF_OK) return rc; }
-  }
-  const Circuit& cc = c->v[k];
-  if (!cc.d_trace && cc.trace_xy.empty()) return fail(VDF_ERR_BAD_ARG, "trace of circuit " + std::to_string(k) + " not materialised");
-  return VDF_OK;
-}
-// Called by prove_step(k), which needs circuits k and k + 1: the pending walks are wanted by prove_step(steps[0] - 1), so the
-// calls from here to there share the remaining rounds evenly.
-int circuits_pump(const vdf_circuits* c, size_t k) {
-  WalkJob* j = c->job.get();
-  if (!j || j->done >= j->every) return VDF_OK;
-  const size_t wanted_at = j->steps[0] ? j->steps[0] - 1 : 0;
-  const uint64_t calls = wanted_at > k ? wanted_at - k : 1, left = j->every - j->done;
-  return job_enqueue(c, (left + calls - 1) / calls);
-}
-}  // namespace vdfnova
-extern "C" {
-
-int vdf_nova_circuits_materialize(vdf_ctx* ctx, vdf_circuits* c, size_t first, size_t count, int wait, int* bad) {
-  return nova_guard([&]() -> int {
-    if (!ctx || !c) return fail(VDF_ERR_BAD_ARG, "null argument");
-    if (!c->checkpoints) return fail(VDF_ERR_BAD_ARG, "these circuits carry their traces: vdf_nova_circuits_upload");
-    if (first > c->v.size() || count > c->v.size() - first) return fail(VDF_ERR_BAD_LENGTH, "circuit range out of bounds");
-    if (bad) for (size_t k = 0; k < count; ++k) bad[k] = 0;
-    const int pending = job_resolve(c, bad, first, count);             // one job at a time; its verdict is this call's too
-    if (pending != VDF_OK && pending != VDF_ERR_BAD_ARG) return pending;
-    if (c->ctx && vdf_ctx_device(c->ctx) != vdf_ctx_device(ctx)) return fail(VDF_ERR_BAD_ARG, "the circuits' traces live on another device");
-    c->ctx = ctx;
-    std::unique_ptr<WalkJob> j(new WalkJob());
-    // (a forward chain may mix steps pushed as traces with steps pushed as checkpoints: only the latter are walked)
-    for (size_t k = first; k < first + count; ++k) if (!c->v[k].d_trace && !c->v[k].cp.empty()) j->steps.push_back(k);
-    if (j->steps.empty()) return pending;
-    if (!c->side) {
-      const int dev = vdf_ctx_device(ctx);
-      if (vdf_ctx_create_pooled(&dev, 1, VDF_QUEUE_SIDE, &c->side) != VDF_OK)
-        return fail(VDF_ERR_DEVICE, std::string("walk context: ") + vdf_last_error(nullptr));
-      HIPCALL(c->side, vdf_ctx_set_async(c->side, 1));
-    }
-    vdf_ctx* q = c->side;
-    const Circuit& c0 = c->v[j->steps[0]];
-    const uint64_t t = c0.t, trace_bytes = (t + 1) * 64;
-    j->every = c0.every;
-    j->per_step = (size_t)(t / c0.every);
-    j->walks = j->steps.size() * j->per_step;
-    if (j->steps.size() > (~(uint64_t)0 >> 1) / trace_bytes) return fail(VDF_ERR_OOM, "the traces do not fit");
-    // the windowed prove_recursively's spare allocation, when it is exactly this size; anything else is asked of the device
-    if (c->spare && c->spare.use_count() == 1 && c->spare->ctx == ctx && c->spare->bytes == j->steps.size() * trace_bytes) j->block = std::move(c->spare);
-    c->spare.reset();
-    if (!j->block) {
-      j->block = std::make_shared<TraceBlock>();
-      j->block->ctx = ctx;
-      j->block->bytes = j->steps.size() * trace_bytes;
-      size_t free_bytes = 0;                       // asked first: an allocation beyond the free memory may be granted and fail later
-      HIPCALL(ctx, vdf_dev_mem_info(ctx, &free_bytes, nullptr));
-      if (j->block->bytes + j->walks * (2 * 96) > free_bytes)
-        return fail(VDF_ERR_OOM, "the traces of " + std::to_string(j->steps.size()) + " circuits (" + std::to_string(j->block->bytes) +
-                                     " bytes) do not fit the device's free memory (" + std::to_string(free_bytes) + " bytes)");
-      if (vdf_dev_alloc(ctx, j->block->bytes, &j->block->d) != VDF_OK) {
-        j->block->d = nullptr;
-        return fail(VDF_ERR_OOM, "the traces of " + std::to_string(j->steps.size()) + " circuits do not fit: " + vdf_last_error(ctx));
-      }
-    }
-    { int rc = scratch_ensure(c, j->walks); if (rc != VDF_OK) return rc; }
-    j->d_walk = c->d_walk; j->d_expect = c->d_expect; j->h_ok = c->h_ok;
-    c->job = std::move(j);
-    WalkJob* job = c->job.get();
-    auto give_up = [&](int rc) { job_drop(c); return rc; };
-    {
-      std::vector<St> from(job->walks), to(job->walks);
-      for (size_t li = 0; li < job->steps.size(); ++li) {
-        const Circuit& cc = c->v[job->steps[li]];
-        for (size_t m = 0; m < job->per_step; ++m) { from[li * job->per_step + m] = cc.cp[m + 1]; to[li * job->per_step + m] = cc.cp[m]; }
-      }
-      memset(job->h_ok, 0, job->walks * sizeof(int));
-      int rc = vdf_dev_memcpy(q, job->d_walk, from.data(), job->walks * 96);
-      if (rc == VDF_OK) rc = vdf_dev_memcpy(q, job->d_expect, to.data(), job->walks * 96);
-      if (rc == VDF_OK) rc = vdf_minroot_trace_heads(q, (const vdf_state*)job->d_expect, job->steps.size(), job->per_step, (vdf_fe*)job->block->d, (size_t)(t + 1));
-      if (rc != VDF_OK) return give_up(fail(rc, std::string("walk set-up: ") + vdf_last_error(q)));
-    }
-    for (size_t li = 0; li < job->steps.size(); ++li) {                 // resident from now on; a walk that misses takes it away again
-      Circuit& cc = c->v[job->steps[li]];
-      cc.d_trace = (char*)job->block->d + li * trace_bytes;
-      cc.block = job->block;
-    }
-    if (!wait) { int rc = job_enqueue(c, walk_launch_rounds()); return rc != VDF_OK ? rc : pending; }
-    const int rc = job_resolve(c, bad, first, count);
-    return rc != VDF_OK ? rc : pending;
-  });
-}
-int vdf_nova_circuits_release(vdf_circuits* c, size_t first, size_t count) {
-  return nova_guard([&]() -> int {
-    if (!c) return fail(VDF_ERR_BAD_ARG, "null argument");
-    if (first > c->v.size() || count > c->v.size() - first) return fail(VDF_ERR_BAD_LENGTH, "circuit range out of bounds");
-    int pending = VDF_OK;
-    if (c->job)
-      for (size_t k : c->job->steps) if (k >= first && k - first < count) { pending = job_resolve(c, nullptr, 0, 0); break; }
-    release_range(c, first, count, false);
-    // a forward chain is a stream: a step that has been proved lets go of its pushed host trace too
-    if (c->forward) for (size_t k = first; k < first + count; ++k) std::vector<Fe>().swap(c->v[k].trace_xy);
-    return pending;
-  });
-}
-int vdf_nova_circuits_memory(const vdf_circuits* c, size_t* resident_steps, uint64_t* device_bytes) {
-  if (!c) return fail(VDF_ERR_BAD_ARG, "null argument");
-  size_t n = 0;
-  uint64_t bytes = 0;
-  std::vector<const TraceBlock*> seen;
-  for (const Circuit& k : c->v) {
-    if (!k.d_trace) continue;
-    ++n;
-    if (!k.block) { bytes += (k.t + 1) * 64; continue; }
-    if (std::find(seen.begin(), seen.end(), k.block.get()) != seen.end()) continue;
-    seen.push_back(k.block.get());
-    bytes += k.block->bytes;
-  }
-  if (resident_steps) *resident_steps = n;
-  if (device_bytes) *device_bytes = bytes;
-  return VDF_OK;
-}
-int vdf_nova_circuit_trace(const vdf_circuits* c, size_t k, const void** d_trace) {
-  return nova_guard([&]() -> int {
-    if (!c || !d_trace) return fail(VDF_ERR_BAD_ARG, "null argument");
-    if (k >= c->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
-    *d_trace = nullptr;
-    if (c->job && std::binary_search(c->job->steps.begin(), c->job->steps.end(), k)) { int rc = job_resolve(c, nullptr, 0, 0); if (rc != VDF_OK && rc != VDF_ERR_BAD_ARG) return rc; }
-    *d_trace = c->v[k].d_trace;
-    return VDF_OK;
-  });
-}
-int vdf_nova_circuits_upload(vdf_ctx* ctx, vdf_circuits* c) {
-  if (ctx && c && c->checkpoints) return vdf_nova_circuits_materialize(ctx, c, 0, c->v.size(), 1, nullptr);
-  return nova_guard([&]() -> int {
-    if (!ctx || !c) return fail(VDF_ERR_BAD_ARG, "null argument");
-    c->ctx = ctx;
-    for (auto& k : c->v) {
-      if (k.d_trace) continue;
-      HIPCALL(ctx, vdf_dev_alloc(ctx, k.trace_xy.size() * 32, &k.d_trace));
-      HIPCALL(ctx, vdf_dev_memcpy(ctx, k.d_trace, k.trace_xy.data(), k.trace_xy.size() * 32));
-    }
-    return VDF_OK;
-  });
-}
-size_t vdf_nova_circuits_len(const vdf_circuits* c) { return c ? c->v.size() : 0; }
-int vdf_nova_circuit_states(const vdf_circuits* c, size_t k, vdf_state* result, vdf_state* input) {
-  if (!c || k >= c->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
-  if (result) store_state(result, c->v[k].result);
-  if (input) store_state(input, c->v[k].input);
-  return VDF_OK;
-}
-void vdf_nova_circuits_free(vdf_circuits* c) {
-  if (!c) return;
-  if (c->job) { vdf_ctx_sync(c->side); job_drop(c); }
-  c->spare.reset();
-  if (c->side) scratch_free(c);
-  if (c->ctx) for (auto& k : c->v) if (k.d_trace && !k.block) vdf_dev_free(c->ctx, k.d_trace);
-  c->v.clear();                                   // the walked traces' allocations go with their circuits
-  if (c->side) vdf_ctx_destroy(c->side);
-  delete c;
-}
-
 // ---- prove_step ----------------------------------------------------------------------------------------
 static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* circuits, size_t k, const vdf_step_circuit* custom,
                            const vdf_fe* z0, vdf_proof** fresh);
@@ -2127,11 +1741,10 @@ int vdf_nova_prove_recursively_windowed(vdf_pp* pp, const vdf_circuits* circuits
     // Checkpoint circuits whose traces are not all there: built window by window on the circuits' side queue, window w + 1 under
     // the proving of window w, and only what this call built is released (window w - 1, once the last step that reads it has returned).
     // The handle is the caller's and is left as it was found; the reference takes the circuits by value (src/nova/proof.rs:302-307).
-    vdf_circuits* cs = const_cast<vdf_circuits*>(circuits);
     bool windowed = false;
-    if (cs->checkpoints) {
-      if (cs->job) { int rc = circuits_need(cs, cs->job->steps[0]); if (rc != VDF_OK) { *out = nullptr; return rc; } }
-      for (const Circuit& c : cs->v) windowed |= !c.d_trace && !c.cp.empty();
+    if (circuits->checkpoints) {
+      { int rc = circuits_settle(circuits); if (rc != VDF_OK) { *out = nullptr; return rc; } }
+      for (const Circuit& c : circuits->v) windowed |= needs_walk(c);
     }
     const size_t W = !windowed ? n : window_steps ? std::max<size_t>(window_steps, 2)
                                                   : std::max<size_t>(2, (size_t)(((uint64_t)1 << 30) / ((pp->t + 1) * 64)));
@@ -2140,13 +1753,10 @@ int vdf_nova_prove_recursively_windowed(vdf_pp* pp, const vdf_circuits* circuits
       const size_t b = w * W;
       if (!windowed || b >= n) return VDF_OK;
       const size_t cnt = std::min(W, n - b);
-      for (size_t k = b; k < b + cnt; ++k) mine[k] = !cs->v[k].d_trace && !cs->v[k].cp.empty();
-      return vdf_nova_circuits_materialize(pp->ctx, cs, b, cnt, wait, nullptr);
+      for (size_t k = b; k < b + cnt; ++k) mine[k] = needs_walk(circuits->v[k]);
+      return circuits_materialize(pp->ctx, circuits, b, cnt, wait, nullptr);
     };
-    auto drop = [&](size_t w) {
-      for (size_t k = w * W; k < std::min(n, (w + 1) * W); ++k) if (mine[k]) { release_range(cs, k, 1, true); mine[k] = 0; }
-    };
-    auto drop_all = [&]() { if (windowed) for (size_t w = 0; w * W < n; ++w) drop(w); };
+    auto drop = [&](size_t w) { for (size_t k = w * W; k < std::min(n, (w + 1) * W); ++k) if (mine[k]) { circuits_park(circuits, k); mine[k] = 0; } };
     vdf_proof* p = nullptr;
     int rc = build(0, 1);
     if (rc == VDF_OK) rc = build(1, 0);
@@ -2158,9 +1768,9 @@ int vdf_nova_prove_recursively_windowed(vdf_pp* pp, const vdf_circuits* circuits
       }
     }
     if (rc == VDF_OK) rc = finalize_l2(p);
-    if (rc != VDF_OK && cs->job) circuits_need(cs, cs->job->steps[0]);   // nothing of this call's stays in flight
-    drop_all();
-    cs->spare.reset();
+    if (rc != VDF_OK) circuits_settle(circuits);                         // nothing of this call's stays in flight
+    if (windowed) for (size_t w = 0; w * W < n; ++w) drop(w);
+    circuits_drop_spare(circuits);
     if (rc != VDF_OK) { vdf_nova_proof_free(p); *out = nullptr; return rc; }
     *out = p;
     return VDF_OK;
@@ -2201,10 +1811,7 @@ int vdf_nova_eval_and_prove(vdf_pp* pp, int mode, const vdf_state* initial_state
       const double t_begin = now_ms();
       for (size_t k = 0; k < num_steps; ++k) {
         std::vector<Fe> trace(2 * (t + 1));
-        vdf_state in, res;
-        store_state(&in, state);
-        vdf_minroot_eval(VDF_FIELD_FQ, mode, &in, t, &res, (vdf_fe*)trace.data());
-        state = load_state(&res);
+        eval_step(mode, t, &state, trace.data());
         std::unique_lock<std::mutex> lk(sh.mu);
         if (k + 1 == num_steps) { sh.eval_end = now_ms(); sh.eval_ms = sh.eval_end - t_begin; }   // the chain's output exists from here
         sh.cv.wait(lk, [&] { return sh.traces.size() < EVAL_QUEUE || sh.stop; });
@@ -2250,14 +1857,6 @@ int vdf_nova_eval_and_prove(vdf_pp* pp, int mode, const vdf_state* initial_state
     *out = p;
     return VDF_OK;
   });
-}
-
-int vdf_nova_circuits_host_bytes(const vdf_circuits* c, uint64_t* bytes) {
-  if (!c || !bytes) return fail(VDF_ERR_BAD_ARG, "null argument");
-  uint64_t n = 0;
-  for (const Circuit& k : c->v) n += k.trace_xy.size() * 32 + k.cp.size() * 96;
-  *bytes = n;
-  return VDF_OK;
 }
 
 void vdf_nova_proof_free(vdf_proof* p) {

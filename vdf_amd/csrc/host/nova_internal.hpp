@@ -1,6 +1,7 @@
-// Shared declarations of the translation units of libvdf_nova.so (minroot_host.cpp, r1cs.cpp, nova_host.cpp,
+// Shared declarations of the translation units of libvdf_nova.so (minroot_host.cpp, r1cs.cpp, nova_host.cpp, circuits_host.cpp,
 // compress_host.cpp, wire_host.cpp): error plumbing, the two sides of the curve cycle, the handle structs.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <chrono>
 #include <functional>
@@ -129,11 +130,12 @@ struct vdf_pp {
   unsigned digit_tables_skipped = 0;       // bit s: side s asked for a digit table and went without (no room, refused window)
 };
 
-// device memory of the traces one vdf_nova_circuits_materialize built: freed when the last circuit that points into it lets go
+// the one owner of a device trace: the traces one vdf_nova_circuits_materialize built, or the one vdf_nova_circuits_upload
+// copied; freed when the last circuit that points into it lets go
 struct TraceBlock {
-  vdf_ctx* ctx = nullptr;
+  vdf_ctx* ctx;
+  uint64_t bytes;
   void* d = nullptr;
-  uint64_t bytes = 0;
   ~TraceBlock() { if (d) vdf_dev_free(ctx, d); }
 };
 struct Circuit {            // InverseMinRootCircuit<G1>, src/nova/proof.rs:57-66, + the forward trace
@@ -141,24 +143,40 @@ struct Circuit {            // InverseMinRootCircuit<G1>, src/nova/proof.rs:57-6
   vdfnova::St result, input;
   uint64_t t = 0;
   std::vector<Fe> trace_xy;  // (x, y) of states 0..t: trace[0] = input, trace[t] = result
-  void* d_trace = nullptr;   // the same trace in HBM (vdf_nova_circuits_upload, vdf_nova_circuits_materialize)
+  void* d_trace = nullptr;   // the same trace in HBM (vdf_nova_circuits_upload, vdf_nova_circuits_materialize): null, or inside `block`
+  std::shared_ptr<TraceBlock> block;
   // a circuit made from checkpoints (vdf_nova_circuits_from_checkpoints) holds no host trace: the step's states every `every`
-  // rounds in forward order, cp[0] = input .. cp[t / every] = result; its d_trace lies inside `block`
+  // rounds in forward order, cp[0] = input .. cp[t / every] = result; its d_trace is built by walks, and is what release lets go of
   uint64_t every = 0;
   std::vector<vdfnova::St> cp;
-  std::shared_ptr<TraceBlock> block;
 };
 // Traces being rebuilt by inverse walks on the circuits' side queue (vdf_nova_circuits_materialize): one walk per checkpoint
 // interval of every step in `steps`, all in one launch per slice of rounds; `done` rounds of `every` are enqueued so far.
 struct WalkJob {
   std::vector<size_t> steps;               // circuit indices, ascending
   std::shared_ptr<TraceBlock> block;       // steps.size() traces of t + 1 entries
-  void* d_walk = nullptr;                  // where each walk stands
-  void* d_expect = nullptr;                // the checkpoint each walk must land on
-  int* h_ok = nullptr;                     // pinned: 1 per walk that landed on it
   size_t walks = 0, per_step = 0;
   uint64_t every = 0, done = 0;
   bool matched = false;                    // the comparison has been enqueued
+};
+// The walks of one vdf_circuits: on a side queue of the device (made by the first materialize), a job enqueued with wait = 0 being
+// finished by the next call that needs its result.  Their buffers are kept from one job to the next, and the windowed prove_recursively
+// keeps the allocation of the window it releases for the window after next (`spare`): a device free is a synchronisation of the
+// whole device, and two per window showed in the prover's rate.  The C ABI hands prove_step and prove_recursively the circuits const
+// (the reference takes them by value), and both finish or start walks under them: this is the one member a const handle may
+// change, and what the walks decide about a trace is written into v[k] through the one cast there is (circuits_host.cpp, `written`).
+struct WalkState {
+  vdf_ctx* side = nullptr;
+  std::unique_ptr<WalkJob> job;
+  void* d_walk = nullptr, *d_expect = nullptr;   // where each walk stands, and the checkpoint it must land on
+  int* h_ok = nullptr;                     // pinned: 1 per walk that landed on it
+  size_t scratch_walks = 0;                // the walks these three have room for
+  std::shared_ptr<TraceBlock> spare;
+  bool job_covers(size_t first, size_t count = 1) const {   // the pending job builds a trace of circuits [first, first + count)
+    if (!job) return false;
+    const auto it = std::lower_bound(job->steps.begin(), job->steps.end(), first);
+    return it != job->steps.end() && *it - first < count;
+  }
 };
 struct vdf_circuits {
   std::vector<Circuit> v;
@@ -169,18 +187,7 @@ struct vdf_circuits {
   bool forward = false;
   uint64_t forward_t = 0;
   vdfnova::St end;
-  // the walks run on a side queue of the device (made by the first materialize); a job enqueued with wait = 0 is finished by
-  // the next call that needs its result -- prove_step takes the circuits const, hence mutable
-  mutable vdf_ctx* side = nullptr;
-  mutable std::unique_ptr<WalkJob> job;
-  // the walks' buffers (where each stands, where it must land, the verdicts: pinned) are kept from one job to the next, and the
-  // windowed prove_recursively keeps the allocation of the window it releases for the window after next: a device free is a
-  // synchronisation of the whole device, and two per window showed in the prover's rate
-  mutable void* d_walk = nullptr;
-  mutable void* d_expect = nullptr;
-  mutable int* h_ok = nullptr;
-  mutable size_t scratch_walks = 0;
-  std::shared_ptr<TraceBlock> spare;
+  mutable WalkState walk;
 };
 
 // NovaVDFProof::Recursive = nova-snark RecursiveSNARK: running instance + witness on both sides, the last secondary
@@ -245,10 +252,24 @@ int alloc_proof_buffers(vdf_proof* p);
 int finalize_l2(const vdf_proof* p);      // commits to the last secondary witness if that is still pending
 std::unique_ptr<StepCircuit> make_primary_circuit(const vdf_pp* pp, const Circuit* c, bool device_rounds);
 std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c);
-// checkpoint circuits (nova_host.cpp): finish the pending walks if they cover circuit k and say whether its trace is there;
+// ---- the circuits as the drivers of nova_host.cpp reach them (circuits_host.cpp) --------------------------------------------
+inline void eval_step(int mode, uint64_t t, St* state, Fe* trace_xy) {   // t rounds from *state: the trace [2 (t + 1)], *state = the result
+  vdf_state in, res;
+  store_state(&in, *state);
+  vdf_minroot_eval(VDF_FIELD_FQ, mode, &in, t, &res, (vdf_fe*)trace_xy);
+  *state = load_state(&res);
+}
+inline bool needs_walk(const Circuit& c) { return !c.d_trace && !c.cp.empty(); }   // not resident and has checkpoints
+// checkpoint circuits: finish the pending walks if they cover circuit k and say whether its trace is there;
 // enqueue the share of the pending walks that keeps them ahead of a prover about to prove circuit k
 int circuits_need(const vdf_circuits* c, size_t k);
 int circuits_pump(const vdf_circuits* c, size_t k);
+// for the windowed prover, handed the circuits const: vdf_nova_circuits_materialize; the pending walks finished whatever they
+// cover; circuit k's walked trace let go of, its allocation kept as the spare if nobody else points into it; the spare freed
+int circuits_materialize(vdf_ctx* ctx, const vdf_circuits* c, size_t first, size_t count, int wait, int* bad);
+int circuits_settle(const vdf_circuits* c);
+void circuits_park(const vdf_circuits* c, size_t k);
+void circuits_drop_spare(const vdf_circuits* c);
 
 // ---- wire formats (wire_host.cpp; layout in include/vdf_nova.h) --------------------------------------------
 constexpr char WIRE_MAGIC_SNARK[9] = "VDFSNK03";      // compressed proof
