@@ -10,6 +10,7 @@ import pytest
 from oracle import nova as nv, pasta as o, wire as w
 from test_gpu_compress import oracle_proof
 from test_gpu_seam import Cubic, fe
+from test_gpu_snark import BIG_N, ONES, SKEWED_CONS, big_reduction, skewed_eq, skewed_shape, spmvt_formula
 from util import ints, mont, unmont, rand_limbs
 from vdf_amd.minroot import PallasVDF, State, FIELD_FQ
 from vdf_amd.nova import (InverseMinRootCircuit, NovaVDFProof, CIRCUIT_MINROOT_BOUND, CIRCUIT_MINROOT_REFERENCE, GENS_TRY_AND_INCREMENT,
@@ -67,6 +68,31 @@ def test_reduce_batch_matches_the_formula_and_single_calls(ctx, field, kind, cou
         single = ctx.reduce(field, kind, dev[q], n, u=mont([us[q]], m) if kind == 2 else None)
         assert np.array_equal(got[q], single), q
         assert unmont(got[q], m) == _reduce_formula(kind, tabs[q], us[q], n, m), q
+
+
+@pytest.mark.parametrize("field", [o.FIELD_FP, o.FIELD_FQ])
+@pytest.mark.parametrize("kind", [0, 1, 2, 3])
+def test_reduce_batch_of_one_above_the_grid_cap(ctx, field, kind):
+    """count = 1 at n = 2^19: 512 workgroups for the instance, so the final pass takes two partials per lane."""
+    tabs, u, exp = big_reduction(field)
+    dev = [_dev(t) for t in tabs[:5 if kind == 2 else 2]]
+    got = ctx.reduce_batch(field, kind, [dev], BIG_N, u=u if kind == 2 else None)
+    assert ints(got[0]) == (exp["dot", BIG_N, 0, 1] if kind == 0 else exp[kind, BIG_N])
+    assert np.array_equal(got[0], ctx.reduce(field, kind, dev, BIG_N, u=u if kind == 2 else None))
+
+
+@pytest.mark.parametrize("field", [o.FIELD_FP, o.FIELD_FQ])
+@pytest.mark.parametrize("count", [2, 3])
+def test_dot_product_batch_strides(ctx, field, count):
+    """n = 2^18 needs 1024 workgroups per instance: count = 2 gives each 256 of four strides, count = 3 gives each 170 (not a power
+    of two: the strides end unevenly)."""
+    n = 1 << 18
+    tabs, _, exp = big_reduction(field)
+    dev = [_dev(t[:n]) for t in tabs[:count + 1]]
+    got = ctx.reduce_batch(field, 0, [[dev[q], dev[q + 1]] for q in range(count)], n)
+    for q in range(count):
+        assert ints(got[q]) == exp["dot", n, q, q + 1], q
+        assert np.array_equal(got[q], ctx.reduce(field, 0, [dev[q], dev[q + 1]], n)), q
 
 
 def test_reduce_batch_refuses_bad_arguments(ctx):
@@ -133,7 +159,8 @@ def test_spmv3_t_batch_on_both_sides_of_t_1024(ctx, side, count):
 
 @pytest.mark.parametrize("count", [1, 2, 8])
 def test_spmv3_t_batch_heavy_columns(ctx, count):
-    """Columns of more than SPMVT_HEAVY (64) entries: one of ~3000 (shared by many workgroups) and several of ~100."""
+    """Columns of more than SPMVT_HEAVY (64) entries: one of 3000 and several of 100, one workgroup each (a column is shared by
+    64 workgroups only past 4096 entries: test_spmv3_t_batch_skewed_columns)."""
     field, m = o.FIELD_FQ, o.Q
     rng = np.random.default_rng(5 + count)
     num_cons, ncols = 4096, 40
@@ -153,6 +180,31 @@ def test_spmv3_t_batch_heavy_columns(ctx, count):
         mats.append((np.array([e[0] for e in es], dtype=np.uint32), np.array([e[1] for e in es], dtype=np.uint32), mont(vals, m)))
     shape = ctx.shape_create(field, num_cons, ncols, mats)
     _check_spmv_batch(ctx, shape, field, num_cons, ncols, count, 77 + count)
+    shape.free()
+
+
+@pytest.mark.parametrize("field", [o.FIELD_FP, o.FIELD_FQ])
+@pytest.mark.parametrize("profile", ["few-big", "many-big"])
+@pytest.mark.parametrize("count", [1, 2, 3, 4, 5, 7, 8])
+def test_spmv3_t_batch_skewed_columns(ctx, count, profile, field):
+    """The batch against the formula over the COO triples (test_gpu_snark.skewed_shape), each instance with its own eq and rho:
+    widths 1, 2 and 4, the widest with cnt < 4 (3; 5 = 4 + 1, 7 = 4 + 3), columns shared by 64 workgroups within the scratch's
+    room (few-big) and past it (many-big: 12, 24 and 30 columns from heavy + shared).  One instance has rho = 0 and one rho = 1;
+    where that leaves no other (count <= 2), a second call has random ones."""
+    m = o.modulus(field)
+    mats, triples, ncols = skewed_shape(profile, field)
+    shape = ctx.shape_create(field, SKEWED_CONS, ncols, mats)
+    rng = np.random.default_rng(1000 * count + 10 * ncols + field)
+    base = _rand(rng, m, count)
+    rho_sets = [[0], [1], base] if count == 1 else [[0] + base[1:-1] + [1]] + ([base] if count == 2 else [])
+    for rhos in rho_sets:
+        eqs = [skewed_eq(rng, m) for _ in range(count)]
+        outs = [_dev(np.full((ncols, 4), ONES, dtype="<u8")) for _ in range(count)]
+        ctx.spmv3_t_batch(shape, [_dev(mont(e, m)) for e in eqs], np.stack([mont([r], m)[0] for r in rhos]), outs)
+        ctx.sync()
+        for q in range(count):
+            exp = spmvt_formula(triples, eqs[q], rhos[q], ncols, m)
+            assert exp[0] == 0 and ints(_host(outs[q])) == ints(mont(exp, m)), (rhos[q], q)
     shape.free()
 
 

@@ -1,4 +1,6 @@
 """GPU parity of the compression-SNARK building blocks (include/vdf_hip.h) against oracle/spartan.py, bit-exact."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -160,3 +162,234 @@ def test_pair_table_pattern(ctx, field, k, log_m):
         assert got[i] == e, i
     with pytest.raises(Exception):
         ctx.pair_table_pattern(field, mont(lo, m), mont(hi, m), k, mont(pat + [1] * 16, m), 5, out)      # pattern too long
+
+
+# ---- every size regime of the blocks, against big-integer formulas over the tests' own inputs ------------------------------------
+FIELDS = [o.FIELD_FP, o.FIELD_FQ]
+ONES = 0xFFFFFFFFFFFFFFFF                                               # prefill of an output: an unwritten element shows up
+
+
+def _randm(rng, m, k):
+    return [int(x) % m for x in ints(rand_limbs(rng, k))]
+
+
+# -- vdf_spmv3_t over skewed columns: <= 64 entries a thread, 65..4096 a workgroup, more than 4096 shared by 64 workgroups as far
+# -- as the 48 KB scratch holds their partials (24 columns; 24 / 12 / 6 for the batch widths 1 / 2 / 4), the rest one workgroup each
+SKEWED_CONS = 6144
+FEW_BIG = [0, 1, 2, 63, 64, 65, 66, 127, 255, 256, 257, 511, 1000, 4095, 4096, 4097, 4160, 4161, 8191, 12000]
+SKEWED_PROFILES = {"few-big": FEW_BIG,                                  # 5 columns past 4096: within the scratch at every width
+                   "many-big": FEW_BIG + list(range(4100, 4131))}       # 36 of them: past the room of 24, 12 and 6
+SKEWED_DUPLICATES = {66: 2, 4097: 3, 12000: 2}                          # column length -> repeated (row, column) pairs inside A
+
+
+@functools.lru_cache(maxsize=None)
+def skewed_shape(profile, field):
+    """(mats, triples, ncols): the COO arrays for shape_create and the same triples as (rows, cols, coefficient integers).  Column
+    c has SKEWED_PROFILES[profile][c] entries, a third in each of A, B, C, on random distinct rows of a matrix (but for the
+    deliberate duplicates, which are legal COO and sum); column 0 is empty and the last column is one of the longest, so
+    colptr[c + 1] is read at the end of the array.  Coefficients come from a pool of 53 values with +1, -1 and 2 in it, and the
+    triples are handed over in shuffled order."""
+    m = o.modulus(field)
+    lens = SKEWED_PROFILES[profile]
+    rng = np.random.default_rng(4000 + 10 * len(lens) + field)
+    pool = [1, m - 1, 2] + _randm(rng, m, 50)
+    pool_mont, pool_obj = mont(pool, m), np.array(pool, dtype=object)
+    mats, triples = [], []
+    for k in range(3):
+        rows, cols = [], []
+        for c, ln in enumerate(lens):
+            part = ln // 3 + (1 if k < ln % 3 else 0)
+            dup = SKEWED_DUPLICATES.get(ln, 0) if k == 0 else 0
+            r = rng.choice(SKEWED_CONS, part - dup, replace=False)
+            rows.append(np.concatenate([r, r[:dup]]))
+            cols.append(np.full(part, c))
+        rows, cols = np.concatenate(rows).astype(np.uint32), np.concatenate(cols).astype(np.uint32)
+        order = rng.permutation(rows.size)
+        rows, cols = rows[order], cols[order]
+        ci = rng.integers(0, len(pool), size=rows.size)
+        mats.append((rows, cols, np.ascontiguousarray(pool_mont[ci])))
+        triples.append((rows, cols, pool_obj[ci]))
+    got_lens = sum(np.bincount(t[1], minlength=len(lens)) for t in triples)
+    assert got_lens.tolist() == lens and len(set(zip(triples[0][0].tolist(), triples[0][1].tolist()))) == triples[0][0].size - 7
+    return mats, triples, len(lens)
+
+
+def skewed_eq(rng, m):
+    eq = _randm(rng, m, SKEWED_CONS)
+    for r in rng.choice(SKEWED_CONS, 200, replace=False):
+        eq[int(r)] = 0
+    for r in rng.choice(SKEWED_CONS, 200, replace=False):
+        eq[int(r)] = m - 1
+    return eq
+
+
+def spmvt_formula(triples, eq, rho, ncols, m):
+    """exp[c] = sum over the triples (row, c, val) of coef * val * eq[row], coef = 1, rho, rho^2 for A, B, C"""
+    eq = np.array(eq, dtype=object)
+    exp = [0] * ncols
+    for coef, (rows, cols, vals) in zip((1, rho, rho * rho % m), triples):
+        term = vals * eq[rows]
+        for c in range(ncols):
+            exp[c] = (exp[c] + coef * int(term[cols == c].sum())) % m
+    return exp
+
+
+@pytest.mark.parametrize("field", FIELDS)
+@pytest.mark.parametrize("profile", ["few-big", "many-big"])
+def test_spmv3_transposed_skewed_columns(ctx, profile, field):
+    """few-big: k_spmvt, k_spmvt_heavy and k_spmvt_heavy_part / k_spmvt_heavy_sum (chunks of 65, 65, 66, 128 and 188 entries per
+    part, the last parts short or empty); many-big: 36 columns past 4096 entries, 12 of them past the scratch's room of 24 and so
+    launched from heavy + shared."""
+    m = o.modulus(field)
+    mats, triples, ncols = skewed_shape(profile, field)
+    shape = ctx.shape_create(field, SKEWED_CONS, ncols, mats)
+    rng = np.random.default_rng(17 + field + ncols)
+    eq = skewed_eq(rng, m)
+    for rho in _randm(rng, m, 1) + [0, 1]:
+        out = _dev(np.full((ncols, 4), ONES, dtype="<u8"))
+        ctx.spmv3_t(shape, _dev(mont(eq, m)), mont([rho], m), out)
+        ctx.sync()
+        exp = spmvt_formula(triples, eq, rho, ncols, m)
+        assert exp[0] == 0 and ints(_host(out)) == ints(mont(exp, m)), rho
+    shape.free()
+
+
+# -- vdf_reduce past the grid cap of 512 workgroups (h > 131072: k_reduce strides) and past 256 partials (h > 65536: the final
+# -- pass takes several per lane)
+BIG_N = 1 << 19
+
+
+@functools.lru_cache(maxsize=None)
+def big_reduction(field):
+    """Five tables of 2^19 raw canonical residues (below 2^254 < m), a residue u, and what each reduction returns over them.
+    The device multiplies residues by Montgomery's product x * y -> x y R^-1 mod m and adds, subtracts and doubles them as they
+    are, so the returned residue is a closed form in the raw integers with one R^-1 per product, computed here once per field:
+      ("dot", n, i, j)   kind 0 over the first n elements of tables i and j
+      (kind, BIG_N)      kinds 1, 2, 3 over the whole tables"""
+    m = o.modulus(field)
+    rng = np.random.default_rng(900 + field)
+    tabs = [rand_limbs(rng, BIG_N) for _ in range(5)]
+    u_limbs = rand_limbs(rng, 1)
+    T = [np.array(ints(t), dtype=object) for t in tabs]
+    u, ri = ints(u_limbs)[0], pow(o.R, -1, m)
+    exp = {}
+    # kind 0: out = R^-1 * sum a[i] b[i]
+    prod = [T[j] * T[j + 1] for j in range(3)]
+    for n in (BIG_N, 65537, 131329):
+        exp["dot", n, 0, 1] = [ri * int(prod[0][:n].sum()) % m]
+    for j in range(3):
+        exp["dot", 1 << 18, j, j + 1] = [ri * int(prod[j][:1 << 18].sum()) % m]
+    del prod
+    h = BIG_N // 2
+    lo, d = [t[:h] for t in T], [t[h:] - t[:h] for t in T]
+    at = lambda k, t: lo[k] + t * d[k]                                  # the table bound to t, as an integer congruent to the device's
+    # kind 1: out[t] = R^-1 * sum p_t[i] q_t[i], t = 0, 2
+    exp[1, BIG_N] = [ri * int((at(0, t) * at(1, t)).sum()) % m for t in (0, 2)]
+    # kind 2: out[t] = R^-1 * sum eq_t[i] * (R^-1 * (a_t[i] b_t[i] - u c_t[i]) - e_t[i]), t = 0, 2, 3: the products a b and u c carry
+    # one R^-1, the outer product by eq a second one
+    exp[2, BIG_N] = [ri * int((at(0, t) * (ri * (at(1, t) * at(2, t) - u * at(3, t)) % m - at(4, t))).sum()) % m for t in (0, 2, 3)]
+    # kind 3: out = R^-1 * sum a[i] b[h + i],  R^-1 * sum a[h + i] b[i]
+    exp[3, BIG_N] = [ri * int((T[0][:h] * T[1][h:]).sum()) % m, ri * int((T[0][h:] * T[1][:h]).sum()) % m]
+    return tabs, u_limbs, exp
+
+
+@pytest.mark.parametrize("field", FIELDS)
+@pytest.mark.parametrize("kind", [0, 1, 2, 3])
+def test_reductions_above_the_grid_cap(ctx, field, kind):
+    """n = 2^19: h = 2^18 for the rounds (512 workgroups of two strides each, 512 partials: two per lane of the final pass), and
+    four strides for the dot product."""
+    tabs, u, exp = big_reduction(field)
+    d = [_dev(t) for t in tabs[:5 if kind == 2 else 2]]
+    got = ctx.reduce(field, kind, d, BIG_N, u=u if kind == 2 else None)
+    assert ints(got) == (exp["dot", BIG_N, 0, 1] if kind == 0 else exp[kind, BIG_N])
+
+
+@pytest.mark.parametrize("field", FIELDS)
+@pytest.mark.parametrize("n", [65537, 131329])
+def test_dot_product_at_the_stride_and_partial_edges(ctx, field, n):
+    """65537: 257 partials, the first lane of the final pass takes a second one; 131329: 514 workgroups' worth on a grid of 512,
+    so only workgroups 0 and 1 stride, the second one with a single lane."""
+    tabs, _, exp = big_reduction(field)
+    got = ctx.reduce(field, 0, [_dev(tabs[0][:n]), _dev(tabs[1][:n])], n)
+    assert ints(got) == exp["dot", n, 0, 1]
+
+
+# -- vdf_ipa_scalars / vdf_scale_pattern at the edges of n_j: 2 (h = 1), n (no wrap), n below one workgroup
+def _ipa_helpers(ctx, field, n, nj, seed):
+    m = o.modulus(field)
+    rng = np.random.default_rng(seed)
+    a, s = _randm(rng, m, nj), _randm(rng, m, n)
+    x, = _randm(rng, m, 1)
+    xi = pow(x, -1, m)
+    sL, sR = _dev(np.full((n, 4), ONES, dtype="<u8")), _dev(np.full((n, 4), ONES, dtype="<u8"))
+    ds = _dev(mont(s, m))
+    da = _dev(np.concatenate([mont(a, m), np.full((1, 4), ONES, dtype="<u8")]))     # a sentinel past a's n_j elements: never read
+    ctx.ipa_scalars(field, da, ds, n, nj, sL, sR)
+    ctx.scale_pattern(field, ds, n, nj, mont([xi], m), mont([x], m))
+    ctx.sync()
+    h = nj // 2
+    eL = [s[t] * a[(t % nj) - h] % m if (t % nj) >= h else 0 for t in range(n)]
+    eR = [s[t] * a[(t % nj) + h] % m if (t % nj) < h else 0 for t in range(n)]
+    assert ints(_host(sL)) == ints(mont(eL, m)) and ints(_host(sR)) == ints(mont(eR, m))
+    assert ints(_host(ds)) == ints(mont([s[t] * (x if (t % nj) >= h else xi) % m for t in range(n)], m))
+
+
+@pytest.mark.parametrize("field", FIELDS)
+@pytest.mark.parametrize("n,nj", [(2, 2), (64, 2), (64, 64), (4096, 2), (4096, 4096), (1 << 13, 256)])
+def test_ipa_round_helpers_at_the_edges(ctx, field, n, nj):
+    _ipa_helpers(ctx, field, n, nj, 3 * n + nj + field)
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_ipa_round_helpers_refuse_bad_lengths(ctx, field):
+    m = o.modulus(field)
+    rng = np.random.default_rng(60 + field)
+    bufs = [rand_limbs(rng, 1024) for _ in range(4)]
+    da, ds, sL, sR = (_dev(b) for b in bufs)
+    x = mont([3], m)
+    for n, nj in [(1024, 0), (1024, 1), (64, 128), (64, 6), (6, 2), (0, 2)]:
+        with pytest.raises(Exception):
+            ctx.ipa_scalars(field, da, ds, n, nj, sL, sR)
+        with pytest.raises(Exception):
+            ctx.scale_pattern(field, ds, n, nj, x, x)
+        ctx.sync()
+        for dv, b in zip((da, ds, sL, sR), bufs):
+            assert np.array_equal(_host(dv), b), (n, nj)
+
+
+# -- vdf_pair_table at depth: the variable-to-bit order at every index bit
+@pytest.mark.parametrize("field", FIELDS)
+def test_pair_table_k18_is_the_eq_table(ctx, field):
+    m, k = o.modulus(field), 18
+    r = _randm(np.random.default_rng(180 + field), m, k)
+    out = _dev(np.full((1 << k, 4), ONES, dtype="<u8"))
+    ctx.pair_table(field, mont([(1 - x) % m for x in r], m), mont(r, m), k, out)
+    ctx.sync()
+    assert ints(_host(out)) == ints(mont(sp.eq_table(r, m), m))
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_pair_table_k22_samples(ctx, field):
+    """128 MB of table, sampled: both ends, every index of a single set bit and of a single clear bit (variable j is bit k-1-j, so
+    each of these pins one variable's position), and 64 random indices."""
+    import torch
+    m, k = o.modulus(field), 22
+    n = 1 << k
+    rng = np.random.default_rng(220 + field)
+    lo, hi = _randm(rng, m, k), _randm(rng, m, k)
+    idx = [0, n - 1] + [1 << b for b in range(k)] + [n - 1 - (1 << b) for b in range(k)] + [int(i) for i in rng.integers(0, n, size=64)]
+    out = torch.full((n, 4), -1, dtype=torch.int64, device="cuda")
+    ctx.pair_table(field, mont(lo, m), mont(hi, m), k, out)
+    ctx.sync()
+    got = unmont(_host(out[torch.tensor(idx, device="cuda")]), m)
+    for i, g in zip(idx, got):
+        e = 1
+        for j in range(k):
+            e = e * (hi[j] if (i >> (k - 1 - j)) & 1 else lo[j]) % m
+        assert g == e, i
+
+
+def test_pair_table_refuses_25_variables(ctx):
+    c = mont([1] * 25, Q)
+    with pytest.raises(Exception):
+        ctx.pair_table(F, c, c, 25, _dev(np.zeros((8, 4), dtype="<u8")))
