@@ -374,6 +374,14 @@ int  vdf_minroot_step_segment_packed(vdf_ctx* ctx, int field, const vdf_fe* trac
  * final_i = i_end (the step's last round counter; host memory).  out has 3t + 1 elements; trace_xy as everywhere
  * (trace_xy[k] = (x_k, y_k), k = 0..t, device memory). */
 int  vdf_minroot_forward_segment(vdf_ctx* ctx, int field, const vdf_fe* trace_xy, uint64_t t, const vdf_fe* i_end, vdf_fe* out);
+/* The same for `lanes` chains at once (vdf_nova.h VDF_CIRCUIT_MINROOT_FORWARD_LANES), ONE launch: lane l's trace starts
+ * lane_stride entries of 64 B after lane l - 1's (lane_stride >= t + 1: the layout vdf_minroot_inverse_walk's groups and
+ * vdf_minroot_forward_walk's walk_stride write) and its 3t + 1 variables follow lane l - 1's in out (lanes x (3t + 1) elements).
+ * i_end: `lanes` elements in HOST memory, handed to the kernel as arguments (no staging copy, no synchronisation).
+ * 1 <= lanes <= VDF_MINROOT_MAX_LANES.  Byte for byte what `lanes` calls of vdf_minroot_forward_segment write. */
+#define VDF_MINROOT_MAX_LANES 16
+int  vdf_minroot_forward_segment_lanes(vdf_ctx* ctx, int field, const vdf_fe* trace_xy, size_t lane_stride, uint64_t t, size_t lanes,
+                                       const vdf_fe* i_end, vdf_fe* out);
 /* vdf_spmv3(shape, z2) followed by vdf_cross_term(Az1, Bz1, Cz1, Az2, Bz2, Cz2, u1): writes Az2, Bz2, Cz2
  * (num_cons each) and T.  u1: host memory.  (nova-snark NIFS::prove -> commit_T, K4 + K5.) */
 int  vdf_nifs_cross_term(vdf_ctx* ctx, const vdf_shape* shape, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,
@@ -411,6 +419,14 @@ int  vdf_nifs_cross_term_minroot(vdf_ctx* ctx, int field, int vars_per_round, ui
 int  vdf_nifs_cross_term_minroot_forward(vdf_ctx* ctx, int field, uint64_t t, size_t seg_begin, size_t one_col, size_t row_begin,
                                          const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1, const vdf_fe* u1,
                                          vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T);
+/* The forward stencil over `lanes` lanes, ONE launch, rows [row_begin, row_begin + lanes (3t + 1)): lane l's variables are
+ * seg_begin + l (3t + 1) .. + 3t (x', tmp1, tmp2 per round, then final_i), its rows row_begin + l (3t + 1) .., and ITS
+ * z_in = (x_0, y_0, i) sits at seg_begin - 3 lanes + 3 l .. + 2, where the single-lane stencil reads seg_begin - 3 .. - 1.
+ * Operands and guarantees as vdf_nifs_cross_term_minroot_forward (exact for any z2, a `one` that is not 1 included).
+ * libvdf_nova.so reports this stencil as code 6 (vdf_nova_pp_stencil). */
+int  vdf_nifs_cross_term_minroot_forward_lanes(vdf_ctx* ctx, int field, uint64_t t, size_t lanes, size_t seg_begin, size_t one_col,
+                                               size_t row_begin, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,
+                                               const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T);
 /* The same rows with the PREVIOUS fold of those rows applied on the way.  A prover that keeps A z, B z, C z of the running
  * instance folds them after every step (X1 <- X1 + r X2); for the stencil rows the fresh vectors X2 of the previous step are
  * exactly what this call is about to overwrite in Az2 / Bz2 / Cz2.  So, per row: Az1 += r Az2, Bz1 += r Bz2, Cz1 += r Cz2

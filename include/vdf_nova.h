@@ -85,9 +85,16 @@ typedef struct vdf_snark vdf_snark;       /* NovaVDFProof::Compressed, :54 */
  * of a round and x -> x^5 is a bijection on Fq.  A proof of this kind states z0 = the chain's INITIAL state and zi = its final
  * state, and its steps are proved in the order they are evaluated (vdf_nova_circuits_forward_begin, vdf_nova_eval_and_prove);
  * verify, compress, the batch calls and both wire formats work on it unchanged.  packed_commit does not apply; fold_fused
- * falls back to the unfused fold. */
+ * falls back to the unfused fold.
+ * FORWARD_LANES: L forward circuits side by side in ONE step circuit of arity 3L, z = (x_0, y_0, i_0, x_1, y_1, i_1, ...): every
+ * lane carries its own round counter, so any L evaluations of equal length share one running proof, one compress, one verify
+ * and one blob on the wire.  Lane l's 3t + 1 variables sit at seg_begin + l (3t + 1) (x', tmp1, tmp2 per round, then final_i),
+ * its constraints at row_begin + l (3t + 1), and the 3L inputs in the variables right in front of seg_begin, lane l at
+ * seg_begin - 3L + 3l.  Made by vdf_nova_public_params_lanes only; outside the rounds a lane costs about 1,059 constraints (the
+ * longer z0 / zi the two state hashes absorb), host-synthesised.  packed_commit does not apply; fold_fused falls back. */
 enum { VDF_CIRCUIT_MINROOT_BOUND = 0, VDF_CIRCUIT_MINROOT_REFERENCE = 1, VDF_CIRCUIT_CUSTOM = 2 /* vdf_step_circuit, below */,
-       VDF_CIRCUIT_MINROOT_FORWARD = 3 };
+       VDF_CIRCUIT_MINROOT_FORWARD = 3, VDF_CIRCUIT_MINROOT_FORWARD_LANES = 4 };
+#define VDF_NOVA_MAX_LANES 16             /* arity 48, under the seam's cap of 64 */
 enum { VDF_SIDE_PRIMARY = 0, VDF_SIDE_SECONDARY = 1 };
 
 /* public_params(num_iters_per_step), :232-237: both augmented circuits synthesised once for their R1CS shapes,
@@ -176,6 +183,14 @@ int  vdf_nova_public_params_ro(vdf_ctx* ctx, uint64_t num_iters_per_step, int ci
                                const vdf_nova_ro_params* ro, const vdf_nova_tuning* tuning, vdf_pp** out);
 /* wall-clock milliseconds of the stages of the call that made `pp`: [0] both shapes + digest (host), [1] shapes to the
  * device, [2] generators, [3] fixed-base tables (the packed commitment's included), [4] digit tables, [5] the rest, [6] total */
+/* Parameters of the forward circuit in `lanes` lanes (VDF_CIRCUIT_MINROOT_FORWARD_LANES), t rounds per lane and step.
+ * lanes == 1 returns exactly the parameters of VDF_CIRCUIT_MINROOT_FORWARD (same kind, same digest); lanes of 0 or above
+ * VDF_NOVA_MAX_LANES is VDF_ERR_BAD_ARG.  ro / tuning: NULL = the defaults.  The digest is the oracle's `params` for
+ * tests/lanes_spec.py's LanesForwardCircuit with digest_shapes(t, ...) as for the forward circuit.  tuning.stencil = 0 keeps
+ * the generic rows kernel (the same bytes); vdf_nova_eval_and_prove refuses such parameters (its evaluator is one chain). */
+int  vdf_nova_public_params_lanes(vdf_ctx* ctx, uint64_t num_iters_per_step, size_t lanes, int gens_family, const vdf_nova_ro_params* ro,
+                                  const vdf_nova_tuning* tuning, vdf_pp** out);
+size_t vdf_nova_pp_lanes(const vdf_pp* pp);     /* 1 for every kind but VDF_CIRCUIT_MINROOT_FORWARD_LANES */
 int  vdf_nova_pp_setup_ms(const vdf_pp* pp, double ms[7]);
 /* bytes of HBM held per side: generators, their fixed-base table, the digit table (0 = none; *skipped bit s set when
  * side s wanted one and it did not fit).  The primary side's figures include the derived generators of the packed
@@ -195,8 +210,10 @@ int  vdf_nova_pp_early_rows(const vdf_pp* pp, uint64_t* begin, uint64_t* len);
  * shape's triples when the parameters were made -- their cross term runs without the sparse matrices
  * (vdf_hip.h vdf_nifs_cross_term_minroot); 5 (VDF_STENCIL_FORWARD): the forward circuit's stencil
  * (vdf_nifs_cross_term_minroot_forward) -- a CODE, not a count of variables per round (that circuit has 3; 3 and 4 were
- * taken); 0: they run through the generic sparse kernel (a custom circuit, or no early rows) */
-enum { VDF_STENCIL_FORWARD = 5 };
+ * taken); 0: they run through the generic sparse kernel (a custom circuit, or no early rows);
+ * 6 (VDF_STENCIL_FORWARD_LANES): the forward circuit in lanes, all L (3t + 1) early rows as one run
+ * (vdf_nifs_cross_term_minroot_forward_lanes) -- a code like 5 */
+enum { VDF_STENCIL_FORWARD = 5, VDF_STENCIL_FORWARD_LANES = 6 };
 int  vdf_nova_pp_stencil(const vdf_pp* pp);
 /* The same answer without a device (host only): builds the shape of the built-in step circuit at t, finds the early rows
  * and compares them with the stencil; returns 5 / 4 / 3 / 0 (negative: an error code).  Outputs may be NULL. */
@@ -264,6 +281,23 @@ int  vdf_nova_circuits_push_trace(vdf_circuits* c, const vdf_fe* trace_xy);
  * vdf_nova_circuits_release on a forward chain also drops the host trace of a step pushed by vdf_nova_circuits_push_trace:
  * a long stream holds a bounded number of steps. */
 int  vdf_nova_circuits_push_checkpoints(vdf_circuits* c, uint64_t every, const vdf_state* states);
+/* ---- forward chains in LANES (for parameters of vdf_nova_public_params_lanes) -------------------------------------------
+ * An empty chain of steps that advance `lanes` evaluations by t rounds each; z0_primary (3 lanes elements) = the initial states,
+ * flattened.  A lanes chain of ONE lane is a forward chain (every call above works on it); on a chain of more lanes the
+ * single-lane push calls return VDF_ERR_BAD_ARG.  Everything else -- materialize / release / memory / prove_step /
+ * prove_recursively[_windowed] -- works as on a forward chain, a step's trace being `lanes` traces back to back, t + 1 entries each. */
+int  vdf_nova_circuits_lanes_begin(uint64_t t, size_t lanes, const vdf_state* initial, vdf_fe* z0_primary, vdf_circuits** out);
+/* Appends one step from `lanes` host traces, lane l's at trace_xy + 2 l lane_stride (lane_stride >= t + 1 entries of 64 B), each
+ * checked as vdf_nova_circuits_push_trace checks one; a bad lane appends nothing and vdf_nova_last_error names it. */
+int  vdf_nova_circuits_push_traces(vdf_circuits* c, const vdf_fe* trace_xy, size_t lane_stride);
+/* Appends one step from every lane's t / every + 1 states: lane l's are states[l lane_stride + k], k = 0 .. t / every, each lane
+ * checked as vdf_nova_circuits_push_checkpoints checks one (a bad lane appends nothing, vdf_nova_last_error names it).  With
+ * lane_stride = rounds_total / every + 1 and the pointer advanced by step * t / every, the output of vdf_minroot_eval_batch
+ * feeds in unchanged. */
+int  vdf_nova_circuits_push_checkpoints_lanes(vdf_circuits* c, uint64_t every, const vdf_state* states, size_t lane_stride);
+size_t vdf_nova_circuits_lanes(const vdf_circuits* c);
+/* result / input of lane `lane` of circuit k (vdf_nova_circuit_states gives lane 0) */
+int  vdf_nova_circuit_lane_states(const vdf_circuits* c, size_t k, size_t lane, vdf_state* result, vdf_state* input);
 size_t vdf_nova_circuits_len(const vdf_circuits* c);
 /* result / input of circuit k (k = 0 is proved first): InverseMinRootCircuit.result / .input */
 int  vdf_nova_circuit_states(const vdf_circuits* c, size_t k, vdf_state* result, vdf_state* input);
@@ -388,6 +422,19 @@ int  vdf_nova_shape_digest_ro(const vdf_nova_ro_params* ro, uint64_t num_iters_p
 int  vdf_nova_aug_synthesize_ro(const vdf_nova_ro_params* ro, int side, uint64_t num_iters_per_step, int circuit_kind,
                                 const vdf_nova_aug_inputs* in, const vdf_state* result, const vdf_state* input, vdf_fe* W, size_t w_cap,
                                 size_t* num_vars, size_t* num_cons, vdf_fe X[2], vdf_fe z_next[3]);
+
+/* the host-only entry points for the forward circuit in lanes (lanes = 1: the forward circuit itself).  shape_stencil_lanes
+ * returns 6 (5 for one lane) when the L (3t + 1) early rows are one run and match the stencil.  aug_synthesize_lanes is the
+ * PRIMARY circuit only: z0 / zi of `in` are ignored and read from the arrays z0 / zi (3 lanes elements each); results / inputs:
+ * one state per lane; z_next: 3 lanes elements. */
+int  vdf_nova_shape_digest_lanes(const vdf_nova_ro_params* ro, uint64_t num_iters_per_step, size_t lanes, int gens_family, uint8_t out[32],
+                                 uint64_t sizes[2][3]);
+int  vdf_nova_shape_stencil_lanes(uint64_t t, size_t lanes, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin);
+int  vdf_nova_shape_export_lanes(uint64_t num_iters_per_step, size_t lanes, int side, uint64_t nnz[3], uint32_t* const rows[3],
+                                 uint32_t* const cols[3], vdf_fe* const vals[3]);
+int  vdf_nova_aug_synthesize_lanes(const vdf_nova_ro_params* ro, uint64_t num_iters_per_step, size_t lanes, const vdf_nova_aug_inputs* in,
+                                   const vdf_fe* z0, const vdf_fe* zi, const vdf_state* results, const vdf_state* inputs, vdf_fe* W,
+                                   size_t w_cap, size_t* num_vars, size_t* num_cons, vdf_fe X[2], vdf_fe* z_next);
 
 /* of the calling thread's last augmented-circuit synthesis: how many slope inverses the native pre-pass queued (batched
  * inversion) and how many of them were wrong or unused (0 for well-formed inputs: the queue is only an accelerator) */

@@ -85,6 +85,7 @@ PROTOTYPES = {
     "vdf_minroot_step_z_packed": (_i, [_vp, _i, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdf_minroot_step_segment": (_i, [_vp, _i, _vp, _u64, _vp, _i, _vp]),
     "vdf_minroot_forward_segment": (_i, [_vp, _i, _vp, _u64, _vp, _vp]),
+    "vdf_minroot_forward_segment_lanes": (_i, [_vp, _i, _vp, _sz, _u64, _sz, _vp, _vp]),
     "vdf_minroot_step_segment_packed": (_i, [_vp, _i, _vp, _u64, _vp, _vp, _vp, _vp]),
     "vdf_minroot_inverse_walk": (_i, [_vp, _i, _vp, _sz, _u64, _vp, _sz, _sz, _sz, _sz]),
     "vdf_minroot_check_batch": (_i, [_vp, _i, _vp, _vp, _sz, _u64, _vp]),
@@ -96,6 +97,7 @@ PROTOTYPES = {
     "vdf_nifs_cross_term_rows": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdf_nifs_cross_term_minroot": (_i, [_vp, _i, _i, _u64, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdf_nifs_cross_term_minroot_forward": (_i, [_vp, _i, _u64, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vdf_nifs_cross_term_minroot_forward_lanes": (_i, [_vp, _i, _u64, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdf_nifs_cross_term_minroot_fold": (_i, [_vp, _i, _i, _u64, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdf_fold_many": (_i, [_vp, _i, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "vdf_pair_table": (_i, [_vp, _i, _vp, _vp, _i, _vp]),

@@ -104,7 +104,8 @@ int job_resolve(const vdf_circuits* c, int* bad, size_t bad_first, size_t bad_co
   size_t first_bad = (size_t)-1;
   for (size_t li = 0; li < j->steps.size(); ++li) {
     bool ok = true;
-    for (size_t m = 0; m < j->per_step; ++m) ok &= w.h_ok[li * j->per_step + m] == 1;
+    const size_t per = j->lanes * j->per_step;                          // every lane's walks of this step
+    for (size_t m = 0; m < per; ++m) ok &= w.h_ok[li * per + m] == 1;
     if (ok) continue;
     const size_t k = j->steps[li];
     lose(k);
@@ -200,6 +201,7 @@ int vdf_nova_circuits_push_trace(vdf_circuits* c, const vdf_fe* trace_xy) {
   return nova_guard([&]() -> int {
     if (!c || !trace_xy) return fail(VDF_ERR_BAD_ARG, "null argument");
     if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_forward_begin)");
+    if (c->lanes > 1) return fail(VDF_ERR_BAD_ARG, "a chain of more than one lane: vdf_nova_circuits_push_traces");
     const uint64_t t = c->forward_t;
     if (memcmp(&trace_xy[0], &c->end.x, 32) != 0 || memcmp(&trace_xy[1], &c->end.y, 32) != 0)
       return fail(VDF_ERR_BAD_ARG, "the trace does not start at the chain's current end");
@@ -219,6 +221,7 @@ int vdf_nova_circuits_push_checkpoints(vdf_circuits* c, uint64_t every, const vd
   return nova_guard([&]() -> int {
     if (!c || !states) return fail(VDF_ERR_BAD_ARG, "null argument");
     if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_forward_begin)");
+    if (c->lanes > 1) return fail(VDF_ERR_BAD_ARG, "a chain of more than one lane: vdf_nova_circuits_push_checkpoints_lanes");
     const uint64_t t = c->forward_t;
     if (every == 0 || t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
     if (!c->v.empty() && c->checkpoints)
@@ -231,6 +234,97 @@ int vdf_nova_circuits_push_checkpoints(vdf_circuits* c, uint64_t every, const vd
     c->checkpoints = true;
     return VDF_OK;
   });
+}
+// ---- forward chains in lanes: a step advances `lanes` evaluations, its trace is their traces back to back ------------------
+int vdf_nova_circuits_lanes_begin(uint64_t t, size_t lanes, const vdf_state* initial, vdf_fe* z0_primary, vdf_circuits** out) {
+  if (lanes == 1) return vdf_nova_circuits_forward_begin(t, initial, z0_primary, out);     // one lane IS a forward chain
+  return nova_guard([&]() -> int {
+    if (!initial || !z0_primary || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    if (lanes == 0 || lanes > VDF_NOVA_MAX_LANES) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_NOVA_MAX_LANES");
+    std::unique_ptr<vdf_circuits> cs(new vdf_circuits());
+    cs->forward = true;
+    cs->forward_t = t;
+    cs->lanes = lanes;
+    for (size_t l = 0; l < lanes; ++l) cs->lane_end.push_back(load_state(&initial[l]));
+    cs->end = cs->lane_end[0];
+    memcpy(z0_primary, initial, 96 * lanes);                           // z0 = the lanes' initial states, flattened
+    *out = cs.release();
+    return VDF_OK;
+  });
+}
+int vdf_nova_circuits_push_traces(vdf_circuits* c, const vdf_fe* trace_xy, size_t lane_stride) {
+  if (c && trace_xy && c->forward && c->lanes == 1) return vdf_nova_circuits_push_trace(c, trace_xy);
+  return nova_guard([&]() -> int {
+    if (!c || !trace_xy) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_lanes_begin)");
+    const uint64_t t = c->forward_t;
+    const size_t L = c->lanes;
+    if (lane_stride < t + 1) return fail(VDF_ERR_BAD_ARG, "lane_stride must be at least t + 1");
+    const Field& F = field(VDF_FIELD_FQ);
+    Circuit cc;
+    cc.t = t;
+    cc.lane_input = c->lane_end;
+    cc.lane_result.resize(L);
+    for (size_t l = 0; l < L; ++l) {                                   // every lane checked before anything is appended
+      const vdf_fe* tr = trace_xy + 2 * l * lane_stride;
+      if (memcmp(&tr[0], &c->lane_end[l].x, 32) != 0 || memcmp(&tr[1], &c->lane_end[l].y, 32) != 0)
+        return fail(VDF_ERR_BAD_ARG, "lane " + std::to_string(l) + ": the trace does not start at the lane's current end");
+      memcpy(&cc.lane_result[l].x, &tr[2 * t], 32);
+      memcpy(&cc.lane_result[l].y, &tr[2 * t + 1], 32);
+      cc.lane_result[l].i = add(c->lane_end[l].i, from_u64(t, F), F);
+    }
+    cc.trace_xy.reserve(L * 2 * (t + 1));
+    for (size_t l = 0; l < L; ++l) {
+      const Fe* tr = (const Fe*)trace_xy + 2 * l * lane_stride;
+      cc.trace_xy.insert(cc.trace_xy.end(), tr, tr + 2 * (t + 1));
+    }
+    cc.input = cc.lane_input[0]; cc.result = cc.lane_result[0];
+    c->lane_end = cc.lane_result;
+    c->end = cc.result;
+    c->v.push_back(std::move(cc));
+    return VDF_OK;
+  });
+}
+int vdf_nova_circuits_push_checkpoints_lanes(vdf_circuits* c, uint64_t every, const vdf_state* states, size_t lane_stride) {
+  if (c && states && c->forward && c->lanes == 1) return vdf_nova_circuits_push_checkpoints(c, every, states);
+  return nova_guard([&]() -> int {
+    if (!c || !states) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_lanes_begin)");
+    const uint64_t t = c->forward_t;
+    const size_t L = c->lanes;
+    if (every == 0 || t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
+    const size_t per = (size_t)(t / every);
+    if (lane_stride < per + 1) return fail(VDF_ERR_BAD_ARG, "lane_stride must be at least t / every + 1");
+    if (!c->v.empty() && c->checkpoints)
+      for (const Circuit& k : c->v) if (k.every && k.every != every) return fail(VDF_ERR_BAD_ARG, "`every` differs from the chain's earlier checkpoint steps");
+    for (size_t l = 0; l < L; ++l) {                                   // every lane checked before anything is appended
+      const vdf_state* st = states + l * lane_stride;
+      if (memcmp(&st[0], &c->lane_end[l], 96) != 0) return fail(VDF_ERR_BAD_ARG, "lane " + std::to_string(l) + ": states[0] is not the lane's current end");
+      if (check_counters(st, per, c->lane_end[l].i, every) != VDF_OK) return fail(VDF_ERR_BAD_ARG, "lane " + std::to_string(l) + ": " + vdf_nova_last_error());
+    }
+    Circuit cc;
+    cc.t = t; cc.every = every;
+    cc.lane_input = c->lane_end;
+    cc.cp.reserve(L * (per + 1));
+    for (size_t l = 0; l < L; ++l)
+      for (size_t m = 0; m <= per; ++m) cc.cp.push_back(load_state(&states[l * lane_stride + m]));
+    for (size_t l = 0; l < L; ++l) cc.lane_result.push_back(cc.cp[l * (per + 1) + per]);
+    cc.input = cc.lane_input[0]; cc.result = cc.lane_result[0];
+    c->lane_end = cc.lane_result;
+    c->end = cc.result;
+    c->v.push_back(std::move(cc));
+    c->checkpoints = true;
+    return VDF_OK;
+  });
+}
+size_t vdf_nova_circuits_lanes(const vdf_circuits* c) { return c ? c->lanes : 0; }
+int vdf_nova_circuit_lane_states(const vdf_circuits* c, size_t k, size_t lane, vdf_state* result, vdf_state* input) {
+  if (!c || k >= c->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
+  if (lane >= c->lanes) return fail(VDF_ERR_BAD_LENGTH, "lane out of range");
+  const Circuit& cc = c->v[k];
+  if (result) store_state(result, c->lanes > 1 ? cc.lane_result[lane] : cc.result);
+  if (input) store_state(input, c->lanes > 1 ? cc.lane_input[lane] : cc.input);
+  return VDF_OK;
 }
 // ---- traces on the device ---------------------------------------------------------------------------------------
 int vdf_nova_circuits_materialize(vdf_ctx* ctx, vdf_circuits* c, size_t first, size_t count, int wait, int* bad) {
@@ -256,10 +350,12 @@ int vdf_nova_circuits_materialize(vdf_ctx* ctx, vdf_circuits* c, size_t first, s
     }
     vdf_ctx* q = w.side;
     const Circuit& c0 = c->v[j->steps[0]];
-    const uint64_t t = c0.t, trace_bytes = (t + 1) * 64;
+    const size_t L = c->lanes;                                          // a step's trace: its lanes' traces back to back
+    const uint64_t t = c0.t, trace_bytes = L * (t + 1) * 64;
     j->every = c0.every;
     j->per_step = (size_t)(t / c0.every);
-    j->walks = j->steps.size() * j->per_step;
+    j->lanes = L;
+    j->walks = j->steps.size() * L * j->per_step;
     if (j->steps.size() > (~(uint64_t)0 >> 1) / trace_bytes) return fail(VDF_ERR_OOM, "the traces do not fit");
     // the windowed prove_recursively's spare allocation, when it is exactly this size; anything else is asked of the device
     if (w.spare && w.spare.use_count() == 1 && w.spare->ctx == ctx && w.spare->bytes == j->steps.size() * trace_bytes) j->block = std::move(w.spare);
@@ -283,12 +379,16 @@ int vdf_nova_circuits_materialize(vdf_ctx* ctx, vdf_circuits* c, size_t first, s
       std::vector<St> from(job->walks), to(job->walks);
       for (size_t li = 0; li < job->steps.size(); ++li) {
         const Circuit& k = c->v[job->steps[li]];
-        for (size_t m = 0; m < job->per_step; ++m) { from[li * job->per_step + m] = k.cp[m + 1]; to[li * job->per_step + m] = k.cp[m]; }
+        for (size_t l = 0; l < L; ++l)                                  // walk (li L + l) per_step + m: lane l's interval m
+          for (size_t m = 0; m < job->per_step; ++m) {
+            const size_t wk = (li * L + l) * job->per_step + m, at = l * (job->per_step + 1) + m;
+            from[wk] = k.cp[at + 1]; to[wk] = k.cp[at];
+          }
       }
       memset(w.h_ok, 0, job->walks * sizeof(int));
       int rc = vdf_dev_memcpy(q, w.d_walk, from.data(), job->walks * 96);
       if (rc == VDF_OK) rc = vdf_dev_memcpy(q, w.d_expect, to.data(), job->walks * 96);
-      if (rc == VDF_OK) rc = vdf_minroot_trace_heads(q, (const vdf_state*)w.d_expect, job->steps.size(), job->per_step, (vdf_fe*)job->block->d, (size_t)(t + 1));
+      if (rc == VDF_OK) rc = vdf_minroot_trace_heads(q, (const vdf_state*)w.d_expect, job->steps.size() * L, job->per_step, (vdf_fe*)job->block->d, (size_t)(t + 1));
       if (rc != VDF_OK) { rc = fail(rc, std::string("walk set-up: ") + vdf_last_error(q)); w.job.reset(); return rc; }
     }
     for (size_t li = 0; li < job->steps.size(); ++li) {                 // resident from now on; a walk that misses takes it away again

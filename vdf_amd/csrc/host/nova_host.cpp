@@ -23,6 +23,20 @@ RelaxedInst to_relaxed(const Inst& in, const Field& own) {
 }
 
 std::unique_ptr<StepCircuit> make_primary_circuit(const vdf_pp* pp, const Circuit* c, bool device_rounds) {
+  if (pp->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES) {
+    std::unique_ptr<LanesForwardCircuit> m(new LanesForwardCircuit());
+    m->t = pp->t;
+    m->device_rounds = device_rounds;
+    m->blank = c == nullptr;
+    m->results.assign(pp->lanes, MinRootState{zero(), zero(), zero()});
+    m->inputs = m->results;
+    if (c)
+      for (size_t l = 0; l < pp->lanes; ++l) {
+        m->results[l] = MinRootState{c->lane_result[l].x, c->lane_result[l].y, c->lane_result[l].i};
+        m->inputs[l] = MinRootState{c->lane_input[l].x, c->lane_input[l].y, c->lane_input[l].i};
+      }
+    return std::unique_ptr<StepCircuit>(m.release());
+  }
   if (pp->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD) {
     std::unique_ptr<ForwardMinRootCircuit> m(new ForwardMinRootCircuit());
     m->t = pp->t;
@@ -127,6 +141,11 @@ namespace {
 bool builtin_circuit(int kind) {
   return kind == VDF_CIRCUIT_MINROOT_BOUND || kind == VDF_CIRCUIT_MINROOT_REFERENCE || kind == VDF_CIRCUIT_MINROOT_FORWARD;
 }
+// the forward circuit, alone or in lanes: steps in the order of evaluation, z_i = the step's input
+bool forward_kind(int kind) { return kind == VDF_CIRCUIT_MINROOT_FORWARD || kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES; }
+static_assert(VDF_NOVA_MAX_LANES == VDF_MINROOT_MAX_LANES, "the lanes kernels take what the lanes circuit has");
+bool lanes_valid(size_t lanes) { return lanes >= 1 && lanes <= VDF_NOVA_MAX_LANES; }
+int lanes_kind(size_t lanes) { return lanes == 1 ? VDF_CIRCUIT_MINROOT_FORWARD : VDF_CIRCUIT_MINROOT_FORWARD_LANES; }
 // variables per round of a built-in circuit
 int vars_per_round(int kind) { return kind == VDF_CIRCUIT_MINROOT_REFERENCE ? 4 : 3; }
 
@@ -145,10 +164,12 @@ AugInputs blank_inputs(size_t arity) {
 struct HostShape { Coo m[3]; size_t num_cons = 0, num_vars = 0, step_begin = 0, step_end = 0; };
 
 // both augmented circuits in shape mode (PublicParams::setup, src/nova/proof.rs:236)
-int build_shapes(uint64_t t, int circuit_kind, HostShape out[2], const vdf_step_circuit* custom = nullptr, const RoInstance* ro = nullptr) {
+int build_shapes(uint64_t t, int circuit_kind, HostShape out[2], const vdf_step_circuit* custom = nullptr, const RoInstance* ro = nullptr,
+                 size_t lanes = 1) {
   vdf_pp tmp;
   tmp.t = t;
   tmp.circuit_kind = circuit_kind;
+  tmp.lanes = lanes;
   for (int side = 0; side < 2; ++side) {
     CS cs(side_field(side), true, ro);
     std::unique_ptr<StepCircuit> step;
@@ -584,6 +605,80 @@ int vdf_nova_aug_synthesize_ro(const vdf_nova_ro_params* rop, int side, uint64_t
   });
 }
 
+// ---- the forward circuit in lanes, host only --------------------------------------------------------------------------
+int vdf_nova_shape_digest_lanes(const vdf_nova_ro_params* rop, uint64_t t, size_t lanes, int gens_family, uint8_t out[32], uint64_t sizes[2][3]) {
+  return nova_guard([&]() -> int {
+    bool bad;
+    const RoInstance* ro = ro_from_abi(rop, &bad);
+    if (bad) return fail(VDF_ERR_BAD_ARG, "unsupported RO parameter block");
+    if (t == 0 || t > (1ull << 24) || !out || !lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    HostShape sh[2];
+    build_shapes(t, lanes_kind(lanes), sh, nullptr, ro, lanes);
+    digest_shapes(t, gens_family, sh, out, ro);
+    if (sizes)
+      for (int s = 0; s < 2; ++s) {
+        sizes[s][0] = sh[s].num_cons; sizes[s][1] = sh[s].num_vars;
+        sizes[s][2] = sh[s].m[0].rows.size() + sh[s].m[1].rows.size() + sh[s].m[2].rows.size();
+      }
+    return VDF_OK;
+  });
+}
+int vdf_nova_shape_export_lanes(uint64_t t, size_t lanes, int side, uint64_t nnz[3], uint32_t* const rows[3], uint32_t* const cols[3],
+                                vdf_fe* const vals[3]) {
+  return nova_guard([&]() -> int {
+    if (t == 0 || t > (1ull << 24) || !nnz || (side != PRIMARY && side != SECONDARY) || !lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    HostShape sh[2];
+    build_shapes(t, lanes_kind(lanes), sh, nullptr, nullptr, lanes);
+    const HostShape& h = sh[side];
+    const bool fill = rows && cols && vals;
+    for (int k = 0; k < 3; ++k) {
+      const size_t z = h.m[k].rows.size();
+      if (fill) {
+        if (nnz[k] < z || !rows[k] || !cols[k] || !vals[k]) return fail(VDF_ERR_BAD_LENGTH, "triple arrays too short");
+        memcpy(rows[k], h.m[k].rows.data(), z * 4);
+        memcpy(cols[k], h.m[k].cols.data(), z * 4);
+        memcpy(vals[k], h.m[k].vals.data(), z * 32);
+      }
+      nnz[k] = z;
+    }
+    return VDF_OK;
+  });
+}
+int vdf_nova_aug_synthesize_lanes(const vdf_nova_ro_params* rop, uint64_t t, size_t lanes, const vdf_nova_aug_inputs* a, const vdf_fe* z0,
+                                  const vdf_fe* zi, const vdf_state* results, const vdf_state* inputs, vdf_fe* W, size_t w_cap,
+                                  size_t* num_vars, size_t* num_cons, vdf_fe X[2], vdf_fe* z_next) {
+  return nova_guard([&]() -> int {
+    bool bad;
+    const RoInstance* ro = ro_from_abi(rop, &bad);
+    if (bad) return fail(VDF_ERR_BAD_ARG, "unsupported RO parameter block");
+    if (!a || t == 0 || !lanes_valid(lanes) || !z0 || !zi || !results || !inputs) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    vdf_pp tmp;
+    tmp.t = t;
+    tmp.circuit_kind = lanes_kind(lanes);
+    tmp.lanes = lanes;
+    Circuit c;
+    c.t = t;
+    c.result = load_state(&results[0]); c.input = load_state(&inputs[0]);
+    for (size_t l = 0; l < lanes; ++l) { c.lane_result.push_back(load_state(&results[l])); c.lane_input.push_back(load_state(&inputs[l])); }
+    std::unique_ptr<StepCircuit> step = make_primary_circuit(&tmp, &c, false);
+    CS cs(side_field(PRIMARY), false, ro);
+    AugInputs ain = aug_from_abi(PRIMARY, a);
+    ain.z0.assign((const Fe*)z0, (const Fe*)z0 + 3 * lanes);
+    ain.zi.assign((const Fe*)zi, (const Fe*)zi + 3 * lanes);
+    ain.ro = ro;
+    const std::vector<Fe> zn = synthesize_augmented(cs, PRIMARY, ain, *step);
+    if (num_vars) *num_vars = cs.W.size();
+    if (num_cons) *num_cons = cs.rows;
+    if (W) {
+      if (w_cap < cs.W.size()) return fail(VDF_ERR_BAD_LENGTH, "W buffer too small");
+      memcpy(W, cs.W.data(), cs.W.size() * 32);
+    }
+    if (X) memcpy(X, cs.X.data(), 64);
+    if (z_next) memcpy(z_next, zn.data(), zn.size() * 32);
+    return VDF_OK;
+  });
+}
+
 int vdf_nova_synthesis_stats(uint64_t* queued, uint64_t* misses) {
   if (!queued || !misses) return fail(VDF_ERR_BAD_ARG, "null argument");
   last_synthesis_stats(queued, misses);
@@ -654,7 +749,7 @@ int vdf_nova_public_params(vdf_ctx* ctx, uint64_t t, vdf_pp** out) {
 }
 
 static int public_params_impl(vdf_ctx* ctx, uint64_t t, int circuit_kind, const vdf_step_circuit* custom, int gens_family,
-                              const vdf_nova_tuning& tune, vdf_pp** out, const RoInstance* ro = nullptr);
+                              const vdf_nova_tuning& tune, vdf_pp** out, const RoInstance* ro = nullptr, size_t lanes = 1);
 
 int vdf_nova_public_params_tuned(vdf_ctx* ctx, uint64_t t, int circuit_kind, int gens_family, const vdf_nova_tuning* tuning, vdf_pp** out) {
   return nova_guard([&]() -> int {
@@ -678,6 +773,20 @@ int vdf_nova_public_params_ro(vdf_ctx* ctx, uint64_t t, int circuit_kind, int ge
     return public_params_impl(ctx, t, circuit_kind, nullptr, gens_family, tuning ? *tuning : default_tuning(), out, ro);
   });
 }
+int vdf_nova_public_params_lanes(vdf_ctx* ctx, uint64_t t, size_t lanes, int gens_family, const vdf_nova_ro_params* rop,
+                                 const vdf_nova_tuning* tuning, vdf_pp** out) {
+  if (lanes == 1) return vdf_nova_public_params_ro(ctx, t, VDF_CIRCUIT_MINROOT_FORWARD, gens_family, rop, tuning, out);
+  return nova_guard([&]() -> int {
+    bool bad;
+    const RoInstance* ro = ro_from_abi(rop, &bad);
+    if (bad) return fail(VDF_ERR_BAD_ARG, "unsupported RO parameter block (vdf_nova.h: alpha 5, 128 / 250 bits, family 1 widths 2..25)");
+    if (!ctx || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    if (!lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_NOVA_MAX_LANES");
+    if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
+    return public_params_impl(ctx, t, VDF_CIRCUIT_MINROOT_FORWARD_LANES, nullptr, gens_family, tuning ? *tuning : default_tuning(), out, ro, lanes);
+  });
+}
+size_t vdf_nova_pp_lanes(const vdf_pp* pp) { return pp ? pp->lanes : 0; }
 int vdf_nova_public_params_flags(vdf_ctx* ctx, uint64_t t, int circuit_kind, int gens_family, uint32_t flags, vdf_pp** out) {
   if (flags & ~(uint32_t)(VDF_PP_NO_DIGIT_TABLES | VDF_PP_NO_EARLY_ROWS)) return fail(VDF_ERR_BAD_ARG, "unknown flag");
   vdf_nova_tuning tn = default_tuning();
@@ -799,9 +908,10 @@ static bool minroot_stencil_matches(const HostShape& h, const Field& F, uint64_t
 
 // The same question for the FORWARD circuit and vdf_nifs_cross_term_minroot_forward (include/vdf_hip.h): round j holds
 // x_(j+1), tmp1, tmp2 at S + 3j .., final_i at S + 3t, z_in in the three variables before S.
-static bool forward_stencil_matches(const HostShape& h, const Field& F, uint64_t t, size_t S, size_t row0) {
+// Z = the column of z_in.x (S - 3 for the circuit alone; a lane of the lanes circuit has its inputs further in front)
+static bool forward_stencil_matches(const HostShape& h, const Field& F, uint64_t t, size_t S, size_t row0, size_t Z) {
   const size_t nrows = 3 * (size_t)t + 1, one_col = h.num_vars;
-  if (S < 3 || row0 + nrows > h.num_cons || S + 3 * (size_t)t + 1 > h.num_vars) return false;
+  if (S < 3 || Z + 3 > S || row0 + nrows > h.num_cons || S + 3 * (size_t)t + 1 > h.num_vars) return false;
   typedef std::vector<std::pair<uint32_t, Fe>> Row;
   const Fe p1 = one(F);
   for (int k = 0; k < 3; ++k) {
@@ -814,7 +924,7 @@ static bool forward_stencil_matches(const HostShape& h, const Field& F, uint64_t
       if (i == nrows - 1) {
         if (k == 0) want = {{(uint32_t)(S + 3 * (size_t)t), p1}};
         else if (k == 1) want = {{(uint32_t)one_col, p1}};
-        else want = {{(uint32_t)(S - 1), p1}, {(uint32_t)one_col, from_u64(t, F)}};
+        else want = {{(uint32_t)(Z + 2), p1}, {(uint32_t)one_col, from_u64(t, F)}};
       } else {
         const size_t j = i / 3, role = i - 3 * j, rd = S + 3 * j;
         const uint32_t nx = (uint32_t)rd, t1 = nx + 1, t2 = nx + 2;
@@ -822,9 +932,9 @@ static bool forward_stencil_matches(const HostShape& h, const Field& F, uint64_t
         else if (role == 1) want = k < 2 ? Row{{t1, p1}} : Row{{t2, p1}};
         else if (k == 0) want = {{t2, p1}};
         else if (k == 1) want = {{nx, p1}};
-        else if (j == 0) want = {{(uint32_t)(S - 3), p1}, {(uint32_t)(S - 2), p1}};
+        else if (j == 0) want = {{(uint32_t)Z, p1}, {(uint32_t)(Z + 1), p1}};
         else {
-          want = {{(uint32_t)(rd - 3), p1}, {(uint32_t)(j > 1 ? rd - 6 : S - 3), p1}, {(uint32_t)(S - 1), p1}};
+          want = {{(uint32_t)(rd - 3), p1}, {(uint32_t)(j > 1 ? rd - 6 : Z), p1}, {(uint32_t)(Z + 2), p1}};
           if (j > 1) want.push_back({(uint32_t)one_col, from_u64(j - 1, F)});
         }
       }
@@ -841,15 +951,22 @@ static bool forward_stencil_matches(const HostShape& h, const Field& F, uint64_t
 }
 // the stencil code of a built-in circuit whose early rows are [row0, row0 + 3t + 1): 3 / 4 = the inverse forms (variables
 // per round), 5 = the forward circuit; 0 = no match
-static int builtin_stencil(const HostShape& h, int circuit_kind, uint64_t t, size_t S, size_t row0) {
+static int builtin_stencil(const HostShape& h, int circuit_kind, uint64_t t, size_t S, size_t row0, size_t lanes = 1) {
   const Field& F = field(side_field(PRIMARY));
-  if (circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD) return forward_stencil_matches(h, F, t, S, row0) ? VDF_STENCIL_FORWARD : 0;
+  if (circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD) return forward_stencil_matches(h, F, t, S, row0, S - 3) ? VDF_STENCIL_FORWARD : 0;
+  if (circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES) {           // lane by lane: its own variables, rows and inputs
+    const size_t per_lane = 3 * (size_t)t + 1;
+    if (S < 3 * lanes) return 0;
+    for (size_t l = 0; l < lanes; ++l)
+      if (!forward_stencil_matches(h, F, t, S + l * per_lane, row0 + l * per_lane, S - 3 * lanes + 3 * l)) return 0;
+    return VDF_STENCIL_FORWARD_LANES;
+  }
   const int per = vars_per_round(circuit_kind);
   return minroot_stencil_matches(h, F, t, per, S, row0) ? per : 0;
 }
 
 static int public_params_impl(vdf_ctx* ctx, uint64_t t, int circuit_kind, const vdf_step_circuit* custom, int gens_family,
-                              const vdf_nova_tuning& tune, vdf_pp** out, const RoInstance* ro) {
+                              const vdf_nova_tuning& tune, vdf_pp** out, const RoInstance* ro, size_t lanes) {
   if (gens_family != VDF_GENS_TRY_AND_INCREMENT && gens_family != VDF_GENS_KNOWN_DLOG && gens_family != VDF_GENS_LABEL_SHAKE)
     return fail(VDF_ERR_BAD_ARG, "unknown generator family");
   *out = nullptr;
@@ -866,14 +983,15 @@ static int public_params_impl(vdf_ctx* ctx, uint64_t t, int circuit_kind, const 
   pp->t = t;
   pp->circuit_kind = circuit_kind;
   pp->gens_family = gens_family;
-  pp->arity = custom ? custom->arity : 3;
+  pp->lanes = lanes;
+  pp->arity = custom ? custom->arity : 3 * lanes;
   pp->tune = tune;
   pp->ro = ro ? ro : ro_default();
   double* ms = pp->setup_ms;                       // [0] shapes + digest, [1] shapes to the device, [2] generators, [3] tables, [4] digit tables
   double mark = t_start;
   auto lap = [&](int k) -> int { HIPCALL(ctx, vdf_ctx_sync(ctx)); const double now = now_ms(); ms[k] += now - mark; mark = now; return VDF_OK; };
   HostShape sh[2];
-  { int rc = build_shapes(t, circuit_kind, sh, custom, pp->ro); if (rc != VDF_OK) return rc; }
+  { int rc = build_shapes(t, circuit_kind, sh, custom, pp->ro, lanes); if (rc != VDF_OK) return rc; }
   digest_shapes(t, gens_family, sh, pp->digest, pp->ro);
   // only the MinRoot rounds are made on the device; a custom circuit's variables all come from the host
   pp->seg_begin = custom ? 0 : sh[PRIMARY].step_begin;
@@ -889,8 +1007,8 @@ static int public_params_impl(vdf_ctx* ctx, uint64_t t, int circuit_kind, const 
     pp->ahead_mode = tune.early_rows == 1 ? 1 : 2;
     // the built-in circuits' early rows are a fixed stencil over the rounds' variables: compared with the shape triple by triple
     // once, here; from then on their cross term reads no sparse matrix (tuning.stencil = 0: the generic kernel, for A/B runs)
-    if (!custom && pp->ahead_rows == 3 * t + 1 && tune.stencil)
-      pp->stencil_per = builtin_stencil(h, circuit_kind, t, pp->seg_begin, pp->ahead_row);
+    if (!custom && pp->ahead_rows == lanes * (3 * t + 1) && tune.stencil)
+      pp->stencil_per = builtin_stencil(h, circuit_kind, t, pp->seg_begin, pp->ahead_row, lanes);
   }
   ms[0] = now_ms() - mark; mark = now_ms();
   for (int s = 0; s < 2; ++s) {
@@ -1059,22 +1177,28 @@ int vdf_nova_pp_early_rows(const vdf_pp* pp, uint64_t* begin, uint64_t* len) {
 }
 int vdf_nova_pp_stencil(const vdf_pp* pp) { return pp ? pp->stencil_per : 0; }
 // host only (no device): what vdf_nova_public_params would find for the built-in step circuit `circuit_kind` at `t`
-int vdf_nova_shape_stencil(uint64_t t, int circuit_kind, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
+static int shape_stencil_impl(uint64_t t, int circuit_kind, size_t lanes, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
   return nova_guard([&]() -> int {
-    if (t == 0 || t > (1ull << 24) || (!builtin_circuit(circuit_kind)))
-      return -fail(VDF_ERR_BAD_ARG, "bad argument");
     HostShape sh[2];
-    if (build_shapes(t, circuit_kind, sh) != VDF_OK) return -VDF_ERR_DEVICE;
+    if (build_shapes(t, circuit_kind, sh, nullptr, nullptr, lanes) != VDF_OK) return -VDF_ERR_DEVICE;
     const HostShape& h = sh[PRIMARY];
     const size_t sb = h.step_begin, sl = h.step_end - h.step_begin;
     size_t b = 0, n = 0;
-    if (sb < 3) return 0;
-    longest_early_run(h, sb, sl, 3, &b, &n);
+    if (sb < 3 * lanes) return 0;
+    longest_early_run(h, sb, sl, 3 * lanes, &b, &n);
     if (early_begin) *early_begin = b;
     if (early_len) *early_len = n;
     if (seg_begin) *seg_begin = sb;
-    return n == 3 * t + 1 ? builtin_stencil(h, circuit_kind, t, sb, b) : 0;
+    return n == lanes * (3 * t + 1) ? builtin_stencil(h, circuit_kind, t, sb, b, lanes) : 0;
   });
+}
+int vdf_nova_shape_stencil(uint64_t t, int circuit_kind, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
+  if (t == 0 || t > (1ull << 24) || (!builtin_circuit(circuit_kind))) return -fail(VDF_ERR_BAD_ARG, "bad argument");
+  return shape_stencil_impl(t, circuit_kind, 1, early_begin, early_len, seg_begin);
+}
+int vdf_nova_shape_stencil_lanes(uint64_t t, size_t lanes, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
+  if (t == 0 || t > (1ull << 24) || !lanes_valid(lanes)) return -fail(VDF_ERR_BAD_ARG, "bad argument");
+  return shape_stencil_impl(t, lanes_kind(lanes), lanes, early_begin, early_len, seg_begin);
 }
 
 // ---- prove_step ----------------------------------------------------------------------------------------
@@ -1191,7 +1315,7 @@ struct StepRun {
   StepRun(vdf_pp* pp_, vdf_proof* p_, const vdf_circuits* circuits_, size_t k_, const vdf_step_circuit* custom_, const Circuit& c_, bool first_)
       : pp(pp_), p(p_), circuits(circuits_), k(k_), custom(custom_), c(c_), first(first_), arity(pp_->arity), ctx(pp_->ctx), ct(p_->ctx3),
         S1(pp_->s[PRIMARY]), S2(pp_->s[SECONDARY]), F1(*pp_->s[PRIMARY].F), F2(*pp_->s[SECONDARY].F), seg_b(pp_->seg_begin), seg_n(pp_->seg_len),
-        seg_e(pp_->seg_begin + pp_->seg_len), per(vars_per_round(pp_->circuit_kind)), forward(pp_->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD),
+        seg_e(pp_->seg_begin + pp_->seg_len), per(vars_per_round(pp_->circuit_kind)), forward(forward_kind(pp_->circuit_kind)),
         t_ahead(!first_ && !custom_ && pp_->ahead_rows != 0), ta_b(pp_->ahead_row), ta_n(pp_->ahead_rows), ta_e(pp_->ahead_row + pp_->ahead_rows),
         t_parts(pp_->tune.early_row_parts), fold_on_rows(pp_->tune.fold_on_rows != 0), hb(&p_->h_pts[R]), early1(nullptr, aug_early_free),
         early2(nullptr, aug_early_free) {
@@ -1208,13 +1332,17 @@ struct StepRun {
     if (!d_trace && cc.trace_xy.empty()) return fail(VDF_ERR_BAD_ARG, "trace of circuit " + std::to_string(j) + " not materialised");
     if (!d_trace) {                               // trace not resident: staged through the proof's own buffer
       void*& stage = p->d_traces[j % D];
-      if (!stage) HIPCALL(ctx, vdf_dev_alloc(ctx, (pp->t + 1) * 64, &stage));
-      HIPCALL(q, vdf_dev_memcpy(q, stage, cc.trace_xy.data(), (pp->t + 1) * 64));
+      if (!stage) HIPCALL(ctx, vdf_dev_alloc(ctx, pp->lanes * (pp->t + 1) * 64, &stage));
+      HIPCALL(q, vdf_dev_memcpy(q, stage, cc.trace_xy.data(), pp->lanes * (pp->t + 1) * 64));
       d_trace = stage;
     }
     char* seg = (char*)p->d_z2s[s] + seg_b * 32;
     void* packed = pp->seg_gens ? p->d_packed[j % D] : nullptr;
-    if (forward) HIPCALL(q, vdf_minroot_forward_segment(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.result.i, (vdf_fe*)seg));
+    if (pp->lanes > 1) {                          // every lane's rounds in one launch, the lanes' traces back to back
+      Fe ends[VDF_NOVA_MAX_LANES];
+      for (size_t l = 0; l < pp->lanes; ++l) ends[l] = cc.lane_result[l].i;
+      HIPCALL(q, vdf_minroot_forward_segment_lanes(q, S1.field, (const vdf_fe*)d_trace, (size_t)pp->t + 1, pp->t, pp->lanes, (const vdf_fe*)ends, (vdf_fe*)seg));
+    } else if (forward) HIPCALL(q, vdf_minroot_forward_segment(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.result.i, (vdf_fe*)seg));
     else if (packed) HIPCALL(q, vdf_minroot_step_segment_packed(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.input.i,
                                                             (const vdf_fe*)&cc.result.i, (vdf_fe*)seg, (vdf_fe*)packed));
     else HIPCALL(q, vdf_minroot_step_segment(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.input.i, per, (vdf_fe*)seg));
@@ -1279,7 +1407,8 @@ struct StepRun {
   // A z, B z, C z and E yet -- the stencil applies it on the way (vdf_nifs_cross_term_minroot_fold) and MARK_FOLD is set behind it
   // (no fused kernel exists for the forward stencil: that kind keeps the unfused fold)
   bool stencil_fold_ok() const {
-    return pp->tune.fold_fused != 0 && pp->stencil_per != 0 && pp->stencil_per != VDF_STENCIL_FORWARD && (t_parts == 1 || ta_n < 4096);
+    return pp->tune.fold_fused != 0 && pp->stencil_per != 0 && pp->stencil_per != VDF_STENCIL_FORWARD && pp->stencil_per != VDF_STENCIL_FORWARD_LANES &&
+           (t_parts == 1 || ta_n < 4096);
   }
   int early_rows_launch(void* d_z2, vdf_ctx* cq, bool zin_in_place, const Fe* fold_r = nullptr) {
     SideState& s1 = p->r[PRIMARY];
@@ -1297,6 +1426,13 @@ struct StepRun {
                                                      (vdf_fe*)s1.d_E, (const vdf_fe*)s1.d_T, (const vdf_fe*)&s1.inst.u, (vdf_fe*)s1.d_abc2[0],
                                                      (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
         HIPCALL(ct, vdf_ctx_mark(ct, MARK_FOLD));                    // the running instance is whole again from here on
+        return VDF_OK;
+      }
+      if (pp->stencil_per == VDF_STENCIL_FORWARD_LANES && b == ta_b && n == ta_n) {
+        HIPCALL(ct, vdf_nifs_cross_term_minroot_forward_lanes(ct, S1.field, pp->t, pp->lanes, seg_b, S1.num_vars, b, (const vdf_fe*)d_z2,
+                                                              (const vdf_fe*)s1.d_abc[0], (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2],
+                                                              (const vdf_fe*)&s1.inst.u, (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1],
+                                                              (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
         return VDF_OK;
       }
       if (pp->stencil_per == VDF_STENCIL_FORWARD && b == ta_b && n == ta_n) {
@@ -1676,9 +1812,12 @@ static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* ci
   if (!custom && k >= circuits->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
   const Circuit& c = custom ? no_circuit : circuits->v[k];
   if (!custom && c.t != pp->t) return fail(VDF_ERR_BAD_LENGTH, "circuit t differs from the public parameters");
-  if (!custom && circuits->forward != (pp->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD))
+  if (!custom && circuits->forward != forward_kind(pp->circuit_kind))
     return fail(VDF_ERR_BAD_ARG, circuits->forward ? "forward circuits need parameters of VDF_CIRCUIT_MINROOT_FORWARD"
                                                    : "forward parameters need circuits made by vdf_nova_circuits_forward_begin");
+  if (!custom && circuits->forward && circuits->lanes != pp->lanes)
+    return fail(VDF_ERR_BAD_ARG, "a chain of " + std::to_string(circuits->lanes) + " lane(s) under parameters of " + std::to_string(pp->lanes) +
+                                     " (vdf_nova_public_params_lanes, vdf_nova_circuits_lanes_begin)");
   if (!custom && circuits->checkpoints) {        // this step reads the trace of circuit k, and enqueues the rounds of circuit k + 1
     int rc = circuits_need(circuits, k);
     if (rc == VDF_OK && k + 1 < circuits->v.size() && circuits->v[k + 1].t == pp->t) rc = circuits_need(circuits, k + 1);
@@ -1706,9 +1845,11 @@ static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* ci
   }
   // StepCircuit::output's debug assertion: z_i must be the circuit's result (src/nova/proof.rs:147-149)
   // (the forward circuit starts from the step's input state and hands on its result)
-  if (!custom && memcmp(p->zi[PRIMARY].data(), pp->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD ? &c.input : &c.result, 96) != 0)
-    return fail(VDF_ERR_BAD_ARG, pp->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD ? "z_i does not match the circuit's input state"
-                                                                               : "z_i does not match the circuit's result state");
+  if (!custom && pp->lanes > 1) {
+    if (memcmp(p->zi[PRIMARY].data(), c.lane_input.data(), 96 * pp->lanes) != 0) return fail(VDF_ERR_BAD_ARG, "z_i does not match the circuit's input states");
+  } else if (!custom && memcmp(p->zi[PRIMARY].data(), forward_kind(pp->circuit_kind) ? &c.input : &c.result, 96) != 0)
+    return fail(VDF_ERR_BAD_ARG, forward_kind(pp->circuit_kind) ? "z_i does not match the circuit's input state"
+                                                                : "z_i does not match the circuit's result state");
   const double t0 = now_ms();
   int was_async = 0;
   HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
@@ -1747,7 +1888,7 @@ int vdf_nova_prove_recursively_windowed(vdf_pp* pp, const vdf_circuits* circuits
       for (const Circuit& c : circuits->v) windowed |= needs_walk(c);
     }
     const size_t W = !windowed ? n : window_steps ? std::max<size_t>(window_steps, 2)
-                                                  : std::max<size_t>(2, (size_t)(((uint64_t)1 << 30) / ((pp->t + 1) * 64)));
+                                                  : std::max<size_t>(2, (size_t)(((uint64_t)1 << 30) / (pp->lanes * (pp->t + 1) * 64)));
     std::vector<char> mine(windowed ? n : 0, 0);
     auto build = [&](size_t w, int wait) -> int {                        // window w = circuits [w W, (w + 1) W)
       const size_t b = w * W;
@@ -1789,7 +1930,9 @@ int vdf_nova_eval_and_prove(vdf_pp* pp, int mode, const vdf_state* initial_state
   return nova_guard([&]() -> int {
     if (!pp || !initial_state || !out || !valid_mode(mode)) return fail(VDF_ERR_BAD_ARG, "bad argument");
     if (num_steps == 0) return fail(VDF_ERR_BAD_ARG, "num_steps must be > 0");
-    if (pp->circuit_kind != VDF_CIRCUIT_MINROOT_FORWARD) return fail(VDF_ERR_BAD_ARG, "these parameters are not for VDF_CIRCUIT_MINROOT_FORWARD");
+    if (pp->circuit_kind != VDF_CIRCUIT_MINROOT_FORWARD)
+      return fail(VDF_ERR_BAD_ARG, pp->lanes > 1 ? "lanes parameters: the evaluator of vdf_nova_eval_and_prove is one chain"
+                                                 : "these parameters are not for VDF_CIRCUIT_MINROOT_FORWARD");
     *out = nullptr;
     constexpr size_t EVAL_QUEUE = 4;
     const uint64_t t = pp->t;

@@ -114,6 +114,7 @@ struct vdf_pp {
                                  // the shape at public_params -- their cross term needs no sparse matrix (vdf_nifs_cross_term_minroot); 0: generic rows
   int ahead_mode = 2;            // when they run: 2 = from the start of the step, beside the secondary side's NIFS; 1 = after it (tuning)
   size_t arity = 3;                        // of the primary step circuit (z0, zi)
+  size_t lanes = 1;                        // VDF_CIRCUIT_MINROOT_FORWARD_LANES: evaluations advanced per step (arity = 3 lanes); 1 for every other kind
   // the reference's step circuit only: generators of the packed commitment to the MinRoot rounds (3t + 4 points derived from
   // the 4t + 1 of the segment: vdf_hip.h vdf_minroot_step_segment_packed), with a fixed-base table of their own
   vdf_bases* seg_gens = nullptr;
@@ -149,13 +150,17 @@ struct Circuit {            // InverseMinRootCircuit<G1>, src/nova/proof.rs:57-6
   // rounds in forward order, cp[0] = input .. cp[t / every] = result; its d_trace is built by walks, and is what release lets go of
   uint64_t every = 0;
   std::vector<vdfnova::St> cp;
+  // a step of a chain in L > 1 lanes (vdf_nova_circuits_lanes_begin): result / input above are lane 0's, these hold every lane's;
+  // trace_xy and the device trace are L traces back to back, t + 1 entries each, and cp is L runs of t / every + 1 states
+  std::vector<vdfnova::St> lane_result, lane_input;
 };
 // Traces being rebuilt by inverse walks on the circuits' side queue (vdf_nova_circuits_materialize): one walk per checkpoint
 // interval of every step in `steps`, all in one launch per slice of rounds; `done` rounds of `every` are enqueued so far.
 struct WalkJob {
   std::vector<size_t> steps;               // circuit indices, ascending
-  std::shared_ptr<TraceBlock> block;       // steps.size() traces of t + 1 entries
-  size_t walks = 0, per_step = 0;
+  std::shared_ptr<TraceBlock> block;       // steps.size() x lanes traces of t + 1 entries
+  size_t walks = 0, per_step = 0;          // per_step: walks per LANE of a step (a step of a lanes chain has lanes x per_step)
+  size_t lanes = 1;
   uint64_t every = 0, done = 0;
   bool matched = false;                    // the comparison has been enqueued
 };
@@ -187,6 +192,8 @@ struct vdf_circuits {
   bool forward = false;
   uint64_t forward_t = 0;
   vdfnova::St end;
+  size_t lanes = 1;                        // a forward chain in lanes (vdf_nova_circuits_lanes_begin): evaluations advanced per step
+  std::vector<vdfnova::St> lane_end;       // lanes > 1: where every lane stands (end = lane 0's)
   mutable WalkState walk;
 };
 

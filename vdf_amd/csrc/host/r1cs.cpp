@@ -1091,6 +1091,29 @@ void ForwardMinRootCircuit::output(const Fe* z, Fe* out) const {
   out[0] = result.x; out[1] = result.y; out[2] = result.i;
 }
 
+std::vector<Num> LanesForwardCircuit::synthesize(CS& cs, const std::vector<Num>& z) const {
+  const size_t L = results.size();
+  std::vector<Num> out(3 * L);
+  if (!cs.shape && device_rounds) {
+    // every lane's rounds are left to the GPU (vdf_minroot_forward_segment_lanes): one run of L (3t + 1) variables and rows
+    cs.skip(L * (3 * t + 1), L * (3 * t + 1));
+    for (size_t l = 0; l < L; ++l) { out[3 * l].v = results[l].x; out[3 * l + 1].v = results[l].y; out[3 * l + 2].v = results[l].i; }
+    return out;
+  }
+  for (size_t l = 0; l < L; ++l) {
+    ForwardMinRootCircuit lane;
+    lane.t = t; lane.blank = blank; lane.device_rounds = false;
+    lane.result = results[l]; lane.input = inputs[l];
+    const std::vector<Num> o = lane.synthesize(cs, {z[3 * l], z[3 * l + 1], z[3 * l + 2]});
+    for (int k = 0; k < 3; ++k) out[3 * l + k] = o[k];
+  }
+  return out;
+}
+void LanesForwardCircuit::output(const Fe* z, Fe* out) const {
+  (void)z;
+  for (size_t l = 0; l < results.size(); ++l) { out[3 * l] = results[l].x; out[3 * l + 1] = results[l].y; out[3 * l + 2] = results[l].i; }
+}
+
 // =============================================================================================================
 // Instances, native hashes, the augmented circuit
 // =============================================================================================================

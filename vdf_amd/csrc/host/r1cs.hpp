@@ -187,6 +187,18 @@ struct ForwardMinRootCircuit : StepCircuit {
   void output(const Fe* z, Fe* out) const override;
   bool output_known() const override { return !blank; }
 };
+// L forward circuits side by side (include/vdf_nova.h VDF_CIRCUIT_MINROOT_FORWARD_LANES): arity 3L, z = (x_0, y_0, i_0, x_1, ...),
+// lane l synthesised over z[3l .. 3l + 3) in order -- its 3t + 1 variables and constraints follow lane l - 1's.
+struct LanesForwardCircuit : StepCircuit {
+  uint64_t t = 0;
+  bool blank = true;
+  bool device_rounds = false;            // witness mode: all lanes' variables are left to the GPU kernel (one cs.skip)
+  std::vector<MinRootState> results, inputs;      // one per lane
+  size_t arity() const override { return 3 * results.size(); }
+  std::vector<Num> synthesize(CS& cs, const std::vector<Num>& z) const override;
+  void output(const Fe* z, Fe* out) const override;
+  bool output_known() const override { return !blank; }
+};
 // nova-snark's TrivialTestCircuit (src/nova/proof.rs:258-260): arity 1, z_out = z_in
 struct TrivialTestCircuit : StepCircuit {
   size_t arity() const override { return 1; }

@@ -317,6 +317,9 @@ Status vec_spmv(int field, const uint32_t* rowptr, const uint32_t* col, const ui
 Status vec_step_segment(int field, const void* trace_xy, uint64_t t, const vdf_fe* i0, int per, void* out, void* packed,
                         const vdf_fe* i_in, hipStream_t s);
 Status vec_forward_segment(int field, const void* trace_xy, uint64_t t, const vdf_fe* i_end, void* out, hipStream_t s);
+// ... for `lanes` traces lane_stride entries apart, lane-major into out (one launch; i_end: `lanes` host elements)
+Status vec_forward_segment_lanes(int field, const void* trace_xy, size_t lane_stride, uint64_t t, size_t lanes, const vdf_fe* i_end, void* out,
+                                 hipStream_t s);
 Status vec_step_z(int field, const void* trace_xy, uint64_t t, const vdf_fe z_in[3], const vdf_fe* i0, const vdf_fe* u,
                   const vdf_fe X[6], void* z, void* packed, hipStream_t s);
 Status vec_nifs_cross(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3],
@@ -331,6 +334,9 @@ Status vec_nifs_cross_minroot(int field, int per, uint64_t t, size_t seg_begin, 
 Status vec_nifs_cross_minroot_forward(int field, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
                                       const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, void* az2, void* bz2,
                                       void* cz2, void* T, hipStream_t s);
+Status vec_nifs_cross_minroot_forward_lanes(int field, uint64_t t, size_t lanes, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
+                                            const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, void* az2, void* bz2,
+                                            void* cz2, void* T, hipStream_t s);
 Status vec_nifs_cross_minroot_fold(int field, int per, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
                                    const vdf_fe* r, void* az1, void* bz1, void* cz1, void* e1, const void* tprev, const vdf_fe* u1,
                                    void* az2, void* bz2, void* cz2, void* T, hipStream_t s);

@@ -415,6 +415,10 @@ class Context:
         """The forward step circuit's 3t + 1 variables: x_(j+1), its square and fourth power per round, then final_i = i_end."""
         self._check(lib.vdf_minroot_forward_segment(self.handle, field, _ptr(trace_xy), t, _ptr(i_end), _ptr(out)))
 
+    def minroot_forward_segment_lanes(self, field, trace_xy, lane_stride, t, lanes, i_end, out) -> None:
+        """The same for `lanes` traces lane_stride entries apart, lane-major into out, in one launch; i_end: `lanes` host elements."""
+        self._check(lib.vdf_minroot_forward_segment_lanes(self.handle, field, _ptr(trace_xy), lane_stride, t, lanes, _ptr(i_end), _ptr(out)))
+
     def minroot_step_segment_packed(self, field, trace_xy, t, i0, i_in, out, packed) -> None:
         """The reference's allocation (4 variables per round) and the 3t + 4 scalars of its commitment without new_x."""
         self._check(lib.vdf_minroot_step_segment_packed(self.handle, field, _ptr(trace_xy), t, _ptr(i0), _ptr(i_in), _ptr(out), _ptr(packed)))
@@ -484,6 +488,11 @@ class Context:
         """The 3t + 1 rows of the forward MinRoot step circuit from row_begin on, by stencil (vdf_hip.h)."""
         self._check(lib.vdf_nifs_cross_term_minroot_forward(self.handle, field, t, seg_begin, one_col, row_begin, _ptr(z2), _ptr(az1),
                                                             _ptr(bz1), _ptr(cz1), _ptr(u1), _ptr(az2), _ptr(bz2), _ptr(cz2), _ptr(T)))
+
+    def nifs_cross_term_minroot_forward_lanes(self, field, t, lanes, seg_begin, one_col, row_begin, z2, az1, bz1, cz1, u1, az2, bz2, cz2, T) -> None:
+        """The lanes x (3t + 1) rows of the forward circuit in lanes from row_begin on, by stencil, one launch (vdf_hip.h)."""
+        self._check(lib.vdf_nifs_cross_term_minroot_forward_lanes(self.handle, field, t, lanes, seg_begin, one_col, row_begin, _ptr(z2), _ptr(az1),
+                                                                  _ptr(bz1), _ptr(cz1), _ptr(u1), _ptr(az2), _ptr(bz2), _ptr(cz2), _ptr(T)))
 
     def nifs_cross_term_minroot_fold(self, field, per, t, seg_begin, one_col, row_begin, z2, r, az1, bz1, cz1, e1, t_prev, u1, az2, bz2, cz2, T) -> None:
         """The same rows with the previous fold of those rows applied on the way (vdf_hip.h); e1 / t_prev may be None."""

@@ -46,14 +46,25 @@ for _name, _res, _args in [
     ("vdf_nova_circuits_forward_begin", _i, [_u64, C.POINTER(_State), C.POINTER(_Fe * 3), C.POINTER(_vp)]),
     ("vdf_nova_circuits_push_trace", _i, [_vp, _vp]),
     ("vdf_nova_circuits_push_checkpoints", _i, [_vp, _u64, _vp]),
+    ("vdf_nova_public_params_lanes", _i, [_vp, _u64, _sz, _i, _vp, _vp, C.POINTER(_vp)]),
+    ("vdf_nova_pp_lanes", _sz, [_vp]),
+    ("vdf_nova_shape_digest_lanes", _i, [_vp, _u64, _sz, _i, _vp, _vp]),
+    ("vdf_nova_shape_stencil_lanes", _i, [_u64, _sz, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    ("vdf_nova_shape_export_lanes", _i, [_u64, _sz, _i, _vp, _vp, _vp, _vp]),
+    ("vdf_nova_aug_synthesize_lanes", _i, [_vp, _u64, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz), _vp, _vp]),
+    ("vdf_nova_circuits_lanes_begin", _i, [_u64, _sz, _vp, _vp, C.POINTER(_vp)]),
+    ("vdf_nova_circuits_push_traces", _i, [_vp, _vp, _sz]),
+    ("vdf_nova_circuits_push_checkpoints_lanes", _i, [_vp, _u64, _vp, _sz]),
+    ("vdf_nova_circuits_lanes", _sz, [_vp]),
+    ("vdf_nova_circuit_lane_states", _i, [_vp, _sz, _sz, C.POINTER(_State), C.POINTER(_State)]),
     ("vdf_nova_eval_and_prove", _i, [_vp, _i, C.POINTER(_State), _sz, C.POINTER(_State), C.POINTER(_vp), _vp]),
-    ("vdf_nova_prove_recursively_windowed", _i, [_vp, _vp, _u64, C.POINTER(_Fe * 3), _sz, C.POINTER(_vp)]),
+    ("vdf_nova_prove_recursively_windowed", _i, [_vp, _vp, _u64, _vp, _sz, C.POINTER(_vp)]),      # z0: `arity` elements
     ("vdf_nova_circuits_len", _sz, [_vp]),
     ("vdf_nova_circuits_upload", _i, [_vp, _vp]),
     ("vdf_nova_circuit_states", _i, [_vp, _sz, C.POINTER(_State), C.POINTER(_State)]),
     ("vdf_nova_circuits_free", None, [_vp]),
-    ("vdf_nova_prove_recursively", _i, [_vp, _vp, _u64, C.POINTER(_Fe * 3), C.POINTER(_vp)]),
-    ("vdf_nova_prove_step", _i, [_vp, C.POINTER(_vp), _vp, _sz, C.POINTER(_Fe * 3)]),
+    ("vdf_nova_prove_recursively", _i, [_vp, _vp, _u64, _vp, C.POINTER(_vp)]),
+    ("vdf_nova_prove_step", _i, [_vp, C.POINTER(_vp), _vp, _sz, _vp]),
     ("vdf_nova_verify", _i, [_vp, _vp, _sz, C.POINTER(_Fe * 3), C.POINTER(_Fe * 3), C.POINTER(_i)]),
     ("vdf_nova_proof_free", None, [_vp]),
     ("vdf_nova_proof_num_steps", _sz, [_vp]),
@@ -108,6 +119,9 @@ for _name, _res, _args in [
 CIRCUIT_MINROOT_BOUND, CIRCUIT_MINROOT_REFERENCE = 0, 1
 CIRCUIT_MINROOT_FORWARD = 3       # the step in the direction of evaluation (include/vdf_nova.h)
 STENCIL_FORWARD = 5               # vdf_nova_pp_stencil's code for the forward circuit's stencil
+CIRCUIT_MINROOT_FORWARD_LANES = 4 # L forward circuits side by side in one step circuit (public_params_lanes)
+STENCIL_FORWARD_LANES = 6         # ... and the code of its stencil
+MAX_LANES = 16
 SIDE_PRIMARY, SIDE_SECONDARY = 0, 1
 INST_RUNNING_PRIMARY, INST_RUNNING_SECONDARY, INST_FRESH_SECONDARY, INST_FRESH_PRIMARY_LAST = 0, 1, 2, 3
 GENS_KNOWN_DLOG, GENS_TRY_AND_INCREMENT, GENS_LABEL_SHAKE = 0, 1, 2
@@ -348,7 +362,7 @@ def aug_synthesize(side: int, t: int, circuit_kind: int, inputs: AugInputs, resu
 
 
 def _z(vals: Sequence[bytes]):
-    return (_Fe * 3)(*[_Fe.from_buffer_copy(v) for v in vals])
+    return (_Fe * len(vals))(*[_Fe.from_buffer_copy(v) for v in vals])
 
 
 class NovaVDFPublicParams:        # src/nova/proof.rs:38-43
@@ -381,8 +395,12 @@ class NovaVDFPublicParams:        # src/nova/proof.rs:38-43
 
     def stencil(self) -> int:
         """4 / 3: the early rows run as the MinRoot stencil (reference / bound rounds), 5: as the forward circuit's stencil,
-        0: through the sparse kernel."""
+        6: as the forward circuit's in lanes, 0: through the sparse kernel."""
         return int(nova_lib.vdf_nova_pp_stencil(self.handle))
+
+    def lanes(self) -> int:
+        """evaluations a step advances: 1 for every kind but CIRCUIT_MINROOT_FORWARD_LANES"""
+        return int(nova_lib.vdf_nova_pp_lanes(self.handle))
 
     def ro(self) -> dict:
         """The random oracle's parameter block this set was made under (vdf_nova_pp_ro)."""
@@ -450,6 +468,67 @@ def public_params(ctx: Context, num_iters_per_step: int, circuit_kind: int = CIR
     pp = NovaVDFPublicParams(ctx, h.value, num_iters_per_step)
     pp.circuit_kind = circuit_kind
     return pp
+
+
+def public_params_lanes(ctx: Context, num_iters_per_step: int, lanes: int, gens_family: int = GENS_TRY_AND_INCREMENT, flags: int = 0,
+                        tuning: "NovaTuning | None" = None, ro: "RoParams | None" = None, **tune) -> NovaVDFPublicParams:
+    """Parameters of the forward circuit in `lanes` lanes (vdf_nova_public_params_lanes); lanes = 1 gives exactly
+    public_params(ctx, t, CIRCUIT_MINROOT_FORWARD).  z0 and zi of proofs under them have 3 * lanes elements."""
+    h = C.c_void_p()
+    t = tuning if tuning is not None else tuning_default()
+    for k, v in tune.items():
+        if k not in dict(NovaTuning._fields_):
+            raise KeyError(k)
+        setattr(t, k, int(v))
+    t.flags |= flags
+    _check(nova_lib.vdf_nova_public_params_lanes(ctx.handle, num_iters_per_step, lanes, gens_family, _ro_ptr(ro), C.byref(t), C.byref(h)))
+    pp = NovaVDFPublicParams(ctx, h.value, num_iters_per_step)
+    pp.circuit_kind = CIRCUIT_MINROOT_FORWARD if lanes == 1 else CIRCUIT_MINROOT_FORWARD_LANES
+    pp.arity = 3 * lanes
+    return pp
+
+
+def shape_digest_lanes(t: int, lanes: int, gens_family: int = 1, ro: "RoParams | None" = None):
+    """shape_digest for the forward circuit in `lanes` lanes (host only)."""
+    d = (C.c_uint8 * 32)()
+    sizes = np.zeros((2, 3), dtype="<u8")
+    _check(nova_lib.vdf_nova_shape_digest_lanes(_ro_ptr(ro), t, lanes, gens_family, d, sizes.ctypes.data))
+    return int.from_bytes(bytes(d), "little"), sizes.tolist()
+
+
+def shape_stencil_lanes(t: int, lanes: int):
+    """(6, or 5 for one lane, or 0; first early row; early rows; first round variable) -- host only, as shape_stencil."""
+    b, n, s_ = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    code = nova_lib.vdf_nova_shape_stencil_lanes(t, lanes, C.byref(b), C.byref(n), C.byref(s_))
+    if code < 0:
+        _check(-code)
+    return code, b.value, n.value, s_.value
+
+
+def shape_export_lanes(t: int, lanes: int, side: int = 0):
+    """shape_export for the forward circuit in `lanes` lanes (host only)."""
+    nnz = np.zeros(3, dtype="<u8")
+    _check(nova_lib.vdf_nova_shape_export_lanes(t, lanes, side, nnz.ctypes.data, None, None, None))
+    mats = [(np.zeros(int(z), dtype=np.uint32), np.zeros(int(z), dtype=np.uint32), np.zeros((int(z), 4), dtype="<u8")) for z in nnz]
+    arr = lambda k: (C.c_void_p * 3)(*[m[k].ctypes.data for m in mats])
+    _check(nova_lib.vdf_nova_shape_export_lanes(t, lanes, side, nnz.ctypes.data, arr(0), arr(1), arr(2)))
+    return mats
+
+
+def aug_synthesize_lanes(t: int, lanes: int, inputs: AugInputs, z0: Sequence[bytes], zi: Sequence[bytes], results: Sequence[State],
+                         inps: Sequence[State], cap: int = 1 << 16, ro=None):
+    """The primary augmented circuit around the forward circuit in lanes, synthesised on the host: (W, X, z_next, num_cons).
+    z0 / zi: 3 * lanes elements (those of `inputs` are ignored); results / inps: one State per lane."""
+    W = np.zeros((cap, 4), dtype="<u8")
+    X, zn = np.zeros((2, 4), dtype="<u8"), np.zeros((3 * lanes, 4), dtype="<u8")
+    nv, nc = C.c_size_t(), C.c_size_t()
+    res = b"".join(s.x + s.y + s.i for s in results)
+    inp = b"".join(s.x + s.y + s.i for s in inps)
+    if len(z0) != 3 * lanes or len(zi) != 3 * lanes or len(res) != 96 * lanes or len(inp) != 96 * lanes:
+        raise ValueError("3 * lanes elements of z0 and zi, one state per lane")
+    _check(nova_lib.vdf_nova_aug_synthesize_lanes(_ro_ptr(ro), t, lanes, C.addressof(inputs), _zn(z0), _zn(zi), res, inp, W.ctypes.data, cap,
+                                                  C.byref(nv), C.byref(nc), X.ctypes.data, zn.ctypes.data))
+    return W[:nv.value].copy(), X, zn, nc.value
 
 
 class Circuits:
@@ -575,6 +654,55 @@ class ForwardCircuits(Circuits):
         raw = b"".join(s.x + s.y + s.i for s in states)
         buf = (C.c_char * max(len(raw), 1)).from_buffer_copy(raw or b"\0")
         _check(nova_lib.vdf_nova_circuits_push_checkpoints(self.handle, every, buf))
+
+
+class LaneCircuits(Circuits):
+    """A forward chain in lanes (CIRCUIT_MINROOT_FORWARD_LANES): every step advances `lanes` evaluations by t rounds.  One lane
+    is a forward chain.  Push and release between prove_steps, never during one (include/vdf_nova.h)."""
+
+    @staticmethod
+    def begin(t: int, initials: Sequence[State]) -> Tuple[List[bytes], "LaneCircuits"]:
+        """(z0 = the lanes' initial states flattened, an empty chain)"""
+        L = len(initials)
+        z0 = (_Fe * (3 * max(L, 1)))()
+        raw = b"".join(s.x + s.y + s.i for s in initials) or bytes(96)
+        h = C.c_void_p()
+        _check(nova_lib.vdf_nova_circuits_lanes_begin(t, L, raw, z0, C.byref(h)))
+        c = LaneCircuits(h.value, t)
+        c.lanes = L
+        return [bytes(z0[k]) for k in range(3 * L)], c
+
+    def push_traces(self, traces, lane_stride: Optional[int] = None) -> None:
+        """Appends a step from the lanes' host traces: a sequence of `lanes` arrays of 2 (t + 1) elements, or one array of
+        lanes x 2 lane_stride elements."""
+        if lane_stride is None:
+            lane_stride = self.t + 1
+            tr = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype="<u8").reshape(-1, 4) for x in traces]), dtype="<u8")
+        else:
+            tr = np.ascontiguousarray(traces, dtype="<u8").reshape(-1, 4)
+        if tr.shape[0] < 2 * ((self.lanes - 1) * lane_stride + self.t + 1):
+            raise ValueError("lanes traces of 2 (t + 1) elements expected")
+        _check(nova_lib.vdf_nova_circuits_push_traces(self.handle, tr.ctypes.data, lane_stride))
+
+    def push_checkpoints(self, every: int, states, lane_stride: Optional[int] = None) -> None:
+        """Appends a step from every lane's t // every + 1 states: a sequence of `lanes` sequences of State, or (with lane_stride)
+        one uint64 array of states laid out as vdf_minroot_eval_batch writes them, lane l's at states[l * lane_stride]."""
+        if lane_stride is None:
+            lane_stride = len(states[0])
+            raw = b"".join(s.x + s.y + s.i for lane in states for s in lane)
+            if any(len(lane) != lane_stride for lane in states) or len(states) != self.lanes:
+                raise ValueError("lanes runs of equally many states expected")
+            buf = (C.c_char * max(len(raw), 1)).from_buffer_copy(raw or b"\0")
+            _check(nova_lib.vdf_nova_circuits_push_checkpoints_lanes(self.handle, every, buf, lane_stride))
+        else:
+            arr = np.ascontiguousarray(states, dtype="<u8")
+            _check(nova_lib.vdf_nova_circuits_push_checkpoints_lanes(self.handle, every, arr.ctypes.data, lane_stride))
+
+    def lane_states(self, k: int, lane: int) -> Tuple[State, State]:
+        """(result, input) of lane `lane` of circuit k"""
+        r, i = _State(), _State()
+        _check(nova_lib.vdf_nova_circuit_lane_states(self.handle, k, lane, C.byref(r), C.byref(i)))
+        return State._from_c(r), State._from_c(i)
 
 
 class StreamStats(C.Structure):   # vdf_nova_stream_stats
