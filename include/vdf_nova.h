@@ -191,6 +191,24 @@ int  vdf_nova_public_params_ro(vdf_ctx* ctx, uint64_t num_iters_per_step, int ci
 int  vdf_nova_public_params_lanes(vdf_ctx* ctx, uint64_t num_iters_per_step, size_t lanes, int gens_family, const vdf_nova_ro_params* ro,
                                   const vdf_nova_tuning* tuning, vdf_pp** out);
 size_t vdf_nova_pp_lanes(const vdf_pp* pp);     /* 1 for every kind but VDF_CIRCUIT_MINROOT_FORWARD_LANES */
+/* ---- the cycle in either ORIENTATION ---------------------------------------------------------------------------------
+ * The orientation of a parameter set is the field of its primary circuit, which is the VDF's field.  VDF_FIELD_FQ (G1 = Pallas,
+ * G2 = Vesta: PallasVDF chains) is what every constructor above makes.  VDF_FIELD_FP is the reverse (G1 = Vesta, G2 = Pallas:
+ * VestaVDF chains, what vdf_minroot_eval*(VDF_FIELD_FP) and vdf_minroot_eval_batch(VDF_FIELD_FP) produce).  Nothing else about
+ * the protocol changes: the digest formula (no orientation byte: the matrices differ), the wire magics, the random-oracle blocks
+ * and the generator families (seed / label per curve) are the same, and the secondary circuit is still TrivialTestCircuit.  A
+ * proof attests a chain over ONE field.  Everything that takes a pp -- prove_step, prove_recursively[_windowed], eval_and_prove
+ * (its evaluator thread runs the pp's field), verify, compress[_batch], verify_compressed[_batch], verify_batch, both
+ * (de)serialisers, the _custom trio, introspection -- follows the pp's orientation; "primary" then reads "the Fp side, committed
+ * on Vesta".  Refused with VDF_ERR_BAD_ARG and nothing done: a pp of one orientation with circuits of the other; a blob made
+ * under the other orientation (its digest differs).  Canonicity of imported scalars is checked against each side's own modulus.
+ *
+ * The general constructor: every built-in kind; lanes is meaningful for VDF_CIRCUIT_MINROOT_FORWARD_LANES (1 gives the forward
+ * circuit itself, as vdf_nova_public_params_lanes does) and must be 1 otherwise.  ro / tuning: NULL = the defaults.  The
+ * constructors above are field = VDF_FIELD_FQ through the same code. */
+int  vdf_nova_public_params_field(vdf_ctx* ctx, int field, uint64_t num_iters_per_step, int circuit_kind, size_t lanes, int gens_family,
+                                  const vdf_nova_ro_params* ro, const vdf_nova_tuning* tuning, vdf_pp** out);
+int  vdf_nova_pp_field(const vdf_pp* pp);       /* the orientation: VDF_FIELD_FQ / VDF_FIELD_FP (-1 for NULL) */
 int  vdf_nova_pp_setup_ms(const vdf_pp* pp, double ms[7]);
 /* bytes of HBM held per side: generators, their fixed-base table, the digit table (0 = none; *skipped bit s set when
  * side s wanted one and it did not fit).  The primary side's figures include the derived generators of the packed
@@ -229,6 +247,16 @@ int  vdf_nova_eval_and_make_circuits(int mode, uint64_t num_iters_per_step, size
  * proving, produced by the untimed forward evaluation).  On checkpoint circuits: vdf_nova_circuits_materialize of all of
  * them with wait = 1, so that eval -> upload -> prove works with either kind. */
 int  vdf_nova_circuits_upload(vdf_ctx* ctx, vdf_circuits* c);
+/* The constructors of circuits with the chain's FIELD given: a handle remembers it (vdf_nova_circuits_field), and its evaluator,
+ * its round counters (.i arithmetic), its push checks and the inverse walks / landing checks of vdf_nova_circuits_materialize
+ * run over it.  The constructors without the argument are field = VDF_FIELD_FQ.  VDF_FIELD_FP ignores `mode`, as VestaVDF does. */
+int  vdf_nova_eval_and_make_circuits_field(int field, int mode, uint64_t num_iters_per_step, size_t num_steps,
+                                           const vdf_state* initial_state, vdf_fe z0_primary[3], vdf_circuits** out);
+int  vdf_nova_circuits_from_checkpoints_field(int field, uint64_t t, uint64_t every, size_t num_steps, const vdf_state* states,
+                                              vdf_fe z0_primary[3], vdf_circuits** out);
+int  vdf_nova_circuits_forward_begin_field(int field, uint64_t t, const vdf_state* initial_state, vdf_fe z0_primary[3], vdf_circuits** out);
+int  vdf_nova_circuits_lanes_begin_field(int field, uint64_t t, size_t lanes, const vdf_state* initial, vdf_fe* z0_primary, vdf_circuits** out);
+int  vdf_nova_circuits_field(const vdf_circuits* c);      /* VDF_FIELD_FQ / VDF_FIELD_FP (-1 for NULL) */
 /* The circuits of a chain evaluated ELSEWHERE.  states: the chain's states every `every` rounds in forward order,
  * num_steps * (t / every) + 1 of them, states[0] the initial state; `every` divides t (every = t: one state per step
  * boundary, exactly what the reference's circuits hold, :57-66).  Host only; holds the states and NO trace (96 bytes per
@@ -338,7 +366,7 @@ int  vdf_nova_verify(const vdf_proof* proof, vdf_pp* pp, size_t num_steps, const
 void vdf_nova_proof_free(vdf_proof* proof);
 size_t vdf_nova_proof_num_steps(const vdf_proof* proof);
 /* Introspection for the parity tests.  Instances: commitments as affine points, u and X[2] in Montgomery form of the
- * instance's own scalar field (Fq on the primary side, Fp on the secondary).  Witness pointers: device memory,
+ * instance's own scalar field (the parameters' field on the primary side, the other one on the secondary).  Witness pointers: device memory,
  * z = [W | u | X] (W = the first num_vars elements) and E (NULL for the fresh instance). */
 enum { VDF_INST_RUNNING_PRIMARY = 0, VDF_INST_RUNNING_SECONDARY = 1, VDF_INST_FRESH_SECONDARY = 2,
        /* witness pointer only: z of the fresh primary instance the LAST prove_step folded (its instance: vdf_nova_proof_last_step);
@@ -391,6 +419,8 @@ int     vdf_cs_value(const vdf_cs* cs, vdf_num a, vdf_fe* out);       /* witness
 int  vdf_nova_public_params_custom(vdf_ctx* ctx, const vdf_step_circuit* primary, int gens_family, vdf_pp** out);
 int  vdf_nova_prove_step_custom(vdf_pp* pp, vdf_proof** proof, const vdf_step_circuit* primary, const vdf_fe* z0);
 int  vdf_nova_verify_custom(const vdf_proof* proof, vdf_pp* pp, size_t num_steps, const vdf_fe* z0, const vdf_fe* zi, int* ok);
+/* the same parameters in the orientation `field`: the custom circuit is synthesised over that field (vdf_cs_* values are its elements) */
+int  vdf_nova_public_params_custom_field(vdf_ctx* ctx, int field, const vdf_step_circuit* primary, int gens_family, vdf_pp** out);
 
 /* ---- host-only entry points (no device): what the CPU tests pin against oracle/nova.py ------------------------- */
 /* the random oracle: lane 1 of the sponge after absorbing xs under `tag` (a full field element, Montgomery in and out) */
@@ -435,6 +465,22 @@ int  vdf_nova_shape_export_lanes(uint64_t num_iters_per_step, size_t lanes, int 
 int  vdf_nova_aug_synthesize_lanes(const vdf_nova_ro_params* ro, uint64_t num_iters_per_step, size_t lanes, const vdf_nova_aug_inputs* in,
                                    const vdf_fe* z0, const vdf_fe* zi, const vdf_state* results, const vdf_state* inputs, vdf_fe* W,
                                    size_t w_cap, size_t* num_vars, size_t* num_cons, vdf_fe X[2], vdf_fe* z_next);
+
+/* The host-only entry points in the orientation `field` (the primary circuit's field), one general form each: circuit_kind is
+ * any built-in kind, lanes is meaningful for VDF_CIRCUIT_MINROOT_FORWARD_LANES (1 = the forward circuit) and must be 1 otherwise;
+ * ro: NULL = the default block.  aug_synthesize_field: side 1 ignores the step's arguments; on side 0, z0 / zi (3 lanes elements)
+ * replace those of `in` when given (required for more than one lane), results / inputs hold one state per lane and z_next gets
+ * 3 lanes elements. */
+int  vdf_nova_shape_digest_field(int field, const vdf_nova_ro_params* ro, uint64_t num_iters_per_step, int circuit_kind, size_t lanes,
+                                 int gens_family, uint8_t out[32], uint64_t sizes[2][3]);
+int  vdf_nova_shape_export_field(int field, uint64_t num_iters_per_step, int circuit_kind, size_t lanes, int side, uint64_t nnz[3],
+                                 uint32_t* const rows[3], uint32_t* const cols[3], vdf_fe* const vals[3]);
+int  vdf_nova_shape_stencil_field(int field, uint64_t t, int circuit_kind, size_t lanes, uint64_t* early_begin, uint64_t* early_len,
+                                  uint64_t* seg_begin);
+int  vdf_nova_aug_synthesize_field(int field, const vdf_nova_ro_params* ro, int side, uint64_t num_iters_per_step, int circuit_kind,
+                                   size_t lanes, const vdf_nova_aug_inputs* in, const vdf_fe* z0, const vdf_fe* zi, const vdf_state* results,
+                                   const vdf_state* inputs, vdf_fe* W, size_t w_cap, size_t* num_vars, size_t* num_cons, vdf_fe X[2],
+                                   vdf_fe* z_next);
 
 /* of the calling thread's last augmented-circuit synthesis: how many slope inverses the native pre-pass queued (batched
  * inversion) and how many of them were wrong or unused (0 for well-formed inputs: the queue is only an accelerator) */

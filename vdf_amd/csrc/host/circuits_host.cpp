@@ -7,8 +7,8 @@ using namespace vdfnova;
 
 namespace {
 // states[1 .. n] count on from states[0], whose i is `from`, in steps of `every`
-int check_counters(const vdf_state* states, size_t n, Fe from, uint64_t every) {
-  const Field& F = field(VDF_FIELD_FQ);
+int check_counters(int fid, const vdf_state* states, size_t n, Fe from, uint64_t every) {
+  const Field& F = field(fid);
   const Fe step = from_u64(every, F);
   for (size_t k = 1; k <= n; ++k) {
     from = add(from, step, F);
@@ -75,7 +75,7 @@ int job_enqueue(const vdf_circuits* c, uint64_t rounds) {
   const uint64_t t = c->v[j->steps[0]].t;
   while (rounds && j->done < j->every) {
     const uint64_t now = std::min(std::min(rounds, j->every - j->done), walk_launch_rounds());
-    HIPCALL(w.side, vdf_minroot_inverse_walk(w.side, VDF_FIELD_FQ, (vdf_state*)w.d_walk, j->walks, now, (vdf_fe*)j->block->d, (size_t)j->every,
+    HIPCALL(w.side, vdf_minroot_inverse_walk(w.side, c->field, (vdf_state*)w.d_walk, j->walks, now, (vdf_fe*)j->block->d, (size_t)j->every,
                                              (size_t)(j->every - j->done), j->per_step, (size_t)(t + 1)));
     j->done += now;
     rounds -= now;
@@ -90,7 +90,7 @@ int job_resolve(const vdf_circuits* c, int* bad, size_t bad_first, size_t bad_co
   auto lose = [&](size_t k) { Circuit& cc = written(c)->v[k]; cc.d_trace = nullptr; cc.block.reset(); };   // left without a trace
   int rc = job_enqueue(c, j->every);
   if (rc == VDF_OK && !j->matched) {
-    rc = vdf_minroot_check_batch(w.side, VDF_FIELD_FQ, (const vdf_state*)w.d_walk, (const vdf_state*)w.d_expect, j->walks, 0, w.h_ok);
+    rc = vdf_minroot_check_batch(w.side, c->field, (const vdf_state*)w.d_walk, (const vdf_state*)w.d_expect, j->walks, 0, w.h_ok);
     if (rc != VDF_OK) fail(rc, std::string("vdf_minroot_check_batch: ") + vdf_last_error(w.side));
     j->matched = true;
   }
@@ -146,17 +146,22 @@ int circuits_materialize(vdf_ctx* ctx, const vdf_circuits* c, size_t first, size
 extern "C" {
 int vdf_nova_eval_and_make_circuits(int mode, uint64_t t, size_t num_steps, const vdf_state* initial_state,
                                     vdf_fe z0_primary[3], vdf_circuits** out) {
+  return vdf_nova_eval_and_make_circuits_field(VDF_FIELD_FQ, mode, t, num_steps, initial_state, z0_primary, out);
+}
+int vdf_nova_eval_and_make_circuits_field(int fid, int mode, uint64_t t, size_t num_steps, const vdf_state* initial_state,
+                                          vdf_fe z0_primary[3], vdf_circuits** out) {
   return nova_guard([&]() -> int {
-    if (!valid_mode(mode) || !initial_state || !z0_primary || !out || t == 0) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    if (!valid_field(fid) || !valid_mode(mode) || !initial_state || !z0_primary || !out || t == 0) return fail(VDF_ERR_BAD_ARG, "bad argument");
     if (num_steps == 0) return fail(VDF_ERR_BAD_ARG, "num_steps must be > 0 (assert!, src/nova/proof.rs:268)");
     vdf_circuits* cs = new vdf_circuits();
+    cs->field = fid;
     St state = load_state(initial_state);
     for (size_t s = 0; s < num_steps; ++s) {                          // :274-279
       Circuit c;
       c.t = t;
       c.input = state;                                                 // previous_state, :285-291
       c.trace_xy.resize(2 * (t + 1));
-      eval_step(mode, t, &state, c.trace_xy.data());
+      eval_step(fid, mode, t, &state, c.trace_xy.data());
       c.result = state;
       cs->v.push_back(std::move(c));
     }
@@ -168,13 +173,18 @@ int vdf_nova_eval_and_make_circuits(int mode, uint64_t t, size_t num_steps, cons
 }
 int vdf_nova_circuits_from_checkpoints(uint64_t t, uint64_t every, size_t num_steps, const vdf_state* states,
                                        vdf_fe z0_primary[3], vdf_circuits** out) {
+  return vdf_nova_circuits_from_checkpoints_field(VDF_FIELD_FQ, t, every, num_steps, states, z0_primary, out);
+}
+int vdf_nova_circuits_from_checkpoints_field(int fid, uint64_t t, uint64_t every, size_t num_steps, const vdf_state* states,
+                                             vdf_fe z0_primary[3], vdf_circuits** out) {
   return nova_guard([&]() -> int {
-    if (!states || !z0_primary || !out || t == 0) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    if (!valid_field(fid) || !states || !z0_primary || !out || t == 0) return fail(VDF_ERR_BAD_ARG, "bad argument");
     if (num_steps == 0) return fail(VDF_ERR_BAD_ARG, "num_steps must be > 0 (assert!, src/nova/proof.rs:268)");
     if (every == 0 || t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
     const size_t per = (size_t)(t / every), total = num_steps * per + 1;
-    { int rc = check_counters(states, total - 1, load_state(&states[0]).i, every); if (rc != VDF_OK) return rc; }
+    { int rc = check_counters(fid, states, total - 1, load_state(&states[0]).i, every); if (rc != VDF_OK) return rc; }
     std::unique_ptr<vdf_circuits> cs(new vdf_circuits());
+    cs->field = fid;
     cs->checkpoints = true;
     cs->v.resize(num_steps);
     for (size_t s = 0; s < num_steps; ++s) cs->v[num_steps - 1 - s] = checkpoint_circuit(t, every, states + s * per, per);   // circuits.reverse(), :294
@@ -186,9 +196,13 @@ int vdf_nova_circuits_from_checkpoints(uint64_t t, uint64_t every, size_t num_st
 
 // ---- forward chains: circuits in the order of evaluation, appended to while the chain grows -------------------------
 int vdf_nova_circuits_forward_begin(uint64_t t, const vdf_state* initial_state, vdf_fe z0_primary[3], vdf_circuits** out) {
+  return vdf_nova_circuits_forward_begin_field(VDF_FIELD_FQ, t, initial_state, z0_primary, out);
+}
+int vdf_nova_circuits_forward_begin_field(int fid, uint64_t t, const vdf_state* initial_state, vdf_fe z0_primary[3], vdf_circuits** out) {
   return nova_guard([&]() -> int {
-    if (!initial_state || !z0_primary || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    if (!valid_field(fid) || !initial_state || !z0_primary || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
     std::unique_ptr<vdf_circuits> cs(new vdf_circuits());
+    cs->field = fid;
     cs->forward = true;
     cs->forward_t = t;
     cs->end = load_state(initial_state);
@@ -210,7 +224,7 @@ int vdf_nova_circuits_push_trace(vdf_circuits* c, const vdf_fe* trace_xy) {
     cc.input = c->end;
     memcpy(&cc.result.x, &trace_xy[2 * t], 32);
     memcpy(&cc.result.y, &trace_xy[2 * t + 1], 32);
-    cc.result.i = add(c->end.i, from_u64(t, field(VDF_FIELD_FQ)), field(VDF_FIELD_FQ));
+    cc.result.i = add(c->end.i, from_u64(t, field(c->field)), field(c->field));
     cc.trace_xy.assign((const Fe*)trace_xy, (const Fe*)trace_xy + 2 * (t + 1));
     c->end = cc.result;
     c->v.push_back(std::move(cc));
@@ -228,7 +242,7 @@ int vdf_nova_circuits_push_checkpoints(vdf_circuits* c, uint64_t every, const vd
       for (const Circuit& k : c->v) if (k.every && k.every != every) return fail(VDF_ERR_BAD_ARG, "`every` differs from the chain's earlier checkpoint steps");
     if (memcmp(&states[0], &c->end, 96) != 0) return fail(VDF_ERR_BAD_ARG, "states[0] is not the chain's current end");
     const size_t per = (size_t)(t / every);
-    { int rc = check_counters(states, per, c->end.i, every); if (rc != VDF_OK) return rc; }
+    { int rc = check_counters(c->field, states, per, c->end.i, every); if (rc != VDF_OK) return rc; }
     c->v.push_back(checkpoint_circuit(t, every, states, per));
     c->end = c->v.back().result;
     c->checkpoints = true;
@@ -237,11 +251,15 @@ int vdf_nova_circuits_push_checkpoints(vdf_circuits* c, uint64_t every, const vd
 }
 // ---- forward chains in lanes: a step advances `lanes` evaluations, its trace is their traces back to back ------------------
 int vdf_nova_circuits_lanes_begin(uint64_t t, size_t lanes, const vdf_state* initial, vdf_fe* z0_primary, vdf_circuits** out) {
-  if (lanes == 1) return vdf_nova_circuits_forward_begin(t, initial, z0_primary, out);     // one lane IS a forward chain
+  return vdf_nova_circuits_lanes_begin_field(VDF_FIELD_FQ, t, lanes, initial, z0_primary, out);
+}
+int vdf_nova_circuits_lanes_begin_field(int fid, uint64_t t, size_t lanes, const vdf_state* initial, vdf_fe* z0_primary, vdf_circuits** out) {
+  if (lanes == 1) return vdf_nova_circuits_forward_begin_field(fid, t, initial, z0_primary, out);     // one lane IS a forward chain
   return nova_guard([&]() -> int {
-    if (!initial || !z0_primary || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    if (!valid_field(fid) || !initial || !z0_primary || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
     if (lanes == 0 || lanes > VDF_NOVA_MAX_LANES) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_NOVA_MAX_LANES");
     std::unique_ptr<vdf_circuits> cs(new vdf_circuits());
+    cs->field = fid;
     cs->forward = true;
     cs->forward_t = t;
     cs->lanes = lanes;
@@ -260,7 +278,7 @@ int vdf_nova_circuits_push_traces(vdf_circuits* c, const vdf_fe* trace_xy, size_
     const uint64_t t = c->forward_t;
     const size_t L = c->lanes;
     if (lane_stride < t + 1) return fail(VDF_ERR_BAD_ARG, "lane_stride must be at least t + 1");
-    const Field& F = field(VDF_FIELD_FQ);
+    const Field& F = field(c->field);
     Circuit cc;
     cc.t = t;
     cc.lane_input = c->lane_end;
@@ -300,7 +318,7 @@ int vdf_nova_circuits_push_checkpoints_lanes(vdf_circuits* c, uint64_t every, co
     for (size_t l = 0; l < L; ++l) {                                   // every lane checked before anything is appended
       const vdf_state* st = states + l * lane_stride;
       if (memcmp(&st[0], &c->lane_end[l], 96) != 0) return fail(VDF_ERR_BAD_ARG, "lane " + std::to_string(l) + ": states[0] is not the lane's current end");
-      if (check_counters(st, per, c->lane_end[l].i, every) != VDF_OK) return fail(VDF_ERR_BAD_ARG, "lane " + std::to_string(l) + ": " + vdf_nova_last_error());
+      if (check_counters(c->field, st, per, c->lane_end[l].i, every) != VDF_OK) return fail(VDF_ERR_BAD_ARG, "lane " + std::to_string(l) + ": " + vdf_nova_last_error());
     }
     Circuit cc;
     cc.t = t; cc.every = every;
@@ -318,6 +336,7 @@ int vdf_nova_circuits_push_checkpoints_lanes(vdf_circuits* c, uint64_t every, co
   });
 }
 size_t vdf_nova_circuits_lanes(const vdf_circuits* c) { return c ? c->lanes : 0; }
+int vdf_nova_circuits_field(const vdf_circuits* c) { return c ? c->field : -1; }
 int vdf_nova_circuit_lane_states(const vdf_circuits* c, size_t k, size_t lane, vdf_state* result, vdf_state* input) {
   if (!c || k >= c->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
   if (lane >= c->lanes) return fail(VDF_ERR_BAD_LENGTH, "lane out of range");

@@ -816,6 +816,7 @@ struct vdf_snark {          // NovaVDFProof::Compressed, src/nova/proof.rs:54 = 
   Fe zi2[1];
   uint64_t t = 0;           // the public parameters it was made under (wire header)
   uint8_t digest[32];
+  int field = VDF_FIELD_FQ; // ... and their orientation: the primary side's scalar field (what the encodings below reduce by)
 };
 
 namespace {
@@ -870,6 +871,7 @@ int compress_prelude(const vdf_proof* p, vdf_pp* pp, vdf_snark* s, void* d_fz, v
   vdf_ctx* ctx = pp->ctx;
   const Side& S2 = pp->s[SECONDARY];
   s->t = pp->t;
+  s->field = pp->field;
   memcpy(s->digest, pp->digest, 32);
   s->r_U1 = p->r[PRIMARY].inst; s->r_U2 = p->r[SECONDARY].inst; s->l_u2 = p->l2;
   s->zi1 = p->zi[PRIMARY];
@@ -1294,8 +1296,8 @@ int vdf_nova_snark_bytes(const vdf_snark* s, uint8_t* out, size_t cap) {
     if (cap < vdf_nova_snark_size(s)) return fail(VDF_ERR_BAD_LENGTH, "buffer too small");
     uint8_t* o = out;
     for (int side = 0; side < 2; ++side) {
-      const Field& F = field(side_field(side));
-      const Field& Fb = field(side_field(1 - side));
+      const Field& F = field(cycle_field(s->field, side));
+      const Field& Fb = field(cycle_field(s->field, 1 - side));
       const Spartan& sp = s->sp[side];
       auto put = [&](const Fe& v, const Field& f) { const Fe c = from_mont(v, f); memcpy(o, c.l, 32); o += 32; };
       auto put_pt = [&](const Aff& a) { if (a.is_id()) { memset(o, 0, 64); o += 64; } else { put(a.x, Fb); put(a.y, Fb); } };
@@ -1322,8 +1324,8 @@ int vdf_nova_snark_set_bytes(vdf_snark* s, const uint8_t* in, size_t len) {
     bool canonical = true, on_curve = true;
     Spartan tmp[2] = {s->sp[0], s->sp[1]};
     for (int side = 0; side < 2; ++side) {
-      const Field& F = field(side_field(side));
-      const Field& Fb = field(side_field(1 - side));
+      const Field& F = field(cycle_field(s->field, side));
+      const Field& Fb = field(cycle_field(s->field, 1 - side));
       Spartan& sp = tmp[side];
       auto get = [&](Fe& v, const Field& f) { Fe c; memcpy(c.l, i, 32); i += 32; if (geq(c.l, f.m)) canonical = false; v = to_mont(c, f); };
       auto get_pt = [&](Aff& a) {
@@ -1360,7 +1362,7 @@ int vdf_nova_snark_serialize(const vdf_snark* s, uint8_t* out, size_t cap) {
     if (!s || !out) return fail(VDF_ERR_BAD_ARG, "null argument");
     if (cap < vdf_nova_snark_serialized_size(s)) return fail(VDF_ERR_BAD_LENGTH, "buffer too small");
     Side sd[2];
-    for (int k = 0; k < 2; ++k) { sd[k].F = &field(side_field(k)); sd[k].Fb = &field(side_field(1 - k)); }
+    for (int k = 0; k < 2; ++k) { sd[k].F = &field(cycle_field(s->field, k)); sd[k].Fb = &field(cycle_field(s->field, 1 - k)); }
     uint8_t* o = out;
     memcpy(o, WIRE_MAGIC_SNARK, 8); o += 8;
     memcpy(o, &s->t, 8); o += 8;
@@ -1403,6 +1405,7 @@ int vdf_nova_snark_deserialize(vdf_pp* pp, const uint8_t* in, size_t len, vdf_sn
       return fail(VDF_ERR_BAD_LENGTH, "encoding has the wrong length for this shape");
     std::unique_ptr<vdf_snark> s(new vdf_snark());
     s->t = t;
+    s->field = pp->field;
     memcpy(s->digest, pp->digest, 32);
     const uint8_t* i = in + 48;
     bool canonical = true, on_curve = true;

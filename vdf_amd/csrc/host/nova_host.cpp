@@ -164,14 +164,15 @@ AugInputs blank_inputs(size_t arity) {
 struct HostShape { Coo m[3]; size_t num_cons = 0, num_vars = 0, step_begin = 0, step_end = 0; };
 
 // both augmented circuits in shape mode (PublicParams::setup, src/nova/proof.rs:236)
-int build_shapes(uint64_t t, int circuit_kind, HostShape out[2], const vdf_step_circuit* custom = nullptr, const RoInstance* ro = nullptr,
+// (fid: the orientation, the primary circuit's field)
+int build_shapes(int fid, uint64_t t, int circuit_kind, HostShape out[2], const vdf_step_circuit* custom = nullptr, const RoInstance* ro = nullptr,
                  size_t lanes = 1) {
   vdf_pp tmp;
   tmp.t = t;
   tmp.circuit_kind = circuit_kind;
   tmp.lanes = lanes;
   for (int side = 0; side < 2; ++side) {
-    CS cs(side_field(side), true, ro);
+    CS cs(cycle_field(fid, side), true, ro);
     std::unique_ptr<StepCircuit> step;
     if (side == PRIMARY) step = custom ? make_custom_circuit(custom) : make_primary_circuit(&tmp, nullptr, false);
     else step.reset(new TrivialTestCircuit());
@@ -191,7 +192,7 @@ int build_shapes(uint64_t t, int circuit_kind, HostShape out[2], const vdf_step_
 }
 
 // oracle/nova.py digest_shapes
-void digest_shapes(uint64_t t, int gens_family, const HostShape sh[2], uint8_t out[32], const RoInstance* ro = nullptr) {
+void digest_shapes(int fid, uint64_t t, int gens_family, const HostShape sh[2], uint8_t out[32], const RoInstance* ro = nullptr) {
   Shake256 h;
   h.absorb("vdf-nova-ivc-v1", 15);
   if (!ro) ro = ro_default();
@@ -199,7 +200,7 @@ void digest_shapes(uint64_t t, int gens_family, const HostShape sh[2], uint8_t o
   const uint64_t hdr[3] = {t, GENS_SEED, (uint64_t)gens_family};
   h.absorb(hdr, sizeof(hdr));
   for (int side = 0; side < 2; ++side) {
-    const Field& F = field(side_field(side));
+    const Field& F = field(cycle_field(fid, side));
     const uint64_t sz[3] = {(uint64_t)sh[side].num_cons, (uint64_t)sh[side].num_vars, (uint64_t)NUM_IO};
     h.absorb(sz, sizeof(sz));
     for (int k = 0; k < 3; ++k) {
@@ -486,18 +487,26 @@ int vdf_nova_ro_hash_ro(const vdf_nova_ro_params* rop, int f, uint64_t tag, cons
 }
 int vdf_nova_ro_hash(int f, uint64_t tag, const vdf_fe* xs, size_t n, vdf_fe* out) { return vdf_nova_ro_hash_ro(nullptr, f, tag, xs, n, out); }
 
-int vdf_nova_shape_digest(uint64_t t, int circuit_kind, int gens_family, uint8_t out[32], uint64_t sizes[2][3]) {
-  return vdf_nova_shape_digest_ro(nullptr, t, circuit_kind, gens_family, out, sizes);
+// One general form per entry point, in either orientation; the entry points of before are these at VDF_FIELD_FQ.
+// kind / lanes as the ABI gives them -> the kind the shapes are built for (lanes of 1 IS the forward circuit); false: refused
+static bool resolve_kind(int* circuit_kind, size_t lanes) {
+  if (*circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES) {
+    if (!lanes_valid(lanes)) return false;
+    *circuit_kind = lanes_kind(lanes);
+    return true;
+  }
+  return builtin_circuit(*circuit_kind) && lanes == 1;
 }
-int vdf_nova_shape_digest_ro(const vdf_nova_ro_params* rop, uint64_t t, int circuit_kind, int gens_family, uint8_t out[32], uint64_t sizes[2][3]) {
+static int shape_digest_impl(int fid, const vdf_nova_ro_params* rop, uint64_t t, int circuit_kind, size_t lanes, int gens_family, uint8_t out[32],
+                             uint64_t sizes[2][3]) {
   return nova_guard([&]() -> int {
     bool bad;
     const RoInstance* ro = ro_from_abi(rop, &bad);
     if (bad) return fail(VDF_ERR_BAD_ARG, "unsupported RO parameter block");
     if (t == 0 || t > (1ull << 24) || !out) return fail(VDF_ERR_BAD_ARG, "bad argument");
     HostShape sh[2];
-    build_shapes(t, circuit_kind, sh, nullptr, ro);
-    digest_shapes(t, gens_family, sh, out, ro);
+    build_shapes(fid, t, circuit_kind, sh, nullptr, ro, lanes);
+    digest_shapes(fid, t, gens_family, sh, out, ro);
     if (sizes)
       for (int s = 0; s < 2; ++s) {
         sizes[s][0] = sh[s].num_cons; sizes[s][1] = sh[s].num_vars;
@@ -506,16 +515,26 @@ int vdf_nova_shape_digest_ro(const vdf_nova_ro_params* rop, uint64_t t, int circ
     return VDF_OK;
   });
 }
+int vdf_nova_shape_digest_field(int fid, const vdf_nova_ro_params* rop, uint64_t t, int circuit_kind, size_t lanes, int gens_family,
+                                uint8_t out[32], uint64_t sizes[2][3]) {
+  if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "field must be VDF_FIELD_FP or VDF_FIELD_FQ");
+  if (!resolve_kind(&circuit_kind, lanes)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit, or lanes out of range for it");
+  return shape_digest_impl(fid, rop, t, circuit_kind, lanes, gens_family, out, sizes);
+}
+int vdf_nova_shape_digest(uint64_t t, int circuit_kind, int gens_family, uint8_t out[32], uint64_t sizes[2][3]) {
+  return vdf_nova_shape_digest_ro(nullptr, t, circuit_kind, gens_family, out, sizes);
+}
+int vdf_nova_shape_digest_ro(const vdf_nova_ro_params* rop, uint64_t t, int circuit_kind, int gens_family, uint8_t out[32], uint64_t sizes[2][3]) {
+  return shape_digest_impl(VDF_FIELD_FQ, rop, t, circuit_kind, 1, gens_family, out, sizes);
+}
 
 // The R1CS shape public_params would make, as COO triples (row-major order of the constraints' creation, values in Montgomery
 // form of the side's field): two calls, first with null arrays for the counts.
-int vdf_nova_shape_export(uint64_t t, int circuit_kind, int side, uint64_t nnz[3], uint32_t* const rows[3], uint32_t* const cols[3],
-                          vdf_fe* const vals[3]) {
+static int shape_export_impl(int fid, uint64_t t, int circuit_kind, size_t lanes, int side, uint64_t nnz[3], uint32_t* const rows[3],
+                             uint32_t* const cols[3], vdf_fe* const vals[3]) {
   return nova_guard([&]() -> int {
-    if (t == 0 || t > (1ull << 24) || !nnz || (side != PRIMARY && side != SECONDARY)) return fail(VDF_ERR_BAD_ARG, "bad argument");
-    if (!builtin_circuit(circuit_kind)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
     HostShape sh[2];
-    build_shapes(t, circuit_kind, sh);
+    build_shapes(fid, t, circuit_kind, sh, nullptr, nullptr, lanes);
     const HostShape& h = sh[side];
     const bool fill = rows && cols && vals;
     for (int k = 0; k < 3; ++k) {
@@ -531,13 +550,25 @@ int vdf_nova_shape_export(uint64_t t, int circuit_kind, int side, uint64_t nnz[3
     return VDF_OK;
   });
 }
+int vdf_nova_shape_export_field(int fid, uint64_t t, int circuit_kind, size_t lanes, int side, uint64_t nnz[3], uint32_t* const rows[3],
+                                uint32_t* const cols[3], vdf_fe* const vals[3]) {
+  if (!valid_field(fid) || t == 0 || t > (1ull << 24) || !nnz || (side != PRIMARY && side != SECONDARY)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+  if (!resolve_kind(&circuit_kind, lanes)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit, or lanes out of range for it");
+  return shape_export_impl(fid, t, circuit_kind, lanes, side, nnz, rows, cols, vals);
+}
+int vdf_nova_shape_export(uint64_t t, int circuit_kind, int side, uint64_t nnz[3], uint32_t* const rows[3], uint32_t* const cols[3],
+                          vdf_fe* const vals[3]) {
+  if (t == 0 || t > (1ull << 24) || !nnz || (side != PRIMARY && side != SECONDARY)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+  if (!builtin_circuit(circuit_kind)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
+  return shape_export_impl(VDF_FIELD_FQ, t, circuit_kind, 1, side, nnz, rows, cols, vals);
+}
 
 int vdf_nova_shape_digest_custom(const vdf_step_circuit* primary, int gens_family, uint8_t out[32], uint64_t sizes[2][3]) {
   return nova_guard([&]() -> int {
     if (!primary || !primary->synthesize || primary->arity == 0 || primary->arity > 64 || !out) return fail(VDF_ERR_BAD_ARG, "bad argument");
     HostShape sh[2];
-    { int rc = build_shapes(0, VDF_CIRCUIT_CUSTOM, sh, primary); if (rc != VDF_OK) return rc; }
-    digest_shapes(0, gens_family, sh, out);
+    { int rc = build_shapes(VDF_FIELD_FQ, 0, VDF_CIRCUIT_CUSTOM, sh, primary); if (rc != VDF_OK) return rc; }
+    digest_shapes(VDF_FIELD_FQ, 0, gens_family, sh, out);
     if (sizes)
       for (int s = 0; s < 2; ++s) {
         sizes[s][0] = sh[s].num_cons; sizes[s][1] = sh[s].num_vars;
@@ -547,8 +578,9 @@ int vdf_nova_shape_digest_custom(const vdf_step_circuit* primary, int gens_famil
   });
 }
 
-static AugInputs aug_from_abi(int side, const vdf_nova_aug_inputs* a) {
-  const Field& own = field(side_field(1 - side));                       // the folded side's scalar field
+// (fid: the orientation; the folded side's scalars are in the field of the OTHER side's circuit)
+static AugInputs aug_from_abi(int fid, int side, const vdf_nova_aug_inputs* a) {
+  const Field& own = field(cycle_field(fid, 1 - side));                 // the folded side's scalar field
   const size_t arity = side == PRIMARY ? 3 : 1;
   AugInputs in;
   memcpy(&in.params, &a->params, 32);
@@ -566,14 +598,11 @@ static AugInputs aug_from_abi(int side, const vdf_nova_aug_inputs* a) {
   return in;
 }
 
-int vdf_nova_aug_synthesize(int side, uint64_t t, int circuit_kind, const vdf_nova_aug_inputs* a, const vdf_state* result,
-                            const vdf_state* input, vdf_fe* W, size_t w_cap, size_t* num_vars, size_t* num_cons, vdf_fe X[2],
-                            vdf_fe z_next[3]) {
-  return vdf_nova_aug_synthesize_ro(nullptr, side, t, circuit_kind, a, result, input, W, w_cap, num_vars, num_cons, X, z_next);
-}
-int vdf_nova_aug_synthesize_ro(const vdf_nova_ro_params* rop, int side, uint64_t t, int circuit_kind, const vdf_nova_aug_inputs* a,
-                               const vdf_state* result, const vdf_state* input, vdf_fe* W, size_t w_cap, size_t* num_vars, size_t* num_cons,
-                               vdf_fe X[2], vdf_fe z_next[3]) {
+// one augmented circuit with every variable made on the host.  Side 0: results / inputs hold one state per lane; z0 / zi (optional
+// for one lane: those of `a` then) 3 lanes elements
+static int aug_synthesize_impl(int fid, const vdf_nova_ro_params* rop, int side, uint64_t t, int circuit_kind, size_t lanes,
+                               const vdf_nova_aug_inputs* a, const vdf_fe* z0, const vdf_fe* zi, const vdf_state* results, const vdf_state* inputs,
+                               vdf_fe* W, size_t w_cap, size_t* num_vars, size_t* num_cons, vdf_fe X[2], vdf_fe* z_next) {
   return nova_guard([&]() -> int {
     bool bad;
     const RoInstance* ro = ro_from_abi(rop, &bad);
@@ -582,15 +611,23 @@ int vdf_nova_aug_synthesize_ro(const vdf_nova_ro_params* rop, int side, uint64_t
     vdf_pp tmp;
     tmp.t = t;
     tmp.circuit_kind = circuit_kind;
+    tmp.lanes = lanes;
     std::unique_ptr<StepCircuit> step;
     Circuit c;
     if (side == PRIMARY) {
-      if (!result || !input) return fail(VDF_ERR_BAD_ARG, "the primary circuit needs the step's states");
-      c.result = load_state(result); c.input = load_state(input); c.t = t;
+      if (!results || !inputs) return fail(VDF_ERR_BAD_ARG, "the primary circuit needs the step's states");
+      if (lanes > 1 && (!z0 || !zi)) return fail(VDF_ERR_BAD_ARG, "a circuit of more than one lane needs z0 and zi");
+      c.result = load_state(&results[0]); c.input = load_state(&inputs[0]); c.t = t;
+      if (circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES)
+        for (size_t l = 0; l < lanes; ++l) { c.lane_result.push_back(load_state(&results[l])); c.lane_input.push_back(load_state(&inputs[l])); }
       step = make_primary_circuit(&tmp, &c, false);
     } else step.reset(new TrivialTestCircuit());
-    CS cs(side_field(side), false, ro);
-    AugInputs ain = aug_from_abi(side, a);
+    CS cs(cycle_field(fid, side), false, ro);
+    AugInputs ain = aug_from_abi(fid, side, a);
+    if (side == PRIMARY && z0 && zi) {
+      ain.z0.assign((const Fe*)z0, (const Fe*)z0 + 3 * lanes);
+      ain.zi.assign((const Fe*)zi, (const Fe*)zi + 3 * lanes);
+    }
     ain.ro = ro;
     const std::vector<Fe> zn = synthesize_augmented(cs, side, ain, *step);
     if (num_vars) *num_vars = cs.W.size();
@@ -604,79 +641,39 @@ int vdf_nova_aug_synthesize_ro(const vdf_nova_ro_params* rop, int side, uint64_t
     return VDF_OK;
   });
 }
+int vdf_nova_aug_synthesize_field(int fid, const vdf_nova_ro_params* rop, int side, uint64_t t, int circuit_kind, size_t lanes,
+                                  const vdf_nova_aug_inputs* a, const vdf_fe* z0, const vdf_fe* zi, const vdf_state* results,
+                                  const vdf_state* inputs, vdf_fe* W, size_t w_cap, size_t* num_vars, size_t* num_cons, vdf_fe X[2], vdf_fe* z_next) {
+  if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "field must be VDF_FIELD_FP or VDF_FIELD_FQ");
+  if (!resolve_kind(&circuit_kind, lanes)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit, or lanes out of range for it");
+  return aug_synthesize_impl(fid, rop, side, t, circuit_kind, lanes, a, z0, zi, results, inputs, W, w_cap, num_vars, num_cons, X, z_next);
+}
+int vdf_nova_aug_synthesize(int side, uint64_t t, int circuit_kind, const vdf_nova_aug_inputs* a, const vdf_state* result,
+                            const vdf_state* input, vdf_fe* W, size_t w_cap, size_t* num_vars, size_t* num_cons, vdf_fe X[2],
+                            vdf_fe z_next[3]) {
+  return vdf_nova_aug_synthesize_ro(nullptr, side, t, circuit_kind, a, result, input, W, w_cap, num_vars, num_cons, X, z_next);
+}
+int vdf_nova_aug_synthesize_ro(const vdf_nova_ro_params* rop, int side, uint64_t t, int circuit_kind, const vdf_nova_aug_inputs* a,
+                               const vdf_state* result, const vdf_state* input, vdf_fe* W, size_t w_cap, size_t* num_vars, size_t* num_cons,
+                               vdf_fe X[2], vdf_fe z_next[3]) {
+  return aug_synthesize_impl(VDF_FIELD_FQ, rop, side, t, circuit_kind, 1, a, nullptr, nullptr, result, input, W, w_cap, num_vars, num_cons, X, z_next);
+}
 
 // ---- the forward circuit in lanes, host only --------------------------------------------------------------------------
 int vdf_nova_shape_digest_lanes(const vdf_nova_ro_params* rop, uint64_t t, size_t lanes, int gens_family, uint8_t out[32], uint64_t sizes[2][3]) {
-  return nova_guard([&]() -> int {
-    bool bad;
-    const RoInstance* ro = ro_from_abi(rop, &bad);
-    if (bad) return fail(VDF_ERR_BAD_ARG, "unsupported RO parameter block");
-    if (t == 0 || t > (1ull << 24) || !out || !lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "bad argument");
-    HostShape sh[2];
-    build_shapes(t, lanes_kind(lanes), sh, nullptr, ro, lanes);
-    digest_shapes(t, gens_family, sh, out, ro);
-    if (sizes)
-      for (int s = 0; s < 2; ++s) {
-        sizes[s][0] = sh[s].num_cons; sizes[s][1] = sh[s].num_vars;
-        sizes[s][2] = sh[s].m[0].rows.size() + sh[s].m[1].rows.size() + sh[s].m[2].rows.size();
-      }
-    return VDF_OK;
-  });
+  if (!lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+  return shape_digest_impl(VDF_FIELD_FQ, rop, t, lanes_kind(lanes), lanes, gens_family, out, sizes);
 }
 int vdf_nova_shape_export_lanes(uint64_t t, size_t lanes, int side, uint64_t nnz[3], uint32_t* const rows[3], uint32_t* const cols[3],
                                 vdf_fe* const vals[3]) {
-  return nova_guard([&]() -> int {
-    if (t == 0 || t > (1ull << 24) || !nnz || (side != PRIMARY && side != SECONDARY) || !lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "bad argument");
-    HostShape sh[2];
-    build_shapes(t, lanes_kind(lanes), sh, nullptr, nullptr, lanes);
-    const HostShape& h = sh[side];
-    const bool fill = rows && cols && vals;
-    for (int k = 0; k < 3; ++k) {
-      const size_t z = h.m[k].rows.size();
-      if (fill) {
-        if (nnz[k] < z || !rows[k] || !cols[k] || !vals[k]) return fail(VDF_ERR_BAD_LENGTH, "triple arrays too short");
-        memcpy(rows[k], h.m[k].rows.data(), z * 4);
-        memcpy(cols[k], h.m[k].cols.data(), z * 4);
-        memcpy(vals[k], h.m[k].vals.data(), z * 32);
-      }
-      nnz[k] = z;
-    }
-    return VDF_OK;
-  });
+  if (t == 0 || t > (1ull << 24) || !nnz || (side != PRIMARY && side != SECONDARY) || !lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+  return shape_export_impl(VDF_FIELD_FQ, t, lanes_kind(lanes), lanes, side, nnz, rows, cols, vals);
 }
 int vdf_nova_aug_synthesize_lanes(const vdf_nova_ro_params* rop, uint64_t t, size_t lanes, const vdf_nova_aug_inputs* a, const vdf_fe* z0,
                                   const vdf_fe* zi, const vdf_state* results, const vdf_state* inputs, vdf_fe* W, size_t w_cap,
                                   size_t* num_vars, size_t* num_cons, vdf_fe X[2], vdf_fe* z_next) {
-  return nova_guard([&]() -> int {
-    bool bad;
-    const RoInstance* ro = ro_from_abi(rop, &bad);
-    if (bad) return fail(VDF_ERR_BAD_ARG, "unsupported RO parameter block");
-    if (!a || t == 0 || !lanes_valid(lanes) || !z0 || !zi || !results || !inputs) return fail(VDF_ERR_BAD_ARG, "bad argument");
-    vdf_pp tmp;
-    tmp.t = t;
-    tmp.circuit_kind = lanes_kind(lanes);
-    tmp.lanes = lanes;
-    Circuit c;
-    c.t = t;
-    c.result = load_state(&results[0]); c.input = load_state(&inputs[0]);
-    for (size_t l = 0; l < lanes; ++l) { c.lane_result.push_back(load_state(&results[l])); c.lane_input.push_back(load_state(&inputs[l])); }
-    std::unique_ptr<StepCircuit> step = make_primary_circuit(&tmp, &c, false);
-    CS cs(side_field(PRIMARY), false, ro);
-    AugInputs ain = aug_from_abi(PRIMARY, a);
-    ain.z0.assign((const Fe*)z0, (const Fe*)z0 + 3 * lanes);
-    ain.zi.assign((const Fe*)zi, (const Fe*)zi + 3 * lanes);
-    ain.ro = ro;
-    const std::vector<Fe> zn = synthesize_augmented(cs, PRIMARY, ain, *step);
-    if (num_vars) *num_vars = cs.W.size();
-    if (num_cons) *num_cons = cs.rows;
-    if (W) {
-      if (w_cap < cs.W.size()) return fail(VDF_ERR_BAD_LENGTH, "W buffer too small");
-      memcpy(W, cs.W.data(), cs.W.size() * 32);
-    }
-    if (X) memcpy(X, cs.X.data(), 64);
-    if (z_next) memcpy(z_next, zn.data(), zn.size() * 32);
-    return VDF_OK;
-  });
+  if (!a || t == 0 || !lanes_valid(lanes) || !z0 || !zi || !results || !inputs) return fail(VDF_ERR_BAD_ARG, "bad argument");
+  return aug_synthesize_impl(VDF_FIELD_FQ, rop, PRIMARY, t, lanes_kind(lanes), lanes, a, z0, zi, results, inputs, W, w_cap, num_vars, num_cons, X, z_next);
 }
 
 int vdf_nova_synthesis_stats(uint64_t* queued, uint64_t* misses) {
@@ -748,8 +745,30 @@ int vdf_nova_public_params(vdf_ctx* ctx, uint64_t t, vdf_pp** out) {
   });
 }
 
-static int public_params_impl(vdf_ctx* ctx, uint64_t t, int circuit_kind, const vdf_step_circuit* custom, int gens_family,
+static int public_params_impl(vdf_ctx* ctx, int fid, uint64_t t, int circuit_kind, const vdf_step_circuit* custom, int gens_family,
                               const vdf_nova_tuning& tune, vdf_pp** out, const RoInstance* ro = nullptr, size_t lanes = 1);
+
+// the general constructor: either orientation, every built-in kind
+int vdf_nova_public_params_field(vdf_ctx* ctx, int fid, uint64_t t, int circuit_kind, size_t lanes, int gens_family, const vdf_nova_ro_params* rop,
+                                 const vdf_nova_tuning* tuning, vdf_pp** out) {
+  return nova_guard([&]() -> int {
+    bool bad;
+    const RoInstance* ro = ro_from_abi(rop, &bad);
+    if (bad) return fail(VDF_ERR_BAD_ARG, "unsupported RO parameter block (vdf_nova.h: alpha 5, 128 / 250 bits, family 1 widths 2..25)");
+    if (!ctx || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "field must be VDF_FIELD_FP or VDF_FIELD_FQ");
+    if (circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES) {
+      if (!lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_NOVA_MAX_LANES");
+      circuit_kind = lanes_kind(lanes);                                // one lane IS the forward circuit (same kind, same digest)
+    } else {
+      if (!builtin_circuit(circuit_kind)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
+      if (lanes != 1) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 for every kind but VDF_CIRCUIT_MINROOT_FORWARD_LANES");
+    }
+    if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
+    return public_params_impl(ctx, fid, t, circuit_kind, nullptr, gens_family, tuning ? *tuning : default_tuning(), out, ro, lanes);
+  });
+}
+int vdf_nova_pp_field(const vdf_pp* pp) { return pp ? pp->field : -1; }
 
 int vdf_nova_public_params_tuned(vdf_ctx* ctx, uint64_t t, int circuit_kind, int gens_family, const vdf_nova_tuning* tuning, vdf_pp** out) {
   return nova_guard([&]() -> int {
@@ -757,7 +776,7 @@ int vdf_nova_public_params_tuned(vdf_ctx* ctx, uint64_t t, int circuit_kind, int
     if (!builtin_circuit(circuit_kind))
       return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
     if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
-    return public_params_impl(ctx, t, circuit_kind, nullptr, gens_family, tuning ? *tuning : default_tuning(), out);
+    return public_params_impl(ctx, VDF_FIELD_FQ, t, circuit_kind, nullptr, gens_family, tuning ? *tuning : default_tuning(), out);
   });
 }
 int vdf_nova_public_params_ro(vdf_ctx* ctx, uint64_t t, int circuit_kind, int gens_family, const vdf_nova_ro_params* rop,
@@ -770,7 +789,7 @@ int vdf_nova_public_params_ro(vdf_ctx* ctx, uint64_t t, int circuit_kind, int ge
     if (!builtin_circuit(circuit_kind))
       return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
     if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
-    return public_params_impl(ctx, t, circuit_kind, nullptr, gens_family, tuning ? *tuning : default_tuning(), out, ro);
+    return public_params_impl(ctx, VDF_FIELD_FQ, t, circuit_kind, nullptr, gens_family, tuning ? *tuning : default_tuning(), out, ro);
   });
 }
 int vdf_nova_public_params_lanes(vdf_ctx* ctx, uint64_t t, size_t lanes, int gens_family, const vdf_nova_ro_params* rop,
@@ -783,7 +802,7 @@ int vdf_nova_public_params_lanes(vdf_ctx* ctx, uint64_t t, size_t lanes, int gen
     if (!ctx || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
     if (!lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_NOVA_MAX_LANES");
     if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
-    return public_params_impl(ctx, t, VDF_CIRCUIT_MINROOT_FORWARD_LANES, nullptr, gens_family, tuning ? *tuning : default_tuning(), out, ro, lanes);
+    return public_params_impl(ctx, VDF_FIELD_FQ, t, VDF_CIRCUIT_MINROOT_FORWARD_LANES, nullptr, gens_family, tuning ? *tuning : default_tuning(), out, ro, lanes);
   });
 }
 size_t vdf_nova_pp_lanes(const vdf_pp* pp) { return pp ? pp->lanes : 0; }
@@ -798,10 +817,13 @@ int vdf_nova_public_params_ex(vdf_ctx* ctx, uint64_t t, int circuit_kind, int ge
 }
 
 int vdf_nova_public_params_custom(vdf_ctx* ctx, const vdf_step_circuit* primary, int gens_family, vdf_pp** out) {
+  return vdf_nova_public_params_custom_field(ctx, VDF_FIELD_FQ, primary, gens_family, out);
+}
+int vdf_nova_public_params_custom_field(vdf_ctx* ctx, int fid, const vdf_step_circuit* primary, int gens_family, vdf_pp** out) {
   return nova_guard([&]() -> int {
-    if (!ctx || !out || !primary || !primary->synthesize || primary->arity == 0 || primary->arity > 64)
+    if (!ctx || !out || !primary || !primary->synthesize || primary->arity == 0 || primary->arity > 64 || !valid_field(fid))
       return fail(VDF_ERR_BAD_ARG, "bad argument");
-    return public_params_impl(ctx, 0, VDF_CIRCUIT_CUSTOM, primary, gens_family, default_tuning(), out);
+    return public_params_impl(ctx, fid, 0, VDF_CIRCUIT_CUSTOM, primary, gens_family, default_tuning(), out);
   });
 }
 
@@ -951,8 +973,8 @@ static bool forward_stencil_matches(const HostShape& h, const Field& F, uint64_t
 }
 // the stencil code of a built-in circuit whose early rows are [row0, row0 + 3t + 1): 3 / 4 = the inverse forms (variables
 // per round), 5 = the forward circuit; 0 = no match
-static int builtin_stencil(const HostShape& h, int circuit_kind, uint64_t t, size_t S, size_t row0, size_t lanes = 1) {
-  const Field& F = field(side_field(PRIMARY));
+static int builtin_stencil(int fid, const HostShape& h, int circuit_kind, uint64_t t, size_t S, size_t row0, size_t lanes = 1) {
+  const Field& F = field(fid);                                        // the primary circuit's
   if (circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD) return forward_stencil_matches(h, F, t, S, row0, S - 3) ? VDF_STENCIL_FORWARD : 0;
   if (circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES) {           // lane by lane: its own variables, rows and inputs
     const size_t per_lane = 3 * (size_t)t + 1;
@@ -965,7 +987,7 @@ static int builtin_stencil(const HostShape& h, int circuit_kind, uint64_t t, siz
   return minroot_stencil_matches(h, F, t, per, S, row0) ? per : 0;
 }
 
-static int public_params_impl(vdf_ctx* ctx, uint64_t t, int circuit_kind, const vdf_step_circuit* custom, int gens_family,
+static int public_params_impl(vdf_ctx* ctx, int fid, uint64_t t, int circuit_kind, const vdf_step_circuit* custom, int gens_family,
                               const vdf_nova_tuning& tune, vdf_pp** out, const RoInstance* ro, size_t lanes) {
   if (gens_family != VDF_GENS_TRY_AND_INCREMENT && gens_family != VDF_GENS_KNOWN_DLOG && gens_family != VDF_GENS_LABEL_SHAKE)
     return fail(VDF_ERR_BAD_ARG, "unknown generator family");
@@ -980,6 +1002,7 @@ static int public_params_impl(vdf_ctx* ctx, uint64_t t, int circuit_kind, const 
   };
   std::unique_ptr<vdf_pp, void (*)(vdf_pp*)> pp(new vdf_pp(), vdf_nova_pp_free);
   pp->ctx = ctx;
+  pp->field = fid;
   pp->t = t;
   pp->circuit_kind = circuit_kind;
   pp->gens_family = gens_family;
@@ -991,8 +1014,8 @@ static int public_params_impl(vdf_ctx* ctx, uint64_t t, int circuit_kind, const 
   double mark = t_start;
   auto lap = [&](int k) -> int { HIPCALL(ctx, vdf_ctx_sync(ctx)); const double now = now_ms(); ms[k] += now - mark; mark = now; return VDF_OK; };
   HostShape sh[2];
-  { int rc = build_shapes(t, circuit_kind, sh, custom, pp->ro, lanes); if (rc != VDF_OK) return rc; }
-  digest_shapes(t, gens_family, sh, pp->digest, pp->ro);
+  { int rc = build_shapes(fid, t, circuit_kind, sh, custom, pp->ro, lanes); if (rc != VDF_OK) return rc; }
+  digest_shapes(fid, t, gens_family, sh, pp->digest, pp->ro);
   // only the MinRoot rounds are made on the device; a custom circuit's variables all come from the host
   pp->seg_begin = custom ? 0 : sh[PRIMARY].step_begin;
   pp->seg_len = custom ? 0 : sh[PRIMARY].step_end - sh[PRIMARY].step_begin;
@@ -1008,14 +1031,14 @@ static int public_params_impl(vdf_ctx* ctx, uint64_t t, int circuit_kind, const 
     // the built-in circuits' early rows are a fixed stencil over the rounds' variables: compared with the shape triple by triple
     // once, here; from then on their cross term reads no sparse matrix (tuning.stencil = 0: the generic kernel, for A/B runs)
     if (!custom && pp->ahead_rows == lanes * (3 * t + 1) && tune.stencil)
-      pp->stencil_per = builtin_stencil(h, circuit_kind, t, pp->seg_begin, pp->ahead_row, lanes);
+      pp->stencil_per = builtin_stencil(fid, h, circuit_kind, t, pp->seg_begin, pp->ahead_row, lanes);
   }
   ms[0] = now_ms() - mark; mark = now_ms();
   for (int s = 0; s < 2; ++s) {
     Side& sd = pp->s[s];
-    sd.side = s; sd.field = side_field(s); sd.curve = side_curve(s);
+    sd.side = s; sd.field = cycle_field(fid, s); sd.curve = curve_of_scalars(sd.field);
     sd.F = &field(sd.field);
-    sd.Fb = &field(s == PRIMARY ? VDF_FIELD_FP : VDF_FIELD_FQ);
+    sd.Fb = &field(other_field(sd.field));                              // a cycle: the curve's coordinates are the other side's scalars
     sd.ctx = ctx;
     sd.arena = &pp->arena[s];
     sd.num_cons = sh[s].num_cons; sd.num_vars = sh[s].num_vars;
@@ -1177,10 +1200,10 @@ int vdf_nova_pp_early_rows(const vdf_pp* pp, uint64_t* begin, uint64_t* len) {
 }
 int vdf_nova_pp_stencil(const vdf_pp* pp) { return pp ? pp->stencil_per : 0; }
 // host only (no device): what vdf_nova_public_params would find for the built-in step circuit `circuit_kind` at `t`
-static int shape_stencil_impl(uint64_t t, int circuit_kind, size_t lanes, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
+static int shape_stencil_impl(int fid, uint64_t t, int circuit_kind, size_t lanes, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
   return nova_guard([&]() -> int {
     HostShape sh[2];
-    if (build_shapes(t, circuit_kind, sh, nullptr, nullptr, lanes) != VDF_OK) return -VDF_ERR_DEVICE;
+    if (build_shapes(fid, t, circuit_kind, sh, nullptr, nullptr, lanes) != VDF_OK) return -VDF_ERR_DEVICE;
     const HostShape& h = sh[PRIMARY];
     const size_t sb = h.step_begin, sl = h.step_end - h.step_begin;
     size_t b = 0, n = 0;
@@ -1189,16 +1212,20 @@ static int shape_stencil_impl(uint64_t t, int circuit_kind, size_t lanes, uint64
     if (early_begin) *early_begin = b;
     if (early_len) *early_len = n;
     if (seg_begin) *seg_begin = sb;
-    return n == lanes * (3 * t + 1) ? builtin_stencil(h, circuit_kind, t, sb, b, lanes) : 0;
+    return n == lanes * (3 * t + 1) ? builtin_stencil(fid, h, circuit_kind, t, sb, b, lanes) : 0;
   });
 }
 int vdf_nova_shape_stencil(uint64_t t, int circuit_kind, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
   if (t == 0 || t > (1ull << 24) || (!builtin_circuit(circuit_kind))) return -fail(VDF_ERR_BAD_ARG, "bad argument");
-  return shape_stencil_impl(t, circuit_kind, 1, early_begin, early_len, seg_begin);
+  return shape_stencil_impl(VDF_FIELD_FQ, t, circuit_kind, 1, early_begin, early_len, seg_begin);
 }
 int vdf_nova_shape_stencil_lanes(uint64_t t, size_t lanes, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
   if (t == 0 || t > (1ull << 24) || !lanes_valid(lanes)) return -fail(VDF_ERR_BAD_ARG, "bad argument");
-  return shape_stencil_impl(t, lanes_kind(lanes), lanes, early_begin, early_len, seg_begin);
+  return shape_stencil_impl(VDF_FIELD_FQ, t, lanes_kind(lanes), lanes, early_begin, early_len, seg_begin);
+}
+int vdf_nova_shape_stencil_field(int fid, uint64_t t, int circuit_kind, size_t lanes, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
+  if (!valid_field(fid) || t == 0 || t > (1ull << 24) || !resolve_kind(&circuit_kind, lanes)) return -fail(VDF_ERR_BAD_ARG, "bad argument");
+  return shape_stencil_impl(fid, t, circuit_kind, lanes, early_begin, early_len, seg_begin);
 }
 
 // ---- prove_step ----------------------------------------------------------------------------------------
@@ -1529,7 +1556,7 @@ struct StepRun {
         if (rc != VDF_OK) return rc;
       }
       p->tahead_valid = false;
-      early1 = synthesize_augmented_early(PRIMARY, in1, *c1);      // the host's share of the wait: what the circuit can do without T
+      early1 = synthesize_augmented_early(PRIMARY, S1.field, in1, *c1);      // the host's share of the wait: what the circuit can do without T
       { int rc = finalize_l2(p); if (rc != VDF_OK) return rc; }      // waits, collects comm_W2 and comm_T2
       comm_T2 = p->nifs2_T;
       p->nifs2 = vdf_proof::NIFS2_NONE;               // consumed: the fold below uses the scratch vectors up
@@ -1635,7 +1662,7 @@ struct StepRun {
       else in2.U = to_relaxed(p->r[PRIMARY].inst, F1);
       memset(&in2.u_W, 0, sizeof(Aff)); memset(&in2.T, 0, sizeof(Aff));
       for (int j = 0; j < 2; ++j) fe_to_int(l1.X[j], F1, in2.u_X[j]);
-      early2 = synthesize_augmented_early(SECONDARY, in2, c2);
+      early2 = synthesize_augmented_early(SECONDARY, S2.field, in2, c2);
       if (seg_n && !waited_w) HIPCALL(cq, vdf_ctx_sync_mark(cq, MARK_W));
       if (t_ahead) HIPCALL(ct, vdf_ctx_sync_mark(ct, MARK_T));
       HIPCALL(ctx, vdf_ctx_sync(ctx));
@@ -1812,6 +1839,9 @@ static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* ci
   if (!custom && k >= circuits->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
   const Circuit& c = custom ? no_circuit : circuits->v[k];
   if (!custom && c.t != pp->t) return fail(VDF_ERR_BAD_LENGTH, "circuit t differs from the public parameters");
+  if (!custom && circuits->field != pp->field)
+    return fail(VDF_ERR_BAD_ARG, std::string("the circuits are a chain over ") + (circuits->field == VDF_FIELD_FP ? "Fp" : "Fq") + ", the parameters' orientation is " +
+                                     (pp->field == VDF_FIELD_FP ? "Fp" : "Fq") + " (vdf_nova_public_params_field, vdf_nova_circuits_*_field)");
   if (!custom && circuits->forward != forward_kind(pp->circuit_kind))
     return fail(VDF_ERR_BAD_ARG, circuits->forward ? "forward circuits need parameters of VDF_CIRCUIT_MINROOT_FORWARD"
                                                    : "forward parameters need circuits made by vdf_nova_circuits_forward_begin");
@@ -1944,17 +1974,18 @@ int vdf_nova_eval_and_prove(vdf_pp* pp, int mode, const vdf_state* initial_state
       double eval_end = 0, eval_ms = 0;
     } sh;
     const St init = load_state(initial_state);
+    const int fid = pp->field;                     // the evaluator runs the parameters' field
     std::thread evaluator;
     struct Join {                                  // whatever way this call ends, the evaluator is told and waited for
       Shared& sh; std::thread& th;
       ~Join() { { std::lock_guard<std::mutex> lk(sh.mu); sh.stop = true; } sh.cv.notify_all(); if (th.joinable()) th.join(); }
     } join{sh, evaluator};
-    evaluator = std::thread([&sh, init, t, num_steps, mode]() {
+    evaluator = std::thread([&sh, init, t, num_steps, mode, fid]() {
       St state = init;
       const double t_begin = now_ms();
       for (size_t k = 0; k < num_steps; ++k) {
         std::vector<Fe> trace(2 * (t + 1));
-        eval_step(mode, t, &state, trace.data());
+        eval_step(fid, mode, t, &state, trace.data());
         std::unique_lock<std::mutex> lk(sh.mu);
         if (k + 1 == num_steps) { sh.eval_end = now_ms(); sh.eval_ms = sh.eval_end - t_begin; }   // the chain's output exists from here
         sh.cv.wait(lk, [&] { return sh.traces.size() < EVAL_QUEUE || sh.stop; });
@@ -1966,7 +1997,7 @@ int vdf_nova_eval_and_prove(vdf_pp* pp, int mode, const vdf_state* initial_state
     vdf_circuits* cs = nullptr;
     vdf_fe z0[3];
     vdf_proof* p = nullptr;
-    int rc = vdf_nova_circuits_forward_begin(t, initial_state, z0, &cs);
+    int rc = vdf_nova_circuits_forward_begin_field(fid, t, initial_state, z0, &cs);
     size_t pushed = 0, max_backlog = 0;
     for (size_t k = 0; rc == VDF_OK && k < num_steps; ++k) {
       // everything the evaluator has finished goes into the chain (the step after this one then rides in this step's lookahead)

@@ -50,7 +50,7 @@ inline bool valid_mode(int m) { return m >= 0 && m <= 3; }
 // ---- Nova (nova_host.cpp) ---------------------------------------------------------------------------------
 constexpr int NUM_IO = AUG_IO;             // public IO of an augmented circuit
 constexpr uint64_t GENS_SEED = 0x4e6f7661; // "Nova": label of the generator families
-constexpr int PRIMARY = 0, SECONDARY = 1;  // G1 = Pallas / G2 = Vesta, src/nova/proof.rs:26-27
+constexpr int PRIMARY = 0, SECONDARY = 1;  // G1 / G2, src/nova/proof.rs:26-27: Pallas / Vesta when the parameters' field is Fq, Vesta / Pallas when it is Fp
 
 // One side of the cycle: an augmented circuit over F (the scalar field of `curve`), its R1CS shape and the Pedersen
 // generators its witnesses are committed under -- everything the folding, the satisfiability check and the
@@ -101,6 +101,7 @@ struct vdf_pp {
   vdf_ctx* ctx = nullptr;
   uint64_t t = 0;
   int circuit_kind = 0, gens_family = 0;
+  int field = VDF_FIELD_FQ;                // the orientation: the primary circuit's field, the VDF's (s[0].field; s[1] has the other one)
   vdfnova::Side s[2];
   uint8_t digest[32];                      // 250-bit little-endian integer
   Fe params[2];                            // the digest as an element of each side's field
@@ -186,6 +187,7 @@ struct WalkState {
 struct vdf_circuits {
   std::vector<Circuit> v;
   vdf_ctx* ctx = nullptr;
+  int field = VDF_FIELD_FQ;                // the chain's field: its evaluator, its counters, its push checks and its walks run over it
   bool checkpoints = false;                // made by vdf_nova_circuits_from_checkpoints (or grown by vdf_nova_circuits_push_checkpoints)
   // a forward chain (vdf_nova_circuits_forward_begin): circuits in the order of evaluation, appended to while the chain grows;
   // `end` is the state the next pushed step must start from
@@ -260,10 +262,10 @@ int finalize_l2(const vdf_proof* p);      // commits to the last secondary witne
 std::unique_ptr<StepCircuit> make_primary_circuit(const vdf_pp* pp, const Circuit* c, bool device_rounds);
 std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c);
 // ---- the circuits as the drivers of nova_host.cpp reach them (circuits_host.cpp) --------------------------------------------
-inline void eval_step(int mode, uint64_t t, St* state, Fe* trace_xy) {   // t rounds from *state: the trace [2 (t + 1)], *state = the result
+inline void eval_step(int field, int mode, uint64_t t, St* state, Fe* trace_xy) {   // t rounds from *state: the trace [2 (t + 1)], *state = the result
   vdf_state in, res;
   store_state(&in, *state);
-  vdf_minroot_eval(VDF_FIELD_FQ, mode, &in, t, &res, (vdf_fe*)trace_xy);
+  vdf_minroot_eval(field, mode, &in, t, &res, (vdf_fe*)trace_xy);
   *state = load_state(&res);
 }
 inline bool needs_walk(const Circuit& c) { return !c.d_trace && !c.cp.empty(); }   // not resident and has checkpoints

@@ -1219,11 +1219,10 @@ struct AugEarly {
 };
 void aug_early_free(AugEarly* e) { delete e; }
 
-AugEarlyPtr synthesize_augmented_early(int side, const AugInputs& in, const StepCircuit& step) {
+AugEarlyPtr synthesize_augmented_early(int side, int fid, const AugInputs& in, const StepCircuit& step) {
   static const bool trace = [] { const char* e = env_override("VDF_NOVA_SYNTH_TRACE"); return e && e[0] == '1'; }();
   const auto T0 = std::chrono::steady_clock::now();
   AugEarlyPtr e(new AugEarly(), aug_early_free);
-  const int fid = side_field(side);
   const Field& F = field(fid);
   e->side = side; e->fid = fid; e->a = step.arity();
   e->in = in;
@@ -1278,7 +1277,7 @@ AugEarlyPtr synthesize_augmented_early(int side, const AugInputs& in, const Step
 static std::vector<Fe> synthesize_augmented_blocks(CS& cs, int side, const AugInputs& in, const StepCircuit& step, Fe* unew_out,
                                                    uint64_t* r_out, AugEarly* early) {
   const Field& F = cs.F;
-  const Field& PF = field(side_field(1 - side));
+  const Field& PF = field(other_field(cs.field_id));
   const int fid = cs.field_id;
   const size_t a = step.arity();
   const Fe ONE = one(F), ZERO = vdfhost::zero();
@@ -1287,9 +1286,9 @@ static std::vector<Fe> synthesize_augmented_blocks(CS& cs, int side, const AugIn
   auto us = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - T0).count(); };
   double tr[8] = {0};
   AugEarlyPtr own(nullptr, aug_early_free);
-  if (!early) { own = synthesize_augmented_early(side, in, step); early = own.get(); }
+  if (!early) { own = synthesize_augmented_early(side, cs.field_id, in, step); early = own.get(); }
   AugEarly& e = *early;
-  if (e.side != side || e.a != a || e.in.ro != in.ro || e.in.params != in.params || e.in.i != in.i || e.in.z0 != in.z0 || e.in.zi != in.zi ||
+  if (e.side != side || e.fid != fid || e.a != a || e.in.ro != in.ro || e.in.params != in.params || e.in.i != in.i || e.in.z0 != in.z0 || e.in.zi != in.zi ||
       memcmp(&e.in.U, &in.U, sizeof(RelaxedInst)) != 0 || memcmp(e.in.u_X, in.u_X, sizeof(in.u_X)) != 0)
     throw std::runtime_error("synthesize_augmented: the early half was made for other inputs");
   const Fe* ue = e.ue;
@@ -1442,7 +1441,7 @@ std::vector<Fe> synthesize_augmented(CS& cs, int side, const AugInputs& in, cons
   if (cs.ro != (in.ro ? in.ro : ro_default())) throw std::runtime_error("synthesize_augmented: the constraint system and the inputs name different RO parameter blocks");
   if (!cs.shape && !sequential) return synthesize_augmented_blocks(cs, side, in, step, unew_out, r_out, early);
   const Field& F = cs.F;
-  const Field& PF = field(side_field(1 - side));
+  const Field& PF = field(other_field(cs.field_id));
   const size_t a = step.arity();
   const Num one_n = cs.constant(one(F));
   const Num params = cs.alloc(in.params);

@@ -235,7 +235,8 @@ Fe hash_state(int field_id, const Fe& params, const Fe& i, const std::vector<Fe>
               const RelaxedInst& U, uint64_t out_int[4], const RoInstance* ro = nullptr);
 void hash_challenge(int field_id, const Fe& params, const RelaxedInst& U, const Aff& u_W, const uint64_t u_X[2][4], const Aff& T,
                     uint64_t r_out[4], const RoInstance* ro = nullptr);
-// side 0 = primary (circuit over Fq, folds Vesta instances), side 1 = secondary; returns z_{i+1}
+// side 0 = primary (the VDF's field; Fq in the reference's orientation, folding Vesta instances), side 1 = secondary; the
+// circuit's field is cs.field_id (field_id for the early half), the folded side's is the other one of the cycle; returns z_{i+1}
 // unew (optional): the nine elements of the running instance the circuit hands on (the folded one, or the base case's);
 // r (optional): the fold challenge it derived, a 128-bit integer
 // Witness mode, in two halves.  Everything that does not depend on the two commitments a step is waiting for (u.comm_W
@@ -246,14 +247,20 @@ void hash_challenge(int field_id, const Fe& params, const RelaxedInst& U, const 
 struct AugEarly;
 void aug_early_free(AugEarly* e);
 typedef std::unique_ptr<AugEarly, void (*)(AugEarly*)> AugEarlyPtr;
-AugEarlyPtr synthesize_augmented_early(int side, const AugInputs& in, const StepCircuit& step);
+AugEarlyPtr synthesize_augmented_early(int side, int field_id, const AugInputs& in, const StepCircuit& step);
 std::vector<Fe> synthesize_augmented(CS& cs, int side, const AugInputs& in, const StepCircuit& step, Fe* unew = nullptr,
                                      uint64_t* r = nullptr, AugEarly* early = nullptr);
 // of the calling thread's last synthesize_augmented in witness mode: slope inverses queued by the pre-pass, and how many of
 // them were wrong or left over (0 unless the inputs were malformed)
 void last_synthesis_stats(uint64_t* queued, uint64_t* misses);
-inline int side_field(int side) { return side == 0 ? VDF_FIELD_FQ : VDF_FIELD_FP; }
-inline int side_curve(int side) { return side == 0 ? VDF_CURVE_PALLAS : VDF_CURVE_VESTA; }
+// The cycle in either orientation.  An orientation is the field of the PRIMARY circuit (the VDF's field): VDF_FIELD_FQ makes
+// G1 = Pallas / G2 = Vesta (src/nova/proof.rs:26-27), VDF_FIELD_FP the reverse.  No function answers "which field is side s"
+// without being told the orientation: it lives in the parameter set and reaches every use through a Side, a CS (whose field is
+// the circuit's) or an explicit argument.
+inline int other_field(int f) { return f == VDF_FIELD_FQ ? VDF_FIELD_FP : VDF_FIELD_FQ; }
+inline int cycle_field(int primary_field, int side) { return side == 0 ? primary_field : other_field(primary_field); }
+// the curve whose scalar field is f: instances of a circuit over f are committed on it
+inline int curve_of_scalars(int f) { return f == VDF_FIELD_FQ ? VDF_CURVE_PALLAS : VDF_CURVE_VESTA; }
 
 // 256-bit helpers on canonical little-endian limbs
 inline void fe_to_int(const Fe& mont, const Field& F, uint64_t out[4]) { const Fe c = from_mont(mont, F); memcpy(out, c.l, 32); }

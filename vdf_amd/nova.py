@@ -11,7 +11,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from .hip import Context, VdfError
-from .minroot import State, _State, _Fe, nova_lib, EvalMode, MinRootVDF, PallasVDF  # noqa: F401
+from .minroot import State, _State, _Fe, nova_lib, EvalMode, MinRootVDF, PallasVDF, VestaVDF, FIELD_FP, FIELD_FQ  # noqa: F401
 
 _vp, _i, _u64, _sz = C.c_void_p, C.c_int, C.c_uint64, C.c_size_t
 for _name, _res, _args in [
@@ -110,6 +110,19 @@ for _name, _res, _args in [
     ("vdf_nova_proof_serialized_size", _sz, [_vp]),
     ("vdf_nova_proof_serialize", _i, [_vp, _vp, _sz]),
     ("vdf_nova_proof_deserialize", _i, [_vp, _vp, _sz, C.POINTER(_vp)]),
+    # the cycle in either orientation (field = the primary circuit's field, the VDF's)
+    ("vdf_nova_public_params_field", _i, [_vp, _i, _u64, _i, _sz, _i, _vp, _vp, C.POINTER(_vp)]),
+    ("vdf_nova_public_params_custom_field", _i, [_vp, _i, _vp, _i, C.POINTER(_vp)]),
+    ("vdf_nova_pp_field", _i, [_vp]),
+    ("vdf_nova_eval_and_make_circuits_field", _i, [_i, _i, _u64, _sz, C.POINTER(_State), C.POINTER(_Fe * 3), C.POINTER(_vp)]),
+    ("vdf_nova_circuits_from_checkpoints_field", _i, [_i, _u64, _u64, _sz, _vp, C.POINTER(_Fe * 3), C.POINTER(_vp)]),
+    ("vdf_nova_circuits_forward_begin_field", _i, [_i, _u64, C.POINTER(_State), C.POINTER(_Fe * 3), C.POINTER(_vp)]),
+    ("vdf_nova_circuits_lanes_begin_field", _i, [_i, _u64, _sz, _vp, _vp, C.POINTER(_vp)]),
+    ("vdf_nova_circuits_field", _i, [_vp]),
+    ("vdf_nova_shape_digest_field", _i, [_i, _vp, _u64, _i, _sz, _i, _vp, _vp]),
+    ("vdf_nova_shape_export_field", _i, [_i, _u64, _i, _sz, _i, _vp, _vp, _vp, _vp]),
+    ("vdf_nova_shape_stencil_field", _i, [_i, _u64, _i, _sz, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    ("vdf_nova_aug_synthesize_field", _i, [_i, _vp, _i, _u64, _i, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz), _vp, _vp]),
 ]:
     if not hasattr(nova_lib, _name):          # AttributeError at call time names the missing entry point
         continue
@@ -235,6 +248,51 @@ def shape_export(t: int, circuit_kind: int = 1, side: int = 0):
     return mats
 
 
+# ---- the host-only entry points in either orientation: one general form each (kind FORWARD_LANES with `lanes`; 1 otherwise) ----
+def shape_digest_field(field: int, t: int, circuit_kind: int = 1, lanes: int = 1, gens_family: int = 1, ro: "RoParams | None" = None):
+    """shape_digest for the orientation `field` (FIELD_FQ: PallasVDF, FIELD_FP: VestaVDF): (digest, sizes[side])."""
+    d = (C.c_uint8 * 32)()
+    sizes = np.zeros((2, 3), dtype="<u8")
+    _check(nova_lib.vdf_nova_shape_digest_field(field, _ro_ptr(ro), t, circuit_kind, lanes, gens_family, d, sizes.ctypes.data))
+    return int.from_bytes(bytes(d), "little"), sizes.tolist()
+
+
+def shape_stencil_field(field: int, t: int, circuit_kind: int = 1, lanes: int = 1):
+    """shape_stencil for the orientation `field`: (code 5 / 6 / 4 / 3 or 0; first early row; early rows; first round variable)."""
+    b, n, s_ = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    code = nova_lib.vdf_nova_shape_stencil_field(field, t, circuit_kind, lanes, C.byref(b), C.byref(n), C.byref(s_))
+    if code < 0:
+        _check(-code)
+    return code, b.value, n.value, s_.value
+
+
+def shape_export_field(field: int, t: int, circuit_kind: int = 1, lanes: int = 1, side: int = 0):
+    """shape_export for the orientation `field`; values in Montgomery form of the side's own scalar field."""
+    nnz = np.zeros(3, dtype="<u8")
+    _check(nova_lib.vdf_nova_shape_export_field(field, t, circuit_kind, lanes, side, nnz.ctypes.data, None, None, None))
+    mats = [(np.zeros(int(z), dtype=np.uint32), np.zeros(int(z), dtype=np.uint32), np.zeros((int(z), 4), dtype="<u8")) for z in nnz]
+    arr = lambda k: (C.c_void_p * 3)(*[m[k].ctypes.data for m in mats])
+    _check(nova_lib.vdf_nova_shape_export_field(field, t, circuit_kind, lanes, side, nnz.ctypes.data, arr(0), arr(1), arr(2)))
+    return mats
+
+
+def aug_synthesize_field(field: int, side: int, t: int, circuit_kind: int, inputs: "AugInputs", results: Sequence[State] = (),
+                         inps: Sequence[State] = (), z0: "Sequence[bytes] | None" = None, zi: "Sequence[bytes] | None" = None,
+                         lanes: int = 1, cap: int = 1 << 16, ro=None):
+    """One augmented circuit of the orientation `field` synthesised on the host: (W, X, z_next, num_cons).  Side 0: results /
+    inps hold one State per lane, z0 / zi (3 * lanes elements) replace those of `inputs` when given."""
+    W = np.zeros((cap, 4), dtype="<u8")
+    n_out = 3 * lanes if side == 0 else 1
+    X, zn = np.zeros((2, 4), dtype="<u8"), np.zeros((max(n_out, 3), 4), dtype="<u8")
+    nv, nc = C.c_size_t(), C.c_size_t()
+    res = b"".join(s.x + s.y + s.i for s in results) or None
+    inp = b"".join(s.x + s.y + s.i for s in inps) or None
+    _check(nova_lib.vdf_nova_aug_synthesize_field(field, _ro_ptr(ro), side, t, circuit_kind, lanes, C.addressof(inputs),
+                                                  _zn(z0) if z0 is not None else None, _zn(zi) if zi is not None else None, res, inp,
+                                                  W.ctypes.data, cap, C.byref(nv), C.byref(nc), X.ctypes.data, zn.ctypes.data))
+    return W[:nv.value].copy(), X, zn[:n_out].copy(), nc.value
+
+
 # ---- the step-circuit seam (include/vdf_nova.h vdf_step_circuit; src/nova/proof.rs:79-153) ---------------------------
 _SYNTH = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
 
@@ -245,7 +303,7 @@ class _StepCircuitC(C.Structure):
 
 class ConstraintSystem:
     """The vdf_cs a step circuit's synthesize receives: numbers are opaque handles; field elements cross as 32-byte
-    Montgomery limbs (Fq: the primary circuit's field)."""
+    Montgomery limbs of the primary circuit's field (Fq, or Fp under public_params_custom(..., field=FIELD_FP))."""
 
     def __init__(self, handle):
         self.h = handle
@@ -321,9 +379,14 @@ def _reraise(circuit) -> None:
         raise e
 
 
-def public_params_custom(ctx: Context, circuit: StepCircuit, gens_family: int = GENS_TRY_AND_INCREMENT) -> "NovaVDFPublicParams":
+def public_params_custom(ctx: Context, circuit: StepCircuit, gens_family: int = GENS_TRY_AND_INCREMENT,
+                         field: int = FIELD_FQ) -> "NovaVDFPublicParams":
+    """`field`: the orientation -- the field the circuit is synthesised over (FIELD_FP: G1 = Vesta)."""
     h = C.c_void_p()
-    rc = nova_lib.vdf_nova_public_params_custom(ctx.handle, C.byref(circuit._c()), gens_family, C.byref(h))
+    if field == FIELD_FQ:
+        rc = nova_lib.vdf_nova_public_params_custom(ctx.handle, C.byref(circuit._c()), gens_family, C.byref(h))
+    else:
+        rc = nova_lib.vdf_nova_public_params_custom_field(ctx.handle, field, C.byref(circuit._c()), gens_family, C.byref(h))
     _reraise(circuit)
     _check(rc)
     pp = NovaVDFPublicParams(ctx, h.value, 0)
@@ -398,6 +461,10 @@ class NovaVDFPublicParams:        # src/nova/proof.rs:38-43
         6: as the forward circuit's in lanes, 0: through the sparse kernel."""
         return int(nova_lib.vdf_nova_pp_stencil(self.handle))
 
+    def field(self) -> int:
+        """The orientation: the primary circuit's field, the VDF's -- FIELD_FQ (PallasVDF, G1 = Pallas) or FIELD_FP (VestaVDF, G1 = Vesta)."""
+        return int(nova_lib.vdf_nova_pp_field(self.handle))
+
     def lanes(self) -> int:
         """evaluations a step advances: 1 for every kind but CIRCUIT_MINROOT_FORWARD_LANES"""
         return int(nova_lib.vdf_nova_pp_lanes(self.handle))
@@ -443,11 +510,21 @@ class NovaVDFPublicParams:        # src/nova/proof.rs:38-43
 
 def public_params(ctx: Context, num_iters_per_step: int, circuit_kind: int = CIRCUIT_MINROOT_REFERENCE,
                   gens_family: int = GENS_TRY_AND_INCREMENT, flags: int = 0, tuning: "NovaTuning | None" = None,
-                  ro: "RoParams | None" = None, **tune) -> NovaVDFPublicParams:      # :232-237
+                  ro: "RoParams | None" = None, field: int = FIELD_FQ, **tune) -> NovaVDFPublicParams:      # :232-237
     """`tuning` / keyword fields of vdf_nova_tuning (e.g. digit_window=12, early_rows=0): vdf_nova_public_params_tuned;
-    `ro`: the random oracle's parameter block (ro_preset): vdf_nova_public_params_ro."""
+    `ro`: the random oracle's parameter block (ro_preset): vdf_nova_public_params_ro; `field`: the orientation, the field of
+    the chains these parameters prove (FIELD_FQ: PallasVDF, the default; FIELD_FP: VestaVDF): vdf_nova_public_params_field."""
     h = C.c_void_p()
-    if ro is not None:
+    if field != FIELD_FQ:
+        t = tuning if tuning is not None else tuning_default()
+        for k, v in tune.items():
+            if k not in dict(NovaTuning._fields_):
+                raise KeyError(k)
+            setattr(t, k, int(v))
+        t.flags |= flags
+        _check(nova_lib.vdf_nova_public_params_field(ctx.handle, field, num_iters_per_step, circuit_kind, 1, gens_family, _ro_ptr(ro),
+                                                     C.byref(t), C.byref(h)))
+    elif ro is not None:
         t = tuning if tuning is not None else tuning_default()
         for k, v in tune.items():
             if k not in dict(NovaTuning._fields_):
@@ -471,9 +548,10 @@ def public_params(ctx: Context, num_iters_per_step: int, circuit_kind: int = CIR
 
 
 def public_params_lanes(ctx: Context, num_iters_per_step: int, lanes: int, gens_family: int = GENS_TRY_AND_INCREMENT, flags: int = 0,
-                        tuning: "NovaTuning | None" = None, ro: "RoParams | None" = None, **tune) -> NovaVDFPublicParams:
+                        tuning: "NovaTuning | None" = None, ro: "RoParams | None" = None, field: int = FIELD_FQ, **tune) -> NovaVDFPublicParams:
     """Parameters of the forward circuit in `lanes` lanes (vdf_nova_public_params_lanes); lanes = 1 gives exactly
-    public_params(ctx, t, CIRCUIT_MINROOT_FORWARD).  z0 and zi of proofs under them have 3 * lanes elements."""
+    public_params(ctx, t, CIRCUIT_MINROOT_FORWARD).  z0 and zi of proofs under them have 3 * lanes elements.  `field`: the
+    orientation (public_params)."""
     h = C.c_void_p()
     t = tuning if tuning is not None else tuning_default()
     for k, v in tune.items():
@@ -481,7 +559,11 @@ def public_params_lanes(ctx: Context, num_iters_per_step: int, lanes: int, gens_
             raise KeyError(k)
         setattr(t, k, int(v))
     t.flags |= flags
-    _check(nova_lib.vdf_nova_public_params_lanes(ctx.handle, num_iters_per_step, lanes, gens_family, _ro_ptr(ro), C.byref(t), C.byref(h)))
+    if field == FIELD_FQ:
+        _check(nova_lib.vdf_nova_public_params_lanes(ctx.handle, num_iters_per_step, lanes, gens_family, _ro_ptr(ro), C.byref(t), C.byref(h)))
+    else:
+        _check(nova_lib.vdf_nova_public_params_field(ctx.handle, field, num_iters_per_step, CIRCUIT_MINROOT_FORWARD_LANES, lanes, gens_family,
+                                                     _ro_ptr(ro), C.byref(t), C.byref(h)))
     pp = NovaVDFPublicParams(ctx, h.value, num_iters_per_step)
     pp.circuit_kind = CIRCUIT_MINROOT_FORWARD if lanes == 1 else CIRCUIT_MINROOT_FORWARD_LANES
     pp.arity = 3 * lanes
@@ -539,6 +621,10 @@ class Circuits:
 
     def __len__(self) -> int:
         return nova_lib.vdf_nova_circuits_len(self.handle)
+
+    def field(self) -> int:
+        """the chain's field (FIELD_FQ / FIELD_FP): what its evaluator, counters, push checks and walks run over"""
+        return int(nova_lib.vdf_nova_circuits_field(self.handle))
 
     def upload(self, ctx: Context) -> None:
         """Move the forward traces into HBM (an input of proving; outside the timed region)."""
@@ -609,12 +695,16 @@ class InverseMinRootCircuit:      # src/nova/proof.rs:57-66, :239-299
             raise AssertionError("num_steps > 0")                                       # :268
         z0 = (_Fe * 3)()
         h = C.c_void_p()
-        _check(nova_lib.vdf_nova_eval_and_make_circuits(int(v.eval_mode), num_iters_per_step, num_steps,
-                                                        C.byref(initial_state._c()), C.byref(z0), C.byref(h)))
+        if v.FIELD == FIELD_FQ:
+            _check(nova_lib.vdf_nova_eval_and_make_circuits(int(v.eval_mode), num_iters_per_step, num_steps,
+                                                            C.byref(initial_state._c()), C.byref(z0), C.byref(h)))
+        else:                                                                           # the field comes from v: VestaVDF gives Fp
+            _check(nova_lib.vdf_nova_eval_and_make_circuits_field(v.FIELD, int(v.eval_mode), num_iters_per_step, num_steps,
+                                                                  C.byref(initial_state._c()), C.byref(z0), C.byref(h)))
         return [bytes(z0[k]) for k in range(3)], Circuits(h.value, num_iters_per_step)
 
     @staticmethod
-    def from_checkpoints(t: int, every: int, num_steps: int, states: Sequence[State]) -> Tuple[List[bytes], Circuits]:
+    def from_checkpoints(t: int, every: int, num_steps: int, states: Sequence[State], field: int = FIELD_FQ) -> Tuple[List[bytes], Circuits]:
         """The circuits of a chain evaluated elsewhere, from its states every `every` rounds in forward order
         (num_steps * (t // every) + 1 of them, e.g. MinRootVDF.eval_checkpoints): no trace is held; Circuits.materialize, or
         prove_recursively by itself, rebuilds the traces on the GPU window by window."""
@@ -624,7 +714,10 @@ class InverseMinRootCircuit:      # src/nova/proof.rs:57-66, :239-299
         buf = (C.c_char * max(len(raw), 1)).from_buffer_copy(raw or b"\0")
         z0 = (_Fe * 3)()
         h = C.c_void_p()
-        _check(nova_lib.vdf_nova_circuits_from_checkpoints(t, every, num_steps, buf, C.byref(z0), C.byref(h)))
+        if field == FIELD_FQ:
+            _check(nova_lib.vdf_nova_circuits_from_checkpoints(t, every, num_steps, buf, C.byref(z0), C.byref(h)))
+        else:
+            _check(nova_lib.vdf_nova_circuits_from_checkpoints_field(field, t, every, num_steps, buf, C.byref(z0), C.byref(h)))
         return [bytes(z0[k]) for k in range(3)], Circuits(h.value, t)
 
 
@@ -633,11 +726,14 @@ class ForwardCircuits(Circuits):
     k-th step pushed.  Push and release between prove_steps, never during one (include/vdf_nova.h)."""
 
     @staticmethod
-    def begin(t: int, initial_state: State) -> Tuple[List[bytes], "ForwardCircuits"]:
-        """(z0 = the initial state, an empty chain)"""
+    def begin(t: int, initial_state: State, field: int = FIELD_FQ) -> Tuple[List[bytes], "ForwardCircuits"]:
+        """(z0 = the initial state, an empty chain); `field`: the chain's field"""
         z0 = (_Fe * 3)()
         h = C.c_void_p()
-        _check(nova_lib.vdf_nova_circuits_forward_begin(t, C.byref(initial_state._c()), C.byref(z0), C.byref(h)))
+        if field == FIELD_FQ:
+            _check(nova_lib.vdf_nova_circuits_forward_begin(t, C.byref(initial_state._c()), C.byref(z0), C.byref(h)))
+        else:
+            _check(nova_lib.vdf_nova_circuits_forward_begin_field(field, t, C.byref(initial_state._c()), C.byref(z0), C.byref(h)))
         return [bytes(z0[k]) for k in range(3)], ForwardCircuits(h.value, t)
 
     def push_trace(self, trace_xy: np.ndarray) -> None:
@@ -661,13 +757,16 @@ class LaneCircuits(Circuits):
     is a forward chain.  Push and release between prove_steps, never during one (include/vdf_nova.h)."""
 
     @staticmethod
-    def begin(t: int, initials: Sequence[State]) -> Tuple[List[bytes], "LaneCircuits"]:
-        """(z0 = the lanes' initial states flattened, an empty chain)"""
+    def begin(t: int, initials: Sequence[State], field: int = FIELD_FQ) -> Tuple[List[bytes], "LaneCircuits"]:
+        """(z0 = the lanes' initial states flattened, an empty chain); `field`: the chains' field"""
         L = len(initials)
         z0 = (_Fe * (3 * max(L, 1)))()
         raw = b"".join(s.x + s.y + s.i for s in initials) or bytes(96)
         h = C.c_void_p()
-        _check(nova_lib.vdf_nova_circuits_lanes_begin(t, L, raw, z0, C.byref(h)))
+        if field == FIELD_FQ:
+            _check(nova_lib.vdf_nova_circuits_lanes_begin(t, L, raw, z0, C.byref(h)))
+        else:
+            _check(nova_lib.vdf_nova_circuits_lanes_begin_field(field, t, L, raw, z0, C.byref(h)))
         c = LaneCircuits(h.value, t)
         c.lanes = L
         return [bytes(z0[k]) for k in range(3 * L)], c
@@ -733,7 +832,10 @@ class NovaVDFProof:               # enum NovaVDFProof { Recursive, Compressed },
     @staticmethod
     def eval_and_prove(pp: NovaVDFPublicParams, v: MinRootVDF, initial_state: State, num_steps: int) -> Tuple["NovaVDFProof", State, dict]:
         """Evaluates num_steps steps from initial_state on a library thread and proves every step as it arrives (forward
-        parameters): (the running proof of z0 = initial, zi = final; the final state; vdf_nova_stream_stats as a dict)."""
+        parameters): (the running proof of z0 = initial, zi = final; the final state; vdf_nova_stream_stats as a dict).  The
+        evaluator runs the parameters' field, which must be v's (VestaVDF needs public_params(..., field=FIELD_FP))."""
+        if nova_lib.vdf_nova_pp_field(pp.handle) != v.FIELD:
+            raise VdfError(1, "the parameters' orientation is not the field of this VDF (public_params(..., field=...))")
         h = C.c_void_p()
         fin, st = _State(), StreamStats()
         _check(nova_lib.vdf_nova_eval_and_prove(pp.handle, int(v.eval_mode), C.byref(initial_state._c()), num_steps, C.byref(fin),
