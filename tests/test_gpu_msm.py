@@ -819,7 +819,7 @@ def test_lazy_addition_chains_stay_inside_their_bound():
     operations, short chains step by step, and 10,240-long chains per lane -- with cancellations to the identity every 997
     additions and further additions behind them -- in which every stored coordinate must stay below 2m + 2^130 (the proven
     bound is 2m + 9 eps, eps ~ 2^125) and the resolved sum must equal the canonical one.  tools/ubench/madd_check.hip, run as
-    a child process (built by vdf_amd/csrc/Makefile)."""
+    a child process (built by vdf_amd/csrc/Makefile), for Fp and then for Fq."""
     import subprocess
     exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "ubench", "madd_check")
     assert os.path.exists(exe), "make -C vdf_amd/csrc"
@@ -827,6 +827,10 @@ def test_lazy_addition_chains_stay_inside_their_bound():
     assert r.returncode == 0, r.stdout + r.stderr
     assert "coordinates above 2m + 2^130: 0, mismatches 0" in r.stdout, r.stdout
     assert "bit for bit (524288 values): mismatches 0" in r.stdout, r.stdout           # fe_sqr_lazy (the additions' two squarings)
+    # the same kernels instantiated for Fq (the Vesta base field): their lines carry a prefix
+    assert "Fq: long chains" in r.stdout and "Fq: fe_mul2_lazy mismatches 0, fe_neg_lazy mismatches 0, chain mismatches 0 " in r.stdout, r.stdout
+    assert r.stdout.count("coordinates above 2m + 2^130: 0, mismatches 0") == 2, r.stdout
+    assert "Fq: fe_sqr_lazy vs fe_mul_lazy(a, a), bit for bit (524288 values): mismatches 0" in r.stdout, r.stdout
 
 
 @pytest.mark.parametrize("curve", CURVES)

@@ -1,5 +1,6 @@
 // Diagnostic (not product code): the bucket loop's sign-tracked mixed addition (ec.cuh xyzz_madd_lazy, fe_mul2_lazy,
-// fe_neg_lazy) against the plain canonical formulas, lane by lane, on random points.
+// fe_neg_lazy) against the plain canonical formulas, lane by lane, on random points -- in both fields: every kernel is a template
+// over the field, run for Fp (Pallas) and then for Fq (Vesta; its lines carry the prefix "Fq: ").  (-1, 2) is on both curves.
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -I vdf_amd/csrc tools/ubench/madd_check.hip -o tools/ubench/madd_check
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -10,16 +11,14 @@
 #include "ec.cuh"
 using namespace vdf;
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); return 1; } } while (0)
-typedef FpParams P;
-
-__device__ Fe<P> rnd_fe(uint32_t& s) {
+template <class P> __device__ Fe<P> rnd_fe(uint32_t& s) {
   Fe<P> r;
   for (int i = 0; i < 8; ++i) { s = s * 1664525u + 1013904223u; r.v[i] = s ^ (s >> 13); }
   r.v[7] &= 0x3fffffffu;
   return r;
 }
 // a point on y^2 = x^3 + 5 from a seed: [k] G by double-and-add with the canonical formulas
-__device__ Affine<P> rnd_pt(uint32_t& s) {
+template <class P> __device__ Affine<P> rnd_pt(uint32_t& s) {
   Affine<P> g; g.x = fe_neg(fe_one<P>()); g.y = fe_from_u64<P>(2);
   s = s * 1664525u + 1013904223u;
   return xyzz_to_affine(xyzz_mul_u64(g, ((uint64_t)s << 20) | 12345u));
@@ -28,7 +27,7 @@ __device__ Affine<P> rnd_pt(uint32_t& s) {
 // (0) fe_sqr_lazy against fe_mul_lazy(a, a), BIT FOR BIT (before any canonicalisation: both compute (a^2 + q m) / 2^256), over
 // all of [0, 2^256): random words, values around 2^255 and 2^256 - 1 (the doubled number's ninth limb), words of all ones / top
 // bits only (every a_j >> 31 carry into the next limb of 2a), small values.
-__global__ void k_sqr(uint32_t* bad) {
+template <class P> __global__ void k_sqr(uint32_t* bad) {
   uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) * 2654435761u + 71u;
   for (int it = 0; it < 512; ++it) {
     Fe<P> a;
@@ -50,11 +49,11 @@ __global__ void k_sqr(uint32_t* bad) {
   }
 }
 
-__global__ void k_check(uint32_t* bad, int steps) {
+template <class P> __global__ void k_check(uint32_t* bad, int steps) {
   uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) * 2654435761u + 17u;
   // (1) fe_mul2_lazy vs two products and an addition
   for (int it = 0; it < 64; ++it) {
-    Fe<P> a = rnd_fe(s), b = rnd_fe(s), c = rnd_fe(s), d = rnd_fe(s);
+    Fe<P> a = rnd_fe<P>(s), b = rnd_fe<P>(s), c = rnd_fe<P>(s), d = rnd_fe<P>(s);
     Fe<P> want = fe_add(fe_mul_inl(a, b), fe_mul_inl(c, d));
     Fe<P> got = fe_canon(fe_mul2_lazy(a, b, c, d));
     if (!fe_eq(want, got)) atomicAdd(&bad[0], 1u);
@@ -66,7 +65,7 @@ __global__ void k_check(uint32_t* bad, int steps) {
   XYZZ<P> acc = xyzz_identity<P>();
   bool have = false, flip = false;
   for (int k = 0; k < steps; ++k) {
-    Affine<P> pt = rnd_pt(s);
+    Affine<P> pt = rnd_pt<P>(s);
     s = s * 1664525u + 1013904223u;
     const bool neg = (s >> 9) & 1u;
     Affine<P> t = pt;
@@ -83,7 +82,7 @@ __global__ void k_check(uint32_t* bad, int steps) {
 }
 
 // value < 2m + 2^130 (2^130 ~ 29 eps; the proven bound is 2m + 9 eps)?  t = a - 2m: a borrow means a < 2m; otherwise t < 2^130.
-__device__ bool below_bound(const Fe<P>& a) {
+template <class P> __device__ bool below_bound(const Fe<P>& a) {
   constexpr uint64_t D1 = 2ull * P::MOD[1], D2 = 2ull * P::MOD[2] + (D1 >> 32), D3 = 2ull * P::MOD[3] + (D2 >> 32);
   const uint32_t T[8] = {2u, (uint32_t)D1, (uint32_t)D2, (uint32_t)D3, (uint32_t)(D3 >> 32), 0u, 0u, 0x80000000u};
   uint32_t t[8];
@@ -101,7 +100,7 @@ __device__ bool below_bound(const Fe<P>& a) {
 // partial sums do not repeat -- and every `cancel_every` additions the negated running sum is added (cancel to the identity:
 // `have` drops, the next point restarts the accumulator with `flip` whatever it was).  After EVERY addition each stored
 // coordinate must be below 2m + 2^130 and the resolved point must equal the canonical reference.
-__global__ void k_long(uint32_t* bad, int steps, int cancel_every) {
+template <class P> __global__ void k_long(uint32_t* bad, int steps, int cancel_every) {
   uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) * 2246822519u + 99u;
   Affine<P> g; g.x = fe_neg(fe_one<P>()); g.y = fe_from_u64<P>(2);
   s = s * 1664525u + 1013904223u;
@@ -140,22 +139,29 @@ __global__ void k_long(uint32_t* bad, int steps, int cancel_every) {
   }
 }
 
-int main(int argc, char** argv) {
-  const int long_steps = argc > 1 ? atoi(argv[1]) : 10240;
+template <class P> int run(const char* tag, int long_steps) {
   uint32_t* d; CK(hipMalloc(&d, 64)); CK(hipMemset(d, 0, 64));
-  hipLaunchKernelGGL(k_sqr, dim3(16), dim3(64), 0, 0, d);
-  hipLaunchKernelGGL(k_check, dim3(8), dim3(64), 0, 0, d, 24);
+  hipLaunchKernelGGL(k_sqr<P>, dim3(16), dim3(64), 0, 0, d);
+  hipLaunchKernelGGL(k_check<P>, dim3(8), dim3(64), 0, 0, d, 24);
   CK(hipDeviceSynchronize());
   uint32_t h[16]; CK(hipMemcpy(h, d, 64, hipMemcpyDeviceToHost));
-  printf("fe_sqr_lazy vs fe_mul_lazy(a, a), bit for bit (524288 values): mismatches %u\n", h[15]);
-  printf("fe_mul2_lazy mismatches %u, fe_neg_lazy mismatches %u, chain mismatches %u (first steps:", h[0], h[1], h[2]);
+  printf("%sfe_sqr_lazy vs fe_mul_lazy(a, a), bit for bit (524288 values): mismatches %u\n", tag, h[15]);
+  printf("%sfe_mul2_lazy mismatches %u, fe_neg_lazy mismatches %u, chain mismatches %u (first steps:", tag, h[0], h[1], h[2]);
   for (int k = 0; k < 8; ++k) printf(" %u", h[3 + k]);
   printf(")\n");
-  hipLaunchKernelGGL(k_long, dim3(4), dim3(64), 0, 0, d, long_steps, 997);
+  hipLaunchKernelGGL(k_long<P>, dim3(4), dim3(64), 0, 0, d, long_steps, 997);
   CK(hipDeviceSynchronize());
   CK(hipMemcpy(h, d, 64, hipMemcpyDeviceToHost));
-  printf("long chains (%d additions x 256 lanes, cancel every 997): coordinates above 2m + 2^130: %u, mismatches %u, cancellations %u\n",
-         long_steps, h[12], h[13], h[14]);
-  if (h[14] == 0) { printf("no cancellation was exercised\n"); return 1; }
+  CK(hipFree(d));
+  printf("%slong chains (%d additions x 256 lanes, cancel every 997): coordinates above 2m + 2^130: %u, mismatches %u, cancellations %u\n",
+         tag, long_steps, h[12], h[13], h[14]);
+  if (h[14] == 0) { printf("%sno cancellation was exercised\n", tag); return 1; }
   return (h[0] | h[1] | h[2] | h[12] | h[13] | h[15]) ? 1 : 0;
+}
+
+int main(int argc, char** argv) {
+  const int long_steps = argc > 1 ? atoi(argv[1]) : 10240;
+  const int fp = run<FpParams>("", long_steps);
+  const int fq = run<FqParams>("Fq: ", long_steps);
+  return fp | fq;
 }

@@ -103,7 +103,11 @@ template <class P, bool INL = false> VDF_HD void xyzz_madd(XYZZ<P>& acc, const A
 // Q - X3 (minuend Q = X1 PP) 1.5 eps + d_x <= 2.5 eps, PPP' 1.5 eps + d_x, and
 //     d_y' <= 2 eps + (0 + 2.5 eps)/2 + (d_y + 2.5 eps)/2 = 4.5 eps + d_y / 2      d_zz' <= 2 eps + d_zz / 2      d_zzz' <= 2.25 eps + d_zzz / 2
 // CONTRACT: every coordinate stays below 2m + 9 eps for a chain of any length (tools/ubench/madd_check.hip runs 10^4-long
-// chains with cancellations and checks the bound at every step).  (With R' = Y1 - S2, as this function first had it, the
+// chains with cancellations and checks the bound at every step).  Per coordinate the invariant is X: eps, Y: 9 eps, ZZ: 4 eps,
+// ZZZ: 4.5 eps (tests/prim_spec.py re-derives it in exact interval arithmetic).  One precondition the bounds above do not show:
+// fe_sub_lazy(a, b) is exact only for b <= a + 2m, and a subtrahend with slack d (Y1 under S2, X3 under Q, Q under R^2) misses it
+// when the minuend -- a Montgomery product, spread over [0, 2m) -- happens to lie below d: a fraction d / m < 2^-126 of all
+// values, the same order as hitting a given point by chance; nothing guards it.  (With R' = Y1 - S2, as this function first had it, the
 // minuend was Y1 and d_y' <= 3.25 eps + 1.5 d_y + 0.5 d_x: safe only with overwhelming probability, not by construction.)
 // (X3, Y3, ZZ3, -ZZZ3) is the negated sum: instead of negating a coordinate (8+ instructions per addition) the sign
 // moves into `flip`, the NEXT point is negated before it is added (the loops negate by the digit's sign anyway:
@@ -111,7 +115,7 @@ template <class P, bool INL = false> VDF_HD void xyzz_madd(XYZZ<P>& acc, const A
 // Per addition: 8 products + 1 product pair + 6 subtractions, ~2,490 VALU instructions against ~2,595 for 10 + 7.
 // `b` is the point to add to the STORED accumulator (the caller has applied digit sign XOR flip), never the identity.
 // the two squarings of an addition (P^2, R^2): 43 limb products instead of 64, the same value bit for bit (fe.cuh fe_sqr_lazy)
-template <class P> __device__ __forceinline__ Fe<P> fe_sqr_madd(const Fe<P>& a) {
+template <class P> VDF_HD Fe<P> fe_sqr_madd(const Fe<P>& a) {
 #ifdef VDF_MADD_NO_SQR  // A/B build only: the general product
   return fe_mul_lazy(a, a);
 #else
@@ -119,7 +123,7 @@ template <class P> __device__ __forceinline__ Fe<P> fe_sqr_madd(const Fe<P>& a) 
 #endif
 }
 template <class P>
-__device__ __forceinline__ void xyzz_madd_lazy(XYZZ<P>& acc, bool& have, bool& flip, const Affine<P>& b) {
+VDF_HD void xyzz_madd_lazy(XYZZ<P>& acc, bool& have, bool& flip, const Affine<P>& b) {
   if (!have) { acc = xyzz_from_affine(b); have = true; flip = false; return; }
 #ifdef VDF_MADD_V1     // A/B build only (tools/ab_madd.sh): round 3's formulas, ten products and seven subtractions, no sign tracking
   {
@@ -174,7 +178,7 @@ __device__ __forceinline__ void xyzz_madd_lazy(XYZZ<P>& acc, bool& have, bool& f
 }
 // the accumulator as a plain XYZZ point (lazy coordinates): a pending sign goes into y
 template <class P>
-__device__ __forceinline__ XYZZ<P> xyzz_lazy_resolve(XYZZ<P> acc, bool have, bool flip) {
+VDF_HD XYZZ<P> xyzz_lazy_resolve(XYZZ<P> acc, bool have, bool flip) {
   if (!have) return xyzz_identity<P>();
   if (flip) acc.y = fe_neg_lazy(acc.y);
   return acc;

@@ -597,6 +597,8 @@ template <class P> VDF_HD Fe<P> fe_from_small(uint32_t k) {
     r.v[i] = (uint32_t)d;
     borrow = (uint32_t)(d >> 63);
   }
+  // (R mod m = 2^254 - 3c gives q = k - 1 and r = 2^254 - (4k - 1) c > 0 for every k < 2^30: the correction below is never taken
+  // inside the contract -- tests/test_prim_spec.py; it stays as the general form of the reduction)
   if (borrow) {                                                   // negative: add m (the result is then within 2^158 of m, below it)
     uint32_t c = 0;
 #pragma unroll
