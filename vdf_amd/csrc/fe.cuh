@@ -235,6 +235,17 @@ template <class P> VDF_HD Fe<P> fe_mul_generic(const Fe<P>& a, const Fe<P>& b) {
 // acc = (lo, mid) in an aligned VGPR pair + hi.  One product costs v_mad_u64_u32 (64-bit
 // accumulate, carry to VCC) + v_addc_co_u32 (carry into hi): 2 instructions, no v_mov glue.
 // hipcc's own lowering of the portable form is 563 instructions for 88 multiplies; this is ~260.
+// The generated bodies (tools/gen_fe_mul.py) leave the carry add out wherever an exact bound of the accumulator shows
+// that the multiply-add cannot overflow 64 bits: a column starts below 2^37 and its reduction products have small
+// constant factors (q*m2 < 2^60, q*m3 < 2^62, q*m7 = q*2^30, and q*m1 < 0.6 * 2^64), so added first they all fit.  That
+// holds for ANY 256-bit operands; the bounds are the modulus limbs' maxima over both fields, asserted where the bodies
+// are included.  -DVDF_FE_CARRY_ALL selects the schedule with every carry add (A/B builds, `make ab AB_FLAGS=-DVDF_FE_CARRY_ALL`).
+// The limbs the scan never multiplies by -- m0 = 1 (the shift step), m4..m6 = 0 -- and m7 = 2^30 are asserted here; the
+// generated bodies assert M1, M2, M3 (and M7) against the very bounds the generator used, so that a third field cannot
+// silently reuse the files.
+template <class P> constexpr bool fe_scan_modulus_ok() {
+  return P::MOD[0] == 1 && P::MOD[4] == 0 && P::MOD[5] == 0 && P::MOD[6] == 0 && P::MOD[7] == 0x40000000u;
+}
 __device__ __forceinline__ void madc(uint64_t& acc, uint32_t& hi, uint32_t a, uint32_t b) {
   asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_addc_co_u32_e32 %1, vcc, 0, %1, vcc"
       : "+v"(acc), "+v"(hi) : "v"(a), "v"(b) : "vcc");
@@ -250,6 +261,13 @@ __device__ __forceinline__ void col_shift_q(uint64_t& acc, uint32_t& hi) {
   uint32_t lo = (uint32_t)acc, mid = (uint32_t)(acc >> 32), nlo, nmid;
   asm("v_cmp_ne_u32_e32 vcc, 0, %2\n\tv_addc_co_u32_e32 %0, vcc, 0, %3, vcc\n\tv_addc_co_u32_e32 %1, vcc, 0, %4, vcc"
       : "=&v"(nlo), "=&v"(nmid) : "v"(lo), "v"(mid), "v"(hi) : "vcc");
+  acc = ((uint64_t)nmid << 32) | nlo;
+}
+// the same after a column none of whose multiply-adds can carry (fe_*_gfx950.inc): hi never existed, its zero is an inline constant
+__device__ __forceinline__ void col_shift_q0(uint64_t& acc) {
+  uint32_t lo = (uint32_t)acc, mid = (uint32_t)(acc >> 32), nlo, nmid;
+  asm("v_cmp_ne_u32_e32 vcc, 0, %2\n\tv_addc_co_u32_e32 %0, vcc, 0, %3, vcc\n\tv_addc_co_u32_e64 %1, vcc, 0, 0, vcc"
+      : "=&v"(nlo), "=&v"(nmid) : "v"(lo), "v"(mid) : "vcc");
   acc = ((uint64_t)nmid << 32) | nlo;
 }
 __device__ __forceinline__ void col_shift(uint64_t& acc, uint32_t& hi) {
@@ -296,6 +314,7 @@ template <class P> __device__ __forceinline__ Fe<P> fe_mul_inl(const Fe<P>& a, c
   const uint32_t* A = a.v;
   const uint32_t* B = b.v;
   uint32_t r[8];
+  static_assert(fe_scan_modulus_ok<P>(), "the generated column scan hard-codes the sparse limbs of the modulus");
 #include "fe_mul_gfx950.inc"
   fe_cond_sub<P>(r);                      // result < 2m < 2^256: the carry word is zero
   Fe<P> o;
@@ -315,6 +334,7 @@ template <class P> __device__ __forceinline__ Fe<P> fe_mul_lazy(const Fe<P>& a, 
   const uint32_t* A = a.v;
   const uint32_t* B = b.v;
   uint32_t r[8];
+  static_assert(fe_scan_modulus_ok<P>(), "the generated column scan hard-codes the sparse limbs of the modulus");
 #include "fe_mul_gfx950.inc"
   Fe<P> o;
 #pragma unroll
@@ -336,6 +356,7 @@ template <class P> __device__ __forceinline__ Fe<P> fe_sqr_lazy(const Fe<P>& a) 
   for (int j = 2; j < 8; ++j) D[j] = __builtin_amdgcn_alignbit(a.v[j], a.v[j - 1], 31);
   D[8] = a.v[7] >> 31;
   uint32_t r[8];
+  static_assert(fe_scan_modulus_ok<P>(), "the generated column scan hard-codes the sparse limbs of the modulus");
 #include "fe_sqr_gfx950.inc"
   Fe<P> o;
 #pragma unroll
@@ -398,6 +419,7 @@ template <class P> __device__ __forceinline__ Fe<P> fe_mul2_lazy(const Fe<P>& a,
   const uint32_t* Cc = c.v;
   const uint32_t* Dd = d.v;
   uint32_t r[8];
+  static_assert(fe_scan_modulus_ok<P>(), "the generated column scan hard-codes the sparse limbs of the modulus");
 #include "fe_mul2_gfx950.inc"
   const uint32_t mask = (uint32_t)((int32_t)r[7] >> 31);
   const uint32_t m0 = mask & 1u, m1 = mask & P::MOD[1], m2 = mask & P::MOD[2], m3 = mask & P::MOD[3], m7 = mask & 0x40000000u;
