@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Emit vdf_amd/csrc/fe_mul_gfx950.inc, fe_sqr_gfx950.inc and fe_mul2_gfx950.inc: the bodies of the gfx950 Montgomery
-products (product scanning, 96-bit column accumulator) with ONE asm statement per column.
+products (product scanning, 96-bit column accumulator) with ONE asm statement per column -- and fe_{mul,sqr,mul2}_t31_gfx950.inc,
+the same columns for multiplicands whose limb 7 is at most 2^31 (every value of the lazy domain: fe.cuh), where that bound lets
+more carry adds of columns 7..14 go.
 
 hipcc pads every boundary between two consecutive inline-asm statements with s_nop and zero-initialises `hi` with a
 v_mov per column; generating the columns (each with its exact number of products and reduction terms, and the first
@@ -17,7 +19,7 @@ the shift step a constant zero.  The sum of a column does not depend on the orde
 overflows that happen, so the result is bit for bit what the schedule with every carry add gives; that schedule is kept
 in each file under VDF_FE_CARRY_ALL for A/B builds.
 
-  gen_fe_mul.py            write the three files
+  gen_fe_mul.py            write the six files
   gen_fe_mul.py --check    regenerate them in memory and fail on any difference from the committed files
 
 schedule() and model() expose the same column lists as a pure-integer model of the emitted schedule (64-bit wrapping
@@ -48,13 +50,20 @@ ADDC_FIRST = "v_addc_co_u32_e64 %[hi], vcc, 0, 0, vcc"
 ADDC = "v_addc_co_u32_e32 %[hi], vcc, 0, %[hi], vcc"
 
 
-def bound(body, name):
+TOP31 = 1 << 31          # the bounded-top bodies: limb 7 of every multiplicand is at most this (a lazy value is below 2^255 + 2^224)
+
+
+def bound(body, name, top31=False):
     """upper bound of an operand: limbs of A, B, C, D, the squaring's shifted limbs and the quotient digits are 32-bit words
-    (nothing is assumed about the operands beyond 256 bits), d8 of the squaring is the carry of 2a, the modulus limbs are constants"""
+    (nothing is assumed about the operands beyond 256 bits), d8 of the squaring is the carry of 2a, the modulus limbs are constants.
+    top31: limb 7 of every multiplicand is at most 2^31 -- a7, b7, c7, d7 of the products, a7 alone of the squaring (d7, s7 and d8
+    are limbs of 2a, which that does not bound)"""
     if name in M_MAX:
         return M_MAX[name]
     if body == "sqr" and name == "d8":
         return 1
+    if top31 and name in (("a7",) if body == "sqr" else ("a7", "b7", "c7", "d7")):
+        return TOP31
     return B32
 
 
@@ -114,23 +123,25 @@ class Column:
         self.has_hi = any(t.carry for t in terms)
 
 
-def schedule(body, carry_all=False):
+def schedule(body, carry_all=False, top31=False):
     """the 15 columns of a body.  carry_all: the order and the carry adds of the schedule before the bound argument (every
-    product followed by its carry add); otherwise ascending bounds and only the carry adds that can see a carry"""
+    product followed by its carry add); otherwise ascending bounds and only the carry adds that can see a carry.
+    top31: the bounded-top body (bound())"""
+    assert not (carry_all and top31)
     cols, entry = [], 0
     for k in range(15):
         first, second, reds = column_terms(body, k)
-        terms = [Term(x, y, bound(body, x) * bound(body, y), False) for x, y in first]
-        terms += [Term(x, y, bound(body, x) * bound(body, y), True) for x, y in second]
+        terms = [Term(x, y, bound(body, x, top31) * bound(body, y, top31), False) for x, y in first]
+        terms += [Term(x, y, bound(body, x, top31) * bound(body, y, top31), True) for x, y in second]
         rterms = [Term(x, y, bound(body, x) * bound(body, y), bool(second)) for x, y in reds]
         if carry_all:
             terms += rterms
         else:
-            # the reduction terms belong to the first statement (30 asm operands allow it); the stable sort keeps the second
-            # product's terms, which share the first's bound, behind them
+            # the reduction terms belong to the first statement (30 asm operands allow it); the second product's terms stay
+            # behind the first's (they share its bounds; with a bounded top limb the ascending order holds within each statement)
             for t in rterms:
                 t.second = False
-            terms = sorted(rterms + terms, key=lambda t: t.bound)
+            terms = sorted(rterms + terms, key=lambda t: (t.second, t.bound))
             assert [t.second for t in terms] == sorted(t.second for t in terms)
         running, emitting = entry, carry_all
         for t in terms:
@@ -151,8 +162,8 @@ def schedule(body, carry_all=False):
     return cols
 
 
-def dropped(body):
-    return sum(1 for c in schedule(body) for t in c.terms if not t.carry)
+def dropped(body, top31=False):
+    return sum(1 for c in schedule(body, top31=top31) for t in c.terms if not t.carry)
 
 
 def emit_statement(body, col, terms, first_stmt, hi_live):
@@ -171,12 +182,14 @@ def emit_statement(body, col, terms, first_stmt, hi_live):
     return '  asm("%s"\n      : %s\n      : %s\n      : "vcc");' % ("\\n\\t".join(lines), outs, inputs)
 
 
-def emit_body(body, carry_all):
+def emit_body(body, carry_all, top31=False):
     out = ["  uint32_t q[8];\n  uint64_t acc;\n  uint32_t hi;"]
     if not carry_all:
         out.append('  static_assert(%s, "the carry adds were dropped for modulus limbs within these bounds (tools/gen_fe_mul.py)");'
                    % " && ".join("%s <= 0x%08xu" % (n.upper(), v) for n, v in M_MAX.items()))
-    for col in schedule(body, carry_all):
+    if top31:
+        out.append('  static_assert(TOP7 <= 0x%08xu, "the carry adds were dropped for multiplicands whose limb 7 is within this bound (tools/gen_fe_mul.py)");' % TOP31)
+    for col in schedule(body, carry_all, top31):
         k = col.k
         if carry_all:
             out.append("  // ---- column %d ----" % k)
@@ -191,8 +204,10 @@ def emit_body(body, carry_all):
         out.append(emit_statement(body, col, one, True, False))
         if two:
             out.append(emit_statement(body, col, two, False, any(t.carry for t in one)))
-        if k < 8:
+        if k < 8 and carry_all:
             out.append("  q[%d] = 0u - (uint32_t)acc;\n  %s;" % (k, "col_shift_q(acc, hi)" if col.has_hi else "col_shift_q0(acc)"))
+        elif k < 8:
+            out.append("  q[%d] = %s;" % (k, "col_shift_qf(acc, hi)" if col.has_hi else "col_shift_qf0(acc)"))
         elif col.has_hi:
             out.append("  r[%d] = (uint32_t)acc;\n  acc = (acc >> 32) | ((uint64_t)hi << 32);" % (k - 8))
         else:
@@ -217,6 +232,38 @@ HEADERS = {
              "// Inputs: const uint32_t* A, * B, * Cc, * Dd; constexpr M1, M2, M3, M7.  Outputs: uint32_t r[8] =",
              "// (A*B + Cc*Dd + q*m) / 2^256, below 3m + eps for inputs below 2m + eps."],
 }
+
+
+T31_ENTRY = {"mul": "fe_mul_lazy_t31", "sqr": "fe_sqr_lazy_t31", "mul2": "fe_mul2_lazy_t31"}
+
+
+def render_t31(body):
+    """the bounded-top body: the same columns with limb 7 of every multiplicand at most 2^31 (fe.cuh: the lazy domain's values)"""
+    mads = sum(len(c.terms) for c in schedule(body, top31=True))
+    n = dropped(body, top31=True)
+    out = ["// GENERATED by tools/gen_fe_mul.py -- do not edit.  Included inside %s (fe.cuh)." % T31_ENTRY[body]]
+    out += HEADERS[body][1:]
+    out.append("// PRECONDITION: limb 7 of %s is at most 0x%08x; constexpr TOP7 is the bound the including function vouches for."
+               % ("A" if body == "sqr" else "every multiplicand (%s)" % ", ".join(["A", "B", "Cc", "Dd"][:2 if body == "mul" else 4]), TOP31))
+    out.append("// %d v_mad_u64_u32, %d v_addc_co_u32: %d carry adds dropped (%d without that precondition, fe_%s_gfx950.inc)."
+               % (mads, mads - n, n, dropped(body), body))
+    out += emit_body(body, False, top31=True)
+    return "\n".join(out) + "\n"
+
+
+def outputs():
+    """file name -> (text, summary line) of everything this tool writes"""
+    out = {}
+    for top31 in (False, True):
+        for body in BODIES:
+            name = "fe_%s_%sgfx950.inc" % (body, "t31_" if top31 else "")
+            cols = schedule(body, top31=top31)
+            mads = sum(len(c.terms) for c in cols)
+            n = dropped(body, top31)
+            out[name] = (render_t31(body) if top31 else render(body),
+                         "%s: %d v_mad_u64_u32, %d v_addc_co_u32 (%d dropped; per column %s)"
+                         % (name, mads, mads - n, n, " ".join(str(sum(1 for t in c.terms if not t.carry)) for c in cols)))
+    return out
 
 
 def render(body):
@@ -295,18 +342,14 @@ def model(cols, vals):
 def main(argv):
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "vdf_amd", "csrc")
     check, bad = "--check" in argv, []
-    for body in BODIES:
-        path = os.path.join(root, "fe_%s_gfx950.inc" % body)
-        text = render(body)
+    for name, (text, summary) in outputs().items():
+        path = os.path.join(root, name)
         if check:
             if not os.path.exists(path) or open(path).read() != text:
                 bad.append(os.path.relpath(path))
         else:
             open(path, "w").write(text)
-        mads = sum(len(c.terms) for c in schedule(body))
-        print("fe_%s_gfx950.inc: %d v_mad_u64_u32, %d v_addc_co_u32 (%d dropped; per column %s)"
-              % (body, mads, mads - dropped(body), dropped(body),
-                 " ".join(str(sum(1 for t in c.terms if not t.carry)) for c in schedule(body))))
+        print(summary)
     if bad:
         print("differs from what tools/gen_fe_mul.py generates: " + ", ".join(bad))
         return 1

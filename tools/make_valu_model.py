@@ -9,6 +9,14 @@ import csv, glob, json, re, sys
 op_rates, clock, pmc_dir, entries, out = sys.argv[1], sys.argv[2], sys.argv[3], float(sys.argv[4]), sys.argv[5]
 tag = sys.argv[6] if len(sys.argv) > 6 else "r03"
 commit = sys.argv[7] if len(sys.argv) > 7 else "unknown"
+
+def cited(path):
+    """the committed name of a raw file: one already under profiles/ with a round tag of its own (an earlier round's measurement
+    reused) keeps its name, anything else is this round's"""
+    name = path.split("/")[-1]
+    return "profiles/" + (name if re.match(r"r\d\d_", name) else tag + "_" + name)
+
+
 cyc = None
 for line in open(op_rates):
     if line.startswith("mad_u64 + addc pair"):
@@ -27,9 +35,9 @@ res = {"produced_at_commit": commit, "round": tag, "valu_per_bucket_addition": p
        "cycles_per_valu_wave_instruction_per_simd": cyc,
        "sustained_shader_clock_ghz": sorted(mhz)[len(mhz) // 2] / 1e3,
        "provenance": {"SQ_INSTS_VALU_per_k_accumulate_launch": per_launch, "launches": len(vals), "entries_per_launch": entries,
-                      "op_rates": "profiles/" + tag + "_" + op_rates.split("/")[-1] + " (row 'mad_u64 + addc pair', best of 1/2/4/8 workgroups per CU; "
+                      "op_rates": cited(op_rates) + " (row 'mad_u64 + addc pair', best of 1/2/4/8 workgroups per CU; "
                                   "the multiply is one v_mad_u64_u32 + one v_addc_co_u32 per product)",
-                      "clock": "profiles/" + tag + "_" + clock.split("/")[-1] + " (median of the reported shader clocks: the first runs ramp up from idle)",
+                      "clock": cited(clock) + " (median of the reported shader clocks: the first runs ramp up from idle)",
                       "note": "MI355X_MICROARCH.md: SIMD-32, a wave64 VALU instruction issues over 2 cycles at full rate; "
                               "v_mad_u64_u32 and the carry-writing adds measure at about twice that"}}
 json.dump(res, open(out, "w"), indent=1)

@@ -36,6 +36,7 @@ using namespace vdf;
   X(22, 6, 4, 1, 0) /* xyzz_madd<false> */ X(23, 6, 4, 1, 0) /* xyzz_madd<true> */ X(24, 8, 4, 1, 0) /* xyzz_add */ \
   X(25, 4, 4, 1, 0) /* xyzz_dbl */         X(26, 2, 4, 1, 0) /* xyzz_dbl_affine */ X(27, 4, 3, 1, 0) /* xyzz_to_jac */ \
   X(28, 3, 4, 1, 0) /* jac_to_xyzz */      X(29, 4, 2, 1, 0) /* xyzz_to_affine */  X(30, 3, 4, 1, 0) /* xyzz_mul_u64: point, k */ \
+  X(31, 2, 1, 1, 0) /* fe_mul_lazy_t31 */  X(32, 1, 1, 1, 0) /* fe_sqr_lazy_t31 */ X(33, 4, 1, 1, 0) /* fe_mul2_lazy_t31: limb 7 of every operand <= 0x80000000 */ \
   X(40, 8, 5, 0, 1) /* qpoint_add -> point, inf */   X(41, 4, 5, 0, 1) /* qpoint_dbl */   X(42, 4, 5, 0, 1) /* qpoint_neg */ \
   X(43, 4, 5, 0, 1) /* qpoint_load_lazy -> qpoint_store */ \
   X(44, 4, 5, 0, 1) /* qpoint_wave_sum over each 16 consecutive cases (ncases a multiple of 16) */
@@ -99,6 +100,9 @@ template <class P, int OP> VDF_HD void apply(const uint32_t* in, uint32_t* out) 
     st4<P>(out, 0, jac_to_xyzz(j));
   } else if constexpr (OP == 29) affine_store<P>(out, xyzz_to_affine(ld4<P>(in, 0)));
   else if constexpr (OP == 30) st4<P>(out, 0, xyzz_mul_u64(affine_load<P>(in), (uint64_t)in[16] | ((uint64_t)in[17] << 32)));
+  else if constexpr (OP == 31) st<P>(out, 0, fe_mul_lazy_t31(ld<P>(in, 0), ld<P>(in, 1)));
+  else if constexpr (OP == 32) st<P>(out, 0, fe_sqr_lazy_t31(ld<P>(in, 0)));
+  else if constexpr (OP == 33) st<P>(out, 0, fe_mul2_lazy_t31(ld<P>(in, 0), ld<P>(in, 1), ld<P>(in, 2), ld<P>(in, 3)));
 }
 
 template <class P, int OP> __global__ __launch_bounds__(64) void k_lane(const uint32_t* in, uint32_t* out, int n, int nin, int nout) {

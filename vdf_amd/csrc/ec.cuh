@@ -115,11 +115,42 @@ template <class P, bool INL = false> VDF_HD void xyzz_madd(XYZZ<P>& acc, const A
 // Per addition: 8 products + 1 product pair + 6 subtractions, ~2,490 VALU instructions against ~2,595 for 10 + 7.
 // `b` is the point to add to the STORED accumulator (the caller has applied digit sign XOR flip), never the identity.
 // the two squarings of an addition (P^2, R^2): 43 limb products instead of 64, the same value bit for bit (fe.cuh fe_sqr_lazy)
+//
+// TOP LIMBS.  The products of this function and of xyzz_add_lazy below are the bounded-top bodies (fe.cuh fe_mul_lazy_t31,
+// fe_sqr_lazy_t31, fe_mul2_lazy_t31): limb 7 of EVERY factor must be at most 0x80000000, i.e. the factor below 2^255 + 2^224,
+// which 2m + 9 eps is in both fields (asserted in fe.cuh).  Audit, factor by factor -- each is one of
+//   * a stored coordinate of acc: below 2m + 9 eps by the contract above.  It got there as a canonical value (xyzz_from_affine,
+//     xyzz_dbl_affine, the canonical law of xyzz_add_lazy's equal-x branch, or a load that went through fe_canon) or as an
+//     output of these two functions: X3 (a difference), Y3 (a product pair, back below 2m + 2 eps + ... by its top-bit step),
+//     ZZ3, ZZZ3 (products);
+//   * a coordinate of b: canonical, or the fe_neg_nz image m - y of a canonical non-zero y -- below m, limb 7 <= 0x40000000;
+//   * a lazy product (U1, U2, S1, S2, PP, PPP', Q, ZZ1 ZZ2, ZZZ1 ZZZ2): below 2m + eps + half its factors' slacks;
+//   * a fe_sub_lazy result (P', R, Q - X3, and X3 itself): a - b <= a without a borrow, a - b + 2m < 2m with one -- below the
+//     larger of 2m and its minuend's bound.  (Outside fe_sub_lazy's own precondition b <= a + 2m -- the 2^-126 event described
+//     above -- the difference wraps and is wrong under either body.)
+// The one value of this file that is NOT inside the bound is fe_neg_lazy's (up to 3m, limb 7 up to 0xC0000000).  It is
+// applied only by xyzz_lazy_resolve, whose result never comes back as a factor: msm.hip k_accumulate (flush_lazy) and
+// msm_direct.hip k_direct_sum store it, and the accumulator they go on with starts again from `have = false`; k_fixup_serial
+// -- the only caller of xyzz_add_lazy -- passes every loaded coordinate through fe_canon before it is a factor, negates a
+// canonical y with fe_neg_nz, and resolves only to store; xyzz_add_lazy's equal-x branch resolves and then canonicalises all
+// four coordinates before the canonical law.  The callers of xyzz_madd_lazy (k_accumulate, k_direct_sum) pass table points as
+// loaded -- the tables and the point arrays of this library hold canonical coordinates -- with y negated by fe_neg_nz.
+// A/B builds: -DVDF_FE_R10 keeps the generic bodies here; so does -DVDF_MADD_R4, whose operand order lets the slack of Y grow
+// with the chain (no contraction), so that its factors are not bounded by the contract.
+#if defined(VDF_FE_R10) || defined(VDF_MADD_R4)
+template <class P> VDF_HD Fe<P> fe_mul_madd(const Fe<P>& a, const Fe<P>& b) { return fe_mul_lazy(a, b); }
+template <class P> VDF_HD Fe<P> fe_mul2_madd(const Fe<P>& a, const Fe<P>& b, const Fe<P>& c, const Fe<P>& d) { return fe_mul2_lazy(a, b, c, d); }
+#else
+template <class P> VDF_HD Fe<P> fe_mul_madd(const Fe<P>& a, const Fe<P>& b) { return fe_mul_lazy_t31(a, b); }
+template <class P> VDF_HD Fe<P> fe_mul2_madd(const Fe<P>& a, const Fe<P>& b, const Fe<P>& c, const Fe<P>& d) { return fe_mul2_lazy_t31(a, b, c, d); }
+#endif
 template <class P> VDF_HD Fe<P> fe_sqr_madd(const Fe<P>& a) {
 #ifdef VDF_MADD_NO_SQR  // A/B build only: the general product
-  return fe_mul_lazy(a, a);
-#else
+  return fe_mul_madd(a, a);
+#elif defined(VDF_FE_R10) || defined(VDF_MADD_R4)
   return fe_sqr_lazy(a);
+#else
+  return fe_sqr_lazy_t31(a);
 #endif
 }
 template <class P>
@@ -148,8 +179,8 @@ VDF_HD void xyzz_madd_lazy(XYZZ<P>& acc, bool& have, bool& flip, const Affine<P>
     return;
   }
 #endif
-  const Fe<P> U2 = fe_mul_lazy(b.x, acc.zz);
-  const Fe<P> S2 = fe_mul_lazy(b.y, acc.zzz);
+  const Fe<P> U2 = fe_mul_madd(b.x, acc.zz);
+  const Fe<P> S2 = fe_mul_madd(b.y, acc.zzz);
   const Fe<P> Pn = fe_sub_lazy(acc.x, U2);         // P' = -P
 #ifdef VDF_MADD_R4     // A/B build only: round 4's operand order (R' = Y1 - S2; same instruction count, no slack contraction)
   const Fe<P> Rr = fe_sub_lazy(acc.y, S2);
@@ -163,17 +194,17 @@ VDF_HD void xyzz_madd_lazy(XYZZ<P>& acc, bool& have, bool& flip, const Affine<P>
     return;
   }
   const Fe<P> PP = fe_sqr_madd(Pn);
-  const Fe<P> PPPn = fe_mul_lazy(Pn, PP);
-  const Fe<P> Qq = fe_mul_lazy(acc.x, PP);
+  const Fe<P> PPPn = fe_mul_madd(Pn, PP);
+  const Fe<P> Qq = fe_mul_madd(acc.x, PP);
   const Fe<P> X3 = fe_sub_lazy(fe_sub_lazy(fe_sqr_madd(Rr), Qq), fe_sub_lazy(Qq, PPPn));
 #ifdef VDF_MADD_R4
-  acc.y = fe_mul2_lazy(Rr, fe_sub_lazy(X3, Qq), acc.y, PPPn);
+  acc.y = fe_mul2_madd(Rr, fe_sub_lazy(X3, Qq), acc.y, PPPn);
 #else
-  acc.y = fe_mul2_lazy(Rr, fe_sub_lazy(Qq, X3), acc.y, PPPn);
+  acc.y = fe_mul2_madd(Rr, fe_sub_lazy(Qq, X3), acc.y, PPPn);
 #endif
   acc.x = X3;
-  acc.zz = fe_mul_lazy(acc.zz, PP);
-  acc.zzz = fe_mul_lazy(acc.zzz, PPPn);
+  acc.zz = fe_mul_madd(acc.zz, PP);
+  acc.zzz = fe_mul_madd(acc.zzz, PPPn);
   flip = !flip;
 }
 // the accumulator as a plain XYZZ point (lazy coordinates): a pending sign goes into y
@@ -220,10 +251,10 @@ template <class P> VDF_HD void xyzz_add(XYZZ<P>& acc, const XYZZ<P>& b) {
 template <class P>
 __device__ __forceinline__ void xyzz_add_lazy(XYZZ<P>& acc, bool& have, bool& flip, const XYZZ<P>& b) {
   if (!have) { acc = b; have = true; flip = false; return; }
-  const Fe<P> U1 = fe_mul_lazy(acc.x, b.zz);
-  const Fe<P> U2 = fe_mul_lazy(b.x, acc.zz);
-  const Fe<P> S1 = fe_mul_lazy(acc.y, b.zzz);
-  const Fe<P> S2 = fe_mul_lazy(b.y, acc.zzz);
+  const Fe<P> U1 = fe_mul_madd(acc.x, b.zz);
+  const Fe<P> U2 = fe_mul_madd(b.x, acc.zz);
+  const Fe<P> S1 = fe_mul_madd(acc.y, b.zzz);
+  const Fe<P> S2 = fe_mul_madd(b.y, acc.zzz);
   const Fe<P> Pn = fe_sub_lazy(U1, U2);
   const Fe<P> Rr = fe_sub_lazy(S2, S1);
   if (Pn.v[0] <= 2u && fe_is_zero(fe_canon(Pn))) {                     // same x: the canonical law decides (double / identity)
@@ -236,13 +267,13 @@ __device__ __forceinline__ void xyzz_add_lazy(XYZZ<P>& acc, bool& have, bool& fl
     return;
   }
   const Fe<P> PP = fe_sqr_madd(Pn);
-  const Fe<P> PPPn = fe_mul_lazy(Pn, PP);
-  const Fe<P> Qq = fe_mul_lazy(U1, PP);
+  const Fe<P> PPPn = fe_mul_madd(Pn, PP);
+  const Fe<P> Qq = fe_mul_madd(U1, PP);
   const Fe<P> X3 = fe_sub_lazy(fe_sub_lazy(fe_sqr_madd(Rr), Qq), fe_sub_lazy(Qq, PPPn));
-  acc.y = fe_mul2_lazy(Rr, fe_sub_lazy(Qq, X3), S1, PPPn);
+  acc.y = fe_mul2_madd(Rr, fe_sub_lazy(Qq, X3), S1, PPPn);
   acc.x = X3;
-  acc.zz = fe_mul_lazy(fe_mul_lazy(acc.zz, b.zz), PP);
-  acc.zzz = fe_mul_lazy(fe_mul_lazy(acc.zzz, b.zzz), PPPn);
+  acc.zz = fe_mul_madd(fe_mul_madd(acc.zz, b.zz), PP);
+  acc.zzz = fe_mul_madd(fe_mul_madd(acc.zzz, b.zzz), PPPn);
   flip = !flip;
 }
 #endif

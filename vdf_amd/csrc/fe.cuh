@@ -270,6 +270,36 @@ __device__ __forceinline__ void col_shift_q0(uint64_t& acc) {
       : "=&v"(nlo), "=&v"(nmid) : "v"(lo), "v"(mid) : "vcc");
   acc = ((uint64_t)nmid << 32) | nlo;
 }
+// The shipped bodies' form of the two: the quotient digit q = 0 - lo borrows exactly when lo != 0, which is the carry the shift
+// step needs, so ONE v_sub_co_u32 yields the digit and the flag (three instructions per reducing column instead of four).
+// Returns q.  -DVDF_FE_R10 (A/B builds, tools/ab_fe_fused.sh) keeps the digit and the compare apart, as before that change;
+// -DVDF_FE_UNFUSED does only that (the bounded-top bodies of the lazy group law stay), to tell the two changes apart.
+__device__ __forceinline__ uint32_t col_shift_qf(uint64_t& acc, uint32_t& hi) {
+#if defined(VDF_FE_R10) || defined(VDF_FE_UNFUSED)
+  const uint32_t q = 0u - (uint32_t)acc;
+  col_shift_q(acc, hi);
+  return q;
+#else
+  uint32_t lo = (uint32_t)acc, mid = (uint32_t)(acc >> 32), q, nlo, nmid;
+  asm("v_sub_co_u32_e32 %0, vcc, 0, %3\n\tv_addc_co_u32_e32 %1, vcc, 0, %4, vcc\n\tv_addc_co_u32_e32 %2, vcc, 0, %5, vcc"
+      : "=&v"(q), "=&v"(nlo), "=&v"(nmid) : "v"(lo), "v"(mid), "v"(hi) : "vcc");
+  acc = ((uint64_t)nmid << 32) | nlo;
+  return q;
+#endif
+}
+__device__ __forceinline__ uint32_t col_shift_qf0(uint64_t& acc) {
+#if defined(VDF_FE_R10) || defined(VDF_FE_UNFUSED)
+  const uint32_t q = 0u - (uint32_t)acc;
+  col_shift_q0(acc);
+  return q;
+#else
+  uint32_t lo = (uint32_t)acc, mid = (uint32_t)(acc >> 32), q, nlo, nmid;
+  asm("v_sub_co_u32_e32 %0, vcc, 0, %3\n\tv_addc_co_u32_e32 %1, vcc, 0, %4, vcc\n\tv_addc_co_u32_e64 %2, vcc, 0, 0, vcc"
+      : "=&v"(q), "=&v"(nlo), "=&v"(nmid) : "v"(lo), "v"(mid) : "vcc");
+  acc = ((uint64_t)nmid << 32) | nlo;
+  return q;
+#endif
+}
 __device__ __forceinline__ void col_shift(uint64_t& acc, uint32_t& hi) {
   acc = (acc >> 32) | ((uint64_t)hi << 32);
   hi = 0;
@@ -364,6 +394,55 @@ template <class P> __device__ __forceinline__ Fe<P> fe_sqr_lazy(const Fe<P>& a) 
   return o;
 }
 
+// ---- the same three products for operands whose limb 7 is at most 0x80000000 ----------------------------------------------------
+// A value of the lazy domain is below 2m + 9 eps (ec.cuh: the bucket additions' contract).  With m = 2^254 + t, t < 2^126 (limbs
+// 4..6 of m are zero and limb 3 is below 2^30), eps = m (m / 2^254 - 1) = t + t^2 / 2^254 < t + 1, so 2m + 9 eps < 2^255 + 11 t + 9
+// < 2^255 + 2^130 < 2^255 + 2^224: limb 7 is at most 0x80000000.  With that bound on limb 7 of every multiplicand the generator
+// drops more carry adds in columns 7..14 (fe_*_t31_gfx950.inc: 39 / 39 / 40 instead of 31 / 38 / 31); the result is bit for bit
+// the generic body's.  PRECONDITION of the three entry points: limb 7 of EVERY operand <= 0x80000000 -- a larger one (a
+// fe_neg_lazy image reaches 0xC0000000, an arbitrary 256-bit word 0xFFFFFFFF) can lose a carry: such operands go to the generic
+// entry points above, which assume nothing.  Callers: ec.cuh xyzz_madd_lazy and xyzz_add_lazy only (audit there).
+template <class P> constexpr uint32_t fe_lazy_top7() {      // the largest limb 7 of a lazy value, 0xFFFFFFFF if the argument above fails
+  return (P::MOD[7] == 0x40000000u && P::MOD[6] == 0 && P::MOD[5] == 0 && P::MOD[4] == 0 && P::MOD[3] < 0x40000000u) ? 0x80000000u
+                                                                                                                    : 0xFFFFFFFFu;
+}
+static_assert(fe_lazy_top7<FpParams>() == 0x80000000u, "Fp: 2m + 9 eps must lie below 2^255 + 2^224");
+static_assert(fe_lazy_top7<FqParams>() == 0x80000000u, "Fq: 2m + 9 eps must lie below 2^255 + 2^224");
+#if defined(VDF_FE_CARRY_ALL)      // A/B build only: no bound argument at all
+template <class P> __device__ __forceinline__ Fe<P> fe_mul_lazy_t31(const Fe<P>& a, const Fe<P>& b) { return fe_mul_lazy(a, b); }
+template <class P> __device__ __forceinline__ Fe<P> fe_sqr_lazy_t31(const Fe<P>& a) { return fe_sqr_lazy(a); }
+#else
+template <class P> __device__ __forceinline__ Fe<P> fe_mul_lazy_t31(const Fe<P>& a, const Fe<P>& b) {
+  constexpr uint32_t M1 = P::MOD[1], M2 = P::MOD[2], M3 = P::MOD[3], M7 = P::MOD[7], TOP7 = fe_lazy_top7<P>();
+  const uint32_t* A = a.v;
+  const uint32_t* B = b.v;
+  uint32_t r[8];
+  static_assert(fe_scan_modulus_ok<P>(), "the generated column scan hard-codes the sparse limbs of the modulus");
+#include "fe_mul_t31_gfx950.inc"
+  Fe<P> o;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) o.v[i] = r[i];
+  return o;
+}
+template <class P> __device__ __forceinline__ Fe<P> fe_sqr_lazy_t31(const Fe<P>& a) {
+  constexpr uint32_t M1 = P::MOD[1], M2 = P::MOD[2], M3 = P::MOD[3], M7 = P::MOD[7], TOP7 = fe_lazy_top7<P>();
+  const uint32_t* A = a.v;
+  uint32_t S[8], D[9];
+#pragma unroll
+  for (int j = 1; j < 8; ++j) S[j] = a.v[j] << 1;
+#pragma unroll
+  for (int j = 2; j < 8; ++j) D[j] = __builtin_amdgcn_alignbit(a.v[j], a.v[j - 1], 31);
+  D[8] = a.v[7] >> 31;
+  uint32_t r[8];
+  static_assert(fe_scan_modulus_ok<P>(), "the generated column scan hard-codes the sparse limbs of the modulus");
+#include "fe_sqr_t31_gfx950.inc"
+  Fe<P> o;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) o.v[i] = r[i];
+  return o;
+}
+#endif
+
 // a - b (+ 2m on borrow) for a, b in [0, 2m + eps).  Three-operand form: the difference goes to registers of its own
 // (early-clobber outputs), so an operand that stays live afterwards -- X1, Y1, Q in the bucket addition -- is not copied first
 // (the in-place form cost eight v_mov per live operand: 42 moves per addition in round 4's first version of the loop).
@@ -412,15 +491,20 @@ template <class P> __device__ __forceinline__ Fe<P> fe_sub_lazy(const Fe<P>& a, 
 // values in [2^255, 2m).)  Exactly: out < 2m + 2 eps + (d_a + d_b + d_c + d_d) / 2 -- each factor's slack is halved, because the
 // OTHER factor is below 2m + d and 2m / 2^256 = 1/2 (+ 2^-130).  The pair alone does not contract (four halves); the mixed
 // addition feeds it one slack-free factor and two bounded ones, which does (ec.cuh xyzz_madd_lazy: d_y' <= 4.5 eps + d_y / 2).
-template <class P> __device__ __forceinline__ Fe<P> fe_mul2_lazy(const Fe<P>& a, const Fe<P>& b, const Fe<P>& c, const Fe<P>& d) {
-  constexpr uint32_t M1 = P::MOD[1], M2 = P::MOD[2], M3 = P::MOD[3], M7 = P::MOD[7];
+// T31: the bounded-top column scan (limb 7 of a, b, c, d <= 0x80000000: fe_mul2_lazy_t31); the correction after it is the same.
+template <class P, bool T31> __device__ __forceinline__ Fe<P> fe_mul2_lazy_scan(const Fe<P>& a, const Fe<P>& b, const Fe<P>& c, const Fe<P>& d) {
+  constexpr uint32_t M1 = P::MOD[1], M2 = P::MOD[2], M3 = P::MOD[3], M7 = P::MOD[7], TOP7 = fe_lazy_top7<P>();
   const uint32_t* A = a.v;
   const uint32_t* B = b.v;
   const uint32_t* Cc = c.v;
   const uint32_t* Dd = d.v;
   uint32_t r[8];
   static_assert(fe_scan_modulus_ok<P>(), "the generated column scan hard-codes the sparse limbs of the modulus");
+  if constexpr (T31) {
+#include "fe_mul2_t31_gfx950.inc"
+  } else {
 #include "fe_mul2_gfx950.inc"
+  }
   const uint32_t mask = (uint32_t)((int32_t)r[7] >> 31);
   const uint32_t m0 = mask & 1u, m1 = mask & P::MOD[1], m2 = mask & P::MOD[2], m3 = mask & P::MOD[3], m7 = mask & 0x40000000u;
   asm("v_sub_co_u32_e32 %0, vcc, %0, %8\n\t"
@@ -438,6 +522,17 @@ template <class P> __device__ __forceinline__ Fe<P> fe_mul2_lazy(const Fe<P>& a,
 #pragma unroll
   for (int i = 0; i < 8; ++i) o.v[i] = r[i];
   return o;
+}
+template <class P> __device__ __forceinline__ Fe<P> fe_mul2_lazy(const Fe<P>& a, const Fe<P>& b, const Fe<P>& c, const Fe<P>& d) {
+  return fe_mul2_lazy_scan<P, false>(a, b, c, d);
+}
+// PRECONDITION: limb 7 of a, b, c and d <= 0x80000000 (see fe_mul_lazy_t31)
+template <class P> __device__ __forceinline__ Fe<P> fe_mul2_lazy_t31(const Fe<P>& a, const Fe<P>& b, const Fe<P>& c, const Fe<P>& d) {
+#if defined(VDF_FE_CARRY_ALL)
+  return fe_mul2_lazy_scan<P, false>(a, b, c, d);
+#else
+  return fe_mul2_lazy_scan<P, true>(a, b, c, d);
+#endif
 }
 
 // -a in the lazy domain: 3m - a, exact for every a below 3m (fe_sub_lazy(0, a) would wrap for a in (2m, 2m + eps));
@@ -506,6 +601,9 @@ template <class P> VDF_HD Fe<P> fe_mul2_lazy(const Fe<P>& a, const Fe<P>& b, con
   return fe_add(fe_mul_generic(a, b), fe_mul_generic(c, d));
 }
 template <class P> VDF_HD Fe<P> fe_neg_lazy(const Fe<P>& a) { return fe_neg(a); }
+template <class P> VDF_HD Fe<P> fe_mul_lazy_t31(const Fe<P>& a, const Fe<P>& b) { return fe_mul_lazy(a, b); }
+template <class P> VDF_HD Fe<P> fe_sqr_lazy_t31(const Fe<P>& a) { return fe_sqr_lazy(a); }
+template <class P> VDF_HD Fe<P> fe_mul2_lazy_t31(const Fe<P>& a, const Fe<P>& b, const Fe<P>& c, const Fe<P>& d) { return fe_mul2_lazy(a, b, c, d); }
 template <class P> VDF_HD Fe<P> fe_neg_nz(const Fe<P>& a) { return fe_neg(a); }
 #endif
 
