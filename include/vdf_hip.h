@@ -372,7 +372,8 @@ int  vdf_minroot_step_segment_packed(vdf_ctx* ctx, int field, const vdf_fe* trac
 /* The variables of the FORWARD MinRoot step circuit (vdf_nova.h VDF_CIRCUIT_MINROOT_FORWARD), which proves a step in the
  * direction it was evaluated: per round j the fifth root x_(j+1) = trace_xy[j + 1].x, its square and its fourth power, then
  * final_i = i_end (the step's last round counter; host memory).  out has 3t + 1 elements; trace_xy as everywhere
- * (trace_xy[k] = (x_k, y_k), k = 0..t, device memory). */
+ * (trace_xy[k] = (x_k, y_k), k = 0..t, device memory).  This is vdf_minroot_forward_segment_lanes with lanes = 1 and
+ * lane_stride = t + 1: the same checks, the same launch. */
 int  vdf_minroot_forward_segment(vdf_ctx* ctx, int field, const vdf_fe* trace_xy, uint64_t t, const vdf_fe* i_end, vdf_fe* out);
 /* The same for `lanes` chains at once (vdf_nova.h VDF_CIRCUIT_MINROOT_FORWARD_LANES), ONE launch: lane l's trace starts
  * lane_stride entries of 64 B after lane l - 1's (lane_stride >= t + 1: the layout vdf_minroot_inverse_walk's groups and
@@ -415,7 +416,8 @@ int  vdf_nifs_cross_term_minroot(vdf_ctx* ctx, int field, int vars_per_round, ui
  *   row 3j + 2  tmp2 * x' = x_j + y_j   (j = 0: z_in.x + z_in.y; j >= 1: x_j + x_(j-1) + i + (j - 1) * one);
  *   row 3t      final_i * one = i + t * one.
  * Operands and guarantees as vdf_nifs_cross_term_minroot (exact for any z2; the caller answers for the rows being this
- * stencil).  libvdf_nova.so reports this stencil as code 5 (vdf_nova_pp_stencil). */
+ * stencil).  libvdf_nova.so reports this stencil as code 5 (vdf_nova_pp_stencil).  This is
+ * vdf_nifs_cross_term_minroot_forward_lanes with lanes = 1: the same checks, the same launch. */
 int  vdf_nifs_cross_term_minroot_forward(vdf_ctx* ctx, int field, uint64_t t, size_t seg_begin, size_t one_col, size_t row_begin,
                                          const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1, const vdf_fe* u1,
                                          vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T);
@@ -423,7 +425,7 @@ int  vdf_nifs_cross_term_minroot_forward(vdf_ctx* ctx, int field, uint64_t t, si
  * seg_begin + l (3t + 1) .. + 3t (x', tmp1, tmp2 per round, then final_i), its rows row_begin + l (3t + 1) .., and ITS
  * z_in = (x_0, y_0, i) sits at seg_begin - 3 lanes + 3 l .. + 2, where the single-lane stencil reads seg_begin - 3 .. - 1.
  * Operands and guarantees as vdf_nifs_cross_term_minroot_forward (exact for any z2, a `one` that is not 1 included).
- * libvdf_nova.so reports this stencil as code 6 (vdf_nova_pp_stencil). */
+ * libvdf_nova.so reports this stencil as code 6 (vdf_nova_pp_stencil), and as code 5 when it runs one lane. */
 int  vdf_nifs_cross_term_minroot_forward_lanes(vdf_ctx* ctx, int field, uint64_t t, size_t lanes, size_t seg_begin, size_t one_col,
                                                size_t row_begin, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,
                                                const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T);

@@ -16,7 +16,7 @@ import vdf_amd
 from oracle import nova as nv, pasta as o
 from forward_spec import ForwardMinRootCircuit, chain, oracle_pp
 from test_gpu_nova import aff_ints, check_instance, _canon
-from util import dev, host, limbs, mont, unmont, rand_limbs
+from util import dev, forward_segment_expected, host, limbs, mont, unmont, rand_limbs
 from vdf_amd._lib import lib
 from vdf_amd.hip import VdfError
 from vdf_amd.minroot import EvalMode, PallasVDF, State, FIELD_FQ
@@ -59,18 +59,12 @@ def test_forward_segment(ctx, cref, field, t):
     """vdf_minroot_forward_segment: x_(j+1), its square and its fourth power per round from the forward trace, then final_i --
     against the C restatement (its evaluator's trace, its field multiplication), for the small sizes over Fq also against the
     witness the specification circuit allocates on the oracle's CS; the fill around the output survives."""
-    L, m = cref.lib(), o.modulus(field)
+    m = o.modulus(field)
     st = mont([o.rand_fe(50 + t, 0, m), o.rand_fe(50 + t, 1, m), 9], m)
-    so, tr = cref.fe_array(3), cref.fe_array(2 * (t + 1))
-    L.ref_minroot_eval(field, 1, cref.p(st), t, cref.p(so), cref.p(tr))
-    xs = np.ascontiguousarray(tr.reshape(t + 1, 2, 4)[1:, 0, :])
-    sq, qd = cref.fe_array(t), cref.fe_array(t)
-    L.ref_fe_mul(field, cref.p(xs), cref.p(xs), t, cref.p(sq))
-    L.ref_fe_mul(field, cref.p(sq), cref.p(sq), t, cref.p(qd))
-    want = np.concatenate([np.stack([xs, sq, qd], axis=1).reshape(3 * t, 4), so[2:3]])
+    tr, i_end, want = forward_segment_expected(cref, field, st, t)
     pad = 7
     buf = dev(np.full((3 * t + 1 + 2 * pad, 4), FILL, dtype="<u8"))
-    ctx.minroot_forward_segment(field, dev(tr), t, so[2:3].copy(), buf[pad:])
+    ctx.minroot_forward_segment(field, dev(tr), t, i_end.copy(), buf[pad:])
     ctx.sync()
     got = host(buf)
     assert np.array_equal(got[pad:pad + 3 * t + 1], want)
@@ -82,9 +76,9 @@ def test_forward_segment(ctx, cref, field, t):
         ForwardMinRootCircuit(t, s0, o.minroot_eval(s0, t, field)).synthesize(cs, z)
         assert unmont(got[pad:pad + 3 * t + 1], m) == cs.W
     with pytest.raises(VdfError):
-        ctx.minroot_forward_segment(field, dev(tr), t, dev(so[2:3]), buf[pad:])          # i_end is a host operand
+        ctx.minroot_forward_segment(field, dev(tr), t, dev(i_end), buf[pad:])            # i_end is a host operand
     with pytest.raises(VdfError):
-        ctx.minroot_forward_segment(field, tr, t, so[2:3].copy(), buf[pad:])             # the trace is a device operand
+        ctx.minroot_forward_segment(field, tr, t, i_end.copy(), buf[pad:])               # the trace is a device operand
 
 
 def spec_shape(t, before=2, after=3):

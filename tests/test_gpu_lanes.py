@@ -15,11 +15,11 @@ import vdf_amd
 from oracle import nova as nv, pasta as o
 from lanes_spec import LanesForwardCircuit, chains, flat, oracle_pp
 from test_gpu_nova import aff_ints, check_instance, _canon
-from util import dev, host, limbs, mont, unmont, rand_limbs, states_array
+from util import dev, forward_segment_expected, host, limbs, mont, unmont, rand_limbs, states_array
 from vdf_amd._lib import lib
 from vdf_amd.hip import VdfError
 from vdf_amd.minroot import EvalMode, PallasVDF, State, FIELD_FQ
-from vdf_amd.nova import (CIRCUIT_MINROOT_BOUND, CIRCUIT_MINROOT_FORWARD, CIRCUIT_MINROOT_FORWARD_LANES, STENCIL_FORWARD_LANES,
+from vdf_amd.nova import (CIRCUIT_MINROOT_BOUND, CIRCUIT_MINROOT_FORWARD, CIRCUIT_MINROOT_FORWARD_LANES, STENCIL_FORWARD, STENCIL_FORWARD_LANES,
                           GENS_KNOWN_DLOG, GENS_TRY_AND_INCREMENT, PP_NO_DIGIT_TABLES, INST_RUNNING_PRIMARY, INST_RUNNING_SECONDARY,
                           INST_FRESH_SECONDARY, INST_FRESH_PRIMARY_LAST, CompressedNovaVDFProof, ForwardCircuits, InverseMinRootCircuit,
                           LaneCircuits, NovaVDFProof, compress_batch, public_params, public_params_lanes, shape_digest_lanes,
@@ -78,18 +78,21 @@ def traces_chain(t, inits, traces):
 @pytest.mark.parametrize("field", [o.FIELD_FP, o.FIELD_FQ])
 @pytest.mark.parametrize("L,t", [(1, 1), (2, 1), (3, 5), (3, 21), (2, 22), (4, 257)])
 def test_segment_in_lanes_equals_the_single_lane_calls(ctx, cref, field, L, t):
-    """vdf_minroot_forward_segment_lanes against L calls of vdf_minroot_forward_segment, byte for byte, with the lanes' traces
-    t + 1 and t + 3 entries apart (3t + 1 = 64 at t = 21 and 67 at t = 22: lanes end on and across a wavefront); the words
-    around the output survive."""
-    ref, m = cref.lib(), o.modulus(field)
+    """vdf_minroot_forward_segment_lanes against the C restatement (its evaluator's traces, its field multiplication twice, the
+    end counters: what test_gpu_forward.py::test_forward_segment expects of one lane) and against L calls of
+    vdf_minroot_forward_segment -- one launch of L lanes against L launches of one, which is the lanes' offsets and strides --
+    byte for byte, with the lanes' traces t + 1 and t + 3 entries apart (3t + 1 = 64 at t = 21 and 67 at t = 22: lanes end on and
+    across a wavefront); the words around the output survive."""
+    m = o.modulus(field)
     per, pad = 3 * t + 1, 7
-    trs, ends = [], cref.fe_array(L)
+    trs, ends, expected = [], cref.fe_array(L), []
     for l in range(L):
         st = mont([o.rand_fe(900 + t, 2 * l, m), o.rand_fe(900 + t, 2 * l + 1, m), 9 + 1000 * l], m)
-        so, tr = cref.fe_array(3), cref.fe_array(2 * (t + 1))
-        ref.ref_minroot_eval(field, 1, cref.p(st), t, cref.p(so), cref.p(tr))
+        tr, i_end, words = forward_segment_expected(cref, field, st, t)
         trs.append(tr)
-        ends[l] = so[2]
+        ends[l] = i_end[0]
+        expected.append(words)
+    expected = np.concatenate(expected)
     want = []
     for l in range(L):
         one = dev(np.full((per, 4), FILL, dtype="<u8"))
@@ -97,6 +100,7 @@ def test_segment_in_lanes_equals_the_single_lane_calls(ctx, cref, field, L, t):
         want.append(one)
     ctx.sync()
     want = np.concatenate([host(w) for w in want])
+    assert np.array_equal(want, expected)
     for stride in (t + 1, t + 3):
         buf = np.full((L * stride * 2, 4), FILL, dtype="<u8")
         for l in range(L):
@@ -105,6 +109,7 @@ def test_segment_in_lanes_equals_the_single_lane_calls(ctx, cref, field, L, t):
         ctx.minroot_forward_segment_lanes(field, dev(buf), stride, t, L, ends.copy(), out[pad:])
         ctx.sync()
         got = host(out)
+        assert np.array_equal(got[pad:pad + L * per], expected), stride
         assert np.array_equal(got[pad:pad + L * per], want), stride
         assert np.all(got[:pad] == FILL) and np.all(got[pad + L * per:] == FILL), stride
     d_tr, out = dev(buf), dev(np.zeros((L * per, 4), dtype="<u8"))
@@ -120,14 +125,16 @@ def test_segment_in_lanes_equals_the_single_lane_calls(ctx, cref, field, L, t):
         ctx.minroot_forward_segment_lanes(field, buf, t + 3, t, L, ends.copy(), out)           # the trace is a device operand
 
 
-@pytest.mark.parametrize("L,t", [(2, 1), (2, 2), (3, 3), (3, 21), (2, 22), (4, 64)])
+@pytest.mark.parametrize("L,t", [(1, 1), (1, 2), (1, 22), (2, 1), (2, 2), (3, 3), (3, 21), (2, 22), (4, 64)])
 def test_stencil_in_lanes_equals_the_sparse_kernel(ctx, L, t):
     """vdf_nifs_cross_term_minroot_forward_lanes against vdf_nifs_cross_term_rows(.., VDF_ROWS_INSIDE) over the shape the
     parameters themselves are made of (its digest is the oracle's: tests/test_lanes_host.py): the same random z2 (constant
-    column random, then ONE), random running vectors; A z2, B z2, C z2 and T equal, every row outside the range untouched."""
+    column random, then ONE), random running vectors; A z2, B z2, C z2 and T equal, every row outside the range untouched.
+    L = 1 is the single chain through the same entry point (stencil code 5): at t = 1, 2 its j = 0, 1 rows, which read z_in, are
+    most or all of it, and at t = 22 it ends across a wavefront."""
     field, m = o.FIELD_FQ, o.Q
     code, row0, nr, S = shape_stencil_lanes(t, L)
-    assert code == STENCIL_FORWARD_LANES and nr == L * (3 * t + 1)
+    assert code == (STENCIL_FORWARD if L == 1 else STENCIL_FORWARD_LANES) and nr == L * (3 * t + 1)
     mats = shape_export_lanes(t, L, 0)
     nc, nvars = shape_digest_lanes(t, L, 1)[1][0][:2]
     ncols = nvars + 3                                               # z = (W, u, X)

@@ -240,6 +240,41 @@ def test_growing_chains_check_every_lane():
             vn.LaneCircuits.begin(t, [inits[0]] * lanes)
 
 
+@pytest.mark.parametrize("every", [None, 2, 4])
+def test_a_forward_chain_and_a_chain_of_one_lane_are_the_same_chain(every):
+    """Two steps at t = 4 pushed through the single-lane calls and through the lanes calls with one lane -- as traces
+    (every = None) or as checkpoints every 2 and every 4 rounds: the same z0, the same states and lane-0 states of every step,
+    and no lane 1 on either."""
+    t, n = 4, 2
+    v = PallasVDF.new()
+    init = State.from_ints(o.FIELD_FQ, 0x4321, 0, 11)
+    z0f, fc = vn.ForwardCircuits.begin(t, init)
+    z0l, lc = vn.LaneCircuits.begin(t, [init])
+    assert z0f == z0l == [init.x, init.y, init.i]
+    want, s = [], init
+    for _ in range(n):
+        if every is None:
+            nxt, tr = v.eval_with_trace(s, t)
+            fc.push_trace(tr)
+            lc.push_traces([tr])
+        else:
+            cps = v.eval_checkpoints(s, t, every)
+            nxt = cps[-1]
+            fc.push_checkpoints(every, cps)
+            lc.push_checkpoints(every, [cps])
+        want.append((nxt, s))
+        s = nxt
+    assert len(fc) == len(lc) == n and fc.host_bytes() == lc.host_bytes()
+    lane_states = vn.LaneCircuits.lane_states                # (ForwardCircuits has no method for it: the call is the handle's)
+    for k in range(n):
+        assert fc.states(k) == lc.states(k) == want[k]
+        assert lane_states(fc, k, 0) == lane_states(lc, k, 0) == want[k]
+        for c in (fc, lc):
+            with pytest.raises(vdf_amd.VdfError):
+                lane_states(c, k, 1)
+    fc.free(); lc.free()
+
+
 def test_every_root_of_every_lane_is_bound():
     """Soundness on the oracle's CS at L = 3, t = 4: the step circuit alone, satisfied by the honest witness, is violated by a
     change to ANY x_(j+1) of ANY lane, also when the prover recomputes the powers that depend on it."""

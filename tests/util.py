@@ -81,6 +81,20 @@ def mont_states(rows, m):
     return np.frombuffer(b"".join(int(o.to_mont(v, m)).to_bytes(32, "little") for r in rows for v in r), dtype="<u8").reshape(-1, 12).copy()
 
 
+def forward_segment_expected(cref, field, st, t):
+    """What vdf_minroot_forward_segment must write for the chain that starts at `st` (uint64[3, 4], Montgomery), by the C
+    restatement alone: (trace uint64[2 (t + 1), 4], i_end uint64[1, 4], words uint64[3t + 1, 4]) -- per round x_(j+1) from its
+    evaluator's trace, its square and fourth power by ref_fe_mul twice, then the end counter."""
+    L = cref.lib()
+    so, tr = cref.fe_array(3), cref.fe_array(2 * (t + 1))
+    L.ref_minroot_eval(field, 1, cref.p(st), t, cref.p(so), cref.p(tr))
+    xs = np.ascontiguousarray(tr.reshape(t + 1, 2, 4)[1:, 0, :])
+    sq, qd = cref.fe_array(t), cref.fe_array(t)
+    L.ref_fe_mul(field, cref.p(xs), cref.p(xs), t, cref.p(sq))
+    L.ref_fe_mul(field, cref.p(sq), cref.p(sq), t, cref.p(qd))
+    return tr, so[2:3].copy(), np.concatenate([np.stack([xs, sq, qd], axis=1).reshape(3 * t, 4), so[2:3]])
+
+
 def host_trace(vdf, s0, t):
     """(result, uint64[t + 1, 8]) of vdf_minroot_eval with its trace"""
     import ctypes as C

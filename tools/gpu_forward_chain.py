@@ -10,6 +10,8 @@
       128-step chain: prove_recursively (BOUND) after the evaluation, traces resident.
   (4) the evaluator must not pay for its prover: eval_ms of eval_and_prove (32 steps) against plain vdf_minroot_eval of the same
       rounds, three times each.
+  --forward-only: the forward leg of (1) alone -- `--steps` steps, `--repeats` timed runs after one warm-up, the step time at the
+      median -- and nothing else: the figure to compare between two builds of the library, run alternately.
   --kernels-only: (2) a short chain of each kind with per-launch HIP events on, printing the time and the TB/s of
       k_nifs_cross_minroot_forward (timed under the label k_nifs_cross_fwd) and k_nifs_cross_minroot (3 variables per round); run it under
       `rocprofv3 --kernel-trace --stats -- python tools/gpu_forward_chain.py --kernels-only` for the profiler's own figures.
@@ -31,6 +33,7 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--kernels-only", action="store_true")
+    ap.add_argument("--forward-only", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_forward_chain.txt"))
     a = ap.parse_args()
     import vdf_amd
@@ -87,12 +90,13 @@ def main():
         return
 
     # ---- (1) step rate ---------------------------------------------------------------------------------------------
-    n = max(a.steps, 128)                                  # (3) reads the first 128 steps of the same chain
+    n = a.steps if a.forward_only else max(a.steps, 128)   # (3) reads the first 128 steps of the same chain
     states, ev, (z0f, fc), (z0b, bc) = chains(n)
     out("(1) %d steps; host evaluation %.1f s (set-up); traces resident: forward %s, bound %s" % (n, ev, fc.memory(), bc.memory()))
     rates = {"forward": [], "bound": []}
+    legs = (("forward", ppf, z0f, fc), ("bound", ppb, z0b, bc))[:1 if a.forward_only else 2]
     for rep in range(a.repeats + 1):                       # one warm-up alternation
-        for name, pp, z0, cs in (("forward", ppf, z0f, fc), ("bound", ppb, z0b, bc)):
+        for name, pp, z0, cs in legs:
             t0 = time.perf_counter()
             p = NovaVDFProof.prove_recursively(pp, cs, t, z0)
             dt = time.perf_counter() - t0
@@ -102,10 +106,13 @@ def main():
             else:
                 rates[name].append(n / dt)
             p.free()
-    for name in ("forward", "bound"):
+    for name, *_ in legs:
         r = rates[name]
         out("    %-8s prove_step/s: %s  median %.1f  min %.1f  max %.1f  (%.4f ms per step at the median)" % (
             name, " ".join("%.1f" % x for x in r), statistics.median(r), min(r), max(r), 1e3 / statistics.median(r)))
+    if a.forward_only:
+        fc.free(); bc.free(); ppf.free(); ppb.free(); ctx.close()
+        return
     fmed, bmin = statistics.median(rates["forward"]), min(rates["bound"])
     out("    target (forward median >= bound's lowest run): %s (%.1f vs %.1f)" % ("met" if fmed >= bmin else "NOT met", fmed, bmin))
     step_ms = 1e3 / fmed

@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Measurements of the forward step circuit in lanes on one MI355X (output: profiles/r09_lanes.txt by default), profiler off.
 
-  --kernels-only   (a) both lanes kernels at (L, t) = (8, 8192) and (16, 4096) against the single-lane kernels at t = 2^16: the
-                   same bytes moved.  Five timed runs each in ONE process (per-launch HIP events of the library), after one
-                   warm-up.  Target: the lanes kernel's median does not exceed the single-lane kernel's slowest run.  Run it
+  --kernels-only   (a) both lanes kernels at (L, t) = (8, 8192) and (16, 4096) against the single-lane entry points at t = 2^16:
+                   the same bytes moved.  Five timed runs each in ONE process (per-launch HIP events of the library), after one
+                   warm-up.  Target: the lanes kernel's median does not exceed the single-lane kernel's slowest run.  Beside
+                   the L = 1 row through the single-lane entry points, one through the lanes entry points with one lane: in a
+                   library that still has single-lane kernels of its own that is what routing one lane through the lanes
+                   kernels costs (both medians, and the single-lane runs' own spread); since the single-lane entry points ARE
+                   the lanes kernels with one lane, the two rows time the same launch.  Run it
                    under `rocprofv3 --kernel-trace --stats -- python tools/gpu_lanes_chain.py --kernels-only` for the
                    profiler's own figures (a run of its own: output profiles/r09_lanes_kernels.txt).
   (b) step rate:   prove_step/s for L = 4, 8, 16 at L t = 2^16 against VDF_CIRCUIT_MINROOT_FORWARD at t = 2^16, `--steps` steps,
@@ -89,7 +93,7 @@ def main():
         T = 1 << 16
         u1 = np.ones((1, 4), dtype="<u8")
         runs = {}
-        for L, t in ((1, T), (8, T // 8), (16, T // 16)):
+        for L, t, single in ((1, T, True), (1, T, False), (8, T // 8, False), (16, T // 16, False)):
             per = 3 * t + 1
             S, nvars = 3 * L + 5, 3 * L + 5 + L * per + 7
             nc, row0 = L * per + 9, 4
@@ -101,7 +105,7 @@ def main():
             outs = [rand(nc) for _ in range(4)]
             ctx.set_kernel_timing(True)
             for rep in range(6):
-                if L == 1:
+                if single:
                     ctx.minroot_forward_segment(FIELD_FQ, trace, t, ends, seg)
                     ctx.nifs_cross_term_minroot_forward(FIELD_FQ, t, S, nvars, row0, z2, *abc1, u1, *outs)
                 else:
@@ -113,14 +117,16 @@ def main():
             for kind in ("k_forward_segment", "k_nifs_cross_fwd"):
                 ms = [e[3] - e[2] for e in ev if e[0].startswith(kind)][1:]          # the first run is the warm-up
                 byt = [e[1] for e in ev if e[0].startswith(kind)][0]
-                runs[(kind, L)] = ms
-                out("(a) %-18s L = %2d t = %5d  runs (ms) %s  median %.4f  min %.4f  max %.4f  algorithmic bytes %.0f  TB/s at the median %.3f" % (
-                    kind, L, t, " ".join("%.4f" % x for x in ms), statistics.median(ms), min(ms), max(ms), byt,
+                runs[(kind, L, single)] = ms
+                out("(a) %-18s %s L = %2d t = %5d  runs (ms) %s  median %.4f  min %.4f  max %.4f  algorithmic bytes %.0f  TB/s at the median %.3f" % (
+                    kind, "single-lane entry" if single else "lanes entry      ", L, t, " ".join("%.4f" % x for x in ms), statistics.median(ms), min(ms), max(ms), byt,
                     byt / (statistics.median(ms) * 1e-3) / 1e12))
         for kind in ("k_forward_segment", "k_nifs_cross_fwd"):
-            slow = max(runs[(kind, 1)])
+            one, slow = runs[(kind, 1, True)], max(runs[(kind, 1, True)])
+            out("    %-18s L =  1: median %.4f ms through the single-lane entry (spread of its runs, max - min: %.4f ms), %.4f ms through the lanes entry" % (
+                kind, statistics.median(one), slow - min(one), statistics.median(runs[(kind, 1, False)])))
             for L in (8, 16):
-                med = statistics.median(runs[(kind, L)])
+                med = statistics.median(runs[(kind, L, False)])
                 out("    %-18s L = %2d: median %.4f ms against the single-lane kernel's slowest run %.4f ms: %s" % (
                     kind, L, med, slow, "met" if med <= slow else "NOT met, by %.1f %%" % (100 * (med / slow - 1))))
         ctx.close()

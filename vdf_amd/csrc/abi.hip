@@ -1473,16 +1473,9 @@ int vdf_minroot_step_segment_packed(vdf_ctx* ctx, int field, const vdf_fe* trace
   });
 }
 
+// one chain is one lane: the same checks in the same order, the same launch
 int vdf_minroot_forward_segment(vdf_ctx* ctx, int field, const vdf_fe* trace_xy, uint64_t t, const vdf_fe* i_end, vdf_fe* out) {
-  return guarded(ctx, [&]() -> Status {
-    if (t == 0 || t >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
-    if (!i_end || ptr_is_device(i_end)) return Status{VDF_ERR_BAD_ARG, "scalar operands of fused calls live in host memory"};
-    if (!ptr_is_device(trace_xy) || !ptr_is_device(out))
-      return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
-    VDF_TRY(vdf::vec_forward_segment(field, trace_xy, t, i_end, out, ctx->stream));
-    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
-    return Status{};
-  });
+  return vdf_minroot_forward_segment_lanes(ctx, field, trace_xy, (size_t)t + 1, t, 1, i_end, out);
 }
 
 int vdf_minroot_forward_segment_lanes(vdf_ctx* ctx, int field, const vdf_fe* trace_xy, size_t lane_stride, uint64_t t, size_t lanes,
@@ -1578,18 +1571,7 @@ int vdf_nifs_cross_term_minroot(vdf_ctx* ctx, int field, int vars_per_round, uin
 int vdf_nifs_cross_term_minroot_forward(vdf_ctx* ctx, int field, uint64_t t, size_t seg_begin, size_t one_col, size_t row_begin,
                                         const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1, const vdf_fe* u1,
                                         vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T) {
-  return guarded(ctx, [&]() -> Status {
-    if (!z2 || !Az1 || !Bz1 || !Cz1 || !u1 || !Az2 || !Bz2 || !Cz2 || !T) return Status{VDF_ERR_BAD_ARG, "null argument"};
-    if (ptr_is_device(u1)) return Status{VDF_ERR_BAD_ARG, "scalar operands of fused calls live in host memory"};
-    for (const void* v : {(const void*)z2, (const void*)Az1, (const void*)Bz1, (const void*)Cz1, (const void*)Az2, (const void*)Bz2,
-                          (const void*)Cz2, (const void*)T})
-      if (!ptr_is_device(v)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
-    if (t == 0 || t > (1ull << 26)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
-    if (seg_begin < 3 || one_col < seg_begin + (size_t)3 * t + 1) return Status{VDF_ERR_BAD_ARG, "the constant's column lies behind the rounds"};
-    VDF_TRY(vdf::vec_nifs_cross_minroot_forward(field, t, seg_begin, one_col, row_begin, z2, Az1, Bz1, Cz1, u1, Az2, Bz2, Cz2, T, ctx->stream));
-    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
-    return Status{};
-  });
+  return vdf_nifs_cross_term_minroot_forward_lanes(ctx, field, t, 1, seg_begin, one_col, row_begin, z2, Az1, Bz1, Cz1, u1, Az2, Bz2, Cz2, T);
 }
 
 int vdf_nifs_cross_term_minroot_forward_lanes(vdf_ctx* ctx, int field, uint64_t t, size_t lanes, size_t seg_begin, size_t one_col,

@@ -26,6 +26,66 @@ Circuit checkpoint_circuit(uint64_t t, uint64_t every, const vdf_state* states, 
   c.input = c.cp.front(); c.result = c.cp.back();
   return c;
 }
+// ---- forward chains: a step pushed for all `lanes` lanes of the chain (a single chain: one) ----------------------------------
+// a refusal about lane l: "lane 2: ... the lane's current end" in a chain of lanes, "... the chain's current end" in a single one
+std::string lane_tag(const vdf_circuits* c, size_t l) { return c->lanes > 1 ? "lane " + std::to_string(l) + ": " : std::string(); }
+const char* lane_owner(const vdf_circuits* c) { return c->lanes > 1 ? "lane's" : "chain's"; }
+// the step every lane ends: appended, and the chain stands where it ends
+void push_step(vdf_circuits* c, Circuit&& cc) {
+  cc.input = cc.lane_input[0]; cc.result = cc.lane_result[0];
+  c->lane_end = cc.lane_result;
+  c->end = cc.result;
+  c->v.push_back(std::move(cc));
+}
+int push_traces(vdf_circuits* c, const vdf_fe* trace_xy, size_t lane_stride) {
+  const uint64_t t = c->forward_t;
+  const size_t L = c->lanes;
+  if (lane_stride < t + 1) return fail(VDF_ERR_BAD_ARG, "lane_stride must be at least t + 1");
+  const Field& F = field(c->field);
+  Circuit cc;
+  cc.t = t;
+  cc.lane_input = c->lane_end;
+  cc.lane_result.resize(L);
+  for (size_t l = 0; l < L; ++l) {                                   // every lane checked before anything is appended
+    const vdf_fe* tr = trace_xy + 2 * l * lane_stride;
+    if (memcmp(&tr[0], &c->lane_end[l].x, 32) != 0 || memcmp(&tr[1], &c->lane_end[l].y, 32) != 0)
+      return fail(VDF_ERR_BAD_ARG, lane_tag(c, l) + "the trace does not start at the " + lane_owner(c) + " current end");
+    memcpy(&cc.lane_result[l].x, &tr[2 * t], 32);
+    memcpy(&cc.lane_result[l].y, &tr[2 * t + 1], 32);
+    cc.lane_result[l].i = add(c->lane_end[l].i, from_u64(t, F), F);
+  }
+  cc.trace_xy.reserve(L * 2 * (t + 1));
+  for (size_t l = 0; l < L; ++l) {
+    const Fe* tr = (const Fe*)trace_xy + 2 * l * lane_stride;
+    cc.trace_xy.insert(cc.trace_xy.end(), tr, tr + 2 * (t + 1));
+  }
+  push_step(c, std::move(cc));
+  return VDF_OK;
+}
+int push_checkpoints(vdf_circuits* c, uint64_t every, const vdf_state* states, size_t lane_stride) {
+  const uint64_t t = c->forward_t;
+  const size_t L = c->lanes;
+  if (every == 0 || t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
+  const size_t per = (size_t)(t / every);
+  if (lane_stride < per + 1) return fail(VDF_ERR_BAD_ARG, "lane_stride must be at least t / every + 1");
+  if (c->checkpoints)
+    for (const Circuit& k : c->v) if (k.every && k.every != every) return fail(VDF_ERR_BAD_ARG, "`every` differs from the chain's earlier checkpoint steps");
+  for (size_t l = 0; l < L; ++l) {                                   // every lane checked before anything is appended
+    const vdf_state* st = states + l * lane_stride;
+    if (memcmp(&st[0], &c->lane_end[l], 96) != 0) return fail(VDF_ERR_BAD_ARG, lane_tag(c, l) + "states[0] is not the " + lane_owner(c) + " current end");
+    if (check_counters(c->field, st, per, c->lane_end[l].i, every) != VDF_OK) return fail(VDF_ERR_BAD_ARG, lane_tag(c, l) + vdf_nova_last_error());
+  }
+  Circuit cc;
+  cc.t = t; cc.every = every;
+  cc.lane_input = c->lane_end;
+  cc.cp.reserve(L * (per + 1));
+  for (size_t l = 0; l < L; ++l)
+    for (size_t m = 0; m <= per; ++m) cc.cp.push_back(load_state(&states[l * lane_stride + m]));
+  for (size_t l = 0; l < L; ++l) cc.lane_result.push_back(cc.cp[l * (per + 1) + per]);
+  push_step(c, std::move(cc));
+  c->checkpoints = true;
+  return VDF_OK;
+}
 // ---- checkpoint circuits: traces by inverse walks ----------------------------------------------------------------
 // rounds per launch of the walks: a launch of 1,024 rounds holds a queue for about a millisecond
 uint64_t walk_launch_rounds() {
@@ -194,67 +254,18 @@ int vdf_nova_circuits_from_checkpoints_field(int fid, uint64_t t, uint64_t every
   });
 }
 
-// ---- forward chains: circuits in the order of evaluation, appended to while the chain grows -------------------------
+// ---- forward chains: circuits in the order of evaluation, appended to while the chain grows.  A step advances `lanes`
+// evaluations, and its trace is their traces back to back; a single chain is the chain of one lane, whose lane_stride is implied.
 int vdf_nova_circuits_forward_begin(uint64_t t, const vdf_state* initial_state, vdf_fe z0_primary[3], vdf_circuits** out) {
-  return vdf_nova_circuits_forward_begin_field(VDF_FIELD_FQ, t, initial_state, z0_primary, out);
+  return vdf_nova_circuits_lanes_begin_field(VDF_FIELD_FQ, t, 1, initial_state, z0_primary, out);
 }
 int vdf_nova_circuits_forward_begin_field(int fid, uint64_t t, const vdf_state* initial_state, vdf_fe z0_primary[3], vdf_circuits** out) {
-  return nova_guard([&]() -> int {
-    if (!valid_field(fid) || !initial_state || !z0_primary || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
-    std::unique_ptr<vdf_circuits> cs(new vdf_circuits());
-    cs->field = fid;
-    cs->forward = true;
-    cs->forward_t = t;
-    cs->end = load_state(initial_state);
-    memcpy(z0_primary, initial_state, 96);                             // z0 = the chain's initial state
-    *out = cs.release();
-    return VDF_OK;
-  });
+  return vdf_nova_circuits_lanes_begin_field(fid, t, 1, initial_state, z0_primary, out);
 }
-int vdf_nova_circuits_push_trace(vdf_circuits* c, const vdf_fe* trace_xy) {
-  return nova_guard([&]() -> int {
-    if (!c || !trace_xy) return fail(VDF_ERR_BAD_ARG, "null argument");
-    if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_forward_begin)");
-    if (c->lanes > 1) return fail(VDF_ERR_BAD_ARG, "a chain of more than one lane: vdf_nova_circuits_push_traces");
-    const uint64_t t = c->forward_t;
-    if (memcmp(&trace_xy[0], &c->end.x, 32) != 0 || memcmp(&trace_xy[1], &c->end.y, 32) != 0)
-      return fail(VDF_ERR_BAD_ARG, "the trace does not start at the chain's current end");
-    Circuit cc;
-    cc.t = t;
-    cc.input = c->end;
-    memcpy(&cc.result.x, &trace_xy[2 * t], 32);
-    memcpy(&cc.result.y, &trace_xy[2 * t + 1], 32);
-    cc.result.i = add(c->end.i, from_u64(t, field(c->field)), field(c->field));
-    cc.trace_xy.assign((const Fe*)trace_xy, (const Fe*)trace_xy + 2 * (t + 1));
-    c->end = cc.result;
-    c->v.push_back(std::move(cc));
-    return VDF_OK;
-  });
-}
-int vdf_nova_circuits_push_checkpoints(vdf_circuits* c, uint64_t every, const vdf_state* states) {
-  return nova_guard([&]() -> int {
-    if (!c || !states) return fail(VDF_ERR_BAD_ARG, "null argument");
-    if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_forward_begin)");
-    if (c->lanes > 1) return fail(VDF_ERR_BAD_ARG, "a chain of more than one lane: vdf_nova_circuits_push_checkpoints_lanes");
-    const uint64_t t = c->forward_t;
-    if (every == 0 || t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
-    if (!c->v.empty() && c->checkpoints)
-      for (const Circuit& k : c->v) if (k.every && k.every != every) return fail(VDF_ERR_BAD_ARG, "`every` differs from the chain's earlier checkpoint steps");
-    if (memcmp(&states[0], &c->end, 96) != 0) return fail(VDF_ERR_BAD_ARG, "states[0] is not the chain's current end");
-    const size_t per = (size_t)(t / every);
-    { int rc = check_counters(c->field, states, per, c->end.i, every); if (rc != VDF_OK) return rc; }
-    c->v.push_back(checkpoint_circuit(t, every, states, per));
-    c->end = c->v.back().result;
-    c->checkpoints = true;
-    return VDF_OK;
-  });
-}
-// ---- forward chains in lanes: a step advances `lanes` evaluations, its trace is their traces back to back ------------------
 int vdf_nova_circuits_lanes_begin(uint64_t t, size_t lanes, const vdf_state* initial, vdf_fe* z0_primary, vdf_circuits** out) {
   return vdf_nova_circuits_lanes_begin_field(VDF_FIELD_FQ, t, lanes, initial, z0_primary, out);
 }
 int vdf_nova_circuits_lanes_begin_field(int fid, uint64_t t, size_t lanes, const vdf_state* initial, vdf_fe* z0_primary, vdf_circuits** out) {
-  if (lanes == 1) return vdf_nova_circuits_forward_begin_field(fid, t, initial, z0_primary, out);     // one lane IS a forward chain
   return nova_guard([&]() -> int {
     if (!valid_field(fid) || !initial || !z0_primary || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
     if (lanes == 0 || lanes > VDF_NOVA_MAX_LANES) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_NOVA_MAX_LANES");
@@ -270,69 +281,34 @@ int vdf_nova_circuits_lanes_begin_field(int fid, uint64_t t, size_t lanes, const
     return VDF_OK;
   });
 }
+int vdf_nova_circuits_push_trace(vdf_circuits* c, const vdf_fe* trace_xy) {
+  return nova_guard([&]() -> int {
+    if (!c || !trace_xy) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_forward_begin)");
+    if (c->lanes > 1) return fail(VDF_ERR_BAD_ARG, "a chain of more than one lane: vdf_nova_circuits_push_traces");
+    return push_traces(c, trace_xy, (size_t)c->forward_t + 1);
+  });
+}
 int vdf_nova_circuits_push_traces(vdf_circuits* c, const vdf_fe* trace_xy, size_t lane_stride) {
-  if (c && trace_xy && c->forward && c->lanes == 1) return vdf_nova_circuits_push_trace(c, trace_xy);
   return nova_guard([&]() -> int {
     if (!c || !trace_xy) return fail(VDF_ERR_BAD_ARG, "null argument");
     if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_lanes_begin)");
-    const uint64_t t = c->forward_t;
-    const size_t L = c->lanes;
-    if (lane_stride < t + 1) return fail(VDF_ERR_BAD_ARG, "lane_stride must be at least t + 1");
-    const Field& F = field(c->field);
-    Circuit cc;
-    cc.t = t;
-    cc.lane_input = c->lane_end;
-    cc.lane_result.resize(L);
-    for (size_t l = 0; l < L; ++l) {                                   // every lane checked before anything is appended
-      const vdf_fe* tr = trace_xy + 2 * l * lane_stride;
-      if (memcmp(&tr[0], &c->lane_end[l].x, 32) != 0 || memcmp(&tr[1], &c->lane_end[l].y, 32) != 0)
-        return fail(VDF_ERR_BAD_ARG, "lane " + std::to_string(l) + ": the trace does not start at the lane's current end");
-      memcpy(&cc.lane_result[l].x, &tr[2 * t], 32);
-      memcpy(&cc.lane_result[l].y, &tr[2 * t + 1], 32);
-      cc.lane_result[l].i = add(c->lane_end[l].i, from_u64(t, F), F);
-    }
-    cc.trace_xy.reserve(L * 2 * (t + 1));
-    for (size_t l = 0; l < L; ++l) {
-      const Fe* tr = (const Fe*)trace_xy + 2 * l * lane_stride;
-      cc.trace_xy.insert(cc.trace_xy.end(), tr, tr + 2 * (t + 1));
-    }
-    cc.input = cc.lane_input[0]; cc.result = cc.lane_result[0];
-    c->lane_end = cc.lane_result;
-    c->end = cc.result;
-    c->v.push_back(std::move(cc));
-    return VDF_OK;
+    return push_traces(c, trace_xy, lane_stride);
+  });
+}
+int vdf_nova_circuits_push_checkpoints(vdf_circuits* c, uint64_t every, const vdf_state* states) {
+  return nova_guard([&]() -> int {
+    if (!c || !states) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_forward_begin)");
+    if (c->lanes > 1) return fail(VDF_ERR_BAD_ARG, "a chain of more than one lane: vdf_nova_circuits_push_checkpoints_lanes");
+    return push_checkpoints(c, every, states, (size_t)(every ? c->forward_t / every : 0) + 1);   // (a bad `every` is refused there)
   });
 }
 int vdf_nova_circuits_push_checkpoints_lanes(vdf_circuits* c, uint64_t every, const vdf_state* states, size_t lane_stride) {
-  if (c && states && c->forward && c->lanes == 1) return vdf_nova_circuits_push_checkpoints(c, every, states);
   return nova_guard([&]() -> int {
     if (!c || !states) return fail(VDF_ERR_BAD_ARG, "null argument");
     if (!c->forward) return fail(VDF_ERR_BAD_ARG, "not a forward chain (vdf_nova_circuits_lanes_begin)");
-    const uint64_t t = c->forward_t;
-    const size_t L = c->lanes;
-    if (every == 0 || t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
-    const size_t per = (size_t)(t / every);
-    if (lane_stride < per + 1) return fail(VDF_ERR_BAD_ARG, "lane_stride must be at least t / every + 1");
-    if (!c->v.empty() && c->checkpoints)
-      for (const Circuit& k : c->v) if (k.every && k.every != every) return fail(VDF_ERR_BAD_ARG, "`every` differs from the chain's earlier checkpoint steps");
-    for (size_t l = 0; l < L; ++l) {                                   // every lane checked before anything is appended
-      const vdf_state* st = states + l * lane_stride;
-      if (memcmp(&st[0], &c->lane_end[l], 96) != 0) return fail(VDF_ERR_BAD_ARG, "lane " + std::to_string(l) + ": states[0] is not the lane's current end");
-      if (check_counters(c->field, st, per, c->lane_end[l].i, every) != VDF_OK) return fail(VDF_ERR_BAD_ARG, "lane " + std::to_string(l) + ": " + vdf_nova_last_error());
-    }
-    Circuit cc;
-    cc.t = t; cc.every = every;
-    cc.lane_input = c->lane_end;
-    cc.cp.reserve(L * (per + 1));
-    for (size_t l = 0; l < L; ++l)
-      for (size_t m = 0; m <= per; ++m) cc.cp.push_back(load_state(&states[l * lane_stride + m]));
-    for (size_t l = 0; l < L; ++l) cc.lane_result.push_back(cc.cp[l * (per + 1) + per]);
-    cc.input = cc.lane_input[0]; cc.result = cc.lane_result[0];
-    c->lane_end = cc.lane_result;
-    c->end = cc.result;
-    c->v.push_back(std::move(cc));
-    c->checkpoints = true;
-    return VDF_OK;
+    return push_checkpoints(c, every, states, lane_stride);
   });
 }
 size_t vdf_nova_circuits_lanes(const vdf_circuits* c) { return c ? c->lanes : 0; }
@@ -341,8 +317,9 @@ int vdf_nova_circuit_lane_states(const vdf_circuits* c, size_t k, size_t lane, v
   if (!c || k >= c->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
   if (lane >= c->lanes) return fail(VDF_ERR_BAD_LENGTH, "lane out of range");
   const Circuit& cc = c->v[k];
-  if (result) store_state(result, c->lanes > 1 ? cc.lane_result[lane] : cc.result);
-  if (input) store_state(input, c->lanes > 1 ? cc.lane_input[lane] : cc.input);
+  const bool per_lane = !cc.lane_result.empty();                       // a forward chain's step; any other circuit is its own lane 0
+  if (result) store_state(result, per_lane ? cc.lane_result[lane] : cc.result);
+  if (input) store_state(input, per_lane ? cc.lane_input[lane] : cc.input);
   return VDF_OK;
 }
 // ---- traces on the device ---------------------------------------------------------------------------------------

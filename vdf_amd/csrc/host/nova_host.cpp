@@ -22,8 +22,11 @@ RelaxedInst to_relaxed(const Inst& in, const Field& own) {
   return r;
 }
 
+// the forward circuit, of one lane (pp->lanes = 1) or of more: steps in the order of evaluation, z_i = the lanes' inputs
+static bool forward_kind(int kind) { return kind == VDF_CIRCUIT_MINROOT_FORWARD || kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES; }
+
 std::unique_ptr<StepCircuit> make_primary_circuit(const vdf_pp* pp, const Circuit* c, bool device_rounds) {
-  if (pp->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES) {
+  if (forward_kind(pp->circuit_kind)) {                                 // a single chain is the circuit of one lane
     std::unique_ptr<LanesForwardCircuit> m(new LanesForwardCircuit());
     m->t = pp->t;
     m->device_rounds = device_rounds;
@@ -35,19 +38,6 @@ std::unique_ptr<StepCircuit> make_primary_circuit(const vdf_pp* pp, const Circui
         m->results[l] = MinRootState{c->lane_result[l].x, c->lane_result[l].y, c->lane_result[l].i};
         m->inputs[l] = MinRootState{c->lane_input[l].x, c->lane_input[l].y, c->lane_input[l].i};
       }
-    return std::unique_ptr<StepCircuit>(m.release());
-  }
-  if (pp->circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD) {
-    std::unique_ptr<ForwardMinRootCircuit> m(new ForwardMinRootCircuit());
-    m->t = pp->t;
-    m->device_rounds = device_rounds;
-    m->blank = c == nullptr;
-    if (c) {
-      m->result = MinRootState{c->result.x, c->result.y, c->result.i};
-      m->input = MinRootState{c->input.x, c->input.y, c->input.i};
-    } else {
-      m->result = m->input = MinRootState{zero(), zero(), zero()};
-    }
     return std::unique_ptr<StepCircuit>(m.release());
   }
   std::unique_ptr<InverseMinRootCircuit> m(new InverseMinRootCircuit());
@@ -141,11 +131,8 @@ namespace {
 bool builtin_circuit(int kind) {
   return kind == VDF_CIRCUIT_MINROOT_BOUND || kind == VDF_CIRCUIT_MINROOT_REFERENCE || kind == VDF_CIRCUIT_MINROOT_FORWARD;
 }
-// the forward circuit, alone or in lanes: steps in the order of evaluation, z_i = the step's input
-bool forward_kind(int kind) { return kind == VDF_CIRCUIT_MINROOT_FORWARD || kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES; }
 static_assert(VDF_NOVA_MAX_LANES == VDF_MINROOT_MAX_LANES, "the lanes kernels take what the lanes circuit has");
 bool lanes_valid(size_t lanes) { return lanes >= 1 && lanes <= VDF_NOVA_MAX_LANES; }
-int lanes_kind(size_t lanes) { return lanes == 1 ? VDF_CIRCUIT_MINROOT_FORWARD : VDF_CIRCUIT_MINROOT_FORWARD_LANES; }
 // variables per round of a built-in circuit
 int vars_per_round(int kind) { return kind == VDF_CIRCUIT_MINROOT_REFERENCE ? 4 : 3; }
 
@@ -488,14 +475,9 @@ int vdf_nova_ro_hash_ro(const vdf_nova_ro_params* rop, int f, uint64_t tag, cons
 int vdf_nova_ro_hash(int f, uint64_t tag, const vdf_fe* xs, size_t n, vdf_fe* out) { return vdf_nova_ro_hash_ro(nullptr, f, tag, xs, n, out); }
 
 // One general form per entry point, in either orientation; the entry points of before are these at VDF_FIELD_FQ.
-// kind / lanes as the ABI gives them -> the kind the shapes are built for (lanes of 1 IS the forward circuit); false: refused
-static bool resolve_kind(int* circuit_kind, size_t lanes) {
-  if (*circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES) {
-    if (!lanes_valid(lanes)) return false;
-    *circuit_kind = lanes_kind(lanes);
-    return true;
-  }
-  return builtin_circuit(*circuit_kind) && lanes == 1;
+// kind / lanes as the ABI gives them: only VDF_CIRCUIT_MINROOT_FORWARD_LANES takes a lane count other than 1
+static bool kind_lanes_valid(int circuit_kind, size_t lanes) {
+  return circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES ? lanes_valid(lanes) : builtin_circuit(circuit_kind) && lanes == 1;
 }
 static int shape_digest_impl(int fid, const vdf_nova_ro_params* rop, uint64_t t, int circuit_kind, size_t lanes, int gens_family, uint8_t out[32],
                              uint64_t sizes[2][3]) {
@@ -518,7 +500,7 @@ static int shape_digest_impl(int fid, const vdf_nova_ro_params* rop, uint64_t t,
 int vdf_nova_shape_digest_field(int fid, const vdf_nova_ro_params* rop, uint64_t t, int circuit_kind, size_t lanes, int gens_family,
                                 uint8_t out[32], uint64_t sizes[2][3]) {
   if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "field must be VDF_FIELD_FP or VDF_FIELD_FQ");
-  if (!resolve_kind(&circuit_kind, lanes)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit, or lanes out of range for it");
+  if (!kind_lanes_valid(circuit_kind, lanes)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit, or lanes out of range for it");
   return shape_digest_impl(fid, rop, t, circuit_kind, lanes, gens_family, out, sizes);
 }
 int vdf_nova_shape_digest(uint64_t t, int circuit_kind, int gens_family, uint8_t out[32], uint64_t sizes[2][3]) {
@@ -553,7 +535,7 @@ static int shape_export_impl(int fid, uint64_t t, int circuit_kind, size_t lanes
 int vdf_nova_shape_export_field(int fid, uint64_t t, int circuit_kind, size_t lanes, int side, uint64_t nnz[3], uint32_t* const rows[3],
                                 uint32_t* const cols[3], vdf_fe* const vals[3]) {
   if (!valid_field(fid) || t == 0 || t > (1ull << 24) || !nnz || (side != PRIMARY && side != SECONDARY)) return fail(VDF_ERR_BAD_ARG, "bad argument");
-  if (!resolve_kind(&circuit_kind, lanes)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit, or lanes out of range for it");
+  if (!kind_lanes_valid(circuit_kind, lanes)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit, or lanes out of range for it");
   return shape_export_impl(fid, t, circuit_kind, lanes, side, nnz, rows, cols, vals);
 }
 int vdf_nova_shape_export(uint64_t t, int circuit_kind, int side, uint64_t nnz[3], uint32_t* const rows[3], uint32_t* const cols[3],
@@ -618,7 +600,7 @@ static int aug_synthesize_impl(int fid, const vdf_nova_ro_params* rop, int side,
       if (!results || !inputs) return fail(VDF_ERR_BAD_ARG, "the primary circuit needs the step's states");
       if (lanes > 1 && (!z0 || !zi)) return fail(VDF_ERR_BAD_ARG, "a circuit of more than one lane needs z0 and zi");
       c.result = load_state(&results[0]); c.input = load_state(&inputs[0]); c.t = t;
-      if (circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES)
+      if (forward_kind(circuit_kind))
         for (size_t l = 0; l < lanes; ++l) { c.lane_result.push_back(load_state(&results[l])); c.lane_input.push_back(load_state(&inputs[l])); }
       step = make_primary_circuit(&tmp, &c, false);
     } else step.reset(new TrivialTestCircuit());
@@ -645,7 +627,7 @@ int vdf_nova_aug_synthesize_field(int fid, const vdf_nova_ro_params* rop, int si
                                   const vdf_nova_aug_inputs* a, const vdf_fe* z0, const vdf_fe* zi, const vdf_state* results,
                                   const vdf_state* inputs, vdf_fe* W, size_t w_cap, size_t* num_vars, size_t* num_cons, vdf_fe X[2], vdf_fe* z_next) {
   if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "field must be VDF_FIELD_FP or VDF_FIELD_FQ");
-  if (!resolve_kind(&circuit_kind, lanes)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit, or lanes out of range for it");
+  if (!kind_lanes_valid(circuit_kind, lanes)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit, or lanes out of range for it");
   return aug_synthesize_impl(fid, rop, side, t, circuit_kind, lanes, a, z0, zi, results, inputs, W, w_cap, num_vars, num_cons, X, z_next);
 }
 int vdf_nova_aug_synthesize(int side, uint64_t t, int circuit_kind, const vdf_nova_aug_inputs* a, const vdf_state* result,
@@ -662,18 +644,18 @@ int vdf_nova_aug_synthesize_ro(const vdf_nova_ro_params* rop, int side, uint64_t
 // ---- the forward circuit in lanes, host only --------------------------------------------------------------------------
 int vdf_nova_shape_digest_lanes(const vdf_nova_ro_params* rop, uint64_t t, size_t lanes, int gens_family, uint8_t out[32], uint64_t sizes[2][3]) {
   if (!lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "bad argument");
-  return shape_digest_impl(VDF_FIELD_FQ, rop, t, lanes_kind(lanes), lanes, gens_family, out, sizes);
+  return shape_digest_impl(VDF_FIELD_FQ, rop, t, VDF_CIRCUIT_MINROOT_FORWARD_LANES, lanes, gens_family, out, sizes);
 }
 int vdf_nova_shape_export_lanes(uint64_t t, size_t lanes, int side, uint64_t nnz[3], uint32_t* const rows[3], uint32_t* const cols[3],
                                 vdf_fe* const vals[3]) {
   if (t == 0 || t > (1ull << 24) || !nnz || (side != PRIMARY && side != SECONDARY) || !lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "bad argument");
-  return shape_export_impl(VDF_FIELD_FQ, t, lanes_kind(lanes), lanes, side, nnz, rows, cols, vals);
+  return shape_export_impl(VDF_FIELD_FQ, t, VDF_CIRCUIT_MINROOT_FORWARD_LANES, lanes, side, nnz, rows, cols, vals);
 }
 int vdf_nova_aug_synthesize_lanes(const vdf_nova_ro_params* rop, uint64_t t, size_t lanes, const vdf_nova_aug_inputs* a, const vdf_fe* z0,
                                   const vdf_fe* zi, const vdf_state* results, const vdf_state* inputs, vdf_fe* W, size_t w_cap,
                                   size_t* num_vars, size_t* num_cons, vdf_fe X[2], vdf_fe* z_next) {
   if (!a || t == 0 || !lanes_valid(lanes) || !z0 || !zi || !results || !inputs) return fail(VDF_ERR_BAD_ARG, "bad argument");
-  return aug_synthesize_impl(VDF_FIELD_FQ, rop, PRIMARY, t, lanes_kind(lanes), lanes, a, z0, zi, results, inputs, W, w_cap, num_vars, num_cons, X, z_next);
+  return aug_synthesize_impl(VDF_FIELD_FQ, rop, PRIMARY, t, VDF_CIRCUIT_MINROOT_FORWARD_LANES, lanes, a, z0, zi, results, inputs, W, w_cap, num_vars, num_cons, X, z_next);
 }
 
 int vdf_nova_synthesis_stats(uint64_t* queued, uint64_t* misses) {
@@ -759,7 +741,6 @@ int vdf_nova_public_params_field(vdf_ctx* ctx, int fid, uint64_t t, int circuit_
     if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "field must be VDF_FIELD_FP or VDF_FIELD_FQ");
     if (circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES) {
       if (!lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_NOVA_MAX_LANES");
-      circuit_kind = lanes_kind(lanes);                                // one lane IS the forward circuit (same kind, same digest)
     } else {
       if (!builtin_circuit(circuit_kind)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
       if (lanes != 1) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 for every kind but VDF_CIRCUIT_MINROOT_FORWARD_LANES");
@@ -794,7 +775,6 @@ int vdf_nova_public_params_ro(vdf_ctx* ctx, uint64_t t, int circuit_kind, int ge
 }
 int vdf_nova_public_params_lanes(vdf_ctx* ctx, uint64_t t, size_t lanes, int gens_family, const vdf_nova_ro_params* rop,
                                  const vdf_nova_tuning* tuning, vdf_pp** out) {
-  if (lanes == 1) return vdf_nova_public_params_ro(ctx, t, VDF_CIRCUIT_MINROOT_FORWARD, gens_family, rop, tuning, out);
   return nova_guard([&]() -> int {
     bool bad;
     const RoInstance* ro = ro_from_abi(rop, &bad);
@@ -930,7 +910,7 @@ static bool minroot_stencil_matches(const HostShape& h, const Field& F, uint64_t
 
 // The same question for the FORWARD circuit and vdf_nifs_cross_term_minroot_forward (include/vdf_hip.h): round j holds
 // x_(j+1), tmp1, tmp2 at S + 3j .., final_i at S + 3t, z_in in the three variables before S.
-// Z = the column of z_in.x (S - 3 for the circuit alone; a lane of the lanes circuit has its inputs further in front)
+// Z = the column of z_in.x (S - 3 for a single chain; a lane of several has its inputs further in front)
 static bool forward_stencil_matches(const HostShape& h, const Field& F, uint64_t t, size_t S, size_t row0, size_t Z) {
   const size_t nrows = 3 * (size_t)t + 1, one_col = h.num_vars;
   if (S < 3 || Z + 3 > S || row0 + nrows > h.num_cons || S + 3 * (size_t)t + 1 > h.num_vars) return false;
@@ -972,16 +952,15 @@ static bool forward_stencil_matches(const HostShape& h, const Field& F, uint64_t
   return true;
 }
 // the stencil code of a built-in circuit whose early rows are [row0, row0 + 3t + 1): 3 / 4 = the inverse forms (variables
-// per round), 5 = the forward circuit; 0 = no match
+// per round), 5 / 6 = the forward circuit of one lane / of more; 0 = no match
 static int builtin_stencil(int fid, const HostShape& h, int circuit_kind, uint64_t t, size_t S, size_t row0, size_t lanes = 1) {
   const Field& F = field(fid);                                        // the primary circuit's
-  if (circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD) return forward_stencil_matches(h, F, t, S, row0, S - 3) ? VDF_STENCIL_FORWARD : 0;
-  if (circuit_kind == VDF_CIRCUIT_MINROOT_FORWARD_LANES) {           // lane by lane: its own variables, rows and inputs
+  if (forward_kind(circuit_kind)) {                                   // lane by lane: its own variables, rows and inputs
     const size_t per_lane = 3 * (size_t)t + 1;
     if (S < 3 * lanes) return 0;
     for (size_t l = 0; l < lanes; ++l)
       if (!forward_stencil_matches(h, F, t, S + l * per_lane, row0 + l * per_lane, S - 3 * lanes + 3 * l)) return 0;
-    return VDF_STENCIL_FORWARD_LANES;
+    return lanes == 1 ? VDF_STENCIL_FORWARD : VDF_STENCIL_FORWARD_LANES;
   }
   const int per = vars_per_round(circuit_kind);
   return minroot_stencil_matches(h, F, t, per, S, row0) ? per : 0;
@@ -1221,10 +1200,10 @@ int vdf_nova_shape_stencil(uint64_t t, int circuit_kind, uint64_t* early_begin, 
 }
 int vdf_nova_shape_stencil_lanes(uint64_t t, size_t lanes, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
   if (t == 0 || t > (1ull << 24) || !lanes_valid(lanes)) return -fail(VDF_ERR_BAD_ARG, "bad argument");
-  return shape_stencil_impl(VDF_FIELD_FQ, t, lanes_kind(lanes), lanes, early_begin, early_len, seg_begin);
+  return shape_stencil_impl(VDF_FIELD_FQ, t, VDF_CIRCUIT_MINROOT_FORWARD_LANES, lanes, early_begin, early_len, seg_begin);
 }
 int vdf_nova_shape_stencil_field(int fid, uint64_t t, int circuit_kind, size_t lanes, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
-  if (!valid_field(fid) || t == 0 || t > (1ull << 24) || !resolve_kind(&circuit_kind, lanes)) return -fail(VDF_ERR_BAD_ARG, "bad argument");
+  if (!valid_field(fid) || t == 0 || t > (1ull << 24) || !kind_lanes_valid(circuit_kind, lanes)) return -fail(VDF_ERR_BAD_ARG, "bad argument");
   return shape_stencil_impl(fid, t, circuit_kind, lanes, early_begin, early_len, seg_begin);
 }
 
@@ -1312,7 +1291,7 @@ struct StepRun {
   const Field& F2;
   const size_t seg_b, seg_n, seg_e;    // the primary witness's run of round variables
   const int per;
-  const bool forward;                  // the forward step circuit: rounds by vdf_minroot_forward_segment, stencil code 5
+  const bool forward;                  // the forward step circuit in pp->lanes lanes: rounds by vdf_minroot_forward_segment_lanes, stencil code 5 / 6
   const bool t_ahead;                  // this step has early rows
   const size_t ta_b, ta_n, ta_e;
   const int t_parts;                   // (tuning.early_row_parts = 2 or 3: the early rows as an MSM job of that many parts (vdf_msm_job_*): a later part's
@@ -1365,12 +1344,11 @@ struct StepRun {
     }
     char* seg = (char*)p->d_z2s[s] + seg_b * 32;
     void* packed = pp->seg_gens ? p->d_packed[j % D] : nullptr;
-    if (pp->lanes > 1) {                          // every lane's rounds in one launch, the lanes' traces back to back
+    if (forward) {                                // every lane's rounds in one launch, the lanes' traces back to back
       Fe ends[VDF_NOVA_MAX_LANES];
       for (size_t l = 0; l < pp->lanes; ++l) ends[l] = cc.lane_result[l].i;
       HIPCALL(q, vdf_minroot_forward_segment_lanes(q, S1.field, (const vdf_fe*)d_trace, (size_t)pp->t + 1, pp->t, pp->lanes, (const vdf_fe*)ends, (vdf_fe*)seg));
-    } else if (forward) HIPCALL(q, vdf_minroot_forward_segment(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.result.i, (vdf_fe*)seg));
-    else if (packed) HIPCALL(q, vdf_minroot_step_segment_packed(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.input.i,
+    } else if (packed) HIPCALL(q, vdf_minroot_step_segment_packed(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.input.i,
                                                             (const vdf_fe*)&cc.result.i, (vdf_fe*)seg, (vdf_fe*)packed));
     else HIPCALL(q, vdf_minroot_step_segment(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.input.i, per, (vdf_fe*)seg));
     HIPCALL(q, vdf_ctx_mark(q, MARK_Z));
@@ -1434,8 +1412,7 @@ struct StepRun {
   // A z, B z, C z and E yet -- the stencil applies it on the way (vdf_nifs_cross_term_minroot_fold) and MARK_FOLD is set behind it
   // (no fused kernel exists for the forward stencil: that kind keeps the unfused fold)
   bool stencil_fold_ok() const {
-    return pp->tune.fold_fused != 0 && pp->stencil_per != 0 && pp->stencil_per != VDF_STENCIL_FORWARD && pp->stencil_per != VDF_STENCIL_FORWARD_LANES &&
-           (t_parts == 1 || ta_n < 4096);
+    return pp->tune.fold_fused != 0 && pp->stencil_per != 0 && !forward && (t_parts == 1 || ta_n < 4096);
   }
   int early_rows_launch(void* d_z2, vdf_ctx* cq, bool zin_in_place, const Fe* fold_r = nullptr) {
     SideState& s1 = p->r[PRIMARY];
@@ -1455,17 +1432,11 @@ struct StepRun {
         HIPCALL(ct, vdf_ctx_mark(ct, MARK_FOLD));                    // the running instance is whole again from here on
         return VDF_OK;
       }
-      if (pp->stencil_per == VDF_STENCIL_FORWARD_LANES && b == ta_b && n == ta_n) {
+      if (forward && pp->stencil_per && b == ta_b && n == ta_n) {
         HIPCALL(ct, vdf_nifs_cross_term_minroot_forward_lanes(ct, S1.field, pp->t, pp->lanes, seg_b, S1.num_vars, b, (const vdf_fe*)d_z2,
                                                               (const vdf_fe*)s1.d_abc[0], (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2],
                                                               (const vdf_fe*)&s1.inst.u, (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1],
                                                               (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
-        return VDF_OK;
-      }
-      if (pp->stencil_per == VDF_STENCIL_FORWARD && b == ta_b && n == ta_n) {
-        HIPCALL(ct, vdf_nifs_cross_term_minroot_forward(ct, S1.field, pp->t, seg_b, S1.num_vars, b, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0],
-                                                        (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2], (const vdf_fe*)&s1.inst.u,
-                                                        (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
         return VDF_OK;
       }
       if (pp->stencil_per && b == ta_b && n == ta_n) {               // the MinRoot stencil: streams only (vdf_hip.h)
@@ -1875,11 +1846,11 @@ static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* ci
   }
   // StepCircuit::output's debug assertion: z_i must be the circuit's result (src/nova/proof.rs:147-149)
   // (the forward circuit starts from the step's input state and hands on its result)
-  if (!custom && pp->lanes > 1) {
-    if (memcmp(p->zi[PRIMARY].data(), c.lane_input.data(), 96 * pp->lanes) != 0) return fail(VDF_ERR_BAD_ARG, "z_i does not match the circuit's input states");
-  } else if (!custom && memcmp(p->zi[PRIMARY].data(), forward_kind(pp->circuit_kind) ? &c.input : &c.result, 96) != 0)
-    return fail(VDF_ERR_BAD_ARG, forward_kind(pp->circuit_kind) ? "z_i does not match the circuit's input state"
-                                                                : "z_i does not match the circuit's result state");
+  if (!custom && forward_kind(pp->circuit_kind)) {
+    if (memcmp(p->zi[PRIMARY].data(), c.lane_input.data(), 96 * pp->lanes) != 0)
+      return fail(VDF_ERR_BAD_ARG, pp->lanes > 1 ? "z_i does not match the circuit's input states" : "z_i does not match the circuit's input state");
+  } else if (!custom && memcmp(p->zi[PRIMARY].data(), &c.result, 96) != 0)
+    return fail(VDF_ERR_BAD_ARG, "z_i does not match the circuit's result state");
   const double t0 = now_ms();
   int was_async = 0;
   HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
@@ -1960,7 +1931,7 @@ int vdf_nova_eval_and_prove(vdf_pp* pp, int mode, const vdf_state* initial_state
   return nova_guard([&]() -> int {
     if (!pp || !initial_state || !out || !valid_mode(mode)) return fail(VDF_ERR_BAD_ARG, "bad argument");
     if (num_steps == 0) return fail(VDF_ERR_BAD_ARG, "num_steps must be > 0");
-    if (pp->circuit_kind != VDF_CIRCUIT_MINROOT_FORWARD)
+    if (!forward_kind(pp->circuit_kind) || pp->lanes > 1)
       return fail(VDF_ERR_BAD_ARG, pp->lanes > 1 ? "lanes parameters: the evaluator of vdf_nova_eval_and_prove is one chain"
                                                  : "these parameters are not for VDF_CIRCUIT_MINROOT_FORWARD");
     *out = nullptr;

@@ -110,12 +110,14 @@ struct vdf_pp {
   // constraints of the primary shape that read nothing of a fresh witness but that segment (and the constant): their
   // share of a step's cross term and of its commitment is made ahead of the rest, [ahead_row, ahead_row + ahead_rows)
   size_t ahead_row = 0, ahead_rows = 0;
-  int stencil_per = 0;           // 5 (VDF_STENCIL_FORWARD): the forward circuit's stencil (vdf_nifs_cross_term_minroot_forward);
+  int stencil_per = 0;           // 5 / 6 (VDF_STENCIL_FORWARD / _LANES): the forward circuit's stencil, of one lane / of more -- one kernel
+                                 // (vdf_nifs_cross_term_minroot_forward_lanes), the code only says how many lanes it runs;
                                  // 3 / 4: the early rows are the built-in MinRoot stencil with that many variables per round, checked against
                                  // the shape at public_params -- their cross term needs no sparse matrix (vdf_nifs_cross_term_minroot); 0: generic rows
   int ahead_mode = 2;            // when they run: 2 = from the start of the step, beside the secondary side's NIFS; 1 = after it (tuning)
   size_t arity = 3;                        // of the primary step circuit (z0, zi)
-  size_t lanes = 1;                        // VDF_CIRCUIT_MINROOT_FORWARD_LANES: evaluations advanced per step (arity = 3 lanes); 1 for every other kind
+  size_t lanes = 1;                        // the forward kinds: evaluations advanced per step (arity = 3 lanes; VDF_CIRCUIT_MINROOT_FORWARD is the
+                                           // circuit of one lane, and so is _LANES with lanes = 1); 1 for every other kind
   // the reference's step circuit only: generators of the packed commitment to the MinRoot rounds (3t + 4 points derived from
   // the 4t + 1 of the segment: vdf_hip.h vdf_minroot_step_segment_packed), with a fixed-base table of their own
   vdf_bases* seg_gens = nullptr;
@@ -151,8 +153,10 @@ struct Circuit {            // InverseMinRootCircuit<G1>, src/nova/proof.rs:57-6
   // rounds in forward order, cp[0] = input .. cp[t / every] = result; its d_trace is built by walks, and is what release lets go of
   uint64_t every = 0;
   std::vector<vdfnova::St> cp;
-  // a step of a chain in L > 1 lanes (vdf_nova_circuits_lanes_begin): result / input above are lane 0's, these hold every lane's;
-  // trace_xy and the device trace are L traces back to back, t + 1 entries each, and cp is L runs of t / every + 1 states
+  // a step of a forward chain in L >= 1 lanes (vdf_nova_circuits_forward_begin: L = 1, vdf_nova_circuits_lanes_begin): these hold every
+  // lane's states and are what the forward circuit reads; result / input above are lane 0's (vdf_proof::Ahead and the inverse
+  // kinds, which leave these empty, read those).  trace_xy and the device trace are L traces back to back, t + 1 entries each,
+  // and cp is L runs of t / every + 1 states
   std::vector<vdfnova::St> lane_result, lane_input;
 };
 // Traces being rebuilt by inverse walks on the circuits' side queue (vdf_nova_circuits_materialize): one walk per checkpoint
@@ -189,13 +193,13 @@ struct vdf_circuits {
   vdf_ctx* ctx = nullptr;
   int field = VDF_FIELD_FQ;                // the chain's field: its evaluator, its counters, its push checks and its walks run over it
   bool checkpoints = false;                // made by vdf_nova_circuits_from_checkpoints (or grown by vdf_nova_circuits_push_checkpoints)
-  // a forward chain (vdf_nova_circuits_forward_begin): circuits in the order of evaluation, appended to while the chain grows;
-  // `end` is the state the next pushed step must start from
+  // a forward chain (vdf_nova_circuits_forward_begin, vdf_nova_circuits_lanes_begin): circuits in the order of evaluation, appended
+  // to while the chain grows; lane_end[l] is the state lane l of the next pushed step must start from
   bool forward = false;
   uint64_t forward_t = 0;
-  vdfnova::St end;
-  size_t lanes = 1;                        // a forward chain in lanes (vdf_nova_circuits_lanes_begin): evaluations advanced per step
-  std::vector<vdfnova::St> lane_end;       // lanes > 1: where every lane stands (end = lane 0's)
+  size_t lanes = 1;                        // evaluations advanced per step (1: a single chain)
+  std::vector<vdfnova::St> lane_end;       // a forward chain: where every lane stands
+  vdfnova::St end;                         // ... lane 0's
   mutable WalkState walk;
 };
 

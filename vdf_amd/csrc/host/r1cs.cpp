@@ -1060,14 +1060,6 @@ std::vector<Num> ForwardMinRootCircuit::synthesize(CS& cs, const std::vector<Num
   const Field& F = cs.F;
   Num x = z[0], y = z[1];
   const Num& i_in = z[2];
-  if (!cs.shape && device_rounds) {
-    // the rounds are left to the GPU (vdf_minroot_forward_segment fills them from the forward trace): the outputs are the
-    // stored state after the step
-    cs.skip(3 * t + 1, 3 * t + 1);
-    std::vector<Num> out(3);
-    out[0].v = result.x; out[1].v = result.y; out[2].v = result.i;
-    return out;
-  }
   for (uint64_t j = 0; j < t; ++j) {
     Fe root = vdfhost::zero();
     if (!cs.shape) {                                                              // the hint: one host fifth root per round
@@ -1086,25 +1078,19 @@ std::vector<Num> ForwardMinRootCircuit::synthesize(CS& cs, const std::vector<Num
   cs.enforce(final_i, cs.constant(one(F)), cs.add(i_in, tn));
   return {x, y, final_i};
 }
-void ForwardMinRootCircuit::output(const Fe* z, Fe* out) const {
-  (void)z;
-  out[0] = result.x; out[1] = result.y; out[2] = result.i;
-}
 
 std::vector<Num> LanesForwardCircuit::synthesize(CS& cs, const std::vector<Num>& z) const {
   const size_t L = results.size();
   std::vector<Num> out(3 * L);
   if (!cs.shape && device_rounds) {
-    // every lane's rounds are left to the GPU (vdf_minroot_forward_segment_lanes): one run of L (3t + 1) variables and rows
+    // every lane's rounds are left to the GPU (vdf_minroot_forward_segment_lanes fills them from the forward traces): one run of
+    // L (3t + 1) variables and rows; the outputs are the stored states after the step
     cs.skip(L * (3 * t + 1), L * (3 * t + 1));
     for (size_t l = 0; l < L; ++l) { out[3 * l].v = results[l].x; out[3 * l + 1].v = results[l].y; out[3 * l + 2].v = results[l].i; }
     return out;
   }
   for (size_t l = 0; l < L; ++l) {
-    ForwardMinRootCircuit lane;
-    lane.t = t; lane.blank = blank; lane.device_rounds = false;
-    lane.result = results[l]; lane.input = inputs[l];
-    const std::vector<Num> o = lane.synthesize(cs, {z[3 * l], z[3 * l + 1], z[3 * l + 2]});
+    const std::vector<Num> o = ForwardMinRootCircuit{t}.synthesize(cs, {z[3 * l], z[3 * l + 1], z[3 * l + 2]});
     for (int k = 0; k < 3; ++k) out[3 * l + k] = o[k];
   }
   return out;

@@ -173,22 +173,17 @@ struct InverseMinRootCircuit : StepCircuit {
   bool output_known() const override { return !blank; }
   size_t vars_per_round() const { return bound ? 3 : 4; }
 };
-// ForwardMinRootCircuit (include/vdf_nova.h VDF_CIRCUIT_MINROOT_FORWARD): the step in the direction of evaluation
-// (src/minroot.rs:329-335), z_in = input, z_out = result.  Per round the fifth root x_(j+1) is allocated (the only free
-// variable, and x -> x^5 is a bijection), squared twice, and tmp2 * x_(j+1) = x_j + y_j enforced; y_(j+1) = x_j + i_in + j
-// is a linear combination.  3 variables and 3 constraints per round, then final_i = i_in + t.
-struct ForwardMinRootCircuit : StepCircuit {
+// ForwardMinRootCircuit: one lane of the forward step circuit, the step in the direction of evaluation (src/minroot.rs:329-335),
+// z_in = input, z_out = result.  Per round the fifth root x_(j+1) is allocated (the only free variable, and x -> x^5 is a
+// bijection), squared twice, and tmp2 * x_(j+1) = x_j + y_j enforced; y_(j+1) = x_j + i_in + j is a linear combination.
+// 3 variables and 3 constraints per round, then final_i = i_in + t.  Not a step circuit of its own: LanesForwardCircuit is.
+struct ForwardMinRootCircuit {
   uint64_t t = 0;
-  bool blank = true;
-  bool device_rounds = false;            // witness mode: leave the per-round variables to the GPU kernel (cs.skip)
-  MinRootState result, input;
-  size_t arity() const override { return 3; }
-  std::vector<Num> synthesize(CS& cs, const std::vector<Num>& z) const override;
-  void output(const Fe* z, Fe* out) const override;
-  bool output_known() const override { return !blank; }
+  std::vector<Num> synthesize(CS& cs, const std::vector<Num>& z) const;
 };
-// L forward circuits side by side (include/vdf_nova.h VDF_CIRCUIT_MINROOT_FORWARD_LANES): arity 3L, z = (x_0, y_0, i_0, x_1, ...),
-// lane l synthesised over z[3l .. 3l + 3) in order -- its 3t + 1 variables and constraints follow lane l - 1's.
+// The forward step circuit (include/vdf_nova.h VDF_CIRCUIT_MINROOT_FORWARD: L = 1, VDF_CIRCUIT_MINROOT_FORWARD_LANES): L lanes side
+// by side, arity 3L, z = (x_0, y_0, i_0, x_1, ...), lane l synthesised over z[3l .. 3l + 3) in order -- its 3t + 1 variables and
+// constraints follow lane l - 1's.
 struct LanesForwardCircuit : StepCircuit {
   uint64_t t = 0;
   bool blank = true;

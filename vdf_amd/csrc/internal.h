@@ -316,8 +316,7 @@ Status vec_spmv(int field, const uint32_t* rowptr, const uint32_t* col, const ui
 // fused step kernels; vdf_fe* arguments are HOST pointers whose values travel as kernel arguments
 Status vec_step_segment(int field, const void* trace_xy, uint64_t t, const vdf_fe* i0, int per, void* out, void* packed,
                         const vdf_fe* i_in, hipStream_t s);
-Status vec_forward_segment(int field, const void* trace_xy, uint64_t t, const vdf_fe* i_end, void* out, hipStream_t s);
-// ... for `lanes` traces lane_stride entries apart, lane-major into out (one launch; i_end: `lanes` host elements)
+// the forward circuit's variables for `lanes` traces lane_stride entries apart, lane-major into out (one launch; i_end: `lanes` host elements)
 Status vec_forward_segment_lanes(int field, const void* trace_xy, size_t lane_stride, uint64_t t, size_t lanes, const vdf_fe* i_end, void* out,
                                  hipStream_t s);
 Status vec_step_z(int field, const void* trace_xy, uint64_t t, const vdf_fe z_in[3], const vdf_fe* i0, const vdf_fe* u,
@@ -331,9 +330,6 @@ int nifs_cross_lanes(size_t rows);                       // lanes per row vec_ni
 Status vec_nifs_cross_minroot(int field, int per, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
                               const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, void* az2, void* bz2, void* cz2,
                               void* T, hipStream_t s);
-Status vec_nifs_cross_minroot_forward(int field, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
-                                      const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, void* az2, void* bz2,
-                                      void* cz2, void* T, hipStream_t s);
 Status vec_nifs_cross_minroot_forward_lanes(int field, uint64_t t, size_t lanes, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
                                             const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, void* az2, void* bz2,
                                             void* cz2, void* T, hipStream_t s);

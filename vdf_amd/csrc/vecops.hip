@@ -179,31 +179,12 @@ __global__ __launch_bounds__(256) void k_step_segment(const char* __restrict__ t
   }
 }
 
-// The variables ForwardMinRootCircuit::synthesize allocates (oracle/nova.py's primary= seam; include/vdf_nova.h
-// VDF_CIRCUIT_MINROOT_FORWARD): per round x_(j+1) -- the fifth root, taken from the forward trace -- and its square and
-// fourth power, then final_i = i_end.  The trace is read in the direction it was written: round j reads entry j + 1.
-template <class P>
-__global__ __launch_bounds__(256) void k_forward_segment(const char* __restrict__ trace, FeVal i_end, uint64_t t,
-                                                         char* __restrict__ out) {
-  __builtin_amdgcn_s_setprio(3);     // light kernel: do not starve behind a co-running k_accumulate
-  const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j > t) return;
-  if (j == t) {
-    fe_store<P>(out + (size_t)3 * t * 32, fe_from_val<P>(i_end));
-    return;
-  }
-  const Fe<P> x = fe_load<P>(trace + (j + 1) * 64);
-  const Fe<P> t1 = fe_sqr(x);
-  const Fe<P> t2 = fe_sqr(t1);
-  char* o = out + j * 96;
-  fe_store<P>(o, x);
-  fe_store<P>(o + 32, t1);
-  fe_store<P>(o + 64, t2);
-}
-
-// The same for L lanes at once (VDF_CIRCUIT_MINROOT_FORWARD_LANES): lane l = blockIdx.y reads the trace that starts lane_stride
-// entries after lane l - 1's and writes its 3t + 1 variables behind lane l - 1's.  The lanes' last round counters arrive as
-// kernel arguments (no staging copy): the lane picks its own with a uniform index.
+// The variables LanesForwardCircuit::synthesize allocates (oracle/nova.py's primary= seam; include/vdf_nova.h
+// VDF_CIRCUIT_MINROOT_FORWARD and _LANES), lane after lane: per round x_(j+1) -- the fifth root, taken from the forward trace -- and
+// its square and fourth power, then final_i = i_end.  A trace is read in the direction it was written: round j reads entry j + 1.
+// Lane l = blockIdx.y reads the trace that starts lane_stride entries after lane l - 1's and writes its 3t + 1 variables behind
+// lane l - 1's; a single chain is the launch of one lane.  The lanes' last round counters arrive as kernel arguments (no
+// staging copy): the lane picks its own with a uniform index.
 struct LaneEnds { FeVal v[VDF_MINROOT_MAX_LANES]; };
 template <class P>
 __global__ __launch_bounds__(256) void k_forward_segment_lanes(const char* __restrict__ trace, size_t lane_stride, LaneEnds i_end,
@@ -559,65 +540,18 @@ __global__ __launch_bounds__(256) void k_nifs_cross_minroot(const char* __restri
   fe_store<P>(T + r * 32, tt);
 }
 
-// The same for the FORWARD step circuit (VDF_CIRCUIT_MINROOT_FORWARD): round j holds x' = x_(j+1), tmp1, tmp2 at
-// S + 3j .. S + 3j + 2 and final_i sits at S + 3t; x_0 = z_in.x, y_0 = z_in.y, and for j >= 1 y_j is no variable but
-// x_(j-1) + i + (j - 1) * one:
+// The same for the FORWARD step circuit over L lanes in one launch (VDF_CIRCUIT_MINROOT_FORWARD: L = 1, and _LANES).  Lane
+// l = blockIdx.y owns the variables S = S0 + l (3t + 1) .. and the rows row0 + l (3t + 1) .., and ITS z_in = (x_0, y_0, i) sits at
+// Z .. Z + 2, Z = S0 - 3L + 3l.  Round j holds x' = x_(j+1), tmp1, tmp2 at S + 3j .. S + 3j + 2 and final_i sits at S + 3t;
+// x_0 = z_in.x, y_0 = z_in.y, and for j >= 1 y_j is no variable but x_(j-1) + i + (j - 1) * one:
 //   row 3j     x' * x'     = tmp1
 //   row 3j + 1 tmp1 * tmp1 = tmp2
 //   row 3j + 2 tmp2 * x'   = x_j + y_j      (j = 0: z_in.x + z_in.y; j >= 1: x_j + x_(j-1) + i + (j - 1) * one)
 //   row 3t     final_i * one = i + t * one
-// Built like the inverse stencil: one row per lane, every source address selected first, every load issued before the
-// first use, the constant's coefficient times z2[one].  pd = the second term of C z2 of a role-2 row (a valid address in
-// every lane, used by that role only).
-template <class P>
-__global__ __launch_bounds__(256) void k_nifs_cross_minroot_forward(const char* __restrict__ z2, size_t S, size_t one_col, uint64_t t,
-                                                                    size_t row0, const char* __restrict__ az1, const char* __restrict__ bz1,
-                                                                    const char* __restrict__ cz1, FeVal u1, char* __restrict__ az2,
-                                                                    char* __restrict__ bz2, char* __restrict__ cz2, char* __restrict__ T) {
-  __builtin_amdgcn_s_setprio(3);     // light kernel: do not starve behind a co-running k_accumulate
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i > 3 * t) return;
-  const size_t r = row0 + i;
-  const bool last = i == 3 * t;
-  const uint64_t j = last ? t - 1 : i / 3;
-  const uint32_t role = last ? 3u : (uint32_t)(i - 3 * j);
-  // columns, not pointers: a column that does not exist for a small j (rd - 6 below) is then never formed as an address
-  const size_t rd = S + (size_t)3 * j;                               // this round's x', tmp1, tmp2
-  const size_t cxj = j ? rd - 3 : S - 3;                             // x_j
-  const size_t ca = role == 3 ? S + (size_t)3 * t : rd + role;
-  const size_t cb = role == 1 ? rd + 1 : (role == 3 ? one_col : rd);
-  const size_t cc = role == 2 ? cxj : (role == 3 ? S - 1 : rd + role + 1);
-  const size_t cd = j >= 2 ? rd - 6 : (j == 1 ? S - 3 : S - 2);      // j >= 2: x_(j-1); j = 1: x_0 = z_in.x; j = 0: y_0 = z_in.y
-  const char *pa = z2 + ca * 32, *pb = z2 + cb * 32, *pc = z2 + cc * 32, *pd = z2 + cd * 32;
-  const Fe<P> a1 = fe_load<P>(az1 + r * 32), b1 = fe_load<P>(bz1 + r * 32), c1 = fe_load<P>(cz1 + r * 32);
-  const Fe<P> onev = fe_load<P>(z2 + one_col * 32);
-  const Fe<P> i_in = fe_load<P>(z2 + (S - 1) * 32);
-  const Fe<P> a2 = fe_load<P>(pa), b2 = fe_load<P>(pb);
-  Fe<P> c2 = fe_load<P>(pc);
-  const Fe<P> d = fe_load<P>(pd);
-  const bool unit = fe_eq(onev, fe_one<P>());                        // ONE in every fresh instance: a uniform branch
-  auto times_one = [&](uint64_t k) -> Fe<P> {
-    const Fe<P> km = k < (1u << 30) ? fe_from_small<P>((uint32_t)k) : fe_from_u64<P>(k);
-    return unit ? km : fe_mul(km, onev);
-  };
-  if (role == 2) {
-    c2 = fe_add(c2, d);
-    if (j > 0) c2 = fe_add(fe_add(c2, i_in), times_one(j - 1));
-  }
-  if (role == 3) c2 = fe_add(c2, times_one(t));
-  fe_store<P>(az2 + r * 32, a2);
-  fe_store<P>(bz2 + r * 32, b2);
-  fe_store<P>(cz2 + r * 32, c2);
-  Fe<P> tt = fe_add(fe_mul(a1, b2), fe_mul(a2, b1));
-  tt = fe_sub(tt, fe_mul(fe_from_val<P>(u1), c2));
-  tt = fe_sub(tt, c1);
-  fe_store<P>(T + r * 32, tt);
-}
-
-// The forward stencil over L lanes in one launch (VDF_CIRCUIT_MINROOT_FORWARD_LANES): lane l = blockIdx.y owns the variables
-// S + l (3t + 1) .. and the rows row0 + l (3t + 1) .., and ITS z_in = (x_0, y_0, i) sits at Z .. Z + 2, Z = S - 3L + 3l, where the
-// single-lane stencil reads S - 3 .. S - 1.  Row for row the kernel above: columns selected first (a lane's j < 2 rows read its
-// own inputs, never the lane before), every load issued before the first use.
+// Built like the inverse stencil: one row per lane, every source address selected first (columns, not pointers: a column that
+// does not exist for a small j, rd - 6 below, is then never formed as an address; a lane's j < 2 rows read its own inputs, never
+// the lane before), every load issued before the first use, the constant's coefficient times z2[one].  pd = the second term of
+// C z2 of a role-2 row (a valid address in every lane, used by that role only).
 template <class P>
 __global__ __launch_bounds__(256) void k_nifs_cross_minroot_forward_lanes(const char* __restrict__ z2, size_t S0, uint32_t lanes, size_t one_col,
                                                                           uint64_t t, size_t row0, const char* __restrict__ az1,
@@ -901,20 +835,14 @@ Status vec_step_segment(int field, const void* trace_xy, uint64_t t, const vdf_f
   });
 }
 
-Status vec_forward_segment(int field, const void* trace_xy, uint64_t t, const vdf_fe* i_end, void* out, hipStream_t s) {
-  KTimer kt(s, "k_forward_segment", (32.0 + 96.0) * t);       // trace x read + three variables written per round
-  return with_field(field, [&](auto f) {
-    hipLaunchKernelGGL((k_forward_segment<tag_t<decltype(f)>>), grid_for(t + 1), dim3(256), 0, s, cbytes_of(trace_xy), to_val(i_end), t, bytes_of(out));
-  });
-}
-
 Status vec_forward_segment_lanes(int field, const void* trace_xy, size_t lane_stride, uint64_t t, size_t lanes, const vdf_fe* i_end, void* out,
                                  hipStream_t s) {
   if (lanes == 0 || lanes > VDF_MINROOT_MAX_LANES || lane_stride < t + 1) return Status{VDF_ERR_BAD_ARG, "bad lanes"};
   LaneEnds e;
   std::memset(&e, 0, sizeof(e));
   for (size_t l = 0; l < lanes; ++l) e.v[l] = to_val(&i_end[l]);
-  KTimer kt(s, "k_forward_segment_lanes", (32.0 + 96.0) * t * lanes);
+  // trace x read + three variables written per round; a single chain keeps the label it always had
+  KTimer kt(s, lanes == 1 ? "k_forward_segment" : "k_forward_segment_lanes", (32.0 + 96.0) * t * lanes);
   const dim3 grid(grid_for(t + 1).x, (unsigned)lanes);
   return with_field(field, [&](auto f) {
     hipLaunchKernelGGL((k_forward_segment_lanes<tag_t<decltype(f)>>), grid, dim3(256), 0, s, cbytes_of(trace_xy), lane_stride, e, t, bytes_of(out));
@@ -984,26 +912,14 @@ Status vec_nifs_cross_minroot(int field, int per, uint64_t t, size_t seg_begin, 
   });
 }
 
-Status vec_nifs_cross_minroot_forward(int field, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
-                                      const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, void* az2, void* bz2,
-                                      void* cz2, void* T, hipStream_t s) {
-  if (t == 0 || seg_begin < 3) return Status{VDF_ERR_BAD_ARG, "bad segment"};
-  const size_t rows = 3 * (size_t)t + 1;
-  // (the label is short on purpose: a timed launch keeps 23 characters of it, and the fused inverse stencil's begins the same way)
-  KTimer kt(s, "k_nifs_cross_fwd", (double)rows * 7 * 32 + 3.0 * t * 32);      // priced as the inverse stencil is
-  const dim3 grid = grid_for(rows);
-  return with_field(field, [&](auto f) {
-    hipLaunchKernelGGL((k_nifs_cross_minroot_forward<tag_t<decltype(f)>>), grid, dim3(256), 0, s, cbytes_of(z2), seg_begin, one_col, t, row0,
-                       cbytes_of(az1), cbytes_of(bz1), cbytes_of(cz1), to_val(u1), bytes_of(az2), bytes_of(bz2), bytes_of(cz2), bytes_of(T));
-  });
-}
-
 Status vec_nifs_cross_minroot_forward_lanes(int field, uint64_t t, size_t lanes, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
                                             const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, void* az2, void* bz2,
                                             void* cz2, void* T, hipStream_t s) {
   if (t == 0 || lanes == 0 || lanes > VDF_MINROOT_MAX_LANES || seg_begin < 3 * lanes) return Status{VDF_ERR_BAD_ARG, "bad segment"};
   const size_t rows = 3 * (size_t)t + 1;
-  KTimer kt(s, "k_nifs_cross_fwd_lanes", ((double)rows * 7 * 32 + 3.0 * t * 32) * lanes);      // priced as the single-lane stencil is
+  // priced as the inverse stencil is; the labels are short on purpose (a timed launch keeps 23 characters, and the fused inverse
+  // stencil's begins the same way), and a single chain keeps the one it always had
+  KTimer kt(s, lanes == 1 ? "k_nifs_cross_fwd" : "k_nifs_cross_fwd_lanes", ((double)rows * 7 * 32 + 3.0 * t * 32) * lanes);
   const dim3 grid(grid_for(rows).x, (unsigned)lanes);
   return with_field(field, [&](auto f) {
     hipLaunchKernelGGL((k_nifs_cross_minroot_forward_lanes<tag_t<decltype(f)>>), grid, dim3(256), 0, s, cbytes_of(z2), seg_begin, (uint32_t)lanes,
