@@ -383,6 +383,40 @@ int  vdf_minroot_forward_segment(vdf_ctx* ctx, int field, const vdf_fe* trace_xy
 #define VDF_MINROOT_MAX_LANES 16
 int  vdf_minroot_forward_segment_lanes(vdf_ctx* ctx, int field, const vdf_fe* trace_xy, size_t lane_stride, uint64_t t, size_t lanes,
                                        const vdf_fe* i_end, vdf_fe* out);
+/* ---- round tapes: the variables of t uniform repetitions of a round somebody else wrote (libvdf_nova.so's vdf_cs_repeat) --
+ * A tape is a short straight-line program over a file of n_slots field values, run once per repetition j = 0 .. t - 1 by one
+ * GPU thread each.  Every op is four bytes {op, dst, a, b}; dst and the operands of the arithmetic ops are slot numbers:
+ *   VDF_TAPE_ADV    slot[dst] = advice entry j + b (b = 0 or 1), column a (a < n_adv)
+ *   VDF_TAPE_INV    slot[dst] = inv[a]                  (loop-invariant values, a < n_inv)
+ *   VDF_TAPE_J      slot[dst] = the constant j          (Montgomery form)
+ *   VDF_TAPE_CONST  slot[dst] = consts[a]
+ *   VDF_TAPE_ADD / _SUB / _MUL   slot[dst] = slot[a] (+ - *) slot[b]   (a = b under _MUL is a squaring)
+ *   VDF_TAPE_SCALE  slot[dst] = slot[a] * consts[b]
+ *   VDF_TAPE_OUT    variable b of this repetition = slot[a]: out[j * n_vars + b]   (dst unused; b < n_vars)
+ * advice: (t + 1) entries of n_adv elements, entry-major (a MinRoot trace is n_adv = 2).  A slot is read only after an op of
+ * the same tape wrote it (refused otherwise) and every variable is written exactly once.  n_cons, the constraints per
+ * repetition, is carried for the caller (constraints cost nothing here).  The caps below are refused with VDF_ERR_BAD_ARG. */
+enum { VDF_TAPE_ADV = 0, VDF_TAPE_INV = 1, VDF_TAPE_J = 2, VDF_TAPE_CONST = 3, VDF_TAPE_ADD = 4, VDF_TAPE_SUB = 5, VDF_TAPE_MUL = 6,
+       VDF_TAPE_SCALE = 7, VDF_TAPE_OUT = 8 };
+#define VDF_TAPE_MAX_OPS 320      /* ops of a tape (loads and stores included) */
+#define VDF_TAPE_MAX_CONSTS 24
+#define VDF_TAPE_MAX_SLOTS 24     /* live values: 2 KiB of LDS each per 64 repetitions */
+#define VDF_TAPE_MAX_VARS 64      /* variables per repetition */
+#define VDF_TAPE_MAX_INV 16
+#define VDF_TAPE_MAX_ADV 8
+typedef struct vdf_tape_op { uint8_t op, dst, a, b; } vdf_tape_op;
+typedef struct vdf_round_tape {
+  const vdf_tape_op* ops;  size_t n_ops;       /* host memory */
+  const vdf_fe* consts;    size_t n_consts;    /* host memory, Montgomery form */
+  uint32_t n_slots, n_vars, n_cons, n_inv, n_adv;
+} vdf_round_tape;
+/* Runs the tape over repetitions 0 .. t - 1: out (device, t * n_vars elements) gets the variables, repetition-major.  inv: n_inv
+ * elements in HOST memory; tape: host memory -- both travel as kernel arguments (no staging copy, no synchronisation).  advice:
+ * device memory.  Values are whatever the ops make of the advice: nothing is checked against a constraint. */
+int  vdf_round_tape_run(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uint64_t t, const vdf_fe* inv, const vdf_fe* advice,
+                        vdf_fe* out);
+/* 1 when a kernel of this library may read p in place (device memory, or host memory of vdf_host_alloc), else 0 */
+int  vdf_ptr_is_device(const void* p);
 /* vdf_spmv3(shape, z2) followed by vdf_cross_term(Az1, Bz1, Cz1, Az2, Bz2, Cz2, u1): writes Az2, Bz2, Cz2
  * (num_cons each) and T.  u1: host memory.  (nova-snark NIFS::prove -> commit_T, K4 + K5.) */
 int  vdf_nifs_cross_term(vdf_ctx* ctx, const vdf_shape* shape, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,

@@ -218,7 +218,8 @@ int  vdf_nova_pp_memory(const vdf_pp* pp, uint64_t gens_bytes[2], uint64_t table
 void vdf_nova_pp_free(vdf_pp* pp);
 int  vdf_nova_pp_sizes(const vdf_pp* pp, int side, uint64_t* num_cons, uint64_t* num_vars, uint64_t* num_io, uint64_t* nnz3,
                        uint64_t* num_gens);
-/* the 250-bit digest of the parameters (little-endian), and the run of primary variables the GPU fills (MinRoot rounds) */
+/* the 250-bit digest of the parameters (little-endian), and the run of primary variables the GPU fills (MinRoot rounds; for a
+ * custom circuit the variables of its vdf_cs_repeat, filled by the GPU in the steps whose advice is in device memory; 0, 0 without one) */
 int  vdf_nova_pp_digest(const vdf_pp* pp, uint8_t out[32]);
 int  vdf_nova_pp_segment(const vdf_pp* pp, uint64_t* begin, uint64_t* len);
 /* the run of primary constraints whose share of a step's cross term T and of comm_T prove_step makes ahead of the rest of
@@ -397,7 +398,8 @@ int  vdf_nova_proof_kernel_events(vdf_proof* proof, vdf_kernel_event* out, int* 
  * runs in two modes, as a bellperson circuit does: when the parameters are made the constraints are recorded (values
  * are ignored); in every prove_step only the values are computed (vdf_cs_is_witness).  `output` of the trait is the
  * value of z_out after a witness synthesis.  The library's own circuits (both MinRoot forms, TrivialTestCircuit) sit
- * behind the same C++ interface (host/r1cs.hpp StepCircuit); a custom circuit's variables are all made on the host. */
+ * behind the same C++ interface (host/r1cs.hpp StepCircuit); a custom circuit's variables are made on the host, except those of
+ * the uniform rounds it hands to vdf_cs_repeat (below) with their advice in device memory. */
 typedef struct vdf_cs vdf_cs;
 typedef uint32_t vdf_num;                 /* a linear combination with its value, owned by the vdf_cs */
 typedef struct {
@@ -414,6 +416,61 @@ vdf_num vdf_cs_alloc(vdf_cs* cs, const vdf_fe* value);                /* a new v
 vdf_num vdf_cs_mul(vdf_cs* cs, vdf_num a, vdf_num b);                 /* a new variable a * b and its constraint */
 int     vdf_cs_enforce(vdf_cs* cs, vdf_num a, vdf_num b, vdf_num c);  /* a * b = c */
 int     vdf_cs_value(const vdf_cs* cs, vdf_num a, vdf_fe* out);       /* witness mode */
+/* ---- uniform rounds of a custom circuit: vdf_cs_repeat ---------------------------------------------------------------------
+ * t repetitions of one round, written once as a callback over the calls above and run, in a prove_step, by ONE GPU thread per
+ * repetition (libvdf_hip.so vdf_round_tape_run) instead of t host callbacks.
+ *
+ * TRACING.  vdf_cs_repeat calls `body` exactly once, on a recording vdf_cs, and keeps what it did as a tape: a straight-line
+ * program of add, sub, scale, const, mul (a variable and its constraint), alloc_from (a variable) and enforce.  Inside the body
+ * only the handles it was given or made itself exist: any other handle, vdf_cs_alloc, vdf_cs_value and a nested vdf_cs_repeat set
+ * the circuit's failure flag (as a bad handle does anywhere) and vdf_cs_repeat returns VDF_ERR_BAD_ARG with nothing allocated.
+ * A body must not branch on values or on vdf_cs_is_witness: it is not run again.
+ *
+ * INPUTS of repetition j = 0 .. t - 1.  `j`: the constant j.  `inv`: n_inv loop-invariant numbers of the caller.  `carry`:
+ * n_carry numbers -- carry_in for j = 0, the previous repetition's carry_out (as linear combinations) after that.  `cur` / `next`:
+ * the n_adv columns of advice entries j and j + 1 as VALUE-ONLY handles: they, and sums / differences / multiples made of them,
+ * feed vdf_cs_alloc_from and further value arithmetic; in vdf_cs_mul, vdf_cs_enforce or carry_out they are an error.
+ *
+ * ADVICE AND VALUES.  advice: (t + 1) entries of n_adv elements, entry-major, Montgomery form (a vdf_minroot_eval trace is
+ * n_adv = 2), in host or device memory; NULL while the shape is recorded.  THE VALUE OF CARRY c IN REPETITION j IS ADVICE ENTRY j,
+ * COLUMN c -- on the host path and on the device path alike, and the values of the returned carry_out are entry t (copied back
+ * when the advice is in device memory).  That rule is what makes repetitions independent.  Advice that disagrees with what the
+ * body computes (a wrong root, the trace of another step) therefore does not fail here: the witness is unsatisfiable,
+ * vdf_nova_prove_step_custom returns VDF_OK and vdf_nova_verify_custom answers 0.  Nothing faults.
+ *
+ * MODES.  Shape: the tape is replayed t times on the host; variables and constraints are repetition-major in the order of the
+ * body's calls, so the same circuit written as a plain loop has the same shape and the same digest.  Witness, host advice: the
+ * tape is interpreted on the host (the fallback, and the reference of the device path).  Witness, device advice (inside
+ * vdf_nova_prove_step_custom): the t n_vars variables are left out of the host's witness and a kernel writes them straight into
+ * the fresh witness before it is committed; vdf_nova_pp_segment names the run.
+ *
+ * LIMITS, each VDF_ERR_BAD_ARG: one vdf_cs_repeat per circuit; 1 <= t < 2^31; n_carry <= n_adv; the caps below.  The parameters
+ * keep the tape: a prove_step whose body records another one is VDF_ERR_BAD_ARG.  Out of scope for custom circuits: early rows
+ * of the cross term, lookahead and stencils (T is made and committed in one piece: vdf_nifs_cross_term). */
+#define VDF_ROUND_MAX_INV 16
+#define VDF_ROUND_MAX_CARRY 8
+#define VDF_ROUND_MAX_ADV 8
+#define VDF_ROUND_MAX_OPS 128      /* vdf_cs_* calls of one body */
+#define VDF_ROUND_MAX_CONSTS 24    /* of them vdf_cs_const and vdf_cs_scale (one stored constant each) */
+#define VDF_ROUND_MAX_VARS 64      /* variables per repetition (vdf_cs_mul, vdf_cs_alloc_from) */
+#define VDF_ROUND_MAX_LIVE 24      /* values alive at once: an input counts from its first use, every value until its last;
+                                      a value that no variable depends on does not count */
+typedef struct {
+  size_t n_inv, n_carry, n_adv;
+  int (*body)(void* self, vdf_cs* cs, vdf_num j, const vdf_num* inv, const vdf_num* carry, const vdf_num* cur, const vdf_num* next,
+              vdf_num* carry_out);                                      /* 0 = ok */
+  void* self;
+} vdf_round_body;
+int     vdf_cs_repeat(vdf_cs* cs, const vdf_round_body* b, uint64_t t, const vdf_num* inv, const vdf_num* carry_in, const vdf_fe* advice,
+                      vdf_num* carry_out);
+vdf_num vdf_cs_alloc_from(vdf_cs* cs, vdf_num src);                    /* a new variable with src's value, no constraint */
+/* Host only.  Records a body and hands out its tape for vdf_round_tape_run (ops / consts: caller's arrays of the two caps, which
+ * out->ops / out->consts then point into); out->n_cons = the constraints per repetition.  field: the body's field. */
+int  vdf_nova_round_body_record(int field, const vdf_round_body* b, vdf_tape_op ops[VDF_TAPE_MAX_OPS], vdf_fe consts[VDF_TAPE_MAX_CONSTS],
+                                vdf_round_tape* out);
+/* Host only.  What vdf_round_tape_run computes, on the host: out = the t n_vars variables (inv, advice, out: host memory). */
+int  vdf_nova_round_tape_eval(int field, const vdf_round_tape* tape, uint64_t t, const vdf_fe* inv, const vdf_fe* advice, vdf_fe* out);
+
 /* public_params / prove_step / verify for a custom primary step circuit (the secondary stays TrivialTestCircuit).
  * z0, zi: `arity` elements.  compress, verify_compressed and the wire formats work on such proofs unchanged. */
 int  vdf_nova_public_params_custom(vdf_ctx* ctx, const vdf_step_circuit* primary, int gens_family, vdf_pp** out);

@@ -1493,6 +1493,20 @@ int vdf_minroot_forward_segment_lanes(vdf_ctx* ctx, int field, const vdf_fe* tra
   });
 }
 
+int vdf_round_tape_run(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uint64_t t, const vdf_fe* inv, const vdf_fe* advice, vdf_fe* out) {
+  return guarded(ctx, [&]() -> Status {
+    if (t == 0 || t >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
+    if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv))
+      return Status{VDF_ERR_BAD_ARG, "the tape and inv live in host memory"};
+    if (!ptr_is_device(advice) || !ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
+    VDF_TRY(vdf::vec_round_tape(field, tape, t, inv, advice, out, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
+int vdf_ptr_is_device(const void* p) { return ptr_is_device(p) ? 1 : 0; }
+
 static Status nifs_cross_impl(vdf_ctx* ctx, const vdf_shape* shape, size_t row_begin, size_t row_count, int part, const vdf_fe* z2,
                               const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2,
                               vdf_fe* Cz2, vdf_fe* T) {

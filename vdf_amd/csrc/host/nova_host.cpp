@@ -7,6 +7,7 @@
 #include <deque>
 #include <thread>
 #include "nova_internal.hpp"
+#include "rounds.hpp"
 
 using namespace vdfnova;
 
@@ -56,16 +57,25 @@ std::unique_ptr<StepCircuit> make_primary_circuit(const vdf_pp* pp, const Circui
 }  // namespace vdfnova
 
 // ---- the step-circuit seam in the C ABI (include/vdf_nova.h) --------------------------------------------------------
-struct vdf_cs { CS* cs; std::vector<Num> pool; bool bad = false; };
+namespace vdfnova {      // rounds_host.cpp: the same calls on the recording handle of a round body
+vdf_num rec_cs_const(vdf_cs* c, const vdf_fe* k);
+vdf_num rec_cs_bin(vdf_cs* c, int op, vdf_num a, vdf_num b);
+vdf_num rec_cs_scale(vdf_cs* c, vdf_num a, const vdf_fe* k);
+int rec_cs_enforce(vdf_cs* c, vdf_num a, vdf_num b, vdf_num cc);
+}
 namespace {
 const Num* cs_get(const vdf_cs* c, vdf_num h) { return h < c->pool.size() ? &c->pool[h] : nullptr; }
 vdf_num cs_put(vdf_cs* c, Num n) { c->pool.push_back(std::move(n)); return (vdf_num)(c->pool.size() - 1); }
 struct CustomStepCircuit : StepCircuit {
   vdf_step_circuit c;
+  vdf_ctx* ctx = nullptr;                 // a prover's: lets a vdf_cs_repeat take advice in device memory
   mutable int rc = 0;
+  mutable RepeatState rep;                // the vdf_cs_repeat of the last synthesis, if it had one
   size_t arity() const override { return c.arity; }
   std::vector<Num> synthesize(CS& cs, const std::vector<Num>& z) const override {
-    vdf_cs h{&cs, z, false};
+    vdf_cs h;
+    h.cs = &cs; h.pool = z; h.rep = &rep; h.ctx = ctx;
+    rep = RepeatState();
     std::vector<vdf_num> zin(c.arity), zout(c.arity, 0);
     for (size_t k = 0; k < c.arity; ++k) zin[k] = (vdf_num)k;
     rc = c.synthesize(c.self, &h, zin.data(), zout.data());
@@ -80,44 +90,53 @@ struct CustomStepCircuit : StepCircuit {
 };
 }  // namespace
 namespace vdfnova {
-std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c) {
+std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx) {
   std::unique_ptr<CustomStepCircuit> m(new CustomStepCircuit());
   m->c = *c;
+  m->ctx = ctx;
   return std::unique_ptr<StepCircuit>(m.release());
 }
 }  // namespace vdfnova
 
 extern "C" {
 int vdf_cs_is_witness(const vdf_cs* c) { return c && !c->cs->shape ? 1 : 0; }
-vdf_num vdf_cs_const(vdf_cs* c, const vdf_fe* k) { Fe v; memcpy(&v, k, 32); return cs_put(c, c->cs->constant(v)); }
-#define CS_BIN(name, op)                                                                      \
+vdf_num vdf_cs_const(vdf_cs* c, const vdf_fe* k) {
+  if (c->rec) return rec_cs_const(c, k);
+  Fe v; memcpy(&v, k, 32); return cs_put(c, c->cs->constant(v));
+}
+#define CS_BIN(name, op, rop)                                                                 \
   vdf_num name(vdf_cs* c, vdf_num a, vdf_num b) {                                             \
+    if (c->rec) return rec_cs_bin(c, rop, a, b);                                              \
     const Num *x = cs_get(c, a), *y = cs_get(c, b);                                           \
     if (!x || !y) { c->bad = true; return 0; }                                                \
     return cs_put(c, c->cs->op(*x, *y));                                                      \
   }
-CS_BIN(vdf_cs_add, add)
-CS_BIN(vdf_cs_sub, sub)
-CS_BIN(vdf_cs_mul, mul)
+CS_BIN(vdf_cs_add, add, R_ADD)
+CS_BIN(vdf_cs_sub, sub, R_SUB)
+CS_BIN(vdf_cs_mul, mul, R_MUL)
 #undef CS_BIN
 vdf_num vdf_cs_scale(vdf_cs* c, vdf_num a, const vdf_fe* k) {
+  if (c->rec) return rec_cs_scale(c, a, k);
   const Num* x = cs_get(c, a);
   if (!x) { c->bad = true; return 0; }
   Fe v; memcpy(&v, k, 32);
   return cs_put(c, c->cs->scale(*x, v));
 }
 vdf_num vdf_cs_alloc(vdf_cs* c, const vdf_fe* value) {
+  if (c->rec) { c->bad = true; return 0; }           // a round body's variables come from vdf_cs_mul and vdf_cs_alloc_from
   Fe v = zero();
   if (value && !c->cs->shape) memcpy(&v, value, 32);
   return cs_put(c, c->cs->alloc(v));
 }
 int vdf_cs_enforce(vdf_cs* c, vdf_num a, vdf_num b, vdf_num cc) {
+  if (c->rec) return rec_cs_enforce(c, a, b, cc);
   const Num *x = cs_get(c, a), *y = cs_get(c, b), *z = cs_get(c, cc);
   if (!x || !y || !z) { c->bad = true; return VDF_ERR_BAD_ARG; }
   c->cs->enforce(*x, *y, *z);
   return VDF_OK;
 }
 int vdf_cs_value(const vdf_cs* c, vdf_num a, vdf_fe* out) {
+  if (c->rec) { const_cast<vdf_cs*>(c)->bad = true; return VDF_ERR_BAD_ARG; }      // a recording has no values
   const Num* x = cs_get(c, a);
   if (!x || !out) return VDF_ERR_BAD_ARG;
   memcpy(out, &x->v, 32);
@@ -152,8 +171,9 @@ struct HostShape { Coo m[3]; size_t num_cons = 0, num_vars = 0, step_begin = 0, 
 
 // both augmented circuits in shape mode (PublicParams::setup, src/nova/proof.rs:236)
 // (fid: the orientation, the primary circuit's field)
+// (rep_out: the custom circuit's vdf_cs_repeat as its shape synthesis recorded it, `used` false without one)
 int build_shapes(int fid, uint64_t t, int circuit_kind, HostShape out[2], const vdf_step_circuit* custom = nullptr, const RoInstance* ro = nullptr,
-                 size_t lanes = 1) {
+                 size_t lanes = 1, RepeatState* rep_out = nullptr) {
   vdf_pp tmp;
   tmp.t = t;
   tmp.circuit_kind = circuit_kind;
@@ -169,6 +189,7 @@ int build_shapes(int fid, uint64_t t, int circuit_kind, HostShape out[2], const 
     synthesize_augmented(cs, side, blank, *step);
     if (side == PRIMARY && custom && static_cast<const CustomStepCircuit*>(step.get())->rc != 0)
       return fail(VDF_ERR_BAD_ARG, "the step circuit's synthesize failed while its shape was recorded");
+    if (side == PRIMARY && custom && rep_out) *rep_out = std::move(static_cast<const CustomStepCircuit*>(step.get())->rep);
     cs.finish(out[side].m);
     out[side].num_cons = cs.rows;
     out[side].num_vars = cs.W.size();
@@ -247,7 +268,8 @@ int alloc_proof_buffers(vdf_proof* p) {
     HIPCALL(ctx, vdf_dev_memset(ctx, st.d_z, 0, sd.ncols * 32));
     HIPCALL(ctx, vdf_dev_memset(ctx, st.d_E, 0, sd.num_cons * 32));
     for (int k = 0; k < 3; ++k) HIPCALL(ctx, vdf_dev_memset(ctx, st.d_abc[k], 0, sd.num_cons * 32));
-    HIPCALL(ctx, vdf_host_alloc(ctx, (sd.ncols - (s == PRIMARY ? pp->seg_len : 0)) * 32, (void**)&p->h_stage[s]));
+    // (a custom circuit's device segment is per step: a step with host advice stages the whole witness)
+    HIPCALL(ctx, vdf_host_alloc(ctx, (sd.ncols - (s == PRIMARY && pp->circuit_kind != VDF_CIRCUIT_CUSTOM ? pp->seg_len : 0)) * 32, (void**)&p->h_stage[s]));
   }
   HIPCALL(ctx, vdf_dev_alloc(ctx, pp->s[SECONDARY].ncols * 32, &p->d_l2z));
   for (int k = 0; k < vdf_proof::RING; ++k) {
@@ -993,12 +1015,13 @@ static int public_params_impl(vdf_ctx* ctx, int fid, uint64_t t, int circuit_kin
   double mark = t_start;
   auto lap = [&](int k) -> int { HIPCALL(ctx, vdf_ctx_sync(ctx)); const double now = now_ms(); ms[k] += now - mark; mark = now; return VDF_OK; };
   HostShape sh[2];
-  { int rc = build_shapes(fid, t, circuit_kind, sh, custom, pp->ro, lanes); if (rc != VDF_OK) return rc; }
+  { int rc = build_shapes(fid, t, circuit_kind, sh, custom, pp->ro, lanes, &pp->round); if (rc != VDF_OK) return rc; }
   digest_shapes(fid, t, gens_family, sh, pp->digest, pp->ro);
-  // only the MinRoot rounds are made on the device; a custom circuit's variables all come from the host
-  pp->seg_begin = custom ? 0 : sh[PRIMARY].step_begin;
-  pp->seg_len = custom ? 0 : sh[PRIMARY].step_end - sh[PRIMARY].step_begin;
-  if (pp->seg_len) {
+  // only the MinRoot rounds are made on the device; of a custom circuit the variables of its vdf_cs_repeat, when a step's advice is
+  // in device memory (everything a built-in circuit gets on top of that -- early rows, lookahead, a stencil -- stays with them)
+  pp->seg_begin = custom ? (pp->round.used ? pp->round.var_begin : 0) : sh[PRIMARY].step_begin;
+  pp->seg_len = custom ? (pp->round.used ? (size_t)pp->round.t * pp->round.rec.n_vars : 0) : sh[PRIMARY].step_end - sh[PRIMARY].step_begin;
+  if (pp->seg_len && !custom) {
     // the longest run of primary constraints that read nothing of a witness but the segment, the step circuit's input z_in
     // (the `arity` variables allocated right before it, synthesize_augmented; known when a step begins) and the constant,
     // none of them a row the device sums by a wavefront (vdf_nifs_cross_term_rows)
@@ -1070,7 +1093,7 @@ static int public_params_impl(vdf_ctx* ctx, int fid, uint64_t t, int circuit_kin
   for (int s = 0; s < 2; ++s) {
     const Side& sd = pp->s[s];
     const size_t top = sd.num_vars > sd.num_cons ? sd.num_vars : sd.num_cons;
-    if (s == SECONDARY || pp->seg_len == 0) { dn[s][0] = top; nr[s] = 1; }
+    if (s == SECONDARY || pp->seg_len == 0 || custom) { dn[s][0] = top; nr[s] = 1; }
     else if (pp->ahead_rows) {
       const size_t se = pp->seg_begin + pp->seg_len, ae = pp->ahead_row + pp->ahead_rows;
       std::vector<std::pair<size_t, size_t>> iv = {{0, pp->seg_begin}, {se, sd.num_vars}, {0, pp->ahead_row}, {ae, sd.num_cons}};
@@ -1289,7 +1312,8 @@ struct StepRun {
   const Side& S2;
   const Field& F1;
   const Field& F2;
-  const size_t seg_b, seg_n, seg_e;    // the primary witness's run of round variables
+  const size_t seg_b, seg_n, seg_e;    // the primary witness's run of round variables made AHEAD of the step (a custom circuit: none -- the
+                                       // rounds of its vdf_cs_repeat are written inside the step, chain_primary_circuit)
   const int per;
   const bool forward;                  // the forward step circuit in pp->lanes lanes: rounds by vdf_minroot_forward_segment_lanes, stencil code 5 / 6
   const bool t_ahead;                  // this step has early rows
@@ -1320,8 +1344,8 @@ struct StepRun {
 
   StepRun(vdf_pp* pp_, vdf_proof* p_, const vdf_circuits* circuits_, size_t k_, const vdf_step_circuit* custom_, const Circuit& c_, bool first_)
       : pp(pp_), p(p_), circuits(circuits_), k(k_), custom(custom_), c(c_), first(first_), arity(pp_->arity), ctx(pp_->ctx), ct(p_->ctx3),
-        S1(pp_->s[PRIMARY]), S2(pp_->s[SECONDARY]), F1(*pp_->s[PRIMARY].F), F2(*pp_->s[SECONDARY].F), seg_b(pp_->seg_begin), seg_n(pp_->seg_len),
-        seg_e(pp_->seg_begin + pp_->seg_len), per(vars_per_round(pp_->circuit_kind)), forward(forward_kind(pp_->circuit_kind)),
+        S1(pp_->s[PRIMARY]), S2(pp_->s[SECONDARY]), F1(*pp_->s[PRIMARY].F), F2(*pp_->s[SECONDARY].F), seg_b(custom_ ? 0 : pp_->seg_begin),
+        seg_n(custom_ ? 0 : pp_->seg_len), seg_e(custom_ ? 0 : pp_->seg_begin + pp_->seg_len), per(vars_per_round(pp_->circuit_kind)), forward(forward_kind(pp_->circuit_kind)),
         t_ahead(!first_ && !custom_ && pp_->ahead_rows != 0), ta_b(pp_->ahead_row), ta_n(pp_->ahead_rows), ta_e(pp_->ahead_row + pp_->ahead_rows),
         t_parts(pp_->tune.early_row_parts), fold_on_rows(pp_->tune.fold_on_rows != 0), hb(&p_->h_pts[R]), early1(nullptr, aug_early_free),
         early2(nullptr, aug_early_free) {
@@ -1489,7 +1513,7 @@ struct StepRun {
       memset(&in1.u_W, 0, sizeof(Aff)); memset(&in1.T, 0, sizeof(Aff));
       for (int j = 0; j < 2; ++j) fe_to_int(p->l2.X[j], F2, in1.u_X[j]);
     }
-    c1 = custom ? make_custom_circuit(custom) : make_primary_circuit(pp, &c, true);
+    c1 = custom ? make_custom_circuit(custom, ctx) : make_primary_circuit(pp, &c, true);
     in2.ro = pp->ro;
   }
   // cross term of (running secondary, l2), commit(w2) unless known, commit(T2)
@@ -1545,9 +1569,24 @@ struct StepRun {
       const std::vector<Fe> z_next = synthesize_augmented(cs, PRIMARY, in, *c1, unew, r2, early1.get());
       early1.reset();
       if (custom && static_cast<const CustomStepCircuit*>(c1.get())->rc != 0) return fail(VDF_ERR_BAD_ARG, "the step circuit's synthesize failed");
-      if (cs.dev_len != seg_n || (seg_n && cs.dev_begin != seg_b)) return fail(VDF_ERR_DEVICE, "device segment moved");
+      const RepeatState* round = custom ? &static_cast<const CustomStepCircuit*>(c1.get())->rep : nullptr;
+      if (custom) {
+        // the body and the count the parameters were made with; the rounds on the device only where the parameters say they are
+        if (round->used != pp->round.used || (round->used && (round->t != pp->round.t || round->var_begin != pp->round.var_begin ||
+                                                             !round->rec.same_body(pp->round.rec))))
+          return fail(VDF_ERR_BAD_ARG, "the circuit's vdf_cs_repeat differs from the one these parameters were made with");
+        if (cs.dev_len && (!round->d_advice || cs.dev_len != pp->seg_len || cs.dev_begin != pp->seg_begin))
+          return fail(VDF_ERR_DEVICE, "device segment moved");
+      } else if (cs.dev_len != seg_n || (seg_n && cs.dev_begin != seg_b)) return fail(VDF_ERR_DEVICE, "device segment moved");
       t2 = now_ms();
       p->r[SECONDARY].inst = inst_from_elements(unew, F1, F2);       // base step: the default instance
+      if (custom && cs.dev_len) {
+        // the rounds of the circuit's vdf_cs_repeat, one repetition per thread, straight into the fresh witness: in front of the
+        // uploads around them and of the commitment of W, on the step's own queue
+        const vdf_round_tape tape = round->rec.view();
+        HIPCALL(ctx, vdf_round_tape_run(ctx, S1.field, &tape, round->t, (const vdf_fe*)round->inv.data(), (const vdf_fe*)round->d_advice,
+                                        (vdf_fe*)((char*)d_z2 + pp->seg_begin * 32)));
+      }
       // the host-made variables go next to the rounds the lookahead context has written (vdf_ctx_wait at their launch)
       int rc = upload_fresh(ctx, S1, cs, p->h_stage[PRIMARY], d_z2);
       if (rc != VDF_OK) return rc;

@@ -17,6 +17,7 @@
 #include "../../../include/vdf_nova.h"
 #include "host_math.hpp"
 #include "r1cs.hpp"
+#include "rounds.hpp"
 
 namespace vdfnova {
 using namespace vdfhost;
@@ -107,6 +108,9 @@ struct vdf_pp {
   Fe params[2];                            // the digest as an element of each side's field
   // variables of the primary witness that the GPU fills from the forward trace (the MinRoot rounds): [seg_begin, seg_begin + seg_len)
   size_t seg_begin = 0, seg_len = 0;
+  // a custom circuit's vdf_cs_repeat as its shape synthesis recorded it (the body, t, where its variables begin): every
+  // prove_step's own recording is compared with it; [seg_begin, seg_begin + seg_len) are its variables
+  vdfnova::RepeatState round;
   // constraints of the primary shape that read nothing of a fresh witness but that segment (and the constant): their
   // share of a step's cross term and of its commitment is made ahead of the rest, [ahead_row, ahead_row + ahead_rows)
   size_t ahead_row = 0, ahead_rows = 0;
@@ -264,7 +268,7 @@ bool tuning_valid(const vdf_nova_tuning& t);
 int alloc_proof_buffers(vdf_proof* p);
 int finalize_l2(const vdf_proof* p);      // commits to the last secondary witness if that is still pending
 std::unique_ptr<StepCircuit> make_primary_circuit(const vdf_pp* pp, const Circuit* c, bool device_rounds);
-std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c);
+std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx = nullptr);
 // ---- the circuits as the drivers of nova_host.cpp reach them (circuits_host.cpp) --------------------------------------------
 inline void eval_step(int field, int mode, uint64_t t, St* state, Fe* trace_xy) {   // t rounds from *state: the trace [2 (t + 1)], *state = the result
   vdf_state in, res;

@@ -1,0 +1,78 @@
+// Uniform rounds of a custom step circuit (include/vdf_nova.h vdf_cs_repeat): the body as recorded, its replay over a constraint
+// system, and the slot-allocated program the GPU runs (include/vdf_hip.h vdf_round_tape).  rounds_host.cpp.
+#pragma once
+#include <vector>
+#include "../../../include/vdf_nova.h"
+#include "r1cs.hpp"
+
+namespace vdfnova {
+
+// What a body did, call by call.  Nodes [0, n_inputs()) are its inputs in the order j, inv, carry, cur, next; every later node is
+// one vdf_cs_* call.  a, b, c name nodes, except: R_CONST a = index into consts; R_SCALE b = index into consts.
+enum RecOp : uint8_t { R_INPUT = 0, R_CONST, R_ADD, R_SUB, R_SCALE, R_MUL, R_ALLOC_FROM, R_ENFORCE };
+struct RecNode {
+  uint8_t op = R_INPUT;
+  bool value_only = false;         // made of advice values: no linear combination stands behind it
+  uint32_t a = 0, b = 0, c = 0;
+  bool operator==(const RecNode& o) const { return op == o.op && value_only == o.value_only && a == o.a && b == o.b && c == o.c; }
+};
+struct RoundRecord {
+  uint32_t n_inv = 0, n_carry = 0, n_adv = 0;
+  std::vector<RecNode> nodes;
+  std::vector<Fe> consts;
+  std::vector<uint32_t> carry_out;                 // nodes
+  uint32_t n_vars = 0, n_cons = 0;                 // per repetition
+  // the device program (compile()): inputs loaded at their first use, slots by a linear scan over live ranges
+  std::vector<vdf_tape_op> ops;
+  uint32_t n_slots = 0;
+
+  uint32_t n_inputs() const { return 1 + n_inv + n_carry + 2 * n_adv; }
+  uint32_t in_j() const { return 0; }
+  uint32_t in_inv(uint32_t k) const { return 1 + k; }
+  uint32_t in_carry(uint32_t k) const { return 1 + n_inv + k; }
+  uint32_t in_cur(uint32_t k) const { return 1 + n_inv + n_carry + k; }
+  uint32_t in_next(uint32_t k) const { return 1 + n_inv + n_carry + n_adv + k; }
+  bool same_body(const RoundRecord& o) const {
+    return n_inv == o.n_inv && n_carry == o.n_carry && n_adv == o.n_adv && nodes == o.nodes && consts == o.consts && carry_out == o.carry_out;
+  }
+  vdf_round_tape view() const {
+    vdf_round_tape t;
+    t.ops = ops.data(); t.n_ops = ops.size();
+    t.consts = (const vdf_fe*)consts.data(); t.n_consts = consts.size();
+    t.n_slots = n_slots; t.n_vars = n_vars; t.n_cons = n_cons; t.n_inv = n_inv; t.n_adv = n_adv;
+    return t;
+  }
+};
+
+// the one vdf_cs_repeat of a custom circuit's synthesis, as the prover needs it afterwards
+struct RepeatState {
+  bool used = false;
+  RoundRecord rec;
+  uint64_t t = 0;
+  size_t var_begin = 0;                            // index of the first variable of repetition 0 in the witness
+  const void* d_advice = nullptr;                  // witness mode, advice in device memory: the variables were skipped (cs.dev_begin / dev_len)
+  std::vector<Fe> inv;                             // ... and the values of inv, for the kernel
+};
+
+// Runs the body once on a recording handle; VDF_ERR_BAD_ARG (message through fail()) for a body that fails, uses a handle it does not
+// own or exceeds a cap.  `is_witness`: what vdf_cs_is_witness answers inside the body.
+int record_round_body(CS* cs, const vdf_round_body* b, RoundRecord* out);
+// One repetition over cs with real calls.  carry: n_carry numbers, replaced by the repetition's carry_out.  cur / next: the advice
+// entries' values (witness mode; carry values are overridden by cur), or null (shape mode).  scratch: reused between repetitions.
+void replay_round(CS& cs, const RoundRecord& r, uint64_t j, const std::vector<Num>& inv, std::vector<Num>& carry, const Fe* cur, const Fe* next,
+                  std::vector<Num>& scratch);
+// the device program's semantics on the host (vdf_nova_round_tape_eval); checks every index like the launcher does
+int eval_round_tape(int field, const vdf_round_tape* tape, uint64_t t, const Fe* inv, const Fe* advice, Fe* out);
+
+}  // namespace vdfnova
+
+// the handle a synthesize callback receives; `rec` set: the recording handle a round body receives (cs is then only asked for its mode)
+struct vdf_cs {
+  vdfnova::CS* cs = nullptr;
+  std::vector<vdfnova::Num> pool;
+  bool bad = false;
+  vdfnova::RoundRecord* rec = nullptr;
+  vdfnova::RepeatState* rep = nullptr;             // where a vdf_cs_repeat on this handle leaves its record (null: repeats are refused)
+  vdf_ctx* ctx = nullptr;                          // for advice in device memory: the copy of its last entry (null: such advice is refused)
+  uint32_t rec_calls = 0;
+};

@@ -319,6 +319,8 @@ Status vec_step_segment(int field, const void* trace_xy, uint64_t t, const vdf_f
 // the forward circuit's variables for `lanes` traces lane_stride entries apart, lane-major into out (one launch; i_end: `lanes` host elements)
 Status vec_forward_segment_lanes(int field, const void* trace_xy, size_t lane_stride, uint64_t t, size_t lanes, const vdf_fe* i_end, void* out,
                                  hipStream_t s);
+// rounds.hip: a recorded round run over t repetitions (every index of the tape is checked before the launch; inv: host)
+Status vec_round_tape(int field, const vdf_round_tape* tape, uint64_t t, const vdf_fe* inv, const void* advice, void* out, hipStream_t s);
 Status vec_step_z(int field, const void* trace_xy, uint64_t t, const vdf_fe z_in[3], const vdf_fe* i0, const vdf_fe* u,
                   const vdf_fe X[6], void* z, void* packed, hipStream_t s);
 Status vec_nifs_cross(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3],

@@ -1,0 +1,123 @@
+// Round tapes (include/vdf_hip.h vdf_round_tape): the variables of t uniform repetitions of a step-circuit round that the host
+// layer recorded from a callback (libvdf_nova.so vdf_cs_repeat) -- the device side of the step-circuit seam
+// (/root/reference/src/nova/proof.rs:79-153, trait StepCircuit) for rounds this library did not write itself.
+//
+// One thread per repetition, workgroups of one wavefront.  The tape travels in the kernel arguments, so every lane reads the same
+// op through scalar loads and the branch on the opcode is uniform.  The value file is in LDS, not in registers: a slot number is
+// a run-time value, and a private array indexed by one would live in scratch.  Layout [slot][half][lane] of 16-byte halves, so a
+// wavefront's access to one half of one slot is 64 consecutive uint4 (1 KiB): conflict-free under ds_read_b128 / ds_write_b128's
+// lane groups.  A lane only ever touches its own column: no barrier.  LDS per workgroup is n_slots x 2 KiB, chosen at launch --
+// the slot allocation of the recorder (live ranges, linear scan) is what keeps occupancy up, not the length of the tape.
+#include <cstring>
+#include "internal.h"
+#include "fe.cuh"
+
+namespace vdf {
+
+struct TapeFe { uint32_t v[8]; };
+struct TapeArgs {
+  uint32_t n_ops, n_vars, n_adv, pad;
+  uint32_t ops[VDF_TAPE_MAX_OPS];                   // op | dst << 8 | a << 16 | b << 24
+  TapeFe consts[VDF_TAPE_MAX_CONSTS];
+  TapeFe inv[VDF_TAPE_MAX_INV];
+};
+static_assert(sizeof(TapeArgs) + 32 <= 4096, "the tape travels in the kernel-argument segment");
+
+template <class P> __device__ __forceinline__ Fe<P> tape_fe(const TapeFe& a) {
+  Fe<P> r;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) r.v[i] = a.v[i];
+  return r;
+}
+template <class P> __device__ __forceinline__ Fe<P> slot_load(const uint4* lds, uint32_t slot, uint32_t lane) {
+  const uint4 lo = lds[(slot * 2) * 64 + lane], hi = lds[(slot * 2 + 1) * 64 + lane];
+  Fe<P> r;
+  r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
+  r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
+  return r;
+}
+template <class P> __device__ __forceinline__ void slot_store(uint4* lds, uint32_t slot, uint32_t lane, const Fe<P>& a) {
+  lds[(slot * 2) * 64 + lane] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
+  lds[(slot * 2 + 1) * 64 + lane] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
+}
+
+template <class P>
+__global__ __launch_bounds__(64) void k_round_tape(TapeArgs tape, const char* __restrict__ advice, uint64_t t, char* __restrict__ out) {
+  extern __shared__ uint4 tape_slots[];
+  __builtin_amdgcn_s_setprio(3);     // light kernel: do not starve behind a co-running k_accumulate
+  const uint32_t lane = threadIdx.x;
+  const uint64_t j = (uint64_t)blockIdx.x * 64 + lane;
+  if (j >= t) return;
+  const char* adv = advice + j * tape.n_adv * 32;
+  char* o = out + j * tape.n_vars * 32;
+  for (uint32_t i = 0; i < tape.n_ops; ++i) {
+    const uint32_t w = tape.ops[i];
+    const uint32_t op = w & 0xFF, dst = (w >> 8) & 0xFF, a = (w >> 16) & 0xFF, b = w >> 24;
+    Fe<P> r;
+    switch (op) {
+      case VDF_TAPE_ADV: r = fe_load<P>(adv + (b * tape.n_adv + a) * 32); break;
+      case VDF_TAPE_INV: r = tape_fe<P>(tape.inv[a]); break;
+      case VDF_TAPE_J: r = fe_from_u64<P>(j); break;
+      case VDF_TAPE_CONST: r = tape_fe<P>(tape.consts[a]); break;
+      case VDF_TAPE_ADD: r = fe_add(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
+      case VDF_TAPE_SUB: r = fe_sub(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
+      case VDF_TAPE_MUL: {
+        const Fe<P> x = slot_load<P>(tape_slots, a, lane);
+        r = a == b ? fe_sqr(x) : fe_mul(x, slot_load<P>(tape_slots, b, lane));
+        break;
+      }
+      case VDF_TAPE_SCALE: r = fe_mul(slot_load<P>(tape_slots, a, lane), tape_fe<P>(tape.consts[b])); break;
+      default:                       // VDF_TAPE_OUT (the launcher admits no other opcode)
+        fe_store<P>(o + b * 32, slot_load<P>(tape_slots, a, lane));
+        continue;
+    }
+    slot_store<P>(tape_slots, dst, lane, r);
+  }
+}
+
+static TapeFe tape_val(const vdf_fe* p) { TapeFe v; std::memcpy(&v, p, 32); return v; }
+
+// Everything a tape could index out of range is checked here, before the launch: opcodes, slots against n_slots, columns,
+// constants, invariants and variables against their counts, reads of slots nothing has written, variables written twice or never.
+Status vec_round_tape(int field, const vdf_round_tape* tp, uint64_t t, const vdf_fe* inv, const void* advice, void* out, hipStream_t s) {
+  if (!tp || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts)) return Status{VDF_ERR_BAD_ARG, "null tape"};
+  if (tp->n_ops > VDF_TAPE_MAX_OPS || tp->n_consts > VDF_TAPE_MAX_CONSTS || tp->n_slots > VDF_TAPE_MAX_SLOTS || tp->n_vars > VDF_TAPE_MAX_VARS ||
+      tp->n_inv > VDF_TAPE_MAX_INV || tp->n_adv > VDF_TAPE_MAX_ADV || tp->n_vars == 0 || tp->n_adv == 0 || tp->n_slots == 0)
+    return Status{VDF_ERR_BAD_ARG, "tape exceeds a published cap (VDF_TAPE_MAX_*), or has no variable, slot or advice column"};
+  if (tp->n_inv && !inv) return Status{VDF_ERR_BAD_ARG, "null inv"};
+  TapeArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.n_ops = (uint32_t)tp->n_ops; a.n_vars = tp->n_vars; a.n_adv = tp->n_adv;
+  bool written[VDF_TAPE_MAX_SLOTS] = {}, var_out[VDF_TAPE_MAX_VARS] = {};
+  for (size_t i = 0; i < tp->n_ops; ++i) {
+    const vdf_tape_op& o = tp->ops[i];
+    auto slot_ok = [&](uint8_t x) { return x < tp->n_slots && written[x]; };
+    bool ok = false;
+    switch (o.op) {
+      case VDF_TAPE_ADV: ok = o.a < tp->n_adv && o.b <= 1; break;
+      case VDF_TAPE_INV: ok = o.a < tp->n_inv; break;
+      case VDF_TAPE_J: ok = true; break;
+      case VDF_TAPE_CONST: ok = o.a < tp->n_consts; break;
+      case VDF_TAPE_ADD: case VDF_TAPE_SUB: case VDF_TAPE_MUL: ok = slot_ok(o.a) && slot_ok(o.b); break;
+      case VDF_TAPE_SCALE: ok = slot_ok(o.a) && o.b < tp->n_consts; break;
+      case VDF_TAPE_OUT: ok = slot_ok(o.a) && o.b < tp->n_vars && !var_out[o.b]; if (ok) var_out[o.b] = true; break;
+      default: break;
+    }
+    if (ok && o.op != VDF_TAPE_OUT) { ok = o.dst < tp->n_slots; if (ok) written[o.dst] = true; }
+    if (!ok) return Status{VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + " is malformed (opcode, index out of range, or a slot read before it is written)"};
+    a.ops[i] = (uint32_t)o.op | (uint32_t)o.dst << 8 | (uint32_t)o.a << 16 | (uint32_t)o.b << 24;
+  }
+  for (uint32_t v = 0; v < tp->n_vars; ++v)
+    if (!var_out[v]) return Status{VDF_ERR_BAD_ARG, "tape leaves variable " + std::to_string(v) + " unwritten"};
+  for (size_t k = 0; k < tp->n_consts; ++k) a.consts[k] = tape_val(&tp->consts[k]);
+  for (uint32_t k = 0; k < tp->n_inv; ++k) a.inv[k] = tape_val(&inv[k]);
+  // advice read + variables written per repetition
+  KTimer kt(s, "k_round_tape", 32.0 * (tp->n_adv + tp->n_vars) * t);
+  const dim3 grid((unsigned)((t + 63) / 64));
+  const size_t lds = (size_t)tp->n_slots * 2 * 64 * sizeof(uint4);
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_round_tape<tag_t<decltype(f)>>), grid, dim3(64), lds, s, a, cbytes_of(advice), t, bytes_of(out));
+  });
+}
+
+}  // namespace vdf

@@ -47,6 +47,31 @@ class IpaOpening(C.Structure):
                 ("pattern", C.c_void_p)]
 
 
+class TapeOp(C.Structure):
+    """vdf_tape_op: one op of a round tape (include/vdf_hip.h VDF_TAPE_*)."""
+    _fields_ = [("op", C.c_uint8), ("dst", C.c_uint8), ("a", C.c_uint8), ("b", C.c_uint8)]
+
+
+class RoundTapeC(C.Structure):
+    _fields_ = [("ops", C.POINTER(TapeOp)), ("n_ops", C.c_size_t), ("consts", C.c_void_p), ("n_consts", C.c_size_t),
+                ("n_slots", C.c_uint32), ("n_vars", C.c_uint32), ("n_cons", C.c_uint32), ("n_inv", C.c_uint32), ("n_adv", C.c_uint32)]
+
+
+TAPE_MAX_OPS, TAPE_MAX_CONSTS, TAPE_MAX_SLOTS, TAPE_MAX_VARS, TAPE_MAX_INV, TAPE_MAX_ADV = 320, 24, 24, 64, 16, 8
+
+
+class RoundTape:
+    """vdf_round_tape with the arrays it points into (vdf_amd.nova.record_round_body makes one)."""
+
+    def __init__(self):
+        self.ops = (TapeOp * TAPE_MAX_OPS)()
+        self.consts = np.zeros((TAPE_MAX_CONSTS, 4), dtype="<u8")
+        self.c = RoundTapeC()
+
+    def op_list(self):
+        return [(o.op, o.dst, o.a, o.b) for o in self.ops[:self.c.n_ops]]
+
+
 class VdfError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"vdf_hip error {code}: {msg}")
@@ -418,6 +443,10 @@ class Context:
     def minroot_forward_segment_lanes(self, field, trace_xy, lane_stride, t, lanes, i_end, out) -> None:
         """The same for `lanes` traces lane_stride entries apart, lane-major into out, in one launch; i_end: `lanes` host elements."""
         self._check(lib.vdf_minroot_forward_segment_lanes(self.handle, field, _ptr(trace_xy), lane_stride, t, lanes, _ptr(i_end), _ptr(out)))
+
+    def round_tape_run(self, field, tape: "RoundTape", t, inv, advice, out) -> None:
+        """t repetitions of a recorded round, one GPU thread each: out (device, t * n_vars elements); inv: host, advice: device."""
+        self._check(lib.vdf_round_tape_run(self.handle, field, C.addressof(tape.c), t, _ptr(inv), _ptr(advice), _ptr(out)))
 
     def minroot_step_segment_packed(self, field, trace_xy, t, i0, i_in, out, packed) -> None:
         """The reference's allocation (4 variables per round) and the 3t + 4 scalars of its commitment without new_x."""

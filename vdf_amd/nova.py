@@ -10,7 +10,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .hip import Context, VdfError
+from .hip import Context, VdfError, RoundTape, _ptr
 from .minroot import State, _State, _Fe, nova_lib, EvalMode, MinRootVDF, PallasVDF, VestaVDF, FIELD_FP, FIELD_FQ  # noqa: F401
 
 _vp, _i, _u64, _sz = C.c_void_p, C.c_int, C.c_uint64, C.c_size_t
@@ -92,6 +92,10 @@ for _name, _res, _args in [
     ("vdf_cs_mul", C.c_uint32, [_vp, C.c_uint32, C.c_uint32]),
     ("vdf_cs_enforce", _i, [_vp, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("vdf_cs_value", _i, [_vp, C.c_uint32, _vp]),
+    ("vdf_cs_alloc_from", C.c_uint32, [_vp, C.c_uint32]),
+    ("vdf_cs_repeat", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    ("vdf_nova_round_body_record", _i, [_i, _vp, _vp, _vp, _vp]),
+    ("vdf_nova_round_tape_eval", _i, [_i, _vp, _u64, _vp, _vp, _vp]),
     ("vdf_nova_synthesis_stats", _i, [C.POINTER(_u64), C.POINTER(_u64)]),
     ("vdf_nova_compress", _i, [_vp, _vp, C.POINTER(_vp)]),
     ("vdf_nova_compress_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_vp)]),
@@ -301,6 +305,69 @@ class _StepCircuitC(C.Structure):
     _fields_ = [("arity", C.c_size_t), ("synthesize", _SYNTH), ("self", C.c_void_p)]
 
 
+_BODY = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
+
+
+class _RoundBodyC(C.Structure):
+    _fields_ = [("n_inv", C.c_size_t), ("n_carry", C.c_size_t), ("n_adv", C.c_size_t), ("body", _BODY), ("self", C.c_void_p)]
+
+
+class RoundBody:
+    """vdf_round_body: one round of a uniform loop.  Subclass (or construct) with n_inv / n_carry / n_adv and
+    `body(cs, j, inv, carry, cur, next) -> carry_out` (lists of handles); it runs ONCE, on a recording ConstraintSystem
+    (include/vdf_nova.h, vdf_cs_repeat: cur / next are value-only)."""
+    n_inv, n_carry, n_adv = 0, 0, 1
+
+    def __init__(self, n_inv=None, n_carry=None, n_adv=None, body=None):
+        for k, v in (("n_inv", n_inv), ("n_carry", n_carry), ("n_adv", n_adv), ("body", body)):
+            if v is not None:
+                setattr(self, k, v)
+
+    def body(self, cs, j, inv, carry, cur, next):
+        raise NotImplementedError
+
+    def _c(self):
+        def cb(_self, cs, j, inv, carry, cur, nxt, out):
+            try:
+                res = self.body(ConstraintSystem(cs), j, [inv[k] for k in range(self.n_inv)], [carry[k] for k in range(self.n_carry)],
+                                [cur[k] for k in range(self.n_adv)], [nxt[k] for k in range(self.n_adv)])
+                res = list(res or [])
+                if len(res) != self.n_carry:
+                    raise ValueError("a round body returns n_carry handles")
+                for k in range(self.n_carry):
+                    out[k] = res[k]
+                return 0
+            except Exception as e:            # must not unwind through the C frames
+                self._error = e
+                return 1
+        self._error = None
+        self._cb = _BODY(cb)                  # kept alive with the body
+        self._struct = _RoundBodyC(self.n_inv, self.n_carry, self.n_adv, self._cb, None)
+        return self._struct
+
+
+def record_round_body(body: RoundBody, field: int = FIELD_FQ) -> RoundTape:
+    """Host only: the body recorded and compiled into the tape Context.round_tape_run / round_tape_eval take."""
+    tape = RoundTape()
+    rc = nova_lib.vdf_nova_round_body_record(field, C.addressof(body._c()), C.addressof(tape.ops), tape.consts.ctypes.data, C.addressof(tape.c))
+    _reraise(body)
+    _check(rc)
+    return tape
+
+
+def round_tape_eval(field: int, tape: RoundTape, t: int, inv, advice) -> np.ndarray:
+    """Host only: what Context.round_tape_run writes, uint64[t * n_vars, 4]; inv, advice: uint64[., 4] arrays (Montgomery form)."""
+    inv = np.ascontiguousarray(inv, dtype="<u8").reshape(-1, 4)
+    advice = np.ascontiguousarray(advice, dtype="<u8").reshape(-1, 4)
+    if inv.shape[0] < tape.c.n_inv or advice.shape[0] < (t + 1) * tape.c.n_adv:
+        raise ValueError("inv or advice shorter than the tape reads")
+    out = np.zeros((t * tape.c.n_vars, 4), dtype="<u8")
+    _check(nova_lib.vdf_nova_round_tape_eval(field, C.addressof(tape.c), t, inv.ctypes.data if tape.c.n_inv else None, advice.ctypes.data,
+                                             out.ctypes.data))
+    return out
+
+
 class ConstraintSystem:
     """The vdf_cs a step circuit's synthesize receives: numbers are opaque handles; field elements cross as 32-byte
     Montgomery limbs of the primary circuit's field (Fq, or Fp under public_params_custom(..., field=FIELD_FP))."""
@@ -337,6 +404,31 @@ class ConstraintSystem:
         out = _Fe()
         _check(nova_lib.vdf_cs_value(self.h, a, C.byref(out)))
         return bytes(out)
+
+    def alloc_from(self, src: int) -> int:
+        """A new variable with src's value and no constraint."""
+        return nova_lib.vdf_cs_alloc_from(self.h, src)
+
+    def repeat(self, body: "RoundBody", t: int, inv, carry_in, advice=None):
+        """vdf_cs_repeat: t repetitions of `body`; returns the carry_out handles.  advice: (t + 1) x n_adv elements, entry-major --
+        bytes or a uint64[., 4] array (host), a device tensor or an address (device: the rounds then run on the GPU); None while
+        the shape is recorded."""
+        if len(inv) != body.n_inv or len(carry_in) != body.n_carry:
+            raise ValueError("inv / carry_in do not match the body's n_inv / n_carry")
+        if isinstance(advice, (bytes, bytearray)):
+            advice = np.frombuffer(bytes(advice), dtype="<u8")
+        if isinstance(advice, np.ndarray):
+            advice = np.ascontiguousarray(advice, dtype="<u8")
+            if advice.size * 8 < (t + 1) * body.n_adv * 32:
+                raise ValueError("advice is shorter than (t + 1) * n_adv elements")
+        if hasattr(advice, "data_ptr") and advice.numel() * advice.element_size() < (t + 1) * body.n_adv * 32:
+            raise ValueError("advice is shorter than (t + 1) * n_adv elements")
+        U = C.c_uint32
+        cin, cout, invs = (U * max(1, body.n_carry))(*carry_in), (U * max(1, body.n_carry))(), (U * max(1, body.n_inv))(*inv)
+        rc = nova_lib.vdf_cs_repeat(self.h, C.addressof(body._c()), t, invs, cin, _ptr(advice), cout)
+        _reraise(body)
+        _check(rc)
+        return [cout[k] for k in range(body.n_carry)]
 
 
 class StepCircuit:
