@@ -417,6 +417,47 @@ int  vdf_round_tape_run(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uin
                         vdf_fe* out);
 /* 1 when a kernel of this library may read p in place (device memory, or host memory of vdf_host_alloc), else 0 */
 int  vdf_ptr_is_device(const void* p);
+/* ---- walk tapes: the ADVICE of such rounds rebuilt on the device from checkpoints ---------------------------------------------
+ * The same seam in the other direction.  Every delay function of this family is slow one way (a root) and a handful of products
+ * per round the other way; a walk tape is that fast round, one advice entry computed from the one after it, and a walk is
+ * `rounds` of them, sequential, one GPU lane per walk -- vdf_minroot_inverse_walk for a round the library did not write, with an
+ * entry of n_adv elements where that call has a 64-byte (x, y).  Only this DESCENDING direction exists: the slow direction is a
+ * 254-bit exponentiation per round and does not fit a tape (vdf_minroot_forward_walk is the built-in one).
+ *
+ * A walk tape is a vdf_round_tape (same struct, same ops, same transport in the kernel arguments) read under these rules:
+ *   n_vars == n_adv          what a round writes is one advice entry
+ *   VDF_TAPE_ADV  b must be 1: slot[dst] = column a of the entry the walk stands on (entry j + 1); b = 0 would be the entry being
+ *                 produced and is refused
+ *   VDF_TAPE_OUT  column b of the produced entry (entry j) = slot[a]; every column exactly once.  An OUT does not disturb a later
+ *                 ADV of the same column in the same round
+ *   VDF_TAPE_J    j, the index of the produced entry -- the meaning j has in the round body, whose repetition j relates entries j
+ *                 and j + 1
+ * everything else as above.  vdf_nova.h vdf_nova_walk_body_record makes one from a callback.
+ *
+ * entries (device, n x n_adv elements): entries[w] is where walk w stands; it is overwritten with where it lands, so a long walk
+ * is cut into calls.  Strides are in ENTRIES.  With g = w / group and the local index k = (w % group) * walk_stride + top - r,
+ * r = 0 .. rounds - 1 (group = 0: all walks are one group and group_stride is ignored), walk w
+ *   writes the entry it stands on before round r to trace[(g * group_stride + k) * n_adv]      (trace: device, or NULL)
+ *   and sees VDF_TAPE_J = j_base + g * j_group_step + k - 1 in that round (arithmetic modulo 2^64),
+ * so a window of steps laid out trace after trace sees a chain-global counter under one host `inv`.  top >= rounds - 1.
+ * heads != 0: the first walk of each group also writes the entry it lands on, at local index top - rounds (then top >= rounds):
+ * with walk_stride = top = rounds one launch leaves complete traces 0 .. t, one per group, each entry written once -- what
+ * vdf_cs_repeat reads as advice.  expect (device, n x n_adv, or NULL): ok[w] (device, required with expect) = 1 iff the landing
+ * equals expect[w] in every column -- the checkpoint check, so that nothing comes back to the host but n ints.
+ *
+ * Refused with VDF_ERR_BAD_ARG before anything is launched: a malformed tape (opcode, slot, column, constant, a read before a
+ * write, a column written twice or never), n_vars != n_adv, an ADV with b = 0, top < rounds - 1 (heads: top < rounds) with a
+ * trace, expect without ok, a device pointer where host memory is read or the reverse, n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS
+ * (the value file and the two entries are 2 KiB of LDS each per wavefront: 64 KiB, the most a launch gets without asking), and
+ * rounds * max(1, products per round) > VDF_WALK_MAX_WORK (products: the tape's MUL and SCALE ops) -- the order of the built-in
+ * walk's own cap of 2^22 rounds of three products, so that one launch holds a queue no longer than the built-in one may; callers
+ * cut longer walks into calls.  n = 0 or rounds = 0 do nothing.
+ * Exact: every value is canonical after every op; entries and trace are byte for byte vdf_nova_walk_tape_eval's (vdf_nova.h). */
+#define VDF_WALK_MAX_SLOTS 32
+#define VDF_WALK_MAX_WORK (1ull << 23)
+int  vdf_round_tape_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n,
+                         uint64_t rounds, vdf_fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride,
+                         uint64_t j_base, uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok);
 /* vdf_spmv3(shape, z2) followed by vdf_cross_term(Az1, Bz1, Cz1, Az2, Bz2, Cz2, u1): writes Az2, Bz2, Cz2
  * (num_cons each) and T.  u1: host memory.  (nova-snark NIFS::prove -> commit_T, K4 + K5.) */
 int  vdf_nifs_cross_term(vdf_ctx* ctx, const vdf_shape* shape, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,

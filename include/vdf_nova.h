@@ -470,6 +470,33 @@ int  vdf_nova_round_body_record(int field, const vdf_round_body* b, vdf_tape_op 
                                 vdf_round_tape* out);
 /* Host only.  What vdf_round_tape_run computes, on the host: out = the t n_vars variables (inv, advice, out: host memory). */
 int  vdf_nova_round_tape_eval(int field, const vdf_round_tape* tape, uint64_t t, const vdf_fe* inv, const vdf_fe* advice, vdf_fe* out);
+/* ---- walk bodies: the advice of such rounds, rebuilt on the GPU from checkpoints (vdf_hip.h vdf_round_tape_walk) -------------
+ * The fast direction of the round, written once: `next` holds the n_adv columns of advice entry j + 1, `j` the index of the entry
+ * to produce (the j of the round body whose repetition j relates entries j and j + 1), `inv` n_inv loop-invariant values; the body
+ * stores the handle of every column of entry j in cur_out.  It is called once, on a recording vdf_cs, where vdf_cs_add, _sub,
+ * _scale, _const and _mul are VALUE arithmetic: _mul makes no variable and no constraint.  vdf_cs_alloc, _alloc_from, _enforce,
+ * _value, _repeat and handles the body was not given or did not make set the failure flag: VDF_ERR_BAD_ARG.  cur_out[c] may be
+ * any handle the body owns: an input passed straight through, or one handle in two columns.  Slots are allocated as for a round
+ * body (inputs loaded at first use, live ranges, a linear scan).  The caps are VDF_ROUND_MAX_INV / _ADV / _OPS / _CONSTS / _LIVE,
+ * and live values + 2 * n_adv <= VDF_WALK_MAX_SLOTS; one beyond is VDF_ERR_BAD_ARG.  Only this direction can be recorded: the slow
+ * direction of a delay function is an exponentiation by a 254-bit number and does not fit a tape.
+ *
+ * The chain's checkpoints (vdf_minroot_eval_checkpoints, or the caller's own evaluator) are then all a prover needs: one
+ * vdf_round_tape_walk per window of steps leaves the traces where vdf_cs_repeat reads its advice, and checks every landing
+ * against the checkpoint below it.  examples/prove_custom_checkpoints.c. */
+typedef struct {
+  size_t n_inv, n_adv;
+  int (*body)(void* self, vdf_cs* cs, vdf_num j, const vdf_num* inv, const vdf_num* next, vdf_num* cur_out);      /* 0 = ok */
+  void* self;
+} vdf_walk_body;
+/* Host only.  Records a walk body and hands out its walk tape (ops / consts as vdf_nova_round_body_record); n_vars = n_adv, n_cons = 0. */
+int  vdf_nova_walk_body_record(int field, const vdf_walk_body* b, vdf_tape_op ops[VDF_TAPE_MAX_OPS], vdf_fe consts[VDF_TAPE_MAX_CONSTS],
+                               vdf_round_tape* out);
+/* Host only.  vdf_round_tape_walk restated on the host: the same arguments, the same refusals, every pointer host memory -- the
+ * reference of the device path, byte for byte. */
+int  vdf_nova_walk_tape_eval(int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n, uint64_t rounds,
+                             vdf_fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride, uint64_t j_base,
+                             uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok);
 
 /* public_params / prove_step / verify for a custom primary step circuit (the secondary stays TrivialTestCircuit).
  * z0, zi: `arity` elements.  compress, verify_compressed and the wire formats work on such proofs unchanged. */

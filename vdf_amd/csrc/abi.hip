@@ -1505,6 +1505,21 @@ int vdf_round_tape_run(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uint
   });
 }
 
+int vdf_round_tape_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n, uint64_t rounds,
+                        vdf_fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride, uint64_t j_base,
+                        uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok) {
+  return guarded(ctx, [&]() -> Status {
+    if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv))
+      return Status{VDF_ERR_BAD_ARG, "the tape and inv live in host memory"};
+    if (n && rounds && (!ptr_is_device(entries) || (trace && !ptr_is_device(trace)) || (expect && !ptr_is_device(expect)) || (ok && !ptr_is_device(ok))))
+      return Status{VDF_ERR_BAD_ARG, "entries, trace, expect and ok live in device memory"};
+    VDF_TRY(vdf::vec_round_tape_walk(field, tape, inv, entries, n, rounds, trace, walk_stride, top, group, group_stride, j_base, j_group_step,
+                                     heads, expect, ok, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
 int vdf_ptr_is_device(const void* p) { return ptr_is_device(p) ? 1 : 0; }
 
 static Status nifs_cross_impl(vdf_ctx* ctx, const vdf_shape* shape, size_t row_begin, size_t row_count, int part, const vdf_fe* z2,

@@ -63,6 +63,12 @@ void replay_round(CS& cs, const RoundRecord& r, uint64_t j, const std::vector<Nu
                   std::vector<Num>& scratch);
 // the device program's semantics on the host (vdf_nova_round_tape_eval); checks every index like the launcher does
 int eval_round_tape(int field, const vdf_round_tape* tape, uint64_t t, const Fe* inv, const Fe* advice, Fe* out);
+// A walk body (vdf_nova.h vdf_walk_body) run once on a recording handle and compiled into a walk tape: the record has no carry, no
+// variable and no constraint; its n_vars = n_adv columns are the handles the body left in cur_out.
+int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out);
+// vdf_round_tape_walk on the host (vdf_nova_walk_tape_eval): the same arguments, the same refusals, host memory
+int eval_walk_tape(int field, const vdf_round_tape* tape, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* trace, size_t walk_stride,
+                   size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok);
 
 }  // namespace vdfnova
 
@@ -75,4 +81,5 @@ struct vdf_cs {
   vdfnova::RepeatState* rep = nullptr;             // where a vdf_cs_repeat on this handle leaves its record (null: repeats are refused)
   vdf_ctx* ctx = nullptr;                          // for advice in device memory: the copy of its last entry (null: such advice is refused)
   uint32_t rec_calls = 0;
+  bool walk = false;                               // the recording is a walk body's (vdf_nova_walk_body_record): value arithmetic only
 };

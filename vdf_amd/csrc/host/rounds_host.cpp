@@ -13,7 +13,9 @@ constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;
 
 // node of a handle the body owns, or -1 (and the failure flag)
 long rec_node(vdf_cs* c, vdf_num h) {
-  if ((h & REC_TAG) && (h & ~REC_TAG) < c->rec->nodes.size()) return (long)(h & ~REC_TAG);
+  const uint32_t k = h & ~REC_TAG;
+  // (a walk body is handed no entry but `next`: the inputs a round body calls cur are not its own)
+  if ((h & REC_TAG) && k < c->rec->nodes.size() && !(c->walk && k >= c->rec->in_cur(0) && k < c->rec->in_next(0))) return (long)k;
   c->bad = true;
   return -1;
 }
@@ -35,7 +37,9 @@ uint32_t rec_const(vdf_cs* c, const vdf_fe* k) {
 // Inputs are loaded where they are first used, every value keeps its slot until its last use, and an operand that dies at an op
 // gives its slot up before the result takes one (the kernel reads both operands before it writes).  A value that no variable
 // depends on gets neither an op nor a slot.  alloc_from makes no value of its own: the variable is its source's slot, written out.
-int compile_round(RoundRecord& r) {
+// outs (a walk body): what is written out is not the products but the nodes outs[c], column c, at the end of the tape -- a product
+// is a value like any other, an output stays alive to the end, and an input that is passed straight through is loaded there.
+int compile_round(RoundRecord& r, const std::vector<uint32_t>* outs = nullptr) {
   const size_t n = r.nodes.size(), nin = r.n_inputs();
   std::vector<uint32_t> root(n);
   for (size_t i = 0; i < n; ++i) root[i] = r.nodes[i].op == R_ALLOC_FROM ? root[r.nodes[i].a] : (uint32_t)i;
@@ -48,9 +52,10 @@ int compile_round(RoundRecord& r) {
   };
   std::vector<char> needed(n, 0);
   std::vector<long> last_use(n, -1);
+  if (outs) for (uint32_t o : *outs) { needed[o] = 1; last_use[o] = (long)n; }
   for (size_t i = n; i-- > nin;) {
     const RecNode& x = r.nodes[i];
-    if (x.op == R_MUL || x.op == R_ALLOC_FROM) needed[i] = 1;
+    if (!outs && (x.op == R_MUL || x.op == R_ALLOC_FROM)) needed[i] = 1;
     if (!needed[i] || x.op == R_ENFORCE) continue;
     uint32_t o[2];
     const int k = operands(x, o);
@@ -70,21 +75,21 @@ int compile_round(RoundRecord& r) {
   };
   r.ops.clear();
   uint32_t var = 0;
+  auto load_input = [&](uint32_t in) {
+    if (in >= nin || slot[in] != NO_SLOT) return;
+    slot[in] = take();
+    if (in == r.in_j()) emit(VDF_TAPE_J, slot[in], 0, 0);
+    else if (in < r.in_carry(0)) emit(VDF_TAPE_INV, slot[in], in - r.in_inv(0), 0);
+    else if (in < r.in_cur(0)) emit(VDF_TAPE_ADV, slot[in], in - r.in_carry(0), 0);      // carry c IS advice entry j, column c
+    else if (in < r.in_next(0)) emit(VDF_TAPE_ADV, slot[in], in - r.in_cur(0), 0);
+    else emit(VDF_TAPE_ADV, slot[in], in - r.in_next(0), 1);
+  };
   for (size_t i = nin; i < n; ++i) {
     const RecNode& x = r.nodes[i];
     if (x.op == R_ENFORCE || !needed[i]) continue;
     uint32_t o[2];
     const int k = operands(x, o);
-    for (int q = 0; q < k; ++q) {                   // inputs at their first use
-      const uint32_t in = o[q];
-      if (in >= nin || slot[in] != NO_SLOT) continue;
-      slot[in] = take();
-      if (in == r.in_j()) emit(VDF_TAPE_J, slot[in], 0, 0);
-      else if (in < r.in_carry(0)) emit(VDF_TAPE_INV, slot[in], in - r.in_inv(0), 0);
-      else if (in < r.in_cur(0)) emit(VDF_TAPE_ADV, slot[in], in - r.in_carry(0), 0);      // carry c IS advice entry j, column c
-      else if (in < r.in_next(0)) emit(VDF_TAPE_ADV, slot[in], in - r.in_cur(0), 0);
-      else emit(VDF_TAPE_ADV, slot[in], in - r.in_next(0), 1);
-    }
+    for (int q = 0; q < k; ++q) load_input(o[q]);      // inputs at their first use
     const uint32_t sa = k > 0 ? slot[o[0]] : 0, sb = k > 1 ? slot[o[1]] : 0;
     for (int q = 0; q < k; ++q)
       if (last_use[o[q]] == (long)i && !(q == 1 && o[1] == o[0])) busy[slot[o[q]]] = 0;
@@ -93,11 +98,13 @@ int compile_round(RoundRecord& r) {
       case R_ADD: slot[i] = take(); emit(VDF_TAPE_ADD, slot[i], sa, sb); break;
       case R_SUB: slot[i] = take(); emit(VDF_TAPE_SUB, slot[i], sa, sb); break;
       case R_SCALE: slot[i] = take(); emit(VDF_TAPE_SCALE, slot[i], sa, x.b); break;
-      case R_MUL: slot[i] = take(); emit(VDF_TAPE_MUL, slot[i], sa, sb); emit(VDF_TAPE_OUT, 0, slot[i], var++); break;
+      case R_MUL: slot[i] = take(); emit(VDF_TAPE_MUL, slot[i], sa, sb); if (!outs) emit(VDF_TAPE_OUT, 0, slot[i], var++); break;
       default: emit(VDF_TAPE_OUT, 0, sa, var++); break;      // R_ALLOC_FROM
     }
     if (x.op != R_ALLOC_FROM && last_use[i] < 0) busy[slot[i]] = 0;      // a product nothing reads again
   }
+  if (outs)
+    for (uint32_t o : *outs) { load_input(o); emit(VDF_TAPE_OUT, 0, slot[o], var++); }
   r.n_slots = (uint32_t)busy.size();
   if (var != r.n_vars) return fail(VDF_ERR_DEVICE, "round tape: variable count drifted");
   if (r.n_slots > VDF_ROUND_MAX_LIVE) return fail(VDF_ERR_BAD_ARG, "the round body keeps more than VDF_ROUND_MAX_LIVE values alive at once");
@@ -221,6 +228,125 @@ int eval_round_tape(int fid, const vdf_round_tape* tp, uint64_t t, const Fe* inv
   return VDF_OK;
 }
 
+
+int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out) {
+  if (!b || !b->body) return fail(VDF_ERR_BAD_ARG, "walk body: null body");
+  if (b->n_inv > VDF_ROUND_MAX_INV || b->n_adv > VDF_ROUND_MAX_ADV || b->n_adv == 0)
+    return fail(VDF_ERR_BAD_ARG, "walk body: n_inv or n_adv beyond its cap (VDF_ROUND_MAX_*), or no advice column");
+  RoundRecord r;
+  r.n_inv = (uint32_t)b->n_inv; r.n_adv = (uint32_t)b->n_adv;
+  r.nodes.resize(r.n_inputs());
+  vdf_cs h;
+  h.cs = cs;
+  h.rec = &r;
+  h.walk = true;
+  std::vector<vdf_num> hin(r.n_inputs()), hout(r.n_adv, 0);
+  for (uint32_t k = 0; k < r.n_inputs(); ++k) hin[k] = REC_TAG | k;
+  const int rc = b->body(b->self, &h, hin[r.in_j()], hin.data() + r.in_inv(0), hin.data() + r.in_next(0), hout.data());
+  if (rc != 0) return fail(VDF_ERR_BAD_ARG, "walk body: the body failed");
+  if (h.rec_calls > VDF_ROUND_MAX_OPS) return fail(VDF_ERR_BAD_ARG, "walk body: more than VDF_ROUND_MAX_OPS calls");
+  if (r.consts.size() > VDF_ROUND_MAX_CONSTS) return fail(VDF_ERR_BAD_ARG, "walk body: more than VDF_ROUND_MAX_CONSTS constants");
+  if (h.bad) return fail(VDF_ERR_BAD_ARG, "walk body: a handle the body does not own, or a call that is not value arithmetic (alloc, alloc_from, enforce, value, repeat)");
+  std::vector<uint32_t> outs;
+  for (uint32_t k = 0; k < r.n_adv; ++k) {
+    const long nd = rec_node(&h, hout[k]);
+    if (nd < 0) return fail(VDF_ERR_BAD_ARG, "walk body: cur_out holds a handle the body does not own");
+    outs.push_back((uint32_t)nd);
+  }
+  r.n_vars = r.n_adv;
+  const int crc = compile_round(r, &outs);
+  if (crc != VDF_OK) return crc;
+  if (r.n_slots + 2 * r.n_adv > VDF_WALK_MAX_SLOTS) return fail(VDF_ERR_BAD_ARG, "walk body: live values + 2 * n_adv > VDF_WALK_MAX_SLOTS");
+  *out = std::move(r);
+  return VDF_OK;
+}
+
+// the walk rules of vdf_hip.h over a tape, once, before anything is evaluated -- what vec_round_tape_walk checks before a launch
+static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rounds) {
+  if (!tp || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts)) return fail(VDF_ERR_BAD_ARG, "null tape");
+  if (tp->n_ops > VDF_TAPE_MAX_OPS || tp->n_consts > VDF_TAPE_MAX_CONSTS || tp->n_slots > VDF_TAPE_MAX_SLOTS || tp->n_vars > VDF_TAPE_MAX_VARS ||
+      tp->n_inv > VDF_TAPE_MAX_INV || tp->n_adv > VDF_TAPE_MAX_ADV || tp->n_vars == 0 || tp->n_adv == 0 || tp->n_slots == 0)
+    return fail(VDF_ERR_BAD_ARG, "tape exceeds a published cap (VDF_TAPE_MAX_*), or has no variable, slot or advice column");
+  if (tp->n_vars != tp->n_adv) return fail(VDF_ERR_BAD_ARG, "walk tape: n_vars != n_adv (a round writes one advice entry)");
+  if (tp->n_inv && !inv) return fail(VDF_ERR_BAD_ARG, "null inv");
+  bool written[VDF_TAPE_MAX_SLOTS] = {}, col_out[VDF_TAPE_MAX_ADV] = {};
+  uint64_t products = 0;
+  for (size_t i = 0; i < tp->n_ops; ++i) {
+    const vdf_tape_op& o = tp->ops[i];
+    auto rd = [&](uint8_t x) { return x < tp->n_slots && written[x]; };
+    bool ok = false;
+    switch (o.op) {
+      case VDF_TAPE_ADV: ok = o.a < tp->n_adv && o.b == 1; break;
+      case VDF_TAPE_INV: ok = o.a < tp->n_inv; break;
+      case VDF_TAPE_J: ok = true; break;
+      case VDF_TAPE_CONST: ok = o.a < tp->n_consts; break;
+      case VDF_TAPE_ADD: case VDF_TAPE_SUB: ok = rd(o.a) && rd(o.b); break;
+      case VDF_TAPE_MUL: ok = rd(o.a) && rd(o.b); ++products; break;
+      case VDF_TAPE_SCALE: ok = rd(o.a) && o.b < tp->n_consts; ++products; break;
+      case VDF_TAPE_OUT: ok = rd(o.a) && o.b < tp->n_adv && !col_out[o.b]; if (ok) col_out[o.b] = true; break;
+      default: break;
+    }
+    if (ok && o.op != VDF_TAPE_OUT) { ok = o.dst < tp->n_slots; if (ok) written[o.dst] = true; }
+    if (!ok) return fail(VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + " is malformed (opcode, index out of range, or a slot read before it is written); a walk tape loads advice with b = 1 only");
+  }
+  for (uint32_t k = 0; k < tp->n_adv; ++k)
+    if (!col_out[k]) return fail(VDF_ERR_BAD_ARG, "tape leaves variable " + std::to_string(k) + " unwritten");
+  if (tp->n_slots + 2 * tp->n_adv > VDF_WALK_MAX_SLOTS) return fail(VDF_ERR_BAD_ARG, "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS");
+  if (rounds > VDF_WALK_MAX_WORK / (products ? products : 1))
+    return fail(VDF_ERR_BAD_ARG, "rounds x products per round > VDF_WALK_MAX_WORK in one call: cut the walk");
+  return VDF_OK;
+}
+
+int eval_walk_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* trace, size_t walk_stride,
+                   size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok) {
+  if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
+  const int rc = check_walk_tape(tp, inv, rounds);
+  if (rc != VDF_OK) return rc;
+  if (expect && !ok) return fail(VDF_ERR_BAD_ARG, "expect without ok");
+  if (n == 0 || rounds == 0) return VDF_OK;
+  if (n > ((size_t)1 << 31)) return fail(VDF_ERR_BAD_LENGTH, "more than 2^31 walks");
+  if (!entries) return fail(VDF_ERR_BAD_ARG, "null entries");
+  if (trace && top + 1 < rounds) return fail(VDF_ERR_BAD_ARG, "top < rounds - 1: the walk would write below its run");
+  if (trace && heads && top < rounds) return fail(VDF_ERR_BAD_ARG, "heads with top < rounds: the landing would be written below the run");
+  if (group == 0) { group = n; group_stride = 0; }
+  const Field& F = field(fid);
+  const Fe* consts = (const Fe*)tp->consts;
+  const size_t na = tp->n_adv;
+  Fe s[VDF_TAPE_MAX_SLOTS], stand[VDF_TAPE_MAX_ADV], prod[VDF_TAPE_MAX_ADV];
+  for (size_t w = 0; w < n; ++w) {
+    const uint64_t g = w / group, first = (w % group) * walk_stride + top;
+    Fe* tr = trace ? trace + (g * group_stride + first) * na : nullptr;
+    uint64_t j = j_base + g * j_group_step + first - 1;
+    for (size_t c = 0; c < na; ++c) stand[c] = entries[w * na + c];
+    for (uint64_t r = 0; r < rounds; ++r, --j) {
+      if (tr) {
+        for (size_t c = 0; c < na; ++c) tr[c] = stand[c];
+        tr -= na;
+      }
+      for (size_t i = 0; i < tp->n_ops; ++i) {
+        const vdf_tape_op& o = tp->ops[i];
+        switch (o.op) {
+          case VDF_TAPE_ADV: s[o.dst] = stand[o.a]; break;
+          case VDF_TAPE_INV: s[o.dst] = inv[o.a]; break;
+          case VDF_TAPE_J: s[o.dst] = from_u64(j, F); break;
+          case VDF_TAPE_CONST: s[o.dst] = consts[o.a]; break;
+          case VDF_TAPE_ADD: s[o.dst] = add(s[o.a], s[o.b], F); break;
+          case VDF_TAPE_SUB: s[o.dst] = sub(s[o.a], s[o.b], F); break;
+          case VDF_TAPE_MUL: s[o.dst] = mul(s[o.a], s[o.b], F); break;
+          case VDF_TAPE_SCALE: s[o.dst] = mul(s[o.a], consts[o.b], F); break;
+          default: prod[o.b] = s[o.a]; break;      // VDF_TAPE_OUT
+        }
+      }
+      for (size_t c = 0; c < na; ++c) stand[c] = prod[c];
+    }
+    for (size_t c = 0; c < na; ++c) entries[w * na + c] = stand[c];
+    if (tr && heads && w % group == 0)
+      for (size_t c = 0; c < na; ++c) tr[c] = stand[c];
+    if (expect) ok[w] = memcmp(stand, expect + w * na, na * sizeof(Fe)) == 0;
+  }
+  return VDF_OK;
+}
+
 }  // namespace vdfnova
 
 // ---- the recording side of the vdf_cs_* calls (nova_host.cpp hands a call over when the handle records) ------------------
@@ -232,7 +358,7 @@ vdf_num rec_cs_const(vdf_cs* c, const vdf_fe* k) {
 vdf_num rec_cs_bin(vdf_cs* c, int op, vdf_num a, vdf_num b) {
   const long x = rec_node(c, a), y = rec_node(c, b);
   if (x < 0 || y < 0) return 0;
-  const bool vo = c->rec->nodes[x].value_only || c->rec->nodes[y].value_only;
+  const bool vo = c->rec->nodes[x].value_only || c->rec->nodes[y].value_only;      // (never set in a walk body: a product there is a value)
   if (op == R_MUL && vo) { c->bad = true; return 0; }      // a constraint over a value without a linear combination
   return rec_push(c, (uint8_t)op, vo, (uint32_t)x, (uint32_t)y, 0);
 }
@@ -242,6 +368,7 @@ vdf_num rec_cs_scale(vdf_cs* c, vdf_num a, const vdf_fe* k) {
   return rec_push(c, R_SCALE, c->rec->nodes[x].value_only, (uint32_t)x, rec_const(c, k), 0);
 }
 int rec_cs_enforce(vdf_cs* c, vdf_num a, vdf_num b, vdf_num cc) {
+  if (c->walk) { c->bad = true; return VDF_ERR_BAD_ARG; }      // a walk body computes values: it has nothing to constrain
   const long x = rec_node(c, a), y = rec_node(c, b), z = rec_node(c, cc);
   if (x < 0 || y < 0 || z < 0) return VDF_ERR_BAD_ARG;
   const std::vector<RecNode>& nd = c->rec->nodes;
@@ -256,6 +383,7 @@ extern "C" {
 vdf_num vdf_cs_alloc_from(vdf_cs* c, vdf_num src) {
   if (!c) return 0;
   if (c->rec) {
+    if (c->walk) { c->bad = true; return 0; }          // a walk body makes no variable
     const long x = rec_node(c, src);
     return x < 0 ? 0 : rec_push(c, R_ALLOC_FROM, false, (uint32_t)x, 0, 0);
   }
@@ -341,6 +469,32 @@ int vdf_nova_round_body_record(int fid, const vdf_round_body* b, vdf_tape_op ops
 
 int vdf_nova_round_tape_eval(int fid, const vdf_round_tape* tape, uint64_t t, const vdf_fe* inv, const vdf_fe* advice, vdf_fe* out) {
   return nova_guard([&]() -> int { return eval_round_tape(fid, tape, t, (const Fe*)inv, (const Fe*)advice, (Fe*)out); });
+}
+
+int vdf_nova_walk_body_record(int fid, const vdf_walk_body* b, vdf_tape_op ops[VDF_TAPE_MAX_OPS], vdf_fe consts[VDF_TAPE_MAX_CONSTS],
+                              vdf_round_tape* out) {
+  return nova_guard([&]() -> int {
+    if (!valid_field(fid) || !ops || !consts || !out) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    CS cs(fid, true);
+    RoundRecord rec;
+    const int rc = record_walk_body(&cs, b, &rec);
+    if (rc != VDF_OK) return rc;
+    *out = rec.view();
+    memcpy(ops, rec.ops.data(), rec.ops.size() * sizeof(vdf_tape_op));
+    if (!rec.consts.empty()) memcpy(consts, rec.consts.data(), rec.consts.size() * 32);      // (a body may have no constant)
+    out->ops = ops;
+    out->consts = consts;
+    return VDF_OK;
+  });
+}
+
+int vdf_nova_walk_tape_eval(int fid, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n, uint64_t rounds, vdf_fe* trace,
+                            size_t walk_stride, size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step, int heads,
+                            const vdf_fe* expect, int32_t* ok) {
+  return nova_guard([&]() -> int {
+    return eval_walk_tape(fid, tape, (const Fe*)inv, (Fe*)entries, n, rounds, (Fe*)trace, walk_stride, top, group, group_stride, j_base,
+                          j_group_step, heads, (const Fe*)expect, ok);
+  });
 }
 
 }  // extern "C"

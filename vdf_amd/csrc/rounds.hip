@@ -75,17 +75,94 @@ __global__ __launch_bounds__(64) void k_round_tape(TapeArgs tape, const char* __
   }
 }
 
+// ---- walk tapes: the advice itself, rebuilt from checkpoints (vdf_hip.h vdf_round_tape_walk) ---------------------------------
+// k_inverse_walk's launch (one lane per walk, workgroups of one wavefront, wave priority left at 0: background work beside a
+// prover) around k_round_tape's interpreter.  Two entries of n_adv slots follow the value file in LDS: the one the walk stands on
+// and the one the round produces, swapped on the round's parity -- an OUT to column c never touches what a later ADV of column c
+// reads.  The slot numbers of both are scalars; nothing is indexed by a run-time value outside LDS.  A round is sequential after
+// the one before it, so unlike k_round_tape the interpreter's scalar loads of the tape recur every round: they stay in the
+// scalar cache (2.5 KiB of arguments).
+struct WalkArgs {
+  uint64_t n, walk_stride, top, group, group_stride, j_base, j_group_step;
+  uint32_t rounds, n_slots, heads, pad;
+};
+static_assert(sizeof(TapeArgs) + sizeof(WalkArgs) + 32 <= 4096, "the tape travels in the kernel-argument segment");
+
+template <class P>
+__global__ __launch_bounds__(64) void k_tape_walk(TapeArgs tape, WalkArgs wa, char* __restrict__ entries, char* __restrict__ trace,
+                                                  const char* __restrict__ expect, int32_t* __restrict__ ok) {
+  extern __shared__ uint4 tape_slots[];
+  const uint32_t lane = threadIdx.x;
+  const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
+  if (w >= wa.n) return;                             // (no barrier below: a lane touches only its own words of LDS)
+  const uint32_t na = tape.n_adv;
+  const size_t esz = (size_t)na * 32;
+  char* const ep = entries + w * esz;
+  const uint64_t g = w / wa.group, first = (w % wa.group) * wa.walk_stride + wa.top;      // local index of the entry the walk stands on
+  uint32_t stand = wa.n_slots, prod = wa.n_slots + na;
+  for (uint32_t c = 0; c < na; ++c) slot_store<P>(tape_slots, stand + c, lane, fe_load<P>(ep + c * 32));
+  char* tp = trace ? trace + (g * wa.group_stride + first) * esz : nullptr;
+  uint64_t j = wa.j_base + g * wa.j_group_step + first - 1;
+#pragma unroll 1
+  for (uint32_t r = 0; r < wa.rounds; ++r, --j) {
+    if (tp) {
+      for (uint32_t c = 0; c < na; ++c) fe_store<P>(tp + c * 32, slot_load<P>(tape_slots, stand + c, lane));
+      tp -= esz;
+    }
+#pragma unroll 1
+    for (uint32_t i = 0; i < tape.n_ops; ++i) {
+      const uint32_t x = tape.ops[i];
+      const uint32_t op = x & 0xFF, dst = (x >> 8) & 0xFF, a = (x >> 16) & 0xFF, b = x >> 24;
+      Fe<P> v;
+      switch (op) {
+        case VDF_TAPE_ADV: v = slot_load<P>(tape_slots, stand + a, lane); break;      // (the launcher admits b = 1 only)
+        case VDF_TAPE_INV: v = tape_fe<P>(tape.inv[a]); break;
+        case VDF_TAPE_J: v = fe_from_u64<P>(j); break;
+        case VDF_TAPE_CONST: v = tape_fe<P>(tape.consts[a]); break;
+        case VDF_TAPE_ADD: v = fe_add(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
+        case VDF_TAPE_SUB: v = fe_sub(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
+        case VDF_TAPE_MUL: {
+          const Fe<P> y = slot_load<P>(tape_slots, a, lane);
+          v = a == b ? fe_sqr(y) : fe_mul(y, slot_load<P>(tape_slots, b, lane));
+          break;
+        }
+        case VDF_TAPE_SCALE: v = fe_mul(slot_load<P>(tape_slots, a, lane), tape_fe<P>(tape.consts[b])); break;
+        default:                       // VDF_TAPE_OUT
+          slot_store<P>(tape_slots, prod + b, lane, slot_load<P>(tape_slots, a, lane));
+          continue;
+      }
+      slot_store<P>(tape_slots, dst, lane, v);
+    }
+    const uint32_t t = stand; stand = prod; prod = t;
+  }
+  // where the walk landed: back into entries, to the head of its group's trace, and against the checkpoint
+  uint32_t diff = 0;
+  const bool head = tp && wa.heads && w % wa.group == 0;
+  for (uint32_t c = 0; c < na; ++c) {
+    const Fe<P> v = slot_load<P>(tape_slots, stand + c, lane);
+    fe_store<P>(ep + c * 32, v);
+    if (head) fe_store<P>(tp + c * 32, v);
+    if (expect) {
+      const Fe<P> e = fe_load<P>(expect + w * esz + c * 32);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) diff |= v.v[q] ^ e.v[q];
+    }
+  }
+  if (expect) ok[w] = diff == 0;
+}
+
 static TapeFe tape_val(const vdf_fe* p) { TapeFe v; std::memcpy(&v, p, 32); return v; }
 
-// Everything a tape could index out of range is checked here, before the launch: opcodes, slots against n_slots, columns,
+// Everything a tape could index out of range is checked here, before a launch: opcodes, slots against n_slots, columns,
 // constants, invariants and variables against their counts, reads of slots nothing has written, variables written twice or never.
-Status vec_round_tape(int field, const vdf_round_tape* tp, uint64_t t, const vdf_fe* inv, const void* advice, void* out, hipStream_t s) {
+// walk: the rules of a walk tape on top (vdf_hip.h): n_vars == n_adv, no ADV of the entry being produced.
+static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, bool walk, TapeArgs& a) {
   if (!tp || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts)) return Status{VDF_ERR_BAD_ARG, "null tape"};
   if (tp->n_ops > VDF_TAPE_MAX_OPS || tp->n_consts > VDF_TAPE_MAX_CONSTS || tp->n_slots > VDF_TAPE_MAX_SLOTS || tp->n_vars > VDF_TAPE_MAX_VARS ||
       tp->n_inv > VDF_TAPE_MAX_INV || tp->n_adv > VDF_TAPE_MAX_ADV || tp->n_vars == 0 || tp->n_adv == 0 || tp->n_slots == 0)
     return Status{VDF_ERR_BAD_ARG, "tape exceeds a published cap (VDF_TAPE_MAX_*), or has no variable, slot or advice column"};
+  if (walk && tp->n_vars != tp->n_adv) return Status{VDF_ERR_BAD_ARG, "walk tape: n_vars != n_adv (a round writes one advice entry)"};
   if (tp->n_inv && !inv) return Status{VDF_ERR_BAD_ARG, "null inv"};
-  TapeArgs a;
   std::memset(&a, 0, sizeof(a));
   a.n_ops = (uint32_t)tp->n_ops; a.n_vars = tp->n_vars; a.n_adv = tp->n_adv;
   bool written[VDF_TAPE_MAX_SLOTS] = {}, var_out[VDF_TAPE_MAX_VARS] = {};
@@ -94,7 +171,7 @@ Status vec_round_tape(int field, const vdf_round_tape* tp, uint64_t t, const vdf
     auto slot_ok = [&](uint8_t x) { return x < tp->n_slots && written[x]; };
     bool ok = false;
     switch (o.op) {
-      case VDF_TAPE_ADV: ok = o.a < tp->n_adv && o.b <= 1; break;
+      case VDF_TAPE_ADV: ok = o.a < tp->n_adv && (walk ? o.b == 1 : o.b <= 1); break;
       case VDF_TAPE_INV: ok = o.a < tp->n_inv; break;
       case VDF_TAPE_J: ok = true; break;
       case VDF_TAPE_CONST: ok = o.a < tp->n_consts; break;
@@ -104,19 +181,58 @@ Status vec_round_tape(int field, const vdf_round_tape* tp, uint64_t t, const vdf
       default: break;
     }
     if (ok && o.op != VDF_TAPE_OUT) { ok = o.dst < tp->n_slots; if (ok) written[o.dst] = true; }
-    if (!ok) return Status{VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + " is malformed (opcode, index out of range, or a slot read before it is written)"};
+    if (!ok) return Status{VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + " is malformed (opcode, index out of range, or a slot read before it is written)" +
+                                            (walk ? "; a walk tape loads advice with b = 1 only" : "")};
     a.ops[i] = (uint32_t)o.op | (uint32_t)o.dst << 8 | (uint32_t)o.a << 16 | (uint32_t)o.b << 24;
   }
   for (uint32_t v = 0; v < tp->n_vars; ++v)
     if (!var_out[v]) return Status{VDF_ERR_BAD_ARG, "tape leaves variable " + std::to_string(v) + " unwritten"};
   for (size_t k = 0; k < tp->n_consts; ++k) a.consts[k] = tape_val(&tp->consts[k]);
   for (uint32_t k = 0; k < tp->n_inv; ++k) a.inv[k] = tape_val(&inv[k]);
+  return Status{};
+}
+
+Status vec_round_tape(int field, const vdf_round_tape* tp, uint64_t t, const vdf_fe* inv, const void* advice, void* out, hipStream_t s) {
+  TapeArgs a;
+  VDF_TRY(pack_tape(tp, inv, false, a));
   // advice read + variables written per repetition
   KTimer kt(s, "k_round_tape", 32.0 * (tp->n_adv + tp->n_vars) * t);
   const dim3 grid((unsigned)((t + 63) / 64));
   const size_t lds = (size_t)tp->n_slots * 2 * 64 * sizeof(uint4);
   return with_field(field, [&](auto f) {
     hipLaunchKernelGGL((k_round_tape<tag_t<decltype(f)>>), grid, dim3(64), lds, s, a, cbytes_of(advice), t, bytes_of(out));
+  });
+}
+
+Status vec_round_tape_walk(int field, const vdf_round_tape* tp, const vdf_fe* inv, void* entries, size_t n, uint64_t rounds, void* trace,
+                           size_t walk_stride, size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step,
+                           int heads, const void* expect, int32_t* ok, hipStream_t s) {
+  VDF_TRY(check_field(field));
+  TapeArgs a;
+  VDF_TRY(pack_tape(tp, inv, true, a));
+  if (tp->n_slots + 2 * tp->n_adv > VDF_WALK_MAX_SLOTS)
+    return Status{VDF_ERR_BAD_ARG, "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"};
+  uint64_t products = 0;
+  for (size_t i = 0; i < tp->n_ops; ++i) products += tp->ops[i].op == VDF_TAPE_MUL || tp->ops[i].op == VDF_TAPE_SCALE;
+  if (products == 0) products = 1;
+  if (rounds > VDF_WALK_MAX_WORK / products) return Status{VDF_ERR_BAD_ARG, "rounds x products per round > VDF_WALK_MAX_WORK in one call: cut the walk"};
+  if (expect && !ok) return Status{VDF_ERR_BAD_ARG, "expect without ok"};
+  if (n == 0 || rounds == 0) return Status{};
+  if (n > ((size_t)1 << 31)) return Status{VDF_ERR_BAD_LENGTH, "more than 2^31 walks"};
+  if (!entries) return Status{VDF_ERR_BAD_ARG, "null entries"};
+  if (trace && top + 1 < rounds) return Status{VDF_ERR_BAD_ARG, "top < rounds - 1: the walk would write below its run"};
+  if (trace && heads && top < rounds) return Status{VDF_ERR_BAD_ARG, "heads with top < rounds: the landing would be written below the run"};
+  if (group == 0) { group = n; group_stride = 0; }
+  WalkArgs wa;
+  std::memset(&wa, 0, sizeof(wa));
+  wa.n = n; wa.walk_stride = walk_stride; wa.top = top; wa.group = group; wa.group_stride = group_stride;
+  wa.j_base = j_base; wa.j_group_step = j_group_step;
+  wa.rounds = (uint32_t)rounds; wa.n_slots = tp->n_slots; wa.heads = heads != 0;
+  KTimer kt(s, "k_tape_walk", trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0);
+  const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv) * 2 * 64 * sizeof(uint4);
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_tape_walk<tag_t<decltype(f)>>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, wa, bytes_of(entries),
+                       bytes_of(trace), cbytes_of(expect), ok);
   });
 }
 

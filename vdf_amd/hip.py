@@ -58,6 +58,7 @@ class RoundTapeC(C.Structure):
 
 
 TAPE_MAX_OPS, TAPE_MAX_CONSTS, TAPE_MAX_SLOTS, TAPE_MAX_VARS, TAPE_MAX_INV, TAPE_MAX_ADV = 320, 24, 24, 64, 16, 8
+WALK_MAX_SLOTS, WALK_MAX_WORK = 32, 1 << 23        # VDF_WALK_MAX_SLOTS, VDF_WALK_MAX_WORK
 
 
 class RoundTape:
@@ -447,6 +448,16 @@ class Context:
     def round_tape_run(self, field, tape: "RoundTape", t, inv, advice, out) -> None:
         """t repetitions of a recorded round, one GPU thread each: out (device, t * n_vars elements); inv: host, advice: device."""
         self._check(lib.vdf_round_tape_run(self.handle, field, C.addressof(tape.c), t, _ptr(inv), _ptr(advice), _ptr(out)))
+
+    def round_tape_walk(self, field, tape: "RoundTape", inv, entries, n, rounds, trace=None, walk_stride=0, top=0, group=0, group_stride=0,
+                        j_base=0, j_group_step=0, heads=False, expect=None, ok=None) -> None:
+        """n walks of `rounds` rounds of a recorded walk body in place over `entries` (device, n x n_adv elements), one lane each;
+        strides in entries.  trace (device or None): walk w writes the entry it stands on before round r to entry
+        (w // group) * group_stride + (w % group) * walk_stride + top - r; heads: a group's first walk also writes its landing.
+        expect / ok (device, int32[n]): ok[w] = the landing equals expect[w].  inv: host."""
+        self._check(lib.vdf_round_tape_walk(self.handle, field, C.addressof(tape.c), _ptr(inv), _ptr(entries), n, rounds, _ptr(trace),
+                                            walk_stride, top, group, group_stride, j_base, j_group_step, int(bool(heads)), _ptr(expect),
+                                            _ptr(ok)))
 
     def minroot_step_segment_packed(self, field, trace_xy, t, i0, i_in, out, packed) -> None:
         """The reference's allocation (4 variables per round) and the 3t + 4 scalars of its commitment without new_x."""

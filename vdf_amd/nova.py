@@ -96,6 +96,8 @@ for _name, _res, _args in [
     ("vdf_cs_repeat", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     ("vdf_nova_round_body_record", _i, [_i, _vp, _vp, _vp, _vp]),
     ("vdf_nova_round_tape_eval", _i, [_i, _vp, _u64, _vp, _vp, _vp]),
+    ("vdf_nova_walk_body_record", _i, [_i, _vp, _vp, _vp, _vp]),
+    ("vdf_nova_walk_tape_eval", _i, [_i, _vp, _vp, _vp, _sz, _u64, _vp, _sz, _sz, _sz, _sz, _u64, _u64, _i, _vp, _vp]),
     ("vdf_nova_synthesis_stats", _i, [C.POINTER(_u64), C.POINTER(_u64)]),
     ("vdf_nova_compress", _i, [_vp, _vp, C.POINTER(_vp)]),
     ("vdf_nova_compress_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_vp)]),
@@ -366,6 +368,82 @@ def round_tape_eval(field: int, tape: RoundTape, t: int, inv, advice) -> np.ndar
     _check(nova_lib.vdf_nova_round_tape_eval(field, C.addressof(tape.c), t, inv.ctypes.data if tape.c.n_inv else None, advice.ctypes.data,
                                              out.ctypes.data))
     return out
+
+
+_WALK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
+
+
+class _WalkBodyC(C.Structure):
+    _fields_ = [("n_inv", C.c_size_t), ("n_adv", C.c_size_t), ("body", _WALK), ("self", C.c_void_p)]
+
+
+class WalkBody:
+    """vdf_walk_body: the fast direction of a round, advice entry j computed from entry j + 1.  Subclass (or construct) with
+    n_inv / n_adv and `body(cs, j, inv, next) -> cur` (n_adv handles); it runs ONCE, on a recording ConstraintSystem where add,
+    sub, scale, const and mul are value arithmetic and nothing else is allowed (include/vdf_nova.h)."""
+    n_inv, n_adv = 0, 1
+
+    def __init__(self, n_inv=None, n_adv=None, body=None):
+        for k, v in (("n_inv", n_inv), ("n_adv", n_adv), ("body", body)):
+            if v is not None:
+                setattr(self, k, v)
+
+    def body(self, cs, j, inv, next):
+        raise NotImplementedError
+
+    def _c(self):
+        def cb(_self, cs, j, inv, nxt, out):
+            try:
+                res = list(self.body(ConstraintSystem(cs), j, [inv[k] for k in range(self.n_inv)], [nxt[k] for k in range(self.n_adv)]) or [])
+                if len(res) != self.n_adv:
+                    raise ValueError("a walk body returns n_adv handles")
+                for k in range(self.n_adv):
+                    out[k] = res[k]
+                return 0
+            except Exception as e:            # must not unwind through the C frames
+                self._error = e
+                return 1
+        self._error = None
+        self._cb = _WALK(cb)                  # kept alive with the body
+        self._struct = _WalkBodyC(self.n_inv, self.n_adv, self._cb, None)
+        return self._struct
+
+
+def record_walk_body(body: WalkBody, field: int = FIELD_FQ) -> RoundTape:
+    """Host only: the walk body recorded and compiled into the walk tape Context.round_tape_walk / walk_tape_eval take."""
+    tape = RoundTape()
+    rc = nova_lib.vdf_nova_walk_body_record(field, C.addressof(body._c()), C.addressof(tape.ops), tape.consts.ctypes.data, C.addressof(tape.c))
+    _reraise(body)
+    _check(rc)
+    return tape
+
+
+def walk_tape_eval(field: int, tape: RoundTape, inv, entries: np.ndarray, n: int, rounds: int, trace: "np.ndarray | None" = None,
+                   walk_stride: int = 0, top: int = 0, group: int = 0, group_stride: int = 0, j_base: int = 0, j_group_step: int = 0,
+                   heads: bool = False, expect: "np.ndarray | None" = None, ok: "np.ndarray | None" = None) -> None:
+    """Host only: Context.round_tape_walk on the host, in place over numpy arrays (entries / trace / expect uint64[., 4]
+    Montgomery, ok int32[n]); the same arguments and the same refusals.  The arrays are checked against what the walks touch."""
+    def arr(x, dtype, what):
+        if x is None:
+            return None
+        if not isinstance(x, np.ndarray) or x.dtype != np.dtype(dtype) or not x.flags["C_CONTIGUOUS"] or not x.flags["WRITEABLE"]:
+            raise ValueError("%s: a writable C-contiguous %s array" % (what, dtype))
+        return x
+    na = tape.c.n_adv
+    inv = np.ascontiguousarray(inv if inv is not None else np.zeros((0, 4)), dtype="<u8").reshape(-1, 4)
+    entries, trace, expect, ok = arr(entries, "<u8", "entries"), arr(trace, "<u8", "trace"), arr(expect, "<u8", "expect"), arr(ok, "<i4", "ok")
+    if inv.shape[0] < tape.c.n_inv or entries.size < 4 * n * na or (expect is not None and expect.size < 4 * n * na) or \
+            (ok is not None and ok.size < n):
+        raise ValueError("inv, entries, expect or ok shorter than the walks read")
+    if trace is not None and n and rounds and top + 1 >= rounds:
+        g = group or n
+        last = ((n - 1) // g) * (group_stride if group else 0) + (min(n, g) - 1) * walk_stride + top
+        if trace.size < 4 * (last + 1) * na:
+            raise ValueError("trace shorter than the walks write")
+    _check(nova_lib.vdf_nova_walk_tape_eval(field, C.addressof(tape.c), inv.ctypes.data if tape.c.n_inv else None, entries.ctypes.data, n, rounds,
+                                            trace.ctypes.data if trace is not None else None, walk_stride, top, group, group_stride, j_base,
+                                            j_group_step, int(bool(heads)), expect.ctypes.data if expect is not None else None,
+                                            ok.ctypes.data if ok is not None else None))
 
 
 class ConstraintSystem:
