@@ -393,11 +393,13 @@ int  vdf_minroot_forward_segment_lanes(vdf_ctx* ctx, int field, const vdf_fe* tr
  *   VDF_TAPE_ADD / _SUB / _MUL   slot[dst] = slot[a] (+ - *) slot[b]   (a = b under _MUL is a squaring)
  *   VDF_TAPE_SCALE  slot[dst] = slot[a] * consts[b]
  *   VDF_TAPE_OUT    variable b of this repetition = slot[a]: out[j * n_vars + b]   (dst unused; b < n_vars)
+ *   VDF_TAPE_POW    slot[dst] = slot[a] ^ E, E = consts[b] read as a PLAIN 256-bit little-endian integer (no field element, no
+ *                   Montgomery form).  Forward walk tapes only (below): anywhere else it is a malformed op
  * advice: (t + 1) entries of n_adv elements, entry-major (a MinRoot trace is n_adv = 2).  A slot is read only after an op of
  * the same tape wrote it (refused otherwise) and every variable is written exactly once.  n_cons, the constraints per
  * repetition, is carried for the caller (constraints cost nothing here).  The caps below are refused with VDF_ERR_BAD_ARG. */
 enum { VDF_TAPE_ADV = 0, VDF_TAPE_INV = 1, VDF_TAPE_J = 2, VDF_TAPE_CONST = 3, VDF_TAPE_ADD = 4, VDF_TAPE_SUB = 5, VDF_TAPE_MUL = 6,
-       VDF_TAPE_SCALE = 7, VDF_TAPE_OUT = 8 };
+       VDF_TAPE_SCALE = 7, VDF_TAPE_OUT = 8, VDF_TAPE_POW = 9 };
 #define VDF_TAPE_MAX_OPS 320      /* ops of a tape (loads and stores included) */
 #define VDF_TAPE_MAX_CONSTS 24
 #define VDF_TAPE_MAX_SLOTS 24     /* live values: 2 KiB of LDS each per 64 repetitions */
@@ -421,8 +423,8 @@ int  vdf_ptr_is_device(const void* p);
  * The same seam in the other direction.  Every delay function of this family is slow one way (a root) and a handful of products
  * per round the other way; a walk tape is that fast round, one advice entry computed from the one after it, and a walk is
  * `rounds` of them, sequential, one GPU lane per walk -- vdf_minroot_inverse_walk for a round the library did not write, with an
- * entry of n_adv elements where that call has a 64-byte (x, y).  Only this DESCENDING direction exists: the slow direction is a
- * 254-bit exponentiation per round and does not fit a tape (vdf_minroot_forward_walk is the built-in one).
+ * entry of n_adv elements where that call has a 64-byte (x, y).  This call walks in the DESCENDING direction; the slow direction,
+ * a 254-bit exponentiation per round, is a forward walk tape (vdf_round_tape_forward_walk below, with VDF_TAPE_POW).
  *
  * A walk tape is a vdf_round_tape (same struct, same ops, same transport in the kernel arguments) read under these rules:
  *   n_vars == n_adv          what a round writes is one advice entry
@@ -458,6 +460,54 @@ int  vdf_ptr_is_device(const void* p);
 int  vdf_round_tape_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n,
                          uint64_t rounds, vdf_fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride,
                          uint64_t j_base, uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok);
+/* ---- forward walk tapes: the chain itself evaluated on the device, many chains at once --------------------------------------
+ * The ascending counterpart: the SLOW direction of the round, advice entry j + 1 computed from entry j, one GPU lane per chain --
+ * vdf_minroot_forward_walk for a round the library did not write, in that call's layout with an entry of n_adv elements in
+ * place of (x, y).  Like that call it is a THROUGHPUT feature for many chains (beacon lanes, sequential-work farms, test and
+ * benchmark corpora), NOT a faster VDF: a single chain on a lane is far slower than a host core.
+ *
+ * A forward walk tape is a vdf_round_tape read under these rules:
+ *   n_vars == n_adv          what a round writes is one advice entry
+ *   VDF_TAPE_ADV  b must be 0: slot[dst] = column a of the entry the walk stands on (entry j); b = 1 would be the entry being
+ *                 produced and is refused
+ *   VDF_TAPE_OUT  column b of the produced entry (entry j + 1) = slot[a]; every column exactly once.  An OUT does not disturb a
+ *                 later ADV of the same column in the same round
+ *   VDF_TAPE_J    j, the index of the entry the walk stands on -- the j of the round body whose repetition j relates entries j
+ *                 and j + 1
+ *   VDF_TAPE_POW  slot[dst] = slot[a] ^ E, E = the 256 bits of consts[b] as a plain little-endian integer.  E = 0 gives 1 (also
+ *                 for base 0), E = 1 copies, any E < 2^256 is accepted; the result is canonical like every other op's.  Left to
+ *                 right square-and-multiply from the top set bit: bitlen(E) - 1 squarings and popcount(E) - 1 products
+ * everything else as above.  vdf_nova.h vdf_nova_forward_body_record makes one from a callback (vdf_cs_pow).
+ *
+ * entries (device, n x n_adv elements): entries[w] is where walk w stands; it is overwritten with where it stands afterwards, so
+ * long chains are cut into calls.  Strides are in ENTRIES.  `base` = the rounds the walks have behind them; with g = base + r + 1
+ * the count after round r (r = 0 .. rounds - 1), walk w
+ *   writes the entry it produced to trace[(w * walk_stride + g) * n_adv]                        (trace: device, or NULL),
+ *   and to checkpoints[(w * cp_stride + g / every) * n_adv] when `every` divides g              (checkpoints: device, or NULL),
+ *   and sees VDF_TAPE_J = j_base + w * j_walk_step + base + r in that round (arithmetic modulo 2^64).
+ * Entry 0 and checkpoint 0 (where a walk starts) are the caller's to write; the caller sizes both arrays.
+ *
+ * Refused with VDF_ERR_BAD_ARG before anything is launched: a malformed tape (opcode, slot, column, constant, a read before a
+ * write, a column written twice or never), n_vars != n_adv, an ADV with b = 1, checkpoints without `every`, a device pointer where
+ * host memory is read or the reverse, n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS, and rounds * max(1, products per round) >
+ * VDF_FORWARD_TAPE_MAX_WORK, where MUL and SCALE count one product each and a POW of exponent E counts max(1, bitlen(E) - 1 +
+ * popcount(E) - 1): 2^20 is within a factor two of what the built-in forward walk allows one launch (2,048 rounds of 283
+ * products), so that one launch holds a queue no longer than that one may.  n = 0 or rounds = 0 do nothing.
+ * Exact: entries, checkpoints and trace are byte for byte vdf_nova_forward_tape_eval's (vdf_nova.h). */
+#define VDF_FORWARD_TAPE_MAX_WORK (1ull << 20)
+int  vdf_round_tape_forward_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n,
+                                 uint64_t rounds, vdf_fe* checkpoints, uint64_t every, size_t cp_stride, vdf_fe* trace,
+                                 size_t walk_stride, uint64_t base, uint64_t j_base, uint64_t j_walk_step);
+/* vdf_minroot_eval_batch for a forward walk tape: rounds_total rounds from initial[w] (n x n_adv elements), cut into launches of
+ * launch_rounds (0 = the largest count VDF_FORWARD_TAPE_MAX_WORK allows the tape, at most 1,024) enqueued on the context's stream.
+ * every = 0: out_entries[w * n_adv] = the final entry of chain w (n entries).  every > 0 (it must divide rounds_total,
+ * VDF_ERR_BAD_ARG otherwise): out_entries[(w * (rounds_total / every + 1) + k) * n_adv] = chain w after k * every rounds, k = 0
+ * (the initial entry) .. rounds_total / every -- per chain the checkpoint array vdf_round_tape_walk's `expect` is cut from.
+ * Chain w sees VDF_TAPE_J = j_base + w * j_walk_step + (rounds behind it).  initial / out_entries: host or device (a device
+ * `initial` is left as it was; they may not overlap).  tape, inv: host memory. */
+int  vdf_round_tape_eval_batch(vdf_ctx* ctx, int field, const vdf_round_tape* tape, const vdf_fe* inv, const vdf_fe* initial, size_t n,
+                               uint64_t rounds_total, uint64_t every, uint64_t launch_rounds, uint64_t j_base, uint64_t j_walk_step,
+                               vdf_fe* out_entries);
 /* vdf_spmv3(shape, z2) followed by vdf_cross_term(Az1, Bz1, Cz1, Az2, Bz2, Cz2, u1): writes Az2, Bz2, Cz2
  * (num_cons each) and T.  u1: host memory.  (nova-snark NIFS::prove -> commit_T, K4 + K5.) */
 int  vdf_nifs_cross_term(vdf_ctx* ctx, const vdf_shape* shape, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,

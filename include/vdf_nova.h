@@ -478,10 +478,10 @@ int  vdf_nova_round_tape_eval(int field, const vdf_round_tape* tape, uint64_t t,
  * _value, _repeat and handles the body was not given or did not make set the failure flag: VDF_ERR_BAD_ARG.  cur_out[c] may be
  * any handle the body owns: an input passed straight through, or one handle in two columns.  Slots are allocated as for a round
  * body (inputs loaded at first use, live ranges, a linear scan).  The caps are VDF_ROUND_MAX_INV / _ADV / _OPS / _CONSTS / _LIVE,
- * and live values + 2 * n_adv <= VDF_WALK_MAX_SLOTS; one beyond is VDF_ERR_BAD_ARG.  Only this direction can be recorded: the slow
- * direction of a delay function is an exponentiation by a 254-bit number and does not fit a tape.
+ * and live values + 2 * n_adv <= VDF_WALK_MAX_SLOTS; one beyond is VDF_ERR_BAD_ARG.  The slow direction of a delay function, an
+ * exponentiation by a 254-bit number, is recorded as a forward body (vdf_nova_forward_body_record below, vdf_cs_pow).
  *
- * The chain's checkpoints (vdf_minroot_eval_checkpoints, or the caller's own evaluator) are then all a prover needs: one
+ * The chain's checkpoints (vdf_round_tape_eval_batch, vdf_minroot_eval_checkpoints, or the caller's own evaluator) are then all a prover needs: one
  * vdf_round_tape_walk per window of steps leaves the traces where vdf_cs_repeat reads its advice, and checks every landing
  * against the checkpoint below it.  examples/prove_custom_checkpoints.c. */
 typedef struct {
@@ -497,6 +497,27 @@ int  vdf_nova_walk_body_record(int field, const vdf_walk_body* b, vdf_tape_op op
 int  vdf_nova_walk_tape_eval(int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n, uint64_t rounds,
                              vdf_fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride, uint64_t j_base,
                              uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok);
+/* ---- forward bodies: the chain itself evaluated on the GPU (vdf_hip.h vdf_round_tape_forward_walk / vdf_round_tape_eval_batch) --
+ * The slow direction of the round, written once, in the same struct: the `next` argument holds the n_adv columns of the entry the
+ * walk STANDS ON (entry j), `j` is that entry's index (the j of the round body whose repetition j relates entries j and j + 1),
+ * and the body stores the handle of every column of entry j + 1 in cur_out.  Everything else is as for a walk body -- value
+ * arithmetic only, the same refusals, the same caps, each refused one beyond -- with one more call:
+ *   vdf_cs_pow(cs, a, e) = a ^ e, e a PLAIN 256-bit little-endian integer (e = 0 gives 1, also for a = 0).  One call, one result
+ *   slot, the exponent one stored constant under VDF_ROUND_MAX_CONSTS.  It is legal ONLY while a forward body is recorded: on a
+ *   live vdf_cs, in a round body and in a descending walk body it sets the failure flag, as a bad handle does.  A power inside
+ *   a circuit would need constraints and is the circuit author's business.
+ * With the three bodies of one round (forward, walk, round) a delay function the library did not write runs the whole pipeline
+ * on the device: vdf_round_tape_eval_batch -> checkpoints -> vdf_round_tape_walk -> vdf_nova_prove_step_custom.
+ * examples/prove_custom_pipeline.c.  A throughput feature for many chains, not a faster single chain (vdf_hip.h). */
+vdf_num vdf_cs_pow(vdf_cs* cs, vdf_num a, const uint64_t e[4]);
+/* Host only.  Records a forward body and hands out its forward walk tape (ops / consts as vdf_nova_round_body_record); n_vars = n_adv, n_cons = 0. */
+int  vdf_nova_forward_body_record(int field, const vdf_walk_body* b, vdf_tape_op ops[VDF_TAPE_MAX_OPS], vdf_fe consts[VDF_TAPE_MAX_CONSTS],
+                                  vdf_round_tape* out);
+/* Host only.  vdf_round_tape_forward_walk restated on the host: the same arguments, the same refusals, every pointer host memory --
+ * the reference of the device path, byte for byte. */
+int  vdf_nova_forward_tape_eval(int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n, uint64_t rounds,
+                                vdf_fe* checkpoints, uint64_t every, size_t cp_stride, vdf_fe* trace, size_t walk_stride, uint64_t base,
+                                uint64_t j_base, uint64_t j_walk_step);
 
 /* public_params / prove_step / verify for a custom primary step circuit (the secondary stays TrivialTestCircuit).
  * z0, zi: `arity` elements.  compress, verify_compressed and the wire formats work on such proofs unchanged. */

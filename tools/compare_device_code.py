@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Compare the gfx950 code of two builds of libvdf_hip.so's objects, kernel by kernel (CPU only; no GPU is touched).
 
-  tools/compare_device_code.py <build dir A> <build dir B>        e.g. a checkout of the parent's vdf_amd/csrc/build and this one's
+  tools/compare_device_code.py <build dir A> <build dir B> [--new TEXT ...]
+                                                                 e.g. a checkout of the parent's vdf_amd/csrc/build and this one's
 
-For each of abi, msm, msm_direct, vecops, snark: the device code object is taken out of the .o, and the two sides are
+--new TEXT: a change that ADDS a kernel names it here; symbols whose name contains TEXT and that only B has are listed as new
+and are no difference (every symbol both sides have is compared as always).
+
+For each of abi, msm, msm_direct, vecops, snark, minroot, rounds (a unit one side has no object of is skipped): the device code object is taken out of the .o, and the two sides are
 compared by (1) the set of kernel names, (2) each kernel's register, scratch, LDS and spill figures from the code object's
 notes, (3) each kernel's disassembly.  A host-only change (a launcher refactor) must leave all three identical.
 Exit status 1 when anything differs."""
@@ -16,7 +20,7 @@ import tempfile
 
 LLVM = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
-UNITS = ("abi", "msm", "msm_direct", "vecops", "snark")
+UNITS = ("abi", "msm", "msm_direct", "vecops", "snark", "minroot", "rounds")
 FIGURES = (".vgpr_count", ".sgpr_count", ".agpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size",
            ".vgpr_spill_count", ".sgpr_spill_count")
 
@@ -109,12 +113,23 @@ def disassembly(co):
 
 
 def main():
-    if len(sys.argv) != 3:
+    args, new = sys.argv[1:], []
+    while "--new" in args:
+        k = args.index("--new")
+        if k + 1 >= len(args):
+            sys.exit(__doc__)
+        new.append(args[k + 1])
+        del args[k:k + 2]
+    if len(args) != 2:
         sys.exit(__doc__)
-    a_dir, b_dir = sys.argv[1:]
+    a_dir, b_dir = args
+    is_new = lambda n, a_side: n not in a_side and any(t in n for t in new)
     bad = False
     with tempfile.TemporaryDirectory() as tmp:
         for unit in UNITS:
+            if not os.path.exists(os.path.join(a_dir, unit + ".o")) or not os.path.exists(os.path.join(b_dir, unit + ".o")):
+                print(f"{unit}: no object on one side, skipped")
+                continue
             a = code_object(os.path.join(a_dir, unit + ".o"), tmp, unit + "_a")
             b = code_object(os.path.join(b_dir, unit + ".o"), tmp, unit + "_b")
             if a is None and b is None:
@@ -127,14 +142,16 @@ def main():
             same_file = open(a, "rb").read() == open(b, "rb").read()
             ka, kb = kernels(a), kernels(b)
             da, db = disassembly(a), disassembly(b)
-            diffs = [f"only in A: {n}" for n in sorted(set(ka) - set(kb))] + [f"only in B: {n}" for n in sorted(set(kb) - set(ka))]
+            diffs = [f"only in A: {n}" for n in sorted(set(ka) - set(kb))] + [f"only in B: {n}" for n in sorted(set(kb) - set(ka)) if not is_new(n, ka)]
             for n in sorted(set(ka) & set(kb)):
                 fa = {f: ka[n].get(f) for f in FIGURES}
                 fb = {f: kb[n].get(f) for f in FIGURES}
                 if fa != fb:
                     diffs.append(f"resources differ: {n}: {fa} -> {fb}")
             for n in sorted(set(da) | set(db) | set(ka) | set(kb)):          # kernels and the functions they call
-                if da.get(n) is None or da.get(n) != db.get(n):
+                if is_new(n, da) and is_new(n, ka):
+                    print(f"   new in B: {n}")
+                elif da.get(n) is None or da.get(n) != db.get(n):
                     diffs.append(f"instructions differ: {n}")
             print(f"{unit}: {len(ka)} kernels in A, {len(kb)} in B, " +
                   ("identical" if not diffs else f"{len(diffs)} differences") +

@@ -1520,6 +1520,62 @@ int vdf_round_tape_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, con
   });
 }
 
+static Status forward_tape_on_host(const vdf_round_tape* tape, const vdf_fe* inv) {
+  if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv))
+    return Status{VDF_ERR_BAD_ARG, "the tape and inv live in host memory"};
+  return Status{};
+}
+
+int vdf_round_tape_forward_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n,
+                                uint64_t rounds, vdf_fe* checkpoints, uint64_t every, size_t cp_stride, vdf_fe* trace, size_t walk_stride,
+                                uint64_t base, uint64_t j_base, uint64_t j_walk_step) {
+  return guarded(ctx, [&]() -> Status {
+    VDF_TRY(forward_tape_on_host(tape, inv));
+    if (n && rounds && (!ptr_is_device(entries) || (checkpoints && !ptr_is_device(checkpoints)) || (trace && !ptr_is_device(trace))))
+      return Status{VDF_ERR_BAD_ARG, "entries, checkpoints and trace live in device memory"};
+    VDF_TRY(vdf::vec_round_tape_forward_walk(field, tape, inv, entries, n, rounds, checkpoints, every, cp_stride, trace, walk_stride, base,
+                                             j_base, j_walk_step, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
+int vdf_round_tape_eval_batch(vdf_ctx* ctx, int field, const vdf_round_tape* tape, const vdf_fe* inv, const vdf_fe* initial, size_t n,
+                              uint64_t rounds_total, uint64_t every, uint64_t launch_rounds, uint64_t j_base, uint64_t j_walk_step,
+                              vdf_fe* out_entries) {
+  return guarded(ctx, [&]() -> Status {
+    VDF_TRY(vdf::check_field(field));
+    VDF_TRY(forward_tape_on_host(tape, inv));
+    uint64_t max_rounds = 0;
+    VDF_TRY(vdf::round_tape_forward_max_rounds(tape, inv, &max_rounds));
+    if (every && rounds_total % every != 0) return Status{VDF_ERR_BAD_ARG, "`every` must divide rounds_total"};
+    if (launch_rounds == 0) launch_rounds = std::min<uint64_t>(1024, max_rounds);
+    if (launch_rounds > max_rounds) return Status{VDF_ERR_BAD_ARG, "launch_rounds x products per round > VDF_FORWARD_TAPE_MAX_WORK"};
+    if (n > ((size_t)1 << 31)) return Status{VDF_ERR_BAD_LENGTH, "more than 2^31 chains"};
+    if (n == 0) return Status{};
+    const size_t esz = (size_t)tape->n_adv * sizeof(vdf_fe);
+    const size_t per = every ? (size_t)(rounds_total / every) + 1 : 1;           // entries per chain in out_entries
+    if (per > SIZE_MAX / esz / n) return Status{VDF_ERR_BAD_LENGTH, "out_entries would not fit the address space"};
+    Staging st(ctx);
+    const void* dinit; void* dout;
+    VDF_TRY(st.in(initial, n * esz, &dinit));
+    VDF_TRY(st.out(out_entries, n * per * esz, &dout));
+    void* walk = dout;                                         // every = 0: the walks run in the output itself
+    if (every) {
+      VDF_TRY(st.temp(n * esz, &walk));
+      VDF_TRY_HIP(hipMemcpy2DAsync(dout, per * esz, dinit, esz, esz, n, hipMemcpyDeviceToDevice, ctx->stream));      // checkpoint 0 of every chain
+    }
+    VDF_TRY_HIP(hipMemcpyAsync(walk, dinit, n * esz, hipMemcpyDeviceToDevice, ctx->stream));
+    for (uint64_t done = 0; done < rounds_total;) {
+      const uint64_t now = std::min<uint64_t>(rounds_total - done, launch_rounds);
+      VDF_TRY(vdf::vec_round_tape_forward_walk(field, tape, inv, walk, n, now, every ? dout : nullptr, every, per, nullptr, 0, done, j_base,
+                                               j_walk_step, ctx->stream));
+      done += now;
+    }
+    return st.finish();
+  });
+}
+
 int vdf_ptr_is_device(const void* p) { return ptr_is_device(p) ? 1 : 0; }
 
 static Status nifs_cross_impl(vdf_ctx* ctx, const vdf_shape* shape, size_t row_begin, size_t row_count, int part, const vdf_fe* z2,

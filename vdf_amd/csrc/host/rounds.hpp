@@ -8,8 +8,9 @@
 namespace vdfnova {
 
 // What a body did, call by call.  Nodes [0, n_inputs()) are its inputs in the order j, inv, carry, cur, next; every later node is
-// one vdf_cs_* call.  a, b, c name nodes, except: R_CONST a = index into consts; R_SCALE b = index into consts.
-enum RecOp : uint8_t { R_INPUT = 0, R_CONST, R_ADD, R_SUB, R_SCALE, R_MUL, R_ALLOC_FROM, R_ENFORCE };
+// one vdf_cs_* call.  a, b, c name nodes, except: R_CONST a = index into consts; R_SCALE and R_POW b = index into consts (R_POW:
+// the exponent, a plain 256-bit integer, stored like a constant).  R_POW exists in forward bodies only.
+enum RecOp : uint8_t { R_INPUT = 0, R_CONST, R_ADD, R_SUB, R_SCALE, R_MUL, R_ALLOC_FROM, R_ENFORCE, R_POW };
 struct RecNode {
   uint8_t op = R_INPUT;
   bool value_only = false;         // made of advice values: no linear combination stands behind it
@@ -65,10 +66,15 @@ void replay_round(CS& cs, const RoundRecord& r, uint64_t j, const std::vector<Nu
 int eval_round_tape(int field, const vdf_round_tape* tape, uint64_t t, const Fe* inv, const Fe* advice, Fe* out);
 // A walk body (vdf_nova.h vdf_walk_body) run once on a recording handle and compiled into a walk tape: the record has no carry, no
 // variable and no constraint; its n_vars = n_adv columns are the handles the body left in cur_out.
-int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out);
+// forward: the body is a forward body (vdf_nova_forward_body_record): the entry it is handed is entry j, loaded with ADV b = 0, and
+// vdf_cs_pow is legal.
+int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out, bool forward = false);
 // vdf_round_tape_walk on the host (vdf_nova_walk_tape_eval): the same arguments, the same refusals, host memory
 int eval_walk_tape(int field, const vdf_round_tape* tape, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* trace, size_t walk_stride,
                    size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok);
+// vdf_round_tape_forward_walk on the host (vdf_nova_forward_tape_eval): the same arguments, the same refusals, host memory
+int eval_forward_tape(int field, const vdf_round_tape* tape, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* checkpoints,
+                      uint64_t every, size_t cp_stride, Fe* trace, size_t walk_stride, uint64_t base, uint64_t j_base, uint64_t j_walk_step);
 
 }  // namespace vdfnova
 
@@ -82,4 +88,5 @@ struct vdf_cs {
   vdf_ctx* ctx = nullptr;                          // for advice in device memory: the copy of its last entry (null: such advice is refused)
   uint32_t rec_calls = 0;
   bool walk = false;                               // the recording is a walk body's (vdf_nova_walk_body_record): value arithmetic only
+  bool forward = false;                            // ... a forward body's (vdf_nova_forward_body_record): vdf_cs_pow is legal
 };

@@ -14,8 +14,9 @@ constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;
 // node of a handle the body owns, or -1 (and the failure flag)
 long rec_node(vdf_cs* c, vdf_num h) {
   const uint32_t k = h & ~REC_TAG;
-  // (a walk body is handed no entry but `next`: the inputs a round body calls cur are not its own)
-  if ((h & REC_TAG) && k < c->rec->nodes.size() && !(c->walk && k >= c->rec->in_cur(0) && k < c->rec->in_next(0))) return (long)k;
+  // (a walk body is handed one entry: `next`, or the inputs a round body calls cur when it walks forward; the other is not its own)
+  const uint32_t other = c->forward ? c->rec->in_next(0) : c->rec->in_cur(0);
+  if ((h & REC_TAG) && k < c->rec->nodes.size() && !(c->walk && k >= other && k < other + c->rec->n_adv)) return (long)k;
   c->bad = true;
   return -1;
 }
@@ -46,7 +47,7 @@ int compile_round(RoundRecord& r, const std::vector<uint32_t>* outs = nullptr) {
   auto operands = [&](const RecNode& x, uint32_t out[2]) -> int {
     switch (x.op) {
       case R_ADD: case R_SUB: case R_MUL: out[0] = root[x.a]; out[1] = root[x.b]; return 2;
-      case R_SCALE: case R_ALLOC_FROM: out[0] = root[x.a]; return 1;
+      case R_SCALE: case R_ALLOC_FROM: case R_POW: out[0] = root[x.a]; return 1;
       default: return 0;                            // inputs, constants; enforce costs the device nothing
     }
   };
@@ -98,6 +99,7 @@ int compile_round(RoundRecord& r, const std::vector<uint32_t>* outs = nullptr) {
       case R_ADD: slot[i] = take(); emit(VDF_TAPE_ADD, slot[i], sa, sb); break;
       case R_SUB: slot[i] = take(); emit(VDF_TAPE_SUB, slot[i], sa, sb); break;
       case R_SCALE: slot[i] = take(); emit(VDF_TAPE_SCALE, slot[i], sa, x.b); break;
+      case R_POW: slot[i] = take(); emit(VDF_TAPE_POW, slot[i], sa, x.b); break;
       case R_MUL: slot[i] = take(); emit(VDF_TAPE_MUL, slot[i], sa, sb); if (!outs) emit(VDF_TAPE_OUT, 0, slot[i], var++); break;
       default: emit(VDF_TAPE_OUT, 0, sa, var++); break;      // R_ALLOC_FROM
     }
@@ -229,7 +231,7 @@ int eval_round_tape(int fid, const vdf_round_tape* tp, uint64_t t, const Fe* inv
 }
 
 
-int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out) {
+int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out, bool forward) {
   if (!b || !b->body) return fail(VDF_ERR_BAD_ARG, "walk body: null body");
   if (b->n_inv > VDF_ROUND_MAX_INV || b->n_adv > VDF_ROUND_MAX_ADV || b->n_adv == 0)
     return fail(VDF_ERR_BAD_ARG, "walk body: n_inv or n_adv beyond its cap (VDF_ROUND_MAX_*), or no advice column");
@@ -240,13 +242,15 @@ int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out) {
   h.cs = cs;
   h.rec = &r;
   h.walk = true;
+  h.forward = forward;
   std::vector<vdf_num> hin(r.n_inputs()), hout(r.n_adv, 0);
   for (uint32_t k = 0; k < r.n_inputs(); ++k) hin[k] = REC_TAG | k;
-  const int rc = b->body(b->self, &h, hin[r.in_j()], hin.data() + r.in_inv(0), hin.data() + r.in_next(0), hout.data());
+  // (the entry stood on: entry j + 1 descending, entry j ascending -- the inputs compile_round loads with ADV b = 1 and b = 0)
+  const int rc = b->body(b->self, &h, hin[r.in_j()], hin.data() + r.in_inv(0), hin.data() + (forward ? r.in_cur(0) : r.in_next(0)), hout.data());
   if (rc != 0) return fail(VDF_ERR_BAD_ARG, "walk body: the body failed");
   if (h.rec_calls > VDF_ROUND_MAX_OPS) return fail(VDF_ERR_BAD_ARG, "walk body: more than VDF_ROUND_MAX_OPS calls");
   if (r.consts.size() > VDF_ROUND_MAX_CONSTS) return fail(VDF_ERR_BAD_ARG, "walk body: more than VDF_ROUND_MAX_CONSTS constants");
-  if (h.bad) return fail(VDF_ERR_BAD_ARG, "walk body: a handle the body does not own, or a call that is not value arithmetic (alloc, alloc_from, enforce, value, repeat)");
+  if (h.bad) return fail(VDF_ERR_BAD_ARG, "walk body: a handle the body does not own, or a call that is not value arithmetic (alloc, alloc_from, enforce, value, repeat; pow outside a forward body)");
   std::vector<uint32_t> outs;
   for (uint32_t k = 0; k < r.n_adv; ++k) {
     const long nd = rec_node(&h, hout[k]);
@@ -262,7 +266,28 @@ int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out) {
 }
 
 // the walk rules of vdf_hip.h over a tape, once, before anything is evaluated -- what vec_round_tape_walk checks before a launch
-static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rounds) {
+// what a POW of exponent e costs: bitlen - 1 squarings and popcount - 1 products from the top set bit, at least one
+static uint64_t pow_products(const Fe& e) {
+  uint64_t bits = 0, ones = 0;
+  for (int q = 0; q < 4; ++q)
+    if (e.l[q]) { bits = 64 * q + 64 - __builtin_clzll(e.l[q]); ones += __builtin_popcountll(e.l[q]); }
+  return bits + ones > 2 ? bits + ones - 2 : 1;
+}
+// x ^ e, e a plain integer: left to right from the top set bit, as the kernel does it (any order gives the same canonical value)
+static Fe pow_plain(const Fe& x, const Fe& e, const Field& F) {
+  int q = 3;
+  while (q >= 0 && e.l[q] == 0) --q;
+  if (q < 0) return one(F);
+  Fe acc = x;
+  for (int bit = 62 - __builtin_clzll(e.l[q]); q >= 0; --q, bit = 63)
+    for (; bit >= 0; --bit) {
+      acc = sqr(acc, F);
+      if ((e.l[q] >> bit) & 1) acc = mul(acc, x, F);
+    }
+  return acc;
+}
+
+static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rounds, bool forward = false) {
   if (!tp || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts)) return fail(VDF_ERR_BAD_ARG, "null tape");
   if (tp->n_ops > VDF_TAPE_MAX_OPS || tp->n_consts > VDF_TAPE_MAX_CONSTS || tp->n_slots > VDF_TAPE_MAX_SLOTS || tp->n_vars > VDF_TAPE_MAX_VARS ||
       tp->n_inv > VDF_TAPE_MAX_INV || tp->n_adv > VDF_TAPE_MAX_ADV || tp->n_vars == 0 || tp->n_adv == 0 || tp->n_slots == 0)
@@ -276,7 +301,7 @@ static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rou
     auto rd = [&](uint8_t x) { return x < tp->n_slots && written[x]; };
     bool ok = false;
     switch (o.op) {
-      case VDF_TAPE_ADV: ok = o.a < tp->n_adv && o.b == 1; break;
+      case VDF_TAPE_ADV: ok = o.a < tp->n_adv && o.b == (forward ? 0 : 1); break;
       case VDF_TAPE_INV: ok = o.a < tp->n_inv; break;
       case VDF_TAPE_J: ok = true; break;
       case VDF_TAPE_CONST: ok = o.a < tp->n_consts; break;
@@ -284,16 +309,20 @@ static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rou
       case VDF_TAPE_MUL: ok = rd(o.a) && rd(o.b); ++products; break;
       case VDF_TAPE_SCALE: ok = rd(o.a) && o.b < tp->n_consts; ++products; break;
       case VDF_TAPE_OUT: ok = rd(o.a) && o.b < tp->n_adv && !col_out[o.b]; if (ok) col_out[o.b] = true; break;
+      case VDF_TAPE_POW:
+        ok = forward && rd(o.a) && o.b < tp->n_consts;
+        if (ok) products += pow_products(((const Fe*)tp->consts)[o.b]);
+        break;
       default: break;
     }
     if (ok && o.op != VDF_TAPE_OUT) { ok = o.dst < tp->n_slots; if (ok) written[o.dst] = true; }
-    if (!ok) return fail(VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + " is malformed (opcode, index out of range, or a slot read before it is written); a walk tape loads advice with b = 1 only");
+    if (!ok) return fail(VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + " is malformed (opcode, index out of range, or a slot read before it is written); a walk tape loads advice with b = " + (forward ? "0" : "1") + " only");
   }
   for (uint32_t k = 0; k < tp->n_adv; ++k)
     if (!col_out[k]) return fail(VDF_ERR_BAD_ARG, "tape leaves variable " + std::to_string(k) + " unwritten");
   if (tp->n_slots + 2 * tp->n_adv > VDF_WALK_MAX_SLOTS) return fail(VDF_ERR_BAD_ARG, "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS");
-  if (rounds > VDF_WALK_MAX_WORK / (products ? products : 1))
-    return fail(VDF_ERR_BAD_ARG, "rounds x products per round > VDF_WALK_MAX_WORK in one call: cut the walk");
+  if (rounds > (forward ? VDF_FORWARD_TAPE_MAX_WORK : VDF_WALK_MAX_WORK) / (products ? products : 1))
+    return fail(VDF_ERR_BAD_ARG, std::string("rounds x products per round > ") + (forward ? "VDF_FORWARD_TAPE_MAX_WORK" : "VDF_WALK_MAX_WORK") + " in one call: cut the walk");
   return VDF_OK;
 }
 
@@ -347,6 +376,50 @@ int eval_walk_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entries
   return VDF_OK;
 }
 
+int eval_forward_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* checkpoints, uint64_t every,
+                      size_t cp_stride, Fe* trace, size_t walk_stride, uint64_t base, uint64_t j_base, uint64_t j_walk_step) {
+  if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
+  const int rc = check_walk_tape(tp, inv, rounds, true);
+  if (rc != VDF_OK) return rc;
+  if (checkpoints && every == 0) return fail(VDF_ERR_BAD_ARG, "checkpoints without `every`");
+  if (n == 0 || rounds == 0) return VDF_OK;
+  if (n > ((size_t)1 << 31)) return fail(VDF_ERR_BAD_LENGTH, "more than 2^31 walks");
+  if (!entries) return fail(VDF_ERR_BAD_ARG, "null entries");
+  const Field& F = field(fid);
+  const Fe* consts = (const Fe*)tp->consts;
+  const size_t na = tp->n_adv;
+  Fe s[VDF_TAPE_MAX_SLOTS], stand[VDF_TAPE_MAX_ADV], prod[VDF_TAPE_MAX_ADV];
+  for (size_t w = 0; w < n; ++w) {
+    uint64_t j = j_base + w * j_walk_step + base;
+    for (size_t c = 0; c < na; ++c) stand[c] = entries[w * na + c];
+    for (uint64_t r = 0; r < rounds; ++r, ++j) {
+      for (size_t i = 0; i < tp->n_ops; ++i) {
+        const vdf_tape_op& o = tp->ops[i];
+        switch (o.op) {
+          case VDF_TAPE_ADV: s[o.dst] = stand[o.a]; break;
+          case VDF_TAPE_INV: s[o.dst] = inv[o.a]; break;
+          case VDF_TAPE_J: s[o.dst] = from_u64(j, F); break;
+          case VDF_TAPE_CONST: s[o.dst] = consts[o.a]; break;
+          case VDF_TAPE_ADD: s[o.dst] = add(s[o.a], s[o.b], F); break;
+          case VDF_TAPE_SUB: s[o.dst] = sub(s[o.a], s[o.b], F); break;
+          case VDF_TAPE_MUL: s[o.dst] = mul(s[o.a], s[o.b], F); break;
+          case VDF_TAPE_SCALE: s[o.dst] = mul(s[o.a], consts[o.b], F); break;
+          case VDF_TAPE_POW: s[o.dst] = pow_plain(s[o.a], consts[o.b], F); break;
+          default: prod[o.b] = s[o.a]; break;      // VDF_TAPE_OUT
+        }
+      }
+      for (size_t c = 0; c < na; ++c) stand[c] = prod[c];
+      const uint64_t g = base + r + 1;
+      if (trace)
+        for (size_t c = 0; c < na; ++c) trace[(w * walk_stride + g) * na + c] = stand[c];
+      if (checkpoints && g % every == 0)
+        for (size_t c = 0; c < na; ++c) checkpoints[(w * cp_stride + g / every) * na + c] = stand[c];
+    }
+    for (size_t c = 0; c < na; ++c) entries[w * na + c] = stand[c];
+  }
+  return VDF_OK;
+}
+
 }  // namespace vdfnova
 
 // ---- the recording side of the vdf_cs_* calls (nova_host.cpp hands a call over when the handle records) ------------------
@@ -366,6 +439,14 @@ vdf_num rec_cs_scale(vdf_cs* c, vdf_num a, const vdf_fe* k) {
   const long x = rec_node(c, a);
   if (x < 0 || !k) { c->bad = true; return 0; }
   return rec_push(c, R_SCALE, c->rec->nodes[x].value_only, (uint32_t)x, rec_const(c, k), 0);
+}
+vdf_num rec_cs_pow(vdf_cs* c, vdf_num a, const uint64_t e[4]) {
+  if (!c->forward || !e) { c->bad = true; return 0; }      // a power inside a circuit would need constraints: the circuit author's business
+  const long x = rec_node(c, a);
+  if (x < 0) return 0;
+  vdf_fe k;
+  memcpy(&k, e, 32);
+  return rec_push(c, R_POW, false, (uint32_t)x, rec_const(c, &k), 0);
 }
 int rec_cs_enforce(vdf_cs* c, vdf_num a, vdf_num b, vdf_num cc) {
   if (c->walk) { c->bad = true; return VDF_ERR_BAD_ARG; }      // a walk body computes values: it has nothing to constrain
@@ -391,6 +472,13 @@ vdf_num vdf_cs_alloc_from(vdf_cs* c, vdf_num src) {
   const Fe v = c->pool[src].v;
   c->pool.push_back(c->cs->alloc(c->cs->shape ? zero() : v));
   return (vdf_num)(c->pool.size() - 1);
+}
+
+vdf_num vdf_cs_pow(vdf_cs* c, vdf_num a, const uint64_t e[4]) {
+  if (!c) return 0;
+  if (c->rec) return rec_cs_pow(c, a, e);
+  c->bad = true;                                       // value arithmetic of a forward body only
+  return 0;
 }
 
 int vdf_cs_repeat(vdf_cs* c, const vdf_round_body* b, uint64_t t, const vdf_num* inv, const vdf_num* carry_in, const vdf_fe* advice,
@@ -471,13 +559,12 @@ int vdf_nova_round_tape_eval(int fid, const vdf_round_tape* tape, uint64_t t, co
   return nova_guard([&]() -> int { return eval_round_tape(fid, tape, t, (const Fe*)inv, (const Fe*)advice, (Fe*)out); });
 }
 
-int vdf_nova_walk_body_record(int fid, const vdf_walk_body* b, vdf_tape_op ops[VDF_TAPE_MAX_OPS], vdf_fe consts[VDF_TAPE_MAX_CONSTS],
-                              vdf_round_tape* out) {
+static int walk_body_record(int fid, const vdf_walk_body* b, vdf_tape_op* ops, vdf_fe* consts, vdf_round_tape* out, bool forward) {
   return nova_guard([&]() -> int {
     if (!valid_field(fid) || !ops || !consts || !out) return fail(VDF_ERR_BAD_ARG, "bad argument");
     CS cs(fid, true);
     RoundRecord rec;
-    const int rc = record_walk_body(&cs, b, &rec);
+    const int rc = record_walk_body(&cs, b, &rec, forward);
     if (rc != VDF_OK) return rc;
     *out = rec.view();
     memcpy(ops, rec.ops.data(), rec.ops.size() * sizeof(vdf_tape_op));
@@ -485,6 +572,25 @@ int vdf_nova_walk_body_record(int fid, const vdf_walk_body* b, vdf_tape_op ops[V
     out->ops = ops;
     out->consts = consts;
     return VDF_OK;
+  });
+}
+
+int vdf_nova_walk_body_record(int fid, const vdf_walk_body* b, vdf_tape_op ops[VDF_TAPE_MAX_OPS], vdf_fe consts[VDF_TAPE_MAX_CONSTS],
+                              vdf_round_tape* out) {
+  return walk_body_record(fid, b, ops, consts, out, false);
+}
+
+int vdf_nova_forward_body_record(int fid, const vdf_walk_body* b, vdf_tape_op ops[VDF_TAPE_MAX_OPS], vdf_fe consts[VDF_TAPE_MAX_CONSTS],
+                                 vdf_round_tape* out) {
+  return walk_body_record(fid, b, ops, consts, out, true);
+}
+
+int vdf_nova_forward_tape_eval(int fid, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n, uint64_t rounds,
+                               vdf_fe* checkpoints, uint64_t every, size_t cp_stride, vdf_fe* trace, size_t walk_stride, uint64_t base,
+                               uint64_t j_base, uint64_t j_walk_step) {
+  return nova_guard([&]() -> int {
+    return eval_forward_tape(fid, tape, (const Fe*)inv, (Fe*)entries, n, rounds, (Fe*)checkpoints, every, cp_stride, (Fe*)trace, walk_stride,
+                             base, j_base, j_walk_step);
   });
 }
 

@@ -324,6 +324,10 @@ Status vec_round_tape(int field, const vdf_round_tape* tape, uint64_t t, const v
 Status vec_round_tape_walk(int field, const vdf_round_tape* tape, const vdf_fe* inv, void* entries, size_t n, uint64_t rounds, void* trace,
                            size_t walk_stride, size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step,
                            int heads, const void* expect, int32_t* ok, hipStream_t s);
+Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tape, const vdf_fe* inv, void* entries, size_t n, uint64_t rounds,
+                                   void* checkpoints, uint64_t every, size_t cp_stride, void* trace, size_t walk_stride, uint64_t base,
+                                   uint64_t j_base, uint64_t j_walk_step, hipStream_t s);
+Status round_tape_forward_max_rounds(const vdf_round_tape* tape, const vdf_fe* inv, uint64_t* max_rounds);
 Status vec_step_z(int field, const void* trace_xy, uint64_t t, const vdf_fe z_in[3], const vdf_fe* i0, const vdf_fe* u,
                   const vdf_fe X[6], void* z, void* packed, hipStream_t s);
 Status vec_nifs_cross(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3],

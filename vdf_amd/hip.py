@@ -59,6 +59,8 @@ class RoundTapeC(C.Structure):
 
 TAPE_MAX_OPS, TAPE_MAX_CONSTS, TAPE_MAX_SLOTS, TAPE_MAX_VARS, TAPE_MAX_INV, TAPE_MAX_ADV = 320, 24, 24, 64, 16, 8
 WALK_MAX_SLOTS, WALK_MAX_WORK = 32, 1 << 23        # VDF_WALK_MAX_SLOTS, VDF_WALK_MAX_WORK
+FORWARD_TAPE_MAX_WORK = 1 << 20                    # VDF_FORWARD_TAPE_MAX_WORK
+TAPE_POW = 9                                       # VDF_TAPE_POW
 
 
 class RoundTape:
@@ -458,6 +460,23 @@ class Context:
         self._check(lib.vdf_round_tape_walk(self.handle, field, C.addressof(tape.c), _ptr(inv), _ptr(entries), n, rounds, _ptr(trace),
                                             walk_stride, top, group, group_stride, j_base, j_group_step, int(bool(heads)), _ptr(expect),
                                             _ptr(ok)))
+
+    def round_tape_forward_walk(self, field, tape: "RoundTape", inv, entries, n, rounds, checkpoints=None, every=0, cp_stride=0, trace=None,
+                                walk_stride=0, base=0, j_base=0, j_walk_step=0) -> None:
+        """n walks of `rounds` rounds of a recorded forward body in place over `entries` (device, n x n_adv elements), one lane each;
+        strides in entries.  With g = base + r + 1 after round r, walk w writes the entry it produced to trace entry
+        w * walk_stride + g and, when every divides g, to checkpoints entry w * cp_stride + g // every (device or None); the round
+        sees j = j_base + w * j_walk_step + base + r.  inv: host."""
+        self._check(lib.vdf_round_tape_forward_walk(self.handle, field, C.addressof(tape.c), _ptr(inv), _ptr(entries), n, rounds, _ptr(checkpoints),
+                                                    every, cp_stride, _ptr(trace), walk_stride, base, j_base, j_walk_step))
+
+    def round_tape_eval_batch(self, field, tape: "RoundTape", inv, initial, n, rounds_total, out_entries, every=0, launch_rounds=0, j_base=0,
+                              j_walk_step=0) -> None:
+        """Context.minroot_eval_batch for a forward walk tape: out_entries[w] = the final entry of chain w (every = 0), or the
+        rounds_total // every + 1 entries it passes every `every` rounds, the initial one first.  initial / out_entries: host or
+        device, n_adv elements per entry; inv: host."""
+        self._check(lib.vdf_round_tape_eval_batch(self.handle, field, C.addressof(tape.c), _ptr(inv), _ptr(initial), n, rounds_total, every,
+                                                  launch_rounds, j_base, j_walk_step, _ptr(out_entries)))
 
     def minroot_step_segment_packed(self, field, trace_xy, t, i0, i_in, out, packed) -> None:
         """The reference's allocation (4 variables per round) and the 3t + 4 scalars of its commitment without new_x."""

@@ -98,6 +98,9 @@ for _name, _res, _args in [
     ("vdf_nova_round_tape_eval", _i, [_i, _vp, _u64, _vp, _vp, _vp]),
     ("vdf_nova_walk_body_record", _i, [_i, _vp, _vp, _vp, _vp]),
     ("vdf_nova_walk_tape_eval", _i, [_i, _vp, _vp, _vp, _sz, _u64, _vp, _sz, _sz, _sz, _sz, _u64, _u64, _i, _vp, _vp]),
+    ("vdf_cs_pow", C.c_uint32, [_vp, C.c_uint32, _vp]),
+    ("vdf_nova_forward_body_record", _i, [_i, _vp, _vp, _vp, _vp]),
+    ("vdf_nova_forward_tape_eval", _i, [_i, _vp, _vp, _vp, _sz, _u64, _vp, _u64, _sz, _vp, _sz, _u64, _u64, _u64]),
     ("vdf_nova_synthesis_stats", _i, [C.POINTER(_u64), C.POINTER(_u64)]),
     ("vdf_nova_compress", _i, [_vp, _vp, C.POINTER(_vp)]),
     ("vdf_nova_compress_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_vp)]),
@@ -446,6 +449,43 @@ def walk_tape_eval(field: int, tape: RoundTape, inv, entries: np.ndarray, n: int
                                             ok.ctypes.data if ok is not None else None))
 
 
+def record_forward_body(body: WalkBody, field: int = FIELD_FQ) -> RoundTape:
+    """Host only: a WalkBody whose `next` argument is the entry stood on (entry j) and whose result is entry j + 1 -- the slow
+    direction, with ConstraintSystem.pow -- recorded into the forward walk tape Context.round_tape_forward_walk /
+    round_tape_eval_batch / forward_tape_eval take."""
+    tape = RoundTape()
+    rc = nova_lib.vdf_nova_forward_body_record(field, C.addressof(body._c()), C.addressof(tape.ops), tape.consts.ctypes.data, C.addressof(tape.c))
+    _reraise(body)
+    _check(rc)
+    return tape
+
+
+def forward_tape_eval(field: int, tape: RoundTape, inv, entries: np.ndarray, n: int, rounds: int, checkpoints: "np.ndarray | None" = None,
+                      every: int = 0, cp_stride: int = 0, trace: "np.ndarray | None" = None, walk_stride: int = 0, base: int = 0,
+                      j_base: int = 0, j_walk_step: int = 0) -> None:
+    """Host only: Context.round_tape_forward_walk on the host, in place over numpy arrays (entries / checkpoints / trace
+    uint64[., 4] Montgomery); the same arguments and the same refusals.  The arrays are checked against what the walks touch."""
+    def arr(x, what):
+        if x is None:
+            return None
+        if not isinstance(x, np.ndarray) or x.dtype != np.dtype("<u8") or not x.flags["C_CONTIGUOUS"] or not x.flags["WRITEABLE"]:
+            raise ValueError("%s: a writable C-contiguous <u8 array" % what)
+        return x
+    na = tape.c.n_adv
+    inv = np.ascontiguousarray(inv if inv is not None else np.zeros((0, 4)), dtype="<u8").reshape(-1, 4)
+    entries, checkpoints, trace = arr(entries, "entries"), arr(checkpoints, "checkpoints"), arr(trace, "trace")
+    if inv.shape[0] < tape.c.n_inv or entries.size < 4 * n * na:
+        raise ValueError("inv or entries shorter than the walks read")
+    if n and rounds:
+        if trace is not None and trace.size < 4 * ((n - 1) * walk_stride + base + rounds + 1) * na:
+            raise ValueError("trace shorter than the walks write")
+        if checkpoints is not None and every and checkpoints.size < 4 * ((n - 1) * cp_stride + (base + rounds) // every + 1) * na:
+            raise ValueError("checkpoints shorter than the walks write")
+    _check(nova_lib.vdf_nova_forward_tape_eval(field, C.addressof(tape.c), inv.ctypes.data if tape.c.n_inv else None, entries.ctypes.data, n, rounds,
+                                               checkpoints.ctypes.data if checkpoints is not None else None, every, cp_stride,
+                                               trace.ctypes.data if trace is not None else None, walk_stride, base, j_base, j_walk_step))
+
+
 class ConstraintSystem:
     """The vdf_cs a step circuit's synthesize receives: numbers are opaque handles; field elements cross as 32-byte
     Montgomery limbs of the primary circuit's field (Fq, or Fp under public_params_custom(..., field=FIELD_FP))."""
@@ -474,6 +514,13 @@ class ConstraintSystem:
 
     def mul(self, a: int, b: int) -> int:
         return nova_lib.vdf_cs_mul(self.h, a, b)
+
+    def pow(self, a: int, e: int) -> int:
+        """a ^ e, e a plain integer below 2^256: value arithmetic of a forward body (record_forward_body) only; anywhere else
+        the failure flag."""
+        if not 0 <= e < 1 << 256:
+            raise ValueError("the exponent is an integer in [0, 2^256)")
+        return nova_lib.vdf_cs_pow(self.h, a, (C.c_uint64 * 4)(*[(e >> (64 * k)) & (2**64 - 1) for k in range(4)]))
 
     def enforce(self, a: int, b: int, c: int) -> None:
         _check(nova_lib.vdf_cs_enforce(self.h, a, b, c))
