@@ -554,6 +554,50 @@ int  vdf_nifs_cross_term_minroot_forward(vdf_ctx* ctx, int field, uint64_t t, si
 int  vdf_nifs_cross_term_minroot_forward_lanes(vdf_ctx* ctx, int field, uint64_t t, size_t lanes, size_t seg_begin, size_t one_col,
                                                size_t row_begin, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,
                                                const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T);
+/* ---- periodic rows: the cross term of the rows of t replays of ONE recorded round, WITHOUT the sparse matrices ------------------
+ * What the stencils above are for the built-in circuits, for a round the library did not write (libvdf_nova.so vdf_cs_repeat).
+ * Rows that come from replaying one tape are periodic: from some repetition on, row c of repetition j + 1 is row c of repetition
+ * j with every column inside the repeat's run of variables moved by n_vars, every other column fixed, and every coefficient equal
+ * but those that are affine in j.  A vdf_periodic_rows describes the rows of ONE repetition; the kernel evaluates them from
+ * coalesced streams and a description of a few hundred bytes that travels in its arguments (no row pointers, no column or
+ * coefficient loads, no staging copy, no synchronisation).  libvdf_nova.so finds the description in a shape's triples and checks
+ * it against every repetition (vdf_nova.h vdf_nova_periodic_rows_detect).
+ *
+ * Row c (c < n_cons), matrix k (0 = A, 1 = B, 2 = C) holds the terms terms[row_start[3 c + k]] .. terms[row_start[3 c + k + 1] - 1];
+ * row_start has 3 n_cons + 1 entries, ascending from 0 to n_terms.  In repetition j a term contributes coefficient * z2[column]:
+ *   VDF_TERM_SEG  column = seg_begin + j * n_vars + col, col read as a SIGNED 32-bit offset (negative: a look-back into earlier
+ *                 repetitions); coefficient = consts[c0]
+ *   VDF_TERM_ABS  column = col (the circuit's inputs, an inv, the constant's column); coefficient = consts[c0], or, with
+ *                 c1 != VDF_TERM_NO_SLOPE, consts[c0] + (j - j0) * consts[c1]
+ * consts: host memory, Montgomery form.  Coefficients 1 and -1 cost an addition or a subtraction, anything else a product.
+ * The caps, each refused one beyond with VDF_ERR_BAD_ARG; with them the whole description is 2 KiB of kernel arguments (1,024 B of terms, 768 B of constants, 200 B of row starts). */
+enum { VDF_TERM_SEG = 0, VDF_TERM_ABS = 1 };
+#define VDF_TERM_NO_SLOPE 0xFF
+#define VDF_PERIODIC_MAX_ROW_TERMS 8   /* terms of one row in one matrix: vdf_nifs_cross_term_rows' bound on a row inside a range */
+#define VDF_PERIODIC_MAX_ROWS 32       /* rows (constraints) per repetition */
+#define VDF_PERIODIC_MAX_STARTS 97     /* ... and the entries of row_start they take: 3 VDF_PERIODIC_MAX_ROWS + 1 */
+#define VDF_PERIODIC_MAX_TERMS 128     /* terms per repetition, all rows and matrices together */
+#define VDF_PERIODIC_MAX_CONSTS 24
+typedef struct vdf_periodic_term { uint8_t kind, c0, c1, pad; uint32_t col; } vdf_periodic_term;
+typedef struct vdf_periodic_rows {
+  uint32_t n_cons, n_vars;                          /* rows and variables per repetition */
+  uint64_t j0;                                      /* the repetition the pattern was taken from: slopes count from it */
+  const uint16_t* row_start;                        /* host memory, 3 n_cons + 1 entries */
+  const vdf_periodic_term* terms;  size_t n_terms;  /* host memory */
+  const vdf_fe* consts;            size_t n_consts; /* host memory, Montgomery form */
+} vdf_periodic_rows;
+/* Az2, Bz2, Cz2 and T of the rows row_begin + (j - j_first) * n_cons + c, j = j_first .. j_first + reps - 1, c < n_cons, with the
+ * operands of vdf_nifs_cross_term_minroot_forward (vectors: device memory, full length num_cons / num_cols; u1: host memory).
+ * Nothing else is touched.  Exact for any z2, a `one` that is not 1 included: byte for byte what vdf_nifs_cross_term writes into
+ * the same rows for a shape whose rows are those terms (and vdf_nova_periodic_rows_eval on the host).  The caller answers for
+ * the rows being those terms.  Checked before anything is launched, each VDF_ERR_BAD_ARG and never an access out of bounds: the
+ * caps, term kinds, constant indices, row_start, j_first < j0, every column a term reaches for the first and the last j against
+ * [0, num_cols), the row range against num_cons, more than 2^31 rows, a device pointer where host memory is read or the
+ * reverse.  reps = 0 does nothing. */
+int  vdf_nifs_cross_term_periodic(vdf_ctx* ctx, int field, const vdf_periodic_rows* rows, uint64_t j_first, uint64_t reps,
+                                  size_t seg_begin, size_t row_begin, size_t num_cols, size_t num_cons, const vdf_fe* z2,
+                                  const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2,
+                                  vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T);
 /* The same rows with the PREVIOUS fold of those rows applied on the way.  A prover that keeps A z, B z, C z of the running
  * instance folds them after every step (X1 <- X1 + r X2); for the stencil rows the fresh vectors X2 of the previous step are
  * exactly what this call is about to overwrite in Az2 / Bz2 / Cz2.  So, per row: Az1 += r Az2, Bz1 += r Bz2, Cz1 += r Cz2

@@ -172,6 +172,9 @@ typedef struct vdf_nova_tuning {
   int32_t  fold_fused;           /* 1: the stencil kernel of the next step's early rows applies the primary fold to ITS rows of A z, B z,
                                     C z and E on the way (vdf_nifs_cross_term_minroot_fold) and only z and the other rows are folded by a
                                     launch of their own, beside it; 0: one fold over whole vectors in front of the rows (0: measured; needs stencil) */
+  int32_t  periodic_rows;        /* 1: a custom circuit whose vdf_cs_repeat rows are periodic (vdf_nova_pp_periodic_rows) gets their share of the
+                                    cross term from the description, without the sparse matrices (vdf_nova_pp_stencil == 7); 0: the generic
+                                    kernel over every row (0 until measured).  The proofs are the same bytes either way */
 } vdf_nova_tuning;
 void vdf_nova_tuning_default(vdf_nova_tuning* out);
 /* public_params with the tuning given (NULL = the defaults); VDF_ERR_BAD_ARG for a field out of range */
@@ -231,9 +234,15 @@ int  vdf_nova_pp_early_rows(const vdf_pp* pp, uint64_t* begin, uint64_t* len);
  * (vdf_nifs_cross_term_minroot_forward) -- a CODE, not a count of variables per round (that circuit has 3; 3 and 4 were
  * taken); 0: they run through the generic sparse kernel (a custom circuit, or no early rows);
  * 6 (VDF_STENCIL_FORWARD_LANES): the forward circuit in lanes, all L (3t + 1) early rows as one run
- * (vdf_nifs_cross_term_minroot_forward_lanes) -- a code like 5 */
-enum { VDF_STENCIL_FORWARD = 5, VDF_STENCIL_FORWARD_LANES = 6 };
+ * (vdf_nifs_cross_term_minroot_forward_lanes) -- a code like 5;
+ * 7 (VDF_STENCIL_PERIODIC): a custom circuit whose vdf_cs_repeat rows are periodic, with tuning.periodic_rows = 1: those rows run
+ * from their description (vdf_hip.h vdf_nifs_cross_term_periodic), every other row through the generic kernel */
+enum { VDF_STENCIL_FORWARD = 5, VDF_STENCIL_FORWARD_LANES = 6, VDF_STENCIL_PERIODIC = 7 };
 int  vdf_nova_pp_stencil(const vdf_pp* pp);
+/* 1 when the parameters of a custom circuit carry a periodic description of its vdf_cs_repeat rows (whatever the tuning says about
+ * using it), else 0 and zeros: the rows [row_begin, row_begin + row_count) it covers (repetitions lead .. t - 1), the lead, and the
+ * terms of one repetition in all three matrices.  Outputs may be NULL. */
+int  vdf_nova_pp_periodic_rows(const vdf_pp* pp, uint64_t* row_begin, uint64_t* row_count, uint64_t* lead, uint64_t* terms_per_rep);
 /* The same answer without a device (host only): builds the shape of the built-in step circuit at t, finds the early rows
  * and compares them with the stencil; returns 5 / 4 / 3 / 0 (negative: an error code).  Outputs may be NULL. */
 int  vdf_nova_shape_stencil(uint64_t t, int circuit_kind, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin);
@@ -445,8 +454,14 @@ int     vdf_cs_value(const vdf_cs* cs, vdf_num a, vdf_fe* out);       /* witness
  * the fresh witness before it is committed; vdf_nova_pp_segment names the run.
  *
  * LIMITS, each VDF_ERR_BAD_ARG: one vdf_cs_repeat per circuit; 1 <= t < 2^31; n_carry <= n_adv; the caps below.  The parameters
- * keep the tape: a prove_step whose body records another one is VDF_ERR_BAD_ARG.  Out of scope for custom circuits: early rows
- * of the cross term, lookahead and stencils (T is made and committed in one piece: vdf_nifs_cross_term). */
+ * keep the tape: a prove_step whose body records another one is VDF_ERR_BAD_ARG.
+ *
+ * THE CROSS TERM.  The rows of the repetitions come from replaying one tape, so from some repetition on they are periodic: the
+ * parameters read that off the shape's triples, compare it with every triple of every repetition, and keep the description
+ * (vdf_nova_pp_periodic_rows).  With tuning.periodic_rows = 1 a step's cross term then takes those rows from the description
+ * (vdf_hip.h vdf_nifs_cross_term_periodic) and only the others through the sparse matrices; a circuit whose rows are not periodic
+ * (a carry that accumulates: its rows grow with j) keeps the generic kernel.  Out of scope for custom circuits: early rows of
+ * the cross term, lookahead and a second repeat (T is made and committed in one piece). */
 #define VDF_ROUND_MAX_INV 16
 #define VDF_ROUND_MAX_CARRY 8
 #define VDF_ROUND_MAX_ADV 8
@@ -526,6 +541,9 @@ int  vdf_nova_prove_step_custom(vdf_pp* pp, vdf_proof** proof, const vdf_step_ci
 int  vdf_nova_verify_custom(const vdf_proof* proof, vdf_pp* pp, size_t num_steps, const vdf_fe* z0, const vdf_fe* zi, int* ok);
 /* the same parameters in the orientation `field`: the custom circuit is synthesised over that field (vdf_cs_* values are its elements) */
 int  vdf_nova_public_params_custom_field(vdf_ctx* ctx, int field, const vdf_step_circuit* primary, int gens_family, vdf_pp** out);
+/* ... with the tuning given (NULL = the defaults, what the two constructors above use); VDF_ERR_BAD_ARG for a field out of range */
+int  vdf_nova_public_params_custom_tuned(vdf_ctx* ctx, int field, const vdf_step_circuit* primary, int gens_family,
+                                         const vdf_nova_tuning* tuning, vdf_pp** out);
 
 /* ---- host-only entry points (no device): what the CPU tests pin against oracle/nova.py ------------------------- */
 /* the random oracle: lane 1 of the sponge after absorbing xs under `tag` (a full field element, Montgomery in and out) */
@@ -538,6 +556,35 @@ int  vdf_nova_shape_digest(uint64_t num_iters_per_step, int circuit_kind, int ge
 int  vdf_nova_shape_export(uint64_t num_iters_per_step, int circuit_kind, int side, uint64_t nnz[3], uint32_t* const rows[3],
                            uint32_t* const cols[3], vdf_fe* const vals[3]);
 int  vdf_nova_shape_digest_custom(const vdf_step_circuit* primary, int gens_family, uint8_t out[32], uint64_t sizes[2][3]);
+/* vdf_nova_shape_export for a custom primary circuit synthesised over `field` (side 1: the secondary shape of that orientation) */
+int  vdf_nova_shape_export_custom(int field, const vdf_step_circuit* primary, int side, uint64_t nnz[3], uint32_t* const rows[3],
+                                  uint32_t* const cols[3], vdf_fe* const vals[3]);
+/* ---- periodic rows (vdf_hip.h vdf_periodic_rows), host only ---------------------------------------------------------------
+ * Detection over COO triples: are the rows row_begin + j * n_cons + c (j < t, c < n_cons; the variables of repetition j at
+ * seg_begin + j * n_vars) periodic from some lead j0 in 0 .. 4 on?  The pattern is taken from repetition j0, the slopes of the
+ * affine coefficients from j0 + 1, and then EVERY triple of EVERY repetition j0 .. t - 1 in all three matrices is compared with
+ * it: the same set of terms, SEG coefficients equal, ABS coefficients equal to c0 + (j - j0) c1 in the field.  Returns 1 and the
+ * description (row_start / terms / consts: caller's arrays of the caps, which *out then points into; *lead = j0; the rows covered
+ * are [*first_row, *first_row + *row_count)), or 0 for none -- a mismatch anywhere, fewer than two periodic repetitions, a row of
+ * more than VDF_PERIODIC_MAX_ROW_TERMS terms, a cap exceeded: not an error, such rows keep the generic kernel -- or a NEGATIVE
+ * error code.  lead, first_row, row_count may be NULL. */
+int  vdf_nova_periodic_rows_detect(int field, const uint64_t nnz[3], const uint32_t* const rows[3], const uint32_t* const cols[3],
+                                   const vdf_fe* const vals[3], size_t seg_begin, size_t n_vars, size_t row_begin, size_t n_cons, uint64_t t,
+                                   uint16_t row_start[VDF_PERIODIC_MAX_STARTS], vdf_periodic_term terms[VDF_PERIODIC_MAX_TERMS],
+                                   vdf_fe consts[VDF_PERIODIC_MAX_CONSTS], vdf_periodic_rows* out, uint64_t* lead, uint64_t* first_row,
+                                   uint64_t* row_count);
+/* vdf_nifs_cross_term_periodic restated on the host: the same arguments, the same refusals, every pointer host memory -- the
+ * reference of the device path, byte for byte. */
+int  vdf_nova_periodic_rows_eval(int field, const vdf_periodic_rows* rows, uint64_t j_first, uint64_t reps, size_t seg_begin,
+                                 size_t row_begin, size_t num_cols, size_t num_cons, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,
+                                 const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T);
+/* The detection public_params_custom would make, without a device: the primary shape of `primary` over `field` and its
+ * vdf_cs_repeat; returns as vdf_nova_periodic_rows_detect (0 also for a circuit without a repeat).  *seg_begin = the first variable
+ * of repetition 0, *num_cons / *num_cols = the primary shape's (num_cols = variables + 1 + public IO), filled either way. */
+int  vdf_nova_shape_periodic_custom(int field, const vdf_step_circuit* primary, uint16_t row_start[VDF_PERIODIC_MAX_STARTS],
+                                    vdf_periodic_term terms[VDF_PERIODIC_MAX_TERMS], vdf_fe consts[VDF_PERIODIC_MAX_CONSTS],
+                                    vdf_periodic_rows* out, uint64_t* seg_begin, uint64_t* lead, uint64_t* first_row, uint64_t* row_count,
+                                    uint64_t* num_cons, uint64_t* num_cols);
 /* One augmented circuit synthesised on the host with every variable computed there (small t only).  The inputs that
  * belong to the folded side (U_u, U_X, u_X) are in Montgomery form of THAT side's scalar field, everything else in the
  * circuit's own field.  result / input: the MinRoot step's states (side 0; ignored for side 1).  arity = 3 / 1. */

@@ -1679,6 +1679,23 @@ int vdf_nifs_cross_term_minroot_forward_lanes(vdf_ctx* ctx, int field, uint64_t 
   });
 }
 
+int vdf_nifs_cross_term_periodic(vdf_ctx* ctx, int field, const vdf_periodic_rows* rows, uint64_t j_first, uint64_t reps, size_t seg_begin,
+                                 size_t row_begin, size_t num_cols, size_t num_cons, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,
+                                 const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T) {
+  return guarded(ctx, [&]() -> Status {
+    if (!rows || !z2 || !Az1 || !Bz1 || !Cz1 || !u1 || !Az2 || !Bz2 || !Cz2 || !T) return Status{VDF_ERR_BAD_ARG, "null argument"};
+    if (ptr_is_device(rows) || ptr_is_device(rows->row_start) || ptr_is_device(rows->terms) || ptr_is_device(rows->consts) || ptr_is_device(u1))
+      return Status{VDF_ERR_BAD_ARG, "the description and scalar operands of fused calls live in host memory"};
+    for (const void* v : {(const void*)z2, (const void*)Az1, (const void*)Bz1, (const void*)Cz1, (const void*)Az2, (const void*)Bz2,
+                          (const void*)Cz2, (const void*)T})
+      if (!ptr_is_device(v)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
+    VDF_TRY(vdf::vec_nifs_cross_periodic(field, rows, j_first, reps, seg_begin, row_begin, num_cols, num_cons, z2, Az1, Bz1, Cz1, u1, Az2, Bz2,
+                                         Cz2, T, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
 int vdf_nifs_cross_term_minroot_fold(vdf_ctx* ctx, int field, int vars_per_round, uint64_t t, size_t seg_begin, size_t one_col,
                                      size_t row_begin, const vdf_fe* z2, const vdf_fe* r, vdf_fe* Az1, vdf_fe* Bz1, vdf_fe* Cz1,
                                      vdf_fe* E1, const vdf_fe* T_prev, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2,

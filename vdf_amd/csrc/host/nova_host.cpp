@@ -582,6 +582,51 @@ int vdf_nova_shape_digest_custom(const vdf_step_circuit* primary, int gens_famil
   });
 }
 
+int vdf_nova_shape_export_custom(int fid, const vdf_step_circuit* primary, int side, uint64_t nnz[3], uint32_t* const rows[3],
+                                 uint32_t* const cols[3], vdf_fe* const vals[3]) {
+  return nova_guard([&]() -> int {
+    if (!valid_field(fid) || !primary || !primary->synthesize || primary->arity == 0 || primary->arity > 64 || !nnz ||
+        (side != PRIMARY && side != SECONDARY))
+      return fail(VDF_ERR_BAD_ARG, "bad argument");
+    HostShape sh[2];
+    { int rc = build_shapes(fid, 0, VDF_CIRCUIT_CUSTOM, sh, primary); if (rc != VDF_OK) return rc; }
+    const HostShape& h = sh[side];
+    const bool fill = rows && cols && vals;
+    for (int k = 0; k < 3; ++k) {
+      const size_t z = h.m[k].rows.size();
+      if (fill) {
+        if (nnz[k] < z || !rows[k] || !cols[k] || !vals[k]) return fail(VDF_ERR_BAD_LENGTH, "triple arrays too short");
+        memcpy(rows[k], h.m[k].rows.data(), z * 4);
+        memcpy(cols[k], h.m[k].cols.data(), z * 4);
+        memcpy(vals[k], h.m[k].vals.data(), z * 32);
+      }
+      nnz[k] = z;
+    }
+    return VDF_OK;
+  });
+}
+
+int vdf_nova_shape_periodic_custom(int fid, const vdf_step_circuit* primary, uint16_t row_start[VDF_PERIODIC_MAX_STARTS],
+                                   vdf_periodic_term terms[VDF_PERIODIC_MAX_TERMS], vdf_fe consts[VDF_PERIODIC_MAX_CONSTS],
+                                   vdf_periodic_rows* out, uint64_t* seg_begin, uint64_t* lead, uint64_t* first_row, uint64_t* row_count,
+                                   uint64_t* num_cons, uint64_t* num_cols) {
+  const int rc = nova_guard([&]() -> int {
+    if (!valid_field(fid) || !primary || !primary->synthesize || primary->arity == 0 || primary->arity > 64 || !row_start || !terms || !consts || !out)
+      return -fail(VDF_ERR_BAD_ARG, "bad argument");
+    HostShape sh[2];
+    RepeatState rp;
+    { int rc = build_shapes(fid, 0, VDF_CIRCUIT_CUSTOM, sh, primary, nullptr, 1, &rp); if (rc != VDF_OK) return -rc; }
+    if (seg_begin) *seg_begin = rp.used ? rp.var_begin : 0;
+    if (num_cons) *num_cons = sh[PRIMARY].num_cons;
+    if (num_cols) *num_cols = sh[PRIMARY].num_vars + 1 + NUM_IO;
+    PeriodicRows pr;
+    if (!rp.used || !detect_periodic_rows(sh[PRIMARY].m, field(fid), rp.var_begin, rp.rec.n_vars, rp.row_begin, rp.rec.n_cons, rp.t, &pr)) return 0;
+    periodic_rows_export(pr, row_start, terms, consts, out, lead, first_row, row_count);
+    return 1;
+  });
+  return rc > 1 ? -rc : rc;                          // (nova_guard's own failures are positive codes)
+}
+
 // (fid: the orientation; the folded side's scalars are in the field of the OTHER side's circuit)
 static AugInputs aug_from_abi(int fid, int side, const vdf_nova_aug_inputs* a) {
   const Field& own = field(cycle_field(fid, 1 - side));                 // the folded side's scalar field
@@ -696,7 +741,7 @@ bool tuning_valid(const vdf_nova_tuning& t) {
          in(t.small_window, 6, 16) && in(t.big_window, 12, 20) && in(t.packed_commit, 0, 1) && in(t.lookahead_early, 0, 1) &&
          in(t.gate_accumulate, 0, 1) && in(t.fold_on_rows, 0, 1) && in(t.nifs_ahead, 0, 1) && in(t.early_row_parts, 1, 3) &&
          in(t.lookahead_priority, 0, 3) && in(t.side_accumulate_fill, 1, 3) && in(t.verbose, 0, 1) && in(t.compress_queues, 0, 1) && in(t.rows_at_challenge, 0, 1) &&
-         in(t.fold_fused, 0, 1);
+         in(t.fold_fused, 0, 1) && in(t.periodic_rows, 0, 1);
 }
 const vdf_nova_tuning& default_tuning() {
   static const vdf_nova_tuning d = [] {
@@ -706,6 +751,7 @@ const vdf_nova_tuning& default_tuning() {
     t.big_window = 16; t.packed_commit = 1; t.lookahead_early = 1; t.gate_accumulate = 1; t.fold_on_rows = 1; t.nifs_ahead = 1;
     t.early_row_parts = 1; t.lookahead_priority = 1; t.side_accumulate_fill = 3; t.verbose = 0; t.compress_queues = 1; t.rows_at_challenge = 1;
     t.fold_fused = 0;      // measured (profiles/r05_ab_fold_fused.txt): the fused fold shortens the rows' path by ~45 us and the step gets no faster
+    t.periodic_rows = 0;   // an option until it is measured against the generic kernel on the same rows
     // the environment overrides of earlier rounds, read once: the only place the prover looks at the environment for tuning
     const struct { const char* name; int32_t* field; } vars[] = {
         {"VDF_NOVA_DIGIT_WINDOW", &t.digit_window}, {"VDF_NOVA_T_AHEAD", &t.early_rows}, {"VDF_NOVA_STENCIL", &t.stencil},
@@ -713,7 +759,7 @@ const vdf_nova_tuning& default_tuning() {
         {"VDF_NOVA_LOOKAHEAD_EARLY", &t.lookahead_early}, {"VDF_NOVA_GATE", &t.gate_accumulate}, {"VDF_NOVA_FOLD_ON_ROWS", &t.fold_on_rows},
         {"VDF_NOVA_NIFS_AHEAD", &t.nifs_ahead}, {"VDF_NOVA_T_PARTS", &t.early_row_parts}, {"VDF_NOVA_LOOKAHEAD_PRIO", &t.lookahead_priority},
         {"VDF_NOVA_SIDE_ACC_WG", &t.side_accumulate_fill}, {"VDF_NOVA_VERBOSE", &t.verbose}, {"VDF_NOVA_COMPRESS_QUEUES", &t.compress_queues}, {"VDF_NOVA_ROWS_AT_CHALLENGE", &t.rows_at_challenge},
-        {"VDF_NOVA_FOLD_FUSED", &t.fold_fused}};
+        {"VDF_NOVA_FOLD_FUSED", &t.fold_fused}, {"VDF_NOVA_PERIODIC_ROWS", &t.periodic_rows}};
     for (const auto& v : vars) {
       const char* e = env_override(v.name);
       if (!e || !*e) continue;
@@ -822,10 +868,15 @@ int vdf_nova_public_params_custom(vdf_ctx* ctx, const vdf_step_circuit* primary,
   return vdf_nova_public_params_custom_field(ctx, VDF_FIELD_FQ, primary, gens_family, out);
 }
 int vdf_nova_public_params_custom_field(vdf_ctx* ctx, int fid, const vdf_step_circuit* primary, int gens_family, vdf_pp** out) {
+  return vdf_nova_public_params_custom_tuned(ctx, fid, primary, gens_family, nullptr, out);
+}
+int vdf_nova_public_params_custom_tuned(vdf_ctx* ctx, int fid, const vdf_step_circuit* primary, int gens_family, const vdf_nova_tuning* tuning,
+                                        vdf_pp** out) {
   return nova_guard([&]() -> int {
     if (!ctx || !out || !primary || !primary->synthesize || primary->arity == 0 || primary->arity > 64 || !valid_field(fid))
       return fail(VDF_ERR_BAD_ARG, "bad argument");
-    return public_params_impl(ctx, fid, 0, VDF_CIRCUIT_CUSTOM, primary, gens_family, default_tuning(), out);
+    if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
+    return public_params_impl(ctx, fid, 0, VDF_CIRCUIT_CUSTOM, primary, gens_family, tuning ? *tuning : default_tuning(), out);
   });
 }
 
@@ -1021,6 +1072,12 @@ static int public_params_impl(vdf_ctx* ctx, int fid, uint64_t t, int circuit_kin
   // in device memory (everything a built-in circuit gets on top of that -- early rows, lookahead, a stencil -- stays with them)
   pp->seg_begin = custom ? (pp->round.used ? pp->round.var_begin : 0) : sh[PRIMARY].step_begin;
   pp->seg_len = custom ? (pp->round.used ? (size_t)pp->round.t * pp->round.rec.n_vars : 0) : sh[PRIMARY].step_end - sh[PRIMARY].step_begin;
+  if (custom && pp->round.used) {
+    // the rows of the repetitions, read off the triples and compared with every one of them: periodic, or the generic kernel
+    const RepeatState& rp = pp->round;
+    detect_periodic_rows(sh[PRIMARY].m, field(fid), rp.var_begin, rp.rec.n_vars, rp.row_begin, rp.rec.n_cons, rp.t, &pp->periodic);
+    pp->periodic_on = pp->periodic.valid && tune.periodic_rows != 0;
+  }
   if (pp->seg_len && !custom) {
     // the longest run of primary constraints that read nothing of a witness but the segment, the step circuit's input z_in
     // (the `arity` variables allocated right before it, synthesize_augmented; known when a step begins) and the constant,
@@ -1200,7 +1257,16 @@ int vdf_nova_pp_early_rows(const vdf_pp* pp, uint64_t* begin, uint64_t* len) {
   if (len) *len = pp->ahead_rows;
   return VDF_OK;
 }
-int vdf_nova_pp_stencil(const vdf_pp* pp) { return pp ? pp->stencil_per : 0; }
+int vdf_nova_pp_stencil(const vdf_pp* pp) { return !pp ? 0 : pp->periodic_on ? VDF_STENCIL_PERIODIC : pp->stencil_per; }
+int vdf_nova_pp_periodic_rows(const vdf_pp* pp, uint64_t* row_begin, uint64_t* row_count, uint64_t* lead, uint64_t* terms_per_rep) {
+  if (!pp) return 0;
+  const PeriodicRows& pr = pp->periodic;
+  if (row_begin) *row_begin = pr.valid ? pr.row_begin : 0;
+  if (row_count) *row_count = pr.valid ? pr.row_count : 0;
+  if (lead) *lead = pr.valid ? pr.lead : 0;
+  if (terms_per_rep) *terms_per_rep = pr.valid ? pr.terms.size() : 0;
+  return pr.valid ? 1 : 0;
+}
 // host only (no device): what vdf_nova_public_params would find for the built-in step circuit `circuit_kind` at `t`
 static int shape_stencil_impl(int fid, uint64_t t, int circuit_kind, size_t lanes, uint64_t* early_begin, uint64_t* early_len, uint64_t* seg_begin) {
   return nova_guard([&]() -> int {
@@ -1627,6 +1693,20 @@ struct StepRun {
           HIPCALL(ctx, vdf_nifs_cross_term_rows(ctx, S1.shape, ta_b, ta_n, VDF_ROWS_OUTSIDE, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0],
                                                 (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2], (const vdf_fe*)&s1.inst.u,
                                                 (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
+        } else if (custom && pp->periodic_on) {
+          // the rows of the repeat's periodic repetitions from their description, every other row through the sparse matrices:
+          // two launches on the step's own queue, T committed in one piece as before
+          group(s1.d_T, 0, S1.num_cons);
+          const PeriodicRows& pr = pp->periodic;
+          const vdf_periodic_rows view = pr.view();
+          HIPCALL(ctx, vdf_nifs_cross_term_rows(ctx, S1.shape, pr.row_begin, pr.row_count, VDF_ROWS_OUTSIDE, (const vdf_fe*)d_z2,
+                                                (const vdf_fe*)s1.d_abc[0], (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2],
+                                                (const vdf_fe*)&s1.inst.u, (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2],
+                                                (vdf_fe*)s1.d_T));
+          HIPCALL(ctx, vdf_nifs_cross_term_periodic(ctx, S1.field, &view, pr.lead, pp->round.t - pr.lead, pp->round.var_begin, pr.row_begin,
+                                                    S1.ncols, S1.num_cons, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0],
+                                                    (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2], (const vdf_fe*)&s1.inst.u,
+                                                    (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
         } else {
           group(s1.d_T, 0, S1.num_cons);
           HIPCALL(ctx, vdf_nifs_cross_term(ctx, S1.shape, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0], (const vdf_fe*)s1.d_abc[1],

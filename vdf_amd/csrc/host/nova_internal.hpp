@@ -111,6 +111,10 @@ struct vdf_pp {
   // a custom circuit's vdf_cs_repeat as its shape synthesis recorded it (the body, t, where its variables begin): every
   // prove_step's own recording is compared with it; [seg_begin, seg_begin + seg_len) are its variables
   vdfnova::RepeatState round;
+  // ... and the rows of its repetitions as a periodic description, when they are one (detect_periodic_rows, checked against every
+  // triple when the parameters were made); periodic_on: tuning.periodic_rows lets the prover use it (vdf_nova_pp_stencil == 7)
+  vdfnova::PeriodicRows periodic;
+  bool periodic_on = false;
   // constraints of the primary shape that read nothing of a fresh witness but that segment (and the constant): their
   // share of a step's cross term and of its commitment is made ahead of the rest, [ahead_row, ahead_row + ahead_rows)
   size_t ahead_row = 0, ahead_rows = 0;

@@ -51,6 +51,7 @@ struct RepeatState {
   RoundRecord rec;
   uint64_t t = 0;
   size_t var_begin = 0;                            // index of the first variable of repetition 0 in the witness
+  size_t row_begin = 0;                            // ... and of its first constraint in the shape
   const void* d_advice = nullptr;                  // witness mode, advice in device memory: the variables were skipped (cs.dev_begin / dev_len)
   std::vector<Fe> inv;                             // ... and the values of inv, for the kernel
 };
@@ -75,6 +76,39 @@ int eval_walk_tape(int field, const vdf_round_tape* tape, const Fe* inv, Fe* ent
 // vdf_round_tape_forward_walk on the host (vdf_nova_forward_tape_eval): the same arguments, the same refusals, host memory
 int eval_forward_tape(int field, const vdf_round_tape* tape, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* checkpoints,
                       uint64_t every, size_t cp_stride, Fe* trace, size_t walk_stride, uint64_t base, uint64_t j_base, uint64_t j_walk_step);
+
+// The periodic rows of a repeat, as detect_periodic_rows read them off a shape's triples (include/vdf_hip.h vdf_periodic_rows):
+// rows [row_begin, row_begin + row_count) are repetitions lead .. t - 1, and `view` is what the kernel and the host evaluator take.
+struct PeriodicRows {
+  bool valid = false;
+  uint64_t lead = 0;
+  size_t row_begin = 0, row_count = 0;
+  uint32_t n_cons = 0, n_vars = 0;
+  std::vector<uint16_t> row_start;
+  std::vector<vdf_periodic_term> terms;
+  std::vector<Fe> consts;
+  vdf_periodic_rows view() const {
+    vdf_periodic_rows v;
+    v.n_cons = n_cons; v.n_vars = n_vars; v.j0 = lead;
+    v.row_start = row_start.data();
+    v.terms = terms.data(); v.n_terms = terms.size();
+    v.consts = (const vdf_fe*)consts.data(); v.n_consts = consts.size();
+    return v;
+  }
+};
+// Are the rows of repetitions j0 .. t - 1 (n_cons each from row_begin on, the variables of repetition j at seg_begin + j n_vars)
+// periodic, for the smallest j0 in 0 .. 4?  The pattern is taken from repetition j0, the slopes from j0 + 1, and then EVERY triple
+// of EVERY repetition in all three matrices is compared with it.  false (and *out untouched): a mismatch anywhere, fewer than two
+// periodic repetitions, a row of more than VDF_PERIODIC_MAX_ROW_TERMS terms, or a cap of the description exceeded.
+bool detect_periodic_rows(const Coo m[3], const Field& F, size_t seg_begin, size_t n_vars, size_t row_begin, size_t n_cons, uint64_t t,
+                          PeriodicRows* out);
+// vdf_nifs_cross_term_periodic on the host (vdf_nova_periodic_rows_eval): the same arguments, the same refusals, host memory
+int eval_periodic_rows(int field, const vdf_periodic_rows* rows, uint64_t j_first, uint64_t reps, size_t seg_begin, size_t row_begin,
+                       size_t num_cols, size_t num_cons, const Fe* z2, const Fe* az1, const Fe* bz1, const Fe* cz1, const Fe* u1, Fe* az2,
+                       Fe* bz2, Fe* cz2, Fe* T);
+// a description into the caller's arrays of the caps, as the host-only entry points of vdf_nova.h hand it out
+void periodic_rows_export(const PeriodicRows& pr, uint16_t* row_start, vdf_periodic_term* terms, vdf_fe* consts, vdf_periodic_rows* out,
+                          uint64_t* lead, uint64_t* first_row, uint64_t* row_count);
 
 }  // namespace vdfnova
 

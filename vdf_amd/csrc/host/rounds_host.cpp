@@ -422,6 +422,166 @@ int eval_forward_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entr
 
 }  // namespace vdfnova
 
+// ---- periodic rows (rounds.hpp) ---------------------------------------------------------------------------------------------
+namespace vdfnova {
+
+bool detect_periodic_rows(const Coo m[3], const Field& F, size_t seg_begin, size_t n_vars, size_t row_begin, size_t n_cons, uint64_t t,
+                          PeriodicRows* out) {
+  if (n_cons == 0 || n_cons > VDF_PERIODIC_MAX_ROWS || n_vars == 0 || n_vars > UINT32_MAX || t < 2 || t > ((uint64_t)1 << 31) / n_cons) return false;
+  typedef std::vector<std::pair<uint32_t, Fe>> Row;
+  const size_t total = (size_t)t * n_cons;
+  const uint64_t run_end = (uint64_t)seg_begin + t * (uint64_t)n_vars;
+  std::vector<Row> got[3];
+  for (int k = 0; k < 3; ++k) {
+    got[k].resize(total);
+    for (size_t e = 0; e < m[k].rows.size(); ++e)
+      if (m[k].rows[e] >= row_begin && m[k].rows[e] - row_begin < total) got[k][m[k].rows[e] - row_begin].push_back({m[k].cols[e], canon(m[k].vals[e], F)});
+    for (Row& g : got[k]) {
+      std::sort(g.begin(), g.end(), [](const std::pair<uint32_t, Fe>& a, const std::pair<uint32_t, Fe>& b) { return a.first < b.first; });
+      size_t w = 0;                                  // a column named twice counts once, with the sum
+      for (size_t e = 0; e < g.size(); ++e)
+        if (w && g[w - 1].first == g[e].first) g[w - 1].second = add(g[w - 1].second, g[e].second, F); else g[w++] = g[e];
+      g.resize(w);
+    }
+  }
+  for (uint64_t j0 = 0; j0 <= 4 && j0 + 2 <= t; ++j0) {
+    PeriodicRows pr;
+    pr.lead = j0; pr.n_cons = (uint32_t)n_cons; pr.n_vars = (uint32_t)n_vars;
+    pr.row_begin = row_begin + (size_t)j0 * n_cons; pr.row_count = (size_t)(t - j0) * n_cons;
+    pr.row_start.push_back(0);
+    bool ok = true;
+    auto konst = [&](const Fe& v) -> int {
+      for (size_t q = 0; q < pr.consts.size(); ++q) if (pr.consts[q] == v) return (int)q;
+      if (pr.consts.size() == VDF_PERIODIC_MAX_CONSTS) return -1;
+      pr.consts.push_back(v);
+      return (int)pr.consts.size() - 1;
+    };
+    const int64_t base0 = (int64_t)(seg_begin + j0 * n_vars);
+    for (size_t c = 0; c < n_cons && ok; ++c)
+      for (int k = 0; k < 3 && ok; ++k) {
+        const Row& ra = got[k][j0 * n_cons + c];
+        const Row& rb = got[k][(j0 + 1) * n_cons + c];
+        if (ra.size() > VDF_PERIODIC_MAX_ROW_TERMS || pr.terms.size() + ra.size() > VDF_PERIODIC_MAX_TERMS) { ok = false; break; }
+        for (const auto& e : ra) {
+          vdf_periodic_term tm;
+          tm.pad = 0; tm.c1 = VDF_TERM_NO_SLOPE;
+          const int k0 = konst(e.second);
+          if (k0 < 0) { ok = false; break; }
+          tm.c0 = (uint8_t)k0;
+          if (e.first >= seg_begin && e.first < run_end) {
+            const int64_t rel = (int64_t)e.first - base0;
+            if (rel < INT32_MIN || rel > INT32_MAX) { ok = false; break; }
+            tm.kind = VDF_TERM_SEG; tm.col = (uint32_t)(int32_t)rel;
+          } else {
+            tm.kind = VDF_TERM_ABS; tm.col = e.first;
+            const auto it = std::lower_bound(rb.begin(), rb.end(), e.first, [](const std::pair<uint32_t, Fe>& a, uint32_t col) { return a.first < col; });
+            if (it == rb.end() || it->first != e.first) { ok = false; break; }
+            const Fe slope = sub(it->second, e.second, F);
+            if (!slope.is_zero()) {
+              const int k1 = konst(slope);
+              if (k1 < 0) { ok = false; break; }
+              tm.c1 = (uint8_t)k1;
+            }
+          }
+          pr.terms.push_back(tm);
+        }
+        pr.row_start.push_back((uint16_t)pr.terms.size());
+      }
+    if (!ok) continue;
+    // every triple of every repetition j0 .. t - 1 against the pattern
+    std::vector<Fe> coef(pr.terms.size());
+    for (size_t e = 0; e < pr.terms.size(); ++e) coef[e] = pr.consts[pr.terms[e].c0];
+    Row want;
+    for (uint64_t j = j0; j < t && ok; ++j) {
+      const int64_t base = (int64_t)(seg_begin + j * n_vars);
+      for (size_t c = 0; c < n_cons && ok; ++c)
+        for (int k = 0; k < 3 && ok; ++k) {
+          const Row& g = got[k][j * n_cons + c];
+          const size_t b = pr.row_start[3 * c + k], e = pr.row_start[3 * c + k + 1];
+          if (g.size() != e - b) { ok = false; break; }
+          want.clear();
+          for (size_t q = b; q < e; ++q) {
+            const vdf_periodic_term& tm = pr.terms[q];
+            const int64_t col = tm.kind == VDF_TERM_SEG ? base + (int32_t)tm.col : (int64_t)tm.col;
+            if (col < 0 || col > (int64_t)UINT32_MAX) { ok = false; break; }
+            want.push_back({(uint32_t)col, coef[q]});
+          }
+          if (!ok) break;
+          std::sort(want.begin(), want.end(), [](const std::pair<uint32_t, Fe>& x, const std::pair<uint32_t, Fe>& y) { return x.first < y.first; });
+          for (size_t q = 0; q < g.size(); ++q)
+            if (g[q].first != want[q].first || g[q].second != want[q].second) { ok = false; break; }
+        }
+      for (size_t e = 0; e < pr.terms.size(); ++e)
+        if (pr.terms[e].c1 != VDF_TERM_NO_SLOPE) coef[e] = add(coef[e], pr.consts[pr.terms[e].c1], F);
+    }
+    if (!ok) continue;
+    pr.valid = true;
+    *out = std::move(pr);
+    return true;
+  }
+  return false;
+}
+
+int eval_periodic_rows(int fid, const vdf_periodic_rows* pr, uint64_t j_first, uint64_t reps, size_t seg_begin, size_t row_begin,
+                       size_t num_cols, size_t num_cons, const Fe* z2, const Fe* az1, const Fe* bz1, const Fe* cz1, const Fe* u1, Fe* az2,
+                       Fe* bz2, Fe* cz2, Fe* T) {
+  if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
+  if (!pr || !z2 || !az1 || !bz1 || !cz1 || !u1 || !az2 || !bz2 || !cz2 || !T) return fail(VDF_ERR_BAD_ARG, "null argument");
+  if (!pr->row_start || (pr->n_terms && !pr->terms) || (pr->n_consts && !pr->consts)) return fail(VDF_ERR_BAD_ARG, "null description");
+  if (pr->n_cons == 0 || pr->n_cons > VDF_PERIODIC_MAX_ROWS || pr->n_vars == 0 || pr->n_terms > VDF_PERIODIC_MAX_TERMS ||
+      pr->n_consts > VDF_PERIODIC_MAX_CONSTS)
+    return fail(VDF_ERR_BAD_ARG, "periodic rows exceed a published cap (VDF_PERIODIC_MAX_*), or have no row or variable");
+  if (pr->row_start[0] != 0 || pr->row_start[3 * pr->n_cons] != pr->n_terms) return fail(VDF_ERR_BAD_ARG, "row_start does not span the terms");
+  for (uint32_t q = 0; q < 3 * pr->n_cons; ++q)
+    if (pr->row_start[q + 1] < pr->row_start[q] || pr->row_start[q + 1] - pr->row_start[q] > VDF_PERIODIC_MAX_ROW_TERMS)
+      return fail(VDF_ERR_BAD_ARG, "row_start descends, or a row has more than VDF_PERIODIC_MAX_ROW_TERMS terms in one matrix");
+  if (j_first < pr->j0) return fail(VDF_ERR_BAD_ARG, "j_first lies before the repetition the pattern was taken from");
+  if (reps == 0) return VDF_OK;
+  if (reps > ((uint64_t)1 << 31) / pr->n_cons || j_first > UINT32_MAX || j_first + reps > UINT32_MAX)
+    return fail(VDF_ERR_BAD_ARG, "more than 2^31 rows, or repetitions beyond 2^32");
+  const uint64_t rows = reps * pr->n_cons, j_last = j_first + reps - 1;
+  if (row_begin > num_cons || rows > num_cons - row_begin) return fail(VDF_ERR_BAD_ARG, "the row range ends beyond num_cons");
+  if (num_cols == 0 || num_cols > ((size_t)1 << 32) || seg_begin > num_cols) return fail(VDF_ERR_BAD_ARG, "num_cols out of range, or seg_begin beyond it");
+  const bool seg_far = j_last * pr->n_vars > ((uint64_t)1 << 33);
+  const int64_t first_seg = (int64_t)(seg_begin + j_first * pr->n_vars), last_seg = (int64_t)(seg_begin + j_last * pr->n_vars);
+  for (size_t e = 0; e < pr->n_terms; ++e) {
+    const vdf_periodic_term& t = pr->terms[e];
+    const std::string at = "term " + std::to_string(e);
+    if (t.kind != VDF_TERM_SEG && t.kind != VDF_TERM_ABS) return fail(VDF_ERR_BAD_ARG, at + ": unknown kind");
+    if (t.c0 >= pr->n_consts || (t.c1 != VDF_TERM_NO_SLOPE && (t.c1 >= pr->n_consts || t.kind != VDF_TERM_ABS)))
+      return fail(VDF_ERR_BAD_ARG, at + ": constant index out of range, or a slope on a SEG term");
+    if (t.kind == VDF_TERM_ABS) {
+      if (t.col >= num_cols) return fail(VDF_ERR_BAD_ARG, at + ": column beyond num_cols");
+    } else if (seg_far || first_seg + (int32_t)t.col < 0 || last_seg + (int32_t)t.col >= (int64_t)num_cols)
+      return fail(VDF_ERR_BAD_ARG, at + ": reaches a column outside [0, num_cols) in the first or the last repetition");
+  }
+  const Field& F = field(fid);
+  const Fe* consts = (const Fe*)pr->consts;
+  for (uint64_t i = 0; i < rows; ++i) {
+    const uint64_t j = j_first + i / pr->n_cons;
+    const uint32_t c = (uint32_t)(i % pr->n_cons);
+    const size_t r = row_begin + i;
+    Fe acc[3];
+    for (int k = 0; k < 3; ++k) {
+      acc[k] = zero();
+      for (uint32_t q = pr->row_start[3 * c + k]; q < pr->row_start[3 * c + k + 1]; ++q) {
+        const vdf_periodic_term& t = pr->terms[q];
+        const size_t col = t.kind == VDF_TERM_SEG ? (size_t)((int64_t)(seg_begin + j * pr->n_vars) + (int32_t)t.col) : (size_t)t.col;
+        Fe coef = consts[t.c0];
+        if (t.c1 != VDF_TERM_NO_SLOPE) coef = add(coef, mul(from_u64(j - pr->j0, F), consts[t.c1], F), F);
+        acc[k] = add(acc[k], mul(coef, z2[col], F), F);
+      }
+    }
+    az2[r] = acc[0]; bz2[r] = acc[1]; cz2[r] = acc[2];
+    Fe tt = add(mul(az1[r], acc[1], F), mul(acc[0], bz1[r], F), F);
+    tt = sub(tt, mul(*u1, acc[2], F), F);
+    T[r] = sub(tt, cz1[r], F);
+  }
+  return VDF_OK;
+}
+
+}  // namespace vdfnova
+
 // ---- the recording side of the vdf_cs_* calls (nova_host.cpp hands a call over when the handle records) ------------------
 namespace vdfnova {
 vdf_num rec_cs_const(vdf_cs* c, const vdf_fe* k) {
@@ -456,6 +616,20 @@ int rec_cs_enforce(vdf_cs* c, vdf_num a, vdf_num b, vdf_num cc) {
   if (nd[x].value_only || nd[y].value_only || nd[z].value_only) { c->bad = true; return VDF_ERR_BAD_ARG; }
   rec_push(c, R_ENFORCE, false, (uint32_t)x, (uint32_t)y, (uint32_t)z);
   return c->bad ? VDF_ERR_BAD_ARG : VDF_OK;
+}
+}  // namespace vdfnova
+
+namespace vdfnova {
+void periodic_rows_export(const PeriodicRows& pr, uint16_t* row_start, vdf_periodic_term* terms, vdf_fe* consts, vdf_periodic_rows* out,
+                          uint64_t* lead, uint64_t* first_row, uint64_t* row_count) {
+  memcpy(row_start, pr.row_start.data(), pr.row_start.size() * sizeof(uint16_t));
+  if (!pr.terms.empty()) memcpy(terms, pr.terms.data(), pr.terms.size() * sizeof(vdf_periodic_term));
+  if (!pr.consts.empty()) memcpy(consts, pr.consts.data(), pr.consts.size() * 32);
+  *out = pr.view();
+  out->row_start = row_start; out->terms = terms; out->consts = consts;
+  if (lead) *lead = pr.lead;
+  if (first_row) *first_row = pr.row_begin;
+  if (row_count) *row_count = pr.row_count;
 }
 }  // namespace vdfnova
 
@@ -510,6 +684,7 @@ int vdf_cs_repeat(vdf_cs* c, const vdf_round_body* b, uint64_t t, const vdf_num*
   rep.used = true;
   rep.t = t;
   rep.var_begin = cs.num_vars();
+  rep.row_begin = cs.rows;
   rep.d_advice = nullptr;
   const size_t na = rec.n_adv;
   if (cs.shape) {
@@ -591,6 +766,37 @@ int vdf_nova_forward_tape_eval(int fid, const vdf_round_tape* tape, const vdf_fe
   return nova_guard([&]() -> int {
     return eval_forward_tape(fid, tape, (const Fe*)inv, (Fe*)entries, n, rounds, (Fe*)checkpoints, every, cp_stride, (Fe*)trace, walk_stride,
                              base, j_base, j_walk_step);
+  });
+}
+
+int vdf_nova_periodic_rows_detect(int fid, const uint64_t nnz[3], const uint32_t* const rows[3], const uint32_t* const cols[3],
+                                  const vdf_fe* const vals[3], size_t seg_begin, size_t n_vars, size_t row_begin, size_t n_cons, uint64_t t,
+                                  uint16_t row_start[VDF_PERIODIC_MAX_STARTS], vdf_periodic_term terms[VDF_PERIODIC_MAX_TERMS],
+                                  vdf_fe consts[VDF_PERIODIC_MAX_CONSTS], vdf_periodic_rows* out, uint64_t* lead, uint64_t* first_row,
+                                  uint64_t* row_count) {
+  const int rc = nova_guard([&]() -> int {
+    if (!valid_field(fid) || !nnz || !rows || !cols || !vals || !row_start || !terms || !consts || !out) return -fail(VDF_ERR_BAD_ARG, "bad argument");
+    Coo m[3];
+    for (int k = 0; k < 3; ++k) {
+      if (nnz[k] && (!rows[k] || !cols[k] || !vals[k])) return -fail(VDF_ERR_BAD_ARG, "null triple array");
+      m[k].rows.assign(rows[k], rows[k] + nnz[k]);
+      m[k].cols.assign(cols[k], cols[k] + nnz[k]);
+      m[k].vals.assign((const Fe*)vals[k], (const Fe*)vals[k] + nnz[k]);
+    }
+    PeriodicRows pr;
+    if (!detect_periodic_rows(m, field(fid), seg_begin, n_vars, row_begin, n_cons, t, &pr)) return 0;
+    periodic_rows_export(pr, row_start, terms, consts, out, lead, first_row, row_count);
+    return 1;
+  });
+  return rc > 1 ? -rc : rc;                          // (nova_guard's own failures are positive codes)
+}
+
+int vdf_nova_periodic_rows_eval(int fid, const vdf_periodic_rows* rows, uint64_t j_first, uint64_t reps, size_t seg_begin, size_t row_begin,
+                                size_t num_cols, size_t num_cons, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1,
+                                const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T) {
+  return nova_guard([&]() -> int {
+    return eval_periodic_rows(fid, rows, j_first, reps, seg_begin, row_begin, num_cols, num_cons, (const Fe*)z2, (const Fe*)Az1, (const Fe*)Bz1,
+                              (const Fe*)Cz1, (const Fe*)u1, (Fe*)Az2, (Fe*)Bz2, (Fe*)Cz2, (Fe*)T);
   });
 }
 

@@ -328,6 +328,10 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tape, const 
                                    void* checkpoints, uint64_t every, size_t cp_stride, void* trace, size_t walk_stride, uint64_t base,
                                    uint64_t j_base, uint64_t j_walk_step, hipStream_t s);
 Status round_tape_forward_max_rounds(const vdf_round_tape* tape, const vdf_fe* inv, uint64_t* max_rounds);
+// rounds.hip: the cross term of periodic rows (vdf_hip.h vdf_periodic_rows; every index is checked before the launch)
+Status vec_nifs_cross_periodic(int field, const vdf_periodic_rows* rows, uint64_t j_first, uint64_t reps, size_t seg_begin, size_t row0,
+                               size_t num_cols, size_t num_cons, const void* z2, const void* az1, const void* bz1, const void* cz1,
+                               const vdf_fe* u1, void* az2, void* bz2, void* cz2, void* T, hipStream_t s);
 Status vec_step_z(int field, const void* trace_xy, uint64_t t, const vdf_fe z_in[3], const vdf_fe* i0, const vdf_fe* u,
                   const vdf_fe X[6], void* z, void* packed, hipStream_t s);
 Status vec_nifs_cross(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3],

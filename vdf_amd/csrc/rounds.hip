@@ -240,6 +240,105 @@ __global__ __launch_bounds__(64) void k_tape_forward_walk(TapeArgs tape, Forward
   for (uint32_t c = 0; c < na; ++c) fe_store<P>(ep + c * 32, slot_load<P>(tape_slots, stand + c, lane));
 }
 
+// ---- periodic rows: the cross term of the rows of such rounds without the sparse matrices (vdf_hip.h vdf_periodic_rows) --------
+// k_nifs_cross_minroot_forward_lanes for a round the library did not write: one row per lane, workgroups of 256, every running /
+// fresh vector read and written as contiguous 32-byte elements.  What the hand-written stencil has in its code -- which columns a
+// row reads, with which coefficients -- is a table here: it travels in the kernel arguments, is staged ONCE per workgroup into LDS
+// (2 KiB), and every lane fetches the terms of its own row (i mod n_cons) from there.  The loop over term slots is uniform (up to the
+// longest list of each matrix, a lane without a term in a slot gathers column 0 and drops it): the gathers of a slot, one per matrix,
+// are all in flight before the first is used, and a1, b1, c1 before any of them.  A product is taken only in the lanes whose
+// coefficient is neither 1 nor -1 (the launcher classifies them); an affine coefficient c0 + (j - j0) c1 skips its second product
+// where the gathered value is 1 (the constant's column in a fresh instance).  Nothing private is indexed by a run-time value.
+// (One repetition per thread with the description read by scalar loads would have uniform control, but strides every stream by
+// n_cons * 32 bytes: a wavefront's store would touch 64 separate cache lines per vector.)
+enum { PT_ONE = 0, PT_MINUS_ONE = 1, PT_MUL = 2, PT_AFFINE_UNIT = 3, PT_AFFINE = 4 };      // how a term's coefficient is applied
+struct PeriodicArgs {
+  uint32_t n_cons, n_vars, n_terms, n_consts;
+  uint32_t max_len[3], rows;                        // the longest list per matrix; rows = reps * n_cons
+  uint64_t j_first, j0;
+  uint64_t seg_begin, row0;
+  uint16_t row_start[3 * VDF_PERIODIC_MAX_ROWS + 4];
+  uint32_t terms[2 * VDF_PERIODIC_MAX_TERMS];       // col, then kind | how << 8 | c0 << 16 | c1 << 24
+  TapeFe consts[VDF_PERIODIC_MAX_CONSTS];
+};
+static_assert(VDF_PERIODIC_MAX_STARTS == 3 * VDF_PERIODIC_MAX_ROWS + 1, "row_start: one entry per row and matrix, and the end");
+static_assert(sizeof(PeriodicArgs) + 8 * 8 + sizeof(TapeFe) <= 4096, "the description travels in the kernel-argument segment");
+
+template <class P> __device__ __forceinline__ Fe<P> lds_fe(const uint4* t, uint32_t k) {
+  const uint4 lo = t[2 * k], hi = t[2 * k + 1];
+  Fe<P> r;
+  r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
+  r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
+  return r;
+}
+
+template <class P>
+__global__ __launch_bounds__(256) void k_nifs_cross_periodic(PeriodicArgs pa, const char* __restrict__ z2, const char* __restrict__ az1,
+                                                             const char* __restrict__ bz1, const char* __restrict__ cz1, TapeFe u1,
+                                                             char* __restrict__ az2, char* __restrict__ bz2, char* __restrict__ cz2,
+                                                             char* __restrict__ T) {
+  __shared__ uint32_t s_terms[2 * VDF_PERIODIC_MAX_TERMS];
+  __shared__ uint32_t s_start[3 * VDF_PERIODIC_MAX_ROWS + 1];
+  __shared__ uint4 s_consts[2 * VDF_PERIODIC_MAX_CONSTS];
+  __builtin_amdgcn_s_setprio(3);     // light kernel: do not starve behind a co-running k_accumulate
+  for (uint32_t w = threadIdx.x; w < 2 * pa.n_terms; w += 256) s_terms[w] = pa.terms[w];
+  for (uint32_t w = threadIdx.x; w <= 3 * pa.n_cons; w += 256) s_start[w] = pa.row_start[w];
+  for (uint32_t w = threadIdx.x; w < 8 * pa.n_consts; w += 256) reinterpret_cast<uint32_t*>(s_consts)[w] = pa.consts[w >> 3].v[w & 7];
+  __syncthreads();
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= pa.rows) return;
+  const uint32_t rep = i / pa.n_cons, c = i - rep * pa.n_cons;
+  const uint64_t j = pa.j_first + rep;
+  const size_t r = pa.row0 + i;
+  const Fe<P> a1 = fe_load<P>(az1 + r * 32), b1 = fe_load<P>(bz1 + r * 32), c1 = fe_load<P>(cz1 + r * 32);
+  const size_t seg = pa.seg_begin + j * pa.n_vars;                   // column of this repetition's first variable
+  const uint32_t st0 = s_start[3 * c], st1 = s_start[3 * c + 1], st2 = s_start[3 * c + 2], st3 = s_start[3 * c + 3];
+  const uint32_t lo[3] = {st0, st1, st2}, hi[3] = {st1, st2, st3};
+  Fe<P> acc[3] = {fe_zero<P>(), fe_zero<P>(), fe_zero<P>()};
+  const uint32_t longest = max(pa.max_len[0], max(pa.max_len[1], pa.max_len[2]));
+#pragma unroll 1
+  for (uint32_t s = 0; s < longest; ++s) {
+    bool has[3];
+    uint32_t how[3];
+    Fe<P> v[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      has[k] = false; how[k] = 0;
+      if (s >= pa.max_len[k]) continue;                              // (uniform)
+      has[k] = lo[k] + s < hi[k];
+      const uint32_t e = has[k] ? lo[k] + s : 0u;
+      const uint32_t col = s_terms[2 * e];
+      how[k] = s_terms[2 * e + 1];
+      const size_t at = (how[k] & 0xFF) == VDF_TERM_SEG ? seg + (size_t)(int64_t)(int32_t)col : (size_t)col;
+      v[k] = fe_load<P>(z2 + (has[k] ? at : (size_t)0) * 32);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (!has[k]) continue;
+      const uint32_t mode = (how[k] >> 8) & 0xFF, k0 = (how[k] >> 16) & 0xFF, k1 = how[k] >> 24;
+      if (mode == PT_ONE) acc[k] = fe_add(acc[k], v[k]);
+      else if (mode == PT_MINUS_ONE) acc[k] = fe_sub(acc[k], v[k]);
+      else {
+        Fe<P> coef = lds_fe<P>(s_consts, k0);
+        if (mode != PT_MUL) {
+          const uint64_t d = j - pa.j0;
+          Fe<P> m = d < (1u << 30) ? fe_from_small<P>((uint32_t)d) : fe_from_u64<P>(d);
+          if (mode == PT_AFFINE) m = fe_mul(m, lds_fe<P>(s_consts, k1));
+          coef = fe_add(coef, m);
+        }
+        acc[k] = fe_add(acc[k], mode != PT_MUL && fe_eq(v[k], fe_one<P>()) ? coef : fe_mul(coef, v[k]));
+      }
+    }
+  }
+  fe_store<P>(az2 + r * 32, acc[0]);
+  fe_store<P>(bz2 + r * 32, acc[1]);
+  fe_store<P>(cz2 + r * 32, acc[2]);
+  Fe<P> tt = fe_add(fe_mul(a1, acc[1]), fe_mul(acc[0], b1));
+  tt = fe_sub(tt, fe_mul(tape_fe<P>(u1), acc[2]));
+  tt = fe_sub(tt, c1);
+  fe_store<P>(T + r * 32, tt);
+}
+
 static TapeFe tape_val(const vdf_fe* p) { TapeFe v; std::memcpy(&v, p, 32); return v; }
 // what k_tape_forward_walk spends on a POW of exponent e: bitlen - 1 squarings and popcount - 1 products, at least one
 static uint64_t pow_products(const TapeFe& e) {
@@ -380,6 +479,72 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tp, const vd
   return with_field(field, [&](auto f) {
     hipLaunchKernelGGL((k_tape_forward_walk<tag_t<decltype(f)>>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, fa, bytes_of(entries),
                        bytes_of(checkpoints), bytes_of(trace));
+  });
+}
+
+// Everything the description could index out of range is checked here, before a launch (vdf_hip.h vdf_nifs_cross_term_periodic)
+Status vec_nifs_cross_periodic(int field, const vdf_periodic_rows* pr, uint64_t j_first, uint64_t reps, size_t seg_begin, size_t row0,
+                               size_t num_cols, size_t num_cons, const void* z2, const void* az1, const void* bz1, const void* cz1,
+                               const vdf_fe* u1, void* az2, void* bz2, void* cz2, void* T, hipStream_t s) {
+  VDF_TRY(check_field(field));
+  if (!pr || !pr->row_start || (pr->n_terms && !pr->terms) || (pr->n_consts && !pr->consts)) return Status{VDF_ERR_BAD_ARG, "null description"};
+  if (pr->n_cons == 0 || pr->n_cons > VDF_PERIODIC_MAX_ROWS || pr->n_vars == 0 || pr->n_terms > VDF_PERIODIC_MAX_TERMS ||
+      pr->n_consts > VDF_PERIODIC_MAX_CONSTS)
+    return Status{VDF_ERR_BAD_ARG, "periodic rows exceed a published cap (VDF_PERIODIC_MAX_*), or have no row or variable"};
+  PeriodicArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.n_cons = pr->n_cons; a.n_vars = pr->n_vars; a.n_terms = (uint32_t)pr->n_terms; a.n_consts = (uint32_t)pr->n_consts;
+  a.j_first = j_first; a.j0 = pr->j0; a.seg_begin = seg_begin; a.row0 = row0;
+  if (pr->row_start[0] != 0 || pr->row_start[3 * pr->n_cons] != pr->n_terms) return Status{VDF_ERR_BAD_ARG, "row_start does not span the terms"};
+  for (uint32_t q = 0; q < 3 * pr->n_cons; ++q) {
+    const uint32_t b = pr->row_start[q], e = pr->row_start[q + 1];
+    if (e < b || e - b > VDF_PERIODIC_MAX_ROW_TERMS) return Status{VDF_ERR_BAD_ARG, "row_start descends, or a row has more than VDF_PERIODIC_MAX_ROW_TERMS terms in one matrix"};
+    if (e - b > a.max_len[q % 3]) a.max_len[q % 3] = e - b;
+    a.row_start[q + 1] = (uint16_t)e;
+  }
+  if (j_first < pr->j0) return Status{VDF_ERR_BAD_ARG, "j_first lies before the repetition the pattern was taken from"};
+  if (reps == 0) return Status{};
+  if (reps > ((uint64_t)1 << 31) / pr->n_cons || j_first > UINT32_MAX || j_first + reps > UINT32_MAX) return Status{VDF_ERR_BAD_ARG, "more than 2^31 rows, or repetitions beyond 2^32"};
+  const uint64_t rows = reps * pr->n_cons, j_last = j_first + reps - 1;
+  if (row0 > num_cons || rows > num_cons - row0) return Status{VDF_ERR_BAD_ARG, "the row range ends beyond num_cons"};
+  if (num_cols == 0 || num_cols > ((size_t)1 << 32) || seg_begin > num_cols) return Status{VDF_ERR_BAD_ARG, "num_cols out of range, or seg_begin beyond it"};
+  // (j < 2^32, n_vars < 2^32, seg_begin <= 2^32: the products stay inside 64 bits, and below 2^34 where a SEG term is admitted)
+  const bool seg_far = j_last * pr->n_vars > ((uint64_t)1 << 33);      // (then no offset of 32 bits brings a SEG term back inside)
+  const int64_t first_seg = (int64_t)(seg_begin + j_first * pr->n_vars), last_seg = (int64_t)(seg_begin + j_last * pr->n_vars);
+  Status st = with_field(field, [&](auto f) -> Status {
+    using P = tag_t<decltype(f)>;
+    auto fe_of = [&](uint32_t k) { Fe<P> v; std::memcpy(v.v, &pr->consts[k], 32); return v; };
+    const Fe<P> p1 = fe_one<P>(), m1 = fe_neg(p1);
+    for (size_t e = 0; e < pr->n_terms; ++e) {
+      const vdf_periodic_term& t = pr->terms[e];
+      const std::string at = "term " + std::to_string(e);
+      if (t.kind != VDF_TERM_SEG && t.kind != VDF_TERM_ABS) return Status{VDF_ERR_BAD_ARG, at + ": unknown kind"};
+      if (t.c0 >= pr->n_consts || (t.c1 != VDF_TERM_NO_SLOPE && (t.c1 >= pr->n_consts || t.kind != VDF_TERM_ABS)))
+        return Status{VDF_ERR_BAD_ARG, at + ": constant index out of range, or a slope on a SEG term"};
+      if (t.kind == VDF_TERM_ABS) {
+        if (t.col >= num_cols) return Status{VDF_ERR_BAD_ARG, at + ": column beyond num_cols"};
+      } else {
+        const int64_t rel = (int32_t)t.col;
+        if (seg_far || first_seg + rel < 0 || last_seg + rel >= (int64_t)num_cols)
+          return Status{VDF_ERR_BAD_ARG, at + ": reaches a column outside [0, num_cols) in the first or the last repetition"};
+      }
+      uint32_t how = PT_MUL;
+      if (t.c1 != VDF_TERM_NO_SLOPE) how = fe_eq(fe_of(t.c1), p1) ? PT_AFFINE_UNIT : PT_AFFINE;
+      else if (fe_eq(fe_of(t.c0), p1)) how = PT_ONE;
+      else if (fe_eq(fe_of(t.c0), m1)) how = PT_MINUS_ONE;
+      a.terms[2 * e] = t.col;
+      a.terms[2 * e + 1] = (uint32_t)t.kind | how << 8 | (uint32_t)t.c0 << 16 | (uint32_t)t.c1 << 24;
+    }
+    return Status{};
+  });
+  VDF_TRY(st);
+  for (size_t k = 0; k < pr->n_consts; ++k) a.consts[k] = tape_val(&pr->consts[k]);
+  a.rows = (uint32_t)rows;
+  // the seven vectors of the cross term per row, and the gathered elements once (they are the repetitions' own variables)
+  KTimer kt(s, "k_nifs_cross_periodic", (double)rows * 7 * 32 + (double)reps * pr->n_vars * 32);
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_nifs_cross_periodic<tag_t<decltype(f)>>), grid_for(rows), dim3(256), 0, s, a, cbytes_of(z2), cbytes_of(az1),
+                       cbytes_of(bz1), cbytes_of(cz1), tape_val(u1), bytes_of(az2), bytes_of(bz2), bytes_of(cz2), bytes_of(T));
   });
 }
 

@@ -75,6 +75,42 @@ class RoundTape:
         return [(o.op, o.dst, o.a, o.b) for o in self.ops[:self.c.n_ops]]
 
 
+TERM_SEG, TERM_ABS, TERM_NO_SLOPE = 0, 1, 0xFF      # VDF_TERM_*
+PERIODIC_MAX_ROW_TERMS, PERIODIC_MAX_ROWS, PERIODIC_MAX_TERMS, PERIODIC_MAX_CONSTS = 8, 32, 128, 24      # VDF_PERIODIC_MAX_*
+
+
+class PeriodicTerm(C.Structure):
+    """vdf_periodic_term: one term of a periodic row (include/vdf_hip.h VDF_TERM_*); col is a signed offset under TERM_SEG."""
+    _fields_ = [("kind", C.c_uint8), ("c0", C.c_uint8), ("c1", C.c_uint8), ("pad", C.c_uint8), ("col", C.c_uint32)]
+
+
+class PeriodicRowsC(C.Structure):
+    _fields_ = [("n_cons", C.c_uint32), ("n_vars", C.c_uint32), ("j0", C.c_uint64), ("row_start", C.c_void_p),
+                ("terms", C.POINTER(PeriodicTerm)), ("n_terms", C.c_size_t), ("consts", C.c_void_p), ("n_consts", C.c_size_t)]
+
+
+class PeriodicRows:
+    """vdf_periodic_rows with the arrays it points into (vdf_amd.nova.periodic_rows_detect / shape_periodic_custom make one).
+    lead, row_begin, row_count: the repetitions and rows the detection found it for (0 when made by hand)."""
+
+    def __init__(self):
+        self.row_start = np.zeros(3 * PERIODIC_MAX_ROWS + 1, dtype=np.uint16)
+        self.terms = (PeriodicTerm * PERIODIC_MAX_TERMS)()
+        self.consts = np.zeros((PERIODIC_MAX_CONSTS, 4), dtype="<u8")
+        self.c = PeriodicRowsC()
+        self.c.row_start = self.row_start.ctypes.data
+        self.c.terms = C.cast(self.terms, C.POINTER(PeriodicTerm))
+        self.c.consts = self.consts.ctypes.data
+        self.lead = self.row_begin = self.row_count = 0
+
+    def term_list(self):
+        """[[(kind, signed col, c0, c1) per term] per matrix A, B, C] per row"""
+        rel = lambda t: t.col - (1 << 32) if t.kind == TERM_SEG and t.col >= 1 << 31 else t.col
+        rs = self.row_start
+        return [[[(t.kind, rel(t), t.c0, t.c1) for t in self.terms[rs[3 * c + k]:rs[3 * c + k + 1]]] for k in range(3)]
+                for c in range(self.c.n_cons)]
+
+
 class VdfError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"vdf_hip error {code}: {msg}")
@@ -552,6 +588,14 @@ class Context:
         """The lanes x (3t + 1) rows of the forward circuit in lanes from row_begin on, by stencil, one launch (vdf_hip.h)."""
         self._check(lib.vdf_nifs_cross_term_minroot_forward_lanes(self.handle, field, t, lanes, seg_begin, one_col, row_begin, _ptr(z2), _ptr(az1),
                                                                   _ptr(bz1), _ptr(cz1), _ptr(u1), _ptr(az2), _ptr(bz2), _ptr(cz2), _ptr(T)))
+
+    def nifs_cross_term_periodic(self, field, rows: "PeriodicRows", j_first, reps, seg_begin, row_begin, num_cols, num_cons, z2, az1, bz1,
+                                 cz1, u1, az2, bz2, cz2, T) -> None:
+        """Az2, Bz2, Cz2 and T of the rows row_begin + (j - j_first) * n_cons + c, j = j_first .. j_first + reps - 1, from the
+        periodic description alone (no sparse matrices); every other row is left as it is.  Vectors: device; u1: host."""
+        self._check(lib.vdf_nifs_cross_term_periodic(self.handle, field, C.addressof(rows.c), j_first, reps, seg_begin, row_begin, num_cols,
+                                                     num_cons, _ptr(z2), _ptr(az1), _ptr(bz1), _ptr(cz1), _ptr(u1), _ptr(az2), _ptr(bz2),
+                                                     _ptr(cz2), _ptr(T)))
 
     def nifs_cross_term_minroot_fold(self, field, per, t, seg_begin, one_col, row_begin, z2, r, az1, bz1, cz1, e1, t_prev, u1, az2, bz2, cz2, T) -> None:
         """The same rows with the previous fold of those rows applied on the way (vdf_hip.h); e1 / t_prev may be None."""

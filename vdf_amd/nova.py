@@ -10,7 +10,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .hip import Context, VdfError, RoundTape, _ptr
+from .hip import Context, VdfError, RoundTape, PeriodicRows, _ptr
 from .minroot import State, _State, _Fe, nova_lib, EvalMode, MinRootVDF, PallasVDF, VestaVDF, FIELD_FP, FIELD_FQ  # noqa: F401
 
 _vp, _i, _u64, _sz = C.c_void_p, C.c_int, C.c_uint64, C.c_size_t
@@ -131,6 +131,12 @@ for _name, _res, _args in [
     ("vdf_nova_shape_digest_field", _i, [_i, _vp, _u64, _i, _sz, _i, _vp, _vp]),
     ("vdf_nova_shape_export_field", _i, [_i, _u64, _i, _sz, _i, _vp, _vp, _vp, _vp]),
     ("vdf_nova_shape_stencil_field", _i, [_i, _u64, _i, _sz, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    ("vdf_nova_public_params_custom_tuned", _i, [_vp, _i, _vp, _i, _vp, C.POINTER(_vp)]),
+    ("vdf_nova_pp_periodic_rows", _i, [_vp] + [C.POINTER(_u64)] * 4),
+    ("vdf_nova_shape_export_custom", _i, [_i, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("vdf_nova_periodic_rows_detect", _i, [_i, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _u64, _vp, _vp, _vp, _vp] + [C.POINTER(_u64)] * 3),
+    ("vdf_nova_periodic_rows_eval", _i, [_i, _vp, _u64, _u64, _sz, _sz, _sz, _sz] + [_vp] * 9),
+    ("vdf_nova_shape_periodic_custom", _i, [_i, _vp, _vp, _vp, _vp, _vp] + [C.POINTER(_u64)] * 6),
     ("vdf_nova_aug_synthesize_field", _i, [_i, _vp, _i, _u64, _i, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz), _vp, _vp]),
 ]:
     if not hasattr(nova_lib, _name):          # AttributeError at call time names the missing entry point
@@ -143,6 +149,7 @@ CIRCUIT_MINROOT_FORWARD = 3       # the step in the direction of evaluation (inc
 STENCIL_FORWARD = 5               # vdf_nova_pp_stencil's code for the forward circuit's stencil
 CIRCUIT_MINROOT_FORWARD_LANES = 4 # L forward circuits side by side in one step circuit (public_params_lanes)
 STENCIL_FORWARD_LANES = 6         # ... and the code of its stencil
+STENCIL_PERIODIC = 7              # a custom circuit's periodic vdf_cs_repeat rows run from their description (tuning periodic_rows)
 MAX_LANES = 16
 SIDE_PRIMARY, SIDE_SECONDARY = 0, 1
 INST_RUNNING_PRIMARY, INST_RUNNING_SECONDARY, INST_FRESH_SECONDARY, INST_FRESH_PRIMARY_LAST = 0, 1, 2, 3
@@ -155,7 +162,8 @@ class NovaTuning(C.Structure):
     """vdf_nova_tuning (include/vdf_nova.h): everything tunable about a parameter set and the prover over it."""
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("digit_budget_bytes", C.c_uint64)] + [(k, C.c_int32) for k in (
         "digit_window", "early_rows", "stencil", "small_window", "big_window", "packed_commit", "lookahead_early", "gate_accumulate",
-        "fold_on_rows", "nifs_ahead", "early_row_parts", "lookahead_priority", "side_accumulate_fill", "verbose", "compress_queues", "rows_at_challenge", "fold_fused")]
+        "fold_on_rows", "nifs_ahead", "early_row_parts", "lookahead_priority", "side_accumulate_fill", "verbose", "compress_queues", "rows_at_challenge", "fold_fused",
+        "periodic_rows")]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -596,11 +604,82 @@ def _reraise(circuit) -> None:
         raise e
 
 
+def shape_export_custom(circuit: StepCircuit, field: int = FIELD_FQ, side: int = 0):
+    """shape_export for a custom primary circuit synthesised over `field` (host only)."""
+    nnz = np.zeros(3, dtype="<u8")
+    cc = circuit._c()
+    rc = nova_lib.vdf_nova_shape_export_custom(field, C.byref(cc), side, nnz.ctypes.data, None, None, None)
+    _reraise(circuit)
+    _check(rc)
+    mats = [(np.zeros(int(z), dtype=np.uint32), np.zeros(int(z), dtype=np.uint32), np.zeros((int(z), 4), dtype="<u8")) for z in nnz]
+    arr = lambda k: (C.c_void_p * 3)(*[m[k].ctypes.data for m in mats])
+    rc = nova_lib.vdf_nova_shape_export_custom(field, C.byref(cc), side, nnz.ctypes.data, arr(0), arr(1), arr(2))
+    _reraise(circuit)
+    _check(rc)
+    return mats
+
+
+def periodic_rows_detect(field: int, mats, seg_begin: int, n_vars: int, row_begin: int, n_cons: int, t: int) -> "PeriodicRows | None":
+    """Host only.  Are the rows row_begin + j * n_cons + c of the COO triples `mats` (as shape_export gives them) periodic from
+    some lead in 0 .. 4 on?  The description (its lead, row_begin, row_count set), or None.  Every triple of every periodic
+    repetition is compared with the pattern."""
+    mats = [(np.ascontiguousarray(r, dtype=np.uint32), np.ascontiguousarray(c, dtype=np.uint32), np.ascontiguousarray(v, dtype="<u8"))
+            for r, c, v in mats]
+    nnz = np.array([m[0].shape[0] for m in mats], dtype="<u8")
+    arr = lambda k: (C.c_void_p * 3)(*[m[k].ctypes.data for m in mats])
+    pr = PeriodicRows()
+    lead, first, count = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rc = nova_lib.vdf_nova_periodic_rows_detect(field, nnz.ctypes.data, arr(0), arr(1), arr(2), seg_begin, n_vars, row_begin, n_cons, t,
+                                                pr.row_start.ctypes.data, C.addressof(pr.terms), pr.consts.ctypes.data, C.addressof(pr.c),
+                                                C.byref(lead), C.byref(first), C.byref(count))
+    if rc < 0:
+        _check(-rc)
+    if rc == 0:
+        return None
+    pr.lead, pr.row_begin, pr.row_count = lead.value, first.value, count.value
+    return pr
+
+
+def shape_periodic_custom(circuit: StepCircuit, field: int = FIELD_FQ):
+    """Host only: the detection public_params_custom makes.  (description or None, info) with info = dict(seg_begin, num_cons,
+    num_cols) of the primary shape."""
+    pr = PeriodicRows()
+    v = [C.c_uint64() for _ in range(6)]
+    rc = nova_lib.vdf_nova_shape_periodic_custom(field, C.byref(circuit._c()), pr.row_start.ctypes.data, C.addressof(pr.terms),
+                                                 pr.consts.ctypes.data, C.addressof(pr.c), *[C.byref(x) for x in v])
+    _reraise(circuit)
+    if rc < 0:
+        _check(-rc)
+    info = dict(seg_begin=v[0].value, num_cons=v[4].value, num_cols=v[5].value)
+    if rc == 0:
+        return None, info
+    pr.lead, pr.row_begin, pr.row_count = v[1].value, v[2].value, v[3].value
+    return pr, info
+
+
+def periodic_rows_eval(field: int, rows: "PeriodicRows", j_first: int, reps: int, seg_begin: int, row_begin: int, num_cols: int,
+                       num_cons: int, z2, az1, bz1, cz1, u1, az2, bz2, cz2, T) -> None:
+    """Host only: Context.nifs_cross_term_periodic restated over numpy arrays (uint64[n, 4], written in place), byte for byte."""
+    for a in (z2, az1, bz1, cz1, u1, az2, bz2, cz2, T):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.dtype("<u8") and a.flags["C_CONTIGUOUS"]):
+            raise TypeError("periodic_rows_eval takes C-contiguous uint64 arrays")
+    _check(nova_lib.vdf_nova_periodic_rows_eval(field, C.addressof(rows.c), j_first, reps, seg_begin, row_begin, num_cols, num_cons,
+                                                *[a.ctypes.data for a in (z2, az1, bz1, cz1, u1, az2, bz2, cz2, T)]))
+
+
 def public_params_custom(ctx: Context, circuit: StepCircuit, gens_family: int = GENS_TRY_AND_INCREMENT,
-                         field: int = FIELD_FQ) -> "NovaVDFPublicParams":
-    """`field`: the orientation -- the field the circuit is synthesised over (FIELD_FP: G1 = Vesta)."""
+                         field: int = FIELD_FQ, tuning: "NovaTuning | None" = None, **tune) -> "NovaVDFPublicParams":
+    """`field`: the orientation -- the field the circuit is synthesised over (FIELD_FP: G1 = Vesta).  `tuning` / keyword fields of
+    vdf_nova_tuning (e.g. periodic_rows=1): vdf_nova_public_params_custom_tuned."""
     h = C.c_void_p()
-    if field == FIELD_FQ:
+    if tuning is not None or tune:
+        t = tuning if tuning is not None else tuning_default()
+        for k, v in tune.items():
+            if k not in dict(NovaTuning._fields_):
+                raise KeyError(k)
+            setattr(t, k, int(v))
+        rc = nova_lib.vdf_nova_public_params_custom_tuned(ctx.handle, field, C.byref(circuit._c()), gens_family, C.byref(t), C.byref(h))
+    elif field == FIELD_FQ:
         rc = nova_lib.vdf_nova_public_params_custom(ctx.handle, C.byref(circuit._c()), gens_family, C.byref(h))
     else:
         rc = nova_lib.vdf_nova_public_params_custom_field(ctx.handle, field, C.byref(circuit._c()), gens_family, C.byref(h))
@@ -675,8 +754,16 @@ class NovaVDFPublicParams:        # src/nova/proof.rs:38-43
 
     def stencil(self) -> int:
         """4 / 3: the early rows run as the MinRoot stencil (reference / bound rounds), 5: as the forward circuit's stencil,
-        6: as the forward circuit's in lanes, 0: through the sparse kernel."""
+        6: as the forward circuit's in lanes, 7: a custom circuit's periodic rows from their description, 0: through the sparse kernel."""
         return int(nova_lib.vdf_nova_pp_stencil(self.handle))
+
+    def periodic_rows(self) -> "dict | None":
+        """A custom circuit's periodic vdf_cs_repeat rows as the parameters found them (whatever the tuning says about using them):
+        dict(row_begin, row_count, lead, terms_per_rep), or None."""
+        v = [C.c_uint64() for _ in range(4)]
+        if not nova_lib.vdf_nova_pp_periodic_rows(self.handle, *[C.byref(x) for x in v]):
+            return None
+        return dict(zip(("row_begin", "row_count", "lead", "terms_per_rep"), [x.value for x in v]))
 
     def field(self) -> int:
         """The orientation: the primary circuit's field, the VDF's -- FIELD_FQ (PallasVDF, G1 = Pallas) or FIELD_FP (VestaVDF, G1 = Vesta)."""
