@@ -263,6 +263,13 @@ int  vdf_cross_term(vdf_ctx* ctx, int field, const vdf_fe* Az1, const vdf_fe* Bz
 /* is_zero = 1 iff all n elements are zero, decided on the device (a verifier's residual A z o B z - u C z - E is checked
  * where it lies instead of being copied out); synchronises. */
 int  vdf_vec_is_zero(vdf_ctx* ctx, const vdf_fe* v, size_t n, int* is_zero);
+/* Which rows of an instance are unsatisfied: out[0] = the number of rows r < n with Az[r] * Bz[r] != Cz[r] (canonical Montgomery
+ * elements of `field`, the product as every kernel makes it), out[1] = the smallest such r, UINT64_MAX when there is none.  One
+ * pass over the three vectors (96 bytes per row), which must be device memory (VDF_ERR_BAD_ARG otherwise); out: host memory or
+ * vdf_host_alloc memory, written when the call returns (an asynchronous context and vdf_host_alloc memory: after vdf_ctx_sync).
+ * n = 0 writes {0, UINT64_MAX} and launches nothing.  A diagnostic for a strict instance (u = 1, E = 0): the fresh instance of a
+ * step whose advice or round body is wrong (vdf_nova.h vdf_nova_proof_last_unsat). */
+int  vdf_unsat_rows(vdf_ctx* ctx, int field, const vdf_fe* Az, const vdf_fe* Bz, const vdf_fe* Cz, size_t n, uint64_t out[2]);
 /* out = a + r*b   (nova-snark RelaxedR1CSWitness::fold: W1 + r*W2, E1 + r*T; K6).
  * `r` is one field element (host or device).  out may alias a. */
 int  vdf_axpy(vdf_ctx* ctx, int field, const vdf_fe* a, const vdf_fe* r, const vdf_fe* b, size_t n, vdf_fe* out);
@@ -776,6 +783,10 @@ int  vdf_dev_alloc(vdf_ctx* ctx, size_t bytes, void** out);
 int  vdf_dev_free(vdf_ctx* ctx, void* p);
 int  vdf_dev_mem_info(vdf_ctx* ctx, size_t* free_bytes, size_t* total_bytes);   /* HBM of the context's device; either may be NULL */
 int  vdf_dev_memcpy(vdf_ctx* ctx, void* dst, const void* src, size_t bytes);   /* any direction */
+/* A blocking copy to host memory without a context, for a holder of a device pointer that has none (the runtime finds the
+ * pointer's device).  src must be complete: what a context's queue is still writing needs that context's vdf_ctx_sync first.
+ * An error's text is vdf_last_error(NULL). */
+int  vdf_ptr_download(void* dst, const void* src, size_t bytes);
 /* Pinned host memory mapped into the device's address space.  Calls treat such a pointer like device memory
  * (used in place, no staging, no implicit synchronisation): a kernel's small result -- an MSM's point -- lands
  * in host memory by itself and is readable after vdf_ctx_sync, with no device-to-host copy. */

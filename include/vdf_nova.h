@@ -545,6 +545,85 @@ int  vdf_nova_public_params_custom_field(vdf_ctx* ctx, int field, const vdf_step
 int  vdf_nova_public_params_custom_tuned(vdf_ctx* ctx, int field, const vdf_step_circuit* primary, int gens_family,
                                          const vdf_nova_tuning* tuning, vdf_pp** out);
 
+/* ---- a custom circuit's chain: proved from its checkpoints, the walks a window ahead of the prover ---------------------------
+ * What vdf_circuits is to the built-in kinds, for a circuit whose rounds are a vdf_cs_repeat and whose advice a walk tape rebuilds:
+ * the chain's checkpoints on the host, and per step a device trace of t + 1 advice entries that exists only while the step's
+ * window is proved.  The walks run on a side queue of the prover's device, all walks of a window in one vdf_round_tape_walk per
+ * slice of rounds, and are finished by the call that needs their result.
+ *
+ * vdf_nova_custom_chain_from_checkpoints: `checkpoints` = num_steps * (t / every) + 1 entries of walk_tape->n_adv elements,
+ * entry-major, Montgomery form, forward order, entry 0 the chain's start; host or device memory (vdf_ptr_is_device; a device array
+ * -- one chain's slice of vdf_round_tape_eval_batch's output -- is downloaded once).  The chain keeps host copies of the tape,
+ * of `inv` (walk_tape->n_inv elements, host memory) and of the checkpoints, and no trace.  j_base: the VDF_TAPE_J that the walk
+ * producing entry 1 sees, minus 0 (the rule of vdf_round_tape_walk); step g's group of walks gets j_base + g * t.  Refused with
+ * VDF_ERR_BAD_ARG on the host, nothing allocated on a device, vdf_nova_last_error naming the check: a walk tape that
+ * vdf_round_tape_walk would refuse (a malformed op, n_vars != n_adv, an ADV with b = 0, a POW, the slot cap), `every` = 0 or not
+ * dividing t, t = 0 or t >= 2^31, num_steps = 0, a null pointer, an unknown field.
+ *
+ * vdf_nova_custom_chain_materialize has the semantics of vdf_nova_circuits_materialize.  The traces of the steps of [first, first
+ * + count) that are not resident are ONE device allocation (of the whole range when none is: count * (t + 1) * n_adv elements,
+ * step g's trace at (g - first) * (t + 1) * n_adv, entries 0 .. t -- what vdf_cs_repeat reads as advice).  One walk per checkpoint
+ * interval of every step; a slice with `done` rounds behind it is vdf_round_tape_walk(rounds = now, top = every - done,
+ * walk_stride = every, group = t / every, group_stride = t + 1, j_base = the chain's + first * t, j_group_step = t), now = min(every
+ * - done, launch_rounds) (vdf_nova_custom_chain_slice; launch_rounds = 0: 1,024); heads = 1, expect and ok only in the slice that
+ * finishes the walks.  wait = 0 enqueues the first slice and returns; later calls pump and resolve.  A step with a walk that missed
+ * its checkpoint is left without a trace, bad[k - first] = 1 (bad: count ints or NULL), and the call that resolves returns
+ * VDF_ERR_BAD_ARG "step k: a walk did not land on the checkpoint below it" for the first such step.
+ * _release / _memory / _host_bytes / _len / _free: as their vdf_nova_circuits_* counterparts.  _advice: the device trace of step k,
+ * NULL when none is resident; pending walks over the step are finished first (for tests and tools).
+ *
+ * vdf_cs_step_advice: inside a synthesize driven by vdf_nova_prove_step_custom_chain or vdf_nova_prove_recursively_custom, in
+ * witness mode, the device trace of the step being proved; NULL in every other case (a shape being recorded, a round or walk
+ * body, plain vdf_nova_prove_step_custom).  A circuit writes vdf_cs_repeat(cs, &body, t, inv, carry_in, vdf_cs_is_witness(cs) ?
+ * vdf_cs_step_advice(cs) : NULL, out) and needs no per-step state of its own; its shape and digest do not depend on the call.
+ *
+ * vdf_nova_prove_step_custom_chain: vdf_nova_prove_step_custom for step k of the chain, k = the steps the proof has (0 for *proof
+ * = NULL).  Pending walks are finished if they cover k; VDF_ERR_BAD_ARG "advice of step k not materialised" when the trace is
+ * absent (nothing else is done); the other pending walks get their share of rounds; then the step runs.  Also VDF_ERR_BAD_ARG: a
+ * chain over the other field than the parameters' orientation, k beyond the chain or out of order, a chain whose t or n_adv is
+ * not the parameters' vdf_cs_repeat's.
+ * vdf_nova_prove_recursively_custom: the loop of vdf_nova_prove_recursively_windowed -- window 0 materialised and waited for,
+ * window 1 enqueued, then step by step; after the last step of window w, window w is released and window w + 2 begun: never more
+ * than two windows of traces in HBM (and one spare allocation).  window_steps = 0: as many steps as fit 1 GiB, at least 2; 1 is
+ * raised to 2.  On an error nothing stays in flight, what the call built is released and *proof = NULL; the chain is left as it
+ * was found.  The proof is byte for byte the one vdf_nova_prove_step_custom makes step by step from the same advice.
+ * flags & VDF_CUSTOM_CHECK_STEPS: after every step vdf_nova_proof_last_unsat runs, and a non-zero count ends the call with
+ * VDF_ERR_BAD_ARG "step k: N unsatisfied rows, first row r (repetition j, constraint c of the repeat)" (the parenthesis for a
+ * row of the repeat).  Without the flag wrong advice is not an error, as in vdf_cs_repeat above.
+ * Out of scope for custom chains: lookahead, early rows of T, a second vdf_cs_repeat, a streaming eval_and_prove, chains in lanes. */
+typedef struct vdf_custom_chain vdf_custom_chain;
+#define VDF_CUSTOM_CHECK_STEPS 1u
+int  vdf_nova_custom_chain_from_checkpoints(int field, const vdf_round_tape* walk_tape, const vdf_fe* inv, uint64_t t, uint64_t every,
+                                            size_t num_steps, const vdf_fe* checkpoints, uint64_t j_base, vdf_custom_chain** out);
+int  vdf_nova_custom_chain_materialize(vdf_ctx* ctx, vdf_custom_chain* chain, size_t first, size_t count, int wait, uint64_t launch_rounds,
+                                       int* bad);
+int  vdf_nova_custom_chain_release(vdf_custom_chain* chain, size_t first, size_t count);
+int  vdf_nova_custom_chain_memory(const vdf_custom_chain* chain, size_t* resident_steps, uint64_t* device_bytes);
+int  vdf_nova_custom_chain_host_bytes(const vdf_custom_chain* chain, uint64_t* bytes);
+size_t vdf_nova_custom_chain_len(const vdf_custom_chain* chain);
+int  vdf_nova_custom_chain_advice(vdf_custom_chain* chain, size_t k, const vdf_fe** d_advice);
+void vdf_nova_custom_chain_free(vdf_custom_chain* chain);
+/* Host only, pure: the slice of the walks that follows `done` rounds of `every`: *rounds = min(every - done, launch_rounds, budget)
+ * (launch_rounds = 0: 1,024; budget = 0: no limit), *top = every - done, *last = 1 when the slice finishes the walks.  What
+ * materialize and the pumps cut their launches by.  VDF_ERR_BAD_ARG: every = 0, done >= every, a null pointer. */
+int  vdf_nova_custom_chain_slice(uint64_t every, uint64_t launch_rounds, uint64_t done, uint64_t budget, uint64_t* rounds, uint64_t* top,
+                                 int* last);
+const vdf_fe* vdf_cs_step_advice(const vdf_cs* cs);
+int  vdf_nova_prove_step_custom_chain(vdf_pp* pp, vdf_proof** proof, const vdf_step_circuit* primary, vdf_custom_chain* chain, size_t k,
+                                      const vdf_fe* z0);
+int  vdf_nova_prove_recursively_custom(vdf_pp* pp, const vdf_step_circuit* primary, vdf_custom_chain* chain, const vdf_fe* z0,
+                                       size_t window_steps, uint32_t flags, vdf_proof** proof);
+/* Which constraint of the LAST step is unsatisfied: *count = the rows r of the fresh primary instance with (A z)[r] (B z)[r] !=
+ * (C z)[r], *first_row = the smallest (UINT64_MAX: none); vdf_hip.h vdf_unsat_rows.  For proofs of every circuit kind.  The step's
+ * own A z, B z, C z do not outlive it on every path (the base step folds nothing and never makes them apart from the running
+ * instance's; a built-in kind's next early rows overwrite theirs on the way out of the step; a verifier uses the vectors as
+ * scratch), so they are made again from the fresh z, which stays in its ring slot until the next step: one sparse product into
+ * three vectors the first request allocates.  VDF_ERR_BAD_ARG before this object's first prove_step (a deserialised proof too). */
+int  vdf_nova_proof_last_unsat(const vdf_proof* proof, uint64_t* count, uint64_t* first_row);
+/* The rows of a custom circuit's vdf_cs_repeat: repetition j, constraint c is row *row_begin + j * *n_cons + c, j < *t.  Returns 1,
+ * or 0 for parameters without a repeat (outputs 0); does not depend on the rows being periodic. */
+int  vdf_nova_pp_repeat_rows(const vdf_pp* pp, uint64_t* row_begin, uint64_t* n_cons, uint64_t* t);
+
 /* ---- host-only entry points (no device): what the CPU tests pin against oracle/nova.py ------------------------- */
 /* the random oracle: lane 1 of the sponge after absorbing xs under `tag` (a full field element, Montgomery in and out) */
 int  vdf_nova_ro_hash(int field, uint64_t tag, const vdf_fe* xs, size_t n, vdf_fe* out);

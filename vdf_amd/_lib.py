@@ -98,6 +98,7 @@ PROTOTYPES = {
     "vdf_minroot_forward_walk": (_i, [_vp, _i, _vp, _sz, _u64, _vp, _u64, _sz, _vp, _sz, _u64]),
     "vdf_minroot_eval_batch": (_i, [_vp, _i, _vp, _sz, _u64, _u64, _u64, _vp]),
     "vdf_vec_is_zero": (_i, [_vp, _vp, _sz, C.POINTER(C.c_int)]),
+    "vdf_unsat_rows": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "vdf_nifs_cross_term": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdf_nifs_cross_term_rows": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdf_nifs_cross_term_minroot": (_i, [_vp, _i, _i, _u64, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -131,6 +132,7 @@ PROTOTYPES = {
     "vdf_dev_free": (_i, [_vp, _vp]),
     "vdf_dev_mem_info": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz)]),
     "vdf_dev_memcpy": (_i, [_vp, _vp, _vp, _sz]),
+    "vdf_ptr_download": (_i, [_vp, _vp, _sz]),
     "vdf_dev_memset": (_i, [_vp, _vp, _i, _sz]),
     "vdf_host_alloc": (_i, [_vp, _sz, C.POINTER(_vp)]),
     "vdf_host_free": (_i, [_vp, _vp]),

@@ -1393,6 +1393,22 @@ int vdf_vec_is_zero(vdf_ctx* ctx, const vdf_fe* v, size_t n, int* is_zero) {
   });
 }
 
+int vdf_unsat_rows(vdf_ctx* ctx, int field, const vdf_fe* Az, const vdf_fe* Bz, const vdf_fe* Cz, size_t n, uint64_t out[2]) {
+  return guarded(ctx, [&]() -> Status {
+    if (!out) return Status{VDF_ERR_BAD_ARG, "null out"};
+    VDF_TRY(vdf::check_field(field));
+    if (n == 0) { out[0] = 0; out[1] = ~(uint64_t)0; return Status{}; }
+    if (!ptr_is_device(Az) || !ptr_is_device(Bz) || !ptr_is_device(Cz)) return Status{VDF_ERR_BAD_ARG, "Az, Bz and Cz must be device memory"};
+    Staging st(ctx);
+    void* d_out;
+    VDF_TRY(st.out(out, 16, &d_out));
+    if (!ctx->reduce_scratch) VDF_TRY_HIP(hipMalloc(&ctx->reduce_scratch, vdf::snark_reduce_scratch_bytes()));
+    VDF_TRY(vdf::vec_unsat_rows(field, Az, Bz, Cz, n, ctx->reduce_scratch, ctx->stream));
+    VDF_TRY_HIP(hipMemcpyAsync(d_out, ctx->reduce_scratch, 16, hipMemcpyDefault, ctx->stream));
+    return st.finish();
+  });
+}
+
 int vdf_axpy(vdf_ctx* ctx, int field, const vdf_fe* a, const vdf_fe* r, const vdf_fe* b, size_t n, vdf_fe* out) {
   return guarded(ctx, [&]() -> Status {
     Staging st(ctx);
@@ -2334,6 +2350,14 @@ int vdf_dev_memcpy(vdf_ctx* ctx, void* dst, const void* src, size_t bytes) {
     if (!(both_dev && ctx->async)) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
     return Status{};
   });
+}
+
+int vdf_ptr_download(void* dst, const void* src, size_t bytes) {
+  if (bytes == 0) return VDF_OK;
+  if (!dst || !src) return fail(nullptr, Status{VDF_ERR_BAD_ARG, "null pointer"});
+  const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyDefault);
+  if (e != hipSuccess) return fail(nullptr, vdf::hip_status(e, "hipMemcpy"));
+  return VDF_OK;
 }
 
 int vdf_dev_memset(vdf_ctx* ctx, void* dst, int value, size_t bytes) {

@@ -69,12 +69,14 @@ vdf_num cs_put(vdf_cs* c, Num n) { c->pool.push_back(std::move(n)); return (vdf_
 struct CustomStepCircuit : StepCircuit {
   vdf_step_circuit c;
   vdf_ctx* ctx = nullptr;                 // a prover's: lets a vdf_cs_repeat take advice in device memory
+  const vdf_fe* step_advice = nullptr;    // ... driven by a chain: the step's device trace (vdf_cs_step_advice)
   mutable int rc = 0;
   mutable RepeatState rep;                // the vdf_cs_repeat of the last synthesis, if it had one
   size_t arity() const override { return c.arity; }
   std::vector<Num> synthesize(CS& cs, const std::vector<Num>& z) const override {
     vdf_cs h;
     h.cs = &cs; h.pool = z; h.rep = &rep; h.ctx = ctx;
+    h.step_advice = cs.shape ? nullptr : step_advice;
     rep = RepeatState();
     std::vector<vdf_num> zin(c.arity), zout(c.arity, 0);
     for (size_t k = 0; k < c.arity; ++k) zin[k] = (vdf_num)k;
@@ -90,16 +92,18 @@ struct CustomStepCircuit : StepCircuit {
 };
 }  // namespace
 namespace vdfnova {
-std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx) {
+std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx, const vdf_fe* step_advice) {
   std::unique_ptr<CustomStepCircuit> m(new CustomStepCircuit());
   m->c = *c;
   m->ctx = ctx;
+  m->step_advice = step_advice;
   return std::unique_ptr<StepCircuit>(m.release());
 }
 }  // namespace vdfnova
 
 extern "C" {
 int vdf_cs_is_witness(const vdf_cs* c) { return c && !c->cs->shape ? 1 : 0; }
+const vdf_fe* vdf_cs_step_advice(const vdf_cs* c) { return c && !c->rec ? c->step_advice : nullptr; }
 vdf_num vdf_cs_const(vdf_cs* c, const vdf_fe* k) {
   if (c->rec) return rec_cs_const(c, k);
   Fe v; memcpy(&v, k, 32); return cs_put(c, c->cs->constant(v));
@@ -1298,7 +1302,7 @@ int vdf_nova_shape_stencil_field(int fid, uint64_t t, int circuit_kind, size_t l
 
 // ---- prove_step ----------------------------------------------------------------------------------------
 static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* circuits, size_t k, const vdf_step_circuit* custom,
-                           const vdf_fe* z0, vdf_proof** fresh);
+                           const vdf_fe* z0, vdf_proof** fresh, const vdf_fe* step_advice = nullptr);
 
 int vdf_nova_prove_step(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* circuits, size_t k, const vdf_fe z0[3]) {
   if (pp && pp->circuit_kind == VDF_CIRCUIT_CUSTOM) return fail(VDF_ERR_BAD_ARG, "these parameters are for a custom step circuit: vdf_nova_prove_step_custom");
@@ -1369,6 +1373,7 @@ struct StepRun {
   const vdf_circuits* const circuits;
   const size_t k;
   const vdf_step_circuit* const custom;
+  const vdf_fe* step_advice = nullptr;  // a custom circuit driven by a chain: what its vdf_cs_step_advice answers
   const Circuit& c;
   const bool first;
   const size_t arity;
@@ -1579,7 +1584,7 @@ struct StepRun {
       memset(&in1.u_W, 0, sizeof(Aff)); memset(&in1.T, 0, sizeof(Aff));
       for (int j = 0; j < 2; ++j) fe_to_int(p->l2.X[j], F2, in1.u_X[j]);
     }
-    c1 = custom ? make_custom_circuit(custom, ctx) : make_primary_circuit(pp, &c, true);
+    c1 = custom ? make_custom_circuit(custom, ctx, step_advice) : make_primary_circuit(pp, &c, true);
     in2.ro = pp->ro;
   }
   // cross term of (running secondary, l2), commit(w2) unless known, commit(T2)
@@ -1912,6 +1917,7 @@ struct StepRun {
     HIPCALL(ctx, vdf_ctx_sync_mark(ctx, MARK_STEP));
     for (int j = 0; j < D; ++j) if (touched[j]) HIPCALL(p->ctx2[j], vdf_ctx_sync_mark(p->ctx2[j], MARK_Z));
     p->i += 1;
+    p->stepped = true;
     memcpy(&p->last.comm_W1, &l1.comm_W, sizeof(vdf_affine));
     memcpy(p->last.X1, l1.X, 64);
     memcpy(&p->last.comm_T1, &comm_T1, 64);
@@ -1923,7 +1929,7 @@ struct StepRun {
 }  // namespace
 
 static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* circuits, size_t k, const vdf_step_circuit* custom,
-                           const vdf_fe* z0, vdf_proof** fresh) {
+                           const vdf_fe* z0, vdf_proof** fresh, const vdf_fe* step_advice) {
   if (!pp || !proof || (!circuits && !custom) || !z0) return fail(VDF_ERR_BAD_ARG, "null argument");
   static const Circuit no_circuit{};
   if (!custom && k >= circuits->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
@@ -1976,6 +1982,7 @@ static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* ci
   HIPCALL(ctx, vdf_ctx_set_async(ctx, 1));
   struct Restore { vdf_ctx* c; int a; ~Restore() { if (!a) { vdf_ctx_sync(c); vdf_ctx_set_async(c, 0); } } } restore{ctx, was_async};
   StepRun run(pp, p, circuits, k, custom, c, first);
+  run.step_advice = step_advice;
   run.t0 = run.t1 = run.t2 = run.t3 = run.t4 = run.t5 = run.t6 = t0;
   { int rc = run.lookahead_select(); if (rc != VDF_OK) return rc; }
   run.chain_prepare_inputs();
@@ -2040,6 +2047,118 @@ int vdf_nova_prove_recursively_windowed(vdf_pp* pp, const vdf_circuits* circuits
 int vdf_nova_prove_recursively(vdf_pp* pp, const vdf_circuits* circuits, uint64_t num_iters_per_step, const vdf_fe z0[3],
                                vdf_proof** out) {
   return vdf_nova_prove_recursively_windowed(pp, circuits, num_iters_per_step, z0, 0, out);
+}
+
+// ---- a custom circuit over its chain (custom_chain_host.cpp): the step's device trace reaches the circuit through vdf_cs_step_advice
+static int chain_fits(const vdf_pp* pp, const vdf_custom_chain* chain) {
+  if (pp->circuit_kind != VDF_CIRCUIT_CUSTOM) return fail(VDF_ERR_BAD_ARG, "these parameters are not for a custom step circuit");
+  const ChainInfo ci = chain_info(chain);
+  if (ci.field != pp->field)
+    return fail(VDF_ERR_BAD_ARG, std::string("the chain is over ") + (ci.field == VDF_FIELD_FP ? "Fp" : "Fq") + ", the parameters' orientation is " +
+                                     (pp->field == VDF_FIELD_FP ? "Fp" : "Fq"));
+  // (a trace shorter or narrower than the repeat reads would be read past its end)
+  if (!pp->round.used || pp->round.t != ci.t || pp->round.rec.n_adv != ci.n_adv)
+    return fail(VDF_ERR_BAD_ARG, "the chain's t or n_adv differs from the vdf_cs_repeat these parameters were made with");
+  return VDF_OK;
+}
+int vdf_nova_prove_step_custom_chain(vdf_pp* pp, vdf_proof** proof, const vdf_step_circuit* primary, vdf_custom_chain* chain, size_t k,
+                                     const vdf_fe* z0) {
+  if (!pp || !proof || !primary || !primary->synthesize || !chain || !z0) return fail(VDF_ERR_BAD_ARG, "null argument");
+  if (primary->arity != pp->arity) return fail(VDF_ERR_BAD_ARG, "the circuit does not belong to these parameters");
+  vdf_proof* fresh = nullptr;
+  int rc;
+  try {
+    rc = chain_fits(pp, chain);
+    if (rc == VDF_OK && k >= chain_info(chain).steps) rc = fail(VDF_ERR_BAD_ARG, "step " + std::to_string(k) + " is beyond the chain");
+    if (rc == VDF_OK && k != (*proof ? (*proof)->i : 0))
+      rc = fail(VDF_ERR_BAD_ARG, "step " + std::to_string(k) + " out of order: the proof has " + std::to_string(*proof ? (*proof)->i : 0) + " steps");
+    const vdf_fe* d_trace = nullptr;
+    if (rc == VDF_OK) rc = chain_need(chain, k, &d_trace);            // (its synchronisation is what the prover's queue waits by)
+    if (rc == VDF_OK && vdf_ctx_device(chain_info(chain).ctx) != vdf_ctx_device(pp->ctx)) rc = fail(VDF_ERR_BAD_ARG, "the chain's traces live on another device");
+    if (rc == VDF_OK) rc = chain_pump(chain, k);
+    if (rc == VDF_OK) rc = prove_step_impl(pp, proof, nullptr, 0, primary, z0, &fresh, d_trace);
+  }
+  catch (const std::exception& ex) { rc = fail(VDF_ERR_DEVICE, ex.what()); }
+  if (rc != VDF_OK && fresh) vdf_nova_proof_free(fresh);
+  return rc;
+}
+int vdf_nova_pp_repeat_rows(const vdf_pp* pp, uint64_t* row_begin, uint64_t* n_cons, uint64_t* t) {
+  const bool used = pp && pp->circuit_kind == VDF_CIRCUIT_CUSTOM && pp->round.used;
+  if (row_begin) *row_begin = used ? pp->round.row_begin : 0;
+  if (n_cons) *n_cons = used ? pp->round.rec.n_cons : 0;
+  if (t) *t = used ? pp->round.t : 0;
+  return used ? 1 : 0;
+}
+int vdf_nova_proof_last_unsat(const vdf_proof* p, uint64_t* count, uint64_t* first_row) {
+  return nova_guard([&]() -> int {
+    if (!p || !count || !first_row) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (!p->stepped || !p->pp) return fail(VDF_ERR_BAD_ARG, "no step has been proved by this proof object yet");
+    const Side& S1 = p->pp->s[PRIMARY];
+    vdf_ctx* ctx = p->pp->ctx;
+    vdf_proof* q = const_cast<vdf_proof*>(p);                          // scratch buffers only
+    for (void*& b : q->d_unsat)
+      if (!b && vdf_dev_alloc(ctx, S1.num_cons * 32, &b) != VDF_OK) { b = nullptr; return fail(VDF_ERR_OOM, std::string("scan vectors: ") + vdf_last_error(ctx)); }
+    // the last step's fresh z = [W | 1 | X] is in its ring slot until the next step
+    HIPCALL(ctx, vdf_spmv3(ctx, S1.shape, (const vdf_fe*)p->d_z2s[p->slot], (vdf_fe*)q->d_unsat[0], (vdf_fe*)q->d_unsat[1], (vdf_fe*)q->d_unsat[2]));
+    uint64_t out[2] = {0, 0};
+    HIPCALL(ctx, vdf_unsat_rows(ctx, S1.field, (const vdf_fe*)q->d_unsat[0], (const vdf_fe*)q->d_unsat[1], (const vdf_fe*)q->d_unsat[2], S1.num_cons, out));
+    *count = out[0]; *first_row = out[1];
+    return VDF_OK;
+  });
+}
+int vdf_nova_prove_recursively_custom(vdf_pp* pp, const vdf_step_circuit* primary, vdf_custom_chain* chain, const vdf_fe* z0,
+                                      size_t window_steps, uint32_t flags, vdf_proof** out) {
+  return nova_guard([&]() -> int {
+    if (!out) return fail(VDF_ERR_BAD_ARG, "null argument");
+    *out = nullptr;
+    if (!pp || !primary || !primary->synthesize || !chain || !z0) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (flags & ~VDF_CUSTOM_CHECK_STEPS) return fail(VDF_ERR_BAD_ARG, "unknown flag");
+    { int rc = chain_fits(pp, chain); if (rc != VDF_OK) return rc; }
+    const ChainInfo ci = chain_info(chain);
+    const size_t n = ci.steps;
+    // The loop of vdf_nova_prove_recursively_windowed: window w + 1 is walked on the chain's side queue under the proving of window
+    // w, and only what this call built is released.  The handle is the caller's and is left as it was found.
+    { int rc = chain_settle(chain); if (rc != VDF_OK) return rc; }
+    const size_t W = window_steps ? std::max<size_t>(window_steps, 2)
+                                  : std::max<size_t>(2, (size_t)(((uint64_t)1 << 30) / ((ci.t + 1) * ci.n_adv * 32)));
+    std::vector<char> mine(n, 0);
+    auto build = [&](size_t w, int wait) -> int {                        // window w = steps [w W, (w + 1) W)
+      if (w >= (n + W - 1) / W) return VDF_OK;
+      const size_t b = w * W, cnt = std::min(W, n - b);
+      for (size_t k = b; k < b + cnt; ++k) mine[k] = !chain_resident(chain, k);
+      return vdf_nova_custom_chain_materialize(pp->ctx, chain, b, cnt, wait, 0, nullptr);
+    };
+    auto drop = [&](size_t w) { for (size_t k = w * W; k < std::min(n, (w + 1) * W); ++k) if (mine[k]) { chain_park(chain, k); mine[k] = 0; } };
+    vdf_proof* p = nullptr;
+    int rc = build(0, 1);
+    if (rc == VDF_OK) rc = build(1, 0);
+    for (size_t k = 0; rc == VDF_OK && k < n; ++k) {
+      rc = vdf_nova_prove_step_custom_chain(pp, &p, primary, chain, k, z0);
+      if (rc == VDF_OK && (flags & VDF_CUSTOM_CHECK_STEPS)) {
+        uint64_t count = 0, row = 0;
+        rc = vdf_nova_proof_last_unsat(p, &count, &row);
+        if (rc == VDF_OK && count) {
+          std::string msg = "step " + std::to_string(k) + ": " + std::to_string(count) + " unsatisfied rows, first row " + std::to_string(row);
+          uint64_t rb = 0, nc = 0, rt = 0;
+          if (vdf_nova_pp_repeat_rows(pp, &rb, &nc, &rt) && nc && row >= rb && row - rb < nc * rt)
+            msg += " (repetition " + std::to_string((row - rb) / nc) + ", constraint " + std::to_string((row - rb) % nc) + " of the repeat)";
+          rc = fail(VDF_ERR_BAD_ARG, msg);
+        }
+      }
+      if (rc == VDF_OK && (k + 1) % W == 0) {                           // the last step that reads window k / W has returned
+        drop(k / W);
+        rc = build(k / W + 2, 0);
+      }
+    }
+    if (rc == VDF_OK) rc = finalize_l2(p);
+    std::string why;
+    if (rc != VDF_OK) { why = vdf_nova_last_error(); chain_settle(chain); }      // nothing of this call's stays in flight
+    for (size_t w = 0; w * W < n; ++w) drop(w);
+    chain_drop_spare(chain);
+    if (rc != VDF_OK) { vdf_nova_proof_free(p); return fail(rc, why); }
+    *out = p;
+    return VDF_OK;
+  });
 }
 
 // Evaluate and prove at once: a thread of this call evaluates the chain step by step and hands every finished trace over
@@ -2135,6 +2254,7 @@ void vdf_nova_proof_free(vdf_proof* p) {
       for (void* b : bufs) if (b) vdf_dev_free(ctx, b);
     }
     if (p->d_l2z) vdf_dev_free(ctx, p->d_l2z);
+    for (void* b : p->d_unsat) if (b) vdf_dev_free(ctx, b);
     for (void* b : p->d_z2s) if (b) vdf_dev_free(ctx, b);
     for (void* b : p->d_traces) if (b) vdf_dev_free(ctx, b);
     for (void* b : p->d_packed) if (b) vdf_dev_free(ctx, b);

@@ -1,4 +1,4 @@
-// Shared declarations of the translation units of libvdf_nova.so (minroot_host.cpp, r1cs.cpp, nova_host.cpp, circuits_host.cpp,
+// Shared declarations of the translation units of libvdf_nova.so (minroot_host.cpp, r1cs.cpp, nova_host.cpp, circuits_host.cpp, custom_chain_host.cpp,
 // compress_host.cpp, wire_host.cpp): error plumbing, the two sides of the curve cycle, the handle structs.
 #pragma once
 #include <algorithm>
@@ -261,6 +261,10 @@ struct vdf_proof {
   Fe* h_zin = nullptr;           // pinned: the step circuit's input for the early rows of T
   vdf_jac* h_pts = nullptr;      // pinned result slots: [0, RING) segment commitments per ring slot, 4 for the batches, 1 for the early rows of T
   Fe* h_stage[2] = {};           // pinned staging of a host-synthesised witness, one per side
+  // vdf_nova_proof_last_unsat: the last prove_step of THIS object left its fresh primary z in d_z2s[slot]; A z, B z, C z of it are
+  // made again on request into these (allocated by the first request)
+  bool stepped = false;
+  void* d_unsat[3] = {};
   // the last step's by-products, for the parity tests
   vdf_nova_step_info last;
   double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -272,7 +276,7 @@ bool tuning_valid(const vdf_nova_tuning& t);
 int alloc_proof_buffers(vdf_proof* p);
 int finalize_l2(const vdf_proof* p);      // commits to the last secondary witness if that is still pending
 std::unique_ptr<StepCircuit> make_primary_circuit(const vdf_pp* pp, const Circuit* c, bool device_rounds);
-std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx = nullptr);
+std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx = nullptr, const vdf_fe* step_advice = nullptr);
 // ---- the circuits as the drivers of nova_host.cpp reach them (circuits_host.cpp) --------------------------------------------
 inline void eval_step(int field, int mode, uint64_t t, St* state, Fe* trace_xy) {   // t rounds from *state: the trace [2 (t + 1)], *state = the result
   vdf_state in, res;
@@ -291,6 +295,20 @@ int circuits_materialize(vdf_ctx* ctx, const vdf_circuits* c, size_t first, size
 int circuits_settle(const vdf_circuits* c);
 void circuits_park(const vdf_circuits* c, size_t k);
 void circuits_drop_spare(const vdf_circuits* c);
+
+// ---- a custom circuit's chain as the drivers of nova_host.cpp reach it (custom_chain_host.cpp) ------------------------------
+// what the prover must know of a chain before it hands a step's trace to a circuit
+struct ChainInfo { int field; uint64_t t; size_t n_adv, steps; vdf_ctx* ctx; };
+ChainInfo chain_info(const vdf_custom_chain* c);
+// finish the pending walks if they cover step k and hand out its device trace (refused when there is none); enqueue the share
+// of the pending walks that keeps them ahead of a prover about to prove step k; finish whatever is pending
+int chain_need(vdf_custom_chain* c, size_t k, const vdf_fe** d_trace);
+int chain_pump(vdf_custom_chain* c, size_t k);
+int chain_settle(vdf_custom_chain* c);
+bool chain_resident(const vdf_custom_chain* c, size_t k);
+// step k's trace let go of, its allocation kept as the spare if nobody else points into it; the spare freed
+void chain_park(vdf_custom_chain* c, size_t k);
+void chain_drop_spare(vdf_custom_chain* c);
 
 // ---- wire formats (wire_host.cpp; layout in include/vdf_nova.h) --------------------------------------------
 constexpr char WIRE_MAGIC_SNARK[9] = "VDFSNK03";      // compressed proof

@@ -123,4 +123,5 @@ struct vdf_cs {
   uint32_t rec_calls = 0;
   bool walk = false;                               // the recording is a walk body's (vdf_nova_walk_body_record): value arithmetic only
   bool forward = false;                            // ... a forward body's (vdf_nova_forward_body_record): vdf_cs_pow is legal
+  const vdf_fe* step_advice = nullptr;             // vdf_cs_step_advice: the device trace of the step a custom chain drives (witness synthesis only)
 };

@@ -365,6 +365,7 @@ Status vec_relaxed_residual_batch(int field, const uint32_t* const rowptr[3], co
                                   size_t n_long_rows, void* out, double alg_bytes, hipStream_t s);
 Status vec_mul(int field, const void* a, const void* b, size_t n, void* out, hipStream_t s);
 Status vec_any_nonzero(const void* v, size_t n, uint32_t* d_flag, hipStream_t s);     // *d_flag = 1 iff some element is non-zero
+Status vec_unsat_rows(int field, const void* a, const void* b, const void* c, size_t n, void* d_res, hipStream_t s);   // d_res[0] = rows with a b != c, d_res[1] = the first
 Status vec_to_mont(int field, const void* a, size_t n, void* out, hipStream_t s);
 Status vec_from_mont(int field, const void* a, size_t n, void* out, hipStream_t s);
 Status vec_mul_chain(int field, const void* a, size_t n, int iters, void* out, hipStream_t s);

@@ -1174,6 +1174,31 @@ Status vec_any_nonzero(const void* v, size_t n, uint32_t* d_flag, hipStream_t s)
   return Status{};
 }
 
+// Which rows of an instance are unsatisfied (include/vdf_hip.h vdf_unsat_rows): one row per lane, res[0] += the rows with
+// a b != c, res[1] = the smallest of them.  A wavefront with a mismatch sends one lane, its first mismatching one, to the two atomics.
+template <class P>
+__global__ __launch_bounds__(256) void k_unsat_rows(const char* __restrict__ a, const char* __restrict__ b, const char* __restrict__ c, size_t n,
+                                                    unsigned long long* __restrict__ res) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  bool bad = false;
+  if (i < n) bad = !fe_eq(fe_mul(fe_load<P>(a + i * 32), fe_load<P>(b + i * 32)), fe_load<P>(c + i * 32));
+  const unsigned long long m = __ballot(bad);
+  if (m != 0 && (int)(threadIdx.x & 63) == __ffsll(m) - 1) {
+    atomicAdd(&res[0], (unsigned long long)__popcll(m));
+    atomicMin(&res[1], (unsigned long long)i);
+  }
+}
+// d_res: 16 bytes of device memory, initialised here to {0, 2^64 - 1}
+Status vec_unsat_rows(int field, const void* a, const void* b, const void* c, size_t n, void* d_res, hipStream_t s) {
+  VDF_TRY_HIP(hipMemsetAsync(d_res, 0, 8, s));
+  VDF_TRY_HIP(hipMemsetAsync(bytes_of(d_res) + 8, 0xff, 8, s));
+  if (n == 0) return Status{};
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_unsat_rows<tag_t<decltype(f)>>), grid_for(n), dim3(256), 0, s, cbytes_of(a), cbytes_of(b), cbytes_of(c), n,
+                       reinterpret_cast<unsigned long long*>(d_res));
+  });
+}
+
 Status vec_mul(int field, const void* a, const void* b, size_t n, void* out, hipStream_t s) {
   if (n == 0) return Status{};
   return with_field(field, [&](auto f) {

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 import weakref
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -564,6 +564,13 @@ class Context:
         out = C.c_int(0)
         self._check(lib.vdf_vec_is_zero(self.handle, _ptr(v), n, C.byref(out)))
         return bool(out.value)
+
+    def unsat_rows(self, field, az, bz, cz, n: int) -> Tuple[int, int]:
+        """(rows r < n with az[r] * bz[r] != cz[r], the smallest of them or 2**64 - 1), decided on the device; az, bz, cz: device
+        memory, canonical Montgomery elements."""
+        out = (C.c_uint64 * 2)()
+        self._check(lib.vdf_unsat_rows(self.handle, field, _ptr(az), _ptr(bz), _ptr(cz), n, out))
+        return int(out[0]), int(out[1])
 
     def nifs_cross_term(self, shape: Shape, z2, az1, bz1, cz1, u1, az2, bz2, cz2, T) -> None:
         self._check(lib.vdf_nifs_cross_term(self.handle, shape.handle, _ptr(z2), _ptr(az1), _ptr(bz1), _ptr(cz1), _ptr(u1),

@@ -138,6 +138,21 @@ for _name, _res, _args in [
     ("vdf_nova_periodic_rows_eval", _i, [_i, _vp, _u64, _u64, _sz, _sz, _sz, _sz] + [_vp] * 9),
     ("vdf_nova_shape_periodic_custom", _i, [_i, _vp, _vp, _vp, _vp, _vp] + [C.POINTER(_u64)] * 6),
     ("vdf_nova_aug_synthesize_field", _i, [_i, _vp, _i, _u64, _i, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz), _vp, _vp]),
+    # a custom circuit's chain
+    ("vdf_nova_custom_chain_from_checkpoints", _i, [_i, _vp, _vp, _u64, _u64, _sz, _vp, _u64, C.POINTER(_vp)]),
+    ("vdf_nova_custom_chain_materialize", _i, [_vp, _vp, _sz, _sz, _i, _u64, _vp]),
+    ("vdf_nova_custom_chain_release", _i, [_vp, _sz, _sz]),
+    ("vdf_nova_custom_chain_memory", _i, [_vp, C.POINTER(_sz), C.POINTER(_u64)]),
+    ("vdf_nova_custom_chain_host_bytes", _i, [_vp, C.POINTER(_u64)]),
+    ("vdf_nova_custom_chain_len", _sz, [_vp]),
+    ("vdf_nova_custom_chain_advice", _i, [_vp, _sz, C.POINTER(_vp)]),
+    ("vdf_nova_custom_chain_free", None, [_vp]),
+    ("vdf_nova_custom_chain_slice", _i, [_u64, _u64, _u64, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_i)]),
+    ("vdf_cs_step_advice", _vp, [_vp]),
+    ("vdf_nova_prove_step_custom_chain", _i, [_vp, C.POINTER(_vp), _vp, _vp, _sz, _vp]),
+    ("vdf_nova_prove_recursively_custom", _i, [_vp, _vp, _vp, _vp, _sz, C.c_uint32, C.POINTER(_vp)]),
+    ("vdf_nova_proof_last_unsat", _i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    ("vdf_nova_pp_repeat_rows", _i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
 ]:
     if not hasattr(nova_lib, _name):          # AttributeError at call time names the missing entry point
         continue
@@ -155,6 +170,7 @@ SIDE_PRIMARY, SIDE_SECONDARY = 0, 1
 INST_RUNNING_PRIMARY, INST_RUNNING_SECONDARY, INST_FRESH_SECONDARY, INST_FRESH_PRIMARY_LAST = 0, 1, 2, 3
 GENS_KNOWN_DLOG, GENS_TRY_AND_INCREMENT, GENS_LABEL_SHAKE = 0, 1, 2
 PP_NO_DIGIT_TABLES, PP_NO_EARLY_ROWS = 1, 2
+CUSTOM_CHECK_STEPS = 1            # vdf_nova_prove_recursively_custom: scan every step's fresh instance for unsatisfied rows
 KERNEL_EVENT_DTYPE = np.dtype([("name", "S24"), ("bytes", "<f8"), ("start_ms", "<f8"), ("end_ms", "<f8")])     # vdf_kernel_event
 
 
@@ -542,6 +558,11 @@ class ConstraintSystem:
         """A new variable with src's value and no constraint."""
         return nova_lib.vdf_cs_alloc_from(self.h, src)
 
+    def step_advice(self) -> Optional[int]:
+        """vdf_cs_step_advice: the device address of the step's trace inside a synthesize driven by prove_step_custom_chain /
+        prove_recursively_custom, in witness mode; None in every other case.  What `repeat` takes as advice."""
+        return nova_lib.vdf_cs_step_advice(self.h)
+
     def repeat(self, body: "RoundBody", t: int, inv, carry_in, advice=None):
         """vdf_cs_repeat: t repetitions of `body`; returns the carry_out handles.  advice: (t + 1) x n_adv elements, entry-major --
         bytes or a uint64[., 4] array (host), a device tensor or an address (device: the rounds then run on the GPU); None while
@@ -764,6 +785,14 @@ class NovaVDFPublicParams:        # src/nova/proof.rs:38-43
         if not nova_lib.vdf_nova_pp_periodic_rows(self.handle, *[C.byref(x) for x in v]):
             return None
         return dict(zip(("row_begin", "row_count", "lead", "terms_per_rep"), [x.value for x in v]))
+
+    def repeat_rows(self) -> "Tuple[int, int, int] | None":
+        """(row_begin, n_cons, t) of a custom circuit's vdf_cs_repeat: repetition j, constraint c is row row_begin + j * n_cons + c;
+        None without a repeat.  Does not depend on the rows being periodic."""
+        b, n, t = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        if not nova_lib.vdf_nova_pp_repeat_rows(self.handle, C.byref(b), C.byref(n), C.byref(t)):
+            return None
+        return b.value, n.value, t.value
 
     def field(self) -> int:
         """The orientation: the primary circuit's field, the VDF's -- FIELD_FQ (PallasVDF, G1 = Pallas) or FIELD_FP (VestaVDF, G1 = Vesta)."""
@@ -989,6 +1018,111 @@ class Circuits:
             pass
 
 
+def custom_chain_slices(every: int, launch_rounds: int = 0):
+    """The launches vdf_nova_custom_chain_materialize cuts the walks of a window into, by the library's own arithmetic
+    (vdf_nova_custom_chain_slice): [(rounds, top, last)], `last` set in the slice that finishes the walks."""
+    out, done = [], 0
+    while done < every:
+        now, top, last = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+        _check(nova_lib.vdf_nova_custom_chain_slice(every, launch_rounds, done, 0, C.byref(now), C.byref(top), C.byref(last)))
+        out.append((now.value, top.value, bool(last.value)))
+        done += now.value
+    return out
+
+
+def custom_chain_window_host(field: int, walk_tape: RoundTape, inv, t: int, every: int, checkpoints: np.ndarray, first: int, count: int,
+                             j_base: int = 0, launch_rounds: int = 0):
+    """Host only: the window CustomChain.materialize(first, count, launch_rounds=...) builds, by the same sequence of calls over the
+    host restatement (walk_tape_eval): (traces uint64[count * (t + 1) * n_adv, 4], the walks' landings, ok int32[count * t / every]).
+    checkpoints: the chain's, uint64[(steps * t / every + 1) * n_adv, 4]."""
+    na, per = walk_tape.c.n_adv, t // every
+    cp = np.ascontiguousarray(checkpoints, dtype="<u8").reshape(-1, na * 4)
+    walks = count * per
+    entries = cp[first * per + 1: first * per + 1 + walks].copy()
+    expect = cp[first * per: first * per + walks].copy()
+    trace = np.zeros((count * (t + 1) * na, 4), dtype="<u8")
+    ok = np.zeros(walks, dtype="<i4")
+    for rounds, top, last in custom_chain_slices(every, launch_rounds):
+        walk_tape_eval(field, walk_tape, inv, entries, walks, rounds, trace, walk_stride=every, top=top, group=per, group_stride=t + 1,
+                       j_base=(j_base + first * t) % 2**64, j_group_step=t, heads=last, expect=expect if last else None,
+                       ok=ok if last else None)
+    return trace, entries.reshape(-1, 4), ok
+
+
+class CustomChain:
+    """vdf_custom_chain: the chain of a custom step circuit, proved from its checkpoints.  The device traces its steps read as
+    advice are rebuilt window by window by the chain's walk tape on a side queue (include/vdf_nova.h)."""
+
+    def __init__(self, handle: int, field: int, t: int, every: int, n_adv: int):
+        self.handle, self.field, self.t, self.every, self.n_adv = handle, field, t, every, n_adv
+
+    @staticmethod
+    def from_checkpoints(field: int, walk_tape: RoundTape, inv, t: int, every: int, num_steps: int, checkpoints, j_base: int = 0) -> "CustomChain":
+        """checkpoints: num_steps * (t // every) + 1 entries of n_adv elements in forward order -- a uint64[., 4] array (host), or a
+        device tensor / address (downloaded once).  inv: the walk tape's loop-invariant values, host."""
+        inv = np.ascontiguousarray(inv if inv is not None else np.zeros((0, 4)), dtype="<u8").reshape(-1, 4)
+        if inv.shape[0] < walk_tape.c.n_inv:
+            raise ValueError("inv shorter than the tape reads")
+        if isinstance(checkpoints, np.ndarray):
+            checkpoints = np.ascontiguousarray(checkpoints, dtype="<u8")
+            if every and t % every == 0 and checkpoints.size < 4 * (num_steps * (t // every) + 1) * walk_tape.c.n_adv:
+                raise ValueError("checkpoints shorter than num_steps * (t / every) + 1 entries")
+        h = C.c_void_p()
+        _check(nova_lib.vdf_nova_custom_chain_from_checkpoints(field, C.addressof(walk_tape.c), inv.ctypes.data if walk_tape.c.n_inv else None,
+                                                               t, every, num_steps, _ptr(checkpoints), j_base % 2**64, C.byref(h)))
+        return CustomChain(h.value, field, t, every, walk_tape.c.n_adv)
+
+    def __len__(self) -> int:
+        return nova_lib.vdf_nova_custom_chain_len(self.handle)
+
+    def materialize(self, ctx: Context, first: int = 0, count: Optional[int] = None, wait: bool = True, launch_rounds: int = 0) -> List[int]:
+        """Build the device traces of steps [first, first + count) by walks on the GPU, at most launch_rounds rounds per launch
+        (0: 1,024).  Returns the flags per step (1 = a walk missed its checkpoint; all 0 with wait=False); raises VdfError when
+        any missed."""
+        count = len(self) - first if count is None else count
+        bad = (C.c_int * max(count, 1))()
+        self._ctx = ctx
+        ctx._children.add(self)
+        rc = nova_lib.vdf_nova_custom_chain_materialize(ctx.handle, self.handle, first, count, 1 if wait else 0, launch_rounds, bad)
+        self.last_bad = list(bad)[:count]
+        _check(rc)
+        return self.last_bad
+
+    def release(self, first: int = 0, count: Optional[int] = None) -> None:
+        count = len(self) - first if count is None else count
+        _check(nova_lib.vdf_nova_custom_chain_release(self.handle, first, count))
+
+    def memory(self) -> Tuple[int, int]:
+        """(steps with a device trace, bytes of device memory the traces hold)"""
+        n, b = C.c_size_t(0), C.c_uint64(0)
+        _check(nova_lib.vdf_nova_custom_chain_memory(self.handle, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def host_bytes(self) -> int:
+        """bytes of host memory held in the tape, inv and the checkpoints"""
+        b = C.c_uint64(0)
+        _check(nova_lib.vdf_nova_custom_chain_host_bytes(self.handle, C.byref(b)))
+        return b.value
+
+    def advice(self, k: int) -> Optional[int]:
+        """device address of step k's trace ((t + 1) * n_adv elements), None without one; pending walks over it are finished first"""
+        p = C.c_void_p()
+        _check(nova_lib.vdf_nova_custom_chain_advice(self.handle, k, C.byref(p)))
+        return p.value
+
+    def free(self) -> None:
+        ctx = getattr(self, "_ctx", None)
+        if self.handle and (ctx is None or ctx.handle):      # device traces need a live context to be released
+            nova_lib.vdf_nova_custom_chain_free(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class InverseMinRootCircuit:      # src/nova/proof.rs:57-66, :239-299
     arity = 3                     # :83-85
 
@@ -1169,6 +1303,37 @@ class NovaVDFProof:               # enum NovaVDFProof { Recursive, Compressed },
         _reraise(circuit)
         _check(rc)
         return NovaVDFProof(h.value, pp) if proof is None else proof
+
+    @staticmethod
+    def prove_step_custom_chain(pp: NovaVDFPublicParams, proof: "NovaVDFProof | None", circuit: "StepCircuit", chain: "CustomChain", k: int,
+                                z0: Sequence[bytes]) -> "NovaVDFProof":
+        """prove_step_custom for step k of a chain, k = 0, 1, ... in order: the step's device trace is what the circuit's
+        cs.step_advice() answers."""
+        h = C.c_void_p(proof.handle if proof is not None else None)
+        rc = nova_lib.vdf_nova_prove_step_custom_chain(pp.handle, C.byref(h), C.byref(circuit._c()), chain.handle, k, _zn(z0))
+        _reraise(circuit)
+        _check(rc)
+        return NovaVDFProof(h.value, pp) if proof is None else proof
+
+    @staticmethod
+    def prove_recursively_custom(pp: NovaVDFPublicParams, circuit: "StepCircuit", chain: "CustomChain", z0: Sequence[bytes],
+                                 window_steps: int = 0, check_steps: bool = False) -> "NovaVDFProof":
+        """Every step of the chain, the walks of window w + 1 under the proving of window w (window_steps = 0: 1 GiB's worth).
+        check_steps: every step's fresh instance is scanned, and an unsatisfied row ends the call with a VdfError naming it."""
+        h = C.c_void_p()
+        chain._ctx = pp.ctx
+        pp.ctx._children.add(chain)
+        rc = nova_lib.vdf_nova_prove_recursively_custom(pp.handle, C.byref(circuit._c()), chain.handle, _zn(z0), window_steps,
+                                                        CUSTOM_CHECK_STEPS if check_steps else 0, C.byref(h))
+        _reraise(circuit)
+        _check(rc)
+        return NovaVDFProof(h.value, pp)
+
+    def last_unsat(self) -> Tuple[int, int]:
+        """(unsatisfied rows of the LAST step's fresh primary instance, the first of them or 2**64 - 1)"""
+        n, r = C.c_uint64(0), C.c_uint64(0)
+        _check(nova_lib.vdf_nova_proof_last_unsat(self.handle, C.byref(n), C.byref(r)))
+        return n.value, r.value
 
     def compress(self, pp: NovaVDFPublicParams) -> "CompressedNovaVDFProof":            # :360-368
         h = C.c_void_p()
