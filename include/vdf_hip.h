@@ -424,6 +424,17 @@ typedef struct vdf_round_tape {
  * device memory.  Values are whatever the ops make of the advice: nothing is checked against a constraint. */
 int  vdf_round_tape_run(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uint64_t t, const vdf_fe* inv, const vdf_fe* advice,
                         vdf_fe* out);
+/* The same for `lanes` advice arrays at once, ONE launch (kernel k_round_tape_lanes, the lane in the grid's second dimension):
+ * lane l reads its advice lane_stride ENTRIES after lane l - 1's (lane_stride >= t + 1: with rounds_total / every + 1 the layout
+ * vdf_round_tape_eval_batch writes per chain, with t + 1 the traces of vdf_round_tape_walk_lanes' groups back to back), writes its
+ * t * n_vars variables at out + l * t * n_vars, and sees VDF_TAPE_J = j and its own inv[l * n_inv .. l * n_inv + n_inv).  inv: lanes *
+ * n_inv elements in HOST memory, lane-major; all of them travel in the kernel arguments' block of VDF_TAPE_MAX_INV elements (no
+ * staging copy, no synchronisation), hence the second cap.  Refused with VDF_ERR_BAD_ARG: lanes outside 1 .. VDF_TAPE_MAX_LANES,
+ * lanes * n_inv > VDF_TAPE_MAX_INV, lane_stride < t + 1, and what vdf_round_tape_run refuses.
+ * Byte for byte what `lanes` calls of vdf_round_tape_run write; vdf_nova.h vdf_nova_round_tape_eval_lanes restates it on the host. */
+#define VDF_TAPE_MAX_LANES 16
+int  vdf_round_tape_run_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uint64_t t, size_t lanes, const vdf_fe* inv,
+                              const vdf_fe* advice, size_t lane_stride, vdf_fe* out);
 /* 1 when a kernel of this library may read p in place (device memory, or host memory of vdf_host_alloc), else 0 */
 int  vdf_ptr_is_device(const void* p);
 /* ---- walk tapes: the ADVICE of such rounds rebuilt on the device from checkpoints ---------------------------------------------
@@ -467,6 +478,20 @@ int  vdf_ptr_is_device(const void* p);
 int  vdf_round_tape_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n,
                          uint64_t rounds, vdf_fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride,
                          uint64_t j_base, uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok);
+/* vdf_round_tape_walk for the chains of `lanes` lanes in ONE launch (kernel k_tape_walk_lanes), with the groups numbered step-major,
+ * lane-minor: group G = w / group = g * lanes + l is lane l of step g.  Everything is vdf_round_tape_walk's with G in the place of
+ * its g, except what a lane owns: the trace of G lies at G * group_stride (with group_stride = t + 1 a step's trace is its lanes'
+ * traces back to back -- vdf_round_tape_run_lanes' advice at lane_stride = t + 1), and a walk of G sees
+ *   VDF_TAPE_J = j_base[l] + g * j_group_step + k - 1 (modulo 2^64) and inv[l * n_inv .. l * n_inv + n_inv).
+ * inv: lanes * n_inv elements, j_base: `lanes` counters, both HOST memory, carried in the kernel arguments.  group = 0: all walks
+ * are group 0, lane 0 of step 0.  heads, expect and ok as there.  A thread keeps its lane's inv in n_inv more slots of LDS, so the
+ * cap on slots is n_slots + 2 * n_adv + n_inv <= VDF_WALK_MAX_SLOTS here (also with lanes = 1); VDF_WALK_MAX_WORK holds as there.
+ * Refused with VDF_ERR_BAD_ARG besides: lanes outside 1 .. VDF_TAPE_MAX_LANES, lanes * n_inv > VDF_TAPE_MAX_INV, a null j_base.
+ * With lanes = 1 entries, trace and ok are byte for byte vdf_round_tape_walk's; for any lanes vdf_nova_walk_tape_eval_lanes'. */
+int  vdf_round_tape_walk_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* tape, size_t lanes, const vdf_fe* inv, vdf_fe* entries,
+                               size_t n, uint64_t rounds, vdf_fe* trace, size_t walk_stride, size_t top, size_t group,
+                               size_t group_stride, const uint64_t* j_base, uint64_t j_group_step, int heads, const vdf_fe* expect,
+                               int32_t* ok);
 /* ---- forward walk tapes: the chain itself evaluated on the device, many chains at once --------------------------------------
  * The ascending counterpart: the SLOW direction of the round, advice entry j + 1 computed from entry j, one GPU lane per chain --
  * vdf_minroot_forward_walk for a round the library did not write, in that call's layout with an entry of n_adv elements in

@@ -478,6 +478,22 @@ typedef struct {
 } vdf_round_body;
 int     vdf_cs_repeat(vdf_cs* cs, const vdf_round_body* b, uint64_t t, const vdf_num* inv, const vdf_num* carry_in, const vdf_fe* advice,
                       vdf_num* carry_out);
+/* CHAINS IN LANES.  vdf_cs_repeat_lanes runs `lanes` chains through ONE recorded body -- the custom circuit's counterpart of
+ * VDF_CIRCUIT_MINROOT_FORWARD_LANES: one proof, one compress, one verify for all of them.  inv and the carries are lane-major
+ * (lanes * n_inv and lanes * n_carry handles); lane l's advice starts lane_stride ENTRIES after lane l - 1's (lane_stride >= t + 1).
+ * The value of carry c of lane l in repetition j is column c of entry j of lane l's advice.  Variables and constraints are
+ * lane-major, then repetition-major: the circuit written as a plain `for l: for j:` loop has the same shape and digest, and
+ * repetition j, constraint c of lane l is row row_begin + (l * t + j) * n_cons + c (vdf_nova_pp_repeat_rows / _lanes).  It still
+ * counts as the circuit's one repeat, and the parameters keep `lanes`.  With device advice a prove_step writes all lanes' variables
+ * by ONE launch (vdf_hip.h vdf_round_tape_run_lanes); with host advice the tape is interpreted on the host.  VDF_ERR_BAD_ARG besides
+ * vdf_cs_repeat's refusals: lanes outside 1 .. VDF_TAPE_MAX_LANES, lanes * n_inv > VDF_TAPE_MAX_INV, lane_stride < t + 1, and -- when
+ * the advice lies in the trace a chain built for the step (vdf_cs_step_advice below: lanes * (t + 1) entries, owned by the library)
+ * -- a repeat that would read past that trace: there lane_stride must be t + 1 and t, lanes and n_adv the chain's (the stride of
+ * vdf_nova_custom_chain_lanes_from_checkpoints is that of the CHECKPOINTS and is not this one).  Periodic
+ * rows are out of scope for more than one lane: the parameters keep no description and tuning.periodic_rows = 1 gives the generic
+ * kernel.  vdf_cs_repeat is this call with lanes = 1 and lane_stride = t + 1, through the same code. */
+int     vdf_cs_repeat_lanes(vdf_cs* cs, const vdf_round_body* b, uint64_t t, size_t lanes, const vdf_num* inv, const vdf_num* carry_in,
+                            const vdf_fe* advice, size_t lane_stride, vdf_num* carry_out);
 vdf_num vdf_cs_alloc_from(vdf_cs* cs, vdf_num src);                    /* a new variable with src's value, no constraint */
 /* Host only.  Records a body and hands out its tape for vdf_round_tape_run (ops / consts: caller's arrays of the two caps, which
  * out->ops / out->consts then point into); out->n_cons = the constraints per repetition.  field: the body's field. */
@@ -512,6 +528,15 @@ int  vdf_nova_walk_body_record(int field, const vdf_walk_body* b, vdf_tape_op op
 int  vdf_nova_walk_tape_eval(int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n, uint64_t rounds,
                              vdf_fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride, uint64_t j_base,
                              uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok);
+/* Host only.  vdf_round_tape_run_lanes and vdf_round_tape_walk_lanes (vdf_hip.h) restated on the host: the same arguments, the same
+ * refusals (the caps on lanes and lanes * n_inv, lane_stride < t + 1, the slot cap with n_inv counted), every pointer host memory
+ * -- the references of the device paths, byte for byte.  With lanes = 1 they write what vdf_nova_round_tape_eval and
+ * vdf_nova_walk_tape_eval write. */
+int  vdf_nova_round_tape_eval_lanes(int field, const vdf_round_tape* tape, uint64_t t, size_t lanes, const vdf_fe* inv, const vdf_fe* advice,
+                                    size_t lane_stride, vdf_fe* out);
+int  vdf_nova_walk_tape_eval_lanes(int field, const vdf_round_tape* tape, size_t lanes, const vdf_fe* inv, vdf_fe* entries, size_t n,
+                                   uint64_t rounds, vdf_fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride,
+                                   const uint64_t* j_base, uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok);
 /* ---- forward bodies: the chain itself evaluated on the GPU (vdf_hip.h vdf_round_tape_forward_walk / vdf_round_tape_eval_batch) --
  * The slow direction of the round, written once, in the same struct: the `next` argument holds the n_adv columns of the entry the
  * walk STANDS ON (entry j), `j` is that entry's index (the j of the round body whose repetition j relates entries j and j + 1),
@@ -589,12 +614,30 @@ int  vdf_nova_public_params_custom_tuned(vdf_ctx* ctx, int field, const vdf_step
  * was found.  The proof is byte for byte the one vdf_nova_prove_step_custom makes step by step from the same advice.
  * flags & VDF_CUSTOM_CHECK_STEPS: after every step vdf_nova_proof_last_unsat runs, and a non-zero count ends the call with
  * VDF_ERR_BAD_ARG "step k: N unsatisfied rows, first row r (repetition j, constraint c of the repeat)" (the parenthesis for a
- * row of the repeat).  Without the flag wrong advice is not an error, as in vdf_cs_repeat above.
- * Out of scope for custom chains: lookahead, early rows of T, a second vdf_cs_repeat, a streaming eval_and_prove, chains in lanes. */
+ * row of the repeat; "lane l, repetition j, ..." when the repeat has more than one lane).  Without the flag wrong advice is not an error, as in vdf_cs_repeat above.
+ *
+ * CHAINS IN LANES (vdf_cs_repeat_lanes).  vdf_nova_custom_chain_lanes_from_checkpoints takes `lanes` chains of equal length: lane l's
+ * num_steps * (t / every) + 1 checkpoints start lane_stride ENTRIES after lane l - 1's -- with lane_stride = rounds_total / every + 1
+ * that is `lanes` consecutive chains of vdf_round_tape_eval_batch's output unchanged, from host or device memory.  inv: lanes *
+ * n_inv elements, lane-major; j_base: `lanes` counters (host memory).  A step's trace is then lanes * (t + 1) entries, lane l's t + 1
+ * at l * (t + 1): what vdf_cs_repeat_lanes reads at lane_stride = t + 1.  materialize makes lanes * (t / every) walks per step and ONE
+ * vdf_round_tape_walk_lanes per slice for the whole window (group = t / every, group_stride = t + 1, j_base[l] = the lane's +
+ * first * t, j_group_step = t); a walk that misses is reported as "step k, lane l: a walk did not land on the checkpoint below it".
+ * Refused with VDF_ERR_BAD_ARG besides the above: lanes outside 1 .. VDF_TAPE_MAX_LANES, lanes * n_inv > VDF_TAPE_MAX_INV,
+ * lane_stride < num_steps * (t / every) + 1, a null j_base, and for lanes > 1 the slot cap of vdf_round_tape_walk_lanes (n_inv more
+ * slots).  vdf_nova_custom_chain_host_bytes counts, besides the tape, inv and the checkpoints, the staging copy of a window's starts
+ * and targets (2 * walks entries, lanes > 1 only) while that window's walks are pending; it is freed when they resolve.
+ * vdf_nova_custom_chain_from_checkpoints is this call with lanes = 1.  The two provers work unchanged above it and refuse a
+ * chain whose lanes are not the parameters' ("the chain has L lanes, the parameters' vdf_cs_repeat has M").
+ * Out of scope for custom chains: lookahead, early rows of T, a second vdf_cs_repeat, a streaming eval_and_prove, lanes of
+ * different length. */
 typedef struct vdf_custom_chain vdf_custom_chain;
 #define VDF_CUSTOM_CHECK_STEPS 1u
 int  vdf_nova_custom_chain_from_checkpoints(int field, const vdf_round_tape* walk_tape, const vdf_fe* inv, uint64_t t, uint64_t every,
                                             size_t num_steps, const vdf_fe* checkpoints, uint64_t j_base, vdf_custom_chain** out);
+int  vdf_nova_custom_chain_lanes_from_checkpoints(int field, const vdf_round_tape* walk_tape, const vdf_fe* inv, uint64_t t, uint64_t every,
+                                                  size_t num_steps, size_t lanes, const vdf_fe* checkpoints, size_t lane_stride,
+                                                  const uint64_t* j_base, vdf_custom_chain** out);
 int  vdf_nova_custom_chain_materialize(vdf_ctx* ctx, vdf_custom_chain* chain, size_t first, size_t count, int wait, uint64_t launch_rounds,
                                        int* bad);
 int  vdf_nova_custom_chain_release(vdf_custom_chain* chain, size_t first, size_t count);
@@ -623,6 +666,9 @@ int  vdf_nova_proof_last_unsat(const vdf_proof* proof, uint64_t* count, uint64_t
 /* The rows of a custom circuit's vdf_cs_repeat: repetition j, constraint c is row *row_begin + j * *n_cons + c, j < *t.  Returns 1,
  * or 0 for parameters without a repeat (outputs 0); does not depend on the rows being periodic. */
 int  vdf_nova_pp_repeat_rows(const vdf_pp* pp, uint64_t* row_begin, uint64_t* n_cons, uint64_t* t);
+/* ... and the lanes of the repeat (vdf_cs_repeat_lanes; 1 for vdf_cs_repeat): lane l, repetition j, constraint c is row *row_begin +
+ * (l * *t + j) * *n_cons + c.  Returns 1, or 0 for parameters without a repeat (*lanes = 0). */
+int  vdf_nova_pp_repeat_lanes(const vdf_pp* pp, uint64_t* lanes);
 
 /* ---- host-only entry points (no device): what the CPU tests pin against oracle/nova.py ------------------------- */
 /* the random oracle: lane 1 of the sponge after absorbing xs under `tag` (a full field element, Montgomery in and out) */

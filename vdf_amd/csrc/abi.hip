@@ -1536,6 +1536,34 @@ int vdf_round_tape_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, con
   });
 }
 
+int vdf_round_tape_run_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uint64_t t, size_t lanes, const vdf_fe* inv,
+                             const vdf_fe* advice, size_t lane_stride, vdf_fe* out) {
+  return guarded(ctx, [&]() -> Status {
+    if (t == 0 || t >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
+    if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv))
+      return Status{VDF_ERR_BAD_ARG, "the tape and inv live in host memory"};
+    if (!ptr_is_device(advice) || !ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
+    VDF_TRY(vdf::vec_round_tape_lanes(field, tape, t, lanes, inv, advice, lane_stride, out, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
+int vdf_round_tape_walk_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* tape, size_t lanes, const vdf_fe* inv, vdf_fe* entries, size_t n,
+                              uint64_t rounds, vdf_fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride,
+                              const uint64_t* j_base, uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok) {
+  return guarded(ctx, [&]() -> Status {
+    if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv) || ptr_is_device(j_base))
+      return Status{VDF_ERR_BAD_ARG, "the tape, inv and j_base live in host memory"};
+    if (n && rounds && (!ptr_is_device(entries) || (trace && !ptr_is_device(trace)) || (expect && !ptr_is_device(expect)) || (ok && !ptr_is_device(ok))))
+      return Status{VDF_ERR_BAD_ARG, "entries, trace, expect and ok live in device memory"};
+    VDF_TRY(vdf::vec_round_tape_walk_lanes(field, tape, lanes, inv, entries, n, rounds, trace, walk_stride, top, group, group_stride, j_base,
+                                           j_group_step, heads, expect, ok, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
 static Status forward_tape_on_host(const vdf_round_tape* tape, const vdf_fe* inv) {
   if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv))
     return Status{VDF_ERR_BAD_ARG, "the tape and inv live in host memory"};

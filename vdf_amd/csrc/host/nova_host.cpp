@@ -70,6 +70,7 @@ struct CustomStepCircuit : StepCircuit {
   vdf_step_circuit c;
   vdf_ctx* ctx = nullptr;                 // a prover's: lets a vdf_cs_repeat take advice in device memory
   const vdf_fe* step_advice = nullptr;    // ... driven by a chain: the step's device trace (vdf_cs_step_advice)
+  size_t step_advice_elems = 0;           // ... and the elements it holds: a repeat that would read past them is refused
   mutable int rc = 0;
   mutable RepeatState rep;                // the vdf_cs_repeat of the last synthesis, if it had one
   size_t arity() const override { return c.arity; }
@@ -77,6 +78,7 @@ struct CustomStepCircuit : StepCircuit {
     vdf_cs h;
     h.cs = &cs; h.pool = z; h.rep = &rep; h.ctx = ctx;
     h.step_advice = cs.shape ? nullptr : step_advice;
+    h.step_advice_elems = cs.shape ? 0 : step_advice_elems;
     rep = RepeatState();
     std::vector<vdf_num> zin(c.arity), zout(c.arity, 0);
     for (size_t k = 0; k < c.arity; ++k) zin[k] = (vdf_num)k;
@@ -92,11 +94,12 @@ struct CustomStepCircuit : StepCircuit {
 };
 }  // namespace
 namespace vdfnova {
-std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx, const vdf_fe* step_advice) {
+std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx, const vdf_fe* step_advice, size_t step_advice_elems) {
   std::unique_ptr<CustomStepCircuit> m(new CustomStepCircuit());
   m->c = *c;
   m->ctx = ctx;
   m->step_advice = step_advice;
+  m->step_advice_elems = step_advice_elems;
   return std::unique_ptr<StepCircuit>(m.release());
 }
 }  // namespace vdfnova
@@ -624,7 +627,7 @@ int vdf_nova_shape_periodic_custom(int fid, const vdf_step_circuit* primary, uin
     if (num_cons) *num_cons = sh[PRIMARY].num_cons;
     if (num_cols) *num_cols = sh[PRIMARY].num_vars + 1 + NUM_IO;
     PeriodicRows pr;
-    if (!rp.used || !detect_periodic_rows(sh[PRIMARY].m, field(fid), rp.var_begin, rp.rec.n_vars, rp.row_begin, rp.rec.n_cons, rp.t, &pr)) return 0;
+    if (!rp.used || rp.lanes != 1 || !detect_periodic_rows(sh[PRIMARY].m, field(fid), rp.var_begin, rp.rec.n_vars, rp.row_begin, rp.rec.n_cons, rp.t, &pr)) return 0;
     periodic_rows_export(pr, row_start, terms, consts, out, lead, first_row, row_count);
     return 1;
   });
@@ -1075,8 +1078,8 @@ static int public_params_impl(vdf_ctx* ctx, int fid, uint64_t t, int circuit_kin
   // only the MinRoot rounds are made on the device; of a custom circuit the variables of its vdf_cs_repeat, when a step's advice is
   // in device memory (everything a built-in circuit gets on top of that -- early rows, lookahead, a stencil -- stays with them)
   pp->seg_begin = custom ? (pp->round.used ? pp->round.var_begin : 0) : sh[PRIMARY].step_begin;
-  pp->seg_len = custom ? (pp->round.used ? (size_t)pp->round.t * pp->round.rec.n_vars : 0) : sh[PRIMARY].step_end - sh[PRIMARY].step_begin;
-  if (custom && pp->round.used) {
+  pp->seg_len = custom ? (pp->round.used ? pp->round.lanes * (size_t)pp->round.t * pp->round.rec.n_vars : 0) : sh[PRIMARY].step_end - sh[PRIMARY].step_begin;
+  if (custom && pp->round.used && pp->round.lanes == 1) {      // (periodic rows of more than one lane: out of scope, the generic kernel)
     // the rows of the repetitions, read off the triples and compared with every one of them: periodic, or the generic kernel
     const RepeatState& rp = pp->round;
     detect_periodic_rows(sh[PRIMARY].m, field(fid), rp.var_begin, rp.rec.n_vars, rp.row_begin, rp.rec.n_cons, rp.t, &pp->periodic);
@@ -1584,7 +1587,9 @@ struct StepRun {
       memset(&in1.u_W, 0, sizeof(Aff)); memset(&in1.T, 0, sizeof(Aff));
       for (int j = 0; j < 2; ++j) fe_to_int(p->l2.X[j], F2, in1.u_X[j]);
     }
-    c1 = custom ? make_custom_circuit(custom, ctx, step_advice) : make_primary_circuit(pp, &c, true);
+    // (a chain's step trace is what chain_fits compared with the parameters' repeat: lanes * (t + 1) entries of n_adv elements)
+    const size_t advice_elems = step_advice && pp->round.used ? pp->round.lanes * (size_t)(pp->round.t + 1) * pp->round.rec.n_adv : 0;
+    c1 = custom ? make_custom_circuit(custom, ctx, step_advice, advice_elems) : make_primary_circuit(pp, &c, true);
     in2.ro = pp->ro;
   }
   // cross term of (running secondary, l2), commit(w2) unless known, commit(T2)
@@ -1643,7 +1648,7 @@ struct StepRun {
       const RepeatState* round = custom ? &static_cast<const CustomStepCircuit*>(c1.get())->rep : nullptr;
       if (custom) {
         // the body and the count the parameters were made with; the rounds on the device only where the parameters say they are
-        if (round->used != pp->round.used || (round->used && (round->t != pp->round.t || round->var_begin != pp->round.var_begin ||
+        if (round->used != pp->round.used || (round->used && (round->t != pp->round.t || round->lanes != pp->round.lanes || round->var_begin != pp->round.var_begin ||
                                                              !round->rec.same_body(pp->round.rec))))
           return fail(VDF_ERR_BAD_ARG, "the circuit's vdf_cs_repeat differs from the one these parameters were made with");
         if (cs.dev_len && (!round->d_advice || cs.dev_len != pp->seg_len || cs.dev_begin != pp->seg_begin))
@@ -1655,8 +1660,12 @@ struct StepRun {
         // the rounds of the circuit's vdf_cs_repeat, one repetition per thread, straight into the fresh witness: in front of the
         // uploads around them and of the commitment of W, on the step's own queue
         const vdf_round_tape tape = round->rec.view();
-        HIPCALL(ctx, vdf_round_tape_run(ctx, S1.field, &tape, round->t, (const vdf_fe*)round->inv.data(), (const vdf_fe*)round->d_advice,
-                                        (vdf_fe*)((char*)d_z2 + pp->seg_begin * 32)));
+        if (round->lanes == 1)
+          HIPCALL(ctx, vdf_round_tape_run(ctx, S1.field, &tape, round->t, (const vdf_fe*)round->inv.data(), (const vdf_fe*)round->d_advice,
+                                          (vdf_fe*)((char*)d_z2 + pp->seg_begin * 32)));
+        else                                         // all lanes in one launch
+          HIPCALL(ctx, vdf_round_tape_run_lanes(ctx, S1.field, &tape, round->t, round->lanes, (const vdf_fe*)round->inv.data(),
+                                                (const vdf_fe*)round->d_advice, round->lane_stride, (vdf_fe*)((char*)d_z2 + pp->seg_begin * 32)));
       }
       // the host-made variables go next to the rounds the lookahead context has written (vdf_ctx_wait at their launch)
       int rc = upload_fresh(ctx, S1, cs, p->h_stage[PRIMARY], d_z2);
@@ -2059,6 +2068,8 @@ static int chain_fits(const vdf_pp* pp, const vdf_custom_chain* chain) {
   // (a trace shorter or narrower than the repeat reads would be read past its end)
   if (!pp->round.used || pp->round.t != ci.t || pp->round.rec.n_adv != ci.n_adv)
     return fail(VDF_ERR_BAD_ARG, "the chain's t or n_adv differs from the vdf_cs_repeat these parameters were made with");
+  if (pp->round.lanes != ci.lanes)
+    return fail(VDF_ERR_BAD_ARG, "the chain has " + std::to_string(ci.lanes) + " lanes, the parameters' vdf_cs_repeat has " + std::to_string(pp->round.lanes));
   return VDF_OK;
 }
 int vdf_nova_prove_step_custom_chain(vdf_pp* pp, vdf_proof** proof, const vdf_step_circuit* primary, vdf_custom_chain* chain, size_t k,
@@ -2087,6 +2098,11 @@ int vdf_nova_pp_repeat_rows(const vdf_pp* pp, uint64_t* row_begin, uint64_t* n_c
   if (row_begin) *row_begin = used ? pp->round.row_begin : 0;
   if (n_cons) *n_cons = used ? pp->round.rec.n_cons : 0;
   if (t) *t = used ? pp->round.t : 0;
+  return used ? 1 : 0;
+}
+int vdf_nova_pp_repeat_lanes(const vdf_pp* pp, uint64_t* lanes) {
+  const bool used = pp && pp->circuit_kind == VDF_CIRCUIT_CUSTOM && pp->round.used;
+  if (lanes) *lanes = used ? pp->round.lanes : 0;
   return used ? 1 : 0;
 }
 int vdf_nova_proof_last_unsat(const vdf_proof* p, uint64_t* count, uint64_t* first_row) {
@@ -2120,7 +2136,7 @@ int vdf_nova_prove_recursively_custom(vdf_pp* pp, const vdf_step_circuit* primar
     // w, and only what this call built is released.  The handle is the caller's and is left as it was found.
     { int rc = chain_settle(chain); if (rc != VDF_OK) return rc; }
     const size_t W = window_steps ? std::max<size_t>(window_steps, 2)
-                                  : std::max<size_t>(2, (size_t)(((uint64_t)1 << 30) / ((ci.t + 1) * ci.n_adv * 32)));
+                                  : std::max<size_t>(2, (size_t)(((uint64_t)1 << 30) / (ci.lanes * (ci.t + 1) * ci.n_adv * 32)));
     std::vector<char> mine(n, 0);
     auto build = [&](size_t w, int wait) -> int {                        // window w = steps [w W, (w + 1) W)
       if (w >= (n + W - 1) / W) return VDF_OK;
@@ -2140,8 +2156,10 @@ int vdf_nova_prove_recursively_custom(vdf_pp* pp, const vdf_step_circuit* primar
         if (rc == VDF_OK && count) {
           std::string msg = "step " + std::to_string(k) + ": " + std::to_string(count) + " unsatisfied rows, first row " + std::to_string(row);
           uint64_t rb = 0, nc = 0, rt = 0;
-          if (vdf_nova_pp_repeat_rows(pp, &rb, &nc, &rt) && nc && row >= rb && row - rb < nc * rt)
-            msg += " (repetition " + std::to_string((row - rb) / nc) + ", constraint " + std::to_string((row - rb) % nc) + " of the repeat)";
+          const uint64_t rl = pp->round.lanes;
+          if (vdf_nova_pp_repeat_rows(pp, &rb, &nc, &rt) && nc && row >= rb && row - rb < nc * rt * rl)
+            msg += " (" + (rl > 1 ? "lane " + std::to_string((row - rb) / (nc * rt)) + ", " : std::string()) + "repetition " +
+                   std::to_string((row - rb) / nc % rt) + ", constraint " + std::to_string((row - rb) % nc) + " of the repeat)";
           rc = fail(VDF_ERR_BAD_ARG, msg);
         }
       }

@@ -276,7 +276,8 @@ bool tuning_valid(const vdf_nova_tuning& t);
 int alloc_proof_buffers(vdf_proof* p);
 int finalize_l2(const vdf_proof* p);      // commits to the last secondary witness if that is still pending
 std::unique_ptr<StepCircuit> make_primary_circuit(const vdf_pp* pp, const Circuit* c, bool device_rounds);
-std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx = nullptr, const vdf_fe* step_advice = nullptr);
+std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx = nullptr, const vdf_fe* step_advice = nullptr,
+                                                 size_t step_advice_elems = 0);
 // ---- the circuits as the drivers of nova_host.cpp reach them (circuits_host.cpp) --------------------------------------------
 inline void eval_step(int field, int mode, uint64_t t, St* state, Fe* trace_xy) {   // t rounds from *state: the trace [2 (t + 1)], *state = the result
   vdf_state in, res;
@@ -298,7 +299,7 @@ void circuits_drop_spare(const vdf_circuits* c);
 
 // ---- a custom circuit's chain as the drivers of nova_host.cpp reach it (custom_chain_host.cpp) ------------------------------
 // what the prover must know of a chain before it hands a step's trace to a circuit
-struct ChainInfo { int field; uint64_t t; size_t n_adv, steps; vdf_ctx* ctx; };
+struct ChainInfo { int field; uint64_t t; size_t n_adv, steps; vdf_ctx* ctx; size_t lanes; };
 ChainInfo chain_info(const vdf_custom_chain* c);
 // finish the pending walks if they cover step k and hand out its device trace (refused when there is none); enqueue the share
 // of the pending walks that keeps them ahead of a prover about to prove step k; finish whatever is pending

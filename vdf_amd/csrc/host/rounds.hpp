@@ -50,10 +50,11 @@ struct RepeatState {
   bool used = false;
   RoundRecord rec;
   uint64_t t = 0;
+  size_t lanes = 1, lane_stride = 0;               // vdf_cs_repeat_lanes: chains side by side, lane l's advice lane_stride entries after lane l - 1's
   size_t var_begin = 0;                            // index of the first variable of repetition 0 in the witness
   size_t row_begin = 0;                            // ... and of its first constraint in the shape
   const void* d_advice = nullptr;                  // witness mode, advice in device memory: the variables were skipped (cs.dev_begin / dev_len)
-  std::vector<Fe> inv;                             // ... and the values of inv, for the kernel
+  std::vector<Fe> inv;                             // ... and the values of inv (lanes * n_inv, lane-major), for the kernel
 };
 
 // Runs the body once on a recording handle; VDF_ERR_BAD_ARG (message through fail()) for a body that fails, uses a handle it does not
@@ -73,6 +74,12 @@ int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out, bool forw
 // vdf_round_tape_walk on the host (vdf_nova_walk_tape_eval): the same arguments, the same refusals, host memory
 int eval_walk_tape(int field, const vdf_round_tape* tape, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* trace, size_t walk_stride,
                    size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok);
+// vdf_round_tape_run_lanes and vdf_round_tape_walk_lanes on the host (vdf_nova_round_tape_eval_lanes / vdf_nova_walk_tape_eval_lanes)
+int eval_round_tape_lanes(int field, const vdf_round_tape* tape, uint64_t t, size_t lanes, const Fe* inv, const Fe* advice, size_t lane_stride,
+                          Fe* out);
+int eval_walk_tape_lanes(int field, const vdf_round_tape* tape, size_t lanes, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* trace,
+                         size_t walk_stride, size_t top, size_t group, size_t group_stride, const uint64_t* j_base, uint64_t j_group_step,
+                         int heads, const Fe* expect, int32_t* ok);
 // vdf_round_tape_forward_walk on the host (vdf_nova_forward_tape_eval): the same arguments, the same refusals, host memory
 int eval_forward_tape(int field, const vdf_round_tape* tape, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* checkpoints,
                       uint64_t every, size_t cp_stride, Fe* trace, size_t walk_stride, uint64_t base, uint64_t j_base, uint64_t j_walk_step);
@@ -124,4 +131,5 @@ struct vdf_cs {
   bool walk = false;                               // the recording is a walk body's (vdf_nova_walk_body_record): value arithmetic only
   bool forward = false;                            // ... a forward body's (vdf_nova_forward_body_record): vdf_cs_pow is legal
   const vdf_fe* step_advice = nullptr;             // vdf_cs_step_advice: the device trace of the step a custom chain drives (witness synthesis only)
+  size_t step_advice_elems = 0;                    // ... and its length in elements: lanes * (t + 1) * n_adv of the parameters' repeat
 };

@@ -230,6 +230,23 @@ int eval_round_tape(int fid, const vdf_round_tape* tp, uint64_t t, const Fe* inv
   return VDF_OK;
 }
 
+// vdf_round_tape_run_lanes on the host: the launcher's refusals, then lane after lane through eval_round_tape
+int eval_round_tape_lanes(int fid, const vdf_round_tape* tp, uint64_t t, size_t lanes, const Fe* inv, const Fe* advice, size_t lane_stride,
+                          Fe* out) {
+  if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
+  if (!tp || !out || !advice || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts) || (tp->n_inv && !inv)) return fail(VDF_ERR_BAD_ARG, "null argument");
+  if (t == 0 || t >= (1ull << 31)) return fail(VDF_ERR_BAD_LENGTH, "t out of range");
+  if (lanes == 0 || lanes > VDF_TAPE_MAX_LANES) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_TAPE_MAX_LANES");
+  if (tp->n_inv > VDF_TAPE_MAX_INV || lanes * tp->n_inv > VDF_TAPE_MAX_INV) return fail(VDF_ERR_BAD_ARG, "lanes * n_inv > VDF_TAPE_MAX_INV");
+  if (lane_stride < t + 1 || lane_stride > ((size_t)1 << 40)) return fail(VDF_ERR_BAD_ARG, "lane_stride must be at least t + 1");
+  for (size_t l = 0; l < lanes; ++l) {
+    const int rc = eval_round_tape(fid, tp, t, inv + l * tp->n_inv, advice + l * lane_stride * tp->n_adv, out + l * t * tp->n_vars);
+    if (rc != VDF_OK) return rc;
+  }
+  return VDF_OK;
+}
+
+
 
 int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out, bool forward) {
   if (!b || !b->body) return fail(VDF_ERR_BAD_ARG, "walk body: null body");
@@ -287,7 +304,8 @@ static Fe pow_plain(const Fe& x, const Fe& e, const Field& F) {
   return acc;
 }
 
-static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rounds, bool forward = false) {
+// inv_slots: the slots a walk in lanes keeps its lane's inv in (n_inv there, 0 elsewhere), counted against VDF_WALK_MAX_SLOTS
+static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rounds, bool forward = false, bool inv_slots = false) {
   if (!tp || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts)) return fail(VDF_ERR_BAD_ARG, "null tape");
   if (tp->n_ops > VDF_TAPE_MAX_OPS || tp->n_consts > VDF_TAPE_MAX_CONSTS || tp->n_slots > VDF_TAPE_MAX_SLOTS || tp->n_vars > VDF_TAPE_MAX_VARS ||
       tp->n_inv > VDF_TAPE_MAX_INV || tp->n_adv > VDF_TAPE_MAX_ADV || tp->n_vars == 0 || tp->n_adv == 0 || tp->n_slots == 0)
@@ -320,17 +338,24 @@ static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rou
   }
   for (uint32_t k = 0; k < tp->n_adv; ++k)
     if (!col_out[k]) return fail(VDF_ERR_BAD_ARG, "tape leaves variable " + std::to_string(k) + " unwritten");
-  if (tp->n_slots + 2 * tp->n_adv > VDF_WALK_MAX_SLOTS) return fail(VDF_ERR_BAD_ARG, "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS");
+  if (tp->n_slots + 2 * tp->n_adv + (inv_slots ? tp->n_inv : 0) > VDF_WALK_MAX_SLOTS)
+    return fail(VDF_ERR_BAD_ARG, inv_slots ? "walk tape in lanes: n_slots + 2 * n_adv + n_inv > VDF_WALK_MAX_SLOTS" : "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS");
   if (rounds > (forward ? VDF_FORWARD_TAPE_MAX_WORK : VDF_WALK_MAX_WORK) / (products ? products : 1))
     return fail(VDF_ERR_BAD_ARG, std::string("rounds x products per round > ") + (forward ? "VDF_FORWARD_TAPE_MAX_WORK" : "VDF_WALK_MAX_WORK") + " in one call: cut the walk");
   return VDF_OK;
 }
 
-int eval_walk_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* trace, size_t walk_stride,
-                   size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok) {
+// both descending walks: vdf_round_tape_walk is lanes = 1 under its own slot cap (in_lanes false); group G = w / group is lane
+// G % lanes of step G / lanes, with that lane's j_base and inv
+static int walk_tape_lanes(int fid, const vdf_round_tape* tp, size_t lanes, bool in_lanes, const Fe* inv, Fe* entries, size_t n, uint64_t rounds,
+                           Fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride, const uint64_t* j_base,
+                           uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok) {
   if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
-  const int rc = check_walk_tape(tp, inv, rounds);
+  if (lanes == 0 || lanes > VDF_TAPE_MAX_LANES) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_TAPE_MAX_LANES");
+  if (tp && tp->n_inv <= VDF_TAPE_MAX_INV && lanes * tp->n_inv > VDF_TAPE_MAX_INV) return fail(VDF_ERR_BAD_ARG, "lanes * n_inv > VDF_TAPE_MAX_INV");
+  const int rc = check_walk_tape(tp, inv, rounds, false, in_lanes);
   if (rc != VDF_OK) return rc;
+  if (!j_base) return fail(VDF_ERR_BAD_ARG, "null j_base");
   if (expect && !ok) return fail(VDF_ERR_BAD_ARG, "expect without ok");
   if (n == 0 || rounds == 0) return VDF_OK;
   if (n > ((size_t)1 << 31)) return fail(VDF_ERR_BAD_LENGTH, "more than 2^31 walks");
@@ -343,9 +368,11 @@ int eval_walk_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entries
   const size_t na = tp->n_adv;
   Fe s[VDF_TAPE_MAX_SLOTS], stand[VDF_TAPE_MAX_ADV], prod[VDF_TAPE_MAX_ADV];
   for (size_t w = 0; w < n; ++w) {
-    const uint64_t g = w / group, first = (w % group) * walk_stride + top;
-    Fe* tr = trace ? trace + (g * group_stride + first) * na : nullptr;
-    uint64_t j = j_base + g * j_group_step + first - 1;
+    const uint64_t G = w / group, first = (w % group) * walk_stride + top;
+    const uint64_t g = G / lanes;
+    const Fe* lane_inv = inv + (G % lanes) * tp->n_inv;
+    Fe* tr = trace ? trace + (G * group_stride + first) * na : nullptr;
+    uint64_t j = j_base[G % lanes] + g * j_group_step + first - 1;
     for (size_t c = 0; c < na; ++c) stand[c] = entries[w * na + c];
     for (uint64_t r = 0; r < rounds; ++r, --j) {
       if (tr) {
@@ -356,7 +383,7 @@ int eval_walk_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entries
         const vdf_tape_op& o = tp->ops[i];
         switch (o.op) {
           case VDF_TAPE_ADV: s[o.dst] = stand[o.a]; break;
-          case VDF_TAPE_INV: s[o.dst] = inv[o.a]; break;
+          case VDF_TAPE_INV: s[o.dst] = lane_inv[o.a]; break;
           case VDF_TAPE_J: s[o.dst] = from_u64(j, F); break;
           case VDF_TAPE_CONST: s[o.dst] = consts[o.a]; break;
           case VDF_TAPE_ADD: s[o.dst] = add(s[o.a], s[o.b], F); break;
@@ -374,6 +401,19 @@ int eval_walk_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entries
     if (expect) ok[w] = memcmp(stand, expect + w * na, na * sizeof(Fe)) == 0;
   }
   return VDF_OK;
+}
+
+int eval_walk_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* trace, size_t walk_stride,
+                   size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok) {
+  return walk_tape_lanes(fid, tp, 1, false, inv, entries, n, rounds, trace, walk_stride, top, group, group_stride, &j_base, j_group_step, heads,
+                         expect, ok);
+}
+
+int eval_walk_tape_lanes(int fid, const vdf_round_tape* tp, size_t lanes, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* trace,
+                         size_t walk_stride, size_t top, size_t group, size_t group_stride, const uint64_t* j_base, uint64_t j_group_step,
+                         int heads, const Fe* expect, int32_t* ok) {
+  return walk_tape_lanes(fid, tp, lanes, true, inv, entries, n, rounds, trace, walk_stride, top, group, group_stride, j_base, j_group_step, heads,
+                         expect, ok);
 }
 
 int eval_forward_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* checkpoints, uint64_t every,
@@ -657,6 +697,12 @@ vdf_num vdf_cs_pow(vdf_cs* c, vdf_num a, const uint64_t e[4]) {
 
 int vdf_cs_repeat(vdf_cs* c, const vdf_round_body* b, uint64_t t, const vdf_num* inv, const vdf_num* carry_in, const vdf_fe* advice,
                   vdf_num* carry_out) {
+  return vdf_cs_repeat_lanes(c, b, t, 1, inv, carry_in, advice, (size_t)t + 1, carry_out);
+}
+
+// `lanes` chains through ONE recorded body: lane after lane, repetition after repetition, what the plain double loop would call
+int vdf_cs_repeat_lanes(vdf_cs* c, const vdf_round_body* b, uint64_t t, size_t lanes, const vdf_num* inv, const vdf_num* carry_in,
+                        const vdf_fe* advice, size_t lane_stride, vdf_num* carry_out) {
   if (!c) return fail(VDF_ERR_BAD_ARG, "vdf_cs_repeat: null vdf_cs");
   // every refusal below happens before the first variable is made
   auto refuse = [&](const std::string& why) { c->bad = true; return fail(VDF_ERR_BAD_ARG, why); };
@@ -665,49 +711,68 @@ int vdf_cs_repeat(vdf_cs* c, const vdf_round_body* b, uint64_t t, const vdf_num*
   if (c->rep->used) return refuse("vdf_cs_repeat: one vdf_cs_repeat per circuit");
   if (!b || (b->n_inv && !inv) || (b->n_carry && (!carry_in || !carry_out))) return refuse("vdf_cs_repeat: null argument");
   if (t == 0 || t >= (1ull << 31)) return refuse("vdf_cs_repeat: t out of range");
+  if (lanes == 0 || lanes > VDF_TAPE_MAX_LANES) return refuse("vdf_cs_repeat_lanes: lanes must be 1 .. VDF_TAPE_MAX_LANES");
+  if (lanes * b->n_inv > VDF_TAPE_MAX_INV && b->n_inv <= VDF_ROUND_MAX_INV) return refuse("vdf_cs_repeat_lanes: lanes * n_inv > VDF_TAPE_MAX_INV");
+  if (lane_stride < t + 1 || lane_stride > ((size_t)1 << 40)) return refuse("vdf_cs_repeat_lanes: lane_stride must be at least t + 1");
   CS& cs = *c->cs;
   if (!cs.shape && !advice) return refuse("vdf_cs_repeat: a witness needs advice");
   RoundRecord rec;
   if (record_round_body(&cs, b, &rec) != VDF_OK) { c->bad = true; return VDF_ERR_BAD_ARG; }
-  std::vector<Num> invn(rec.n_inv), carry(rec.n_carry);
-  for (uint32_t k = 0; k < rec.n_inv; ++k) {
+  std::vector<Num> invn(lanes * rec.n_inv), carry_all(lanes * rec.n_carry);
+  for (size_t k = 0; k < invn.size(); ++k) {
     if (inv[k] >= c->pool.size()) return refuse("vdf_cs_repeat: bad handle in inv");
     invn[k] = c->pool[inv[k]];
   }
-  for (uint32_t k = 0; k < rec.n_carry; ++k) {
+  for (size_t k = 0; k < carry_all.size(); ++k) {
     if (carry_in[k] >= c->pool.size()) return refuse("vdf_cs_repeat: bad handle in carry_in");
-    carry[k] = c->pool[carry_in[k]];
+    carry_all[k] = c->pool[carry_in[k]];
   }
   const bool device = !cs.shape && vdf_ptr_is_device(advice);
   if (device && (!c->ctx || cs.dev_len != 0)) return refuse("vdf_cs_repeat: advice in device memory outside vdf_nova_prove_step_custom");
+  if (device && c->step_advice && c->step_advice_elems) {
+    // advice inside the trace a chain built for this step: the library owns that buffer and knows its length -- lanes * (t + 1)
+    // entries -- so nothing may be read behind it, by the copies of entry t below or by the kernel
+    const uintptr_t lo = (uintptr_t)c->step_advice, hi = lo + c->step_advice_elems * 32, at = (uintptr_t)advice;
+    if (at >= lo && at < hi && ((lanes - 1) * lane_stride + t + 1) * rec.n_adv * 32 > hi - at)
+      return refuse("vdf_cs_repeat_lanes: the repeat reads past the step's trace of lanes * (t + 1) entries (vdf_cs_step_advice): over a "
+                    "chain's trace lane_stride must be t + 1, and t, lanes and n_adv the chain's");
+  }
   RepeatState& rep = *c->rep;
   rep.used = true;
   rep.t = t;
+  rep.lanes = lanes;
+  rep.lane_stride = lane_stride;
   rep.var_begin = cs.num_vars();
   rep.row_begin = cs.rows;
   rep.d_advice = nullptr;
   const size_t na = rec.n_adv;
-  if (cs.shape) {
-    std::vector<Num> scratch;
-    for (uint64_t j = 0; j < t; ++j) replay_round(cs, rec, j, invn, carry, nullptr, nullptr, scratch);
-  } else if (!device) {
-    const Fe* adv = (const Fe*)advice;
-    std::vector<Num> scratch;
-    for (uint64_t j = 0; j < t; ++j) replay_round(cs, rec, j, invn, carry, adv + j * na, adv + (j + 1) * na, scratch);
-    for (uint32_t k = 0; k < rec.n_carry; ++k) carry[k].v = adv[t * na + k];
-  } else {
+  if (device) {
     std::vector<Fe> last(na);
-    const int rc = vdf_dev_memcpy(c->ctx, last.data(), (const char*)advice + t * na * 32, na * 32);
-    if (rc != VDF_OK) { c->bad = true; return fail(rc, std::string("vdf_cs_repeat: advice entry t: ") + vdf_last_error(c->ctx)); }
-    cs.skip(t * rec.n_vars, t * rec.n_cons);
+    for (size_t l = 0; l < lanes; ++l) {                                 // entry t of every lane: the values of its carry_out
+      const int rc = vdf_dev_memcpy(c->ctx, last.data(), (const char*)advice + (l * lane_stride + t) * na * 32, na * 32);
+      if (rc != VDF_OK) { c->bad = true; return fail(rc, std::string("vdf_cs_repeat: advice entry t: ") + vdf_last_error(c->ctx)); }
+      for (uint32_t k = 0; k < rec.n_carry; ++k) { carry_all[l * rec.n_carry + k] = cs.zero_num(); carry_all[l * rec.n_carry + k].v = last[k]; }
+    }
+    cs.skip(lanes * t * rec.n_vars, lanes * t * rec.n_cons);
     rep.d_advice = advice;
-    rep.inv.resize(rec.n_inv);
-    for (uint32_t k = 0; k < rec.n_inv; ++k) rep.inv[k] = invn[k].v;
-    for (uint32_t k = 0; k < rec.n_carry; ++k) { carry[k] = cs.zero_num(); carry[k].v = last[k]; }
+    rep.inv.resize(invn.size());
+    for (size_t k = 0; k < invn.size(); ++k) rep.inv[k] = invn[k].v;
+  } else {
+    std::vector<Num> scratch, lane_inv(rec.n_inv), carry(rec.n_carry);
+    for (size_t l = 0; l < lanes; ++l) {
+      for (uint32_t k = 0; k < rec.n_inv; ++k) lane_inv[k] = invn[l * rec.n_inv + k];
+      for (uint32_t k = 0; k < rec.n_carry; ++k) carry[k] = std::move(carry_all[l * rec.n_carry + k]);
+      const Fe* adv = cs.shape ? nullptr : (const Fe*)advice + l * lane_stride * na;
+      for (uint64_t j = 0; j < t; ++j) replay_round(cs, rec, j, lane_inv, carry, adv ? adv + j * na : nullptr, adv ? adv + (j + 1) * na : nullptr, scratch);
+      for (uint32_t k = 0; k < rec.n_carry; ++k) {
+        if (adv) carry[k].v = adv[t * na + k];
+        carry_all[l * rec.n_carry + k] = std::move(carry[k]);
+      }
+    }
   }
   rep.rec = std::move(rec);
-  for (uint32_t k = 0; k < rep.rec.n_carry; ++k) {
-    c->pool.push_back(std::move(carry[k]));
+  for (size_t k = 0; k < carry_all.size(); ++k) {
+    c->pool.push_back(std::move(carry_all[k]));
     carry_out[k] = (vdf_num)(c->pool.size() - 1);
   }
   return VDF_OK;
@@ -723,7 +788,7 @@ int vdf_nova_round_body_record(int fid, const vdf_round_body* b, vdf_tape_op ops
     if (rc != VDF_OK) return rc;
     *out = rec.view();
     memcpy(ops, rec.ops.data(), rec.ops.size() * sizeof(vdf_tape_op));
-    memcpy(consts, rec.consts.data(), rec.consts.size() * 32);
+    if (!rec.consts.empty()) memcpy(consts, rec.consts.data(), rec.consts.size() * 32);      // (a body may have no constant)
     out->ops = ops;
     out->consts = consts;
     return VDF_OK;
@@ -797,6 +862,20 @@ int vdf_nova_periodic_rows_eval(int fid, const vdf_periodic_rows* rows, uint64_t
   return nova_guard([&]() -> int {
     return eval_periodic_rows(fid, rows, j_first, reps, seg_begin, row_begin, num_cols, num_cons, (const Fe*)z2, (const Fe*)Az1, (const Fe*)Bz1,
                               (const Fe*)Cz1, (const Fe*)u1, (Fe*)Az2, (Fe*)Bz2, (Fe*)Cz2, (Fe*)T);
+  });
+}
+
+int vdf_nova_round_tape_eval_lanes(int fid, const vdf_round_tape* tape, uint64_t t, size_t lanes, const vdf_fe* inv, const vdf_fe* advice,
+                                   size_t lane_stride, vdf_fe* out) {
+  return nova_guard([&]() -> int { return eval_round_tape_lanes(fid, tape, t, lanes, (const Fe*)inv, (const Fe*)advice, lane_stride, (Fe*)out); });
+}
+
+int vdf_nova_walk_tape_eval_lanes(int fid, const vdf_round_tape* tape, size_t lanes, const vdf_fe* inv, vdf_fe* entries, size_t n, uint64_t rounds,
+                                  vdf_fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride, const uint64_t* j_base,
+                                  uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok) {
+  return nova_guard([&]() -> int {
+    return eval_walk_tape_lanes(fid, tape, lanes, (const Fe*)inv, (Fe*)entries, n, rounds, (Fe*)trace, walk_stride, top, group, group_stride,
+                                j_base, j_group_step, heads, (const Fe*)expect, ok);
   });
 }
 

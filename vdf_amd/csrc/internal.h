@@ -321,6 +321,11 @@ Status vec_forward_segment_lanes(int field, const void* trace_xy, size_t lane_st
                                  hipStream_t s);
 // rounds.hip: a recorded round run over t repetitions (every index of the tape is checked before the launch; inv: host)
 Status vec_round_tape(int field, const vdf_round_tape* tape, uint64_t t, const vdf_fe* inv, const void* advice, void* out, hipStream_t s);
+Status vec_round_tape_lanes(int field, const vdf_round_tape* tape, uint64_t t, size_t lanes, const vdf_fe* inv, const void* advice,
+                            size_t lane_stride, void* out, hipStream_t s);
+Status vec_round_tape_walk_lanes(int field, const vdf_round_tape* tape, size_t lanes, const vdf_fe* inv, void* entries, size_t n,
+                                 uint64_t rounds, void* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride,
+                                 const uint64_t* j_base, uint64_t j_group_step, int heads, const void* expect, int32_t* ok, hipStream_t s);
 Status vec_round_tape_walk(int field, const vdf_round_tape* tape, const vdf_fe* inv, void* entries, size_t n, uint64_t rounds, void* trace,
                            size_t walk_stride, size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step,
                            int heads, const void* expect, int32_t* ok, hipStream_t s);

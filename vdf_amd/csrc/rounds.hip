@@ -75,6 +75,48 @@ __global__ __launch_bounds__(64) void k_round_tape(TapeArgs tape, const char* __
   }
 }
 
+// k_round_tape for `lanes` advice arrays in ONE launch (vdf_hip.h vdf_round_tape_run_lanes): the lane is the grid's second dimension,
+// so it is a scalar like the tape: the lane's advice, its variables and its own n_inv invariants -- all lanes' invariants share the
+// 512-byte block of the arguments, lane-major -- are reached through scalar offsets, and the interpreter is k_round_tape's.
+struct LaneRunArgs { uint64_t t, lane_stride; uint32_t n_inv, pad; };
+static_assert(sizeof(TapeArgs) + sizeof(LaneRunArgs) + 16 <= 4096, "the tape travels in the kernel-argument segment");
+
+template <class P>
+__global__ __launch_bounds__(64) void k_round_tape_lanes(TapeArgs tape, LaneRunArgs la, const char* __restrict__ advice, char* __restrict__ out) {
+  extern __shared__ uint4 tape_slots[];
+  __builtin_amdgcn_s_setprio(3);     // light kernel: do not starve behind a co-running k_accumulate
+  const uint32_t lane = threadIdx.x;
+  const uint64_t j = (uint64_t)blockIdx.x * 64 + lane;
+  if (j >= la.t) return;
+  const uint64_t l = blockIdx.y;                     // (wave-uniform)
+  const uint32_t inv0 = (uint32_t)l * la.n_inv;
+  const char* adv = advice + (l * la.lane_stride + j) * tape.n_adv * 32;
+  char* o = out + (l * la.t + j) * tape.n_vars * 32;
+  for (uint32_t i = 0; i < tape.n_ops; ++i) {
+    const uint32_t w = tape.ops[i];
+    const uint32_t op = w & 0xFF, dst = (w >> 8) & 0xFF, a = (w >> 16) & 0xFF, b = w >> 24;
+    Fe<P> r;
+    switch (op) {
+      case VDF_TAPE_ADV: r = fe_load<P>(adv + (b * tape.n_adv + a) * 32); break;
+      case VDF_TAPE_INV: r = tape_fe<P>(tape.inv[inv0 + a]); break;
+      case VDF_TAPE_J: r = fe_from_u64<P>(j); break;
+      case VDF_TAPE_CONST: r = tape_fe<P>(tape.consts[a]); break;
+      case VDF_TAPE_ADD: r = fe_add(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
+      case VDF_TAPE_SUB: r = fe_sub(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
+      case VDF_TAPE_MUL: {
+        const Fe<P> x = slot_load<P>(tape_slots, a, lane);
+        r = a == b ? fe_sqr(x) : fe_mul(x, slot_load<P>(tape_slots, b, lane));
+        break;
+      }
+      case VDF_TAPE_SCALE: r = fe_mul(slot_load<P>(tape_slots, a, lane), tape_fe<P>(tape.consts[b])); break;
+      default:                       // VDF_TAPE_OUT (the launcher admits no other opcode)
+        fe_store<P>(o + b * 32, slot_load<P>(tape_slots, a, lane));
+        continue;
+    }
+    slot_store<P>(tape_slots, dst, lane, r);
+  }
+}
+
 // ---- walk tapes: the advice itself, rebuilt from checkpoints (vdf_hip.h vdf_round_tape_walk) ---------------------------------
 // k_inverse_walk's launch (one lane per walk, workgroups of one wavefront, wave priority left at 0: background work beside a
 // prover) around k_round_tape's interpreter.  Two entries of n_adv slots follow the value file in LDS: the one the walk stands on
@@ -138,6 +180,101 @@ __global__ __launch_bounds__(64) void k_tape_walk(TapeArgs tape, WalkArgs wa, ch
   // where the walk landed: back into entries, to the head of its group's trace, and against the checkpoint
   uint32_t diff = 0;
   const bool head = tp && wa.heads && w % wa.group == 0;
+  for (uint32_t c = 0; c < na; ++c) {
+    const Fe<P> v = slot_load<P>(tape_slots, stand + c, lane);
+    fe_store<P>(ep + c * 32, v);
+    if (head) fe_store<P>(tp + c * 32, v);
+    if (expect) {
+      const Fe<P> e = fe_load<P>(expect + w * esz + c * 32);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) diff |= v.v[q] ^ e.v[q];
+    }
+  }
+  if (expect) ok[w] = diff == 0;
+}
+
+// k_tape_walk with the groups numbered step-major, lane-minor (vdf_hip.h vdf_round_tape_walk_lanes): group G = g * lanes + l is lane
+// l of step g.  Here the lane is a per-thread value -- one wavefront holds walks of several lanes -- and the kernel arguments
+// indexed by it would go to scratch.  So each thread selects its own j_base and invariants ONCE, before the rounds, in a uniform
+// loop over the at most VDF_TAPE_MAX_LANES argument elements (scalar loads, a select per element), and keeps the invariants in n_inv
+// more lane-private slots of LDS behind the two entries: an INV op is then a slot load like any other.
+struct WalkLanesArgs {
+  WalkArgs w;
+  uint32_t lanes, n_inv;
+  uint64_t j_base[VDF_TAPE_MAX_LANES];
+};
+static_assert(sizeof(TapeArgs) + sizeof(WalkLanesArgs) + 32 <= 4096, "the tape travels in the kernel-argument segment");
+
+template <class P>
+__global__ __launch_bounds__(64) void k_tape_walk_lanes(TapeArgs tape, WalkLanesArgs wl, char* __restrict__ entries, char* __restrict__ trace,
+                                                        const char* __restrict__ expect, int32_t* __restrict__ ok) {
+  extern __shared__ uint4 tape_slots[];
+  const uint32_t lane = threadIdx.x;
+  const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
+  if (w >= wl.w.n) return;                           // (no barrier below: a lane touches only its own words of LDS)
+  const uint32_t na = tape.n_adv;
+  const size_t esz = (size_t)na * 32;
+  char* const ep = entries + w * esz;
+  const uint64_t G = w / wl.w.group, first = (w % wl.w.group) * wl.w.walk_stride + wl.w.top;
+  const uint64_t g = G / wl.lanes;
+  const uint32_t l = (uint32_t)(G % wl.lanes);
+  uint32_t stand = wl.w.n_slots, prod = wl.w.n_slots + na;
+  const uint32_t inv0 = wl.w.n_slots + 2 * na;
+  uint64_t jb = 0;
+#pragma unroll 1
+  for (uint32_t q = 0; q < wl.lanes; ++q) {
+    const uint64_t x = wl.j_base[q];
+    jb = q == l ? x : jb;
+  }
+#pragma unroll 1
+  for (uint32_t k = 0; k < wl.n_inv; ++k) {
+    Fe<P> v = fe_zero<P>();
+#pragma unroll 1
+    for (uint32_t q = 0; q < wl.lanes; ++q) {
+      const Fe<P> x = tape_fe<P>(tape.inv[q * wl.n_inv + k]);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v.v[i] = q == l ? x.v[i] : v.v[i];
+    }
+    slot_store<P>(tape_slots, inv0 + k, lane, v);
+  }
+  for (uint32_t c = 0; c < na; ++c) slot_store<P>(tape_slots, stand + c, lane, fe_load<P>(ep + c * 32));
+  char* tp = trace ? trace + (G * wl.w.group_stride + first) * esz : nullptr;
+  uint64_t j = jb + g * wl.w.j_group_step + first - 1;
+#pragma unroll 1
+  for (uint32_t r = 0; r < wl.w.rounds; ++r, --j) {
+    if (tp) {
+      for (uint32_t c = 0; c < na; ++c) fe_store<P>(tp + c * 32, slot_load<P>(tape_slots, stand + c, lane));
+      tp -= esz;
+    }
+#pragma unroll 1
+    for (uint32_t i = 0; i < tape.n_ops; ++i) {
+      const uint32_t x = tape.ops[i];
+      const uint32_t op = x & 0xFF, dst = (x >> 8) & 0xFF, a = (x >> 16) & 0xFF, b = x >> 24;
+      Fe<P> v;
+      switch (op) {
+        case VDF_TAPE_ADV: v = slot_load<P>(tape_slots, stand + a, lane); break;      // (the launcher admits b = 1 only)
+        case VDF_TAPE_INV: v = slot_load<P>(tape_slots, inv0 + a, lane); break;
+        case VDF_TAPE_J: v = fe_from_u64<P>(j); break;
+        case VDF_TAPE_CONST: v = tape_fe<P>(tape.consts[a]); break;
+        case VDF_TAPE_ADD: v = fe_add(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
+        case VDF_TAPE_SUB: v = fe_sub(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
+        case VDF_TAPE_MUL: {
+          const Fe<P> y = slot_load<P>(tape_slots, a, lane);
+          v = a == b ? fe_sqr(y) : fe_mul(y, slot_load<P>(tape_slots, b, lane));
+          break;
+        }
+        case VDF_TAPE_SCALE: v = fe_mul(slot_load<P>(tape_slots, a, lane), tape_fe<P>(tape.consts[b])); break;
+        default:                       // VDF_TAPE_OUT
+          slot_store<P>(tape_slots, prod + b, lane, slot_load<P>(tape_slots, a, lane));
+          continue;
+      }
+      slot_store<P>(tape_slots, dst, lane, v);
+    }
+    const uint32_t t = stand; stand = prod; prod = t;
+  }
+  // where the walk landed: back into entries, to the head of its group's trace, and against the checkpoint
+  uint32_t diff = 0;
+  const bool head = tp && wl.w.heads && w % wl.w.group == 0;
   for (uint32_t c = 0; c < na; ++c) {
     const Fe<P> v = slot_load<P>(tape_slots, stand + c, lane);
     fe_store<P>(ep + c * 32, v);
@@ -354,13 +491,16 @@ static uint64_t pow_products(const TapeFe& e) {
 // (b = 0 descending, b = 1 ascending).  VDF_TAPE_POW is an op of forward tapes only.  products (if asked for): the field products of
 // one round, a POW counted as its squarings and multiplications.
 enum TapeMode { TAPE_ROUND, TAPE_WALK, TAPE_FORWARD };
-static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, TapeMode mode, TapeArgs& a, uint64_t* products = nullptr) {
+// lanes: inv holds lanes * n_inv elements, lane-major; all of them go into the block of VDF_TAPE_MAX_INV (the *_lanes launchers).
+static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, TapeMode mode, TapeArgs& a, uint64_t* products = nullptr, size_t lanes = 1) {
   const bool walk = mode != TAPE_ROUND;
   if (!tp || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts)) return Status{VDF_ERR_BAD_ARG, "null tape"};
   if (tp->n_ops > VDF_TAPE_MAX_OPS || tp->n_consts > VDF_TAPE_MAX_CONSTS || tp->n_slots > VDF_TAPE_MAX_SLOTS || tp->n_vars > VDF_TAPE_MAX_VARS ||
       tp->n_inv > VDF_TAPE_MAX_INV || tp->n_adv > VDF_TAPE_MAX_ADV || tp->n_vars == 0 || tp->n_adv == 0 || tp->n_slots == 0)
     return Status{VDF_ERR_BAD_ARG, "tape exceeds a published cap (VDF_TAPE_MAX_*), or has no variable, slot or advice column"};
   if (walk && tp->n_vars != tp->n_adv) return Status{VDF_ERR_BAD_ARG, "walk tape: n_vars != n_adv (a round writes one advice entry)"};
+  if (lanes == 0 || lanes > VDF_TAPE_MAX_LANES) return Status{VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_TAPE_MAX_LANES"};
+  if (lanes * tp->n_inv > VDF_TAPE_MAX_INV) return Status{VDF_ERR_BAD_ARG, "lanes * n_inv > VDF_TAPE_MAX_INV (all lanes' inv travel in the kernel arguments)"};
   if (tp->n_inv && !inv) return Status{VDF_ERR_BAD_ARG, "null inv"};
   std::memset(&a, 0, sizeof(a));
   a.n_ops = (uint32_t)tp->n_ops; a.n_vars = tp->n_vars; a.n_adv = tp->n_adv;
@@ -394,7 +534,7 @@ static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, TapeMode mo
   for (uint32_t v = 0; v < tp->n_vars; ++v)
     if (!var_out[v]) return Status{VDF_ERR_BAD_ARG, "tape leaves variable " + std::to_string(v) + " unwritten"};
   for (size_t k = 0; k < tp->n_consts; ++k) a.consts[k] = tape_val(&tp->consts[k]);
-  for (uint32_t k = 0; k < tp->n_inv; ++k) a.inv[k] = tape_val(&inv[k]);
+  for (size_t k = 0; k < lanes * tp->n_inv; ++k) a.inv[k] = tape_val(&inv[k]);
   if (products) *products = n_products ? n_products : 1;
   return Status{};
 }
@@ -411,34 +551,92 @@ Status vec_round_tape(int field, const vdf_round_tape* tp, uint64_t t, const vdf
   });
 }
 
-Status vec_round_tape_walk(int field, const vdf_round_tape* tp, const vdf_fe* inv, void* entries, size_t n, uint64_t rounds, void* trace,
-                           size_t walk_stride, size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step,
-                           int heads, const void* expect, int32_t* ok, hipStream_t s) {
-  VDF_TRY(check_field(field));
-  TapeArgs a;
-  VDF_TRY(pack_tape(tp, inv, TAPE_WALK, a));
-  if (tp->n_slots + 2 * tp->n_adv > VDF_WALK_MAX_SLOTS)
-    return Status{VDF_ERR_BAD_ARG, "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"};
-  uint64_t products = 0;
-  for (size_t i = 0; i < tp->n_ops; ++i) products += tp->ops[i].op == VDF_TAPE_MUL || tp->ops[i].op == VDF_TAPE_SCALE;
-  if (products == 0) products = 1;
+// What both descending walks check between packing the tape and launching (vdf_hip.h): the slot cap (inv_slots: the slots a walk
+// in lanes keeps its lane's inv in), the work cap over pack_tape's products, and the layout.  *nothing: n = 0 or rounds = 0.
+static Status walk_launch_checks(const vdf_round_tape* tp, uint32_t inv_slots, uint64_t products, size_t n, uint64_t rounds,
+                                 const void* entries, const void* trace, size_t top, int heads, const void* expect, const int32_t* ok,
+                                 bool* nothing) {
+  *nothing = false;
+  if (tp->n_slots + 2 * tp->n_adv + inv_slots > VDF_WALK_MAX_SLOTS)
+    return Status{VDF_ERR_BAD_ARG, inv_slots ? "walk tape in lanes: n_slots + 2 * n_adv + n_inv > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"
+                                             : "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"};
   if (rounds > VDF_WALK_MAX_WORK / products) return Status{VDF_ERR_BAD_ARG, "rounds x products per round > VDF_WALK_MAX_WORK in one call: cut the walk"};
   if (expect && !ok) return Status{VDF_ERR_BAD_ARG, "expect without ok"};
-  if (n == 0 || rounds == 0) return Status{};
+  if (n == 0 || rounds == 0) { *nothing = true; return Status{}; }
   if (n > ((size_t)1 << 31)) return Status{VDF_ERR_BAD_LENGTH, "more than 2^31 walks"};
   if (!entries) return Status{VDF_ERR_BAD_ARG, "null entries"};
   if (trace && top + 1 < rounds) return Status{VDF_ERR_BAD_ARG, "top < rounds - 1: the walk would write below its run"};
   if (trace && heads && top < rounds) return Status{VDF_ERR_BAD_ARG, "heads with top < rounds: the landing would be written below the run"};
+  return Status{};
+}
+static WalkArgs walk_args(const vdf_round_tape* tp, size_t n, uint64_t rounds, size_t walk_stride, size_t top, size_t group, size_t group_stride,
+                          uint64_t j_base, uint64_t j_group_step, int heads) {
   if (group == 0) { group = n; group_stride = 0; }
   WalkArgs wa;
   std::memset(&wa, 0, sizeof(wa));
   wa.n = n; wa.walk_stride = walk_stride; wa.top = top; wa.group = group; wa.group_stride = group_stride;
   wa.j_base = j_base; wa.j_group_step = j_group_step;
   wa.rounds = (uint32_t)rounds; wa.n_slots = tp->n_slots; wa.heads = heads != 0;
+  return wa;
+}
+
+Status vec_round_tape_walk(int field, const vdf_round_tape* tp, const vdf_fe* inv, void* entries, size_t n, uint64_t rounds, void* trace,
+                           size_t walk_stride, size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step,
+                           int heads, const void* expect, int32_t* ok, hipStream_t s) {
+  VDF_TRY(check_field(field));
+  TapeArgs a;
+  uint64_t products = 1;
+  VDF_TRY(pack_tape(tp, inv, TAPE_WALK, a, &products));
+  bool nothing = false;
+  VDF_TRY(walk_launch_checks(tp, 0, products, n, rounds, entries, trace, top, heads, expect, ok, &nothing));
+  if (nothing) return Status{};
+  const WalkArgs wa = walk_args(tp, n, rounds, walk_stride, top, group, group_stride, j_base, j_group_step, heads);
   KTimer kt(s, "k_tape_walk", trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0);
   const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv) * 2 * 64 * sizeof(uint4);
   return with_field(field, [&](auto f) {
     hipLaunchKernelGGL((k_tape_walk<tag_t<decltype(f)>>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, wa, bytes_of(entries),
+                       bytes_of(trace), cbytes_of(expect), ok);
+  });
+}
+
+Status vec_round_tape_lanes(int field, const vdf_round_tape* tp, uint64_t t, size_t lanes, const vdf_fe* inv, const void* advice,
+                            size_t lane_stride, void* out, hipStream_t s) {
+  VDF_TRY(check_field(field));
+  TapeArgs a;
+  VDF_TRY(pack_tape(tp, inv, TAPE_ROUND, a, nullptr, lanes));
+  if (t == 0 || t >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
+  if (lane_stride < t + 1 || lane_stride > ((size_t)1 << 40)) return Status{VDF_ERR_BAD_ARG, "lane_stride must be at least t + 1"};
+  LaneRunArgs la;
+  std::memset(&la, 0, sizeof(la));
+  la.t = t; la.lane_stride = lane_stride; la.n_inv = tp->n_inv;
+  KTimer kt(s, "k_round_tape_lanes", 32.0 * (tp->n_adv + tp->n_vars) * t * lanes);
+  const dim3 grid((unsigned)((t + 63) / 64), (unsigned)lanes);
+  const size_t lds = (size_t)tp->n_slots * 2 * 64 * sizeof(uint4);
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_round_tape_lanes<tag_t<decltype(f)>>), grid, dim3(64), lds, s, a, la, cbytes_of(advice), bytes_of(out));
+  });
+}
+
+Status vec_round_tape_walk_lanes(int field, const vdf_round_tape* tp, size_t lanes, const vdf_fe* inv, void* entries, size_t n, uint64_t rounds,
+                                 void* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride, const uint64_t* j_base,
+                                 uint64_t j_group_step, int heads, const void* expect, int32_t* ok, hipStream_t s) {
+  VDF_TRY(check_field(field));
+  TapeArgs a;
+  uint64_t products = 1;
+  VDF_TRY(pack_tape(tp, inv, TAPE_WALK, a, &products, lanes));
+  if (!j_base) return Status{VDF_ERR_BAD_ARG, "null j_base"};
+  bool nothing = false;
+  VDF_TRY(walk_launch_checks(tp, tp->n_inv, products, n, rounds, entries, trace, top, heads, expect, ok, &nothing));
+  if (nothing) return Status{};
+  WalkLanesArgs wl;
+  std::memset(&wl, 0, sizeof(wl));
+  wl.w = walk_args(tp, n, rounds, walk_stride, top, group, group_stride, 0, j_group_step, heads);
+  wl.lanes = (uint32_t)lanes; wl.n_inv = tp->n_inv;
+  for (size_t l = 0; l < lanes; ++l) wl.j_base[l] = j_base[l];
+  KTimer kt(s, "k_tape_walk_lanes", trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0);
+  const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv + tp->n_inv) * 2 * 64 * sizeof(uint4);
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_tape_walk_lanes<tag_t<decltype(f)>>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, wl, bytes_of(entries),
                        bytes_of(trace), cbytes_of(expect), ok);
   });
 }

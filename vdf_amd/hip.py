@@ -59,6 +59,7 @@ class RoundTapeC(C.Structure):
 
 TAPE_MAX_OPS, TAPE_MAX_CONSTS, TAPE_MAX_SLOTS, TAPE_MAX_VARS, TAPE_MAX_INV, TAPE_MAX_ADV = 320, 24, 24, 64, 16, 8
 WALK_MAX_SLOTS, WALK_MAX_WORK = 32, 1 << 23        # VDF_WALK_MAX_SLOTS, VDF_WALK_MAX_WORK
+TAPE_MAX_LANES = 16                                # VDF_TAPE_MAX_LANES
 FORWARD_TAPE_MAX_WORK = 1 << 20                    # VDF_FORWARD_TAPE_MAX_WORK
 TAPE_POW = 9                                       # VDF_TAPE_POW
 
@@ -496,6 +497,24 @@ class Context:
         self._check(lib.vdf_round_tape_walk(self.handle, field, C.addressof(tape.c), _ptr(inv), _ptr(entries), n, rounds, _ptr(trace),
                                             walk_stride, top, group, group_stride, j_base, j_group_step, int(bool(heads)), _ptr(expect),
                                             _ptr(ok)))
+
+    def round_tape_run_lanes(self, field, tape: "RoundTape", t, lanes, inv, advice, lane_stride, out) -> None:
+        """round_tape_run for `lanes` advice arrays lane_stride entries apart in ONE launch: lane l's t * n_vars variables at
+        out + l * t * n_vars, under its own inv[l * n_inv:(l + 1) * n_inv] (host, lanes * n_inv elements); advice, out: device."""
+        self._check(lib.vdf_round_tape_run_lanes(self.handle, field, C.addressof(tape.c), t, lanes, _ptr(inv), _ptr(advice), lane_stride,
+                                                 _ptr(out)))
+
+    def round_tape_walk_lanes(self, field, tape: "RoundTape", lanes, inv, entries, n, rounds, trace=None, walk_stride=0, top=0, group=0,
+                              group_stride=0, j_base=None, j_group_step=0, heads=False, expect=None, ok=None) -> None:
+        """round_tape_walk with the groups numbered step-major, lane-minor, in ONE launch: group G = w // group is lane G % lanes of
+        step G // lanes, its trace at G * group_stride; its rounds see j_base[lane] + (G // lanes) * j_group_step + k - 1 and
+        inv[lane * n_inv:(lane + 1) * n_inv].  inv (lanes * n_inv elements) and j_base (`lanes` ints, default zeros): host."""
+        jb = np.ascontiguousarray([0] * lanes if j_base is None else [int(v) % 2**64 for v in j_base], dtype="<u8")
+        if jb.size < lanes:
+            raise ValueError("j_base: one counter per lane")
+        self._check(lib.vdf_round_tape_walk_lanes(self.handle, field, C.addressof(tape.c), lanes, _ptr(inv), _ptr(entries), n, rounds,
+                                                  _ptr(trace), walk_stride, top, group, group_stride, jb.ctypes.data, j_group_step,
+                                                  int(bool(heads)), _ptr(expect), _ptr(ok)))
 
     def round_tape_forward_walk(self, field, tape: "RoundTape", inv, entries, n, rounds, checkpoints=None, every=0, cp_stride=0, trace=None,
                                 walk_stride=0, base=0, j_base=0, j_walk_step=0) -> None:

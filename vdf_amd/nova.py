@@ -94,10 +94,13 @@ for _name, _res, _args in [
     ("vdf_cs_value", _i, [_vp, C.c_uint32, _vp]),
     ("vdf_cs_alloc_from", C.c_uint32, [_vp, C.c_uint32]),
     ("vdf_cs_repeat", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    ("vdf_cs_repeat_lanes", _i, [_vp, _vp, _u64, _sz, _vp, _vp, _vp, _sz, _vp]),
     ("vdf_nova_round_body_record", _i, [_i, _vp, _vp, _vp, _vp]),
     ("vdf_nova_round_tape_eval", _i, [_i, _vp, _u64, _vp, _vp, _vp]),
     ("vdf_nova_walk_body_record", _i, [_i, _vp, _vp, _vp, _vp]),
     ("vdf_nova_walk_tape_eval", _i, [_i, _vp, _vp, _vp, _sz, _u64, _vp, _sz, _sz, _sz, _sz, _u64, _u64, _i, _vp, _vp]),
+    ("vdf_nova_round_tape_eval_lanes", _i, [_i, _vp, _u64, _sz, _vp, _vp, _sz, _vp]),
+    ("vdf_nova_walk_tape_eval_lanes", _i, [_i, _vp, _sz, _vp, _vp, _sz, _u64, _vp, _sz, _sz, _sz, _sz, _vp, _u64, _i, _vp, _vp]),
     ("vdf_cs_pow", C.c_uint32, [_vp, C.c_uint32, _vp]),
     ("vdf_nova_forward_body_record", _i, [_i, _vp, _vp, _vp, _vp]),
     ("vdf_nova_forward_tape_eval", _i, [_i, _vp, _vp, _vp, _sz, _u64, _vp, _u64, _sz, _vp, _sz, _u64, _u64, _u64]),
@@ -140,6 +143,8 @@ for _name, _res, _args in [
     ("vdf_nova_aug_synthesize_field", _i, [_i, _vp, _i, _u64, _i, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz), _vp, _vp]),
     # a custom circuit's chain
     ("vdf_nova_custom_chain_from_checkpoints", _i, [_i, _vp, _vp, _u64, _u64, _sz, _vp, _u64, C.POINTER(_vp)]),
+    ("vdf_nova_custom_chain_lanes_from_checkpoints", _i, [_i, _vp, _vp, _u64, _u64, _sz, _sz, _vp, _sz, _vp, C.POINTER(_vp)]),
+    ("vdf_nova_pp_repeat_lanes", _i, [_vp, C.POINTER(_u64)]),
     ("vdf_nova_custom_chain_materialize", _i, [_vp, _vp, _sz, _sz, _i, _u64, _vp]),
     ("vdf_nova_custom_chain_release", _i, [_vp, _sz, _sz]),
     ("vdf_nova_custom_chain_memory", _i, [_vp, C.POINTER(_sz), C.POINTER(_u64)]),
@@ -397,6 +402,20 @@ def round_tape_eval(field: int, tape: RoundTape, t: int, inv, advice) -> np.ndar
     return out
 
 
+def round_tape_eval_lanes(field: int, tape: RoundTape, t: int, lanes: int, inv, advice, lane_stride: int) -> np.ndarray:
+    """Host only: what Context.round_tape_run_lanes writes, uint64[lanes * t * n_vars, 4]; inv: lanes * n_inv elements, advice:
+    lane l's t + 1 entries from entry l * lane_stride on."""
+    inv = np.ascontiguousarray(inv if inv is not None else np.zeros((0, 4)), dtype="<u8").reshape(-1, 4)
+    advice = np.ascontiguousarray(advice, dtype="<u8").reshape(-1, 4)
+    ok_shape = 0 < lanes <= 16 and lane_stride >= t + 1
+    if ok_shape and (inv.shape[0] < lanes * tape.c.n_inv or advice.shape[0] < ((lanes - 1) * lane_stride + t + 1) * tape.c.n_adv):
+        raise ValueError("inv or advice shorter than the tape reads")
+    out = np.zeros((max(lanes, 0) * t * tape.c.n_vars, 4), dtype="<u8")
+    _check(nova_lib.vdf_nova_round_tape_eval_lanes(field, C.addressof(tape.c), t, lanes, inv.ctypes.data if tape.c.n_inv else None,
+                                                   advice.ctypes.data, lane_stride, out.ctypes.data))
+    return out
+
+
 _WALK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
 
 
@@ -471,6 +490,38 @@ def walk_tape_eval(field: int, tape: RoundTape, inv, entries: np.ndarray, n: int
                                             trace.ctypes.data if trace is not None else None, walk_stride, top, group, group_stride, j_base,
                                             j_group_step, int(bool(heads)), expect.ctypes.data if expect is not None else None,
                                             ok.ctypes.data if ok is not None else None))
+
+
+def walk_tape_eval_lanes(field: int, tape: RoundTape, lanes: int, inv, entries: np.ndarray, n: int, rounds: int,
+                         trace: "np.ndarray | None" = None, walk_stride: int = 0, top: int = 0, group: int = 0, group_stride: int = 0,
+                         j_base=None, j_group_step: int = 0, heads: bool = False, expect: "np.ndarray | None" = None,
+                         ok: "np.ndarray | None" = None) -> None:
+    """Host only: Context.round_tape_walk_lanes on the host, in place over numpy arrays as walk_tape_eval; inv: lanes * n_inv
+    elements, j_base: `lanes` ints (default zeros).  The same arguments and the same refusals."""
+    def arr(x, dtype, what):
+        if x is None:
+            return None
+        if not isinstance(x, np.ndarray) or x.dtype != np.dtype(dtype) or not x.flags["C_CONTIGUOUS"] or not x.flags["WRITEABLE"]:
+            raise ValueError("%s: a writable C-contiguous %s array" % (what, dtype))
+        return x
+    na = tape.c.n_adv
+    inv = np.ascontiguousarray(inv if inv is not None else np.zeros((0, 4)), dtype="<u8").reshape(-1, 4)
+    jb = np.ascontiguousarray([0] * max(lanes, 1) if j_base is None else [int(v) % 2**64 for v in j_base], dtype="<u8")
+    entries, trace, expect, ok = arr(entries, "<u8", "entries"), arr(trace, "<u8", "trace"), arr(expect, "<u8", "expect"), arr(ok, "<i4", "ok")
+    if 0 < lanes <= 16:
+        if inv.shape[0] < lanes * tape.c.n_inv or jb.size < lanes or entries.size < 4 * n * na or \
+                (expect is not None and expect.size < 4 * n * na) or (ok is not None and ok.size < n):
+            raise ValueError("inv, j_base, entries, expect or ok shorter than the walks read")
+    if trace is not None and n and rounds and top + 1 >= rounds:
+        g = group or n
+        last = ((n - 1) // g) * (group_stride if group else 0) + (min(n, g) - 1) * walk_stride + top
+        if trace.size < 4 * (last + 1) * na:
+            raise ValueError("trace shorter than the walks write")
+    _check(nova_lib.vdf_nova_walk_tape_eval_lanes(field, C.addressof(tape.c), lanes, inv.ctypes.data if tape.c.n_inv else None,
+                                                  entries.ctypes.data, n, rounds, trace.ctypes.data if trace is not None else None,
+                                                  walk_stride, top, group, group_stride, jb.ctypes.data, j_group_step, int(bool(heads)),
+                                                  expect.ctypes.data if expect is not None else None,
+                                                  ok.ctypes.data if ok is not None else None))
 
 
 def record_forward_body(body: WalkBody, field: int = FIELD_FQ) -> RoundTape:
@@ -583,6 +634,30 @@ class ConstraintSystem:
         _reraise(body)
         _check(rc)
         return [cout[k] for k in range(body.n_carry)]
+
+    def repeat_lanes(self, body: "RoundBody", t: int, lanes: int, inv, carry_in, advice=None, lane_stride: Optional[int] = None):
+        """vdf_cs_repeat_lanes: `lanes` chains through one recorded body, lane after lane; inv / carry_in: lanes * n_inv / lanes *
+        n_carry handles, lane-major; returns the lanes * n_carry carry_out handles.  advice as in `repeat`, lane l's t + 1 entries
+        from entry l * lane_stride on (default t + 1)."""
+        lane_stride = t + 1 if lane_stride is None else lane_stride
+        if len(inv) != lanes * body.n_inv or len(carry_in) != lanes * body.n_carry:
+            raise ValueError("inv / carry_in do not match lanes * n_inv / lanes * n_carry")
+        need = ((lanes - 1) * lane_stride + t + 1) * body.n_adv * 32 if lanes > 0 and lane_stride >= t + 1 else 0
+        if isinstance(advice, (bytes, bytearray)):
+            advice = np.frombuffer(bytes(advice), dtype="<u8")
+        if isinstance(advice, np.ndarray):
+            advice = np.ascontiguousarray(advice, dtype="<u8")
+            if advice.size * 8 < need:
+                raise ValueError("advice is shorter than the lanes read")
+        if hasattr(advice, "data_ptr") and advice.numel() * advice.element_size() < need:
+            raise ValueError("advice is shorter than the lanes read")
+        U = C.c_uint32
+        n_c, n_i = max(1, len(carry_in)), max(1, len(inv))
+        cin, cout, invs = (U * n_c)(*carry_in), (U * n_c)(), (U * n_i)(*inv)
+        rc = nova_lib.vdf_cs_repeat_lanes(self.h, C.addressof(body._c()), t, lanes, invs, cin, _ptr(advice), lane_stride, cout)
+        _reraise(body)
+        _check(rc)
+        return [cout[k] for k in range(len(carry_in))]
 
 
 class StepCircuit:
@@ -793,6 +868,13 @@ class NovaVDFPublicParams:        # src/nova/proof.rs:38-43
         if not nova_lib.vdf_nova_pp_repeat_rows(self.handle, C.byref(b), C.byref(n), C.byref(t)):
             return None
         return b.value, n.value, t.value
+
+    def repeat_lanes(self) -> int:
+        """The lanes of a custom circuit's repeat (1 for ConstraintSystem.repeat); 0 without a repeat.  Lane l, repetition j,
+        constraint c is row row_begin + (l * t + j) * n_cons + c of repeat_rows()."""
+        n = C.c_uint64(0)
+        nova_lib.vdf_nova_pp_repeat_lanes(self.handle, C.byref(n))
+        return n.value
 
     def field(self) -> int:
         """The orientation: the primary circuit's field, the VDF's -- FIELD_FQ (PallasVDF, G1 = Pallas) or FIELD_FP (VestaVDF, G1 = Vesta)."""
@@ -1053,8 +1135,32 @@ class CustomChain:
     """vdf_custom_chain: the chain of a custom step circuit, proved from its checkpoints.  The device traces its steps read as
     advice are rebuilt window by window by the chain's walk tape on a side queue (include/vdf_nova.h)."""
 
-    def __init__(self, handle: int, field: int, t: int, every: int, n_adv: int):
-        self.handle, self.field, self.t, self.every, self.n_adv = handle, field, t, every, n_adv
+    def __init__(self, handle: int, field: int, t: int, every: int, n_adv: int, lanes: int = 1):
+        self.handle, self.field, self.t, self.every, self.n_adv, self.lanes = handle, field, t, every, n_adv, lanes
+
+    @staticmethod
+    def lanes_from_checkpoints(field: int, walk_tape: RoundTape, inv, t: int, every: int, num_steps: int, lanes: int, checkpoints,
+                               lane_stride: Optional[int] = None, j_base=None) -> "CustomChain":
+        """`lanes` chains of equal length in one chain object (ConstraintSystem.repeat_lanes): lane l's num_steps * (t // every) + 1
+        checkpoints start lane_stride entries (default: exactly that many) after lane l - 1's -- consecutive chains of
+        Context.round_tape_eval_batch's output, host array or device tensor / address.  inv: lanes * n_inv elements, j_base: one
+        counter per lane (default zeros).  A step's trace is lanes * (t + 1) entries."""
+        per_lane = num_steps * (t // every) + 1 if every and t % every == 0 else 0
+        lane_stride = per_lane if lane_stride is None else lane_stride
+        inv = np.ascontiguousarray(inv if inv is not None else np.zeros((0, 4)), dtype="<u8").reshape(-1, 4)
+        jb = np.ascontiguousarray([0] * max(lanes, 1) if j_base is None else [int(v) % 2**64 for v in j_base], dtype="<u8")
+        if 0 < lanes <= 16 and (inv.shape[0] < lanes * walk_tape.c.n_inv or jb.size < lanes):
+            raise ValueError("inv or j_base shorter than the lanes read")
+        if isinstance(checkpoints, np.ndarray):
+            checkpoints = np.ascontiguousarray(checkpoints, dtype="<u8")
+            if per_lane and 0 < lanes <= 16 and lane_stride >= per_lane and \
+                    checkpoints.size < 4 * ((lanes - 1) * lane_stride + per_lane) * walk_tape.c.n_adv:
+                raise ValueError("checkpoints shorter than the lanes read")
+        h = C.c_void_p()
+        _check(nova_lib.vdf_nova_custom_chain_lanes_from_checkpoints(field, C.addressof(walk_tape.c),
+                                                                     inv.ctypes.data if walk_tape.c.n_inv else None, t, every, num_steps,
+                                                                     lanes, _ptr(checkpoints), lane_stride, jb.ctypes.data, C.byref(h)))
+        return CustomChain(h.value, field, t, every, walk_tape.c.n_adv, lanes)
 
     @staticmethod
     def from_checkpoints(field: int, walk_tape: RoundTape, inv, t: int, every: int, num_steps: int, checkpoints, j_base: int = 0) -> "CustomChain":
@@ -1105,7 +1211,7 @@ class CustomChain:
         return b.value
 
     def advice(self, k: int) -> Optional[int]:
-        """device address of step k's trace ((t + 1) * n_adv elements), None without one; pending walks over it are finished first"""
+        """device address of step k's trace (lanes * (t + 1) * n_adv elements), None without one; pending walks over it are finished first"""
         p = C.c_void_p()
         _check(nova_lib.vdf_nova_custom_chain_advice(self.handle, k, C.byref(p)))
         return p.value
