@@ -402,11 +402,13 @@ int  vdf_minroot_forward_segment_lanes(vdf_ctx* ctx, int field, const vdf_fe* tr
  *   VDF_TAPE_OUT    variable b of this repetition = slot[a]: out[j * n_vars + b]   (dst unused; b < n_vars)
  *   VDF_TAPE_POW    slot[dst] = slot[a] ^ E, E = consts[b] read as a PLAIN 256-bit little-endian integer (no field element, no
  *                   Montgomery form).  Forward walk tapes only (below): anywhere else it is a malformed op
+ *   VDF_TAPE_POWC   slot[dst] = slot[a] ^ E(chain), the chain a caller-supplied addition chain that lies in the constants from
+ *                   consts[b] on (vdf_pow_step below).  Forward walk tapes only, like VDF_TAPE_POW
  * advice: (t + 1) entries of n_adv elements, entry-major (a MinRoot trace is n_adv = 2).  A slot is read only after an op of
  * the same tape wrote it (refused otherwise) and every variable is written exactly once.  n_cons, the constraints per
  * repetition, is carried for the caller (constraints cost nothing here).  The caps below are refused with VDF_ERR_BAD_ARG. */
 enum { VDF_TAPE_ADV = 0, VDF_TAPE_INV = 1, VDF_TAPE_J = 2, VDF_TAPE_CONST = 3, VDF_TAPE_ADD = 4, VDF_TAPE_SUB = 5, VDF_TAPE_MUL = 6,
-       VDF_TAPE_SCALE = 7, VDF_TAPE_OUT = 8, VDF_TAPE_POW = 9 };
+       VDF_TAPE_SCALE = 7, VDF_TAPE_OUT = 8, VDF_TAPE_POW = 9, VDF_TAPE_POWC = 10 };
 #define VDF_TAPE_MAX_OPS 320      /* ops of a tape (loads and stores included) */
 #define VDF_TAPE_MAX_CONSTS 24
 #define VDF_TAPE_MAX_SLOTS 24     /* live values: 2 KiB of LDS each per 64 repetitions */
@@ -509,7 +511,26 @@ int  vdf_round_tape_walk_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* ta
  *   VDF_TAPE_POW  slot[dst] = slot[a] ^ E, E = the 256 bits of consts[b] as a plain little-endian integer.  E = 0 gives 1 (also
  *                 for base 0), E = 1 copies, any E < 2^256 is accepted; the result is canonical like every other op's.  Left to
  *                 right square-and-multiply from the top set bit: bitlen(E) - 1 squarings and popcount(E) - 1 products
- * everything else as above.  vdf_nova.h vdf_nova_forward_body_record makes one from a callback (vdf_cs_pow).
+ *   VDF_TAPE_POWC slot[dst] = slot[a] ^ E, E the exponent of the addition chain in consts[b ..] (below).  The result is canonical:
+ *                 byte for byte what VDF_TAPE_POW with exponent E gives.  POW and POWC may stand in one tape
+ * everything else as above.  vdf_nova.h vdf_nova_forward_body_record makes one from a callback (vdf_cs_pow, vdf_cs_pow_chain).
+ *
+ * An addition chain (vdf_pow_step) is a straight-line program over an accumulator v and n_tmp temporaries T[0 .. n_tmp), T[0] the
+ * base on entry.  One step is
+ *   v = T[src] unless src == VDF_POW_ACC;  v = v^(2^squarings);  v = v * T[mul] unless mul == VDF_POW_NONE;
+ *   T[dst] = v unless dst == VDF_POW_NONE
+ * and the result is v after the last step.  Its exponent E follows from the steps: e(T[0]) = 1, and a step gives e = e(src) *
+ * 2^squarings + e(mul).  A chain is VALID when it has 1 .. VDF_POW_CHAIN_MAX_STEPS steps, n_tmp is 1 .. VDF_POW_CHAIN_MAX_TMP and
+ * every index is below n_tmp, step 0 does not start from VDF_POW_ACC, no temporary is read before a step wrote it (T[0] counts as
+ * written) and every intermediate exponent is below 2^256.  A step of 0 squarings, no product and no dst is legal (padding).
+ * In a tape the chain is read as plain BYTES, as VDF_TAPE_POW reads its exponent as a plain integer: byte 0 of consts[b] is n_steps,
+ * byte 1 n_tmp, bytes 2 and 3 zero; the steps follow at four bytes each and run on into consts[b + 1] and further, ceil((4 + 4
+ * n_steps) / 32) constants in all (at most 12); the bytes behind the last step up to the end of the last constant are zero.
+ * The kernel (k_tape_forward_walk_chain, launched only for a tape that holds a POWC; any other tape launches k_tape_forward_walk as
+ * before) keeps the accumulator in registers and the temporaries in n_tmp more slots of LDS, all products in the lazy domain and
+ * the result made canonical once.  A POWC counts max(1, sum of squarings + steps with a product) products.
+ * Refused with VDF_ERR_BAD_ARG on top of the list below: an invalid chain, one that runs past n_consts, non-zero padding, and
+ * n_slots + 2 * n_adv + (the largest n_tmp of the tape's chains) > VDF_WALK_MAX_SLOTS.
  *
  * entries (device, n x n_adv elements): entries[w] is where walk w stands; it is overwritten with where it stands afterwards, so
  * long chains are cut into calls.  Strides are in ENTRIES.  `base` = the rounds the walks have behind them; with g = base + r + 1
@@ -527,6 +548,11 @@ int  vdf_round_tape_walk_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* ta
  * products), so that one launch holds a queue no longer than that one may.  n = 0 or rounds = 0 do nothing.
  * Exact: entries, checkpoints and trace are byte for byte vdf_nova_forward_tape_eval's (vdf_nova.h). */
 #define VDF_FORWARD_TAPE_MAX_WORK (1ull << 20)
+typedef struct vdf_pow_step { uint8_t src, squarings, mul, dst; } vdf_pow_step;
+#define VDF_POW_ACC  0xFE   /* src: go on from the accumulator */
+#define VDF_POW_NONE 0xFF   /* mul: no product; dst: nothing kept */
+#define VDF_POW_CHAIN_MAX_STEPS 95
+#define VDF_POW_CHAIN_MAX_TMP   12
 int  vdf_round_tape_forward_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n,
                                  uint64_t rounds, vdf_fe* checkpoints, uint64_t every, size_t cp_stride, vdf_fe* trace,
                                  size_t walk_stride, uint64_t base, uint64_t j_base, uint64_t j_walk_step);

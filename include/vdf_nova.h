@@ -541,7 +541,7 @@ int  vdf_nova_walk_tape_eval_lanes(int field, const vdf_round_tape* tape, size_t
  * The slow direction of the round, written once, in the same struct: the `next` argument holds the n_adv columns of the entry the
  * walk STANDS ON (entry j), `j` is that entry's index (the j of the round body whose repetition j relates entries j and j + 1),
  * and the body stores the handle of every column of entry j + 1 in cur_out.  Everything else is as for a walk body -- value
- * arithmetic only, the same refusals, the same caps, each refused one beyond -- with one more call:
+ * arithmetic only, the same refusals, the same caps, each refused one beyond -- with two more calls:
  *   vdf_cs_pow(cs, a, e) = a ^ e, e a PLAIN 256-bit little-endian integer (e = 0 gives 1, also for a = 0).  One call, one result
  *   slot, the exponent one stored constant under VDF_ROUND_MAX_CONSTS.  It is legal ONLY while a forward body is recorded: on a
  *   live vdf_cs, in a round body and in a descending walk body it sets the failure flag, as a bad handle does.  A power inside
@@ -550,6 +550,29 @@ int  vdf_nova_walk_tape_eval_lanes(int field, const vdf_round_tape* tape, size_t
  * on the device: vdf_round_tape_eval_batch -> checkpoints -> vdf_round_tape_walk -> vdf_nova_prove_step_custom.
  * examples/prove_custom_pipeline.c.  A throughput feature for many chains, not a faster single chain (vdf_hip.h). */
 vdf_num vdf_cs_pow(vdf_cs* cs, vdf_num a, const uint64_t e[4]);
+/*   vdf_cs_pow_chain(cs, a, steps, n_steps) = a ^ E, E the exponent of the caller's ADDITION CHAIN (vdf_hip.h vdf_pow_step: a
+ *   straight-line program over an accumulator and a few temporaries; every real delay function of this family is a power by a huge
+ *   fixed exponent, and its authors have such a chain).  Recorded as ONE VDF_TAPE_POWC: one call, one result slot; the chain takes
+ *   ceil((4 + 4 n_steps) / 32) packed constants under VDF_ROUND_MAX_CONSTS, and its temporaries count against the slot cap: live
+ *   values + 2 * n_adv + (the largest n_tmp of the body's chains) <= VDF_WALK_MAX_SLOTS.  The value is byte for byte vdf_cs_pow(cs,
+ *   a, E)'s; on the device the chain's products stay in the lazy domain and only the result is made canonical.  Legal ONLY while a
+ *   forward body is recorded, as vdf_cs_pow; there and for an invalid chain it sets the failure flag. */
+vdf_num vdf_cs_pow_chain(vdf_cs* cs, vdf_num a, const vdf_pow_step* steps, size_t n_steps);
+/* Host only.  Validates a chain (vdf_hip.h: VDF_ERR_BAD_ARG, vdf_nova_last_error names the step) and returns its exponent e (a plain
+ * 256-bit little-endian integer), the temporaries it needs (its largest index + 1) and its product count, max(1, squarings + steps
+ * with a product) -- what VDF_FORWARD_TAPE_MAX_WORK counts.  Each output may be NULL. */
+int  vdf_nova_pow_chain_exponent(const vdf_pow_step* steps, size_t n_steps, uint64_t e[4], uint32_t* n_tmp, uint64_t* products);
+/* Host only.  A chain for ANY exponent e >= 1: left to right, sliding windows of at most `window` bits (2 .. 4).  The table comes
+ * first, always whole: T[1] = x^2 and the odd powers T[1 + k] = x^(2k + 1) up to 2^window - 1 (2^(window - 1) + 1 temporaries, one
+ * squaring and 2^(window - 1) - 1 products); then one step per window.  For both MinRoot root exponents window 4 gives 316 products
+ * (252 squarings, 56 products, 8 for the table) against 377 of VDF_TAPE_POW's square-and-multiply and 283 / 282 of the hand-made
+ * chains.  steps: `cap` steps of room; *n_steps: the steps written.  VDF_ERR_BAD_LENGTH when the chain does not fit cap or
+ * VDF_POW_CHAIN_MAX_STEPS (window 2 over a dense exponent), VDF_ERR_BAD_ARG for e = 0 or a window outside 2 .. 4. */
+int  vdf_nova_pow_chain_window(const uint64_t e[4], unsigned window, vdf_pow_step* steps, size_t cap, size_t* n_steps);
+/* Host only.  The library's own two chains for the MinRoot fifth root x -> x^(1/5 mod (m - 1)) (src/minroot.rs:88-127 over Fq,
+ * :223-261 over Fp), as the host evaluator and vdf_minroot_forward_walk run them: 32 steps (padded with steps that do nothing), 9
+ * temporaries, 253 squarings, 30 products over Fq and 29 over Fp.  cap < 32: VDF_ERR_BAD_LENGTH. */
+int  vdf_minroot_pow_chain(int field, vdf_pow_step* steps, size_t cap, size_t* n_steps);
 /* Host only.  Records a forward body and hands out its forward walk tape (ops / consts as vdf_nova_round_body_record); n_vars = n_adv, n_cons = 0. */
 int  vdf_nova_forward_body_record(int field, const vdf_walk_body* b, vdf_tape_op ops[VDF_TAPE_MAX_OPS], vdf_fe consts[VDF_TAPE_MAX_CONSTS],
                                   vdf_round_tape* out);

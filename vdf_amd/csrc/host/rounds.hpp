@@ -9,8 +9,9 @@ namespace vdfnova {
 
 // What a body did, call by call.  Nodes [0, n_inputs()) are its inputs in the order j, inv, carry, cur, next; every later node is
 // one vdf_cs_* call.  a, b, c name nodes, except: R_CONST a = index into consts; R_SCALE and R_POW b = index into consts (R_POW:
-// the exponent, a plain 256-bit integer, stored like a constant).  R_POW exists in forward bodies only.
-enum RecOp : uint8_t { R_INPUT = 0, R_CONST, R_ADD, R_SUB, R_SCALE, R_MUL, R_ALLOC_FROM, R_ENFORCE, R_POW };
+// the exponent, a plain 256-bit integer, stored like a constant).  R_POWC (vdf_cs_pow_chain): b = index of the first of the
+// constants the packed chain lies in (csrc/pow_chain.h), c = its n_tmp.  R_POW and R_POWC exist in forward bodies only.
+enum RecOp : uint8_t { R_INPUT = 0, R_CONST, R_ADD, R_SUB, R_SCALE, R_MUL, R_ALLOC_FROM, R_ENFORCE, R_POW, R_POWC };
 struct RecNode {
   uint8_t op = R_INPUT;
   bool value_only = false;         // made of advice values: no linear combination stands behind it
@@ -26,6 +27,7 @@ struct RoundRecord {
   // the device program (compile()): inputs loaded at their first use, slots by a linear scan over live ranges
   std::vector<vdf_tape_op> ops;
   uint32_t n_slots = 0;
+  uint32_t chain_tmp = 0;                          // the largest n_tmp of the POWCs the program holds (slots behind the two entries)
 
   uint32_t n_inputs() const { return 1 + n_inv + n_carry + 2 * n_adv; }
   uint32_t in_j() const { return 0; }
@@ -69,7 +71,7 @@ int eval_round_tape(int field, const vdf_round_tape* tape, uint64_t t, const Fe*
 // A walk body (vdf_nova.h vdf_walk_body) run once on a recording handle and compiled into a walk tape: the record has no carry, no
 // variable and no constraint; its n_vars = n_adv columns are the handles the body left in cur_out.
 // forward: the body is a forward body (vdf_nova_forward_body_record): the entry it is handed is entry j, loaded with ADV b = 0, and
-// vdf_cs_pow is legal.
+// vdf_cs_pow and vdf_cs_pow_chain are legal.
 int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out, bool forward = false);
 // vdf_round_tape_walk on the host (vdf_nova_walk_tape_eval): the same arguments, the same refusals, host memory
 int eval_walk_tape(int field, const vdf_round_tape* tape, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* trace, size_t walk_stride,
@@ -129,7 +131,7 @@ struct vdf_cs {
   vdf_ctx* ctx = nullptr;                          // for advice in device memory: the copy of its last entry (null: such advice is refused)
   uint32_t rec_calls = 0;
   bool walk = false;                               // the recording is a walk body's (vdf_nova_walk_body_record): value arithmetic only
-  bool forward = false;                            // ... a forward body's (vdf_nova_forward_body_record): vdf_cs_pow is legal
+  bool forward = false;                            // ... a forward body's (vdf_nova_forward_body_record): vdf_cs_pow / _pow_chain are legal
   const vdf_fe* step_advice = nullptr;             // vdf_cs_step_advice: the device trace of the step a custom chain drives (witness synthesis only)
   size_t step_advice_elems = 0;                    // ... and its length in elements: lanes * (t + 1) * n_adv of the parameters' repeat
 };

@@ -4,8 +4,13 @@
 // advice), and compiled into the slot program libvdf_hip.so runs one repetition per thread (RoundRecord::ops; vdf_round_tape_run).
 #include "nova_internal.hpp"
 #include "rounds.hpp"
+#include "../minroot_chain.h"
+#include "../pow_chain.h"
 
 using namespace vdfnova;
+
+static_assert(VDF_POW_ACC == vdf::MR_ACC && VDF_POW_NONE == vdf::MR_NONE && sizeof(vdf_pow_step) == sizeof(vdf::MinrootChainStep),
+              "vdf_pow_step is minroot_chain.h's step format made public");
 
 namespace {
 constexpr uint32_t REC_TAG = 0x80000000u;        // handles of a recording vdf_cs: REC_TAG | node -- no handle of another vdf_cs looks like one
@@ -47,7 +52,7 @@ int compile_round(RoundRecord& r, const std::vector<uint32_t>* outs = nullptr) {
   auto operands = [&](const RecNode& x, uint32_t out[2]) -> int {
     switch (x.op) {
       case R_ADD: case R_SUB: case R_MUL: out[0] = root[x.a]; out[1] = root[x.b]; return 2;
-      case R_SCALE: case R_ALLOC_FROM: case R_POW: out[0] = root[x.a]; return 1;
+      case R_SCALE: case R_ALLOC_FROM: case R_POW: case R_POWC: out[0] = root[x.a]; return 1;
       default: return 0;                            // inputs, constants; enforce costs the device nothing
     }
   };
@@ -75,6 +80,7 @@ int compile_round(RoundRecord& r, const std::vector<uint32_t>* outs = nullptr) {
     r.ops.push_back(o);
   };
   r.ops.clear();
+  r.chain_tmp = 0;
   uint32_t var = 0;
   auto load_input = [&](uint32_t in) {
     if (in >= nin || slot[in] != NO_SLOT) return;
@@ -100,6 +106,7 @@ int compile_round(RoundRecord& r, const std::vector<uint32_t>* outs = nullptr) {
       case R_SUB: slot[i] = take(); emit(VDF_TAPE_SUB, slot[i], sa, sb); break;
       case R_SCALE: slot[i] = take(); emit(VDF_TAPE_SCALE, slot[i], sa, x.b); break;
       case R_POW: slot[i] = take(); emit(VDF_TAPE_POW, slot[i], sa, x.b); break;
+      case R_POWC: slot[i] = take(); emit(VDF_TAPE_POWC, slot[i], sa, x.b); if (x.c > r.chain_tmp) r.chain_tmp = x.c; break;
       case R_MUL: slot[i] = take(); emit(VDF_TAPE_MUL, slot[i], sa, sb); if (!outs) emit(VDF_TAPE_OUT, 0, slot[i], var++); break;
       default: emit(VDF_TAPE_OUT, 0, sa, var++); break;      // R_ALLOC_FROM
     }
@@ -267,7 +274,7 @@ int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out, bool forw
   if (rc != 0) return fail(VDF_ERR_BAD_ARG, "walk body: the body failed");
   if (h.rec_calls > VDF_ROUND_MAX_OPS) return fail(VDF_ERR_BAD_ARG, "walk body: more than VDF_ROUND_MAX_OPS calls");
   if (r.consts.size() > VDF_ROUND_MAX_CONSTS) return fail(VDF_ERR_BAD_ARG, "walk body: more than VDF_ROUND_MAX_CONSTS constants");
-  if (h.bad) return fail(VDF_ERR_BAD_ARG, "walk body: a handle the body does not own, or a call that is not value arithmetic (alloc, alloc_from, enforce, value, repeat; pow outside a forward body)");
+  if (h.bad) return fail(VDF_ERR_BAD_ARG, "walk body: a handle the body does not own, or a call that is not value arithmetic (alloc, alloc_from, enforce, value, repeat; pow or pow_chain outside a forward body, an invalid chain)");
   std::vector<uint32_t> outs;
   for (uint32_t k = 0; k < r.n_adv; ++k) {
     const long nd = rec_node(&h, hout[k]);
@@ -277,7 +284,8 @@ int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out, bool forw
   r.n_vars = r.n_adv;
   const int crc = compile_round(r, &outs);
   if (crc != VDF_OK) return crc;
-  if (r.n_slots + 2 * r.n_adv > VDF_WALK_MAX_SLOTS) return fail(VDF_ERR_BAD_ARG, "walk body: live values + 2 * n_adv > VDF_WALK_MAX_SLOTS");
+  if (r.n_slots + 2 * r.n_adv + r.chain_tmp > VDF_WALK_MAX_SLOTS)
+    return fail(VDF_ERR_BAD_ARG, "walk body: live values + 2 * n_adv + the chains' temporaries > VDF_WALK_MAX_SLOTS");
   *out = std::move(r);
   return VDF_OK;
 }
@@ -304,6 +312,22 @@ static Fe pow_plain(const Fe& x, const Fe& e, const Field& F) {
   return acc;
 }
 
+// x ^ E(chain): the chain's steps with the host's canonical sqr / mul -- the byte-for-byte reference of k_tape_forward_walk_chain,
+// whose lazy values are these modulo m.  consts[b ..]: a packed chain check_walk_tape has accepted.
+static Fe pow_chain_run(const Fe& x, const Fe* consts, size_t b, const Field& F) {
+  const uint8_t* p = (const uint8_t*)(consts + b);
+  const vdf_pow_step* st = (const vdf_pow_step*)(p + 4);
+  Fe T[VDF_POW_CHAIN_MAX_TMP], v = x;
+  T[0] = x;
+  for (size_t k = 0; k < p[0]; ++k) {
+    if (st[k].src != VDF_POW_ACC) v = T[st[k].src];
+    for (unsigned q = st[k].squarings; q; --q) v = sqr(v, F);
+    if (st[k].mul != VDF_POW_NONE) v = mul(v, T[st[k].mul], F);
+    if (st[k].dst != VDF_POW_NONE) T[st[k].dst] = v;
+  }
+  return v;
+}
+
 // inv_slots: the slots a walk in lanes keeps its lane's inv in (n_inv there, 0 elsewhere), counted against VDF_WALK_MAX_SLOTS
 static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rounds, bool forward = false, bool inv_slots = false) {
   if (!tp || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts)) return fail(VDF_ERR_BAD_ARG, "null tape");
@@ -314,6 +338,7 @@ static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rou
   if (tp->n_inv && !inv) return fail(VDF_ERR_BAD_ARG, "null inv");
   bool written[VDF_TAPE_MAX_SLOTS] = {}, col_out[VDF_TAPE_MAX_ADV] = {};
   uint64_t products = 0;
+  uint32_t chain_tmp = 0;                              // the largest n_tmp of the tape's chains: slots behind the two entries
   for (size_t i = 0; i < tp->n_ops; ++i) {
     const vdf_tape_op& o = tp->ops[i];
     auto rd = [&](uint8_t x) { return x < tp->n_slots && written[x]; };
@@ -331,6 +356,16 @@ static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rou
         ok = forward && rd(o.a) && o.b < tp->n_consts;
         if (ok) products += pow_products(((const Fe*)tp->consts)[o.b]);
         break;
+      case VDF_TAPE_POWC:
+        ok = forward && rd(o.a);
+        if (ok) {
+          vdfpow::ChainInfo ci;
+          const std::string why = vdfpow::check_packed(tp->consts, tp->n_consts, o.b, &ci, nullptr, nullptr);
+          if (!why.empty()) return fail(VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + ": the chain of a POWC: " + why);
+          products += ci.products();
+          if (ci.n_tmp > chain_tmp) chain_tmp = ci.n_tmp;
+        }
+        break;
       default: break;
     }
     if (ok && o.op != VDF_TAPE_OUT) { ok = o.dst < tp->n_slots; if (ok) written[o.dst] = true; }
@@ -338,8 +373,8 @@ static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rou
   }
   for (uint32_t k = 0; k < tp->n_adv; ++k)
     if (!col_out[k]) return fail(VDF_ERR_BAD_ARG, "tape leaves variable " + std::to_string(k) + " unwritten");
-  if (tp->n_slots + 2 * tp->n_adv + (inv_slots ? tp->n_inv : 0) > VDF_WALK_MAX_SLOTS)
-    return fail(VDF_ERR_BAD_ARG, inv_slots ? "walk tape in lanes: n_slots + 2 * n_adv + n_inv > VDF_WALK_MAX_SLOTS" : "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS");
+  if (tp->n_slots + 2 * tp->n_adv + (inv_slots ? tp->n_inv : 0) + chain_tmp > VDF_WALK_MAX_SLOTS)
+    return fail(VDF_ERR_BAD_ARG, chain_tmp ? "forward walk tape: n_slots + 2 * n_adv + the chains' n_tmp > VDF_WALK_MAX_SLOTS" : inv_slots ? "walk tape in lanes: n_slots + 2 * n_adv + n_inv > VDF_WALK_MAX_SLOTS" : "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS");
   if (rounds > (forward ? VDF_FORWARD_TAPE_MAX_WORK : VDF_WALK_MAX_WORK) / (products ? products : 1))
     return fail(VDF_ERR_BAD_ARG, std::string("rounds x products per round > ") + (forward ? "VDF_FORWARD_TAPE_MAX_WORK" : "VDF_WALK_MAX_WORK") + " in one call: cut the walk");
   return VDF_OK;
@@ -445,6 +480,7 @@ int eval_forward_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entr
           case VDF_TAPE_MUL: s[o.dst] = mul(s[o.a], s[o.b], F); break;
           case VDF_TAPE_SCALE: s[o.dst] = mul(s[o.a], consts[o.b], F); break;
           case VDF_TAPE_POW: s[o.dst] = pow_plain(s[o.a], consts[o.b], F); break;
+          case VDF_TAPE_POWC: s[o.dst] = pow_chain_run(s[o.a], consts, o.b, F); break;
           default: prod[o.b] = s[o.a]; break;      // VDF_TAPE_OUT
         }
       }
@@ -648,6 +684,20 @@ vdf_num rec_cs_pow(vdf_cs* c, vdf_num a, const uint64_t e[4]) {
   memcpy(&k, e, 32);
   return rec_push(c, R_POW, false, (uint32_t)x, rec_const(c, &k), 0);
 }
+// the chain goes into the constants as vdf_hip.h lays it out: pow_chain.h packs it, and checks it first
+vdf_num rec_cs_pow_chain(vdf_cs* c, vdf_num a, const vdf_pow_step* steps, size_t n_steps) {
+  if (!c->forward) { c->bad = true; return 0; }
+  vdfpow::ChainInfo ci;
+  if (!vdfpow::check(steps, n_steps, 0, &ci).empty()) { c->bad = true; return 0; }
+  const long x = rec_node(c, a);
+  if (x < 0) return 0;
+  vdf_fe k[(4 + 4 * VDF_POW_CHAIN_MAX_STEPS + 31) / 32];
+  vdfpow::pack(steps, n_steps, ci.n_tmp, (uint8_t*)k);
+  const size_t nk = vdfpow::packed_consts(n_steps);
+  const uint32_t first = rec_const(c, &k[0]);
+  for (size_t q = 1; q < nk; ++q) rec_const(c, &k[q]);
+  return rec_push(c, R_POWC, false, (uint32_t)x, first, ci.n_tmp);
+}
 int rec_cs_enforce(vdf_cs* c, vdf_num a, vdf_num b, vdf_num cc) {
   if (c->walk) { c->bad = true; return VDF_ERR_BAD_ARG; }      // a walk body computes values: it has nothing to constrain
   const long x = rec_node(c, a), y = rec_node(c, b), z = rec_node(c, cc);
@@ -693,6 +743,80 @@ vdf_num vdf_cs_pow(vdf_cs* c, vdf_num a, const uint64_t e[4]) {
   if (c->rec) return rec_cs_pow(c, a, e);
   c->bad = true;                                       // value arithmetic of a forward body only
   return 0;
+}
+
+vdf_num vdf_cs_pow_chain(vdf_cs* c, vdf_num a, const vdf_pow_step* steps, size_t n_steps) {
+  if (!c) return 0;
+  if (c->rec) return rec_cs_pow_chain(c, a, steps, n_steps);
+  c->bad = true;                                       // value arithmetic of a forward body only
+  return 0;
+}
+
+int vdf_nova_pow_chain_exponent(const vdf_pow_step* steps, size_t n_steps, uint64_t e[4], uint32_t* n_tmp, uint64_t* products) {
+  return nova_guard([&]() -> int {
+    vdfpow::ChainInfo ci;
+    const std::string why = vdfpow::check(steps, n_steps, 0, &ci);
+    if (!why.empty()) return fail(VDF_ERR_BAD_ARG, "vdf_nova_pow_chain_exponent: " + why);
+    if (e) memcpy(e, ci.e.l, 32);
+    if (n_tmp) *n_tmp = ci.n_tmp;
+    if (products) *products = ci.products();
+    return VDF_OK;
+  });
+}
+
+// Left to right, sliding windows of at most `window` bits that begin and end in a one.  The table first: T[1] = x^2, then T[1 + k]
+// = x^(2k + 1) = T[k] * T[1] for k = 1 .. 2^(window - 1) - 1 (T[0] = x), whether the exponent uses every entry or not -- one squaring
+// and 2^(window - 1) - 1 products.  Then one step per window: the squarings since the window before, and the product by the window's
+// odd value; the first window only names the temporary the accumulator starts from, and zeros at the bottom are a last step of
+// squarings alone.
+int vdf_nova_pow_chain_window(const uint64_t e[4], unsigned window, vdf_pow_step* steps, size_t cap, size_t* n_steps) {
+  return nova_guard([&]() -> int {
+    if (!e || !steps || !n_steps) return fail(VDF_ERR_BAD_ARG, "vdf_nova_pow_chain_window: null argument");
+    if (window < 2 || window > 4) return fail(VDF_ERR_BAD_ARG, "vdf_nova_pow_chain_window: window must be 2 .. 4");
+    vdfpow::U256 E;
+    memcpy(E.l, e, 32);
+    const int bits = (int)vdfpow::bitlen(E);
+    if (bits == 0) return fail(VDF_ERR_BAD_ARG, "vdf_nova_pow_chain_window: e = 0 has no chain");
+    auto bit = [&](int i) { return (unsigned)((E.l[i / 64] >> (i % 64)) & 1); };
+    std::vector<vdf_pow_step> out;
+    out.push_back(vdf_pow_step{0, 1, VDF_POW_NONE, 1});
+    for (unsigned k = 1; k < (1u << (window - 1)); ++k) out.push_back(vdf_pow_step{VDF_POW_ACC, 0, (uint8_t)(k == 1 ? 0 : 1), (uint8_t)(1 + k)});
+    auto slot_of = [](unsigned odd) { return (uint8_t)(odd == 1 ? 0 : (odd + 1) / 2); };
+    uint8_t src = VDF_POW_ACC;                         // the first window: where the accumulator starts
+    unsigned pending = 0;
+    bool first = true;
+    for (int i = bits - 1; i >= 0;) {
+      if (!bit(i)) { ++pending; --i; continue; }
+      int lo = i - (int)window + 1 > 0 ? i - (int)window + 1 : 0;
+      while (!bit(lo)) ++lo;
+      unsigned val = 0;
+      for (int q = i; q >= lo; --q) val = 2 * val + bit(q);
+      if (first) { src = slot_of(val); first = false; }
+      else {
+        out.push_back(vdf_pow_step{src, (uint8_t)(pending + (unsigned)(i - lo + 1)), slot_of(val), VDF_POW_NONE});
+        src = VDF_POW_ACC; pending = 0;
+      }
+      i = lo - 1;
+    }
+    if (pending || src != VDF_POW_ACC) out.push_back(vdf_pow_step{src, (uint8_t)pending, VDF_POW_NONE, VDF_POW_NONE});
+    if (out.size() > cap || out.size() > VDF_POW_CHAIN_MAX_STEPS)
+      return fail(VDF_ERR_BAD_LENGTH, "vdf_nova_pow_chain_window: the chain has " + std::to_string(out.size()) + " steps: more than cap or VDF_POW_CHAIN_MAX_STEPS");
+    memcpy(steps, out.data(), out.size() * sizeof(vdf_pow_step));
+    *n_steps = out.size();
+    return VDF_OK;
+  });
+}
+
+int vdf_minroot_pow_chain(int fid, vdf_pow_step* steps, size_t cap, size_t* n_steps) {
+  return nova_guard([&]() -> int {
+    if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
+    if (!steps || !n_steps) return fail(VDF_ERR_BAD_ARG, "vdf_minroot_pow_chain: null argument");
+    const vdf::MinrootChainProgram& p = fid == VDF_FIELD_FQ ? vdf::MINROOT_CHAIN_FQ : vdf::MINROOT_CHAIN_FP;
+    if (cap < vdf::MINROOT_CHAIN_MAX_STEPS) return fail(VDF_ERR_BAD_LENGTH, "vdf_minroot_pow_chain: the programs have 32 steps");
+    memcpy(steps, p.step, sizeof(p.step));             // (padded to 32 with steps that do nothing)
+    *n_steps = vdf::MINROOT_CHAIN_MAX_STEPS;
+    return VDF_OK;
+  });
 }
 
 int vdf_cs_repeat(vdf_cs* c, const vdf_round_body* b, uint64_t t, const vdf_num* inv, const vdf_num* carry_in, const vdf_fe* advice,

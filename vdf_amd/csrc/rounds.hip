@@ -11,6 +11,7 @@
 #include <cstring>
 #include "internal.h"
 #include "fe.cuh"
+#include "pow_chain.h"
 
 namespace vdf {
 
@@ -377,6 +378,113 @@ __global__ __launch_bounds__(64) void k_tape_forward_walk(TapeArgs tape, Forward
   for (uint32_t c = 0; c < na; ++c) fe_store<P>(ep + c * 32, slot_load<P>(tape_slots, stand + c, lane));
 }
 
+// k_tape_forward_walk for a tape that holds a VDF_TAPE_POWC (vdf_hip.h): the same launch, the same interpreter, binary POW still
+// accepted, and one more case -- a power by a caller-supplied addition chain, interpreted as k_forward_walk (minroot.hip) interprets
+// the built-in one.  The accumulator stays in registers; the chain's temporaries are n_tmp more lane-private slots of LDS behind the
+// two entries, same [slot][half][lane] layout, indexed by scalars.  The step words and the trip counts come from tape.consts by
+// scalar loads (the chain is the same for every lane), so every branch is wave-uniform.  ONE squaring site and ONE product site,
+// both in loops: the chain is not inlined.  Nothing private is indexed by a run-time value.
+//
+// Bound: inside a chain the values are in the lazy domain of fe.cuh.  The base is canonical (every slot is).  A lazy square or
+// product of operands below 2m + k eps is below 2m + (k + 1) eps.  On any path from the base to a value every squaring doubles the
+// exponent and every product raises it, and a valid chain's exponents stay below 2^256: at most 255 squarings; a path passes a step
+// at most once: at most 95 products.  So every value stays below 2m + 350 eps < 2^256 (eps ~ 2^126), the GENERAL lazy forms apply
+// (the _t31 forms carry a nine-product bound that a chain exceeds), and fe_canon's two subtractions make the result canonical.
+template <class P>
+__global__ __launch_bounds__(64) void k_tape_forward_walk_chain(TapeArgs tape, ForwardArgs fa, char* __restrict__ entries,
+                                                                char* __restrict__ checkpoints, char* __restrict__ trace) {
+  extern __shared__ uint4 tape_slots[];
+  const uint32_t lane = threadIdx.x;
+  const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
+  if (w >= fa.n) return;                             // (no barrier below: a lane touches only its own words of LDS)
+  const uint32_t na = tape.n_adv;
+  const size_t esz = (size_t)na * 32;
+  char* const ep = entries + w * esz;
+  uint32_t stand = fa.n_slots, prod = fa.n_slots + na;
+  const uint32_t tmp0 = fa.n_slots + 2 * na;         // T[0] of a chain
+  const uint32_t* const cwords = &tape.consts[0].v[0];
+  for (uint32_t c = 0; c < na; ++c) slot_store<P>(tape_slots, stand + c, lane, fe_load<P>(ep + c * 32));
+  char* tp = trace ? trace + (w * fa.walk_stride + fa.base + 1) * esz : nullptr;
+  uint64_t cp_left = checkpoints ? fa.every - fa.base % fa.every : 0;
+  char* cp = checkpoints ? checkpoints + (w * fa.cp_stride + fa.base / fa.every + 1) * esz : nullptr;
+  uint64_t j = fa.j_base + w * fa.j_walk_step + fa.base;
+#pragma unroll 1
+  for (uint32_t r = 0; r < fa.rounds; ++r, ++j) {
+#pragma unroll 1
+    for (uint32_t i = 0; i < tape.n_ops; ++i) {
+      const uint32_t x = tape.ops[i];
+      const uint32_t op = x & 0xFF, dst = (x >> 8) & 0xFF, a = (x >> 16) & 0xFF, b = x >> 24;
+      Fe<P> v;
+      switch (op) {
+        case VDF_TAPE_ADV: v = slot_load<P>(tape_slots, stand + a, lane); break;      // (the launcher admits b = 0 only)
+        case VDF_TAPE_INV: v = tape_fe<P>(tape.inv[a]); break;
+        case VDF_TAPE_J: v = fe_from_u64<P>(j); break;
+        case VDF_TAPE_CONST: v = tape_fe<P>(tape.consts[a]); break;
+        case VDF_TAPE_ADD: v = fe_add(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
+        case VDF_TAPE_SUB: v = fe_sub(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
+        case VDF_TAPE_MUL: {
+          const Fe<P> y = slot_load<P>(tape_slots, a, lane);
+          v = a == b ? fe_sqr(y) : fe_mul(y, slot_load<P>(tape_slots, b, lane));
+          break;
+        }
+        case VDF_TAPE_SCALE: v = fe_mul(slot_load<P>(tape_slots, a, lane), tape_fe<P>(tape.consts[b])); break;
+        case VDF_TAPE_POW: {
+          uint32_t q = 8, word = 0;                    // words of the exponent still to read, and the one being read
+          while (q && (word = tape.consts[b].v[q - 1]) == 0) --q;
+          if (q == 0) { v = fe_one<P>(); break; }      // E = 0
+          const Fe<P> y = slot_load<P>(tape_slots, a, lane);
+          v = y;                                       // the top set bit
+          int bit = 31 - __builtin_clz(word);
+          for (;;) {
+#pragma unroll 1
+            while (bit-- > 0) {
+              v = fe_sqr(v);
+              if ((word >> bit) & 1) v = fe_mul(v, y);
+            }
+            if (--q == 0) break;
+            word = tape.consts[b].v[q - 1];
+            bit = 32;
+          }
+          break;
+        }
+        case VDF_TAPE_POWC: {
+          const uint32_t* const cw = cwords + b * 8;   // word 0: n_steps | n_tmp << 8; word 1 + k: step k (the launcher checked all)
+          const uint32_t n_steps = cw[0] & 0xFF;
+          v = slot_load<P>(tape_slots, a, lane);
+          slot_store<P>(tape_slots, tmp0, lane, v);    // T[0] = the base
+#pragma unroll 1
+          for (uint32_t k = 0; k < n_steps; ++k) {
+            const uint32_t st = cw[1 + k];
+            const uint32_t src = st & 0xFF, mul = (st >> 16) & 0xFF, keep = st >> 24;
+            if (src != VDF_POW_ACC) v = slot_load<P>(tape_slots, tmp0 + src, lane);
+#pragma unroll 1
+            for (uint32_t q = (st >> 8) & 0xFF; q; --q) v = fe_sqr_lazy(v);
+            if (mul != VDF_POW_NONE) v = fe_mul_lazy(v, slot_load<P>(tape_slots, tmp0 + mul, lane));
+            if (keep != VDF_POW_NONE) slot_store<P>(tape_slots, tmp0 + keep, lane, v);
+          }
+          v = fe_canon(v);                             // below 2m + 350 eps (above): two conditional subtractions
+          break;
+        }
+        default:                       // VDF_TAPE_OUT
+          slot_store<P>(tape_slots, prod + b, lane, slot_load<P>(tape_slots, a, lane));
+          continue;
+      }
+      slot_store<P>(tape_slots, dst, lane, v);
+    }
+    const uint32_t t = stand; stand = prod; prod = t;
+    if (tp) {
+      for (uint32_t c = 0; c < na; ++c) fe_store<P>(tp + c * 32, slot_load<P>(tape_slots, stand + c, lane));
+      tp += esz;
+    }
+    if (cp && --cp_left == 0) {
+      for (uint32_t c = 0; c < na; ++c) fe_store<P>(cp + c * 32, slot_load<P>(tape_slots, stand + c, lane));
+      cp += esz;
+      cp_left = fa.every;
+    }
+  }
+  for (uint32_t c = 0; c < na; ++c) fe_store<P>(ep + c * 32, slot_load<P>(tape_slots, stand + c, lane));
+}
+
 // ---- periodic rows: the cross term of the rows of such rounds without the sparse matrices (vdf_hip.h vdf_periodic_rows) --------
 // k_nifs_cross_minroot_forward_lanes for a round the library did not write: one row per lane, workgroups of 256, every running /
 // fresh vector read and written as contiguous 32-byte elements.  What the hand-written stencil has in its code -- which columns a
@@ -488,11 +596,14 @@ static uint64_t pow_products(const TapeFe& e) {
 // Everything a tape could index out of range is checked here, before a launch: opcodes, slots against n_slots, columns,
 // constants, invariants and variables against their counts, reads of slots nothing has written, variables written twice or never.
 // TAPE_WALK / TAPE_FORWARD: the rules of a walk tape on top (vdf_hip.h): n_vars == n_adv, no ADV of the entry being produced
-// (b = 0 descending, b = 1 ascending).  VDF_TAPE_POW is an op of forward tapes only.  products (if asked for): the field products of
-// one round, a POW counted as its squarings and multiplications.
+// (b = 0 descending, b = 1 ascending).  VDF_TAPE_POW and VDF_TAPE_POWC are ops of forward tapes only.  products (if asked for): the
+// field products of one round, a POW or POWC counted as its squarings and multiplications.  A POWC's chain is checked by
+// pow_chain.h (valid, inside n_consts, zero padding); chain_tmp (if asked for): the largest n_tmp of the tape's chains, 0 for a
+// tape without a POWC -- the slots k_tape_forward_walk_chain keeps behind the two entries.
 enum TapeMode { TAPE_ROUND, TAPE_WALK, TAPE_FORWARD };
 // lanes: inv holds lanes * n_inv elements, lane-major; all of them go into the block of VDF_TAPE_MAX_INV (the *_lanes launchers).
-static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, TapeMode mode, TapeArgs& a, uint64_t* products = nullptr, size_t lanes = 1) {
+static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, TapeMode mode, TapeArgs& a, uint64_t* products = nullptr, size_t lanes = 1,
+                        uint32_t* chain_tmp = nullptr) {
   const bool walk = mode != TAPE_ROUND;
   if (!tp || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts)) return Status{VDF_ERR_BAD_ARG, "null tape"};
   if (tp->n_ops > VDF_TAPE_MAX_OPS || tp->n_consts > VDF_TAPE_MAX_CONSTS || tp->n_slots > VDF_TAPE_MAX_SLOTS || tp->n_vars > VDF_TAPE_MAX_VARS ||
@@ -506,6 +617,7 @@ static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, TapeMode mo
   a.n_ops = (uint32_t)tp->n_ops; a.n_vars = tp->n_vars; a.n_adv = tp->n_adv;
   bool written[VDF_TAPE_MAX_SLOTS] = {}, var_out[VDF_TAPE_MAX_VARS] = {};
   uint64_t n_products = 0;
+  uint32_t max_tmp = 0;
   for (size_t i = 0; i < tp->n_ops; ++i) {
     const vdf_tape_op& o = tp->ops[i];
     auto slot_ok = [&](uint8_t x) { return x < tp->n_slots && written[x]; };
@@ -523,6 +635,16 @@ static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, TapeMode mo
         ok = mode == TAPE_FORWARD && slot_ok(o.a) && o.b < tp->n_consts;
         if (ok) n_products += pow_products(tape_val(&tp->consts[o.b]));
         break;
+      case VDF_TAPE_POWC:
+        ok = mode == TAPE_FORWARD && slot_ok(o.a);
+        if (ok) {
+          vdfpow::ChainInfo ci;
+          const std::string why = vdfpow::check_packed(tp->consts, tp->n_consts, o.b, &ci, nullptr, nullptr);
+          if (!why.empty()) return Status{VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + ": the chain of a POWC: " + why};
+          n_products += ci.products();
+          if (ci.n_tmp > max_tmp) max_tmp = ci.n_tmp;
+        }
+        break;
       default: break;
     }
     if (ok && o.op != VDF_TAPE_OUT) { ok = o.dst < tp->n_slots; if (ok) written[o.dst] = true; }
@@ -536,6 +658,7 @@ static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, TapeMode mo
   for (size_t k = 0; k < tp->n_consts; ++k) a.consts[k] = tape_val(&tp->consts[k]);
   for (size_t k = 0; k < lanes * tp->n_inv; ++k) a.inv[k] = tape_val(&inv[k]);
   if (products) *products = n_products ? n_products : 1;
+  if (chain_tmp) *chain_tmp = max_tmp;
   return Status{};
 }
 
@@ -645,9 +768,10 @@ Status vec_round_tape_walk_lanes(int field, const vdf_round_tape* tp, size_t lan
 Status round_tape_forward_max_rounds(const vdf_round_tape* tp, const vdf_fe* inv, uint64_t* max_rounds) {
   TapeArgs a;
   uint64_t products = 1;
-  VDF_TRY(pack_tape(tp, inv, TAPE_FORWARD, a, &products));
-  if (tp->n_slots + 2 * tp->n_adv > VDF_WALK_MAX_SLOTS)
-    return Status{VDF_ERR_BAD_ARG, "forward walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"};
+  uint32_t chain_tmp = 0;
+  VDF_TRY(pack_tape(tp, inv, TAPE_FORWARD, a, &products, 1, &chain_tmp));
+  if (tp->n_slots + 2 * tp->n_adv + chain_tmp > VDF_WALK_MAX_SLOTS)
+    return Status{VDF_ERR_BAD_ARG, "forward walk tape: n_slots + 2 * n_adv + the chains' n_tmp > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"};
   *max_rounds = VDF_FORWARD_TAPE_MAX_WORK / products;
   return Status{};
 }
@@ -658,9 +782,10 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tp, const vd
   VDF_TRY(check_field(field));
   TapeArgs a;
   uint64_t products = 1;
-  VDF_TRY(pack_tape(tp, inv, TAPE_FORWARD, a, &products));
-  if (tp->n_slots + 2 * tp->n_adv > VDF_WALK_MAX_SLOTS)
-    return Status{VDF_ERR_BAD_ARG, "forward walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"};
+  uint32_t chain_tmp = 0;                            // > 0: the tape holds a POWC
+  VDF_TRY(pack_tape(tp, inv, TAPE_FORWARD, a, &products, 1, &chain_tmp));
+  if (tp->n_slots + 2 * tp->n_adv + chain_tmp > VDF_WALK_MAX_SLOTS)
+    return Status{VDF_ERR_BAD_ARG, "forward walk tape: n_slots + 2 * n_adv + the chains' n_tmp > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"};
   if (rounds > VDF_FORWARD_TAPE_MAX_WORK / products)
     return Status{VDF_ERR_BAD_ARG, "rounds x products per round > VDF_FORWARD_TAPE_MAX_WORK in one call: cut the walk"};
   if (checkpoints && every == 0) return Status{VDF_ERR_BAD_ARG, "checkpoints without `every`"};
@@ -672,11 +797,18 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tp, const vd
   fa.n = n; fa.walk_stride = walk_stride; fa.cp_stride = cp_stride; fa.every = every; fa.base = base;
   fa.j_base = j_base; fa.j_walk_step = j_walk_step;
   fa.rounds = (uint32_t)rounds; fa.n_slots = tp->n_slots;
-  KTimer kt(s, "k_tape_forward_walk", (trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0) + 64.0 * tp->n_adv * (double)n);
-  const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv) * 2 * 64 * sizeof(uint4);
+  KTimer kt(s, chain_tmp ? "k_tape_forward_walk_chain" : "k_tape_forward_walk",
+            (trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0) + 64.0 * tp->n_adv * (double)n);
+  const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv + chain_tmp) * 2 * 64 * sizeof(uint4);
+  const dim3 grid((unsigned)((n + 63) / 64));
+  if (chain_tmp)        // a tape with a POWC: the interpreter that also runs addition chains; every other tape: the kernel as it was
+    return with_field(field, [&](auto f) {
+      hipLaunchKernelGGL((k_tape_forward_walk_chain<tag_t<decltype(f)>>), grid, dim3(64), lds, s, a, fa, bytes_of(entries), bytes_of(checkpoints),
+                         bytes_of(trace));
+    });
   return with_field(field, [&](auto f) {
-    hipLaunchKernelGGL((k_tape_forward_walk<tag_t<decltype(f)>>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, fa, bytes_of(entries),
-                       bytes_of(checkpoints), bytes_of(trace));
+    hipLaunchKernelGGL((k_tape_forward_walk<tag_t<decltype(f)>>), grid, dim3(64), lds, s, a, fa, bytes_of(entries), bytes_of(checkpoints),
+                       bytes_of(trace));
   });
 }
 

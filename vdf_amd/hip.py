@@ -62,6 +62,7 @@ WALK_MAX_SLOTS, WALK_MAX_WORK = 32, 1 << 23        # VDF_WALK_MAX_SLOTS, VDF_WAL
 TAPE_MAX_LANES = 16                                # VDF_TAPE_MAX_LANES
 FORWARD_TAPE_MAX_WORK = 1 << 20                    # VDF_FORWARD_TAPE_MAX_WORK
 TAPE_POW = 9                                       # VDF_TAPE_POW
+TAPE_POWC = 10                                     # VDF_TAPE_POWC
 
 
 class RoundTape:

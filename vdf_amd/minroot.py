@@ -49,11 +49,22 @@ for _name, _args in {
     "vdf_minroot_inverse_eval": [_i, C.POINTER(_State), _u64, C.POINTER(_State)],
     "vdf_minroot_check": [_i, C.POINTER(_State), _u64, C.POINTER(_State)],
     "vdf_minroot_element": [_i, _u64, C.POINTER(_Fe)],
+    "vdf_minroot_pow_chain": [_i, _vp, _sz, C.POINTER(_sz)],
 }.items():
     getattr(nova_lib, _name).argtypes = _args
     getattr(nova_lib, _name).restype = _i
 nova_lib.vdf_nova_last_error.restype = C.c_char_p
 nova_lib.vdf_nova_last_error.argtypes = []
+
+
+def pow_chain(field: int):
+    """vdf_minroot_pow_chain: the library's own addition chain for the fifth root of `field`, [(src, squarings, mul, dst)] -- what
+    ConstraintSystem.pow_chain takes, so that a MinRoot forward body runs the reference's chain without restating it."""
+    arr, n = (C.c_uint8 * (4 * 32))(), C.c_size_t()
+    rc = nova_lib.vdf_minroot_pow_chain(field, arr, 32, C.byref(n))
+    if rc != 0:
+        raise ValueError("vdf_minroot_pow_chain: %s" % nova_lib.vdf_nova_last_error().decode())
+    return [tuple(arr[4 * k:4 * k + 4]) for k in range(n.value)]
 
 
 def _modulus(field: int) -> int:

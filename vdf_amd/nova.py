@@ -102,6 +102,9 @@ for _name, _res, _args in [
     ("vdf_nova_round_tape_eval_lanes", _i, [_i, _vp, _u64, _sz, _vp, _vp, _sz, _vp]),
     ("vdf_nova_walk_tape_eval_lanes", _i, [_i, _vp, _sz, _vp, _vp, _sz, _u64, _vp, _sz, _sz, _sz, _sz, _vp, _u64, _i, _vp, _vp]),
     ("vdf_cs_pow", C.c_uint32, [_vp, C.c_uint32, _vp]),
+    ("vdf_cs_pow_chain", C.c_uint32, [_vp, C.c_uint32, _vp, _sz]),
+    ("vdf_nova_pow_chain_exponent", _i, [_vp, _sz, _vp, C.POINTER(C.c_uint32), C.POINTER(_u64)]),
+    ("vdf_nova_pow_chain_window", _i, [_vp, C.c_uint, _vp, _sz, C.POINTER(_sz)]),
     ("vdf_nova_forward_body_record", _i, [_i, _vp, _vp, _vp, _vp]),
     ("vdf_nova_forward_tape_eval", _i, [_i, _vp, _vp, _vp, _sz, _u64, _vp, _u64, _sz, _vp, _sz, _u64, _u64, _u64]),
     ("vdf_nova_synthesis_stats", _i, [C.POINTER(_u64), C.POINTER(_u64)]),
@@ -561,6 +564,37 @@ def forward_tape_eval(field: int, tape: RoundTape, inv, entries: np.ndarray, n: 
                                                trace.ctypes.data if trace is not None else None, walk_stride, base, j_base, j_walk_step))
 
 
+POW_ACC, POW_NONE, POW_CHAIN_MAX_STEPS, POW_CHAIN_MAX_TMP = 0xFE, 0xFF, 95, 12      # VDF_POW_*
+
+
+def _pow_steps(steps):
+    """[(src, squarings, mul, dst)] -> a ctypes array of vdf_pow_step (one spare element, so that no chain is a null pointer)"""
+    arr = (C.c_uint8 * (4 * (len(steps) + 1)))()
+    for k, st in enumerate(steps):
+        if len(st) != 4 or any(not 0 <= int(v) <= 255 for v in st):
+            raise ValueError("a step is (src, squarings, mul, dst), each a byte")
+        arr[4 * k:4 * k + 4] = [int(v) for v in st]
+    return arr
+
+
+def pow_chain_exponent(steps):
+    """Host only (vdf_nova_pow_chain_exponent): validates the chain and returns (E, n_tmp, products); VdfError(BAD_ARG) names the
+    step of an invalid one."""
+    e, n_tmp, products = (C.c_uint64 * 4)(), C.c_uint32(), C.c_uint64()
+    _check(nova_lib.vdf_nova_pow_chain_exponent(_pow_steps(steps), len(steps), e, C.byref(n_tmp), C.byref(products)))
+    return sum(int(e[k]) << (64 * k) for k in range(4)), n_tmp.value, products.value
+
+
+def pow_chain_window(e: int, window: int = 4, cap: int = POW_CHAIN_MAX_STEPS):
+    """Host only (vdf_nova_pow_chain_window): a left-to-right sliding-window chain for any exponent 1 <= e < 2^256, as a list of
+    (src, squarings, mul, dst); window 2 .. 4."""
+    if not 0 <= e < 1 << 256:
+        raise ValueError("the exponent is an integer in [0, 2^256)")
+    arr, n = (C.c_uint8 * (4 * (cap + 1)))(), C.c_size_t()
+    _check(nova_lib.vdf_nova_pow_chain_window((C.c_uint64 * 4)(*[(e >> (64 * k)) & (2**64 - 1) for k in range(4)]), window, arr, cap, C.byref(n)))
+    return [tuple(arr[4 * k:4 * k + 4]) for k in range(n.value)]
+
+
 class ConstraintSystem:
     """The vdf_cs a step circuit's synthesize receives: numbers are opaque handles; field elements cross as 32-byte
     Montgomery limbs of the primary circuit's field (Fq, or Fp under public_params_custom(..., field=FIELD_FP))."""
@@ -596,6 +630,13 @@ class ConstraintSystem:
         if not 0 <= e < 1 << 256:
             raise ValueError("the exponent is an integer in [0, 2^256)")
         return nova_lib.vdf_cs_pow(self.h, a, (C.c_uint64 * 4)(*[(e >> (64 * k)) & (2**64 - 1) for k in range(4)]))
+
+    def pow_chain(self, a: int, steps) -> int:
+        """a ^ E by the caller's addition chain: steps = [(src, squarings, mul, dst)] (include/vdf_hip.h vdf_pow_step; POW_ACC /
+        POW_NONE), E its exponent (pow_chain_exponent).  Value arithmetic of a forward body only, as `pow`; anywhere else, and for
+        an invalid chain, the failure flag."""
+        arr = _pow_steps(steps)
+        return nova_lib.vdf_cs_pow_chain(self.h, a, arr, len(steps))
 
     def enforce(self, a: int, b: int, c: int) -> None:
         _check(nova_lib.vdf_cs_enforce(self.h, a, b, c))
