@@ -5,7 +5,7 @@
 #include "nova_internal.hpp"
 #include "rounds.hpp"
 #include "../minroot_chain.h"
-#include "../pow_chain.h"
+#include "../tape_rules.h"
 
 using namespace vdfnova;
 
@@ -195,44 +195,76 @@ void replay_round(CS& cs, const RoundRecord& r, uint64_t j, const std::vector<Nu
   for (uint32_t k = 0; k < r.n_carry; ++k) carry[k] = v[r.carry_out[k]];
 }
 
+// ---- the host interpreter of round tapes: a restatement of rounds.hip's tape_round that shares no text with it (the GPU tests
+// compare the device's bytes with this), only the rules: a tape is checked ONCE by tape_rules.h, then run without looking again.
+static int check_tape(const vdf_round_tape* tp, vdftape::Mode mode, vdftape::Info* info = nullptr) {
+  const std::string why = vdftape::check(tp, mode, info);
+  return why.empty() ? VDF_OK : fail(VDF_ERR_BAD_ARG, why);
+}
+
+// x ^ e, e a plain integer: left to right from the top set bit, as the kernel does it (any order gives the same canonical value)
+static Fe pow_plain(const Fe& x, const Fe& e, const Field& F) {
+  int q = 3;
+  while (q >= 0 && e.l[q] == 0) --q;
+  if (q < 0) return one(F);
+  Fe acc = x;
+  for (int bit = 62 - __builtin_clzll(e.l[q]); q >= 0; --q, bit = 63)
+    for (; bit >= 0; --bit) {
+      acc = sqr(acc, F);
+      if ((e.l[q] >> bit) & 1) acc = mul(acc, x, F);
+    }
+  return acc;
+}
+
+// x ^ E(chain): the chain's steps with the host's canonical sqr / mul -- the byte-for-byte reference of k_tape_forward_walk_chain,
+// whose lazy values are these modulo m.  consts[b ..]: a packed chain tape_rules.h has accepted.
+static Fe pow_chain_run(const Fe& x, const Fe* consts, size_t b, const Field& F) {
+  const uint8_t* p = (const uint8_t*)(consts + b);
+  const vdf_pow_step* st = (const vdf_pow_step*)(p + 4);
+  Fe T[VDF_POW_CHAIN_MAX_TMP], v = x;
+  T[0] = x;
+  for (size_t k = 0; k < p[0]; ++k) {
+    if (st[k].src != VDF_POW_ACC) v = T[st[k].src];
+    for (unsigned q = st[k].squarings; q; --q) v = sqr(v, F);
+    if (st[k].mul != VDF_POW_NONE) v = mul(v, T[st[k].mul], F);
+    if (st[k].dst != VDF_POW_NONE) T[st[k].dst] = v;
+  }
+  return v;
+}
+
+// One round of a checked tape over the slot file s.  adv[b]: the advice entry an ADV with that b reads (the rules admit one b only
+// in a walk: the entry stood on); out: where OUT writes (the repetition's variables, or the entry a walk's round produces).
+static void run_tape_round(const vdf_round_tape* tp, const Field& F, uint64_t j, const Fe* inv, const Fe* const adv[2], Fe* s, Fe* out) {
+  const Fe* consts = (const Fe*)tp->consts;
+  for (size_t i = 0; i < tp->n_ops; ++i) {
+    const vdf_tape_op& o = tp->ops[i];
+    switch (o.op) {
+      case VDF_TAPE_ADV: s[o.dst] = adv[o.b][o.a]; break;
+      case VDF_TAPE_INV: s[o.dst] = inv[o.a]; break;
+      case VDF_TAPE_J: s[o.dst] = from_u64(j, F); break;
+      case VDF_TAPE_CONST: s[o.dst] = consts[o.a]; break;
+      case VDF_TAPE_ADD: s[o.dst] = add(s[o.a], s[o.b], F); break;
+      case VDF_TAPE_SUB: s[o.dst] = sub(s[o.a], s[o.b], F); break;
+      case VDF_TAPE_MUL: s[o.dst] = mul(s[o.a], s[o.b], F); break;
+      case VDF_TAPE_SCALE: s[o.dst] = mul(s[o.a], consts[o.b], F); break;
+      case VDF_TAPE_POW: s[o.dst] = pow_plain(s[o.a], consts[o.b], F); break;
+      case VDF_TAPE_POWC: s[o.dst] = pow_chain_run(s[o.a], consts, o.b, F); break;
+      default: out[o.b] = s[o.a]; break;      // VDF_TAPE_OUT
+    }
+  }
+}
+
 int eval_round_tape(int fid, const vdf_round_tape* tp, uint64_t t, const Fe* inv, const Fe* advice, Fe* out) {
   if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
   if (!tp || !out || !advice || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts) || (tp->n_inv && !inv)) return fail(VDF_ERR_BAD_ARG, "null argument");
   if (t == 0 || t >= (1ull << 31)) return fail(VDF_ERR_BAD_LENGTH, "t out of range");
-  if (tp->n_ops > VDF_TAPE_MAX_OPS || tp->n_consts > VDF_TAPE_MAX_CONSTS || tp->n_slots > VDF_TAPE_MAX_SLOTS || tp->n_vars > VDF_TAPE_MAX_VARS ||
-      tp->n_inv > VDF_TAPE_MAX_INV || tp->n_adv > VDF_TAPE_MAX_ADV || tp->n_vars == 0 || tp->n_adv == 0 || tp->n_slots == 0)
-    return fail(VDF_ERR_BAD_ARG, "tape exceeds a published cap (VDF_TAPE_MAX_*), or has no variable, slot or advice column");
+  const int rc = check_tape(tp, vdftape::ROUND);
+  if (rc != VDF_OK) return rc;
   const Field& F = field(fid);
-  const Fe* consts = (const Fe*)tp->consts;
   Fe s[VDF_TAPE_MAX_SLOTS];
   for (uint64_t j = 0; j < t; ++j) {
-    bool written[VDF_TAPE_MAX_SLOTS] = {}, var_out[VDF_TAPE_MAX_VARS] = {};
-    const Fe* adv = advice + j * tp->n_adv;
-    for (size_t i = 0; i < tp->n_ops; ++i) {
-      const vdf_tape_op& o = tp->ops[i];
-      auto rd = [&](uint8_t x) { return x < tp->n_slots && written[x]; };
-      bool ok = false;
-      Fe r = zero();
-      switch (o.op) {
-        case VDF_TAPE_ADV: ok = o.a < tp->n_adv && o.b <= 1; if (ok) r = adv[o.b * tp->n_adv + o.a]; break;
-        case VDF_TAPE_INV: ok = o.a < tp->n_inv; if (ok) r = inv[o.a]; break;
-        case VDF_TAPE_J: ok = true; r = from_u64(j, F); break;
-        case VDF_TAPE_CONST: ok = o.a < tp->n_consts; if (ok) r = consts[o.a]; break;
-        case VDF_TAPE_ADD: ok = rd(o.a) && rd(o.b); if (ok) r = add(s[o.a], s[o.b], F); break;
-        case VDF_TAPE_SUB: ok = rd(o.a) && rd(o.b); if (ok) r = sub(s[o.a], s[o.b], F); break;
-        case VDF_TAPE_MUL: ok = rd(o.a) && rd(o.b); if (ok) r = mul(s[o.a], s[o.b], F); break;
-        case VDF_TAPE_SCALE: ok = rd(o.a) && o.b < tp->n_consts; if (ok) r = mul(s[o.a], consts[o.b], F); break;
-        case VDF_TAPE_OUT:
-          ok = rd(o.a) && o.b < tp->n_vars && !var_out[o.b];
-          if (ok) { var_out[o.b] = true; out[j * tp->n_vars + o.b] = s[o.a]; }
-          break;
-        default: break;
-      }
-      if (ok && o.op != VDF_TAPE_OUT) { ok = o.dst < tp->n_slots; if (ok) { s[o.dst] = r; written[o.dst] = true; } }
-      if (!ok) return fail(VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + " is malformed (opcode, index out of range, or a slot read before it is written)");
-    }
-    for (uint32_t k = 0; k < tp->n_vars; ++k)
-      if (!var_out[k]) return fail(VDF_ERR_BAD_ARG, "tape leaves variable " + std::to_string(k) + " unwritten");
+    const Fe* const adv[2] = {advice + j * tp->n_adv, advice + (j + 1) * tp->n_adv};
+    run_tape_round(tp, F, j, inv, adv, s, out + j * tp->n_vars);
   }
   return VDF_OK;
 }
@@ -252,8 +284,6 @@ int eval_round_tape_lanes(int fid, const vdf_round_tape* tp, uint64_t t, size_t 
   }
   return VDF_OK;
 }
-
-
 
 int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out, bool forward) {
   if (!b || !b->body) return fail(VDF_ERR_BAD_ARG, "walk body: null body");
@@ -290,92 +320,16 @@ int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out, bool forw
   return VDF_OK;
 }
 
-// the walk rules of vdf_hip.h over a tape, once, before anything is evaluated -- what vec_round_tape_walk checks before a launch
-// what a POW of exponent e costs: bitlen - 1 squarings and popcount - 1 products from the top set bit, at least one
-static uint64_t pow_products(const Fe& e) {
-  uint64_t bits = 0, ones = 0;
-  for (int q = 0; q < 4; ++q)
-    if (e.l[q]) { bits = 64 * q + 64 - __builtin_clzll(e.l[q]); ones += __builtin_popcountll(e.l[q]); }
-  return bits + ones > 2 ? bits + ones - 2 : 1;
-}
-// x ^ e, e a plain integer: left to right from the top set bit, as the kernel does it (any order gives the same canonical value)
-static Fe pow_plain(const Fe& x, const Fe& e, const Field& F) {
-  int q = 3;
-  while (q >= 0 && e.l[q] == 0) --q;
-  if (q < 0) return one(F);
-  Fe acc = x;
-  for (int bit = 62 - __builtin_clzll(e.l[q]); q >= 0; --q, bit = 63)
-    for (; bit >= 0; --bit) {
-      acc = sqr(acc, F);
-      if ((e.l[q] >> bit) & 1) acc = mul(acc, x, F);
-    }
-  return acc;
-}
-
-// x ^ E(chain): the chain's steps with the host's canonical sqr / mul -- the byte-for-byte reference of k_tape_forward_walk_chain,
-// whose lazy values are these modulo m.  consts[b ..]: a packed chain check_walk_tape has accepted.
-static Fe pow_chain_run(const Fe& x, const Fe* consts, size_t b, const Field& F) {
-  const uint8_t* p = (const uint8_t*)(consts + b);
-  const vdf_pow_step* st = (const vdf_pow_step*)(p + 4);
-  Fe T[VDF_POW_CHAIN_MAX_TMP], v = x;
-  T[0] = x;
-  for (size_t k = 0; k < p[0]; ++k) {
-    if (st[k].src != VDF_POW_ACC) v = T[st[k].src];
-    for (unsigned q = st[k].squarings; q; --q) v = sqr(v, F);
-    if (st[k].mul != VDF_POW_NONE) v = mul(v, T[st[k].mul], F);
-    if (st[k].dst != VDF_POW_NONE) T[st[k].dst] = v;
-  }
-  return v;
-}
-
+// what the walk launchers check of a tape before a launch (rounds.hip): the rules of its mode, then the slot and work caps.
 // inv_slots: the slots a walk in lanes keeps its lane's inv in (n_inv there, 0 elsewhere), counted against VDF_WALK_MAX_SLOTS
 static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rounds, bool forward = false, bool inv_slots = false) {
-  if (!tp || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts)) return fail(VDF_ERR_BAD_ARG, "null tape");
-  if (tp->n_ops > VDF_TAPE_MAX_OPS || tp->n_consts > VDF_TAPE_MAX_CONSTS || tp->n_slots > VDF_TAPE_MAX_SLOTS || tp->n_vars > VDF_TAPE_MAX_VARS ||
-      tp->n_inv > VDF_TAPE_MAX_INV || tp->n_adv > VDF_TAPE_MAX_ADV || tp->n_vars == 0 || tp->n_adv == 0 || tp->n_slots == 0)
-    return fail(VDF_ERR_BAD_ARG, "tape exceeds a published cap (VDF_TAPE_MAX_*), or has no variable, slot or advice column");
-  if (tp->n_vars != tp->n_adv) return fail(VDF_ERR_BAD_ARG, "walk tape: n_vars != n_adv (a round writes one advice entry)");
+  vdftape::Info ti;
+  const int rc = check_tape(tp, forward ? vdftape::FORWARD : vdftape::WALK, &ti);
+  if (rc != VDF_OK) return rc;
   if (tp->n_inv && !inv) return fail(VDF_ERR_BAD_ARG, "null inv");
-  bool written[VDF_TAPE_MAX_SLOTS] = {}, col_out[VDF_TAPE_MAX_ADV] = {};
-  uint64_t products = 0;
-  uint32_t chain_tmp = 0;                              // the largest n_tmp of the tape's chains: slots behind the two entries
-  for (size_t i = 0; i < tp->n_ops; ++i) {
-    const vdf_tape_op& o = tp->ops[i];
-    auto rd = [&](uint8_t x) { return x < tp->n_slots && written[x]; };
-    bool ok = false;
-    switch (o.op) {
-      case VDF_TAPE_ADV: ok = o.a < tp->n_adv && o.b == (forward ? 0 : 1); break;
-      case VDF_TAPE_INV: ok = o.a < tp->n_inv; break;
-      case VDF_TAPE_J: ok = true; break;
-      case VDF_TAPE_CONST: ok = o.a < tp->n_consts; break;
-      case VDF_TAPE_ADD: case VDF_TAPE_SUB: ok = rd(o.a) && rd(o.b); break;
-      case VDF_TAPE_MUL: ok = rd(o.a) && rd(o.b); ++products; break;
-      case VDF_TAPE_SCALE: ok = rd(o.a) && o.b < tp->n_consts; ++products; break;
-      case VDF_TAPE_OUT: ok = rd(o.a) && o.b < tp->n_adv && !col_out[o.b]; if (ok) col_out[o.b] = true; break;
-      case VDF_TAPE_POW:
-        ok = forward && rd(o.a) && o.b < tp->n_consts;
-        if (ok) products += pow_products(((const Fe*)tp->consts)[o.b]);
-        break;
-      case VDF_TAPE_POWC:
-        ok = forward && rd(o.a);
-        if (ok) {
-          vdfpow::ChainInfo ci;
-          const std::string why = vdfpow::check_packed(tp->consts, tp->n_consts, o.b, &ci, nullptr, nullptr);
-          if (!why.empty()) return fail(VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + ": the chain of a POWC: " + why);
-          products += ci.products();
-          if (ci.n_tmp > chain_tmp) chain_tmp = ci.n_tmp;
-        }
-        break;
-      default: break;
-    }
-    if (ok && o.op != VDF_TAPE_OUT) { ok = o.dst < tp->n_slots; if (ok) written[o.dst] = true; }
-    if (!ok) return fail(VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + " is malformed (opcode, index out of range, or a slot read before it is written); a walk tape loads advice with b = " + (forward ? "0" : "1") + " only");
-  }
-  for (uint32_t k = 0; k < tp->n_adv; ++k)
-    if (!col_out[k]) return fail(VDF_ERR_BAD_ARG, "tape leaves variable " + std::to_string(k) + " unwritten");
-  if (tp->n_slots + 2 * tp->n_adv + (inv_slots ? tp->n_inv : 0) + chain_tmp > VDF_WALK_MAX_SLOTS)
-    return fail(VDF_ERR_BAD_ARG, chain_tmp ? "forward walk tape: n_slots + 2 * n_adv + the chains' n_tmp > VDF_WALK_MAX_SLOTS" : inv_slots ? "walk tape in lanes: n_slots + 2 * n_adv + n_inv > VDF_WALK_MAX_SLOTS" : "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS");
-  if (rounds > (forward ? VDF_FORWARD_TAPE_MAX_WORK : VDF_WALK_MAX_WORK) / (products ? products : 1))
+  if (tp->n_slots + 2 * tp->n_adv + (inv_slots ? tp->n_inv : 0) + ti.chain_tmp > VDF_WALK_MAX_SLOTS)
+    return fail(VDF_ERR_BAD_ARG, ti.chain_tmp ? "forward walk tape: n_slots + 2 * n_adv + the chains' n_tmp > VDF_WALK_MAX_SLOTS" : inv_slots ? "walk tape in lanes: n_slots + 2 * n_adv + n_inv > VDF_WALK_MAX_SLOTS" : "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS");
+  if (rounds > (forward ? VDF_FORWARD_TAPE_MAX_WORK : VDF_WALK_MAX_WORK) / ti.products)
     return fail(VDF_ERR_BAD_ARG, std::string("rounds x products per round > ") + (forward ? "VDF_FORWARD_TAPE_MAX_WORK" : "VDF_WALK_MAX_WORK") + " in one call: cut the walk");
   return VDF_OK;
 }
@@ -399,9 +353,9 @@ static int walk_tape_lanes(int fid, const vdf_round_tape* tp, size_t lanes, bool
   if (trace && heads && top < rounds) return fail(VDF_ERR_BAD_ARG, "heads with top < rounds: the landing would be written below the run");
   if (group == 0) { group = n; group_stride = 0; }
   const Field& F = field(fid);
-  const Fe* consts = (const Fe*)tp->consts;
   const size_t na = tp->n_adv;
   Fe s[VDF_TAPE_MAX_SLOTS], stand[VDF_TAPE_MAX_ADV], prod[VDF_TAPE_MAX_ADV];
+  const Fe* const adv[2] = {nullptr, stand};      // a descending walk stands on entry j + 1
   for (size_t w = 0; w < n; ++w) {
     const uint64_t G = w / group, first = (w % group) * walk_stride + top;
     const uint64_t g = G / lanes;
@@ -414,20 +368,7 @@ static int walk_tape_lanes(int fid, const vdf_round_tape* tp, size_t lanes, bool
         for (size_t c = 0; c < na; ++c) tr[c] = stand[c];
         tr -= na;
       }
-      for (size_t i = 0; i < tp->n_ops; ++i) {
-        const vdf_tape_op& o = tp->ops[i];
-        switch (o.op) {
-          case VDF_TAPE_ADV: s[o.dst] = stand[o.a]; break;
-          case VDF_TAPE_INV: s[o.dst] = lane_inv[o.a]; break;
-          case VDF_TAPE_J: s[o.dst] = from_u64(j, F); break;
-          case VDF_TAPE_CONST: s[o.dst] = consts[o.a]; break;
-          case VDF_TAPE_ADD: s[o.dst] = add(s[o.a], s[o.b], F); break;
-          case VDF_TAPE_SUB: s[o.dst] = sub(s[o.a], s[o.b], F); break;
-          case VDF_TAPE_MUL: s[o.dst] = mul(s[o.a], s[o.b], F); break;
-          case VDF_TAPE_SCALE: s[o.dst] = mul(s[o.a], consts[o.b], F); break;
-          default: prod[o.b] = s[o.a]; break;      // VDF_TAPE_OUT
-        }
-      }
+      run_tape_round(tp, F, j, lane_inv, adv, s, prod);
       for (size_t c = 0; c < na; ++c) stand[c] = prod[c];
     }
     for (size_t c = 0; c < na; ++c) entries[w * na + c] = stand[c];
@@ -461,29 +402,14 @@ int eval_forward_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entr
   if (n > ((size_t)1 << 31)) return fail(VDF_ERR_BAD_LENGTH, "more than 2^31 walks");
   if (!entries) return fail(VDF_ERR_BAD_ARG, "null entries");
   const Field& F = field(fid);
-  const Fe* consts = (const Fe*)tp->consts;
   const size_t na = tp->n_adv;
   Fe s[VDF_TAPE_MAX_SLOTS], stand[VDF_TAPE_MAX_ADV], prod[VDF_TAPE_MAX_ADV];
+  const Fe* const adv[2] = {stand, nullptr};      // a forward walk stands on entry j
   for (size_t w = 0; w < n; ++w) {
     uint64_t j = j_base + w * j_walk_step + base;
     for (size_t c = 0; c < na; ++c) stand[c] = entries[w * na + c];
     for (uint64_t r = 0; r < rounds; ++r, ++j) {
-      for (size_t i = 0; i < tp->n_ops; ++i) {
-        const vdf_tape_op& o = tp->ops[i];
-        switch (o.op) {
-          case VDF_TAPE_ADV: s[o.dst] = stand[o.a]; break;
-          case VDF_TAPE_INV: s[o.dst] = inv[o.a]; break;
-          case VDF_TAPE_J: s[o.dst] = from_u64(j, F); break;
-          case VDF_TAPE_CONST: s[o.dst] = consts[o.a]; break;
-          case VDF_TAPE_ADD: s[o.dst] = add(s[o.a], s[o.b], F); break;
-          case VDF_TAPE_SUB: s[o.dst] = sub(s[o.a], s[o.b], F); break;
-          case VDF_TAPE_MUL: s[o.dst] = mul(s[o.a], s[o.b], F); break;
-          case VDF_TAPE_SCALE: s[o.dst] = mul(s[o.a], consts[o.b], F); break;
-          case VDF_TAPE_POW: s[o.dst] = pow_plain(s[o.a], consts[o.b], F); break;
-          case VDF_TAPE_POWC: s[o.dst] = pow_chain_run(s[o.a], consts, o.b, F); break;
-          default: prod[o.b] = s[o.a]; break;      // VDF_TAPE_OUT
-        }
-      }
+      run_tape_round(tp, F, j, inv, adv, s, prod);
       for (size_t c = 0; c < na; ++c) stand[c] = prod[c];
       const uint64_t g = base + r + 1;
       if (trace)

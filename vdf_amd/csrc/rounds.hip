@@ -11,7 +11,7 @@
 #include <cstring>
 #include "internal.h"
 #include "fe.cuh"
-#include "pow_chain.h"
+#include "tape_rules.h"
 
 namespace vdf {
 
@@ -42,6 +42,126 @@ template <class P> __device__ __forceinline__ void slot_store(uint4* lds, uint32
   lds[(slot * 2 + 1) * 64 + lane] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
 }
 
+// ---- the interpreter: the ops of ONE round of a tape for one lane, the only statement of them on the device -------------------
+// Six kernels run tapes (the two round kernels, the two descending walks, the two forward walks); they differ in their setup and
+// landing and in three ops, which a kernel hands over as its IO: where ADV reads (global advice, or the entry stood on in LDS),
+// where INV reads (the kernel arguments from an offset, or slots of LDS) and where OUT writes (global variables, or the entry
+// produced in LDS).  ADMIT: the ops beyond the base set that the kernel's launcher lets through (pack_tape's mode) -- an op that is
+// not admitted has no case here, so a kernel pays in registers and code only for what it can meet.
+// What every kernel relies on: the slot file is in LDS, a lane touching only its own column (no barrier); nothing private is
+// indexed by a run-time value (slot numbers, columns and constant indices are scalars read from the arguments, and index LDS or the
+// arguments, never a register array: that would be scratch); control is wave-uniform (the opcode, every trip count and every
+// exponent bit come from the kernel arguments by scalar loads).  No index is checked here: tape_rules.h has checked them all.
+//
+// A NEW OP touches exactly: the op enum in include/vdf_hip.h; the rules in tape_rules.h; tape_round below; the host interpreter
+// run_tape_round in host/rounds_host.cpp (a separate restatement: the GPU tests compare the two); the recorder's compile_round there.
+enum { TAPE_BASE = 0, TAPE_POW = 1, TAPE_POWC = 2 };      // ADMIT: the base ops; and VDF_TAPE_POW; and VDF_TAPE_POWC
+constexpr int TAPE_NO_OP = 0x100;                         // the case label of an op that is not admitted: an opcode is one byte
+
+// k_round_tape, k_round_tape_lanes: advice and variables in global memory, this launch's (lane's) invariants from tape.inv[inv0]
+template <class P> struct RoundIO {
+  const char* adv;
+  char* out;
+  uint32_t inv0;
+  __device__ __forceinline__ Fe<P> load_adv(const TapeArgs& tape, const uint4*, uint32_t, uint32_t a, uint32_t b) const {
+    return fe_load<P>(adv + (b * tape.n_adv + a) * 32);
+  }
+  __device__ __forceinline__ Fe<P> load_inv(const TapeArgs& tape, const uint4*, uint32_t, uint32_t a) const { return tape_fe<P>(tape.inv[inv0 + a]); }
+  __device__ __forceinline__ void store_out(uint4*, uint32_t, uint32_t b, const Fe<P>& v) const { fe_store<P>(out + b * 32, v); }
+};
+// the walks: ADV is the entry stood on (the launcher admits one b only), OUT the entry produced, both slots of LDS behind the value
+// file; INV_LDS: the invariants are slots too, from inv0 (k_tape_walk_lanes), else tape.inv as it is
+template <class P, bool INV_LDS> struct WalkIO {
+  uint32_t stand, prod, inv0;
+  __device__ __forceinline__ Fe<P> load_adv(const TapeArgs&, const uint4* slots, uint32_t lane, uint32_t a, uint32_t) const {
+    return slot_load<P>(slots, stand + a, lane);
+  }
+  __device__ __forceinline__ Fe<P> load_inv(const TapeArgs& tape, const uint4* slots, uint32_t lane, uint32_t a) const {
+    if constexpr (INV_LDS) return slot_load<P>(slots, inv0 + a, lane);
+    else return tape_fe<P>(tape.inv[a]);
+  }
+  __device__ __forceinline__ void store_out(uint4* slots, uint32_t lane, uint32_t b, const Fe<P>& v) const { slot_store<P>(slots, prod + b, lane, v); }
+};
+
+// tmp0: T[0] of a chain, the first of the n_tmp slots behind the two entries (ADMIT = TAPE_POWC only)
+template <class P, int ADMIT, class IO>
+__device__ __forceinline__ void tape_round(const TapeArgs& tape, uint4* slots, uint32_t lane, uint64_t j, const IO& io, uint32_t tmp0 = 0) {
+#pragma unroll 1
+  for (uint32_t i = 0; i < tape.n_ops; ++i) {
+    const uint32_t x = tape.ops[i];
+    const uint32_t op = x & 0xFF, dst = (x >> 8) & 0xFF, a = (x >> 16) & 0xFF, b = x >> 24;
+    Fe<P> v;
+    switch (op) {
+      case VDF_TAPE_ADV: v = io.load_adv(tape, slots, lane, a, b); break;
+      case VDF_TAPE_INV: v = io.load_inv(tape, slots, lane, a); break;
+      case VDF_TAPE_J: v = fe_from_u64<P>(j); break;
+      case VDF_TAPE_CONST: v = tape_fe<P>(tape.consts[a]); break;
+      case VDF_TAPE_ADD: v = fe_add(slot_load<P>(slots, a, lane), slot_load<P>(slots, b, lane)); break;
+      case VDF_TAPE_SUB: v = fe_sub(slot_load<P>(slots, a, lane), slot_load<P>(slots, b, lane)); break;
+      case VDF_TAPE_MUL: {
+        const Fe<P> y = slot_load<P>(slots, a, lane);
+        v = a == b ? fe_sqr(y) : fe_mul(y, slot_load<P>(slots, b, lane));
+        break;
+      }
+      case VDF_TAPE_SCALE: v = fe_mul(slot_load<P>(slots, a, lane), tape_fe<P>(tape.consts[b])); break;
+      // left-to-right square-and-multiply from the exponent's top set bit.  The base is read from its slot once and stays in
+      // registers with the accumulator; the exponent's words come from the kernel arguments by scalar loads.  No table.
+      case ADMIT >= TAPE_POW ? VDF_TAPE_POW : TAPE_NO_OP: {
+        uint32_t q = 8, word = 0;                    // words of the exponent still to read, and the one being read
+        while (q && (word = tape.consts[b].v[q - 1]) == 0) --q;
+        if (q == 0) { v = fe_one<P>(); break; }      // E = 0
+        const Fe<P> y = slot_load<P>(slots, a, lane);
+        v = y;                                       // the top set bit
+        int bit = 31 - __builtin_clz(word);
+        for (;;) {
+#pragma unroll 1
+          while (bit-- > 0) {
+            v = fe_sqr(v);
+            if ((word >> bit) & 1) v = fe_mul(v, y);
+          }
+          if (--q == 0) break;
+          word = tape.consts[b].v[q - 1];
+          bit = 32;
+        }
+        break;
+      }
+      // a power by a caller-supplied addition chain, interpreted as k_forward_walk (minroot.hip) interprets the built-in one.  The
+      // accumulator stays in registers; the chain's temporaries are n_tmp more lane-private slots of LDS from tmp0, same
+      // [slot][half][lane] layout.  The step words and the trip counts come from tape.consts by scalar loads (the chain is the same
+      // for every lane).  ONE squaring site and ONE product site, both in loops: the chain is not inlined.
+      //
+      // Bound: inside a chain the values are in the lazy domain of fe.cuh.  The base is canonical (every slot is).  A lazy square or
+      // product of operands below 2m + k eps is below 2m + (k + 1) eps.  On any path from the base to a value every squaring doubles
+      // the exponent and every product raises it, and a valid chain's exponents stay below 2^256: at most 255 squarings; a path
+      // passes a step at most once: at most 95 products.  So every value stays below 2m + 350 eps < 2^256 (eps ~ 2^126), the GENERAL
+      // lazy forms apply (the _t31 forms carry a nine-product bound that a chain exceeds), and fe_canon's two subtractions make the
+      // result canonical.
+      case ADMIT >= TAPE_POWC ? VDF_TAPE_POWC : TAPE_NO_OP + 1: {
+        const uint32_t* const cw = &tape.consts[0].v[0] + b * 8;      // word 0: n_steps | n_tmp << 8; word 1 + k: step k (the launcher checked all)
+        const uint32_t n_steps = cw[0] & 0xFF;
+        v = slot_load<P>(slots, a, lane);
+        slot_store<P>(slots, tmp0, lane, v);         // T[0] = the base
+#pragma unroll 1
+        for (uint32_t k = 0; k < n_steps; ++k) {
+          const uint32_t st = cw[1 + k];
+          const uint32_t src = st & 0xFF, mul = (st >> 16) & 0xFF, keep = st >> 24;
+          if (src != VDF_POW_ACC) v = slot_load<P>(slots, tmp0 + src, lane);
+#pragma unroll 1
+          for (uint32_t q = (st >> 8) & 0xFF; q; --q) v = fe_sqr_lazy(v);
+          if (mul != VDF_POW_NONE) v = fe_mul_lazy(v, slot_load<P>(slots, tmp0 + mul, lane));
+          if (keep != VDF_POW_NONE) slot_store<P>(slots, tmp0 + keep, lane, v);
+        }
+        v = fe_canon(v);                             // below 2m + 350 eps (above): two conditional subtractions
+        break;
+      }
+      default:                       // VDF_TAPE_OUT (the launcher admits no other opcode)
+        io.store_out(slots, lane, b, slot_load<P>(slots, a, lane));
+        continue;
+    }
+    slot_store<P>(slots, dst, lane, v);
+  }
+}
+
 template <class P>
 __global__ __launch_bounds__(64) void k_round_tape(TapeArgs tape, const char* __restrict__ advice, uint64_t t, char* __restrict__ out) {
   extern __shared__ uint4 tape_slots[];
@@ -49,36 +169,13 @@ __global__ __launch_bounds__(64) void k_round_tape(TapeArgs tape, const char* __
   const uint32_t lane = threadIdx.x;
   const uint64_t j = (uint64_t)blockIdx.x * 64 + lane;
   if (j >= t) return;
-  const char* adv = advice + j * tape.n_adv * 32;
-  char* o = out + j * tape.n_vars * 32;
-  for (uint32_t i = 0; i < tape.n_ops; ++i) {
-    const uint32_t w = tape.ops[i];
-    const uint32_t op = w & 0xFF, dst = (w >> 8) & 0xFF, a = (w >> 16) & 0xFF, b = w >> 24;
-    Fe<P> r;
-    switch (op) {
-      case VDF_TAPE_ADV: r = fe_load<P>(adv + (b * tape.n_adv + a) * 32); break;
-      case VDF_TAPE_INV: r = tape_fe<P>(tape.inv[a]); break;
-      case VDF_TAPE_J: r = fe_from_u64<P>(j); break;
-      case VDF_TAPE_CONST: r = tape_fe<P>(tape.consts[a]); break;
-      case VDF_TAPE_ADD: r = fe_add(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
-      case VDF_TAPE_SUB: r = fe_sub(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
-      case VDF_TAPE_MUL: {
-        const Fe<P> x = slot_load<P>(tape_slots, a, lane);
-        r = a == b ? fe_sqr(x) : fe_mul(x, slot_load<P>(tape_slots, b, lane));
-        break;
-      }
-      case VDF_TAPE_SCALE: r = fe_mul(slot_load<P>(tape_slots, a, lane), tape_fe<P>(tape.consts[b])); break;
-      default:                       // VDF_TAPE_OUT (the launcher admits no other opcode)
-        fe_store<P>(o + b * 32, slot_load<P>(tape_slots, a, lane));
-        continue;
-    }
-    slot_store<P>(tape_slots, dst, lane, r);
-  }
+  const RoundIO<P> io = {advice + j * tape.n_adv * 32, out + j * tape.n_vars * 32, 0};
+  tape_round<P, TAPE_BASE>(tape, tape_slots, lane, j, io);
 }
 
 // k_round_tape for `lanes` advice arrays in ONE launch (vdf_hip.h vdf_round_tape_run_lanes): the lane is the grid's second dimension,
 // so it is a scalar like the tape: the lane's advice, its variables and its own n_inv invariants -- all lanes' invariants share the
-// 512-byte block of the arguments, lane-major -- are reached through scalar offsets, and the interpreter is k_round_tape's.
+// 512-byte block of the arguments, lane-major -- are reached through scalar offsets.
 struct LaneRunArgs { uint64_t t, lane_stride; uint32_t n_inv, pad; };
 static_assert(sizeof(TapeArgs) + sizeof(LaneRunArgs) + 16 <= 4096, "the tape travels in the kernel-argument segment");
 
@@ -91,114 +188,27 @@ __global__ __launch_bounds__(64) void k_round_tape_lanes(TapeArgs tape, LaneRunA
   if (j >= la.t) return;
   const uint64_t l = blockIdx.y;                     // (wave-uniform)
   const uint32_t inv0 = (uint32_t)l * la.n_inv;
-  const char* adv = advice + (l * la.lane_stride + j) * tape.n_adv * 32;
-  char* o = out + (l * la.t + j) * tape.n_vars * 32;
-  for (uint32_t i = 0; i < tape.n_ops; ++i) {
-    const uint32_t w = tape.ops[i];
-    const uint32_t op = w & 0xFF, dst = (w >> 8) & 0xFF, a = (w >> 16) & 0xFF, b = w >> 24;
-    Fe<P> r;
-    switch (op) {
-      case VDF_TAPE_ADV: r = fe_load<P>(adv + (b * tape.n_adv + a) * 32); break;
-      case VDF_TAPE_INV: r = tape_fe<P>(tape.inv[inv0 + a]); break;
-      case VDF_TAPE_J: r = fe_from_u64<P>(j); break;
-      case VDF_TAPE_CONST: r = tape_fe<P>(tape.consts[a]); break;
-      case VDF_TAPE_ADD: r = fe_add(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
-      case VDF_TAPE_SUB: r = fe_sub(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
-      case VDF_TAPE_MUL: {
-        const Fe<P> x = slot_load<P>(tape_slots, a, lane);
-        r = a == b ? fe_sqr(x) : fe_mul(x, slot_load<P>(tape_slots, b, lane));
-        break;
-      }
-      case VDF_TAPE_SCALE: r = fe_mul(slot_load<P>(tape_slots, a, lane), tape_fe<P>(tape.consts[b])); break;
-      default:                       // VDF_TAPE_OUT (the launcher admits no other opcode)
-        fe_store<P>(o + b * 32, slot_load<P>(tape_slots, a, lane));
-        continue;
-    }
-    slot_store<P>(tape_slots, dst, lane, r);
-  }
+  const RoundIO<P> io = {advice + (l * la.lane_stride + j) * tape.n_adv * 32, out + (l * la.t + j) * tape.n_vars * 32, inv0};
+  tape_round<P, TAPE_BASE>(tape, tape_slots, lane, j, io);
 }
 
 // ---- walk tapes: the advice itself, rebuilt from checkpoints (vdf_hip.h vdf_round_tape_walk) ---------------------------------
 // k_inverse_walk's launch (one lane per walk, workgroups of one wavefront, wave priority left at 0: background work beside a
-// prover) around k_round_tape's interpreter.  Two entries of n_adv slots follow the value file in LDS: the one the walk stands on
-// and the one the round produces, swapped on the round's parity -- an OUT to column c never touches what a later ADV of column c
-// reads.  The slot numbers of both are scalars; nothing is indexed by a run-time value outside LDS.  A round is sequential after
-// the one before it, so unlike k_round_tape the interpreter's scalar loads of the tape recur every round: they stay in the
-// scalar cache (2.5 KiB of arguments).
+// prover) around the interpreter.  Two entries of n_adv slots follow the value file in LDS: the one the walk stands on and the one
+// the round produces, swapped on the round's parity -- an OUT to column c never touches what a later ADV of column c reads.  The
+// slot numbers of both are scalars; nothing is indexed by a run-time value outside LDS.  A round is sequential after the one before
+// it, so unlike k_round_tape the interpreter's scalar loads of the tape recur every round: they stay in the scalar cache (2.5 KiB
+// of arguments).
+//
+// In lanes (vdf_hip.h vdf_round_tape_walk_lanes) the groups are numbered step-major, lane-minor: group G = g * lanes + l is lane l
+// of step g.  There the lane is a per-thread value -- one wavefront holds walks of several lanes -- and the kernel arguments
+// indexed by it would go to scratch.  So each thread selects its own j_base and invariants ONCE, before the rounds, in a uniform
+// loop over the at most VDF_TAPE_MAX_LANES argument elements (scalar loads, a select per element), and keeps the invariants in n_inv
+// more lane-private slots of LDS behind the two entries: an INV op is then a slot load like any other.
 struct WalkArgs {
   uint64_t n, walk_stride, top, group, group_stride, j_base, j_group_step;
   uint32_t rounds, n_slots, heads, pad;
 };
-static_assert(sizeof(TapeArgs) + sizeof(WalkArgs) + 32 <= 4096, "the tape travels in the kernel-argument segment");
-
-template <class P>
-__global__ __launch_bounds__(64) void k_tape_walk(TapeArgs tape, WalkArgs wa, char* __restrict__ entries, char* __restrict__ trace,
-                                                  const char* __restrict__ expect, int32_t* __restrict__ ok) {
-  extern __shared__ uint4 tape_slots[];
-  const uint32_t lane = threadIdx.x;
-  const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
-  if (w >= wa.n) return;                             // (no barrier below: a lane touches only its own words of LDS)
-  const uint32_t na = tape.n_adv;
-  const size_t esz = (size_t)na * 32;
-  char* const ep = entries + w * esz;
-  const uint64_t g = w / wa.group, first = (w % wa.group) * wa.walk_stride + wa.top;      // local index of the entry the walk stands on
-  uint32_t stand = wa.n_slots, prod = wa.n_slots + na;
-  for (uint32_t c = 0; c < na; ++c) slot_store<P>(tape_slots, stand + c, lane, fe_load<P>(ep + c * 32));
-  char* tp = trace ? trace + (g * wa.group_stride + first) * esz : nullptr;
-  uint64_t j = wa.j_base + g * wa.j_group_step + first - 1;
-#pragma unroll 1
-  for (uint32_t r = 0; r < wa.rounds; ++r, --j) {
-    if (tp) {
-      for (uint32_t c = 0; c < na; ++c) fe_store<P>(tp + c * 32, slot_load<P>(tape_slots, stand + c, lane));
-      tp -= esz;
-    }
-#pragma unroll 1
-    for (uint32_t i = 0; i < tape.n_ops; ++i) {
-      const uint32_t x = tape.ops[i];
-      const uint32_t op = x & 0xFF, dst = (x >> 8) & 0xFF, a = (x >> 16) & 0xFF, b = x >> 24;
-      Fe<P> v;
-      switch (op) {
-        case VDF_TAPE_ADV: v = slot_load<P>(tape_slots, stand + a, lane); break;      // (the launcher admits b = 1 only)
-        case VDF_TAPE_INV: v = tape_fe<P>(tape.inv[a]); break;
-        case VDF_TAPE_J: v = fe_from_u64<P>(j); break;
-        case VDF_TAPE_CONST: v = tape_fe<P>(tape.consts[a]); break;
-        case VDF_TAPE_ADD: v = fe_add(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
-        case VDF_TAPE_SUB: v = fe_sub(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
-        case VDF_TAPE_MUL: {
-          const Fe<P> y = slot_load<P>(tape_slots, a, lane);
-          v = a == b ? fe_sqr(y) : fe_mul(y, slot_load<P>(tape_slots, b, lane));
-          break;
-        }
-        case VDF_TAPE_SCALE: v = fe_mul(slot_load<P>(tape_slots, a, lane), tape_fe<P>(tape.consts[b])); break;
-        default:                       // VDF_TAPE_OUT
-          slot_store<P>(tape_slots, prod + b, lane, slot_load<P>(tape_slots, a, lane));
-          continue;
-      }
-      slot_store<P>(tape_slots, dst, lane, v);
-    }
-    const uint32_t t = stand; stand = prod; prod = t;
-  }
-  // where the walk landed: back into entries, to the head of its group's trace, and against the checkpoint
-  uint32_t diff = 0;
-  const bool head = tp && wa.heads && w % wa.group == 0;
-  for (uint32_t c = 0; c < na; ++c) {
-    const Fe<P> v = slot_load<P>(tape_slots, stand + c, lane);
-    fe_store<P>(ep + c * 32, v);
-    if (head) fe_store<P>(tp + c * 32, v);
-    if (expect) {
-      const Fe<P> e = fe_load<P>(expect + w * esz + c * 32);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) diff |= v.v[q] ^ e.v[q];
-    }
-  }
-  if (expect) ok[w] = diff == 0;
-}
-
-// k_tape_walk with the groups numbered step-major, lane-minor (vdf_hip.h vdf_round_tape_walk_lanes): group G = g * lanes + l is lane
-// l of step g.  Here the lane is a per-thread value -- one wavefront holds walks of several lanes -- and the kernel arguments
-// indexed by it would go to scratch.  So each thread selects its own j_base and invariants ONCE, before the rounds, in a uniform
-// loop over the at most VDF_TAPE_MAX_LANES argument elements (scalar loads, a select per element), and keeps the invariants in n_inv
-// more lane-private slots of LDS behind the two entries: an INV op is then a slot load like any other.
 struct WalkLanesArgs {
   WalkArgs w;
   uint32_t lanes, n_inv;
@@ -206,78 +216,59 @@ struct WalkLanesArgs {
 };
 static_assert(sizeof(TapeArgs) + sizeof(WalkLanesArgs) + 32 <= 4096, "the tape travels in the kernel-argument segment");
 
-template <class P>
-__global__ __launch_bounds__(64) void k_tape_walk_lanes(TapeArgs tape, WalkLanesArgs wl, char* __restrict__ entries, char* __restrict__ trace,
-                                                        const char* __restrict__ expect, int32_t* __restrict__ ok) {
-  extern __shared__ uint4 tape_slots[];
+// wl: the lanes form's arguments behind wa (= wl->w), null for k_tape_walk
+template <class P, bool LANES>
+__device__ __forceinline__ void tape_walk(const TapeArgs& tape, const WalkArgs& wa, const WalkLanesArgs* wl, uint4* slots, char* entries,
+                                          char* trace, const char* expect, int32_t* ok) {
   const uint32_t lane = threadIdx.x;
   const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
-  if (w >= wl.w.n) return;                           // (no barrier below: a lane touches only its own words of LDS)
+  if (w >= wa.n) return;                             // (no barrier below: a lane touches only its own words of LDS)
   const uint32_t na = tape.n_adv;
   const size_t esz = (size_t)na * 32;
   char* const ep = entries + w * esz;
-  const uint64_t G = w / wl.w.group, first = (w % wl.w.group) * wl.w.walk_stride + wl.w.top;
-  const uint64_t g = G / wl.lanes;
-  const uint32_t l = (uint32_t)(G % wl.lanes);
-  uint32_t stand = wl.w.n_slots, prod = wl.w.n_slots + na;
-  const uint32_t inv0 = wl.w.n_slots + 2 * na;
-  uint64_t jb = 0;
+  const uint64_t G = w / wa.group, first = (w % wa.group) * wa.walk_stride + wa.top;      // local index of the entry the walk stands on
+  uint64_t g = G, jb = wa.j_base;
+  uint32_t stand = wa.n_slots, prod = wa.n_slots + na;
+  const uint32_t inv0 = wa.n_slots + 2 * na;
+  if constexpr (LANES) {
+    g = G / wl->lanes;
+    const uint32_t l = (uint32_t)(G % wl->lanes);
+    jb = 0;
 #pragma unroll 1
-  for (uint32_t q = 0; q < wl.lanes; ++q) {
-    const uint64_t x = wl.j_base[q];
-    jb = q == l ? x : jb;
-  }
-#pragma unroll 1
-  for (uint32_t k = 0; k < wl.n_inv; ++k) {
-    Fe<P> v = fe_zero<P>();
-#pragma unroll 1
-    for (uint32_t q = 0; q < wl.lanes; ++q) {
-      const Fe<P> x = tape_fe<P>(tape.inv[q * wl.n_inv + k]);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v.v[i] = q == l ? x.v[i] : v.v[i];
+    for (uint32_t q = 0; q < wl->lanes; ++q) {
+      const uint64_t x = wl->j_base[q];
+      jb = q == l ? x : jb;
     }
-    slot_store<P>(tape_slots, inv0 + k, lane, v);
-  }
-  for (uint32_t c = 0; c < na; ++c) slot_store<P>(tape_slots, stand + c, lane, fe_load<P>(ep + c * 32));
-  char* tp = trace ? trace + (G * wl.w.group_stride + first) * esz : nullptr;
-  uint64_t j = jb + g * wl.w.j_group_step + first - 1;
 #pragma unroll 1
-  for (uint32_t r = 0; r < wl.w.rounds; ++r, --j) {
+    for (uint32_t k = 0; k < wl->n_inv; ++k) {
+      Fe<P> v = fe_zero<P>();
+#pragma unroll 1
+      for (uint32_t q = 0; q < wl->lanes; ++q) {
+        const Fe<P> x = tape_fe<P>(tape.inv[q * wl->n_inv + k]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v.v[i] = q == l ? x.v[i] : v.v[i];
+      }
+      slot_store<P>(slots, inv0 + k, lane, v);
+    }
+  }
+  for (uint32_t c = 0; c < na; ++c) slot_store<P>(slots, stand + c, lane, fe_load<P>(ep + c * 32));
+  char* tp = trace ? trace + (G * wa.group_stride + first) * esz : nullptr;
+  uint64_t j = jb + g * wa.j_group_step + first - 1;
+#pragma unroll 1
+  for (uint32_t r = 0; r < wa.rounds; ++r, --j) {
     if (tp) {
-      for (uint32_t c = 0; c < na; ++c) fe_store<P>(tp + c * 32, slot_load<P>(tape_slots, stand + c, lane));
+      for (uint32_t c = 0; c < na; ++c) fe_store<P>(tp + c * 32, slot_load<P>(slots, stand + c, lane));
       tp -= esz;
     }
-#pragma unroll 1
-    for (uint32_t i = 0; i < tape.n_ops; ++i) {
-      const uint32_t x = tape.ops[i];
-      const uint32_t op = x & 0xFF, dst = (x >> 8) & 0xFF, a = (x >> 16) & 0xFF, b = x >> 24;
-      Fe<P> v;
-      switch (op) {
-        case VDF_TAPE_ADV: v = slot_load<P>(tape_slots, stand + a, lane); break;      // (the launcher admits b = 1 only)
-        case VDF_TAPE_INV: v = slot_load<P>(tape_slots, inv0 + a, lane); break;
-        case VDF_TAPE_J: v = fe_from_u64<P>(j); break;
-        case VDF_TAPE_CONST: v = tape_fe<P>(tape.consts[a]); break;
-        case VDF_TAPE_ADD: v = fe_add(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
-        case VDF_TAPE_SUB: v = fe_sub(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
-        case VDF_TAPE_MUL: {
-          const Fe<P> y = slot_load<P>(tape_slots, a, lane);
-          v = a == b ? fe_sqr(y) : fe_mul(y, slot_load<P>(tape_slots, b, lane));
-          break;
-        }
-        case VDF_TAPE_SCALE: v = fe_mul(slot_load<P>(tape_slots, a, lane), tape_fe<P>(tape.consts[b])); break;
-        default:                       // VDF_TAPE_OUT
-          slot_store<P>(tape_slots, prod + b, lane, slot_load<P>(tape_slots, a, lane));
-          continue;
-      }
-      slot_store<P>(tape_slots, dst, lane, v);
-    }
+    const WalkIO<P, LANES> io = {stand, prod, inv0};
+    tape_round<P, TAPE_BASE>(tape, slots, lane, j, io);
     const uint32_t t = stand; stand = prod; prod = t;
   }
   // where the walk landed: back into entries, to the head of its group's trace, and against the checkpoint
   uint32_t diff = 0;
-  const bool head = tp && wl.w.heads && w % wl.w.group == 0;
+  const bool head = tp && wa.heads && w % wa.group == 0;
   for (uint32_t c = 0; c < na; ++c) {
-    const Fe<P> v = slot_load<P>(tape_slots, stand + c, lane);
+    const Fe<P> v = slot_load<P>(slots, stand + c, lane);
     fe_store<P>(ep + c * 32, v);
     if (head) fe_store<P>(tp + c * 32, v);
     if (expect) {
@@ -289,111 +280,35 @@ __global__ __launch_bounds__(64) void k_tape_walk_lanes(TapeArgs tape, WalkLanes
   if (expect) ok[w] = diff == 0;
 }
 
+template <class P>
+__global__ __launch_bounds__(64) void k_tape_walk(TapeArgs tape, WalkArgs wa, char* __restrict__ entries, char* __restrict__ trace,
+                                                  const char* __restrict__ expect, int32_t* __restrict__ ok) {
+  extern __shared__ uint4 tape_slots[];
+  tape_walk<P, false>(tape, wa, nullptr, tape_slots, entries, trace, expect, ok);
+}
+
+template <class P>
+__global__ __launch_bounds__(64) void k_tape_walk_lanes(TapeArgs tape, WalkLanesArgs wl, char* __restrict__ entries, char* __restrict__ trace,
+                                                        const char* __restrict__ expect, int32_t* __restrict__ ok) {
+  extern __shared__ uint4 tape_slots[];
+  tape_walk<P, true>(tape, wl.w, &wl, tape_slots, entries, trace, expect, ok);
+}
+
 // ---- forward walk tapes: the chain itself, many at once (vdf_hip.h vdf_round_tape_forward_walk) -------------------------------
 // k_tape_walk ascending: the same launch (one lane per walk, workgroups of one wavefront, wave priority left at 0), the same
 // interpreter and the same two entries behind the value file in LDS, swapped each round; what a round produces goes to the trace
-// and, every `every` rounds, to the checkpoints, in k_forward_walk's layout.  The one new op is VDF_TAPE_POW: left-to-right
-// square-and-multiply from the exponent's top set bit.  The base is read from its slot once and stays in registers with the
-// accumulator; the exponent's words come from the kernel arguments by scalar loads, so the loop and the branch on every bit are
-// wave-uniform.  No table, no LDS beyond the slots.
+// and, every `every` rounds, to the checkpoints, in k_forward_walk's layout.  k_tape_forward_walk admits VDF_TAPE_POW on top of the
+// base ops; k_tape_forward_walk_chain, for a tape that holds a VDF_TAPE_POWC, admits that too and keeps the chains' temporaries in
+// n_tmp more slots behind the two entries -- every other tape runs the kernel that does not carry the chain interpreter.
 struct ForwardArgs {
   uint64_t n, walk_stride, cp_stride, every, base, j_base, j_walk_step;
   uint32_t rounds, n_slots;
 };
 static_assert(sizeof(TapeArgs) + sizeof(ForwardArgs) + 24 <= 4096, "the tape travels in the kernel-argument segment");
 
-template <class P>
-__global__ __launch_bounds__(64) void k_tape_forward_walk(TapeArgs tape, ForwardArgs fa, char* __restrict__ entries,
-                                                          char* __restrict__ checkpoints, char* __restrict__ trace) {
-  extern __shared__ uint4 tape_slots[];
-  const uint32_t lane = threadIdx.x;
-  const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
-  if (w >= fa.n) return;                             // (no barrier below: a lane touches only its own words of LDS)
-  const uint32_t na = tape.n_adv;
-  const size_t esz = (size_t)na * 32;
-  char* const ep = entries + w * esz;
-  uint32_t stand = fa.n_slots, prod = fa.n_slots + na;
-  for (uint32_t c = 0; c < na; ++c) slot_store<P>(tape_slots, stand + c, lane, fe_load<P>(ep + c * 32));
-  // entry base + r + 1 after round r; checkpoint (base + r + 1) / every when `every` divides base + r + 1
-  char* tp = trace ? trace + (w * fa.walk_stride + fa.base + 1) * esz : nullptr;
-  uint64_t cp_left = checkpoints ? fa.every - fa.base % fa.every : 0;
-  char* cp = checkpoints ? checkpoints + (w * fa.cp_stride + fa.base / fa.every + 1) * esz : nullptr;
-  uint64_t j = fa.j_base + w * fa.j_walk_step + fa.base;
-#pragma unroll 1
-  for (uint32_t r = 0; r < fa.rounds; ++r, ++j) {
-#pragma unroll 1
-    for (uint32_t i = 0; i < tape.n_ops; ++i) {
-      const uint32_t x = tape.ops[i];
-      const uint32_t op = x & 0xFF, dst = (x >> 8) & 0xFF, a = (x >> 16) & 0xFF, b = x >> 24;
-      Fe<P> v;
-      switch (op) {
-        case VDF_TAPE_ADV: v = slot_load<P>(tape_slots, stand + a, lane); break;      // (the launcher admits b = 0 only)
-        case VDF_TAPE_INV: v = tape_fe<P>(tape.inv[a]); break;
-        case VDF_TAPE_J: v = fe_from_u64<P>(j); break;
-        case VDF_TAPE_CONST: v = tape_fe<P>(tape.consts[a]); break;
-        case VDF_TAPE_ADD: v = fe_add(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
-        case VDF_TAPE_SUB: v = fe_sub(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
-        case VDF_TAPE_MUL: {
-          const Fe<P> y = slot_load<P>(tape_slots, a, lane);
-          v = a == b ? fe_sqr(y) : fe_mul(y, slot_load<P>(tape_slots, b, lane));
-          break;
-        }
-        case VDF_TAPE_SCALE: v = fe_mul(slot_load<P>(tape_slots, a, lane), tape_fe<P>(tape.consts[b])); break;
-        case VDF_TAPE_POW: {
-          uint32_t q = 8, word = 0;                    // words of the exponent still to read, and the one being read
-          while (q && (word = tape.consts[b].v[q - 1]) == 0) --q;
-          if (q == 0) { v = fe_one<P>(); break; }      // E = 0
-          const Fe<P> y = slot_load<P>(tape_slots, a, lane);
-          v = y;                                       // the top set bit
-          int bit = 31 - __builtin_clz(word);
-          for (;;) {
-#pragma unroll 1
-            while (bit-- > 0) {
-              v = fe_sqr(v);
-              if ((word >> bit) & 1) v = fe_mul(v, y);
-            }
-            if (--q == 0) break;
-            word = tape.consts[b].v[q - 1];
-            bit = 32;
-          }
-          break;
-        }
-        default:                       // VDF_TAPE_OUT
-          slot_store<P>(tape_slots, prod + b, lane, slot_load<P>(tape_slots, a, lane));
-          continue;
-      }
-      slot_store<P>(tape_slots, dst, lane, v);
-    }
-    const uint32_t t = stand; stand = prod; prod = t;
-    if (tp) {
-      for (uint32_t c = 0; c < na; ++c) fe_store<P>(tp + c * 32, slot_load<P>(tape_slots, stand + c, lane));
-      tp += esz;
-    }
-    if (cp && --cp_left == 0) {
-      for (uint32_t c = 0; c < na; ++c) fe_store<P>(cp + c * 32, slot_load<P>(tape_slots, stand + c, lane));
-      cp += esz;
-      cp_left = fa.every;
-    }
-  }
-  for (uint32_t c = 0; c < na; ++c) fe_store<P>(ep + c * 32, slot_load<P>(tape_slots, stand + c, lane));
-}
-
-// k_tape_forward_walk for a tape that holds a VDF_TAPE_POWC (vdf_hip.h): the same launch, the same interpreter, binary POW still
-// accepted, and one more case -- a power by a caller-supplied addition chain, interpreted as k_forward_walk (minroot.hip) interprets
-// the built-in one.  The accumulator stays in registers; the chain's temporaries are n_tmp more lane-private slots of LDS behind the
-// two entries, same [slot][half][lane] layout, indexed by scalars.  The step words and the trip counts come from tape.consts by
-// scalar loads (the chain is the same for every lane), so every branch is wave-uniform.  ONE squaring site and ONE product site,
-// both in loops: the chain is not inlined.  Nothing private is indexed by a run-time value.
-//
-// Bound: inside a chain the values are in the lazy domain of fe.cuh.  The base is canonical (every slot is).  A lazy square or
-// product of operands below 2m + k eps is below 2m + (k + 1) eps.  On any path from the base to a value every squaring doubles the
-// exponent and every product raises it, and a valid chain's exponents stay below 2^256: at most 255 squarings; a path passes a step
-// at most once: at most 95 products.  So every value stays below 2m + 350 eps < 2^256 (eps ~ 2^126), the GENERAL lazy forms apply
-// (the _t31 forms carry a nine-product bound that a chain exceeds), and fe_canon's two subtractions make the result canonical.
-template <class P>
-__global__ __launch_bounds__(64) void k_tape_forward_walk_chain(TapeArgs tape, ForwardArgs fa, char* __restrict__ entries,
-                                                                char* __restrict__ checkpoints, char* __restrict__ trace) {
-  extern __shared__ uint4 tape_slots[];
+template <class P, int ADMIT>
+__device__ __forceinline__ void tape_forward_walk(const TapeArgs& tape, const ForwardArgs& fa, uint4* slots, char* entries, char* checkpoints,
+                                                  char* trace) {
   const uint32_t lane = threadIdx.x;
   const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
   if (w >= fa.n) return;                             // (no barrier below: a lane touches only its own words of LDS)
@@ -402,89 +317,43 @@ __global__ __launch_bounds__(64) void k_tape_forward_walk_chain(TapeArgs tape, F
   char* const ep = entries + w * esz;
   uint32_t stand = fa.n_slots, prod = fa.n_slots + na;
   const uint32_t tmp0 = fa.n_slots + 2 * na;         // T[0] of a chain
-  const uint32_t* const cwords = &tape.consts[0].v[0];
-  for (uint32_t c = 0; c < na; ++c) slot_store<P>(tape_slots, stand + c, lane, fe_load<P>(ep + c * 32));
+  for (uint32_t c = 0; c < na; ++c) slot_store<P>(slots, stand + c, lane, fe_load<P>(ep + c * 32));
+  // entry base + r + 1 after round r; checkpoint (base + r + 1) / every when `every` divides base + r + 1
   char* tp = trace ? trace + (w * fa.walk_stride + fa.base + 1) * esz : nullptr;
   uint64_t cp_left = checkpoints ? fa.every - fa.base % fa.every : 0;
   char* cp = checkpoints ? checkpoints + (w * fa.cp_stride + fa.base / fa.every + 1) * esz : nullptr;
   uint64_t j = fa.j_base + w * fa.j_walk_step + fa.base;
 #pragma unroll 1
   for (uint32_t r = 0; r < fa.rounds; ++r, ++j) {
-#pragma unroll 1
-    for (uint32_t i = 0; i < tape.n_ops; ++i) {
-      const uint32_t x = tape.ops[i];
-      const uint32_t op = x & 0xFF, dst = (x >> 8) & 0xFF, a = (x >> 16) & 0xFF, b = x >> 24;
-      Fe<P> v;
-      switch (op) {
-        case VDF_TAPE_ADV: v = slot_load<P>(tape_slots, stand + a, lane); break;      // (the launcher admits b = 0 only)
-        case VDF_TAPE_INV: v = tape_fe<P>(tape.inv[a]); break;
-        case VDF_TAPE_J: v = fe_from_u64<P>(j); break;
-        case VDF_TAPE_CONST: v = tape_fe<P>(tape.consts[a]); break;
-        case VDF_TAPE_ADD: v = fe_add(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
-        case VDF_TAPE_SUB: v = fe_sub(slot_load<P>(tape_slots, a, lane), slot_load<P>(tape_slots, b, lane)); break;
-        case VDF_TAPE_MUL: {
-          const Fe<P> y = slot_load<P>(tape_slots, a, lane);
-          v = a == b ? fe_sqr(y) : fe_mul(y, slot_load<P>(tape_slots, b, lane));
-          break;
-        }
-        case VDF_TAPE_SCALE: v = fe_mul(slot_load<P>(tape_slots, a, lane), tape_fe<P>(tape.consts[b])); break;
-        case VDF_TAPE_POW: {
-          uint32_t q = 8, word = 0;                    // words of the exponent still to read, and the one being read
-          while (q && (word = tape.consts[b].v[q - 1]) == 0) --q;
-          if (q == 0) { v = fe_one<P>(); break; }      // E = 0
-          const Fe<P> y = slot_load<P>(tape_slots, a, lane);
-          v = y;                                       // the top set bit
-          int bit = 31 - __builtin_clz(word);
-          for (;;) {
-#pragma unroll 1
-            while (bit-- > 0) {
-              v = fe_sqr(v);
-              if ((word >> bit) & 1) v = fe_mul(v, y);
-            }
-            if (--q == 0) break;
-            word = tape.consts[b].v[q - 1];
-            bit = 32;
-          }
-          break;
-        }
-        case VDF_TAPE_POWC: {
-          const uint32_t* const cw = cwords + b * 8;   // word 0: n_steps | n_tmp << 8; word 1 + k: step k (the launcher checked all)
-          const uint32_t n_steps = cw[0] & 0xFF;
-          v = slot_load<P>(tape_slots, a, lane);
-          slot_store<P>(tape_slots, tmp0, lane, v);    // T[0] = the base
-#pragma unroll 1
-          for (uint32_t k = 0; k < n_steps; ++k) {
-            const uint32_t st = cw[1 + k];
-            const uint32_t src = st & 0xFF, mul = (st >> 16) & 0xFF, keep = st >> 24;
-            if (src != VDF_POW_ACC) v = slot_load<P>(tape_slots, tmp0 + src, lane);
-#pragma unroll 1
-            for (uint32_t q = (st >> 8) & 0xFF; q; --q) v = fe_sqr_lazy(v);
-            if (mul != VDF_POW_NONE) v = fe_mul_lazy(v, slot_load<P>(tape_slots, tmp0 + mul, lane));
-            if (keep != VDF_POW_NONE) slot_store<P>(tape_slots, tmp0 + keep, lane, v);
-          }
-          v = fe_canon(v);                             // below 2m + 350 eps (above): two conditional subtractions
-          break;
-        }
-        default:                       // VDF_TAPE_OUT
-          slot_store<P>(tape_slots, prod + b, lane, slot_load<P>(tape_slots, a, lane));
-          continue;
-      }
-      slot_store<P>(tape_slots, dst, lane, v);
-    }
+    const WalkIO<P, false> io = {stand, prod, 0};
+    tape_round<P, ADMIT>(tape, slots, lane, j, io, tmp0);
     const uint32_t t = stand; stand = prod; prod = t;
     if (tp) {
-      for (uint32_t c = 0; c < na; ++c) fe_store<P>(tp + c * 32, slot_load<P>(tape_slots, stand + c, lane));
+      for (uint32_t c = 0; c < na; ++c) fe_store<P>(tp + c * 32, slot_load<P>(slots, stand + c, lane));
       tp += esz;
     }
     if (cp && --cp_left == 0) {
-      for (uint32_t c = 0; c < na; ++c) fe_store<P>(cp + c * 32, slot_load<P>(tape_slots, stand + c, lane));
+      for (uint32_t c = 0; c < na; ++c) fe_store<P>(cp + c * 32, slot_load<P>(slots, stand + c, lane));
       cp += esz;
       cp_left = fa.every;
     }
   }
-  for (uint32_t c = 0; c < na; ++c) fe_store<P>(ep + c * 32, slot_load<P>(tape_slots, stand + c, lane));
+  for (uint32_t c = 0; c < na; ++c) fe_store<P>(ep + c * 32, slot_load<P>(slots, stand + c, lane));
 }
 
+template <class P>
+__global__ __launch_bounds__(64) void k_tape_forward_walk(TapeArgs tape, ForwardArgs fa, char* __restrict__ entries,
+                                                          char* __restrict__ checkpoints, char* __restrict__ trace) {
+  extern __shared__ uint4 tape_slots[];
+  tape_forward_walk<P, TAPE_POW>(tape, fa, tape_slots, entries, checkpoints, trace);
+}
+
+template <class P>
+__global__ __launch_bounds__(64) void k_tape_forward_walk_chain(TapeArgs tape, ForwardArgs fa, char* __restrict__ entries,
+                                                                char* __restrict__ checkpoints, char* __restrict__ trace) {
+  extern __shared__ uint4 tape_slots[];
+  tape_forward_walk<P, TAPE_POWC>(tape, fa, tape_slots, entries, checkpoints, trace);
+}
 // ---- periodic rows: the cross term of the rows of such rounds without the sparse matrices (vdf_hip.h vdf_periodic_rows) --------
 // k_nifs_cross_minroot_forward_lanes for a round the library did not write: one row per lane, workgroups of 256, every running /
 // fresh vector read and written as contiguous 32-byte elements.  What the hand-written stencil has in its code -- which columns a
@@ -585,86 +454,31 @@ __global__ __launch_bounds__(256) void k_nifs_cross_periodic(PeriodicArgs pa, co
 }
 
 static TapeFe tape_val(const vdf_fe* p) { TapeFe v; std::memcpy(&v, p, 32); return v; }
-// what k_tape_forward_walk spends on a POW of exponent e: bitlen - 1 squarings and popcount - 1 products, at least one
-static uint64_t pow_products(const TapeFe& e) {
-  uint64_t bits = 0, ones = 0;
-  for (int q = 0; q < 8; ++q)
-    if (e.v[q]) { bits = 32 * q + 32 - __builtin_clz(e.v[q]); ones += __builtin_popcount(e.v[q]); }
-  return bits + ones > 2 ? bits + ones - 2 : 1;
-}
-
-// Everything a tape could index out of range is checked here, before a launch: opcodes, slots against n_slots, columns,
-// constants, invariants and variables against their counts, reads of slots nothing has written, variables written twice or never.
-// TAPE_WALK / TAPE_FORWARD: the rules of a walk tape on top (vdf_hip.h): n_vars == n_adv, no ADV of the entry being produced
-// (b = 0 descending, b = 1 ascending).  VDF_TAPE_POW and VDF_TAPE_POWC are ops of forward tapes only.  products (if asked for): the
-// field products of one round, a POW or POWC counted as its squarings and multiplications.  A POWC's chain is checked by
-// pow_chain.h (valid, inside n_consts, zero padding); chain_tmp (if asked for): the largest n_tmp of the tape's chains, 0 for a
-// tape without a POWC -- the slots k_tape_forward_walk_chain keeps behind the two entries.
-enum TapeMode { TAPE_ROUND, TAPE_WALK, TAPE_FORWARD };
-// lanes: inv holds lanes * n_inv elements, lane-major; all of them go into the block of VDF_TAPE_MAX_INV (the *_lanes launchers).
-static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, TapeMode mode, TapeArgs& a, uint64_t* products = nullptr, size_t lanes = 1,
-                        uint32_t* chain_tmp = nullptr) {
-  const bool walk = mode != TAPE_ROUND;
-  if (!tp || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts)) return Status{VDF_ERR_BAD_ARG, "null tape"};
-  if (tp->n_ops > VDF_TAPE_MAX_OPS || tp->n_consts > VDF_TAPE_MAX_CONSTS || tp->n_slots > VDF_TAPE_MAX_SLOTS || tp->n_vars > VDF_TAPE_MAX_VARS ||
-      tp->n_inv > VDF_TAPE_MAX_INV || tp->n_adv > VDF_TAPE_MAX_ADV || tp->n_vars == 0 || tp->n_adv == 0 || tp->n_slots == 0)
-    return Status{VDF_ERR_BAD_ARG, "tape exceeds a published cap (VDF_TAPE_MAX_*), or has no variable, slot or advice column"};
-  if (walk && tp->n_vars != tp->n_adv) return Status{VDF_ERR_BAD_ARG, "walk tape: n_vars != n_adv (a round writes one advice entry)"};
+// Check, then pack: tape_rules.h refuses everything a tape could index out of range, before a launch; what is left here is what
+// only a launch has -- the lanes (inv holds lanes * n_inv elements, lane-major; all of them go into the block of VDF_TAPE_MAX_INV:
+// the *_lanes launchers) -- and the words of TapeArgs.  info (if asked for): the products per round and the chains' n_tmp.
+static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, vdftape::Mode mode, TapeArgs& a, vdftape::Info* info = nullptr, size_t lanes = 1) {
+  vdftape::Info got;
+  const std::string why = vdftape::check(tp, mode, &got);
+  if (!why.empty()) return Status{VDF_ERR_BAD_ARG, why};
   if (lanes == 0 || lanes > VDF_TAPE_MAX_LANES) return Status{VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_TAPE_MAX_LANES"};
   if (lanes * tp->n_inv > VDF_TAPE_MAX_INV) return Status{VDF_ERR_BAD_ARG, "lanes * n_inv > VDF_TAPE_MAX_INV (all lanes' inv travel in the kernel arguments)"};
   if (tp->n_inv && !inv) return Status{VDF_ERR_BAD_ARG, "null inv"};
   std::memset(&a, 0, sizeof(a));
   a.n_ops = (uint32_t)tp->n_ops; a.n_vars = tp->n_vars; a.n_adv = tp->n_adv;
-  bool written[VDF_TAPE_MAX_SLOTS] = {}, var_out[VDF_TAPE_MAX_VARS] = {};
-  uint64_t n_products = 0;
-  uint32_t max_tmp = 0;
   for (size_t i = 0; i < tp->n_ops; ++i) {
     const vdf_tape_op& o = tp->ops[i];
-    auto slot_ok = [&](uint8_t x) { return x < tp->n_slots && written[x]; };
-    bool ok = false;
-    switch (o.op) {
-      case VDF_TAPE_ADV: ok = o.a < tp->n_adv && (mode == TAPE_WALK ? o.b == 1 : mode == TAPE_FORWARD ? o.b == 0 : o.b <= 1); break;
-      case VDF_TAPE_INV: ok = o.a < tp->n_inv; break;
-      case VDF_TAPE_J: ok = true; break;
-      case VDF_TAPE_CONST: ok = o.a < tp->n_consts; break;
-      case VDF_TAPE_ADD: case VDF_TAPE_SUB: ok = slot_ok(o.a) && slot_ok(o.b); break;
-      case VDF_TAPE_MUL: ok = slot_ok(o.a) && slot_ok(o.b); ++n_products; break;
-      case VDF_TAPE_SCALE: ok = slot_ok(o.a) && o.b < tp->n_consts; ++n_products; break;
-      case VDF_TAPE_OUT: ok = slot_ok(o.a) && o.b < tp->n_vars && !var_out[o.b]; if (ok) var_out[o.b] = true; break;
-      case VDF_TAPE_POW:
-        ok = mode == TAPE_FORWARD && slot_ok(o.a) && o.b < tp->n_consts;
-        if (ok) n_products += pow_products(tape_val(&tp->consts[o.b]));
-        break;
-      case VDF_TAPE_POWC:
-        ok = mode == TAPE_FORWARD && slot_ok(o.a);
-        if (ok) {
-          vdfpow::ChainInfo ci;
-          const std::string why = vdfpow::check_packed(tp->consts, tp->n_consts, o.b, &ci, nullptr, nullptr);
-          if (!why.empty()) return Status{VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + ": the chain of a POWC: " + why};
-          n_products += ci.products();
-          if (ci.n_tmp > max_tmp) max_tmp = ci.n_tmp;
-        }
-        break;
-      default: break;
-    }
-    if (ok && o.op != VDF_TAPE_OUT) { ok = o.dst < tp->n_slots; if (ok) written[o.dst] = true; }
-    if (!ok) return Status{VDF_ERR_BAD_ARG, "tape op " + std::to_string(i) + " is malformed (opcode, index out of range, or a slot read before it is written)" +
-                                            (mode == TAPE_WALK ? "; a walk tape loads advice with b = 1 only" :
-                                             mode == TAPE_FORWARD ? "; a forward walk tape loads advice with b = 0 only" : "")};
     a.ops[i] = (uint32_t)o.op | (uint32_t)o.dst << 8 | (uint32_t)o.a << 16 | (uint32_t)o.b << 24;
   }
-  for (uint32_t v = 0; v < tp->n_vars; ++v)
-    if (!var_out[v]) return Status{VDF_ERR_BAD_ARG, "tape leaves variable " + std::to_string(v) + " unwritten"};
   for (size_t k = 0; k < tp->n_consts; ++k) a.consts[k] = tape_val(&tp->consts[k]);
   for (size_t k = 0; k < lanes * tp->n_inv; ++k) a.inv[k] = tape_val(&inv[k]);
-  if (products) *products = n_products ? n_products : 1;
-  if (chain_tmp) *chain_tmp = max_tmp;
+  if (info) *info = got;
   return Status{};
 }
 
 Status vec_round_tape(int field, const vdf_round_tape* tp, uint64_t t, const vdf_fe* inv, const void* advice, void* out, hipStream_t s) {
   TapeArgs a;
-  VDF_TRY(pack_tape(tp, inv, TAPE_ROUND, a));
+  VDF_TRY(pack_tape(tp, inv, vdftape::ROUND, a));
   // advice read + variables written per repetition
   KTimer kt(s, "k_round_tape", 32.0 * (tp->n_adv + tp->n_vars) * t);
   const dim3 grid((unsigned)((t + 63) / 64));
@@ -708,10 +522,10 @@ Status vec_round_tape_walk(int field, const vdf_round_tape* tp, const vdf_fe* in
                            int heads, const void* expect, int32_t* ok, hipStream_t s) {
   VDF_TRY(check_field(field));
   TapeArgs a;
-  uint64_t products = 1;
-  VDF_TRY(pack_tape(tp, inv, TAPE_WALK, a, &products));
+  vdftape::Info ti;
+  VDF_TRY(pack_tape(tp, inv, vdftape::WALK, a, &ti));
   bool nothing = false;
-  VDF_TRY(walk_launch_checks(tp, 0, products, n, rounds, entries, trace, top, heads, expect, ok, &nothing));
+  VDF_TRY(walk_launch_checks(tp, 0, ti.products, n, rounds, entries, trace, top, heads, expect, ok, &nothing));
   if (nothing) return Status{};
   const WalkArgs wa = walk_args(tp, n, rounds, walk_stride, top, group, group_stride, j_base, j_group_step, heads);
   KTimer kt(s, "k_tape_walk", trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0);
@@ -726,7 +540,7 @@ Status vec_round_tape_lanes(int field, const vdf_round_tape* tp, uint64_t t, siz
                             size_t lane_stride, void* out, hipStream_t s) {
   VDF_TRY(check_field(field));
   TapeArgs a;
-  VDF_TRY(pack_tape(tp, inv, TAPE_ROUND, a, nullptr, lanes));
+  VDF_TRY(pack_tape(tp, inv, vdftape::ROUND, a, nullptr, lanes));
   if (t == 0 || t >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
   if (lane_stride < t + 1 || lane_stride > ((size_t)1 << 40)) return Status{VDF_ERR_BAD_ARG, "lane_stride must be at least t + 1"};
   LaneRunArgs la;
@@ -745,11 +559,11 @@ Status vec_round_tape_walk_lanes(int field, const vdf_round_tape* tp, size_t lan
                                  uint64_t j_group_step, int heads, const void* expect, int32_t* ok, hipStream_t s) {
   VDF_TRY(check_field(field));
   TapeArgs a;
-  uint64_t products = 1;
-  VDF_TRY(pack_tape(tp, inv, TAPE_WALK, a, &products, lanes));
+  vdftape::Info ti;
+  VDF_TRY(pack_tape(tp, inv, vdftape::WALK, a, &ti, lanes));
   if (!j_base) return Status{VDF_ERR_BAD_ARG, "null j_base"};
   bool nothing = false;
-  VDF_TRY(walk_launch_checks(tp, tp->n_inv, products, n, rounds, entries, trace, top, heads, expect, ok, &nothing));
+  VDF_TRY(walk_launch_checks(tp, tp->n_inv, ti.products, n, rounds, entries, trace, top, heads, expect, ok, &nothing));
   if (nothing) return Status{};
   WalkLanesArgs wl;
   std::memset(&wl, 0, sizeof(wl));
@@ -764,15 +578,20 @@ Status vec_round_tape_walk_lanes(int field, const vdf_round_tape* tp, size_t lan
   });
 }
 
+// a forward tape checked and packed, and its slot cap (ti.chain_tmp > 0: the tape holds a POWC)
+static Status pack_forward_tape(const vdf_round_tape* tp, const vdf_fe* inv, TapeArgs& a, vdftape::Info& ti) {
+  VDF_TRY(pack_tape(tp, inv, vdftape::FORWARD, a, &ti));
+  if (tp->n_slots + 2 * tp->n_adv + ti.chain_tmp > VDF_WALK_MAX_SLOTS)
+    return Status{VDF_ERR_BAD_ARG, "forward walk tape: n_slots + 2 * n_adv + the chains' n_tmp > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"};
+  return Status{};
+}
+
 // the forward-tape rules and the work cap, nothing launched: the rounds one call may run (vdf_round_tape_eval_batch cuts by it)
 Status round_tape_forward_max_rounds(const vdf_round_tape* tp, const vdf_fe* inv, uint64_t* max_rounds) {
   TapeArgs a;
-  uint64_t products = 1;
-  uint32_t chain_tmp = 0;
-  VDF_TRY(pack_tape(tp, inv, TAPE_FORWARD, a, &products, 1, &chain_tmp));
-  if (tp->n_slots + 2 * tp->n_adv + chain_tmp > VDF_WALK_MAX_SLOTS)
-    return Status{VDF_ERR_BAD_ARG, "forward walk tape: n_slots + 2 * n_adv + the chains' n_tmp > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"};
-  *max_rounds = VDF_FORWARD_TAPE_MAX_WORK / products;
+  vdftape::Info ti;
+  VDF_TRY(pack_forward_tape(tp, inv, a, ti));
+  *max_rounds = VDF_FORWARD_TAPE_MAX_WORK / ti.products;
   return Status{};
 }
 
@@ -781,12 +600,9 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tp, const vd
                                    uint64_t j_base, uint64_t j_walk_step, hipStream_t s) {
   VDF_TRY(check_field(field));
   TapeArgs a;
-  uint64_t products = 1;
-  uint32_t chain_tmp = 0;                            // > 0: the tape holds a POWC
-  VDF_TRY(pack_tape(tp, inv, TAPE_FORWARD, a, &products, 1, &chain_tmp));
-  if (tp->n_slots + 2 * tp->n_adv + chain_tmp > VDF_WALK_MAX_SLOTS)
-    return Status{VDF_ERR_BAD_ARG, "forward walk tape: n_slots + 2 * n_adv + the chains' n_tmp > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"};
-  if (rounds > VDF_FORWARD_TAPE_MAX_WORK / products)
+  vdftape::Info ti;
+  VDF_TRY(pack_forward_tape(tp, inv, a, ti));
+  if (rounds > VDF_FORWARD_TAPE_MAX_WORK / ti.products)
     return Status{VDF_ERR_BAD_ARG, "rounds x products per round > VDF_FORWARD_TAPE_MAX_WORK in one call: cut the walk"};
   if (checkpoints && every == 0) return Status{VDF_ERR_BAD_ARG, "checkpoints without `every`"};
   if (n == 0 || rounds == 0) return Status{};
@@ -797,18 +613,14 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tp, const vd
   fa.n = n; fa.walk_stride = walk_stride; fa.cp_stride = cp_stride; fa.every = every; fa.base = base;
   fa.j_base = j_base; fa.j_walk_step = j_walk_step;
   fa.rounds = (uint32_t)rounds; fa.n_slots = tp->n_slots;
-  KTimer kt(s, chain_tmp ? "k_tape_forward_walk_chain" : "k_tape_forward_walk",
+  const bool chain = ti.chain_tmp != 0;      // a tape with a POWC: the kernel that also runs addition chains; every other tape: the one without
+  KTimer kt(s, chain ? "k_tape_forward_walk_chain" : "k_tape_forward_walk",
             (trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0) + 64.0 * tp->n_adv * (double)n);
-  const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv + chain_tmp) * 2 * 64 * sizeof(uint4);
-  const dim3 grid((unsigned)((n + 63) / 64));
-  if (chain_tmp)        // a tape with a POWC: the interpreter that also runs addition chains; every other tape: the kernel as it was
-    return with_field(field, [&](auto f) {
-      hipLaunchKernelGGL((k_tape_forward_walk_chain<tag_t<decltype(f)>>), grid, dim3(64), lds, s, a, fa, bytes_of(entries), bytes_of(checkpoints),
-                         bytes_of(trace));
-    });
+  const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv + ti.chain_tmp) * 2 * 64 * sizeof(uint4);
   return with_field(field, [&](auto f) {
-    hipLaunchKernelGGL((k_tape_forward_walk<tag_t<decltype(f)>>), grid, dim3(64), lds, s, a, fa, bytes_of(entries), bytes_of(checkpoints),
-                       bytes_of(trace));
+    using P = tag_t<decltype(f)>;
+    hipLaunchKernelGGL(chain ? k_tape_forward_walk_chain<P> : k_tape_forward_walk<P>, dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, fa,
+                       bytes_of(entries), bytes_of(checkpoints), bytes_of(trace));
   });
 }
 
