@@ -175,8 +175,18 @@ typedef struct vdf_nova_tuning {
   int32_t  periodic_rows;        /* 1: a custom circuit whose vdf_cs_repeat rows are periodic (vdf_nova_pp_periodic_rows) gets their share of the
                                     cross term from the description, without the sparse matrices (vdf_nova_pp_stencil == 7); 0: the generic
                                     kernel over every row (0 until measured).  The proofs are the same bytes either way */
+  int32_t  custom_ahead;         /* a custom circuit with a vdf_cs_repeat, in the steps a chain drives (vdf_nova_prove_step_custom_chain,
+                                    vdf_nova_prove_recursively_custom): 0 = the repeat's rounds, their commitment and all of T inside the step
+                                    (default); 1 = the NEXT step's rounds and their commitment on the lookahead queue, as for a built-in kind;
+                                    2 = that, and the rows of T that read only those rounds and z_in on the early-rows queue
+                                    (vdf_nova_pp_early_rows).  Costs one more `synthesize` per step (the probe, vdf_cs_is_probe).  The proofs
+                                    are the same bytes in all three; every other circuit and driver ignores it */
 } vdf_nova_tuning;
 void vdf_nova_tuning_default(vdf_nova_tuning* out);
+/* Host only.  The tuning a constructor would run with when handed `tuning` (NULL = the defaults): a struct_size smaller than this
+ * build's, down to the struct as it was before `custom_ahead`, is a caller compiled against an older header -- the fields it does
+ * not have read as 0; VDF_ERR_BAD_ARG for any other struct_size and for a field out of range.  out->struct_size = this build's. */
+int  vdf_nova_tuning_read(const vdf_nova_tuning* tuning, vdf_nova_tuning* out);
 /* public_params with the tuning given (NULL = the defaults); VDF_ERR_BAD_ARG for a field out of range */
 int  vdf_nova_public_params_tuned(vdf_ctx* ctx, uint64_t num_iters_per_step, int circuit_kind, int gens_family,
                                   const vdf_nova_tuning* tuning, vdf_pp** out);
@@ -226,7 +236,9 @@ int  vdf_nova_pp_sizes(const vdf_pp* pp, int side, uint64_t* num_cons, uint64_t*
 int  vdf_nova_pp_digest(const vdf_pp* pp, uint8_t out[32]);
 int  vdf_nova_pp_segment(const vdf_pp* pp, uint64_t* begin, uint64_t* len);
 /* the run of primary constraints whose share of a step's cross term T and of comm_T prove_step makes ahead of the rest of
- * the step (they read only that segment, the step's input and the constant); len = 0: none, T is committed in one piece */
+ * the step (they read only that segment, the step's input and the constant); len = 0: none, T is committed in one piece.
+ * A custom circuit: the run when tuning.custom_ahead = 2 (the same rule: the longest run, no row of more than 8 entries per
+ * matrix, at least 64 rows), else 0, 0 */
 int  vdf_nova_pp_early_rows(const vdf_pp* pp, uint64_t* begin, uint64_t* len);
 /* 4 / 3: the early rows are the built-in MinRoot stencil (the reference's rounds / the bound form), verified against the
  * shape's triples when the parameters were made -- their cross term runs without the sparse matrices
@@ -236,7 +248,8 @@ int  vdf_nova_pp_early_rows(const vdf_pp* pp, uint64_t* begin, uint64_t* len);
  * 6 (VDF_STENCIL_FORWARD_LANES): the forward circuit in lanes, all L (3t + 1) early rows as one run
  * (vdf_nifs_cross_term_minroot_forward_lanes) -- a code like 5;
  * 7 (VDF_STENCIL_PERIODIC): a custom circuit whose vdf_cs_repeat rows are periodic, with tuning.periodic_rows = 1: those rows run
- * from their description (vdf_hip.h vdf_nifs_cross_term_periodic), every other row through the generic kernel */
+ * from their description (vdf_hip.h vdf_nifs_cross_term_periodic), every other row through the generic kernel -- on the
+ * early-rows queue when the step has early rows (tuning.custom_ahead = 2), on the step's own otherwise */
 enum { VDF_STENCIL_FORWARD = 5, VDF_STENCIL_FORWARD_LANES = 6, VDF_STENCIL_PERIODIC = 7 };
 int  vdf_nova_pp_stencil(const vdf_pp* pp);
 /* 1 when the parameters of a custom circuit carry a periodic description of its vdf_cs_repeat rows (whatever the tuning says about
@@ -417,6 +430,7 @@ typedef struct {
   void* self;
 } vdf_step_circuit;
 int     vdf_cs_is_witness(const vdf_cs* cs);                          /* 1: values are live; 0: the shape is being recorded */
+int     vdf_cs_is_probe(const vdf_cs* cs);                            /* 1: the extra witness synthesis of tuning.custom_ahead (below) */
 vdf_num vdf_cs_const(vdf_cs* cs, const vdf_fe* k);                    /* the constant k (Montgomery form) */
 vdf_num vdf_cs_add(vdf_cs* cs, vdf_num a, vdf_num b);
 vdf_num vdf_cs_sub(vdf_cs* cs, vdf_num a, vdf_num b);
@@ -460,8 +474,8 @@ int     vdf_cs_value(const vdf_cs* cs, vdf_num a, vdf_fe* out);       /* witness
  * parameters read that off the shape's triples, compare it with every triple of every repetition, and keep the description
  * (vdf_nova_pp_periodic_rows).  With tuning.periodic_rows = 1 a step's cross term then takes those rows from the description
  * (vdf_hip.h vdf_nifs_cross_term_periodic) and only the others through the sparse matrices; a circuit whose rows are not periodic
- * (a carry that accumulates: its rows grow with j) keeps the generic kernel.  Out of scope for custom circuits: early rows of
- * the cross term, lookahead and a second repeat (T is made and committed in one piece). */
+ * (a carry that accumulates: its rows grow with j) keeps the generic kernel.  Lookahead and early rows of the cross term: for
+ * the steps a chain drives, tuning.custom_ahead (THE PROBE, below).  Out of scope for custom circuits: a second repeat. */
 #define VDF_ROUND_MAX_INV 16
 #define VDF_ROUND_MAX_CARRY 8
 #define VDF_ROUND_MAX_ADV 8
@@ -652,7 +666,26 @@ int  vdf_nova_public_params_custom_tuned(vdf_ctx* ctx, int field, const vdf_step
  * and targets (2 * walks entries, lanes > 1 only) while that window's walks are pending; it is freed when they resolve.
  * vdf_nova_custom_chain_from_checkpoints is this call with lanes = 1.  The two provers work unchanged above it and refuse a
  * chain whose lanes are not the parameters' ("the chain has L lanes, the parameters' vdf_cs_repeat has M").
- * Out of scope for custom chains: lookahead, early rows of T, a second vdf_cs_repeat, a streaming eval_and_prove, lanes of
+ *
+ * LOOKAHEAD AND EARLY ROWS (tuning.custom_ahead = 1 / 2; 0, the default, is the schedule above launch for launch).  A chain knows
+ * step k + 1's advice while step k runs, so the rounds of step k + 1's repeat and their commitment can be made on the lookahead
+ * queue during step k, and (mode 2) the rows of T that read nothing but those rounds, z_in and the constant on the early-rows queue,
+ * as for a built-in kind.  What the library does not know is the repeat's `inv` of step k + 1: linear combinations of variables
+ * only `synthesize` makes.  THE PROBE: once step k's primary circuit has produced z_(k+1), `synthesize` is called ONE EXTRA TIME per
+ * step on a throw-away witness-mode vdf_cs whose z_in holds z_(k+1) and whose vdf_cs_step_advice is step k + 1's trace.
+ * vdf_cs_is_probe answers 1 there (0 everywhere else), so a circuit may skip host work it does not need; in that call
+ * vdf_cs_repeat[_lanes] records the body and keeps the values of `inv`, reads nothing of the advice (the carry_out it returns have
+ * the value 0), and makes no variable and no row; everything else the circuit does works on values nobody keeps.  THE CONTRACT:
+ * `synthesize` must be a function of z_in and the step's advice -- a circuit that counts its calls, or computes `inv` from anything
+ * else, is not broken by the probe but gets nothing from it.  The real step compares what its own vdf_cs_repeat sees with what the
+ * lookahead used: the bytes of `inv`, the advice pointer, t, lanes and lane_stride, the chain object and k.  Equal: a HIT, the
+ * rounds are not made again.  Anything else: a MISS -- the side queues are drained, what they made is discarded, and the step runs
+ * as under custom_ahead = 0.  No lookahead is attempted (the step is SKIPPED) over a trace whose walks are still pending or not
+ * checked against their checkpoints, or beyond the chain.  A miss or a skip costs time, never correctness: the proof is byte for
+ * byte the same in every case.  vdf_nova_proof_ahead_stats counts the three.  A repeat whose rows read some other variable of the
+ * circuit has no early rows, and mode 2 is mode 1 for it.
+ * Out of scope for custom chains: custom_ahead for steps not driven by a chain (plain vdf_nova_prove_step_custom keeps the schedule
+ * of custom_ahead = 0: the library does not know its next advice), a second vdf_cs_repeat, a streaming eval_and_prove, lanes of
  * different length. */
 typedef struct vdf_custom_chain vdf_custom_chain;
 #define VDF_CUSTOM_CHECK_STEPS 1u
@@ -682,10 +715,15 @@ int  vdf_nova_prove_recursively_custom(vdf_pp* pp, const vdf_step_circuit* prima
 /* Which constraint of the LAST step is unsatisfied: *count = the rows r of the fresh primary instance with (A z)[r] (B z)[r] !=
  * (C z)[r], *first_row = the smallest (UINT64_MAX: none); vdf_hip.h vdf_unsat_rows.  For proofs of every circuit kind.  The step's
  * own A z, B z, C z do not outlive it on every path (the base step folds nothing and never makes them apart from the running
- * instance's; a built-in kind's next early rows overwrite theirs on the way out of the step; a verifier uses the vectors as
+ * instance's; the next step's early rows -- a built-in kind's, or a custom chain's under tuning.custom_ahead = 2 -- overwrite
+ * theirs on the way out of the step; a verifier uses the vectors as
  * scratch), so they are made again from the fresh z, which stays in its ring slot until the next step: one sparse product into
  * three vectors the first request allocates.  VDF_ERR_BAD_ARG before this object's first prove_step (a deserialised proof too). */
 int  vdf_nova_proof_last_unsat(const vdf_proof* proof, uint64_t* count, uint64_t* first_row);
+/* Of the steps after the first that this proof object proved: in how many a lookahead of a custom chain (tuning.custom_ahead) was
+ * used (*hits), discarded (*misses), or not attempted (*skipped).  All three are 0 for every other kind of proof, for
+ * custom_ahead = 0 and for steps of plain vdf_nova_prove_step_custom.  Outputs may be NULL. */
+int  vdf_nova_proof_ahead_stats(const vdf_proof* proof, uint64_t* hits, uint64_t* misses, uint64_t* skipped);
 /* The rows of a custom circuit's vdf_cs_repeat: repetition j, constraint c is row *row_begin + j * *n_cons + c, j < *t.  Returns 1,
  * or 0 for parameters without a repeat (outputs 0); does not depend on the rows being periodic. */
 int  vdf_nova_pp_repeat_rows(const vdf_pp* pp, uint64_t* row_begin, uint64_t* n_cons, uint64_t* t);
@@ -733,6 +771,13 @@ int  vdf_nova_shape_periodic_custom(int field, const vdf_step_circuit* primary, 
                                     vdf_periodic_term terms[VDF_PERIODIC_MAX_TERMS], vdf_fe consts[VDF_PERIODIC_MAX_CONSTS],
                                     vdf_periodic_rows* out, uint64_t* seg_begin, uint64_t* lead, uint64_t* first_row, uint64_t* row_count,
                                     uint64_t* num_cons, uint64_t* num_cols);
+/* The early rows public_params_custom would find under tuning.custom_ahead = 2, without a device: the longest run of primary
+ * constraints that read nothing of a witness but the variables of the circuit's vdf_cs_repeat, the constant and the `arity`
+ * variables of z_in where the augmented circuit allocates them, none of more than 8 entries in any matrix; *rows = 0 (and
+ * *row_begin = 0) when the run is shorter than 64 rows or the circuit has no repeat.  *zin_begin = the column of z_in[0],
+ * *seg_begin = the first variable of repetition 0 (0 without a repeat).  Outputs may be NULL. */
+int  vdf_nova_shape_early_rows_custom(int field, const vdf_step_circuit* primary, uint64_t* row_begin, uint64_t* rows,
+                                      uint64_t* zin_begin, uint64_t* seg_begin);
 /* One augmented circuit synthesised on the host with every variable computed there (small t only).  The inputs that
  * belong to the folded side (U_u, U_X, u_X) are in Montgomery form of THAT side's scalar field, everything else in the
  * circuit's own field.  result / input: the MinRoot step's states (side 0; ignored for side 1).  arity = 3 / 1. */

@@ -157,6 +157,9 @@ int chain_pump(vdf_custom_chain* c, size_t k) {
 }
 int chain_settle(vdf_custom_chain* c) { return job_resolve(c, nullptr, 0, 0); }
 bool chain_resident(const vdf_custom_chain* c, size_t k) { return c->v[k].d_trace != nullptr; }
+const vdf_fe* chain_ready(const vdf_custom_chain* c, size_t k) {
+  return k < c->v.size() && !c->job_covers(k) ? (const vdf_fe*)c->v[k].d_trace : nullptr;
+}
 void chain_park(vdf_custom_chain* c, size_t k) { release_range(c, k, 1, true); }
 void chain_drop_spare(vdf_custom_chain* c) { c->spare.reset(); }
 }  // namespace vdfnova

@@ -3,6 +3,7 @@
 // circuits_host.cpp's.  Protocol "vdf-nova-ivc-v1", specified by oracle/nova.py; see include/vdf_nova.h.
 #include <sys/random.h>
 #include <cerrno>
+#include <cstddef>
 #include <condition_variable>
 #include <deque>
 #include <thread>
@@ -71,6 +72,7 @@ struct CustomStepCircuit : StepCircuit {
   vdf_ctx* ctx = nullptr;                 // a prover's: lets a vdf_cs_repeat take advice in device memory
   const vdf_fe* step_advice = nullptr;    // ... driven by a chain: the step's device trace (vdf_cs_step_advice)
   size_t step_advice_elems = 0;           // ... and the elements it holds: a repeat that would read past them is refused
+  bool probe = false;                     // the extra synthesis of tuning.custom_ahead (vdf_cs_is_probe)
   mutable int rc = 0;
   mutable RepeatState rep;                // the vdf_cs_repeat of the last synthesis, if it had one
   size_t arity() const override { return c.arity; }
@@ -79,6 +81,7 @@ struct CustomStepCircuit : StepCircuit {
     h.cs = &cs; h.pool = z; h.rep = &rep; h.ctx = ctx;
     h.step_advice = cs.shape ? nullptr : step_advice;
     h.step_advice_elems = cs.shape ? 0 : step_advice_elems;
+    h.probe = probe && !cs.shape;
     rep = RepeatState();
     std::vector<vdf_num> zin(c.arity), zout(c.arity, 0);
     for (size_t k = 0; k < c.arity; ++k) zin[k] = (vdf_num)k;
@@ -94,18 +97,21 @@ struct CustomStepCircuit : StepCircuit {
 };
 }  // namespace
 namespace vdfnova {
-std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx, const vdf_fe* step_advice, size_t step_advice_elems) {
+std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx, const vdf_fe* step_advice, size_t step_advice_elems,
+                                                 bool probe) {
   std::unique_ptr<CustomStepCircuit> m(new CustomStepCircuit());
   m->c = *c;
   m->ctx = ctx;
   m->step_advice = step_advice;
   m->step_advice_elems = step_advice_elems;
+  m->probe = probe;
   return std::unique_ptr<StepCircuit>(m.release());
 }
 }  // namespace vdfnova
 
 extern "C" {
 int vdf_cs_is_witness(const vdf_cs* c) { return c && !c->cs->shape ? 1 : 0; }
+int vdf_cs_is_probe(const vdf_cs* c) { return c && c->probe ? 1 : 0; }
 const vdf_fe* vdf_cs_step_advice(const vdf_cs* c) { return c && !c->rec ? c->step_advice : nullptr; }
 vdf_num vdf_cs_const(vdf_cs* c, const vdf_fe* k) {
   if (c->rec) return rec_cs_const(c, k);
@@ -748,7 +754,20 @@ bool tuning_valid(const vdf_nova_tuning& t) {
          in(t.small_window, 6, 16) && in(t.big_window, 12, 20) && in(t.packed_commit, 0, 1) && in(t.lookahead_early, 0, 1) &&
          in(t.gate_accumulate, 0, 1) && in(t.fold_on_rows, 0, 1) && in(t.nifs_ahead, 0, 1) && in(t.early_row_parts, 1, 3) &&
          in(t.lookahead_priority, 0, 3) && in(t.side_accumulate_fill, 1, 3) && in(t.verbose, 0, 1) && in(t.compress_queues, 0, 1) && in(t.rows_at_challenge, 0, 1) &&
-         in(t.fold_fused, 0, 1) && in(t.periodic_rows, 0, 1);
+         in(t.fold_fused, 0, 1) && in(t.periodic_rows, 0, 1) && in(t.custom_ahead, 0, 2);
+}
+// the tuning a constructor runs with: the caller's (null: the defaults); a struct of an older header, without the fields added
+// since, reads them as 0
+int read_tuning(const vdf_nova_tuning* in, vdf_nova_tuning* out) {
+  if (!in) { *out = default_tuning(); return VDF_OK; }
+  const size_t oldest = offsetof(vdf_nova_tuning, custom_ahead);
+  if (in->struct_size != sizeof(vdf_nova_tuning) && in->struct_size != oldest) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
+  vdf_nova_tuning t{};
+  memcpy(&t, in, in->struct_size);
+  t.struct_size = (uint32_t)sizeof(vdf_nova_tuning);
+  if (!tuning_valid(t)) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
+  *out = t;
+  return VDF_OK;
 }
 const vdf_nova_tuning& default_tuning() {
   static const vdf_nova_tuning d = [] {
@@ -759,6 +778,7 @@ const vdf_nova_tuning& default_tuning() {
     t.early_row_parts = 1; t.lookahead_priority = 1; t.side_accumulate_fill = 3; t.verbose = 0; t.compress_queues = 1; t.rows_at_challenge = 1;
     t.fold_fused = 0;      // measured (profiles/r05_ab_fold_fused.txt): the fused fold shortens the rows' path by ~45 us and the step gets no faster
     t.periodic_rows = 0;   // an option until it is measured against the generic kernel on the same rows
+    t.custom_ahead = 0;    // a custom chain's lookahead and early rows: off until a later change flips it
     // the environment overrides of earlier rounds, read once: the only place the prover looks at the environment for tuning
     const struct { const char* name; int32_t* field; } vars[] = {
         {"VDF_NOVA_DIGIT_WINDOW", &t.digit_window}, {"VDF_NOVA_T_AHEAD", &t.early_rows}, {"VDF_NOVA_STENCIL", &t.stencil},
@@ -766,7 +786,8 @@ const vdf_nova_tuning& default_tuning() {
         {"VDF_NOVA_LOOKAHEAD_EARLY", &t.lookahead_early}, {"VDF_NOVA_GATE", &t.gate_accumulate}, {"VDF_NOVA_FOLD_ON_ROWS", &t.fold_on_rows},
         {"VDF_NOVA_NIFS_AHEAD", &t.nifs_ahead}, {"VDF_NOVA_T_PARTS", &t.early_row_parts}, {"VDF_NOVA_LOOKAHEAD_PRIO", &t.lookahead_priority},
         {"VDF_NOVA_SIDE_ACC_WG", &t.side_accumulate_fill}, {"VDF_NOVA_VERBOSE", &t.verbose}, {"VDF_NOVA_COMPRESS_QUEUES", &t.compress_queues}, {"VDF_NOVA_ROWS_AT_CHALLENGE", &t.rows_at_challenge},
-        {"VDF_NOVA_FOLD_FUSED", &t.fold_fused}, {"VDF_NOVA_PERIODIC_ROWS", &t.periodic_rows}};
+        {"VDF_NOVA_FOLD_FUSED", &t.fold_fused}, {"VDF_NOVA_PERIODIC_ROWS", &t.periodic_rows},
+        {"VDF_NOVA_CUSTOM_AHEAD", &t.custom_ahead}};
     for (const auto& v : vars) {
       const char* e = env_override(v.name);
       if (!e || !*e) continue;
@@ -783,6 +804,10 @@ const vdf_nova_tuning& default_tuning() {
 }  // namespace vdfnova
 extern "C" {
 void vdf_nova_tuning_default(vdf_nova_tuning* out) { if (out) *out = default_tuning(); }
+int vdf_nova_tuning_read(const vdf_nova_tuning* tuning, vdf_nova_tuning* out) {
+  if (!out) return fail(VDF_ERR_BAD_ARG, "null argument");
+  return read_tuning(tuning, out);
+}
 int vdf_nova_pp_tuning(const vdf_pp* pp, vdf_nova_tuning* out) {
   if (!pp || !out) return fail(VDF_ERR_BAD_ARG, "null argument");
   *out = pp->tune;
@@ -820,8 +845,9 @@ int vdf_nova_public_params_field(vdf_ctx* ctx, int fid, uint64_t t, int circuit_
       if (!builtin_circuit(circuit_kind)) return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
       if (lanes != 1) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 for every kind but VDF_CIRCUIT_MINROOT_FORWARD_LANES");
     }
-    if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
-    return public_params_impl(ctx, fid, t, circuit_kind, nullptr, gens_family, tuning ? *tuning : default_tuning(), out, ro, lanes);
+    vdf_nova_tuning tn;
+    { int rc = read_tuning(tuning, &tn); if (rc != VDF_OK) return rc; }
+    return public_params_impl(ctx, fid, t, circuit_kind, nullptr, gens_family, tn, out, ro, lanes);
   });
 }
 int vdf_nova_pp_field(const vdf_pp* pp) { return pp ? pp->field : -1; }
@@ -831,8 +857,9 @@ int vdf_nova_public_params_tuned(vdf_ctx* ctx, uint64_t t, int circuit_kind, int
     if (!ctx || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
     if (!builtin_circuit(circuit_kind))
       return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
-    if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
-    return public_params_impl(ctx, VDF_FIELD_FQ, t, circuit_kind, nullptr, gens_family, tuning ? *tuning : default_tuning(), out);
+    vdf_nova_tuning tn;
+    { int rc = read_tuning(tuning, &tn); if (rc != VDF_OK) return rc; }
+    return public_params_impl(ctx, VDF_FIELD_FQ, t, circuit_kind, nullptr, gens_family, tn, out);
   });
 }
 int vdf_nova_public_params_ro(vdf_ctx* ctx, uint64_t t, int circuit_kind, int gens_family, const vdf_nova_ro_params* rop,
@@ -844,8 +871,9 @@ int vdf_nova_public_params_ro(vdf_ctx* ctx, uint64_t t, int circuit_kind, int ge
     if (!ctx || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
     if (!builtin_circuit(circuit_kind))
       return fail(VDF_ERR_BAD_ARG, "unknown step circuit");
-    if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
-    return public_params_impl(ctx, VDF_FIELD_FQ, t, circuit_kind, nullptr, gens_family, tuning ? *tuning : default_tuning(), out, ro);
+    vdf_nova_tuning tn;
+    { int rc = read_tuning(tuning, &tn); if (rc != VDF_OK) return rc; }
+    return public_params_impl(ctx, VDF_FIELD_FQ, t, circuit_kind, nullptr, gens_family, tn, out, ro);
   });
 }
 int vdf_nova_public_params_lanes(vdf_ctx* ctx, uint64_t t, size_t lanes, int gens_family, const vdf_nova_ro_params* rop,
@@ -856,8 +884,9 @@ int vdf_nova_public_params_lanes(vdf_ctx* ctx, uint64_t t, size_t lanes, int gen
     if (bad) return fail(VDF_ERR_BAD_ARG, "unsupported RO parameter block (vdf_nova.h: alpha 5, 128 / 250 bits, family 1 widths 2..25)");
     if (!ctx || !out || t == 0 || t > (1ull << 24)) return fail(VDF_ERR_BAD_ARG, "bad argument");
     if (!lanes_valid(lanes)) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_NOVA_MAX_LANES");
-    if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
-    return public_params_impl(ctx, VDF_FIELD_FQ, t, VDF_CIRCUIT_MINROOT_FORWARD_LANES, nullptr, gens_family, tuning ? *tuning : default_tuning(), out, ro, lanes);
+    vdf_nova_tuning tn;
+    { int rc = read_tuning(tuning, &tn); if (rc != VDF_OK) return rc; }
+    return public_params_impl(ctx, VDF_FIELD_FQ, t, VDF_CIRCUIT_MINROOT_FORWARD_LANES, nullptr, gens_family, tn, out, ro, lanes);
   });
 }
 size_t vdf_nova_pp_lanes(const vdf_pp* pp) { return pp ? pp->lanes : 0; }
@@ -882,8 +911,9 @@ int vdf_nova_public_params_custom_tuned(vdf_ctx* ctx, int fid, const vdf_step_ci
   return nova_guard([&]() -> int {
     if (!ctx || !out || !primary || !primary->synthesize || primary->arity == 0 || primary->arity > 64 || !valid_field(fid))
       return fail(VDF_ERR_BAD_ARG, "bad argument");
-    if (tuning && (tuning->struct_size != sizeof(vdf_nova_tuning) || !tuning_valid(*tuning))) return fail(VDF_ERR_BAD_ARG, "tuning: a field is out of range");
-    return public_params_impl(ctx, fid, 0, VDF_CIRCUIT_CUSTOM, primary, gens_family, tuning ? *tuning : default_tuning(), out);
+    vdf_nova_tuning tn;
+    { int rc = read_tuning(tuning, &tn); if (rc != VDF_OK) return rc; }
+    return public_params_impl(ctx, fid, 0, VDF_CIRCUIT_CUSTOM, primary, gens_family, tn, out);
   });
 }
 
@@ -927,16 +957,18 @@ static int make_packed_generators(vdf_pp* pp) {
   return VDF_OK;
 }
 
-// the longest run of constraints that read nothing of a witness but [seg_begin - arity, seg_begin + seg_len) and the constant, none
-// of them longer than 8 entries in any matrix (public_params_impl)
-static void longest_early_run(const HostShape& h, size_t seg_begin, size_t seg_len, size_t arity, size_t* best_b, size_t* best_n) {
-  const size_t sb = seg_begin - arity, se = seg_begin + seg_len;
+// the longest run of constraints that read nothing of a witness but the segment [seg_begin, seg_begin + seg_len), the step
+// circuit's input [zin_begin, zin_begin + arity) and the constant, none of them longer than 8 entries in any matrix
+// (public_params_impl).  A built-in kind's input sits right in front of its segment; a custom circuit's wherever the augmented
+// circuit allocated it, with variables of the circuit's own in between that no early row may read.
+static void longest_early_run(const HostShape& h, size_t seg_begin, size_t seg_len, size_t zin_begin, size_t arity, size_t* best_b, size_t* best_n) {
+  const size_t se = seg_begin + seg_len, ze = zin_begin + arity;
   std::vector<uint8_t> early(h.num_cons, 1);
   for (int k = 0; k < 3; ++k) {
     std::vector<uint32_t> per_row(h.num_cons, 0);
     for (size_t e = 0; e < h.m[k].rows.size(); ++e) {
       const uint32_t r = h.m[k].rows[e], c = h.m[k].cols[e];
-      if (!((c >= sb && c < se) || c == h.num_vars) || ++per_row[r] > 8) early[r] = 0;
+      if (!((c >= seg_begin && c < se) || (c >= zin_begin && c < ze) || c == h.num_vars) || ++per_row[r] > 8) early[r] = 0;
     }
   }
   *best_b = 0; *best_n = 0;
@@ -1091,13 +1123,23 @@ static int public_params_impl(vdf_ctx* ctx, int fid, uint64_t t, int circuit_kin
     // none of them a row the device sums by a wavefront (vdf_nifs_cross_term_rows)
     const HostShape& h = sh[PRIMARY];
     size_t best_b = 0, best_n = 0;
-    longest_early_run(h, pp->seg_begin, pp->seg_len, pp->arity, &best_b, &best_n);
+    pp->zin_begin = pp->seg_begin >= pp->arity ? pp->seg_begin - pp->arity : 0;
+    if (pp->seg_begin >= pp->arity) longest_early_run(h, pp->seg_begin, pp->seg_len, pp->zin_begin, pp->arity, &best_b, &best_n);
     if (best_n >= 64 && pp->seg_begin >= pp->arity && tune.early_rows != 0 && !(tune.flags & VDF_PP_NO_EARLY_ROWS)) { pp->ahead_row = best_b; pp->ahead_rows = best_n; }
     pp->ahead_mode = tune.early_rows == 1 ? 1 : 2;
     // the built-in circuits' early rows are a fixed stencil over the rounds' variables: compared with the shape triple by triple
     // once, here; from then on their cross term reads no sparse matrix (tuning.stencil = 0: the generic kernel, for A/B runs)
     if (!custom && pp->ahead_rows == lanes * (3 * t + 1) && tune.stencil)
       pp->stencil_per = builtin_stencil(fid, h, circuit_kind, t, pp->seg_begin, pp->ahead_row, lanes);
+  }
+  if (pp->seg_len && custom && sh[PRIMARY].step_begin >= pp->arity) {
+    // a custom circuit's early rows, for the steps a chain drives under tuning.custom_ahead = 2: the same rule over the variables of
+    // its vdf_cs_repeat and z_in where the augmented circuit allocated it (the `arity` variables in front of the step circuit's own)
+    pp->zin_begin = sh[PRIMARY].step_begin - pp->arity;
+    size_t best_b = 0, best_n = 0;
+    longest_early_run(sh[PRIMARY], pp->seg_begin, pp->seg_len, pp->zin_begin, pp->arity, &best_b, &best_n);
+    if (best_n >= 64 && tune.custom_ahead == 2 && tune.early_rows != 0 && !(tune.flags & VDF_PP_NO_EARLY_ROWS)) { pp->ahead_row = best_b; pp->ahead_rows = best_n; }
+    pp->ahead_mode = tune.early_rows == 1 ? 1 : 2;
   }
   ms[0] = now_ms() - mark; mark = now_ms();
   for (int s = 0; s < 2; ++s) {
@@ -1283,7 +1325,7 @@ static int shape_stencil_impl(int fid, uint64_t t, int circuit_kind, size_t lane
     const size_t sb = h.step_begin, sl = h.step_end - h.step_begin;
     size_t b = 0, n = 0;
     if (sb < 3 * lanes) return 0;
-    longest_early_run(h, sb, sl, 3 * lanes, &b, &n);
+    longest_early_run(h, sb, sl, sb - 3 * lanes, 3 * lanes, &b, &n);
     if (early_begin) *early_begin = b;
     if (early_len) *early_len = n;
     if (seg_begin) *seg_begin = sb;
@@ -1302,10 +1344,30 @@ int vdf_nova_shape_stencil_field(int fid, uint64_t t, int circuit_kind, size_t l
   if (!valid_field(fid) || t == 0 || t > (1ull << 24) || !kind_lanes_valid(circuit_kind, lanes)) return -fail(VDF_ERR_BAD_ARG, "bad argument");
   return shape_stencil_impl(fid, t, circuit_kind, lanes, early_begin, early_len, seg_begin);
 }
+int vdf_nova_shape_early_rows_custom(int fid, const vdf_step_circuit* primary, uint64_t* row_begin, uint64_t* rows, uint64_t* zin_begin,
+                                     uint64_t* seg_begin) {
+  return nova_guard([&]() -> int {
+    if (!valid_field(fid) || !primary || !primary->synthesize || primary->arity == 0 || primary->arity > 64) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    HostShape sh[2];
+    RepeatState rp;
+    { int rc = build_shapes(fid, 0, VDF_CIRCUIT_CUSTOM, sh, primary, nullptr, 1, &rp); if (rc != VDF_OK) return rc; }
+    const HostShape& h = sh[PRIMARY];
+    const size_t zb = h.step_begin >= primary->arity ? h.step_begin - primary->arity : 0;
+    size_t b = 0, n = 0;
+    if (rp.used && h.step_begin >= primary->arity)
+      longest_early_run(h, rp.var_begin, rp.lanes * (size_t)rp.t * rp.rec.n_vars, zb, primary->arity, &b, &n);
+    if (n < 64) b = n = 0;
+    if (row_begin) *row_begin = b;
+    if (rows) *rows = n;
+    if (zin_begin) *zin_begin = zb;
+    if (seg_begin) *seg_begin = rp.used ? rp.var_begin : 0;
+    return VDF_OK;
+  });
+}
 
 // ---- prove_step ----------------------------------------------------------------------------------------
 static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* circuits, size_t k, const vdf_step_circuit* custom,
-                           const vdf_fe* z0, vdf_proof** fresh, const vdf_fe* step_advice = nullptr);
+                           const vdf_fe* z0, vdf_proof** fresh, const vdf_fe* step_advice = nullptr, vdf_custom_chain* chain = nullptr);
 
 int vdf_nova_prove_step(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* circuits, size_t k, const vdf_fe z0[3]) {
   if (pp && pp->circuit_kind == VDF_CIRCUIT_CUSTOM) return fail(VDF_ERR_BAD_ARG, "these parameters are for a custom step circuit: vdf_nova_prove_step_custom");
@@ -1356,6 +1418,9 @@ static int upload_fresh(vdf_ctx* ctx, const Side& sd, const CS& cs, Fe* stage, v
 //               a step's critical path.
 //   LOOKAHEAD   p->ctx2[j % DEPTH]: the MinRoot rounds of step k + 1 from the forward trace, and their commitment.
 //   EARLY ROWS  p->ctx3: the rows of the primary cross term T that read only those rounds, and their commitment.
+// A custom circuit's step driven by a chain under tuning.custom_ahead runs the same programme: LOOKAHEAD holds the rounds of its
+// vdf_cs_repeat (k_round_tape from the chain's device trace, with the `inv` a probe synthesis captured), EARLY ROWS the run of rows
+// vdf_nova_pp_early_rows names, through the generic or the periodic row kernel.
 //
 //   MARK_Z        set on LOOKAHEAD   the rounds of a ring slot are written            EARLY ROWS start behind it; a step ends behind it
 //   MARK_W        set on LOOKAHEAD   their commitment has landed in h_pts[slot]       CHAIN (c) waits for it before it sums comm_W
@@ -1377,6 +1442,7 @@ struct StepRun {
   const size_t k;
   const vdf_step_circuit* const custom;
   const vdf_fe* step_advice = nullptr;  // a custom circuit driven by a chain: what its vdf_cs_step_advice answers
+  vdf_custom_chain* chain = nullptr;    // ... and the chain (k is then the chain's step), for tuning.custom_ahead
   const Circuit& c;
   const bool first;
   const size_t arity;
@@ -1386,11 +1452,12 @@ struct StepRun {
   const Side& S2;
   const Field& F1;
   const Field& F2;
-  const size_t seg_b, seg_n, seg_e;    // the primary witness's run of round variables made AHEAD of the step (a custom circuit: none -- the
-                                       // rounds of its vdf_cs_repeat are written inside the step, chain_primary_circuit)
+  size_t seg_b, seg_n, seg_e;          // the primary witness's run of round variables made AHEAD of the step: a built-in kind's segment; a custom
+                                       // circuit's when a chain's lookahead made them (decided by lookahead_select, taken back by a late miss in
+                                       // chain_primary_circuit), else none -- the rounds of its vdf_cs_repeat are then written inside the step
   const int per;
   const bool forward;                  // the forward step circuit in pp->lanes lanes: rounds by vdf_minroot_forward_segment_lanes, stencil code 5 / 6
-  const bool t_ahead;                  // this step has early rows
+  bool t_ahead;                        // this step has early rows (a custom circuit: decided with seg_*)
   const size_t ta_b, ta_n, ta_e;
   const int t_parts;                   // (tuning.early_row_parts = 2 or 3: the early rows as an MSM job of that many parts (vdf_msm_job_*): a later part's
                                        // rows and sort run under an earlier part's bucket accumulation, one shared bucket reduction.  r3: 1.10 ms per step against 0.95 as ONE MSM, the default)
@@ -1399,6 +1466,8 @@ struct StepRun {
   // ---- state of this step
   double t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
   bool hit = false;                    // the rounds of this step were made by the previous step's lookahead
+  bool ca = false;                     // a custom chain's step under tuning.custom_ahead: it may be a hit, and looks ahead itself
+  vdf_proof::CustomAhead la;           // ... a hit: what the lookahead used, until the step's own vdf_cs_repeat has been compared with it
   int slot = 0;                        // ring slot of this step's fresh primary witness
   vdf_ctx* cq = nullptr;               // LOOKAHEAD queue that made this step's rounds
   void* d_z2 = nullptr;
@@ -1428,38 +1497,57 @@ struct StepRun {
 
   // ================================ LOOKAHEAD queue ==================================================================
   // the MinRoot rounds of step j into ring slot s on that step's lookahead context, and their share of the commitment
-  int lookahead_enqueue(size_t j, int s, bool cold) {
-    const Circuit& cc = circuits->v[j];
+  // (a custom chain: `probed` is the vdf_cs_repeat a probe synthesis of step j recorded, d_probed the chain's trace of that step)
+  int lookahead_enqueue(size_t j, int s, bool cold, const RepeatState* probed = nullptr, const vdf_fe* d_probed = nullptr) {
     vdf_ctx* q = p->ctx2[j % D];
     if (cold) HIPCALL(q, vdf_ctx_wait(q, ctx));   // outside the steady state the ring slot may still be read by a fold
-    const void* d_trace = cc.d_trace;
-    if (!d_trace && cc.trace_xy.empty()) return fail(VDF_ERR_BAD_ARG, "trace of circuit " + std::to_string(j) + " not materialised");
-    if (!d_trace) {                               // trace not resident: staged through the proof's own buffer
-      void*& stage = p->d_traces[j % D];
-      if (!stage) HIPCALL(ctx, vdf_dev_alloc(ctx, pp->lanes * (pp->t + 1) * 64, &stage));
-      HIPCALL(q, vdf_dev_memcpy(q, stage, cc.trace_xy.data(), pp->lanes * (pp->t + 1) * 64));
-      d_trace = stage;
+    char* seg = (char*)p->d_z2s[s] + pp->seg_begin * 32;
+    void* packed = nullptr;
+    vdf_proof::CustomAhead next;
+    if (custom) {
+      // the rounds of the repeat, one repetition per thread, from the chain's trace: resolved, so the walk queue that wrote it has
+      // been synchronised by the host and this queue is behind it
+      next.chain = chain; next.k = j; next.d_trace = d_probed; next.lane_stride = probed->lane_stride; next.slot = s;
+      next.inv = probed->inv;
+      const vdf_round_tape tape = pp->round.rec.view();      // (the probe's body is the parameters': compared by the caller)
+      if (pp->round.lanes == 1)
+        HIPCALL(q, vdf_round_tape_run(q, S1.field, &tape, pp->round.t, (const vdf_fe*)next.inv.data(), d_probed, (vdf_fe*)seg));
+      else
+        HIPCALL(q, vdf_round_tape_run_lanes(q, S1.field, &tape, pp->round.t, pp->round.lanes, (const vdf_fe*)next.inv.data(), d_probed,
+                                            probed->lane_stride, (vdf_fe*)seg));
+    } else {
+      const Circuit& cc = circuits->v[j];
+      const void* d_trace = cc.d_trace;
+      if (!d_trace && cc.trace_xy.empty()) return fail(VDF_ERR_BAD_ARG, "trace of circuit " + std::to_string(j) + " not materialised");
+      if (!d_trace) {                               // trace not resident: staged through the proof's own buffer
+        void*& stage = p->d_traces[j % D];
+        if (!stage) HIPCALL(ctx, vdf_dev_alloc(ctx, pp->lanes * (pp->t + 1) * 64, &stage));
+        HIPCALL(q, vdf_dev_memcpy(q, stage, cc.trace_xy.data(), pp->lanes * (pp->t + 1) * 64));
+        d_trace = stage;
+      }
+      packed = pp->seg_gens ? p->d_packed[j % D] : nullptr;
+      if (forward) {                                // every lane's rounds in one launch, the lanes' traces back to back
+        Fe ends[VDF_NOVA_MAX_LANES];
+        for (size_t l = 0; l < pp->lanes; ++l) ends[l] = cc.lane_result[l].i;
+        HIPCALL(q, vdf_minroot_forward_segment_lanes(q, S1.field, (const vdf_fe*)d_trace, (size_t)pp->t + 1, pp->t, pp->lanes, (const vdf_fe*)ends, (vdf_fe*)seg));
+      } else if (packed) HIPCALL(q, vdf_minroot_step_segment_packed(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.input.i,
+                                                              (const vdf_fe*)&cc.result.i, (vdf_fe*)seg, (vdf_fe*)packed));
+      else HIPCALL(q, vdf_minroot_step_segment(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.input.i, per, (vdf_fe*)seg));
     }
-    char* seg = (char*)p->d_z2s[s] + seg_b * 32;
-    void* packed = pp->seg_gens ? p->d_packed[j % D] : nullptr;
-    if (forward) {                                // every lane's rounds in one launch, the lanes' traces back to back
-      Fe ends[VDF_NOVA_MAX_LANES];
-      for (size_t l = 0; l < pp->lanes; ++l) ends[l] = cc.lane_result[l].i;
-      HIPCALL(q, vdf_minroot_forward_segment_lanes(q, S1.field, (const vdf_fe*)d_trace, (size_t)pp->t + 1, pp->t, pp->lanes, (const vdf_fe*)ends, (vdf_fe*)seg));
-    } else if (packed) HIPCALL(q, vdf_minroot_step_segment_packed(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.input.i,
-                                                            (const vdf_fe*)&cc.result.i, (vdf_fe*)seg, (vdf_fe*)packed));
-    else HIPCALL(q, vdf_minroot_step_segment(q, S1.field, (const vdf_fe*)d_trace, pp->t, (const vdf_fe*)&cc.input.i, per, (vdf_fe*)seg));
     HIPCALL(q, vdf_ctx_mark(q, MARK_Z));
     HIPCALL(ctx, vdf_ctx_wait(ctx, q));          // the first context waits for the rounds only, not for their commitment
     // the reference's circuit: the same commitment from 3t + 4 terms over the derived generators (make_packed_generators)
     if (gate_next_segment) { HIPCALL(q, vdf_ctx_gate_accumulate(q, ctx, MARK_PRIMARY)); gate_next_segment = false; }
     if (packed) HIPCALL(q, vdf_msm(q, pp->seg_gens, 0, (const vdf_fe*)packed, 3 * pp->t + 4, 1, &p->h_pts[s]));
-    else HIPCALL(q, vdf_msm(q, S1.gens, seg_b, (const vdf_fe*)seg, seg_n, 1, &p->h_pts[s]));
+    else HIPCALL(q, vdf_msm(q, S1.gens, pp->seg_begin, (const vdf_fe*)seg, pp->seg_len, 1, &p->h_pts[s]));
     HIPCALL(q, vdf_ctx_mark(q, MARK_W));
     touched[j % D] = true;
     vdf_proof::Ahead a;
-    a.result = cc.result; a.input = cc.input; a.slot = s;
+    memset(&a.result, 0, sizeof(St)); memset(&a.input, 0, sizeof(St));
+    if (!custom) { a.result = circuits->v[j].result; a.input = circuits->v[j].input; }
+    a.slot = s;
     p->ahead.push_back(a);
+    if (custom) { next.valid = true; p->cahead = std::move(next); }
     return VDF_OK;
   }
   // which ring slot holds this step's rounds: the previous step's lookahead (a hit), or made now
@@ -1467,10 +1555,29 @@ struct StepRun {
     hit = !custom && !p->ahead.empty() && p->ahead_circuits == circuits && p->ahead_k == k &&
           memcmp(&p->ahead[0].result, &c.result, sizeof(St)) == 0 && memcmp(&p->ahead[0].input, &c.input, sizeof(St)) == 0;
     if (custom) {
-      // every variable comes from the host: no rounds to make ahead of time, the ring just rotates
-      vdf_proof::Ahead a;
-      a.slot = first ? 0 : (p->slot + 1) % R;
-      p->ahead.assign(1, a);
+      // A chain's step under tuning.custom_ahead: the previous step may have made this step's rounds.  What can be compared before the
+      // synthesis is compared here -- the chain, k, the trace; the repeat's own inv and advice pointer in chain_primary_circuit.
+      ca = chain && step_advice && pp->tune.custom_ahead != 0 && pp->round.used && pp->seg_len != 0;
+      vdf_proof::CustomAhead& made = p->cahead;
+      hit = ca && !first && made.valid && made.chain == chain && made.k == k && made.d_trace == step_advice && !p->ahead.empty() &&
+            p->ahead[0].slot == made.slot;
+      if (made.valid && !hit) {                      // a lookahead nobody came for: drained, what it made is discarded
+        for (vdf_ctx* q : p->ctx2) HIPCALL(q, vdf_ctx_sync(q));
+        ++p->ahead_misses;
+      } else if (ca && !first && !made.valid) ++p->ahead_skipped;
+      if (!hit && p->tahead_valid) { HIPCALL(ct, vdf_ctx_sync(ct)); p->tahead_valid = false; }      // ... and its early rows are let finish
+      if (hit) {
+        la = std::move(made);
+        seg_b = pp->seg_begin; seg_n = pp->seg_len; seg_e = seg_b + seg_n;
+        t_ahead = pp->ahead_rows != 0;
+      } else {
+        // no rounds made ahead of time: every variable comes from the host or from the step's own launch, the ring just rotates
+        vdf_proof::Ahead a;
+        memset(&a.result, 0, sizeof(St)); memset(&a.input, 0, sizeof(St));
+        a.slot = first ? 0 : (p->slot + 1) % R;
+        p->ahead.assign(1, a);
+      }
+      made = vdf_proof::CustomAhead();
     } else if (!hit) {
       if (!p->ahead.empty()) for (vdf_ctx* q : p->ctx2) HIPCALL(q, vdf_ctx_sync(q));       // lookaheads nobody came for
       p->ahead.clear();
@@ -1488,7 +1595,7 @@ struct StepRun {
   // this step's entry leaves the list; the rounds of the steps that follow are enqueued
   int lookahead_advance() {
     p->ahead.erase(p->ahead.begin());
-    if (custom) return VDF_OK;
+    if (custom) return ca ? lookahead_probe() : VDF_OK;
     p->ahead_k = k + 1;
     while (p->ahead.size() < (size_t)D) {
       const size_t j = p->ahead_k + p->ahead.size();
@@ -1498,6 +1605,30 @@ struct StepRun {
       if (rc != VDF_OK) return rc;
     }
     return VDF_OK;
+  }
+
+  // A custom chain under tuning.custom_ahead: the rounds of step k + 1, when its trace is resolved.  The values of the repeat's `inv`
+  // are known to `synthesize` alone: it is run once more (THE PROBE, include/vdf_nova.h) on a throw-away witness-mode constraint system
+  // over z_(k+1), which this step's primary circuit has just produced, and step k + 1's trace; its vdf_cs_repeat records the body and
+  // keeps inv, and touches neither the advice nor the device.  Anything that does not fit is no error here: no lookahead, the step
+  // that comes counts as skipped and says itself what is wrong.
+  int lookahead_probe() {
+    const size_t j = k + 1;
+    if (j >= chain_info(chain).steps) return VDF_OK;
+    const vdf_fe* d_next = chain_ready(chain, j);               // never over a trace whose walks are pending
+    if (!d_next) return VDF_OK;
+    const RepeatState& want = pp->round;
+    std::unique_ptr<StepCircuit> pc = make_custom_circuit(custom, nullptr, d_next, want.lanes * (size_t)(want.t + 1) * want.rec.n_adv, true);
+    CS cs(S1.field, false, pp->ro);
+    std::vector<Num> z(arity, cs.zero_num());
+    for (size_t a = 0; a < arity; ++a) z[a].v = p->zi[PRIMARY][a];
+    pc->synthesize(cs, z);
+    const CustomStepCircuit* cc = static_cast<const CustomStepCircuit*>(pc.get());
+    const RepeatState& got = cc->rep;
+    if (cc->rc != 0 || !got.used || got.t != want.t || got.lanes != want.lanes || !got.rec.same_body(want.rec) || got.d_advice != (const void*)d_next ||
+        got.inv.size() != want.lanes * want.rec.n_inv)
+      return VDF_OK;
+    return lookahead_enqueue(j, (slot + 1) % R, !hit, &got, d_next);
   }
 
   // ================================ EARLY ROWS queue =================================================================
@@ -1518,8 +1649,15 @@ struct StepRun {
     // z_in = z_i past the base step (the circuit's selection); the same values arrive again with the host's variables
     if (!zin_in_place) {
       memcpy(p->h_zin, p->zi[PRIMARY].data(), arity * 32);          // pinned: the copy reads it when it runs
-      HIPCALL(ct, vdf_dev_memcpy(ct, (char*)d_z2 + (seg_b - arity) * 32, p->h_zin, arity * 32));
+      HIPCALL(ct, vdf_dev_memcpy(ct, (char*)d_z2 + pp->zin_begin * 32, p->h_zin, arity * 32));
     }
+    auto generic = [&](size_t b, size_t n) -> int {
+      if (n == 0) return VDF_OK;
+      HIPCALL(ct, vdf_nifs_cross_term_rows(ct, S1.shape, b, n, VDF_ROWS_INSIDE, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0],
+                                           (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2], (const vdf_fe*)&s1.inst.u,
+                                           (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
+      return VDF_OK;
+    };
     auto rows = [&](size_t b, size_t n) -> int {
       if (fold_r) {                                                  // the stencil with the previous fold of its rows on the way
         if (!(pp->stencil_per && b == ta_b && n == ta_n)) return fail(VDF_ERR_DEVICE, "fused fold without the stencil");
@@ -1544,10 +1682,20 @@ struct StepRun {
                                                 (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
         return VDF_OK;
       }
-      HIPCALL(ct, vdf_nifs_cross_term_rows(ct, S1.shape, b, n, VDF_ROWS_INSIDE, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0],
-                                           (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2], (const vdf_fe*)&s1.inst.u,
-                                           (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
-      return VDF_OK;
+      const PeriodicRows& pr = pp->periodic;
+      if (custom && pp->periodic_on && pr.row_begin >= b && pr.row_begin + pr.row_count <= b + n) {
+        // a custom circuit's periodic repetitions (lead .. t - 1 of its repeat) from their description; the rows of the run in front
+        // of them and behind them through the sparse matrices, as in chain_primary_nifs
+        const vdf_periodic_rows view = pr.view();
+        int rc = generic(b, pr.row_begin - b);
+        if (rc != VDF_OK) return rc;
+        HIPCALL(ct, vdf_nifs_cross_term_periodic(ct, S1.field, &view, pr.lead, pp->round.t - pr.lead, pp->round.var_begin, pr.row_begin,
+                                                  S1.ncols, S1.num_cons, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0],
+                                                  (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2], (const vdf_fe*)&s1.inst.u,
+                                                  (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
+        return generic(pr.row_begin + pr.row_count, b + n - (pr.row_begin + pr.row_count));
+      }
+      return generic(b, n);
     };
     memset(&hb[5], 0, 2 * sizeof(vdf_jac));                          // parts not used this time: the identity
     if (t_parts == 1 || ta_n < 4096) {
@@ -1619,7 +1767,7 @@ struct StepRun {
       // the primary side's own commitments are (0.65 ms into the step), and this side's direct sum, one prioritised
       // wavefront per SIMD for 0.1 ms, loses little to a bucket accumulation beside it
       const bool rows_inflight = t_ahead && hit && p->tahead_valid && p->tahead_slot == slot && p->tahead_k == k &&
-                                 p->tahead_circuits == circuits;       // launched by the previous step on its way out
+                                 p->tahead_circuits == circuits && p->tahead_chain == chain;       // launched by the previous step on its way out
       if (t_ahead && !rows_inflight) {
         if (pp->ahead_mode == 1) HIPCALL(ct, vdf_ctx_wait(ct, ctx));
         else if (p->tahead_valid) HIPCALL(ct, vdf_ctx_sync(ct));       // rows made for a step that did not come: let them finish
@@ -1654,9 +1802,24 @@ struct StepRun {
         if (cs.dev_len && (!round->d_advice || cs.dev_len != pp->seg_len || cs.dev_begin != pp->seg_begin))
           return fail(VDF_ERR_DEVICE, "device segment moved");
       } else if (cs.dev_len != seg_n || (seg_n && cs.dev_begin != seg_b)) return fail(VDF_ERR_DEVICE, "device segment moved");
+      if (custom && hit) {
+        // the lookahead made this step's rounds from the chain's trace with a probe's inv: are they what this step's own repeat sees?
+        const bool same = cs.dev_len != 0 && round->d_advice == (const void*)la.d_trace && round->lane_stride == la.lane_stride &&
+                          round->inv.size() == la.inv.size() && (la.inv.empty() || memcmp(round->inv.data(), la.inv.data(), la.inv.size() * 32) == 0);
+        if (same) ++p->ahead_hits;
+        else {
+          // a late MISS: both side queues are drained, the rounds, their commitment and any early rows are discarded (everything they
+          // wrote is written again below), and the step goes on as under custom_ahead = 0
+          HIPCALL(cq, vdf_ctx_sync(cq));
+          HIPCALL(ct, vdf_ctx_sync(ct));
+          hit = false; t_ahead = false;
+          seg_b = seg_n = seg_e = 0;
+          ++p->ahead_misses;
+        }
+      }
       t2 = now_ms();
       p->r[SECONDARY].inst = inst_from_elements(unew, F1, F2);       // base step: the default instance
-      if (custom && cs.dev_len) {
+      if (custom && cs.dev_len && !hit) {
         // the rounds of the circuit's vdf_cs_repeat, one repetition per thread, straight into the fresh witness: in front of the
         // uploads around them and of the commitment of W, on the step's own queue
         const vdf_round_tape tape = round->rec.view();
@@ -1670,12 +1833,12 @@ struct StepRun {
       // the host-made variables go next to the rounds the lookahead context has written (vdf_ctx_wait at their launch)
       int rc = upload_fresh(ctx, S1, cs, p->h_stage[PRIMARY], d_z2);
       if (rc != VDF_OK) return rc;
-      if (!first && !custom && pp->ahead_rows != 0 && seg_n) {
+      if (!first && (custom ? ca : seg_n != 0) && pp->ahead_rows != 0) {
         // the NEXT step's z_in = this step's output, known now: into its place in the next ring slot's fresh witness, half a
         // step before the early rows of that step read it
         zin_slot = (slot + 1) % R;
         memcpy(p->h_zin + arity, z_next.data(), arity * 32);          // the second pinned slot (the first may still feed this step's early rows)
-        HIPCALL(ctx, vdf_dev_memcpy(ctx, (char*)p->d_z2s[zin_slot] + (seg_b - arity) * 32, p->h_zin + arity, arity * 32));
+        HIPCALL(ctx, vdf_dev_memcpy(ctx, (char*)p->d_z2s[zin_slot] + pp->zin_begin * 32, p->h_zin + arity, arity * 32));
         HIPCALL(ctx, vdf_ctx_mark(ctx, MARK_ZIN));
       }
       l1.X[0] = cs.X[0]; l1.X[1] = cs.X[1];
@@ -1732,7 +1895,7 @@ struct StepRun {
       // the lookahead launched under this wait sorts beside these commitments but holds its bucket accumulation -- every SIMD
       // for 0.25 ms -- until they are done: it then runs while the host synthesises the secondary circuit (tuning.gate_accumulate = 0: no hold)
       const bool gate = pp->tune.gate_accumulate != 0;
-      if (gate && !first && !custom) { HIPCALL(ctx, vdf_ctx_mark(ctx, MARK_PRIMARY)); gate_next_segment = true; }
+      if (gate && !first && (!custom || ca)) { HIPCALL(ctx, vdf_ctx_mark(ctx, MARK_PRIMARY)); gate_next_segment = true; }
       if (!first) {
         // behind the primary side's launches (it does not depend on them, they do not wait for it): the fold of the secondary
         // witness on the device (z, E, A z, B z, C z += r2 * fresh); the instance came from the circuit
@@ -1750,7 +1913,7 @@ struct StepRun {
       // commitment; back to back the device is the co-bottleneck).  This step's own rounds were committed a step ago; their
       // mark is waited for first, because the launch reuses it.  (tuning.lookahead_early = 0: launched after the wait.)
       const bool la_early = pp->tune.lookahead_early != 0;
-      if (la_early && !first && !custom) {
+      if (la_early && !first && (!custom || ca)) {
         if (seg_n) HIPCALL(cq, vdf_ctx_sync_mark(cq, MARK_W));
         waited_w = true;
         int rc = lookahead_advance();
@@ -1799,7 +1962,9 @@ struct StepRun {
       CS cs(S2.field, false, pp->ro);
       Fe unew[9];
       const bool ahead_rows = pp->tune.nifs_ahead != 0;
-      const bool rows_next = ahead_rows && !first && !custom && pp->ahead_rows != 0 && pp->ahead_mode != 1 && !p->ahead.empty();
+      // (a custom chain: when this step's lookahead_probe has put the next step's rounds on their queue)
+      const bool rows_next = ahead_rows && !first && (!custom || (p->cahead.valid && p->cahead.k == k + 1)) && pp->ahead_rows != 0 &&
+                             pp->ahead_mode != 1 && !p->ahead.empty();
       // The fold of the primary side and, behind it, the early rows of the NEXT step's cross term need nothing of this circuit
       // but its fold challenge r1 -- and from the fold to their commitment those rows are a step's longest dependent path
       // (fold, rows, sort, bucket accumulation, bucket reduction: ~0.7 ms; the chain waits for MARK_T half a step later).  The
@@ -1814,7 +1979,7 @@ struct StepRun {
         if (rows_next && p->ahead[0].slot != zin_slot) {
           // (not the slot the primary phase wrote z_in to: cannot happen with a lookahead of one step; copied again if it does)
           memcpy(p->h_zin + arity, p->zi[PRIMARY].data(), arity * 32);   // (this thread has waited for the primary side's launches: the slot's last copy is over)
-          HIPCALL(ctx, vdf_dev_memcpy(ctx, (char*)p->d_z2s[p->ahead[0].slot] + (seg_b - arity) * 32, p->h_zin + arity, arity * 32));
+          HIPCALL(ctx, vdf_dev_memcpy(ctx, (char*)p->d_z2s[p->ahead[0].slot] + pp->zin_begin * 32, p->h_zin + arity, arity * 32));
           HIPCALL(ctx, vdf_ctx_mark(ctx, MARK_ZIN));
         }
         // The fold of the primary side goes to the queue of the early rows when they follow (they are what waits for it: the
@@ -1868,7 +2033,7 @@ struct StepRun {
             int rc = early_rows_launch(d_next, cq_next, true, fused ? &rr : nullptr);
             if (rc != VDF_OK) return rc;                                 // tahead_valid stays false: a retried step launches its rows itself
             p->poisoned = false;
-            p->tahead_valid = true; p->tahead_slot = p->ahead[0].slot; p->tahead_k = k + 1; p->tahead_circuits = circuits;
+            p->tahead_valid = true; p->tahead_slot = p->ahead[0].slot; p->tahead_k = k + 1; p->tahead_circuits = circuits; p->tahead_chain = chain;
             rows_launched = true;
           } else {
             deferred.pending = true; deferred.d_next = d_next; deferred.cq_next = cq_next; deferred.fq = fq;
@@ -1920,7 +2085,7 @@ struct StepRun {
       int rc = early_rows_launch(deferred.d_next, deferred.cq_next, true, deferred.fused ? &deferred.fold_r : nullptr);
       if (rc != VDF_OK) return rc;                  // tahead_valid stays false: a retried step launches its rows itself
       p->poisoned = false;
-      p->tahead_valid = true; p->tahead_slot = deferred.slot; p->tahead_k = k + 1; p->tahead_circuits = circuits;
+      p->tahead_valid = true; p->tahead_slot = deferred.slot; p->tahead_k = k + 1; p->tahead_circuits = circuits; p->tahead_chain = chain;
     }
     if (fold_elsewhere) HIPCALL(ctx, vdf_ctx_wait_mark(ctx, ct, MARK_FOLD));      // whatever reads the folded instance on the main queue comes after
     HIPCALL(ctx, vdf_ctx_sync_mark(ctx, MARK_STEP));
@@ -1938,7 +2103,7 @@ struct StepRun {
 }  // namespace
 
 static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* circuits, size_t k, const vdf_step_circuit* custom,
-                           const vdf_fe* z0, vdf_proof** fresh, const vdf_fe* step_advice) {
+                           const vdf_fe* z0, vdf_proof** fresh, const vdf_fe* step_advice, vdf_custom_chain* chain) {
   if (!pp || !proof || (!circuits && !custom) || !z0) return fail(VDF_ERR_BAD_ARG, "null argument");
   static const Circuit no_circuit{};
   if (!custom && k >= circuits->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
@@ -1992,6 +2157,7 @@ static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* ci
   struct Restore { vdf_ctx* c; int a; ~Restore() { if (!a) { vdf_ctx_sync(c); vdf_ctx_set_async(c, 0); } } } restore{ctx, was_async};
   StepRun run(pp, p, circuits, k, custom, c, first);
   run.step_advice = step_advice;
+  run.chain = chain;                               // (k is then the chain's step: a custom circuit has no vdf_circuits to index)
   run.t0 = run.t1 = run.t2 = run.t3 = run.t4 = run.t5 = run.t6 = t0;
   { int rc = run.lookahead_select(); if (rc != VDF_OK) return rc; }
   run.chain_prepare_inputs();
@@ -2087,7 +2253,7 @@ int vdf_nova_prove_step_custom_chain(vdf_pp* pp, vdf_proof** proof, const vdf_st
     if (rc == VDF_OK) rc = chain_need(chain, k, &d_trace);            // (its synchronisation is what the prover's queue waits by)
     if (rc == VDF_OK && vdf_ctx_device(chain_info(chain).ctx) != vdf_ctx_device(pp->ctx)) rc = fail(VDF_ERR_BAD_ARG, "the chain's traces live on another device");
     if (rc == VDF_OK) rc = chain_pump(chain, k);
-    if (rc == VDF_OK) rc = prove_step_impl(pp, proof, nullptr, 0, primary, z0, &fresh, d_trace);
+    if (rc == VDF_OK) rc = prove_step_impl(pp, proof, nullptr, k, primary, z0, &fresh, d_trace, chain);
   }
   catch (const std::exception& ex) { rc = fail(VDF_ERR_DEVICE, ex.what()); }
   if (rc != VDF_OK && fresh) vdf_nova_proof_free(fresh);
@@ -2121,6 +2287,13 @@ int vdf_nova_proof_last_unsat(const vdf_proof* p, uint64_t* count, uint64_t* fir
     *count = out[0]; *first_row = out[1];
     return VDF_OK;
   });
+}
+int vdf_nova_proof_ahead_stats(const vdf_proof* p, uint64_t* hits, uint64_t* misses, uint64_t* skipped) {
+  if (!p) return fail(VDF_ERR_BAD_ARG, "null argument");
+  if (hits) *hits = p->ahead_hits;
+  if (misses) *misses = p->ahead_misses;
+  if (skipped) *skipped = p->ahead_skipped;
+  return VDF_OK;
 }
 int vdf_nova_prove_recursively_custom(vdf_pp* pp, const vdf_step_circuit* primary, vdf_custom_chain* chain, const vdf_fe* z0,
                                       size_t window_steps, uint32_t flags, vdf_proof** out) {
@@ -2170,7 +2343,11 @@ int vdf_nova_prove_recursively_custom(vdf_pp* pp, const vdf_step_circuit* primar
     }
     if (rc == VDF_OK) rc = finalize_l2(p);
     std::string why;
-    if (rc != VDF_OK) { why = vdf_nova_last_error(); chain_settle(chain); }      // nothing of this call's stays in flight
+    if (rc != VDF_OK) {                                                         // nothing of this call's stays in flight: the walks, and a
+      why = vdf_nova_last_error();                                              // lookahead over a trace that is released below
+      chain_settle(chain);
+      if (p) { for (vdf_ctx* q : p->ctx2) if (q) vdf_ctx_sync(q); if (p->ctx3) vdf_ctx_sync(p->ctx3); vdf_ctx_sync(pp->ctx); }
+    }
     for (size_t w = 0; w * W < n; ++w) drop(w);
     chain_drop_spare(chain);
     if (rc != VDF_OK) { vdf_nova_proof_free(p); return fail(rc, why); }

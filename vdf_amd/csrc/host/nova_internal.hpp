@@ -118,6 +118,9 @@ struct vdf_pp {
   // constraints of the primary shape that read nothing of a fresh witness but that segment (and the constant): their
   // share of a step's cross term and of its commitment is made ahead of the rest, [ahead_row, ahead_row + ahead_rows)
   size_t ahead_row = 0, ahead_rows = 0;
+  // the column of z_in[0] in the primary witness: where synthesize_augmented allocates the step circuit's `arity` inputs.  A built-in
+  // kind's sit right in front of the segment (seg_begin - arity); a custom circuit may allocate variables of its own in between
+  size_t zin_begin = 0;
   int stencil_per = 0;           // 5 / 6 (VDF_STENCIL_FORWARD / _LANES): the forward circuit's stencil, of one lane / of more -- one kernel
                                  // (vdf_nifs_cross_term_minroot_forward_lanes), the code only says how many lanes it runs;
                                  // 3 / 4: the early rows are the built-in MinRoot stencil with that many variables per round, checked against
@@ -245,6 +248,7 @@ struct vdf_proof {
   int tahead_slot = -1;
   size_t tahead_k = 0;
   const vdf_circuits* tahead_circuits = nullptr;
+  const vdf_custom_chain* tahead_chain = nullptr;     // ... of a custom chain's step (tuning.custom_ahead = 2; tahead_circuits is null then)
   // fresh primary z: ring of slots, the MinRoot segment of a later step is filled (and committed) ahead of time on ctx2
   static constexpr int DEPTH = 1, RING = DEPTH + 2;
   vdf_ctx* ctx2[DEPTH] = {};
@@ -258,6 +262,19 @@ struct vdf_proof {
   const vdf_circuits* ahead_circuits = nullptr;
   size_t ahead_k = 0;
   std::vector<Ahead> ahead;
+  // The lookahead of a custom chain (tuning.custom_ahead): the rounds of step k of `chain` are in ring slot `slot` (ahead[0] names it
+  // too) and their commitment is on its way to h_pts[slot], made from the trace d_trace with the `inv` a probe synthesis captured.
+  // The step that comes compares all of it with what its own vdf_cs_repeat sees (StepRun::lookahead_select, chain_primary_circuit).
+  struct CustomAhead {
+    bool valid = false;
+    const vdf_custom_chain* chain = nullptr;
+    size_t k = 0;
+    const vdf_fe* d_trace = nullptr;
+    size_t lane_stride = 0;
+    std::vector<Fe> inv;
+    int slot = -1;
+  } cahead;
+  uint64_t ahead_hits = 0, ahead_misses = 0, ahead_skipped = 0;     // vdf_nova_proof_ahead_stats
   Fe* h_zin = nullptr;           // pinned: the step circuit's input for the early rows of T
   vdf_jac* h_pts = nullptr;      // pinned result slots: [0, RING) segment commitments per ring slot, 4 for the batches, 1 for the early rows of T
   Fe* h_stage[2] = {};           // pinned staging of a host-synthesised witness, one per side
@@ -276,8 +293,9 @@ bool tuning_valid(const vdf_nova_tuning& t);
 int alloc_proof_buffers(vdf_proof* p);
 int finalize_l2(const vdf_proof* p);      // commits to the last secondary witness if that is still pending
 std::unique_ptr<StepCircuit> make_primary_circuit(const vdf_pp* pp, const Circuit* c, bool device_rounds);
+// probe: the synthesis is the extra one of tuning.custom_ahead (vdf_cs_is_probe; its vdf_cs_repeat touches neither advice nor cs)
 std::unique_ptr<StepCircuit> make_custom_circuit(const vdf_step_circuit* c, vdf_ctx* ctx = nullptr, const vdf_fe* step_advice = nullptr,
-                                                 size_t step_advice_elems = 0);
+                                                 size_t step_advice_elems = 0, bool probe = false);
 // ---- the circuits as the drivers of nova_host.cpp reach them (circuits_host.cpp) --------------------------------------------
 inline void eval_step(int field, int mode, uint64_t t, St* state, Fe* trace_xy) {   // t rounds from *state: the trace [2 (t + 1)], *state = the result
   vdf_state in, res;
@@ -307,6 +325,9 @@ int chain_need(vdf_custom_chain* c, size_t k, const vdf_fe** d_trace);
 int chain_pump(vdf_custom_chain* c, size_t k);
 int chain_settle(vdf_custom_chain* c);
 bool chain_resident(const vdf_custom_chain* c, size_t k);
+// step k's device trace when it is RESOLVED: resident, and no pending walks cover it (they are finished -- the walk queue has been
+// synchronised by the host -- and every one of them landed on its checkpoint); null otherwise.  Never waits.
+const vdf_fe* chain_ready(const vdf_custom_chain* c, size_t k);
 // step k's trace let go of, its allocation kept as the spare if nobody else points into it; the spare freed
 void chain_park(vdf_custom_chain* c, size_t k);
 void chain_drop_spare(vdf_custom_chain* c);

@@ -55,7 +55,8 @@ struct RepeatState {
   size_t lanes = 1, lane_stride = 0;               // vdf_cs_repeat_lanes: chains side by side, lane l's advice lane_stride entries after lane l - 1's
   size_t var_begin = 0;                            // index of the first variable of repetition 0 in the witness
   size_t row_begin = 0;                            // ... and of its first constraint in the shape
-  const void* d_advice = nullptr;                  // witness mode, advice in device memory: the variables were skipped (cs.dev_begin / dev_len)
+  const void* d_advice = nullptr;                  // witness mode, advice in device memory: the variables were skipped (cs.dev_begin / dev_len);
+                                                   // a probe: the advice pointer as the circuit handed it over, never read
   std::vector<Fe> inv;                             // ... and the values of inv (lanes * n_inv, lane-major), for the kernel
 };
 
@@ -134,4 +135,6 @@ struct vdf_cs {
   bool forward = false;                            // ... a forward body's (vdf_nova_forward_body_record): vdf_cs_pow / _pow_chain are legal
   const vdf_fe* step_advice = nullptr;             // vdf_cs_step_advice: the device trace of the step a custom chain drives (witness synthesis only)
   size_t step_advice_elems = 0;                    // ... and its length in elements: lanes * (t + 1) * n_adv of the parameters' repeat
+  bool probe = false;                              // vdf_cs_is_probe: the extra synthesis of tuning.custom_ahead -- a vdf_cs_repeat records the body and
+                                                   // keeps `inv`, reads no advice and makes no variable (rounds_host.cpp)
 };

@@ -777,9 +777,11 @@ int vdf_cs_repeat_lanes(vdf_cs* c, const vdf_round_body* b, uint64_t t, size_t l
     if (carry_in[k] >= c->pool.size()) return refuse("vdf_cs_repeat: bad handle in carry_in");
     carry_all[k] = c->pool[carry_in[k]];
   }
-  const bool device = !cs.shape && vdf_ptr_is_device(advice);
+  // (a probe looks at no advice, not even at where it lives: no device call is made on its behalf)
+  const bool probe = c->probe && !cs.shape;
+  const bool device = !cs.shape && !probe && vdf_ptr_is_device(advice);
   if (device && (!c->ctx || cs.dev_len != 0)) return refuse("vdf_cs_repeat: advice in device memory outside vdf_nova_prove_step_custom");
-  if (device && c->step_advice && c->step_advice_elems) {
+  if ((device || probe) && c->step_advice && c->step_advice_elems) {
     // advice inside the trace a chain built for this step: the library owns that buffer and knows its length -- lanes * (t + 1)
     // entries -- so nothing may be read behind it, by the copies of entry t below or by the kernel
     const uintptr_t lo = (uintptr_t)c->step_advice, hi = lo + c->step_advice_elems * 32, at = (uintptr_t)advice;
@@ -796,7 +798,14 @@ int vdf_cs_repeat_lanes(vdf_cs* c, const vdf_round_body* b, uint64_t t, size_t l
   rep.row_begin = cs.rows;
   rep.d_advice = nullptr;
   const size_t na = rec.n_adv;
-  if (device) {
+  if (probe) {
+    // the body and the values of inv are what a lookahead needs; entry t is not copied (that would wait for the device), so the
+    // carries leave with the value 0, and neither variables nor rows are made
+    for (Num& n : carry_all) n = cs.zero_num();
+    rep.d_advice = advice;
+    rep.inv.resize(invn.size());
+    for (size_t k = 0; k < invn.size(); ++k) rep.inv[k] = invn[k].v;
+  } else if (device) {
     std::vector<Fe> last(na);
     for (size_t l = 0; l < lanes; ++l) {                                 // entry t of every lane: the values of its carry_out
       const int rc = vdf_dev_memcpy(c->ctx, last.data(), (const char*)advice + (l * lane_stride + t) * na * 32, na * 32);

@@ -161,6 +161,11 @@ for _name, _res, _args in [
     ("vdf_nova_prove_recursively_custom", _i, [_vp, _vp, _vp, _vp, _sz, C.c_uint32, C.POINTER(_vp)]),
     ("vdf_nova_proof_last_unsat", _i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     ("vdf_nova_pp_repeat_rows", _i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    # a custom chain's lookahead and early rows (tuning custom_ahead)
+    ("vdf_cs_is_probe", _i, [_vp]),
+    ("vdf_nova_tuning_read", _i, [_vp, _vp]),
+    ("vdf_nova_shape_early_rows_custom", _i, [_i, _vp] + [C.POINTER(_u64)] * 4),
+    ("vdf_nova_proof_ahead_stats", _i, [_vp] + [C.POINTER(_u64)] * 3),
 ]:
     if not hasattr(nova_lib, _name):          # AttributeError at call time names the missing entry point
         continue
@@ -187,7 +192,7 @@ class NovaTuning(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("digit_budget_bytes", C.c_uint64)] + [(k, C.c_int32) for k in (
         "digit_window", "early_rows", "stencil", "small_window", "big_window", "packed_commit", "lookahead_early", "gate_accumulate",
         "fold_on_rows", "nifs_ahead", "early_row_parts", "lookahead_priority", "side_accumulate_fill", "verbose", "compress_queues", "rows_at_challenge", "fold_fused",
-        "periodic_rows")]
+        "periodic_rows", "custom_ahead")]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -235,6 +240,19 @@ def tuning_default(**fields) -> NovaTuning:
 def _check(rc: int) -> None:
     if rc != 0:
         raise VdfError(rc, (nova_lib.vdf_nova_last_error() or b"").decode())
+
+
+def tuning_read(tuning: "NovaTuning | None" = None, struct_size: "int | None" = None) -> NovaTuning:
+    """Host only (vdf_nova_tuning_read): the tuning a constructor would run with.  struct_size: hand the struct over as a caller
+    compiled against an older header would -- the fields it does not have read as 0."""
+    t = NovaTuning()
+    if tuning is not None:
+        C.memmove(C.byref(t), C.byref(tuning), C.sizeof(NovaTuning))
+        if struct_size is not None:
+            t.struct_size = struct_size
+    out = NovaTuning()
+    _check(nova_lib.vdf_nova_tuning_read(C.byref(t) if tuning is not None else None, C.byref(out)))
+    return out
 
 
 def point_compress(aff: np.ndarray, curve: int = 0) -> bytes:
@@ -606,6 +624,12 @@ class ConstraintSystem:
     def is_witness(self) -> bool:
         return bool(nova_lib.vdf_cs_is_witness(self.h))
 
+    @property
+    def is_probe(self) -> bool:
+        """vdf_cs_is_probe: this witness synthesis is the extra one of tuning custom_ahead -- its values are kept by nobody, and
+        its `repeat` only records the body and the values of inv (include/vdf_nova.h, THE PROBE)."""
+        return bool(nova_lib.vdf_cs_is_probe(self.h))
+
     def const(self, k: bytes) -> int:
         return nova_lib.vdf_cs_const(self.h, C.byref(_Fe.from_buffer_copy(k)))
 
@@ -794,6 +818,16 @@ def shape_periodic_custom(circuit: StepCircuit, field: int = FIELD_FQ):
     return pr, info
 
 
+def shape_early_rows_custom(circuit: StepCircuit, field: int = FIELD_FQ) -> dict:
+    """Host only: the early rows public_params_custom(..., custom_ahead=2) would find -- dict(row_begin, rows, zin_begin,
+    seg_begin); rows = 0 for a run shorter than 64 rows or a circuit without a repeat."""
+    v = [C.c_uint64() for _ in range(4)]
+    rc = nova_lib.vdf_nova_shape_early_rows_custom(field, C.byref(circuit._c()), *[C.byref(x) for x in v])
+    _reraise(circuit)
+    _check(rc)
+    return dict(row_begin=v[0].value, rows=v[1].value, zin_begin=v[2].value, seg_begin=v[3].value)
+
+
 def periodic_rows_eval(field: int, rows: "PeriodicRows", j_first: int, reps: int, seg_begin: int, row_begin: int, num_cols: int,
                        num_cons: int, z2, az1, bz1, cz1, u1, az2, bz2, cz2, T) -> None:
     """Host only: Context.nifs_cross_term_periodic restated over numpy arrays (uint64[n, 4], written in place), byte for byte."""
@@ -807,7 +841,7 @@ def periodic_rows_eval(field: int, rows: "PeriodicRows", j_first: int, reps: int
 def public_params_custom(ctx: Context, circuit: StepCircuit, gens_family: int = GENS_TRY_AND_INCREMENT,
                          field: int = FIELD_FQ, tuning: "NovaTuning | None" = None, **tune) -> "NovaVDFPublicParams":
     """`field`: the orientation -- the field the circuit is synthesised over (FIELD_FP: G1 = Vesta).  `tuning` / keyword fields of
-    vdf_nova_tuning (e.g. periodic_rows=1): vdf_nova_public_params_custom_tuned."""
+    vdf_nova_tuning (e.g. periodic_rows=1, custom_ahead=2): vdf_nova_public_params_custom_tuned."""
     h = C.c_void_p()
     if tuning is not None or tune:
         t = tuning if tuning is not None else tuning_default()
@@ -1481,6 +1515,13 @@ class NovaVDFProof:               # enum NovaVDFProof { Recursive, Compressed },
         n, r = C.c_uint64(0), C.c_uint64(0)
         _check(nova_lib.vdf_nova_proof_last_unsat(self.handle, C.byref(n), C.byref(r)))
         return n.value, r.value
+
+    def ahead_stats(self) -> Tuple[int, int, int]:
+        """(hits, misses, skipped): the steps after the first in which a custom chain's lookahead (tuning custom_ahead) was used,
+        discarded, or not attempted; zeros for every other kind of proof."""
+        v = [C.c_uint64() for _ in range(3)]
+        _check(nova_lib.vdf_nova_proof_ahead_stats(self.handle, *[C.byref(x) for x in v]))
+        return v[0].value, v[1].value, v[2].value
 
     def compress(self, pp: NovaVDFPublicParams) -> "CompressedNovaVDFProof":            # :360-368
         h = C.c_void_p()
