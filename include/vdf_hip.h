@@ -767,6 +767,21 @@ int  vdf_lincomb_u128(vdf_ctx* ctx, int field, int count, const vdf_fe* const v[
  * VDF_ERR_BAD_ARG); z, E, out device memory; count 1..64.  The rows are read once for all instances. */
 int  vdf_relaxed_residual_batch(vdf_ctx* ctx, const vdf_shape* shape, int count, const vdf_fe* const z[], const vdf_fe* const E[],
                                 const vdf_fe u[], const vdf_fe rho[], vdf_fe* out);
+/* Many points of the shape's polynomial in one pass over its rows (vdf_nova_verify_compressed_batch: every proof's M(r_x, r_y)):
+ * out[q] = sum over the entries (x, y, v) of A, B, C of  eq_x[q][x] * w_q(matrix) * v * eq_y[q][ycol(y)],
+ * w_q = 1, rho[q], rho[q]^2;  ycol(y) = y for y < col_split, else col_hi_base + (y - col_split).
+ * eq_x[q]: nx >= num_cons elements, eq_y[q]: ny elements (device, Montgomery); rho Montgomery (host);
+ * out: count elements in HOST memory (Montgomery); count 0..VDF_SPARSE_EVAL_MAX (64).  The rows are read
+ * once per launch for all instances of that launch.  Synchronises once, whether the context is asynchronous or not.
+ * The vectors need not be eq tables: they are arbitrary field vectors to the kernel.  With eq_x[q] = eq(r_x, .) and
+ * eq_y[q] = eq(r_y, .) the result equals vdf_pair_table -> vdf_spmv3_t -> vdf_reduce(VDF_REDUCE_DOT) for the same point,
+ * limb for limb, without the transposed product and without the M vector.
+ * VDF_ERR_BAD_ARG, before anything is launched: a null pointer with count > 0, count above the cap, nx < num_cons,
+ * col_split > num_cols, col_split > ny, col_hi_base + (num_cols - col_split) > ny.  count == 0 is VDF_OK and writes nothing. */
+#define VDF_SPARSE_EVAL_MAX 64
+int  vdf_sparse_eval_multi(vdf_ctx* ctx, const vdf_shape* shape, int count, const vdf_fe* const eq_x[], size_t nx,
+                           const vdf_fe* const eq_y[], size_t ny, const vdf_fe rho[], size_t col_split, size_t col_hi_base,
+                           vdf_fe* out);
 /* One round of the inner-product argument without materialising folded generators: with n_j the current length of
  * a, s[t] the coefficient of original generator t in its folded generator, h = n_j / 2 and r = t mod n_j,
  *   sL[t] = r >= h ? s[t] a[r - h] : 0,   sR[t] = r < h ? s[t] a[r + h] : 0,   t < n,

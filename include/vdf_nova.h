@@ -863,6 +863,23 @@ int  vdf_nova_verify_compressed(const vdf_snark* snark, vdf_pp* pp, size_t num_s
  * count = 0 gives *all_ok = 1. */
 int  vdf_nova_verify_compressed_batch(vdf_pp* pp, size_t count, const vdf_snark* const snarks[], const size_t num_steps[],
                                       const vdf_fe* z0, const vdf_fe* zi, int ok[], int* all_ok);
+/* How vdf_nova_verify_compressed_batch evaluates the shape's polynomial at every proof's point, M(r_x, r_y) -- the one value a
+ * replay needs the device for.  The transcript does not absorb it, so the batch replays every proof on the host without a
+ * device wait and evaluates all of a side's points afterwards by passes over the shape's rows (vdf_hip.h
+ * vdf_sparse_eval_multi); an entry whose comparison fails leaves the batch before the combined group check.  Verdicts, *all_ok
+ * and error codes do not depend on the setting, and no proof's bytes do.  A switch of the parameter set, not of vdf_nova_tuning:
+ *   n = 0      every replay evaluates its own point, as vdf_nova_verify_compressed does (eq table, transposed product, dot, a wait);
+ *   n = 1..64  at most n points per pass.  A point holds 32 (M + Z) bytes of tables meanwhile (M, Z: the padded numbers of
+ *              constraints and of columns; 24 MB on the primary side at t = 2^16); a pass takes fewer points when the free
+ *              device memory less 2 GiB does not hold n of them.  The tables live in the side's scratch block, which the set keeps
+ *              at its largest size until it is freed.  A verifier short of memory lowers n.
+ * Anything else is VDF_ERR_BAD_ARG.  The initial value is the environment variable VDF_NOVA_VERIFY_MULTI (0..64) when it is
+ * set, else 16 (measured: DESIGN.md 4.4, profiles/r21_verify_multi.txt; tools/gpu_verify_multi_time.py).
+ * vdf_nova_pp_verify_multi reads the value back (0 for a null pp).  vdf_nova_pp_verify_multi_stats: out[0] = passes launched,
+ * out[1] = points evaluated, out[2] = points whose comparison failed, since the set was made. */
+int  vdf_nova_pp_set_verify_multi(vdf_pp* pp, int n);
+int  vdf_nova_pp_verify_multi(const vdf_pp* pp);
+int  vdf_nova_pp_verify_multi_stats(const vdf_pp* pp, uint64_t out[3]);
 /* Many running proofs under one parameter set: ok[q] = what vdf_nova_verify_custom returns for entry q (up to a soundness
  * error of about 2^-128), *all_ok = 1 iff every entry verifies; z0, zi: count x arity elements.  Each entry's exact checks
  * (step count, z0, output hashes, the last secondary instance's u and comm_E, zi, every instance's z tail) run on their own;

@@ -120,6 +120,7 @@ PROTOTYPES = {
     "vdf_spmv3_t_batch": (_i, [_vp, _vp, _sz, C.POINTER(_vp), _vp, C.POINTER(_vp)]),
     "vdf_lincomb_u128": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, _vp]),
     "vdf_relaxed_residual_batch": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp]),
+    "vdf_sparse_eval_multi": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.c_size_t, C.POINTER(_vp), C.c_size_t, _vp, C.c_size_t, C.c_size_t, _vp]),
     "vdf_ipa_scalars": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _vp]),
     "vdf_scale_pattern": (_i, [_vp, _i, _vp, _sz, _sz, _vp, _vp]),
     "vdf_fe_mul": (_i, [_vp, _i, _vp, _vp, _sz, _vp]),

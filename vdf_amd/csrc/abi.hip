@@ -673,6 +673,7 @@ void vdf_ctx_destroy(vdf_ctx* ctx) {
   if (ctx->small_pool) (void)hipFree(ctx->small_pool);
   if (ctx->h_out) (void)hipHostFree(ctx->h_out);
   if (ctx->reduce_scratch) (void)hipFree(ctx->reduce_scratch);
+  if (ctx->eval_scratch) (void)hipFree(ctx->eval_scratch);
   if (ctx->ipa_host) (void)hipHostFree(ctx->ipa_host);
   if (ctx->ipa_dev) (void)hipFree(ctx->ipa_dev);
   if (ctx->ipa_copied) (void)hipEventDestroy(ctx->ipa_copied);
@@ -2108,6 +2109,58 @@ int vdf_relaxed_residual_batch(vdf_ctx* ctx, const vdf_shape* shape, int count, 
     VDF_TRY(vdf::vec_relaxed_residual_batch(shape->field, shape->d_rowptr, shape->d_col, shape->d_coef, shape->d_dict, block, count,
                                             shape->num_cons, shape->d_long_rowlist, shape->n_long_rowlist, out, bytes, ctx->stream));
     if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
+int vdf_sparse_eval_multi(vdf_ctx* ctx, const vdf_shape* shape, int count, const vdf_fe* const eq_x[], size_t nx,
+                          const vdf_fe* const eq_y[], size_t ny, const vdf_fe rho[], size_t col_split, size_t col_hi_base, vdf_fe* out) {
+  return guarded(ctx, [&]() -> Status {
+    // every refusal comes before the first launch; the shape is read-only device data: any context of its device may run over it
+    if (!shape || !shape->ctx || shape->ctx->device != ctx->device) return Status{VDF_ERR_BAD_ARG, "bad shape handle"};
+    if (count < 0 || count > vdf::SPARSE_EVAL_MAX) return Status{VDF_ERR_BAD_ARG, "count must be 0..64"};
+    if (count == 0) return Status{};
+    if (nx < shape->num_cons) return Status{VDF_ERR_BAD_ARG, "the row vectors are shorter than the shape has rows"};
+    if (col_split > shape->num_cols || col_split > ny || col_hi_base > ny || shape->num_cols - col_split > ny - col_hi_base)
+      return Status{VDF_ERR_BAD_ARG, "the column map leaves the column vectors"};
+    if (!eq_x || !eq_y || !rho || !out) return Status{VDF_ERR_BAD_ARG, "null argument"};
+    if (ptr_is_device(rho) || ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, kHostScalar};
+    for (int q = 0; q < count; ++q) {
+      if (!eq_x[q] || !eq_y[q]) return Status{VDF_ERR_BAD_ARG, "null argument"};
+      if (!ptr_is_device(eq_x[q]) || !ptr_is_device(eq_y[q])) return Status{VDF_ERR_BAD_ARG, kDevVec};
+    }
+    const size_t wgs = vdf::sparse_eval_workgroups(shape->num_cons, shape->d_long_rowlist ? shape->n_long_rowlist : 0);
+    if (wgs >= ((size_t)1 << 31)) return Status{VDF_ERR_BAD_LENGTH, "shape too large"};
+    if (ny == 0 || wgs == 0) {                                        // no columns or no rows: every sum is empty
+      memset(out, 0, (size_t)count * sizeof(vdf_fe));
+      return Status{};
+    }
+    const size_t need = ((size_t)count + wgs * (size_t)count) * 32;
+    if (ctx->eval_scratch_bytes < need) {
+      VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));                 // an earlier launch may still write the block
+      if (ctx->eval_scratch) { (void)hipFree(ctx->eval_scratch); ctx->eval_scratch = nullptr; ctx->eval_scratch_bytes = 0; }
+      VDF_TRY_HIP(hipMalloc(&ctx->eval_scratch, need));
+      ctx->eval_scratch_bytes = need;
+    }
+    const void* block = nullptr;
+    Status packed;
+    VDF_TRY(arg_block(ctx, (size_t)count * vdf::sparse_eval_item_bytes(),
+                      [&](void* h) {
+                        packed = vdf::sparse_eval_pack(shape->field, count, reinterpret_cast<const void* const*>(eq_x),
+                                                       reinterpret_cast<const void* const*>(eq_y), rho, h);
+                      },
+                      &block));
+    VDF_TRY(packed);
+    // algorithmic bytes: the structure once (row pointers, columns and coefficient indices), per instance the gathered value of
+    // every entry and the row's weight
+    const double nnz3 = (double)(shape->nnz[0] + shape->nnz[1] + shape->nnz[2]);
+    const double bytes = (double)shape->num_cons * 3 * 4 + nnz3 * 8 + (double)count * 32 * (nnz3 + (double)shape->num_cons);
+    char* d_res = static_cast<char*>(ctx->eval_scratch);
+    VDF_TRY(vdf::vec_sparse_eval_multi(shape->field, shape->d_rowptr, shape->d_col, shape->d_coef, shape->d_dict, block, count,
+                                       shape->num_cons, col_split, col_hi_base, shape->d_long_rowlist, shape->n_long_rowlist,
+                                       d_res + (size_t)count * 32, d_res, bytes, ctx->stream));
+    VDF_TRY_HIP(hipMemcpyAsync(out, d_res, (size_t)count * 32, hipMemcpyDeviceToHost, ctx->stream));
+    VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));                   // the results are host memory: this call waits, asynchronous context or not
     return Status{};
   });
 }

@@ -483,6 +483,8 @@ int ipa_check_one(const Side& sd, const IpaDeferred& d, void* d_s, bool* ok) {
 
 // tables of this many entries and fewer finish their sum-check on the host (a power of two; at least 2)
 constexpr size_t SUMCHECK_HOST_TAIL = 512;
+// the HBM spartan_m_check leaves free beside its tables (the rule of vdf_nova_compress_batch's groups: COMPRESS_HBM_RESERVE)
+constexpr size_t VERIFY_HBM_RESERVE = (size_t)2 << 30;
 
 // The passes of K proofs' rounds: one launch for all of them (vdf_*_batch), or the single call for one proof (the launches
 // of vdf_nova_compress stay what they were)
@@ -733,12 +735,19 @@ int spartan_prove_many(const Side& sd, size_t K, const ProveIn* in, Arena* arena
 }
 
 
-// The verifier's transcript replay of one side's argument: sizes, both sum-checks, M(r_y) on the device, the openings up to
-// their deferred group checks (out[0]: W, out[1]: E).  *ok = false when an exact check fails.
-int spartan_replay(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, const Fe* X, const Spartan& pf, IpaDeferred out[2],
-                   bool* ok) {
-  const Side* pp = &sd;
-  vdf_ctx* ctx = sd.ctx;
+// What is left of the inner sum-check once the transcript is replayed: claim == M(r_x, r_y) z(r_y), with M(r_x, r_y) the one
+// value the verifier needs the device for.  The transcript does not absorb it and nothing after it depends on it, so the
+// comparison can wait until every proof of a batch has been replayed (spartan_m_check).
+struct MDeferred {
+  std::vector<Fe> rx, ry;
+  Fe rho, claim, z_ry;
+};
+
+// The verifier's transcript replay of one side's argument on the host alone, without a device call or wait: sizes, both
+// sum-checks up to the last comparison of the inner one (left in *md), the openings up to their deferred group checks
+// (out[0]: W, out[1]: E).  *ok = false when an exact check fails.
+int spartan_replay_host(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, const Fe* X, const Spartan& pf, IpaDeferred out[2],
+                        MDeferred* md, bool* ok) {
   const Field& F = *sd.F;
   const Layout L = layout_of(sd);
   *ok = false;
@@ -746,7 +755,10 @@ int spartan_replay(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, co
   Transcript tr("compress");
   instance_bytes(tr, sd, cW, cE, u, X);
   uint64_t raw[4];
-  std::vector<Fe> tau(L.s), rx, ry;
+  std::vector<Fe> tau(L.s);
+  std::vector<Fe>& rx = md->rx;
+  std::vector<Fe>& ry = md->ry;
+  rx.clear(); ry.clear();
   for (int j = 0; j < L.s; ++j) tau[j] = tr.challenge("tau", F, raw);
   // outer
   Fe claim = zero();
@@ -773,21 +785,6 @@ int spartan_replay(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, co
     claim = interpolate(y, 3, r, F);
     ry.push_back(r);
   }
-  // M(r_y) on the device: eq(r_x, .) -> transposed product -> dot with eq(r_y, .)
-  DevBufs bufs(ctx, sd.arena);
-  { int rc = bufs.reserve(L.M + pp->ncols + 2 * L.Z); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
-  void *d_eq_rx, *d_cols, *d_mvec, *d_eq_ry;
-  { int rc = bufs.zeros(L.M, &d_eq_rx); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
-  { int rc = bufs.zeros(pp->ncols, &d_cols); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
-  for (void** p : {&d_mvec, &d_eq_ry}) { int rc = bufs.zeros(L.Z, p); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
-  { int rc = eq_table_dev(sd, rx, d_eq_rx); if (rc != VDF_OK) return rc; }
-  { int rc = m_vector_dev(sd, L, d_eq_rx, rho, d_cols, d_mvec); if (rc != VDF_OK) return rc; }
-  { int rc = eq_table_dev(sd, ry, d_eq_ry); if (rc != VDF_OK) return rc; }
-  Fe m_ry;
-  {
-    const vdf_fe* tabs[2] = {(const vdf_fe*)d_mvec, (const vdf_fe*)d_eq_ry};
-    HIPCALL(ctx, vdf_reduce(ctx, sd.field, VDF_REDUCE_DOT, tabs, nullptr, L.Z, (vdf_fe*)&m_ry));
-  }
   // z(r_y) = (1 - r_y[0]) W~(rest) + r_y[0] * (u, X)~(rest); index i of the public half has bits MSB-first over rest
   std::vector<Fe> rest(ry.begin() + 1, ry.end());
   const int k = (int)rest.size();
@@ -797,13 +794,98 @@ int spartan_replay(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, co
     for (int j = 0; j < k; ++j) w = mul(w, ((i >> (k - 1 - j)) & 1) ? rest[j] : sub(one(F), rest[j], F), F);
     pub = add(pub, mul(w, i == 0 ? u : X[i - 1], F), F);
   }
-  const Fe z_ry = add(mul(sub(one(F), ry[0], F), pf.w_eval, F), mul(ry[0], pub, F), F);
-  if (claim != mul(m_ry, z_ry, F)) return VDF_OK;
+  md->rho = rho;
+  md->claim = claim;
+  md->z_ry = add(mul(sub(one(F), ry[0], F), pf.w_eval, F), mul(ry[0], pub, F), F);
   tr.absorb_fe("weval", &pf.w_eval, 1, F);
   IpaCheck checks[2];
   checks[0].label = "ipaW"; checks[0].n = L.NW; checks[0].rb = &rest; checks[0].v = pf.w_eval; checks[0].P = cW; checks[0].proof = &pf.ipaW;
   checks[1].label = "ipaE"; checks[1].n = L.M; checks[1].rb = &rx; checks[1].v = e; checks[1].P = cE; checks[1].proof = &pf.ipaE;
   return ipa_replay(sd, tr, checks, 2, out, ok);
+}
+
+// One proof's deferred comparison by the single verifier's device sequence: eq(r_x, .) -> transposed product -> dot with
+// eq(r_y, .), and a wait for the element.
+int spartan_m_single(const Side& sd, const MDeferred& md, bool* ok) {
+  const Side* pp = &sd;
+  vdf_ctx* ctx = sd.ctx;
+  const Field& F = *sd.F;
+  const Layout L = layout_of(sd);
+  *ok = false;
+  DevBufs bufs(ctx, sd.arena);
+  { int rc = bufs.reserve(L.M + pp->ncols + 2 * L.Z); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+  void *d_eq_rx, *d_cols, *d_mvec, *d_eq_ry;
+  { int rc = bufs.zeros(L.M, &d_eq_rx); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+  { int rc = bufs.zeros(pp->ncols, &d_cols); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+  for (void** p : {&d_mvec, &d_eq_ry}) { int rc = bufs.zeros(L.Z, p); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+  { int rc = eq_table_dev(sd, md.rx, d_eq_rx); if (rc != VDF_OK) return rc; }
+  { int rc = m_vector_dev(sd, L, d_eq_rx, md.rho, d_cols, d_mvec); if (rc != VDF_OK) return rc; }
+  { int rc = eq_table_dev(sd, md.ry, d_eq_ry); if (rc != VDF_OK) return rc; }
+  Fe m_ry;
+  {
+    const vdf_fe* tabs[2] = {(const vdf_fe*)d_mvec, (const vdf_fe*)d_eq_ry};
+    HIPCALL(ctx, vdf_reduce(ctx, sd.field, VDF_REDUCE_DOT, tabs, nullptr, L.Z, (vdf_fe*)&m_ry));
+  }
+  *ok = md.claim == mul(m_ry, md.z_ry, F);
+  return VDF_OK;
+}
+
+// The single verifier's replay of one side: the host part, then M(r_x, r_y) on the device.
+int spartan_replay(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, const Fe* X, const Spartan& pf, IpaDeferred out[2],
+                   bool* ok) {
+  MDeferred md;
+  { int rc = spartan_replay_host(sd, cW, cE, u, X, pf, out, &md, ok); if (rc != VDF_OK || !*ok) return rc; }
+  return spartan_m_single(sd, md, ok);
+}
+
+// The deferred comparisons of n proofs of one side (vdf_nova_verify_compressed_batch): the n pairs of eq tables (asynchronous,
+// no wait between them), then every M(r_x, r_y) of a group by ONE pass over the shape's rows (vdf_sparse_eval_multi, with the
+// column map of the padded layout m_vector_dev builds by copies: W at [0, NW), u and X from NW), one wait per group.  A group
+// is at most `width` points, and fewer when the free HBM (less the reserve vdf_nova_compress_batch keeps) does not hold the
+// tables beside the side's block.  stats: launches, points evaluated, points whose comparison failed.
+int spartan_m_check(const Side& sd, const MDeferred* const items[], size_t n, size_t width, bool ok[], uint64_t stats[3]) {
+  vdf_ctx* ctx = sd.ctx;
+  const Field& F = *sd.F;
+  const Layout L = layout_of(sd);
+  for (size_t q = 0; q < n; ++q) ok[q] = false;
+  if (n == 0) return VDF_OK;
+  const size_t per_point = 32 * (L.M + L.Z);
+  width = std::max<size_t>(1, std::min<size_t>({width, n, (size_t)VDF_SPARSE_EVAL_MAX}));
+  Arena* arena = sd.arena;
+  if (arena->cap < width * per_point) {
+    size_t free_b = 0, total_b = 0;
+    HIPCALL(ctx, vdf_dev_mem_info(ctx, &free_b, &total_b));
+    const size_t avail = arena->cap + (free_b > VERIFY_HBM_RESERVE ? free_b - VERIFY_HBM_RESERVE : 0);
+    width = std::max<size_t>(1, std::min(width, avail / per_point));
+    if (arena->cap < width * per_point) {
+      if (arena->p) { vdf_ctx_sync(ctx); vdf_dev_free(ctx, arena->p); arena->p = nullptr; arena->cap = 0; }
+      int rc = vdf_dev_alloc(ctx, width * per_point, &arena->p);
+      if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx));
+      arena->cap = width * per_point;
+    }
+  }
+  std::vector<const vdf_fe*> ex(width), ey(width);
+  std::vector<Fe> rho(width), m(width);
+  for (size_t g0 = 0; g0 < n; g0 += width) {
+    const size_t K = std::min(width, n - g0);
+    for (size_t q = 0; q < K; ++q) {                                  // (a table is written whole: the block needs no memset)
+      char* base = static_cast<char*>(arena->p) + q * per_point;
+      const MDeferred& d = *items[g0 + q];
+      { int rc = eq_table_dev(sd, d.rx, base); if (rc != VDF_OK) return rc; }
+      { int rc = eq_table_dev(sd, d.ry, base + 32 * L.M); if (rc != VDF_OK) return rc; }
+      ex[q] = (const vdf_fe*)base; ey[q] = (const vdf_fe*)(base + 32 * L.M);
+      rho[q] = d.rho;
+    }
+    HIPCALL(ctx, vdf_sparse_eval_multi(ctx, sd.shape, (int)K, ex.data(), L.M, ey.data(), L.Z, (const vdf_fe*)rho.data(), sd.num_vars, L.NW,
+                                       (vdf_fe*)m.data()));
+    stats[0] += 1; stats[1] += K;
+    for (size_t q = 0; q < K; ++q) {
+      const MDeferred& d = *items[g0 + q];
+      ok[g0 + q] = d.claim == mul(m[q], d.z_ry, F);
+      if (!ok[g0 + q]) stats[2] += 1;
+    }
+  }
+  return VDF_OK;
 }
 
 }  // namespace
@@ -1066,7 +1148,8 @@ namespace {
 // The exact checks of one compressed proof (src/nova/proof.rs:383): the two output hashes, the carried z_i, the last fold of
 // the instances, then each side's transcript replay; its four openings' group checks are left in d[side][W / E].  *ok =
 // false when an exact check fails.  The caller has checked the parameters and made the context asynchronous.
-int verify_replay(const vdf_snark* s, vdf_pp* pp, size_t num_steps, const vdf_fe* z0, const vdf_fe* zi, IpaDeferred d[2][2], bool* ok) {
+int verify_replay(const vdf_snark* s, vdf_pp* pp, size_t num_steps, const vdf_fe* z0, const vdf_fe* zi, IpaDeferred d[2][2], bool* ok,
+                  MDeferred* md = nullptr) {
   *ok = false;
   if (num_steps == 0) return VDF_OK;
   const Side& S1 = pp->s[PRIMARY];
@@ -1085,9 +1168,12 @@ int verify_replay(const vdf_snark* s, vdf_pp* pp, size_t num_steps, const vdf_fe
   fold_challenge(pp, s->r_U2, s->l_u2, s->T2, r);
   const Inst f2 = fold_instance(S2, s->r_U2, s->l_u2, s->T2, r);
   bool good = false;
-  int rc = spartan_replay(S1, s->r_U1.comm_W, s->r_U1.comm_E, s->r_U1.u, s->r_U1.X, s->sp[0], d[0], &good);
+  // md (two entries, one per side): the replays stay on the host and leave their comparison with M(r_x, r_y) there
+  int rc = md ? spartan_replay_host(S1, s->r_U1.comm_W, s->r_U1.comm_E, s->r_U1.u, s->r_U1.X, s->sp[0], d[0], &md[0], &good)
+              : spartan_replay(S1, s->r_U1.comm_W, s->r_U1.comm_E, s->r_U1.u, s->r_U1.X, s->sp[0], d[0], &good);
   if (rc != VDF_OK || !good) return rc;
-  rc = spartan_replay(S2, f2.comm_W, f2.comm_E, f2.u, f2.X, s->sp[1], d[1], &good);
+  rc = md ? spartan_replay_host(S2, f2.comm_W, f2.comm_E, f2.u, f2.X, s->sp[1], d[1], &md[1], &good)
+          : spartan_replay(S2, f2.comm_W, f2.comm_E, f2.u, f2.X, s->sp[1], d[1], &good);
   if (rc != VDF_OK || !good) return rc;
   *ok = true;
   return VDF_OK;
@@ -1173,6 +1259,21 @@ int msm_points(const Side& sd, const std::vector<Aff>& pts, const std::vector<Fe
   return VDF_OK;
 }
 
+// Points per pass of the batch verifier's M(r_x, r_y) for a new parameter set.  Shipped: 16 -- at t = 2^16 its slowest batch of 16
+// was faster than the per-proof sequence's fastest, and a batch of one no slower (profiles/r21_verify_multi.txt;
+// tools/gpu_verify_multi_time.py states the rule).
+int verify_multi_default() {
+  static const int v = [] {
+    if (const char* e = env_override("VDF_NOVA_VERIFY_MULTI")) {
+      char* end = nullptr;
+      const long n = strtol(e, &end, 10);
+      if (end != e && *end == 0 && n >= 0 && n <= VDF_SPARSE_EVAL_MAX) return (int)n;
+    }
+    return 16;
+  }();
+  return v;
+}
+
 }  // namespace vdfnova
 
 extern "C" {
@@ -1239,17 +1340,33 @@ int vdf_nova_verify_compressed_batch(vdf_pp* pp, size_t count, const vdf_snark* 
     HIPCALL(ctx, vdf_ctx_set_async(ctx, 1));
     struct Restore { vdf_ctx* c; int a; ~Restore() { vdf_ctx_sync(c); vdf_ctx_set_async(c, a); } } restore{ctx, was_async};
     // exact checks and replays; an entry that fails one leaves the batch
+    // verify_multi = n > 0: the replays run on the host alone, and every live entry's M(r_x, r_y) is evaluated afterwards, at
+    // most n points per pass over a side's shape (spartan_m_check); 0: each replay evaluates its own, as the single verifier does
+    const size_t multi = (size_t)pp->verify_multi.load();
     std::vector<std::array<std::array<IpaDeferred, 2>, 2>> d(count);
+    std::vector<std::array<MDeferred, 2>> md(multi ? count : 0);
     std::vector<size_t> live;
     for (size_t q = 0; q < count; ++q) {
       IpaDeferred dq[2][2];
       bool good = false;
-      int rc = verify_replay(snarks[q], pp, num_steps[q], z0 + q * ar, zi + q * ar, dq, &good);
+      int rc = verify_replay(snarks[q], pp, num_steps[q], z0 + q * ar, zi + q * ar, dq, &good, multi ? md[q].data() : nullptr);
       if (rc != VDF_OK) return rc;
       if (!good) continue;
       for (int side = 0; side < 2; ++side)
         for (int o = 0; o < 2; ++o) d[q][side][o] = std::move(dq[side][o]);
       live.push_back(q);
+    }
+    for (int side = 0; multi && side < 2 && !live.empty(); ++side) {
+      std::vector<const MDeferred*> items;
+      for (size_t q : live) items.push_back(&md[q][side]);
+      std::unique_ptr<bool[]> good(new bool[items.size()]);
+      uint64_t st[3] = {0, 0, 0};
+      int rc = spartan_m_check(pp->s[side], items.data(), items.size(), multi, good.get(), st);
+      for (int k = 0; k < 3; ++k) pp->verify_multi_stats[k] += st[k];
+      if (rc != VDF_OK) return rc;
+      std::vector<size_t> still;
+      for (size_t k = 0; k < live.size(); ++k) if (good[k]) still.push_back(live[k]);
+      live.swap(still);
     }
     // one weight per opening: entry by entry, side by side, W then E (drawn for every entry, so that the weights of an
     // entry do not depend on which others failed)
@@ -1440,6 +1557,20 @@ int vdf_nova_snark_deserialize(vdf_pp* pp, const uint8_t* in, size_t len, vdf_sn
     *out = s.release();
     return VDF_OK;
   });
+}
+
+// ---- how many points of a shape one pass of the batch verifier evaluates (include/vdf_nova.h) ------------------------
+int vdf_nova_pp_set_verify_multi(vdf_pp* pp, int n) {
+  if (!pp) return fail(VDF_ERR_BAD_ARG, "null argument");
+  if (n < 0 || n > VDF_SPARSE_EVAL_MAX) return fail(VDF_ERR_BAD_ARG, "verify_multi must be 0..64");
+  pp->verify_multi.store(n);
+  return VDF_OK;
+}
+int vdf_nova_pp_verify_multi(const vdf_pp* pp) { return pp ? pp->verify_multi.load() : 0; }
+int vdf_nova_pp_verify_multi_stats(const vdf_pp* pp, uint64_t out[3]) {
+  if (!pp || !out) return fail(VDF_ERR_BAD_ARG, "null argument");
+  for (int k = 0; k < 3; ++k) out[k] = pp->verify_multi_stats[k].load();
+  return VDF_OK;
 }
 
 }  // extern "C"

@@ -1100,6 +1100,7 @@ static int public_params_impl(vdf_ctx* ctx, int fid, uint64_t t, int circuit_kin
   pp->lanes = lanes;
   pp->arity = custom ? custom->arity : 3 * lanes;
   pp->tune = tune;
+  pp->verify_multi.store(verify_multi_default());
   pp->ro = ro ? ro : ro_default();
   double* ms = pp->setup_ms;                       // [0] shapes + digest, [1] shapes to the device, [2] generators, [3] tables, [4] digit tables
   double mark = t_start;

@@ -3,6 +3,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <chrono>
 #include <functional>
 #include <cstdio>
@@ -140,6 +141,10 @@ struct vdf_pp {
   std::mutex aux_mu;                       // ... one compression at a time uses it: concurrent vdf_nova_compress calls under ONE parameter
                                            // set take turns at the arguments (calls under different sets do not meet)
   vdf_nova_tuning tune;                    // the tuning this set was made with, and that its prover runs with
+  // vdf_nova_verify_compressed_batch: 0 = every replay evaluates its own M(r_x, r_y); n = 1..64: all of a side's by passes over the
+  // shape of at most n points each (vdf_nova_pp_set_verify_multi; initial value: VDF_NOVA_VERIFY_MULTI, else verify_multi_default)
+  std::atomic<int> verify_multi{0};
+  std::atomic<uint64_t> verify_multi_stats[3] = {{0}, {0}, {0}};      // launches, points evaluated, points whose comparison failed
   double setup_ms[7] = {0, 0, 0, 0, 0, 0, 0};
   uint64_t digit_table_bytes[2] = {0, 0};  // HBM held by each side's digit table (vdf_nova_pp_memory)
   unsigned digit_tables_skipped = 0;       // bit s: side s asked for a digit table and went without (no room, refused window)
@@ -289,6 +294,7 @@ struct vdf_proof {
 
 namespace vdfnova {
 const vdf_nova_tuning& default_tuning();   // defaults + the VDF_NOVA_* environment overrides, read once
+int verify_multi_default();                // VDF_NOVA_VERIFY_MULTI (0..64) when set, else the shipped default (compress_host.cpp)
 bool tuning_valid(const vdf_nova_tuning& t);
 int alloc_proof_buffers(vdf_proof* p);
 int finalize_l2(const vdf_proof* p);      // commits to the last secondary witness if that is still pending

@@ -88,6 +88,8 @@ struct vdf_ctx {
   hipEvent_t side_go[4] = {nullptr, nullptr, nullptr, nullptr}, side_done[4] = {nullptr, nullptr, nullptr, nullptr};
   bool job_open = false;
   void* reduce_scratch = nullptr;    // per-workgroup partial sums of vdf_reduce
+  void* eval_scratch = nullptr;      // vdf_sparse_eval_multi: count results, then its per-workgroup partial sums (grown on demand)
+  size_t eval_scratch_bytes = 0;
   void* ipa_host = nullptr;          // vdf_ipa_coefficients: the openings' factors packed in pinned memory ...
   void* ipa_dev = nullptr;           // ... and their device copy, ipa_cap bytes each (grown on demand)
   size_t ipa_cap = 0;
@@ -368,6 +370,16 @@ void residual_pack(int count, const void* const z[], const void* const E[], cons
 Status vec_relaxed_residual_batch(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3], const uint32_t* const coef[3],
                                   const void* dict, const void* block, int count, size_t rows, const uint32_t* long_rowlist,
                                   size_t n_long_rows, void* out, double alg_bytes, hipStream_t s);
+// multi-point sparse evaluation (vdf_sparse_eval_multi): the instances (two device vectors, rho Montgomery; rho^2 made here)
+// packed into a block the kernel reads from device memory; partials: sparse_eval_workgroups() x count elements of scratch
+constexpr int SPARSE_EVAL_MAX = VDF_SPARSE_EVAL_MAX;     // instances of one vdf_sparse_eval_multi
+size_t sparse_eval_item_bytes();
+size_t sparse_eval_workgroups(size_t rows, size_t n_long_rows);
+Status sparse_eval_pack(int field, int count, const void* const ex[], const void* const ey[], const vdf_fe rho[], void* block);
+Status vec_sparse_eval_multi(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3], const uint32_t* const coef[3],
+                             const void* dict, const void* block, int count, size_t rows, size_t col_split, size_t col_hi_base,
+                             const uint32_t* long_rowlist, size_t n_long_rows, void* partials, void* d_out, double alg_bytes,
+                             hipStream_t s);
 Status vec_mul(int field, const void* a, const void* b, size_t n, void* out, hipStream_t s);
 Status vec_any_nonzero(const void* v, size_t n, uint32_t* d_flag, hipStream_t s);     // *d_flag = 1 iff some element is non-zero
 Status vec_unsat_rows(int field, const void* a, const void* b, const void* c, size_t n, void* d_res, hipStream_t s);   // d_res[0] = rows with a b != c, d_res[1] = the first

@@ -1156,6 +1156,203 @@ void residual_pack(int count, const void* const z[], const void* const E[], cons
 }
 size_t residual_item_bytes() { return sizeof(ResidualItem); }
 
+// ---- multi-point sparse evaluation (vdf_nova_verify_compressed_batch) ------------------------------------------------
+// out[q] = sum over the entries (x, y, v) of A, B, C of  ex_q[x] w_q(matrix) v ey_q[ycol(y)],  w_q = 1, rho_q, rho_q^2:
+// M(r_x, r_y) of many proofs in one pass over the rows, with no transposed product and no M vector.  Rows are taken as
+// k_relaxed_residual_batch takes them (one lane per short row with its first PRE entries loaded once; the first `long_wgs`
+// workgroups give every row of the long-row list one wavefront whose lanes stride the entries).  Per instance a lane forms
+// ex_q[r] (s_A + rho_q s_B + rho_q^2 s_C) of ITS entries -- the term is linear in the entries, so a long row's lanes need no
+// sum of their own: the workgroup's reduction adds them.  CH instances per pass keep their terms in registers; at the end of
+// a pass: butterfly over the wave, LDS over the four waves, one partial per workgroup and instance (partials[q][workgroup]).
+// Field addition is exact and commutative: no atomics, and the result does not depend on the order.
+// ycol(y) = y below col_split, else col_hi_base + (y - col_split): the padded layout of the compression argument.
+struct EvalItem { const char* ex; const char* ey; uint32_t rho[8]; uint32_t rho2[8]; };
+static_assert(sizeof(EvalItem) == 80, "argument block layout");
+// instances per pass, by the register report: 2 = 244 VGPRs, two waves per SIMD; 4 = 256 + 5 AGPRs, one wave; 8 goes
+// to scratch memory.  `make ab AB_FLAGS=-DVDF_SPARSE_EVAL_CHUNK=4` builds the other for a timing (tools/gpu_verify_multi_time.py).
+#ifndef VDF_SPARSE_EVAL_CHUNK
+#define VDF_SPARSE_EVAL_CHUNK 2
+#endif
+constexpr int SPARSE_EVAL_CHUNK = VDF_SPARSE_EVAL_CHUNK;
+static_assert(SPARSE_EVAL_CHUNK == 2 || SPARSE_EVAL_CHUNK == 4, "8 instances per pass spill");
+template <class P>
+__device__ __forceinline__ Fe<P> fe_wave_sum(Fe<P> a) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    Fe<P> o;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o.v[i] = __shfl_xor(a.v[i], off, 64);
+    a = fe_add(a, o);
+  }
+  return a;
+}
+template <class P>
+__device__ __forceinline__ Fe<P> eval_term(const Fe<P>& ex, const Fe<P> s[3], const EvalItem& it) {
+  Fe<P> rho, rho2;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { rho.v[k] = it.rho[k]; rho2.v[k] = it.rho2[k]; }
+  return fe_mul(ex, fe_add(s[0], fe_add(fe_mul(rho, s[1]), fe_mul(rho2, s[2]))));
+}
+template <class P, int CH>
+__global__ __launch_bounds__(256) void k_sparse_eval_multi(Csr3 m, const char* __restrict__ dict, const EvalItem* __restrict__ items, int count,
+                                                           size_t rows, size_t col_split, size_t col_hi_base,
+                                                           const uint32_t* __restrict__ long_rowlist, size_t n_long, uint32_t long_wgs,
+                                                           char* __restrict__ partials) {
+  __builtin_amdgcn_s_setprio(3);     // light kernel: do not starve behind a co-running k_accumulate
+  __shared__ uint32_t red[4][CH][8];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool long_wg = blockIdx.x < long_wgs;                       // uniform: a workgroup takes long rows or short ones
+  auto ycol = [&](uint32_t c) -> size_t { return c < col_split ? (size_t)c : col_hi_base + ((size_t)c - col_split); };
+  // no lane leaves before the last barrier: one without a row (the grid's tail, a long row among the short, a wavefront past
+  // the long-row list) carries zero terms
+  bool active;
+  size_t r = 0;
+  if (long_wg) {
+    const size_t w = (size_t)blockIdx.x * 4 + wave;
+    active = w < n_long;
+    if (active) r = long_rowlist[w];
+  } else {
+    r = (size_t)(blockIdx.x - long_wgs) * 256 + threadIdx.x;
+    active = r < rows;
+  }
+  uint32_t lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  if (active) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { lo[k] = m.rowptr[k][r]; hi[k] = m.rowptr[k][r + 1]; }
+  }
+  if (!long_wg && (hi[0] - lo[0] > VDF_LONG_ROW || hi[1] - lo[1] > VDF_LONG_ROW || hi[2] - lo[2] > VDF_LONG_ROW)) active = false;   // a wavefront's row
+  constexpr int PRE[3] = {2, 2, 4};
+  size_t cc[3][4];
+  uint32_t kk[3][4];
+  Fe<P> dv[3][4];
+  if (!long_wg) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int j = 0; j < PRE[k]; ++j) {
+        const bool has = active && lo[k] + j < hi[k];                  // (an absent entry gathers element 0 and is not used)
+        cc[k][j] = has ? ycol(m.col[k][lo[k] + j]) : 0;
+        kk[k][j] = has ? m.coef[k][lo[k] + j] : 0u;
+      }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int j = 0; j < PRE[k]; ++j) dv[k][j] = kk[k][j] > 1 ? fe_load<P>(dict + (size_t)kk[k][j] * 32) : fe_zero<P>();
+  }
+  for (int q0 = 0; q0 < count; q0 += CH) {
+    Fe<P> acc[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      acc[c] = fe_zero<P>();
+      if (q0 + c >= count || !active) continue;
+      const EvalItem& it = items[q0 + c];
+      const Fe<P> ex = fe_load<P>(it.ex + r * 32);
+      Fe<P> s[3];
+      if (long_wg) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          s[k] = fe_zero<P>();
+          for (uint32_t e = lo[k] + lane; e < hi[k]; e += 64)
+            s[k] = fe_add(s[k], spmv_term<P>(fe_load<P>(it.ey + ycol(m.col[k][e]) * 32), m.coef[k][e], dict));
+        }
+      } else {
+        Fe<P> v[3][4];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+          for (int j = 0; j < PRE[k]; ++j) v[k][j] = fe_load<P>(it.ey + cc[k][j] * 32);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          s[k] = fe_zero<P>();
+#pragma unroll
+          for (int j = 0; j < PRE[k]; ++j) {
+            if (lo[k] + j >= hi[k]) break;
+            const uint32_t ci = kk[k][j];
+            s[k] = ci == 0 ? fe_add(s[k], v[k][j]) : ci == 1 ? fe_sub(s[k], v[k][j]) : fe_add(s[k], fe_mul(v[k][j], dv[k][j]));
+          }
+          for (uint32_t e = lo[k] + PRE[k]; e < hi[k]; ++e)
+            s[k] = fe_add(s[k], spmv_term<P>(fe_load<P>(it.ey + ycol(m.col[k][e]) * 32), m.coef[k][e], dict));
+        }
+      }
+      acc[c] = eval_term<P>(ex, s, it);
+    }
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      if (q0 + c >= count) continue;                                   // uniform
+      const Fe<P> t = fe_wave_sum<P>(acc[c]);
+      if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) red[wave][c][i] = t.v[i];
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < CH && q0 + (int)threadIdx.x < count) {
+      Fe<P> t = fe_zero<P>();
+      for (int w = 0; w < 4; ++w) {
+        Fe<P> o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o.v[i] = red[w][threadIdx.x][i];
+        t = fe_add(t, o);
+      }
+      fe_store<P>(partials + ((size_t)(q0 + threadIdx.x) * gridDim.x + blockIdx.x) * 32, t);
+    }
+    __syncthreads();                                                   // the next pass writes red again
+  }
+}
+// out[q] = the sum of instance q's partials: one wavefront per instance
+template <class P>
+__global__ __launch_bounds__(64) void k_sparse_eval_sum(const char* __restrict__ partials, uint32_t nwg, char* __restrict__ out) {
+  __builtin_amdgcn_s_setprio(3);
+  const uint32_t q = blockIdx.x, lane = threadIdx.x;
+  Fe<P> acc = fe_zero<P>();
+  for (uint32_t w = lane; w < nwg; w += 64) acc = fe_add(acc, fe_load<P>(partials + ((size_t)q * nwg + w) * 32));
+  acc = fe_wave_sum<P>(acc);
+  if (lane == 0) fe_store<P>(out + (size_t)q * 32, acc);
+}
+
+size_t sparse_eval_item_bytes() { return sizeof(EvalItem); }
+// workgroups of a launch over `rows` rows; every instance keeps one 32-byte partial per workgroup
+size_t sparse_eval_workgroups(size_t rows, size_t n_long_rows) { return (rows + 255) / 256 + (n_long_rows + 3) / 4; }
+Status sparse_eval_pack(int field, int count, const void* const ex[], const void* const ey[], const vdf_fe rho[], void* block) {
+  EvalItem* it = reinterpret_cast<EvalItem*>(block);
+  return with_field(field, [&](auto f) {
+    using P = tag_t<decltype(f)>;
+    for (int q = 0; q < count; ++q) {
+      it[q].ex = cbytes_of(ex[q]);
+      it[q].ey = cbytes_of(ey[q]);
+      Fe<P> r;
+      memcpy(r.v, rho[q].l, 32);
+      const Fe<P> r2 = fe_sqr(r);
+      memcpy(it[q].rho, r.v, 32);
+      memcpy(it[q].rho2, r2.v, 32);
+    }
+    return Status{};
+  });
+}
+// partials: sparse_eval_workgroups() x count elements; d_out: count elements
+Status vec_sparse_eval_multi(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3], const uint32_t* const coef[3],
+                             const void* dict, const void* block, int count, size_t rows, size_t col_split, size_t col_hi_base,
+                             const uint32_t* long_rowlist, size_t n_long_rows, void* partials, void* d_out, double alg_bytes,
+                             hipStream_t s) {
+  if (count == 0) return Status{};
+  Csr3 m;
+  for (int k = 0; k < 3; ++k) { m.rowptr[k] = rowptr[k]; m.col[k] = col[k]; m.coef[k] = coef[k]; }
+  if (!long_rowlist) n_long_rows = 0;
+  const size_t wgs = sparse_eval_workgroups(rows, n_long_rows);
+  if (wgs >= ((size_t)1 << 31)) return Status{VDF_ERR_BAD_LENGTH, "shape too large"};
+  if (wgs == 0) return hip_status(hipMemsetAsync(d_out, 0, (size_t)count * 32, s), "hipMemsetAsync");     // no rows: every sum is empty
+  const uint32_t long_wgs = (uint32_t)((n_long_rows + 3) / 4);
+  KTimer kt(s, "k_sparse_eval_multi", alg_bytes);        // both launches: the sum of the partials is part of the evaluation
+  VDF_TRY(with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_sparse_eval_multi<tag_t<decltype(f)>, SPARSE_EVAL_CHUNK>), dim3((unsigned)wgs), dim3(256), 0, s, m, cbytes_of(dict),
+                       reinterpret_cast<const EvalItem*>(block), count, rows, col_split, col_hi_base, long_rowlist, n_long_rows, long_wgs,
+                       bytes_of(partials));
+  }));
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_sparse_eval_sum<tag_t<decltype(f)>>), dim3((unsigned)count), dim3(64), 0, s, cbytes_of(partials), (uint32_t)wgs, bytes_of(d_out));
+  });
+}
+
 // flag |= 1 when any of the n 32-byte elements is not all-zero (a residual vector checked where it lies)
 __global__ __launch_bounds__(256) void k_any_nonzero(const uint4* __restrict__ v, size_t n16, uint32_t* __restrict__ flag) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

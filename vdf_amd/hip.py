@@ -720,6 +720,30 @@ class Context:
         r = np.ascontiguousarray(rhos, dtype="<u8").reshape(-1, 4)
         self._check(lib.vdf_relaxed_residual_batch(self.handle, shape.handle, count, z, e, _ptr(u), _ptr(r), _ptr(out)))
 
+    def sparse_eval_multi(self, shape: Shape, eq_xs, eq_ys, rhos, col_split=None, col_hi_base=0, out=None):
+        """vdf_sparse_eval_multi: out[q] = sum over the entries (x, y, v) of A, B, C of eq_xs[q][x] w_q v eq_ys[q][ycol(y)], w_q = 1,
+        rhos[q], rhos[q]^2, for all q in one pass over the rows; ycol(y) = y below col_split (default: num_cols, the identity), else
+        col_hi_base + (y - col_split).  eq_xs, eq_ys: device tensors of (nx, 4) and (ny, 4) uint64 limbs, Montgomery, one length
+        each; rhos: (count, 4) Montgomery host limbs.  Returns the (count, 4) limbs (a host array; `out` if given)."""
+        count = len(eq_xs)
+        if len(eq_ys) != count:
+            raise ValueError("one column vector per row vector")
+        nx = {int(x.shape[0]) for x in eq_xs}
+        ny = {int(y.shape[0]) for y in eq_ys}
+        if len(nx) > 1 or len(ny) > 1:
+            raise ValueError("the vectors of a call have one length")
+        ex = (C.c_void_p * max(count, 1))(*[_ptr(x) for x in eq_xs])
+        ey = (C.c_void_p * max(count, 1))(*[_ptr(y) for y in eq_ys])
+        r = np.ascontiguousarray(rhos, dtype="<u8").reshape(-1, 4)
+        if r.shape[0] != count:
+            raise ValueError("one rho per instance")
+        if out is None:
+            out = np.zeros((count, 4), dtype="<u8")
+        split = shape.num_cols if col_split is None else col_split
+        self._check(lib.vdf_sparse_eval_multi(self.handle, shape.handle, count, ex, nx.pop() if nx else 0, ey, ny.pop() if ny else 0,
+                                              _ptr(r), split, col_hi_base, _ptr(out)))
+        return out
+
     def ipa_scalars(self, field, a, s, n, nj, sL, sR) -> None:
         self._check(lib.vdf_ipa_scalars(self.handle, field, _ptr(a), _ptr(s), n, nj, _ptr(sL), _ptr(sR)))
 

@@ -35,6 +35,9 @@ for _name, _res, _args in [
     ("vdf_nova_pp_segment", _i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     ("vdf_nova_pp_early_rows", _i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     ("vdf_nova_pp_stencil", _i, [_vp]),
+    ("vdf_nova_pp_set_verify_multi", _i, [_vp, _i]),
+    ("vdf_nova_pp_verify_multi", _i, [_vp]),
+    ("vdf_nova_pp_verify_multi_stats", _i, [_vp, C.POINTER(_u64)]),
     ("vdf_nova_shape_stencil", _i, [_u64, _i, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     ("vdf_nova_eval_and_make_circuits", _i, [_i, _u64, _sz, C.POINTER(_State), C.POINTER(_Fe * 3), C.POINTER(_vp)]),
     ("vdf_nova_circuits_from_checkpoints", _i, [_u64, _u64, _sz, _vp, C.POINTER(_Fe * 3), C.POINTER(_vp)]),
@@ -922,6 +925,22 @@ class NovaVDFPublicParams:        # src/nova/proof.rs:38-43
         b, n = C.c_uint64(), C.c_uint64()
         _check(nova_lib.vdf_nova_pp_early_rows(self.handle, C.byref(b), C.byref(n)))
         return b.value, n.value
+
+    def set_verify_multi(self, n: int) -> None:
+        """vdf_nova_pp_set_verify_multi: how many proofs' M(r_x, r_y) one pass over a side's shape evaluates in
+        verify_compressed_batch (1..64), or 0 for the per-proof device sequence of the single verifier.  Verdicts do not depend on
+        it; a verifier short of device memory lowers it (a point holds its two eq tables meanwhile)."""
+        _check(nova_lib.vdf_nova_pp_set_verify_multi(self.handle, n))
+
+    @property
+    def verify_multi(self) -> int:
+        return int(nova_lib.vdf_nova_pp_verify_multi(self.handle))
+
+    def verify_multi_stats(self) -> Tuple[int, int, int]:
+        """(passes launched, points evaluated, points whose comparison failed) since the set was made."""
+        out = (_u64 * 3)()
+        _check(nova_lib.vdf_nova_pp_verify_multi_stats(self.handle, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def stencil(self) -> int:
         """4 / 3: the early rows run as the MinRoot stencil (reference / bound rounds), 5: as the forward circuit's stencil,
