@@ -305,7 +305,9 @@ int  vdf_nova_circuits_materialize(vdf_ctx* ctx, vdf_circuits* c, size_t first, 
  * returns -- makes a release between two steps safe. */
 int  vdf_nova_circuits_release(vdf_circuits* c, size_t first, size_t count);
 /* how many circuits have a device trace now, and the device memory the traces hold: resident x (t + 1) x 64 bytes, plus the
- * traces already released out of an allocation that others still use.  Pending walks are not waited for.  Outputs may be NULL. */
+ * traces already released out of an allocation that others still use, plus the allocation a windowed prove_recursively keeps
+ * between two windows (it exists only inside that call, so a single-threaded caller never sees it; vdf_nova_custom_chain_memory
+ * counts it the same way).  Pending walks are not waited for.  Outputs may be NULL. */
 int  vdf_nova_circuits_memory(const vdf_circuits* c, size_t* resident_steps, uint64_t* device_bytes);
 /* the device trace of circuit k, 2 (t + 1) elements, NULL when it has none (pending walks over it are finished first): for
  * tests and tools */

@@ -403,3 +403,16 @@ def test_c_example_runs_as_a_fresh_process():
         r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
         assert "verify: true" in r.stdout and "traces left on the device: 0 steps, 0 bytes" in r.stdout
+
+
+@pytest.mark.parametrize("args, launch", [(["6", "7", "4", "3"], 3), (["6", "7", "6", "2"], 5)])
+def test_c_example_walks_in_many_launches_through_the_pump(args, launch):
+    """A launch length below `every` (VDF_NOVA_WALK_LAUNCH, read once per process: hence a child): the first enqueue of a window's
+    job no longer finishes it, and the rest of its rounds is what every prove_step's pump shares out -- t = 64 with `every` = 16
+    in launches of 3 (six per job, windows of three steps), and `every` = 64 in launches of 5 (thirteen, windows of two).  The
+    example exits 0 only if the proof verifies, which one over a wrongly rebuilt trace does not, and no trace is left resident."""
+    exe = os.path.join(ROOT, "examples", "prove_from_checkpoints")
+    assert os.path.exists(exe), "examples/prove_from_checkpoints is built by vdf_amd/csrc/Makefile (all)"
+    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=600, env=dict(os.environ, VDF_NOVA_WALK_LAUNCH=str(launch)))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "verify: true" in r.stdout and "traces left on the device: 0 steps, 0 bytes" in r.stdout

@@ -8,7 +8,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 W=${1:-/tmp/vdf_lanes_asan}
 rm -rf "$W" && mkdir -p "$W"
 cd "$ROOT/vdf_amd/csrc"
-for f in host_math minroot_host r1cs nova_host circuits_host compress_host wire_host rounds_host custom_chain_host; do
+for f in host_math minroot_host r1cs nova_host trace_walks circuits_host compress_host wire_host rounds_host custom_chain_host; do
   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -pthread -c host/$f.cpp -o "$W/$f.o" &
 done
 wait

@@ -96,108 +96,57 @@ uint64_t walk_launch_rounds() {
   }();
   return v;
 }
-// the one cast (WalkState, nova_internal.hpp): walks resolved, begun or parked under a const handle write d_trace and block of v[k]
+// the one cast (CircuitWalks, nova_internal.hpp): walks resolved, begun or parked under a const handle write d_trace and block of v[k]
 vdf_circuits* written(const vdf_circuits* c) { return const_cast<vdf_circuits*>(c); }
-void scratch_free(WalkState& w) {
-  if (w.d_walk) vdf_dev_free(w.side, w.d_walk);
-  if (w.d_expect) vdf_dev_free(w.side, w.d_expect);
-  if (w.h_ok) vdf_host_free(w.side, w.h_ok);
-  w.d_walk = w.d_expect = nullptr; w.h_ok = nullptr;
-  w.scratch_walks = 0;
-}
-int scratch_ensure(WalkState& w, size_t walks) {
-  if (w.scratch_walks >= walks) return VDF_OK;
-  scratch_free(w);
-  vdf_ctx* q = w.side;
-  if (vdf_dev_alloc(q, walks * 96, &w.d_walk) != VDF_OK || vdf_dev_alloc(q, walks * 96, &w.d_expect) != VDF_OK ||
-      vdf_host_alloc(q, walks * sizeof(int), (void**)&w.h_ok) != VDF_OK) {
-    const int rc = fail(VDF_ERR_OOM, std::string("walk buffers: ") + vdf_last_error(q));
-    scratch_free(w);
-    return rc;
-  }
-  w.scratch_walks = walks;
-  return VDF_OK;
-}
-// circuits [first, first + count) let go of their walked traces (one copied from the host stays); park: an allocation left to nobody becomes the spare
-void release_range(const vdf_circuits* c, size_t first, size_t count, bool park) {
-  for (size_t k = first; k < first + count; ++k) {
-    Circuit& cc = written(c)->v[k];
-    if (!cc.block || cc.cp.empty()) continue;
-    cc.d_trace = nullptr;
-    if (park && cc.block.use_count() == 1) c->walk.spare = std::move(cc.block);
-    cc.block.reset();
-  }
-}
-// enqueue up to `rounds` more rounds of the pending walks, in launches of the bounded length
-int job_enqueue(const vdf_circuits* c, uint64_t rounds) {
-  const WalkState& w = c->walk;
-  WalkJob* j = w.job.get();
-  const uint64_t t = c->v[j->steps[0]].t;
-  while (rounds && j->done < j->every) {
-    const uint64_t now = std::min(std::min(rounds, j->every - j->done), walk_launch_rounds());
-    HIPCALL(w.side, vdf_minroot_inverse_walk(w.side, c->field, (vdf_state*)w.d_walk, j->walks, now, (vdf_fe*)j->block->d, (size_t)j->every,
-                                             (size_t)(j->every - j->done), j->per_step, (size_t)(t + 1)));
-    j->done += now;
-    rounds -= now;
-  }
-  return VDF_OK;
-}
-// finish the pending walks: the rest of their rounds, the comparison on the device, and the verdict per step
-int job_resolve(const vdf_circuits* c, int* bad, size_t bad_first, size_t bad_count) {
-  WalkState& w = c->walk;
-  WalkJob* j = w.job.get();
-  if (!j) return VDF_OK;
-  auto lose = [&](size_t k) { Circuit& cc = written(c)->v[k]; cc.d_trace = nullptr; cc.block.reset(); };   // left without a trace
-  int rc = job_enqueue(c, j->every);
-  if (rc == VDF_OK && !j->matched) {
-    rc = vdf_minroot_check_batch(w.side, c->field, (const vdf_state*)w.d_walk, (const vdf_state*)w.d_expect, j->walks, 0, w.h_ok);
-    if (rc != VDF_OK) fail(rc, std::string("vdf_minroot_check_batch: ") + vdf_last_error(w.side));
-    j->matched = true;
-  }
-  if (rc == VDF_OK && (rc = vdf_ctx_sync(w.side)) != VDF_OK) fail(rc, std::string("vdf_ctx_sync: ") + vdf_last_error(w.side));
-  if (rc != VDF_OK) {                                                   // a device failure: none of these traces can be trusted
-    vdf_ctx_sync(w.side);
-    for (size_t k : j->steps) lose(k);
-    w.job.reset();
-    return rc;
-  }
-  size_t first_bad = (size_t)-1;
-  for (size_t li = 0; li < j->steps.size(); ++li) {
-    bool ok = true;
-    const size_t per = j->lanes * j->per_step;                          // every lane's walks of this step
-    for (size_t m = 0; m < per; ++m) ok &= w.h_ok[li * per + m] == 1;
-    if (ok) continue;
-    const size_t k = j->steps[li];
-    lose(k);
-    if (first_bad == (size_t)-1) first_bad = k;
-    if (bad && k >= bad_first && k - bad_first < bad_count) bad[k - bad_first] = 1;
-  }
-  w.job.reset();                                                        // (its buffers stay: scratch_free)
-  if (first_bad != (size_t)-1)
-    return fail(VDF_ERR_BAD_ARG, "circuit " + std::to_string(first_bad) + ": an inverse walk did not land on the checkpoint before it");
-  return VDF_OK;
-}
 }  // namespace
+
+// ---- what TraceWalks asks of the circuits: walk (li L + l) per_lane + m is lane l's interval m of step steps[li] -------------------
+TraceSlot& CircuitWalks::slot(size_t k) { return written(c)->v[k]; }
+void CircuitWalks::shape(size_t first_step, WalkJob* j) {
+  const Circuit& c0 = c->v[first_step];
+  j->every = c0.every;
+  j->trace_bytes = c->lanes * (c0.t + 1) * 64;                          // a step's trace: its lanes' traces back to back
+  j->step_walks = c->lanes * (size_t)(c0.t / c0.every);
+  j->entry_bytes = 96;
+}
+void CircuitWalks::stage_walks(const WalkJob& j, const void** starts, const void** expects) {
+  const size_t L = c->lanes, per = j.step_walks / L;
+  from.resize(j.walks); to.resize(j.walks);
+  for (size_t li = 0; li < j.steps.size(); ++li) {
+    const Circuit& k = c->v[j.steps[li]];
+    for (size_t l = 0; l < L; ++l)
+      for (size_t m = 0; m < per; ++m) {
+        const size_t wk = (li * L + l) * per + m, at = l * (per + 1) + m;
+        from[wk] = k.cp[at + 1]; to[wk] = k.cp[at];
+      }
+  }
+  *starts = from.data(); *expects = to.data();
+}
+void CircuitWalks::unstage() { std::vector<St>().swap(from); std::vector<St>().swap(to); }
+int CircuitWalks::setup(vdf_ctx* q, const WalkJob& j, const WalkScratch& s) {
+  const size_t per = j.step_walks / c->lanes;
+  return vdf_minroot_trace_heads(q, (const vdf_state*)s.d_expect, j.steps.size() * c->lanes, per, (vdf_fe*)j.block->d, (size_t)(c->v[j.steps[0]].t + 1));
+}
+int CircuitWalks::launch(vdf_ctx* q, const WalkJob& j, const WalkScratch& s, uint64_t rounds, uint64_t top, int) {
+  HIPCALL(q, vdf_minroot_inverse_walk(q, c->field, (vdf_state*)s.d_walk, j.walks, rounds, (vdf_fe*)j.block->d, (size_t)j.every, (size_t)top,
+                                      j.step_walks / c->lanes, (size_t)(c->v[j.steps[0]].t + 1)));
+  return VDF_OK;
+}
+int CircuitWalks::finish(vdf_ctx* q, const WalkJob& j, const WalkScratch& s) {   // the comparison on the device
+  const int rc = vdf_minroot_check_batch(q, c->field, (const vdf_state*)s.d_walk, (const vdf_state*)s.d_expect, j.walks, 0, s.h_ok);
+  return rc == VDF_OK ? rc : fail(rc, std::string("vdf_minroot_check_batch: ") + vdf_last_error(q));
+}
+std::string CircuitWalks::missed(size_t k, size_t) { return "circuit " + std::to_string(k) + ": an inverse walk did not land on the checkpoint before it"; }
 
 namespace vdfnova {
 int circuits_need(const vdf_circuits* c, size_t k) {
-  if (c->walk.job_covers(k)) { int rc = job_resolve(c, nullptr, 0, 0); if (rc != VDF_OK) return rc; }
+  if (c->walk.covers(k)) { int rc = c->walk.resolve(nullptr, 0, 0); if (rc != VDF_OK) return rc; }
   const Circuit& cc = c->v[k];
   if (!cc.d_trace && cc.trace_xy.empty()) return fail(VDF_ERR_BAD_ARG, "trace of circuit " + std::to_string(k) + " not materialised");
   return VDF_OK;
 }
-// Called by prove_step(k), which needs circuits k and k + 1: the pending walks are wanted by prove_step(steps[0] - 1), so the
-// calls from here to there share the remaining rounds evenly.
-int circuits_pump(const vdf_circuits* c, size_t k) {
-  WalkJob* j = c->walk.job.get();
-  if (!j || j->done >= j->every) return VDF_OK;
-  const size_t wanted_at = j->steps[0] ? j->steps[0] - 1 : 0;
-  const uint64_t calls = wanted_at > k ? wanted_at - k : 1, left = j->every - j->done;
-  return job_enqueue(c, (left + calls - 1) / calls);
-}
-int circuits_settle(const vdf_circuits* c) { return job_resolve(c, nullptr, 0, 0); }
-void circuits_park(const vdf_circuits* c, size_t k) { release_range(c, k, 1, true); }
-void circuits_drop_spare(const vdf_circuits* c) { c->walk.spare.reset(); }
+// prove_step(k) needs circuits k and k + 1: the pending walks are wanted by the prove_step one before their first step
+int circuits_pump(const vdf_circuits* c, size_t k) { return c->walk.pump(k, 1); }
 int circuits_materialize(vdf_ctx* ctx, const vdf_circuits* c, size_t first, size_t count, int wait, int* bad) {
   return vdf_nova_circuits_materialize(ctx, written(c), first, count, wait, bad);
 }
@@ -326,102 +275,33 @@ int vdf_nova_circuit_lane_states(const vdf_circuits* c, size_t k, size_t lane, v
 int vdf_nova_circuits_materialize(vdf_ctx* ctx, vdf_circuits* c, size_t first, size_t count, int wait, int* bad) {
   return nova_guard([&]() -> int {
     if (!ctx || !c) return fail(VDF_ERR_BAD_ARG, "null argument");
-    WalkState& w = c->walk;
     if (!c->checkpoints) return fail(VDF_ERR_BAD_ARG, "these circuits carry their traces: vdf_nova_circuits_upload");
     if (first > c->v.size() || count > c->v.size() - first) return fail(VDF_ERR_BAD_LENGTH, "circuit range out of bounds");
     if (bad) for (size_t k = 0; k < count; ++k) bad[k] = 0;
-    const int pending = job_resolve(c, bad, first, count);             // one job at a time; its verdict is this call's too
+    const int pending = c->walk.resolve(bad, first, count);            // one job at a time; its verdict is this call's too
     if (pending != VDF_OK && pending != VDF_ERR_BAD_ARG) return pending;
-    if (c->ctx && vdf_ctx_device(c->ctx) != vdf_ctx_device(ctx)) return fail(VDF_ERR_BAD_ARG, "the circuits' traces live on another device");
-    c->ctx = ctx;
-    std::unique_ptr<WalkJob> j(new WalkJob());
     // (a forward chain may mix steps pushed as traces with steps pushed as checkpoints: only the latter are walked)
-    for (size_t k = first; k < first + count; ++k) if (needs_walk(c->v[k])) j->steps.push_back(k);
-    if (j->steps.empty()) return pending;
-    if (!w.side) {
-      const int dev = vdf_ctx_device(ctx);
-      if (vdf_ctx_create_pooled(&dev, 1, VDF_QUEUE_SIDE, &w.side) != VDF_OK)
-        return fail(VDF_ERR_DEVICE, std::string("walk context: ") + vdf_last_error(nullptr));
-      HIPCALL(w.side, vdf_ctx_set_async(w.side, 1));
-    }
-    vdf_ctx* q = w.side;
-    const Circuit& c0 = c->v[j->steps[0]];
-    const size_t L = c->lanes;                                          // a step's trace: its lanes' traces back to back
-    const uint64_t t = c0.t, trace_bytes = L * (t + 1) * 64;
-    j->every = c0.every;
-    j->per_step = (size_t)(t / c0.every);
-    j->lanes = L;
-    j->walks = j->steps.size() * L * j->per_step;
-    if (j->steps.size() > (~(uint64_t)0 >> 1) / trace_bytes) return fail(VDF_ERR_OOM, "the traces do not fit");
-    // the windowed prove_recursively's spare allocation, when it is exactly this size; anything else is asked of the device
-    if (w.spare && w.spare.use_count() == 1 && w.spare->ctx == ctx && w.spare->bytes == j->steps.size() * trace_bytes) j->block = std::move(w.spare);
-    w.spare.reset();
-    if (!j->block) {
-      j->block = std::shared_ptr<TraceBlock>(new TraceBlock{ctx, j->steps.size() * trace_bytes});
-      size_t free_bytes = 0;                       // asked first: an allocation beyond the free memory may be granted and fail later
-      HIPCALL(ctx, vdf_dev_mem_info(ctx, &free_bytes, nullptr));
-      if (j->block->bytes + j->walks * (2 * 96) > free_bytes)
-        return fail(VDF_ERR_OOM, "the traces of " + std::to_string(j->steps.size()) + " circuits (" + std::to_string(j->block->bytes) +
-                                     " bytes) do not fit the device's free memory (" + std::to_string(free_bytes) + " bytes)");
-      if (vdf_dev_alloc(ctx, j->block->bytes, &j->block->d) != VDF_OK) {
-        j->block->d = nullptr;
-        return fail(VDF_ERR_OOM, "the traces of " + std::to_string(j->steps.size()) + " circuits do not fit: " + vdf_last_error(ctx));
-      }
-    }
-    { int rc = scratch_ensure(w, j->walks); if (rc != VDF_OK) return rc; }
-    w.job = std::move(j);
-    WalkJob* job = w.job.get();
-    {
-      std::vector<St> from(job->walks), to(job->walks);
-      for (size_t li = 0; li < job->steps.size(); ++li) {
-        const Circuit& k = c->v[job->steps[li]];
-        for (size_t l = 0; l < L; ++l)                                  // walk (li L + l) per_step + m: lane l's interval m
-          for (size_t m = 0; m < job->per_step; ++m) {
-            const size_t wk = (li * L + l) * job->per_step + m, at = l * (job->per_step + 1) + m;
-            from[wk] = k.cp[at + 1]; to[wk] = k.cp[at];
-          }
-      }
-      memset(w.h_ok, 0, job->walks * sizeof(int));
-      int rc = vdf_dev_memcpy(q, w.d_walk, from.data(), job->walks * 96);
-      if (rc == VDF_OK) rc = vdf_dev_memcpy(q, w.d_expect, to.data(), job->walks * 96);
-      if (rc == VDF_OK) rc = vdf_minroot_trace_heads(q, (const vdf_state*)w.d_expect, job->steps.size() * L, job->per_step, (vdf_fe*)job->block->d, (size_t)(t + 1));
-      if (rc != VDF_OK) { rc = fail(rc, std::string("walk set-up: ") + vdf_last_error(q)); w.job.reset(); return rc; }
-    }
-    for (size_t li = 0; li < job->steps.size(); ++li) {                 // resident from now on; a walk that misses takes it away again
-      Circuit& k = c->v[job->steps[li]];
-      k.d_trace = (char*)job->block->d + li * trace_bytes;
-      k.block = job->block;
-    }
-    if (!wait) { int rc = job_enqueue(c, walk_launch_rounds()); return rc != VDF_OK ? rc : pending; }
-    const int rc = job_resolve(c, bad, first, count);
-    return rc != VDF_OK ? rc : pending;
+    std::vector<size_t> steps;
+    for (size_t k = first; k < first + count; ++k) if (needs_walk(c->v[k])) steps.push_back(k);
+    return c->walk.begin(ctx, std::move(steps), wait, walk_launch_rounds(), pending, bad, first, count);
   });
 }
 int vdf_nova_circuits_release(vdf_circuits* c, size_t first, size_t count) {
   return nova_guard([&]() -> int {
     if (!c) return fail(VDF_ERR_BAD_ARG, "null argument");
     if (first > c->v.size() || count > c->v.size() - first) return fail(VDF_ERR_BAD_LENGTH, "circuit range out of bounds");
-    const int pending = c->walk.job_covers(first, count) ? job_resolve(c, nullptr, 0, 0) : VDF_OK;
-    release_range(c, first, count, false);
-    // a forward chain is a stream: a step that has been proved lets go of its pushed host trace too
-    if (c->forward) for (size_t k = first; k < first + count; ++k) std::vector<Fe>().swap(c->v[k].trace_xy);
+    const int pending = c->walk.covers(first, count) ? c->walk.resolve(nullptr, 0, 0) : VDF_OK;
+    for (size_t k = first; k < first + count; ++k) {
+      if (!c->v[k].cp.empty()) c->walk.release(k, 1, false);            // a walked trace (one copied from the host stays)
+      // a forward chain is a stream: a step that has been proved lets go of its pushed host trace too
+      if (c->forward) std::vector<Fe>().swap(c->v[k].trace_xy);
+    }
     return pending;
   });
 }
 int vdf_nova_circuits_memory(const vdf_circuits* c, size_t* resident_steps, uint64_t* device_bytes) {
   if (!c) return fail(VDF_ERR_BAD_ARG, "null argument");
-  size_t n = 0;
-  uint64_t bytes = 0;
-  std::vector<const TraceBlock*> seen;
-  for (const Circuit& k : c->v) {
-    if (!k.d_trace) continue;
-    ++n;
-    if (std::find(seen.begin(), seen.end(), k.block.get()) != seen.end()) continue;   // a block counts once
-    seen.push_back(k.block.get());
-    bytes += k.block->bytes;
-  }
-  if (resident_steps) *resident_steps = n;
-  if (device_bytes) *device_bytes = bytes;
+  c->walk.memory(c->v.size(), resident_steps, device_bytes);
   return VDF_OK;
 }
 int vdf_nova_circuit_trace(const vdf_circuits* c, size_t k, const void** d_trace) {
@@ -429,7 +309,7 @@ int vdf_nova_circuit_trace(const vdf_circuits* c, size_t k, const void** d_trace
     if (!c || !d_trace) return fail(VDF_ERR_BAD_ARG, "null argument");
     if (k >= c->v.size()) return fail(VDF_ERR_BAD_LENGTH, "circuit index out of range");
     *d_trace = nullptr;
-    if (c->walk.job_covers(k)) { int rc = job_resolve(c, nullptr, 0, 0); if (rc != VDF_OK && rc != VDF_ERR_BAD_ARG) return rc; }
+    if (c->walk.covers(k)) { int rc = c->walk.resolve(nullptr, 0, 0); if (rc != VDF_OK && rc != VDF_ERR_BAD_ARG) return rc; }
     *d_trace = c->v[k].d_trace;
     return VDF_OK;
   });
@@ -438,7 +318,7 @@ int vdf_nova_circuits_upload(vdf_ctx* ctx, vdf_circuits* c) {
   if (ctx && c && c->checkpoints) return vdf_nova_circuits_materialize(ctx, c, 0, c->v.size(), 1, nullptr);
   return nova_guard([&]() -> int {
     if (!ctx || !c) return fail(VDF_ERR_BAD_ARG, "null argument");
-    c->ctx = ctx;
+    c->walk.home = ctx;
     for (auto& k : c->v) {                          // a block per circuit
       if (k.d_trace) continue;
       std::shared_ptr<TraceBlock> b(new TraceBlock{ctx, k.trace_xy.size() * 32});
@@ -465,12 +345,7 @@ int vdf_nova_circuits_host_bytes(const vdf_circuits* c, uint64_t* bytes) {
 }
 void vdf_nova_circuits_free(vdf_circuits* c) {
   if (!c) return;
-  WalkState& w = c->walk;
-  if (w.job) { vdf_ctx_sync(w.side); w.job.reset(); }
-  w.spare.reset();
-  if (w.side) scratch_free(w);
-  c->v.clear();                                   // every trace's allocation goes with the last circuit that points into it
-  if (w.side) vdf_ctx_destroy(w.side);
+  c->walk.teardown(c->v.size());
   delete c;
 }
 }  // extern "C"

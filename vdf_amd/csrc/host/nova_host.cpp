@@ -2175,6 +2175,52 @@ static int prove_step_impl(vdf_pp* pp, vdf_proof** proof, const vdf_circuits* ci
   return VDF_OK;
 }
 
+// THE windowed proving loop, of checkpoint circuits and of a custom chain: steps [0, n) proved in order while their traces are built
+// window by window (W steps) on the owner's side queue, window w + 1 under the proving of window w.  Only what this call built is
+// released (window w, once the last step that reads it has returned; its allocation is parked for window w + 2), so the caller's
+// handle is left as it was found.  Not windowed: every trace is there, nothing is built or dropped.
+struct WindowedRun {
+  size_t n, W;
+  bool windowed;
+  TraceWalks& walks;
+  std::function<bool(size_t)> absent;                                  // step k has no trace yet
+  std::function<int(size_t, size_t, int)> materialize;                 // (first, count, wait)
+  std::function<int(vdf_proof**, size_t)> prove;                       // step k
+  // after a failure, before anything is dropped: nothing of this call's stays in flight.  Returns the message the call fails with
+  // (empty: whatever is current by then)
+  std::function<std::string(vdf_proof*)> failed;
+};
+static int prove_windowed(const WindowedRun& r, vdf_proof** out) {
+  const size_t n = r.n, W = r.W;
+  std::vector<char> mine(r.windowed ? n : 0, 0);
+  auto build = [&](size_t w, int wait) -> int {                        // window w = steps [w W, (w + 1) W)
+    const size_t b = w * W;
+    if (!r.windowed || b >= n) return VDF_OK;
+    const size_t cnt = std::min(W, n - b);
+    for (size_t k = b; k < b + cnt; ++k) mine[k] = r.absent(k);
+    return r.materialize(b, cnt, wait);
+  };
+  auto drop = [&](size_t w) { for (size_t k = w * W; k < std::min(n, (w + 1) * W); ++k) if (mine[k]) { r.walks.release(k, 1, true); mine[k] = 0; } };
+  vdf_proof* p = nullptr;
+  int rc = build(0, 1);
+  if (rc == VDF_OK) rc = build(1, 0);
+  for (size_t k = 0; rc == VDF_OK && k < n; ++k) {                     // :318-355
+    rc = r.prove(&p, k);
+    if (rc == VDF_OK && r.windowed && (k + 1) % W == 0) {               // the last step that reads window k / W has returned
+      drop(k / W);
+      rc = build(k / W + 2, 0);
+    }
+  }
+  if (rc == VDF_OK) rc = finalize_l2(p);
+  std::string why;
+  if (rc != VDF_OK) why = r.failed(p);
+  if (r.windowed) for (size_t w = 0; w * W < n; ++w) drop(w);
+  r.walks.drop_spare();
+  if (rc != VDF_OK) { vdf_nova_proof_free(p); *out = nullptr; return why.empty() ? rc : fail(rc, why); }
+  *out = p;
+  return VDF_OK;
+}
+
 int vdf_nova_prove_recursively_windowed(vdf_pp* pp, const vdf_circuits* circuits, uint64_t num_iters_per_step, const vdf_fe z0[3],
                                         size_t window_steps, vdf_proof** out) {
   return nova_guard([&]() -> int {
@@ -2182,42 +2228,19 @@ int vdf_nova_prove_recursively_windowed(vdf_pp* pp, const vdf_circuits* circuits
     if (num_iters_per_step != pp->t) return fail(VDF_ERR_BAD_LENGTH, "num_iters_per_step differs from the public parameters");
     if (circuits->v.empty()) return fail(VDF_ERR_BAD_LENGTH, "no circuits (recursive_snark.unwrap(), src/nova/proof.rs:357)");
     const size_t n = circuits->v.size();
-    // Checkpoint circuits whose traces are not all there: built window by window on the circuits' side queue, window w + 1 under
-    // the proving of window w, and only what this call built is released (window w - 1, once the last step that reads it has returned).
-    // The handle is the caller's and is left as it was found; the reference takes the circuits by value (src/nova/proof.rs:302-307).
+    // windowed: checkpoint circuits whose traces are not all there (the reference takes the circuits by value, src/nova/proof.rs:302-307)
     bool windowed = false;
     if (circuits->checkpoints) {
-      { int rc = circuits_settle(circuits); if (rc != VDF_OK) { *out = nullptr; return rc; } }
+      { int rc = circuits->walk.resolve(nullptr, 0, 0); if (rc != VDF_OK) { *out = nullptr; return rc; } }
       for (const Circuit& c : circuits->v) windowed |= needs_walk(c);
     }
     const size_t W = !windowed ? n : window_steps ? std::max<size_t>(window_steps, 2)
                                                   : std::max<size_t>(2, (size_t)(((uint64_t)1 << 30) / (pp->lanes * (pp->t + 1) * 64)));
-    std::vector<char> mine(windowed ? n : 0, 0);
-    auto build = [&](size_t w, int wait) -> int {                        // window w = circuits [w W, (w + 1) W)
-      const size_t b = w * W;
-      if (!windowed || b >= n) return VDF_OK;
-      const size_t cnt = std::min(W, n - b);
-      for (size_t k = b; k < b + cnt; ++k) mine[k] = needs_walk(circuits->v[k]);
-      return circuits_materialize(pp->ctx, circuits, b, cnt, wait, nullptr);
-    };
-    auto drop = [&](size_t w) { for (size_t k = w * W; k < std::min(n, (w + 1) * W); ++k) if (mine[k]) { circuits_park(circuits, k); mine[k] = 0; } };
-    vdf_proof* p = nullptr;
-    int rc = build(0, 1);
-    if (rc == VDF_OK) rc = build(1, 0);
-    for (size_t k = 0; rc == VDF_OK && k < n; ++k) {                   // :318-355
-      rc = vdf_nova_prove_step(pp, &p, circuits, k, z0);
-      if (rc == VDF_OK && windowed && (k + 1) % W == 0) {               // the last step that reads window k / W has returned
-        drop(k / W);
-        rc = build(k / W + 2, 0);
-      }
-    }
-    if (rc == VDF_OK) rc = finalize_l2(p);
-    if (rc != VDF_OK) circuits_settle(circuits);                         // nothing of this call's stays in flight
-    if (windowed) for (size_t w = 0; w * W < n; ++w) drop(w);
-    circuits_drop_spare(circuits);
-    if (rc != VDF_OK) { vdf_nova_proof_free(p); *out = nullptr; return rc; }
-    *out = p;
-    return VDF_OK;
+    return prove_windowed({n, W, windowed, circuits->walk,
+                           [&](size_t k) { return needs_walk(circuits->v[k]); },
+                           [&](size_t b, size_t cnt, int wait) { return circuits_materialize(pp->ctx, circuits, b, cnt, wait, nullptr); },
+                           [&](vdf_proof** p, size_t k) { return vdf_nova_prove_step(pp, p, circuits, k, z0); },
+                           [&](vdf_proof*) { circuits->walk.resolve(nullptr, 0, 0); return std::string(); }}, out);
   });
 }
 int vdf_nova_prove_recursively(vdf_pp* pp, const vdf_circuits* circuits, uint64_t num_iters_per_step, const vdf_fe z0[3],
@@ -2305,55 +2328,34 @@ int vdf_nova_prove_recursively_custom(vdf_pp* pp, const vdf_step_circuit* primar
     if (flags & ~VDF_CUSTOM_CHECK_STEPS) return fail(VDF_ERR_BAD_ARG, "unknown flag");
     { int rc = chain_fits(pp, chain); if (rc != VDF_OK) return rc; }
     const ChainInfo ci = chain_info(chain);
-    const size_t n = ci.steps;
-    // The loop of vdf_nova_prove_recursively_windowed: window w + 1 is walked on the chain's side queue under the proving of window
-    // w, and only what this call built is released.  The handle is the caller's and is left as it was found.
-    { int rc = chain_settle(chain); if (rc != VDF_OK) return rc; }
+    TraceWalks& walks = chain_walks(chain);
+    { int rc = walks.resolve(nullptr, 0, 0); if (rc != VDF_OK) return rc; }
     const size_t W = window_steps ? std::max<size_t>(window_steps, 2)
                                   : std::max<size_t>(2, (size_t)(((uint64_t)1 << 30) / (ci.lanes * (ci.t + 1) * ci.n_adv * 32)));
-    std::vector<char> mine(n, 0);
-    auto build = [&](size_t w, int wait) -> int {                        // window w = steps [w W, (w + 1) W)
-      if (w >= (n + W - 1) / W) return VDF_OK;
-      const size_t b = w * W, cnt = std::min(W, n - b);
-      for (size_t k = b; k < b + cnt; ++k) mine[k] = !chain_resident(chain, k);
-      return vdf_nova_custom_chain_materialize(pp->ctx, chain, b, cnt, wait, 0, nullptr);
+    auto prove = [&](vdf_proof** p, size_t k) -> int {
+      int rc = vdf_nova_prove_step_custom_chain(pp, p, primary, chain, k, z0);
+      if (rc != VDF_OK || !(flags & VDF_CUSTOM_CHECK_STEPS)) return rc;
+      uint64_t count = 0, row = 0;
+      rc = vdf_nova_proof_last_unsat(*p, &count, &row);
+      if (rc != VDF_OK || !count) return rc;
+      std::string msg = "step " + std::to_string(k) + ": " + std::to_string(count) + " unsatisfied rows, first row " + std::to_string(row);
+      uint64_t rb = 0, nc = 0, rt = 0;
+      const uint64_t rl = pp->round.lanes;
+      if (vdf_nova_pp_repeat_rows(pp, &rb, &nc, &rt) && nc && row >= rb && row - rb < nc * rt * rl)
+        msg += " (" + (rl > 1 ? "lane " + std::to_string((row - rb) / (nc * rt)) + ", " : std::string()) + "repetition " +
+               std::to_string((row - rb) / nc % rt) + ", constraint " + std::to_string((row - rb) % nc) + " of the repeat)";
+      return fail(VDF_ERR_BAD_ARG, msg);
     };
-    auto drop = [&](size_t w) { for (size_t k = w * W; k < std::min(n, (w + 1) * W); ++k) if (mine[k]) { chain_park(chain, k); mine[k] = 0; } };
-    vdf_proof* p = nullptr;
-    int rc = build(0, 1);
-    if (rc == VDF_OK) rc = build(1, 0);
-    for (size_t k = 0; rc == VDF_OK && k < n; ++k) {
-      rc = vdf_nova_prove_step_custom_chain(pp, &p, primary, chain, k, z0);
-      if (rc == VDF_OK && (flags & VDF_CUSTOM_CHECK_STEPS)) {
-        uint64_t count = 0, row = 0;
-        rc = vdf_nova_proof_last_unsat(p, &count, &row);
-        if (rc == VDF_OK && count) {
-          std::string msg = "step " + std::to_string(k) + ": " + std::to_string(count) + " unsatisfied rows, first row " + std::to_string(row);
-          uint64_t rb = 0, nc = 0, rt = 0;
-          const uint64_t rl = pp->round.lanes;
-          if (vdf_nova_pp_repeat_rows(pp, &rb, &nc, &rt) && nc && row >= rb && row - rb < nc * rt * rl)
-            msg += " (" + (rl > 1 ? "lane " + std::to_string((row - rb) / (nc * rt)) + ", " : std::string()) + "repetition " +
-                   std::to_string((row - rb) / nc % rt) + ", constraint " + std::to_string((row - rb) % nc) + " of the repeat)";
-          rc = fail(VDF_ERR_BAD_ARG, msg);
-        }
-      }
-      if (rc == VDF_OK && (k + 1) % W == 0) {                           // the last step that reads window k / W has returned
-        drop(k / W);
-        rc = build(k / W + 2, 0);
-      }
-    }
-    if (rc == VDF_OK) rc = finalize_l2(p);
-    std::string why;
-    if (rc != VDF_OK) {                                                         // nothing of this call's stays in flight: the walks, and a
-      why = vdf_nova_last_error();                                              // lookahead over a trace that is released below
-      chain_settle(chain);
-      if (p) { for (vdf_ctx* q : p->ctx2) if (q) vdf_ctx_sync(q); if (p->ctx3) vdf_ctx_sync(p->ctx3); vdf_ctx_sync(pp->ctx); }
-    }
-    for (size_t w = 0; w * W < n; ++w) drop(w);
-    chain_drop_spare(chain);
-    if (rc != VDF_OK) { vdf_nova_proof_free(p); return fail(rc, why); }
-    *out = p;
-    return VDF_OK;
+    return prove_windowed({ci.steps, W, true, walks,
+                           [&](size_t k) { return !walks.resident(k); },
+                           [&](size_t b, size_t cnt, int wait) { return vdf_nova_custom_chain_materialize(pp->ctx, chain, b, cnt, wait, 0, nullptr); },
+                           prove,
+                           [&](vdf_proof* p) {                          // the walks, and a lookahead over a trace that is released next
+                             const std::string why = vdf_nova_last_error();
+                             walks.resolve(nullptr, 0, 0);
+                             if (p) { for (vdf_ctx* q : p->ctx2) if (q) vdf_ctx_sync(q); if (p->ctx3) vdf_ctx_sync(p->ctx3); vdf_ctx_sync(pp->ctx); }
+                             return why;
+                           }}, out);
   });
 }
 

@@ -1,5 +1,5 @@
-// Shared declarations of the translation units of libvdf_nova.so (minroot_host.cpp, r1cs.cpp, nova_host.cpp, circuits_host.cpp, custom_chain_host.cpp,
-// compress_host.cpp, wire_host.cpp): error plumbing, the two sides of the curve cycle, the handle structs.
+// Shared declarations of the translation units of libvdf_nova.so (minroot_host.cpp, r1cs.cpp, nova_host.cpp, trace_walks.cpp, circuits_host.cpp,
+// custom_chain_host.cpp, compress_host.cpp, wire_host.cpp): error plumbing, the two sides of the curve cycle, the handle structs.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -19,6 +19,7 @@
 #include "host_math.hpp"
 #include "r1cs.hpp"
 #include "rounds.hpp"
+#include "trace_walks.hpp"
 
 namespace vdfnova {
 using namespace vdfhost;
@@ -150,21 +151,12 @@ struct vdf_pp {
   unsigned digit_tables_skipped = 0;       // bit s: side s asked for a digit table and went without (no room, refused window)
 };
 
-// the one owner of a device trace: the traces one vdf_nova_circuits_materialize built, or the one vdf_nova_circuits_upload
-// copied; freed when the last circuit that points into it lets go
-struct TraceBlock {
-  vdf_ctx* ctx;
-  uint64_t bytes;
-  void* d = nullptr;
-  ~TraceBlock() { if (d) vdf_dev_free(ctx, d); }
-};
-struct Circuit {            // InverseMinRootCircuit<G1>, src/nova/proof.rs:57-66, + the forward trace
+struct Circuit : TraceSlot { // InverseMinRootCircuit<G1>, src/nova/proof.rs:57-66, + the forward trace; its TraceSlot: that trace in HBM
+                            // (vdf_nova_circuits_upload, vdf_nova_circuits_materialize)
   uint64_t inverse_exponent = 5;
   vdfnova::St result, input;
   uint64_t t = 0;
   std::vector<Fe> trace_xy;  // (x, y) of states 0..t: trace[0] = input, trace[t] = result
-  void* d_trace = nullptr;   // the same trace in HBM (vdf_nova_circuits_upload, vdf_nova_circuits_materialize): null, or inside `block`
-  std::shared_ptr<TraceBlock> block;
   // a circuit made from checkpoints (vdf_nova_circuits_from_checkpoints) holds no host trace: the step's states every `every`
   // rounds in forward order, cp[0] = input .. cp[t / every] = result; its d_trace is built by walks, and is what release lets go of
   uint64_t every = 0;
@@ -175,38 +167,25 @@ struct Circuit {            // InverseMinRootCircuit<G1>, src/nova/proof.rs:57-6
   // and cp is L runs of t / every + 1 states
   std::vector<vdfnova::St> lane_result, lane_input;
 };
-// Traces being rebuilt by inverse walks on the circuits' side queue (vdf_nova_circuits_materialize): one walk per checkpoint
-// interval of every step in `steps`, all in one launch per slice of rounds; `done` rounds of `every` are enqueued so far.
-struct WalkJob {
-  std::vector<size_t> steps;               // circuit indices, ascending
-  std::shared_ptr<TraceBlock> block;       // steps.size() x lanes traces of t + 1 entries
-  size_t walks = 0, per_step = 0;          // per_step: walks per LANE of a step (a step of a lanes chain has lanes x per_step)
-  size_t lanes = 1;
-  uint64_t every = 0, done = 0;
-  bool matched = false;                    // the comparison has been enqueued
-};
-// The walks of one vdf_circuits: on a side queue of the device (made by the first materialize), a job enqueued with wait = 0 being
-// finished by the next call that needs its result.  Their buffers are kept from one job to the next, and the windowed prove_recursively
-// keeps the allocation of the window it releases for the window after next (`spare`): a device free is a synchronisation of the
-// whole device, and two per window showed in the prover's rate.  The C ABI hands prove_step and prove_recursively the circuits const
-// (the reference takes them by value), and both finish or start walks under them: this is the one member a const handle may
-// change, and what the walks decide about a trace is written into v[k] through the one cast there is (circuits_host.cpp, `written`).
-struct WalkState {
-  vdf_ctx* side = nullptr;
-  std::unique_ptr<WalkJob> job;
-  void* d_walk = nullptr, *d_expect = nullptr;   // where each walk stands, and the checkpoint it must land on
-  int* h_ok = nullptr;                     // pinned: 1 per walk that landed on it
-  size_t scratch_walks = 0;                // the walks these three have room for
-  std::shared_ptr<TraceBlock> spare;
-  bool job_covers(size_t first, size_t count = 1) const {   // the pending job builds a trace of circuits [first, first + count)
-    if (!job) return false;
-    const auto it = std::lower_bound(job->steps.begin(), job->steps.end(), first);
-    return it != job->steps.end() && *it - first < count;
-  }
+// What the walks of a vdf_circuits are to TraceWalks (trace_walks.hpp): inverse MinRoot walks over vdf_state entries (circuits_host.cpp).
+// The C ABI hands prove_step and prove_recursively the circuits const (the reference takes them by value), and both finish or start
+// walks under them: `walk` is the one member a const handle may change, and what the walks decide about a trace is written into
+// v[k] through the one cast there is (CircuitWalks::slot, by circuits_host.cpp's `written`).
+struct CircuitWalks final : vdfnova::WalkOwner {
+  const vdf_circuits* c;
+  std::vector<vdfnova::St> from, to;       // where a pending job's walks start and must land, in the walks' order
+  explicit CircuitWalks(const vdf_circuits* c) : WalkOwner("circuits'", "circuits"), c(c) {}
+  TraceSlot& slot(size_t k) override;
+  void shape(size_t first_step, vdfnova::WalkJob* j) override;
+  void stage_walks(const vdfnova::WalkJob& j, const void** starts, const void** expects) override;
+  void unstage() override;
+  int setup(vdf_ctx* q, const vdfnova::WalkJob& j, const vdfnova::WalkScratch& s) override;
+  int launch(vdf_ctx* q, const vdfnova::WalkJob& j, const vdfnova::WalkScratch& s, uint64_t rounds, uint64_t top, int last) override;
+  int finish(vdf_ctx* q, const vdfnova::WalkJob& j, const vdfnova::WalkScratch& s) override;
+  std::string missed(size_t k, size_t walk) override;
 };
 struct vdf_circuits {
   std::vector<Circuit> v;
-  vdf_ctx* ctx = nullptr;
   int field = VDF_FIELD_FQ;                // the chain's field: its evaluator, its counters, its push checks and its walks run over it
   bool checkpoints = false;                // made by vdf_nova_circuits_from_checkpoints (or grown by vdf_nova_circuits_push_checkpoints)
   // a forward chain (vdf_nova_circuits_forward_begin, vdf_nova_circuits_lanes_begin): circuits in the order of evaluation, appended
@@ -216,7 +195,8 @@ struct vdf_circuits {
   size_t lanes = 1;                        // evaluations advanced per step (1: a single chain)
   std::vector<vdfnova::St> lane_end;       // a forward chain: where every lane stands
   vdfnova::St end;                         // ... lane 0's
-  mutable WalkState walk;
+  CircuitWalks walked{this};
+  mutable vdfnova::TraceWalks walk{&walked};   // (walk.home: where the traces live)
 };
 
 // NovaVDFProof::Recursive = nova-snark RecursiveSNARK: running instance + witness on both sides, the last secondary
@@ -314,29 +294,21 @@ inline bool needs_walk(const Circuit& c) { return !c.d_trace && !c.cp.empty(); }
 // enqueue the share of the pending walks that keeps them ahead of a prover about to prove circuit k
 int circuits_need(const vdf_circuits* c, size_t k);
 int circuits_pump(const vdf_circuits* c, size_t k);
-// for the windowed prover, handed the circuits const: vdf_nova_circuits_materialize; the pending walks finished whatever they
-// cover; circuit k's walked trace let go of, its allocation kept as the spare if nobody else points into it; the spare freed
+// vdf_nova_circuits_materialize for the windowed prover, which is handed the circuits const
 int circuits_materialize(vdf_ctx* ctx, const vdf_circuits* c, size_t first, size_t count, int wait, int* bad);
-int circuits_settle(const vdf_circuits* c);
-void circuits_park(const vdf_circuits* c, size_t k);
-void circuits_drop_spare(const vdf_circuits* c);
 
 // ---- a custom circuit's chain as the drivers of nova_host.cpp reach it (custom_chain_host.cpp) ------------------------------
 // what the prover must know of a chain before it hands a step's trace to a circuit
 struct ChainInfo { int field; uint64_t t; size_t n_adv, steps; vdf_ctx* ctx; size_t lanes; };
 ChainInfo chain_info(const vdf_custom_chain* c);
+TraceWalks& chain_walks(vdf_custom_chain* c);
 // finish the pending walks if they cover step k and hand out its device trace (refused when there is none); enqueue the share
-// of the pending walks that keeps them ahead of a prover about to prove step k; finish whatever is pending
+// of the pending walks that keeps them ahead of a prover about to prove step k
 int chain_need(vdf_custom_chain* c, size_t k, const vdf_fe** d_trace);
 int chain_pump(vdf_custom_chain* c, size_t k);
-int chain_settle(vdf_custom_chain* c);
-bool chain_resident(const vdf_custom_chain* c, size_t k);
 // step k's device trace when it is RESOLVED: resident, and no pending walks cover it (they are finished -- the walk queue has been
 // synchronised by the host -- and every one of them landed on its checkpoint); null otherwise.  Never waits.
 const vdf_fe* chain_ready(const vdf_custom_chain* c, size_t k);
-// step k's trace let go of, its allocation kept as the spare if nobody else points into it; the spare freed
-void chain_park(vdf_custom_chain* c, size_t k);
-void chain_drop_spare(vdf_custom_chain* c);
 
 // ---- wire formats (wire_host.cpp; layout in include/vdf_nova.h) --------------------------------------------
 constexpr char WIRE_MAGIC_SNARK[9] = "VDFSNK03";      // compressed proof
