@@ -1623,15 +1623,31 @@ int vdf_round_tape_eval_batch(vdf_ctx* ctx, int field, const vdf_round_tape* tap
 
 int vdf_ptr_is_device(const void* p) { return ptr_is_device(p) ? 1 : 0; }
 
-static Status nifs_cross_impl(vdf_ctx* ctx, const vdf_shape* shape, size_t row_begin, size_t row_count, int part, const vdf_fe* z2,
-                              const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2,
-                              vdf_fe* Cz2, vdf_fe* T) {
+// The operand block of a cross-term entry point, checked the way all of them always did: nothing NULL, u1 (and whatever else the
+// call reads on the host: also_host) in host memory, the eight vectors in device memory.  null_is_misplaced: vdf_nifs_cross_term
+// and _rows never had a NULL check of their own -- a NULL u1 is reported as not in host memory, a NULL vector as not in device
+// memory -- and keep those answers.
+static bool cross_operand_missing(const vdf::CrossOperands& o) {
+  return !o.z2 || !o.abc1[0] || !o.abc1[1] || !o.abc1[2] || !o.u1 || !o.abc2[0] || !o.abc2[1] || !o.abc2[2] || !o.T;
+}
+static Status check_cross_operands(const vdf::CrossOperands& o, bool null_is_misplaced = false,
+                                   std::initializer_list<const void*> also_host = {},
+                                   const char* host_text = "scalar operands of fused calls live in host memory") {
+  if (!null_is_misplaced && cross_operand_missing(o)) return Status{VDF_ERR_BAD_ARG, "null argument"};
+  bool on_device = !o.u1 || ptr_is_device(o.u1);
+  for (const void* h : also_host) on_device = on_device || ptr_is_device(h);
+  if (on_device) return Status{VDF_ERR_BAD_ARG, host_text};
+  for (const void* v : {o.z2, o.abc1[0], o.abc1[1], o.abc1[2], (const void*)o.abc2[0], (const void*)o.abc2[1], (const void*)o.abc2[2],
+                        (const void*)o.T})
+    if (!ptr_is_device(v)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
+  return Status{};
+}
+
+static Status nifs_cross_impl(vdf_ctx* ctx, const vdf_shape* shape, size_t row_begin, size_t row_count, int part,
+                              const vdf::CrossOperands& o) {
   // the shape is read-only device data: any context of its device may run over it (the early rows run on a second one)
   if (!shape || !shape->ctx || shape->ctx->device != ctx->device) return Status{VDF_ERR_BAD_ARG, "bad shape handle"};
-  if (!u1 || ptr_is_device(u1)) return Status{VDF_ERR_BAD_ARG, "scalar operands of fused calls live in host memory"};
-  const void* vec[8] = {z2, Az1, Bz1, Cz1, Az2, Bz2, Cz2, T};
-  for (const void* v : vec)
-    if (!ptr_is_device(v)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
+  VDF_TRY(check_cross_operands(o, true));
   if (part != VDF_ROWS_ALL && part != VDF_ROWS_INSIDE && part != VDF_ROWS_OUTSIDE) return Status{VDF_ERR_BAD_ARG, "unknown row selection"};
   if (part != VDF_ROWS_ALL) {
     if (row_begin > shape->num_cons || row_count > shape->num_cons - row_begin) return Status{VDF_ERR_BAD_LENGTH, "row range outside the shape"};
@@ -1647,11 +1663,9 @@ static Status nifs_cross_impl(vdf_ctx* ctx, const vdf_shape* shape, size_t row_b
   // (an augmented circuit, ~10^4 rows: one launch to wait for instead of two), else by a launch of their own before it
   const bool long_inside = part != VDF_ROWS_INSIDE && shape->n_long_rowlist > 0 && vdf::tuning().nifs_fused &&
                            vdf::nifs_cross_lanes(rows) == 8;
-  if (part != VDF_ROWS_INSIDE && !long_inside) {
-    void* const outs[3] = {Az2, Bz2, Cz2};
-    VDF_TRY(vdf::vec_spmv_long(shape->field, shape->d_rowptr, shape->d_col, shape->d_coef, shape->d_dict, z2, shape->d_long,
-                               shape->n_long, outs, ctx->stream));
-  }
+  if (part != VDF_ROWS_INSIDE && !long_inside)
+    VDF_TRY(vdf::vec_spmv_long(shape->field, shape->d_rowptr, shape->d_col, shape->d_coef, shape->d_dict, o.z2, shape->d_long,
+                               shape->n_long, o.abc2, ctx->stream));
   // algorithmic bytes of the launch: per entry of A, B, C the column and coefficient index (8 B), per
   // row three row pointers and three results (3 x 36 B) and the seven vectors of the cross term (7 x 32 B); the gathered
   // elements of z are not counted (they are re-reads of a vector the launch already reads once through the cache)
@@ -1663,36 +1677,35 @@ static Status nifs_cross_impl(vdf_ctx* ctx, const vdf_shape* shape, size_t row_b
     const double nnz_run = part == VDF_ROWS_INSIDE ? nnz_range : nnz_all - nnz_range;
     alg_bytes = nnz_run * 8.0 + (double)rows * (3 * 36.0 + 7 * 32.0);
   }
-  VDF_TRY(vdf::vec_nifs_cross(shape->field, shape->d_rowptr, shape->d_col, shape->d_coef, shape->d_dict, z2, Az1, Bz1, Cz1,
-                              u1, rows, skip_begin, skip_len, long_inside ? shape->d_long_rowlist : nullptr,
-                              long_inside ? shape->n_long_rowlist : 0, Az2, Bz2, Cz2, T, alg_bytes, ctx->stream));
+  VDF_TRY(vdf::vec_nifs_cross(shape->field, shape->d_rowptr, shape->d_col, shape->d_coef, shape->d_dict, o, rows, skip_begin, skip_len,
+                              long_inside ? shape->d_long_rowlist : nullptr, long_inside ? shape->n_long_rowlist : 0, alg_bytes,
+                              ctx->stream));
   if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
   return Status{};
 }
 
 int vdf_nifs_cross_term(vdf_ctx* ctx, const vdf_shape* shape, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,
                         const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T) {
-  return guarded(ctx, [&]() -> Status { return nifs_cross_impl(ctx, shape, 0, 0, VDF_ROWS_ALL, z2, Az1, Bz1, Cz1, u1, Az2, Bz2, Cz2, T); });
+  return guarded(ctx, [&]() -> Status { return nifs_cross_impl(ctx, shape, 0, 0, VDF_ROWS_ALL, {z2, {Az1, Bz1, Cz1}, u1, {Az2, Bz2, Cz2}, T}); });
 }
 
 int vdf_nifs_cross_term_rows(vdf_ctx* ctx, const vdf_shape* shape, size_t row_begin, size_t row_count, int part, const vdf_fe* z2,
                              const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2,
                              vdf_fe* Cz2, vdf_fe* T) {
-  return guarded(ctx, [&]() -> Status { return nifs_cross_impl(ctx, shape, row_begin, row_count, part, z2, Az1, Bz1, Cz1, u1, Az2, Bz2, Cz2, T); });
+  return guarded(ctx, [&]() -> Status {
+    return nifs_cross_impl(ctx, shape, row_begin, row_count, part, {z2, {Az1, Bz1, Cz1}, u1, {Az2, Bz2, Cz2}, T});
+  });
 }
 
 int vdf_nifs_cross_term_minroot(vdf_ctx* ctx, int field, int vars_per_round, uint64_t t, size_t seg_begin, size_t one_col, size_t row_begin,
                                 const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2,
                                 vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T) {
   return guarded(ctx, [&]() -> Status {
-    if (!z2 || !Az1 || !Bz1 || !Cz1 || !u1 || !Az2 || !Bz2 || !Cz2 || !T) return Status{VDF_ERR_BAD_ARG, "null argument"};
-    if (ptr_is_device(u1)) return Status{VDF_ERR_BAD_ARG, "scalar operands of fused calls live in host memory"};
-    for (const void* v : {(const void*)z2, (const void*)Az1, (const void*)Bz1, (const void*)Cz1, (const void*)Az2, (const void*)Bz2,
-                          (const void*)Cz2, (const void*)T})
-      if (!ptr_is_device(v)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
+    const vdf::CrossOperands o{z2, {Az1, Bz1, Cz1}, u1, {Az2, Bz2, Cz2}, T};
+    VDF_TRY(check_cross_operands(o));
     if (t == 0 || t > (1ull << 26)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
     if (seg_begin < 3 || one_col < seg_begin + (size_t)vars_per_round * t + 1) return Status{VDF_ERR_BAD_ARG, "the constant's column lies behind the rounds"};
-    VDF_TRY(vdf::vec_nifs_cross_minroot(field, vars_per_round, t, seg_begin, one_col, row_begin, z2, Az1, Bz1, Cz1, u1, Az2, Bz2, Cz2, T, ctx->stream));
+    VDF_TRY(vdf::vec_nifs_cross_minroot(field, vars_per_round, t, seg_begin, one_col, row_begin, o, ctx->stream));
     if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
     return Status{};
   });
@@ -1708,17 +1721,13 @@ int vdf_nifs_cross_term_minroot_forward_lanes(vdf_ctx* ctx, int field, uint64_t 
                                               size_t row_begin, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,
                                               const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T) {
   return guarded(ctx, [&]() -> Status {
-    if (!z2 || !Az1 || !Bz1 || !Cz1 || !u1 || !Az2 || !Bz2 || !Cz2 || !T) return Status{VDF_ERR_BAD_ARG, "null argument"};
-    if (ptr_is_device(u1)) return Status{VDF_ERR_BAD_ARG, "scalar operands of fused calls live in host memory"};
-    for (const void* v : {(const void*)z2, (const void*)Az1, (const void*)Bz1, (const void*)Cz1, (const void*)Az2, (const void*)Bz2,
-                          (const void*)Cz2, (const void*)T})
-      if (!ptr_is_device(v)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
+    const vdf::CrossOperands o{z2, {Az1, Bz1, Cz1}, u1, {Az2, Bz2, Cz2}, T};
+    VDF_TRY(check_cross_operands(o));
     if (t == 0 || t > (1ull << 26)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
     if (lanes == 0 || lanes > VDF_MINROOT_MAX_LANES) return Status{VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_MINROOT_MAX_LANES"};
     if (seg_begin < 3 * lanes || one_col < seg_begin + lanes * ((size_t)3 * t + 1))
       return Status{VDF_ERR_BAD_ARG, "the constant's column lies behind the rounds"};
-    VDF_TRY(vdf::vec_nifs_cross_minroot_forward_lanes(field, t, lanes, seg_begin, one_col, row_begin, z2, Az1, Bz1, Cz1, u1, Az2, Bz2, Cz2, T,
-                                                      ctx->stream));
+    VDF_TRY(vdf::vec_nifs_cross_minroot_forward_lanes(field, t, lanes, seg_begin, one_col, row_begin, o, ctx->stream));
     if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
     return Status{};
   });
@@ -1728,14 +1737,12 @@ int vdf_nifs_cross_term_periodic(vdf_ctx* ctx, int field, const vdf_periodic_row
                                  size_t row_begin, size_t num_cols, size_t num_cons, const vdf_fe* z2, const vdf_fe* Az1, const vdf_fe* Bz1,
                                  const vdf_fe* Cz1, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2, vdf_fe* T) {
   return guarded(ctx, [&]() -> Status {
-    if (!rows || !z2 || !Az1 || !Bz1 || !Cz1 || !u1 || !Az2 || !Bz2 || !Cz2 || !T) return Status{VDF_ERR_BAD_ARG, "null argument"};
-    if (ptr_is_device(rows) || ptr_is_device(rows->row_start) || ptr_is_device(rows->terms) || ptr_is_device(rows->consts) || ptr_is_device(u1))
-      return Status{VDF_ERR_BAD_ARG, "the description and scalar operands of fused calls live in host memory"};
-    for (const void* v : {(const void*)z2, (const void*)Az1, (const void*)Bz1, (const void*)Cz1, (const void*)Az2, (const void*)Bz2,
-                          (const void*)Cz2, (const void*)T})
-      if (!ptr_is_device(v)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
-    VDF_TRY(vdf::vec_nifs_cross_periodic(field, rows, j_first, reps, seg_begin, row_begin, num_cols, num_cons, z2, Az1, Bz1, Cz1, u1, Az2, Bz2,
-                                         Cz2, T, ctx->stream));
+    const vdf::CrossOperands o{z2, {Az1, Bz1, Cz1}, u1, {Az2, Bz2, Cz2}, T};
+    static constexpr const char* ON_HOST = "the description and scalar operands of fused calls live in host memory";
+    if (!rows || cross_operand_missing(o)) return Status{VDF_ERR_BAD_ARG, "null argument"};
+    if (ptr_is_device(rows)) return Status{VDF_ERR_BAD_ARG, ON_HOST};       // before anything is read through it
+    VDF_TRY(check_cross_operands(o, false, {rows->row_start, rows->terms, rows->consts}, ON_HOST));
+    VDF_TRY(vdf::vec_nifs_cross_periodic(field, rows, j_first, reps, seg_begin, row_begin, num_cols, num_cons, o, ctx->stream));
     if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
     return Status{};
   });
@@ -1746,17 +1753,17 @@ int vdf_nifs_cross_term_minroot_fold(vdf_ctx* ctx, int field, int vars_per_round
                                      vdf_fe* E1, const vdf_fe* T_prev, const vdf_fe* u1, vdf_fe* Az2, vdf_fe* Bz2, vdf_fe* Cz2,
                                      vdf_fe* T) {
   return guarded(ctx, [&]() -> Status {
-    if (!z2 || !r || !Az1 || !Bz1 || !Cz1 || !u1 || !Az2 || !Bz2 || !Cz2 || !T) return Status{VDF_ERR_BAD_ARG, "null argument"};
+    const vdf::CrossOperands o{z2, {Az1, Bz1, Cz1}, u1, {Az2, Bz2, Cz2}, T};
+    // (the checker looks for NULLs again: asked here first so that "E1 without T_prev" keeps its place behind them)
+    if (!r || cross_operand_missing(o)) return Status{VDF_ERR_BAD_ARG, "null argument"};
     if (E1 && !T_prev) return Status{VDF_ERR_BAD_ARG, "E1 without T_prev"};
-    if (ptr_is_device(u1) || ptr_is_device(r)) return Status{VDF_ERR_BAD_ARG, "scalar operands of fused calls live in host memory"};
-    for (const void* v : {(const void*)z2, (const void*)Az1, (const void*)Bz1, (const void*)Cz1, (const void*)Az2, (const void*)Bz2,
-                          (const void*)Cz2, (const void*)T})
-      if (!ptr_is_device(v)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
+    VDF_TRY(check_cross_operands(o, false, {r}));
     if (E1 && (!ptr_is_device(E1) || !ptr_is_device(T_prev))) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
     if (t == 0 || t > (1ull << 26)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
     if (seg_begin < 3 || one_col < seg_begin + (size_t)vars_per_round * t + 1) return Status{VDF_ERR_BAD_ARG, "the constant's column lies behind the rounds"};
-    VDF_TRY(vdf::vec_nifs_cross_minroot_fold(field, vars_per_round, t, seg_begin, one_col, row_begin, z2, r, Az1, Bz1, Cz1, E1, E1 ? T_prev : nullptr,
-                                             u1, Az2, Bz2, Cz2, T, ctx->stream));
+    void* const folded[3] = {Az1, Bz1, Cz1};
+    VDF_TRY(vdf::vec_nifs_cross_minroot_fold(field, vars_per_round, t, seg_begin, one_col, row_begin, r, folded, E1, E1 ? T_prev : nullptr, o,
+                                             ctx->stream));
     if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
     return Status{};
   });

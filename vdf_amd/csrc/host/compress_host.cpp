@@ -960,9 +960,7 @@ int compress_prelude(const vdf_proof* p, vdf_pp* pp, vdf_snark* s, void* d_fz, v
   s->zi2[0] = p->zi[SECONDARY][0];
   vdf_proof* q = const_cast<vdf_proof*>(p);
   SideState& s2 = q->r[SECONDARY];
-  HIPCALL(ctx, vdf_nifs_cross_term(ctx, S2.shape, (const vdf_fe*)p->d_l2z, (const vdf_fe*)s2.d_abc[0], (const vdf_fe*)s2.d_abc[1],
-                                   (const vdf_fe*)s2.d_abc[2], (const vdf_fe*)&s2.inst.u, (vdf_fe*)s2.d_abc2[0], (vdf_fe*)s2.d_abc2[1],
-                                   (vdf_fe*)s2.d_abc2[2], (vdf_fe*)s2.d_T));
+  { int rc = cross_all(ctx, S2, s2, p->d_l2z); if (rc != VDF_OK) return rc; }
   vdf_jac jt;
   HIPCALL(ctx, vdf_msm(ctx, S2.gens, 0, (const vdf_fe*)s2.d_T, S2.num_cons, 1, &jt));
   s->T2 = jac_to_aff(jt, *S2.Fb);

@@ -1434,6 +1434,41 @@ static int upload_fresh(vdf_ctx* ctx, const Side& sd, const CS& cs, Fe* stage, v
 namespace {
 enum StepMark { MARK_Z = 0, MARK_W = 1, MARK_T = 2, MARK_STEP = 4, MARK_PRIMARY = 5, MARK_FOLD = 6, MARK_ZIN = 7 };
 
+// The cross term of side S's running instance `st` with the fresh witness d_z2, enqueued on q: one helper per entry point of
+// libvdf_hip.so (include/vdf_hip.h; cross_all, every row through the sparse matrices, is in nova_internal.hpp).  The stencils' and
+// the periodic rows' constant column is num_vars.
+static int cross_rows(vdf_ctx* q, const Side& S, const SideState& st, const void* d_z2, size_t begin, size_t n, int part) {
+  const SideState::Cross c = st.cross(d_z2);
+  HIPCALL(q, vdf_nifs_cross_term_rows(q, S.shape, begin, n, part, CROSS_ARGS(c)));
+  return VDF_OK;
+}
+static int cross_stencil(vdf_ctx* q, const Side& S, const SideState& st, const void* d_z2, int per, uint64_t t, size_t seg_b, size_t row0) {
+  const SideState::Cross c = st.cross(d_z2);
+  HIPCALL(q, vdf_nifs_cross_term_minroot(q, S.field, per, t, seg_b, S.num_vars, row0, CROSS_ARGS(c)));
+  return VDF_OK;
+}
+static int cross_forward(vdf_ctx* q, const Side& S, const SideState& st, const void* d_z2, uint64_t t, size_t lanes, size_t seg_b, size_t row0) {
+  const SideState::Cross c = st.cross(d_z2);
+  HIPCALL(q, vdf_nifs_cross_term_minroot_forward_lanes(q, S.field, t, lanes, seg_b, S.num_vars, row0, CROSS_ARGS(c)));
+  return VDF_OK;
+}
+// a custom circuit's periodic repetitions (lead .. t - 1 of its repeat) from their description
+static int cross_periodic(vdf_ctx* q, const Side& S, const SideState& st, const void* d_z2, const PeriodicRows& pr, const RepeatState& round) {
+  const SideState::Cross c = st.cross(d_z2);
+  const vdf_periodic_rows view = pr.view();
+  HIPCALL(q, vdf_nifs_cross_term_periodic(q, S.field, &view, pr.lead, round.t - pr.lead, round.var_begin, pr.row_begin, S.ncols, S.num_cons,
+                                          CROSS_ARGS(c)));
+  return VDF_OK;
+}
+// the inverse stencil with the fold by r of its rows of the running A z, B z, C z and E applied on the way (the one call that writes them)
+static int cross_stencil_fold(vdf_ctx* q, const Side& S, SideState& st, const void* d_z2, int per, uint64_t t, size_t seg_b, size_t row0, const Fe* r) {
+  const SideState::Cross c = st.cross(d_z2);
+  HIPCALL(q, vdf_nifs_cross_term_minroot_fold(q, S.field, per, t, seg_b, S.num_vars, row0, c.z2, (const vdf_fe*)r, (vdf_fe*)st.d_abc[0],
+                                              (vdf_fe*)st.d_abc[1], (vdf_fe*)st.d_abc[2], (vdf_fe*)st.d_E, c.T, c.u1, c.abc2[0], c.abc2[1],
+                                              c.abc2[2], c.T));
+  return VDF_OK;
+}
+
 struct StepRun {
   static constexpr int D = vdf_proof::DEPTH, R = vdf_proof::RING;
   // ---- what the step works on
@@ -1644,6 +1679,31 @@ struct StepRun {
   bool stencil_fold_ok() const {
     return pp->tune.fold_fused != 0 && pp->stencil_per != 0 && !forward && (t_parts == 1 || ta_n < 4096);
   }
+  // A z2, B z2, C z2 and T of the rows [b, b + n) of the primary side on the EARLY ROWS queue, by whatever the parameters allow:
+  // the stencil with the previous fold of its rows on the way (fold_r), the forward stencil, the inverse stencil (vdf_hip.h: streams
+  // only), a custom circuit's periodic repetitions from their description with the rows of the run in front of them and behind
+  // them through the sparse matrices, or the sparse matrices alone
+  int primary_rows(void* d_z2, size_t b, size_t n, const Fe* fold_r) {
+    SideState& s1 = p->r[PRIMARY];
+    const bool stencil = pp->stencil_per && b == ta_b && n == ta_n;
+    auto generic = [&](size_t rb, size_t rn) -> int { return rn ? cross_rows(ct, S1, s1, d_z2, rb, rn, VDF_ROWS_INSIDE) : VDF_OK; };
+    if (fold_r) {
+      if (!stencil) return fail(VDF_ERR_DEVICE, "fused fold without the stencil");
+      int rc = cross_stencil_fold(ct, S1, s1, d_z2, pp->stencil_per, pp->t, seg_b, b, fold_r);
+      if (rc != VDF_OK) return rc;
+      HIPCALL(ct, vdf_ctx_mark(ct, MARK_FOLD));                      // the running instance is whole again from here on
+      return VDF_OK;
+    }
+    if (stencil) return forward ? cross_forward(ct, S1, s1, d_z2, pp->t, pp->lanes, seg_b, b) : cross_stencil(ct, S1, s1, d_z2, pp->stencil_per, pp->t, seg_b, b);
+    const PeriodicRows& pr = pp->periodic;
+    if (custom && pp->periodic_on && pr.row_begin >= b && pr.row_begin + pr.row_count <= b + n) {
+      int rc = generic(b, pr.row_begin - b);
+      if (rc == VDF_OK) rc = cross_periodic(ct, S1, s1, d_z2, pr, pp->round);
+      if (rc != VDF_OK) return rc;
+      return generic(pr.row_begin + pr.row_count, b + n - (pr.row_begin + pr.row_count));
+    }
+    return generic(b, n);
+  }
   int early_rows_launch(void* d_z2, vdf_ctx* cq, bool zin_in_place, const Fe* fold_r = nullptr) {
     SideState& s1 = p->r[PRIMARY];
     HIPCALL(ct, vdf_ctx_wait_mark(ct, cq, MARK_Z));                 // the rounds are in place (written a step ago, normally)
@@ -1652,55 +1712,9 @@ struct StepRun {
       memcpy(p->h_zin, p->zi[PRIMARY].data(), arity * 32);          // pinned: the copy reads it when it runs
       HIPCALL(ct, vdf_dev_memcpy(ct, (char*)d_z2 + pp->zin_begin * 32, p->h_zin, arity * 32));
     }
-    auto generic = [&](size_t b, size_t n) -> int {
-      if (n == 0) return VDF_OK;
-      HIPCALL(ct, vdf_nifs_cross_term_rows(ct, S1.shape, b, n, VDF_ROWS_INSIDE, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0],
-                                           (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2], (const vdf_fe*)&s1.inst.u,
-                                           (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
-      return VDF_OK;
-    };
-    auto rows = [&](size_t b, size_t n) -> int {
-      if (fold_r) {                                                  // the stencil with the previous fold of its rows on the way
-        if (!(pp->stencil_per && b == ta_b && n == ta_n)) return fail(VDF_ERR_DEVICE, "fused fold without the stencil");
-        HIPCALL(ct, vdf_nifs_cross_term_minroot_fold(ct, S1.field, pp->stencil_per, pp->t, seg_b, S1.num_vars, b, (const vdf_fe*)d_z2,
-                                                     (const vdf_fe*)fold_r, (vdf_fe*)s1.d_abc[0], (vdf_fe*)s1.d_abc[1], (vdf_fe*)s1.d_abc[2],
-                                                     (vdf_fe*)s1.d_E, (const vdf_fe*)s1.d_T, (const vdf_fe*)&s1.inst.u, (vdf_fe*)s1.d_abc2[0],
-                                                     (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
-        HIPCALL(ct, vdf_ctx_mark(ct, MARK_FOLD));                    // the running instance is whole again from here on
-        return VDF_OK;
-      }
-      if (forward && pp->stencil_per && b == ta_b && n == ta_n) {
-        HIPCALL(ct, vdf_nifs_cross_term_minroot_forward_lanes(ct, S1.field, pp->t, pp->lanes, seg_b, S1.num_vars, b, (const vdf_fe*)d_z2,
-                                                              (const vdf_fe*)s1.d_abc[0], (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2],
-                                                              (const vdf_fe*)&s1.inst.u, (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1],
-                                                              (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
-        return VDF_OK;
-      }
-      if (pp->stencil_per && b == ta_b && n == ta_n) {               // the MinRoot stencil: streams only (vdf_hip.h)
-        HIPCALL(ct, vdf_nifs_cross_term_minroot(ct, S1.field, pp->stencil_per, pp->t, seg_b, S1.num_vars, b, (const vdf_fe*)d_z2,
-                                                (const vdf_fe*)s1.d_abc[0], (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2],
-                                                (const vdf_fe*)&s1.inst.u, (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1],
-                                                (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
-        return VDF_OK;
-      }
-      const PeriodicRows& pr = pp->periodic;
-      if (custom && pp->periodic_on && pr.row_begin >= b && pr.row_begin + pr.row_count <= b + n) {
-        // a custom circuit's periodic repetitions (lead .. t - 1 of its repeat) from their description; the rows of the run in front
-        // of them and behind them through the sparse matrices, as in chain_primary_nifs
-        const vdf_periodic_rows view = pr.view();
-        int rc = generic(b, pr.row_begin - b);
-        if (rc != VDF_OK) return rc;
-        HIPCALL(ct, vdf_nifs_cross_term_periodic(ct, S1.field, &view, pr.lead, pp->round.t - pr.lead, pp->round.var_begin, pr.row_begin,
-                                                  S1.ncols, S1.num_cons, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0],
-                                                  (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2], (const vdf_fe*)&s1.inst.u,
-                                                  (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
-        return generic(pr.row_begin + pr.row_count, b + n - (pr.row_begin + pr.row_count));
-      }
-      return generic(b, n);
-    };
     memset(&hb[5], 0, 2 * sizeof(vdf_jac));                          // parts not used this time: the identity
     if (t_parts == 1 || ta_n < 4096) {
-      int rc = rows(ta_b, ta_n);
+      int rc = primary_rows(d_z2, ta_b, ta_n, fold_r);
       if (rc != VDF_OK) return rc;
       HIPCALL(ct, vdf_msm(ct, S1.gens, ta_b, (const vdf_fe*)((const char*)s1.d_T + ta_b * 32), ta_n, 1, &hb[4]));
     } else {
@@ -1709,7 +1723,7 @@ struct StepRun {
       vdf_msm_job* job = nullptr;
       HIPCALL(ct, vdf_msm_job_begin(ct, S1.gens, t_parts, off, len, 1, &job));
       for (int g = 0; g < t_parts; ++g) {
-        int rc = rows(off[g], len[g]);
+        int rc = primary_rows(d_z2, off[g], len[g], fold_r);
         if (rc == VDF_OK && vdf_msm_job_push(job, g, (const vdf_fe*)((const char*)s1.d_T + off[g] * 32)) != VDF_OK)
           rc = fail(VDF_ERR_DEVICE, std::string("vdf_msm_job_push: ") + vdf_last_error(ct));
         if (rc != VDF_OK) { vdf_jac scratch[3]; (void)vdf_msm_job_finish(job, scratch); return rc; }
@@ -1744,9 +1758,7 @@ struct StepRun {
   // cross term of (running secondary, l2), commit(w2) unless known, commit(T2)
   int chain_launch_nifs2() {
     SideState& s2 = p->r[SECONDARY];
-    HIPCALL(ctx, vdf_nifs_cross_term(ctx, S2.shape, (const vdf_fe*)p->d_l2z, (const vdf_fe*)s2.d_abc[0], (const vdf_fe*)s2.d_abc[1],
-                                     (const vdf_fe*)s2.d_abc[2], (const vdf_fe*)&s2.inst.u, (vdf_fe*)s2.d_abc2[0], (vdf_fe*)s2.d_abc2[1],
-                                     (vdf_fe*)s2.d_abc2[2], (vdf_fe*)s2.d_T));
+    { int rc = cross_all(ctx, S2, s2, p->d_l2z); if (rc != VDF_OK) return rc; }
     if (p->l2_committed) {
       HIPCALL(ctx, vdf_msm(ctx, S2.gens, 0, (const vdf_fe*)s2.d_T, S2.num_cons, 1, &hb[1]));
     } else {
@@ -1868,28 +1880,18 @@ struct StepRun {
       if (!first) {
         if (t_ahead) {
           group(s1.d_T, 0, ta_b); group(s1.d_T, ta_e, S1.num_cons - ta_e);
-          HIPCALL(ctx, vdf_nifs_cross_term_rows(ctx, S1.shape, ta_b, ta_n, VDF_ROWS_OUTSIDE, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0],
-                                                (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2], (const vdf_fe*)&s1.inst.u,
-                                                (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
+          { int rc = cross_rows(ctx, S1, s1, d_z2, ta_b, ta_n, VDF_ROWS_OUTSIDE); if (rc != VDF_OK) return rc; }
         } else if (custom && pp->periodic_on) {
           // the rows of the repeat's periodic repetitions from their description, every other row through the sparse matrices:
           // two launches on the step's own queue, T committed in one piece as before
           group(s1.d_T, 0, S1.num_cons);
           const PeriodicRows& pr = pp->periodic;
-          const vdf_periodic_rows view = pr.view();
-          HIPCALL(ctx, vdf_nifs_cross_term_rows(ctx, S1.shape, pr.row_begin, pr.row_count, VDF_ROWS_OUTSIDE, (const vdf_fe*)d_z2,
-                                                (const vdf_fe*)s1.d_abc[0], (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2],
-                                                (const vdf_fe*)&s1.inst.u, (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2],
-                                                (vdf_fe*)s1.d_T));
-          HIPCALL(ctx, vdf_nifs_cross_term_periodic(ctx, S1.field, &view, pr.lead, pp->round.t - pr.lead, pp->round.var_begin, pr.row_begin,
-                                                    S1.ncols, S1.num_cons, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0],
-                                                    (const vdf_fe*)s1.d_abc[1], (const vdf_fe*)s1.d_abc[2], (const vdf_fe*)&s1.inst.u,
-                                                    (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1], (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
+          int rc = cross_rows(ctx, S1, s1, d_z2, pr.row_begin, pr.row_count, VDF_ROWS_OUTSIDE);
+          if (rc == VDF_OK) rc = cross_periodic(ctx, S1, s1, d_z2, pr, pp->round);
+          if (rc != VDF_OK) return rc;
         } else {
           group(s1.d_T, 0, S1.num_cons);
-          HIPCALL(ctx, vdf_nifs_cross_term(ctx, S1.shape, (const vdf_fe*)d_z2, (const vdf_fe*)s1.d_abc[0], (const vdf_fe*)s1.d_abc[1],
-                                           (const vdf_fe*)s1.d_abc[2], (const vdf_fe*)&s1.inst.u, (vdf_fe*)s1.d_abc2[0], (vdf_fe*)s1.d_abc2[1],
-                                           (vdf_fe*)s1.d_abc2[2], (vdf_fe*)s1.d_T));
+          { int rc = cross_all(ctx, S1, s1, d_z2); if (rc != VDF_OK) return rc; }
         }
       }
       HIPCALL(ctx, vdf_msm_batch(ctx, S1.gens, ng, off, sc, len, 1, hb));

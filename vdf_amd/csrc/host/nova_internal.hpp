@@ -208,7 +208,21 @@ struct SideState {
   void* d_abc[3] = {};       // A z, B z, C z of the running instance, folded along (linear in z)
   void* d_abc2[3] = {};      // the fresh instance's
   void* d_T = nullptr;
+  // The operands of a cross term of this running instance with a fresh z2, typed and ordered as every vdf_nifs_cross_term* of
+  // include/vdf_hip.h takes them (CROSS_ARGS): z2, A z1, B z1, C z1, u1 | A z2, B z2, C z2, T
+  struct Cross { const vdf_fe* z2; const vdf_fe* abc1[3]; const vdf_fe* u1; vdf_fe* abc2[3]; vdf_fe* T; };
+  Cross cross(const void* d_z2) const {
+    return {(const vdf_fe*)d_z2, {(const vdf_fe*)d_abc[0], (const vdf_fe*)d_abc[1], (const vdf_fe*)d_abc[2]}, (const vdf_fe*)&inst.u,
+            {(vdf_fe*)d_abc2[0], (vdf_fe*)d_abc2[1], (vdf_fe*)d_abc2[2]}, (vdf_fe*)d_T};
+  }
 };
+#define CROSS_ARGS(c) (c).z2, (c).abc1[0], (c).abc1[1], (c).abc1[2], (c).u1, (c).abc2[0], (c).abc2[1], (c).abc2[2], (c).T
+// A z2, B z2, C z2 and T of EVERY row of side S through its sparse matrices, enqueued on q (nova_host.cpp has the other entry points)
+inline int cross_all(vdf_ctx* q, const vdfnova::Side& S, const SideState& st, const void* d_z2) {
+  const SideState::Cross c = st.cross(d_z2);
+  HIPCALL(q, vdf_nifs_cross_term(q, S.shape, CROSS_ARGS(c)));
+  return VDF_OK;
+}
 struct vdf_proof {
   vdf_pp* pp = nullptr;
   size_t i = 0;

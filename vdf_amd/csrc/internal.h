@@ -335,27 +335,26 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tape, const 
                                    void* checkpoints, uint64_t every, size_t cp_stride, void* trace, size_t walk_stride, uint64_t base,
                                    uint64_t j_base, uint64_t j_walk_step, hipStream_t s);
 Status round_tape_forward_max_rounds(const vdf_round_tape* tape, const vdf_fe* inv, uint64_t* max_rounds);
+// The operands every cross-term launcher shares: the fresh z2, the running A z1, B z1, C z1 and u1 (host memory: it travels as a
+// kernel argument), and what is written -- the fresh A z2, B z2, C z2 and T.  Host-side only: it ends at the launch line, where the
+// kernels keep their own __restrict__ pointers.
+struct CrossOperands { const void* z2; const void* abc1[3]; const vdf_fe* u1; void* abc2[3]; void* T; };
 // rounds.hip: the cross term of periodic rows (vdf_hip.h vdf_periodic_rows; every index is checked before the launch)
 Status vec_nifs_cross_periodic(int field, const vdf_periodic_rows* rows, uint64_t j_first, uint64_t reps, size_t seg_begin, size_t row0,
-                               size_t num_cols, size_t num_cons, const void* z2, const void* az1, const void* bz1, const void* cz1,
-                               const vdf_fe* u1, void* az2, void* bz2, void* cz2, void* T, hipStream_t s);
+                               size_t num_cols, size_t num_cons, const CrossOperands& o, hipStream_t s);
 Status vec_step_z(int field, const void* trace_xy, uint64_t t, const vdf_fe z_in[3], const vdf_fe* i0, const vdf_fe* u,
                   const vdf_fe X[6], void* z, void* packed, hipStream_t s);
 Status vec_nifs_cross(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3],
-                      const uint32_t* const coef[3], const void* dict, const void* z2, const void* az1, const void* bz1,
-                      const void* cz1, const vdf_fe* u1, size_t rows, size_t skip_begin, size_t skip_len,
-                      const uint32_t* long_rowlist, size_t n_long_rows, void* az2, void* bz2, void* cz2, void* T,
-                      double alg_bytes, hipStream_t s);
+                      const uint32_t* const coef[3], const void* dict, const CrossOperands& o, size_t rows, size_t skip_begin,
+                      size_t skip_len, const uint32_t* long_rowlist, size_t n_long_rows, double alg_bytes, hipStream_t s);
 int nifs_cross_lanes(size_t rows);                       // lanes per row vec_nifs_cross picks for a launch over `rows` rows
-Status vec_nifs_cross_minroot(int field, int per, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
-                              const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, void* az2, void* bz2, void* cz2,
-                              void* T, hipStream_t s);
-Status vec_nifs_cross_minroot_forward_lanes(int field, uint64_t t, size_t lanes, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
-                                            const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, void* az2, void* bz2,
-                                            void* cz2, void* T, hipStream_t s);
-Status vec_nifs_cross_minroot_fold(int field, int per, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
-                                   const vdf_fe* r, void* az1, void* bz1, void* cz1, void* e1, const void* tprev, const vdf_fe* u1,
-                                   void* az2, void* bz2, void* cz2, void* T, hipStream_t s);
+Status vec_nifs_cross_minroot(int field, int per, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const CrossOperands& o,
+                              hipStream_t s);
+Status vec_nifs_cross_minroot_forward_lanes(int field, uint64_t t, size_t lanes, size_t seg_begin, size_t one_col, size_t row0,
+                                            const CrossOperands& o, hipStream_t s);
+// folded: o.abc1 again, as the pointers this variant alone WRITES through (the running rows, folded in place); r: host memory
+Status vec_nifs_cross_minroot_fold(int field, int per, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const vdf_fe* r,
+                                   void* const folded[3], void* e1, const void* tprev, const CrossOperands& o, hipStream_t s);
 Status vec_fold_many(int field, const vdf_fe* r, int k, void* const acc[], const void* const add[], const size_t n[],
                      hipStream_t s);
 // random linear combinations of many instances (vdf_lincomb_u128, vdf_relaxed_residual_batch): w and rho plain integers below

@@ -11,6 +11,7 @@
 #include <cstring>
 #include "internal.h"
 #include "fe.cuh"
+#include "cross.cuh"
 #include "tape_rules.h"
 
 namespace vdf {
@@ -436,7 +437,7 @@ __global__ __launch_bounds__(256) void k_nifs_cross_periodic(PeriodicArgs pa, co
         Fe<P> coef = lds_fe<P>(s_consts, k0);
         if (mode != PT_MUL) {
           const uint64_t d = j - pa.j0;
-          Fe<P> m = d < (1u << 30) ? fe_from_small<P>((uint32_t)d) : fe_from_u64<P>(d);
+          Fe<P> m = fe_from_count<P>(d);
           if (mode == PT_AFFINE) m = fe_mul(m, lds_fe<P>(s_consts, k1));
           coef = fe_add(coef, m);
         }
@@ -444,13 +445,7 @@ __global__ __launch_bounds__(256) void k_nifs_cross_periodic(PeriodicArgs pa, co
       }
     }
   }
-  fe_store<P>(az2 + r * 32, acc[0]);
-  fe_store<P>(bz2 + r * 32, acc[1]);
-  fe_store<P>(cz2 + r * 32, acc[2]);
-  Fe<P> tt = fe_add(fe_mul(a1, acc[1]), fe_mul(acc[0], b1));
-  tt = fe_sub(tt, fe_mul(tape_fe<P>(u1), acc[2]));
-  tt = fe_sub(tt, c1);
-  fe_store<P>(T + r * 32, tt);
+  cross_finish<P>(az2, bz2, cz2, T, r, a1, b1, c1, tape_fe<P>(u1), acc[0], acc[1], acc[2]);
 }
 
 static TapeFe tape_val(const vdf_fe* p) { TapeFe v; std::memcpy(&v, p, 32); return v; }
@@ -626,8 +621,7 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tp, const vd
 
 // Everything the description could index out of range is checked here, before a launch (vdf_hip.h vdf_nifs_cross_term_periodic)
 Status vec_nifs_cross_periodic(int field, const vdf_periodic_rows* pr, uint64_t j_first, uint64_t reps, size_t seg_begin, size_t row0,
-                               size_t num_cols, size_t num_cons, const void* z2, const void* az1, const void* bz1, const void* cz1,
-                               const vdf_fe* u1, void* az2, void* bz2, void* cz2, void* T, hipStream_t s) {
+                               size_t num_cols, size_t num_cons, const CrossOperands& o, hipStream_t s) {
   VDF_TRY(check_field(field));
   if (!pr || !pr->row_start || (pr->n_terms && !pr->terms) || (pr->n_consts && !pr->consts)) return Status{VDF_ERR_BAD_ARG, "null description"};
   if (pr->n_cons == 0 || pr->n_cons > VDF_PERIODIC_MAX_ROWS || pr->n_vars == 0 || pr->n_terms > VDF_PERIODIC_MAX_TERMS ||
@@ -685,8 +679,9 @@ Status vec_nifs_cross_periodic(int field, const vdf_periodic_rows* pr, uint64_t 
   // the seven vectors of the cross term per row, and the gathered elements once (they are the repetitions' own variables)
   KTimer kt(s, "k_nifs_cross_periodic", (double)rows * 7 * 32 + (double)reps * pr->n_vars * 32);
   return with_field(field, [&](auto f) {
-    hipLaunchKernelGGL((k_nifs_cross_periodic<tag_t<decltype(f)>>), grid_for(rows), dim3(256), 0, s, a, cbytes_of(z2), cbytes_of(az1),
-                       cbytes_of(bz1), cbytes_of(cz1), tape_val(u1), bytes_of(az2), bytes_of(bz2), bytes_of(cz2), bytes_of(T));
+    hipLaunchKernelGGL((k_nifs_cross_periodic<tag_t<decltype(f)>>), grid_for(rows), dim3(256), 0, s, a, cbytes_of(o.z2), cbytes_of(o.abc1[0]),
+                       cbytes_of(o.abc1[1]), cbytes_of(o.abc1[2]), tape_val(o.u1), bytes_of(o.abc2[0]), bytes_of(o.abc2[1]), bytes_of(o.abc2[2]),
+                       bytes_of(o.T));
   });
 }
 

@@ -10,6 +10,7 @@
 #include <cstring>
 #include "internal.h"
 #include "fe.cuh"
+#include "cross.cuh"
 
 namespace vdf {
 
@@ -37,9 +38,7 @@ __global__ __launch_bounds__(256) void k_cross_term(const char* __restrict__ az1
   const Fe<P> u = fe_load<P>(u1);
   Fe<P> a1 = fe_load<P>(az1 + i * 32), b1 = fe_load<P>(bz1 + i * 32), c1 = fe_load<P>(cz1 + i * 32);
   Fe<P> a2 = fe_load<P>(az2 + i * 32), b2 = fe_load<P>(bz2 + i * 32), c2 = fe_load<P>(cz2 + i * 32);
-  Fe<P> t = fe_add(fe_mul(a1, b2), fe_mul(a2, b1));
-  t = fe_sub(t, fe_mul(u, c2));
-  t = fe_sub(t, c1);
+  const Fe<P> t = cross_value(a1, b1, c1, u, a2, b2, c2);
   fe_store<P>(T + i * 32, t);
 }
 
@@ -234,13 +233,7 @@ __global__ __launch_bounds__(256) void k_spmv_long(Csr3 m, const char* __restric
   Fe<P> acc = fe_zero<P>();
   for (uint32_t e = lo + lane; e < hi; e += 64)
     acc = fe_add(acc, spmv_term<P>(fe_load<P>(z + (size_t)col[e] * 32), coef[e], dict));
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    Fe<P> o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o.v[i] = __shfl_xor(acc.v[i], off, 64);
-    acc = fe_add(acc, o);
-  }
+  acc = fe_group_sum<P, 64>(acc);
   if (lane == 0) fe_store<P>(out + (size_t)r * 32, acc);
 }
 
@@ -294,13 +287,7 @@ __global__ __launch_bounds__(256) void k_nifs_cross(Csr3 m, const char* __restri
     for (uint32_t e = lo[k] + PRE[k]; e < hi[k]; ++e)
       acc[k] = fe_add(acc[k], spmv_term<P>(fe_load<P>(z2 + (size_t)m.col[k][e] * 32), m.coef[k][e], dict));
   }
-  fe_store<P>(az2 + r * 32, acc[0]);
-  fe_store<P>(bz2 + r * 32, acc[1]);
-  fe_store<P>(cz2 + r * 32, acc[2]);
-  Fe<P> t = fe_add(fe_mul(a1, acc[1]), fe_mul(acc[0], b1));
-  t = fe_sub(t, fe_mul(fe_from_val<P>(u1), acc[2]));
-  t = fe_sub(t, c1);
-  fe_store<P>(T + r * 32, t);
+  cross_finish<P>(az2, bz2, cz2, T, r, a1, b1, c1, fe_from_val<P>(u1), acc[0], acc[1], acc[2]);
 }
 
 // The same with LPR lanes per row (4 or 8): lane l of a row's group takes the entries l, l + LPR, ... of each of the three
@@ -354,23 +341,9 @@ __device__ __forceinline__ void nifs_cross_group(const Csr3& m, const char* __re
       acc[k] = fe_add(acc[k], spmv_term<P>(fe_load<P>(z2 + (size_t)m.col[k][e] * 32), m.coef[k][e], dict));
   }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-#pragma unroll
-    for (int off = LPR / 2; off >= 1; off >>= 1) {
-      Fe<P> o;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o.v[i] = __shfl_xor(acc[k].v[i], off, 64);
-      acc[k] = fe_add(acc[k], o);
-    }
-  }
+  for (int k = 0; k < 3; ++k) acc[k] = fe_group_sum<P, LPR>(acc[k]);
   if (l != 0 || !live) return;
-  fe_store<P>(az2 + r * 32, acc[0]);
-  fe_store<P>(bz2 + r * 32, acc[1]);
-  fe_store<P>(cz2 + r * 32, acc[2]);
-  Fe<P> t = fe_add(fe_mul(a1, acc[1]), fe_mul(acc[0], b1));
-  t = fe_sub(t, fe_mul(fe_from_val<P>(u1), acc[2]));
-  t = fe_sub(t, c1);
-  fe_store<P>(T + r * 32, t);
+  cross_finish<P>(az2, bz2, cz2, T, r, a1, b1, c1, fe_from_val<P>(u1), acc[0], acc[1], acc[2]);
 }
 
 template <class P, int LPR>
@@ -448,23 +421,9 @@ __global__ __launch_bounds__(256) void k_nifs_cross_f(Csr3 m, const char* __rest
       }
   }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      Fe<P> o;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o.v[i] = __shfl_xor(acc[k].v[i], off, 64);
-      acc[k] = fe_add(acc[k], o);
-    }
-  }
+  for (int k = 0; k < 3; ++k) acc[k] = fe_group_sum<P, 64>(acc[k]);
   if (lane != 0) return;
-  fe_store<P>(az2 + r * 32, acc[0]);
-  fe_store<P>(bz2 + r * 32, acc[1]);
-  fe_store<P>(cz2 + r * 32, acc[2]);
-  Fe<P> t = fe_add(fe_mul(a1, acc[1]), fe_mul(acc[0], b1));
-  t = fe_sub(t, fe_mul(fe_from_val<P>(u1), acc[2]));
-  t = fe_sub(t, c1);
-  fe_store<P>(T + r * 32, t);
+  cross_finish<P>(az2, bz2, cz2, T, r, a1, b1, c1, fe_from_val<P>(u1), acc[0], acc[1], acc[2]);
 }
 
 // The cross term over the rows of the built-in MinRoot step circuits WITHOUT the sparse matrices: the 3t + 1 constraints
@@ -487,13 +446,9 @@ __device__ __forceinline__ void minroot_stencil_row(const char* __restrict__ z2,
                                                     Fe<P>& a2, Fe<P>& b2, Fe<P>& c2) {
   const Fe<P> onev = fe_load<P>(z2 + one_col * 32);
   const Fe<P> i_in = fe_load<P>(z2 + (S - 1) * 32);
-  // k * z2[one]: the constant's value is ONE in every fresh instance (the same for all lanes: a uniform branch), and then
-  // the small-integer conversion is all it takes -- no Montgomery product (fe.cuh fe_from_small: ~50 instructions)
+  // k * z2[one]: the constant's value is ONE in every fresh instance, and then the small-integer conversion is all it takes --
+  // no Montgomery product (cross.cuh times_one; fe.cuh fe_from_small: ~50 instructions)
   const bool unit = fe_eq(onev, fe_one<P>());
-  auto times_one = [&](uint64_t k) -> Fe<P> {
-    const Fe<P> km = k < (1u << 30) ? fe_from_small<P>((uint32_t)k) : fe_from_u64<P>(k);
-    return unit ? km : fe_mul(km, onev);
-  };
   // The three kinds of row differ in WHERE their values sit, not in what is done with them: the addresses are selected
   // first and every load of the row is issued before the first use (a wavefront holds all three kinds: as branches they
   // would be three serial rounds of loads).  pa / pb / pc = the sources of A z2, B z2 and the first term of C z2.
@@ -512,11 +467,11 @@ __device__ __forceinline__ void minroot_stencil_row(const char* __restrict__ z2,
   a2 = fe_load<P>(pa); b2 = fe_load<P>(pb); c2 = fe_load<P>(pc);
   const Fe<P> y = fe_load<P>(yp);
   if (PER == 3 && j > 0) {                                          // the loaded value is y_(j-1): turn it into x_j
-    const Fe<P> xa = fe_add(fe_sub(role == 0 ? a2 : b2, i_in), times_one(j));
+    const Fe<P> xa = fe_add(fe_sub(role == 0 ? a2 : b2, i_in), times_one(j, unit, onev));
     if (role == 0) { a2 = xa; b2 = xa; } else if (role == 2) b2 = xa;
   }
-  if (role == 2) c2 = fe_add(fe_sub(fe_add(c2, y), i_in), times_one(j + 1));
-  if (role == 3) c2 = fe_sub(c2, times_one(t));
+  if (role == 2) c2 = fe_add(fe_sub(fe_add(c2, y), i_in), times_one(j + 1, unit, onev));
+  if (role == 3) c2 = fe_sub(c2, times_one(t, unit, onev));
 }
 
 template <class P, int PER>
@@ -531,13 +486,7 @@ __global__ __launch_bounds__(256) void k_nifs_cross_minroot(const char* __restri
   const Fe<P> a1 = fe_load<P>(az1 + r * 32), b1 = fe_load<P>(bz1 + r * 32), c1 = fe_load<P>(cz1 + r * 32);
   Fe<P> a2, b2, c2;
   minroot_stencil_row<P, PER>(z2, S, one_col, t, i, a2, b2, c2);
-  fe_store<P>(az2 + r * 32, a2);
-  fe_store<P>(bz2 + r * 32, b2);
-  fe_store<P>(cz2 + r * 32, c2);
-  Fe<P> tt = fe_add(fe_mul(a1, b2), fe_mul(a2, b1));
-  tt = fe_sub(tt, fe_mul(fe_from_val<P>(u1), c2));
-  tt = fe_sub(tt, c1);
-  fe_store<P>(T + r * 32, tt);
+  cross_finish<P>(az2, bz2, cz2, T, r, a1, b1, c1, fe_from_val<P>(u1), a2, b2, c2);
 }
 
 // The same for the FORWARD step circuit over L lanes in one launch (VDF_CIRCUIT_MINROOT_FORWARD: L = 1, and _LANES).  Lane
@@ -583,22 +532,12 @@ __global__ __launch_bounds__(256) void k_nifs_cross_minroot_forward_lanes(const 
   Fe<P> c2 = fe_load<P>(pc);
   const Fe<P> d = fe_load<P>(pd);
   const bool unit = fe_eq(onev, fe_one<P>());                        // ONE in every fresh instance: a uniform branch
-  auto times_one = [&](uint64_t k) -> Fe<P> {
-    const Fe<P> km = k < (1u << 30) ? fe_from_small<P>((uint32_t)k) : fe_from_u64<P>(k);
-    return unit ? km : fe_mul(km, onev);
-  };
   if (role == 2) {
     c2 = fe_add(c2, d);
-    if (j > 0) c2 = fe_add(fe_add(c2, i_in), times_one(j - 1));
+    if (j > 0) c2 = fe_add(fe_add(c2, i_in), times_one(j - 1, unit, onev));
   }
-  if (role == 3) c2 = fe_add(c2, times_one(t));
-  fe_store<P>(az2 + r * 32, a2);
-  fe_store<P>(bz2 + r * 32, b2);
-  fe_store<P>(cz2 + r * 32, c2);
-  Fe<P> tt = fe_add(fe_mul(a1, b2), fe_mul(a2, b1));
-  tt = fe_sub(tt, fe_mul(fe_from_val<P>(u1), c2));
-  tt = fe_sub(tt, c1);
-  fe_store<P>(T + r * 32, tt);
+  if (role == 3) c2 = fe_add(c2, times_one(t, unit, onev));
+  cross_finish<P>(az2, bz2, cz2, T, r, a1, b1, c1, fe_from_val<P>(u1), a2, b2, c2);
 }
 
 // y * r for a scalar r below 2^128 given as a PLAIN integer (four limbs), y and the result in Montgomery form: the fold
@@ -683,13 +622,7 @@ __global__ __launch_bounds__(256) void k_nifs_cross_minroot_fold(const char* __r
   fe_store<P>(az1 + r * 32, a1);
   fe_store<P>(bz1 + r * 32, b1);
   fe_store<P>(cz1 + r * 32, c1);
-  fe_store<P>(az2 + r * 32, a2);
-  fe_store<P>(bz2 + r * 32, b2);
-  fe_store<P>(cz2 + r * 32, c2);
-  Fe<P> tt = fe_add(fe_mul(a1, b2), fe_mul(a2, b1));
-  tt = fe_sub(tt, fe_mul(fe_from_val<P>(u1), c2));
-  tt = fe_sub(tt, c1);
-  fe_store<P>(T + r * 32, tt);
+  cross_finish<P>(az2, bz2, cz2, T, r, a1, b1, c1, fe_from_val<P>(u1), a2, b2, c2);
 }
 
 // acc_k <- acc_k + r * add_k for up to 8 vectors in one launch (the witness fold W, E and the running Az, Bz, Cz)
@@ -859,10 +792,8 @@ int nifs_cross_lanes(size_t rows) {
 // With `long_rowlist` (the distinct rows that have a matrix of more than VDF_LONG_ROW entries) the launch sums those rows
 // itself (k_nifs_cross_f; the caller checked nifs_cross_lanes(rows) == 8); without, vec_spmv_long ran before it.
 Status vec_nifs_cross(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3],
-                      const uint32_t* const coef[3], const void* dict, const void* z2, const void* az1, const void* bz1,
-                      const void* cz1, const vdf_fe* u1, size_t rows, size_t skip_begin, size_t skip_len,
-                      const uint32_t* long_rowlist, size_t n_long_rows, void* az2, void* bz2, void* cz2, void* T,
-                      double alg_bytes, hipStream_t s) {
+                      const uint32_t* const coef[3], const void* dict, const CrossOperands& o, size_t rows, size_t skip_begin,
+                      size_t skip_len, const uint32_t* long_rowlist, size_t n_long_rows, double alg_bytes, hipStream_t s) {
   if (rows == 0) return Status{};
   Csr3 m;
   for (int k = 0; k < 3; ++k) { m.rowptr[k] = rowptr[k]; m.col[k] = col[k]; m.coef[k] = coef[k]; }
@@ -873,30 +804,31 @@ Status vec_nifs_cross(int field, const uint32_t* const rowptr[3], const uint32_t
     const uint32_t long_wgs = (uint32_t)((n_long_rows + 3) / 4);
     const dim3 grid((unsigned)((rows + 31) / 32) + long_wgs);
     return with_field(field, [&](auto f) {
-      hipLaunchKernelGGL((k_nifs_cross_f<tag_t<decltype(f)>>), grid, dim3(256), 0, s, m, cbytes_of(dict), cbytes_of(z2), cbytes_of(az1), cbytes_of(bz1),
-                         cbytes_of(cz1), to_val(u1), rows, skip_begin, skip_len, long_rowlist, n_long_rows, long_wgs, bytes_of(az2), bytes_of(bz2),
-                         bytes_of(cz2), bytes_of(T));
+      hipLaunchKernelGGL((k_nifs_cross_f<tag_t<decltype(f)>>), grid, dim3(256), 0, s, m, cbytes_of(dict), cbytes_of(o.z2), cbytes_of(o.abc1[0]),
+                         cbytes_of(o.abc1[1]), cbytes_of(o.abc1[2]), to_val(o.u1), rows, skip_begin, skip_len, long_rowlist, n_long_rows, long_wgs,
+                         bytes_of(o.abc2[0]), bytes_of(o.abc2[1]), bytes_of(o.abc2[2]), bytes_of(o.T));
     });
   }
   KTimer kt(s, lpr == 1 ? "k_nifs_cross" : (lpr == 4 ? "k_nifs_cross_w4" : "k_nifs_cross_w8"), alg_bytes);
   if (lpr == 1)
     return with_field(field, [&](auto f) {
-      hipLaunchKernelGGL((k_nifs_cross<tag_t<decltype(f)>>), grid_for(rows), dim3(256), 0, s, m, cbytes_of(dict), cbytes_of(z2), cbytes_of(az1),
-                         cbytes_of(bz1), cbytes_of(cz1), to_val(u1), rows, skip_begin, skip_len, bytes_of(az2), bytes_of(bz2), bytes_of(cz2), bytes_of(T));
+      hipLaunchKernelGGL((k_nifs_cross<tag_t<decltype(f)>>), grid_for(rows), dim3(256), 0, s, m, cbytes_of(dict), cbytes_of(o.z2), cbytes_of(o.abc1[0]),
+                         cbytes_of(o.abc1[1]), cbytes_of(o.abc1[2]), to_val(o.u1), rows, skip_begin, skip_len, bytes_of(o.abc2[0]), bytes_of(o.abc2[1]),
+                         bytes_of(o.abc2[2]), bytes_of(o.T));
     });
   const dim3 grid((unsigned)((rows + 256 / lpr - 1) / (256 / lpr)));       // 64 rows of 4 lanes or 32 rows of 8 per workgroup
   return with_int<4, 8>(lpr, "lanes per row", [&](auto lanes) {
     return with_field(field, [&](auto f) {
-      hipLaunchKernelGGL((k_nifs_cross_w<tag_t<decltype(f)>, lanes.value>), grid, dim3(256), 0, s, m, cbytes_of(dict), cbytes_of(z2), cbytes_of(az1),
-                         cbytes_of(bz1), cbytes_of(cz1), to_val(u1), rows, skip_begin, skip_len, bytes_of(az2), bytes_of(bz2), bytes_of(cz2), bytes_of(T));
+      hipLaunchKernelGGL((k_nifs_cross_w<tag_t<decltype(f)>, lanes.value>), grid, dim3(256), 0, s, m, cbytes_of(dict), cbytes_of(o.z2), cbytes_of(o.abc1[0]),
+                         cbytes_of(o.abc1[1]), cbytes_of(o.abc1[2]), to_val(o.u1), rows, skip_begin, skip_len, bytes_of(o.abc2[0]), bytes_of(o.abc2[1]),
+                         bytes_of(o.abc2[2]), bytes_of(o.T));
     });
   });
 }
 
 static constexpr const char* BAD_PER = "variables per round must be 3 or 4";
-Status vec_nifs_cross_minroot(int field, int per, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
-                              const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, void* az2, void* bz2, void* cz2,
-                              void* T, hipStream_t s) {
+Status vec_nifs_cross_minroot(int field, int per, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const CrossOperands& o,
+                              hipStream_t s) {
   if (per != 3 && per != 4) return Status{VDF_ERR_BAD_ARG, BAD_PER};
   if (t == 0 || seg_begin < 3) return Status{VDF_ERR_BAD_ARG, "bad segment"};
   const size_t rows = 3 * (size_t)t + 1;
@@ -906,15 +838,15 @@ Status vec_nifs_cross_minroot(int field, int per, uint64_t t, size_t seg_begin, 
   const dim3 grid = grid_for(rows);
   return with_field(field, [&](auto f) {
     return with_int<4, 3>(per, BAD_PER, [&](auto perv) {
-      hipLaunchKernelGGL((k_nifs_cross_minroot<tag_t<decltype(f)>, perv.value>), grid, dim3(256), 0, s, cbytes_of(z2), seg_begin, one_col, t, row0,
-                         cbytes_of(az1), cbytes_of(bz1), cbytes_of(cz1), to_val(u1), bytes_of(az2), bytes_of(bz2), bytes_of(cz2), bytes_of(T));
+      hipLaunchKernelGGL((k_nifs_cross_minroot<tag_t<decltype(f)>, perv.value>), grid, dim3(256), 0, s, cbytes_of(o.z2), seg_begin, one_col, t, row0,
+                         cbytes_of(o.abc1[0]), cbytes_of(o.abc1[1]), cbytes_of(o.abc1[2]), to_val(o.u1), bytes_of(o.abc2[0]), bytes_of(o.abc2[1]),
+                         bytes_of(o.abc2[2]), bytes_of(o.T));
     });
   });
 }
 
-Status vec_nifs_cross_minroot_forward_lanes(int field, uint64_t t, size_t lanes, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
-                                            const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, void* az2, void* bz2,
-                                            void* cz2, void* T, hipStream_t s) {
+Status vec_nifs_cross_minroot_forward_lanes(int field, uint64_t t, size_t lanes, size_t seg_begin, size_t one_col, size_t row0,
+                                            const CrossOperands& o, hipStream_t s) {
   if (t == 0 || lanes == 0 || lanes > VDF_MINROOT_MAX_LANES || seg_begin < 3 * lanes) return Status{VDF_ERR_BAD_ARG, "bad segment"};
   const size_t rows = 3 * (size_t)t + 1;
   // priced as the inverse stencil is; the labels are short on purpose (a timed launch keeps 23 characters, and the fused inverse
@@ -922,9 +854,9 @@ Status vec_nifs_cross_minroot_forward_lanes(int field, uint64_t t, size_t lanes,
   KTimer kt(s, lanes == 1 ? "k_nifs_cross_fwd" : "k_nifs_cross_fwd_lanes", ((double)rows * 7 * 32 + 3.0 * t * 32) * lanes);
   const dim3 grid(grid_for(rows).x, (unsigned)lanes);
   return with_field(field, [&](auto f) {
-    hipLaunchKernelGGL((k_nifs_cross_minroot_forward_lanes<tag_t<decltype(f)>>), grid, dim3(256), 0, s, cbytes_of(z2), seg_begin, (uint32_t)lanes,
-                       one_col, t, row0, cbytes_of(az1), cbytes_of(bz1), cbytes_of(cz1), to_val(u1), bytes_of(az2), bytes_of(bz2), bytes_of(cz2),
-                       bytes_of(T));
+    hipLaunchKernelGGL((k_nifs_cross_minroot_forward_lanes<tag_t<decltype(f)>>), grid, dim3(256), 0, s, cbytes_of(o.z2), seg_begin, (uint32_t)lanes,
+                       one_col, t, row0, cbytes_of(o.abc1[0]), cbytes_of(o.abc1[1]), cbytes_of(o.abc1[2]), to_val(o.u1), bytes_of(o.abc2[0]),
+                       bytes_of(o.abc2[1]), bytes_of(o.abc2[2]), bytes_of(o.T));
   });
 }
 
@@ -933,9 +865,8 @@ template <class P> static bool plain_if_u128(const vdf_fe* r, FeVal& out) {
   Fe<P> t; memcpy(t.v, r, 32); t = fe_from_mont(t); memcpy(out.v, t.v, 32);
   return (out.v[4] | out.v[5] | out.v[6] | out.v[7]) == 0;
 }
-Status vec_nifs_cross_minroot_fold(int field, int per, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const void* z2,
-                                   const vdf_fe* r, void* az1, void* bz1, void* cz1, void* e1, const void* tprev, const vdf_fe* u1,
-                                   void* az2, void* bz2, void* cz2, void* T, hipStream_t s) {
+Status vec_nifs_cross_minroot_fold(int field, int per, uint64_t t, size_t seg_begin, size_t one_col, size_t row0, const vdf_fe* r,
+                                   void* const folded[3], void* e1, const void* tprev, const CrossOperands& o, hipStream_t s) {
   if (per != 3 && per != 4) return Status{VDF_ERR_BAD_ARG, BAD_PER};
   if (t == 0 || seg_begin < 3) return Status{VDF_ERR_BAD_ARG, "bad segment"};
   const size_t rows = 3 * (size_t)t + 1;
@@ -950,9 +881,9 @@ Status vec_nifs_cross_minroot_fold(int field, int per, uint64_t t, size_t seg_be
     const FeVal rv = small ? plain : to_val(r);
     return with_int<4, 3>(per, BAD_PER, [&](auto perv) {
       return with_bool(small, [&](auto u128) {
-        hipLaunchKernelGGL((k_nifs_cross_minroot_fold<P, perv.value, u128.value>), grid, dim3(256), 0, s, cbytes_of(z2), seg_begin, one_col, t, row0, rv,
-                           bytes_of(az1), bytes_of(bz1), bytes_of(cz1), bytes_of(e1), cbytes_of(tprev), to_val(u1), bytes_of(az2), bytes_of(bz2),
-                           bytes_of(cz2), bytes_of(T));
+        hipLaunchKernelGGL((k_nifs_cross_minroot_fold<P, perv.value, u128.value>), grid, dim3(256), 0, s, cbytes_of(o.z2), seg_begin, one_col, t, row0,
+                           rv, bytes_of(folded[0]), bytes_of(folded[1]), bytes_of(folded[2]), bytes_of(e1), cbytes_of(tprev), to_val(o.u1),
+                           bytes_of(o.abc2[0]), bytes_of(o.abc2[1]), bytes_of(o.abc2[2]), bytes_of(o.T));
       });
     });
   });
@@ -1053,13 +984,7 @@ __global__ __launch_bounds__(256) void k_relaxed_residual_batch(Csr3 m, const ch
         s[k] = fe_zero<P>();
         for (uint32_t e = lo[k] + lane; e < hi[k]; e += 64)
           s[k] = fe_add(s[k], spmv_term<P>(fe_load<P>(it.z + (size_t)m.col[k][e] * 32), m.coef[k][e], dict));
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-          Fe<P> o;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) o.v[i] = __shfl_xor(s[k].v[i], off, 64);
-          s[k] = fe_add(s[k], o);
-        }
+        s[k] = fe_group_sum<P, 64>(s[k]);
       }
       if (lane == 0) acc = fe_add(acc, residual_term<P>(s[0], s[1], s[2], it, r));
     }
@@ -1176,17 +1101,6 @@ static_assert(sizeof(EvalItem) == 80, "argument block layout");
 constexpr int SPARSE_EVAL_CHUNK = VDF_SPARSE_EVAL_CHUNK;
 static_assert(SPARSE_EVAL_CHUNK == 2 || SPARSE_EVAL_CHUNK == 4, "8 instances per pass spill");
 template <class P>
-__device__ __forceinline__ Fe<P> fe_wave_sum(Fe<P> a) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    Fe<P> o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o.v[i] = __shfl_xor(a.v[i], off, 64);
-    a = fe_add(a, o);
-  }
-  return a;
-}
-template <class P>
 __device__ __forceinline__ Fe<P> eval_term(const Fe<P>& ex, const Fe<P> s[3], const EvalItem& it) {
   Fe<P> rho, rho2;
 #pragma unroll
@@ -1279,7 +1193,7 @@ __global__ __launch_bounds__(256) void k_sparse_eval_multi(Csr3 m, const char* _
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       if (q0 + c >= count) continue;                                   // uniform
-      const Fe<P> t = fe_wave_sum<P>(acc[c]);
+      const Fe<P> t = fe_group_sum<P, 64>(acc[c]);
       if (lane == 0) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) red[wave][c][i] = t.v[i];
@@ -1306,7 +1220,7 @@ __global__ __launch_bounds__(64) void k_sparse_eval_sum(const char* __restrict__
   const uint32_t q = blockIdx.x, lane = threadIdx.x;
   Fe<P> acc = fe_zero<P>();
   for (uint32_t w = lane; w < nwg; w += 64) acc = fe_add(acc, fe_load<P>(partials + ((size_t)q * nwg + w) * 32));
-  acc = fe_wave_sum<P>(acc);
+  acc = fe_group_sum<P, 64>(acc);
   if (lane == 0) fe_store<P>(out + (size_t)q * 32, acc);
 }
 
