@@ -795,6 +795,20 @@ int  vdf_scale_pattern(vdf_ctx* ctx, int field, vdf_fe* s, size_t n, size_t nj, 
 int  vdf_fe_mul(vdf_ctx* ctx, int field, const vdf_fe* a, const vdf_fe* b, size_t n, vdf_fe* out);
 int  vdf_fe_to_mont(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, vdf_fe* out);
 int  vdf_fe_from_mont(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, vdf_fe* out);
+/* Element-wise square root, n elements (Montgomery in and out): out[i] is the root of a[i] whose canonical value is even
+ * (the convention of the generator families) and ok[i] = 1; for a non-residue ok[i] = 0 and out[i] = 0.  a = 0 has the
+ * root 0.  Tonelli-Shanks with every trip count fixed (both fields have 2-adicity 32): every lane runs the same number of
+ * products whatever its element.  Each array in host or device memory.  The root of vdf_points_decompress as a primitive of
+ * its own, so that every 2-adic depth can be tested: a random element reaches depth k with probability 2^(k-32). */
+int  vdf_fe_sqrt(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, vdf_fe* out, uint8_t* ok);
+/* n points from the wire's 32-byte encoding (vdf_nova.h: x little-endian, the parity of y in bit 255, 32 zero bytes the
+ * identity), one lane per point: ok[i] = 1 and out[i] = the point in Montgomery form, byte for byte what
+ * vdf_nova_point_decompress writes, exactly when that call returns VDF_OK for the 32 bytes; otherwise (x >= m after masking
+ * bit 255, zero bytes with the parity bit set, x^3 + 5 a non-residue) ok[i] = 0 and out[i] is zeroed.  The 32 zero bytes give
+ * the identity (0, 0) with ok[i] = 1.  enc: n x 32 bytes, no alignment asked; out: n points; ok: n bytes; each of the three in
+ * host or device memory (vdf_ptr_is_device).  The bytes are a peer's: no loop of the kernel depends on them.  n = 0 is VDF_OK
+ * and touches nothing. */
+int  vdf_points_decompress(vdf_ctx* ctx, int curve, const uint8_t* enc, size_t n, vdf_affine* out, uint8_t* ok);
 /* Throughput probe: each of n lanes runs `iters` dependent Montgomery multiplications
  * (roofline / issue-rate calibration for DESIGN.md; not on the prove path). */
 int  vdf_fe_mul_chain(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, int iters, vdf_fe* out);

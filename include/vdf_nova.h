@@ -927,6 +927,26 @@ int  vdf_nova_point_decompress(int curve, const uint8_t in[32], vdf_affine* out)
 size_t vdf_nova_snark_serialized_size(const vdf_snark* snark);
 int  vdf_nova_snark_serialize(const vdf_snark* snark, uint8_t* out, size_t cap);
 int  vdf_nova_snark_deserialize(vdf_pp* pp, const uint8_t* in, size_t len, vdf_snark** out);
+/* Many compressed proofs from their wire bytes under one parameter set, their points decoded on the device.  status[q] is exactly
+ * the code vdf_nova_snark_deserialize(pp, in[q], len[q], ..) returns for that entry alone (a null in[q]: VDF_ERR_BAD_ARG);
+ * out[q] is NULL unless status[q] == VDF_OK, and is then the object the single call makes (vdf_nova_snark_bytes and
+ * vdf_nova_snark_serialize give the same bytes; the caller frees it with vdf_nova_snark_free).  The host walks every encoding
+ * once -- magic, t, digest, length, the range of every field element -- and notes its point encodings; one
+ * vdf_points_decompress (vdf_hip.h) per curve then decodes the points of all entries that passed, and one wait follows.  An entry
+ * that failed a host check sends no point to the device, and no entry changes another's result.  The call returns VDF_OK when it
+ * ran, whatever the entries' codes; VDF_ERR_BAD_ARG for a null pp or (count > 0) a null array; a device failure is the call's
+ * own error and leaves every out[q] NULL.  count = 0 does nothing.  The single call decodes on the host, one square root per
+ * point: use it for one proof where no device wait is wanted, this one for many. */
+int  vdf_nova_snark_deserialize_batch(vdf_pp* pp, size_t count, const uint8_t* const in[], const size_t len[], vdf_snark* out[],
+                                      int status[]);
+/* A verifier that holds bytes only: vdf_nova_snark_deserialize_batch, then vdf_nova_verify_compressed_batch over the entries
+ * that decoded.  An entry that does not decode has ok[q] = 0 and its code in status[q] (VDF_OK for every entry that decoded,
+ * verified or not), and the others are verified as if it were absent: their verdicts are those of
+ * vdf_nova_verify_compressed_batch over handles made by vdf_nova_snark_deserialize.  num_steps: count values; z0, zi: count x
+ * arity elements, entry-major (those of an undecodable entry are not read).  *all_ok = 1 iff every entry decoded and verified;
+ * count = 0 gives *all_ok = 1.  A null pp, all_ok or (count > 0) array: VDF_ERR_BAD_ARG. */
+int  vdf_nova_verify_wire_batch(vdf_pp* pp, size_t count, const uint8_t* const in[], const size_t len[], const size_t num_steps[],
+                                const vdf_fe* z0, const vdf_fe* zi, int ok[], int status[], int* all_ok);
 size_t vdf_nova_proof_serialized_size(const vdf_proof* proof);
 int  vdf_nova_proof_serialize(const vdf_proof* proof, uint8_t* out, size_t cap);
 int  vdf_nova_proof_deserialize(vdf_pp* pp, const uint8_t* in, size_t len, vdf_proof** out);

@@ -126,6 +126,8 @@ PROTOTYPES = {
     "vdf_fe_mul": (_i, [_vp, _i, _vp, _vp, _sz, _vp]),
     "vdf_fe_to_mont": (_i, [_vp, _i, _vp, _sz, _vp]),
     "vdf_fe_from_mont": (_i, [_vp, _i, _vp, _sz, _vp]),
+    "vdf_fe_sqrt": (_i, [_vp, _i, _vp, _sz, _vp, _vp]),
+    "vdf_points_decompress": (_i, [_vp, _i, _vp, _sz, _vp, _vp]),
     "vdf_fe_mul_chain": (_i, [_vp, _i, _vp, _sz, _i, _vp]),
     "vdf_hip_tuning_get": (_i, [_vp]),
     "vdf_hip_tuning_set": (_i, [_vp]),

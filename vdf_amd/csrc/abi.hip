@@ -2225,6 +2225,30 @@ int vdf_fe_from_mont(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, vdf_fe*
   });
 }
 
+int vdf_fe_sqrt(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, vdf_fe* out, uint8_t* ok) {
+  return guarded(ctx, [&]() -> Status {
+    Staging st(ctx);
+    const void* da; void *dout, *dok;
+    VDF_TRY(st.in(a, n * 32, &da));
+    VDF_TRY(st.out(out, n * 32, &dout));
+    VDF_TRY(st.out(ok, n, &dok));
+    VDF_TRY(vdf::fe_sqrt_vec(field, da, n, dout, static_cast<uint8_t*>(dok), ctx->stream));
+    return st.finish();
+  });
+}
+
+int vdf_points_decompress(vdf_ctx* ctx, int curve, const uint8_t* enc, size_t n, vdf_affine* out, uint8_t* ok) {
+  return guarded(ctx, [&]() -> Status {
+    Staging st(ctx);
+    const void* denc; void *dout, *dok;
+    VDF_TRY(st.in(enc, n * 32, &denc));
+    VDF_TRY(st.out(out, n * 64, &dout));
+    VDF_TRY(st.out(ok, n, &dok));
+    VDF_TRY(vdf::points_decompress(curve, static_cast<const uint8_t*>(denc), n, dout, static_cast<uint8_t*>(dok), ctx->stream));
+    return st.finish();
+  });
+}
+
 int vdf_fe_mul_chain(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, int iters, vdf_fe* out) {
   return guarded(ctx, [&]() -> Status {
     Staging st(ctx);

@@ -1274,6 +1274,60 @@ int verify_multi_default() {
 
 }  // namespace vdfnova
 
+namespace {
+// ---- "VDFSNK03" read back: the one walk over the layout (include/vdf_nova.h) ----------------------------------------------------
+// What stands in front of the elements: length, magic, t, digest.  The codes are vdf_nova_snark_deserialize's.  *L: both layouts.
+int snark_wire_header(const vdf_pp* pp, const uint8_t* in, size_t len, Layout L[2]) {
+  if (len < 48 + statement_wire(pp->arity)) return fail(VDF_ERR_BAD_LENGTH, "encoding is shorter than its header");
+  if (memcmp(in, WIRE_MAGIC_SNARK, 8) != 0) return fail(VDF_ERR_BAD_ARG, "not this kind of encoding (magic)");
+  uint64_t t;
+  memcpy(&t, in + 8, 8);
+  if (t != pp->t || memcmp(in + 16, pp->digest, 32) != 0) return fail(VDF_ERR_BAD_ARG, "encoding was made under other public parameters");
+  L[0] = layout_of(pp->s[0]); L[1] = layout_of(pp->s[1]);
+  if (len != 48 + statement_wire(pp->arity) + spartan_wire_size(L[0]) + spartan_wire_size(L[1]))
+    return fail(VDF_ERR_BAD_LENGTH, "encoding has the wrong length for this shape");
+  return VDF_OK;
+}
+// Every element behind a header that passed: field elements are range-checked and converted here (*canonical), every point's 32
+// bytes go to point(enc, side, dst) with the place in the object they decode to -- the single call decodes them on the host as it
+// walks, the batch call notes them and decodes all entries' points on the device.  The object's vectors are sized before any
+// point is handed out and not again: dst stays valid for as long as the object does.
+template <class PointFn>
+std::unique_ptr<vdf_snark> snark_wire_walk(const vdf_pp* pp, const Layout L[2], const uint8_t* in, bool* canonical, PointFn&& point) {
+  std::unique_ptr<vdf_snark> s(new vdf_snark());
+  memcpy(&s->t, in + 8, 8);
+  s->field = pp->field;
+  memcpy(s->digest, pp->digest, 32);
+  const uint8_t* i = in + 48;
+  i = get_inst_points(i, &s->r_U1, pp->s[0], true, canonical, point);
+  i = get_inst_points(i, &s->r_U2, pp->s[1], true, canonical, point);
+  i = get_inst_points(i, &s->l_u2, pp->s[1], false, canonical, point);
+  point(i, pp->s[1], &s->T2); i += 32;
+  s->zi1.resize(pp->arity);
+  for (size_t k = 0; k < pp->arity; ++k, i += 32) *canonical &= wire_get_fe(i, *pp->s[0].F, &s->zi1[k]);
+  *canonical &= wire_get_fe(i, *pp->s[1].F, &s->zi2[0]); i += 32;
+  for (int side = 0; side < 2; ++side) {
+    const Field& F = *pp->s[side].F;
+    Spartan& p = s->sp[side];
+    spartan_resize(p, L[side]);
+    auto get = [&](Fe& v) { *canonical &= wire_get_fe(i, F, &v); i += 32; };
+    for (auto& ev : p.outer) for (Fe& v : ev) get(v);
+    for (Fe& v : p.claims) get(v);
+    for (auto& ev : p.inner) for (Fe& v : ev) get(v);
+    get(p.w_eval);
+    for (Ipa* ip : {&p.ipaW, &p.ipaE}) {
+      for (size_t j = 0; j < ip->L.size(); ++j) {
+        point(i, pp->s[side], &ip->L[j]);
+        point(i + 32, pp->s[side], &ip->R[j]);
+        i += 64;
+      }
+      for (Fe& v : ip->a) get(v);
+    }
+  }
+  return s;
+}
+}  // namespace
+
 extern "C" {
 
 // verification of the compressed proof (src/nova/proof.rs:383): the two output hashes, the last fold of the instances,
@@ -1510,49 +1564,125 @@ int vdf_nova_snark_deserialize(vdf_pp* pp, const uint8_t* in, size_t len, vdf_sn
   return nova_guard([&]() -> int {
     if (!pp || !in || !out) return fail(VDF_ERR_BAD_ARG, "null argument");
     *out = nullptr;
-    if (len < 48 + statement_wire(pp->arity)) return fail(VDF_ERR_BAD_LENGTH, "encoding is shorter than its header");
-    if (memcmp(in, WIRE_MAGIC_SNARK, 8) != 0) return fail(VDF_ERR_BAD_ARG, "not this kind of encoding (magic)");
-    uint64_t t;
-    memcpy(&t, in + 8, 8);
-    if (t != pp->t || memcmp(in + 16, pp->digest, 32) != 0) return fail(VDF_ERR_BAD_ARG, "encoding was made under other public parameters");
-    const Layout L[2] = {layout_of(pp->s[0]), layout_of(pp->s[1])};
-    if (len != 48 + statement_wire(pp->arity) + spartan_wire_size(L[0]) + spartan_wire_size(L[1]))
-      return fail(VDF_ERR_BAD_LENGTH, "encoding has the wrong length for this shape");
-    std::unique_ptr<vdf_snark> s(new vdf_snark());
-    s->t = t;
-    s->field = pp->field;
-    memcpy(s->digest, pp->digest, 32);
-    const uint8_t* i = in + 48;
+    Layout L[2];
+    { int rc = snark_wire_header(pp, in, len, L); if (rc != VDF_OK) return rc; }
     bool canonical = true, on_curve = true;
-    i = get_inst(i, &s->r_U1, pp->s[0], true, &canonical, &on_curve);
-    i = get_inst(i, &s->r_U2, pp->s[1], true, &canonical, &on_curve);
-    i = get_inst(i, &s->l_u2, pp->s[1], false, &canonical, &on_curve);
-    on_curve &= pt_decompress(i, *pp->s[1].Fb, &s->T2); i += 32;
-    s->zi1.resize(pp->arity);
-    for (size_t k = 0; k < pp->arity; ++k, i += 32) canonical &= wire_get_fe(i, *pp->s[0].F, &s->zi1[k]);
-    canonical &= wire_get_fe(i, *pp->s[1].F, &s->zi2[0]); i += 32;
-    for (int side = 0; side < 2; ++side) {
-      const Field& F = *pp->s[side].F;
-      const Field& Fb = *pp->s[side].Fb;
-      Spartan& p = s->sp[side];
-      spartan_resize(p, L[side]);
-      auto get = [&](Fe& v) { canonical &= wire_get_fe(i, F, &v); i += 32; };
-      for (auto& ev : p.outer) for (Fe& v : ev) get(v);
-      for (Fe& v : p.claims) get(v);
-      for (auto& ev : p.inner) for (Fe& v : ev) get(v);
-      get(p.w_eval);
-      for (Ipa* ip : {&p.ipaW, &p.ipaE}) {
-        for (size_t j = 0; j < ip->L.size(); ++j) {
-          on_curve &= pt_decompress(i, Fb, &ip->L[j]);
-          on_curve &= pt_decompress(i + 32, Fb, &ip->R[j]);
-          i += 64;
-        }
-        for (Fe& v : ip->a) get(v);
-      }
-    }
+    std::unique_ptr<vdf_snark> s = snark_wire_walk(pp, L, in, &canonical, [&](const uint8_t* enc, const Side& sd, Aff* dst) {
+      on_curve &= pt_decompress(enc, *sd.Fb, dst);
+    });
     if (!canonical) return fail(VDF_ERR_NONCANONICAL, "a field element of the encoding is not canonical");
     if (!on_curve) return fail(VDF_ERR_NONCANONICAL, "a point of the encoding does not decode to a curve point");
     *out = s.release();
+    return VDF_OK;
+  });
+}
+
+// Many encodings under one parameter set: the same header checks and the same walk per entry, the points of every entry that
+// passed them decoded by one vdf_points_decompress per curve (side 0's commitments lie on pp->s[0].curve, side 1's on the other)
+// on a pinned block the kernels read and write in place, one wait, and the points scattered to where the walk said they go.
+int vdf_nova_snark_deserialize_batch(vdf_pp* pp, size_t count, const uint8_t* const in[], const size_t len[], vdf_snark* out[],
+                                     int status[]) {
+  return nova_guard([&]() -> int {
+    if (!pp || (count && (!in || !len || !out || !status))) return fail(VDF_ERR_BAD_ARG, "null argument");
+    for (size_t q = 0; q < count; ++q) out[q] = nullptr;
+    struct WirePoint { const uint8_t* enc; Aff* dst; size_t entry; };
+    std::vector<WirePoint> pts[2];
+    std::vector<std::unique_ptr<vdf_snark>> made(count);
+    for (size_t q = 0; q < count; ++q) {
+      if (!in[q]) { status[q] = fail(VDF_ERR_BAD_ARG, "null argument"); continue; }
+      Layout L[2];
+      status[q] = snark_wire_header(pp, in[q], len[q], L);
+      if (status[q] != VDF_OK) continue;
+      const size_t mark[2] = {pts[0].size(), pts[1].size()};
+      bool canonical = true;
+      made[q] = snark_wire_walk(pp, L, in[q], &canonical, [&](const uint8_t* enc, const Side& sd, Aff* dst) {
+        pts[&sd - pp->s].push_back({enc, dst, q});
+      });
+      if (!canonical) {                                  // it leaves with its points: they are not decoded
+        status[q] = fail(VDF_ERR_NONCANONICAL, "a field element of the encoding is not canonical");
+        made[q].reset();
+        pts[0].resize(mark[0]); pts[1].resize(mark[1]);
+      }
+    }
+    const size_t n[2] = {pts[0].size(), pts[1].size()}, total = n[0] + n[1];
+    if (total) {
+      vdf_ctx* ctx = pp->ctx;
+      // [enc: 32 total | points: 64 total | ok: total], side 0's share of each first
+      void* blk = nullptr;
+      HIPCALL(ctx, vdf_host_alloc(ctx, 97 * total, &blk));
+      struct Free { vdf_ctx* c; void* p; ~Free() { vdf_host_free(c, p); } } free_blk{ctx, blk};
+      uint8_t* enc = static_cast<uint8_t*>(blk);
+      vdf_affine* dec = reinterpret_cast<vdf_affine*>(enc + 32 * total);
+      uint8_t* good = enc + 96 * total;
+      {
+        uint8_t* e = enc;
+        for (int side = 0; side < 2; ++side)
+          for (const WirePoint& w : pts[side]) { memcpy(e, w.enc, 32); e += 32; }
+      }
+      {
+        int was_async = 0;
+        HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
+        HIPCALL(ctx, vdf_ctx_set_async(ctx, 1));
+        struct Restore { vdf_ctx* c; int a; ~Restore() { vdf_ctx_sync(c); vdf_ctx_set_async(c, a); } } restore{ctx, was_async};
+        for (int side = 0; side < 2; ++side) {
+          const size_t at = side ? n[0] : 0;
+          HIPCALL(ctx, vdf_points_decompress(ctx, pp->s[side].curve, enc + 32 * at, n[side], dec + at, good + at));
+        }
+        HIPCALL(ctx, vdf_ctx_sync(ctx));
+      }
+      size_t k = 0;
+      for (int side = 0; side < 2; ++side)
+        for (const WirePoint& w : pts[side])
+          if (!good[k++] && made[w.entry]) {
+            status[w.entry] = fail(VDF_ERR_NONCANONICAL, "a point of the encoding does not decode to a curve point");
+            made[w.entry].reset();
+          }
+      k = 0;
+      for (int side = 0; side < 2; ++side)
+        for (const WirePoint& w : pts[side]) {
+          if (made[w.entry]) memcpy(w.dst, &dec[k], sizeof(Aff));
+          ++k;
+        }
+    }
+    for (size_t q = 0; q < count; ++q) out[q] = made[q].release();
+    return VDF_OK;
+  });
+}
+
+// Bytes in, verdicts out: vdf_nova_snark_deserialize_batch, then vdf_nova_verify_compressed_batch over the entries that decoded.
+int vdf_nova_verify_wire_batch(vdf_pp* pp, size_t count, const uint8_t* const in[], const size_t len[], const size_t num_steps[],
+                               const vdf_fe* z0, const vdf_fe* zi, int ok[], int status[], int* all_ok) {
+  return nova_guard([&]() -> int {
+    if (!pp || !all_ok) return fail(VDF_ERR_BAD_ARG, "null argument");
+    *all_ok = 0;
+    if (count == 0) { *all_ok = 1; return VDF_OK; }
+    if (!in || !len || !num_steps || !z0 || !zi || !ok || !status) return fail(VDF_ERR_BAD_ARG, "null argument");
+    for (size_t q = 0; q < count; ++q) ok[q] = 0;
+    struct Handles {
+      std::vector<vdf_snark*> v;
+      ~Handles() { for (vdf_snark* s : v) delete s; }
+    } hs{std::vector<vdf_snark*>(count, nullptr)};
+    { int rc = vdf_nova_snark_deserialize_batch(pp, count, in, len, hs.v.data(), status); if (rc != VDF_OK) return rc; }
+    const size_t ar = pp->arity;
+    std::vector<size_t> live, steps;
+    std::vector<const vdf_snark*> snarks;
+    std::vector<vdf_fe> lz0, lzi;
+    for (size_t q = 0; q < count; ++q) {
+      if (!hs.v[q]) continue;
+      live.push_back(q);
+      snarks.push_back(hs.v[q]);
+      steps.push_back(num_steps[q]);
+      lz0.insert(lz0.end(), z0 + q * ar, z0 + (q + 1) * ar);
+      lzi.insert(lzi.end(), zi + q * ar, zi + (q + 1) * ar);
+    }
+    std::vector<int> okl(live.size(), 0);
+    int all = 1;
+    if (!live.empty()) {
+      int rc = vdf_nova_verify_compressed_batch(pp, live.size(), snarks.data(), steps.data(), lz0.data(), lzi.data(), okl.data(), &all);
+      if (rc != VDF_OK) return rc;
+    }
+    for (size_t k = 0; k < live.size(); ++k) ok[live[k]] = okl[k];
+    *all_ok = (all && live.size() == count) ? 1 : 0;
     return VDF_OK;
   });
 }

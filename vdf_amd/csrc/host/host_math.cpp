@@ -133,7 +133,10 @@ bool fe_sqrt(const Fe& a, const Field& F, Fe* out) {
   if (a.is_zero()) { *out = a; return true; }
   uint64_t T[4] = {(F.m[0] >> 32) | (F.m[1] << 32), (F.m[1] >> 32) | (F.m[2] << 32), (F.m[2] >> 32) | (F.m[3] << 32), F.m[3] >> 32};
   uint64_t Th[4] = {(T[0] >> 1) | (T[1] << 63), (T[1] >> 1) | (T[2] << 63), (T[2] >> 1) | (T[3] << 63), T[3] >> 1};   // (T - 1) / 2
-  Fe z = pow_vartime(from_u64(5, F), T, F);
+  // z = 5^T from the table the device reads (pasta_constants.h TS_Z, Montgomery form): it was a 222-bit power on every call
+  const uint32_t* tz = F.m[0] == field_fp().m[0] ? FpParams::TS_Z : FqParams::TS_Z;
+  Fe z;
+  for (int k = 0; k < 4; ++k) z.l[k] = (uint64_t)tz[2 * k] | ((uint64_t)tz[2 * k + 1] << 32);
   const Fe w = pow_vartime(a, Th, F);
   Fe x = mul(a, w, F);            // a^((T+1)/2)
   Fe b = mul(x, w, F);            // a^T

@@ -342,10 +342,13 @@ inline uint8_t* put_inst(uint8_t* o, const Inst& in, const Side& sd, bool relaxe
   for (int k = 0; k < NUM_IO; ++k) o = wire_put_fe(o, in.X[k], *sd.F);
   return o;
 }
-inline const uint8_t* get_inst(const uint8_t* i, Inst* in, const Side& sd, bool relaxed, bool* canonical, bool* on_curve) {
-  *on_curve &= pt_decompress(i, *sd.Fb, &in->comm_W); i += 32;
+// point(enc, sd, dst): what becomes of a 32-byte point encoding of side sd -- decoded on the spot (get_inst below), or noted for
+// a batch that decodes every entry's points in one launch per curve (compress_host.cpp)
+template <class PointFn>
+inline const uint8_t* get_inst_points(const uint8_t* i, Inst* in, const Side& sd, bool relaxed, bool* canonical, PointFn&& point) {
+  point(i, sd, &in->comm_W); i += 32;
   if (relaxed) {
-    *on_curve &= pt_decompress(i, *sd.Fb, &in->comm_E); i += 32;
+    point(i, sd, &in->comm_E); i += 32;
     *canonical &= wire_get_fe(i, *sd.F, &in->u); i += 32;
   } else {
     memset(&in->comm_E, 0, sizeof(Aff));
@@ -353,6 +356,10 @@ inline const uint8_t* get_inst(const uint8_t* i, Inst* in, const Side& sd, bool 
   }
   for (int k = 0; k < NUM_IO; ++k) { *canonical &= wire_get_fe(i, *sd.F, &in->X[k]); i += 32; }
   return i;
+}
+inline const uint8_t* get_inst(const uint8_t* i, Inst* in, const Side& sd, bool relaxed, bool* canonical, bool* on_curve) {
+  return get_inst_points(i, in, sd, relaxed, canonical,
+                         [&](const uint8_t* enc, const Side& s, Aff* dst) { *on_curve &= pt_decompress(enc, *s.Fb, dst); });
 }
 constexpr size_t INST_WIRE_RELAXED = 32 * 5, INST_WIRE_STRICT = 32 * 3;
 }  // namespace vdfnova

@@ -305,6 +305,10 @@ Status point_sum(int curve, const void* d_jac, size_t n, void* d_out, hipStream_
 Status bases_validate(int curve, const void* d_pts, size_t n, uint32_t* d_flags, hipStream_t stream);   // d_flags: 2 words
 Status bases_precompute(int curve, const void* d_pts, size_t n, int c, int sets, int tables, void* d_table,
                         hipStream_t stream);
+// the even square root of n elements (d_ok[i] = 0 and a zero for a non-residue), and n points from their 32-byte wire
+// encoding (d_ok[i] = 0 and a zeroed point for bytes that decode to none): every lane runs the same number of products
+Status fe_sqrt_vec(int field, const void* d_a, size_t n, void* d_out, uint8_t* d_ok, hipStream_t stream);
+Status points_decompress(int curve, const uint8_t* d_enc, size_t n, void* d_out, uint8_t* d_ok, hipStream_t stream);
 
 // ---- vecops.hip ------------------------------------------------------------------------
 Status vec_axpy(int field, const void* a, const void* r, const void* b, size_t n, void* out, hipStream_t s);

@@ -1370,6 +1370,89 @@ __global__ __launch_bounds__(256) void k_validate_points(const char* __restrict_
   if (bad) { atomicOr(&flags[0], bad); atomicMin(&flags[1], i); }
 }
 
+// ---- points from the wire: the 32-byte encoding decoded one lane per point (vdf_points_decompress) ---------------------------
+// The input is whatever a peer sent, so nothing here loops on the data: Tonelli-Shanks with every trip count fixed.  With
+// m - 1 = 2^32 T, w = a^((T-1)/2), x = a w, b = x w = a^T and z = 5^T (order 2^32), x^2 = a b holds throughout; going into
+// round v (31 .. 1) the order of b divides 2^v when a is a square, and z has order 2^(v+1).  b^(2^(v-1)) is then 1 or -1; where
+// it is -1, x takes a factor z and b a factor z^2, which halves b's order; z is squared either way.  After round 1, b = 1 and
+// x^2 = a.  A non-residue starts with b of order 2^32 and cannot end there: the closing x^2 == a is the one test of residuosity,
+// for every input.  a = 0 gives x = 0 and ok.  About 265 products for w (a 222-bit exponent), 558 for the rounds (v + 2 in round
+// v) and one for the closing test, the same in every lane:
+// a wavefront of fe_sqrt (above) lasts as long as its deepest lane, and a non-residue is the deepest there is.
+template <class P>
+__device__ bool fe_sqrt_fixed(const Fe<P>& a, Fe<P>& root) {
+  uint32_t e[8];
+  Fe<P> z;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { e[i] = P::TS_EXP[i]; z.v[i] = P::TS_Z[i]; }
+  const Fe<P> w = fe_pow(a, e);
+  Fe<P> x = fe_mul(a, w);
+  Fe<P> b = fe_mul(x, w);
+  const Fe<P> one = fe_one<P>();
+  for (int v = 31; v >= 1; --v) {
+    Fe<P> t = b;
+    for (int k = 1; k < v; ++k) t = fe_sqr(t);
+    const Fe<P> xz = fe_mul(x, z);
+    z = fe_sqr(z);
+    const Fe<P> bz = fe_mul(b, z);
+    const bool take = !fe_eq(t, one);
+#pragma unroll
+    for (int l = 0; l < 8; ++l) { x.v[l] = take ? xz.v[l] : x.v[l]; b.v[l] = take ? bz.v[l] : b.v[l]; }
+  }
+  root = x;
+  return fe_eq(fe_sqr(x), a);
+}
+
+// out[i] = the root of a[i] whose canonical value is even, ok[i] = 1; a non-residue: out[i] = 0, ok[i] = 0
+template <class P>
+__global__ __launch_bounds__(256) void k_fe_sqrt(const char* __restrict__ a, uint32_t n, char* __restrict__ out, uint8_t* __restrict__ ok) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  Fe<P> y;
+  const bool good = fe_sqrt_fixed(fe_load<P>(a + (size_t)i * 32), y);
+  if (!good) y = fe_zero<P>();
+  else if (fe_from_mont(y).v[0] & 1u) y = fe_neg(y);
+  fe_store<P>(out + (size_t)i * 32, y);
+  ok[i] = good ? 1 : 0;
+}
+
+// enc: n x 32 bytes, x little-endian with the parity of y in bit 255 (host/host_math.cpp pt_decompress is the statement this
+// repeats, rule for rule); out: n affine points in Montgomery form, zeroed where ok[i] = 0.  The bytes are read one by one
+// unless the array is 16-byte aligned (the same for every lane): a caller's slice of a received buffer has no alignment.
+template <class P>
+__global__ __launch_bounds__(256) void k_points_decompress(const uint8_t* __restrict__ enc, uint32_t n, char* __restrict__ out,
+                                                            uint8_t* __restrict__ ok) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* in = enc + (size_t)i * 32;
+  Fe<P> x;
+  if ((reinterpret_cast<uintptr_t>(enc) & 15) == 0) x = fe_load<P>(in);
+  else
+#pragma unroll
+    for (int l = 0; l < 8; ++l)
+      x.v[l] = (uint32_t)in[4 * l] | ((uint32_t)in[4 * l + 1] << 8) | ((uint32_t)in[4 * l + 2] << 16) | ((uint32_t)in[4 * l + 3] << 24);
+  const uint32_t odd = x.v[7] >> 31;
+  x.v[7] &= 0x7FFFFFFFu;
+  const bool canonical = fe_is_canonical(x), zero = fe_is_zero(x);
+  Fe<P> five;
+#pragma unroll
+  for (int l = 0; l < 8; ++l) five.v[l] = P::FIVE[l];
+  // a lane whose x is refused or zero runs the root of 5 all the same: the wavefront's time does not depend on the bytes
+  Affine<P> a;
+  a.x = fe_to_mont(canonical ? x : fe_zero<P>());
+#ifdef VDF_POINTS_SQRT_VARTIME      // make ab AB_FLAGS=-DVDF_POINTS_SQRT_VARTIME: the generators' data-dependent root, to time against
+  a.y = fe_zero<P>();
+  const bool residue = fe_sqrt(fe_add(fe_mul(fe_sqr(a.x), a.x), five), a.y);
+#else
+  const bool residue = fe_sqrt_fixed(fe_add(fe_mul(fe_sqr(a.x), a.x), five), a.y);
+#endif
+  if ((fe_from_mont(a.y).v[0] & 1u) != odd) a.y = fe_neg(a.y);
+  const bool good = canonical && (zero ? !odd : residue);           // the identity has one encoding: 32 zero bytes
+  if (!good || zero) { a.x = fe_zero<P>(); a.y = fe_zero<P>(); }
+  affine_store<P>(out + (size_t)i * 64, a);
+  ok[i] = good ? 1 : 0;
+}
+
 // ---- the curves' endomorphism for the table-less path (vdf_hip_tuning.glv) --------------------------------------------
 // y^2 = x^3 + 5 has phi(x, y) = (zeta x, y) = [lambda] (x, y) with zeta, lambda primitive cube roots of unity in the base and
 // scalar field.  k = k1 + lambda k2 with |k1|, |k2| < 2^129 (pasta_constants.h: the lattice and its rounding constants), so
@@ -1715,6 +1798,26 @@ Status bases_validate(int curve, const void* d_pts, size_t n, uint32_t* d_flags,
   if (n == 0) return Status{};
   return with_curve(curve, [&](auto base, auto) {
     hipLaunchKernelGGL((k_validate_points<tag_t<decltype(base)>>), grid_for(n), dim3(256), 0, stream, cbytes_of(d_pts), (uint32_t)n, d_flags);
+  });
+}
+
+Status fe_sqrt_vec(int field, const void* d_a, size_t n, void* d_out, uint8_t* d_ok, hipStream_t stream) {
+  VDF_TRY(check_field(field));
+  if (n == 0) return Status{};
+  if (n > 0xFFFFFFFFull) return Status{VDF_ERR_BAD_LENGTH, "at most 2^32 - 1 elements per call"};
+  KTimer kt(stream, "k_fe_sqrt", 65.0 * n);
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_fe_sqrt<tag_t<decltype(f)>>), grid_for(n), dim3(256), 0, stream, cbytes_of(d_a), (uint32_t)n, bytes_of(d_out), d_ok);
+  });
+}
+
+Status points_decompress(int curve, const uint8_t* d_enc, size_t n, void* d_out, uint8_t* d_ok, hipStream_t stream) {
+  VDF_TRY(check_curve(curve));
+  if (n == 0) return Status{};
+  if (n > 0xFFFFFFFFull) return Status{VDF_ERR_BAD_LENGTH, "at most 2^32 - 1 points per call"};
+  KTimer kt(stream, "k_points_decompress", 97.0 * n);
+  return with_curve(curve, [&](auto base, auto) {
+    hipLaunchKernelGGL((k_points_decompress<tag_t<decltype(base)>>), grid_for(n), dim3(256), 0, stream, d_enc, (uint32_t)n, bytes_of(d_out), d_ok);
   });
 }
 

@@ -759,6 +759,16 @@ class Context:
     def fe_from_mont(self, field, a, n, out) -> None:
         self._check(lib.vdf_fe_from_mont(self.handle, field, _ptr(a), n, _ptr(out)))
 
+    def fe_sqrt(self, field, a, n, out, ok) -> None:
+        """vdf_fe_sqrt: out[i] = the root of a[i] whose canonical value is even and ok[i] = 1, or zero and ok[i] = 0 for a
+        non-residue; a, out: (n, 4) uint64 Montgomery limbs, ok: n uint8; numpy arrays or device tensors, each on its own."""
+        self._check(lib.vdf_fe_sqrt(self.handle, field, _ptr(a), n, _ptr(out), _ptr(ok)))
+
+    def points_decompress(self, curve, enc, n, out, ok) -> None:
+        """vdf_points_decompress: n points from their 32-byte wire encodings; enc: n x 32 uint8, out: (n, 8) uint64 Montgomery
+        limbs (x, y), ok: n uint8 (0: the bytes decode to no point, out zeroed); numpy arrays or device tensors, each on its own."""
+        self._check(lib.vdf_points_decompress(self.handle, curve, _ptr(enc), n, _ptr(out), _ptr(ok)))
+
     def clock_probe(self, iters: int = 6000):
         """(shader MHz sustained under a multiply-bound load on every SIMD, the probe kernel's duration in ms)."""
         mhz, ms = C.c_double(), C.c_double()

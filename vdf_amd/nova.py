@@ -125,6 +125,9 @@ for _name, _res, _args in [
     ("vdf_nova_snark_serialized_size", _sz, [_vp]),
     ("vdf_nova_snark_serialize", _i, [_vp, _vp, _sz]),
     ("vdf_nova_snark_deserialize", _i, [_vp, _vp, _sz, C.POINTER(_vp)]),
+    ("vdf_nova_snark_deserialize_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_i)]),
+    ("vdf_nova_verify_wire_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz), _vp, _vp, C.POINTER(_i), C.POINTER(_i),
+                                        C.POINTER(_i)]),
     ("vdf_nova_proof_serialized_size", _sz, [_vp]),
     ("vdf_nova_proof_serialize", _i, [_vp, _vp, _sz]),
     ("vdf_nova_proof_deserialize", _i, [_vp, _vp, _sz, C.POINTER(_vp)]),
@@ -1707,6 +1710,49 @@ def verify_compressed_batch(pp: NovaVDFPublicParams, items: Sequence[tuple]) -> 
     all_ok = C.c_int(0)
     _check(nova_lib.vdf_nova_verify_compressed_batch(pp.handle, n, snarks, steps, z0, zi, ok, C.byref(all_ok)))
     return [bool(ok[q]) for q in range(n)]
+
+
+def _blob_arrays(blobs):
+    """(keep-alive buffers, const uint8_t* const in[], size_t len[]) of a list of byte strings"""
+    n = len(blobs)
+    bufs = [(C.c_uint8 * max(len(b), 1)).from_buffer_copy(bytes(b) or b"\0") for b in blobs]
+    ins = (_vp * max(n, 1))(*[C.addressof(b) for b in bufs])
+    lens = (_sz * max(n, 1))(*[len(b) for b in blobs])
+    return bufs, ins, lens
+
+
+def deserialize_compressed_batch(pp: NovaVDFPublicParams, blobs: Sequence[bytes]) -> list:
+    """Many compressed proofs from their wire bytes, their points decoded on the device (vdf_nova_snark_deserialize_batch):
+    [(proof | None, status)] per blob, status the code CompressedNovaVDFProof.deserialize would raise for that blob alone
+    (vdf_amd.OK = 0 with the proof)."""
+    n = len(blobs)
+    bufs, ins, lens = _blob_arrays(blobs)
+    out = (_vp * max(n, 1))()
+    status = (_i * max(n, 1))()
+    _check(nova_lib.vdf_nova_snark_deserialize_batch(pp.handle, n, ins, lens, out, status))
+    return [(CompressedNovaVDFProof(out[q], pp) if out[q] else None, int(status[q])) for q in range(n)]
+
+
+def verify_wire_batch(pp: NovaVDFPublicParams, items: Sequence[tuple]) -> list:
+    """Bytes in, verdicts out (vdf_nova_verify_wire_batch): items = [(blob, num_steps, z0, zi), ...]; [(ok, status)] per item.
+    A blob that does not decode has ok = False and its code; the others' verdicts are those of verify_compressed_batch over
+    singly deserialised proofs, as if that blob were absent."""
+    n = len(items)
+    arity = getattr(pp, "arity", 3)
+    for it in items:
+        if len(it[2]) != arity or len(it[3]) != arity:
+            raise ValueError(f"z0 and zi need {arity} elements each")
+    bufs, ins, lens = _blob_arrays([it[0] for it in items])
+    steps = (_sz * max(n, 1))(*[int(it[1]) for it in items])
+    z0 = _zn([v for it in items for v in it[2]] or [bytes(32)])
+    zi = _zn([v for it in items for v in it[3]] or [bytes(32)])
+    ok = (_i * max(n, 1))()
+    status = (_i * max(n, 1))()
+    all_ok = C.c_int(0)
+    _check(nova_lib.vdf_nova_verify_wire_batch(pp.handle, n, ins, lens, steps, z0, zi, ok, status, C.byref(all_ok)))
+    res = [(bool(ok[q]), int(status[q])) for q in range(n)]
+    assert bool(all_ok.value) == all(o for o, _ in res)
+    return res
 
 
 def verify_batch(pp: NovaVDFPublicParams, items: Sequence[tuple]) -> list:
