@@ -404,26 +404,48 @@ int  vdf_minroot_forward_segment_lanes(vdf_ctx* ctx, int field, const vdf_fe* tr
  *                   Montgomery form).  Forward walk tapes only (below): anywhere else it is a malformed op
  *   VDF_TAPE_POWC   slot[dst] = slot[a] ^ E(chain), the chain a caller-supplied addition chain that lies in the constants from
  *                   consts[b] on (vdf_pow_step below).  Forward walk tapes only, like VDF_TAPE_POW
+ *   VDF_TAPE_TAB    slot[dst] = table[(J mod tab_rows) * tab_cols + a]: the round constant of round J from the tape's TABLE, a
+ *                   short list cycled over the rounds.  J is the 64-bit value VDF_TAPE_J has in that round (already reduced
+ *                   modulo 2^64 by the call's J rule), so the row is exactly J mod tab_rows for any tab_rows, a power of two
+ *                   or not, also where a walk's J crosses 2^64.  a < tab_cols, b = 0.  Valid in round, walk and forward walk
+ *                   tapes alike; it counts no product.  In a tape with tab_rows = 0 it is a malformed op
+ * THE TABLE: one per tape, tab_rows x tab_cols elements (at most VDF_TAPE_MAX_TAB_ROWS x VDF_TAPE_MAX_TAB_COLS: 1 MiB), row-major,
+ * canonical Montgomery form; tab_rows = tab_cols = 0 and table = NULL for a tape without one.  Unlike ops and consts it does NOT
+ * travel in the kernel arguments (it would not fit, and a lane's row is a per-lane value: arguments indexed by one would go to
+ * scratch): for the six launchers of this header `table` is memory a kernel may read in place, as advice and entries are --
+ * vdf_dev_alloc or vdf_host_alloc, checked with vdf_ptr_is_device; for the host evaluators of vdf_nova.h it is host memory.  A TAB
+ * is a per-lane 32-byte load from it.  Nothing on the device can index out of range: the row is below tab_rows by construction
+ * and the column is checked before the launch.  A tape that holds a TAB launches kernels of its own (k_round_tape_tab,
+ * k_round_tape_lanes_tab, k_tape_walk_tab, k_tape_walk_lanes_tab, k_tape_forward_walk_tab); every other tape launches the kernels
+ * it always did.  Refused with VDF_ERR_BAD_ARG naming the op: a TAB with tab_rows = 0, a >= tab_cols or b != 0; and naming the
+ * table: one dimension 0 beside a non-zero one, a cap exceeded, a null table with tab_rows > 0.
+ * THE STRUCT GREW at its end by table, tab_rows, tab_cols (vdf_version r2): callers are rebuilt, and one that fills the struct
+ * field by field sets the three to 0.
  * advice: (t + 1) entries of n_adv elements, entry-major (a MinRoot trace is n_adv = 2).  A slot is read only after an op of
  * the same tape wrote it (refused otherwise) and every variable is written exactly once.  n_cons, the constraints per
  * repetition, is carried for the caller (constraints cost nothing here).  The caps below are refused with VDF_ERR_BAD_ARG. */
 enum { VDF_TAPE_ADV = 0, VDF_TAPE_INV = 1, VDF_TAPE_J = 2, VDF_TAPE_CONST = 3, VDF_TAPE_ADD = 4, VDF_TAPE_SUB = 5, VDF_TAPE_MUL = 6,
-       VDF_TAPE_SCALE = 7, VDF_TAPE_OUT = 8, VDF_TAPE_POW = 9, VDF_TAPE_POWC = 10 };
+       VDF_TAPE_SCALE = 7, VDF_TAPE_OUT = 8, VDF_TAPE_POW = 9, VDF_TAPE_POWC = 10, VDF_TAPE_TAB = 11 };
 #define VDF_TAPE_MAX_OPS 320      /* ops of a tape (loads and stores included) */
 #define VDF_TAPE_MAX_CONSTS 24
 #define VDF_TAPE_MAX_SLOTS 24     /* live values: 2 KiB of LDS each per 64 repetitions */
 #define VDF_TAPE_MAX_VARS 64      /* variables per repetition */
 #define VDF_TAPE_MAX_INV 16
 #define VDF_TAPE_MAX_ADV 8
+#define VDF_TAPE_MAX_TAB_ROWS 4096
+#define VDF_TAPE_MAX_TAB_COLS 8
 typedef struct vdf_tape_op { uint8_t op, dst, a, b; } vdf_tape_op;
 typedef struct vdf_round_tape {
   const vdf_tape_op* ops;  size_t n_ops;       /* host memory */
   const vdf_fe* consts;    size_t n_consts;    /* host memory, Montgomery form */
   uint32_t n_slots, n_vars, n_cons, n_inv, n_adv;
+  const vdf_fe* table;                         /* VDF_TAPE_TAB's table (above): device-readable for the launchers, host for vdf_nova.h's evaluators */
+  uint32_t tab_rows, tab_cols;
 } vdf_round_tape;
 /* Runs the tape over repetitions 0 .. t - 1: out (device, t * n_vars elements) gets the variables, repetition-major.  inv: n_inv
  * elements in HOST memory; tape: host memory -- both travel as kernel arguments (no staging copy, no synchronisation).  advice:
- * device memory.  Values are whatever the ops make of the advice: nothing is checked against a constraint. */
+ * device memory; tape->table (if any): device-readable memory, "a device pointer where host memory is read or the reverse"
+ * otherwise, in all six launchers.  Values are whatever the ops make of the advice: nothing is checked against a constraint. */
 int  vdf_round_tape_run(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uint64_t t, const vdf_fe* inv, const vdf_fe* advice,
                         vdf_fe* out);
 /* The same for `lanes` advice arrays at once, ONE launch (kernel k_round_tape_lanes, the lane in the grid's second dimension):

@@ -511,6 +511,30 @@ int     vdf_cs_repeat(vdf_cs* cs, const vdf_round_body* b, uint64_t t, const vdf
 int     vdf_cs_repeat_lanes(vdf_cs* cs, const vdf_round_body* b, uint64_t t, size_t lanes, const vdf_num* inv, const vdf_num* carry_in,
                             const vdf_fe* advice, size_t lane_stride, vdf_num* carry_out);
 vdf_num vdf_cs_alloc_from(vdf_cs* cs, vdf_num src);                    /* a new variable with src's value, no constraint */
+/* THE ROUND CONSTANT OF ROUND j FROM A TABLE (vdf_hip.h VDF_TAPE_TAB).  vdf_cs_tab(cs, table, rows, cols, col) = table[(j mod rows)
+ * * cols + col], j the counter the body was handed: a short fixed list cycled over the rounds, as VeeDo / MiMC-style roots and
+ * Rescue- or Poseidon-shaped rounds add one; a 0 / 1 column switches a term on and off by round.  table: rows x cols elements,
+ * row-major, canonical Montgomery form, HOST memory, 1 <= rows <= VDF_TAPE_MAX_TAB_ROWS, 1 <= cols <= VDF_TAPE_MAX_TAB_COLS, col <
+ * cols.  Legal ONLY while a body is recorded -- a round, walk or forward body; on a live vdf_cs it sets the failure flag, as
+ * vdf_cs_pow does.  ONE table per body: a second call with another (pointer, rows, cols) sets the failure flag, as do a null
+ * table and dimensions outside the caps.  A recording copies nothing: the caller keeps the table alive and unchanged for as long
+ * as the circuit or the tape is in use.  The tape that vdf_nova_round_body_record, _walk_body_record and _forward_body_record hand
+ * out names the CALLER'S pointer (out->table, tab_rows, tab_cols) -- host memory, so the tape goes to the host evaluators below as it is, and to a launcher of vdf_hip.h with `table`
+ * replaced by a device-readable copy.
+ * In a ROUND body the result is a constant handle, like j: usable in linear combinations, vdf_cs_mul, vdf_cs_enforce and carry_out;
+ * in repetition j it contributes table[j mod rows][col] on the constant's column, so the same circuit written as a plain loop
+ * with vdf_cs_const(&table[(j % rows) * cols + col]) has the same shape and the same digest.  In walk and forward bodies it is a
+ * value.  It costs one call of VDF_ROUND_MAX_OPS and no stored constant.
+ * The parameters of a custom circuit keep a copy of the table with the tape and ONE device copy, freed with them; a step whose
+ * recorded body has another table -- one element is enough -- is "differs from the one these parameters were made with" (the
+ * comparison is one pass over the table per step on the host, and one more for a probe of tuning.custom_ahead).  Rows
+ * that read a table are periodic only with the table's period: the detection compares every triple of every repetition and
+ * keeps the generic kernel for them (tuning.periodic_rows = 1 included).
+ * CHAINS.  A chain's walks see the chain-global J (step g: j_base + g * t + ...), the round body's j is step-local; the two name
+ * the same row only when tab_rows divides t and every j_base, and vdf_nova_custom_chain_[lanes_]from_checkpoints refuse anything
+ * else (VDF_ERR_BAD_ARG naming the check).  There the walk tape's table is HOST memory; the chain copies it, makes one device copy
+ * with its first walks, and counts both in _host_bytes and _memory. */
+vdf_num vdf_cs_tab(vdf_cs* cs, const vdf_fe* table, size_t rows, size_t cols, size_t col);
 /* Host only.  Records a body and hands out its tape for vdf_round_tape_run (ops / consts: caller's arrays of the two caps, which
  * out->ops / out->consts then point into); out->n_cons = the constraints per repetition.  field: the body's field. */
 int  vdf_nova_round_body_record(int field, const vdf_round_body* b, vdf_tape_op ops[VDF_TAPE_MAX_OPS], vdf_fe consts[VDF_TAPE_MAX_CONSTS],

@@ -566,7 +566,7 @@ extern "C" {
 
 int vdf_ctx_device(vdf_ctx* ctx) { return ctx ? ctx->device : 0; }
 
-const char* vdf_version(void) { return "vdf_hip gfx950 r1 (" __DATE__ ")"; }
+const char* vdf_version(void) { return "vdf_hip gfx950 r2 (" __DATE__ ")"; }
 
 static int ctx_create_impl(const int* device_ids, int n_devices, int role, vdf_ctx** out);
 int vdf_ctx_create_pooled_near(vdf_ctx* parent, int role, vdf_ctx** out);
@@ -1510,11 +1510,19 @@ int vdf_minroot_forward_segment_lanes(vdf_ctx* ctx, int field, const vdf_fe* tra
   });
 }
 
+// a tape's table (VDF_TAPE_TAB) is read by the kernel in place, as advice and entries are
+static Status tape_table_on_device(const vdf_round_tape* tape) {
+  if (tape->tab_rows && tape->table && !ptr_is_device(tape->table))
+    return Status{VDF_ERR_BAD_ARG, "the tape's table lives in device memory (vdf_dev_alloc or vdf_host_alloc): a kernel reads it in place"};
+  return Status{};
+}
+
 int vdf_round_tape_run(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uint64_t t, const vdf_fe* inv, const vdf_fe* advice, vdf_fe* out) {
   return guarded(ctx, [&]() -> Status {
     if (t == 0 || t >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
     if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv))
       return Status{VDF_ERR_BAD_ARG, "the tape and inv live in host memory"};
+    VDF_TRY(tape_table_on_device(tape));
     if (!ptr_is_device(advice) || !ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
     VDF_TRY(vdf::vec_round_tape(field, tape, t, inv, advice, out, ctx->stream));
     if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
@@ -1528,6 +1536,7 @@ int vdf_round_tape_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, con
   return guarded(ctx, [&]() -> Status {
     if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv))
       return Status{VDF_ERR_BAD_ARG, "the tape and inv live in host memory"};
+    VDF_TRY(tape_table_on_device(tape));
     if (n && rounds && (!ptr_is_device(entries) || (trace && !ptr_is_device(trace)) || (expect && !ptr_is_device(expect)) || (ok && !ptr_is_device(ok))))
       return Status{VDF_ERR_BAD_ARG, "entries, trace, expect and ok live in device memory"};
     VDF_TRY(vdf::vec_round_tape_walk(field, tape, inv, entries, n, rounds, trace, walk_stride, top, group, group_stride, j_base, j_group_step,
@@ -1543,6 +1552,7 @@ int vdf_round_tape_run_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* tape
     if (t == 0 || t >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
     if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv))
       return Status{VDF_ERR_BAD_ARG, "the tape and inv live in host memory"};
+    VDF_TRY(tape_table_on_device(tape));
     if (!ptr_is_device(advice) || !ptr_is_device(out)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
     VDF_TRY(vdf::vec_round_tape_lanes(field, tape, t, lanes, inv, advice, lane_stride, out, ctx->stream));
     if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
@@ -1556,6 +1566,7 @@ int vdf_round_tape_walk_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* tap
   return guarded(ctx, [&]() -> Status {
     if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv) || ptr_is_device(j_base))
       return Status{VDF_ERR_BAD_ARG, "the tape, inv and j_base live in host memory"};
+    VDF_TRY(tape_table_on_device(tape));
     if (n && rounds && (!ptr_is_device(entries) || (trace && !ptr_is_device(trace)) || (expect && !ptr_is_device(expect)) || (ok && !ptr_is_device(ok))))
       return Status{VDF_ERR_BAD_ARG, "entries, trace, expect and ok live in device memory"};
     VDF_TRY(vdf::vec_round_tape_walk_lanes(field, tape, lanes, inv, entries, n, rounds, trace, walk_stride, top, group, group_stride, j_base,
@@ -1568,7 +1579,7 @@ int vdf_round_tape_walk_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* tap
 static Status forward_tape_on_host(const vdf_round_tape* tape, const vdf_fe* inv) {
   if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv))
     return Status{VDF_ERR_BAD_ARG, "the tape and inv live in host memory"};
-  return Status{};
+  return tape_table_on_device(tape);
 }
 
 int vdf_round_tape_forward_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n,

@@ -1,6 +1,7 @@
 // libvdf_nova.so, part 2c: the chain of a custom step circuit (vdf_custom_chain, include/vdf_nova.h) -- what circuits_host.cpp is
 // to the built-in kinds: the checkpoints of a chain on the host, and per step a device trace rebuilt by the chain's walk tape
 // (vdf_round_tape_walk; vdf_round_tape_walk_lanes for a chain of several lanes) on a side queue, a window ahead of the prover.
+#include <atomic>
 #include "nova_internal.hpp"
 
 using namespace vdfnova;
@@ -16,6 +17,9 @@ struct vdf_custom_chain final : WalkOwner {
   size_t per = 0, na = 0;                  // walks per step AND LANE, elements per entry
   std::vector<vdf_tape_op> ops;
   std::vector<Fe> consts, inv, cp;         // inv: lanes * n_inv; cp: per lane (steps * per + 1) entries, forward order, lane-major
+  std::vector<Fe> table;                   // the walk tape's table (VDF_TAPE_TAB), a host copy ...
+  std::atomic<void*> d_table{nullptr};     // ... and its ONE device copy, made by the first job on the traces' device, freed with the
+                                           // chain; published only once it is whole (vdf_nova_custom_chain_memory may ask from another thread)
   std::vector<Fe> stage;                 // lanes > 1, while a job is pending: the walks' starts, then their targets, gathered
                                            // step-major, lane-minor (freed when the job resolves)
   size_t lane_entries() const { return v.size() * per + 1; }
@@ -50,6 +54,18 @@ struct vdf_custom_chain final : WalkOwner {
     *expects = stage.data() + j.walks * na;
   }
   void unstage() override { std::vector<Fe>().swap(stage); }
+  // the table goes to the device once, on the queue the walks run on and in front of them
+  int setup(vdf_ctx* q, const WalkJob&, const WalkScratch&) override {
+    if (table.empty() || d_table.load()) return VDF_OK;
+    void* d = nullptr;
+    int rc = vdf_dev_alloc(walk.home, table.size() * 32, &d);
+    if (rc != VDF_OK) return rc;
+    rc = vdf_dev_memcpy(q, d, table.data(), table.size() * 32);
+    if (rc != VDF_OK) { vdf_dev_free(walk.home, d); return rc; }      // nothing is kept: the next job tries again
+    tape.table = (const vdf_fe*)d;
+    d_table.store(d);
+    return VDF_OK;
+  }
   // the comparison rides in the last slice
   int launch(vdf_ctx* q, const WalkJob& j, const WalkScratch& s, uint64_t rounds, uint64_t top, int last) override {
     uint64_t jb[VDF_TAPE_MAX_LANES];
@@ -116,6 +132,13 @@ int vdf_nova_custom_chain_lanes_from_checkpoints(int fid, const vdf_round_tape* 
                                 : eval_walk_tape_lanes(fid, walk_tape, lanes, (const Fe*)inv, nullptr, 0, 0, nullptr, 0, 0, 0, 0, j_base, 0, 0, nullptr, nullptr);
       if (rc != VDF_OK) return rc;
     }
+    // a chain's walks see the chain-global J (step g's walks j_base + g * t + ...), the round body's j is step-local: the two name
+    // the same row of a table only when its rows divide t and every j_base
+    if (walk_tape->tab_rows) {
+      if (t % walk_tape->tab_rows != 0) return fail(VDF_ERR_BAD_ARG, "the walk tape's tab_rows must divide t (the round body's j is step-local, the walks' J chain-global)");
+      for (size_t l = 0; l < lanes; ++l)
+        if (j_base[l] % walk_tape->tab_rows != 0) return fail(VDF_ERR_BAD_ARG, "the walk tape's tab_rows must divide every j_base (the round body's j is step-local, the walks' J chain-global)");
+    }
     const size_t per = (size_t)(t / every), na = walk_tape->n_adv;
     if (num_steps > ((size_t)1 << 40) / per) return fail(VDF_ERR_BAD_LENGTH, "too many checkpoints");
     const size_t entries = num_steps * per + 1;
@@ -129,6 +152,8 @@ int vdf_nova_custom_chain_lanes_from_checkpoints(int fid, const vdf_round_tape* 
     c->tape = *walk_tape;
     c->tape.ops = c->ops.data();
     c->tape.consts = (const vdf_fe*)c->consts.data();
+    if (walk_tape->tab_rows) c->table.assign((const Fe*)walk_tape->table, (const Fe*)walk_tape->table + (size_t)walk_tape->tab_rows * walk_tape->tab_cols);
+    c->tape.table = nullptr;                           // the device copy, once a job has made it (setup)
     c->cp.resize(lanes * entries * na);
     const bool device = vdf_ptr_is_device(checkpoints);
     for (size_t l = 0; l < lanes; ++l) {
@@ -173,11 +198,12 @@ int vdf_nova_custom_chain_release(vdf_custom_chain* c, size_t first, size_t coun
 int vdf_nova_custom_chain_memory(const vdf_custom_chain* c, size_t* resident_steps, uint64_t* device_bytes) {
   if (!c) return fail(VDF_ERR_BAD_ARG, "null argument");
   c->walk.memory(c->v.size(), resident_steps, device_bytes);
+  if (device_bytes && c->d_table.load()) *device_bytes += c->table.size() * 32;      // the table's device copy
   return VDF_OK;
 }
 int vdf_nova_custom_chain_host_bytes(const vdf_custom_chain* c, uint64_t* bytes) {
   if (!c || !bytes) return fail(VDF_ERR_BAD_ARG, "null argument");
-  *bytes = c->ops.size() * sizeof(vdf_tape_op) + (c->consts.size() + c->inv.size() + c->cp.size() + c->stage.size()) * 32;
+  *bytes = c->ops.size() * sizeof(vdf_tape_op) + (c->consts.size() + c->inv.size() + c->cp.size() + c->stage.size() + c->table.size()) * 32;
   return VDF_OK;
 }
 size_t vdf_nova_custom_chain_len(const vdf_custom_chain* c) { return c ? c->v.size() : 0; }
@@ -193,7 +219,9 @@ int vdf_nova_custom_chain_advice(vdf_custom_chain* c, size_t k, const vdf_fe** d
 }
 void vdf_nova_custom_chain_free(vdf_custom_chain* c) {
   if (!c) return;
-  c->walk.teardown(c->v.size());
+  vdf_ctx* home = c->walk.home;
+  c->walk.teardown(c->v.size());                       // (synchronises the walks' queue)
+  if (c->d_table.load()) vdf_dev_free(home, c->d_table.load());
   delete c;
 }
 }  // extern "C"

@@ -1108,6 +1108,15 @@ static int public_params_impl(vdf_ctx* ctx, int fid, uint64_t t, int circuit_kin
   HostShape sh[2];
   { int rc = build_shapes(fid, t, circuit_kind, sh, custom, pp->ro, lanes, &pp->round); if (rc != VDF_OK) return rc; }
   digest_shapes(fid, t, gens_family, sh, pp->digest, pp->ro);
+  if (custom && pp->round.used && pp->round.rec.tab_rows) {
+    // the table of the repeat's body (vdf_cs_tab): the parameters' record takes the ONE host copy every later body is compared
+    // with, byte for byte (a step's own record only points at its caller's), and this is the ONE device copy the round kernels
+    // of every step read; freed with the parameters
+    pp->round.rec.keep_table();
+    const size_t bytes = pp->round.rec.table.size() * 32;
+    HIPCALL(ctx, vdf_dev_alloc(ctx, bytes, &pp->d_round_table));
+    HIPCALL(ctx, vdf_dev_memcpy(ctx, pp->d_round_table, pp->round.rec.table.data(), bytes));
+  }
   // only the MinRoot rounds are made on the device; of a custom circuit the variables of its vdf_cs_repeat, when a step's advice is
   // in device memory (everything a built-in circuit gets on top of that -- early rows, lookahead, a stencil -- stays with them)
   pp->seg_begin = custom ? (pp->round.used ? pp->round.var_begin : 0) : sh[PRIMARY].step_begin;
@@ -1259,6 +1268,7 @@ void vdf_nova_pp_free(vdf_pp* pp) {
   if (pp->aux_ctx2) vdf_ctx_destroy(pp->aux_ctx2);
   for (auto& a : pp->arena) if (a.p) vdf_dev_free(pp->ctx, a.p);
   if (pp->seg_gens) vdf_bases_free(pp->seg_gens);
+  if (pp->d_round_table) vdf_dev_free(pp->ctx, pp->d_round_table);
   for (Side& sd : pp->s) {
     if (sd.d_zero) vdf_dev_free(pp->ctx, sd.d_zero);
     if (sd.shape) vdf_shape_free(sd.shape);
@@ -1545,7 +1555,8 @@ struct StepRun {
       // been synchronised by the host and this queue is behind it
       next.chain = chain; next.k = j; next.d_trace = d_probed; next.lane_stride = probed->lane_stride; next.slot = s;
       next.inv = probed->inv;
-      const vdf_round_tape tape = pp->round.rec.view();      // (the probe's body is the parameters': compared by the caller)
+      vdf_round_tape tape = pp->round.rec.view();            // (the probe's body is the parameters': compared by the caller)
+      tape.table = (const vdf_fe*)pp->d_round_table;         // (null without a table)
       if (pp->round.lanes == 1)
         HIPCALL(q, vdf_round_tape_run(q, S1.field, &tape, pp->round.t, (const vdf_fe*)next.inv.data(), d_probed, (vdf_fe*)seg));
       else
@@ -1835,7 +1846,8 @@ struct StepRun {
       if (custom && cs.dev_len && !hit) {
         // the rounds of the circuit's vdf_cs_repeat, one repetition per thread, straight into the fresh witness: in front of the
         // uploads around them and of the commitment of W, on the step's own queue
-        const vdf_round_tape tape = round->rec.view();
+        vdf_round_tape tape = round->rec.view();
+        tape.table = (const vdf_fe*)pp->d_round_table;       // the parameters' device copy: same_body above compared the table's bytes
         if (round->lanes == 1)
           HIPCALL(ctx, vdf_round_tape_run(ctx, S1.field, &tape, round->t, (const vdf_fe*)round->inv.data(), (const vdf_fe*)round->d_advice,
                                           (vdf_fe*)((char*)d_z2 + pp->seg_begin * 32)));

@@ -113,6 +113,7 @@ struct vdf_pp {
   // a custom circuit's vdf_cs_repeat as its shape synthesis recorded it (the body, t, where its variables begin): every
   // prove_step's own recording is compared with it; [seg_begin, seg_begin + seg_len) are its variables
   vdfnova::RepeatState round;
+  void* d_round_table = nullptr;                   // the device copy of round.rec.table (vdf_cs_tab), null without one
   // ... and the rows of its repetitions as a periodic description, when they are one (detect_periodic_rows, checked against every
   // triple when the parameters were made); periodic_on: tuning.periodic_rows lets the prover use it (vdf_nova_pp_stencil == 7)
   vdfnova::PeriodicRows periodic;

@@ -1,6 +1,7 @@
 // Uniform rounds of a custom step circuit (include/vdf_nova.h vdf_cs_repeat): the body as recorded, its replay over a constraint
 // system, and the slot-allocated program the GPU runs (include/vdf_hip.h vdf_round_tape).  rounds_host.cpp.
 #pragma once
+#include <cstring>
 #include <vector>
 #include "../../../include/vdf_nova.h"
 #include "r1cs.hpp"
@@ -11,7 +12,9 @@ namespace vdfnova {
 // one vdf_cs_* call.  a, b, c name nodes, except: R_CONST a = index into consts; R_SCALE and R_POW b = index into consts (R_POW:
 // the exponent, a plain 256-bit integer, stored like a constant).  R_POWC (vdf_cs_pow_chain): b = index of the first of the
 // constants the packed chain lies in (csrc/pow_chain.h), c = its n_tmp.  R_POW and R_POWC exist in forward bodies only.
-enum RecOp : uint8_t { R_INPUT = 0, R_CONST, R_ADD, R_SUB, R_SCALE, R_MUL, R_ALLOC_FROM, R_ENFORCE, R_POW, R_POWC };
+// R_TAB (vdf_cs_tab): a = the column of the record's one table; the round constant table[j mod rows][a] -- in a round body a
+// constant like j (replay_round puts its value on the constant's column), in walk and forward bodies a value.
+enum RecOp : uint8_t { R_INPUT = 0, R_CONST, R_ADD, R_SUB, R_SCALE, R_MUL, R_ALLOC_FROM, R_ENFORCE, R_POW, R_POWC, R_TAB };
 struct RecNode {
   uint8_t op = R_INPUT;
   bool value_only = false;         // made of advice values: no linear combination stands behind it
@@ -28,6 +31,19 @@ struct RoundRecord {
   std::vector<vdf_tape_op> ops;
   uint32_t n_slots = 0;
   uint32_t chain_tmp = 0;                          // the largest n_tmp of the POWCs the program holds (slots behind the two entries)
+  // the body's one table (vdf_cs_tab): the caller's pointer, which identifies it while the body records and which the caller
+  // keeps alive for as long as the record is used -- a recording copies nothing (a body is recorded again in every step).  A
+  // record that OUTLIVES the call it was made in (the parameters') takes its own copy once: keep_table().  same_body compares the
+  // elements, wherever they lie: one pass over at most 1 MiB per step, the price of "another table is another circuit".
+  const vdf_fe* tab_src = nullptr;
+  uint32_t tab_rows = 0, tab_cols = 0;
+  std::vector<Fe> table;                           // keep_table()'s copy, else empty
+  size_t tab_elems() const { return (size_t)tab_rows * tab_cols; }
+  const Fe* tab_data() const { return table.empty() ? (const Fe*)tab_src : table.data(); }
+  void keep_table() {
+    if (tab_rows && table.empty()) table.assign((const Fe*)tab_src, (const Fe*)tab_src + tab_elems());
+    tab_src = nullptr;
+  }
 
   uint32_t n_inputs() const { return 1 + n_inv + n_carry + 2 * n_adv; }
   uint32_t in_j() const { return 0; }
@@ -36,13 +52,16 @@ struct RoundRecord {
   uint32_t in_cur(uint32_t k) const { return 1 + n_inv + n_carry + k; }
   uint32_t in_next(uint32_t k) const { return 1 + n_inv + n_carry + n_adv + k; }
   bool same_body(const RoundRecord& o) const {
-    return n_inv == o.n_inv && n_carry == o.n_carry && n_adv == o.n_adv && nodes == o.nodes && consts == o.consts && carry_out == o.carry_out;
+    return n_inv == o.n_inv && n_carry == o.n_carry && n_adv == o.n_adv && nodes == o.nodes && consts == o.consts && carry_out == o.carry_out &&
+           tab_rows == o.tab_rows && tab_cols == o.tab_cols &&
+           (tab_rows == 0 || tab_data() == o.tab_data() || memcmp(tab_data(), o.tab_data(), tab_elems() * sizeof(Fe)) == 0);
   }
   vdf_round_tape view() const {
     vdf_round_tape t;
     t.ops = ops.data(); t.n_ops = ops.size();
     t.consts = (const vdf_fe*)consts.data(); t.n_consts = consts.size();
     t.n_slots = n_slots; t.n_vars = n_vars; t.n_cons = n_cons; t.n_inv = n_inv; t.n_adv = n_adv;
+    t.table = tab_rows ? (const vdf_fe*)tab_data() : nullptr; t.tab_rows = tab_rows; t.tab_cols = tab_cols;      // (host memory)
     return t;
   }
 };

@@ -107,6 +107,7 @@ int compile_round(RoundRecord& r, const std::vector<uint32_t>* outs = nullptr) {
       case R_SCALE: slot[i] = take(); emit(VDF_TAPE_SCALE, slot[i], sa, x.b); break;
       case R_POW: slot[i] = take(); emit(VDF_TAPE_POW, slot[i], sa, x.b); break;
       case R_POWC: slot[i] = take(); emit(VDF_TAPE_POWC, slot[i], sa, x.b); if (x.c > r.chain_tmp) r.chain_tmp = x.c; break;
+      case R_TAB: slot[i] = take(); emit(VDF_TAPE_TAB, slot[i], x.a, 0); break;
       case R_MUL: slot[i] = take(); emit(VDF_TAPE_MUL, slot[i], sa, sb); if (!outs) emit(VDF_TAPE_OUT, 0, slot[i], var++); break;
       default: emit(VDF_TAPE_OUT, 0, sa, var++); break;      // R_ALLOC_FROM
     }
@@ -148,7 +149,7 @@ int record_round_body(CS* cs, const vdf_round_body* b, RoundRecord* out) {
   if (rc != 0) return fail(VDF_ERR_BAD_ARG, "vdf_cs_repeat: the round body failed");
   if (h.rec_calls > VDF_ROUND_MAX_OPS) return fail(VDF_ERR_BAD_ARG, "vdf_cs_repeat: more than VDF_ROUND_MAX_OPS calls in the round body");
   if (r.consts.size() > VDF_ROUND_MAX_CONSTS) return fail(VDF_ERR_BAD_ARG, "vdf_cs_repeat: more than VDF_ROUND_MAX_CONSTS constants in the round body");
-  if (h.bad) return fail(VDF_ERR_BAD_ARG, "vdf_cs_repeat: the round body used a handle it does not own, a value-only handle in a constraint, or a call that is not recordable");
+  if (h.bad) return fail(VDF_ERR_BAD_ARG, "vdf_cs_repeat: the round body used a handle it does not own, a value-only handle in a constraint, or a call that is not recordable (a second table of vdf_cs_tab included)");
   for (uint32_t k = 0; k < r.n_carry; ++k) {
     const long nd = rec_node(&h, hout[k]);
     if (nd < 0 || r.nodes[nd].value_only) return fail(VDF_ERR_BAD_ARG, "vdf_cs_repeat: carry_out holds a foreign or value-only handle");
@@ -184,6 +185,7 @@ void replay_round(CS& cs, const RoundRecord& r, uint64_t j, const std::vector<Nu
     const RecNode& x = r.nodes[i];
     switch (x.op) {
       case R_CONST: v[i] = cs.constant(r.consts[x.a]); break;
+      case R_TAB: v[i] = cs.constant(r.tab_data()[(size_t)(j % r.tab_rows) * r.tab_cols + x.a]); break;      // what vdf_cs_const of that entry would make
       case R_ADD: v[i] = cs.add(v[x.a], v[x.b]); break;
       case R_SUB: v[i] = cs.sub(v[x.a], v[x.b]); break;
       case R_SCALE: v[i] = cs.scale(v[x.a], r.consts[x.b]); break;
@@ -249,6 +251,7 @@ static void run_tape_round(const vdf_round_tape* tp, const Field& F, uint64_t j,
       case VDF_TAPE_SCALE: s[o.dst] = mul(s[o.a], consts[o.b], F); break;
       case VDF_TAPE_POW: s[o.dst] = pow_plain(s[o.a], consts[o.b], F); break;
       case VDF_TAPE_POWC: s[o.dst] = pow_chain_run(s[o.a], consts, o.b, F); break;
+      case VDF_TAPE_TAB: s[o.dst] = ((const Fe*)tp->table)[(size_t)(j % tp->tab_rows) * tp->tab_cols + o.a]; break;
       default: out[o.b] = s[o.a]; break;      // VDF_TAPE_OUT
     }
   }
@@ -304,7 +307,7 @@ int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out, bool forw
   if (rc != 0) return fail(VDF_ERR_BAD_ARG, "walk body: the body failed");
   if (h.rec_calls > VDF_ROUND_MAX_OPS) return fail(VDF_ERR_BAD_ARG, "walk body: more than VDF_ROUND_MAX_OPS calls");
   if (r.consts.size() > VDF_ROUND_MAX_CONSTS) return fail(VDF_ERR_BAD_ARG, "walk body: more than VDF_ROUND_MAX_CONSTS constants");
-  if (h.bad) return fail(VDF_ERR_BAD_ARG, "walk body: a handle the body does not own, or a call that is not value arithmetic (alloc, alloc_from, enforce, value, repeat; pow or pow_chain outside a forward body, an invalid chain)");
+  if (h.bad) return fail(VDF_ERR_BAD_ARG, "walk body: a handle the body does not own, or a call that is not value arithmetic (alloc, alloc_from, enforce, value, repeat; pow or pow_chain outside a forward body, an invalid chain, a second table of vdf_cs_tab)");
   std::vector<uint32_t> outs;
   for (uint32_t k = 0; k < r.n_adv; ++k) {
     const long nd = rec_node(&h, hout[k]);
@@ -624,6 +627,15 @@ vdf_num rec_cs_pow_chain(vdf_cs* c, vdf_num a, const vdf_pow_step* steps, size_t
   for (size_t q = 1; q < nk; ++q) rec_const(c, &k[q]);
   return rec_push(c, R_POWC, false, (uint32_t)x, first, ci.n_tmp);
 }
+// one table per body: the first call names it (nothing is copied); every later call must name the same (pointer, rows, cols)
+vdf_num rec_cs_tab(vdf_cs* c, const vdf_fe* table, size_t rows, size_t cols, size_t col) {
+  RoundRecord& r = *c->rec;
+  if (!table || rows == 0 || rows > VDF_TAPE_MAX_TAB_ROWS || cols == 0 || cols > VDF_TAPE_MAX_TAB_COLS || col >= cols) { c->bad = true; return 0; }
+  if (r.tab_rows == 0) {
+    r.tab_src = table; r.tab_rows = (uint32_t)rows; r.tab_cols = (uint32_t)cols;
+  } else if (r.tab_src != table || r.tab_rows != rows || r.tab_cols != cols) { c->bad = true; return 0; }
+  return rec_push(c, R_TAB, false, (uint32_t)col, 0, 0);
+}
 int rec_cs_enforce(vdf_cs* c, vdf_num a, vdf_num b, vdf_num cc) {
   if (c->walk) { c->bad = true; return VDF_ERR_BAD_ARG; }      // a walk body computes values: it has nothing to constrain
   const long x = rec_node(c, a), y = rec_node(c, b), z = rec_node(c, cc);
@@ -668,6 +680,13 @@ vdf_num vdf_cs_pow(vdf_cs* c, vdf_num a, const uint64_t e[4]) {
   if (!c) return 0;
   if (c->rec) return rec_cs_pow(c, a, e);
   c->bad = true;                                       // value arithmetic of a forward body only
+  return 0;
+}
+
+vdf_num vdf_cs_tab(vdf_cs* c, const vdf_fe* table, size_t rows, size_t cols, size_t col) {
+  if (!c) return 0;
+  if (c->rec) return rec_cs_tab(c, table, rows, cols, col);
+  c->bad = true;                                       // the round constant of round j: only a body has a j
   return 0;
 }
 
@@ -850,6 +869,7 @@ int vdf_nova_round_body_record(int fid, const vdf_round_body* b, vdf_tape_op ops
     if (!rec.consts.empty()) memcpy(consts, rec.consts.data(), rec.consts.size() * 32);      // (a body may have no constant)
     out->ops = ops;
     out->consts = consts;
+    out->table = rec.tab_src;                          // the caller's own array, which the caller keeps alive
     return VDF_OK;
   });
 }
@@ -870,6 +890,7 @@ static int walk_body_record(int fid, const vdf_walk_body* b, vdf_tape_op* ops, v
     if (!rec.consts.empty()) memcpy(consts, rec.consts.data(), rec.consts.size() * 32);      // (a body may have no constant)
     out->ops = ops;
     out->consts = consts;
+    out->table = rec.tab_src;                          // the caller's own array, which the caller keeps alive
     return VDF_OK;
   });
 }

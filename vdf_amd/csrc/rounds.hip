@@ -9,6 +9,7 @@
 // lane groups.  A lane only ever touches its own column: no barrier.  LDS per workgroup is n_slots x 2 KiB, chosen at launch --
 // the slot allocation of the recorder (live ranges, linear scan) is what keeps occupancy up, not the length of the tape.
 #include <cstring>
+#include <type_traits>
 #include "internal.h"
 #include "fe.cuh"
 #include "cross.cuh"
@@ -44,8 +45,9 @@ template <class P> __device__ __forceinline__ void slot_store(uint4* lds, uint32
 }
 
 // ---- the interpreter: the ops of ONE round of a tape for one lane, the only statement of them on the device -------------------
-// Six kernels run tapes (the two round kernels, the two descending walks, the two forward walks); they differ in their setup and
-// landing and in three ops, which a kernel hands over as its IO: where ADV reads (global advice, or the entry stood on in LDS),
+// Six kernels run tapes (the two round kernels, the two descending walks, the two forward walks), and five more the tapes that
+// hold a VDF_TAPE_TAB (k_*_tab, below); they differ in their setup and landing and in three ops, which a kernel hands over as its
+// IO: where ADV reads (global advice, or the entry stood on in LDS),
 // where INV reads (the kernel arguments from an offset, or slots of LDS) and where OUT writes (global variables, or the entry
 // produced in LDS).  ADMIT: the ops beyond the base set that the kernel's launcher lets through (pack_tape's mode) -- an op that is
 // not admitted has no case here, so a kernel pays in registers and code only for what it can meet.
@@ -58,6 +60,28 @@ template <class P> __device__ __forceinline__ void slot_store(uint4* lds, uint32
 // run_tape_round in host/rounds_host.cpp (a separate restatement: the GPU tests compare the two); the recorder's compile_round there.
 enum { TAPE_BASE = 0, TAPE_POW = 1, TAPE_POWC = 2 };      // ADMIT: the base ops; and VDF_TAPE_POW; and VDF_TAPE_POWC
 constexpr int TAPE_NO_OP = 0x100;                         // the case label of an op that is not admitted: an opcode is one byte
+
+// VDF_TAPE_TAB is admitted by a second parameter, TAB, a type: NoTab for every tape without one -- the kernels those tapes always
+// launched, unchanged to the instruction -- and TabIO for a tape that holds a TAB, in kernels of their own (k_*_tab).  The table lies
+// in device-readable memory, not in the kernel arguments: 1 MiB would not fit, and the row is a per-lane value (one repetition per
+// lane, one walk per lane), which as an index into the arguments would send them to scratch.  So a TAB is a per-lane 32-byte global
+// load from a scalar base at (row * cols + a) * 32, and its value goes into its slot of LDS like any other; control stays uniform.
+// The row is exactly J mod rows: the round kernels take the remainder once per thread; a walk takes it once, before its rounds, and
+// then steps it with J -- down from 0 to rows - 1, up from rows - 1 to 0 -- except where J itself wraps modulo 2^64, which no
+// increment of the row follows when rows is no power of two: there (J = 2^64 - 1 after a step down, J = 0 after a step up: a
+// compare of the counter, uniform or not it is two selects) the remainder is taken again.  Nothing here can index out of range:
+// row < rows by construction, a < cols by tape_rules.h.
+struct NoTab {};
+struct TabArgs { const char* table; uint32_t rows, cols; };      // behind the existing arguments of a k_*_tab kernel
+struct TabIO {
+  const char* table;
+  uint32_t rows, cols, row;
+  __device__ __forceinline__ void at(uint64_t j) { row = (uint32_t)(j % rows); }
+  __device__ __forceinline__ void down(uint64_t j) { row = j == ~0ull ? (uint32_t)(j % rows) : row == 0 ? rows - 1 : row - 1; }      // j: after the step
+  __device__ __forceinline__ void up(uint64_t j) { row = j == 0 ? 0u : row + 1 == rows ? 0u : row + 1; }
+  template <class P> __device__ __forceinline__ Fe<P> load(uint32_t a) const { return fe_load<P>(table + ((size_t)row * cols + a) * 32); }
+};
+__device__ __forceinline__ TabIO tab_io(const TabArgs& t) { return TabIO{t.table, t.rows, t.cols, 0}; }
 
 // k_round_tape, k_round_tape_lanes: advice and variables in global memory, this launch's (lane's) invariants from tape.inv[inv0]
 template <class P> struct RoundIO {
@@ -85,8 +109,10 @@ template <class P, bool INV_LDS> struct WalkIO {
 };
 
 // tmp0: T[0] of a chain, the first of the n_tmp slots behind the two entries (ADMIT = TAPE_POWC only)
-template <class P, int ADMIT, class IO>
-__device__ __forceinline__ void tape_round(const TapeArgs& tape, uint4* slots, uint32_t lane, uint64_t j, const IO& io, uint32_t tmp0 = 0) {
+template <class P, int ADMIT, class IO, class TAB = NoTab>
+__device__ __forceinline__ void tape_round(const TapeArgs& tape, uint4* slots, uint32_t lane, uint64_t j, const IO& io, uint32_t tmp0 = 0,
+                                           const TAB& tab = TAB()) {
+  constexpr bool HAS_TAB = !std::is_same<TAB, NoTab>::value;
 #pragma unroll 1
   for (uint32_t i = 0; i < tape.n_ops; ++i) {
     const uint32_t x = tape.ops[i];
@@ -155,6 +181,9 @@ __device__ __forceinline__ void tape_round(const TapeArgs& tape, uint4* slots, u
         v = fe_canon(v);                             // below 2m + 350 eps (above): two conditional subtractions
         break;
       }
+      case HAS_TAB ? VDF_TAPE_TAB : TAPE_NO_OP + 2:
+        if constexpr (HAS_TAB) v = tab.template load<P>(a);
+        break;
       default:                       // VDF_TAPE_OUT (the launcher admits no other opcode)
         io.store_out(slots, lane, b, slot_load<P>(slots, a, lane));
         continue;
@@ -174,6 +203,20 @@ __global__ __launch_bounds__(64) void k_round_tape(TapeArgs tape, const char* __
   tape_round<P, TAPE_BASE>(tape, tape_slots, lane, j, io);
 }
 
+// k_round_tape for a tape that holds a TAB: the row of repetition j, taken once per thread
+template <class P>
+__global__ __launch_bounds__(64) void k_round_tape_tab(TapeArgs tape, const char* __restrict__ advice, uint64_t t, char* __restrict__ out, TabArgs ta) {
+  extern __shared__ uint4 tape_slots[];
+  __builtin_amdgcn_s_setprio(3);
+  const uint32_t lane = threadIdx.x;
+  const uint64_t j = (uint64_t)blockIdx.x * 64 + lane;
+  if (j >= t) return;
+  const RoundIO<P> io = {advice + j * tape.n_adv * 32, out + j * tape.n_vars * 32, 0};
+  TabIO tab = tab_io(ta);
+  tab.at(j);
+  tape_round<P, TAPE_BASE>(tape, tape_slots, lane, j, io, 0, tab);
+}
+
 // k_round_tape for `lanes` advice arrays in ONE launch (vdf_hip.h vdf_round_tape_run_lanes): the lane is the grid's second dimension,
 // so it is a scalar like the tape: the lane's advice, its variables and its own n_inv invariants -- all lanes' invariants share the
 // 512-byte block of the arguments, lane-major -- are reached through scalar offsets.
@@ -191,6 +234,22 @@ __global__ __launch_bounds__(64) void k_round_tape_lanes(TapeArgs tape, LaneRunA
   const uint32_t inv0 = (uint32_t)l * la.n_inv;
   const RoundIO<P> io = {advice + (l * la.lane_stride + j) * tape.n_adv * 32, out + (l * la.t + j) * tape.n_vars * 32, inv0};
   tape_round<P, TAPE_BASE>(tape, tape_slots, lane, j, io);
+}
+
+template <class P>
+__global__ __launch_bounds__(64) void k_round_tape_lanes_tab(TapeArgs tape, LaneRunArgs la, const char* __restrict__ advice, char* __restrict__ out,
+                                                             TabArgs ta) {
+  extern __shared__ uint4 tape_slots[];
+  __builtin_amdgcn_s_setprio(3);
+  const uint32_t lane = threadIdx.x;
+  const uint64_t j = (uint64_t)blockIdx.x * 64 + lane;
+  if (j >= la.t) return;
+  const uint64_t l = blockIdx.y;                     // (wave-uniform)
+  const uint32_t inv0 = (uint32_t)l * la.n_inv;
+  const RoundIO<P> io = {advice + (l * la.lane_stride + j) * tape.n_adv * 32, out + (l * la.t + j) * tape.n_vars * 32, inv0};
+  TabIO tab = tab_io(ta);
+  tab.at(j);
+  tape_round<P, TAPE_BASE>(tape, tape_slots, lane, j, io, 0, tab);
 }
 
 // ---- walk tapes: the advice itself, rebuilt from checkpoints (vdf_hip.h vdf_round_tape_walk) ---------------------------------
@@ -218,9 +277,10 @@ struct WalkLanesArgs {
 static_assert(sizeof(TapeArgs) + sizeof(WalkLanesArgs) + 32 <= 4096, "the tape travels in the kernel-argument segment");
 
 // wl: the lanes form's arguments behind wa (= wl->w), null for k_tape_walk
-template <class P, bool LANES>
+template <class P, bool LANES, class TAB = NoTab>
 __device__ __forceinline__ void tape_walk(const TapeArgs& tape, const WalkArgs& wa, const WalkLanesArgs* wl, uint4* slots, char* entries,
-                                          char* trace, const char* expect, int32_t* ok) {
+                                          char* trace, const char* expect, int32_t* ok, TAB tab = TAB()) {
+  constexpr bool HAS_TAB = !std::is_same<TAB, NoTab>::value;
   const uint32_t lane = threadIdx.x;
   const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
   if (w >= wa.n) return;                             // (no barrier below: a lane touches only its own words of LDS)
@@ -255,6 +315,7 @@ __device__ __forceinline__ void tape_walk(const TapeArgs& tape, const WalkArgs& 
   for (uint32_t c = 0; c < na; ++c) slot_store<P>(slots, stand + c, lane, fe_load<P>(ep + c * 32));
   char* tp = trace ? trace + (G * wa.group_stride + first) * esz : nullptr;
   uint64_t j = jb + g * wa.j_group_step + first - 1;
+  if constexpr (HAS_TAB) tab.at(j);
 #pragma unroll 1
   for (uint32_t r = 0; r < wa.rounds; ++r, --j) {
     if (tp) {
@@ -262,8 +323,9 @@ __device__ __forceinline__ void tape_walk(const TapeArgs& tape, const WalkArgs& 
       tp -= esz;
     }
     const WalkIO<P, LANES> io = {stand, prod, inv0};
-    tape_round<P, TAPE_BASE>(tape, slots, lane, j, io);
+    tape_round<P, TAPE_BASE>(tape, slots, lane, j, io, 0, tab);
     const uint32_t t = stand; stand = prod; prod = t;
+    if constexpr (HAS_TAB) tab.down(j - 1);
   }
   // where the walk landed: back into entries, to the head of its group's trace, and against the checkpoint
   uint32_t diff = 0;
@@ -295,6 +357,20 @@ __global__ __launch_bounds__(64) void k_tape_walk_lanes(TapeArgs tape, WalkLanes
   tape_walk<P, true>(tape, wl.w, &wl, tape_slots, entries, trace, expect, ok);
 }
 
+template <class P>
+__global__ __launch_bounds__(64) void k_tape_walk_tab(TapeArgs tape, WalkArgs wa, char* __restrict__ entries, char* __restrict__ trace,
+                                                      const char* __restrict__ expect, int32_t* __restrict__ ok, TabArgs ta) {
+  extern __shared__ uint4 tape_slots[];
+  tape_walk<P, false>(tape, wa, nullptr, tape_slots, entries, trace, expect, ok, tab_io(ta));
+}
+
+template <class P>
+__global__ __launch_bounds__(64) void k_tape_walk_lanes_tab(TapeArgs tape, WalkLanesArgs wl, char* __restrict__ entries, char* __restrict__ trace,
+                                                            const char* __restrict__ expect, int32_t* __restrict__ ok, TabArgs ta) {
+  extern __shared__ uint4 tape_slots[];
+  tape_walk<P, true>(tape, wl.w, &wl, tape_slots, entries, trace, expect, ok, tab_io(ta));
+}
+
 // ---- forward walk tapes: the chain itself, many at once (vdf_hip.h vdf_round_tape_forward_walk) -------------------------------
 // k_tape_walk ascending: the same launch (one lane per walk, workgroups of one wavefront, wave priority left at 0), the same
 // interpreter and the same two entries behind the value file in LDS, swapped each round; what a round produces goes to the trace
@@ -307,9 +383,10 @@ struct ForwardArgs {
 };
 static_assert(sizeof(TapeArgs) + sizeof(ForwardArgs) + 24 <= 4096, "the tape travels in the kernel-argument segment");
 
-template <class P, int ADMIT>
+template <class P, int ADMIT, class TAB = NoTab>
 __device__ __forceinline__ void tape_forward_walk(const TapeArgs& tape, const ForwardArgs& fa, uint4* slots, char* entries, char* checkpoints,
-                                                  char* trace) {
+                                                  char* trace, TAB tab = TAB()) {
+  constexpr bool HAS_TAB = !std::is_same<TAB, NoTab>::value;
   const uint32_t lane = threadIdx.x;
   const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
   if (w >= fa.n) return;                             // (no barrier below: a lane touches only its own words of LDS)
@@ -324,10 +401,12 @@ __device__ __forceinline__ void tape_forward_walk(const TapeArgs& tape, const Fo
   uint64_t cp_left = checkpoints ? fa.every - fa.base % fa.every : 0;
   char* cp = checkpoints ? checkpoints + (w * fa.cp_stride + fa.base / fa.every + 1) * esz : nullptr;
   uint64_t j = fa.j_base + w * fa.j_walk_step + fa.base;
+  if constexpr (HAS_TAB) tab.at(j);
 #pragma unroll 1
   for (uint32_t r = 0; r < fa.rounds; ++r, ++j) {
     const WalkIO<P, false> io = {stand, prod, 0};
-    tape_round<P, ADMIT>(tape, slots, lane, j, io, tmp0);
+    tape_round<P, ADMIT>(tape, slots, lane, j, io, tmp0, tab);
+    if constexpr (HAS_TAB) tab.up(j + 1);
     const uint32_t t = stand; stand = prod; prod = t;
     if (tp) {
       for (uint32_t c = 0; c < na; ++c) fe_store<P>(tp + c * 32, slot_load<P>(slots, stand + c, lane));
@@ -354,6 +433,13 @@ __global__ __launch_bounds__(64) void k_tape_forward_walk_chain(TapeArgs tape, F
                                                                 char* __restrict__ checkpoints, char* __restrict__ trace) {
   extern __shared__ uint4 tape_slots[];
   tape_forward_walk<P, TAPE_POWC>(tape, fa, tape_slots, entries, checkpoints, trace);
+}
+// a forward tape that holds a TAB: ONE kernel that admits POW, POWC and TAB together
+template <class P>
+__global__ __launch_bounds__(64) void k_tape_forward_walk_tab(TapeArgs tape, ForwardArgs fa, char* __restrict__ entries,
+                                                              char* __restrict__ checkpoints, char* __restrict__ trace, TabArgs ta) {
+  extern __shared__ uint4 tape_slots[];
+  tape_forward_walk<P, TAPE_POWC>(tape, fa, tape_slots, entries, checkpoints, trace, tab_io(ta));
 }
 // ---- periodic rows: the cross term of the rows of such rounds without the sparse matrices (vdf_hip.h vdf_periodic_rows) --------
 // k_nifs_cross_minroot_forward_lanes for a round the library did not write: one row per lane, workgroups of 256, every running /
@@ -471,15 +557,21 @@ static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, vdftape::Mo
   return Status{};
 }
 
+// the table of a tape that holds a TAB, as the k_*_tab kernels take it (the abi has checked that a kernel may read it in place)
+static TabArgs tab_args(const vdf_round_tape* tp) { return TabArgs{cbytes_of(tp->table), tp->tab_rows, tp->tab_cols}; }
+
 Status vec_round_tape(int field, const vdf_round_tape* tp, uint64_t t, const vdf_fe* inv, const void* advice, void* out, hipStream_t s) {
   TapeArgs a;
-  VDF_TRY(pack_tape(tp, inv, vdftape::ROUND, a));
+  vdftape::Info ti;
+  VDF_TRY(pack_tape(tp, inv, vdftape::ROUND, a, &ti));
   // advice read + variables written per repetition
-  KTimer kt(s, "k_round_tape", 32.0 * (tp->n_adv + tp->n_vars) * t);
+  KTimer kt(s, ti.tab ? "k_round_tape_tab" : "k_round_tape", 32.0 * (tp->n_adv + tp->n_vars) * t);
   const dim3 grid((unsigned)((t + 63) / 64));
   const size_t lds = (size_t)tp->n_slots * 2 * 64 * sizeof(uint4);
   return with_field(field, [&](auto f) {
-    hipLaunchKernelGGL((k_round_tape<tag_t<decltype(f)>>), grid, dim3(64), lds, s, a, cbytes_of(advice), t, bytes_of(out));
+    using P = tag_t<decltype(f)>;
+    if (ti.tab) hipLaunchKernelGGL((k_round_tape_tab<P>), grid, dim3(64), lds, s, a, cbytes_of(advice), t, bytes_of(out), tab_args(tp));
+    else hipLaunchKernelGGL((k_round_tape<P>), grid, dim3(64), lds, s, a, cbytes_of(advice), t, bytes_of(out));
   });
 }
 
@@ -523,11 +615,16 @@ Status vec_round_tape_walk(int field, const vdf_round_tape* tp, const vdf_fe* in
   VDF_TRY(walk_launch_checks(tp, 0, ti.products, n, rounds, entries, trace, top, heads, expect, ok, &nothing));
   if (nothing) return Status{};
   const WalkArgs wa = walk_args(tp, n, rounds, walk_stride, top, group, group_stride, j_base, j_group_step, heads);
-  KTimer kt(s, "k_tape_walk", trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0);
+  KTimer kt(s, ti.tab ? "k_tape_walk_tab" : "k_tape_walk", trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0);
   const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv) * 2 * 64 * sizeof(uint4);
   return with_field(field, [&](auto f) {
-    hipLaunchKernelGGL((k_tape_walk<tag_t<decltype(f)>>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, wa, bytes_of(entries),
-                       bytes_of(trace), cbytes_of(expect), ok);
+    using P = tag_t<decltype(f)>;
+    if (ti.tab)
+      hipLaunchKernelGGL((k_tape_walk_tab<P>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, wa, bytes_of(entries), bytes_of(trace),
+                         cbytes_of(expect), ok, tab_args(tp));
+    else
+      hipLaunchKernelGGL((k_tape_walk<P>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, wa, bytes_of(entries), bytes_of(trace),
+                         cbytes_of(expect), ok);
   });
 }
 
@@ -535,17 +632,20 @@ Status vec_round_tape_lanes(int field, const vdf_round_tape* tp, uint64_t t, siz
                             size_t lane_stride, void* out, hipStream_t s) {
   VDF_TRY(check_field(field));
   TapeArgs a;
-  VDF_TRY(pack_tape(tp, inv, vdftape::ROUND, a, nullptr, lanes));
+  vdftape::Info ti;
+  VDF_TRY(pack_tape(tp, inv, vdftape::ROUND, a, &ti, lanes));
   if (t == 0 || t >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
   if (lane_stride < t + 1 || lane_stride > ((size_t)1 << 40)) return Status{VDF_ERR_BAD_ARG, "lane_stride must be at least t + 1"};
   LaneRunArgs la;
   std::memset(&la, 0, sizeof(la));
   la.t = t; la.lane_stride = lane_stride; la.n_inv = tp->n_inv;
-  KTimer kt(s, "k_round_tape_lanes", 32.0 * (tp->n_adv + tp->n_vars) * t * lanes);
+  KTimer kt(s, ti.tab ? "k_round_tape_lanes_tab" : "k_round_tape_lanes", 32.0 * (tp->n_adv + tp->n_vars) * t * lanes);
   const dim3 grid((unsigned)((t + 63) / 64), (unsigned)lanes);
   const size_t lds = (size_t)tp->n_slots * 2 * 64 * sizeof(uint4);
   return with_field(field, [&](auto f) {
-    hipLaunchKernelGGL((k_round_tape_lanes<tag_t<decltype(f)>>), grid, dim3(64), lds, s, a, la, cbytes_of(advice), bytes_of(out));
+    using P = tag_t<decltype(f)>;
+    if (ti.tab) hipLaunchKernelGGL((k_round_tape_lanes_tab<P>), grid, dim3(64), lds, s, a, la, cbytes_of(advice), bytes_of(out), tab_args(tp));
+    else hipLaunchKernelGGL((k_round_tape_lanes<P>), grid, dim3(64), lds, s, a, la, cbytes_of(advice), bytes_of(out));
   });
 }
 
@@ -565,11 +665,16 @@ Status vec_round_tape_walk_lanes(int field, const vdf_round_tape* tp, size_t lan
   wl.w = walk_args(tp, n, rounds, walk_stride, top, group, group_stride, 0, j_group_step, heads);
   wl.lanes = (uint32_t)lanes; wl.n_inv = tp->n_inv;
   for (size_t l = 0; l < lanes; ++l) wl.j_base[l] = j_base[l];
-  KTimer kt(s, "k_tape_walk_lanes", trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0);
+  KTimer kt(s, ti.tab ? "k_tape_walk_lanes_tab" : "k_tape_walk_lanes", trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0);
   const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv + tp->n_inv) * 2 * 64 * sizeof(uint4);
   return with_field(field, [&](auto f) {
-    hipLaunchKernelGGL((k_tape_walk_lanes<tag_t<decltype(f)>>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, wl, bytes_of(entries),
-                       bytes_of(trace), cbytes_of(expect), ok);
+    using P = tag_t<decltype(f)>;
+    if (ti.tab)
+      hipLaunchKernelGGL((k_tape_walk_lanes_tab<P>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, wl, bytes_of(entries), bytes_of(trace),
+                         cbytes_of(expect), ok, tab_args(tp));
+    else
+      hipLaunchKernelGGL((k_tape_walk_lanes<P>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, wl, bytes_of(entries), bytes_of(trace),
+                         cbytes_of(expect), ok);
   });
 }
 
@@ -609,13 +714,17 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tp, const vd
   fa.j_base = j_base; fa.j_walk_step = j_walk_step;
   fa.rounds = (uint32_t)rounds; fa.n_slots = tp->n_slots;
   const bool chain = ti.chain_tmp != 0;      // a tape with a POWC: the kernel that also runs addition chains; every other tape: the one without
-  KTimer kt(s, chain ? "k_tape_forward_walk_chain" : "k_tape_forward_walk",
+  KTimer kt(s, ti.tab ? "k_tape_forward_walk_tab" : chain ? "k_tape_forward_walk_chain" : "k_tape_forward_walk",
             (trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0) + 64.0 * tp->n_adv * (double)n);
   const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv + ti.chain_tmp) * 2 * 64 * sizeof(uint4);
   return with_field(field, [&](auto f) {
     using P = tag_t<decltype(f)>;
-    hipLaunchKernelGGL(chain ? k_tape_forward_walk_chain<P> : k_tape_forward_walk<P>, dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, fa,
-                       bytes_of(entries), bytes_of(checkpoints), bytes_of(trace));
+    if (ti.tab)                              // a tape with a TAB: the one kernel that admits POW, POWC and TAB (ti.chain_tmp may be 0)
+      hipLaunchKernelGGL((k_tape_forward_walk_tab<P>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, fa, bytes_of(entries),
+                         bytes_of(checkpoints), bytes_of(trace), tab_args(tp));
+    else
+      hipLaunchKernelGGL(chain ? k_tape_forward_walk_chain<P> : k_tape_forward_walk<P>, dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, fa,
+                         bytes_of(entries), bytes_of(checkpoints), bytes_of(trace));
   });
 }
 

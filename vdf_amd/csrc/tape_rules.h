@@ -12,11 +12,14 @@ namespace vdftape {
 // ROUND: vdf_round_tape_run -- an ADV reads entry j (b = 0) or j + 1 (b = 1).  The walks write one advice entry per round
 // (n_vars == n_adv) and may not load the entry being produced: WALK (vdf_round_tape_walk, descending) stands on entry j + 1,
 // b = 1 only; FORWARD (vdf_round_tape_forward_walk) stands on entry j, b = 0 only.  POW and POWC are ops of FORWARD tapes only.
+// TAB is an op of all three, in a tape that has a table: where the table lives (device-readable memory for a launcher, host memory
+// for an evaluator) is the caller's to check -- here it is only not null.
 enum Mode { ROUND, WALK, FORWARD };
 
 struct Info {
   uint64_t products;       // the field products of one round, a POW or POWC counted as its squarings and multiplications; >= 1
   uint32_t chain_tmp;      // the largest n_tmp of the tape's chains (the slots a POWC keeps behind the two entries); 0: no POWC
+  bool tab;                // the tape holds a TAB: it launches the kernels that admit one
 };
 
 // what square-and-multiply from the top set bit spends on exponent e: bitlen - 1 squarings and popcount - 1 products, at least one
@@ -34,8 +37,12 @@ inline std::string check(const vdf_round_tape* tp, Mode mode, Info* out) {
       tp->n_inv > VDF_TAPE_MAX_INV || tp->n_adv > VDF_TAPE_MAX_ADV || tp->n_vars == 0 || tp->n_adv == 0 || tp->n_slots == 0)
     return "tape exceeds a published cap (VDF_TAPE_MAX_*), or has no variable, slot or advice column";
   if (mode != ROUND && tp->n_vars != tp->n_adv) return "walk tape: n_vars != n_adv (a round writes one advice entry)";
+  if ((tp->tab_rows == 0) != (tp->tab_cols == 0)) return "tape table: tab_rows and tab_cols are both 0 (no table) or both positive";
+  if (tp->tab_rows > VDF_TAPE_MAX_TAB_ROWS || tp->tab_cols > VDF_TAPE_MAX_TAB_COLS)
+    return "tape table exceeds a published cap (VDF_TAPE_MAX_TAB_ROWS, VDF_TAPE_MAX_TAB_COLS)";
+  if (tp->tab_rows && !tp->table) return "tape table: null table with tab_rows > 0";
   bool written[VDF_TAPE_MAX_SLOTS] = {}, var_out[VDF_TAPE_MAX_VARS] = {};
-  Info info = {0, 0};
+  Info info = {0, 0, false};
   for (size_t i = 0; i < tp->n_ops; ++i) {
     const vdf_tape_op& o = tp->ops[i];
     auto rd = [&](uint8_t x) { return x < tp->n_slots && written[x]; };
@@ -62,6 +69,12 @@ inline std::string check(const vdf_round_tape* tp, Mode mode, Info* out) {
           info.products += ci.products();
           if (ci.n_tmp > info.chain_tmp) info.chain_tmp = ci.n_tmp;
         }
+        break;
+      case VDF_TAPE_TAB:
+        if (tp->tab_rows == 0) return "tape op " + std::to_string(i) + " is malformed: a TAB in a tape without a table (tab_rows = 0)";
+        if (o.a >= tp->tab_cols) return "tape op " + std::to_string(i) + ": a TAB of column " + std::to_string(o.a) + " >= tab_cols";
+        if (o.b != 0) return "tape op " + std::to_string(i) + ": a TAB with b != 0";
+        ok = info.tab = true;
         break;
       default: break;
     }

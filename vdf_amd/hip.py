@@ -54,7 +54,8 @@ class TapeOp(C.Structure):
 
 class RoundTapeC(C.Structure):
     _fields_ = [("ops", C.POINTER(TapeOp)), ("n_ops", C.c_size_t), ("consts", C.c_void_p), ("n_consts", C.c_size_t),
-                ("n_slots", C.c_uint32), ("n_vars", C.c_uint32), ("n_cons", C.c_uint32), ("n_inv", C.c_uint32), ("n_adv", C.c_uint32)]
+                ("n_slots", C.c_uint32), ("n_vars", C.c_uint32), ("n_cons", C.c_uint32), ("n_inv", C.c_uint32), ("n_adv", C.c_uint32),
+                ("table", C.c_void_p), ("tab_rows", C.c_uint32), ("tab_cols", C.c_uint32)]
 
 
 TAPE_MAX_OPS, TAPE_MAX_CONSTS, TAPE_MAX_SLOTS, TAPE_MAX_VARS, TAPE_MAX_INV, TAPE_MAX_ADV = 320, 24, 24, 64, 16, 8
@@ -63,15 +64,31 @@ TAPE_MAX_LANES = 16                                # VDF_TAPE_MAX_LANES
 FORWARD_TAPE_MAX_WORK = 1 << 20                    # VDF_FORWARD_TAPE_MAX_WORK
 TAPE_POW = 9                                       # VDF_TAPE_POW
 TAPE_POWC = 10                                     # VDF_TAPE_POWC
+TAPE_TAB = 11                                      # VDF_TAPE_TAB
+TAPE_MAX_TAB_ROWS, TAPE_MAX_TAB_COLS = 4096, 8     # VDF_TAPE_MAX_TAB_ROWS, VDF_TAPE_MAX_TAB_COLS
 
 
 class RoundTape:
-    """vdf_round_tape with the arrays it points into (vdf_amd.nova.record_round_body makes one)."""
+    """vdf_round_tape with the arrays it points into (vdf_amd.nova.record_round_body makes one).  table: the numpy array
+    uint64[rows, cols, 4] of a tape that holds a TAPE_TAB (None without one); `c` names it as HOST memory, which is what the host
+    evaluators of vdf_amd.nova read, and the Context.round_tape_* methods hand the kernels a device copy in its place."""
 
     def __init__(self):
         self.ops = (TapeOp * TAPE_MAX_OPS)()
         self.consts = np.zeros((TAPE_MAX_CONSTS, 4), dtype="<u8")
         self.c = RoundTapeC()
+        self.table = None
+
+    def set_table(self, table) -> None:
+        """Gives the tape the table uint64[rows, cols, 4] (Montgomery form), or none (None)."""
+        if table is None:
+            self.table, self.c.table, self.c.tab_rows, self.c.tab_cols = None, None, 0, 0
+            return
+        table = np.ascontiguousarray(table, dtype="<u8")
+        if table.ndim != 3 or table.shape[2] != 4:
+            raise ValueError("a tape's table is uint64[rows, cols, 4]")
+        self.table = table
+        self.c.table, self.c.tab_rows, self.c.tab_cols = table.ctypes.data, table.shape[0], table.shape[1]
 
     def op_list(self):
         return [(o.op, o.dst, o.a, o.b) for o in self.ops[:self.c.n_ops]]
@@ -259,6 +276,16 @@ class MsmJob:
 QUEUE_CRITICAL, QUEUE_SIDE = 1, 2
 
 
+class _TapeTable:
+    """One context's device copy of one tape's table (Context._tape): the array it was made from (identity decides whether the
+    copy still is the tape's table), its size, and the vdf_round_tape handed to the launchers in the tape's place."""
+
+    def __init__(self, tape, array, d_table, nbytes):
+        self.tape, self.array, self.d_table, self.nbytes = weakref.ref(tape), array, d_table, nbytes
+        self.c = RoundTapeC()
+        self.finalizer = None
+
+
 class Context:
     """One context per GPU (one process per GPU)."""
 
@@ -274,6 +301,7 @@ class Context:
         self.handle = h.value
         self.device = device
         self._children = weakref.WeakSet()      # handles that own device memory of this context
+        self._tape_tables = {}                  # id(tape) -> _TapeTable: the device copy of a live tape's table (_tape)
 
     def _check(self, rc: int) -> None:
         if rc != _lib.VDF_OK:
@@ -289,6 +317,10 @@ class Context:
         if self.handle:
             for child in list(self._children):   # bases / shapes must go before their context
                 child.free()
+            for ent in self._tape_tables.values():
+                ent.finalizer.detach()
+                lib.vdf_dev_free(self.handle, ent.d_table)
+            self._tape_tables = {}
             lib.vdf_ctx_destroy(self.handle)
             self.handle = None
 
@@ -485,9 +517,54 @@ class Context:
         """The same for `lanes` traces lane_stride entries apart, lane-major into out, in one launch; i_end: `lanes` host elements."""
         self._check(lib.vdf_minroot_forward_segment_lanes(self.handle, field, _ptr(trace_xy), lane_stride, t, lanes, _ptr(i_end), _ptr(out)))
 
+    def _tape(self, tape: "RoundTape") -> int:
+        """Address of the vdf_round_tape a launcher takes: the tape's own, or for a tape with a table a copy of it whose `table`
+        is this context's device copy of that table.  The copy is made once per (tape, table array) -- the array's contents as
+        they were then -- and made again when the tape has been given another array (RoundTape.set_table, or a new `table`); it
+        is freed when the tape is collected or the context closed.  The dimensions a kernel is handed never exceed the copy."""
+        if tape.table is None:
+            return C.addressof(tape.c)
+        ent = self._tape_tables.get(id(tape))
+        if ent is not None and (ent.tape() is not tape or ent.array is not tape.table):
+            self._drop_tape_table(id(tape), ent)      # another table: the old copy goes, a kernel never sees it under the new dimensions
+            ent = None
+        if ent is None:
+            array = tape.table
+            p = C.c_void_p()
+            self._check(lib.vdf_dev_alloc(self.handle, array.nbytes, C.byref(p)))
+            rc = lib.vdf_dev_memcpy(self.handle, p.value, array.ctypes.data, array.nbytes)
+            if rc == _lib.VDF_OK:
+                rc = lib.vdf_ctx_sync(self.handle)
+            if rc != _lib.VDF_OK:
+                lib.vdf_dev_free(self.handle, p.value)
+                self._check(rc)
+            ent = _TapeTable(tape, array, p.value, array.nbytes)
+            ent.finalizer = weakref.finalize(tape, Context._tape_collected, weakref.ref(self), id(tape), ent)
+            self._tape_tables[id(tape)] = ent
+        if tape.c.tab_rows * tape.c.tab_cols * 32 > ent.nbytes:      # (a kernel would read past the device copy)
+            raise ValueError("tab_rows x tab_cols exceeds the tape's table")
+        c = ent.c
+        for name, _ in RoundTapeC._fields_:      # (ops and counts as they are now: a test may patch a tape between two calls)
+            setattr(c, name, getattr(tape.c, name))
+        c.table = ent.d_table
+        return C.addressof(c)
+
+    def _drop_tape_table(self, key, ent) -> None:
+        if self._tape_tables.get(key) is ent:
+            del self._tape_tables[key]
+            ent.finalizer.detach()
+            if self.handle:
+                lib.vdf_dev_free(self.handle, ent.d_table)
+
+    @staticmethod
+    def _tape_collected(ctx_ref, key, ent) -> None:
+        ctx = ctx_ref()
+        if ctx is not None:                      # (a closed context has freed every copy already)
+            ctx._drop_tape_table(key, ent)
+
     def round_tape_run(self, field, tape: "RoundTape", t, inv, advice, out) -> None:
         """t repetitions of a recorded round, one GPU thread each: out (device, t * n_vars elements); inv: host, advice: device."""
-        self._check(lib.vdf_round_tape_run(self.handle, field, C.addressof(tape.c), t, _ptr(inv), _ptr(advice), _ptr(out)))
+        self._check(lib.vdf_round_tape_run(self.handle, field, self._tape(tape), t, _ptr(inv), _ptr(advice), _ptr(out)))
 
     def round_tape_walk(self, field, tape: "RoundTape", inv, entries, n, rounds, trace=None, walk_stride=0, top=0, group=0, group_stride=0,
                         j_base=0, j_group_step=0, heads=False, expect=None, ok=None) -> None:
@@ -495,14 +572,14 @@ class Context:
         strides in entries.  trace (device or None): walk w writes the entry it stands on before round r to entry
         (w // group) * group_stride + (w % group) * walk_stride + top - r; heads: a group's first walk also writes its landing.
         expect / ok (device, int32[n]): ok[w] = the landing equals expect[w].  inv: host."""
-        self._check(lib.vdf_round_tape_walk(self.handle, field, C.addressof(tape.c), _ptr(inv), _ptr(entries), n, rounds, _ptr(trace),
+        self._check(lib.vdf_round_tape_walk(self.handle, field, self._tape(tape), _ptr(inv), _ptr(entries), n, rounds, _ptr(trace),
                                             walk_stride, top, group, group_stride, j_base, j_group_step, int(bool(heads)), _ptr(expect),
                                             _ptr(ok)))
 
     def round_tape_run_lanes(self, field, tape: "RoundTape", t, lanes, inv, advice, lane_stride, out) -> None:
         """round_tape_run for `lanes` advice arrays lane_stride entries apart in ONE launch: lane l's t * n_vars variables at
         out + l * t * n_vars, under its own inv[l * n_inv:(l + 1) * n_inv] (host, lanes * n_inv elements); advice, out: device."""
-        self._check(lib.vdf_round_tape_run_lanes(self.handle, field, C.addressof(tape.c), t, lanes, _ptr(inv), _ptr(advice), lane_stride,
+        self._check(lib.vdf_round_tape_run_lanes(self.handle, field, self._tape(tape), t, lanes, _ptr(inv), _ptr(advice), lane_stride,
                                                  _ptr(out)))
 
     def round_tape_walk_lanes(self, field, tape: "RoundTape", lanes, inv, entries, n, rounds, trace=None, walk_stride=0, top=0, group=0,
@@ -513,7 +590,7 @@ class Context:
         jb = np.ascontiguousarray([0] * lanes if j_base is None else [int(v) % 2**64 for v in j_base], dtype="<u8")
         if jb.size < lanes:
             raise ValueError("j_base: one counter per lane")
-        self._check(lib.vdf_round_tape_walk_lanes(self.handle, field, C.addressof(tape.c), lanes, _ptr(inv), _ptr(entries), n, rounds,
+        self._check(lib.vdf_round_tape_walk_lanes(self.handle, field, self._tape(tape), lanes, _ptr(inv), _ptr(entries), n, rounds,
                                                   _ptr(trace), walk_stride, top, group, group_stride, jb.ctypes.data, j_group_step,
                                                   int(bool(heads)), _ptr(expect), _ptr(ok)))
 
@@ -523,7 +600,7 @@ class Context:
         strides in entries.  With g = base + r + 1 after round r, walk w writes the entry it produced to trace entry
         w * walk_stride + g and, when every divides g, to checkpoints entry w * cp_stride + g // every (device or None); the round
         sees j = j_base + w * j_walk_step + base + r.  inv: host."""
-        self._check(lib.vdf_round_tape_forward_walk(self.handle, field, C.addressof(tape.c), _ptr(inv), _ptr(entries), n, rounds, _ptr(checkpoints),
+        self._check(lib.vdf_round_tape_forward_walk(self.handle, field, self._tape(tape), _ptr(inv), _ptr(entries), n, rounds, _ptr(checkpoints),
                                                     every, cp_stride, _ptr(trace), walk_stride, base, j_base, j_walk_step))
 
     def round_tape_eval_batch(self, field, tape: "RoundTape", inv, initial, n, rounds_total, out_entries, every=0, launch_rounds=0, j_base=0,
@@ -531,7 +608,7 @@ class Context:
         """Context.minroot_eval_batch for a forward walk tape: out_entries[w] = the final entry of chain w (every = 0), or the
         rounds_total // every + 1 entries it passes every `every` rounds, the initial one first.  initial / out_entries: host or
         device, n_adv elements per entry; inv: host."""
-        self._check(lib.vdf_round_tape_eval_batch(self.handle, field, C.addressof(tape.c), _ptr(inv), _ptr(initial), n, rounds_total, every,
+        self._check(lib.vdf_round_tape_eval_batch(self.handle, field, self._tape(tape), _ptr(inv), _ptr(initial), n, rounds_total, every,
                                                   launch_rounds, j_base, j_walk_step, _ptr(out_entries)))
 
     def minroot_step_segment_packed(self, field, trace_xy, t, i0, i_in, out, packed) -> None:

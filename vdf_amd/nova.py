@@ -105,6 +105,7 @@ for _name, _res, _args in [
     ("vdf_nova_round_tape_eval_lanes", _i, [_i, _vp, _u64, _sz, _vp, _vp, _sz, _vp]),
     ("vdf_nova_walk_tape_eval_lanes", _i, [_i, _vp, _sz, _vp, _vp, _sz, _u64, _vp, _sz, _sz, _sz, _sz, _vp, _u64, _i, _vp, _vp]),
     ("vdf_cs_pow", C.c_uint32, [_vp, C.c_uint32, _vp]),
+    ("vdf_cs_tab", C.c_uint32, [_vp, _vp, _sz, _sz, _sz]),
     ("vdf_cs_pow_chain", C.c_uint32, [_vp, C.c_uint32, _vp, _sz]),
     ("vdf_nova_pow_chain_exponent", _i, [_vp, _sz, _vp, C.POINTER(C.c_uint32), C.POINTER(_u64)]),
     ("vdf_nova_pow_chain_window", _i, [_vp, C.c_uint, _vp, _sz, C.POINTER(_sz)]),
@@ -408,13 +409,28 @@ class RoundBody:
         return self._struct
 
 
-def record_round_body(body: RoundBody, field: int = FIELD_FQ) -> RoundTape:
-    """Host only: the body recorded and compiled into the tape Context.round_tape_run / round_tape_eval take."""
-    tape = RoundTape()
-    rc = nova_lib.vdf_nova_round_body_record(field, C.addressof(body._c()), C.addressof(tape.ops), tape.consts.ctypes.data, C.addressof(tape.c))
+_RECORDINGS = []      # one dict per record_*_body call in progress: address -> the numpy table its body handed to ConstraintSystem.tab
+
+
+def _record(call, field: int, body, tape: RoundTape) -> RoundTape:
+    """One recording: the tables the body names are remembered for this call only (whether it returns or raises), and the tape
+    that comes back names its table by address -- it keeps that array alive from then on."""
+    seen = {}
+    _RECORDINGS.append(seen)
+    try:
+        rc = call(field, C.addressof(body._c()), C.addressof(tape.ops), tape.consts.ctypes.data, C.addressof(tape.c))
+    finally:
+        _RECORDINGS.pop()
     _reraise(body)
     _check(rc)
+    if tape.c.tab_rows:
+        tape.table = seen[tape.c.table]
     return tape
+
+
+def record_round_body(body: RoundBody, field: int = FIELD_FQ) -> RoundTape:
+    """Host only: the body recorded and compiled into the tape Context.round_tape_run / round_tape_eval take."""
+    return _record(nova_lib.vdf_nova_round_body_record, field, body, RoundTape())
 
 
 def round_tape_eval(field: int, tape: RoundTape, t: int, inv, advice) -> np.ndarray:
@@ -484,11 +500,7 @@ class WalkBody:
 
 def record_walk_body(body: WalkBody, field: int = FIELD_FQ) -> RoundTape:
     """Host only: the walk body recorded and compiled into the walk tape Context.round_tape_walk / walk_tape_eval take."""
-    tape = RoundTape()
-    rc = nova_lib.vdf_nova_walk_body_record(field, C.addressof(body._c()), C.addressof(tape.ops), tape.consts.ctypes.data, C.addressof(tape.c))
-    _reraise(body)
-    _check(rc)
-    return tape
+    return _record(nova_lib.vdf_nova_walk_body_record, field, body, RoundTape())
 
 
 def walk_tape_eval(field: int, tape: RoundTape, inv, entries: np.ndarray, n: int, rounds: int, trace: "np.ndarray | None" = None,
@@ -555,11 +567,7 @@ def record_forward_body(body: WalkBody, field: int = FIELD_FQ) -> RoundTape:
     """Host only: a WalkBody whose `next` argument is the entry stood on (entry j) and whose result is entry j + 1 -- the slow
     direction, with ConstraintSystem.pow -- recorded into the forward walk tape Context.round_tape_forward_walk /
     round_tape_eval_batch / forward_tape_eval take."""
-    tape = RoundTape()
-    rc = nova_lib.vdf_nova_forward_body_record(field, C.addressof(body._c()), C.addressof(tape.ops), tape.consts.ctypes.data, C.addressof(tape.c))
-    _reraise(body)
-    _check(rc)
-    return tape
+    return _record(nova_lib.vdf_nova_forward_body_record, field, body, RoundTape())
 
 
 def forward_tape_eval(field: int, tape: RoundTape, inv, entries: np.ndarray, n: int, rounds: int, checkpoints: "np.ndarray | None" = None,
@@ -660,6 +668,17 @@ class ConstraintSystem:
         if not 0 <= e < 1 << 256:
             raise ValueError("the exponent is an integer in [0, 2^256)")
         return nova_lib.vdf_cs_pow(self.h, a, (C.c_uint64 * 4)(*[(e >> (64 * k)) & (2**64 - 1) for k in range(4)]))
+
+    def tab(self, table: np.ndarray, col: int) -> int:
+        """The round constant of round j from a table: table[j mod rows][col], table a C-contiguous uint64[rows, cols, 4] array in
+        Montgomery form that the caller keeps alive and hands over UNCHANGED in every call -- a body has one table, named by its
+        address (include/vdf_nova.h vdf_cs_tab).  Legal only while a round, walk or forward body is recorded."""
+        if not (isinstance(table, np.ndarray) and table.dtype == np.dtype("<u8") and table.ndim == 3 and table.shape[2] == 4 and
+                table.flags["C_CONTIGUOUS"]):
+            raise ValueError("a table is a C-contiguous uint64[rows, cols, 4] array")
+        if _RECORDINGS:                        # (outside record_*_body nothing is kept: the caller keeps the table alive)
+            _RECORDINGS[-1][table.ctypes.data] = table
+        return nova_lib.vdf_cs_tab(self.h, table.ctypes.data, table.shape[0], table.shape[1], col)
 
     def pow_chain(self, a: int, steps) -> int:
         """a ^ E by the caller's addition chain: steps = [(src, squarings, mul, dst)] (include/vdf_hip.h vdf_pow_step; POW_ACC /
