@@ -412,11 +412,11 @@ int  vdf_minroot_forward_segment_lanes(vdf_ctx* ctx, int field, const vdf_fe* tr
  * THE TABLE: one per tape, tab_rows x tab_cols elements (at most VDF_TAPE_MAX_TAB_ROWS x VDF_TAPE_MAX_TAB_COLS: 1 MiB), row-major,
  * canonical Montgomery form; tab_rows = tab_cols = 0 and table = NULL for a tape without one.  Unlike ops and consts it does NOT
  * travel in the kernel arguments (it would not fit, and a lane's row is a per-lane value: arguments indexed by one would go to
- * scratch): for the six launchers of this header `table` is memory a kernel may read in place, as advice and entries are --
+ * scratch): for the seven launchers of this header `table` is memory a kernel may read in place, as advice and entries are --
  * vdf_dev_alloc or vdf_host_alloc, checked with vdf_ptr_is_device; for the host evaluators of vdf_nova.h it is host memory.  A TAB
  * is a per-lane 32-byte load from it.  Nothing on the device can index out of range: the row is below tab_rows by construction
  * and the column is checked before the launch.  A tape that holds a TAB launches kernels of its own (k_round_tape_tab,
- * k_round_tape_lanes_tab, k_tape_walk_tab, k_tape_walk_lanes_tab, k_tape_forward_walk_tab); every other tape launches the kernels
+ * k_round_tape_lanes_tab, k_tape_walk_tab, k_tape_walk_lanes_tab, k_tape_forward_walk_tab, k_tape_rebuild_lanes_tab); every other tape launches the kernels
  * it always did.  Refused with VDF_ERR_BAD_ARG naming the op: a TAB with tab_rows = 0, a >= tab_cols or b != 0; and naming the
  * table: one dimension 0 beside a non-zero one, a cap exceeded, a null table with tab_rows > 0.
  * THE STRUCT GREW at its end by table, tab_rows, tab_cols (vdf_version r2): callers are rebuilt, and one that fills the struct
@@ -445,7 +445,7 @@ typedef struct vdf_round_tape {
 /* Runs the tape over repetitions 0 .. t - 1: out (device, t * n_vars elements) gets the variables, repetition-major.  inv: n_inv
  * elements in HOST memory; tape: host memory -- both travel as kernel arguments (no staging copy, no synchronisation).  advice:
  * device memory; tape->table (if any): device-readable memory, "a device pointer where host memory is read or the reverse"
- * otherwise, in all six launchers.  Values are whatever the ops make of the advice: nothing is checked against a constraint. */
+ * otherwise, in all seven launchers.  Values are whatever the ops make of the advice: nothing is checked against a constraint. */
 int  vdf_round_tape_run(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uint64_t t, const vdf_fe* inv, const vdf_fe* advice,
                         vdf_fe* out);
 /* The same for `lanes` advice arrays at once, ONE launch (kernel k_round_tape_lanes, the lane in the grid's second dimension):
@@ -578,6 +578,34 @@ typedef struct vdf_pow_step { uint8_t src, squarings, mul, dst; } vdf_pow_step;
 int  vdf_round_tape_forward_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n,
                                  uint64_t rounds, vdf_fe* checkpoints, uint64_t every, size_t cp_stride, vdf_fe* trace,
                                  size_t walk_stride, uint64_t base, uint64_t j_base, uint64_t j_walk_step);
+/* ---- traces rebuilt by forward tapes: vdf_round_tape_walk_lanes ascending -----------------------------------------------------
+ * For a round with no cheap inverse (a Rescue-shaped round has a root layer AND a power layer; a lossy mix has no inverse at all):
+ * one lane per checkpoint interval walks UP from the checkpoint below with the chain's own forward tape, writes the entries it
+ * produces where vdf_cs_repeat reads its advice, and is compared with the checkpoint above.  The tape is read under the rules of a
+ * forward walk tape (ADV with b = 0 only; POW, POWC and TAB admitted).  The groups are vdf_round_tape_walk_lanes': group G =
+ * w / group = g * lanes + l is lane l of step g; group = 0: everything is group 0 and group_stride is ignored.  Strides are in ENTRIES.
+ * `base` = the rounds the walks have behind them.  Before round r (r = 0 .. rounds - 1) walk w stands on local index
+ * k = (w % group) * walk_stride + base + r, and in that round it
+ *   sees VDF_TAPE_J = j_base[l] + g * j_group_step + k (modulo 2^64): the index of the entry it stands on, the j of the round body's
+ *   repetition j -- the value the descending walk sees when it PRODUCES that entry, so one chain's two tapes take the same j_base;
+ *   writes the entry it produced to trace[(G * group_stride + k + 1) * n_adv]                  (trace: device, or NULL).
+ * heads != 0: the first walk of each group also writes the entry it stands on before round 0 of the call, at local index `base`.
+ * With walk_stride = every and slices that add up to `every`, one window's launches leave complete traces 0 .. t per group; the
+ * interior boundaries are written once each, by the walk below -- its landing, not the checkpoint (the two are compared).
+ * expect / ok as in the descending call: ok[w] = 1 iff the entry the walk stands on after the call equals expect[w] in every column.
+ * entries[w] is overwritten with where the walk stands afterwards.  inv (lanes * n_inv elements, lane-major) and j_base (`lanes`
+ * counters) are HOST memory and travel in the kernel arguments; a thread keeps its lane's inv in n_inv more slots of LDS.
+ * Kernels: k_tape_rebuild_lanes, and k_tape_rebuild_lanes_tab for a tape that holds a TAB; lanes = 1 is the same kernel.
+ * Refused with VDF_ERR_BAD_ARG before anything is launched: everything vdf_round_tape_forward_walk refuses of a tape; lanes outside
+ * 1 .. VDF_TAPE_MAX_LANES, lanes * n_inv > VDF_TAPE_MAX_INV, a null j_base; expect without ok; with a trace and more than one walk
+ * per group, base + rounds > walk_stride; n_slots + 2 * n_adv + n_inv + (the largest n_tmp of the tape's chains) >
+ * VDF_WALK_MAX_SLOTS; rounds * max(1, products per round) > VDF_FORWARD_TAPE_MAX_WORK; a device pointer where host memory is read
+ * or the reverse.  n = 0 or rounds = 0 do nothing.
+ * Exact: entries, trace and ok are byte for byte vdf_nova_forward_tape_rebuild_eval_lanes' (vdf_nova.h). */
+int  vdf_round_tape_rebuild_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* forward_tape, size_t lanes, const vdf_fe* inv,
+                                  vdf_fe* entries, size_t n, uint64_t rounds, vdf_fe* trace, size_t walk_stride, uint64_t base,
+                                  size_t group, size_t group_stride, const uint64_t* j_base, uint64_t j_group_step, int heads,
+                                  const vdf_fe* expect, int32_t* ok);
 /* vdf_minroot_eval_batch for a forward walk tape: rounds_total rounds from initial[w] (n x n_adv elements), cut into launches of
  * launch_rounds (0 = the largest count VDF_FORWARD_TAPE_MAX_WORK allows the tape, at most 1,024) enqueued on the context's stream.
  * every = 0: out_entries[w * n_adv] = the final entry of chain w (n entries).  every > 0 (it must divide rounds_total,

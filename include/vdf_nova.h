@@ -621,6 +621,14 @@ int  vdf_nova_forward_body_record(int field, const vdf_walk_body* b, vdf_tape_op
 int  vdf_nova_forward_tape_eval(int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n, uint64_t rounds,
                                 vdf_fe* checkpoints, uint64_t every, size_t cp_stride, vdf_fe* trace, size_t walk_stride, uint64_t base,
                                 uint64_t j_base, uint64_t j_walk_step);
+/* Host only.  vdf_round_tape_rebuild_lanes (vdf_hip.h) restated on the host: the same arguments, the same refusals (the rules of a
+ * forward walk tape, the caps on lanes and lanes * n_inv, a null j_base, expect without ok, base + rounds > walk_stride, the slot cap
+ * with n_inv and the chains' n_tmp counted, the work cap), every pointer host memory -- the reference of the device path, byte for
+ * byte.  The index arithmetic is the launcher's own statement (csrc/tape_rebuild.h), the interpreter the host's. */
+int  vdf_nova_forward_tape_rebuild_eval_lanes(int field, const vdf_round_tape* forward_tape, size_t lanes, const vdf_fe* inv, vdf_fe* entries,
+                                              size_t n, uint64_t rounds, vdf_fe* trace, size_t walk_stride, uint64_t base, size_t group,
+                                              size_t group_stride, const uint64_t* j_base, uint64_t j_group_step, int heads,
+                                              const vdf_fe* expect, int32_t* ok);
 
 /* public_params / prove_step / verify for a custom primary step circuit (the secondary stays TrivialTestCircuit).
  * z0, zi: `arity` elements.  compress, verify_compressed and the wire formats work on such proofs unchanged. */
@@ -712,14 +720,49 @@ int  vdf_nova_public_params_custom_tuned(vdf_ctx* ctx, int field, const vdf_step
  * circuit has no early rows, and mode 2 is mode 1 for it.
  * Out of scope for custom chains: custom_ahead for steps not driven by a chain (plain vdf_nova_prove_step_custom keeps the schedule
  * of custom_ahead = 0: the library does not know its next advice), a second vdf_cs_repeat, a streaming eval_and_prove, lanes of
- * different length. */
+ * different length.
+ *
+ * ASCENDING CHAINS: rounds without a cheap inverse.  A walk tape may hold no power, so the constructors above serve rounds whose
+ * inverse direction is a handful of products.  A Rescue-shaped round (a root layer and a power layer: a 254-bit exponentiation in
+ * BOTH directions) or a round with a lossy mix (no inverse at all) has no such tape.  vdf_nova_custom_chain_from_checkpoints_forward
+ * and vdf_nova_custom_chain_lanes_from_checkpoints_forward build the same object from the chain's own FORWARD tape (the one
+ * vdf_round_tape_eval_batch evaluated it with; POW, POWC and TAB admitted): one walk per checkpoint interval starts on the
+ * checkpoint BELOW it, walks up, and is compared with the checkpoint ABOVE.  Checkpoints, lane_stride, inv, the copy of the table
+ * and the rule that tab_rows divides t and every j_base are as above.  j_base means the same number in both directions -- the
+ * VDF_TAPE_J of the round between entries 0 and 1 -- so one chain's two tapes take the same argument.  A slice with `done` rounds
+ * behind it is vdf_round_tape_rebuild_lanes(rounds = now, base = done, walk_stride = every, group = t / every, group_stride = t + 1,
+ * j_base[l] = the lane's + first * t, j_group_step = t, heads = 1), expect and ok only in the slice that finishes; lanes = 1 is the
+ * same call.  launch_rounds = 0 means min(1,024, VDF_FORWARD_TAPE_MAX_WORK / the tape's products per round), and a larger value of
+ * the caller's is LOWERED to that bound, not refused (a launch of a power tape may not hold a queue longer):
+ * vdf_nova_custom_chain_launch_rounds says what a value becomes.  A walk that misses reads "step k[, lane l]: a walk did not land on
+ * the checkpoint above it".  Refused with VDF_ERR_BAD_ARG: what vdf_round_tape_rebuild_lanes refuses of the tape, and the list above.
+ * Everything above the constructors -- materialize, release, memory, host_bytes, advice, vdf_cs_step_advice, both provers,
+ * VDF_CUSTOM_CHECK_STEPS, custom_ahead, both orientations -- works unchanged above an ascending chain.  A capability and a matter of
+ * resident memory (checkpoints, not traces), NOT of speed: a lane spends about 0.1 ms per round of a fifth root, so an ascending
+ * chain wants dense checkpoints, and a round WITH a cheap inverse keeps its descending tape. */
 typedef struct vdf_custom_chain vdf_custom_chain;
+enum { VDF_CHAIN_DESCENDING = 0, VDF_CHAIN_ASCENDING = 1 };
 #define VDF_CUSTOM_CHECK_STEPS 1u
 int  vdf_nova_custom_chain_from_checkpoints(int field, const vdf_round_tape* walk_tape, const vdf_fe* inv, uint64_t t, uint64_t every,
                                             size_t num_steps, const vdf_fe* checkpoints, uint64_t j_base, vdf_custom_chain** out);
 int  vdf_nova_custom_chain_lanes_from_checkpoints(int field, const vdf_round_tape* walk_tape, const vdf_fe* inv, uint64_t t, uint64_t every,
                                                   size_t num_steps, size_t lanes, const vdf_fe* checkpoints, size_t lane_stride,
                                                   const uint64_t* j_base, vdf_custom_chain** out);
+int  vdf_nova_custom_chain_from_checkpoints_forward(int field, const vdf_round_tape* forward_tape, const vdf_fe* inv, uint64_t t,
+                                                    uint64_t every, size_t num_steps, const vdf_fe* checkpoints, uint64_t j_base,
+                                                    vdf_custom_chain** out);
+int  vdf_nova_custom_chain_lanes_from_checkpoints_forward(int field, const vdf_round_tape* forward_tape, const vdf_fe* inv, uint64_t t,
+                                                          uint64_t every, size_t num_steps, size_t lanes, const vdf_fe* checkpoints,
+                                                          size_t lane_stride, const uint64_t* j_base, vdf_custom_chain** out);
+/* VDF_CHAIN_DESCENDING or VDF_CHAIN_ASCENDING; -1 for NULL */
+int  vdf_nova_custom_chain_direction(const vdf_custom_chain* chain);
+/* the launch_rounds a job of this chain runs with when the caller asks for `launch_rounds`: 0 is first replaced by the chain's own
+ * default (_set_launch_rounds; 0 until set); then the value itself for a descending chain (0 stays 0: walk_slice's 1,024), the
+ * bound of an ascending chain for 0 or anything above it */
+int  vdf_nova_custom_chain_launch_rounds(const vdf_custom_chain* chain, uint64_t launch_rounds, uint64_t* out);
+/* the rounds per launch of the jobs whose caller asks for 0 -- vdf_nova_prove_recursively_custom always does: how a caller of the
+ * prover cuts the walks of its windows finer than 1,024 rounds (0: back to the default).  Either direction. */
+int  vdf_nova_custom_chain_set_launch_rounds(vdf_custom_chain* chain, uint64_t launch_rounds);
 int  vdf_nova_custom_chain_materialize(vdf_ctx* ctx, vdf_custom_chain* chain, size_t first, size_t count, int wait, uint64_t launch_rounds,
                                        int* bad);
 int  vdf_nova_custom_chain_release(vdf_custom_chain* chain, size_t first, size_t count);

@@ -91,6 +91,7 @@ PROTOTYPES = {
     "vdf_ptr_is_device": (_i, [_vp]),
     "vdf_round_tape_walk": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _u64, _vp, _sz, _sz, _sz, _sz, _u64, _u64, _i, _vp, _vp]),
     "vdf_round_tape_walk_lanes": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _sz, _u64, _vp, _sz, _sz, _sz, _sz, _vp, _u64, _i, _vp, _vp]),
+    "vdf_round_tape_rebuild_lanes": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _sz, _u64, _vp, _sz, _u64, _sz, _sz, _vp, _u64, _i, _vp, _vp]),
     "vdf_round_tape_forward_walk": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _u64, _vp, _u64, _sz, _vp, _sz, _u64, _u64, _u64]),
     "vdf_round_tape_eval_batch": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _u64, _u64, _u64, _u64, _u64, _vp]),
     "vdf_minroot_step_segment_packed": (_i, [_vp, _i, _vp, _u64, _vp, _vp, _vp, _vp]),

@@ -1596,6 +1596,21 @@ int vdf_round_tape_forward_walk(vdf_ctx* ctx, int field, const vdf_round_tape* t
   });
 }
 
+int vdf_round_tape_rebuild_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* forward_tape, size_t lanes, const vdf_fe* inv, vdf_fe* entries,
+                                 size_t n, uint64_t rounds, vdf_fe* trace, size_t walk_stride, uint64_t base, size_t group, size_t group_stride,
+                                 const uint64_t* j_base, uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok) {
+  return guarded(ctx, [&]() -> Status {
+    if (ptr_is_device(j_base)) return Status{VDF_ERR_BAD_ARG, "the tape, inv and j_base live in host memory"};
+    VDF_TRY(forward_tape_on_host(forward_tape, inv));
+    if (n && rounds && (!ptr_is_device(entries) || (trace && !ptr_is_device(trace)) || (expect && !ptr_is_device(expect)) || (ok && !ptr_is_device(ok))))
+      return Status{VDF_ERR_BAD_ARG, "entries, trace, expect and ok live in device memory"};
+    VDF_TRY(vdf::vec_round_tape_rebuild_lanes(field, forward_tape, lanes, inv, entries, n, rounds, trace, walk_stride, base, group, group_stride,
+                                              j_base, j_group_step, heads, expect, ok, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
 int vdf_round_tape_eval_batch(vdf_ctx* ctx, int field, const vdf_round_tape* tape, const vdf_fe* inv, const vdf_fe* initial, size_t n,
                               uint64_t rounds_total, uint64_t every, uint64_t launch_rounds, uint64_t j_base, uint64_t j_walk_step,
                               vdf_fe* out_entries) {

@@ -1,6 +1,8 @@
 // libvdf_nova.so, part 2c: the chain of a custom step circuit (vdf_custom_chain, include/vdf_nova.h) -- what circuits_host.cpp is
 // to the built-in kinds: the checkpoints of a chain on the host, and per step a device trace rebuilt by the chain's walk tape
 // (vdf_round_tape_walk; vdf_round_tape_walk_lanes for a chain of several lanes) on a side queue, a window ahead of the prover.
+// An ASCENDING chain (rounds without a cheap inverse) rebuilds them by its forward tape instead (vdf_round_tape_rebuild_lanes): the
+// two hooks that know a direction are stage_walks and launch; the window above them does not.
 #include <atomic>
 #include "nova_internal.hpp"
 
@@ -13,6 +15,13 @@ struct vdf_custom_chain final : WalkOwner {
   int field = VDF_FIELD_FQ;
   uint64_t t = 0, every = 0;
   size_t lanes = 1;                        // chains side by side in every step (vdf_cs_repeat_lanes)
+  bool ascending = false;                  // the tape is the chain's forward tape: walks start below their interval and land above it
+  uint64_t launch_bound = 0;               // ascending: the rounds one launch of the tape may run, min(1,024, the work cap / products)
+  uint64_t launch_default = 0;             // what a job runs with when its caller asks for 0 (vdf_nova_custom_chain_set_launch_rounds)
+  uint64_t launch_rounds_of(uint64_t asked) const {
+    if (!asked) asked = launch_default;
+    return !ascending ? asked : asked ? std::min(asked, launch_bound) : launch_bound;
+  }
   std::vector<uint64_t> j_base;            // per lane
   size_t per = 0, na = 0;                  // walks per step AND LANE, elements per entry
   std::vector<vdf_tape_op> ops;
@@ -30,14 +39,18 @@ struct vdf_custom_chain final : WalkOwner {
   TraceSlot& slot(size_t k) override { return v[k]; }
   void shape(size_t, WalkJob* j) override {
     j->every = every;
+    j->launch_rounds = launch_rounds_of(j->launch_rounds);      // (set by the window before it asks for the shape)
     j->trace_bytes = lanes * (t + 1) * na * 32;
     j->step_walks = lanes * per;
     j->entry_bytes = na * 32;
   }
   // walk li * per + m stands on the checkpoint above interval m of step lo + li and must land on the one below it: both runs
   // are contiguous in the lane's checkpoints; with more lanes than one they are gathered step-major, lane-minor (the walks'
-  // order), into a staging vector that lives until the job resolves
+  // order), into a staging vector that lives until the job resolves.  Ascending: the same two runs, the other way round.
   void stage_walks(const WalkJob& j, const void** starts, const void** expects) override {
+    stage_descending(j, ascending ? expects : starts, ascending ? starts : expects);
+  }
+  void stage_descending(const WalkJob& j, const void** starts, const void** expects) {
     const size_t lo = j.steps[0];
     *expects = cp.data() + lo * per * na;
     *starts = cp.data() + lo * per * na + na;
@@ -70,7 +83,11 @@ struct vdf_custom_chain final : WalkOwner {
   int launch(vdf_ctx* q, const WalkJob& j, const WalkScratch& s, uint64_t rounds, uint64_t top, int last) override {
     uint64_t jb[VDF_TAPE_MAX_LANES];
     for (size_t l = 0; l < lanes; ++l) jb[l] = j_base[l] + (uint64_t)j.steps[0] * t;
-    if (lanes == 1)
+    if (ascending)                                   // top = every - done (walk_slice): the rounds behind the walks are every - top
+      HIPCALL(q, vdf_round_tape_rebuild_lanes(q, field, &tape, lanes, (const vdf_fe*)inv.data(), (vdf_fe*)s.d_walk, j.walks, rounds, (vdf_fe*)j.block->d,
+                                              (size_t)every, every - top, per, (size_t)(t + 1), jb, t, 1, last ? (const vdf_fe*)s.d_expect : nullptr,
+                                              last ? s.h_ok : nullptr));
+    else if (lanes == 1)
       HIPCALL(q, vdf_round_tape_walk(q, field, &tape, (const vdf_fe*)inv.data(), (vdf_fe*)s.d_walk, j.walks, rounds, (vdf_fe*)j.block->d, (size_t)every,
                                      (size_t)top, per, (size_t)(t + 1), jb[0], t, last, last ? (const vdf_fe*)s.d_expect : nullptr, last ? s.h_ok : nullptr));
     else                                             // every lane of every step of the window in ONE launch: group G = step * lanes + lane
@@ -80,7 +97,7 @@ struct vdf_custom_chain final : WalkOwner {
     return VDF_OK;
   }
   std::string missed(size_t k, size_t walk) override {
-    return "step " + std::to_string(k) + (lanes > 1 ? ", lane " + std::to_string(walk / per) : std::string()) + ": a walk did not land on the checkpoint below it";
+    return "step " + std::to_string(k) + (lanes > 1 ? ", lane " + std::to_string(walk / per) : std::string()) + ": a walk did not land on the checkpoint " + (ascending ? "above" : "below") + " it";
   }
 };
 
@@ -108,14 +125,14 @@ int vdf_nova_custom_chain_slice(uint64_t every, uint64_t launch_rounds, uint64_t
   walk_slice(every, launch_rounds, done, budget, rounds, top, last);
   return VDF_OK;
 }
-int vdf_nova_custom_chain_from_checkpoints(int fid, const vdf_round_tape* walk_tape, const vdf_fe* inv, uint64_t t, uint64_t every,
-                                           size_t num_steps, const vdf_fe* checkpoints, uint64_t j_base, vdf_custom_chain** out) {
-  const size_t stride = every && t && num_steps <= ((size_t)1 << 40) ? num_steps * (size_t)(t / every) + 1 : 1;      // (refused below otherwise)
-  return vdf_nova_custom_chain_lanes_from_checkpoints(fid, walk_tape, inv, t, every, num_steps, 1, checkpoints, stride, &j_base, out);
+// one chain's checkpoints: the stride of a single lane (refused by the constructor otherwise)
+static size_t single_stride(uint64_t t, uint64_t every, size_t num_steps) {
+  return every && t && num_steps <= ((size_t)1 << 40) ? num_steps * (size_t)(t / every) + 1 : 1;
 }
-int vdf_nova_custom_chain_lanes_from_checkpoints(int fid, const vdf_round_tape* walk_tape, const vdf_fe* inv, uint64_t t, uint64_t every,
-                                                 size_t num_steps, size_t lanes, const vdf_fe* checkpoints, size_t lane_stride,
-                                                 const uint64_t* j_base, vdf_custom_chain** out) {
+// all four constructors: `walk_tape` is the chain's walk tape, or (ascending) its forward tape
+static int chain_from_checkpoints(int fid, const vdf_round_tape* walk_tape, bool ascending, const vdf_fe* inv, uint64_t t, uint64_t every,
+                                  size_t num_steps, size_t lanes, const vdf_fe* checkpoints, size_t lane_stride, const uint64_t* j_base,
+                                  vdf_custom_chain** out) {
   return nova_guard([&]() -> int {
     if (!out) return fail(VDF_ERR_BAD_ARG, "null out");
     *out = nullptr;
@@ -127,7 +144,10 @@ int vdf_nova_custom_chain_lanes_from_checkpoints(int fid, const vdf_round_tape* 
     if (lanes == 0 || lanes > VDF_TAPE_MAX_LANES) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_TAPE_MAX_LANES");
     // the check the walk's launcher applies, by its host restatement with nothing to walk (a null `inv` the tape reads included):
     // vdf_round_tape_walk's for one lane, vdf_round_tape_walk_lanes' (lanes * n_inv, n_inv more slots) for more
-    {
+    if (ascending) {                                   // vdf_round_tape_rebuild_lanes', for any lanes
+      const int rc = eval_forward_tape_rebuild_lanes(fid, walk_tape, lanes, (const Fe*)inv, nullptr, 0, 0, nullptr, 0, 0, 0, 0, j_base, 0, 0, nullptr, nullptr);
+      if (rc != VDF_OK) return rc;
+    } else {
       const int rc = lanes == 1 ? eval_walk_tape(fid, walk_tape, (const Fe*)inv, nullptr, 0, 0, nullptr, 0, 0, 0, 0, 0, 0, 0, nullptr, nullptr)
                                 : eval_walk_tape_lanes(fid, walk_tape, lanes, (const Fe*)inv, nullptr, 0, 0, nullptr, 0, 0, 0, 0, j_base, 0, 0, nullptr, nullptr);
       if (rc != VDF_OK) return rc;
@@ -145,6 +165,8 @@ int vdf_nova_custom_chain_lanes_from_checkpoints(int fid, const vdf_round_tape* 
     if (lane_stride < entries || lane_stride > ((size_t)1 << 44)) return fail(VDF_ERR_BAD_ARG, "lane_stride must be at least num_steps * (t / every) + 1");
     std::unique_ptr<vdf_custom_chain> c(new vdf_custom_chain());
     c->field = fid; c->t = t; c->every = every; c->lanes = lanes; c->per = per; c->na = na;
+    c->ascending = ascending;
+    if (ascending) c->launch_bound = forward_tape_launch_bound(walk_tape);
     c->j_base.assign(j_base, j_base + lanes);
     c->ops.assign(walk_tape->ops, walk_tape->ops + walk_tape->n_ops);
     c->consts.assign((const Fe*)walk_tape->consts, (const Fe*)walk_tape->consts + walk_tape->n_consts);
@@ -168,6 +190,35 @@ int vdf_nova_custom_chain_lanes_from_checkpoints(int fid, const vdf_round_tape* 
     *out = c.release();
     return VDF_OK;
   });
+}
+int vdf_nova_custom_chain_from_checkpoints(int fid, const vdf_round_tape* walk_tape, const vdf_fe* inv, uint64_t t, uint64_t every,
+                                           size_t num_steps, const vdf_fe* checkpoints, uint64_t j_base, vdf_custom_chain** out) {
+  return chain_from_checkpoints(fid, walk_tape, false, inv, t, every, num_steps, 1, checkpoints, single_stride(t, every, num_steps), &j_base, out);
+}
+int vdf_nova_custom_chain_lanes_from_checkpoints(int fid, const vdf_round_tape* walk_tape, const vdf_fe* inv, uint64_t t, uint64_t every,
+                                                 size_t num_steps, size_t lanes, const vdf_fe* checkpoints, size_t lane_stride,
+                                                 const uint64_t* j_base, vdf_custom_chain** out) {
+  return chain_from_checkpoints(fid, walk_tape, false, inv, t, every, num_steps, lanes, checkpoints, lane_stride, j_base, out);
+}
+int vdf_nova_custom_chain_from_checkpoints_forward(int fid, const vdf_round_tape* forward_tape, const vdf_fe* inv, uint64_t t, uint64_t every,
+                                                   size_t num_steps, const vdf_fe* checkpoints, uint64_t j_base, vdf_custom_chain** out) {
+  return chain_from_checkpoints(fid, forward_tape, true, inv, t, every, num_steps, 1, checkpoints, single_stride(t, every, num_steps), &j_base, out);
+}
+int vdf_nova_custom_chain_lanes_from_checkpoints_forward(int fid, const vdf_round_tape* forward_tape, const vdf_fe* inv, uint64_t t,
+                                                         uint64_t every, size_t num_steps, size_t lanes, const vdf_fe* checkpoints,
+                                                         size_t lane_stride, const uint64_t* j_base, vdf_custom_chain** out) {
+  return chain_from_checkpoints(fid, forward_tape, true, inv, t, every, num_steps, lanes, checkpoints, lane_stride, j_base, out);
+}
+int vdf_nova_custom_chain_direction(const vdf_custom_chain* c) { return !c ? -1 : c->ascending ? VDF_CHAIN_ASCENDING : VDF_CHAIN_DESCENDING; }
+int vdf_nova_custom_chain_launch_rounds(const vdf_custom_chain* c, uint64_t launch_rounds, uint64_t* out) {
+  if (!c || !out) return fail(VDF_ERR_BAD_ARG, "null argument");
+  *out = c->launch_rounds_of(launch_rounds);
+  return VDF_OK;
+}
+int vdf_nova_custom_chain_set_launch_rounds(vdf_custom_chain* c, uint64_t launch_rounds) {
+  if (!c) return fail(VDF_ERR_BAD_ARG, "null argument");
+  c->launch_default = launch_rounds;
+  return VDF_OK;
 }
 int vdf_nova_custom_chain_materialize(vdf_ctx* ctx, vdf_custom_chain* c, size_t first, size_t count, int wait, uint64_t launch_rounds,
                                       int* bad) {

@@ -105,6 +105,12 @@ int eval_walk_tape_lanes(int field, const vdf_round_tape* tape, size_t lanes, co
 // vdf_round_tape_forward_walk on the host (vdf_nova_forward_tape_eval): the same arguments, the same refusals, host memory
 int eval_forward_tape(int field, const vdf_round_tape* tape, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* checkpoints,
                       uint64_t every, size_t cp_stride, Fe* trace, size_t walk_stride, uint64_t base, uint64_t j_base, uint64_t j_walk_step);
+// vdf_round_tape_rebuild_lanes on the host (vdf_nova_forward_tape_rebuild_eval_lanes): the same arguments, the same refusals, host memory
+int eval_forward_tape_rebuild_lanes(int field, const vdf_round_tape* tape, size_t lanes, const Fe* inv, Fe* entries, size_t n, uint64_t rounds,
+                                    Fe* trace, size_t walk_stride, uint64_t base, size_t group, size_t group_stride, const uint64_t* j_base,
+                                    uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok);
+// the rounds one launch of a forward tape may run: min(1,024, VDF_FORWARD_TAPE_MAX_WORK / products); 0 for a tape the FORWARD rules refuse
+uint64_t forward_tape_launch_bound(const vdf_round_tape* tape);
 
 // The periodic rows of a repeat, as detect_periodic_rows read them off a shape's triples (include/vdf_hip.h vdf_periodic_rows):
 // rows [row_begin, row_begin + row_count) are repetitions lead .. t - 1, and `view` is what the kernel and the host evaluator take.

@@ -6,6 +6,7 @@
 #include "rounds.hpp"
 #include "../minroot_chain.h"
 #include "../tape_rules.h"
+#include "../tape_rebuild.h"
 
 using namespace vdfnova;
 
@@ -423,6 +424,51 @@ int eval_forward_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entr
     for (size_t c = 0; c < na; ++c) entries[w * na + c] = stand[c];
   }
   return VDF_OK;
+}
+
+// vdf_round_tape_rebuild_lanes on the host: the tape's rules are FORWARD's, the other refusals and the whole of the index
+// arithmetic tape_rebuild.h's -- the statement the launcher and its kernel read
+int eval_forward_tape_rebuild_lanes(int fid, const vdf_round_tape* tp, size_t lanes, const Fe* inv, Fe* entries, size_t n, uint64_t rounds,
+                                    Fe* trace, size_t walk_stride, uint64_t base, size_t group, size_t group_stride, const uint64_t* j_base,
+                                    uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok) {
+  if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
+  vdftape::Info ti;
+  const int rc = check_tape(tp, vdftape::FORWARD, &ti);
+  if (rc != VDF_OK) return rc;
+  bool nothing = false;
+  const std::string why = vdfrebuild::refuse(tp, ti, lanes, (const vdf_fe*)inv, j_base, n, rounds, entries, trace, walk_stride, base, group, expect, ok, &nothing);
+  if (!why.empty()) return fail(VDF_ERR_BAD_ARG, why);
+  if (nothing) return VDF_OK;
+  uint64_t grp = group, gstride = group_stride;
+  vdfrebuild::groups(n, &grp, &gstride);
+  const Field& F = field(fid);
+  const size_t na = tp->n_adv;
+  Fe s[VDF_TAPE_MAX_SLOTS], stand[VDF_TAPE_MAX_ADV], prod[VDF_TAPE_MAX_ADV];
+  const Fe* const adv[2] = {stand, nullptr};      // an ascending walk stands on entry j
+  for (size_t w = 0; w < n; ++w) {
+    const vdfrebuild::Place p = vdfrebuild::place(w, grp, walk_stride, base, (uint32_t)lanes);
+    const Fe* lane_inv = inv + p.l * tp->n_inv;
+    uint64_t j = vdfrebuild::counter(p, j_base[p.l], j_group_step);
+    for (size_t c = 0; c < na; ++c) stand[c] = entries[w * na + c];
+    if (trace && heads && p.first)
+      for (size_t c = 0; c < na; ++c) trace[vdfrebuild::trace_entry(p, gstride, p.k) * na + c] = stand[c];
+    for (uint64_t r = 0; r < rounds; ++r, ++j) {
+      run_tape_round(tp, F, j, lane_inv, adv, s, prod);
+      for (size_t c = 0; c < na; ++c) stand[c] = prod[c];
+      if (trace)
+        for (size_t c = 0; c < na; ++c) trace[vdfrebuild::trace_entry(p, gstride, p.k + r + 1) * na + c] = stand[c];
+    }
+    for (size_t c = 0; c < na; ++c) entries[w * na + c] = stand[c];
+    if (expect) ok[w] = memcmp(stand, expect + w * na, na * sizeof(Fe)) == 0;
+  }
+  return VDF_OK;
+}
+
+// the rounds one launch of a forward tape may run: min(1,024, VDF_FORWARD_TAPE_MAX_WORK / products); 0 for a tape FORWARD refuses
+uint64_t forward_tape_launch_bound(const vdf_round_tape* tp) {
+  vdftape::Info ti;
+  if (!vdftape::check(tp, vdftape::FORWARD, &ti).empty()) return 0;
+  return std::min<uint64_t>(1024, VDF_FORWARD_TAPE_MAX_WORK / ti.products);
 }
 
 }  // namespace vdfnova
@@ -911,6 +957,14 @@ int vdf_nova_forward_tape_eval(int fid, const vdf_round_tape* tape, const vdf_fe
   return nova_guard([&]() -> int {
     return eval_forward_tape(fid, tape, (const Fe*)inv, (Fe*)entries, n, rounds, (Fe*)checkpoints, every, cp_stride, (Fe*)trace, walk_stride,
                              base, j_base, j_walk_step);
+  });
+}
+int vdf_nova_forward_tape_rebuild_eval_lanes(int fid, const vdf_round_tape* forward_tape, size_t lanes, const vdf_fe* inv, vdf_fe* entries, size_t n,
+                                             uint64_t rounds, vdf_fe* trace, size_t walk_stride, uint64_t base, size_t group, size_t group_stride,
+                                             const uint64_t* j_base, uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok) {
+  return nova_guard([&]() -> int {
+    return eval_forward_tape_rebuild_lanes(fid, forward_tape, lanes, (const Fe*)inv, (Fe*)entries, n, rounds, (Fe*)trace, walk_stride, base, group,
+                                           group_stride, j_base, j_group_step, heads, (const Fe*)expect, ok);
   });
 }
 

@@ -14,6 +14,7 @@
 #include "fe.cuh"
 #include "cross.cuh"
 #include "tape_rules.h"
+#include "tape_rebuild.h"
 
 namespace vdf {
 
@@ -45,8 +46,8 @@ template <class P> __device__ __forceinline__ void slot_store(uint4* lds, uint32
 }
 
 // ---- the interpreter: the ops of ONE round of a tape for one lane, the only statement of them on the device -------------------
-// Six kernels run tapes (the two round kernels, the two descending walks, the two forward walks), and five more the tapes that
-// hold a VDF_TAPE_TAB (k_*_tab, below); they differ in their setup and landing and in three ops, which a kernel hands over as its
+// Seven kernels run tapes (the two round kernels, the two descending walks, the two forward walks, the ascending rebuild), and six
+// more the tapes that hold a VDF_TAPE_TAB (k_*_tab, below); they differ in their setup and landing and in three ops, which a kernel hands over as its
 // IO: where ADV reads (global advice, or the entry stood on in LDS),
 // where INV reads (the kernel arguments from an offset, or slots of LDS) and where OUT writes (global variables, or the entry
 // produced in LDS).  ADMIT: the ops beyond the base set that the kernel's launcher lets through (pack_tape's mode) -- an op that is
@@ -441,6 +442,100 @@ __global__ __launch_bounds__(64) void k_tape_forward_walk_tab(TapeArgs tape, For
   extern __shared__ uint4 tape_slots[];
   tape_forward_walk<P, TAPE_POWC>(tape, fa, tape_slots, entries, checkpoints, trace, tab_io(ta));
 }
+
+// ---- traces rebuilt by forward tapes: k_tape_walk_lanes ascending (vdf_hip.h vdf_round_tape_rebuild_lanes) ---------------------
+// One lane per checkpoint interval, for a round with no cheap inverse: the walk stands on the checkpoint BELOW its interval, runs the
+// chain's own forward tape (POW, POWC and in the _tab kernel TAB admitted), writes every entry it produces where vdf_cs_repeat reads
+// its advice, and is compared with the checkpoint ABOVE.  The launch, the interpreter and the two entries swapped each round are
+// k_tape_forward_walk_chain's; the groups, the per-lane counter and the invariants kept in n_inv slots of LDS are
+// k_tape_walk_lanes'.  Which walk stands where and sees which counter is tape_rebuild.h's, shared with the host restatement.
+// LDS: the value file, the two entries, the chains' temporaries, the lane's invariants.
+struct RebuildArgs {
+  uint64_t n, walk_stride, base, group, group_stride, j_group_step;
+  uint32_t rounds, n_slots, heads, lanes, n_inv, chain_tmp;
+  uint64_t j_base[VDF_TAPE_MAX_LANES];
+};
+static_assert(sizeof(TapeArgs) + sizeof(RebuildArgs) + 32 + sizeof(TabArgs) <= 4096, "the tape travels in the kernel-argument segment");
+
+template <class P, class TAB = NoTab>
+__device__ __forceinline__ void tape_rebuild(const TapeArgs& tape, const RebuildArgs& ra, uint4* slots, char* entries, char* trace,
+                                             const char* expect, int32_t* ok, TAB tab = TAB()) {
+  constexpr bool HAS_TAB = !std::is_same<TAB, NoTab>::value;
+  const uint32_t lane = threadIdx.x;
+  const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
+  if (w >= ra.n) return;                             // (no barrier below: a lane touches only its own words of LDS)
+  const uint32_t na = tape.n_adv;
+  const size_t esz = (size_t)na * 32;
+  char* const ep = entries + w * esz;
+  const vdfrebuild::Place p = vdfrebuild::place(w, ra.group, ra.walk_stride, ra.base, ra.lanes);
+  uint32_t stand = ra.n_slots, prod = ra.n_slots + na;
+  const uint32_t tmp0 = ra.n_slots + 2 * na, inv0 = tmp0 + ra.chain_tmp;
+  // the lane is a per-thread value: its counter and invariants are selected ONCE, in uniform loops over the argument elements
+  uint64_t jb = 0;
+#pragma unroll 1
+  for (uint32_t q = 0; q < ra.lanes; ++q) {
+    const uint64_t x = ra.j_base[q];
+    jb = q == p.l ? x : jb;
+  }
+#pragma unroll 1
+  for (uint32_t k = 0; k < ra.n_inv; ++k) {
+    Fe<P> v = fe_zero<P>();
+#pragma unroll 1
+    for (uint32_t q = 0; q < ra.lanes; ++q) {
+      const Fe<P> x = tape_fe<P>(tape.inv[q * ra.n_inv + k]);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v.v[i] = q == p.l ? x.v[i] : v.v[i];
+    }
+    slot_store<P>(slots, inv0 + k, lane, v);
+  }
+  char* tp = trace ? trace + vdfrebuild::trace_entry(p, ra.group_stride, p.k) * esz : nullptr;      // the entry stood on
+  const bool head = tp && ra.heads && p.first;
+  for (uint32_t c = 0; c < na; ++c) {
+    const Fe<P> v = fe_load<P>(ep + c * 32);
+    slot_store<P>(slots, stand + c, lane, v);
+    if (head) fe_store<P>(tp + c * 32, v);
+  }
+  uint64_t j = vdfrebuild::counter(p, jb, ra.j_group_step);
+  if constexpr (HAS_TAB) tab.at(j);
+#pragma unroll 1
+  for (uint32_t r = 0; r < ra.rounds; ++r, ++j) {
+    const WalkIO<P, true> io = {stand, prod, inv0};
+    tape_round<P, TAPE_POWC>(tape, slots, lane, j, io, tmp0, tab);
+    if constexpr (HAS_TAB) tab.up(j + 1);
+    const uint32_t t = stand; stand = prod; prod = t;
+    if (tp) {
+      tp += esz;
+      for (uint32_t c = 0; c < na; ++c) fe_store<P>(tp + c * 32, slot_load<P>(slots, stand + c, lane));
+    }
+  }
+  // where the walk stands now: back into entries, and against the checkpoint above
+  uint32_t diff = 0;
+  for (uint32_t c = 0; c < na; ++c) {
+    const Fe<P> v = slot_load<P>(slots, stand + c, lane);
+    fe_store<P>(ep + c * 32, v);
+    if (expect) {
+      const Fe<P> e = fe_load<P>(expect + w * esz + c * 32);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) diff |= v.v[q] ^ e.v[q];
+    }
+  }
+  if (expect) ok[w] = diff == 0;
+}
+
+template <class P>
+__global__ __launch_bounds__(64) void k_tape_rebuild_lanes(TapeArgs tape, RebuildArgs ra, char* __restrict__ entries, char* __restrict__ trace,
+                                                           const char* __restrict__ expect, int32_t* __restrict__ ok) {
+  extern __shared__ uint4 tape_slots[];
+  tape_rebuild<P>(tape, ra, tape_slots, entries, trace, expect, ok);
+}
+
+template <class P>
+__global__ __launch_bounds__(64) void k_tape_rebuild_lanes_tab(TapeArgs tape, RebuildArgs ra, char* __restrict__ entries,
+                                                               char* __restrict__ trace, const char* __restrict__ expect,
+                                                               int32_t* __restrict__ ok, TabArgs ta) {
+  extern __shared__ uint4 tape_slots[];
+  tape_rebuild<P>(tape, ra, tape_slots, entries, trace, expect, ok, tab_io(ta));
+}
 // ---- periodic rows: the cross term of the rows of such rounds without the sparse matrices (vdf_hip.h vdf_periodic_rows) --------
 // k_nifs_cross_minroot_forward_lanes for a round the library did not write: one row per lane, workgroups of 256, every running /
 // fresh vector read and written as contiguous 32-byte elements.  What the hand-written stencil has in its code -- which columns a
@@ -725,6 +820,45 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tp, const vd
     else
       hipLaunchKernelGGL(chain ? k_tape_forward_walk_chain<P> : k_tape_forward_walk<P>, dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, fa,
                          bytes_of(entries), bytes_of(checkpoints), bytes_of(trace));
+  });
+}
+
+// the tape's rules are FORWARD's (tape_rules.h), the rest of the refusals tape_rebuild.h's: neither is stated here
+Status vec_round_tape_rebuild_lanes(int field, const vdf_round_tape* tp, size_t lanes, const vdf_fe* inv, void* entries, size_t n, uint64_t rounds,
+                                    void* trace, size_t walk_stride, uint64_t base, size_t group, size_t group_stride, const uint64_t* j_base,
+                                    uint64_t j_group_step, int heads, const void* expect, int32_t* ok, hipStream_t s) {
+  VDF_TRY(check_field(field));
+  vdftape::Info ti;
+  {
+    const std::string why = vdftape::check(tp, vdftape::FORWARD, &ti);
+    if (!why.empty()) return Status{VDF_ERR_BAD_ARG, why};
+  }
+  bool nothing = false;
+  {
+    const std::string why = vdfrebuild::refuse(tp, ti, lanes, inv, j_base, n, rounds, entries, trace, walk_stride, base, group, expect, ok, &nothing);
+    if (!why.empty()) return Status{VDF_ERR_BAD_ARG, why};
+  }
+  if (nothing) return Status{};
+  TapeArgs a;
+  VDF_TRY(pack_tape(tp, inv, vdftape::FORWARD, a, nullptr, lanes));
+  RebuildArgs ra;
+  std::memset(&ra, 0, sizeof(ra));
+  uint64_t grp = group, gstride = group_stride;
+  vdfrebuild::groups(n, &grp, &gstride);
+  ra.n = n; ra.walk_stride = walk_stride; ra.base = base; ra.group = grp; ra.group_stride = gstride; ra.j_group_step = j_group_step;
+  ra.rounds = (uint32_t)rounds; ra.n_slots = tp->n_slots; ra.heads = heads != 0; ra.lanes = (uint32_t)lanes; ra.n_inv = tp->n_inv;
+  ra.chain_tmp = ti.chain_tmp;
+  for (size_t l = 0; l < lanes; ++l) ra.j_base[l] = j_base[l];
+  KTimer kt(s, ti.tab ? "k_tape_rebuild_lanes_tab" : "k_tape_rebuild_lanes", (trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0) + 64.0 * tp->n_adv * (double)n);
+  const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv + ti.chain_tmp + tp->n_inv) * 2 * 64 * sizeof(uint4);
+  return with_field(field, [&](auto f) {
+    using P = tag_t<decltype(f)>;
+    if (ti.tab)
+      hipLaunchKernelGGL((k_tape_rebuild_lanes_tab<P>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, ra, bytes_of(entries), bytes_of(trace),
+                         cbytes_of(expect), ok, tab_args(tp));
+    else
+      hipLaunchKernelGGL((k_tape_rebuild_lanes<P>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, ra, bytes_of(entries), bytes_of(trace),
+                         cbytes_of(expect), ok);
   });
 }
 

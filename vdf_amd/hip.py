@@ -594,6 +594,20 @@ class Context:
                                                   _ptr(trace), walk_stride, top, group, group_stride, jb.ctypes.data, j_group_step,
                                                   int(bool(heads)), _ptr(expect), _ptr(ok)))
 
+    def round_tape_rebuild_lanes(self, field, forward_tape: "RoundTape", lanes, inv, entries, n, rounds, trace=None, walk_stride=0, base=0,
+                                 group=0, group_stride=0, j_base=None, j_group_step=0, heads=False, expect=None, ok=None) -> None:
+        """round_tape_walk_lanes ascending, by a FORWARD tape (POW, POWC and TAB admitted): walk w of group G = w // group (lane
+        G % lanes of step G // lanes) has `base` rounds behind it, stands on local index k = (w % group) * walk_stride + base + r
+        before round r, sees j_base[lane] + (G // lanes) * j_group_step + k there and writes what it produces to trace entry
+        G * group_stride + k + 1; heads: a group's first walk also writes the entry it starts on.  expect / ok (device, int32[n]):
+        ok[w] = where the walk stands afterwards equals expect[w].  inv (lanes * n_inv elements), j_base (`lanes` ints): host."""
+        jb = np.ascontiguousarray([0] * lanes if j_base is None else [int(v) % 2**64 for v in j_base], dtype="<u8")
+        if jb.size < lanes:
+            raise ValueError("j_base: one counter per lane")
+        self._check(lib.vdf_round_tape_rebuild_lanes(self.handle, field, self._tape(forward_tape), lanes, _ptr(inv), _ptr(entries), n, rounds,
+                                                     _ptr(trace), walk_stride, base, group, group_stride, jb.ctypes.data, j_group_step,
+                                                     int(bool(heads)), _ptr(expect), _ptr(ok)))
+
     def round_tape_forward_walk(self, field, tape: "RoundTape", inv, entries, n, rounds, checkpoints=None, every=0, cp_stride=0, trace=None,
                                 walk_stride=0, base=0, j_base=0, j_walk_step=0) -> None:
         """n walks of `rounds` rounds of a recorded forward body in place over `entries` (device, n x n_adv elements), one lane each;

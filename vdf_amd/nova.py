@@ -155,6 +155,12 @@ for _name, _res, _args in [
     ("vdf_nova_custom_chain_from_checkpoints", _i, [_i, _vp, _vp, _u64, _u64, _sz, _vp, _u64, C.POINTER(_vp)]),
     ("vdf_nova_custom_chain_lanes_from_checkpoints", _i, [_i, _vp, _vp, _u64, _u64, _sz, _sz, _vp, _sz, _vp, C.POINTER(_vp)]),
     ("vdf_nova_pp_repeat_lanes", _i, [_vp, C.POINTER(_u64)]),
+    ("vdf_nova_custom_chain_from_checkpoints_forward", _i, [_i, _vp, _vp, _u64, _u64, _sz, _vp, _u64, C.POINTER(_vp)]),
+    ("vdf_nova_custom_chain_lanes_from_checkpoints_forward", _i, [_i, _vp, _vp, _u64, _u64, _sz, _sz, _vp, _sz, _vp, C.POINTER(_vp)]),
+    ("vdf_nova_custom_chain_direction", _i, [_vp]),
+    ("vdf_nova_custom_chain_launch_rounds", _i, [_vp, _u64, C.POINTER(_u64)]),
+    ("vdf_nova_custom_chain_set_launch_rounds", _i, [_vp, _u64]),
+    ("vdf_nova_forward_tape_rebuild_eval_lanes", _i, [_i, _vp, _sz, _vp, _vp, _sz, _u64, _vp, _sz, _u64, _sz, _sz, _vp, _u64, _i, _vp, _vp]),
     ("vdf_nova_custom_chain_materialize", _i, [_vp, _vp, _sz, _sz, _i, _u64, _vp]),
     ("vdf_nova_custom_chain_release", _i, [_vp, _sz, _sz]),
     ("vdf_nova_custom_chain_memory", _i, [_vp, C.POINTER(_sz), C.POINTER(_u64)]),
@@ -594,6 +600,40 @@ def forward_tape_eval(field: int, tape: RoundTape, inv, entries: np.ndarray, n: 
     _check(nova_lib.vdf_nova_forward_tape_eval(field, C.addressof(tape.c), inv.ctypes.data if tape.c.n_inv else None, entries.ctypes.data, n, rounds,
                                                checkpoints.ctypes.data if checkpoints is not None else None, every, cp_stride,
                                                trace.ctypes.data if trace is not None else None, walk_stride, base, j_base, j_walk_step))
+
+
+def forward_tape_rebuild_eval_lanes(field: int, forward_tape: RoundTape, lanes: int, inv, entries: np.ndarray, n: int, rounds: int,
+                                    trace: "np.ndarray | None" = None, walk_stride: int = 0, base: int = 0, group: int = 0,
+                                    group_stride: int = 0, j_base=None, j_group_step: int = 0, heads: bool = False,
+                                    expect: "np.ndarray | None" = None, ok: "np.ndarray | None" = None) -> None:
+    """Host only: Context.round_tape_rebuild_lanes on the host, in place over numpy arrays as walk_tape_eval_lanes; inv: lanes *
+    n_inv elements, j_base: `lanes` ints (default zeros).  The same arguments and the same refusals; the arrays are checked against
+    what the walks touch."""
+    def arr(x, dtype, what):
+        if x is None:
+            return None
+        if not isinstance(x, np.ndarray) or x.dtype != np.dtype(dtype) or not x.flags["C_CONTIGUOUS"] or not x.flags["WRITEABLE"]:
+            raise ValueError("%s: a writable C-contiguous %s array" % (what, dtype))
+        return x
+    na = forward_tape.c.n_adv
+    inv = np.ascontiguousarray(inv if inv is not None else np.zeros((0, 4)), dtype="<u8").reshape(-1, 4)
+    jb = None if j_base is False else np.ascontiguousarray([0] * max(lanes, 1) if j_base is None else [int(v) % 2**64 for v in j_base], dtype="<u8")
+    entries, trace, expect, ok = arr(entries, "<u8", "entries"), arr(trace, "<u8", "trace"), arr(expect, "<u8", "expect"), arr(ok, "<i4", "ok")
+    if 0 < lanes <= 16:
+        if inv.shape[0] < lanes * forward_tape.c.n_inv or (jb is not None and jb.size < lanes) or (entries is not None and entries.size < 4 * n * na) or \
+                (expect is not None and expect.size < 4 * n * na) or (ok is not None and ok.size < n):
+            raise ValueError("inv, j_base, entries, expect or ok shorter than the walks read")
+    if trace is not None and n and rounds:
+        g = group or n
+        last = ((n - 1) // g) * (group_stride if group else 0) + (min(n, g) - 1) * walk_stride + base + rounds
+        if trace.size < 4 * (last + 1) * na:
+            raise ValueError("trace shorter than the walks write")
+    _check(nova_lib.vdf_nova_forward_tape_rebuild_eval_lanes(field, C.addressof(forward_tape.c), lanes, inv.ctypes.data if forward_tape.c.n_inv else None,
+                                                             entries.ctypes.data if entries is not None else None, n, rounds,
+                                                             trace.ctypes.data if trace is not None else None, walk_stride, base, group,
+                                                             group_stride, jb.ctypes.data if jb is not None else None, j_group_step,
+                                                             int(bool(heads)), expect.ctypes.data if expect is not None else None,
+                                                             ok.ctypes.data if ok is not None else None))
 
 
 POW_ACC, POW_NONE, POW_CHAIN_MAX_STEPS, POW_CHAIN_MAX_TMP = 0xFE, 0xFF, 95, 12      # VDF_POW_*
@@ -1247,6 +1287,9 @@ def custom_chain_window_host(field: int, walk_tape: RoundTape, inv, t: int, ever
     return trace, entries.reshape(-1, 4), ok
 
 
+CHAIN_DESCENDING, CHAIN_ASCENDING = 0, 1      # vdf_nova_custom_chain_direction
+
+
 class CustomChain:
     """vdf_custom_chain: the chain of a custom step circuit, proved from its checkpoints.  The device traces its steps read as
     advice are rebuilt window by window by the chain's walk tape on a side queue (include/vdf_nova.h)."""
@@ -1256,11 +1299,12 @@ class CustomChain:
 
     @staticmethod
     def lanes_from_checkpoints(field: int, walk_tape: RoundTape, inv, t: int, every: int, num_steps: int, lanes: int, checkpoints,
-                               lane_stride: Optional[int] = None, j_base=None) -> "CustomChain":
+                               lane_stride: Optional[int] = None, j_base=None, forward: bool = False) -> "CustomChain":
         """`lanes` chains of equal length in one chain object (ConstraintSystem.repeat_lanes): lane l's num_steps * (t // every) + 1
         checkpoints start lane_stride entries (default: exactly that many) after lane l - 1's -- consecutive chains of
         Context.round_tape_eval_batch's output, host array or device tensor / address.  inv: lanes * n_inv elements, j_base: one
-        counter per lane (default zeros).  A step's trace is lanes * (t + 1) entries."""
+        counter per lane (default zeros).  A step's trace is lanes * (t + 1) entries.  forward: `walk_tape` is the chain's FORWARD tape
+        (a round without a cheap inverse): an ascending chain, its walks start below their interval and land above it."""
         per_lane = num_steps * (t // every) + 1 if every and t % every == 0 else 0
         lane_stride = per_lane if lane_stride is None else lane_stride
         inv = np.ascontiguousarray(inv if inv is not None else np.zeros((0, 4)), dtype="<u8").reshape(-1, 4)
@@ -1273,15 +1317,17 @@ class CustomChain:
                     checkpoints.size < 4 * ((lanes - 1) * lane_stride + per_lane) * walk_tape.c.n_adv:
                 raise ValueError("checkpoints shorter than the lanes read")
         h = C.c_void_p()
-        _check(nova_lib.vdf_nova_custom_chain_lanes_from_checkpoints(field, C.addressof(walk_tape.c),
-                                                                     inv.ctypes.data if walk_tape.c.n_inv else None, t, every, num_steps,
-                                                                     lanes, _ptr(checkpoints), lane_stride, jb.ctypes.data, C.byref(h)))
+        make = nova_lib.vdf_nova_custom_chain_lanes_from_checkpoints_forward if forward else nova_lib.vdf_nova_custom_chain_lanes_from_checkpoints
+        _check(make(field, C.addressof(walk_tape.c), inv.ctypes.data if walk_tape.c.n_inv else None, t, every, num_steps, lanes,
+                    _ptr(checkpoints), lane_stride, jb.ctypes.data, C.byref(h)))
         return CustomChain(h.value, field, t, every, walk_tape.c.n_adv, lanes)
 
     @staticmethod
-    def from_checkpoints(field: int, walk_tape: RoundTape, inv, t: int, every: int, num_steps: int, checkpoints, j_base: int = 0) -> "CustomChain":
+    def from_checkpoints(field: int, walk_tape: RoundTape, inv, t: int, every: int, num_steps: int, checkpoints, j_base: int = 0,
+                         forward: bool = False) -> "CustomChain":
         """checkpoints: num_steps * (t // every) + 1 entries of n_adv elements in forward order -- a uint64[., 4] array (host), or a
-        device tensor / address (downloaded once).  inv: the walk tape's loop-invariant values, host."""
+        device tensor / address (downloaded once).  inv: the walk tape's loop-invariant values, host.  forward: `walk_tape` is the
+        chain's FORWARD tape (an ascending chain: rounds without a cheap inverse); j_base means the same number either way."""
         inv = np.ascontiguousarray(inv if inv is not None else np.zeros((0, 4)), dtype="<u8").reshape(-1, 4)
         if inv.shape[0] < walk_tape.c.n_inv:
             raise ValueError("inv shorter than the tape reads")
@@ -1290,12 +1336,28 @@ class CustomChain:
             if every and t % every == 0 and checkpoints.size < 4 * (num_steps * (t // every) + 1) * walk_tape.c.n_adv:
                 raise ValueError("checkpoints shorter than num_steps * (t / every) + 1 entries")
         h = C.c_void_p()
-        _check(nova_lib.vdf_nova_custom_chain_from_checkpoints(field, C.addressof(walk_tape.c), inv.ctypes.data if walk_tape.c.n_inv else None,
-                                                               t, every, num_steps, _ptr(checkpoints), j_base % 2**64, C.byref(h)))
+        make = nova_lib.vdf_nova_custom_chain_from_checkpoints_forward if forward else nova_lib.vdf_nova_custom_chain_from_checkpoints
+        _check(make(field, C.addressof(walk_tape.c), inv.ctypes.data if walk_tape.c.n_inv else None, t, every, num_steps, _ptr(checkpoints),
+                    j_base % 2**64, C.byref(h)))
         return CustomChain(h.value, field, t, every, walk_tape.c.n_adv)
 
     def __len__(self) -> int:
         return nova_lib.vdf_nova_custom_chain_len(self.handle)
+
+    @property
+    def direction(self) -> int:
+        """CHAIN_DESCENDING (a walk tape) or CHAIN_ASCENDING (a forward tape)"""
+        return nova_lib.vdf_nova_custom_chain_direction(self.handle)
+
+    def launch_rounds(self, asked: int = 0) -> int:
+        """the rounds per launch a job of this chain runs with when `asked` is requested (an ascending chain lowers it to its bound)"""
+        out = C.c_uint64(0)
+        _check(nova_lib.vdf_nova_custom_chain_launch_rounds(self.handle, asked, C.byref(out)))
+        return out.value
+
+    def set_launch_rounds(self, launch_rounds: int) -> None:
+        """the rounds per launch of the jobs whose caller asks for 0, prove_recursively_custom's among them (0: the default)"""
+        _check(nova_lib.vdf_nova_custom_chain_set_launch_rounds(self.handle, launch_rounds))
 
     def materialize(self, ctx: Context, first: int = 0, count: Optional[int] = None, wait: bool = True, launch_rounds: int = 0) -> List[int]:
         """Build the device traces of steps [first, first + count) by walks on the GPU, at most launch_rounds rounds per launch
