@@ -719,8 +719,7 @@ int  vdf_nova_public_params_custom_tuned(vdf_ctx* ctx, int field, const vdf_step
  * byte the same in every case.  vdf_nova_proof_ahead_stats counts the three.  A repeat whose rows read some other variable of the
  * circuit has no early rows, and mode 2 is mode 1 for it.
  * Out of scope for custom chains: custom_ahead for steps not driven by a chain (plain vdf_nova_prove_step_custom keeps the schedule
- * of custom_ahead = 0: the library does not know its next advice), a second vdf_cs_repeat, a streaming eval_and_prove, lanes of
- * different length.
+ * of custom_ahead = 0: the library does not know its next advice), a second vdf_cs_repeat, lanes of different length.
  *
  * ASCENDING CHAINS: rounds without a cheap inverse.  A walk tape may hold no power, so the constructors above serve rounds whose
  * inverse direction is a handful of products.  A Rescue-shaped round (a root layer and a power layer: a 254-bit exponentiation in
@@ -739,7 +738,48 @@ int  vdf_nova_public_params_custom_tuned(vdf_ctx* ctx, int field, const vdf_step
  * Everything above the constructors -- materialize, release, memory, host_bytes, advice, vdf_cs_step_advice, both provers,
  * VDF_CUSTOM_CHECK_STEPS, custom_ahead, both orientations -- works unchanged above an ascending chain.  A capability and a matter of
  * resident memory (checkpoints, not traces), NOT of speed: a lane spends about 0.1 ms per round of a fifth root, so an ascending
- * chain wants dense checkpoints, and a round WITH a cheap inverse keeps its descending tape. */
+ * chain wants dense checkpoints, and a round WITH a cheap inverse keeps its descending tape.
+ *
+ * CHAINS THAT GROW: proved while they are evaluated.  vdf_nova_custom_chain_begin makes an EMPTY chain that stands on `initial`
+ * (lanes * n_adv elements, lane-major: entry 0 of every lane; host memory).  tape: the walk tape (direction = VDF_CHAIN_DESCENDING)
+ * or the chain's forward tape (VDF_CHAIN_ASCENDING); inv, t, lanes and j_base as the four constructors take them, and every refusal
+ * of theirs that does not concern checkpoints applies (the tape's rules, t, lanes, a table's tab_rows dividing t and every j_base),
+ * besides a direction that is neither.  Each push appends ONE step, step k being the k-th pushed, and _len grows by one:
+ * - vdf_nova_custom_chain_push_checkpoints: every lane's t / every + 1 checkpoints of the step, lane l's at checkpoints + l *
+ *   lane_stride * n_adv (host or device memory; lane_stride in entries, at least t / every + 1, not read for one lane);
+ * - vdf_nova_custom_chain_push_advice: every lane's whole trace, t + 1 entries, lane l's at advice + l * lane_stride * n_adv (host
+ *   memory; lane_stride at least t + 1).  The chain keeps a host copy until the step is released.
+ * THE JOINT IS CHECKED: entry 0 of every lane of a pushed step must equal, byte for byte, the chain's end -- `initial` before the
+ * first push, then the last entry of the last push, per lane.  Otherwise VDF_ERR_BAD_ARG "lane l: the step does not start on the
+ * chain's end" and nothing is appended (as vdf_nova_circuits_push_trace).  ONE HAND-OVER PER CHAIN: the first push decides between
+ * checkpoints and advice, and the other call on the same chain is VDF_ERR_BAD_ARG from then on; for checkpoints it also decides
+ * `every` (it must divide t), and a push with another is refused -- a walk job is a contiguous run of steps with one shape.  Both
+ * calls return VDF_ERR_BAD_ARG on a chain made by a from_checkpoints constructor.
+ * Everything above the constructors works unchanged over the steps pushed so far: materialize, release, memory, advice, direction,
+ * [set_]launch_rounds, vdf_nova_prove_step_custom_chain (a k not yet pushed is "step k is beyond the chain", and the proof object
+ * goes on after the push), vdf_nova_prove_recursively_custom over a chain that has been pushed completely, VDF_CUSTOM_CHECK_STEPS,
+ * lanes, both orientations, and tuning.custom_ahead, whose lookahead stops at the end of the chain and counts a skip: push step k +
+ * 1 before step k is proved and it rides in step k's lookahead.  materialize over steps pushed as ADVICE uploads their host copies
+ * into one allocation on the side queue where it would otherwise launch walks, with no walk and no comparison; wait = 0 means what
+ * it means for walks (the next call that needs the trace synchronises), and the circuit and both provers see a device trace exactly
+ * as over a walked step.  release also drops the host copy of a released step pushed as advice -- a long stream holds a bounded
+ * number of traces, and such a step cannot be materialised again (VDF_ERR_BAD_ARG) -- while checkpoints (n_adv * 32 bytes per
+ * interval) are kept; vdf_nova_custom_chain_host_bytes counts both.
+ * CONCURRENCY: no lock, as for forward circuits.  A push or a release must not overlap a vdf_nova_prove_step_custom_chain (or any
+ * other call) over the same chain; both are safe between two steps.
+ *
+ * vdf_nova_eval_and_prove_custom: vdf_nova_eval_and_prove for a custom chain.  One library thread per lane evaluates the chain step
+ * by step with the host restatement of forward_tape (vdf_nova_forward_tape_eval; lane l's rounds see VDF_TAPE_J = j_base[l] + the
+ * rounds behind them) and hands finished steps over through a queue of at most 4: whole traces (every = 0, push_advice) or the
+ * entries every `every` rounds (push_checkpoints), which the chain rebuilds on the device by walk_tape (descending), or, walk_tape =
+ * NULL, by forward_tape itself (ascending).  The CALLING thread pushes everything that is ready, materialises it with wait = 0,
+ * proves step k, releases it, and finalises the proof as the built-in call does; `synthesize` is called on the calling thread only
+ * (a circuit written in another language is never entered from a library thread).  However the call ends -- a refused push, a step
+ * that fails, a `synthesize` that returns an error -- the evaluators are told to stop and are joined before it returns.
+ * initial: lanes * n_adv elements; final_entries (optional): the lanes' last entries; stats as for vdf_nova_eval_and_prove: eval_ms
+ * to the last lane's last round, after_eval_ms from there to the return.  pp: parameters of the custom circuit `primary`, whose
+ * repeat has t rounds and `lanes` lanes and reads vdf_cs_step_advice.  The proof is byte for byte the one
+ * vdf_nova_prove_step_custom makes from the same traces. */
 typedef struct vdf_custom_chain vdf_custom_chain;
 enum { VDF_CHAIN_DESCENDING = 0, VDF_CHAIN_ASCENDING = 1 };
 #define VDF_CUSTOM_CHECK_STEPS 1u
@@ -754,6 +794,10 @@ int  vdf_nova_custom_chain_from_checkpoints_forward(int field, const vdf_round_t
 int  vdf_nova_custom_chain_lanes_from_checkpoints_forward(int field, const vdf_round_tape* forward_tape, const vdf_fe* inv, uint64_t t,
                                                           uint64_t every, size_t num_steps, size_t lanes, const vdf_fe* checkpoints,
                                                           size_t lane_stride, const uint64_t* j_base, vdf_custom_chain** out);
+int  vdf_nova_custom_chain_begin(int field, const vdf_round_tape* tape, int direction, const vdf_fe* inv, uint64_t t, size_t lanes,
+                                 const vdf_fe* initial, const uint64_t* j_base, vdf_custom_chain** out);
+int  vdf_nova_custom_chain_push_checkpoints(vdf_custom_chain* chain, uint64_t every, const vdf_fe* checkpoints, size_t lane_stride);
+int  vdf_nova_custom_chain_push_advice(vdf_custom_chain* chain, const vdf_fe* advice, size_t lane_stride);
 /* VDF_CHAIN_DESCENDING or VDF_CHAIN_ASCENDING; -1 for NULL */
 int  vdf_nova_custom_chain_direction(const vdf_custom_chain* chain);
 /* the launch_rounds a job of this chain runs with when the caller asks for `launch_rounds`: 0 is first replaced by the chain's own
@@ -781,6 +825,17 @@ int  vdf_nova_prove_step_custom_chain(vdf_pp* pp, vdf_proof** proof, const vdf_s
                                       const vdf_fe* z0);
 int  vdf_nova_prove_recursively_custom(vdf_pp* pp, const vdf_step_circuit* primary, vdf_custom_chain* chain, const vdf_fe* z0,
                                        size_t window_steps, uint32_t flags, vdf_proof** proof);
+typedef struct vdf_nova_custom_stream {
+  const vdf_round_tape* forward_tape;  /* evaluates the chain; required */
+  const vdf_fe* inv;                   /* lanes * forward_tape->n_inv */
+  const vdf_round_tape* walk_tape;     /* NULL: steps handed over as checkpoints are rebuilt by forward_tape (ascending) */
+  const vdf_fe* walk_inv;              /* lanes * walk_tape->n_inv */
+  uint64_t t, every;                   /* every = 0: whole traces are handed over (push_advice); else it divides t (push_checkpoints) */
+  size_t lanes; const uint64_t* j_base;
+} vdf_nova_custom_stream;
+int  vdf_nova_eval_and_prove_custom(vdf_pp* pp, const vdf_step_circuit* primary, const vdf_nova_custom_stream* s, const vdf_fe* initial,
+                                    size_t num_steps, const vdf_fe* z0, vdf_fe* final_entries /* lanes * n_adv, optional */,
+                                    vdf_proof** out, vdf_nova_stream_stats* stats /* optional */);
 /* Which constraint of the LAST step is unsatisfied: *count = the rows r of the fresh primary instance with (A z)[r] (B z)[r] !=
  * (C z)[r], *first_row = the smallest (UINT64_MAX: none); vdf_hip.h vdf_unsat_rows.  For proofs of every circuit kind.  The step's
  * own A z, B z, C z do not outlive it on every path (the base step folds nothing and never makes them apart from the running

@@ -3,6 +3,8 @@
 // (vdf_round_tape_walk; vdf_round_tape_walk_lanes for a chain of several lanes) on a side queue, a window ahead of the prover.
 // An ASCENDING chain (rounds without a cheap inverse) rebuilds them by its forward tape instead (vdf_round_tape_rebuild_lanes): the
 // two hooks that know a direction are stage_walks and launch; the window above them does not.
+// A GROWING chain (vdf_nova_custom_chain_begin) gets its steps one push at a time, as checkpoints or as whole traces; a step pushed
+// as a trace is "walked" by a job of no walks whose set-up uploads the host copy.
 #include <atomic>
 #include "nova_internal.hpp"
 
@@ -25,23 +27,31 @@ struct vdf_custom_chain final : WalkOwner {
   std::vector<uint64_t> j_base;            // per lane
   size_t per = 0, na = 0;                  // walks per step AND LANE, elements per entry
   std::vector<vdf_tape_op> ops;
-  std::vector<Fe> consts, inv, cp;         // inv: lanes * n_inv; cp: per lane (steps * per + 1) entries, forward order, lane-major
+  std::vector<Fe> consts, inv;             // inv: lanes * n_inv
+  std::vector<std::vector<Fe>> cp;         // per lane: (steps * per + 1) entries, forward order -- a lane of its own, so that it grows in
+                                           // place; handed over as traces: the ONE entry the chain ends on
+  // a growing chain: NONE until the first push decides; TRACES: adv[k] is step k's host copy (lanes * (t + 1) entries) until released
+  enum Handover { CHECKPOINTS, NONE, TRACES } handover = CHECKPOINTS;
+  bool growing = false;
+  std::vector<std::vector<Fe>> adv;
+  const Fe* end_of(size_t l) const { return cp[l].data() + cp[l].size() - na; }
+  size_t cp_elems() const { size_t n = 0; for (const auto& l : cp) n += l.size(); return n; }
+  size_t adv_elems() const { size_t n = 0; for (const auto& a : adv) n += a.size(); return n; }
   std::vector<Fe> table;                   // the walk tape's table (VDF_TAPE_TAB), a host copy ...
   std::atomic<void*> d_table{nullptr};     // ... and its ONE device copy, made by the first job on the traces' device, freed with the
                                            // chain; published only once it is whole (vdf_nova_custom_chain_memory may ask from another thread)
   std::vector<Fe> stage;                 // lanes > 1, while a job is pending: the walks' starts, then their targets, gathered
                                            // step-major, lane-minor (freed when the job resolves)
-  size_t lane_entries() const { return v.size() * per + 1; }
   std::vector<TraceSlot> v;
   vdf_round_tape tape;                     // into ops / consts
   TraceWalks walk{this};                   // (walk.home: where the traces live)
 
   TraceSlot& slot(size_t k) override { return v[k]; }
   void shape(size_t, WalkJob* j) override {
-    j->every = every;
+    j->every = handover == TRACES ? 0 : every;                  // traces handed over: no walks and no rounds, set-up uploads them
     j->launch_rounds = launch_rounds_of(j->launch_rounds);      // (set by the window before it asks for the shape)
     j->trace_bytes = lanes * (t + 1) * na * 32;
-    j->step_walks = lanes * per;
+    j->step_walks = handover == TRACES ? 0 : lanes * per;
     j->entry_bytes = na * 32;
   }
   // walk li * per + m stands on the checkpoint above interval m of step lo + li and must land on the one below it: both runs
@@ -52,14 +62,14 @@ struct vdf_custom_chain final : WalkOwner {
   }
   void stage_descending(const WalkJob& j, const void** starts, const void** expects) {
     const size_t lo = j.steps[0];
-    *expects = cp.data() + lo * per * na;
-    *starts = cp.data() + lo * per * na + na;
+    *expects = cp[0].data() + lo * per * na;
+    *starts = cp[0].data() + lo * per * na + na;
     if (lanes == 1) return;
     const size_t run = per * na;
     stage.resize(2 * j.walks * na);
     for (size_t li = 0; li < j.steps.size(); ++li)
       for (size_t l = 0; l < lanes; ++l) {
-        const Fe* src = cp.data() + (l * lane_entries() + (lo + li) * per) * na;
+        const Fe* src = cp[l].data() + (lo + li) * per * na;
         memcpy(stage.data() + (li * lanes + l) * run, src + na, run * 32);
         memcpy(stage.data() + j.walks * na + (li * lanes + l) * run, src, run * 32);
       }
@@ -67,8 +77,16 @@ struct vdf_custom_chain final : WalkOwner {
     *expects = stage.data() + j.walks * na;
   }
   void unstage() override { std::vector<Fe>().swap(stage); }
-  // the table goes to the device once, on the queue the walks run on and in front of them
-  int setup(vdf_ctx* q, const WalkJob&, const WalkScratch&) override {
+  // the table goes to the device once, on the queue the walks run on and in front of them; traces handed over are uploaded here,
+  // step li's host copy into trace li of the job's block (materialize has refused a step whose copy is gone)
+  int setup(vdf_ctx* q, const WalkJob& j, const WalkScratch&) override {
+    if (handover == TRACES) {
+      for (size_t li = 0; li < j.steps.size(); ++li) {
+        const int rc = vdf_dev_memcpy(q, (char*)j.block->d + li * j.trace_bytes, adv[j.steps[li]].data(), j.trace_bytes);
+        if (rc != VDF_OK) return rc;
+      }
+      return VDF_OK;
+    }
     if (table.empty() || d_table.load()) return VDF_OK;
     void* d = nullptr;
     int rc = vdf_dev_alloc(walk.home, table.size() * 32, &d);
@@ -129,18 +147,19 @@ int vdf_nova_custom_chain_slice(uint64_t every, uint64_t launch_rounds, uint64_t
 static size_t single_stride(uint64_t t, uint64_t every, size_t num_steps) {
   return every && t && num_steps <= ((size_t)1 << 40) ? num_steps * (size_t)(t / every) + 1 : 1;
 }
-// all four constructors: `walk_tape` is the chain's walk tape, or (ascending) its forward tape
+// all four constructors and vdf_nova_custom_chain_begin: `walk_tape` is the chain's walk tape, or (ascending) its forward tape.
+// growing: no steps yet, `checkpoints` is entry 0 of every lane (lane_stride 1) and every / num_steps are the pushes' to say.
 static int chain_from_checkpoints(int fid, const vdf_round_tape* walk_tape, bool ascending, const vdf_fe* inv, uint64_t t, uint64_t every,
                                   size_t num_steps, size_t lanes, const vdf_fe* checkpoints, size_t lane_stride, const uint64_t* j_base,
-                                  vdf_custom_chain** out) {
+                                  vdf_custom_chain** out, bool growing = false) {
   return nova_guard([&]() -> int {
     if (!out) return fail(VDF_ERR_BAD_ARG, "null out");
     *out = nullptr;
     if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
     if (!walk_tape || !checkpoints || !j_base) return fail(VDF_ERR_BAD_ARG, "null argument");
-    if (num_steps == 0) return fail(VDF_ERR_BAD_ARG, "num_steps must be > 0");
+    if (!growing && num_steps == 0) return fail(VDF_ERR_BAD_ARG, "num_steps must be > 0");
     if (t == 0 || t >= (1ull << 31)) return fail(VDF_ERR_BAD_ARG, "t out of range (1 <= t < 2^31, vdf_cs_repeat)");
-    if (every == 0 || t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
+    if (!growing && (every == 0 || t % every != 0)) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
     if (lanes == 0 || lanes > VDF_TAPE_MAX_LANES) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_TAPE_MAX_LANES");
     // the check the walk's launcher applies, by its host restatement with nothing to walk (a null `inv` the tape reads included):
     // vdf_round_tape_walk's for one lane, vdf_round_tape_walk_lanes' (lanes * n_inv, n_inv more slots) for more
@@ -159,13 +178,15 @@ static int chain_from_checkpoints(int fid, const vdf_round_tape* walk_tape, bool
       for (size_t l = 0; l < lanes; ++l)
         if (j_base[l] % walk_tape->tab_rows != 0) return fail(VDF_ERR_BAD_ARG, "the walk tape's tab_rows must divide every j_base (the round body's j is step-local, the walks' J chain-global)");
     }
-    const size_t per = (size_t)(t / every), na = walk_tape->n_adv;
-    if (num_steps > ((size_t)1 << 40) / per) return fail(VDF_ERR_BAD_LENGTH, "too many checkpoints");
+    const size_t per = growing ? 0 : (size_t)(t / every), na = walk_tape->n_adv;
+    if (!growing && num_steps > ((size_t)1 << 40) / per) return fail(VDF_ERR_BAD_LENGTH, "too many checkpoints");
     const size_t entries = num_steps * per + 1;
     if (lane_stride < entries || lane_stride > ((size_t)1 << 44)) return fail(VDF_ERR_BAD_ARG, "lane_stride must be at least num_steps * (t / every) + 1");
     std::unique_ptr<vdf_custom_chain> c(new vdf_custom_chain());
     c->field = fid; c->t = t; c->every = every; c->lanes = lanes; c->per = per; c->na = na;
     c->ascending = ascending;
+    c->growing = growing;
+    if (growing) c->handover = vdf_custom_chain::NONE;
     if (ascending) c->launch_bound = forward_tape_launch_bound(walk_tape);
     c->j_base.assign(j_base, j_base + lanes);
     c->ops.assign(walk_tape->ops, walk_tape->ops + walk_tape->n_ops);
@@ -176,15 +197,16 @@ static int chain_from_checkpoints(int fid, const vdf_round_tape* walk_tape, bool
     c->tape.consts = (const vdf_fe*)c->consts.data();
     if (walk_tape->tab_rows) c->table.assign((const Fe*)walk_tape->table, (const Fe*)walk_tape->table + (size_t)walk_tape->tab_rows * walk_tape->tab_cols);
     c->tape.table = nullptr;                           // the device copy, once a job has made it (setup)
-    c->cp.resize(lanes * entries * na);
+    c->cp.resize(lanes);
     const bool device = vdf_ptr_is_device(checkpoints);
     for (size_t l = 0; l < lanes; ++l) {
       const Fe* src = (const Fe*)checkpoints + l * lane_stride * na;
+      c->cp[l].resize(entries * na);
       if (device) {
         // (a copy only, after every refusal: the runtime finds the pointer's device, nothing is allocated there)
-        const int rc = vdf_ptr_download(c->cp.data() + l * entries * na, src, entries * na * 32);
+        const int rc = vdf_ptr_download(c->cp[l].data(), src, entries * na * 32);
         if (rc != VDF_OK) return fail(rc, std::string("checkpoints: ") + vdf_last_error(nullptr));
-      } else memcpy(c->cp.data() + l * entries * na, src, entries * na * 32);
+      } else memcpy(c->cp[l].data(), src, entries * na * 32);
     }
     c->v.resize(num_steps);
     *out = c.release();
@@ -208,6 +230,67 @@ int vdf_nova_custom_chain_lanes_from_checkpoints_forward(int fid, const vdf_roun
                                                          uint64_t every, size_t num_steps, size_t lanes, const vdf_fe* checkpoints,
                                                          size_t lane_stride, const uint64_t* j_base, vdf_custom_chain** out) {
   return chain_from_checkpoints(fid, forward_tape, true, inv, t, every, num_steps, lanes, checkpoints, lane_stride, j_base, out);
+}
+int vdf_nova_custom_chain_begin(int fid, const vdf_round_tape* tape, int direction, const vdf_fe* inv, uint64_t t, size_t lanes,
+                                const vdf_fe* initial, const uint64_t* j_base, vdf_custom_chain** out) {
+  if (direction != VDF_CHAIN_DESCENDING && direction != VDF_CHAIN_ASCENDING) {
+    if (out) *out = nullptr;
+    return fail(VDF_ERR_BAD_ARG, "direction must be VDF_CHAIN_DESCENDING or VDF_CHAIN_ASCENDING");
+  }
+  return chain_from_checkpoints(fid, tape, direction == VDF_CHAIN_ASCENDING, inv, t, 0, 0, lanes, initial, 1, j_base, out, true);
+}
+// One more step of a growing chain.  entries: what a lane hands over, per + 1 checkpoints or t + 1 trace entries; lane l's run starts
+// lane_stride entries after lane l - 1's (not read for one lane).  Nothing is appended unless every lane starts on the chain's end.
+static int chain_push(vdf_custom_chain* c, vdf_custom_chain::Handover kind, uint64_t every, const vdf_fe* src, size_t lane_stride) {
+  return nova_guard([&]() -> int {
+    if (!c || !src) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (!c->growing) return fail(VDF_ERR_BAD_ARG, "the chain was made whole from its checkpoints: only a chain of vdf_nova_custom_chain_begin grows");
+    const bool traces = kind == vdf_custom_chain::TRACES;
+    if (c->handover != vdf_custom_chain::NONE && c->handover != kind)
+      return fail(VDF_ERR_BAD_ARG, std::string("the chain's steps are handed over as ") + (traces ? "checkpoints" : "whole traces") + ": one hand-over per chain");
+    if (!traces) {
+      if (every == 0 || c->t % every != 0) return fail(VDF_ERR_BAD_ARG, "`every` must be positive and divide t");
+      if (c->handover != vdf_custom_chain::NONE && every != c->every)
+        return fail(VDF_ERR_BAD_ARG, "every = " + std::to_string(every) + ", the chain's first push said " + std::to_string(c->every));
+    }
+    const size_t na = c->na, per = traces ? 0 : (size_t)(c->t / every), entries = traces ? (size_t)c->t + 1 : per + 1;
+    if (c->lanes > 1 && (lane_stride < entries || lane_stride > ((size_t)1 << 44)))
+      return fail(VDF_ERR_BAD_ARG, std::string("lane_stride must be at least ") + (traces ? "t + 1" : "t / every + 1"));
+    if (!traces && c->v.size() + 1 > ((size_t)1 << 40) / per) return fail(VDF_ERR_BAD_LENGTH, "too many checkpoints");
+    const bool device = vdf_ptr_is_device(src);
+    if (traces && device) return fail(VDF_ERR_BAD_ARG, "advice: host memory expected");
+    std::vector<Fe> got(c->lanes * entries * na);
+    for (size_t l = 0; l < c->lanes; ++l) {
+      const Fe* from = (const Fe*)src + l * lane_stride * na;
+      if (device) {
+        const int rc = vdf_ptr_download(got.data() + l * entries * na, from, entries * na * 32);
+        if (rc != VDF_OK) return fail(rc, std::string("checkpoints: ") + vdf_last_error(nullptr));
+      } else memcpy(got.data() + l * entries * na, from, entries * na * 32);
+    }
+    for (size_t l = 0; l < c->lanes; ++l)
+      if (memcmp(got.data() + l * entries * na, c->end_of(l), na * 32) != 0)
+        return fail(VDF_ERR_BAD_ARG, "lane " + std::to_string(l) + ": the step does not start on the chain's end");
+    // from here nothing is refused; room first, so that a failed allocation leaves the chain as it was
+    c->v.reserve(c->v.size() + 1);
+    if (traces) c->adv.reserve(c->adv.size() + 1);
+    else for (size_t l = 0; l < c->lanes; ++l) c->cp[l].reserve(c->cp[l].size() + per * na);
+    for (size_t l = 0; l < c->lanes; ++l) {
+      const Fe* lane = got.data() + l * entries * na;
+      if (traces) memcpy(c->cp[l].data(), lane + (size_t)c->t * na, na * 32);      // the chain's new end
+      else c->cp[l].insert(c->cp[l].end(), lane + na, lane + entries * na);
+    }
+    if (traces) c->adv.push_back(std::move(got));
+    else { c->every = every; c->per = per; }
+    c->handover = kind;
+    c->v.emplace_back();
+    return VDF_OK;
+  });
+}
+int vdf_nova_custom_chain_push_checkpoints(vdf_custom_chain* c, uint64_t every, const vdf_fe* checkpoints, size_t lane_stride) {
+  return chain_push(c, vdf_custom_chain::CHECKPOINTS, every, checkpoints, lane_stride);
+}
+int vdf_nova_custom_chain_push_advice(vdf_custom_chain* c, const vdf_fe* advice, size_t lane_stride) {
+  return chain_push(c, vdf_custom_chain::TRACES, 0, advice, lane_stride);
 }
 int vdf_nova_custom_chain_direction(const vdf_custom_chain* c) { return !c ? -1 : c->ascending ? VDF_CHAIN_ASCENDING : VDF_CHAIN_DESCENDING; }
 int vdf_nova_custom_chain_launch_rounds(const vdf_custom_chain* c, uint64_t launch_rounds, uint64_t* out) {
@@ -233,6 +316,9 @@ int vdf_nova_custom_chain_materialize(vdf_ctx* ctx, vdf_custom_chain* c, size_t 
     for (size_t k = first; k < first + count; ++k) if (!c->v[k].d_trace) { lo = std::min(lo, k); hi = k + 1; }
     std::vector<size_t> steps;
     for (size_t k = lo; k < hi; ++k) steps.push_back(k);
+    if (c->handover == vdf_custom_chain::TRACES)
+      for (size_t k : steps)
+        if (c->adv[k].empty()) return fail(VDF_ERR_BAD_ARG, "step " + std::to_string(k) + " was released: a growing chain does not keep the advice of a released step");
     if (steps.size() * c->lanes * c->per > ((size_t)1 << 31)) return fail(VDF_ERR_BAD_LENGTH, "more than 2^31 walks in a window");
     return c->walk.begin(ctx, std::move(steps), wait, launch_rounds, pending, bad, first, count);
   });
@@ -243,6 +329,8 @@ int vdf_nova_custom_chain_release(vdf_custom_chain* c, size_t first, size_t coun
     if (first > c->v.size() || count > c->v.size() - first) return fail(VDF_ERR_BAD_LENGTH, "step range out of bounds");
     const int pending = c->walk.covers(first, count) ? c->walk.resolve(nullptr, 0, 0) : VDF_OK;
     c->walk.release(first, count, false);
+    if (c->handover == vdf_custom_chain::TRACES)                        // a long stream holds a bounded number of traces
+      for (size_t k = first; k < first + count; ++k) std::vector<Fe>().swap(c->adv[k]);
     return pending;
   });
 }
@@ -254,7 +342,7 @@ int vdf_nova_custom_chain_memory(const vdf_custom_chain* c, size_t* resident_ste
 }
 int vdf_nova_custom_chain_host_bytes(const vdf_custom_chain* c, uint64_t* bytes) {
   if (!c || !bytes) return fail(VDF_ERR_BAD_ARG, "null argument");
-  *bytes = c->ops.size() * sizeof(vdf_tape_op) + (c->consts.size() + c->inv.size() + c->cp.size() + c->stage.size() + c->table.size()) * 32;
+  *bytes = c->ops.size() * sizeof(vdf_tape_op) + (c->consts.size() + c->inv.size() + c->cp_elems() + c->adv_elems() + c->stage.size() + c->table.size()) * 32;
   return VDF_OK;
 }
 size_t vdf_nova_custom_chain_len(const vdf_custom_chain* c) { return c ? c->v.size() : 0; }

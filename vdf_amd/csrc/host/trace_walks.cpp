@@ -123,11 +123,14 @@ int TraceWalks::begin(vdf_ctx* ctx, std::vector<size_t> steps, int wait, uint64_
   }
   { int rc = scratch_ensure(j->walks, j->entry_bytes); if (rc != VDF_OK) return rc; }
   {
-    const void* starts, *expects;
-    owner->stage_walks(*j, &starts, &expects);
-    memset(s.h_ok, 0, j->walks * sizeof(int32_t));
-    int rc = vdf_dev_memcpy(side, s.d_walk, starts, j->walks * j->entry_bytes);
-    if (rc == VDF_OK) rc = vdf_dev_memcpy(side, s.d_expect, expects, j->walks * j->entry_bytes);
+    int rc = VDF_OK;
+    if (j->walks) {                                  // (a job of no walks -- traces its owner uploads in setup -- stages nothing)
+      const void* starts, *expects;
+      owner->stage_walks(*j, &starts, &expects);
+      memset(s.h_ok, 0, j->walks * sizeof(int32_t));
+      rc = vdf_dev_memcpy(side, s.d_walk, starts, j->walks * j->entry_bytes);
+      if (rc == VDF_OK) rc = vdf_dev_memcpy(side, s.d_expect, expects, j->walks * j->entry_bytes);
+    }
     if (rc == VDF_OK) rc = owner->setup(side, *j, s);
     if (rc != VDF_OK) return fail(rc, std::string("walk set-up: ") + vdf_last_error(side));
   }

@@ -33,7 +33,7 @@ void walk_slice(uint64_t every, uint64_t launch_rounds, uint64_t done, uint64_t 
 struct WalkJob {
   std::vector<size_t> steps;               // step indices, ascending
   std::shared_ptr<TraceBlock> block;       // steps.size() traces of trace_bytes
-  size_t walks = 0;                        // steps.size() * step_walks
+  size_t walks = 0;                        // steps.size() * step_walks; 0 (and every = 0): traces the owner's setup uploads, nothing walked
   uint64_t done = 0, launch_rounds = 0;    // launch_rounds: the bound of walk_slice
   // what the owner says of a job (WalkOwner::shape)
   uint64_t every = 0, trace_bytes = 0;     // rounds per walk; bytes of a step's trace

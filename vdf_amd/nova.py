@@ -179,6 +179,11 @@ for _name, _res, _args in [
     ("vdf_nova_tuning_read", _i, [_vp, _vp]),
     ("vdf_nova_shape_early_rows_custom", _i, [_i, _vp] + [C.POINTER(_u64)] * 4),
     ("vdf_nova_proof_ahead_stats", _i, [_vp] + [C.POINTER(_u64)] * 3),
+    # a custom chain that grows, proved while it is evaluated
+    ("vdf_nova_custom_chain_begin", _i, [_i, _vp, _i, _vp, _u64, _sz, _vp, _vp, C.POINTER(_vp)]),
+    ("vdf_nova_custom_chain_push_checkpoints", _i, [_vp, _u64, _vp, _sz]),
+    ("vdf_nova_custom_chain_push_advice", _i, [_vp, _vp, _sz]),
+    ("vdf_nova_eval_and_prove_custom", _i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
 ]:
     if not hasattr(nova_lib, _name):          # AttributeError at call time names the missing entry point
         continue
@@ -1341,6 +1346,41 @@ class CustomChain:
                     j_base % 2**64, C.byref(h)))
         return CustomChain(h.value, field, t, every, walk_tape.c.n_adv)
 
+    @staticmethod
+    def begin(field: int, tape: RoundTape, direction: int, inv, t: int, initial, lanes: int = 1, j_base=None) -> "CustomChain":
+        """An EMPTY chain that stands on `initial` (lanes * n_adv elements: entry 0 of every lane) and grows by one step per
+        push_checkpoints / push_advice.  tape: the walk tape (CHAIN_DESCENDING) or the chain's forward tape (CHAIN_ASCENDING)."""
+        inv = np.ascontiguousarray(inv if inv is not None else np.zeros((0, 4)), dtype="<u8").reshape(-1, 4)
+        jb = np.ascontiguousarray([0] * max(lanes, 1) if j_base is None else [int(v) % 2**64 for v in j_base], dtype="<u8")
+        initial = np.ascontiguousarray(initial, dtype="<u8").reshape(-1, 4)
+        if 0 < lanes <= 16 and (inv.shape[0] < lanes * tape.c.n_inv or jb.size < lanes or initial.shape[0] < lanes * tape.c.n_adv):
+            raise ValueError("inv, j_base or initial shorter than the lanes read")
+        h = C.c_void_p()
+        _check(nova_lib.vdf_nova_custom_chain_begin(field, C.addressof(tape.c), direction, inv.ctypes.data if tape.c.n_inv else None, t, lanes,
+                                                    initial.ctypes.data, jb.ctypes.data, C.byref(h)))
+        return CustomChain(h.value, field, t, 0, tape.c.n_adv, lanes)
+
+    def push_checkpoints(self, every: int, cps, lane_stride: Optional[int] = None) -> None:
+        """One more step from every lane's t // every + 1 checkpoints, lane l's lane_stride entries (default: exactly that many)
+        after lane l - 1's; a uint64[., 4] array (host) or a device tensor / address.  Entry 0 of every lane must be the chain's end."""
+        per_lane = self.t // every + 1 if every and self.t % every == 0 else 0
+        lane_stride = per_lane if lane_stride is None else lane_stride
+        if isinstance(cps, np.ndarray):
+            cps = np.ascontiguousarray(cps, dtype="<u8")
+            if per_lane and lane_stride >= per_lane and cps.size < 4 * ((self.lanes - 1) * lane_stride + per_lane) * self.n_adv:
+                raise ValueError("checkpoints shorter than the lanes read")
+        _check(nova_lib.vdf_nova_custom_chain_push_checkpoints(self.handle, every, _ptr(cps), lane_stride))
+        self.every = every
+
+    def push_advice(self, advice, lane_stride: Optional[int] = None) -> None:
+        """One more step from every lane's whole trace, t + 1 entries each (a host uint64[., 4] array), lane l's lane_stride entries
+        (default t + 1) after lane l - 1's.  The chain keeps a host copy until the step is released."""
+        lane_stride = self.t + 1 if lane_stride is None else lane_stride
+        advice = np.ascontiguousarray(advice, dtype="<u8")
+        if lane_stride >= self.t + 1 and advice.size < 4 * ((self.lanes - 1) * lane_stride + self.t + 1) * self.n_adv:
+            raise ValueError("advice shorter than the lanes read")
+        _check(nova_lib.vdf_nova_custom_chain_push_advice(self.handle, advice.ctypes.data, lane_stride))
+
     def __len__(self) -> int:
         return nova_lib.vdf_nova_custom_chain_len(self.handle)
 
@@ -1533,6 +1573,11 @@ class StreamStats(C.Structure):   # vdf_nova_stream_stats
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class _CustomStream(C.Structure):  # vdf_nova_custom_stream
+    _fields_ = [("forward_tape", C.c_void_p), ("inv", C.c_void_p), ("walk_tape", C.c_void_p), ("walk_inv", C.c_void_p),
+                ("t", C.c_uint64), ("every", C.c_uint64), ("lanes", C.c_size_t), ("j_base", C.c_void_p)]
+
+
 class NovaVDFProof:               # enum NovaVDFProof { Recursive, Compressed }, :51-55
     def __init__(self, handle: int, pp: NovaVDFPublicParams):
         self.handle, self.pp = handle, pp
@@ -1563,6 +1608,33 @@ class NovaVDFProof:               # enum NovaVDFProof { Recursive, Compressed },
         _check(nova_lib.vdf_nova_eval_and_prove(pp.handle, int(v.eval_mode), C.byref(initial_state._c()), num_steps, C.byref(fin),
                                                 C.byref(h), C.addressof(st)))
         return NovaVDFProof(h.value, pp), State._from_c(fin), st.as_dict()
+
+    @staticmethod
+    def eval_and_prove_custom(pp: NovaVDFPublicParams, circuit: "StepCircuit", forward_tape: RoundTape, inv, t: int, initial, num_steps: int,
+                              z0: Sequence[bytes], every: int = 0, walk_tape: Optional[RoundTape] = None, walk_inv=None, lanes: int = 1,
+                              j_base=None) -> Tuple["NovaVDFProof", np.ndarray, dict]:
+        """A custom chain proved while it is evaluated (vdf_nova_eval_and_prove_custom): library threads, one per lane, evaluate
+        num_steps steps of t rounds from `initial` (lanes * n_adv elements) by forward_tape on the host; this thread is handed the
+        steps -- whole traces (every = 0) or checkpoints every `every` rounds, rebuilt on the GPU by walk_tape or, without one, by
+        forward_tape itself -- and proves them as they arrive.  `circuit.synthesize` runs on this thread only.  Returns (the running
+        proof, the lanes' final entries as uint64[lanes * n_adv, 4], vdf_nova_stream_stats as a dict)."""
+        arr = lambda a: np.ascontiguousarray(a if a is not None else np.zeros((0, 4)), dtype="<u8").reshape(-1, 4)
+        inv, walk_inv, initial = arr(inv), arr(walk_inv), arr(initial)
+        jb = np.ascontiguousarray([0] * max(lanes, 1) if j_base is None else [int(v) % 2**64 for v in j_base], dtype="<u8")
+        n_adv = forward_tape.c.n_adv
+        if 0 < lanes <= 16 and (inv.shape[0] < lanes * forward_tape.c.n_inv or jb.size < lanes or initial.shape[0] < lanes * n_adv or
+                                (walk_tape is not None and walk_inv.shape[0] < lanes * walk_tape.c.n_inv)):
+            raise ValueError("inv, walk_inv, j_base or initial shorter than the lanes read")
+        s = _CustomStream(C.addressof(forward_tape.c), inv.ctypes.data if forward_tape.c.n_inv else None,
+                          C.addressof(walk_tape.c) if walk_tape is not None else None,
+                          walk_inv.ctypes.data if walk_tape is not None and walk_tape.c.n_inv else None, t, every, lanes, jb.ctypes.data)
+        fin = np.zeros((max(lanes, 1) * n_adv, 4), dtype="<u8")
+        h, st = C.c_void_p(), StreamStats()
+        rc = nova_lib.vdf_nova_eval_and_prove_custom(pp.handle, C.byref(circuit._c()), C.byref(s), initial.ctypes.data, num_steps, _zn(z0),
+                                                     fin.ctypes.data, C.byref(h), C.addressof(st))
+        _reraise(circuit)
+        _check(rc)
+        return NovaVDFProof(h.value, pp), fin, st.as_dict()
 
     @staticmethod
     def prove_step(pp: NovaVDFPublicParams, proof: "NovaVDFProof | None", circuits: Circuits, k: int,
