@@ -455,7 +455,8 @@ int  vdf_round_tape_run(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uin
  * n_inv elements in HOST memory, lane-major; all of them travel in the kernel arguments' block of VDF_TAPE_MAX_INV elements (no
  * staging copy, no synchronisation), hence the second cap.  Refused with VDF_ERR_BAD_ARG: lanes outside 1 .. VDF_TAPE_MAX_LANES,
  * lanes * n_inv > VDF_TAPE_MAX_INV, lane_stride < t + 1, and what vdf_round_tape_run refuses.
- * Byte for byte what `lanes` calls of vdf_round_tape_run write; vdf_nova.h vdf_nova_round_tape_eval_lanes restates it on the host. */
+ * Byte for byte what `lanes` calls of vdf_round_tape_run write; vdf_nova.h vdf_nova_round_tape_eval_lanes restates it on the host
+ * (what a launch of a tape is refused for is stated once for both libraries, in csrc/tape_launch.h). */
 #define VDF_TAPE_MAX_LANES 16
 int  vdf_round_tape_run_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uint64_t t, size_t lanes, const vdf_fe* inv,
                               const vdf_fe* advice, size_t lane_stride, vdf_fe* out);

@@ -564,7 +564,9 @@ typedef struct {
 int  vdf_nova_walk_body_record(int field, const vdf_walk_body* b, vdf_tape_op ops[VDF_TAPE_MAX_OPS], vdf_fe consts[VDF_TAPE_MAX_CONSTS],
                                vdf_round_tape* out);
 /* Host only.  vdf_round_tape_walk restated on the host: the same arguments, the same refusals, every pointer host memory -- the
- * reference of the device path, byte for byte. */
+ * reference of the device path, byte for byte.  The refusals of this and of every restatement below are not written twice: both
+ * libraries read them from one header (csrc/tape_launch.h; the periodic rows' from csrc/periodic_rules.h), so a call is refused
+ * here for what its launcher refuses it for, in the same order, with the same code and the same words. */
 int  vdf_nova_walk_tape_eval(int field, const vdf_round_tape* tape, const vdf_fe* inv, vdf_fe* entries, size_t n, uint64_t rounds,
                              vdf_fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride, uint64_t j_base,
                              uint64_t j_group_step, int heads, const vdf_fe* expect, int32_t* ok);
@@ -624,7 +626,7 @@ int  vdf_nova_forward_tape_eval(int field, const vdf_round_tape* tape, const vdf
 /* Host only.  vdf_round_tape_rebuild_lanes (vdf_hip.h) restated on the host: the same arguments, the same refusals (the rules of a
  * forward walk tape, the caps on lanes and lanes * n_inv, a null j_base, expect without ok, base + rounds > walk_stride, the slot cap
  * with n_inv and the chains' n_tmp counted, the work cap), every pointer host memory -- the reference of the device path, byte for
- * byte.  The index arithmetic is the launcher's own statement (csrc/tape_rebuild.h), the interpreter the host's. */
+ * byte.  The index arithmetic is the launcher's own statement (csrc/tape_launch.h), the interpreter the host's. */
 int  vdf_nova_forward_tape_rebuild_eval_lanes(int field, const vdf_round_tape* forward_tape, size_t lanes, const vdf_fe* inv, vdf_fe* entries,
                                               size_t n, uint64_t rounds, vdf_fe* trace, size_t walk_stride, uint64_t base, size_t group,
                                               size_t group_stride, const uint64_t* j_base, uint64_t j_group_step, int heads,

@@ -1,4 +1,4 @@
-// Stand-alone driver of the host code of traces rebuilt by forward tapes (vdf_amd/csrc/tape_rebuild.h, host/rounds_host.cpp
+// Stand-alone driver of the host code of traces rebuilt by forward tapes (vdf_amd/csrc/tape_launch.h, host/rounds_host.cpp
 // vdf_nova_forward_tape_rebuild_eval_lanes, host/custom_chain_host.cpp's ascending constructors) for the sanitizers: the restatement
 // over a window laid out EXACTLY -- every array as long as the call may touch and no longer, so that an index one past its run is
 // an error the sanitizer reports -- against one whole chain by vdf_nova_forward_tape_eval; the same with a table of three rows and

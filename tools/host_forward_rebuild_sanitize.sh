@@ -1,6 +1,6 @@
 #!/bin/bash
 # AddressSanitizer + UBSan (leak check included) over the host code of traces rebuilt by forward tapes
-# (vdf_nova_forward_tape_rebuild_eval_lanes, the ascending vdf_custom_chain constructors, csrc/tape_rebuild.h), CPU only:
+# (vdf_nova_forward_tape_rebuild_eval_lanes, the ascending vdf_custom_chain constructors, csrc/tape_launch.h), CPU only:
 # tools/host_tape_table_sanitize.sh's recipe with tools/host_forward_rebuild_check.cpp as the program.  The host translation units of
 # libvdf_nova.so are compiled with the sanitizers into ONE stand-alone program with its own main, which is then run.  Nothing is
 # loaded into an interpreter and no device is touched; libvdf_hip.so is linked as it is for the symbols the host objects name.

@@ -17,6 +17,7 @@
 #include <utility>
 #include "internal.h"
 #include "fe.cuh"
+#include "tape_launch.h"
 
 using vdf::Status;
 
@@ -1517,9 +1518,15 @@ static Status tape_table_on_device(const vdf_round_tape* tape) {
   return Status{};
 }
 
+// the first refusal of a round launch (tape_launch.h), made here ahead of the checks of where the pointers live
+static Status tape_t_in_range(uint64_t t) {
+  const vdflaunch::Verdict v = vdflaunch::t_range(t);
+  return Status{v.code, v.why};
+}
+
 int vdf_round_tape_run(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uint64_t t, const vdf_fe* inv, const vdf_fe* advice, vdf_fe* out) {
   return guarded(ctx, [&]() -> Status {
-    if (t == 0 || t >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
+    VDF_TRY(tape_t_in_range(t));
     if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv))
       return Status{VDF_ERR_BAD_ARG, "the tape and inv live in host memory"};
     VDF_TRY(tape_table_on_device(tape));
@@ -1549,7 +1556,7 @@ int vdf_round_tape_walk(vdf_ctx* ctx, int field, const vdf_round_tape* tape, con
 int vdf_round_tape_run_lanes(vdf_ctx* ctx, int field, const vdf_round_tape* tape, uint64_t t, size_t lanes, const vdf_fe* inv,
                              const vdf_fe* advice, size_t lane_stride, vdf_fe* out) {
   return guarded(ctx, [&]() -> Status {
-    if (t == 0 || t >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
+    VDF_TRY(tape_t_in_range(t));
     if (!tape || ptr_is_device(tape) || ptr_is_device(tape->ops) || ptr_is_device(tape->consts) || ptr_is_device(inv))
       return Status{VDF_ERR_BAD_ARG, "the tape and inv live in host memory"};
     VDF_TRY(tape_table_on_device(tape));
@@ -1617,10 +1624,10 @@ int vdf_round_tape_eval_batch(vdf_ctx* ctx, int field, const vdf_round_tape* tap
   return guarded(ctx, [&]() -> Status {
     VDF_TRY(vdf::check_field(field));
     VDF_TRY(forward_tape_on_host(tape, inv));
-    uint64_t max_rounds = 0;
-    VDF_TRY(vdf::round_tape_forward_max_rounds(tape, inv, &max_rounds));
+    uint64_t max_rounds = 0, launch_bound = 0;
+    VDF_TRY(vdf::round_tape_forward_max_rounds(tape, inv, &max_rounds, &launch_bound));
     if (every && rounds_total % every != 0) return Status{VDF_ERR_BAD_ARG, "`every` must divide rounds_total"};
-    if (launch_rounds == 0) launch_rounds = std::min<uint64_t>(1024, max_rounds);
+    if (launch_rounds == 0) launch_rounds = launch_bound;
     if (launch_rounds > max_rounds) return Status{VDF_ERR_BAD_ARG, "launch_rounds x products per round > VDF_FORWARD_TAPE_MAX_WORK"};
     if (n > ((size_t)1 << 31)) return Status{VDF_ERR_BAD_LENGTH, "more than 2^31 chains"};
     if (n == 0) return Status{};

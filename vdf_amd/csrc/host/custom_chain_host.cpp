@@ -7,6 +7,7 @@
 // as a trace is "walked" by a job of no walks whose set-up uploads the host copy.
 #include <atomic>
 #include "nova_internal.hpp"
+#include "../tape_launch.h"
 
 using namespace vdfnova;
 
@@ -135,6 +136,17 @@ const vdf_fe* chain_ready(const vdf_custom_chain* c, size_t k) {
 }
 }  // namespace vdfnova
 
+namespace vdfnova {
+std::string tape_table_rows_fit_chain(const vdf_round_tape* tape, uint64_t t, size_t lanes, const uint64_t* j_base, const char* whose, const char* sees) {
+  if (tape->tab_rows == 0) return "";
+  const std::string head = std::string("the ") + whose + " tape's tab_rows must divide ", tail = std::string(" (the round body's j is step-local, the ") + sees + " J chain-global)";
+  if (t % tape->tab_rows != 0) return head + "t" + tail;
+  for (size_t l = 0; l < lanes; ++l)
+    if (j_base[l] % tape->tab_rows != 0) return head + "every j_base" + tail;
+  return "";
+}
+}  // namespace vdfnova
+
 extern "C" {
 int vdf_nova_custom_chain_slice(uint64_t every, uint64_t launch_rounds, uint64_t done, uint64_t budget, uint64_t* rounds, uint64_t* top,
                                 int* last) {
@@ -173,11 +185,8 @@ static int chain_from_checkpoints(int fid, const vdf_round_tape* walk_tape, bool
     }
     // a chain's walks see the chain-global J (step g's walks j_base + g * t + ...), the round body's j is step-local: the two name
     // the same row of a table only when its rows divide t and every j_base
-    if (walk_tape->tab_rows) {
-      if (t % walk_tape->tab_rows != 0) return fail(VDF_ERR_BAD_ARG, "the walk tape's tab_rows must divide t (the round body's j is step-local, the walks' J chain-global)");
-      for (size_t l = 0; l < lanes; ++l)
-        if (j_base[l] % walk_tape->tab_rows != 0) return fail(VDF_ERR_BAD_ARG, "the walk tape's tab_rows must divide every j_base (the round body's j is step-local, the walks' J chain-global)");
-    }
+    const std::string rows = tape_table_rows_fit_chain(walk_tape, t, lanes, j_base, "walk", "walks'");
+    if (!rows.empty()) return fail(VDF_ERR_BAD_ARG, rows);
     const size_t per = growing ? 0 : (size_t)(t / every), na = walk_tape->n_adv;
     if (!growing && num_steps > ((size_t)1 << 40) / per) return fail(VDF_ERR_BAD_LENGTH, "too many checkpoints");
     const size_t entries = num_steps * per + 1;
@@ -187,7 +196,7 @@ static int chain_from_checkpoints(int fid, const vdf_round_tape* walk_tape, bool
     c->ascending = ascending;
     c->growing = growing;
     if (growing) c->handover = vdf_custom_chain::NONE;
-    if (ascending) c->launch_bound = forward_tape_launch_bound(walk_tape);
+    if (ascending) c->launch_bound = vdflaunch::forward_launch_bound(walk_tape);
     c->j_base.assign(j_base, j_base + lanes);
     c->ops.assign(walk_tape->ops, walk_tape->ops + walk_tape->n_ops);
     c->consts.assign((const Fe*)walk_tape->consts, (const Fe*)walk_tape->consts + walk_tape->n_consts);

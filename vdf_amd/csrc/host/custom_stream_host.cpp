@@ -2,6 +2,7 @@
 // vdf_nova_eval_and_prove is to the built-in forward circuit.  ChainEvaluator (custom_stream.hpp) evaluates on threads of its own,
 // the calling thread grows a vdf_custom_chain (custom_chain_host.cpp) by what they finish, proves and releases.
 #include "nova_internal.hpp"
+#include "../tape_launch.h"
 #include "custom_stream.hpp"
 
 using namespace vdfnova;
@@ -36,7 +37,7 @@ void ChainEvaluator::eval_times(double* eval_ms, double* eval_end) {
 // path's work cap), into a trace of its own; what is handed over is copied into the step's slot once the queue has room for it.
 void ChainEvaluator::lane_main(size_t l) {
   const size_t na = spec.tape->n_adv, n = entries(), stride = spec.every ? (size_t)spec.every : 1;
-  const uint64_t bound = std::max<uint64_t>(1, forward_tape_launch_bound(spec.tape));
+  const uint64_t bound = std::max<uint64_t>(1, vdflaunch::forward_launch_bound(spec.tape));
   const Fe* inv = spec.tape->n_inv ? (const Fe*)spec.inv + l * spec.tape->n_inv : nullptr;
   std::vector<Fe> trace(((size_t)spec.t + 1) * na), stand((const Fe*)initial.data() + l * na, (const Fe*)initial.data() + (l + 1) * na);
   auto failed = [&](int rc, const std::string& msg) {
@@ -106,11 +107,9 @@ extern "C" int vdf_nova_eval_and_prove_custom(vdf_pp* pp, const vdf_step_circuit
     // ... and the evaluator's tape by the evaluator's own rules, with nothing to walk
     rc = eval_forward_tape(pp->field, s->forward_tape, (const Fe*)s->inv, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0, 0, 0);
     if (rc != VDF_OK) return rc;
-    if (s->forward_tape->tab_rows) {                   // the evaluator's J is chain-global like the walks' (vdf_nova_custom_chain_begin)
-      if (s->t % s->forward_tape->tab_rows != 0) return fail(VDF_ERR_BAD_ARG, "the forward tape's tab_rows must divide t (the round body's j is step-local, the evaluator's J chain-global)");
-      for (size_t l = 0; l < s->lanes; ++l)
-        if (s->j_base[l] % s->forward_tape->tab_rows != 0) return fail(VDF_ERR_BAD_ARG, "the forward tape's tab_rows must divide every j_base (the round body's j is step-local, the evaluator's J chain-global)");
-    }
+    // the evaluator's J is chain-global like the walks' (vdf_nova_custom_chain_begin)
+    const std::string tab = tape_table_rows_fit_chain(s->forward_tape, s->t, s->lanes, s->j_base, "forward", "evaluator's");
+    if (!tab.empty()) return fail(VDF_ERR_BAD_ARG, tab);
     constexpr size_t EVAL_QUEUE = 4;
     const size_t na = s->forward_tape->n_adv;
     // declared after the chain: whatever way this call ends, the lanes are told and joined first (no thread outlives the call)

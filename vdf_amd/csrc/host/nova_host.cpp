@@ -1463,6 +1463,17 @@ static int cross_forward(vdf_ctx* q, const Side& S, const SideState& st, const v
   return VDF_OK;
 }
 // a custom circuit's periodic repetitions (lead .. t - 1 of its repeat) from their description
+// The rounds of repeat r of a custom circuit, one repetition per thread on queue q, into `out`: the recorded tape with the
+// parameters' device copy of its table (null without one); one lane through the single launcher, more through the lanes launcher
+// (all lanes in one launch).  lane_stride: the advice's, unread for one lane.
+static int launch_repeat_rounds(vdf_ctx* q, const vdf_pp* pp, int field, const RepeatState& r, const Fe* inv, const void* d_advice, size_t lane_stride,
+                                void* out) {
+  vdf_round_tape tape = r.rec.view();
+  tape.table = (const vdf_fe*)pp->d_round_table;
+  if (r.lanes == 1) HIPCALL(q, vdf_round_tape_run(q, field, &tape, r.t, (const vdf_fe*)inv, (const vdf_fe*)d_advice, (vdf_fe*)out));
+  else HIPCALL(q, vdf_round_tape_run_lanes(q, field, &tape, r.t, r.lanes, (const vdf_fe*)inv, (const vdf_fe*)d_advice, lane_stride, (vdf_fe*)out));
+  return VDF_OK;
+}
 static int cross_periodic(vdf_ctx* q, const Side& S, const SideState& st, const void* d_z2, const PeriodicRows& pr, const RepeatState& round) {
   const SideState::Cross c = st.cross(d_z2);
   const vdf_periodic_rows view = pr.view();
@@ -1555,13 +1566,9 @@ struct StepRun {
       // been synchronised by the host and this queue is behind it
       next.chain = chain; next.k = j; next.d_trace = d_probed; next.lane_stride = probed->lane_stride; next.slot = s;
       next.inv = probed->inv;
-      vdf_round_tape tape = pp->round.rec.view();            // (the probe's body is the parameters': compared by the caller)
-      tape.table = (const vdf_fe*)pp->d_round_table;         // (null without a table)
-      if (pp->round.lanes == 1)
-        HIPCALL(q, vdf_round_tape_run(q, S1.field, &tape, pp->round.t, (const vdf_fe*)next.inv.data(), d_probed, (vdf_fe*)seg));
-      else
-        HIPCALL(q, vdf_round_tape_run_lanes(q, S1.field, &tape, pp->round.t, pp->round.lanes, (const vdf_fe*)next.inv.data(), d_probed,
-                                            probed->lane_stride, (vdf_fe*)seg));
+      // (the probe's body is the parameters': compared by the caller)
+      const int rc = launch_repeat_rounds(q, pp, S1.field, pp->round, next.inv.data(), d_probed, probed->lane_stride, seg);
+      if (rc != VDF_OK) return rc;
     } else {
       const Circuit& cc = circuits->v[j];
       const void* d_trace = cc.d_trace;
@@ -1846,14 +1853,9 @@ struct StepRun {
       if (custom && cs.dev_len && !hit) {
         // the rounds of the circuit's vdf_cs_repeat, one repetition per thread, straight into the fresh witness: in front of the
         // uploads around them and of the commitment of W, on the step's own queue
-        vdf_round_tape tape = round->rec.view();
-        tape.table = (const vdf_fe*)pp->d_round_table;       // the parameters' device copy: same_body above compared the table's bytes
-        if (round->lanes == 1)
-          HIPCALL(ctx, vdf_round_tape_run(ctx, S1.field, &tape, round->t, (const vdf_fe*)round->inv.data(), (const vdf_fe*)round->d_advice,
-                                          (vdf_fe*)((char*)d_z2 + pp->seg_begin * 32)));
-        else                                         // all lanes in one launch
-          HIPCALL(ctx, vdf_round_tape_run_lanes(ctx, S1.field, &tape, round->t, round->lanes, (const vdf_fe*)round->inv.data(),
-                                                (const vdf_fe*)round->d_advice, round->lane_stride, (vdf_fe*)((char*)d_z2 + pp->seg_begin * 32)));
+        // (the table is the parameters' device copy: same_body above compared the table's bytes)
+        const int rc = launch_repeat_rounds(ctx, pp, S1.field, *round, round->inv.data(), round->d_advice, round->lane_stride, (char*)d_z2 + pp->seg_begin * 32);
+        if (rc != VDF_OK) return rc;
       }
       // the host-made variables go next to the rounds the lookahead context has written (vdf_ctx_wait at their launch)
       int rc = upload_fresh(ctx, S1, cs, p->h_stage[PRIMARY], d_z2);

@@ -109,8 +109,9 @@ int eval_forward_tape(int field, const vdf_round_tape* tape, const Fe* inv, Fe* 
 int eval_forward_tape_rebuild_lanes(int field, const vdf_round_tape* tape, size_t lanes, const Fe* inv, Fe* entries, size_t n, uint64_t rounds,
                                     Fe* trace, size_t walk_stride, uint64_t base, size_t group, size_t group_stride, const uint64_t* j_base,
                                     uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok);
-// the rounds one launch of a forward tape may run: min(1,024, VDF_FORWARD_TAPE_MAX_WORK / products); 0 for a tape the FORWARD rules refuse
-uint64_t forward_tape_launch_bound(const vdf_round_tape* tape);
+// "" where a tape's table names the same row for the round body's step-local j and for the chain-global J of what runs the tape over
+// a chain (`whose`: "walk" or "forward" tape; `sees`: "walks'" or "evaluator's" J): tab_rows divides t and every lane's j_base
+std::string tape_table_rows_fit_chain(const vdf_round_tape* tape, uint64_t t, size_t lanes, const uint64_t* j_base, const char* whose, const char* sees);
 
 // The periodic rows of a repeat, as detect_periodic_rows read them off a shape's triples (include/vdf_hip.h vdf_periodic_rows):
 // rows [row_begin, row_begin + row_count) are repetitions lead .. t - 1, and `view` is what the kernel and the host evaluator take.

@@ -5,10 +5,11 @@
 #include "nova_internal.hpp"
 #include "rounds.hpp"
 #include "../minroot_chain.h"
-#include "../tape_rules.h"
-#include "../tape_rebuild.h"
+#include "../tape_launch.h"
+#include "../periodic_rules.h"
 
 using namespace vdfnova;
+using namespace vdflaunch;
 
 static_assert(VDF_POW_ACC == vdf::MR_ACC && VDF_POW_NONE == vdf::MR_NONE && sizeof(vdf_pow_step) == sizeof(vdf::MinrootChainStep),
               "vdf_pow_step is minroot_chain.h's step format made public");
@@ -199,11 +200,9 @@ void replay_round(CS& cs, const RoundRecord& r, uint64_t j, const std::vector<Nu
 }
 
 // ---- the host interpreter of round tapes: a restatement of rounds.hip's tape_round that shares no text with it (the GPU tests
-// compare the device's bytes with this), only the rules: a tape is checked ONCE by tape_rules.h, then run without looking again.
-static int check_tape(const vdf_round_tape* tp, vdftape::Mode mode, vdftape::Info* info = nullptr) {
-  const std::string why = vdftape::check(tp, mode, info);
-  return why.empty() ? VDF_OK : fail(VDF_ERR_BAD_ARG, why);
-}
+// compare the device's bytes with this), only the rules: a call is checked ONCE by tape_launch.h (the tape by tape_rules.h behind
+// it) -- what the launcher of its kind refuses, in the launcher's order, code and words -- then run without looking again.
+static int refused(const Verdict& v) { return v.refused() ? fail(v.code, v.why) : VDF_OK; }
 
 // x ^ e, e a plain integer: left to right from the top set bit, as the kernel does it (any order gives the same canonical value)
 static Fe pow_plain(const Fe& x, const Fe& e, const Field& F) {
@@ -258,35 +257,30 @@ static void run_tape_round(const vdf_round_tape* tp, const Field& F, uint64_t j,
   }
 }
 
-int eval_round_tape(int fid, const vdf_round_tape* tp, uint64_t t, const Fe* inv, const Fe* advice, Fe* out) {
+// both round restatements: vdf_round_tape_run (kind RUN) is lanes = 1, its lane_stride unread; lane after lane
+static int round_tape_lanes(int fid, Kind kind, const vdf_round_tape* tp, uint64_t t, size_t lanes, const Fe* inv, const Fe* advice,
+                            size_t lane_stride, Fe* out) {
   if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
-  if (!tp || !out || !advice || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts) || (tp->n_inv && !inv)) return fail(VDF_ERR_BAD_ARG, "null argument");
-  if (t == 0 || t >= (1ull << 31)) return fail(VDF_ERR_BAD_LENGTH, "t out of range");
-  const int rc = check_tape(tp, vdftape::ROUND);
+  if (!out || !advice) return fail(VDF_ERR_BAD_ARG, "null argument");
+  const int rc = refused(round_launch(kind, tp, t, lanes, (const vdf_fe*)inv, lane_stride));
   if (rc != VDF_OK) return rc;
   const Field& F = field(fid);
   Fe s[VDF_TAPE_MAX_SLOTS];
-  for (uint64_t j = 0; j < t; ++j) {
-    const Fe* const adv[2] = {advice + j * tp->n_adv, advice + (j + 1) * tp->n_adv};
-    run_tape_round(tp, F, j, inv, adv, s, out + j * tp->n_vars);
-  }
+  for (size_t l = 0; l < lanes; ++l)
+    for (uint64_t j = 0; j < t; ++j) {
+      const Fe* const adv[2] = {advice + (l * lane_stride + j) * tp->n_adv, advice + (l * lane_stride + j + 1) * tp->n_adv};
+      run_tape_round(tp, F, j, inv + l * tp->n_inv, adv, s, out + (l * t + j) * tp->n_vars);
+    }
   return VDF_OK;
 }
 
-// vdf_round_tape_run_lanes on the host: the launcher's refusals, then lane after lane through eval_round_tape
+int eval_round_tape(int fid, const vdf_round_tape* tp, uint64_t t, const Fe* inv, const Fe* advice, Fe* out) {
+  return round_tape_lanes(fid, RUN, tp, t, 1, inv, advice, 0, out);
+}
+
 int eval_round_tape_lanes(int fid, const vdf_round_tape* tp, uint64_t t, size_t lanes, const Fe* inv, const Fe* advice, size_t lane_stride,
                           Fe* out) {
-  if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
-  if (!tp || !out || !advice || (tp->n_ops && !tp->ops) || (tp->n_consts && !tp->consts) || (tp->n_inv && !inv)) return fail(VDF_ERR_BAD_ARG, "null argument");
-  if (t == 0 || t >= (1ull << 31)) return fail(VDF_ERR_BAD_LENGTH, "t out of range");
-  if (lanes == 0 || lanes > VDF_TAPE_MAX_LANES) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_TAPE_MAX_LANES");
-  if (tp->n_inv > VDF_TAPE_MAX_INV || lanes * tp->n_inv > VDF_TAPE_MAX_INV) return fail(VDF_ERR_BAD_ARG, "lanes * n_inv > VDF_TAPE_MAX_INV");
-  if (lane_stride < t + 1 || lane_stride > ((size_t)1 << 40)) return fail(VDF_ERR_BAD_ARG, "lane_stride must be at least t + 1");
-  for (size_t l = 0; l < lanes; ++l) {
-    const int rc = eval_round_tape(fid, tp, t, inv + l * tp->n_inv, advice + l * lane_stride * tp->n_adv, out + l * t * tp->n_vars);
-    if (rc != VDF_OK) return rc;
-  }
-  return VDF_OK;
+  return round_tape_lanes(fid, RUN_LANES, tp, t, lanes, inv, advice, lane_stride, out);
 }
 
 int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out, bool forward) {
@@ -324,38 +318,15 @@ int record_walk_body(CS* cs, const vdf_walk_body* b, RoundRecord* out, bool forw
   return VDF_OK;
 }
 
-// what the walk launchers check of a tape before a launch (rounds.hip): the rules of its mode, then the slot and work caps.
-// inv_slots: the slots a walk in lanes keeps its lane's inv in (n_inv there, 0 elsewhere), counted against VDF_WALK_MAX_SLOTS
-static int check_walk_tape(const vdf_round_tape* tp, const Fe* inv, uint64_t rounds, bool forward = false, bool inv_slots = false) {
-  vdftape::Info ti;
-  const int rc = check_tape(tp, forward ? vdftape::FORWARD : vdftape::WALK, &ti);
-  if (rc != VDF_OK) return rc;
-  if (tp->n_inv && !inv) return fail(VDF_ERR_BAD_ARG, "null inv");
-  if (tp->n_slots + 2 * tp->n_adv + (inv_slots ? tp->n_inv : 0) + ti.chain_tmp > VDF_WALK_MAX_SLOTS)
-    return fail(VDF_ERR_BAD_ARG, ti.chain_tmp ? "forward walk tape: n_slots + 2 * n_adv + the chains' n_tmp > VDF_WALK_MAX_SLOTS" : inv_slots ? "walk tape in lanes: n_slots + 2 * n_adv + n_inv > VDF_WALK_MAX_SLOTS" : "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS");
-  if (rounds > (forward ? VDF_FORWARD_TAPE_MAX_WORK : VDF_WALK_MAX_WORK) / ti.products)
-    return fail(VDF_ERR_BAD_ARG, std::string("rounds x products per round > ") + (forward ? "VDF_FORWARD_TAPE_MAX_WORK" : "VDF_WALK_MAX_WORK") + " in one call: cut the walk");
-  return VDF_OK;
-}
-
-// both descending walks: vdf_round_tape_walk is lanes = 1 under its own slot cap (in_lanes false); group G = w / group is lane
+// both descending walks: vdf_round_tape_walk (kind WALK) is lanes = 1 under its own slot cap; group G = w / group is lane
 // G % lanes of step G / lanes, with that lane's j_base and inv
-static int walk_tape_lanes(int fid, const vdf_round_tape* tp, size_t lanes, bool in_lanes, const Fe* inv, Fe* entries, size_t n, uint64_t rounds,
-                           Fe* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride, const uint64_t* j_base,
+static int walk_tape_lanes(int fid, Kind kind, const vdf_round_tape* tp, size_t lanes, const Fe* inv, Fe* entries, size_t n,
+                           uint64_t rounds, Fe* trace, size_t walk_stride, size_t top, uint64_t group, uint64_t group_stride, const uint64_t* j_base,
                            uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok) {
   if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
-  if (lanes == 0 || lanes > VDF_TAPE_MAX_LANES) return fail(VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_TAPE_MAX_LANES");
-  if (tp && tp->n_inv <= VDF_TAPE_MAX_INV && lanes * tp->n_inv > VDF_TAPE_MAX_INV) return fail(VDF_ERR_BAD_ARG, "lanes * n_inv > VDF_TAPE_MAX_INV");
-  const int rc = check_walk_tape(tp, inv, rounds, false, in_lanes);
-  if (rc != VDF_OK) return rc;
-  if (!j_base) return fail(VDF_ERR_BAD_ARG, "null j_base");
-  if (expect && !ok) return fail(VDF_ERR_BAD_ARG, "expect without ok");
-  if (n == 0 || rounds == 0) return VDF_OK;
-  if (n > ((size_t)1 << 31)) return fail(VDF_ERR_BAD_LENGTH, "more than 2^31 walks");
-  if (!entries) return fail(VDF_ERR_BAD_ARG, "null entries");
-  if (trace && top + 1 < rounds) return fail(VDF_ERR_BAD_ARG, "top < rounds - 1: the walk would write below its run");
-  if (trace && heads && top < rounds) return fail(VDF_ERR_BAD_ARG, "heads with top < rounds: the landing would be written below the run");
-  if (group == 0) { group = n; group_stride = 0; }
+  const Verdict v = walk_launch({kind, tp, lanes, (const vdf_fe*)inv, j_base, n, rounds, entries, trace, walk_stride, top, group, heads, expect, ok, nullptr, 0});
+  if (v.refused() || v.nothing) return refused(v);
+  groups(n, &group, &group_stride);
   const Field& F = field(fid);
   const size_t na = tp->n_adv;
   Fe s[VDF_TAPE_MAX_SLOTS], stand[VDF_TAPE_MAX_ADV], prod[VDF_TAPE_MAX_ADV];
@@ -385,26 +356,22 @@ static int walk_tape_lanes(int fid, const vdf_round_tape* tp, size_t lanes, bool
 
 int eval_walk_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* trace, size_t walk_stride,
                    size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok) {
-  return walk_tape_lanes(fid, tp, 1, false, inv, entries, n, rounds, trace, walk_stride, top, group, group_stride, &j_base, j_group_step, heads,
+  return walk_tape_lanes(fid, WALK, tp, 1, inv, entries, n, rounds, trace, walk_stride, top, group, group_stride, &j_base, j_group_step, heads,
                          expect, ok);
 }
 
 int eval_walk_tape_lanes(int fid, const vdf_round_tape* tp, size_t lanes, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* trace,
                          size_t walk_stride, size_t top, size_t group, size_t group_stride, const uint64_t* j_base, uint64_t j_group_step,
                          int heads, const Fe* expect, int32_t* ok) {
-  return walk_tape_lanes(fid, tp, lanes, true, inv, entries, n, rounds, trace, walk_stride, top, group, group_stride, j_base, j_group_step, heads,
+  return walk_tape_lanes(fid, WALK_LANES, tp, lanes, inv, entries, n, rounds, trace, walk_stride, top, group, group_stride, j_base, j_group_step, heads,
                          expect, ok);
 }
 
 int eval_forward_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entries, size_t n, uint64_t rounds, Fe* checkpoints, uint64_t every,
                       size_t cp_stride, Fe* trace, size_t walk_stride, uint64_t base, uint64_t j_base, uint64_t j_walk_step) {
   if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
-  const int rc = check_walk_tape(tp, inv, rounds, true);
-  if (rc != VDF_OK) return rc;
-  if (checkpoints && every == 0) return fail(VDF_ERR_BAD_ARG, "checkpoints without `every`");
-  if (n == 0 || rounds == 0) return VDF_OK;
-  if (n > ((size_t)1 << 31)) return fail(VDF_ERR_BAD_LENGTH, "more than 2^31 walks");
-  if (!entries) return fail(VDF_ERR_BAD_ARG, "null entries");
+  const Verdict v = walk_launch({FORWARD, tp, 1, (const vdf_fe*)inv, nullptr, n, rounds, entries, trace, walk_stride, base, 0, 0, nullptr, nullptr, checkpoints, every});
+  if (v.refused() || v.nothing) return refused(v);
   const Field& F = field(fid);
   const size_t na = tp->n_adv;
   Fe s[VDF_TAPE_MAX_SLOTS], stand[VDF_TAPE_MAX_ADV], prod[VDF_TAPE_MAX_ADV];
@@ -426,49 +393,37 @@ int eval_forward_tape(int fid, const vdf_round_tape* tp, const Fe* inv, Fe* entr
   return VDF_OK;
 }
 
-// vdf_round_tape_rebuild_lanes on the host: the tape's rules are FORWARD's, the other refusals and the whole of the index
-// arithmetic tape_rebuild.h's -- the statement the launcher and its kernel read
+// vdf_round_tape_rebuild_lanes on the host: the refusals and the whole of the index arithmetic are tape_launch.h's -- the statement
+// the launcher and its kernel read
 int eval_forward_tape_rebuild_lanes(int fid, const vdf_round_tape* tp, size_t lanes, const Fe* inv, Fe* entries, size_t n, uint64_t rounds,
                                     Fe* trace, size_t walk_stride, uint64_t base, size_t group, size_t group_stride, const uint64_t* j_base,
                                     uint64_t j_group_step, int heads, const Fe* expect, int32_t* ok) {
   if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
-  vdftape::Info ti;
-  const int rc = check_tape(tp, vdftape::FORWARD, &ti);
-  if (rc != VDF_OK) return rc;
-  bool nothing = false;
-  const std::string why = vdfrebuild::refuse(tp, ti, lanes, (const vdf_fe*)inv, j_base, n, rounds, entries, trace, walk_stride, base, group, expect, ok, &nothing);
-  if (!why.empty()) return fail(VDF_ERR_BAD_ARG, why);
-  if (nothing) return VDF_OK;
+  const Verdict v = walk_launch({REBUILD, tp, lanes, (const vdf_fe*)inv, j_base, n, rounds, entries, trace, walk_stride, base, group, heads, expect, ok, nullptr, 0});
+  if (v.refused() || v.nothing) return refused(v);
   uint64_t grp = group, gstride = group_stride;
-  vdfrebuild::groups(n, &grp, &gstride);
+  groups(n, &grp, &gstride);
   const Field& F = field(fid);
   const size_t na = tp->n_adv;
   Fe s[VDF_TAPE_MAX_SLOTS], stand[VDF_TAPE_MAX_ADV], prod[VDF_TAPE_MAX_ADV];
   const Fe* const adv[2] = {stand, nullptr};      // an ascending walk stands on entry j
   for (size_t w = 0; w < n; ++w) {
-    const vdfrebuild::Place p = vdfrebuild::place(w, grp, walk_stride, base, (uint32_t)lanes);
+    const Place p = place(w, grp, walk_stride, base, (uint32_t)lanes);
     const Fe* lane_inv = inv + p.l * tp->n_inv;
-    uint64_t j = vdfrebuild::counter(p, j_base[p.l], j_group_step);
+    uint64_t j = counter(p, j_base[p.l], j_group_step);
     for (size_t c = 0; c < na; ++c) stand[c] = entries[w * na + c];
     if (trace && heads && p.first)
-      for (size_t c = 0; c < na; ++c) trace[vdfrebuild::trace_entry(p, gstride, p.k) * na + c] = stand[c];
+      for (size_t c = 0; c < na; ++c) trace[trace_entry(p, gstride, p.k) * na + c] = stand[c];
     for (uint64_t r = 0; r < rounds; ++r, ++j) {
       run_tape_round(tp, F, j, lane_inv, adv, s, prod);
       for (size_t c = 0; c < na; ++c) stand[c] = prod[c];
       if (trace)
-        for (size_t c = 0; c < na; ++c) trace[vdfrebuild::trace_entry(p, gstride, p.k + r + 1) * na + c] = stand[c];
+        for (size_t c = 0; c < na; ++c) trace[trace_entry(p, gstride, p.k + r + 1) * na + c] = stand[c];
     }
     for (size_t c = 0; c < na; ++c) entries[w * na + c] = stand[c];
     if (expect) ok[w] = memcmp(stand, expect + w * na, na * sizeof(Fe)) == 0;
   }
   return VDF_OK;
-}
-
-// the rounds one launch of a forward tape may run: min(1,024, VDF_FORWARD_TAPE_MAX_WORK / products); 0 for a tape FORWARD refuses
-uint64_t forward_tape_launch_bound(const vdf_round_tape* tp) {
-  vdftape::Info ti;
-  if (!vdftape::check(tp, vdftape::FORWARD, &ti).empty()) return 0;
-  return std::min<uint64_t>(1024, VDF_FORWARD_TAPE_MAX_WORK / ti.products);
 }
 
 }  // namespace vdfnova
@@ -577,35 +532,12 @@ int eval_periodic_rows(int fid, const vdf_periodic_rows* pr, uint64_t j_first, u
                        size_t num_cols, size_t num_cons, const Fe* z2, const Fe* az1, const Fe* bz1, const Fe* cz1, const Fe* u1, Fe* az2,
                        Fe* bz2, Fe* cz2, Fe* T) {
   if (!valid_field(fid)) return fail(VDF_ERR_BAD_ARG, "unknown field");
-  if (!pr || !z2 || !az1 || !bz1 || !cz1 || !u1 || !az2 || !bz2 || !cz2 || !T) return fail(VDF_ERR_BAD_ARG, "null argument");
-  if (!pr->row_start || (pr->n_terms && !pr->terms) || (pr->n_consts && !pr->consts)) return fail(VDF_ERR_BAD_ARG, "null description");
-  if (pr->n_cons == 0 || pr->n_cons > VDF_PERIODIC_MAX_ROWS || pr->n_vars == 0 || pr->n_terms > VDF_PERIODIC_MAX_TERMS ||
-      pr->n_consts > VDF_PERIODIC_MAX_CONSTS)
-    return fail(VDF_ERR_BAD_ARG, "periodic rows exceed a published cap (VDF_PERIODIC_MAX_*), or have no row or variable");
-  if (pr->row_start[0] != 0 || pr->row_start[3 * pr->n_cons] != pr->n_terms) return fail(VDF_ERR_BAD_ARG, "row_start does not span the terms");
-  for (uint32_t q = 0; q < 3 * pr->n_cons; ++q)
-    if (pr->row_start[q + 1] < pr->row_start[q] || pr->row_start[q + 1] - pr->row_start[q] > VDF_PERIODIC_MAX_ROW_TERMS)
-      return fail(VDF_ERR_BAD_ARG, "row_start descends, or a row has more than VDF_PERIODIC_MAX_ROW_TERMS terms in one matrix");
-  if (j_first < pr->j0) return fail(VDF_ERR_BAD_ARG, "j_first lies before the repetition the pattern was taken from");
-  if (reps == 0) return VDF_OK;
-  if (reps > ((uint64_t)1 << 31) / pr->n_cons || j_first > UINT32_MAX || j_first + reps > UINT32_MAX)
-    return fail(VDF_ERR_BAD_ARG, "more than 2^31 rows, or repetitions beyond 2^32");
-  const uint64_t rows = reps * pr->n_cons, j_last = j_first + reps - 1;
-  if (row_begin > num_cons || rows > num_cons - row_begin) return fail(VDF_ERR_BAD_ARG, "the row range ends beyond num_cons");
-  if (num_cols == 0 || num_cols > ((size_t)1 << 32) || seg_begin > num_cols) return fail(VDF_ERR_BAD_ARG, "num_cols out of range, or seg_begin beyond it");
-  const bool seg_far = j_last * pr->n_vars > ((uint64_t)1 << 33);
-  const int64_t first_seg = (int64_t)(seg_begin + j_first * pr->n_vars), last_seg = (int64_t)(seg_begin + j_last * pr->n_vars);
-  for (size_t e = 0; e < pr->n_terms; ++e) {
-    const vdf_periodic_term& t = pr->terms[e];
-    const std::string at = "term " + std::to_string(e);
-    if (t.kind != VDF_TERM_SEG && t.kind != VDF_TERM_ABS) return fail(VDF_ERR_BAD_ARG, at + ": unknown kind");
-    if (t.c0 >= pr->n_consts || (t.c1 != VDF_TERM_NO_SLOPE && (t.c1 >= pr->n_consts || t.kind != VDF_TERM_ABS)))
-      return fail(VDF_ERR_BAD_ARG, at + ": constant index out of range, or a slope on a SEG term");
-    if (t.kind == VDF_TERM_ABS) {
-      if (t.col >= num_cols) return fail(VDF_ERR_BAD_ARG, at + ": column beyond num_cols");
-    } else if (seg_far || first_seg + (int32_t)t.col < 0 || last_seg + (int32_t)t.col >= (int64_t)num_cols)
-      return fail(VDF_ERR_BAD_ARG, at + ": reaches a column outside [0, num_cols) in the first or the last repetition");
-  }
+  if (!z2 || !az1 || !bz1 || !cz1 || !u1 || !az2 || !bz2 || !cz2 || !T) return fail(VDF_ERR_BAD_ARG, "null argument");
+  bool nothing = false;
+  const std::string why = vdfperiodic::refuse(pr, j_first, reps, seg_begin, row_begin, num_cols, num_cons, &nothing);
+  if (!why.empty()) return fail(VDF_ERR_BAD_ARG, why);
+  if (nothing) return VDF_OK;
+  const uint64_t rows = reps * pr->n_cons;
   const Field& F = field(fid);
   const Fe* consts = (const Fe*)pr->consts;
   for (uint64_t i = 0; i < rows; ++i) {

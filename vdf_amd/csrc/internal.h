@@ -341,7 +341,8 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tape, const 
 Status vec_round_tape_rebuild_lanes(int field, const vdf_round_tape* tape, size_t lanes, const vdf_fe* inv, void* entries, size_t n,
                                     uint64_t rounds, void* trace, size_t walk_stride, uint64_t base, size_t group, size_t group_stride,
                                     const uint64_t* j_base, uint64_t j_group_step, int heads, const void* expect, int32_t* ok, hipStream_t s);
-Status round_tape_forward_max_rounds(const vdf_round_tape* tape, const vdf_fe* inv, uint64_t* max_rounds);
+// launch_bound: the rounds a launch runs when the caller names no number (tape_launch.h forward_launch_bound)
+Status round_tape_forward_max_rounds(const vdf_round_tape* tape, const vdf_fe* inv, uint64_t* max_rounds, uint64_t* launch_bound);
 // The operands every cross-term launcher shares: the fresh z2, the running A z1, B z1, C z1 and u1 (host memory: it travels as a
 // kernel argument), and what is written -- the fresh A z2, B z2, C z2 and T.  Host-side only: it ends at the launch line, where the
 // kernels keep their own __restrict__ pointers.

@@ -13,8 +13,8 @@
 #include "internal.h"
 #include "fe.cuh"
 #include "cross.cuh"
-#include "tape_rules.h"
-#include "tape_rebuild.h"
+#include "tape_launch.h"
+#include "periodic_rules.h"
 
 namespace vdf {
 
@@ -59,6 +59,10 @@ template <class P> __device__ __forceinline__ void slot_store(uint4* lds, uint32
 //
 // A NEW OP touches exactly: the op enum in include/vdf_hip.h; the rules in tape_rules.h; tape_round below; the host interpreter
 // run_tape_round in host/rounds_host.cpp (a separate restatement: the GPU tests compare the two); the recorder's compile_round there.
+// A NEW LAUNCH KIND touches exactly: a Kind in tape_launch.h with its slots and whatever it is refused for beyond the skeleton there
+// (both libraries read the refusals from that header, never from here); its kernel and launcher below, which packs and launches;
+// its index arithmetic restated in host/rounds_host.cpp (separately, unless it is shared through the header as the rebuild's is);
+// its rows in tests/launch_rules_spec.py.
 enum { TAPE_BASE = 0, TAPE_POW = 1, TAPE_POWC = 2 };      // ADMIT: the base ops; and VDF_TAPE_POW; and VDF_TAPE_POWC
 constexpr int TAPE_NO_OP = 0x100;                         // the case label of an op that is not admitted: an opcode is one byte
 
@@ -448,7 +452,7 @@ __global__ __launch_bounds__(64) void k_tape_forward_walk_tab(TapeArgs tape, For
 // chain's own forward tape (POW, POWC and in the _tab kernel TAB admitted), writes every entry it produces where vdf_cs_repeat reads
 // its advice, and is compared with the checkpoint ABOVE.  The launch, the interpreter and the two entries swapped each round are
 // k_tape_forward_walk_chain's; the groups, the per-lane counter and the invariants kept in n_inv slots of LDS are
-// k_tape_walk_lanes'.  Which walk stands where and sees which counter is tape_rebuild.h's, shared with the host restatement.
+// k_tape_walk_lanes'.  Which walk stands where and sees which counter is tape_launch.h's, shared with the host restatement.
 // LDS: the value file, the two entries, the chains' temporaries, the lane's invariants.
 struct RebuildArgs {
   uint64_t n, walk_stride, base, group, group_stride, j_group_step;
@@ -467,7 +471,7 @@ __device__ __forceinline__ void tape_rebuild(const TapeArgs& tape, const Rebuild
   const uint32_t na = tape.n_adv;
   const size_t esz = (size_t)na * 32;
   char* const ep = entries + w * esz;
-  const vdfrebuild::Place p = vdfrebuild::place(w, ra.group, ra.walk_stride, ra.base, ra.lanes);
+  const vdflaunch::Place p = vdflaunch::place(w, ra.group, ra.walk_stride, ra.base, ra.lanes);
   uint32_t stand = ra.n_slots, prod = ra.n_slots + na;
   const uint32_t tmp0 = ra.n_slots + 2 * na, inv0 = tmp0 + ra.chain_tmp;
   // the lane is a per-thread value: its counter and invariants are selected ONCE, in uniform loops over the argument elements
@@ -488,14 +492,14 @@ __device__ __forceinline__ void tape_rebuild(const TapeArgs& tape, const Rebuild
     }
     slot_store<P>(slots, inv0 + k, lane, v);
   }
-  char* tp = trace ? trace + vdfrebuild::trace_entry(p, ra.group_stride, p.k) * esz : nullptr;      // the entry stood on
+  char* tp = trace ? trace + vdflaunch::trace_entry(p, ra.group_stride, p.k) * esz : nullptr;      // the entry stood on
   const bool head = tp && ra.heads && p.first;
   for (uint32_t c = 0; c < na; ++c) {
     const Fe<P> v = fe_load<P>(ep + c * 32);
     slot_store<P>(slots, stand + c, lane, v);
     if (head) fe_store<P>(tp + c * 32, v);
   }
-  uint64_t j = vdfrebuild::counter(p, jb, ra.j_group_step);
+  uint64_t j = vdflaunch::counter(p, jb, ra.j_group_step);
   if constexpr (HAS_TAB) tab.at(j);
 #pragma unroll 1
   for (uint32_t r = 0; r < ra.rounds; ++r, ++j) {
@@ -629,17 +633,13 @@ __global__ __launch_bounds__(256) void k_nifs_cross_periodic(PeriodicArgs pa, co
   cross_finish<P>(az2, bz2, cz2, T, r, a1, b1, c1, tape_fe<P>(u1), acc[0], acc[1], acc[2]);
 }
 
+using namespace vdflaunch;      // the launch kinds and the verdicts (tape_launch.h)
 static TapeFe tape_val(const vdf_fe* p) { TapeFe v; std::memcpy(&v, p, 32); return v; }
-// Check, then pack: tape_rules.h refuses everything a tape could index out of range, before a launch; what is left here is what
-// only a launch has -- the lanes (inv holds lanes * n_inv elements, lane-major; all of them go into the block of VDF_TAPE_MAX_INV:
-// the *_lanes launchers) -- and the words of TapeArgs.  info (if asked for): the products per round and the chains' n_tmp.
-static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, vdftape::Mode mode, TapeArgs& a, vdftape::Info* info = nullptr, size_t lanes = 1) {
-  vdftape::Info got;
-  const std::string why = vdftape::check(tp, mode, &got);
-  if (!why.empty()) return Status{VDF_ERR_BAD_ARG, why};
-  if (lanes == 0 || lanes > VDF_TAPE_MAX_LANES) return Status{VDF_ERR_BAD_ARG, "lanes must be 1 .. VDF_TAPE_MAX_LANES"};
-  if (lanes * tp->n_inv > VDF_TAPE_MAX_INV) return Status{VDF_ERR_BAD_ARG, "lanes * n_inv > VDF_TAPE_MAX_INV (all lanes' inv travel in the kernel arguments)"};
-  if (tp->n_inv && !inv) return Status{VDF_ERR_BAD_ARG, "null inv"};
+static Status status_of(const Verdict& v) { return Status{v.code, v.why}; }
+// Every refusal of a launch is tape_launch.h's (with tape_rules.h's behind it), made before anything here runs: what is left is the
+// words of TapeArgs.  inv holds lanes * n_inv elements, lane-major; all of them go into the block of VDF_TAPE_MAX_INV.
+static TapeArgs pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, size_t lanes = 1) {
+  TapeArgs a;
   std::memset(&a, 0, sizeof(a));
   a.n_ops = (uint32_t)tp->n_ops; a.n_vars = tp->n_vars; a.n_adv = tp->n_adv;
   for (size_t i = 0; i < tp->n_ops; ++i) {
@@ -648,49 +648,30 @@ static Status pack_tape(const vdf_round_tape* tp, const vdf_fe* inv, vdftape::Mo
   }
   for (size_t k = 0; k < tp->n_consts; ++k) a.consts[k] = tape_val(&tp->consts[k]);
   for (size_t k = 0; k < lanes * tp->n_inv; ++k) a.inv[k] = tape_val(&inv[k]);
-  if (info) *info = got;
-  return Status{};
+  return a;
 }
 
 // the table of a tape that holds a TAB, as the k_*_tab kernels take it (the abi has checked that a kernel may read it in place)
 static TabArgs tab_args(const vdf_round_tape* tp) { return TabArgs{cbytes_of(tp->table), tp->tab_rows, tp->tab_cols}; }
 
 Status vec_round_tape(int field, const vdf_round_tape* tp, uint64_t t, const vdf_fe* inv, const void* advice, void* out, hipStream_t s) {
-  TapeArgs a;
-  vdftape::Info ti;
-  VDF_TRY(pack_tape(tp, inv, vdftape::ROUND, a, &ti));
+  const Verdict v = round_launch(RUN, tp, t, 1, inv, 0);
+  VDF_TRY(status_of(v));
+  const TapeArgs a = pack_tape(tp, inv);
   // advice read + variables written per repetition
-  KTimer kt(s, ti.tab ? "k_round_tape_tab" : "k_round_tape", 32.0 * (tp->n_adv + tp->n_vars) * t);
+  KTimer kt(s, v.ti.tab ? "k_round_tape_tab" : "k_round_tape", 32.0 * (tp->n_adv + tp->n_vars) * t);
   const dim3 grid((unsigned)((t + 63) / 64));
-  const size_t lds = (size_t)tp->n_slots * 2 * 64 * sizeof(uint4);
+  const size_t lds = lds_bytes(RUN, tp, v.ti);
   return with_field(field, [&](auto f) {
     using P = tag_t<decltype(f)>;
-    if (ti.tab) hipLaunchKernelGGL((k_round_tape_tab<P>), grid, dim3(64), lds, s, a, cbytes_of(advice), t, bytes_of(out), tab_args(tp));
+    if (v.ti.tab) hipLaunchKernelGGL((k_round_tape_tab<P>), grid, dim3(64), lds, s, a, cbytes_of(advice), t, bytes_of(out), tab_args(tp));
     else hipLaunchKernelGGL((k_round_tape<P>), grid, dim3(64), lds, s, a, cbytes_of(advice), t, bytes_of(out));
   });
 }
 
-// What both descending walks check between packing the tape and launching (vdf_hip.h): the slot cap (inv_slots: the slots a walk
-// in lanes keeps its lane's inv in), the work cap over pack_tape's products, and the layout.  *nothing: n = 0 or rounds = 0.
-static Status walk_launch_checks(const vdf_round_tape* tp, uint32_t inv_slots, uint64_t products, size_t n, uint64_t rounds,
-                                 const void* entries, const void* trace, size_t top, int heads, const void* expect, const int32_t* ok,
-                                 bool* nothing) {
-  *nothing = false;
-  if (tp->n_slots + 2 * tp->n_adv + inv_slots > VDF_WALK_MAX_SLOTS)
-    return Status{VDF_ERR_BAD_ARG, inv_slots ? "walk tape in lanes: n_slots + 2 * n_adv + n_inv > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"
-                                             : "walk tape: n_slots + 2 * n_adv > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"};
-  if (rounds > VDF_WALK_MAX_WORK / products) return Status{VDF_ERR_BAD_ARG, "rounds x products per round > VDF_WALK_MAX_WORK in one call: cut the walk"};
-  if (expect && !ok) return Status{VDF_ERR_BAD_ARG, "expect without ok"};
-  if (n == 0 || rounds == 0) { *nothing = true; return Status{}; }
-  if (n > ((size_t)1 << 31)) return Status{VDF_ERR_BAD_LENGTH, "more than 2^31 walks"};
-  if (!entries) return Status{VDF_ERR_BAD_ARG, "null entries"};
-  if (trace && top + 1 < rounds) return Status{VDF_ERR_BAD_ARG, "top < rounds - 1: the walk would write below its run"};
-  if (trace && heads && top < rounds) return Status{VDF_ERR_BAD_ARG, "heads with top < rounds: the landing would be written below the run"};
-  return Status{};
-}
-static WalkArgs walk_args(const vdf_round_tape* tp, size_t n, uint64_t rounds, size_t walk_stride, size_t top, size_t group, size_t group_stride,
+static WalkArgs walk_args(const vdf_round_tape* tp, size_t n, uint64_t rounds, size_t walk_stride, size_t top, uint64_t group, uint64_t group_stride,
                           uint64_t j_base, uint64_t j_group_step, int heads) {
-  if (group == 0) { group = n; group_stride = 0; }
+  groups(n, &group, &group_stride);
   WalkArgs wa;
   std::memset(&wa, 0, sizeof(wa));
   wa.n = n; wa.walk_stride = walk_stride; wa.top = top; wa.group = group; wa.group_stride = group_stride;
@@ -703,18 +684,15 @@ Status vec_round_tape_walk(int field, const vdf_round_tape* tp, const vdf_fe* in
                            size_t walk_stride, size_t top, size_t group, size_t group_stride, uint64_t j_base, uint64_t j_group_step,
                            int heads, const void* expect, int32_t* ok, hipStream_t s) {
   VDF_TRY(check_field(field));
-  TapeArgs a;
-  vdftape::Info ti;
-  VDF_TRY(pack_tape(tp, inv, vdftape::WALK, a, &ti));
-  bool nothing = false;
-  VDF_TRY(walk_launch_checks(tp, 0, ti.products, n, rounds, entries, trace, top, heads, expect, ok, &nothing));
-  if (nothing) return Status{};
+  const Verdict v = walk_launch({WALK, tp, 1, inv, nullptr, n, rounds, entries, trace, walk_stride, top, group, heads, expect, ok, nullptr, 0});
+  if (v.refused() || v.nothing) return status_of(v);
+  const TapeArgs a = pack_tape(tp, inv);
   const WalkArgs wa = walk_args(tp, n, rounds, walk_stride, top, group, group_stride, j_base, j_group_step, heads);
-  KTimer kt(s, ti.tab ? "k_tape_walk_tab" : "k_tape_walk", trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0);
-  const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv) * 2 * 64 * sizeof(uint4);
+  KTimer kt(s, v.ti.tab ? "k_tape_walk_tab" : "k_tape_walk", trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0);
+  const size_t lds = lds_bytes(WALK, tp, v.ti);
   return with_field(field, [&](auto f) {
     using P = tag_t<decltype(f)>;
-    if (ti.tab)
+    if (v.ti.tab)
       hipLaunchKernelGGL((k_tape_walk_tab<P>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, wa, bytes_of(entries), bytes_of(trace),
                          cbytes_of(expect), ok, tab_args(tp));
     else
@@ -726,20 +704,18 @@ Status vec_round_tape_walk(int field, const vdf_round_tape* tp, const vdf_fe* in
 Status vec_round_tape_lanes(int field, const vdf_round_tape* tp, uint64_t t, size_t lanes, const vdf_fe* inv, const void* advice,
                             size_t lane_stride, void* out, hipStream_t s) {
   VDF_TRY(check_field(field));
-  TapeArgs a;
-  vdftape::Info ti;
-  VDF_TRY(pack_tape(tp, inv, vdftape::ROUND, a, &ti, lanes));
-  if (t == 0 || t >= (1ull << 31)) return Status{VDF_ERR_BAD_LENGTH, "t out of range"};
-  if (lane_stride < t + 1 || lane_stride > ((size_t)1 << 40)) return Status{VDF_ERR_BAD_ARG, "lane_stride must be at least t + 1"};
+  const Verdict v = round_launch(RUN_LANES, tp, t, lanes, inv, lane_stride);
+  VDF_TRY(status_of(v));
+  const TapeArgs a = pack_tape(tp, inv, lanes);
   LaneRunArgs la;
   std::memset(&la, 0, sizeof(la));
   la.t = t; la.lane_stride = lane_stride; la.n_inv = tp->n_inv;
-  KTimer kt(s, ti.tab ? "k_round_tape_lanes_tab" : "k_round_tape_lanes", 32.0 * (tp->n_adv + tp->n_vars) * t * lanes);
+  KTimer kt(s, v.ti.tab ? "k_round_tape_lanes_tab" : "k_round_tape_lanes", 32.0 * (tp->n_adv + tp->n_vars) * t * lanes);
   const dim3 grid((unsigned)((t + 63) / 64), (unsigned)lanes);
-  const size_t lds = (size_t)tp->n_slots * 2 * 64 * sizeof(uint4);
+  const size_t lds = lds_bytes(RUN_LANES, tp, v.ti);
   return with_field(field, [&](auto f) {
     using P = tag_t<decltype(f)>;
-    if (ti.tab) hipLaunchKernelGGL((k_round_tape_lanes_tab<P>), grid, dim3(64), lds, s, a, la, cbytes_of(advice), bytes_of(out), tab_args(tp));
+    if (v.ti.tab) hipLaunchKernelGGL((k_round_tape_lanes_tab<P>), grid, dim3(64), lds, s, a, la, cbytes_of(advice), bytes_of(out), tab_args(tp));
     else hipLaunchKernelGGL((k_round_tape_lanes<P>), grid, dim3(64), lds, s, a, la, cbytes_of(advice), bytes_of(out));
   });
 }
@@ -748,23 +724,19 @@ Status vec_round_tape_walk_lanes(int field, const vdf_round_tape* tp, size_t lan
                                  void* trace, size_t walk_stride, size_t top, size_t group, size_t group_stride, const uint64_t* j_base,
                                  uint64_t j_group_step, int heads, const void* expect, int32_t* ok, hipStream_t s) {
   VDF_TRY(check_field(field));
-  TapeArgs a;
-  vdftape::Info ti;
-  VDF_TRY(pack_tape(tp, inv, vdftape::WALK, a, &ti, lanes));
-  if (!j_base) return Status{VDF_ERR_BAD_ARG, "null j_base"};
-  bool nothing = false;
-  VDF_TRY(walk_launch_checks(tp, tp->n_inv, ti.products, n, rounds, entries, trace, top, heads, expect, ok, &nothing));
-  if (nothing) return Status{};
+  const Verdict v = walk_launch({WALK_LANES, tp, lanes, inv, j_base, n, rounds, entries, trace, walk_stride, top, group, heads, expect, ok, nullptr, 0});
+  if (v.refused() || v.nothing) return status_of(v);
+  const TapeArgs a = pack_tape(tp, inv, lanes);
   WalkLanesArgs wl;
   std::memset(&wl, 0, sizeof(wl));
   wl.w = walk_args(tp, n, rounds, walk_stride, top, group, group_stride, 0, j_group_step, heads);
   wl.lanes = (uint32_t)lanes; wl.n_inv = tp->n_inv;
   for (size_t l = 0; l < lanes; ++l) wl.j_base[l] = j_base[l];
-  KTimer kt(s, ti.tab ? "k_tape_walk_lanes_tab" : "k_tape_walk_lanes", trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0);
-  const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv + tp->n_inv) * 2 * 64 * sizeof(uint4);
+  KTimer kt(s, v.ti.tab ? "k_tape_walk_lanes_tab" : "k_tape_walk_lanes", trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0);
+  const size_t lds = lds_bytes(WALK_LANES, tp, v.ti);
   return with_field(field, [&](auto f) {
     using P = tag_t<decltype(f)>;
-    if (ti.tab)
+    if (v.ti.tab)
       hipLaunchKernelGGL((k_tape_walk_lanes_tab<P>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, wl, bytes_of(entries), bytes_of(trace),
                          cbytes_of(expect), ok, tab_args(tp));
     else
@@ -773,20 +745,13 @@ Status vec_round_tape_walk_lanes(int field, const vdf_round_tape* tp, size_t lan
   });
 }
 
-// a forward tape checked and packed, and its slot cap (ti.chain_tmp > 0: the tape holds a POWC)
-static Status pack_forward_tape(const vdf_round_tape* tp, const vdf_fe* inv, TapeArgs& a, vdftape::Info& ti) {
-  VDF_TRY(pack_tape(tp, inv, vdftape::FORWARD, a, &ti));
-  if (tp->n_slots + 2 * tp->n_adv + ti.chain_tmp > VDF_WALK_MAX_SLOTS)
-    return Status{VDF_ERR_BAD_ARG, "forward walk tape: n_slots + 2 * n_adv + the chains' n_tmp > VDF_WALK_MAX_SLOTS (64 KiB of LDS per wavefront)"};
-  return Status{};
-}
-
-// the forward-tape rules and the work cap, nothing launched: the rounds one call may run (vdf_round_tape_eval_batch cuts by it)
-Status round_tape_forward_max_rounds(const vdf_round_tape* tp, const vdf_fe* inv, uint64_t* max_rounds) {
-  TapeArgs a;
-  vdftape::Info ti;
-  VDF_TRY(pack_forward_tape(tp, inv, a, ti));
-  *max_rounds = VDF_FORWARD_TAPE_MAX_WORK / ti.products;
+// what a forward launch of no rounds is refused for -- the tape's rules, inv, the slot cap -- nothing launched: the rounds one call
+// may run, and the rounds vdf_round_tape_eval_batch gives a launch when its caller names no number
+Status round_tape_forward_max_rounds(const vdf_round_tape* tp, const vdf_fe* inv, uint64_t* max_rounds, uint64_t* launch_bound) {
+  const Verdict v = walk_launch({FORWARD, tp, 1, inv, nullptr, 0, 0, nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr, nullptr, 0});
+  VDF_TRY(status_of(v));
+  *max_rounds = VDF_FORWARD_TAPE_MAX_WORK / v.ti.products;
+  *launch_bound = forward_launch_bound(v.ti);
   return Status{};
 }
 
@@ -794,27 +759,21 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tp, const vd
                                    void* checkpoints, uint64_t every, size_t cp_stride, void* trace, size_t walk_stride, uint64_t base,
                                    uint64_t j_base, uint64_t j_walk_step, hipStream_t s) {
   VDF_TRY(check_field(field));
-  TapeArgs a;
-  vdftape::Info ti;
-  VDF_TRY(pack_forward_tape(tp, inv, a, ti));
-  if (rounds > VDF_FORWARD_TAPE_MAX_WORK / ti.products)
-    return Status{VDF_ERR_BAD_ARG, "rounds x products per round > VDF_FORWARD_TAPE_MAX_WORK in one call: cut the walk"};
-  if (checkpoints && every == 0) return Status{VDF_ERR_BAD_ARG, "checkpoints without `every`"};
-  if (n == 0 || rounds == 0) return Status{};
-  if (n > ((size_t)1 << 31)) return Status{VDF_ERR_BAD_LENGTH, "more than 2^31 walks"};
-  if (!entries) return Status{VDF_ERR_BAD_ARG, "null entries"};
+  const Verdict v = walk_launch({FORWARD, tp, 1, inv, nullptr, n, rounds, entries, trace, walk_stride, base, 0, 0, nullptr, nullptr, checkpoints, every});
+  if (v.refused() || v.nothing) return status_of(v);
+  const TapeArgs a = pack_tape(tp, inv);
   ForwardArgs fa;
   std::memset(&fa, 0, sizeof(fa));
   fa.n = n; fa.walk_stride = walk_stride; fa.cp_stride = cp_stride; fa.every = every; fa.base = base;
   fa.j_base = j_base; fa.j_walk_step = j_walk_step;
   fa.rounds = (uint32_t)rounds; fa.n_slots = tp->n_slots;
-  const bool chain = ti.chain_tmp != 0;      // a tape with a POWC: the kernel that also runs addition chains; every other tape: the one without
-  KTimer kt(s, ti.tab ? "k_tape_forward_walk_tab" : chain ? "k_tape_forward_walk_chain" : "k_tape_forward_walk",
+  const bool chain = v.ti.chain_tmp != 0;      // a tape with a POWC: the kernel that also runs addition chains; every other tape: the one without
+  KTimer kt(s, v.ti.tab ? "k_tape_forward_walk_tab" : chain ? "k_tape_forward_walk_chain" : "k_tape_forward_walk",
             (trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0) + 64.0 * tp->n_adv * (double)n);
-  const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv + ti.chain_tmp) * 2 * 64 * sizeof(uint4);
+  const size_t lds = lds_bytes(FORWARD, tp, v.ti);
   return with_field(field, [&](auto f) {
     using P = tag_t<decltype(f)>;
-    if (ti.tab)                              // a tape with a TAB: the one kernel that admits POW, POWC and TAB (ti.chain_tmp may be 0)
+    if (v.ti.tab)                              // a tape with a TAB: the one kernel that admits POW, POWC and TAB (v.ti.chain_tmp may be 0)
       hipLaunchKernelGGL((k_tape_forward_walk_tab<P>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, fa, bytes_of(entries),
                          bytes_of(checkpoints), bytes_of(trace), tab_args(tp));
     else
@@ -823,37 +782,26 @@ Status vec_round_tape_forward_walk(int field, const vdf_round_tape* tp, const vd
   });
 }
 
-// the tape's rules are FORWARD's (tape_rules.h), the rest of the refusals tape_rebuild.h's: neither is stated here
 Status vec_round_tape_rebuild_lanes(int field, const vdf_round_tape* tp, size_t lanes, const vdf_fe* inv, void* entries, size_t n, uint64_t rounds,
                                     void* trace, size_t walk_stride, uint64_t base, size_t group, size_t group_stride, const uint64_t* j_base,
                                     uint64_t j_group_step, int heads, const void* expect, int32_t* ok, hipStream_t s) {
   VDF_TRY(check_field(field));
-  vdftape::Info ti;
-  {
-    const std::string why = vdftape::check(tp, vdftape::FORWARD, &ti);
-    if (!why.empty()) return Status{VDF_ERR_BAD_ARG, why};
-  }
-  bool nothing = false;
-  {
-    const std::string why = vdfrebuild::refuse(tp, ti, lanes, inv, j_base, n, rounds, entries, trace, walk_stride, base, group, expect, ok, &nothing);
-    if (!why.empty()) return Status{VDF_ERR_BAD_ARG, why};
-  }
-  if (nothing) return Status{};
-  TapeArgs a;
-  VDF_TRY(pack_tape(tp, inv, vdftape::FORWARD, a, nullptr, lanes));
+  const Verdict v = walk_launch({REBUILD, tp, lanes, inv, j_base, n, rounds, entries, trace, walk_stride, base, group, heads, expect, ok, nullptr, 0});
+  if (v.refused() || v.nothing) return status_of(v);
+  const TapeArgs a = pack_tape(tp, inv, lanes);
   RebuildArgs ra;
   std::memset(&ra, 0, sizeof(ra));
   uint64_t grp = group, gstride = group_stride;
-  vdfrebuild::groups(n, &grp, &gstride);
+  groups(n, &grp, &gstride);
   ra.n = n; ra.walk_stride = walk_stride; ra.base = base; ra.group = grp; ra.group_stride = gstride; ra.j_group_step = j_group_step;
   ra.rounds = (uint32_t)rounds; ra.n_slots = tp->n_slots; ra.heads = heads != 0; ra.lanes = (uint32_t)lanes; ra.n_inv = tp->n_inv;
-  ra.chain_tmp = ti.chain_tmp;
+  ra.chain_tmp = v.ti.chain_tmp;
   for (size_t l = 0; l < lanes; ++l) ra.j_base[l] = j_base[l];
-  KTimer kt(s, ti.tab ? "k_tape_rebuild_lanes_tab" : "k_tape_rebuild_lanes", (trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0) + 64.0 * tp->n_adv * (double)n);
-  const size_t lds = (size_t)(tp->n_slots + 2 * tp->n_adv + ti.chain_tmp + tp->n_inv) * 2 * 64 * sizeof(uint4);
+  KTimer kt(s, v.ti.tab ? "k_tape_rebuild_lanes_tab" : "k_tape_rebuild_lanes", (trace ? 32.0 * tp->n_adv * (double)n * (double)rounds : 0.0) + 64.0 * tp->n_adv * (double)n);
+  const size_t lds = lds_bytes(REBUILD, tp, v.ti);
   return with_field(field, [&](auto f) {
     using P = tag_t<decltype(f)>;
-    if (ti.tab)
+    if (v.ti.tab)
       hipLaunchKernelGGL((k_tape_rebuild_lanes_tab<P>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, a, ra, bytes_of(entries), bytes_of(trace),
                          cbytes_of(expect), ok, tab_args(tp));
     else
@@ -862,51 +810,31 @@ Status vec_round_tape_rebuild_lanes(int field, const vdf_round_tape* tp, size_t 
   });
 }
 
-// Everything the description could index out of range is checked here, before a launch (vdf_hip.h vdf_nifs_cross_term_periodic)
+// Everything the description could index out of range is refused by periodic_rules.h, before a launch (vdf_hip.h
+// vdf_nifs_cross_term_periodic); here it is packed: the longest list of each matrix, and how each term's coefficient is applied
 Status vec_nifs_cross_periodic(int field, const vdf_periodic_rows* pr, uint64_t j_first, uint64_t reps, size_t seg_begin, size_t row0,
                                size_t num_cols, size_t num_cons, const CrossOperands& o, hipStream_t s) {
   VDF_TRY(check_field(field));
-  if (!pr || !pr->row_start || (pr->n_terms && !pr->terms) || (pr->n_consts && !pr->consts)) return Status{VDF_ERR_BAD_ARG, "null description"};
-  if (pr->n_cons == 0 || pr->n_cons > VDF_PERIODIC_MAX_ROWS || pr->n_vars == 0 || pr->n_terms > VDF_PERIODIC_MAX_TERMS ||
-      pr->n_consts > VDF_PERIODIC_MAX_CONSTS)
-    return Status{VDF_ERR_BAD_ARG, "periodic rows exceed a published cap (VDF_PERIODIC_MAX_*), or have no row or variable"};
+  bool nothing = false;
+  const std::string why = vdfperiodic::refuse(pr, j_first, reps, seg_begin, row0, num_cols, num_cons, &nothing);
+  if (!why.empty()) return Status{VDF_ERR_BAD_ARG, why};
+  if (nothing) return Status{};
   PeriodicArgs a;
   std::memset(&a, 0, sizeof(a));
   a.n_cons = pr->n_cons; a.n_vars = pr->n_vars; a.n_terms = (uint32_t)pr->n_terms; a.n_consts = (uint32_t)pr->n_consts;
   a.j_first = j_first; a.j0 = pr->j0; a.seg_begin = seg_begin; a.row0 = row0;
-  if (pr->row_start[0] != 0 || pr->row_start[3 * pr->n_cons] != pr->n_terms) return Status{VDF_ERR_BAD_ARG, "row_start does not span the terms"};
   for (uint32_t q = 0; q < 3 * pr->n_cons; ++q) {
-    const uint32_t b = pr->row_start[q], e = pr->row_start[q + 1];
-    if (e < b || e - b > VDF_PERIODIC_MAX_ROW_TERMS) return Status{VDF_ERR_BAD_ARG, "row_start descends, or a row has more than VDF_PERIODIC_MAX_ROW_TERMS terms in one matrix"};
-    if (e - b > a.max_len[q % 3]) a.max_len[q % 3] = e - b;
-    a.row_start[q + 1] = (uint16_t)e;
+    const uint32_t len = pr->row_start[q + 1] - pr->row_start[q];
+    if (len > a.max_len[q % 3]) a.max_len[q % 3] = len;
+    a.row_start[q + 1] = pr->row_start[q + 1];
   }
-  if (j_first < pr->j0) return Status{VDF_ERR_BAD_ARG, "j_first lies before the repetition the pattern was taken from"};
-  if (reps == 0) return Status{};
-  if (reps > ((uint64_t)1 << 31) / pr->n_cons || j_first > UINT32_MAX || j_first + reps > UINT32_MAX) return Status{VDF_ERR_BAD_ARG, "more than 2^31 rows, or repetitions beyond 2^32"};
-  const uint64_t rows = reps * pr->n_cons, j_last = j_first + reps - 1;
-  if (row0 > num_cons || rows > num_cons - row0) return Status{VDF_ERR_BAD_ARG, "the row range ends beyond num_cons"};
-  if (num_cols == 0 || num_cols > ((size_t)1 << 32) || seg_begin > num_cols) return Status{VDF_ERR_BAD_ARG, "num_cols out of range, or seg_begin beyond it"};
-  // (j < 2^32, n_vars < 2^32, seg_begin <= 2^32: the products stay inside 64 bits, and below 2^34 where a SEG term is admitted)
-  const bool seg_far = j_last * pr->n_vars > ((uint64_t)1 << 33);      // (then no offset of 32 bits brings a SEG term back inside)
-  const int64_t first_seg = (int64_t)(seg_begin + j_first * pr->n_vars), last_seg = (int64_t)(seg_begin + j_last * pr->n_vars);
-  Status st = with_field(field, [&](auto f) -> Status {
+  const uint64_t rows = reps * pr->n_cons;
+  (void)with_field(field, [&](auto f) -> Status {
     using P = tag_t<decltype(f)>;
     auto fe_of = [&](uint32_t k) { Fe<P> v; std::memcpy(v.v, &pr->consts[k], 32); return v; };
     const Fe<P> p1 = fe_one<P>(), m1 = fe_neg(p1);
     for (size_t e = 0; e < pr->n_terms; ++e) {
       const vdf_periodic_term& t = pr->terms[e];
-      const std::string at = "term " + std::to_string(e);
-      if (t.kind != VDF_TERM_SEG && t.kind != VDF_TERM_ABS) return Status{VDF_ERR_BAD_ARG, at + ": unknown kind"};
-      if (t.c0 >= pr->n_consts || (t.c1 != VDF_TERM_NO_SLOPE && (t.c1 >= pr->n_consts || t.kind != VDF_TERM_ABS)))
-        return Status{VDF_ERR_BAD_ARG, at + ": constant index out of range, or a slope on a SEG term"};
-      if (t.kind == VDF_TERM_ABS) {
-        if (t.col >= num_cols) return Status{VDF_ERR_BAD_ARG, at + ": column beyond num_cols"};
-      } else {
-        const int64_t rel = (int32_t)t.col;
-        if (seg_far || first_seg + rel < 0 || last_seg + rel >= (int64_t)num_cols)
-          return Status{VDF_ERR_BAD_ARG, at + ": reaches a column outside [0, num_cols) in the first or the last repetition"};
-      }
       uint32_t how = PT_MUL;
       if (t.c1 != VDF_TERM_NO_SLOPE) how = fe_eq(fe_of(t.c1), p1) ? PT_AFFINE_UNIT : PT_AFFINE;
       else if (fe_eq(fe_of(t.c0), p1)) how = PT_ONE;
@@ -916,7 +844,6 @@ Status vec_nifs_cross_periodic(int field, const vdf_periodic_rows* pr, uint64_t 
     }
     return Status{};
   });
-  VDF_TRY(st);
   for (size_t k = 0; k < pr->n_consts; ++k) a.consts[k] = tape_val(&pr->consts[k]);
   a.rows = (uint32_t)rows;
   // the seven vectors of the cross term per row, and the gathered elements once (they are the repetitions' own variables)
