@@ -273,6 +273,20 @@ int  vdf_unsat_rows(vdf_ctx* ctx, int field, const vdf_fe* Az, const vdf_fe* Bz,
 /* out = a + r*b   (nova-snark RelaxedR1CSWitness::fold: W1 + r*W2, E1 + r*T; K6).
  * `r` is one field element (host or device).  out may alias a. */
 int  vdf_axpy(vdf_ctx* ctx, int field, const vdf_fe* a, const vdf_fe* r, const vdf_fe* b, size_t n, vdf_fe* out);
+/* Folding two RELAXED instances (Nova's folding scheme in its general form; vdf_nova.h vdf_nova_compress_aggregate).
+ * vdf_cross_term_relaxed: T = Az1 o Bz2 + Az2 o Bz1 - u1*Cz2 - u2*Cz1, canonical; with u2 = 1 byte for byte vdf_cross_term's T.
+ * vdf_fold_relaxed: in ONE pass over the n rows and in place on the index-1 vectors,
+ *   Az1 += r*Az2, Bz1 += r*Bz2, Cz1 += r*Cz2, E1 += r*T + r^2*E2
+ * (A z, B z, C z are linear in z: the accumulator's products stay current and no sparse product runs on it; z itself is folded
+ * with vdf_axpy).  r^2 is formed once on the host.  With E2 = 0 the result is byte for byte four vdf_axpy calls.
+ * u1, u2, r: canonical Montgomery elements in HOST memory (they travel in the kernel arguments).  Every vector: n elements of
+ * device memory (vdf_ptr_is_device); the vectors a call writes may not overlap any other operand.  Refused with VDF_ERR_BAD_ARG:
+ * a null pointer with n > 0, a host pointer where a vector is read or written, a device pointer for u1, u2 or r, an unknown
+ * field.  n = 0 launches nothing and touches no pointer.  Asynchronous on an asynchronous context, like their neighbours. */
+int  vdf_cross_term_relaxed(vdf_ctx* ctx, int field, const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1, const vdf_fe* u1,
+                            const vdf_fe* Az2, const vdf_fe* Bz2, const vdf_fe* Cz2, const vdf_fe* u2, size_t n, vdf_fe* T);
+int  vdf_fold_relaxed(vdf_ctx* ctx, int field, const vdf_fe* r, size_t n, vdf_fe* Az1, vdf_fe* Bz1, vdf_fe* Cz1, vdf_fe* E1,
+                      const vdf_fe* Az2, const vdf_fe* Bz2, const vdf_fe* Cz2, const vdf_fe* E2, const vdf_fe* T);
 
 /* ---- MinRoot step-circuit witness ------------------------------------------------------- */
 /* Fills the 4t+1 auxiliary values `InverseMinRootCircuit::synthesize` allocates

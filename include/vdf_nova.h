@@ -1071,6 +1071,70 @@ int  vdf_nova_snark_deserialize_batch(vdf_pp* pp, size_t count, const uint8_t* c
  * count = 0 gives *all_ok = 1.  A null pp, all_ok or (count > 0) array: VDF_ERR_BAD_ARG. */
 int  vdf_nova_verify_wire_batch(vdf_pp* pp, size_t count, const uint8_t* const in[], const size_t len[], const size_t num_steps[],
                                 const vdf_fe* z0, const vdf_fe* zi, int ok[], int status[], int* all_ok);
+/* ---- aggregation: many running proofs as ONE compressed proof ("vdf-aggregate-v1") ----------------------------------------
+ * vdf_nova_compress_batch makes K proofs of 11 KB each and its verifiers pay K arguments; lanes put many chains into one proof,
+ * but only up to 16 of equal length, fixed before the first step and proved by one prover.  Aggregation is for proofs made
+ * independently -- other provers' step counts, other times, any circuit kind, either orientation -- under one parameter set:
+ * Nova's folding scheme for two RELAXED instances folds the K running primary instances into one and the K folded secondary
+ * instances into one, and one argument per side is made for the two accumulators.
+ *
+ *   per proof k   as vdf_nova_compress begins: R1_k = the running primary instance; F2_k = the running secondary instance
+ *                 folded with the last secondary one (cross-term commitment T2_k, the Poseidon challenge the circuits
+ *                 recompute).  Statement k = what "VDFSNK03" carries: r_U1, r_U2, l_u2, T2, z_i primary, z_i secondary.
+ *   per side s    (0: the R1_k, 1: the F2_k) a transcript of oracle/spartan.py, label "aggregate": absorb("count", K u64 LE |
+ *                 s u64 LE), then EVERY instance as the compression argument absorbs one (digest, comm_W, comm_E, u, X), in
+ *                 order, before the first challenge: each challenge binds all K statements.  acc = instance 1; for k = 2..K
+ *                 (index 1: acc, index 2: instance k)
+ *                     TT_k = A z1 o B z2 + A z2 o B z1 - u1 C z2 - u2 C z1,   absorb_pt("T", commit(TT_k)),   r = challenge("r")
+ *                     W <- W1 + r W2,   E <- E1 + r TT_k + r^2 E2,   u <- u1 + r u2,   X <- X1 + r X2
+ *                     comm_W <- comm_W1 + r comm_W2,   comm_E <- comm_E1 + r commit(TT_k) + r^2 comm_E2       (r: 128 bits)
+ *   arguments     one "vdf-spartan-v3" argument per side for acc, on its own transcript "compress" as always.  For K = 1
+ *                 nothing is folded and the two arguments are byte for byte those of vdf_nova_compress.
+ *   verifier      K >= 1 and every num_steps[k] >= 1; per k the two output hashes, z_i and z_i secondary == [0] exactly as
+ *                 vdf_nova_verify_compressed checks them; its own secondary fold with T2_k; the transcripts and folds above
+ *                 on instances only (host point arithmetic); then both arguments.
+ * SOUNDNESS: knowledge soundness of Nova's folding of two relaxed instances, applied K - 1 times per side with 128-bit
+ * Fiat-Shamir challenges: a valid aggregate attests all K statements.  Nothing about zero knowledge is claimed.  The verdict
+ * is ONE bit for the whole aggregate (there is one argument); only the exact per-entry checks can name an entry.
+ *
+ *   "VDFAGG01" = magic[8] | t u64 | count u64 | digest [32] | count x statement (r_U1 | r_U2 | l_u2 | T2 | z_i primary |
+ *        z_i secondary, as in "VDFSNK03") | (count - 1) x commit(TT) primary [32] | (count - 1) x commit(TT) secondary [32]
+ *        | argument of the primary side | argument of the secondary side
+ *
+ * vdf_nova_compress_aggregate: count = 1 .. VDF_NOVA_AGGREGATE_MAX.  Entries are folded one at a time: the device scratch is
+ * one accumulator per side and one incoming instance, whatever the count.  Each incoming instance costs one sparse product
+ * (vdf_spmv3), one vdf_cross_term_relaxed, one commitment and one vdf_fold_relaxed per side; the accumulator's A z, B z, C z
+ * are folded along.  The proofs are left as vdf_nova_compress leaves them and can go on proving; a proof named twice is
+ * folded twice.  Refused before any device work, with *out = NULL and vdf_nova_last_error naming the entry: a null pp or out,
+ * count 0 or above the cap, a null proof or one made under other parameters (VDF_ERR_BAD_ARG); a proof with no steps
+ * (VDF_ERR_BAD_LENGTH).
+ * vdf_nova_verify_aggregate: z0, zi: count x arity elements, entry-major.  *ok = 1 iff every check above holds.  *bad_entry
+ * (may be NULL) = the first entry whose exact checks fail, -1 when they all pass: a failing argument gives *ok = 0,
+ * *bad_entry = -1.  A count other than the aggregate's gives *ok = 0 and VDF_OK; other parameters: VDF_ERR_BAD_ARG.
+ * vdf_nova_aggregate_deserialize: the codes of vdf_nova_snark_deserialize (VDF_ERR_BAD_ARG: foreign magic, another t or
+ * digest; VDF_ERR_BAD_LENGTH: a length that does not fit count and the shapes; VDF_ERR_NONCANONICAL: an element out of range
+ * or bytes that decode to no point). */
+#define VDF_NOVA_AGGREGATE_MAX 1024
+typedef struct vdf_aggregate vdf_aggregate;
+int  vdf_nova_compress_aggregate(vdf_pp* pp, size_t count, const vdf_proof* const proofs[], vdf_aggregate** out);
+int  vdf_nova_verify_aggregate(const vdf_aggregate* agg, vdf_pp* pp, size_t count, const size_t num_steps[], const vdf_fe* z0,
+                               const vdf_fe* zi, int* ok, int64_t* bad_entry);
+void vdf_nova_aggregate_free(vdf_aggregate* agg);
+size_t vdf_nova_aggregate_count(const vdf_aggregate* agg);
+size_t vdf_nova_aggregate_serialized_size(const vdf_aggregate* agg);
+int  vdf_nova_aggregate_serialize(const vdf_aggregate* agg, uint8_t* out, size_t cap);
+int  vdf_nova_aggregate_deserialize(vdf_pp* pp, const uint8_t* in, size_t len, vdf_aggregate** out);
+/* Host only, no context: the verifier's transcript and folds of ONE side over plain arrays (vdf_nova_verify_aggregate runs the
+ * same code on its decoded instances).  A relaxed instance as the wire encodes it: */
+typedef struct vdf_wire_instance { uint8_t comm_W[32], comm_E[32], u[32], X[2][32]; } vdf_wire_instance;
+/* field_of_primary: the orientation (VDF_FIELD_FQ: the parameters' default); side 0 / 1: instances over that field / the other
+ * one, commitments on the curve whose scalars it is; digest: the parameters'.  inst: count instances, comm_TT: count - 1 points
+ * (may be NULL for count = 1).  *acc = the folded instance; r_out (may be NULL): the count - 1 challenges, Montgomery form of
+ * the side's field.  VDF_ERR_BAD_ARG: a null pointer, an unknown field or side, count outside 1 .. VDF_NOVA_AGGREGATE_MAX;
+ * VDF_ERR_NONCANONICAL: an element out of range or bytes that decode to no point. */
+int  vdf_nova_aggregate_fold_instances(int field_of_primary, int side, const uint8_t digest[32], size_t count,
+                                       const vdf_wire_instance inst[], const uint8_t comm_TT[][32], vdf_wire_instance* acc,
+                                       vdf_fe r_out[]);
 size_t vdf_nova_proof_serialized_size(const vdf_proof* proof);
 int  vdf_nova_proof_serialize(const vdf_proof* proof, uint8_t* out, size_t cap);
 int  vdf_nova_proof_deserialize(vdf_pp* pp, const uint8_t* in, size_t len, vdf_proof** out);

@@ -80,6 +80,8 @@ PROTOTYPES = {
     "vdf_spmv3": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "vdf_cross_term": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vdf_axpy": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "vdf_cross_term_relaxed": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vdf_fold_relaxed": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdf_minroot_witness": (_i, [_vp, _i, _vp, _vp, _u64, _vp]),
     "vdf_minroot_step_z": (_i, [_vp, _i, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "vdf_minroot_step_z_packed": (_i, [_vp, _i, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),

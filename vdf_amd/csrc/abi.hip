@@ -1821,6 +1821,43 @@ int vdf_fold_many(vdf_ctx* ctx, int field, const vdf_fe* r, int k, vdf_fe* const
   });
 }
 
+// the operands of the two relaxed-fold calls: host scalars, device vectors, nothing null (n > 0)
+static Status check_relaxed_operands(std::initializer_list<const void*> scalars, std::initializer_list<const void*> vectors) {
+  for (const void* h : scalars) {
+    if (!h) return Status{VDF_ERR_BAD_ARG, "null argument"};
+    if (ptr_is_device(h)) return Status{VDF_ERR_BAD_ARG, "scalar operands of fused calls live in host memory"};
+  }
+  for (const void* v : vectors) {
+    if (!v) return Status{VDF_ERR_BAD_ARG, "null argument"};
+    if (!ptr_is_device(v)) return Status{VDF_ERR_BAD_ARG, "vector operands of fused calls live in device memory"};
+  }
+  return Status{};
+}
+
+int vdf_cross_term_relaxed(vdf_ctx* ctx, int field, const vdf_fe* Az1, const vdf_fe* Bz1, const vdf_fe* Cz1, const vdf_fe* u1,
+                           const vdf_fe* Az2, const vdf_fe* Bz2, const vdf_fe* Cz2, const vdf_fe* u2, size_t n, vdf_fe* T) {
+  return guarded(ctx, [&]() -> Status {
+    VDF_TRY(vdf::check_field(field));
+    if (n == 0) return Status{};
+    VDF_TRY(check_relaxed_operands({u1, u2}, {Az1, Bz1, Cz1, Az2, Bz2, Cz2, T}));
+    VDF_TRY(vdf::vec_cross_term_relaxed(field, Az1, Bz1, Cz1, u1, Az2, Bz2, Cz2, u2, n, T, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
+int vdf_fold_relaxed(vdf_ctx* ctx, int field, const vdf_fe* r, size_t n, vdf_fe* Az1, vdf_fe* Bz1, vdf_fe* Cz1, vdf_fe* E1,
+                     const vdf_fe* Az2, const vdf_fe* Bz2, const vdf_fe* Cz2, const vdf_fe* E2, const vdf_fe* T) {
+  return guarded(ctx, [&]() -> Status {
+    VDF_TRY(vdf::check_field(field));
+    if (n == 0) return Status{};
+    VDF_TRY(check_relaxed_operands({r}, {Az1, Bz1, Cz1, E1, Az2, Bz2, Cz2, E2, T}));
+    VDF_TRY(vdf::vec_fold_relaxed(field, r, n, Az1, Bz1, Cz1, E1, Az2, Bz2, Cz2, E2, T, ctx->stream));
+    if (!ctx->async) VDF_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    return Status{};
+  });
+}
+
 int vdf_ctx_wait(vdf_ctx* ctx, vdf_ctx* other) {
   if (!other || other == ctx) return ctx ? VDF_OK : VDF_ERR_BAD_ARG;
   return guarded(ctx, [&]() -> Status {

@@ -1,0 +1,418 @@
+// libvdf_nova.so, part 4: many running proofs under one parameter set aggregated into ONE compressed proof by folding.
+//
+// Protocol "vdf-aggregate-v1" (restated by tests/aggregate_spec.py).  Per proof k the prelude of vdf_nova_compress: R1_k = the
+// running primary instance, F2_k = the running secondary instance folded with the last secondary one (cross-term commitment
+// T2_k, the Poseidon challenge the circuits recompute).  Per side (0: the R1_k, 1: the F2_k) a transcript "aggregate" absorbs
+// count | side and then EVERY instance before the first challenge is drawn; acc = instance 1, and for k = 2..K
+//   TT_k = A z1 o B z2 + A z2 o B z1 - u1 C z2 - u2 C z1   (index 1: acc, index 2: instance k; vdf_cross_term_relaxed)
+//   absorb commit(TT_k), r = a 128-bit challenge
+//   W <- W1 + r W2, E <- E1 + r TT_k + r^2 E2, u <- u1 + r u2, X <- X1 + r X2                      (vdf_fold_relaxed, vdf_axpy)
+//   comm_W <- comm_W1 + r comm_W2, comm_E <- comm_E1 + r comm_TT_k + r^2 comm_E2
+// and one argument per side (compress_host.cpp, unchanged, on its own transcript "compress") for the two accumulators.
+//
+// Soundness: knowledge soundness of Nova's folding scheme for two relaxed instances (Kothapalli, Setty, Tzialla: "Nova",
+// CRYPTO 2022, construction 1 with both instances relaxed), applied K - 1 times per side with 128-bit Fiat-Shamir challenges
+// that bind every statement of the aggregate; a valid aggregate attests all K statements.  Nothing about zero knowledge is claimed.
+#include "nova_internal.hpp"
+
+using namespace vdfnova;
+
+struct vdf_aggregate {
+  struct Statement {                 // what "VDFSNK03" carries of a proof in front of its arguments
+    Inst r_U1, r_U2, l_u2;
+    Aff T2;
+    std::vector<Fe> zi1;
+    Fe zi2;
+  };
+  std::vector<Statement> st;
+  std::vector<Aff> TT[2];            // the count - 1 cross-term commitments of each side's folds
+  Spartan sp[2];                     // the arguments for the two accumulators
+  uint64_t t = 0;
+  uint8_t digest[32];
+  int field = VDF_FIELD_FQ;          // the orientation: the primary side's scalar field
+  size_t arity = 0;
+};
+
+namespace {
+
+// a <- a + r b with the cross-term commitment TT (r: Montgomery form, raw: the same 128-bit integer): the points by host arithmetic
+void fold_pair(const Side& sd, Inst& a, const Inst& b, const Aff& TT, const Fe& r, const uint64_t raw[4]) {
+  const Field& F = *sd.F;
+  const Field& Fb = *sd.Fb;
+  const Fe r2 = from_mont(sqr(r, F), F);                                    // r^2 mod the group order, a plain 255-bit integer
+  const Pt w = pt_add(pt_from_aff(a.comm_W, Fb), pt_mul(pt_from_aff(b.comm_W, Fb), raw, 128, Fb), Fb);
+  Pt e = pt_add(pt_from_aff(a.comm_E, Fb), pt_mul(pt_from_aff(TT, Fb), raw, 128, Fb), Fb);
+  e = pt_add(e, pt_mul(pt_from_aff(b.comm_E, Fb), r2.l, 255, Fb), Fb);
+  a.comm_W = pt_to_aff(w, Fb);
+  a.comm_E = pt_to_aff(e, Fb);
+  a.u = add(a.u, mul(r, b.u, F), F);
+  for (int j = 0; j < NUM_IO; ++j) a.X[j] = add(a.X[j], mul(r, b.X[j], F), F);
+}
+
+// Steps 2-3 of the protocol on instances alone: the transcript, the challenges (Montgomery form of the side's scalar field) and
+// the folded instance.  sd: F, Fb and digest are read, nothing else.
+void fold_instances_core(const Side& sd, int side, size_t count, const Inst* inst, const Aff* TT, Inst* acc, Fe* r_out) {
+  const Field& F = *sd.F;
+  const Field& Fb = *sd.Fb;
+  Transcript tr("aggregate");
+  const uint64_t head[2] = {(uint64_t)count, (uint64_t)side};
+  tr.absorb("count", head, 16);
+  for (size_t k = 0; k < count; ++k) instance_bytes(tr, sd, inst[k].comm_W, inst[k].comm_E, inst[k].u, inst[k].X);
+  Inst a = inst[0];
+  for (size_t k = 1; k < count; ++k) {
+    tr.absorb_pt("T", &TT[k - 1], 1, Fb);
+    uint64_t raw[4];
+    const Fe r = tr.challenge("r", F, raw);
+    fold_pair(sd, a, inst[k], TT[k - 1], r, raw);
+    if (r_out) r_out[k - 1] = r;
+  }
+  *acc = a;
+}
+
+Side host_side(int field_of_primary, int side, const uint8_t digest[32]) {
+  Side sd;
+  sd.side = side;
+  sd.field = cycle_field(field_of_primary, side);
+  sd.F = &field(sd.field);
+  sd.Fb = &field(cycle_field(field_of_primary, 1 - side));
+  memcpy(sd.digest, digest, 32);
+  return sd;
+}
+
+// one side's argument on the wire (as vdf_nova_snark_serialize lays it out: 32-byte points)
+uint8_t* put_argument(uint8_t* o, const Spartan& sp, const Field& F, const Field& Fb) {
+  for (const auto& ev : sp.outer) for (const Fe& v : ev) o = wire_put_fe(o, v, F);
+  for (const Fe& v : sp.claims) o = wire_put_fe(o, v, F);
+  for (const auto& ev : sp.inner) for (const Fe& v : ev) o = wire_put_fe(o, v, F);
+  o = wire_put_fe(o, sp.w_eval, F);
+  for (const Ipa* ip : {&sp.ipaW, &sp.ipaE}) {
+    for (size_t j = 0; j < ip->L.size(); ++j) { pt_compress(ip->L[j], Fb, o); pt_compress(ip->R[j], Fb, o + 32); o += 64; }
+    for (const Fe& v : ip->a) o = wire_put_fe(o, v, F);
+  }
+  return o;
+}
+const uint8_t* get_argument(const uint8_t* i, Spartan& p, const Layout& L, const Field& F, const Field& Fb, bool* canonical, bool* on_curve) {
+  spartan_resize(p, L);
+  auto get = [&](Fe& v) { *canonical &= wire_get_fe(i, F, &v); i += 32; };
+  for (auto& ev : p.outer) for (Fe& v : ev) get(v);
+  for (Fe& v : p.claims) get(v);
+  for (auto& ev : p.inner) for (Fe& v : ev) get(v);
+  get(p.w_eval);
+  for (Ipa* ip : {&p.ipaW, &p.ipaE}) {
+    for (size_t j = 0; j < ip->L.size(); ++j) {
+      *on_curve &= pt_decompress(i, Fb, &ip->L[j]);
+      *on_curve &= pt_decompress(i + 32, Fb, &ip->R[j]);
+      i += 64;
+    }
+    for (Fe& v : ip->a) get(v);
+  }
+  return i;
+}
+
+constexpr size_t AGG_HEADER = 8 + 8 + 8 + 32;
+size_t aggregate_wire_size(size_t count, size_t arity, const Layout L[2]) {
+  return AGG_HEADER + count * statement_wire(arity) + 2 * (count - 1) * 32 + spartan_wire_size(L[0]) + spartan_wire_size(L[1]);
+}
+
+// One side's accumulator on the device: z = [W | u | X], E, and A z, B z, C z kept current by the fold (they are linear in z);
+// beside it the products of the incoming instance and the cross term.
+struct SideFold {
+  const Side& sd;
+  vdf_ctx* ctx;
+  void *z = nullptr, *E = nullptr, *abc[3] = {}, *abc2[3] = {}, *T = nullptr;
+  Inst inst;
+  size_t have = 0;
+  Transcript tr{"aggregate"};
+  SideFold(const Side& s, vdf_ctx* c) : sd(s), ctx(c) {}
+  int alloc(DevBufs& bufs, bool folds) {
+    { int rc = bufs.zeros(sd.ncols, &z); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+    { int rc = bufs.zeros(sd.num_cons, &E); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+    if (!folds) return VDF_OK;                       // a single proof: the accumulator is a copy of its instance
+    for (void** p : {&abc[0], &abc[1], &abc[2], &abc2[0], &abc2[1], &abc2[2], &T}) {
+      int rc = bufs.zeros(sd.num_cons, p);
+      if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx));
+    }
+    return VDF_OK;
+  }
+  void start(size_t count, const Inst* all) {        // every instance is absorbed before the first challenge
+    const uint64_t head[2] = {(uint64_t)count, (uint64_t)sd.side};
+    tr.absorb("count", head, 16);
+    for (size_t k = 0; k < count; ++k) instance_bytes(tr, sd, all[k].comm_W, all[k].comm_E, all[k].u, all[k].X);
+  }
+  // the next instance with its witness on the device (left as it is); *TT: the commitment to the cross term of a fold
+  int take(const Inst& in, const void* d_z, const void* d_E, bool folds, Aff* TT) {
+    const Field& F = *sd.F;
+    const Field& Fb = *sd.Fb;
+    if (have++ == 0) {
+      inst = in;
+      HIPCALL(ctx, vdf_dev_memcpy(ctx, z, d_z, sd.ncols * 32));
+      HIPCALL(ctx, vdf_dev_memcpy(ctx, E, d_E, sd.num_cons * 32));
+      if (folds) HIPCALL(ctx, vdf_spmv3(ctx, sd.shape, (const vdf_fe*)z, (vdf_fe*)abc[0], (vdf_fe*)abc[1], (vdf_fe*)abc[2]));
+      return VDF_OK;
+    }
+    const size_t n = sd.num_cons;
+    HIPCALL(ctx, vdf_spmv3(ctx, sd.shape, (const vdf_fe*)d_z, (vdf_fe*)abc2[0], (vdf_fe*)abc2[1], (vdf_fe*)abc2[2]));
+    HIPCALL(ctx, vdf_cross_term_relaxed(ctx, sd.field, (const vdf_fe*)abc[0], (const vdf_fe*)abc[1], (const vdf_fe*)abc[2], (const vdf_fe*)&inst.u,
+                                        (const vdf_fe*)abc2[0], (const vdf_fe*)abc2[1], (const vdf_fe*)abc2[2], (const vdf_fe*)&in.u, n, (vdf_fe*)T));
+    vdf_jac jt;
+    HIPCALL(ctx, vdf_msm(ctx, sd.gens, 0, (const vdf_fe*)T, n, 1, &jt));          // (a host result: the call waits for it)
+    *TT = jac_to_aff(jt, Fb);
+    tr.absorb_pt("T", TT, 1, Fb);
+    uint64_t raw[4];
+    const Fe r = tr.challenge("r", F, raw);
+    HIPCALL(ctx, vdf_fold_relaxed(ctx, sd.field, (const vdf_fe*)&r, n, (vdf_fe*)abc[0], (vdf_fe*)abc[1], (vdf_fe*)abc[2], (vdf_fe*)E,
+                                  (const vdf_fe*)abc2[0], (const vdf_fe*)abc2[1], (const vdf_fe*)abc2[2], (const vdf_fe*)d_E, (const vdf_fe*)T));
+    HIPCALL(ctx, vdf_axpy(ctx, sd.field, (const vdf_fe*)z, (const vdf_fe*)&r, (const vdf_fe*)d_z, sd.ncols, (vdf_fe*)z));
+    fold_pair(sd, inst, in, *TT, r, raw);                                    // the instance, as the verifier folds it
+    return VDF_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int vdf_nova_compress_aggregate(vdf_pp* pp, size_t count, const vdf_proof* const proofs[], vdf_aggregate** out) {
+  return nova_guard([&]() -> int {
+    if (!pp || !out) return fail(VDF_ERR_BAD_ARG, "null argument");
+    *out = nullptr;
+    if (count == 0 || count > VDF_NOVA_AGGREGATE_MAX) return fail(VDF_ERR_BAD_ARG, "count must be 1.." + std::to_string(VDF_NOVA_AGGREGATE_MAX));
+    if (!proofs) return fail(VDF_ERR_BAD_ARG, "null argument");
+    for (size_t q = 0; q < count; ++q) {
+      const vdf_proof* p = proofs[q];
+      if (!p) return fail(VDF_ERR_BAD_ARG, "entry " + std::to_string(q) + ": null proof");
+      if (p->pp != pp) return fail(VDF_ERR_BAD_ARG, "entry " + std::to_string(q) + ": proof was made under other public parameters");
+      if (p->i == 0) return fail(VDF_ERR_BAD_LENGTH, "entry " + std::to_string(q) + ": nothing to compress");
+    }
+    for (size_t q = 0; q < count; ++q) { int rc = finalize_l2(proofs[q]); if (rc != VDF_OK) return rc; }
+    vdf_ctx* ctx = pp->ctx;
+    const Side& S1 = pp->s[PRIMARY];
+    const Side& S2 = pp->s[SECONDARY];
+    int was_async = 0;
+    HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
+    HIPCALL(ctx, vdf_ctx_sync(ctx));
+    HIPCALL(ctx, vdf_ctx_set_async(ctx, 1));
+    struct Restore { vdf_ctx* c; int a; ~Restore() { vdf_ctx_sync(c); vdf_ctx_set_async(c, a); } } restore{ctx, was_async};
+    std::unique_ptr<vdf_aggregate> a(new vdf_aggregate());
+    a->t = pp->t;
+    a->field = pp->field;
+    a->arity = pp->arity;
+    memcpy(a->digest, pp->digest, 32);
+    a->st.resize(count);
+    const bool folds = count > 1;
+    // device scratch: one accumulator per side and one incoming folded secondary instance, whatever the count
+    DevBufs bufs(ctx);
+    SideFold f1(S1, ctx), f2(S2, ctx);
+    { int rc = f1.alloc(bufs, folds); if (rc != VDF_OK) return rc; }
+    { int rc = f2.alloc(bufs, folds); if (rc != VDF_OK) return rc; }
+    void *d_fz, *d_fE;
+    { int rc = bufs.zeros(S2.ncols, &d_fz); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+    { int rc = bufs.zeros(S2.num_cons, &d_fE); if (rc != VDF_OK) return fail(rc, vdf_last_error(ctx)); }
+    // Every instance is absorbed before the first challenge of its side, and a secondary instance F2_k is the result of a
+    // prelude: the preludes run first, entry by entry.  Each leaves its cross term T2_k in the proof's own secondary scratch
+    // vector, so the folded witness of an entry is two vdf_axpy away when its turn to be folded comes.
+    std::vector<Inst> i1(count), i2(count);
+    for (size_t q = 0; q < count; ++q) {
+      vdf_snark s;
+      { int rc = compress_prelude(proofs[q], pp, &s, d_fz, d_fE, &i2[q]); if (rc != VDF_OK) return rc; }
+      vdf_aggregate::Statement& st = a->st[q];
+      st.r_U1 = s.r_U1; st.r_U2 = s.r_U2; st.l_u2 = s.l_u2; st.T2 = s.T2; st.zi1 = s.zi1; st.zi2 = s.zi2[0];
+      i1[q] = s.r_U1;
+    }
+    f1.start(count, i1.data());
+    f2.start(count, i2.data());
+    a->TT[0].resize(count - 1);
+    a->TT[1].resize(count - 1);
+    for (size_t q = 0; q < count; ++q) {
+      const vdf_proof* p = proofs[q];
+      Aff tt;
+      { int rc = f1.take(i1[q], p->r[PRIMARY].d_z, p->r[PRIMARY].d_E, folds, &tt); if (rc != VDF_OK) return rc; }
+      if (q) a->TT[0][q - 1] = tt;
+      if (folds) {                                     // (a single entry's folded witness is where its prelude left it)
+        const vdf_aggregate::Statement& st = a->st[q];
+        const SideState& s2 = p->r[SECONDARY];
+        uint64_t r[4];
+        fold_challenge(pp, st.r_U2, st.l_u2, st.T2, r);
+        const Fe rf = int_to_fe(r, *S2.F);
+        HIPCALL(ctx, vdf_axpy(ctx, S2.field, (const vdf_fe*)s2.d_z, (const vdf_fe*)&rf, (const vdf_fe*)p->d_l2z, S2.ncols, (vdf_fe*)d_fz));
+        HIPCALL(ctx, vdf_axpy(ctx, S2.field, (const vdf_fe*)s2.d_E, (const vdf_fe*)&rf, (const vdf_fe*)s2.d_T, S2.num_cons, (vdf_fe*)d_fE));
+      }
+      { int rc = f2.take(i2[q], d_fz, d_fE, folds, &tt); if (rc != VDF_OK) return rc; }
+      if (q) a->TT[1][q - 1] = tt;
+    }
+    std::lock_guard<std::mutex> aux_lock(pp->aux_mu);
+    const ProveIn in1{f1.inst.comm_W, f1.inst.comm_E, f1.inst.u, f1.inst.X, f1.z, f1.E, &a->sp[0]};
+    const ProveIn in2{f2.inst.comm_W, f2.inst.comm_E, f2.inst.u, f2.inst.X, f2.z, f2.E, &a->sp[1]};
+    { int rc = prove_both_sides(pp, 1, &in1, &in2, &pp->arena[PRIMARY], &pp->arena[SECONDARY]); if (rc != VDF_OK) return rc; }
+    *out = a.release();
+    return VDF_OK;
+  });
+}
+
+void vdf_nova_aggregate_free(vdf_aggregate* agg) { delete agg; }
+size_t vdf_nova_aggregate_count(const vdf_aggregate* agg) { return agg ? agg->st.size() : 0; }
+
+int vdf_nova_aggregate_fold_instances(int field_of_primary, int side, const uint8_t digest[32], size_t count, const vdf_wire_instance inst[],
+                                      const uint8_t comm_TT[][32], vdf_wire_instance* acc, vdf_fe r_out[]) {
+  return nova_guard([&]() -> int {
+    if (!valid_field(field_of_primary) || (side != 0 && side != 1)) return fail(VDF_ERR_BAD_ARG, "unknown field or side");
+    if (!digest || !inst || !acc || (count > 1 && !comm_TT)) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (count == 0 || count > VDF_NOVA_AGGREGATE_MAX) return fail(VDF_ERR_BAD_ARG, "count must be 1.." + std::to_string(VDF_NOVA_AGGREGATE_MAX));
+    const Side sd = host_side(field_of_primary, side, digest);
+    std::vector<Inst> in(count);
+    std::vector<Aff> tt(count - 1);
+    bool canonical = true, on_curve = true;
+    for (size_t k = 0; k < count; ++k) get_inst(reinterpret_cast<const uint8_t*>(&inst[k]), &in[k], sd, true, &canonical, &on_curve);
+    for (size_t k = 0; k + 1 < count; ++k) on_curve &= pt_decompress(comm_TT[k], *sd.Fb, &tt[k]);
+    if (!canonical) return fail(VDF_ERR_NONCANONICAL, "a field element of an instance is not canonical");
+    if (!on_curve) return fail(VDF_ERR_NONCANONICAL, "a point does not decode to a curve point");
+    Inst folded;
+    fold_instances_core(sd, side, count, in.data(), tt.data(), &folded, reinterpret_cast<Fe*>(r_out));
+    put_inst(reinterpret_cast<uint8_t*>(acc), folded, sd, true);
+    return VDF_OK;
+  });
+}
+
+int vdf_nova_verify_aggregate(const vdf_aggregate* agg, vdf_pp* pp, size_t count, const size_t num_steps[], const vdf_fe* z0, const vdf_fe* zi,
+                              int* ok, int64_t* bad_entry) {
+  return nova_guard([&]() -> int {
+    if (!agg || !pp || !ok) return fail(VDF_ERR_BAD_ARG, "null argument");
+    *ok = 0;
+    if (bad_entry) *bad_entry = -1;
+    if (agg->t != pp->t || memcmp(agg->digest, pp->digest, 32) != 0) return fail(VDF_ERR_BAD_ARG, "aggregate was made under other public parameters");
+    if (count == 0 || count != agg->st.size()) return VDF_OK;
+    if (!num_steps || !z0 || !zi) return fail(VDF_ERR_BAD_ARG, "null argument");
+    const Side& S1 = pp->s[PRIMARY];
+    const Side& S2 = pp->s[SECONDARY];
+    const Field& F1 = *S1.F;
+    const Field& F2 = *S2.F;
+    const size_t ar = pp->arity;
+    auto bad = [&](size_t k) { if (bad_entry) *bad_entry = (int64_t)k; return VDF_OK; };
+    for (size_t k = 0; k < count; ++k) if (num_steps[k] == 0) return bad(k);
+    // the exact checks of every entry (as vdf_nova_verify_compressed makes them), then the verifier's own secondary fold
+    std::vector<Inst> i1(count), i2(count);
+    for (size_t k = 0; k < count; ++k) {
+      const vdf_aggregate::Statement& s = agg->st[k];
+      if (s.zi1.size() != ar) return bad(k);
+      const Fe* z0k = (const Fe*)z0 + k * ar;
+      const std::vector<Fe> z0p(z0k, z0k + ar), z0s(1, zero()), zi2(1, s.zi2);
+      uint64_t hv[4];
+      hash_state(S1.field, pp->params[PRIMARY], from_u64(num_steps[k], F1), z0p, s.zi1, to_relaxed(s.r_U2, F2), hv, pp->ro);
+      if (int_to_fe(hv, F2) != s.l_u2.X[0]) return bad(k);
+      hash_state(S2.field, pp->params[SECONDARY], from_u64(num_steps[k], F2), z0s, zi2, to_relaxed(s.r_U1, F1), hv, pp->ro);
+      if (int_to_fe(hv, F2) != s.l_u2.X[1]) return bad(k);
+      if (memcmp(s.zi1.data(), (const Fe*)zi + k * ar, 32 * ar) != 0 || !s.zi2.is_zero()) return bad(k);
+      uint64_t r[4];
+      fold_challenge(pp, s.r_U2, s.l_u2, s.T2, r);
+      i1[k] = s.r_U1;
+      i2[k] = fold_instance(S2, s.r_U2, s.l_u2, s.T2, r);
+    }
+    if (agg->TT[0].size() != count - 1 || agg->TT[1].size() != count - 1) return VDF_OK;
+    Inst acc[2];
+    fold_instances_core(S1, PRIMARY, count, i1.data(), agg->TT[0].data(), &acc[0], nullptr);
+    fold_instances_core(S2, SECONDARY, count, i2.data(), agg->TT[1].data(), &acc[1], nullptr);
+    vdf_ctx* ctx = pp->ctx;
+    int was_async = 0;
+    HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
+    HIPCALL(ctx, vdf_ctx_sync(ctx));
+    HIPCALL(ctx, vdf_ctx_set_async(ctx, 1));
+    struct Restore { vdf_ctx* c; int a; ~Restore() { vdf_ctx_sync(c); vdf_ctx_set_async(c, a); } } restore{ctx, was_async};
+    for (int side = 0; side < 2; ++side) {
+      const Side& sd = pp->s[side];
+      IpaDeferred d[2];
+      bool good = false;
+      int rc = spartan_replay(sd, acc[side].comm_W, acc[side].comm_E, acc[side].u, acc[side].X, agg->sp[side], d, &good);
+      if (rc != VDF_OK || !good) return rc;
+      DevBufs bufs(sd.ctx, sd.arena);
+      const size_t n = std::max(d[0].n, d[1].n);
+      void* d_s;
+      { int rc2 = bufs.reserve(n); if (rc2 != VDF_OK) return fail(rc2, vdf_last_error(sd.ctx)); }
+      { int rc2 = bufs.zeros(n, &d_s); if (rc2 != VDF_OK) return fail(rc2, vdf_last_error(sd.ctx)); }
+      for (int q = 0; q < 2; ++q) {
+        rc = ipa_check_one(sd, d[q], d_s, &good);
+        if (rc != VDF_OK || !good) return rc;
+      }
+    }
+    *ok = 1;
+    return VDF_OK;
+  });
+}
+
+// ---- "VDFAGG01" (layout in include/vdf_nova.h) ---------------------------------------------------------------------------------
+size_t vdf_nova_aggregate_serialized_size(const vdf_aggregate* agg) {
+  if (!agg || agg->st.empty()) return 0;
+  size_t n = AGG_HEADER + agg->st.size() * statement_wire(agg->arity) + 2 * (agg->st.size() - 1) * 32;
+  for (const Spartan& p : agg->sp)
+    n += 32 * (3 * p.outer.size() + 4 + 2 * p.inner.size() + 1 + p.ipaW.a.size() + p.ipaE.a.size()) + 64 * (p.ipaW.L.size() + p.ipaE.L.size());
+  return n;
+}
+
+int vdf_nova_aggregate_serialize(const vdf_aggregate* agg, uint8_t* out, size_t cap) {
+  return nova_guard([&]() -> int {
+    if (!agg || !out) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (cap < vdf_nova_aggregate_serialized_size(agg)) return fail(VDF_ERR_BAD_LENGTH, "buffer too small");
+    const Side sd[2] = {host_side(agg->field, 0, agg->digest), host_side(agg->field, 1, agg->digest)};
+    uint8_t* o = out;
+    memcpy(o, WIRE_MAGIC_AGGREGATE, 8); o += 8;
+    memcpy(o, &agg->t, 8); o += 8;
+    const uint64_t count = agg->st.size();
+    memcpy(o, &count, 8); o += 8;
+    memcpy(o, agg->digest, 32); o += 32;
+    for (const vdf_aggregate::Statement& s : agg->st) {
+      o = put_inst(o, s.r_U1, sd[0], true);
+      o = put_inst(o, s.r_U2, sd[1], true);
+      o = put_inst(o, s.l_u2, sd[1], false);
+      pt_compress(s.T2, *sd[1].Fb, o); o += 32;
+      for (const Fe& v : s.zi1) o = wire_put_fe(o, v, *sd[0].F);
+      o = wire_put_fe(o, s.zi2, *sd[1].F);
+    }
+    for (int side = 0; side < 2; ++side)
+      for (const Aff& p : agg->TT[side]) { pt_compress(p, *sd[side].Fb, o); o += 32; }
+    for (int side = 0; side < 2; ++side) o = put_argument(o, agg->sp[side], *sd[side].F, *sd[side].Fb);
+    return VDF_OK;
+  });
+}
+
+int vdf_nova_aggregate_deserialize(vdf_pp* pp, const uint8_t* in, size_t len, vdf_aggregate** out) {
+  return nova_guard([&]() -> int {
+    if (!pp || !in || !out) return fail(VDF_ERR_BAD_ARG, "null argument");
+    *out = nullptr;
+    if (len < AGG_HEADER) return fail(VDF_ERR_BAD_LENGTH, "encoding is shorter than its header");
+    if (memcmp(in, WIRE_MAGIC_AGGREGATE, 8) != 0) return fail(VDF_ERR_BAD_ARG, "not this kind of encoding (magic)");
+    uint64_t t, count;
+    memcpy(&t, in + 8, 8);
+    memcpy(&count, in + 16, 8);
+    if (t != pp->t || memcmp(in + 24, pp->digest, 32) != 0) return fail(VDF_ERR_BAD_ARG, "encoding was made under other public parameters");
+    const Layout L[2] = {layout_of(pp->s[0]), layout_of(pp->s[1])};
+    if (count == 0 || count > VDF_NOVA_AGGREGATE_MAX || len != aggregate_wire_size((size_t)count, pp->arity, L))
+      return fail(VDF_ERR_BAD_LENGTH, "encoding has the wrong length for this count and shape");
+    std::unique_ptr<vdf_aggregate> a(new vdf_aggregate());
+    a->t = t;
+    a->field = pp->field;
+    a->arity = pp->arity;
+    memcpy(a->digest, pp->digest, 32);
+    a->st.resize((size_t)count);
+    bool canonical = true, on_curve = true;
+    const uint8_t* i = in + AGG_HEADER;
+    for (vdf_aggregate::Statement& s : a->st) {
+      i = get_inst(i, &s.r_U1, pp->s[0], true, &canonical, &on_curve);
+      i = get_inst(i, &s.r_U2, pp->s[1], true, &canonical, &on_curve);
+      i = get_inst(i, &s.l_u2, pp->s[1], false, &canonical, &on_curve);
+      on_curve &= pt_decompress(i, *pp->s[1].Fb, &s.T2); i += 32;
+      s.zi1.resize(pp->arity);
+      for (size_t k = 0; k < pp->arity; ++k, i += 32) canonical &= wire_get_fe(i, *pp->s[0].F, &s.zi1[k]);
+      canonical &= wire_get_fe(i, *pp->s[1].F, &s.zi2); i += 32;
+    }
+    for (int side = 0; side < 2; ++side) {
+      a->TT[side].resize((size_t)count - 1);
+      for (Aff& p : a->TT[side]) { on_curve &= pt_decompress(i, *pp->s[side].Fb, &p); i += 32; }
+    }
+    for (int side = 0; side < 2; ++side) i = get_argument(i, a->sp[side], L[side], *pp->s[side].F, *pp->s[side].Fb, &canonical, &on_curve);
+    if (!canonical) return fail(VDF_ERR_NONCANONICAL, "a field element of the encoding is not canonical");
+    if (!on_curve) return fail(VDF_ERR_NONCANONICAL, "a point of the encoding does not decode to a curve point");
+    *out = a.release();
+    return VDF_OK;
+  });
+}
+
+}  // extern "C"

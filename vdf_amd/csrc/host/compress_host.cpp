@@ -13,71 +13,11 @@ using namespace vdfnova;
 // =============================================================================================================
 namespace {
 
-struct Transcript {
-  uint8_t state[32];
-  explicit Transcript(const char* label) {
-    Shake256 h;
-    h.absorb("vdf-spartan-v3|", 15);
-    h.absorb(label, strlen(label));
-    h.squeeze(state, 32);
-  }
-  void absorb(const char* label, const void* data, size_t n) {
-    Shake256 h;
-    h.absorb(state, 32);
-    h.absorb(label, strlen(label));
-    h.absorb(":", 1);
-    h.absorb(data, n);
-    h.squeeze(state, 32);
-  }
-  void absorb_fe(const char* label, const Fe* v, size_t k, const Field& F) {
-    std::vector<uint8_t> b(k * 32);
-    for (size_t i = 0; i < k; ++i) { const Fe c = from_mont(v[i], F); memcpy(&b[i * 32], c.l, 32); }
-    absorb(label, b.data(), b.size());
-  }
-  void absorb_pt(const char* label, const Aff* p, size_t k, const Field& F) {      // F: the points' coordinate field
-    std::vector<uint8_t> b(k * 64, 0);
-    for (size_t i = 0; i < k; ++i)
-      if (!p[i].is_id()) {
-        const Fe x = from_mont(p[i].x, F), y = from_mont(p[i].y, F);
-        memcpy(&b[i * 64], x.l, 32); memcpy(&b[i * 64 + 32], y.l, 32);
-      }
-    absorb(label, b.data(), b.size());
-  }
-  // 128-bit challenge: raw = the integer, return = its Montgomery form in F
-  Fe challenge(const char* label, const Field& F, uint64_t raw[4]) {
-    Shake256 h;
-    h.absorb(state, 32);
-    h.absorb(label, strlen(label));
-    h.absorb("?", 1);
-    uint8_t out[48];
-    h.squeeze(out, 48);
-    memcpy(state, out + 16, 32);
-    raw[0] = raw[1] = raw[2] = raw[3] = 0;
-    memcpy(raw, out, 16);
-    Fe r;
-    memcpy(r.l, raw, 32);
-    return to_mont(r, F);
-  }
-};
-
-// The halving of an inner-product argument stops at IPA_STOP elements: the prover sends that vector instead of four more
-// rounds (each a pair of MSMs over all generators for the prover; the verifier's one MSM is the same either way).
-constexpr size_t IPA_STOP = 16;
-inline size_t ipa_final(size_t n) { return n < IPA_STOP ? n : IPA_STOP; }
-inline size_t ipa_rounds(size_t n) { size_t k = 0; for (size_t m = n; m > IPA_STOP; m >>= 1) ++k; return k; }
-struct Ipa { std::vector<Aff> L, R; std::vector<Fe> a; };
-struct Spartan {
-  std::vector<std::array<Fe, 3>> outer;
-  Fe claims[4];
-  std::vector<std::array<Fe, 2>> inner;
-  Fe w_eval;
-  Ipa ipaW, ipaE;
-};
-
 size_t pow2_at_least(size_t n) { size_t p = 1; while (p < n) p <<= 1; return p; }
 int log2_exact(size_t n) { int k = 0; while (((size_t)1 << k) < n) ++k; return k; }
 
-struct Layout { size_t M, NW, Z; int s, l1; };
+}  // namespace
+namespace vdfnova {
 Layout layout_of(const Side& pp_) {
   const Side* pp = &pp_;
   Layout l;
@@ -85,36 +25,8 @@ Layout layout_of(const Side& pp_) {
   l.s = log2_exact(l.M); l.l1 = log2_exact(l.Z);
   return l;
 }
-
-// device buffers released on scope exit
-struct DevBufs {
-  vdf_ctx* ctx;
-  Arena* arena;                    // the side's block (kept by the parameter set), or none: every vector its own allocation
-  size_t reserved = 0, used = 0;
-  std::vector<void*> v;
-  explicit DevBufs(vdf_ctx* c, Arena* a = nullptr) : ctx(c), arena(a) {}
-  ~DevBufs() { for (void* p : v) vdf_dev_free(ctx, p); }
-  // all vectors of a call at once: one allocation the first time (or when a larger call comes), one memset every time
-  int reserve(size_t elems) {
-    if (!arena) return VDF_OK;
-    const size_t bytes = elems * 32;
-    if (arena->cap < bytes) {
-      if (arena->p) { vdf_ctx_sync(ctx); vdf_dev_free(ctx, arena->p); arena->p = nullptr; arena->cap = 0; }
-      int rc = vdf_dev_alloc(ctx, bytes, &arena->p);
-      if (rc != VDF_OK) return rc;
-      arena->cap = bytes;
-    }
-    reserved = bytes; used = 0;
-    return vdf_dev_memset(ctx, arena->p, 0, bytes);
-  }
-  int zeros(size_t elems, void** out) {
-    if (arena && used + elems * 32 <= reserved) { *out = static_cast<char*>(arena->p) + used; used += elems * 32; return VDF_OK; }
-    int rc = vdf_dev_alloc(ctx, elems * 32, out);
-    if (rc != VDF_OK) return rc;
-    v.push_back(*out);
-    return vdf_dev_memset(ctx, *out, 0, elems * 32);
-  }
-};
+}  // namespace vdfnova
+namespace {
 
 Fe small(uint64_t k, const Field& F) { return from_u64(k, F); }
 // value at r of the polynomial through (0, y0), (1, y1), (2, y2)[, (3, y3)]
@@ -132,6 +44,8 @@ Fe interpolate(const Fe* y, int npts, const Fe& r, const Field& F) {
   return acc;
 }
 
+}  // namespace
+namespace vdfnova {
 void instance_bytes(Transcript& tr, const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, const Fe* X) {
   const Field& F = *sd.F;
   tr.absorb("shape", sd.digest, 32);
@@ -142,6 +56,8 @@ void instance_bytes(Transcript& tr, const Side& sd, const Aff& cW, const Aff& cE
   for (int j = 0; j < NUM_IO; ++j) v[1 + j] = X[j];
   tr.absorb_fe("inst", v, 1 + NUM_IO, F);
 }
+}  // namespace vdfnova
+namespace {
 
 // lo = 1 - r, hi = r table of eq(r, .) on the device
 int eq_table_dev(const Side& sd, const std::vector<Fe>& r, void* out) {
@@ -358,23 +274,6 @@ struct IpaCheck {
   Fe bfin;
 };
 
-// What is left of an opening's check once the transcript is replayed: with Q' = c gen_u (c the 128-bit challenge) and ab the
-// sent vector against b's fold,
-//   P + c (v - ab) gen_u + sum_j (x_j^2 L_j + x_j^-2 R_j) == MSM(G, coefficients)
-// where the coefficients are vdf_ipa_coefficients' table of the rounds (lo = x^-1, hi = x) over the sent vector a.  Linear in
-// the group: checks of many openings combine with random weights into one equation (vdf_nova_verify_compressed_batch).
-struct IpaDeferred {
-  size_t n = 0;
-  int k = 0, log_m = 0;
-  std::vector<Fe> xs, xis;         // the round challenges and their inverses
-  std::vector<Aff> lr_pts;         // L_0, R_0, L_1, R_1, ...
-  std::vector<Fe> lr_sc;           // x_0^2, x_0^-2, ...
-  std::vector<Fe> a;               // the sent vector (2^log_m elements)
-  Aff P;
-  Fe v, ab;
-  uint64_t q_raw[4];
-};
-
 // The transcript order of ipa_prove_units, up to the last check of each opening (sizes, challenges, b's fold, ab).  *ok =
 // false for a proof that fails a size check or draws a zero challenge.
 int ipa_replay(const Side& sd, Transcript& tr, IpaCheck* jobs, int njobs, IpaDeferred* out, bool* ok) {
@@ -446,6 +345,8 @@ int ipa_replay(const Side& sd, Transcript& tr, IpaCheck* jobs, int njobs, IpaDef
   return VDF_OK;
 }
 
+}  // namespace
+namespace vdfnova {
 // One opening's check on its own: two device MSMs, sum_j x_j^2 L_j + x_j^-2 R_j (2k multiplications by full-size scalars: on
 // the host they were the whole cost of verification, 0.25 ms each) and the folded generators against the sent vector.
 // d_s: n device elements of scratch.
@@ -480,6 +381,8 @@ int ipa_check_one(const Side& sd, const IpaDeferred& d, void* d_s, bool* ok) {
   *ok = memcmp(&a1, &a2, sizeof(Aff)) == 0;
   return VDF_OK;
 }
+}  // namespace vdfnova
+namespace {
 
 // tables of this many entries and fewer finish their sum-check on the host (a power of two; at least 2)
 constexpr size_t SUMCHECK_HOST_TAIL = 512;
@@ -500,9 +403,6 @@ int fold_k(const Side& sd, int k, vdf_fe* const* vecs, const Fe* c_lo, const Fe*
   else HIPCALL(ctx, vdf_fold_halves_batch(ctx, sd.field, k, vecs, (const vdf_fe*)c_lo, (const vdf_fe*)c_hi, n));
   return VDF_OK;
 }
-
-// the statement and witness of one side's argument
-struct ProveIn { Aff cW, cE; Fe u; const Fe* X; const void* d_z; const void* d_E; Spartan* out; };
 
 // the scratch vectors of one proof's argument, in elements
 size_t spartan_scratch_elems(const Side& sd) {
@@ -830,6 +730,8 @@ int spartan_m_single(const Side& sd, const MDeferred& md, bool* ok) {
   return VDF_OK;
 }
 
+}  // namespace
+namespace vdfnova {
 // The single verifier's replay of one side: the host part, then M(r_x, r_y) on the device.
 int spartan_replay(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, const Fe* X, const Spartan& pf, IpaDeferred out[2],
                    bool* ok) {
@@ -837,6 +739,8 @@ int spartan_replay(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, co
   { int rc = spartan_replay_host(sd, cW, cE, u, X, pf, out, &md, ok); if (rc != VDF_OK || !*ok) return rc; }
   return spartan_m_single(sd, md, ok);
 }
+}  // namespace vdfnova
+namespace {
 
 // The deferred comparisons of n proofs of one side (vdf_nova_verify_compressed_batch): the n pairs of eq tables (asynchronous,
 // no wait between them), then every M(r_x, r_y) of a group by ONE pass over the shape's rows (vdf_sparse_eval_multi, with the
@@ -890,18 +794,7 @@ int spartan_m_check(const Side& sd, const MDeferred* const items[], size_t n, si
 
 }  // namespace
 
-struct vdf_snark {          // NovaVDFProof::Compressed, src/nova/proof.rs:54 = nova-snark CompressedSNARK
-  Inst r_U1, r_U2, l_u2;    // running primary, running secondary BEFORE the last fold, the last secondary instance
-  Aff T2;                   // cross-term commitment of that last fold
-  Spartan sp[2];            // sp[0]: r_U1 is satisfiable; sp[1]: fold(r_U2, l_u2) is
-  std::vector<Fe> zi1;      // z_i of the primary side (arity of its step circuit)
-  Fe zi2[1];
-  uint64_t t = 0;           // the public parameters it was made under (wire header)
-  uint8_t digest[32];
-  int field = VDF_FIELD_FQ; // ... and their orientation: the primary side's scalar field (what the encodings below reduce by)
-};
-
-namespace {
+namespace vdfnova {
 
 // instance fold on the host: U + r u with the cross-term commitment T (two 128-bit scalar multiplications)
 Inst fold_instance(const Side& sd, const Inst& U, const Inst& u, const Aff& T, const uint64_t r[4]) {
@@ -938,14 +831,12 @@ void spartan_resize(Spartan& p, const Layout& L) {
 // the statement part of a compressed proof on the wire: instances with 32-byte points, then both z_i
 // without the primary z_i (32 bytes per element of the step circuit's arity)
 constexpr size_t STATEMENT_WIRE_FIXED = 5 * 32 * 2 + 3 * 32 + 32 + 32;
-inline size_t statement_wire(size_t arity) { return STATEMENT_WIRE_FIXED + 32 * arity; }
+size_t statement_wire(size_t arity) { return STATEMENT_WIRE_FIXED + 32 * arity; }
 
 // vdf_nova_compress_batch: proofs per lockstep group, and the HBM left free beside the groups' scratch
 constexpr size_t COMPRESS_LOCKSTEP = 8;
 constexpr size_t COMPRESS_HBM_RESERVE = (size_t)2 << 30;
-}  // namespace
 
-namespace {
 // The statement of a compressed proof, and the last secondary instance folded into the running one (NIFS, as a prove_step
 // would) into scratch d_fz / d_fE: the proof keeps its instances; its secondary cross-term buffers (d_abc2, d_T) are
 // overwritten.  *f2: the folded instance.
@@ -1025,7 +916,7 @@ struct OwnedArena : Arena {
   explicit OwnedArena(vdf_ctx* c) : ctx(c) {}
   ~OwnedArena() { if (p) vdf_dev_free(ctx, p); }
 };
-}  // namespace
+}  // namespace vdfnova
 
 extern "C" {
 

@@ -1,5 +1,5 @@
 // Shared declarations of the translation units of libvdf_nova.so (minroot_host.cpp, r1cs.cpp, nova_host.cpp, trace_walks.cpp, circuits_host.cpp,
-// custom_chain_host.cpp, compress_host.cpp, wire_host.cpp): error plumbing, the two sides of the curve cycle, the handle structs.
+// custom_chain_host.cpp, compress_host.cpp, aggregate_host.cpp, wire_host.cpp): error plumbing, the two sides of the curve cycle, the handle structs.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -363,4 +363,154 @@ inline const uint8_t* get_inst(const uint8_t* i, Inst* in, const Side& sd, bool 
                          [&](const uint8_t* enc, const Side& s, Aff* dst) { *on_curve &= pt_decompress(enc, *s.Fb, dst); });
 }
 constexpr size_t INST_WIRE_RELAXED = 32 * 5, INST_WIRE_STRICT = 32 * 3;
+}  // namespace vdfnova
+
+// ---- the compression argument as compress_host.cpp lends it to aggregate_host.cpp -------------------------------------------
+namespace vdfnova {
+// Protocol "vdf-spartan-v3", restated line by line by the test oracle (spartan.py: prove / verify): the transcript, the proof
+// objects and the device scratch of compress_host.cpp.
+struct Transcript {
+  uint8_t state[32];
+  explicit Transcript(const char* label) {
+    Shake256 h;
+    h.absorb("vdf-spartan-v3|", 15);
+    h.absorb(label, strlen(label));
+    h.squeeze(state, 32);
+  }
+  void absorb(const char* label, const void* data, size_t n) {
+    Shake256 h;
+    h.absorb(state, 32);
+    h.absorb(label, strlen(label));
+    h.absorb(":", 1);
+    h.absorb(data, n);
+    h.squeeze(state, 32);
+  }
+  void absorb_fe(const char* label, const Fe* v, size_t k, const Field& F) {
+    std::vector<uint8_t> b(k * 32);
+    for (size_t i = 0; i < k; ++i) { const Fe c = from_mont(v[i], F); memcpy(&b[i * 32], c.l, 32); }
+    absorb(label, b.data(), b.size());
+  }
+  void absorb_pt(const char* label, const Aff* p, size_t k, const Field& F) {      // F: the points' coordinate field
+    std::vector<uint8_t> b(k * 64, 0);
+    for (size_t i = 0; i < k; ++i)
+      if (!p[i].is_id()) {
+        const Fe x = from_mont(p[i].x, F), y = from_mont(p[i].y, F);
+        memcpy(&b[i * 64], x.l, 32); memcpy(&b[i * 64 + 32], y.l, 32);
+      }
+    absorb(label, b.data(), b.size());
+  }
+  // 128-bit challenge: raw = the integer, return = its Montgomery form in F
+  Fe challenge(const char* label, const Field& F, uint64_t raw[4]) {
+    Shake256 h;
+    h.absorb(state, 32);
+    h.absorb(label, strlen(label));
+    h.absorb("?", 1);
+    uint8_t out[48];
+    h.squeeze(out, 48);
+    memcpy(state, out + 16, 32);
+    raw[0] = raw[1] = raw[2] = raw[3] = 0;
+    memcpy(raw, out, 16);
+    Fe r;
+    memcpy(r.l, raw, 32);
+    return to_mont(r, F);
+  }
+};
+
+// The halving of an inner-product argument stops at IPA_STOP elements: the prover sends that vector instead of four more
+// rounds (each a pair of MSMs over all generators for the prover; the verifier's one MSM is the same either way).
+constexpr size_t IPA_STOP = 16;
+inline size_t ipa_final(size_t n) { return n < IPA_STOP ? n : IPA_STOP; }
+inline size_t ipa_rounds(size_t n) { size_t k = 0; for (size_t m = n; m > IPA_STOP; m >>= 1) ++k; return k; }
+struct Ipa { std::vector<Aff> L, R; std::vector<Fe> a; };
+struct Spartan {
+  std::vector<std::array<Fe, 3>> outer;
+  Fe claims[4];
+  std::vector<std::array<Fe, 2>> inner;
+  Fe w_eval;
+  Ipa ipaW, ipaE;
+};
+
+struct Layout { size_t M, NW, Z; int s, l1; };
+Layout layout_of(const Side& sd);
+
+// device buffers released on scope exit
+struct DevBufs {
+  vdf_ctx* ctx;
+  Arena* arena;                    // the side's block (kept by the parameter set), or none: every vector its own allocation
+  size_t reserved = 0, used = 0;
+  std::vector<void*> v;
+  explicit DevBufs(vdf_ctx* c, Arena* a = nullptr) : ctx(c), arena(a) {}
+  ~DevBufs() { for (void* p : v) vdf_dev_free(ctx, p); }
+  // all vectors of a call at once: one allocation the first time (or when a larger call comes), one memset every time
+  int reserve(size_t elems) {
+    if (!arena) return VDF_OK;
+    const size_t bytes = elems * 32;
+    if (arena->cap < bytes) {
+      if (arena->p) { vdf_ctx_sync(ctx); vdf_dev_free(ctx, arena->p); arena->p = nullptr; arena->cap = 0; }
+      int rc = vdf_dev_alloc(ctx, bytes, &arena->p);
+      if (rc != VDF_OK) return rc;
+      arena->cap = bytes;
+    }
+    reserved = bytes; used = 0;
+    return vdf_dev_memset(ctx, arena->p, 0, bytes);
+  }
+  int zeros(size_t elems, void** out) {
+    if (arena && used + elems * 32 <= reserved) { *out = static_cast<char*>(arena->p) + used; used += elems * 32; return VDF_OK; }
+    int rc = vdf_dev_alloc(ctx, elems * 32, out);
+    if (rc != VDF_OK) return rc;
+    v.push_back(*out);
+    return vdf_dev_memset(ctx, *out, 0, elems * 32);
+  }
+};
+
+// What is left of an opening's check once the transcript is replayed: with Q' = c gen_u (c the 128-bit challenge) and ab the
+// sent vector against b's fold,
+//   P + c (v - ab) gen_u + sum_j (x_j^2 L_j + x_j^-2 R_j) == MSM(G, coefficients)
+// where the coefficients are vdf_ipa_coefficients' table of the rounds (lo = x^-1, hi = x) over the sent vector a.  Linear in
+// the group: checks of many openings combine with random weights into one equation (vdf_nova_verify_compressed_batch).
+struct IpaDeferred {
+  size_t n = 0;
+  int k = 0, log_m = 0;
+  std::vector<Fe> xs, xis;         // the round challenges and their inverses
+  std::vector<Aff> lr_pts;         // L_0, R_0, L_1, R_1, ...
+  std::vector<Fe> lr_sc;           // x_0^2, x_0^-2, ...
+  std::vector<Fe> a;               // the sent vector (2^log_m elements)
+  Aff P;
+  Fe v, ab;
+  uint64_t q_raw[4];
+};
+
+// the statement and witness of one side's argument
+struct ProveIn { Aff cW, cE; Fe u; const Fe* X; const void* d_z; const void* d_E; Spartan* out; };
+
+void instance_bytes(Transcript& tr, const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, const Fe* X);
+// one opening's deferred check on its own (d_s: n device elements of scratch)
+int ipa_check_one(const Side& sd, const IpaDeferred& d, void* d_s, bool* ok);
+// the single verifier's replay of one side's argument: the host part, then M(r_x, r_y) on the device
+int spartan_replay(const Side& sd, const Aff& cW, const Aff& cE, const Fe& u, const Fe* X, const Spartan& pf, IpaDeferred out[2], bool* ok);
+// instance fold on the host: U + r u with the cross-term commitment T; the NIFS challenge the circuits recompute
+Inst fold_instance(const Side& sd, const Inst& U, const Inst& u, const Aff& T, const uint64_t r[4]);
+void fold_challenge(const vdf_pp* pp, const Inst& U2, const Inst& l2, const Aff& T2, uint64_t r[4]);
+size_t spartan_wire_size(const Layout& L);
+void spartan_resize(Spartan& p, const Layout& L);
+size_t statement_wire(size_t arity);      // the statement part of "VDFSNK03" (and of every entry of "VDFAGG01")
+}  // namespace vdfnova
+
+struct vdf_snark {          // NovaVDFProof::Compressed, src/nova/proof.rs:54 = nova-snark CompressedSNARK
+  vdfnova::Inst r_U1, r_U2, l_u2;    // running primary, running secondary BEFORE the last fold, the last secondary instance
+  Aff T2;                   // cross-term commitment of that last fold
+  vdfnova::Spartan sp[2];   // sp[0]: r_U1 is satisfiable; sp[1]: fold(r_U2, l_u2) is
+  std::vector<Fe> zi1;      // z_i of the primary side (arity of its step circuit)
+  Fe zi2[1];
+  uint64_t t = 0;           // the public parameters it was made under (wire header)
+  uint8_t digest[32];
+  int field = VDF_FIELD_FQ; // ... and their orientation: the primary side's scalar field (what the encodings below reduce by)
+};
+
+namespace vdfnova {
+// the statement of a compressed proof, and the last secondary instance folded into the running one (scratch d_fz / d_fE; *f2: the folded instance)
+int compress_prelude(const vdf_proof* p, vdf_pp* pp, vdf_snark* s, void* d_fz, void* d_fE, Inst* f2);
+// both sides' arguments of K statements (the caller holds pp->aux_mu)
+int prove_both_sides(vdf_pp* pp, size_t K, const ProveIn* in1, const ProveIn* in2, Arena* arena1, Arena* arena2);
+constexpr char WIRE_MAGIC_AGGREGATE[9] = "VDFAGG01";  // aggregate of compressed proofs (aggregate_host.cpp)
 }  // namespace vdfnova

@@ -314,6 +314,11 @@ Status points_decompress(int curve, const uint8_t* d_enc, size_t n, void* d_out,
 Status vec_axpy(int field, const void* a, const void* r, const void* b, size_t n, void* out, hipStream_t s);
 Status vec_cross_term(int field, const void* az1, const void* bz1, const void* cz1, const void* az2,
                       const void* bz2, const void* cz2, const void* u1, size_t n, void* T, hipStream_t s);
+// two relaxed instances: u1, u2 and r are HOST elements whose values travel as kernel arguments; the fold is in place on the index-1 vectors
+Status vec_cross_term_relaxed(int field, const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, const void* az2,
+                              const void* bz2, const void* cz2, const vdf_fe* u2, size_t n, void* T, hipStream_t s);
+Status vec_fold_relaxed(int field, const vdf_fe* r, size_t n, void* az1, void* bz1, void* cz1, void* e1, const void* az2,
+                        const void* bz2, const void* cz2, const void* e2, const void* T, hipStream_t s);
 Status vec_minroot_witness(int field, const void* trace_xy, const void* i0, uint64_t t, void* W, hipStream_t s);
 Status vec_spmv_long(int field, const uint32_t* const rowptr[3], const uint32_t* const col[3], const uint32_t* const coef[3],
                      const void* dict, const void* z, const uint32_t* long_rows, size_t n_long, void* const out[3], hipStream_t s);

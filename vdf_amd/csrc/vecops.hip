@@ -1344,4 +1344,70 @@ Status vec_clock_probe(int iters, int workgroups, unsigned long long* d_out3, hi
   return Status{};
 }
 
+// ---- folding two RELAXED instances (vdf_nova_compress_aggregate) ----------------------------------------------------------------
+// The cross term when neither instance is fresh: T = Az1 o Bz2 + Az2 o Bz1 - u1 Cz2 - u2 Cz1 (k_cross_term is the case u2 = 1, and
+// gives the same bytes there: every value is canonical).  One row per lane over contiguous 32-byte elements; u1 and u2 travel as
+// kernel arguments.
+template <class P>
+__global__ __launch_bounds__(256) void k_cross_term_relaxed(const char* __restrict__ az1, const char* __restrict__ bz1,
+                                                            const char* __restrict__ cz1, FeVal u1, const char* __restrict__ az2,
+                                                            const char* __restrict__ bz2, const char* __restrict__ cz2, FeVal u2,
+                                                            size_t n, char* __restrict__ T) {
+  __builtin_amdgcn_s_setprio(3);     // light kernel: do not starve behind a co-running k_accumulate
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const Fe<P> a1 = fe_load<P>(az1 + i * 32), b1 = fe_load<P>(bz1 + i * 32), c1 = fe_load<P>(cz1 + i * 32);
+  const Fe<P> a2 = fe_load<P>(az2 + i * 32), b2 = fe_load<P>(bz2 + i * 32), c2 = fe_load<P>(cz2 + i * 32);
+  Fe<P> t = fe_add(fe_mul(a1, b2), fe_mul(a2, b1));
+  t = fe_sub(t, fe_mul(fe_from_val<P>(u1), c2));
+  t = fe_sub(t, fe_mul(fe_from_val<P>(u2), c1));
+  fe_store<P>(T + i * 32, t);
+}
+
+// The fold that goes with it, in place on the index-1 vectors and in one pass over the rows:
+//   Az1 += r Az2, Bz1 += r Bz2, Cz1 += r Cz2 (A z, B z, C z are linear in z: the accumulator's products stay current),
+//   E1 += r T + r^2 E2.
+// r and r^2 are Montgomery forms made on the host.  Nine vectors read and four written per row.
+template <class P>
+__global__ __launch_bounds__(256) void k_fold_relaxed(FeVal rv, FeVal r2v, size_t n, char* __restrict__ az1, char* __restrict__ bz1,
+                                                      char* __restrict__ cz1, char* __restrict__ e1, const char* __restrict__ az2,
+                                                      const char* __restrict__ bz2, const char* __restrict__ cz2,
+                                                      const char* __restrict__ e2, const char* __restrict__ T) {
+  __builtin_amdgcn_s_setprio(3);
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const Fe<P> r = fe_from_val<P>(rv), r2 = fe_from_val<P>(r2v);
+  fe_store<P>(az1 + i * 32, fe_add(fe_load<P>(az1 + i * 32), fe_mul(r, fe_load<P>(az2 + i * 32))));
+  fe_store<P>(bz1 + i * 32, fe_add(fe_load<P>(bz1 + i * 32), fe_mul(r, fe_load<P>(bz2 + i * 32))));
+  fe_store<P>(cz1 + i * 32, fe_add(fe_load<P>(cz1 + i * 32), fe_mul(r, fe_load<P>(cz2 + i * 32))));
+  const Fe<P> e = fe_add(fe_load<P>(e1 + i * 32), fe_mul(r, fe_load<P>(T + i * 32)));
+  fe_store<P>(e1 + i * 32, fe_add(e, fe_mul(r2, fe_load<P>(e2 + i * 32))));
+}
+
+Status vec_cross_term_relaxed(int field, const void* az1, const void* bz1, const void* cz1, const vdf_fe* u1, const void* az2,
+                              const void* bz2, const void* cz2, const vdf_fe* u2, size_t n, void* T, hipStream_t s) {
+  if (n == 0) return Status{};
+  if (n >= ((size_t)1 << 39)) return Status{VDF_ERR_BAD_LENGTH, "cross term too large"};
+  KTimer kt(s, "k_cross_term_relaxed", 224.0 * n);
+  return with_field(field, [&](auto f) {
+    hipLaunchKernelGGL((k_cross_term_relaxed<tag_t<decltype(f)>>), grid_for(n), dim3(256), 0, s, cbytes_of(az1), cbytes_of(bz1),
+                       cbytes_of(cz1), to_val(u1), cbytes_of(az2), cbytes_of(bz2), cbytes_of(cz2), to_val(u2), n, bytes_of(T));
+  });
+}
+
+Status vec_fold_relaxed(int field, const vdf_fe* r, size_t n, void* az1, void* bz1, void* cz1, void* e1, const void* az2,
+                        const void* bz2, const void* cz2, const void* e2, const void* T, hipStream_t s) {
+  if (n == 0) return Status{};
+  if (n >= ((size_t)1 << 39)) return Status{VDF_ERR_BAD_LENGTH, "fold too large"};
+  KTimer kt(s, "k_fold_relaxed", 13 * 32.0 * n);
+  return with_field(field, [&](auto f) {
+    using P = tag_t<decltype(f)>;
+    Fe<P> rm; std::memcpy(rm.v, r, 32);
+    const Fe<P> rr = fe_mul(rm, rm);                  // r^2, once, on the host
+    FeVal r2v; std::memcpy(r2v.v, rr.v, 32);
+    hipLaunchKernelGGL((k_fold_relaxed<P>), grid_for(n), dim3(256), 0, s, to_val(r), r2v, n, bytes_of(az1), bytes_of(bz1), bytes_of(cz1),
+                       bytes_of(e1), cbytes_of(az2), cbytes_of(bz2), cbytes_of(cz2), cbytes_of(e2), cbytes_of(T));
+  });
+}
+
 }  // namespace vdf

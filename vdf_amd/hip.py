@@ -494,6 +494,17 @@ class Context:
     def axpy(self, field, a, r, b, n, out) -> None:
         self._check(lib.vdf_axpy(self.handle, field, _ptr(a), _ptr(r), _ptr(b), n, _ptr(out)))
 
+    # ---- folding two relaxed instances: u1, u2, r are HOST arrays, every vector is device memory ----
+    def cross_term_relaxed(self, field, az1, bz1, cz1, u1, az2, bz2, cz2, u2, n, out) -> None:
+        """T = Az1 o Bz2 + Az2 o Bz1 - u1 Cz2 - u2 Cz1 (vdf_hip.h vdf_cross_term_relaxed)."""
+        self._check(lib.vdf_cross_term_relaxed(self.handle, field, _ptr(az1), _ptr(bz1), _ptr(cz1), _ptr(u1), _ptr(az2), _ptr(bz2),
+                                               _ptr(cz2), _ptr(u2), n, _ptr(out)))
+
+    def fold_relaxed(self, field, r, n, az1, bz1, cz1, e1, az2, bz2, cz2, e2, T) -> None:
+        """In place: Az1 += r Az2, Bz1 += r Bz2, Cz1 += r Cz2, E1 += r T + r^2 E2 (vdf_hip.h vdf_fold_relaxed)."""
+        self._check(lib.vdf_fold_relaxed(self.handle, field, _ptr(r), n, _ptr(az1), _ptr(bz1), _ptr(cz1), _ptr(e1), _ptr(az2), _ptr(bz2),
+                                         _ptr(cz2), _ptr(e2), _ptr(T)))
+
     def minroot_witness(self, field, trace_xy, i0, t, out) -> None:
         self._check(lib.vdf_minroot_witness(self.handle, field, _ptr(trace_xy), _ptr(i0), t, _ptr(out)))
 

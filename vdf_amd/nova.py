@@ -129,6 +129,14 @@ for _name, _res, _args in [
     ("vdf_nova_snark_deserialize_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_i)]),
     ("vdf_nova_verify_wire_batch", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz), _vp, _vp, C.POINTER(_i), C.POINTER(_i),
                                         C.POINTER(_i)]),
+    ("vdf_nova_compress_aggregate", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_vp)]),
+    ("vdf_nova_verify_aggregate", _i, [_vp, _vp, _sz, C.POINTER(_sz), _vp, _vp, C.POINTER(_i), C.POINTER(C.c_int64)]),
+    ("vdf_nova_aggregate_free", None, [_vp]),
+    ("vdf_nova_aggregate_count", _sz, [_vp]),
+    ("vdf_nova_aggregate_serialized_size", _sz, [_vp]),
+    ("vdf_nova_aggregate_serialize", _i, [_vp, _vp, _sz]),
+    ("vdf_nova_aggregate_deserialize", _i, [_vp, _vp, _sz, C.POINTER(_vp)]),
+    ("vdf_nova_aggregate_fold_instances", _i, [_i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("vdf_nova_proof_serialized_size", _sz, [_vp]),
     ("vdf_nova_proof_serialize", _i, [_vp, _vp, _sz]),
     ("vdf_nova_proof_deserialize", _i, [_vp, _vp, _sz, C.POINTER(_vp)]),
@@ -1924,3 +1932,87 @@ def verify_batch(pp: NovaVDFPublicParams, items: Sequence[tuple]) -> list:
     all_ok = C.c_int(0)
     _check(nova_lib.vdf_nova_verify_batch(pp.handle, n, proofs, steps, z0, zi, ok, C.byref(all_ok)))
     return [bool(ok[q]) for q in range(n)]
+
+
+AGGREGATE_MAX = 1024              # VDF_NOVA_AGGREGATE_MAX
+WIRE_INSTANCE_BYTES = 160         # sizeof(vdf_wire_instance): comm_W | comm_E | u | X[2]
+
+
+class AggregateProof:
+    """Many running proofs under one parameter set as ONE compressed proof ("vdf-aggregate-v1", include/vdf_nova.h)."""
+
+    def __init__(self, handle: int, pp: NovaVDFPublicParams):
+        self.handle, self.pp = handle, pp
+        pp.ctx._children.add(self)
+        pp._proofs.add(self)
+
+    @property
+    def count(self) -> int:
+        return int(nova_lib.vdf_nova_aggregate_count(self.handle))
+
+    def verify(self, pp: NovaVDFPublicParams, num_steps: Sequence[int], z0: Sequence[Sequence[bytes]], zi: Sequence[Sequence[bytes]]):
+        """(ok, bad_entry): one verdict for the whole aggregate; bad_entry = the first entry whose exact checks fail, else -1.
+        num_steps, z0, zi: one per entry (z0[k], zi[k]: `arity` elements)."""
+        n = len(num_steps)
+        arity = getattr(pp, "arity", 3)
+        if len(z0) != n or len(zi) != n or any(len(v) != arity for v in list(z0) + list(zi)):
+            raise ValueError(f"z0 and zi need {arity} elements for each of the {n} entries")
+        steps = (_sz * max(n, 1))(*[int(v) for v in num_steps])
+        z0a = _zn([v for e in z0 for v in e] or [bytes(32)])
+        zia = _zn([v for e in zi for v in e] or [bytes(32)])
+        ok, bad = C.c_int(0), C.c_int64(-1)
+        _check(nova_lib.vdf_nova_verify_aggregate(self.handle, pp.handle, n, steps, z0a, zia, C.byref(ok), C.byref(bad)))
+        return bool(ok.value), int(bad.value)
+
+    def serialize(self) -> bytes:
+        """ "VDFAGG01" (include/vdf_nova.h)."""
+        n = nova_lib.vdf_nova_aggregate_serialized_size(self.handle)
+        buf = (C.c_uint8 * n)()
+        _check(nova_lib.vdf_nova_aggregate_serialize(self.handle, buf, n))
+        return bytes(buf)
+
+    def free(self) -> None:
+        if self.handle and self.pp.handle and self.pp.ctx.handle:
+            nova_lib.vdf_nova_aggregate_free(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def compress_aggregate(pp: NovaVDFPublicParams, proofs: Sequence["NovaVDFProof"]) -> AggregateProof:
+    """Folds the running instances of many proofs into one and proves one argument per side (vdf_nova_compress_aggregate).  The
+    proofs are left as compress leaves them; a proof named twice is folded twice."""
+    n = len(proofs)
+    hs = (_vp * max(n, 1))(*[None if p is None else p.handle for p in proofs])
+    out = C.c_void_p()
+    _check(nova_lib.vdf_nova_compress_aggregate(pp.handle, n, hs, C.byref(out)))
+    return AggregateProof(out.value, pp)
+
+
+def deserialize_aggregate(pp: NovaVDFPublicParams, data: bytes) -> AggregateProof:
+    buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(bytes(data) or b"\0")
+    h = C.c_void_p()
+    _check(nova_lib.vdf_nova_aggregate_deserialize(pp.handle, buf, len(data), C.byref(h)))
+    return AggregateProof(h.value, pp)
+
+
+def aggregate_fold_instances(field_of_primary: int, side: int, digest: bytes, instances: Sequence[bytes], comm_TT: Sequence[bytes]):
+    """The verifier's transcript and folds of one side over plain bytes, on the host alone (vdf_nova_aggregate_fold_instances).
+    instances: 160-byte wire instances (comm_W | comm_E | u | X0 | X1); comm_TT: len(instances) - 1 32-byte points.  Returns
+    (the folded instance's 160 bytes, the challenges as 32-byte Montgomery elements of the side's field)."""
+    n = len(instances)
+    if any(len(b) != WIRE_INSTANCE_BYTES for b in instances) or any(len(b) != 32 for b in comm_TT) or len(digest) != 32:
+        raise ValueError("instances are 160 bytes, points and the digest 32")
+    if n and len(comm_TT) != n - 1:
+        raise ValueError("one cross-term commitment per fold")
+    inst = (C.c_uint8 * max(160 * n, 1)).from_buffer_copy(b"".join(instances) or b"\0")
+    tt = (C.c_uint8 * max(32 * len(comm_TT), 1)).from_buffer_copy(b"".join(comm_TT) or b"\0")
+    dg = (C.c_uint8 * 32).from_buffer_copy(digest)
+    acc = (C.c_uint8 * 160)()
+    r = (C.c_uint8 * max(32 * (n - 1), 1))()
+    _check(nova_lib.vdf_nova_aggregate_fold_instances(field_of_primary, side, dg, n, inst, tt, acc, r))
+    return bytes(acc), [bytes(r[32 * k:32 * k + 32]) for k in range(max(n - 1, 0))]
