@@ -874,6 +874,19 @@ int  vdf_fe_sqrt(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, vdf_fe* out
  * host or device memory (vdf_ptr_is_device).  The bytes are a peer's: no loop of the kernel depends on them.  n = 0 is VDF_OK
  * and touches nothing. */
 int  vdf_points_decompress(vdf_ctx* ctx, int curve, const uint8_t* enc, size_t n, vdf_affine* out, uint8_t* ok);
+/* out[i] = a[i] + s[i] * b[i] on `curve`, one lane per entry: the per-entry folds of a verifier that holds many statements
+ * (vdf_nova_verify_aggregate_device).  a, b, out: affine points in Montgomery form, the identity (0, 0); s[i]: a PLAIN
+ * little-endian integer (not Montgomery form).  bits = 128 or 255 (anything else: VDF_ERR_BAD_ARG) is how many of its low bits
+ * count: bits of s[i] at and above `bits` are MASKED -- never read -- so the call computes a[i] + (s[i] mod 2^bits) * b[i]; a
+ * scalar at or above the group order is not reduced first (the result is the same point).  out[i] is canonical affine
+ * Montgomery form, byte for byte the host's pt_to_aff(pt_add(a, pt_mul(b, s, bits))); every exceptional case of the group law
+ * is handled (either operand the identity, a = -s b, a = s b, a = b).  The points are not checked to lie on the curve
+ * (vdf_bases_validate, vdf_points_decompress do that).  The operands are a peer's: every lane runs `bits` doublings and
+ * `bits` additions, a scalar's bit only selects.  Each array in host or device memory (vdf_ptr_is_device), device arrays
+ * 16-byte aligned, `out` not overlapping an input.  n = 0 is VDF_OK and touches nothing; a null pointer with n > 0 is
+ * VDF_ERR_BAD_ARG. */
+int  vdf_points_axpy(vdf_ctx* ctx, int curve, const vdf_affine* a, const vdf_affine* b, const vdf_fe* s, int bits, size_t n,
+                     vdf_affine* out);
 /* Throughput probe: each of n lanes runs `iters` dependent Montgomery multiplications
  * (roofline / issue-rate calibration for DESIGN.md; not on the prove path). */
 int  vdf_fe_mul_chain(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, int iters, vdf_fe* out);

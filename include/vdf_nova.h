@@ -1135,6 +1135,39 @@ typedef struct vdf_wire_instance { uint8_t comm_W[32], comm_E[32], u[32], X[2][3
 int  vdf_nova_aggregate_fold_instances(int field_of_primary, int side, const uint8_t digest[32], size_t count,
                                        const vdf_wire_instance inst[], const uint8_t comm_TT[][32], vdf_wire_instance* acc,
                                        vdf_fe r_out[]);
+/* ---- the aggregate's verifier with its per-entry group arithmetic on the device ---------------------------------------------
+ * vdf_nova_verify_aggregate spends, per entry, eight point decodings (in vdf_nova_aggregate_deserialize) and eight scalar
+ * multiplications on the host; the two arguments that are the point of aggregation do not grow with the count.  In
+ * "vdf-aggregate-v1" every instance is absorbed before the first challenge and only commit(TT_k) after it, so no challenge
+ * depends on a folded accumulator and a side's sequential folds are two sums,
+ *     comm_W = W_1 + sum_{k>=2} r_k W_k        comm_E = E_1 + sum_{k>=2} (r_k^2 E_k + r_k commit(TT_k)),
+ * one vdf_msm_batch over the 3 count - 1 uploaded points; the count secondary folds F2_k = r_U2_k + rho_k l_u2_k are one
+ * vdf_points_axpy (vdf_hip.h) of 2 count entries.  Transcripts, challenges, the Poseidon hashes, the exact per-entry checks and
+ * the folds of u and X stay on the host.  The three calls below are held, byte for byte and code for code, to the host calls
+ * above, which stay the statement; they run on the parameter set's context and leave its asynchronous flag and stream as they
+ * found them, whatever they return.
+ *
+ * vdf_nova_aggregate_fold_instances_device: vdf_nova_aggregate_fold_instances with the orientation and the digest taken from
+ *   pp; the points are decoded by one vdf_points_decompress and go to the sums as they lie.  *acc and r_out: the host call's
+ *   bytes.  The same refusals with the same codes (a null pp: VDF_ERR_BAD_ARG).
+ * vdf_nova_verify_aggregate_device: vdf_nova_verify_aggregate's contract -- the same checks in the same order, the same *ok,
+ *   *bad_entry and return codes.
+ * vdf_nova_verify_aggregate_wire: bytes in, verdict out (the aggregate's vdf_nova_verify_wire_batch).  Every point of "VDFAGG01"
+ *   -- the statements', the commit(TT), the arguments' L and R -- is decoded by one vdf_points_decompress per curve, then the
+ *   device verifier runs.  *decode_code = exactly what vdf_nova_aggregate_deserialize(pp, bytes, len, ..) returns for these
+ *   bytes; unless it is VDF_OK nothing is verified and *ok = 0, *bad_entry = -1, and the call itself returns VDF_OK.  With
+ *   *decode_code == VDF_OK the return code, *ok and *bad_entry are vdf_nova_verify_aggregate's for the decoded object.  A null
+ *   pp, bytes, ok or decode_code: VDF_ERR_BAD_ARG.
+ * vdf_nova_aggregate_verify_times: what the last of the two verifiers above spent on this thread, host wall time in ms:
+ *   [0] the exact checks (three Poseidon hashes per entry), [1] the secondary folds, [2] both accumulators, [3] both arguments,
+ *   [4] the decoding (the wire call only).  For tools/gpu_aggregate_verify.py. */
+int  vdf_nova_aggregate_fold_instances_device(vdf_pp* pp, int side, size_t count, const vdf_wire_instance inst[],
+                                              const uint8_t comm_TT[][32], vdf_wire_instance* acc, vdf_fe r_out[]);
+int  vdf_nova_verify_aggregate_device(const vdf_aggregate* agg, vdf_pp* pp, size_t count, const size_t num_steps[],
+                                      const vdf_fe* z0, const vdf_fe* zi, int* ok, int64_t* bad_entry);
+int  vdf_nova_verify_aggregate_wire(vdf_pp* pp, const uint8_t* bytes, size_t len, size_t count, const size_t num_steps[],
+                                    const vdf_fe* z0, const vdf_fe* zi, int* ok, int64_t* bad_entry, int* decode_code);
+int  vdf_nova_aggregate_verify_times(double ms[5]);
 size_t vdf_nova_proof_serialized_size(const vdf_proof* proof);
 int  vdf_nova_proof_serialize(const vdf_proof* proof, uint8_t* out, size_t cap);
 int  vdf_nova_proof_deserialize(vdf_pp* pp, const uint8_t* in, size_t len, vdf_proof** out);

@@ -2319,6 +2319,23 @@ int vdf_points_decompress(vdf_ctx* ctx, int curve, const uint8_t* enc, size_t n,
   });
 }
 
+int vdf_points_axpy(vdf_ctx* ctx, int curve, const vdf_affine* a, const vdf_affine* b, const vdf_fe* s, int bits, size_t n, vdf_affine* out) {
+  return guarded(ctx, [&]() -> Status {
+    VDF_TRY(vdf::check_curve(curve));
+    if (bits != 128 && bits != 255) return Status{VDF_ERR_BAD_ARG, "bits must be 128 or 255"};
+    if (n == 0) return Status{};
+    if (!a || !b || !s || !out) return Status{VDF_ERR_BAD_ARG, "null argument"};
+    Staging st(ctx);
+    const void *da, *db, *ds; void* dout;
+    VDF_TRY(st.in(a, n * 64, &da));
+    VDF_TRY(st.in(b, n * 64, &db));
+    VDF_TRY(st.in(s, n * 32, &ds));
+    VDF_TRY(st.out(out, n * 64, &dout));
+    VDF_TRY(vdf::points_axpy(curve, da, db, ds, bits, n, dout, ctx->stream));
+    return st.finish();
+  });
+}
+
 int vdf_fe_mul_chain(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, int iters, vdf_fe* out) {
   return guarded(ctx, [&]() -> Status {
     Staging st(ctx);

@@ -91,7 +91,10 @@ uint8_t* put_argument(uint8_t* o, const Spartan& sp, const Field& F, const Field
   }
   return o;
 }
-const uint8_t* get_argument(const uint8_t* i, Spartan& p, const Layout& L, const Field& F, const Field& Fb, bool* canonical, bool* on_curve) {
+// point(enc, sd, dst): what becomes of a 32-byte point encoding (nova_internal.hpp get_inst_points has the rule)
+template <class PointFn>
+const uint8_t* get_argument(const uint8_t* i, Spartan& p, const Layout& L, const Side& sd, bool* canonical, PointFn&& point) {
+  const Field& F = *sd.F;
   spartan_resize(p, L);
   auto get = [&](Fe& v) { *canonical &= wire_get_fe(i, F, &v); i += 32; };
   for (auto& ev : p.outer) for (Fe& v : ev) get(v);
@@ -100,8 +103,8 @@ const uint8_t* get_argument(const uint8_t* i, Spartan& p, const Layout& L, const
   get(p.w_eval);
   for (Ipa* ip : {&p.ipaW, &p.ipaE}) {
     for (size_t j = 0; j < ip->L.size(); ++j) {
-      *on_curve &= pt_decompress(i, Fb, &ip->L[j]);
-      *on_curve &= pt_decompress(i + 32, Fb, &ip->R[j]);
+      point(i, sd, &ip->L[j]);
+      point(i + 32, sd, &ip->R[j]);
       i += 64;
     }
     for (Fe& v : ip->a) get(v);
@@ -112,6 +115,49 @@ const uint8_t* get_argument(const uint8_t* i, Spartan& p, const Layout& L, const
 constexpr size_t AGG_HEADER = 8 + 8 + 8 + 32;
 size_t aggregate_wire_size(size_t count, size_t arity, const Layout L[2]) {
   return AGG_HEADER + count * statement_wire(arity) + 2 * (count - 1) * 32 + spartan_wire_size(L[0]) + spartan_wire_size(L[1]);
+}
+
+// ---- "VDFAGG01" read back: the one walk over the layout (include/vdf_nova.h) ---------------------------------------------------
+// What stands in front of the elements: length, magic, t, digest, count.  The codes are vdf_nova_aggregate_deserialize's.
+int aggregate_wire_header(const vdf_pp* pp, const uint8_t* in, size_t len, Layout L[2], size_t* count_out) {
+  if (len < AGG_HEADER) return fail(VDF_ERR_BAD_LENGTH, "encoding is shorter than its header");
+  if (memcmp(in, WIRE_MAGIC_AGGREGATE, 8) != 0) return fail(VDF_ERR_BAD_ARG, "not this kind of encoding (magic)");
+  uint64_t t, count;
+  memcpy(&t, in + 8, 8);
+  memcpy(&count, in + 16, 8);
+  if (t != pp->t || memcmp(in + 24, pp->digest, 32) != 0) return fail(VDF_ERR_BAD_ARG, "encoding was made under other public parameters");
+  L[0] = layout_of(pp->s[0]); L[1] = layout_of(pp->s[1]);
+  if (count == 0 || count > VDF_NOVA_AGGREGATE_MAX || len != aggregate_wire_size((size_t)count, pp->arity, L))
+    return fail(VDF_ERR_BAD_LENGTH, "encoding has the wrong length for this count and shape");
+  *count_out = (size_t)count;
+  return VDF_OK;
+}
+// Every element behind a header that passed: field elements are range-checked and converted here (*canonical), every point's 32
+// bytes go to point(enc, side, dst) -- decoded on the spot by the host deserialiser, noted by the wire verifier for one launch per curve.
+template <class PointFn>
+std::unique_ptr<vdf_aggregate> aggregate_wire_walk(vdf_pp* pp, const Layout L[2], const uint8_t* in, size_t count, bool* canonical, PointFn&& point) {
+  std::unique_ptr<vdf_aggregate> a(new vdf_aggregate());
+  a->t = pp->t;
+  a->field = pp->field;
+  a->arity = pp->arity;
+  memcpy(a->digest, pp->digest, 32);
+  a->st.resize(count);
+  const uint8_t* i = in + AGG_HEADER;
+  for (vdf_aggregate::Statement& s : a->st) {
+    i = get_inst_points(i, &s.r_U1, pp->s[0], true, canonical, point);
+    i = get_inst_points(i, &s.r_U2, pp->s[1], true, canonical, point);
+    i = get_inst_points(i, &s.l_u2, pp->s[1], false, canonical, point);
+    point(i, pp->s[1], &s.T2); i += 32;
+    s.zi1.resize(pp->arity);
+    for (size_t k = 0; k < pp->arity; ++k, i += 32) *canonical &= wire_get_fe(i, *pp->s[0].F, &s.zi1[k]);
+    *canonical &= wire_get_fe(i, *pp->s[1].F, &s.zi2); i += 32;
+  }
+  for (int side = 0; side < 2; ++side) {
+    a->TT[side].resize(count - 1);
+    for (Aff& p : a->TT[side]) { point(i, pp->s[side], &p); i += 32; }
+  }
+  for (int side = 0; side < 2; ++side) i = get_argument(i, a->sp[side], L[side], pp->s[side], canonical, point);
+  return a;
 }
 
 // One side's accumulator on the device: z = [W | u | X], E, and A z, B z, C z kept current by the fold (they are linear in z);
@@ -166,6 +212,151 @@ struct SideFold {
     fold_pair(sd, inst, in, *TT, r, raw);                                    // the instance, as the verifier folds it
     return VDF_OK;
   }
+};
+
+// The exact checks of every entry (as vdf_nova_verify_compressed makes them) and the Poseidon challenge of the verifier's own
+// secondary fold: passed(k, statement, r) receives each entry that holds, in order.  Returns the first entry that fails, -1 when none
+// does.  Both verifiers (host folds, device folds) run this and nothing else per entry.
+template <class Passed>
+int64_t exact_checks(const vdf_aggregate* agg, const vdf_pp* pp, size_t count, const size_t num_steps[], const vdf_fe* z0, const vdf_fe* zi,
+                     Passed&& passed) {
+  const Side& S1 = pp->s[PRIMARY];
+  const Side& S2 = pp->s[SECONDARY];
+  const Field& F1 = *S1.F;
+  const Field& F2 = *S2.F;
+  const size_t ar = pp->arity;
+  for (size_t k = 0; k < count; ++k) {
+    const vdf_aggregate::Statement& s = agg->st[k];
+    if (s.zi1.size() != ar) return (int64_t)k;
+    const Fe* z0k = (const Fe*)z0 + k * ar;
+    const std::vector<Fe> z0p(z0k, z0k + ar), z0s(1, zero()), zi2(1, s.zi2);
+    uint64_t hv[4];
+    hash_state(S1.field, pp->params[PRIMARY], from_u64(num_steps[k], F1), z0p, s.zi1, to_relaxed(s.r_U2, F2), hv, pp->ro);
+    if (int_to_fe(hv, F2) != s.l_u2.X[0]) return (int64_t)k;
+    hash_state(S2.field, pp->params[SECONDARY], from_u64(num_steps[k], F2), z0s, zi2, to_relaxed(s.r_U1, F1), hv, pp->ro);
+    if (int_to_fe(hv, F2) != s.l_u2.X[1]) return (int64_t)k;
+    if (memcmp(s.zi1.data(), (const Fe*)zi + k * ar, 32 * ar) != 0 || !s.zi2.is_zero()) return (int64_t)k;
+    uint64_t r[4];
+    fold_challenge(pp, s.r_U2, s.l_u2, s.T2, r);
+    passed(k, s, r);
+  }
+  return -1;
+}
+
+// Both arguments against the two accumulators (the unchanged spartan_replay / ipa_check_one): *ok = 1 when they hold.  The
+// context is switched to asynchronous calls for the replay and put back as it was.
+int check_arguments(const vdf_aggregate* agg, vdf_pp* pp, const Inst acc[2], int* ok) {
+  vdf_ctx* ctx = pp->ctx;
+  int was_async = 0;
+  HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
+  HIPCALL(ctx, vdf_ctx_sync(ctx));
+  HIPCALL(ctx, vdf_ctx_set_async(ctx, 1));
+  struct Restore { vdf_ctx* c; int a; ~Restore() { vdf_ctx_sync(c); vdf_ctx_set_async(c, a); } } restore{ctx, was_async};
+  for (int side = 0; side < 2; ++side) {
+    const Side& sd = pp->s[side];
+    IpaDeferred d[2];
+    bool good = false;
+    int rc = spartan_replay(sd, acc[side].comm_W, acc[side].comm_E, acc[side].u, acc[side].X, agg->sp[side], d, &good);
+    if (rc != VDF_OK || !good) return rc;
+    DevBufs bufs(sd.ctx, sd.arena);
+    const size_t n = std::max(d[0].n, d[1].n);
+    void* d_s;
+    { int rc2 = bufs.reserve(n); if (rc2 != VDF_OK) return fail(rc2, vdf_last_error(sd.ctx)); }
+    { int rc2 = bufs.zeros(n, &d_s); if (rc2 != VDF_OK) return fail(rc2, vdf_last_error(sd.ctx)); }
+    for (int q = 0; q < 2; ++q) {
+      rc = ipa_check_one(sd, d[q], d_s, &good);
+      if (rc != VDF_OK || !good) return rc;
+    }
+  }
+  *ok = 1;
+  return VDF_OK;
+}
+
+// fold_instances_core with the group arithmetic on the device.  No challenge depends on a folded accumulator (every instance is
+// absorbed before the first one, then only commit(TT_k)), so the K - 1 sequential folds of the commitments are two sums,
+//   comm_W = W_1 + sum_{k>=2} r_k W_k          comm_E = E_1 + sum_{k>=2} (r_k^2 E_k + r_k TT_k),
+// one vdf_msm_batch of two vectors over the 3K - 1 points [W_1..W_K | E_1..E_K | TT_2..TT_K] uploaded as they are (no table: the
+// bucket method takes equal points, opposite points and the identity, msm.hip k_accumulate).  The transcript, the challenges and
+// the folds of u and X stay on the host.  packed: those points in that order in memory a copy can read (a device or pinned
+// block the decoder wrote), or null: they are gathered from inst and TT.  sd: a side of the parameter set (ctx, curve, F, Fb, digest).
+int fold_instances_on_device(const Side& sd, int side, size_t count, const Inst* inst, const Aff* TT, const vdf_affine* packed, Inst* acc,
+                             Fe* r_out) {
+  const Field& F = *sd.F;
+  const Field& Fb = *sd.Fb;
+  vdf_ctx* ctx = sd.ctx;
+  Transcript tr("aggregate");
+  const uint64_t head[2] = {(uint64_t)count, (uint64_t)side};
+  tr.absorb("count", head, 16);
+  for (size_t k = 0; k < count; ++k) instance_bytes(tr, sd, inst[k].comm_W, inst[k].comm_E, inst[k].u, inst[k].X);
+  Inst a = inst[0];
+  if (count == 1) { *acc = a; return VDF_OK; }
+  std::vector<Fe> sw(count), se(2 * count - 1);
+  sw[0] = se[0] = one(F);
+  for (size_t k = 1; k < count; ++k) {
+    tr.absorb_pt("T", &TT[k - 1], 1, Fb);
+    uint64_t raw[4];
+    const Fe r = tr.challenge("r", F, raw);
+    sw[k] = r;
+    se[k] = sqr(r, F);
+    se[count + k - 1] = r;
+    a.u = add(a.u, mul(r, inst[k].u, F), F);
+    for (int j = 0; j < NUM_IO; ++j) a.X[j] = add(a.X[j], mul(r, inst[k].X[j], F), F);
+    if (r_out) r_out[k - 1] = r;
+  }
+  std::vector<Aff> own;
+  if (!packed) {
+    own.resize(3 * count - 1);
+    for (size_t k = 0; k < count; ++k) { own[k] = inst[k].comm_W; own[count + k] = inst[k].comm_E; }
+    for (size_t k = 0; k + 1 < count; ++k) own[2 * count + k] = TT[k];
+    packed = (const vdf_affine*)own.data();
+  }
+  vdf_bases* pb = nullptr;
+  HIPCALL(ctx, vdf_bases_upload(ctx, sd.curve, packed, 3 * count - 1, &pb));
+  const size_t off[2] = {0, count}, n[2] = {count, 2 * count - 1};
+  const vdf_fe* const sc[2] = {(const vdf_fe*)sw.data(), (const vdf_fe*)se.data()};
+  vdf_jac j[2];
+  int rc = vdf_msm_batch(ctx, pb, 2, off, sc, n, 1, j);
+  if (rc == VDF_OK) rc = vdf_ctx_sync(ctx);
+  const std::string err = rc == VDF_OK ? "" : vdf_last_error(ctx);
+  vdf_bases_free(pb);
+  if (rc != VDF_OK) return fail(rc, "vdf_msm_batch (aggregate fold): " + err);
+  jac_to_aff2(j[0], j[1], Fb, &a.comm_W, &a.comm_E);
+  *acc = a;
+  return VDF_OK;
+}
+
+// n 32-byte encodings of one curve decoded by one vdf_points_decompress on a pinned block the kernel reads and writes in place
+// (compress_host.cpp's wire batch has the same block): [enc: 32 n | points: 64 n | ok: n].  The caller fills enc(), decodes
+// and reads points() / good() after a wait; the block is a device address too, so the points can go on to an upload as they lie.
+struct DecodeBlock {
+  vdf_ctx* ctx;
+  size_t n;
+  void* blk = nullptr;
+  DecodeBlock(vdf_ctx* c, size_t n_) : ctx(c), n(n_) {}
+  ~DecodeBlock() { if (blk) vdf_host_free(ctx, blk); }
+  int alloc() { return vdf_host_alloc(ctx, 97 * n, &blk); }
+  uint8_t* enc() { return static_cast<uint8_t*>(blk); }
+  vdf_affine* points() { return reinterpret_cast<vdf_affine*>(enc() + 32 * n); }
+  const uint8_t* good() { return enc() + 96 * n; }
+};
+
+// what the last device verification of this thread spent where, in ms (vdf_nova_aggregate_verify_times)
+thread_local double g_verify_ms[5] = {0, 0, 0, 0, 0};
+
+// the context's asynchronous flag set for a scope and put back, with a wait, on every way out
+struct AsyncScope {
+  vdf_ctx* c;
+  int was = 0;
+  bool armed = false;
+  explicit AsyncScope(vdf_ctx* ctx) : c(ctx) {}
+  int enter() {
+    HIPCALL(c, vdf_ctx_get_async(c, &was));
+    HIPCALL(c, vdf_ctx_sync(c));
+    HIPCALL(c, vdf_ctx_set_async(c, 1));
+    armed = true;
+    return VDF_OK;
+  }
+  ~AsyncScope() { if (armed) { vdf_ctx_sync(c); vdf_ctx_set_async(c, was); } }
 };
 
 }  // namespace
@@ -284,57 +475,20 @@ int vdf_nova_verify_aggregate(const vdf_aggregate* agg, vdf_pp* pp, size_t count
     if (!num_steps || !z0 || !zi) return fail(VDF_ERR_BAD_ARG, "null argument");
     const Side& S1 = pp->s[PRIMARY];
     const Side& S2 = pp->s[SECONDARY];
-    const Field& F1 = *S1.F;
-    const Field& F2 = *S2.F;
-    const size_t ar = pp->arity;
     auto bad = [&](size_t k) { if (bad_entry) *bad_entry = (int64_t)k; return VDF_OK; };
     for (size_t k = 0; k < count; ++k) if (num_steps[k] == 0) return bad(k);
-    // the exact checks of every entry (as vdf_nova_verify_compressed makes them), then the verifier's own secondary fold
+    // the exact checks of every entry, then the verifier's own secondary fold
     std::vector<Inst> i1(count), i2(count);
-    for (size_t k = 0; k < count; ++k) {
-      const vdf_aggregate::Statement& s = agg->st[k];
-      if (s.zi1.size() != ar) return bad(k);
-      const Fe* z0k = (const Fe*)z0 + k * ar;
-      const std::vector<Fe> z0p(z0k, z0k + ar), z0s(1, zero()), zi2(1, s.zi2);
-      uint64_t hv[4];
-      hash_state(S1.field, pp->params[PRIMARY], from_u64(num_steps[k], F1), z0p, s.zi1, to_relaxed(s.r_U2, F2), hv, pp->ro);
-      if (int_to_fe(hv, F2) != s.l_u2.X[0]) return bad(k);
-      hash_state(S2.field, pp->params[SECONDARY], from_u64(num_steps[k], F2), z0s, zi2, to_relaxed(s.r_U1, F1), hv, pp->ro);
-      if (int_to_fe(hv, F2) != s.l_u2.X[1]) return bad(k);
-      if (memcmp(s.zi1.data(), (const Fe*)zi + k * ar, 32 * ar) != 0 || !s.zi2.is_zero()) return bad(k);
-      uint64_t r[4];
-      fold_challenge(pp, s.r_U2, s.l_u2, s.T2, r);
+    const int64_t first_bad = exact_checks(agg, pp, count, num_steps, z0, zi, [&](size_t k, const vdf_aggregate::Statement& s, const uint64_t r[4]) {
       i1[k] = s.r_U1;
       i2[k] = fold_instance(S2, s.r_U2, s.l_u2, s.T2, r);
-    }
+    });
+    if (first_bad >= 0) return bad((size_t)first_bad);
     if (agg->TT[0].size() != count - 1 || agg->TT[1].size() != count - 1) return VDF_OK;
     Inst acc[2];
     fold_instances_core(S1, PRIMARY, count, i1.data(), agg->TT[0].data(), &acc[0], nullptr);
     fold_instances_core(S2, SECONDARY, count, i2.data(), agg->TT[1].data(), &acc[1], nullptr);
-    vdf_ctx* ctx = pp->ctx;
-    int was_async = 0;
-    HIPCALL(ctx, vdf_ctx_get_async(ctx, &was_async));
-    HIPCALL(ctx, vdf_ctx_sync(ctx));
-    HIPCALL(ctx, vdf_ctx_set_async(ctx, 1));
-    struct Restore { vdf_ctx* c; int a; ~Restore() { vdf_ctx_sync(c); vdf_ctx_set_async(c, a); } } restore{ctx, was_async};
-    for (int side = 0; side < 2; ++side) {
-      const Side& sd = pp->s[side];
-      IpaDeferred d[2];
-      bool good = false;
-      int rc = spartan_replay(sd, acc[side].comm_W, acc[side].comm_E, acc[side].u, acc[side].X, agg->sp[side], d, &good);
-      if (rc != VDF_OK || !good) return rc;
-      DevBufs bufs(sd.ctx, sd.arena);
-      const size_t n = std::max(d[0].n, d[1].n);
-      void* d_s;
-      { int rc2 = bufs.reserve(n); if (rc2 != VDF_OK) return fail(rc2, vdf_last_error(sd.ctx)); }
-      { int rc2 = bufs.zeros(n, &d_s); if (rc2 != VDF_OK) return fail(rc2, vdf_last_error(sd.ctx)); }
-      for (int q = 0; q < 2; ++q) {
-        rc = ipa_check_one(sd, d[q], d_s, &good);
-        if (rc != VDF_OK || !good) return rc;
-      }
-    }
-    *ok = 1;
-    return VDF_OK;
+    return check_arguments(agg, pp, acc, ok);
   });
 }
 
@@ -377,41 +531,175 @@ int vdf_nova_aggregate_deserialize(vdf_pp* pp, const uint8_t* in, size_t len, vd
   return nova_guard([&]() -> int {
     if (!pp || !in || !out) return fail(VDF_ERR_BAD_ARG, "null argument");
     *out = nullptr;
-    if (len < AGG_HEADER) return fail(VDF_ERR_BAD_LENGTH, "encoding is shorter than its header");
-    if (memcmp(in, WIRE_MAGIC_AGGREGATE, 8) != 0) return fail(VDF_ERR_BAD_ARG, "not this kind of encoding (magic)");
-    uint64_t t, count;
-    memcpy(&t, in + 8, 8);
-    memcpy(&count, in + 16, 8);
-    if (t != pp->t || memcmp(in + 24, pp->digest, 32) != 0) return fail(VDF_ERR_BAD_ARG, "encoding was made under other public parameters");
-    const Layout L[2] = {layout_of(pp->s[0]), layout_of(pp->s[1])};
-    if (count == 0 || count > VDF_NOVA_AGGREGATE_MAX || len != aggregate_wire_size((size_t)count, pp->arity, L))
-      return fail(VDF_ERR_BAD_LENGTH, "encoding has the wrong length for this count and shape");
-    std::unique_ptr<vdf_aggregate> a(new vdf_aggregate());
-    a->t = t;
-    a->field = pp->field;
-    a->arity = pp->arity;
-    memcpy(a->digest, pp->digest, 32);
-    a->st.resize((size_t)count);
+    Layout L[2];
+    size_t count = 0;
+    { int rc = aggregate_wire_header(pp, in, len, L, &count); if (rc != VDF_OK) return rc; }
     bool canonical = true, on_curve = true;
-    const uint8_t* i = in + AGG_HEADER;
-    for (vdf_aggregate::Statement& s : a->st) {
-      i = get_inst(i, &s.r_U1, pp->s[0], true, &canonical, &on_curve);
-      i = get_inst(i, &s.r_U2, pp->s[1], true, &canonical, &on_curve);
-      i = get_inst(i, &s.l_u2, pp->s[1], false, &canonical, &on_curve);
-      on_curve &= pt_decompress(i, *pp->s[1].Fb, &s.T2); i += 32;
-      s.zi1.resize(pp->arity);
-      for (size_t k = 0; k < pp->arity; ++k, i += 32) canonical &= wire_get_fe(i, *pp->s[0].F, &s.zi1[k]);
-      canonical &= wire_get_fe(i, *pp->s[1].F, &s.zi2); i += 32;
-    }
-    for (int side = 0; side < 2; ++side) {
-      a->TT[side].resize((size_t)count - 1);
-      for (Aff& p : a->TT[side]) { on_curve &= pt_decompress(i, *pp->s[side].Fb, &p); i += 32; }
-    }
-    for (int side = 0; side < 2; ++side) i = get_argument(i, a->sp[side], L[side], *pp->s[side].F, *pp->s[side].Fb, &canonical, &on_curve);
+    std::unique_ptr<vdf_aggregate> a = aggregate_wire_walk(pp, L, in, count, &canonical, [&](const uint8_t* enc, const Side& sd, Aff* dst) {
+      on_curve &= pt_decompress(enc, *sd.Fb, dst);
+    });
     if (!canonical) return fail(VDF_ERR_NONCANONICAL, "a field element of the encoding is not canonical");
     if (!on_curve) return fail(VDF_ERR_NONCANONICAL, "a point of the encoding does not decode to a curve point");
     *out = a.release();
     return VDF_OK;
+  });
+}
+
+// ---- the verifier with its per-entry group arithmetic on the device -------------------------------------------------------------
+int vdf_nova_aggregate_fold_instances_device(vdf_pp* pp, int side, size_t count, const vdf_wire_instance inst[], const uint8_t comm_TT[][32],
+                                             vdf_wire_instance* acc, vdf_fe r_out[]) {
+  return nova_guard([&]() -> int {
+    if (!pp) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (side != 0 && side != 1) return fail(VDF_ERR_BAD_ARG, "unknown field or side");
+    if (!inst || !acc || (count > 1 && !comm_TT)) return fail(VDF_ERR_BAD_ARG, "null argument");
+    if (count == 0 || count > VDF_NOVA_AGGREGATE_MAX) return fail(VDF_ERR_BAD_ARG, "count must be 1.." + std::to_string(VDF_NOVA_AGGREGATE_MAX));
+    const Side& sd = pp->s[side];
+    vdf_ctx* ctx = sd.ctx;
+    std::vector<Inst> in(count);
+    bool canonical = true;
+    for (size_t k = 0; k < count; ++k) {
+      canonical &= wire_get_fe(inst[k].u, *sd.F, &in[k].u);
+      for (int j = 0; j < NUM_IO; ++j) canonical &= wire_get_fe(inst[k].X[j], *sd.F, &in[k].X[j]);
+    }
+    if (!canonical) return fail(VDF_ERR_NONCANONICAL, "a field element of an instance is not canonical");
+    // the 3 count - 1 encodings in the order the sums take their points: [W_1..W_K | E_1..E_K | TT_2..TT_K]
+    const size_t np = 3 * count - 1;
+    DecodeBlock blk(ctx, np);
+    HIPCALL(ctx, blk.alloc());
+    for (size_t k = 0; k < count; ++k) {
+      memcpy(blk.enc() + 32 * k, inst[k].comm_W, 32);
+      memcpy(blk.enc() + 32 * (count + k), inst[k].comm_E, 32);
+    }
+    for (size_t k = 0; k + 1 < count; ++k) memcpy(blk.enc() + 32 * (2 * count + k), comm_TT[k], 32);
+    AsyncScope scope(ctx);
+    { int rc = scope.enter(); if (rc != VDF_OK) return rc; }
+    HIPCALL(ctx, vdf_points_decompress(ctx, sd.curve, blk.enc(), np, blk.points(), const_cast<uint8_t*>(blk.good())));
+    HIPCALL(ctx, vdf_ctx_sync(ctx));
+    for (size_t k = 0; k < np; ++k)
+      if (!blk.good()[k]) return fail(VDF_ERR_NONCANONICAL, "a point does not decode to a curve point");
+    const Aff* pts = reinterpret_cast<const Aff*>(blk.points());
+    for (size_t k = 0; k < count; ++k) { in[k].comm_W = pts[k]; in[k].comm_E = pts[count + k]; }
+    Inst folded;
+    { int rc = fold_instances_on_device(sd, side, count, in.data(), pts + 2 * count, blk.points(), &folded, reinterpret_cast<Fe*>(r_out)); if (rc != VDF_OK) return rc; }
+    put_inst(reinterpret_cast<uint8_t*>(acc), folded, sd, true);
+    return VDF_OK;
+  });
+}
+
+int vdf_nova_verify_aggregate_device(const vdf_aggregate* agg, vdf_pp* pp, size_t count, const size_t num_steps[], const vdf_fe* z0,
+                                     const vdf_fe* zi, int* ok, int64_t* bad_entry) {
+  return nova_guard([&]() -> int {
+    if (!agg || !pp || !ok) return fail(VDF_ERR_BAD_ARG, "null argument");
+    *ok = 0;
+    if (bad_entry) *bad_entry = -1;
+    if (agg->t != pp->t || memcmp(agg->digest, pp->digest, 32) != 0) return fail(VDF_ERR_BAD_ARG, "aggregate was made under other public parameters");
+    if (count == 0 || count != agg->st.size()) return VDF_OK;
+    if (!num_steps || !z0 || !zi) return fail(VDF_ERR_BAD_ARG, "null argument");
+    const Side& S1 = pp->s[PRIMARY];
+    const Side& S2 = pp->s[SECONDARY];
+    const Field& F2 = *S2.F;
+    auto bad = [&](size_t k) { if (bad_entry) *bad_entry = (int64_t)k; return VDF_OK; };
+    for (size_t k = 0; k < count; ++k) if (num_steps[k] == 0) return bad(k);
+    for (double& v : g_verify_ms) v = 0;
+    double t0 = now_ms();
+    // the exact checks of every entry on the host; of the verifier's own secondary fold only the challenge, u and X
+    std::vector<Inst> i1(count), i2(count);
+    std::vector<Aff> fa(2 * count), fb(2 * count), fo(2 * count);          // [comm_W of every entry | comm_E of every entry]
+    std::vector<Fe> rho(2 * count);
+    const int64_t first_bad = exact_checks(agg, pp, count, num_steps, z0, zi, [&](size_t k, const vdf_aggregate::Statement& s, const uint64_t r[4]) {
+      i1[k] = s.r_U1;
+      const Fe rf = int_to_fe(r, F2);
+      i2[k].u = add(s.r_U2.u, rf, F2);
+      for (int j = 0; j < NUM_IO; ++j) i2[k].X[j] = add(s.r_U2.X[j], mul(rf, s.l_u2.X[j], F2), F2);
+      fa[k] = s.r_U2.comm_W; fb[k] = s.l_u2.comm_W;
+      fa[count + k] = s.r_U2.comm_E; fb[count + k] = s.T2;
+      memcpy(rho[k].l, r, 32);
+      rho[count + k] = rho[k];
+    });
+    g_verify_ms[0] = now_ms() - t0;
+    if (first_bad >= 0) return bad((size_t)first_bad);
+    if (agg->TT[0].size() != count - 1 || agg->TT[1].size() != count - 1) return VDF_OK;
+    Inst acc[2];
+    {
+      vdf_ctx* ctx = pp->ctx;
+      AsyncScope scope(ctx);
+      { int rc = scope.enter(); if (rc != VDF_OK) return rc; }
+      t0 = now_ms();
+      // F2_k = r_U2_k + rho_k l_u2_k: comm_W = W_r + rho W_l, comm_E = E_r + rho T2 (rho: the 128-bit Poseidon challenge)
+      HIPCALL(ctx, vdf_points_axpy(ctx, S2.curve, (const vdf_affine*)fa.data(), (const vdf_affine*)fb.data(), (const vdf_fe*)rho.data(), 128,
+                                   2 * count, (vdf_affine*)fo.data()));
+      for (size_t k = 0; k < count; ++k) { i2[k].comm_W = fo[k]; i2[k].comm_E = fo[count + k]; }
+      g_verify_ms[1] = now_ms() - t0;
+      t0 = now_ms();
+      { int rc = fold_instances_on_device(S1, PRIMARY, count, i1.data(), agg->TT[0].data(), nullptr, &acc[0], nullptr); if (rc != VDF_OK) return rc; }
+      { int rc = fold_instances_on_device(S2, SECONDARY, count, i2.data(), agg->TT[1].data(), nullptr, &acc[1], nullptr); if (rc != VDF_OK) return rc; }
+      g_verify_ms[2] = now_ms() - t0;
+    }
+    t0 = now_ms();
+    const int rc = check_arguments(agg, pp, acc, ok);
+    g_verify_ms[3] = now_ms() - t0;
+    return rc;
+  });
+}
+
+int vdf_nova_aggregate_verify_times(double ms[5]) {
+  if (!ms) return fail(VDF_ERR_BAD_ARG, "null argument");
+  for (int k = 0; k < 5; ++k) ms[k] = g_verify_ms[k];
+  return VDF_OK;
+}
+
+int vdf_nova_verify_aggregate_wire(vdf_pp* pp, const uint8_t* bytes, size_t len, size_t count, const size_t num_steps[], const vdf_fe* z0,
+                                   const vdf_fe* zi, int* ok, int64_t* bad_entry, int* decode_code) {
+  return nova_guard([&]() -> int {
+    if (!pp || !bytes || !ok || !decode_code) return fail(VDF_ERR_BAD_ARG, "null argument");
+    *ok = 0;
+    if (bad_entry) *bad_entry = -1;
+    *decode_code = VDF_OK;
+    const double t_decode = now_ms();
+    Layout L[2];
+    size_t wire_count = 0;
+    *decode_code = aggregate_wire_header(pp, bytes, len, L, &wire_count);
+    if (*decode_code != VDF_OK) return VDF_OK;
+    struct WirePoint { const uint8_t* enc; Aff* dst; };
+    std::vector<WirePoint> pts[2];
+    bool canonical = true;
+    std::unique_ptr<vdf_aggregate> a = aggregate_wire_walk(pp, L, bytes, wire_count, &canonical, [&](const uint8_t* enc, const Side& sd, Aff* dst) {
+      pts[&sd - pp->s].push_back({enc, dst});
+    });
+    if (!canonical) { *decode_code = fail(VDF_ERR_NONCANONICAL, "a field element of the encoding is not canonical"); return VDF_OK; }
+    {
+      vdf_ctx* ctx = pp->ctx;
+      const size_t n[2] = {pts[0].size(), pts[1].size()}, total = n[0] + n[1];
+      DecodeBlock blk(ctx, total);                       // side 0's share of each part first
+      HIPCALL(ctx, blk.alloc());
+      {
+        uint8_t* e = blk.enc();
+        for (int side = 0; side < 2; ++side)
+          for (const WirePoint& w : pts[side]) { memcpy(e, w.enc, 32); e += 32; }
+      }
+      {
+        AsyncScope scope(ctx);
+        { int rc = scope.enter(); if (rc != VDF_OK) return rc; }
+        for (int side = 0; side < 2; ++side) {
+          const size_t at = side ? n[0] : 0;
+          HIPCALL(ctx, vdf_points_decompress(ctx, pp->s[side].curve, blk.enc() + 32 * at, n[side], blk.points() + at,
+                                             const_cast<uint8_t*>(blk.good()) + at));
+        }
+        HIPCALL(ctx, vdf_ctx_sync(ctx));
+      }
+      for (size_t k = 0; k < total; ++k)
+        if (!blk.good()[k]) {
+          *decode_code = fail(VDF_ERR_NONCANONICAL, "a point of the encoding does not decode to a curve point");
+          return VDF_OK;
+        }
+      size_t k = 0;
+      for (int side = 0; side < 2; ++side)
+        for (const WirePoint& w : pts[side]) memcpy(w.dst, &blk.points()[k++], sizeof(Aff));
+    }
+    const double decode_ms = now_ms() - t_decode;
+    const int rc = vdf_nova_verify_aggregate_device(a.get(), pp, count, num_steps, z0, zi, ok, bad_entry);
+    g_verify_ms[4] = decode_ms;
+    return rc;
   });
 }
 

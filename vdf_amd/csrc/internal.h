@@ -309,6 +309,7 @@ Status bases_precompute(int curve, const void* d_pts, size_t n, int c, int sets,
 // encoding (d_ok[i] = 0 and a zeroed point for bytes that decode to none): every lane runs the same number of products
 Status fe_sqrt_vec(int field, const void* d_a, size_t n, void* d_out, uint8_t* d_ok, hipStream_t stream);
 Status points_decompress(int curve, const uint8_t* d_enc, size_t n, void* d_out, uint8_t* d_ok, hipStream_t stream);
+Status points_axpy(int curve, const void* d_a, const void* d_b, const void* d_s, int bits, size_t n, void* d_out, hipStream_t stream);
 
 // ---- vecops.hip ------------------------------------------------------------------------
 Status vec_axpy(int field, const void* a, const void* r, const void* b, size_t n, void* out, hipStream_t s);

@@ -1453,6 +1453,50 @@ __global__ __launch_bounds__(256) void k_points_decompress(const uint8_t* __rest
   ok[i] = good ? 1 : 0;
 }
 
+// ---- out[i] = a[i] + s[i] b[i], one lane per entry (vdf_points_axpy) ----------------------------------------------------------
+// A verifier's per-entry folds (host/aggregate_host.cpp): the points and the scalars are a peer's, so the rule of
+// k_points_decompress holds here too -- BITS doublings and BITS mixed additions in every lane, and the scalar's bit only decides
+// whether the addition's result is kept; no trip count depends on the data.  s[i]: a plain little-endian integer whose bits at
+// and above BITS are not read.  The group law is ec.cuh's canonical one (xyzz_dbl, xyzz_madd: every exceptional case), the
+// output canonical affine Montgomery form with the identity as (0, 0): what host_math.cpp's pt_to_aff(pt_add(a, pt_mul(b, s,
+// bits))) gives, byte for byte.  Per lane 19 products per bit, 10 for the closing addition and fe_inv's for the affine
+// output (DESIGN.md 4.25 has the shares).
+template <class P, int BITS>
+__global__ __launch_bounds__(256) void k_points_axpy(const char* __restrict__ a, const char* __restrict__ b, const uint4* __restrict__ s,
+                                                      uint32_t n, char* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const Affine<P> pb = affine_load<P>(b + (size_t)i * 64);
+  const uint4 slo = s[2 * (size_t)i], shi = s[2 * (size_t)i + 1];
+  // the scalar as a shift register of W words with bit BITS - 1 on top (every index a constant: the words stay in registers)
+  constexpr int W = (BITS + 31) / 32, PAD = 32 * W - BITS;
+  uint32_t k[8] = {slo.x, slo.y, slo.z, slo.w, shi.x, shi.y, shi.z, shi.w};
+  if constexpr (PAD != 0) {
+#pragma unroll
+    for (int l = W - 1; l > 0; --l) k[l] = (k[l] << PAD) | (k[l - 1] >> (32 - PAD));
+    k[0] <<= PAD;
+  }
+  XYZZ<P> acc = xyzz_identity<P>();
+  for (int bit = 0; bit < BITS; ++bit) {
+    acc = xyzz_dbl(acc);
+    XYZZ<P> sum = acc;
+    xyzz_madd(sum, pb);
+    const bool take = (k[W - 1] >> 31) != 0;
+#pragma unroll
+    for (int l = W - 1; l > 0; --l) k[l] = (k[l] << 1) | (k[l - 1] >> 31);
+    k[0] <<= 1;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) {
+      acc.x.v[l] = take ? sum.x.v[l] : acc.x.v[l];
+      acc.y.v[l] = take ? sum.y.v[l] : acc.y.v[l];
+      acc.zz.v[l] = take ? sum.zz.v[l] : acc.zz.v[l];
+      acc.zzz.v[l] = take ? sum.zzz.v[l] : acc.zzz.v[l];
+    }
+  }
+  xyzz_madd(acc, affine_load<P>(a + (size_t)i * 64));
+  affine_store<P>(out + (size_t)i * 64, xyzz_to_affine(acc));
+}
+
 // ---- the curves' endomorphism for the table-less path (vdf_hip_tuning.glv) --------------------------------------------
 // y^2 = x^3 + 5 has phi(x, y) = (zeta x, y) = [lambda] (x, y) with zeta, lambda primitive cube roots of unity in the base and
 // scalar field.  k = k1 + lambda k2 with |k1|, |k2| < 2^129 (pasta_constants.h: the lattice and its rounding constants), so
@@ -1818,6 +1862,23 @@ Status points_decompress(int curve, const uint8_t* d_enc, size_t n, void* d_out,
   KTimer kt(stream, "k_points_decompress", 97.0 * n);
   return with_curve(curve, [&](auto base, auto) {
     hipLaunchKernelGGL((k_points_decompress<tag_t<decltype(base)>>), grid_for(n), dim3(256), 0, stream, d_enc, (uint32_t)n, bytes_of(d_out), d_ok);
+  });
+}
+
+Status points_axpy(int curve, const void* d_a, const void* d_b, const void* d_s, int bits, size_t n, void* d_out, hipStream_t stream) {
+  VDF_TRY(check_curve(curve));
+  if (bits != 128 && bits != 255) return Status{VDF_ERR_BAD_ARG, "bits must be 128 or 255"};
+  if (n == 0) return Status{};
+  if (n > 0xFFFFFFFFull) return Status{VDF_ERR_BAD_LENGTH, "at most 2^32 - 1 points per call"};
+  KTimer kt(stream, "k_points_axpy", 224.0 * n);
+  return with_curve(curve, [&](auto base, auto) {
+    using P = tag_t<decltype(base)>;
+    if (bits == 128)
+      hipLaunchKernelGGL((k_points_axpy<P, 128>), grid_for(n), dim3(256), 0, stream, cbytes_of(d_a), cbytes_of(d_b), static_cast<const uint4*>(d_s),
+                         (uint32_t)n, bytes_of(d_out));
+    else
+      hipLaunchKernelGGL((k_points_axpy<P, 255>), grid_for(n), dim3(256), 0, stream, cbytes_of(d_a), cbytes_of(d_b), static_cast<const uint4*>(d_s),
+                         (uint32_t)n, bytes_of(d_out));
   });
 }
 

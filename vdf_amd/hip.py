@@ -871,6 +871,12 @@ class Context:
         limbs (x, y), ok: n uint8 (0: the bytes decode to no point, out zeroed); numpy arrays or device tensors, each on its own."""
         self._check(lib.vdf_points_decompress(self.handle, curve, _ptr(enc), n, _ptr(out), _ptr(ok)))
 
+    def points_axpy(self, curve, a, b, s, bits, n, out) -> None:
+        """vdf_points_axpy: out[i] = a[i] + s[i] b[i]; a, b, out: (n, 8) uint64 affine points in Montgomery form (the identity
+        is all zero), s: (n, 4) uint64 plain little-endian integers of which the low `bits` (128 or 255) count and the rest is
+        masked; numpy arrays or device tensors, each on its own."""
+        self._check(lib.vdf_points_axpy(self.handle, curve, _ptr(a), _ptr(b), _ptr(s), bits, n, _ptr(out)))
+
     def clock_probe(self, iters: int = 6000):
         """(shader MHz sustained under a multiply-bound load on every SIMD, the probe kernel's duration in ms)."""
         mhz, ms = C.c_double(), C.c_double()

@@ -137,6 +137,10 @@ for _name, _res, _args in [
     ("vdf_nova_aggregate_serialize", _i, [_vp, _vp, _sz]),
     ("vdf_nova_aggregate_deserialize", _i, [_vp, _vp, _sz, C.POINTER(_vp)]),
     ("vdf_nova_aggregate_fold_instances", _i, [_i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("vdf_nova_aggregate_fold_instances_device", _i, [_vp, _i, _sz, _vp, _vp, _vp, _vp]),
+    ("vdf_nova_verify_aggregate_device", _i, [_vp, _vp, _sz, C.POINTER(_sz), _vp, _vp, C.POINTER(_i), C.POINTER(C.c_int64)]),
+    ("vdf_nova_verify_aggregate_wire", _i, [_vp, _vp, _sz, _sz, C.POINTER(_sz), _vp, _vp, C.POINTER(_i), C.POINTER(C.c_int64), C.POINTER(_i)]),
+    ("vdf_nova_aggregate_verify_times", _i, [C.POINTER(C.c_double)]),
     ("vdf_nova_proof_serialized_size", _sz, [_vp]),
     ("vdf_nova_proof_serialize", _i, [_vp, _vp, _sz]),
     ("vdf_nova_proof_deserialize", _i, [_vp, _vp, _sz, C.POINTER(_vp)]),
@@ -1938,6 +1942,30 @@ AGGREGATE_MAX = 1024              # VDF_NOVA_AGGREGATE_MAX
 WIRE_INSTANCE_BYTES = 160         # sizeof(vdf_wire_instance): comm_W | comm_E | u | X[2]
 
 
+def _aggregate_statements(pp, num_steps, z0, zi):
+    """(count, num_steps, z0, zi) as the aggregate's verifiers take them; the shapes are checked here, before any library call"""
+    n = len(num_steps)
+    arity = getattr(pp, "arity", 3)
+    if len(z0) != n or len(zi) != n or any(len(v) != arity for v in list(z0) + list(zi)):
+        raise ValueError(f"z0 and zi need {arity} elements for each of the {n} entries")
+    steps = (_sz * max(n, 1))(*[int(v) for v in num_steps])
+    z0a = _zn([v for e in z0 for v in e] or [bytes(32)])
+    zia = _zn([v for e in zi for v in e] or [bytes(32)])
+    return n, steps, z0a, zia
+
+
+def _wire_instances(instances, comm_TT):
+    """the byte arrays of a fold over plain bytes; the lengths are checked here, before any library call"""
+    n = len(instances)
+    if any(len(b) != WIRE_INSTANCE_BYTES for b in instances) or any(len(b) != 32 for b in comm_TT):
+        raise ValueError("instances are 160 bytes, points and the digest 32")
+    if n and len(comm_TT) != n - 1:
+        raise ValueError("one cross-term commitment per fold")
+    inst = (C.c_uint8 * max(160 * n, 1)).from_buffer_copy(b"".join(instances) or b"\0")
+    tt = (C.c_uint8 * max(32 * len(comm_TT), 1)).from_buffer_copy(b"".join(comm_TT) or b"\0")
+    return n, inst, tt
+
+
 class AggregateProof:
     """Many running proofs under one parameter set as ONE compressed proof ("vdf-aggregate-v1", include/vdf_nova.h)."""
 
@@ -1950,18 +1978,15 @@ class AggregateProof:
     def count(self) -> int:
         return int(nova_lib.vdf_nova_aggregate_count(self.handle))
 
-    def verify(self, pp: NovaVDFPublicParams, num_steps: Sequence[int], z0: Sequence[Sequence[bytes]], zi: Sequence[Sequence[bytes]]):
+    def verify(self, pp: NovaVDFPublicParams, num_steps: Sequence[int], z0: Sequence[Sequence[bytes]], zi: Sequence[Sequence[bytes]],
+               device: bool = False):
         """(ok, bad_entry): one verdict for the whole aggregate; bad_entry = the first entry whose exact checks fail, else -1.
-        num_steps, z0, zi: one per entry (z0[k], zi[k]: `arity` elements)."""
-        n = len(num_steps)
-        arity = getattr(pp, "arity", 3)
-        if len(z0) != n or len(zi) != n or any(len(v) != arity for v in list(z0) + list(zi)):
-            raise ValueError(f"z0 and zi need {arity} elements for each of the {n} entries")
-        steps = (_sz * max(n, 1))(*[int(v) for v in num_steps])
-        z0a = _zn([v for e in z0 for v in e] or [bytes(32)])
-        zia = _zn([v for e in zi for v in e] or [bytes(32)])
+        num_steps, z0, zi: one per entry (z0[k], zi[k]: `arity` elements).  device: the per-entry folds and both accumulators by
+        the GPU (vdf_nova_verify_aggregate_device) instead of host point arithmetic; the same verdict either way."""
+        n, steps, z0a, zia = _aggregate_statements(pp, num_steps, z0, zi)
         ok, bad = C.c_int(0), C.c_int64(-1)
-        _check(nova_lib.vdf_nova_verify_aggregate(self.handle, pp.handle, n, steps, z0a, zia, C.byref(ok), C.byref(bad)))
+        call = nova_lib.vdf_nova_verify_aggregate_device if device else nova_lib.vdf_nova_verify_aggregate
+        _check(call(self.handle, pp.handle, n, steps, z0a, zia, C.byref(ok), C.byref(bad)))
         return bool(ok.value), int(bad.value)
 
     def serialize(self) -> bytes:
@@ -2004,15 +2029,41 @@ def aggregate_fold_instances(field_of_primary: int, side: int, digest: bytes, in
     """The verifier's transcript and folds of one side over plain bytes, on the host alone (vdf_nova_aggregate_fold_instances).
     instances: 160-byte wire instances (comm_W | comm_E | u | X0 | X1); comm_TT: len(instances) - 1 32-byte points.  Returns
     (the folded instance's 160 bytes, the challenges as 32-byte Montgomery elements of the side's field)."""
-    n = len(instances)
-    if any(len(b) != WIRE_INSTANCE_BYTES for b in instances) or any(len(b) != 32 for b in comm_TT) or len(digest) != 32:
+    if len(digest) != 32:
         raise ValueError("instances are 160 bytes, points and the digest 32")
-    if n and len(comm_TT) != n - 1:
-        raise ValueError("one cross-term commitment per fold")
-    inst = (C.c_uint8 * max(160 * n, 1)).from_buffer_copy(b"".join(instances) or b"\0")
-    tt = (C.c_uint8 * max(32 * len(comm_TT), 1)).from_buffer_copy(b"".join(comm_TT) or b"\0")
+    n, inst, tt = _wire_instances(instances, comm_TT)
     dg = (C.c_uint8 * 32).from_buffer_copy(digest)
     acc = (C.c_uint8 * 160)()
     r = (C.c_uint8 * max(32 * (n - 1), 1))()
     _check(nova_lib.vdf_nova_aggregate_fold_instances(field_of_primary, side, dg, n, inst, tt, acc, r))
     return bytes(acc), [bytes(r[32 * k:32 * k + 32]) for k in range(max(n - 1, 0))]
+
+
+def aggregate_fold_instances_device(pp: NovaVDFPublicParams, side: int, instances: Sequence[bytes], comm_TT: Sequence[bytes]):
+    """aggregate_fold_instances with the points decoded and summed on the GPU (vdf_nova_aggregate_fold_instances_device); the
+    orientation and the digest are pp's.  Returns the same (folded instance, challenges), byte for byte."""
+    n, inst, tt = _wire_instances(instances, comm_TT)
+    acc = (C.c_uint8 * 160)()
+    r = (C.c_uint8 * max(32 * (n - 1), 1))()
+    _check(nova_lib.vdf_nova_aggregate_fold_instances_device(pp.handle, side, n, inst, tt, acc, r))
+    return bytes(acc), [bytes(r[32 * k:32 * k + 32]) for k in range(max(n - 1, 0))]
+
+
+def verify_aggregate_wire(pp: NovaVDFPublicParams, data: bytes, num_steps: Sequence[int], z0: Sequence[Sequence[bytes]],
+                          zi: Sequence[Sequence[bytes]]):
+    """A verifier that holds bytes only (vdf_nova_verify_aggregate_wire): "VDFAGG01" in, (ok, bad_entry, decode_code) out.  Every
+    point is decoded on the GPU and the device verifier runs; decode_code is deserialize_aggregate's error code for these bytes
+    (0: they decode), and anything but 0 gives ok = False."""
+    n, steps, z0a, zia = _aggregate_statements(pp, num_steps, z0, zi)
+    buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(bytes(data) or b"\0")
+    ok, bad, code = C.c_int(0), C.c_int64(-1), C.c_int(0)
+    _check(nova_lib.vdf_nova_verify_aggregate_wire(pp.handle, buf, len(data), n, steps, z0a, zia, C.byref(ok), C.byref(bad), C.byref(code)))
+    return bool(ok.value), int(bad.value), int(code.value)
+
+
+def aggregate_verify_times() -> list:
+    """ms of the last device / wire verification on this thread: [exact checks (hashes), secondary folds, accumulators, arguments,
+    decoding] (vdf_nova_aggregate_verify_times)."""
+    ms = (C.c_double * 5)()
+    _check(nova_lib.vdf_nova_aggregate_verify_times(ms))
+    return list(ms)
