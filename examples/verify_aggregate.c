@@ -1,10 +1,13 @@
 /* A verifier of an aggregate that holds bytes only: a file of "VDFAGG01" wire bytes (what examples/aggregate_proofs writes, or
  * AggregateProof.serialize) and a text file of the statements go straight to vdf_nova_verify_aggregate_wire -- every point of the
  * encoding is decoded on the GPU (vdf_points_decompress), the per-entry folds and both accumulators are made there
- * (vdf_points_axpy, vdf_msm_batch), the hashes and the exact checks run on the host.  Plain C, the two C ABIs only.
+ * (vdf_points_axpy, vdf_msm_batch), the hashes and the exact checks run on the host -- or, with the optional fourth argument, the
+ * three Poseidon hashes of every entry on the GPU as well (vdf_ro_hash_batch).  Plain C, the two C ABIs only.
  *
  * Build:  cc -O2 examples/verify_aggregate.c -Iinclude -Lvdf_amd -lvdf_nova -lvdf_hip -Wl,-rpath,'$ORIGIN/../vdf_amd' -o examples/verify_aggregate
- * Run:    examples/verify_aggregate <iterations per step> <aggregate file> <statements file>
+ * Run:    examples/verify_aggregate <iterations per step> <aggregate file> <statements file> [<ro device min count>]
+ *         the optional last argument is vdf_nova_pp_set_verify_ro_device's: from that many entries on the per-entry hashes are
+ *         made on the GPU (0, or no argument: on the host); the line that comes out does not depend on it.
  *         the parameter set is the default one (the reference's inverse MinRoot step circuit, arity 3) at that many iterations
  *         per step.  The statements file has one line per entry, in the aggregate's order:
  *             <num_steps> <z0[0]> <z0[1]> <z0[2]> <zi[0]> <zi[1]> <zi[2]>
@@ -37,7 +40,10 @@ static int hex_fe(const char* s, vdf_fe* out) {
 }
 
 int main(int argc, char** argv) {
-  if (argc != 4) { fprintf(stderr, "usage: verify_aggregate <iterations per step> <aggregate file> <statements file>\n"); return 2; }
+  if (argc != 4 && argc != 5) {
+    fprintf(stderr, "usage: verify_aggregate <iterations per step> <aggregate file> <statements file> [<ro device min count>]\n");
+    return 2;
+  }
   const uint64_t t = strtoull(argv[1], NULL, 10);
   if (t < 1 || t > (1ull << 20)) { fprintf(stderr, "iterations per step in 1..2^20\n"); return 2; }
 
@@ -74,6 +80,7 @@ int main(int argc, char** argv) {
   if (vdf_ctx_create(&device, 1, &ctx) != VDF_OK) { fprintf(stderr, "no GPU: %s\n", vdf_last_error(NULL)); return 1; }
   vdf_pp* pp = NULL;
   CHECK(vdf_nova_public_params(ctx, t, &pp), "public_params");
+  if (argc == 5) CHECK(vdf_nova_pp_set_verify_ro_device(pp, atoi(argv[4])), "pp_set_verify_ro_device");
 
   int ok = 0, decode_code = 0;
   int64_t bad_entry = -1;

@@ -887,6 +887,25 @@ int  vdf_points_decompress(vdf_ctx* ctx, int curve, const uint8_t* enc, size_t n
  * VDF_ERR_BAD_ARG. */
 int  vdf_points_axpy(vdf_ctx* ctx, int curve, const vdf_affine* a, const vdf_affine* b, const vdf_fe* s, int bits, size_t n,
                      vdf_affine* out);
+/* The random oracle of the folding layer on the device (family 0, the default block of vdf_nova.h: Poseidon2 of width 4,
+ * rate 3, x^5, 8 external and 56 internal rounds), one lane per message: the per-entry hashes of a verifier that holds many
+ * statements (vdf_nova_verify_aggregate_device under vdf_nova_pp_set_verify_ro_device).  n messages of `len` elements each,
+ * message-major (xs[i * len + j]), canonical Montgomery form.  rc: the field's VDF_RO_CONSTANTS round constants in Montgomery
+ * form, ext[r][lane] for r = 0..7 (lane-minor) and then in[0..55] -- what vdf_nova_ro_constants writes.  out[i] is
+ * vdf_nova_ro_hash(field, tag, xs + i * len, len): the state starts as (tag + (len << 32), 0, 0, 0), each block of three
+ * elements (the last one possibly short) is added into lanes 1..3 and followed by one permutation, the result is lane 1;
+ * len = 0 permutes nothing and gives 0.  bits = 0 writes that element in Montgomery form; bits in 1..255 writes the low `bits`
+ * bits of its canonical integer as a PLAIN little-endian 256-bit integer (the state hash at 250, the fold challenge at 128);
+ * any other value is VDF_ERR_BAD_ARG, as are an unknown field and len > VDF_RO_HASH_MAX_LEN.  The messages are a peer's: no
+ * loop, branch or address of the kernel depends on them.  Each array in host or device memory (vdf_ptr_is_device), device
+ * arrays 16-byte aligned (otherwise VDF_ERR_BAD_ARG), `out` not overlapping an input.  n = 0 is VDF_OK and touches nothing; a
+ * null pointer with n > 0 is VDF_ERR_BAD_ARG (xs may be null when len = 0).  Only family 0 runs on the device: the dense
+ * width-25 matrix of family 1 does not fit a lane's registers and stays on the host.  vdf_nova_ro_hash_batch_eval is the host
+ * restatement. */
+#define VDF_RO_CONSTANTS  88          /* 8 external rounds x 4 lanes, then 56 internal */
+#define VDF_RO_HASH_MAX_LEN 1024
+int  vdf_ro_hash_batch(vdf_ctx* ctx, int field, uint64_t tag, const vdf_fe* rc, const vdf_fe* xs, size_t len, size_t n, int bits,
+                       vdf_fe* out);
 /* Throughput probe: each of n lanes runs `iters` dependent Montgomery multiplications
  * (roofline / issue-rate calibration for DESIGN.md; not on the prove path). */
 int  vdf_fe_mul_chain(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, int iters, vdf_fe* out);

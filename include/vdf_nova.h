@@ -860,6 +860,14 @@ int  vdf_nova_pp_repeat_lanes(const vdf_pp* pp, uint64_t* lanes);
 /* ---- host-only entry points (no device): what the CPU tests pin against oracle/nova.py ------------------------- */
 /* the random oracle: lane 1 of the sponge after absorbing xs under `tag` (a full field element, Montgomery in and out) */
 int  vdf_nova_ro_hash(int field, uint64_t tag, const vdf_fe* xs, size_t n, vdf_fe* out);
+/* the default block's VDF_RO_CONSTANTS (88) round constants of `field` in Montgomery form, in the order vdf_ro_hash_batch
+ * (vdf_hip.h) reads them: ext[r][lane] for r = 0..7, lane-minor, then in[0..55].  Pure: callable without a GPU. */
+int  vdf_nova_ro_constants(int field, vdf_fe out[VDF_RO_CONSTANTS]);
+/* the host restatement of vdf_ro_hash_batch, and the reference its tests compare with byte for byte: out[i] =
+ * vdf_nova_ro_hash(field, tag, xs + i * len, len) for bits = 0, the low `bits` bits of its canonical integer as a plain
+ * little-endian integer for bits in 1..255.  The same refusals: an unknown field, any other `bits`, len > VDF_RO_HASH_MAX_LEN,
+ * a null pointer with n > 0 (xs may be null when len = 0): VDF_ERR_BAD_ARG.  n = 0 is VDF_OK and touches nothing. */
+int  vdf_nova_ro_hash_batch_eval(int field, uint64_t tag, const vdf_fe* xs, size_t len, size_t n, int bits, vdf_fe* out);
 /* digest of the parameters public_params would make (both shapes synthesised on the host), and the sizes per side:
  * sizes[side] = {num_cons, num_vars, nnz(A) + nnz(B) + nnz(C)} */
 int  vdf_nova_shape_digest(uint64_t num_iters_per_step, int circuit_kind, int gens_family, uint8_t out[32], uint64_t sizes[2][3]);
@@ -1142,8 +1150,8 @@ int  vdf_nova_aggregate_fold_instances(int field_of_primary, int side, const uin
  * depends on a folded accumulator and a side's sequential folds are two sums,
  *     comm_W = W_1 + sum_{k>=2} r_k W_k        comm_E = E_1 + sum_{k>=2} (r_k^2 E_k + r_k commit(TT_k)),
  * one vdf_msm_batch over the 3 count - 1 uploaded points; the count secondary folds F2_k = r_U2_k + rho_k l_u2_k are one
- * vdf_points_axpy (vdf_hip.h) of 2 count entries.  Transcripts, challenges, the Poseidon hashes, the exact per-entry checks and
- * the folds of u and X stay on the host.  The three calls below are held, byte for byte and code for code, to the host calls
+ * vdf_points_axpy (vdf_hip.h) of 2 count entries.  Transcripts, challenges, the exact per-entry checks and the folds of u and X
+ * stay on the host, and so do the Poseidon hashes unless vdf_nova_pp_set_verify_ro_device moves them (below).  The three calls below are held, byte for byte and code for code, to the host calls
  * above, which stay the statement; they run on the parameter set's context and leave its asynchronous flag and stream as they
  * found them, whatever they return.
  *
@@ -1160,7 +1168,18 @@ int  vdf_nova_aggregate_fold_instances(int field_of_primary, int side, const uin
  *   pp, bytes, ok or decode_code: VDF_ERR_BAD_ARG.
  * vdf_nova_aggregate_verify_times: what the last of the two verifiers above spent on this thread, host wall time in ms:
  *   [0] the exact checks (three Poseidon hashes per entry), [1] the secondary folds, [2] both accumulators, [3] both arguments,
- *   [4] the decoding (the wire call only).  For tools/gpu_aggregate_verify.py. */
+ *   [4] the decoding (the wire call only).  For tools/gpu_aggregate_verify.py.  [0] means "exact checks and hashes" whoever
+ *   computed the hashes (see below).
+ * vdf_nova_pp_set_verify_ro_device: where vdf_nova_verify_aggregate_device (and with it vdf_nova_verify_aggregate_wire) makes the
+ *   three Poseidon hashes of every entry -- both state hashes and the fold challenge.  min_count = 0 (the default): on the host,
+ *   one entry after the other.  min_count > 0: for an aggregate of at least min_count entries a host pass packs the messages,
+ *   three vdf_ro_hash_batch launches (vdf_hip.h; bits = 250, 250, 128) and one wait follow, and the comparisons run on the host
+ *   in entry order.  *ok and *bad_entry are the same for EVERY input: the first failing entry is named, whichever check it
+ *   fails.  A negative value: VDF_ERR_BAD_ARG.  The device oracle is family 0 only: a parameter set made under another RO
+ *   parameter block accepts the switch and keeps the host hashes.  The set keeps one device copy of each field's 88 round
+ *   constants, made on first use and freed with it.  vdf_nova_verify_aggregate, the maker and the batch verifiers do not read
+ *   the switch.  vdf_nova_pp_verify_ro_device reads it back (0 for a null pp); vdf_nova_pp_verify_ro_stats: out[0] = hashes made
+ *   on the device under this set, out[1] = launches. */
 int  vdf_nova_aggregate_fold_instances_device(vdf_pp* pp, int side, size_t count, const vdf_wire_instance inst[],
                                               const uint8_t comm_TT[][32], vdf_wire_instance* acc, vdf_fe r_out[]);
 int  vdf_nova_verify_aggregate_device(const vdf_aggregate* agg, vdf_pp* pp, size_t count, const size_t num_steps[],
@@ -1168,6 +1187,9 @@ int  vdf_nova_verify_aggregate_device(const vdf_aggregate* agg, vdf_pp* pp, size
 int  vdf_nova_verify_aggregate_wire(vdf_pp* pp, const uint8_t* bytes, size_t len, size_t count, const size_t num_steps[],
                                     const vdf_fe* z0, const vdf_fe* zi, int* ok, int64_t* bad_entry, int* decode_code);
 int  vdf_nova_aggregate_verify_times(double ms[5]);
+int  vdf_nova_pp_set_verify_ro_device(vdf_pp* pp, int min_count);
+int  vdf_nova_pp_verify_ro_device(const vdf_pp* pp);
+int  vdf_nova_pp_verify_ro_stats(const vdf_pp* pp, uint64_t out[2]);
 size_t vdf_nova_proof_serialized_size(const vdf_proof* proof);
 int  vdf_nova_proof_serialize(const vdf_proof* proof, uint8_t* out, size_t cap);
 int  vdf_nova_proof_deserialize(vdf_pp* pp, const uint8_t* in, size_t len, vdf_proof** out);

@@ -9,7 +9,13 @@ accumulators, both arguments) beside the kernel events (KTimer) of k_points_deco
 launch of one more call; and k_points_axpy alone at n = 2 K for both scalar lengths.
 THE RULE: "faster at K" is claimed only where the device way's slowest repeat is below the host way's fastest; the K where it is
 not are listed as such.  Every K runs under a time limit of its own (--step-timeout, a watchdog that ends the process).
-usage: python tools/gpu_aggregate_verify.py [--lg 16] [--ks 1,2,16,128,1024] [--proofs 4] [--repeats 5] [--step-timeout 240] [--out FILE]"""
+--ro-device: the other comparison, same K set and method -- the device way with its per-entry Poseidon hashes on the host
+(vdf_nova_pp_set_verify_ro_device at 0) against the same call with the switch at 1 (three vdf_ro_hash_batch launches), taking
+turns repeat by repeat; per K both wall times, both ways' parts, k_ro_hash by events (one more call, and alone at n = K for the
+three message lengths of an aggregate), and the rule with "switch at 1" in the place of the device way and "switch at 0" in
+the place of the host way.  The smallest K of an unbroken run of "yes" up to the largest K is the min_count to recommend.
+usage: python tools/gpu_aggregate_verify.py [--lg 16] [--ks 1,2,16,128,1024] [--proofs 4] [--repeats 5] [--step-timeout 240] [--out FILE]
+                                            [--ro-device]"""
 import argparse
 import os
 import signal
@@ -31,6 +37,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ro-device", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -39,7 +46,7 @@ def main():
     from vdf_amd import _lib
     from vdf_amd.minroot import EvalMode, PallasVDF, State, FIELD_FQ
     from vdf_amd.nova import (InverseMinRootCircuit, NovaVDFProof, aggregate_verify_times, compress_aggregate, deserialize_aggregate, public_params,
-                              verify_aggregate_wire)
+                              ro_constants, verify_aggregate_wire)
     lines = []
 
     def say(s=""):
@@ -73,6 +80,63 @@ def main():
     say(f"t = 2^{a.lg}, {a.proofs} distinct proofs named cyclically, {a.repeats} alternating repeats in one process; ms as median [min .. max]")
     fmt = lambda v: "%9.2f [%9.2f .. %9.2f]" % (statistics.median(v), min(v), max(v))
     faster, not_faster = [], []
+    PARTS = ("exact checks and hashes", "secondary folds", "both accumulators", "both arguments", "decoding")
+
+    def ro_device_at(K, data, stmt):
+        ways = (("switch at 0", 0), ("switch at 1", 1))
+        for _, sw in ways:                                 # warm both ways (the second makes the constants' device copies)
+            pp.set_verify_ro_device(sw)
+            if verify_aggregate_wire(pp, data, *stmt) != (True, -1, 0):
+                sys.exit(f"K = {K}: the aggregate does not verify")
+        tm = {name: [] for name, _ in ways}
+        parts = {name: [] for name, _ in ways}
+        for _ in range(a.repeats):
+            for name, sw in ways:
+                pp.set_verify_ro_device(sw)
+                ctx.sync(); t0 = time.perf_counter()
+                wired = verify_aggregate_wire(pp, data, *stmt); ctx.sync()
+                tm[name].append(1e3 * (time.perf_counter() - t0))
+                parts[name].append(aggregate_verify_times())
+                if wired != (True, -1, 0):
+                    sys.exit(f"K = {K}: the aggregate does not verify")
+        say(f"K = {K:4d}   {len(data)} bytes")
+        for name, v in tm.items():
+            say(f"   device way, {name} ms {fmt(v)}   per entry {statistics.median(v) / K:8.3f}")
+        ok = max(tm["switch at 1"]) < min(tm["switch at 0"])
+        (faster if ok else not_faster).append(K)
+        say(f"   switch at 1 faster by the rule (its slowest repeat below the fastest with the switch at 0): {'yes' if ok else 'NO'}")
+        for name, _ in ways:
+            for j, part in enumerate(PARTS):
+                say(f"   {name}, {part:24s} ms {fmt([p[j] for p in parts[name]])}")
+        pp.set_verify_ro_device(1)                         # one more call with the library's events around its launches
+        before = pp.verify_ro_stats()
+        ctx.set_kernel_timing(True)
+        ctx.kernel_events()
+        verify_aggregate_wire(pp, data, *stmt)
+        ctx.sync()
+        ev = ctx.kernel_events()
+        ctx.set_kernel_timing(False)
+        after = pp.verify_ro_stats()
+        pp.set_verify_ro_device(0)
+        ms = [e1 - e0 for kn, _, e0, e1 in ev if kn == "k_ro_hash"]
+        say(f"   events: k_ro_hash {len(ms):3d} launches, {sum(ms):9.3f} ms ({', '.join('%.3f' % v for v in ms)});"
+            f" stats: {after[0] - before[0]} hashes in {after[1] - before[1]} launches")
+        rng = np.random.default_rng(K)                     # the kernel alone at n = K, device arrays, the aggregate's three lengths
+        rc = torch.from_numpy(ro_constants(FIELD_FQ).view(np.int64)).cuda()
+        out = torch.zeros((K, 4), dtype=torch.int64, device="cuda")
+        for ln, bits in ((17, 250), (13, 250), (16, 128)):
+            xs = rng.integers(0, 2**62, size=(K * ln, 4), dtype=np.int64)
+            xs[:, 3] &= 0x3FFFFFFFFFFFFFFF
+            dxs = torch.from_numpy(xs).cuda()
+            ctx.set_kernel_timing(True)
+            ctx.kernel_events()
+            for _ in range(a.repeats + 1):
+                ctx.ro_hash_batch(FIELD_FQ, 1, rc, dxs, ln, K, bits, out)
+            ctx.sync()
+            us = [1e3 * (e1 - e0) for kn, _, e0, e1 in ctx.kernel_events() if kn == "k_ro_hash"][1:]
+            ctx.set_kernel_timing(False)
+            say(f"   k_ro_hash alone, n = {K:4d}, len = {ln:2d}, bits = {bits:3d}: us {statistics.median(us):9.1f} [{min(us):9.1f} .. {max(us):9.1f}]")
+
     for K in ks:
         signal.alarm(a.step_timeout)
         its = [items[k % a.proofs] for k in range(K)]
@@ -82,6 +146,11 @@ def main():
         agg.free()
         if deserialize_aggregate(pp, data).verify(pp, *stmt) != (True, -1) or verify_aggregate_wire(pp, data, *stmt) != (True, -1, 0):   # warm both ways
             sys.exit(f"K = {K}: the aggregate does not verify")
+        if a.ro_device:
+            ro_device_at(K, data, stmt)
+            signal.alarm(0)
+            save()
+            continue
         tm = {"host way": [], "device way": []}
         parts = []
         for _ in range(a.repeats):
@@ -134,8 +203,11 @@ def main():
             say(f"   k_points_axpy alone, n = {n:4d}, bits = {bits:3d}: us {statistics.median(us):9.1f} [{min(us):9.1f} .. {max(us):9.1f}]")
         signal.alarm(0)
         save()
-    say(f"device way faster by the rule at K in {faster}; not faster at K in {not_faster}")
-    for sym, vgpr, agpr, lds, scratch in kernel_figures(_lib.lib._name, "k_points_axpy"):
+    if a.ro_device:
+        say(f"switch at 1 faster by the rule at K in {faster}; not faster at K in {not_faster}")
+    else:
+        say(f"device way faster by the rule at K in {faster}; not faster at K in {not_faster}")
+    for sym, vgpr, agpr, lds, scratch in kernel_figures(_lib.lib._name, "k_ro_hash" if a.ro_device else "k_points_axpy"):
         say(f"{sym}: {vgpr} VGPRs, {agpr} AGPRs, {lds} B LDS, {scratch} B scratch")
     save()
 

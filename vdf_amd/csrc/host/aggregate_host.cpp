@@ -214,6 +214,22 @@ struct SideFold {
   }
 };
 
+// the context's asynchronous flag set for a scope and put back, with a wait, on every way out
+struct AsyncScope {
+  vdf_ctx* c;
+  int was = 0;
+  bool armed = false;
+  explicit AsyncScope(vdf_ctx* ctx) : c(ctx) {}
+  int enter() {
+    HIPCALL(c, vdf_ctx_get_async(c, &was));
+    HIPCALL(c, vdf_ctx_sync(c));
+    HIPCALL(c, vdf_ctx_set_async(c, 1));
+    armed = true;
+    return VDF_OK;
+  }
+  ~AsyncScope() { if (armed) { vdf_ctx_sync(c); vdf_ctx_set_async(c, was); } }
+};
+
 // The exact checks of every entry (as vdf_nova_verify_compressed makes them) and the Poseidon challenge of the verifier's own
 // secondary fold: passed(k, statement, r) receives each entry that holds, in order.  Returns the first entry that fails, -1 when none
 // does.  Both verifiers (host folds, device folds) run this and nothing else per entry.
@@ -241,6 +257,98 @@ int64_t exact_checks(const vdf_aggregate* agg, const vdf_pp* pp, size_t count, c
     passed(k, s, r);
   }
   return -1;
+}
+
+// The device copy of a field's 88 round constants (vdf_nova_ro_constants' order), made on first use and freed with the set.
+int ro_constants_on_device(vdf_pp* pp, int field_id, const void** out) {
+  std::lock_guard<std::mutex> lock(pp->ro_mu);
+  void*& d = pp->d_ro_rc[field_id];
+  if (!d) {
+    void* p = nullptr;
+    HIPCALL(pp->ctx, vdf_dev_alloc(pp->ctx, VDF_RO_CONSTANTS * sizeof(Fe), &p));
+    const int rc = vdf_dev_memcpy(pp->ctx, p, ro_constants(field_id).ext, VDF_RO_CONSTANTS * sizeof(Fe));
+    if (rc != VDF_OK) { vdf_dev_free(pp->ctx, p); return fail(rc, std::string("vdf_dev_memcpy (round constants): ") + vdf_last_error(pp->ctx)); }
+    d = p;
+  }
+  *out = d;
+  return VDF_OK;
+}
+static_assert(offsetof(RoConstants, in) == RO_RF * RO_T * sizeof(Fe) && RO_RF * RO_T + RO_RP == VDF_RO_CONSTANTS,
+              "RoConstants begins with the 88 constants in the order vdf_ro_hash_batch reads them");
+
+// exact_checks with the three Poseidon hashes of every entry made by vdf_ro_hash_batch (the default block only): a host pass
+// packs the messages of hash_state (both sides) and hash_challenge into one pinned block the kernel reads in place, three
+// launches and one wait follow, and the comparisons run on the host in entry order.  *first_bad is exact_checks' value for
+// every input: the entries in front of the first structural failure are hashed and compared, so an earlier mismatch wins.
+template <class Passed>
+int exact_checks_ro_device(const vdf_aggregate* agg, vdf_pp* pp, size_t count, const size_t num_steps[], const vdf_fe* z0, const vdf_fe* zi,
+                           int64_t* first_bad, Passed&& passed) {
+  const Side& S1 = pp->s[PRIMARY];
+  const Side& S2 = pp->s[SECONDARY];
+  const Field& F1 = *S1.F;
+  const Field& F2 = *S2.F;
+  const size_t ar = pp->arity;
+  vdf_ctx* ctx = pp->ctx;
+  *first_bad = -1;
+  size_t live = count;                                     // the entries in front of the first structural failure
+  for (size_t k = 0; k < count; ++k)
+    if (agg->st[k].zi1.size() != ar) { live = k; *first_bad = (int64_t)k; break; }
+  if (live == 0) return VDF_OK;
+  const size_t len1 = 2 + 2 * ar + 9, len2 = 13, len3 = 16;
+  void* blk = nullptr;
+  HIPCALL(ctx, vdf_host_alloc(ctx, live * (len1 + len2 + len3 + 3) * sizeof(Fe), &blk));
+  struct Free { vdf_ctx* c; void* p; ~Free() { vdf_host_free(c, p); } } free_blk{ctx, blk};
+  Fe* m1 = static_cast<Fe*>(blk);
+  Fe* m2 = m1 + live * len1;
+  Fe* m3 = m2 + live * len2;
+  Fe* h1 = m3 + live * len3;                               // plain integers: 250, 250 and 128 bits
+  Fe* h2 = h1 + live;
+  Fe* h3 = h2 + live;
+  for (size_t k = 0; k < live; ++k) {
+    const vdf_aggregate::Statement& s = agg->st[k];
+    const RelaxedInst U2 = to_relaxed(s.r_U2, F2), U1 = to_relaxed(s.r_U1, F1);
+    Fe* x = m1 + k * len1;                                 // hash_state over S1.field: params, i, z0, zi, the running secondary instance
+    x[0] = pp->params[PRIMARY];
+    x[1] = from_u64(num_steps[k], F1);
+    memcpy(x + 2, (const Fe*)z0 + k * ar, ar * sizeof(Fe));
+    memcpy(x + 2 + ar, s.zi1.data(), ar * sizeof(Fe));
+    relaxed_elements(U2, F1, x + 2 + 2 * ar);
+    x = m2 + k * len2;                                     // hash_state over S2.field: z0 = (0), zi = (zi2), the running primary instance
+    x[0] = pp->params[SECONDARY];
+    x[1] = from_u64(num_steps[k], F2);
+    x[2] = zero();
+    x[3] = s.zi2;
+    relaxed_elements(U1, F2, x + 4);
+    x = m3 + k * len3;                                     // hash_challenge over S1.field (fold_challenge)
+    x[0] = pp->params[PRIMARY];
+    relaxed_elements(U2, F1, x + 1);
+    x[10] = s.l_u2.comm_W.x; x[11] = s.l_u2.comm_W.y;
+    for (int j = 0; j < 2; ++j) { uint64_t ux[4]; fe_to_int(s.l_u2.X[j], F2, ux); x[12 + j] = int_to_fe(ux, F1); }
+    x[14] = s.T2.x; x[15] = s.T2.y;
+  }
+  const void *rc1 = nullptr, *rc2 = nullptr;
+  { int rc = ro_constants_on_device(pp, S1.field, &rc1); if (rc != VDF_OK) return rc; }
+  { int rc = ro_constants_on_device(pp, S2.field, &rc2); if (rc != VDF_OK) return rc; }
+  {
+    AsyncScope scope(ctx);
+    { int rc = scope.enter(); if (rc != VDF_OK) return rc; }
+    HIPCALL(ctx, vdf_ro_hash_batch(ctx, S1.field, TAG_STATE, (const vdf_fe*)rc1, (const vdf_fe*)m1, len1, live, HASH_BITS, (vdf_fe*)h1));
+    HIPCALL(ctx, vdf_ro_hash_batch(ctx, S2.field, TAG_STATE, (const vdf_fe*)rc2, (const vdf_fe*)m2, len2, live, HASH_BITS, (vdf_fe*)h2));
+    HIPCALL(ctx, vdf_ro_hash_batch(ctx, S1.field, TAG_CHAL, (const vdf_fe*)rc1, (const vdf_fe*)m3, len3, live, CHAL_BITS, (vdf_fe*)h3));
+    HIPCALL(ctx, vdf_ctx_sync(ctx));
+  }
+  pp->verify_ro_stats[0] += 3 * live;
+  pp->verify_ro_stats[1] += 3;
+  for (size_t k = 0; k < live; ++k) {
+    const vdf_aggregate::Statement& s = agg->st[k];
+    if (int_to_fe(h1[k].l, F2) != s.l_u2.X[0] || int_to_fe(h2[k].l, F2) != s.l_u2.X[1] ||
+        memcmp(s.zi1.data(), (const Fe*)zi + k * ar, 32 * ar) != 0 || !s.zi2.is_zero()) {
+      *first_bad = (int64_t)k;
+      return VDF_OK;
+    }
+    passed(k, s, h3[k].l);
+  }
+  return VDF_OK;
 }
 
 // Both arguments against the two accumulators (the unchanged spartan_replay / ipa_check_one): *ok = 1 when they hold.  The
@@ -342,22 +450,6 @@ struct DecodeBlock {
 
 // what the last device verification of this thread spent where, in ms (vdf_nova_aggregate_verify_times)
 thread_local double g_verify_ms[5] = {0, 0, 0, 0, 0};
-
-// the context's asynchronous flag set for a scope and put back, with a wait, on every way out
-struct AsyncScope {
-  vdf_ctx* c;
-  int was = 0;
-  bool armed = false;
-  explicit AsyncScope(vdf_ctx* ctx) : c(ctx) {}
-  int enter() {
-    HIPCALL(c, vdf_ctx_get_async(c, &was));
-    HIPCALL(c, vdf_ctx_sync(c));
-    HIPCALL(c, vdf_ctx_set_async(c, 1));
-    armed = true;
-    return VDF_OK;
-  }
-  ~AsyncScope() { if (armed) { vdf_ctx_sync(c); vdf_ctx_set_async(c, was); } }
-};
 
 }  // namespace
 
@@ -606,7 +698,7 @@ int vdf_nova_verify_aggregate_device(const vdf_aggregate* agg, vdf_pp* pp, size_
     std::vector<Inst> i1(count), i2(count);
     std::vector<Aff> fa(2 * count), fb(2 * count), fo(2 * count);          // [comm_W of every entry | comm_E of every entry]
     std::vector<Fe> rho(2 * count);
-    const int64_t first_bad = exact_checks(agg, pp, count, num_steps, z0, zi, [&](size_t k, const vdf_aggregate::Statement& s, const uint64_t r[4]) {
+    auto passed = [&](size_t k, const vdf_aggregate::Statement& s, const uint64_t r[4]) {
       i1[k] = s.r_U1;
       const Fe rf = int_to_fe(r, F2);
       i2[k].u = add(s.r_U2.u, rf, F2);
@@ -615,7 +707,16 @@ int vdf_nova_verify_aggregate_device(const vdf_aggregate* agg, vdf_pp* pp, size_
       fa[count + k] = s.r_U2.comm_E; fb[count + k] = s.T2;
       memcpy(rho[k].l, r, 32);
       rho[count + k] = rho[k];
-    });
+    };
+    // the three Poseidon hashes of every entry: on the host, or by vdf_ro_hash_batch (vdf_nova_pp_set_verify_ro_device)
+    const int ro_min = pp->verify_ro_device.load();
+    int64_t first_bad = -1;
+    if (ro_min > 0 && count >= (size_t)ro_min && pp->ro->is_default) {
+      int rc = exact_checks_ro_device(agg, pp, count, num_steps, z0, zi, &first_bad, passed);
+      if (rc != VDF_OK) return rc;
+    } else {
+      first_bad = exact_checks(agg, pp, count, num_steps, z0, zi, passed);
+    }
     g_verify_ms[0] = now_ms() - t0;
     if (first_bad >= 0) return bad((size_t)first_bad);
     if (agg->TT[0].size() != count - 1 || agg->TT[1].size() != count - 1) return VDF_OK;
@@ -640,6 +741,19 @@ int vdf_nova_verify_aggregate_device(const vdf_aggregate* agg, vdf_pp* pp, size_
     g_verify_ms[3] = now_ms() - t0;
     return rc;
   });
+}
+
+int vdf_nova_pp_set_verify_ro_device(vdf_pp* pp, int min_count) {
+  if (!pp) return fail(VDF_ERR_BAD_ARG, "null argument");
+  if (min_count < 0) return fail(VDF_ERR_BAD_ARG, "min_count must be 0 (never) or a positive count");
+  pp->verify_ro_device.store(min_count);
+  return VDF_OK;
+}
+int vdf_nova_pp_verify_ro_device(const vdf_pp* pp) { return pp ? pp->verify_ro_device.load() : 0; }
+int vdf_nova_pp_verify_ro_stats(const vdf_pp* pp, uint64_t out[2]) {
+  if (!pp || !out) return fail(VDF_ERR_BAD_ARG, "null argument");
+  for (int k = 0; k < 2; ++k) out[k] = pp->verify_ro_stats[k].load();
+  return VDF_OK;
 }
 
 int vdf_nova_aggregate_verify_times(double ms[5]) {

@@ -508,6 +508,38 @@ int vdf_nova_ro_hash_ro(const vdf_nova_ro_params* rop, int f, uint64_t tag, cons
   });
 }
 int vdf_nova_ro_hash(int f, uint64_t tag, const vdf_fe* xs, size_t n, vdf_fe* out) { return vdf_nova_ro_hash_ro(nullptr, f, tag, xs, n, out); }
+static_assert(offsetof(RoConstants, in) == RO_RF * RO_T * sizeof(Fe) && RO_RF * RO_T + RO_RP == VDF_RO_CONSTANTS,
+              "RoConstants begins with the 88 constants in the order of vdf_nova_ro_constants");
+int vdf_nova_ro_constants(int f, vdf_fe out[VDF_RO_CONSTANTS]) {
+  return nova_guard([&]() -> int {
+    if (!valid_field(f) || !out) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    memcpy(out, ro_constants(f).ext, VDF_RO_CONSTANTS * sizeof(Fe));
+    return VDF_OK;
+  });
+}
+// the host restatement of vdf_ro_hash_batch (vdf_hip.h): the same refusals in the same order, ro_hash per message
+int vdf_nova_ro_hash_batch_eval(int f, uint64_t tag, const vdf_fe* xs, size_t len, size_t n, int bits, vdf_fe* out) {
+  return nova_guard([&]() -> int {
+    if (!valid_field(f)) return fail(VDF_ERR_BAD_ARG, "unknown field");
+    if (bits < 0 || bits > 255) return fail(VDF_ERR_BAD_ARG, "bits must be 0 (the element) or 1..255");
+    if (len > VDF_RO_HASH_MAX_LEN) return fail(VDF_ERR_BAD_ARG, "at most VDF_RO_HASH_MAX_LEN elements per message");
+    if (n == 0) return VDF_OK;
+    if (!out || (!xs && len)) return fail(VDF_ERR_BAD_ARG, "null argument");
+    const Field& F = field(f);
+    for (size_t i = 0; i < n; ++i) {
+      const Fe h = ro_hash(f, tag, (const Fe*)xs + i * len, len);
+      if (bits == 0) { memcpy(&out[i], &h, 32); continue; }
+      uint64_t v[4];
+      fe_to_int(h, F, v);
+      for (int j = 0; j < 4; ++j) {                        // the canonical integer mod 2^bits
+        const int keep = bits - 64 * j;
+        if (keep < 64) v[j] = keep > 0 ? v[j] & ((1ull << keep) - 1) : 0;
+      }
+      memcpy(&out[i], v, 32);
+    }
+    return VDF_OK;
+  });
+}
 
 // One general form per entry point, in either orientation; the entry points of before are these at VDF_FIELD_FQ.
 // kind / lanes as the ABI gives them: only VDF_CIRCUIT_MINROOT_FORWARD_LANES takes a lane count other than 1
@@ -1269,6 +1301,7 @@ void vdf_nova_pp_free(vdf_pp* pp) {
   for (auto& a : pp->arena) if (a.p) vdf_dev_free(pp->ctx, a.p);
   if (pp->seg_gens) vdf_bases_free(pp->seg_gens);
   if (pp->d_round_table) vdf_dev_free(pp->ctx, pp->d_round_table);
+  for (void* p : pp->d_ro_rc) if (p) vdf_dev_free(pp->ctx, p);
   for (Side& sd : pp->s) {
     if (sd.d_zero) vdf_dev_free(pp->ctx, sd.d_zero);
     if (sd.shape) vdf_shape_free(sd.shape);

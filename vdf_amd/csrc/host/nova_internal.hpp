@@ -147,6 +147,12 @@ struct vdf_pp {
   // shape of at most n points each (vdf_nova_pp_set_verify_multi; initial value: VDF_NOVA_VERIFY_MULTI, else verify_multi_default)
   std::atomic<int> verify_multi{0};
   std::atomic<uint64_t> verify_multi_stats[3] = {{0}, {0}, {0}};      // launches, points evaluated, points whose comparison failed
+  // vdf_nova_verify_aggregate_device: 0 = an aggregate's per-entry Poseidon hashes are made on the host; n > 0: by three
+  // vdf_ro_hash_batch launches when the aggregate holds at least n entries (vdf_nova_pp_set_verify_ro_device; the default block only)
+  std::atomic<int> verify_ro_device{0};
+  std::atomic<uint64_t> verify_ro_stats[2] = {{0}, {0}};               // hashes made on the device, launches
+  void* d_ro_rc[2] = {nullptr, nullptr};   // each field's 88 round constants on the device (index: VDF_FIELD_*), made on first use under ro_mu
+  std::mutex ro_mu;
   double setup_ms[7] = {0, 0, 0, 0, 0, 0, 0};
   uint64_t digit_table_bytes[2] = {0, 0};  // HBM held by each side's digit table (vdf_nova_pp_memory)
   unsigned digit_tables_skipped = 0;       // bit s: side s asked for a digit table and went without (no room, refused window)

@@ -399,6 +399,8 @@ Status vec_unsat_rows(int field, const void* a, const void* b, const void* c, si
 Status vec_to_mont(int field, const void* a, size_t n, void* out, hipStream_t s);
 Status vec_from_mont(int field, const void* a, size_t n, void* out, hipStream_t s);
 Status vec_mul_chain(int field, const void* a, size_t n, int iters, void* out, hipStream_t s);
+// out[i] = the family-0 random oracle of message i (n messages of len elements, message-major); rc: the 88 round constants
+Status ro_hash_batch(int field, uint64_t tag, const void* d_rc, const void* d_xs, size_t len, size_t n, int bits, void* d_out, hipStream_t s);
 Status vec_clock_probe(int iters, int workgroups, unsigned long long* d_out3, hipStream_t s);   // d_out3 zeroed by the caller
 
 // ---- minroot.hip -----------------------------------------------------------------------

@@ -1410,4 +1410,101 @@ Status vec_fold_relaxed(int field, const vdf_fe* r, size_t n, void* az1, void* b
   });
 }
 
+// ---- the random oracle, family 0 (vdf_ro_hash_batch) ----------------------------------------------------------------------------
+// host/r1cs.cpp ro_hash / ro_permute restated one message per lane: width 4, rate 3, x^5, 8 external and 56 internal rounds.
+// The state is four NAMED elements (a run-time lane index would put it in scratch); every value between two S-boxes is
+// canonical (fe_add), and inside an S-box the three products are lazy: x < m gives x^2 < 2m + eps, x^4 < 2m + 2 eps,
+// x^5 < 2m + 3 eps < 3m (fe.cuh, "lazy domain"), which fe_canon's two conditional subtractions bring below m.
+template <class P> __device__ __forceinline__ Fe<P> ro_sbox(const Fe<P>& x) {
+  const Fe<P> x2 = fe_sqr_lazy(x);
+  const Fe<P> x4 = fe_sqr_lazy(x2);
+  return fe_canon(fe_mul_lazy(x4, x));
+}
+// M4 = [[5,7,1,3],[4,6,1,1],[1,3,5,7],[1,1,4,6]] with 14 additions (ext_layer)
+template <class P> __device__ __forceinline__ void ro_ext_layer(Fe<P>& a, Fe<P>& b, Fe<P>& c, Fe<P>& d) {
+  const Fe<P> t0 = fe_add(a, b), t1 = fe_add(c, d);
+  const Fe<P> t2 = fe_add(fe_dbl(b), t1), t3 = fe_add(fe_dbl(d), t0);
+  const Fe<P> t4 = fe_add(fe_dbl(fe_dbl(t1)), t3), t5 = fe_add(fe_dbl(fe_dbl(t0)), t2);
+  a = fe_add(t3, t5); b = t5; c = fe_add(t2, t4); d = t4;
+}
+// ones off the diagonal, (2, 3, 6, 8) on it: s_i <- sum + (1, 2, 5, 7)_i s_i (int_layer); no products
+template <class P> __device__ __forceinline__ void ro_int_layer(Fe<P>& a, Fe<P>& b, Fe<P>& c, Fe<P>& d) {
+  const Fe<P> tot = fe_add(fe_add(a, b), fe_add(c, d));
+  const Fe<P> c4 = fe_dbl(fe_dbl(c)), d8 = fe_dbl(fe_dbl(fe_dbl(d)));
+  a = fe_add(tot, a);
+  b = fe_add(tot, fe_dbl(b));
+  c = fe_add(tot, fe_add(c4, c));
+  d = fe_add(tot, fe_sub(d8, d));
+}
+// rc: VDF_RO_CONSTANTS elements, ext[r][lane] for r = 0..7 and then in[0..55].  The index of every constant is the loop counter,
+// the same in every lane, so the constants travel through scalar loads.  The rounds are three loops (4 + 56 + 4) in one outer
+// loop of two trips, so that the external round's four S-boxes exist once in the code.
+template <class P> __device__ __forceinline__ void ro_permute_dev(Fe<P>& a, Fe<P>& b, Fe<P>& c, Fe<P>& d, const char* __restrict__ rc) {
+  ro_ext_layer(a, b, c, d);
+#pragma unroll 1
+  for (int half = 0; half < 2; ++half) {
+#pragma unroll 1
+    for (int r = 0; r < 4; ++r) {
+      const char* k = rc + (size_t)(half * 4 + r) * 128;
+      a = ro_sbox(fe_add(a, fe_load<P>(k)));
+      b = ro_sbox(fe_add(b, fe_load<P>(k + 32)));
+      c = ro_sbox(fe_add(c, fe_load<P>(k + 64)));
+      d = ro_sbox(fe_add(d, fe_load<P>(k + 96)));
+      ro_ext_layer(a, b, c, d);
+    }
+    if (half == 0) {
+#pragma unroll 1
+      for (int r = 0; r < 56; ++r) {
+        a = ro_sbox(fe_add(a, fe_load<P>(rc + (size_t)(32 + r) * 32)));
+        ro_int_layer(a, b, c, d);
+      }
+    }
+  }
+}
+// out[i] = ro_hash(tag, xs + i len, len): lane 0 starts as s0 = tag + (len << 32) in Montgomery form (made by the launcher),
+// each block of three elements is added into lanes 1..3 and followed by one permutation, the result is lane 1.  len, bits and
+// every constant index are wave-uniform: no loop, branch or address depends on a message.  bits = 0 stores the Montgomery
+// form; otherwise the canonical integer's low `bits` bits as a plain integer.
+template <class P>
+__global__ __launch_bounds__(256) void k_ro_hash(const char* __restrict__ rc, const char* __restrict__ xs, uint32_t len, uint32_t n,
+                                                 FeVal s0, int bits, char* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  Fe<P> a = fe_from_val<P>(s0), b = fe_zero<P>(), c = fe_zero<P>(), d = fe_zero<P>();
+  const char* x = xs + (size_t)i * len * 32;
+#pragma unroll 1
+  for (uint32_t k = 0; k < len; k += 3) {
+    b = fe_add(b, fe_load<P>(x + (size_t)k * 32));
+    if (k + 1 < len) c = fe_add(c, fe_load<P>(x + (size_t)(k + 1) * 32));
+    if (k + 2 < len) d = fe_add(d, fe_load<P>(x + (size_t)(k + 2) * 32));
+    ro_permute_dev(a, b, c, d, rc);
+  }
+  if (bits != 0) {
+    b = fe_from_mont(b);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int keep = bits - 32 * j;
+      b.v[j] &= keep >= 32 ? 0xFFFFFFFFu : (keep <= 0 ? 0u : (1u << keep) - 1u);
+    }
+  }
+  fe_store<P>(out + (size_t)i * 32, b);
+}
+
+Status ro_hash_batch(int field, uint64_t tag, const void* d_rc, const void* d_xs, size_t len, size_t n, int bits, void* d_out,
+                     hipStream_t s) {
+  VDF_TRY(check_field(field));
+  if (bits < 0 || bits > 255) return Status{VDF_ERR_BAD_ARG, "bits must be 0 (the element) or 1..255"};
+  if (len > VDF_RO_HASH_MAX_LEN) return Status{VDF_ERR_BAD_ARG, "at most VDF_RO_HASH_MAX_LEN elements per message"};
+  if (n == 0) return Status{};
+  if (n > 0xFFFFFFFFull) return Status{VDF_ERR_BAD_LENGTH, "at most 2^32 - 1 messages per call"};
+  KTimer kt(s, "k_ro_hash", 32.0 * n * (len + 1));
+  return with_field(field, [&](auto f) {
+    using P = tag_t<decltype(f)>;
+    const Fe<P> s0 = fe_from_u64<P>(tag + ((uint64_t)len << 32));
+    FeVal s0v; std::memcpy(s0v.v, s0.v, 32);
+    hipLaunchKernelGGL((k_ro_hash<P>), grid_for(n), dim3(256), 0, s, cbytes_of(d_rc), cbytes_of(d_xs), (uint32_t)len, (uint32_t)n, s0v, bits,
+                       bytes_of(d_out));
+  });
+}
+
 }  // namespace vdf

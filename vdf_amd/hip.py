@@ -877,6 +877,13 @@ class Context:
         masked; numpy arrays or device tensors, each on its own."""
         self._check(lib.vdf_points_axpy(self.handle, curve, _ptr(a), _ptr(b), _ptr(s), bits, n, _ptr(out)))
 
+    def ro_hash_batch(self, field, tag, rc, xs, len, n, bits, out) -> None:
+        """vdf_ro_hash_batch: the family-0 random oracle of n messages of `len` elements each (message-major Montgomery limbs),
+        one lane per message; rc: the field's 88 round constants (nova.ro_constants); out: (n, 4) uint64 -- bits = 0: the element
+        in Montgomery form, 1..255: the low bits of its canonical integer as a plain integer.  Each array in host or device
+        memory."""
+        self._check(lib.vdf_ro_hash_batch(self.handle, field, tag, _ptr(rc), _ptr(xs), len, n, bits, _ptr(out)))
+
     def clock_probe(self, iters: int = 6000):
         """(shader MHz sustained under a multiply-bound load on every SIMD, the probe kernel's duration in ms)."""
         mhz, ms = C.c_double(), C.c_double()

@@ -79,6 +79,8 @@ for _name, _res, _args in [
     ("vdf_nova_proof_set_kernel_timing", _i, [_vp, _i]),
     ("vdf_nova_proof_kernel_events", _i, [_vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     ("vdf_nova_ro_hash", _i, [_i, _u64, _vp, _sz, _vp]),
+    ("vdf_nova_ro_constants", _i, [_i, _vp]),
+    ("vdf_nova_ro_hash_batch_eval", _i, [_i, _u64, _vp, _sz, _sz, _i, _vp]),
     ("vdf_nova_shape_digest", _i, [_u64, _i, _i, _vp, _vp]),
     ("vdf_nova_shape_digest_custom", _i, [_vp, _i, _vp, _vp]),
     ("vdf_nova_shape_export", _i, [_u64, _i, _i, _vp, _vp, _vp, _vp]),
@@ -141,6 +143,9 @@ for _name, _res, _args in [
     ("vdf_nova_verify_aggregate_device", _i, [_vp, _vp, _sz, C.POINTER(_sz), _vp, _vp, C.POINTER(_i), C.POINTER(C.c_int64)]),
     ("vdf_nova_verify_aggregate_wire", _i, [_vp, _vp, _sz, _sz, C.POINTER(_sz), _vp, _vp, C.POINTER(_i), C.POINTER(C.c_int64), C.POINTER(_i)]),
     ("vdf_nova_aggregate_verify_times", _i, [C.POINTER(C.c_double)]),
+    ("vdf_nova_pp_set_verify_ro_device", _i, [_vp, _i]),
+    ("vdf_nova_pp_verify_ro_device", _i, [_vp]),
+    ("vdf_nova_pp_verify_ro_stats", _i, [_vp, C.POINTER(_u64)]),
     ("vdf_nova_proof_serialized_size", _sz, [_vp]),
     ("vdf_nova_proof_serialize", _i, [_vp, _vp, _sz]),
     ("vdf_nova_proof_deserialize", _i, [_vp, _vp, _sz, C.POINTER(_vp)]),
@@ -299,6 +304,22 @@ def point_decompress(data: bytes, curve: int = 0) -> np.ndarray:
     out = np.zeros(8, dtype="<u8")
     _check(nova_lib.vdf_nova_point_decompress(curve, (C.c_uint8 * 32).from_buffer_copy(data), out.ctypes.data))
     return out
+
+
+def ro_constants(field: int) -> np.ndarray:
+    """vdf_nova_ro_constants: the default block's 88 round constants of `field` (Montgomery limbs, (88, 4) uint64), in the order
+    Context.ro_hash_batch reads them: ext[r][lane] for r = 0..7, then in[0..55]."""
+    out = np.zeros((88, 4), dtype="<u8")
+    _check(nova_lib.vdf_nova_ro_constants(field, out.ctypes.data))
+    return out
+
+
+def ro_hash_batch_eval(field: int, tag: int, xs, len_: int, n: int, bits: int, out) -> None:
+    """vdf_nova_ro_hash_batch_eval: the host restatement of Context.ro_hash_batch -- n messages of len_ elements (message-major
+    Montgomery limbs) hashed into out[(n, 4) uint64]; bits = 0: the element, 1..255: the low bits of its canonical integer.  xs
+    and out: numpy arrays or None."""
+    ptr = lambda a: None if a is None else a.ctypes.data
+    _check(nova_lib.vdf_nova_ro_hash_batch_eval(field, tag, ptr(xs), len_, n, bits, ptr(out)))
 
 
 def ro_hash(field: int, tag: int, xs: np.ndarray, ro: "RoParams | None" = None) -> np.ndarray:
@@ -1020,6 +1041,22 @@ class NovaVDFPublicParams:        # src/nova/proof.rs:38-43
         out = (_u64 * 3)()
         _check(nova_lib.vdf_nova_pp_verify_multi_stats(self.handle, out))
         return int(out[0]), int(out[1]), int(out[2])
+
+    def set_verify_ro_device(self, min_count: int) -> None:
+        """vdf_nova_pp_set_verify_ro_device: from how many entries on verify_aggregate_device / verify_aggregate_wire make an
+        aggregate's per-entry Poseidon hashes by vdf_ro_hash_batch on the device; 0 (the default): always on the host.  Verdicts
+        do not depend on it."""
+        _check(nova_lib.vdf_nova_pp_set_verify_ro_device(self.handle, min_count))
+
+    @property
+    def verify_ro_device(self) -> int:
+        return int(nova_lib.vdf_nova_pp_verify_ro_device(self.handle))
+
+    def verify_ro_stats(self) -> Tuple[int, int]:
+        """(hashes made on the device, launches) since the set was made."""
+        out = (_u64 * 2)()
+        _check(nova_lib.vdf_nova_pp_verify_ro_stats(self.handle, out))
+        return int(out[0]), int(out[1])
 
     def stencil(self) -> int:
         """4 / 3: the early rows run as the MinRoot stencil (reference / bound rounds), 5: as the forward circuit's stencil,
