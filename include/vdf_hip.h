@@ -899,13 +899,31 @@ int  vdf_points_axpy(vdf_ctx* ctx, int curve, const vdf_affine* a, const vdf_aff
  * any other value is VDF_ERR_BAD_ARG, as are an unknown field and len > VDF_RO_HASH_MAX_LEN.  The messages are a peer's: no
  * loop, branch or address of the kernel depends on them.  Each array in host or device memory (vdf_ptr_is_device), device
  * arrays 16-byte aligned (otherwise VDF_ERR_BAD_ARG), `out` not overlapping an input.  n = 0 is VDF_OK and touches nothing; a
- * null pointer with n > 0 is VDF_ERR_BAD_ARG (xs may be null when len = 0).  Only family 0 runs on the device: the dense
- * width-25 matrix of family 1 does not fit a lane's registers and stays on the host.  vdf_nova_ro_hash_batch_eval is the host
+ * null pointer with n > 0 is VDF_ERR_BAD_ARG (xs may be null when len = 0).  This call is family 0 only; a family-1 block
+ * (the dense matrix of width up to 25) runs through vdf_ro_hash_batch_block below.  vdf_nova_ro_hash_batch_eval is the host
  * restatement. */
 #define VDF_RO_CONSTANTS  88          /* 8 external rounds x 4 lanes, then 56 internal */
 #define VDF_RO_HASH_MAX_LEN 1024
 int  vdf_ro_hash_batch(vdf_ctx* ctx, int field, uint64_t tag, const vdf_fe* rc, const vdf_fe* xs, size_t len, size_t n, int bits,
                        vdf_fe* out);
+/* The same oracle under a family-1 block of vdf_nova.h (the original Poseidon permutation: `width` elements, x^5 on every
+ * element in the first and last full_rounds / 2 rounds and on element 0 in the partial_rounds between, a dense width x width
+ * matrix after every round; the sponge's rate is width - 1), one message per 32 lanes: lane i of a group holds state element
+ * i, and the matrix product goes through LDS.  rc: (full_rounds + partial_rounds) * width round constants, round-major and
+ * lane-minor; mds: width * width elements, row-major; both in Montgomery form -- what vdf_nova_ro_block_constants writes.
+ * out[i] is vdf_nova_ro_hash_ro(block, field, tag, xs + i * len, len): the state starts as (tag + (len << 32), 0, ..), each
+ * block of width - 1 elements (the last one possibly short) is added into elements 1..width - 1 and followed by one
+ * permutation, the result is element 1; len = 0 permutes nothing and gives 0.  xs, len, n, bits and out as above, and every
+ * rule above carries over.  Refusals, in this order, each VDF_ERR_BAD_ARG: an unknown field; width outside
+ * 2..VDF_RO_BLOCK_MAX_WIDTH; full_rounds odd or outside 2..VDF_RO_BLOCK_MAX_FULL; partial_rounds outside
+ * 0..VDF_RO_BLOCK_MAX_PARTIAL; bits outside 0..255; len > VDF_RO_HASH_MAX_LEN; then n = 0 is VDF_OK and touches nothing; a null
+ * rc, mds or out, or a null xs with len > 0; a device array that is not 16-byte aligned.  No loop, branch or address of the
+ * kernel depends on a message.  vdf_nova_ro_hash_batch_eval_ro is the host restatement. */
+#define VDF_RO_BLOCK_MAX_WIDTH   25
+#define VDF_RO_BLOCK_MAX_FULL    16
+#define VDF_RO_BLOCK_MAX_PARTIAL 128
+int  vdf_ro_hash_batch_block(vdf_ctx* ctx, int field, uint64_t tag, int width, int full_rounds, int partial_rounds,
+                             const vdf_fe* rc, const vdf_fe* mds, const vdf_fe* xs, size_t len, size_t n, int bits, vdf_fe* out);
 /* Throughput probe: each of n lanes runs `iters` dependent Montgomery multiplications
  * (roofline / issue-rate calibration for DESIGN.md; not on the prove path). */
 int  vdf_fe_mul_chain(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, int iters, vdf_fe* out);

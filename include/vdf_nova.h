@@ -926,6 +926,19 @@ int  vdf_nova_aug_synthesize(int side, uint64_t num_iters_per_step, int circuit_
                              size_t* num_cons, vdf_fe X[2], vdf_fe z_next[3]);
 /* the host-only entry points under another random-oracle block (NULL = the default): sponge, shape digest, synthesis */
 int  vdf_nova_ro_hash_ro(const vdf_nova_ro_params* ro, int field, uint64_t tag, const vdf_fe* xs, size_t n, vdf_fe* out);
+/* a family-1 block's constants of `field` in Montgomery form, in the layout vdf_ro_hash_batch_block (vdf_hip.h) reads: rc, the
+ * (full_rounds + partial_rounds) * width round constants, round-major and lane-minor; mds, the width * width matrix, row-major.
+ * counts (optional) receives {(full_rounds + partial_rounds) * width, width * width}; with rc = mds = NULL only the counts are
+ * written (either pointer alone may be NULL too).  ro = NULL, the default block (family 0 has vdf_nova_ro_constants), a block
+ * this build does not support or an unknown field: VDF_ERR_BAD_ARG.  Pure: callable without a GPU. */
+int  vdf_nova_ro_block_constants(const vdf_nova_ro_params* ro, int field, vdf_fe* rc, vdf_fe* mds, size_t counts[2]);
+/* the host restatement of vdf_ro_hash_batch_block, and the reference its tests compare with byte for byte: out[i] =
+ * vdf_nova_ro_hash_ro(ro, field, tag, xs + i * len, len) under the `bits` rule of vdf_nova_ro_hash_batch_eval.  ro = NULL
+ * behaves as vdf_nova_ro_hash_batch_eval.  Refusals as the device call's, in its order, each VDF_ERR_BAD_ARG: an unknown field;
+ * a block this build does not support (a width, full_rounds or partial_rounds out of range among them); bits outside 0..255;
+ * len > VDF_RO_HASH_MAX_LEN; then n = 0 is VDF_OK and touches nothing; a null out, or a null xs with len > 0. */
+int  vdf_nova_ro_hash_batch_eval_ro(const vdf_nova_ro_params* ro, int field, uint64_t tag, const vdf_fe* xs, size_t len, size_t n,
+                                    int bits, vdf_fe* out);
 int  vdf_nova_shape_digest_ro(const vdf_nova_ro_params* ro, uint64_t num_iters_per_step, int circuit_kind, int gens_family, uint8_t out[32],
                               uint64_t sizes[2][3]);
 int  vdf_nova_aug_synthesize_ro(const vdf_nova_ro_params* ro, int side, uint64_t num_iters_per_step, int circuit_kind,
@@ -1175,11 +1188,19 @@ int  vdf_nova_aggregate_fold_instances(int field_of_primary, int side, const uin
  *   one entry after the other.  min_count > 0: for an aggregate of at least min_count entries a host pass packs the messages,
  *   three vdf_ro_hash_batch launches (vdf_hip.h; bits = 250, 250, 128) and one wait follow, and the comparisons run on the host
  *   in entry order.  *ok and *bad_entry are the same for EVERY input: the first failing entry is named, whichever check it
- *   fails.  A negative value: VDF_ERR_BAD_ARG.  The device oracle is family 0 only: a parameter set made under another RO
- *   parameter block accepts the switch and keeps the host hashes.  The set keeps one device copy of each field's 88 round
+ *   fails.  A negative value: VDF_ERR_BAD_ARG.  This switch is family 0 only: a parameter set made under another RO
+ *   parameter block accepts it and keeps the host hashes (vdf_nova_pp_set_verify_ro_block_device below is that set's switch).  The set keeps one device copy of each field's 88 round
  *   constants, made on first use and freed with it.  vdf_nova_verify_aggregate, the maker and the batch verifiers do not read
  *   the switch.  vdf_nova_pp_verify_ro_device reads it back (0 for a null pp); vdf_nova_pp_verify_ro_stats: out[0] = hashes made
- *   on the device under this set, out[1] = launches. */
+ *   on the device under this set, out[1] = launches.
+ * vdf_nova_pp_set_verify_ro_block_device: the same choice for a parameter set made under ANOTHER RO parameter block (family 1),
+ *   a separate switch that leaves the one above as it is.  It is read only for such a set; a default-block set accepts it and
+ *   ignores it.  min_count = 0 (the default): the host hashes.  min_count > 0: for an aggregate of at least min_count entries
+ *   the same host pass packs the messages and three vdf_ro_hash_batch_block launches (vdf_hip.h) and one wait make the hashes;
+ *   *ok, *bad_entry and the decode code are the same for every input.  A negative value: VDF_ERR_BAD_ARG.  The set keeps one
+ *   device copy of the block's round constants and matrix per field, made on first use and freed with it.
+ *   vdf_nova_pp_verify_ro_block_device reads it back (0 for a null pp); vdf_nova_pp_verify_ro_stats counts these hashes and
+ *   launches in the same two counters. */
 int  vdf_nova_aggregate_fold_instances_device(vdf_pp* pp, int side, size_t count, const vdf_wire_instance inst[],
                                               const uint8_t comm_TT[][32], vdf_wire_instance* acc, vdf_fe r_out[]);
 int  vdf_nova_verify_aggregate_device(const vdf_aggregate* agg, vdf_pp* pp, size_t count, const size_t num_steps[],
@@ -1190,6 +1211,8 @@ int  vdf_nova_aggregate_verify_times(double ms[5]);
 int  vdf_nova_pp_set_verify_ro_device(vdf_pp* pp, int min_count);
 int  vdf_nova_pp_verify_ro_device(const vdf_pp* pp);
 int  vdf_nova_pp_verify_ro_stats(const vdf_pp* pp, uint64_t out[2]);
+int  vdf_nova_pp_set_verify_ro_block_device(vdf_pp* pp, int min_count);
+int  vdf_nova_pp_verify_ro_block_device(const vdf_pp* pp);
 size_t vdf_nova_proof_serialized_size(const vdf_proof* proof);
 int  vdf_nova_proof_serialize(const vdf_proof* proof, uint8_t* out, size_t cap);
 int  vdf_nova_proof_deserialize(vdf_pp* pp, const uint8_t* in, size_t len, vdf_proof** out);

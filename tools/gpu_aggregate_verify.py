@@ -14,8 +14,11 @@ not are listed as such.  Every K runs under a time limit of its own (--step-time
 turns repeat by repeat; per K both wall times, both ways' parts, k_ro_hash by events (one more call, and alone at n = K for the
 three message lengths of an aggregate), and the rule with "switch at 1" in the place of the device way and "switch at 0" in
 the place of the host way.  The smallest K of an unbroken run of "yes" up to the largest K is the min_count to recommend.
+--ro-block: the same comparison under the neptune-shaped parameter set (family 1: width 25, 8 + 57 rounds) -- the device way
+with vdf_nova_pp_set_verify_ro_block_device at 0 (the host hashes) against the same call with that switch at 1 (three
+vdf_ro_hash_batch_block launches); k_ro_hash_block by events, and alone at n = K for the three message lengths.
 usage: python tools/gpu_aggregate_verify.py [--lg 16] [--ks 1,2,16,128,1024] [--proofs 4] [--repeats 5] [--step-timeout 240] [--out FILE]
-                                            [--ro-device]"""
+                                            [--ro-device | --ro-block]"""
 import argparse
 import os
 import signal
@@ -38,7 +41,10 @@ def main():
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--out", default=None)
     ap.add_argument("--ro-device", action="store_true")
+    ap.add_argument("--ro-block", action="store_true")
     a = ap.parse_args()
+    if a.ro_device and a.ro_block:
+        ap.error("--ro-device and --ro-block are two runs")
     import numpy as np
     import torch
     import vdf_amd
@@ -46,7 +52,7 @@ def main():
     from vdf_amd import _lib
     from vdf_amd.minroot import EvalMode, PallasVDF, State, FIELD_FQ
     from vdf_amd.nova import (InverseMinRootCircuit, NovaVDFProof, aggregate_verify_times, compress_aggregate, deserialize_aggregate, public_params,
-                              ro_constants, verify_aggregate_wire)
+                              RO_NEPTUNE_SHAPED, ro_block_constants, ro_constants, ro_preset, verify_aggregate_wire)
     lines = []
 
     def say(s=""):
@@ -69,7 +75,11 @@ def main():
     ks = [int(x) for x in a.ks.split(",") if x]
     signal.alarm(a.step_timeout)
     ctx = vdf_amd.Context(0)
-    pp = public_params(ctx, t)
+    ro = ro_preset(RO_NEPTUNE_SHAPED) if a.ro_block else None
+    pp = public_params(ctx, t, ro=ro)
+    # which switch the run turns, the kernel it watches and that kernel alone at n messages
+    set_switch = pp.set_verify_ro_block_device if a.ro_block else pp.set_verify_ro_device
+    kernel = "k_ro_hash_block" if a.ro_block else "k_ro_hash"
     items = []
     for q in range(a.proofs):                              # distinct chains of 1, 2, 1, 2, ... steps
         n = 1 + q % 2
@@ -85,14 +95,14 @@ def main():
     def ro_device_at(K, data, stmt):
         ways = (("switch at 0", 0), ("switch at 1", 1))
         for _, sw in ways:                                 # warm both ways (the second makes the constants' device copies)
-            pp.set_verify_ro_device(sw)
+            set_switch(sw)
             if verify_aggregate_wire(pp, data, *stmt) != (True, -1, 0):
                 sys.exit(f"K = {K}: the aggregate does not verify")
         tm = {name: [] for name, _ in ways}
         parts = {name: [] for name, _ in ways}
         for _ in range(a.repeats):
             for name, sw in ways:
-                pp.set_verify_ro_device(sw)
+                set_switch(sw)
                 ctx.sync(); t0 = time.perf_counter()
                 wired = verify_aggregate_wire(pp, data, *stmt); ctx.sync()
                 tm[name].append(1e3 * (time.perf_counter() - t0))
@@ -108,7 +118,7 @@ def main():
         for name, _ in ways:
             for j, part in enumerate(PARTS):
                 say(f"   {name}, {part:24s} ms {fmt([p[j] for p in parts[name]])}")
-        pp.set_verify_ro_device(1)                         # one more call with the library's events around its launches
+        set_switch(1)                                      # one more call with the library's events around its launches
         before = pp.verify_ro_stats()
         ctx.set_kernel_timing(True)
         ctx.kernel_events()
@@ -117,12 +127,18 @@ def main():
         ev = ctx.kernel_events()
         ctx.set_kernel_timing(False)
         after = pp.verify_ro_stats()
-        pp.set_verify_ro_device(0)
-        ms = [e1 - e0 for kn, _, e0, e1 in ev if kn == "k_ro_hash"]
-        say(f"   events: k_ro_hash {len(ms):3d} launches, {sum(ms):9.3f} ms ({', '.join('%.3f' % v for v in ms)});"
+        set_switch(0)
+        ms = [e1 - e0 for kn, _, e0, e1 in ev if kn == kernel]
+        say(f"   events: {kernel} {len(ms):3d} launches, {sum(ms):9.3f} ms ({', '.join('%.3f' % v for v in ms)});"
             f" stats: {after[0] - before[0]} hashes in {after[1] - before[1]} launches")
         rng = np.random.default_rng(K)                     # the kernel alone at n = K, device arrays, the aggregate's three lengths
-        rc = torch.from_numpy(ro_constants(FIELD_FQ).view(np.int64)).cuda()
+        if a.ro_block:
+            rc, mds = (torch.from_numpy(c.view(np.int64)).cuda() for c in ro_block_constants(FIELD_FQ, ro))
+            alone = lambda dxs, ln, bits, out: ctx.ro_hash_batch_block(FIELD_FQ, 1, ro.width, ro.full_rounds, ro.partial_rounds, rc, mds, dxs, ln, K,
+                                                                       bits, out)
+        else:
+            rc = torch.from_numpy(ro_constants(FIELD_FQ).view(np.int64)).cuda()
+            alone = lambda dxs, ln, bits, out: ctx.ro_hash_batch(FIELD_FQ, 1, rc, dxs, ln, K, bits, out)
         out = torch.zeros((K, 4), dtype=torch.int64, device="cuda")
         for ln, bits in ((17, 250), (13, 250), (16, 128)):
             xs = rng.integers(0, 2**62, size=(K * ln, 4), dtype=np.int64)
@@ -131,11 +147,11 @@ def main():
             ctx.set_kernel_timing(True)
             ctx.kernel_events()
             for _ in range(a.repeats + 1):
-                ctx.ro_hash_batch(FIELD_FQ, 1, rc, dxs, ln, K, bits, out)
+                alone(dxs, ln, bits, out)
             ctx.sync()
-            us = [1e3 * (e1 - e0) for kn, _, e0, e1 in ctx.kernel_events() if kn == "k_ro_hash"][1:]
+            us = [1e3 * (e1 - e0) for kn, _, e0, e1 in ctx.kernel_events() if kn == kernel][1:]
             ctx.set_kernel_timing(False)
-            say(f"   k_ro_hash alone, n = {K:4d}, len = {ln:2d}, bits = {bits:3d}: us {statistics.median(us):9.1f} [{min(us):9.1f} .. {max(us):9.1f}]")
+            say(f"   {kernel} alone, n = {K:4d}, len = {ln:2d}, bits = {bits:3d}: us {statistics.median(us):9.1f} [{min(us):9.1f} .. {max(us):9.1f}]")
 
     for K in ks:
         signal.alarm(a.step_timeout)
@@ -146,7 +162,7 @@ def main():
         agg.free()
         if deserialize_aggregate(pp, data).verify(pp, *stmt) != (True, -1) or verify_aggregate_wire(pp, data, *stmt) != (True, -1, 0):   # warm both ways
             sys.exit(f"K = {K}: the aggregate does not verify")
-        if a.ro_device:
+        if a.ro_device or a.ro_block:
             ro_device_at(K, data, stmt)
             signal.alarm(0)
             save()
@@ -203,11 +219,11 @@ def main():
             say(f"   k_points_axpy alone, n = {n:4d}, bits = {bits:3d}: us {statistics.median(us):9.1f} [{min(us):9.1f} .. {max(us):9.1f}]")
         signal.alarm(0)
         save()
-    if a.ro_device:
+    if a.ro_device or a.ro_block:
         say(f"switch at 1 faster by the rule at K in {faster}; not faster at K in {not_faster}")
     else:
         say(f"device way faster by the rule at K in {faster}; not faster at K in {not_faster}")
-    for sym, vgpr, agpr, lds, scratch in kernel_figures(_lib.lib._name, "k_ro_hash" if a.ro_device else "k_points_axpy"):
+    for sym, vgpr, agpr, lds, scratch in kernel_figures(_lib.lib._name, kernel if a.ro_device or a.ro_block else "k_points_axpy"):
         say(f"{sym}: {vgpr} VGPRs, {agpr} AGPRs, {lds} B LDS, {scratch} B scratch")
     save()
 

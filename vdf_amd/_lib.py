@@ -133,6 +133,7 @@ PROTOTYPES = {
     "vdf_points_decompress": (_i, [_vp, _i, _vp, _sz, _vp, _vp]),
     "vdf_points_axpy": (_i, [_vp, _i, _vp, _vp, _vp, _i, _sz, _vp]),
     "vdf_ro_hash_batch": (_i, [_vp, _i, C.c_uint64, _vp, _vp, _sz, _sz, _i, _vp]),
+    "vdf_ro_hash_batch_block": (_i, [_vp, _i, C.c_uint64, _i, _i, _i, _vp, _vp, _vp, _sz, _sz, _i, _vp]),
     "vdf_fe_mul_chain": (_i, [_vp, _i, _vp, _sz, _i, _vp]),
     "vdf_hip_tuning_get": (_i, [_vp]),
     "vdf_hip_tuning_set": (_i, [_vp]),

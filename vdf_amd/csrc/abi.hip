@@ -2355,6 +2355,28 @@ int vdf_ro_hash_batch(vdf_ctx* ctx, int field, uint64_t tag, const vdf_fe* rc, c
   });
 }
 
+int vdf_ro_hash_batch_block(vdf_ctx* ctx, int field, uint64_t tag, int width, int full_rounds, int partial_rounds, const vdf_fe* rc,
+                            const vdf_fe* mds, const vdf_fe* xs, size_t len, size_t n, int bits, vdf_fe* out) {
+  return guarded(ctx, [&]() -> Status {
+    VDF_TRY(vdf::check_field(field));
+    VDF_TRY(vdf::ro_block_shape(width, full_rounds, partial_rounds));
+    if (bits < 0 || bits > 255) return Status{VDF_ERR_BAD_ARG, "bits must be 0 (the element) or 1..255"};
+    if (len > VDF_RO_HASH_MAX_LEN) return Status{VDF_ERR_BAD_ARG, "at most VDF_RO_HASH_MAX_LEN elements per message"};
+    if (n == 0) return Status{};
+    if (!rc || !mds || !out || (!xs && len)) return Status{VDF_ERR_BAD_ARG, "null argument"};
+    for (const void* p : {(const void*)rc, (const void*)mds, (const void*)xs, (const void*)out})
+      if (p && (reinterpret_cast<uintptr_t>(p) & 15) && ptr_is_device(p)) return Status{VDF_ERR_BAD_ARG, "device arrays are 16-byte aligned"};
+    Staging st(ctx);
+    const void *drc, *dmds, *dxs; void* dout;
+    VDF_TRY(st.in(rc, (size_t)(full_rounds + partial_rounds) * width * 32, &drc));
+    VDF_TRY(st.in(mds, (size_t)width * width * 32, &dmds));
+    VDF_TRY(st.in(xs, n * len * 32, &dxs));
+    VDF_TRY(st.out(out, n * 32, &dout));
+    VDF_TRY(vdf::ro_hash_batch_block(field, tag, width, full_rounds, partial_rounds, drc, dmds, dxs, len, n, bits, dout, ctx->stream));
+    return st.finish();
+  });
+}
+
 int vdf_fe_mul_chain(vdf_ctx* ctx, int field, const vdf_fe* a, size_t n, int iters, vdf_fe* out) {
   return guarded(ctx, [&]() -> Status {
     Staging st(ctx);

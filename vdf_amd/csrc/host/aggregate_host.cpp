@@ -259,24 +259,39 @@ int64_t exact_checks(const vdf_aggregate* agg, const vdf_pp* pp, size_t count, c
   return -1;
 }
 
-// The device copy of a field's 88 round constants (vdf_nova_ro_constants' order), made on first use and freed with the set.
-int ro_constants_on_device(vdf_pp* pp, int field_id, const void** out) {
+// The device copy of what the set's oracle reads for a field, made on first use and freed with the set: the default block's 88
+// round constants (vdf_nova_ro_constants' order; *mds stays null), or another block's round constants and matrix
+// (vdf_nova_ro_block_constants' layout).
+int ro_constants_on_device(vdf_pp* pp, int field_id, const void** rc_out, const void** mds_out) {
   std::lock_guard<std::mutex> lock(pp->ro_mu);
-  void*& d = pp->d_ro_rc[field_id];
-  if (!d) {
+  auto upload = [&](void*& d, const void* src, size_t bytes) -> int {
+    if (d) return VDF_OK;
     void* p = nullptr;
-    HIPCALL(pp->ctx, vdf_dev_alloc(pp->ctx, VDF_RO_CONSTANTS * sizeof(Fe), &p));
-    const int rc = vdf_dev_memcpy(pp->ctx, p, ro_constants(field_id).ext, VDF_RO_CONSTANTS * sizeof(Fe));
+    HIPCALL(pp->ctx, vdf_dev_alloc(pp->ctx, bytes, &p));
+    const int rc = vdf_dev_memcpy(pp->ctx, p, src, bytes);
     if (rc != VDF_OK) { vdf_dev_free(pp->ctx, p); return fail(rc, std::string("vdf_dev_memcpy (round constants): ") + vdf_last_error(pp->ctx)); }
     d = p;
+    return VDF_OK;
+  };
+  *mds_out = nullptr;
+  if (pp->ro->is_default) {
+    { int rc = upload(pp->d_ro_rc[field_id], ro_constants(field_id).ext, VDF_RO_CONSTANTS * sizeof(Fe)); if (rc != VDF_OK) return rc; }
+    *rc_out = pp->d_ro_rc[field_id];
+    return VDF_OK;
   }
-  *out = d;
+  const std::vector<Fe>& k = pp->ro->rc[field_id];
+  const std::vector<Fe>& m = pp->ro->mds[field_id];
+  { int rc = upload(pp->d_ro_block[field_id][0], k.data(), k.size() * sizeof(Fe)); if (rc != VDF_OK) return rc; }
+  { int rc = upload(pp->d_ro_block[field_id][1], m.data(), m.size() * sizeof(Fe)); if (rc != VDF_OK) return rc; }
+  *rc_out = pp->d_ro_block[field_id][0];
+  *mds_out = pp->d_ro_block[field_id][1];
   return VDF_OK;
 }
 static_assert(offsetof(RoConstants, in) == RO_RF * RO_T * sizeof(Fe) && RO_RF * RO_T + RO_RP == VDF_RO_CONSTANTS,
               "RoConstants begins with the 88 constants in the order vdf_ro_hash_batch reads them");
 
-// exact_checks with the three Poseidon hashes of every entry made by vdf_ro_hash_batch (the default block only): a host pass
+// exact_checks with the three Poseidon hashes of every entry made by vdf_ro_hash_batch (the default block) or
+// vdf_ro_hash_batch_block (any other): a host pass
 // packs the messages of hash_state (both sides) and hash_challenge into one pinned block the kernel reads in place, three
 // launches and one wait follow, and the comparisons run on the host in entry order.  *first_bad is exact_checks' value for
 // every input: the entries in front of the first structural failure are hashed and compared, so an earlier mismatch wins.
@@ -326,15 +341,23 @@ int exact_checks_ro_device(const vdf_aggregate* agg, vdf_pp* pp, size_t count, c
     for (int j = 0; j < 2; ++j) { uint64_t ux[4]; fe_to_int(s.l_u2.X[j], F2, ux); x[12 + j] = int_to_fe(ux, F1); }
     x[14] = s.T2.x; x[15] = s.T2.y;
   }
-  const void *rc1 = nullptr, *rc2 = nullptr;
-  { int rc = ro_constants_on_device(pp, S1.field, &rc1); if (rc != VDF_OK) return rc; }
-  { int rc = ro_constants_on_device(pp, S2.field, &rc2); if (rc != VDF_OK) return rc; }
+  const void *rc1 = nullptr, *rc2 = nullptr, *mds1 = nullptr, *mds2 = nullptr;
+  { int rc = ro_constants_on_device(pp, S1.field, &rc1, &mds1); if (rc != VDF_OK) return rc; }
+  { int rc = ro_constants_on_device(pp, S2.field, &rc2, &mds2); if (rc != VDF_OK) return rc; }
+  const RoSpec& sp = pp->ro->spec;
+  // one launch: the family-0 kernel for the default block, the block kernel for any other
+  auto hash = [&](int f, uint64_t tag, const void* rc, const void* mds, const Fe* xs, size_t len, int bits, Fe* out) -> int {
+    return pp->ro->is_default
+               ? vdf_ro_hash_batch(ctx, f, tag, (const vdf_fe*)rc, (const vdf_fe*)xs, len, live, bits, (vdf_fe*)out)
+               : vdf_ro_hash_batch_block(ctx, f, tag, sp.width, sp.full_rounds, sp.partial_rounds, (const vdf_fe*)rc, (const vdf_fe*)mds,
+                                         (const vdf_fe*)xs, len, live, bits, (vdf_fe*)out);
+  };
   {
     AsyncScope scope(ctx);
     { int rc = scope.enter(); if (rc != VDF_OK) return rc; }
-    HIPCALL(ctx, vdf_ro_hash_batch(ctx, S1.field, TAG_STATE, (const vdf_fe*)rc1, (const vdf_fe*)m1, len1, live, HASH_BITS, (vdf_fe*)h1));
-    HIPCALL(ctx, vdf_ro_hash_batch(ctx, S2.field, TAG_STATE, (const vdf_fe*)rc2, (const vdf_fe*)m2, len2, live, HASH_BITS, (vdf_fe*)h2));
-    HIPCALL(ctx, vdf_ro_hash_batch(ctx, S1.field, TAG_CHAL, (const vdf_fe*)rc1, (const vdf_fe*)m3, len3, live, CHAL_BITS, (vdf_fe*)h3));
+    HIPCALL(ctx, hash(S1.field, TAG_STATE, rc1, mds1, m1, len1, HASH_BITS, h1));
+    HIPCALL(ctx, hash(S2.field, TAG_STATE, rc2, mds2, m2, len2, HASH_BITS, h2));
+    HIPCALL(ctx, hash(S1.field, TAG_CHAL, rc1, mds1, m3, len3, CHAL_BITS, h3));
     HIPCALL(ctx, vdf_ctx_sync(ctx));
   }
   pp->verify_ro_stats[0] += 3 * live;
@@ -708,10 +731,11 @@ int vdf_nova_verify_aggregate_device(const vdf_aggregate* agg, vdf_pp* pp, size_
       memcpy(rho[k].l, r, 32);
       rho[count + k] = rho[k];
     };
-    // the three Poseidon hashes of every entry: on the host, or by vdf_ro_hash_batch (vdf_nova_pp_set_verify_ro_device)
-    const int ro_min = pp->verify_ro_device.load();
+    // the three Poseidon hashes of every entry: on the host, or by vdf_ro_hash_batch under the default block
+    // (vdf_nova_pp_set_verify_ro_device), or by vdf_ro_hash_batch_block under another block (vdf_nova_pp_set_verify_ro_block_device)
+    const int ro_min = pp->ro->is_default ? pp->verify_ro_device.load() : pp->verify_ro_block_device.load();
     int64_t first_bad = -1;
-    if (ro_min > 0 && count >= (size_t)ro_min && pp->ro->is_default) {
+    if (ro_min > 0 && count >= (size_t)ro_min) {
       int rc = exact_checks_ro_device(agg, pp, count, num_steps, z0, zi, &first_bad, passed);
       if (rc != VDF_OK) return rc;
     } else {
@@ -750,6 +774,13 @@ int vdf_nova_pp_set_verify_ro_device(vdf_pp* pp, int min_count) {
   return VDF_OK;
 }
 int vdf_nova_pp_verify_ro_device(const vdf_pp* pp) { return pp ? pp->verify_ro_device.load() : 0; }
+int vdf_nova_pp_set_verify_ro_block_device(vdf_pp* pp, int min_count) {
+  if (!pp) return fail(VDF_ERR_BAD_ARG, "null argument");
+  if (min_count < 0) return fail(VDF_ERR_BAD_ARG, "min_count must be 0 (never) or a positive count");
+  pp->verify_ro_block_device.store(min_count);
+  return VDF_OK;
+}
+int vdf_nova_pp_verify_ro_block_device(const vdf_pp* pp) { return pp ? pp->verify_ro_block_device.load() : 0; }
 int vdf_nova_pp_verify_ro_stats(const vdf_pp* pp, uint64_t out[2]) {
   if (!pp || !out) return fail(VDF_ERR_BAD_ARG, "null argument");
   for (int k = 0; k < 2; ++k) out[k] = pp->verify_ro_stats[k].load();

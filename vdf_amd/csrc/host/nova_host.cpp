@@ -517,17 +517,40 @@ int vdf_nova_ro_constants(int f, vdf_fe out[VDF_RO_CONSTANTS]) {
     return VDF_OK;
   });
 }
+// a family-1 block's constants as RoInstance holds them: the layout vdf_ro_hash_batch_block reads
+static_assert(RO_MAX_T == VDF_RO_BLOCK_MAX_WIDTH, "ro_instance and vdf_ro_hash_batch_block accept the same widths");
+int vdf_nova_ro_block_constants(const vdf_nova_ro_params* rop, int f, vdf_fe* rc, vdf_fe* mds, size_t counts[2]) {
+  return nova_guard([&]() -> int {
+    if (!rop || !valid_field(f)) return fail(VDF_ERR_BAD_ARG, "bad argument");
+    bool bad;
+    const RoInstance* ro = ro_from_abi(rop, &bad);
+    if (bad) return fail(VDF_ERR_BAD_ARG, "unsupported RO parameter block");
+    if (ro->is_default) return fail(VDF_ERR_BAD_ARG, "the default block's constants are vdf_nova_ro_constants'");
+    if (counts) { counts[0] = ro->rc[f].size(); counts[1] = ro->mds[f].size(); }
+    if (rc) memcpy(rc, ro->rc[f].data(), ro->rc[f].size() * sizeof(Fe));
+    if (mds) memcpy(mds, ro->mds[f].data(), ro->mds[f].size() * sizeof(Fe));
+    return VDF_OK;
+  });
+}
 // the host restatement of vdf_ro_hash_batch (vdf_hip.h): the same refusals in the same order, ro_hash per message
 int vdf_nova_ro_hash_batch_eval(int f, uint64_t tag, const vdf_fe* xs, size_t len, size_t n, int bits, vdf_fe* out) {
+  return vdf_nova_ro_hash_batch_eval_ro(nullptr, f, tag, xs, len, n, bits, out);
+}
+// ... and of vdf_ro_hash_batch_block under another block: the shape refusals stand where the device call has them
+int vdf_nova_ro_hash_batch_eval_ro(const vdf_nova_ro_params* rop, int f, uint64_t tag, const vdf_fe* xs, size_t len, size_t n, int bits,
+                                   vdf_fe* out) {
   return nova_guard([&]() -> int {
     if (!valid_field(f)) return fail(VDF_ERR_BAD_ARG, "unknown field");
+    bool bad;
+    const RoInstance* ro = ro_from_abi(rop, &bad);
+    if (bad) return fail(VDF_ERR_BAD_ARG, "unsupported RO parameter block");
     if (bits < 0 || bits > 255) return fail(VDF_ERR_BAD_ARG, "bits must be 0 (the element) or 1..255");
     if (len > VDF_RO_HASH_MAX_LEN) return fail(VDF_ERR_BAD_ARG, "at most VDF_RO_HASH_MAX_LEN elements per message");
     if (n == 0) return VDF_OK;
     if (!out || (!xs && len)) return fail(VDF_ERR_BAD_ARG, "null argument");
     const Field& F = field(f);
     for (size_t i = 0; i < n; ++i) {
-      const Fe h = ro_hash(f, tag, (const Fe*)xs + i * len, len);
+      const Fe h = ro_hash(f, tag, (const Fe*)xs + i * len, len, ro);
       if (bits == 0) { memcpy(&out[i], &h, 32); continue; }
       uint64_t v[4];
       fe_to_int(h, F, v);
@@ -1302,6 +1325,7 @@ void vdf_nova_pp_free(vdf_pp* pp) {
   if (pp->seg_gens) vdf_bases_free(pp->seg_gens);
   if (pp->d_round_table) vdf_dev_free(pp->ctx, pp->d_round_table);
   for (void* p : pp->d_ro_rc) if (p) vdf_dev_free(pp->ctx, p);
+  for (auto& fld : pp->d_ro_block) for (void* p : fld) if (p) vdf_dev_free(pp->ctx, p);
   for (Side& sd : pp->s) {
     if (sd.d_zero) vdf_dev_free(pp->ctx, sd.d_zero);
     if (sd.shape) vdf_shape_free(sd.shape);

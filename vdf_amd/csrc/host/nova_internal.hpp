@@ -152,6 +152,9 @@ struct vdf_pp {
   std::atomic<int> verify_ro_device{0};
   std::atomic<uint64_t> verify_ro_stats[2] = {{0}, {0}};               // hashes made on the device, launches
   void* d_ro_rc[2] = {nullptr, nullptr};   // each field's 88 round constants on the device (index: VDF_FIELD_*), made on first use under ro_mu
+  // the same choice for a set made under another block: by three vdf_ro_hash_batch_block launches (vdf_nova_pp_set_verify_ro_block_device)
+  std::atomic<int> verify_ro_block_device{0};
+  void* d_ro_block[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [field][rc, mds] of the set's own block, made on first use under ro_mu
   std::mutex ro_mu;
   double setup_ms[7] = {0, 0, 0, 0, 0, 0, 0};
   uint64_t digit_table_bytes[2] = {0, 0};  // HBM held by each side's digit table (vdf_nova_pp_memory)

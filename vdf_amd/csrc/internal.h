@@ -401,6 +401,12 @@ Status vec_from_mont(int field, const void* a, size_t n, void* out, hipStream_t 
 Status vec_mul_chain(int field, const void* a, size_t n, int iters, void* out, hipStream_t s);
 // out[i] = the family-0 random oracle of message i (n messages of len elements, message-major); rc: the 88 round constants
 Status ro_hash_batch(int field, uint64_t tag, const void* d_rc, const void* d_xs, size_t len, size_t n, int bits, void* d_out, hipStream_t s);
+// the shape refusals of a family-1 block, in the order width, full_rounds, partial_rounds (the ranges vdf_nova's ro_instance accepts)
+Status ro_block_shape(int width, int full_rounds, int partial_rounds);
+// out[i] = the family-1 random oracle of message i, one message per 32 lanes; rc: (full + partial) x width round constants
+// (round-major), mds: width x width (row-major), both in Montgomery form
+Status ro_hash_batch_block(int field, uint64_t tag, int width, int full_rounds, int partial_rounds, const void* d_rc, const void* d_mds,
+                           const void* d_xs, size_t len, size_t n, int bits, void* d_out, hipStream_t s);
 Status vec_clock_probe(int iters, int workgroups, unsigned long long* d_out3, hipStream_t s);   // d_out3 zeroed by the caller
 
 // ---- minroot.hip -----------------------------------------------------------------------

@@ -1507,4 +1507,117 @@ Status ro_hash_batch(int field, uint64_t tag, const void* d_rc, const void* d_xs
   });
 }
 
+// ---- the random oracle, family 1 (vdf_ro_hash_batch_block) ----------------------------------------------------------------------
+// host/r1cs.cpp ro_hash / classic_permute restated for a non-default block (width t <= 25, rf full and rp partial rounds, dense
+// t x t matrix), one message per 32 consecutive lanes: lane i < t of a group owns state element i in registers, so no lane
+// holds an array indexed at run time.  A round adds rc[r t + i] (loaded during the round before), applies x^5 (every lane in a
+// full round, lane 0 otherwise: a per-lane select on a wave-uniform flag), and then s_i <- sum_j M[i][j] s_j: every lane
+// publishes its element in its message's LDS slots and reads all t back -- the 32 lanes of a group read ONE address, which
+// broadcasts.
+//
+// LDS: M once per workgroup, transposed and split into two planes of 16-byte halves, sM[half][j * 32 + i]: for a fixed j the
+// lanes of a group read consecutive 16-byte slots (dword 4 i, 64 banks: the 16 lanes of every ds_read_b128 lane group fall on 16
+// distinct bank quads), and lanes i and i + 32 read the same address.  Rows i >= t of both planes are zero, so an idle lane's
+// element stays zero.  The slots are double-buffered on the round's parity: a lane writes buffer p, passes the round's one
+// barrier and reads buffer p; the next write to p is two rounds later, behind the next round's barrier, which no wavefront
+// passes before every reader of p has arrived at it.
+//
+// Every wavefront runs every loop and every barrier: groups past n and lanes >= t skip only global loads and stores.  Trip
+// counts, branches and addresses come from the kernel arguments and the lane index, never from a message.  Every value kept
+// between two operations is canonical (fe_add, fe_mul_inl; ro_sbox ends in fe_canon), so the result is ro_hash's mod m.
+constexpr int RO_BLOCK_MAX_T = 25;
+static_assert(RO_BLOCK_MAX_T == VDF_RO_BLOCK_MAX_WIDTH && RO_BLOCK_MAX_T <= 32, "one state element per lane of a 32-lane group");
+template <class P>
+__global__ __launch_bounds__(256) void k_ro_hash_block(const char* __restrict__ rc, const char* __restrict__ mds, const char* __restrict__ xs,
+                                                       uint32_t len, uint32_t n, uint32_t t, uint32_t rf, uint32_t rp, FeVal s0, int bits,
+                                                       char* __restrict__ out) {
+  __shared__ uint4 sM[2][RO_BLOCK_MAX_T * 32];         // [half][column j][row i]
+  __shared__ uint4 sS[2][8][32][2];                    // [parity][message of the workgroup][element][half]
+  const uint32_t g = threadIdx.x >> 5, i = threadIdx.x & 31;
+  const uint32_t msg = blockIdx.x * 8 + g;
+  const bool mine = i < t, live = mine && msg < n;     // live: this lane may touch global memory
+  for (uint32_t e = threadIdx.x; e < t * 32; e += 256) {
+    const uint32_t j = e >> 5, row = e & 31;
+    uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+    if (row < t) {
+      const uint4* q = reinterpret_cast<const uint4*>(mds + ((size_t)row * t + j) * 32);
+      lo = q[0]; hi = q[1];
+    }
+    sM[0][e] = lo; sM[1][e] = hi;
+  }
+  __syncthreads();
+  Fe<P> s = i == 0 ? fe_from_val<P>(s0) : fe_zero<P>();
+  const uint32_t rate = t - 1, half = rf / 2, rounds = rf + rp;
+  uint32_t par = 0;
+  Fe<P> c = fe_zero<P>();                              // the round's constant, loaded one round ahead (an idle lane's stays zero)
+  if (live) c = fe_load<P>(rc + (size_t)i * 32);
+#pragma unroll 1
+  for (uint32_t k = 0; k < len; k += rate) {
+    // lane i >= 1 absorbs element k + (i - 1) of its message; lane 0 absorbs nothing (and its i - 1 is never formed)
+    const uint32_t idx = i >= 1 ? k + (i - 1) : len;
+    if (live && idx < len) s = fe_add(s, fe_load<P>(xs + ((size_t)msg * len + idx) * 32));
+#pragma unroll 1
+    for (uint32_t r = 0; r < rounds; ++r) {
+      s = fe_add(s, c);
+      const Fe<P> s5 = ro_sbox(s);
+      const bool box = r < half || r >= half + rp || i == 0;
+#pragma unroll
+      for (int w = 0; w < 8; ++w) s.v[w] = box ? s5.v[w] : s.v[w];
+      sS[par][g][i][0] = make_uint4(s.v[0], s.v[1], s.v[2], s.v[3]);
+      sS[par][g][i][1] = make_uint4(s.v[4], s.v[5], s.v[6], s.v[7]);
+      // the next round's constant does not depend on the state: its load is issued here and lands during the matrix loop.  After
+      // the last round that is round 0 again, which the next block's permutation begins with (and which is in range at the end).
+      const uint32_t rn = r + 1 < rounds ? r + 1 : 0;
+      if (live) c = fe_load<P>(rc + ((size_t)rn * t + i) * 32);
+      __syncthreads();
+      Fe<P> acc = fe_zero<P>();
+#pragma unroll 1
+      for (uint32_t j = 0; j < t; ++j) {
+        const uint4 ml = sM[0][j * 32 + i], mh = sM[1][j * 32 + i], vl = sS[par][g][j][0], vh = sS[par][g][j][1];
+        Fe<P> m, v;
+        m.v[0] = ml.x; m.v[1] = ml.y; m.v[2] = ml.z; m.v[3] = ml.w; m.v[4] = mh.x; m.v[5] = mh.y; m.v[6] = mh.z; m.v[7] = mh.w;
+        v.v[0] = vl.x; v.v[1] = vl.y; v.v[2] = vl.z; v.v[3] = vl.w; v.v[4] = vh.x; v.v[5] = vh.y; v.v[6] = vh.z; v.v[7] = vh.w;
+        acc = fe_add(acc, fe_mul_inl(m, v));
+      }
+      s = acc;
+      par ^= 1;
+    }
+  }
+  if (bits != 0) {
+    s = fe_from_mont(s);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int keep = bits - 32 * j;
+      s.v[j] &= keep >= 32 ? 0xFFFFFFFFu : (keep <= 0 ? 0u : (1u << keep) - 1u);
+    }
+  }
+  if (live && i == 1) fe_store<P>(out + (size_t)msg * 32, s);
+}
+
+Status ro_block_shape(int width, int full_rounds, int partial_rounds) {
+  if (width < 2 || width > VDF_RO_BLOCK_MAX_WIDTH) return Status{VDF_ERR_BAD_ARG, "width must be 2..VDF_RO_BLOCK_MAX_WIDTH"};
+  if (full_rounds < 2 || full_rounds > VDF_RO_BLOCK_MAX_FULL || (full_rounds & 1))
+    return Status{VDF_ERR_BAD_ARG, "full_rounds must be even and 2..VDF_RO_BLOCK_MAX_FULL"};
+  if (partial_rounds < 0 || partial_rounds > VDF_RO_BLOCK_MAX_PARTIAL) return Status{VDF_ERR_BAD_ARG, "partial_rounds must be 0..VDF_RO_BLOCK_MAX_PARTIAL"};
+  return Status{};
+}
+
+Status ro_hash_batch_block(int field, uint64_t tag, int width, int full_rounds, int partial_rounds, const void* d_rc, const void* d_mds,
+                           const void* d_xs, size_t len, size_t n, int bits, void* d_out, hipStream_t s) {
+  VDF_TRY(check_field(field));
+  VDF_TRY(ro_block_shape(width, full_rounds, partial_rounds));
+  if (bits < 0 || bits > 255) return Status{VDF_ERR_BAD_ARG, "bits must be 0 (the element) or 1..255"};
+  if (len > VDF_RO_HASH_MAX_LEN) return Status{VDF_ERR_BAD_ARG, "at most VDF_RO_HASH_MAX_LEN elements per message"};
+  if (n == 0) return Status{};
+  if (n > 0xFFFFFFFFull) return Status{VDF_ERR_BAD_LENGTH, "at most 2^32 - 1 messages per call"};
+  KTimer kt(s, "k_ro_hash_block", 32.0 * n * (len + 1));
+  return with_field(field, [&](auto f) {
+    using P = tag_t<decltype(f)>;
+    const Fe<P> s0 = fe_from_u64<P>(tag + ((uint64_t)len << 32));
+    FeVal s0v; std::memcpy(s0v.v, s0.v, 32);
+    hipLaunchKernelGGL((k_ro_hash_block<P>), dim3((unsigned)((n + 7) / 8)), dim3(256), 0, s, cbytes_of(d_rc), cbytes_of(d_mds), cbytes_of(d_xs),
+                       (uint32_t)len, (uint32_t)n, (uint32_t)width, (uint32_t)full_rounds, (uint32_t)partial_rounds, s0v, bits, bytes_of(d_out));
+  });
+}
+
 }  // namespace vdf

@@ -884,6 +884,13 @@ class Context:
         memory."""
         self._check(lib.vdf_ro_hash_batch(self.handle, field, tag, _ptr(rc), _ptr(xs), len, n, bits, _ptr(out)))
 
+    def ro_hash_batch_block(self, field, tag, width, full_rounds, partial_rounds, rc, mds, xs, len, n, bits, out) -> None:
+        """vdf_ro_hash_batch_block: the family-1 random oracle (width, full_rounds, partial_rounds; rate width - 1) of n messages
+        of `len` elements each, one message per 32 lanes; rc, mds: the block's round constants and matrix (nova.ro_block_constants);
+        xs, bits and out as ro_hash_batch.  Each array in host or device memory."""
+        self._check(lib.vdf_ro_hash_batch_block(self.handle, field, tag, width, full_rounds, partial_rounds, _ptr(rc), _ptr(mds), _ptr(xs),
+                                                len, n, bits, _ptr(out)))
+
     def clock_probe(self, iters: int = 6000):
         """(shader MHz sustained under a multiply-bound load on every SIMD, the probe kernel's duration in ms)."""
         mhz, ms = C.c_double(), C.c_double()

@@ -81,6 +81,8 @@ for _name, _res, _args in [
     ("vdf_nova_ro_hash", _i, [_i, _u64, _vp, _sz, _vp]),
     ("vdf_nova_ro_constants", _i, [_i, _vp]),
     ("vdf_nova_ro_hash_batch_eval", _i, [_i, _u64, _vp, _sz, _sz, _i, _vp]),
+    ("vdf_nova_ro_block_constants", _i, [_vp, _i, _vp, _vp, C.POINTER(_sz)]),
+    ("vdf_nova_ro_hash_batch_eval_ro", _i, [_vp, _i, _u64, _vp, _sz, _sz, _i, _vp]),
     ("vdf_nova_shape_digest", _i, [_u64, _i, _i, _vp, _vp]),
     ("vdf_nova_shape_digest_custom", _i, [_vp, _i, _vp, _vp]),
     ("vdf_nova_shape_export", _i, [_u64, _i, _i, _vp, _vp, _vp, _vp]),
@@ -146,6 +148,8 @@ for _name, _res, _args in [
     ("vdf_nova_pp_set_verify_ro_device", _i, [_vp, _i]),
     ("vdf_nova_pp_verify_ro_device", _i, [_vp]),
     ("vdf_nova_pp_verify_ro_stats", _i, [_vp, C.POINTER(_u64)]),
+    ("vdf_nova_pp_set_verify_ro_block_device", _i, [_vp, _i]),
+    ("vdf_nova_pp_verify_ro_block_device", _i, [_vp]),
     ("vdf_nova_proof_serialized_size", _sz, [_vp]),
     ("vdf_nova_proof_serialize", _i, [_vp, _vp, _sz]),
     ("vdf_nova_proof_deserialize", _i, [_vp, _vp, _sz, C.POINTER(_vp)]),
@@ -314,12 +318,26 @@ def ro_constants(field: int) -> np.ndarray:
     return out
 
 
-def ro_hash_batch_eval(field: int, tag: int, xs, len_: int, n: int, bits: int, out) -> None:
-    """vdf_nova_ro_hash_batch_eval: the host restatement of Context.ro_hash_batch -- n messages of len_ elements (message-major
-    Montgomery limbs) hashed into out[(n, 4) uint64]; bits = 0: the element, 1..255: the low bits of its canonical integer.  xs
-    and out: numpy arrays or None."""
+def ro_block_constants(field: int, ro: RoParams):
+    """vdf_nova_ro_block_constants: a family-1 block's constants of `field` as Context.ro_hash_batch_block reads them -- (rc, mds),
+    Montgomery limbs: rc ((full_rounds + partial_rounds) * width, 4) uint64, round-major and lane-minor; mds (width * width, 4),
+    row-major.  The default block is refused (ro_constants is its call)."""
+    counts = (_sz * 2)()
+    _check(nova_lib.vdf_nova_ro_block_constants(_ro_ptr(ro), field, None, None, counts))
+    rc, mds = np.zeros((counts[0], 4), dtype="<u8"), np.zeros((counts[1], 4), dtype="<u8")
+    _check(nova_lib.vdf_nova_ro_block_constants(_ro_ptr(ro), field, rc.ctypes.data, mds.ctypes.data, counts))
+    return rc, mds
+
+
+def ro_hash_batch_eval(field: int, tag: int, xs, len_: int, n: int, bits: int, out, ro: "RoParams | None" = None) -> None:
+    """vdf_nova_ro_hash_batch_eval_ro: the host restatement of Context.ro_hash_batch (ro = None, the default block) and of
+    Context.ro_hash_batch_block (another block) -- n messages of len_ elements (message-major Montgomery limbs) hashed into
+    out[(n, 4) uint64]; bits = 0: the element, 1..255: the low bits of its canonical integer.  xs and out: numpy arrays or None."""
     ptr = lambda a: None if a is None else a.ctypes.data
-    _check(nova_lib.vdf_nova_ro_hash_batch_eval(field, tag, ptr(xs), len_, n, bits, ptr(out)))
+    if ro is None:
+        _check(nova_lib.vdf_nova_ro_hash_batch_eval(field, tag, ptr(xs), len_, n, bits, ptr(out)))
+    else:
+        _check(nova_lib.vdf_nova_ro_hash_batch_eval_ro(_ro_ptr(ro), field, tag, ptr(xs), len_, n, bits, ptr(out)))
 
 
 def ro_hash(field: int, tag: int, xs: np.ndarray, ro: "RoParams | None" = None) -> np.ndarray:
@@ -1051,6 +1069,16 @@ class NovaVDFPublicParams:        # src/nova/proof.rs:38-43
     @property
     def verify_ro_device(self) -> int:
         return int(nova_lib.vdf_nova_pp_verify_ro_device(self.handle))
+
+    def set_verify_ro_block_device(self, min_count: int) -> None:
+        """vdf_nova_pp_set_verify_ro_block_device: the same choice for a set made under another RO block (family 1) -- from how many
+        entries on the per-entry hashes are made by vdf_ro_hash_batch_block; 0 (the default): on the host.  A separate switch: a
+        default-block set ignores it, and set_verify_ro_device keeps its meaning.  Verdicts do not depend on it."""
+        _check(nova_lib.vdf_nova_pp_set_verify_ro_block_device(self.handle, min_count))
+
+    @property
+    def verify_ro_block_device(self) -> int:
+        return int(nova_lib.vdf_nova_pp_verify_ro_block_device(self.handle))
 
     def verify_ro_stats(self) -> Tuple[int, int]:
         """(hashes made on the device, launches) since the set was made."""
